@@ -9,9 +9,11 @@ every step:
              typing of the consensuses against every allele = K2, het / hom call)
     CYP2D6   sp_cyp_diplotype (K3 regions -> multi-way consensus K8 -> K9 / K7 typing -> K4 weights -> chains -> K5 chain pair) on a context of its own,
              beside the HLA half on the same GPU (two host threads, two HIP streams + their helpers)
-Beside it in the same JSON line: `roofline` (k1_cells_kernel), `cpu_baseline` (the reference's call pattern on the minimap2
-restatement of the oracle, see tests/cpu_port_seeded.py), `legs` (HLA alone with resident reads = round 2's headline, the six CYP2D6 scenarios, the
-256-sample cohort on this one GPU, K5 at scale).
+A plain run sets up, warms up, times the steps, writes the last step's outputs if `--dump-outputs DIR` is given and prints the line, with what the timed
+steps' own counters tell (critical path, kernel and host times); `roofline` and `cpu_baseline` are null there.  `--full` adds what takes runs of its own:
+`roofline` (the consensus step kernel), `cpu_baseline` (the reference's call pattern on the minimap2 restatement of the oracle, see
+tests/cpu_port_seeded.py), `upload.alone`, `legs` (the headline in the other consensus mode, HLA alone with resident reads = round 2's headline, K1 both
+ways, other numbers of CYP2D6 lanes, the six CYP2D6 scenarios, the 256-sample cohort on this one GPU, K5 at scale) and, at N > 1, the second blocks.
 
 N > 1 (`--gpus N`, or under torch.distributed.run), one process per GPU: every rank runs the same stream of samples (its own samples) -- per-GPU work
 fixed, nothing exchanged, `value` = all ranks' reads / the slowest rank's time between the barriers (weak scaling by independent samples).
@@ -135,6 +137,59 @@ def emit(full, compact, path):
         sys.stderr.write(json.dumps(full) + "\n")
     print(text, flush=True)
 
+
+DUMP_LIMIT = 60_000_000    # bytes of all arrays --dump-outputs writes (64 MB with room for the files' headers); above it, every array keeps the same fixed, seeded share of its rows
+
+
+def _text_rows(texts):
+    """strings -> float32 [len(texts), longest] of their byte values, zero-padded"""
+    out = np.zeros((len(texts), max([1] + [len(t) for t in texts])), np.float32)
+    for k, t in enumerate(texts):
+        out[k, :len(t)] = np.frombuffer(t.encode(), np.uint8)
+    return out
+
+
+def _struct_rows(structs):
+    """ctypes structures -> float64 [len(structs), fields] of their scalar fields, in declaration order"""
+    names = [n for n, t in structs[0]._fields_ if not hasattr(t, "_length_")] if structs else []
+    return np.array([[float(getattr(s, n)) for n in names] for s in structs], np.float64).reshape(len(structs), len(names))
+
+
+def sample_outputs(final):
+    """what a caller of the headline's path receives for the last timed step, as float arrays: the HLA half's realignment records (sp_hla_realign per read),
+    calls (sp_hla_call per gene), consensus texts and consensus-1 flags per read; the CYP2D6 half's call (sp_cyp_call), its chains, haplotype texts, consensus
+    texts and their labels"""
+    from numpy.lib import recfunctions
+    o, calls, is1 = final["hla"]
+    call, cons, labels = final["cyp"]
+    n = call.n_consensus
+    return {"hla_realign": recfunctions.structured_to_unstructured(o, np.float64),
+            "hla_calls": _struct_rows([c for c, _c1, _c2 in calls]),
+            "hla_consensus": _text_rows([t for _c, c1, c2 in calls for t in (c1, c2)]),
+            "hla_is_consensus1": is1.astype(np.float32),
+            "cyp2d6_call": _struct_rows([call])[0],
+            "cyp2d6_chains": np.array([list(call.chain1), list(call.chain2)], np.float64),
+            "cyp2d6_haplotypes": _text_rows([getattr(call, f).decode() for f in ("hap1", "hap2", "core1", "core2", "deep1", "deep2")]),
+            "cyp2d6_consensus": _text_rows(cons),
+            "cyp2d6_consensus_type": np.array([t for t, _s in labels], np.float64).reshape(n),
+            "cyp2d6_consensus_subtype": _text_rows([s or "" for _t, s in labels])}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy in float32 / float64 (structured records as one float64 column per field), at most DUMP_LIMIT bytes in all"""
+    from numpy.lib import recfunctions
+    arrays = {k: (recfunctions.structured_to_unstructured(v, np.float64) if v.dtype.names else v) for k, v in arrays.items()}
+    arrays = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT:
+        share = DUMP_LIMIT / total
+        for k, v in arrays.items():
+            if v.ndim and len(v) > 1:
+                keep = np.sort(np.random.default_rng(0).choice(len(v), max(1, int(len(v) * share)), replace=False))
+                arrays[k] = v[keep]
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the ranks' group
@@ -653,8 +708,11 @@ def cohort_line(pkg, ctx, fx, db, cdb, locus, scen, world, rank, group, args, ba
     equal_shares = len(set(sizes)) == 1
     empty = np.zeros(0, shard.CALL_DTYPE)
 
+    last_tables = []                          # the gathered call records of the last pass (--dump-outputs)
+
     def one_pass(only_first=False):
         good_sum, n_tab = np.zeros(3, np.int64), 0
+        del last_tables[:]
         for q in range(1 if only_first else rounds):
             if q < len(shares):
                 table, good = shares[q].step(pkg, ctx, db, cdb, shard, group, rank, same_count=equal_shares)
@@ -662,6 +720,7 @@ def cohort_line(pkg, ctx, fx, db, cdb, locus, scen, world, rank, group, args, ba
             else:
                 table = shard.gather_calls(empty, group=group, same_count=False)
             n_tab += len(table)
+            last_tables.append(table)
         return good_sum, n_tab
     for _ in range(args.warmup):
         one_pass(only_first=True)
@@ -676,6 +735,7 @@ def cohort_line(pkg, ctx, fx, db, cdb, locus, scen, world, rank, group, args, ba
         ok += good; n_table += n_tab
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
+    outputs = {"cohort_call_records": np.concatenate(last_tables)} if last_tables else {}
     # what a rank's share costs by its size (one GPU): the share a rank holds at N = 8 / 4 / 2 of a 256-sample cohort, each in one pass after a warm-up pass
     by_share = None
     if world == 1 and (getattr(args, "cohort_shares", False) or os.environ.get("SP_BENCH_COHORT_SHARES")) and mine:
@@ -702,7 +762,7 @@ def cohort_line(pkg, ctx, fx, db, cdb, locus, scen, world, rank, group, args, ba
     reads_all, samples_all = int(totals[0]), int(totals[1])
     n_genes = len(fx.genes)
     return {"value": reads_all * args.steps / dt, "unit": "reads/s", "samples_per_s": samples_all * args.steps / dt, "ms_per_step": 1e3 * dt / args.steps,
-            "samples": samples_all, "reads_per_pass": reads_all, "by_share_size": by_share,
+            "samples": samples_all, "reads_per_pass": reads_all, "by_share_size": by_share, "outputs": outputs,
             "rank0_host_seconds_per_pass": {k: sum(sh.host_s.get(k, 0.0) for sh in shares) / max(1, args.steps) for k in ("upload", "hla", "cyp2d6", "loci_side_by_side", "variant_genes", "records_and_gather")}, "records_gathered_per_pass": n_table // max(1, args.steps),
             "calls_equal_truth": {"hla": f"{int(totals[2])}/{samples_all * n_genes * args.steps}", "cyp2d6": f"{int(totals[3])}/{samples_all * args.steps}",
                                   "variant_genes_truth_among_reported": f"{int(totals[4])}/{samples_all * len(panel.genes) * args.steps}"},
@@ -790,6 +850,9 @@ def main():
     ap.add_argument("--cpu-cyp-reads", type=int, default=1000, help="reads of every CYP2D6 scenario of the mix the CPU leg runs (0: all of them)")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the resident-HLA, CYP2D6-scenario, cohort and K5 legs")
     ap.add_argument("--full-out", default=os.path.join(ROOT, "bench_full.json"), help="where the whole record goes (legs, critical path, per-scenario CPU blocks); stdout carries ONE compact line")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: CPU baseline, roofline, upload alone, legs, the N > 1 second blocks "
+                                                         "(--no-cpu-baseline / --no-extra-legs leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -812,6 +875,8 @@ def main():
     scen = cr.scenarios(locus)
     # the steps cycle through ALL SIX configs[2] scenarios (*1/*2, *4/*4, *5/*1, *4+*68/*1, *10+*36/*10, *2x2/*1; round 4 alternated the first two, the cheap third of the config)
     cyp_samples = [CypSample(pkg, locus, scen[k], args.cyp_reads, 7 + k) for k in range(len(scen))] if workload == "sample" else []
+    if not args.full:
+        args.no_cpu_baseline = args.no_extra_legs = True    # (a plain run measures the headline only)
     cohort_in_own_process = cohort_leg_in_a_process_of_its_own(args.cohort_samples) if (world == 1 and workload == "sample" and not args.no_extra_legs) else None
     cb, cpu_ref = None, None
     if not args.no_cpu_baseline and world == 1 and workload == "sample":
@@ -859,6 +924,9 @@ def main():
 
     if workload == "cohort":
         line = cohort_line(pkg, ctx, fx, db, cdb, locus, scen, world, rank, group, args, barrier, max_over_ranks, (cfg, gene_def), device_index)
+        outputs = line.pop("outputs")
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
         blocks = {}
         if world > 1 and not args.no_extra_legs:
             # (a) the same cohort on ONE GPU (rank 0 alone, the others wait): what the N ranks' value is to be held against; (b) the ranks' independent streams of samples
@@ -926,12 +994,15 @@ def main():
         ctx_c.set_option("k8_persistent", int(forced))
     genes = list(range(len(fx.genes)))
     last = {}
+    final = {}                                              # what each locus returned in the last timed step, step steps - 1 (--dump-outputs)
 
     def hla_work(R, i):
         db_ = hla_dbs[hla_ctxs.index(R.ctx)]
         o = db_.realign_reads(R)
-        calls = db_.diplotype_genes(genes, R, o)[0]
+        calls, is1 = db_.diplotype_genes(genes, R, o)
         last["hla"] = (i, o, calls)
+        if i == args.steps - 1:
+            final["hla"] = (o, calls, is1)
         return calls
 
     cyp_log = []                                            # (step, scenario index, call strings, seconds of the library call) of every CYP2D6 call of the lanes
@@ -940,8 +1011,10 @@ def main():
         if headline_mode["persistent"] and os.environ.get("SP_BENCH_INJECT_FAILURE"):       # (a test of the fall-back below: profiles/scripts/r04_run67.sh)
             raise RuntimeError("injected failure of the persistent mode")
         t_ = time.perf_counter()
-        call, _cons, _labels = cyp_dbs[cyp_ctxs.index(R.ctx)].diplotype(R)
+        call, cons, labels = cyp_dbs[cyp_ctxs.index(R.ctx)].diplotype(R)
         last["cyp"] = (i, call)
+        if i == args.steps - 1:
+            final["cyp"] = (call, cons, labels)
         cyp_log.append((i, i % len(cyp_samples), call.hap1.decode(), call.hap2.decode(), time.perf_counter() - t_))
         return call
 
@@ -974,6 +1047,7 @@ def main():
             run_lanes(make_lanes(max(1, args.warmup)))
         ctx_h.profile_reset(); ctx_c.profile_reset()
         del cyp_log[:]
+        final.clear()
         lanes = make_lanes(args.steps)                      # (sample 0's bytes start travelling here: the pipeline is full when the clock starts)
         for x in lanes:
             x.wait_first()
@@ -992,6 +1066,8 @@ def main():
         sys.stderr.write("bench: persistent consensus kernels failed (%s): the headline runs with a launch pair per step\n" % e)
         ctx_c.set_option("k8_persistent", 0)
         lanes, dt = timed_region()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sample_outputs(final))
     reads_per_step = samples[0].n + cyp_samples[0].n        # (every scenario has the same number of reads)
     line_value = world * reads_per_step * args.steps / dt
     timed_cyp = list(cyp_log)
@@ -1054,17 +1130,18 @@ def main():
     cyp_ok = all(m["calls_equal_truth"] == m["steps"] for m in mix.values())
     k1_gene_ok = float(np.mean([k1_out[r]["gene"] == smp.wl.read_truth[r][0] for r in range(smp.n)]))
 
-    # the bytes' way alone: one synchronous upload of the HLA half in either form
+    # the bytes' way alone (--full): one synchronous upload of the HLA half in either form
     t_up = {}
-    for name, fmt, payload in (("bam4", pkg.ffi.SP_SEQ_BAM4, samples[0].payload), ("ascii", pkg.ffi.SP_SEQ_ASCII, pkg.ffi._concat(samples[0].wl.reads) + (None,))):
-        best = None
-        for _ in range(3):
-            t1 = time.perf_counter()
-            S = ctx.upload_format(fmt, payload[0], payload[1], payload[2])
-            d = time.perf_counter() - t1
-            S.close()
-            best = d if best is None or d < best else best
-        t_up[name] = {"seconds": best, "bytes": int(len(payload[0])), "GBps": len(payload[0]) / best / 1e9, "bases_per_s": samples[0].ascii_bytes / best}
+    if args.full:
+        for name, fmt, payload in (("bam4", pkg.ffi.SP_SEQ_BAM4, samples[0].payload), ("ascii", pkg.ffi.SP_SEQ_ASCII, pkg.ffi._concat(samples[0].wl.reads) + (None,))):
+            best = None
+            for _ in range(3):
+                t1 = time.perf_counter()
+                S = ctx.upload_format(fmt, payload[0], payload[1], payload[2])
+                d = time.perf_counter() - t1
+                S.close()
+                best = d if best is None or d < best else best
+            t_up[name] = {"seconds": best, "bytes": int(len(payload[0])), "GBps": len(payload[0]) / best / 1e9, "bases_per_s": samples[0].ascii_bytes / best}
 
     legs = {}
     other_leg = "headline_with_launch_pairs" if headline_mode["persistent"] else "headline_with_persistent_consensus"
@@ -1160,54 +1237,57 @@ def main():
         legs["k5_chain_pairs"] = chain_pair_leg(pkg, ctx)
         legs["cohort"] = cohort_in_own_process             # (measured before this process touched the GPU: cohort_leg_in_a_process_of_its_own)
 
-    peaks = {"valu_int_wave_instr_per_s": ctx.microbench("valu_int"), "match16_valu_wave_instr_per_s": ctx.microbench("match16"),
-             "hbm_copy_bytes_per_s": ctx.microbench("hbm_copy")}
-    # The dominant kernel of the step since round 5 is the consensus step kernel of the CYP2D6 context (K8: cons_step_persist_kernel<8>, cons_step_kernel<8> as launch pairs;
-    # 55 % of the kernel time of profiles/r05/rocprof_r05_kernel_stats.csv with its control kernel).  Its time per step is measured live -- the chain between HIP events on the
-    # library's stream (cons_steps) and, inside it, the step body by the device clock the kernels stamp (critical_path) --; its instruction and HBM byte counts per bench step come
-    # from the committed rocprofv3 PMC passes of this workload (profiles/r05/counters_cons_step.json), quoted only while the kernel's source is the one they were made on
-    import hashlib
-    cons_sha = hashlib.sha256(open(os.path.join(ROOT, "pb-starphase_amd", "csrc", "sp_consensus.hip"), "rb").read()).hexdigest()[:16]
-    stale, pmc = [], None
-    cfile = os.path.join(COUNTER_DIR, "counters_cons_step.json")
-    if os.path.exists(cfile):
-        rec = json.load(open(cfile))
-        if rec.get("cons_source_sha16") == cons_sha and args.cyp_reads == 2000:
-            pmc = rec
-        else:
-            stale.append("counters_cons_step.json")
-    cp = crit["cyp2d6"]
-    step_ms, chain_ms, dep_steps = cp["step_kernel_ms"], cp["chain_ms"], cp["dependent_steps"]
-    batches = batches_per_step if batches_per_step > 0 else None
-    cyp_packed_bytes = float(np.mean([c.ascii_bytes for c in cyp_samples])) / 4.0
-    # SURVEY 8(d)'s streaming model for the consensus: every search level reads the packed bases of its reads once and writes one 32-byte record per read
-    searches = batches if batches else 3.0                  # (a batch = the searches of one level of the multi-way consensus, all open groups in lockstep)
-    algo_bytes = searches * (cyp_packed_bytes + 32.0 * cyp_samples[0].n)
-    achieved = (pmc["sq_insts_valu_per_bench_step"] / (step_ms * 1e-3)) if (pmc and step_ms > 0) else None
-    # `peak` is the NOMINAL VALU issue rate (256 CUs x 4 SIMDs x one wave-instruction per 2 cycles at 2.4 GHz = 1,229 G wave-instr/s, MI355X_MICROARCH.md); the measured rate of
-    # sp_microbench's integer loop (`measured_peak`) is beside it
-    roof = {"bound": "valu", "kernel": "cons_step_wide_kernel<8> / cons_step_kernel<8> (one body at 2 / 4 waves per SIMD: batches of up to 320 / more workgroups)" +
-                                       ("" if batches_per_step == 0 else "; %.1f batches per step ran as cons_step_persist_kernel<8>, the library's choice" % batches_per_step),
-            "kernel_short": "cons_step_wide_kernel<8> (K8 consensus step)" if batches_per_step == 0 else "cons_step_persist_kernel<8> (K8 consensus step)",
-            "achieved": achieved, "peak": VALU_PEAK_WAVE_INSTR, "unit": "wave-instr/s",
-            "frac": (achieved / VALU_PEAK_WAVE_INSTR) if achieved else None,
-            "measured_peak": peaks["valu_int_wave_instr_per_s"], "frac_of_measured_peak": (achieved / peaks["valu_int_wave_instr_per_s"]) if achieved else None,
-            "avg_launch_us": _r(1e3 * step_ms / dep_steps, 4) if dep_steps > 0 else None, "avg_launch_us_rocprof": (pmc or {}).get("rocprof_avg_launch_us"),
-            "traffic": pmc["hbm_bytes_per_bench_step"] if pmc else None,
-            # (PMC passes: the waves resident on average while a step launch is active / the wave slots of the device at the kernel's register budget, and the share of a
-            #  resident wave's cycles in which it issues anything -- a launch lasts as long as its slowest wave, most of its waves are done in a sixth of that)
-            "occupancy": (pmc or {}).get("occupancy"),
-            "per": "bench step (the consensus searches of one 2,000-read CYP2D6 sample: %.0f dependent window / expansion steps%s)" % (dep_steps, "" if batches is None else ", %.1f persistent launches" % batches),
-            "step_kernel_ms_per_step": step_ms, "chain_ms_per_step_hip_events": chain_ms, "nominal_peak": VALU_PEAK_WAVE_INSTR,
-            "sq_insts_valu_per_step": pmc["sq_insts_valu_per_bench_step"] if pmc else None, "sq_insts_salu_per_step": pmc["sq_insts_salu_per_bench_step"] if pmc else None,
-            "sq_insts_lds_per_step": pmc["sq_insts_lds_per_bench_step"] if pmc else None,
-            "hbm": {"algorithmic_bytes_per_step": algo_bytes, "achieved_GBs": algo_bytes / (step_ms * 1e-3) / 1e9 if step_ms > 0 else None, "peak_GBs": HBM_PEAK_GBS,
-                    "frac": algo_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if step_ms > 0 else None, "measured_hbm_copy_GBs": peaks["hbm_copy_bytes_per_s"] / 1e9,
-                    "note": "SURVEY 8(d)'s streaming model applied to the consensus: every search reads its reads' packed bases once and writes a 32-byte record per read"},
-            "counters_from": ("profiles/r06/counters_cons_step.json: " + pmc["method"]) if pmc else "no counter file for this kernel source (profiles/run_rocprof.sh makes it)",
-            "note": "the step's dominant kernel is a LATENCY chain, not a throughput kernel: a sample's searches are a few hundred dependent steps (critical_path), each the slowest "
-                    "wavefront of a launch that fills a fraction of the device -- the fraction of the VALU peak (and of HBM: the reads are 3 MB) says how little of the machine one "
-                    "sample's chain can use; what bounds it is per-step latency (critical_path.cyp2d6.per_step_us) and the number of steps"}
+    # the roofline block (--full): the device's peaks by microbenchmark, the committed counters of the step's dominant kernel
+    roof, stale = None, []
+    if args.full:
+        peaks = {"valu_int_wave_instr_per_s": ctx.microbench("valu_int"), "match16_valu_wave_instr_per_s": ctx.microbench("match16"),
+                 "hbm_copy_bytes_per_s": ctx.microbench("hbm_copy")}
+        # The dominant kernel of the step since round 5 is the consensus step kernel of the CYP2D6 context (K8: cons_step_persist_kernel<8>, cons_step_kernel<8> as launch pairs;
+        # 55 % of the kernel time of profiles/r05/rocprof_r05_kernel_stats.csv with its control kernel).  Its time per step is measured live -- the chain between HIP events on the
+        # library's stream (cons_steps) and, inside it, the step body by the device clock the kernels stamp (critical_path) --; its instruction and HBM byte counts per bench step come
+        # from the committed rocprofv3 PMC passes of this workload (profiles/r05/counters_cons_step.json), quoted only while the kernel's source is the one they were made on
+        import hashlib
+        cons_sha = hashlib.sha256(open(os.path.join(ROOT, "pb-starphase_amd", "csrc", "sp_consensus.hip"), "rb").read()).hexdigest()[:16]
+        stale, pmc = [], None
+        cfile = os.path.join(COUNTER_DIR, "counters_cons_step.json")
+        if os.path.exists(cfile):
+            rec = json.load(open(cfile))
+            if rec.get("cons_source_sha16") == cons_sha and args.cyp_reads == 2000:
+                pmc = rec
+            else:
+                stale.append("counters_cons_step.json")
+        cp = crit["cyp2d6"]
+        step_ms, chain_ms, dep_steps = cp["step_kernel_ms"], cp["chain_ms"], cp["dependent_steps"]
+        batches = batches_per_step if batches_per_step > 0 else None
+        cyp_packed_bytes = float(np.mean([c.ascii_bytes for c in cyp_samples])) / 4.0
+        # SURVEY 8(d)'s streaming model for the consensus: every search level reads the packed bases of its reads once and writes one 32-byte record per read
+        searches = batches if batches else 3.0                  # (a batch = the searches of one level of the multi-way consensus, all open groups in lockstep)
+        algo_bytes = searches * (cyp_packed_bytes + 32.0 * cyp_samples[0].n)
+        achieved = (pmc["sq_insts_valu_per_bench_step"] / (step_ms * 1e-3)) if (pmc and step_ms > 0) else None
+        # `peak` is the NOMINAL VALU issue rate (256 CUs x 4 SIMDs x one wave-instruction per 2 cycles at 2.4 GHz = 1,229 G wave-instr/s, MI355X_MICROARCH.md); the measured rate of
+        # sp_microbench's integer loop (`measured_peak`) is beside it
+        roof = {"bound": "valu", "kernel": "cons_step_wide_kernel<8> / cons_step_kernel<8> (one body at 2 / 4 waves per SIMD: batches of up to 320 / more workgroups)" +
+                                           ("" if batches_per_step == 0 else "; %.1f batches per step ran as cons_step_persist_kernel<8>, the library's choice" % batches_per_step),
+                "kernel_short": "cons_step_wide_kernel<8> (K8 consensus step)" if batches_per_step == 0 else "cons_step_persist_kernel<8> (K8 consensus step)",
+                "achieved": achieved, "peak": VALU_PEAK_WAVE_INSTR, "unit": "wave-instr/s",
+                "frac": (achieved / VALU_PEAK_WAVE_INSTR) if achieved else None,
+                "measured_peak": peaks["valu_int_wave_instr_per_s"], "frac_of_measured_peak": (achieved / peaks["valu_int_wave_instr_per_s"]) if achieved else None,
+                "avg_launch_us": _r(1e3 * step_ms / dep_steps, 4) if dep_steps > 0 else None, "avg_launch_us_rocprof": (pmc or {}).get("rocprof_avg_launch_us"),
+                "traffic": pmc["hbm_bytes_per_bench_step"] if pmc else None,
+                # (PMC passes: the waves resident on average while a step launch is active / the wave slots of the device at the kernel's register budget, and the share of a
+                #  resident wave's cycles in which it issues anything -- a launch lasts as long as its slowest wave, most of its waves are done in a sixth of that)
+                "occupancy": (pmc or {}).get("occupancy"),
+                "per": "bench step (the consensus searches of one 2,000-read CYP2D6 sample: %.0f dependent window / expansion steps%s)" % (dep_steps, "" if batches is None else ", %.1f persistent launches" % batches),
+                "step_kernel_ms_per_step": step_ms, "chain_ms_per_step_hip_events": chain_ms, "nominal_peak": VALU_PEAK_WAVE_INSTR,
+                "sq_insts_valu_per_step": pmc["sq_insts_valu_per_bench_step"] if pmc else None, "sq_insts_salu_per_step": pmc["sq_insts_salu_per_bench_step"] if pmc else None,
+                "sq_insts_lds_per_step": pmc["sq_insts_lds_per_bench_step"] if pmc else None,
+                "hbm": {"algorithmic_bytes_per_step": algo_bytes, "achieved_GBs": algo_bytes / (step_ms * 1e-3) / 1e9 if step_ms > 0 else None, "peak_GBs": HBM_PEAK_GBS,
+                        "frac": algo_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if step_ms > 0 else None, "measured_hbm_copy_GBs": peaks["hbm_copy_bytes_per_s"] / 1e9,
+                        "note": "SURVEY 8(d)'s streaming model applied to the consensus: every search reads its reads' packed bases once and writes a 32-byte record per read"},
+                "counters_from": ("profiles/r06/counters_cons_step.json: " + pmc["method"]) if pmc else "no counter file for this kernel source (profiles/run_rocprof.sh makes it)",
+                "note": "the step's dominant kernel is a LATENCY chain, not a throughput kernel: a sample's searches are a few hundred dependent steps (critical_path), each the slowest "
+                        "wavefront of a launch that fills a fraction of the device -- the fraction of the VALU peak (and of HBM: the reads are 3 MB) says how little of the machine one "
+                        "sample's chain can use; what bounds it is per-step latency (critical_path.cyp2d6.per_step_us) and the number of steps"}
     line = {
         "metric": "HiFi reads/sec diplotyped (HLA+CYP2D6)",
         "value": world * reads_per_step * args.steps / dt, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1233,8 +1313,8 @@ def main():
         "consensus_hla": cons,
         "concordance": {"hla_diplotypes_equal_truth": f"{ok}/{len(genes)} genes", "cyp2d6_call_equals_truth": bool(cyp_ok), "k1_gene_correct": k1_gene_ok,
                         "cyp2d6_call": [cyp_call.hap1.decode(), cyp_call.hap2.decode()]},
-        "upload": {"per_step_bytes": int(len(samples[0].payload[0]) + len(cyp_samples[0].payload[0])), "alone": t_up,
-                   "note": "inside `value` every step uploads a new sample (4-bit SEQ bytes, sp_seqset_upload_async); `alone` = one synchronous upload of the HLA half"},
+        "upload": {"per_step_bytes": int(len(samples[0].payload[0]) + len(cyp_samples[0].payload[0])), "alone": t_up or None,
+                   "note": "inside `value` every step uploads a new sample (4-bit SEQ bytes, sp_seqset_upload_async); `alone` (--full) = one synchronous upload of the HLA half"},
         "legs": legs or None,
         "context": dict(ctx.info(), legs_k8_persistent=cyp_persistent()),          # sp_ctx_get_info: the hardware queues the streams of the run were mapped onto (this script exports GPU_MAX_HW_QUEUES=16 before torch initialises HIP)
     }
@@ -1302,7 +1382,7 @@ def main():
                                "mean_resident_waves_over_slots": _r((rf.get("occupancy") or {}).get("mean_resident_over_slots")),
                                "hbm": {"algorithmic_bytes_per_step": _r(rf["hbm"]["algorithmic_bytes_per_step"]), "achieved_GBs": _r(rf["hbm"]["achieved_GBs"]), "peak_GBs": HBM_PEAK_GBS,
                                        "frac": _r(rf["hbm"]["frac"])},
-                               "counters_from": ("profiles/%s/counters_cons_step.json" % os.path.basename(COUNTER_DIR)) if rf["traffic"] is not None else None}
+                               "counters_from": ("profiles/%s/counters_cons_step.json" % os.path.basename(COUNTER_DIR)) if rf["traffic"] is not None else None} if rf is not None else None
         cbf = line["cpu_baseline"]
         if cbf is not None:
             compact["cpu_baseline"] = {"value": _r(cbf["value"]), "unit": cbf["unit"], "cores": cbf["cores"], "kind": cbf["kind"], "sample": cbf["sample_short"],

@@ -7,7 +7,7 @@ cd /tmp/consvar
 for defs in "$@"; do
     (cd pb-starphase_amd/csrc && rm -f sp_consensus.o && /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off $defs -c sp_consensus.hip -o sp_consensus.o 2>/dev/null && make -s 2>/dev/null)
     echo "== [$defs]"
-    python bench.py --no-cpu-baseline 2>/tmp/consvar_err.txt | tail -1 | python -c "
+    python bench.py --full --no-cpu-baseline 2>/tmp/consvar_err.txt | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 c=d['critical_path']['cyp2d6']

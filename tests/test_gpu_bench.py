@@ -41,7 +41,7 @@ def run_bench(extra, env=None, tmp=None):
 def test_sample_line_and_two_rank_cohort_over_gloo():
     """N = 1: one sample with both loci, a new upload every step.  N = 2: the cohort sharded by sample (two ranks sharing device 0, the gather over
     gloo: RCCL refuses two ranks on one device; the RCCL gather of one rank runs in tests/test_gpu_upload.py)."""
-    one = run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "2000", "--cyp-reads", "400", "--no-cpu-baseline", "--no-extra-legs"])
+    one = run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "2000", "--cyp-reads", "400", "--full", "--no-cpu-baseline", "--no-extra-legs"])
     assert one["n_gpus"] == 1 and one["steps"] == 2 and one["warmup"] == 1 and one["scaling"] == "weak"
     assert one["metric"] == "HiFi reads/sec diplotyped (HLA+CYP2D6)" and one["unit"] == "reads/s" and one["higher_is_better"] is True
     assert one["value"] > 0 and one["ms_per_step"] > 0 and one["vs_baseline"] is None
@@ -52,7 +52,7 @@ def test_sample_line_and_two_rank_cohort_over_gloo():
     assert one["concordance"]["hla_diplotypes_equal_truth"] == "2/2 genes" and one["concordance"]["cyp2d6_call_equals_truth"] is True
     assert one["upload"]["per_step_bytes"] > 5_000_000 and one["upload"]["alone"]["bam4"]["GBps"] > 0
     for n in (1, 2):
-        line = run_bench(["--gpus", str(n), "--steps", "1", "--warmup", "1", "--cohort-samples", "8", "--reads", "1500", "--cyp-reads", "300"] + (["--workload", "cohort"] if n == 1 else []),
+        line = run_bench(["--gpus", str(n), "--steps", "1", "--warmup", "1", "--cohort-samples", "8", "--reads", "1500", "--cyp-reads", "300", "--full"] + (["--workload", "cohort"] if n == 1 else []),
                          env={"SP_BENCH_BACKEND": "gloo"})              # (N > 1: the cohort is the default workload)
         assert line["n_gpus"] == n and line["scaling"] == "strong" and line["metric"] == one["metric"] and line["value"] > 0
         c = line["cohort"]
@@ -123,10 +123,38 @@ def test_two_ranks_each_with_its_own_stream_of_samples():
 
 def test_the_headline_falls_back_to_launch_pairs_when_the_persistent_mode_fails():
     """The headline's CYP2D6 context runs its consensus as persistent kernels; if the library reports that a batch's kernels could not run side by side (its time-out, an
-    error) the bench starts the region over with a launch pair per step and says so in the line.  The failure is injected here (SP_BENCH_INJECT_FAILURE)."""
+    error) the bench starts the region over with a launch pair per step and says so in the line.  The failure is injected here (SP_BENCH_INJECT_FAILURE).
+    The library's own choice is persistent kernels only when the process's streams have hardware queues of their own (GPU_MAX_HW_QUEUES >= 16, what bench.py
+    sets when the host has not): the runs get that value whatever the host exports."""
+    queues = {"GPU_MAX_HW_QUEUES": "16"}
     line = run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "1500", "--cyp-reads", "300", "--no-cpu-baseline", "--no-extra-legs"],
-                     env={"SP_BENCH_INJECT_FAILURE": "1"})
+                     env=dict(queues, SP_BENCH_INJECT_FAILURE="1"))
     assert line["config"]["cyp2d6_consensus"].startswith("a launch pair per step (the persistent kernels failed here: injected failure")
     assert line["value"] > 0 and line["concordance"]["cyp2d6_call_equals_truth"] is True and line["concordance"]["hla_diplotypes_equal_truth"] == "2/2 genes"
-    ok = run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "1500", "--cyp-reads", "300", "--no-cpu-baseline", "--no-extra-legs"])
+    ok = run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "1500", "--cyp-reads", "300", "--no-cpu-baseline", "--no-extra-legs"], env=queues)
     assert ok["config"]["cyp2d6_consensus"].startswith("persistent kernels") and ok["critical_path"]["cyp2d6"]["launches_per_step"] == 0
+
+
+def test_a_plain_run_times_the_headline_only_and_dumps_its_last_step():
+    """without --full the line carries the headline and what its own steps counted, and none of the blocks that take runs of their own; --dump-outputs writes the
+    last timed step's outputs as float arrays, the same in two runs with the same arguments"""
+    import numpy as np
+    import tempfile
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--reads", "1500", "--cyp-reads", "300"]
+    with tempfile.TemporaryDirectory() as d:
+        runs = []
+        for k in range(2):
+            out = os.path.join(d, str(k))
+            line = run_bench(args + ["--dump-outputs", out])
+            assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0
+            assert line["roofline"] is None and line["cpu_baseline"] is None and not line["legs"] and line["upload"]["alone"] is None
+            assert line["_line"]["roofline"] is None and line["_line"]["cpu_baseline"] is None
+            assert line["concordance"]["hla_diplotypes_equal_truth"] == "2/2 genes" and line["concordance"]["cyp2d6_call_equals_truth"] is True
+            runs.append({f[:-4]: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out))})
+            assert sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out)) < 64_000_000
+        a, b = runs
+        assert {"hla_realign", "hla_calls", "hla_consensus", "hla_is_consensus1", "cyp2d6_call", "cyp2d6_chains", "cyp2d6_haplotypes", "cyp2d6_consensus"} <= set(a)
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+        assert a["hla_realign"].shape[0] == line["config"]["hla_reads"] and a["hla_calls"].shape[0] == 2
+        assert a["cyp2d6_consensus"].shape[0] == a["cyp2d6_call"][1] > 0                      # (sp_cyp_call.n_consensus)
+        assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)
