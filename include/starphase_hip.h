@@ -267,7 +267,8 @@ typedef struct {
      * (no best allele).  Exhaustive mode: a report beside the counts above, which decide; left zero with context option "mm2_rescore" 0.
      * Seeded mode: these ARE the numbers the acceptance loop ran on (<= 0.03 edit fraction, <= 0.5 penalised: mm2_nm over the re-scored extent) and they are written whatever
      * "mm2_rescore" says; nm / unmapped / aln above stay the unit-cost cell's numbers of the same mapping, so a record judged by nm / target_len alone may look as if it
-     * missed or passed a cut-off it did not.  status 2 in seeded mode: best_allele is -1 and mm2_* describe the reverse-strand mapping that was accepted. */
+     * missed or passed a cut-off it did not.  status 2 in seeded mode: best_allele is -1 and mm2_* are 0; sp_hla_realign_seeded_audit hands out the reverse-strand mapping that was accepted
+     * (its allele, t_len, nm and spans). */
     int32_t mm2_score, mm2_nm;
     int32_t mm2_t_start, mm2_t_end, mm2_q_start, mm2_q_end;
     int32_t k1_chains, k1_mappings, k1_chain_score;      /* seeded mode: chains of the read, mappings returned, chain score of the accepted mapping */
@@ -519,6 +520,15 @@ int32_t sp_cyp_diplotype_detailed(sp_ctx* ctx, const sp_cyp_problem* problem, co
                                   char* consensus, uint32_t cons_cap, sp_cyp_region_variants* region_variants /* optional */);
 int32_t sp_cyp_alleles_json(const sp_cyp_problem* problem, const sp_cyp_call* call, const sp_cyp_region_variants* region_variants,
                             char* out, uint64_t cap, uint64_t* needed);
+/* The same call, also handing out the read assignments behind PgxGeneDetails::multi_mapping_details (src/cyp2d6/caller.rs:434-565): for every read
+ * (in the order of `reads` = QNAME order) whose chain set is exactly one chain after the chains with a consensus nothing maps to uniquely were
+ * removed, one record per element of that chain, paired in order with the read's regions of interest (Rust's zip: the shorter list ends it) --
+ * the region's read range [read_start, read_end), the consensus index and its index_label ("<index>_<full allele>", the label before
+ * mark_false_allele, as the reference reads it).  mappings: cap records; *n_mappings = the number there are (SP_ERR_CAPACITY when more than
+ * cap: the call itself is complete, call again with more room for the list).  No records when call->status is not 0. */
+typedef struct { uint32_t read, consensus; uint64_t read_start, read_end; char index_label[64]; } sp_cyp_read_mapping;
+int32_t sp_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* problem, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
+                                  sp_cyp_region_variants* region_variants /* optional */, sp_cyp_read_mapping* mappings, uint64_t cap, uint64_t* n_mappings);
 
 /* ------------------------------------------------------------------ CYP2D6 templates and typing tables
  * Replaces generate_cyp_hybrids (src/cyp2d6/definitions.rs:346-464), LoadedVariants::load_variant_database
@@ -1093,6 +1103,61 @@ void    sp_fasta_free(sp_fasta* fasta);
 const char* sp_fasta_last_error(const sp_fasta* fasta);
 int32_t sp_fasta_sequences(sp_fasta* fasta, uint32_t* n, const char* const** names, const uint64_t** lengths);
 int32_t sp_fasta_fetch(sp_fasta* fasta, const char* chrom, uint64_t start, uint64_t end, const char** bases, uint64_t* len);
+
+/* ------------------------------------------------------------------ files to files: the whole `diplotype` run
+ * call_diplotypes (src/diplotyper.rs:40-330) behind one handle: the database, the reference FASTA and the per-database tables (HLA database,
+ * CYP2D6 templates and typing tables, every variant gene normalised) are made once by sp_starphase_create; sp_starphase_call then types one sample
+ * from its files -- variant genes from the VCF (+ SV VCF) in one sp_variant_solve_batch, the HLA genes of hla_config from the BAMs (K1 / K8 / K2,
+ * PgxMappingDetails of every read), CYP2D6 from the BAMs (K3 / K8 / K9 / K7 / K4 / K5) -- and returns an sp_result for sp_result_save /
+ * sp_result_save_pharmcat_tsv.  The CYP2D6 locus runs on a second context of the handle (same device), on a host thread of its own, beside the
+ * variant genes and the HLA genes of the main context; `sequential` = 1 runs the three one after another on the calling thread.  The output does not
+ * depend on which: every gene's entry is made from its own inputs alone.
+ *
+ * sp_diplotype_settings: DiplotypeSettings (src/cli/diplotype.rs:14-196) minus the inputs of one sample; sp_diplotype_settings_default fills the
+ * reference's default_values (max_sv_length 1,000,000, max_error_rate 0.07, min_cdf_prob 0.001, expected_maf 0.45, min_consensus_fraction 0.10,
+ * min_consensus_count 3, dual_max_ed_delta 100, every switch off, every path NULL).  include_set / exclude_set: files of gene names, one per line
+ * (load_file_lines); sample_name NULL = the first sample of the VCF; sv_vcf: the SV VCF of every sample unless sp_sample_inputs names one.
+ * debug_folder: hla_debug.json (per gene: the consensus matches and DualPassingStats) and cyp2d6_alleles.json are written there, nothing else.
+ * sp_diplotype_settings_check is check_diplotype_settings (:200-330) without the file-existence checks (a host does those; the command line exits
+ * with NOINPUT): SP_ERR_INVALID_ARG with the reference's message in err ("Must provide a VCF file and/or aligned BAM file to perform diplotyping.",
+ * "Only one of --exclude-set and --include-set can be specified.", "--max-error-rate must be between 0.0 and 1.0", ...); with BAMs and
+ * disable_cdna_scoring it sets hla_require_dna as the reference does. */
+typedef struct {
+    const char* include_set; const char* exclude_set;   /* --include-set / --exclude-set (at most one) */
+    const char* sample_name;                            /* --sample-name */
+    const char* sv_vcf;                                 /* --sv-vcf */
+    const char* debug_folder;                           /* --output-debug */
+    uint64_t max_sv_length;                             /* --max-sv-length */
+    int32_t  disable_cdna_scoring, hla_require_dna;     /* --disable-cdna-scoring, --hla-require-dna */
+    double   max_error_rate, min_cdf_prob, expected_maf;/* --max-error-rate, --min-cdf-prob, --expected-maf */
+    int32_t  infer_connections, normalize_d6_only;      /* --infer-connections, --normalize-d6-only */
+    double   min_consensus_fraction;                    /* --min-consensus-fraction */
+    uint64_t min_consensus_count, dual_max_ed_delta;    /* --min-consensus-count, --dual-max-ed-delta */
+    int32_t  debug_skip_hla;                            /* --debug-skip-hla */
+    int32_t  sequential;                                /* 1: variant genes, HLA, CYP2D6 one after another on the calling thread */
+} sp_diplotype_settings;
+typedef struct {
+    uint32_t n_bams; const char* const* bams;           /* --bam, in the order given */
+    const char* vcf;                                    /* --vcf or NULL */
+    const char* sv_vcf;                                 /* NULL: settings.sv_vcf */
+    const char* sample_name;                            /* NULL: settings.sample_name */
+} sp_sample_inputs;
+void    sp_diplotype_settings_default(sp_diplotype_settings* out);
+int32_t sp_diplotype_settings_check(sp_diplotype_settings* settings, const sp_sample_inputs* inputs, char* err, uint32_t err_cap);
+/* ctx: the context to run on, or NULL for one of the handle's own on device 0 (no device: SP_ERR_NO_DEVICE).  reference_fasta may be NULL (variant
+ * genes are then normalised without a genome and a sample with BAMs fails: "Reference genome is required for reading alignment files").
+ * The settings and their strings are copied.  A failed create returns no handle; sp_starphase_last_error(NULL) then gives the reason (per thread). */
+typedef struct sp_starphase sp_starphase;
+int32_t sp_starphase_create(sp_ctx* ctx, const char* database_path, const char* reference_fasta, const sp_diplotype_settings* settings, sp_starphase** out);
+void    sp_starphase_free(sp_starphase* handle);
+const char* sp_starphase_last_error(const sp_starphase* handle);
+/* one sample: *out is a new sp_result (sp_result_free).  Errors as the reference's: a region fetch that fails counts as no reads (the warning is kept:
+ * sp_starphase_warnings), an expected CYP2D6 CallerError gives the NO_MATCH entry, anything else fails the call (DATAERR on the command line). */
+int32_t sp_starphase_call(sp_starphase* handle, const sp_sample_inputs* inputs, sp_result** out);
+const char* sp_starphase_warnings(const sp_starphase* handle);      /* the warnings of the last call, one per line */
+/* where the last call spent its time (wall ms): whole call, BAM decode (host, both loci), variant genes, HLA lane, CYP2D6 lane */
+typedef struct { double call_ms, bam_decode_ms, variant_ms, hla_ms, cyp_ms; uint32_t n_hla_reads, n_cyp_reads; } sp_starphase_timing;
+int32_t sp_starphase_last_timing(const sp_starphase* handle, sp_starphase_timing* out);
 
 #ifdef __cplusplus
 }

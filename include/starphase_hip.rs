@@ -265,6 +265,14 @@ pub struct sp_cyp_region_variants {
     pub state: *mut u8,
 }
 #[repr(C)]
+pub struct sp_cyp_read_mapping {
+    pub read: u32,
+    pub consensus: u32,
+    pub read_start: u64,
+    pub read_end: u64,
+    pub index_label: [c_char; 64],
+}
+#[repr(C)]
 pub struct sp_cyp_locus {
     pub chrom_name: *const c_char,
     pub chrom_seq: *const c_char,
@@ -580,6 +588,45 @@ pub struct sp_bam_read {
     pub n_cigar: u32,
     pub cigar: *const u32,
 }
+#[repr(C)]
+pub struct sp_diplotype_settings {
+    pub include_set: *const c_char,
+    pub exclude_set: *const c_char,
+    pub sample_name: *const c_char,
+    pub sv_vcf: *const c_char,
+    pub debug_folder: *const c_char,
+    pub max_sv_length: u64,
+    pub disable_cdna_scoring: i32,
+    pub hla_require_dna: i32,
+    pub max_error_rate: f64,
+    pub min_cdf_prob: f64,
+    pub expected_maf: f64,
+    pub infer_connections: i32,
+    pub normalize_d6_only: i32,
+    pub min_consensus_fraction: f64,
+    pub min_consensus_count: u64,
+    pub dual_max_ed_delta: u64,
+    pub debug_skip_hla: i32,
+    pub sequential: i32,
+}
+#[repr(C)]
+pub struct sp_sample_inputs {
+    pub n_bams: u32,
+    pub bams: *const *const c_char,
+    pub vcf: *const c_char,
+    pub sv_vcf: *const c_char,
+    pub sample_name: *const c_char,
+}
+#[repr(C)]
+pub struct sp_starphase_timing {
+    pub call_ms: f64,
+    pub bam_decode_ms: f64,
+    pub variant_ms: f64,
+    pub hla_ms: f64,
+    pub cyp_ms: f64,
+    pub n_hla_reads: u32,
+    pub n_cyp_reads: u32,
+}
 
 #[repr(C)] pub struct sp_bam { _private: [u8; 0] }
 #[repr(C)] pub struct sp_ctx { _private: [u8; 0] }
@@ -592,6 +639,7 @@ pub struct sp_bam_read {
 #[repr(C)] pub struct sp_hla_debug { _private: [u8; 0] }
 #[repr(C)] pub struct sp_result { _private: [u8; 0] }
 #[repr(C)] pub struct sp_seqset { _private: [u8; 0] }
+#[repr(C)] pub struct sp_starphase { _private: [u8; 0] }
 #[repr(C)] pub struct sp_variant_gene { _private: [u8; 0] }
 #[repr(C)] pub struct sp_vcf { _private: [u8; 0] }
 
@@ -637,6 +685,7 @@ extern "C" {
     pub fn sp_cyp_diplotype_cohort(ctx: *mut sp_ctx, problem: *const sp_cyp_problem, n_samples: u32, reads: *const *const sp_seqset, calls: *mut sp_cyp_call, consensus: *mut c_char, cons_cap: u32, sample_rc: *mut i32) -> i32;
     pub fn sp_cyp_diplotype_detailed(ctx: *mut sp_ctx, problem: *const sp_cyp_problem, reads: *const sp_seqset, call: *mut sp_cyp_call, consensus: *mut c_char, cons_cap: u32, region_variants: *mut sp_cyp_region_variants) -> i32;
     pub fn sp_cyp_alleles_json(problem: *const sp_cyp_problem, call: *const sp_cyp_call, region_variants: *const sp_cyp_region_variants, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
+    pub fn sp_cyp_diplotype_mappings(ctx: *mut sp_ctx, problem: *const sp_cyp_problem, reads: *const sp_seqset, call: *mut sp_cyp_call, consensus: *mut c_char, cons_cap: u32, region_variants: *mut sp_cyp_region_variants, mappings: *mut sp_cyp_read_mapping, cap: u64, n_mappings: *mut u64) -> i32;
     pub fn sp_cyp_db_create(ctx: *mut sp_ctx, locus: *const sp_cyp_locus, gene_def: *const sp_cyp_gene_def, config: *const sp_cyp_config, out: *mut *mut sp_cyp_db) -> i32;
     pub fn sp_cyp_db_free(db: *mut sp_cyp_db);
     pub fn sp_cyp_db_info(db: *const sp_cyp_db, stats: *mut sp_cyp_db_stats) -> i32;
@@ -746,4 +795,12 @@ extern "C" {
     pub fn sp_fasta_last_error(fasta: *const sp_fasta) -> *const c_char;
     pub fn sp_fasta_sequences(fasta: *mut sp_fasta, n: *mut u32, names: *mut *const *const c_char, lengths: *mut *const u64) -> i32;
     pub fn sp_fasta_fetch(fasta: *mut sp_fasta, chrom: *const c_char, start: u64, end: u64, bases: *mut *const c_char, len: *mut u64) -> i32;
+    pub fn sp_diplotype_settings_default(out: *mut sp_diplotype_settings);
+    pub fn sp_diplotype_settings_check(settings: *mut sp_diplotype_settings, inputs: *const sp_sample_inputs, err: *mut c_char, err_cap: u32) -> i32;
+    pub fn sp_starphase_create(ctx: *mut sp_ctx, database_path: *const c_char, reference_fasta: *const c_char, settings: *const sp_diplotype_settings, out: *mut *mut sp_starphase) -> i32;
+    pub fn sp_starphase_free(handle: *mut sp_starphase);
+    pub fn sp_starphase_last_error(handle: *const sp_starphase) -> *const c_char;
+    pub fn sp_starphase_call(handle: *mut sp_starphase, inputs: *const sp_sample_inputs, out: *mut *mut sp_result) -> i32;
+    pub fn sp_starphase_warnings(handle: *const sp_starphase) -> *const c_char;
+    pub fn sp_starphase_last_timing(handle: *const sp_starphase, out: *mut sp_starphase_timing) -> i32;
 }

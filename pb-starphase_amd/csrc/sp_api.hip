@@ -157,6 +157,10 @@ int32_t sp_struct_size(const char* name) {
     SP_SZ(sp_priority_job)
     SP_SZ(sp_hla_call_config)
     SP_SZ(sp_hla_call)
+    SP_SZ(sp_diplotype_settings)
+    SP_SZ(sp_sample_inputs)
+    SP_SZ(sp_starphase_timing)
+    SP_SZ(sp_cyp_read_mapping)
     SP_SZ(sp_database_metadata)
     SP_SZ(sp_database_stats)
     SP_SZ(sp_gene_region)

@@ -1687,6 +1687,7 @@ struct CypMid {
     uint32_t n_in = 0, cap = 0, n_groups = 0;
     std::vector<int32_t> group_of; std::vector<char> text;
     bool finished = false;                                // the call is complete after part (a) already (no reads)
+    std::vector<sp_cyp_read_mapping>* mappings = nullptr; // sp_cyp_diplotype_mappings: the reads with one chain (multi_mapping_details)
     // between (c1), the weights and (c2)
     std::vector<std::string> full_cons, final_cons; std::vector<int32_t> final_group; std::vector<Label> labels; DeepInfo deep; std::vector<uint8_t> allowed;
     std::vector<uint32_t> a_idx, seg_off; std::vector<int32_t> a_start, a_len; uint32_t H = 0;
@@ -2025,6 +2026,22 @@ int32_t cyp_part_c2(sp_ctx* ctx, const sp_cyp_problem* pr, sp_cyp_call* call, ch
     }
     if (rc == SP_ERR_CHAIN_COLLAPSE) { call->status = SP_ERR_CHAIN_COLLAPSE; return SP_OK; }
     if (rc != SP_OK) return sp_fail(ctx, rc, "sp_cyp_diplotype: chain building");
+    if (m.mappings) {                    // multi_mapping_details (:541-565): a read with one chain, its elements zipped with the read's regions of interest
+        m.mappings->clear();
+        for (uint32_t k = 0; k < info.n_reads; ++k) {
+            if (rco[k + 1] - rco[k] != 1) continue;
+            const uint32_t r = read_index[k], c = rco[k];
+            const uint32_t n_regions = seg_off[r + 1] - seg_off[r], n_items = chain_off[c + 1] - chain_off[c];
+            for (uint32_t x = 0; x < std::min(n_regions, n_items); ++x) {
+                const sp_region_hit& q = m.hits[seg_off[r] + x];
+                const uint32_t h = chain_items[chain_off[c] + x];
+                sp_cyp_read_mapping rm{};
+                rm.read = r; rm.consensus = h; rm.read_start = (uint64_t)q.start; rm.read_end = (uint64_t)q.end;
+                std::snprintf(rm.index_label, sizeof rm.index_label, "%u_%s", h, label_full(labels[h]).c_str());     // before mark_false_allele
+                m.mappings->push_back(rm);
+            }
+        }
+    }
     for (uint32_t h = 0; h < H; ++h) if (fa[h]) labels[h].type = SP_CYP_FALSE_ALLELE;                       // mark_false_allele (:574-583)
     call->n_consensus = (int32_t)H;
     std::vector<const char*> subs(H);
@@ -2093,10 +2110,11 @@ int32_t cyp_part_c(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads
 
 } // namespace
 
-extern "C" int32_t sp_cyp_diplotype_detailed(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
-                                             sp_cyp_region_variants* region_variants) {
+int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
+                                   sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings) {
     if (!ctx) return SP_ERR_INVALID_ARG;
     CypMid m;
+    if (mappings) { mappings->clear(); m.mappings = mappings; }
     int32_t rc = cyp_part_a(ctx, pr, reads, call, region_variants, "cypc", m);
     if (rc != SP_OK || m.finished) return rc;
     {
@@ -2108,7 +2126,25 @@ extern "C" int32_t sp_cyp_diplotype_detailed(sp_ctx* ctx, const sp_cyp_problem* 
         call->searches_gave_up = J.gave_up;
     }
     if (rc != SP_OK) return rc;
-    return cyp_part_c(ctx, pr, reads, call, consensus, cons_cap, region_variants, m);
+    rc = cyp_part_c(ctx, pr, reads, call, consensus, cons_cap, region_variants, m);
+    if (mappings && (rc != SP_OK || call->status != 0)) mappings->clear();
+    return rc;
+}
+
+extern "C" int32_t sp_cyp_diplotype_detailed(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
+                                             sp_cyp_region_variants* region_variants) {
+    return spi_cyp_diplotype_mappings(ctx, pr, reads, call, consensus, cons_cap, region_variants, nullptr);
+}
+
+extern "C" int32_t sp_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
+                                             sp_cyp_region_variants* region_variants, sp_cyp_read_mapping* mappings, uint64_t cap, uint64_t* n_mappings) {
+    if (!n_mappings || (cap && !mappings)) return ctx ? sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_diplotype_mappings: null argument") : SP_ERR_INVALID_ARG;
+    std::vector<sp_cyp_read_mapping> all;
+    const int32_t rc = spi_cyp_diplotype_mappings(ctx, pr, reads, call, consensus, cons_cap, region_variants, &all);
+    *n_mappings = all.size();
+    if (rc != SP_OK) return rc;
+    std::copy(all.begin(), all.begin() + std::min<uint64_t>(cap, all.size()), mappings);
+    return all.size() > cap ? sp_fail(ctx, SP_ERR_CAPACITY, "sp_cyp_diplotype_mappings: more read mappings than cap") : SP_OK;
 }
 
 // The CYP2D6 calls of several samples (one GPU's share of a cohort): each sample alone is a chain of small launches that wait for one another, so

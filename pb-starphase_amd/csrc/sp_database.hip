@@ -688,3 +688,17 @@ int32_t sp_variant_gene_problem_sv_label(const sp_variant_gene* g, int32_t label
 }
 
 } // extern "C"
+
+// what the whole-sample driver (sp_diplotype.hip) needs of a gene entry beyond the public accessors: PgxGene::reference_allele (None ->
+// "NO_REFERENCE_ALLELE", src/diplotyper.rs:94), whether the entry has structural_variants, and the chromosome of its SV genes
+int32_t spi_gene_entry_extras(const sp_database* db, const sp_variant_gene* g, std::string* reference_allele, bool* has_sv, std::string* sv_chrom) {
+    if (!db || !g) return SP_ERR_INVALID_ARG;
+    const Value* entries = db->root.get("gene_entries");
+    const Value* ge = entries ? entries->get(g->gene_name.c_str()) : nullptr;
+    if (!ge) return SP_ERR_INVALID_ARG;
+    const Value* ra = member(*ge, "reference_allele");
+    *reference_allele = (ra && ra->kind == Value::String) ? ra->as_str() : std::string("NO_REFERENCE_ALLELE");
+    *has_sv = member(*ge, "structural_variants") != nullptr;
+    *sv_chrom = g->sv_chrom.empty() ? g->chrom : g->sv_chrom;
+    return SP_OK;
+}

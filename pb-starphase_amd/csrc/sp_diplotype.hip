@@ -1,0 +1,762 @@
+// sp_diplotype.hip -- files to files: call_diplotypes (src/diplotyper.rs:40-330) behind one handle, on top of the library's own entry points.
+// Per database (sp_starphase_create): the database file, the reference FASTA, the HLA database of the hla_config genes (K1 / K2 tables), the
+// CYP2D6 templates and typing tables (on a second context of the same device), every variant gene normalised.  Per sample (sp_starphase_call):
+//   variant genes  VCF (+ SV VCF) -> sp_variant_gene_problem -> one sp_variant_solve_batch (K6) -> the packaging of call_diplotypes (:130-204)
+//   HLA            the read loop of diplotype_hla_batch (src/hla/caller.rs:540-596) -> K1 -> buckets in QNAME order -> K8 / K2 -> new_from_mappings
+//   CYP2D6         the read collection of diplotype_cyp2d6 (src/cyp2d6/caller.rs:60-139) -> K3 / K8 / K9 / K7 / K4 / K5 -> new_from_multi_mappings
+// The CYP2D6 lane (BAM decode, upload, call) runs on a host thread of its own with the second context while the calling thread does the variant genes
+// and the HLA genes; every entry is built from its own lane's inputs only, and the entries are inserted in one fixed order at the end, so the result is
+// the same whichever way the lanes ran (settings.sequential = 1 runs them one after another).
+#include "sp_internal.h"
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <map>
+#include <memory>
+#include <set>
+#include <string>
+#include <sys/stat.h>
+#include <thread>
+#include <vector>
+
+namespace {
+
+thread_local std::string g_create_error;        // sp_starphase_last_error(NULL): why the last create of this thread failed
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+std::string opt(const char* s) { return s ? std::string(s) : std::string(); }
+
+// one read of a locus: QNAME and its SEQ as the file stores it (4 bits per base)
+struct Read4 { std::string qname; std::vector<uint8_t> seq4; uint32_t len = 0; };
+
+// the records of [start, end) of chrom in every BAM, in file order; a QNAME already seen (in an earlier file or region of this lane) is skipped.
+// No FLAG filter: rust-htslib's records() hands out every record of the fetch (the reference filters none).  A fetch that fails counts as no reads.
+int32_t collect_reads(const std::vector<std::string>& bams, const std::string& chrom, uint64_t start, uint64_t end, std::set<std::string>& seen,
+                      std::vector<Read4>& out, std::string& warnings, std::string& err) {
+    for (const std::string& path : bams) {
+        sp_bam* bam = nullptr;
+        char e[512] = {0};
+        if (sp_bam_open(path.c_str(), &bam, e, sizeof e) != SP_OK) { err = "Error while opening " + path + ": " + e; return SP_ERR_INVALID_ARG; }
+        const sp_bam_read* reads = nullptr; uint32_t n = 0; const char* bases = nullptr; const uint64_t* offsets = nullptr;
+        if (sp_bam_fetch(bam, chrom.c_str(), start, end, 0, 0, &reads, &n, &bases, &offsets) != SP_OK) {
+            warnings += "Received error \"" + opt(sp_bam_last_error(bam)) + "\" while fetching " + chrom + ":" + std::to_string(start + 1) + "-" +
+                        std::to_string(end) + " in \"" + path + "\", assuming no reads for region.\n";
+            sp_bam_free(bam);
+            continue;
+        }
+        const uint8_t* seq4 = nullptr; const uint64_t* boff = nullptr; const uint32_t* lens = nullptr; uint32_t n4 = 0;
+        if (sp_bam_last_seq4(bam, &seq4, &boff, &lens, &n4) != SP_OK || n4 != n) { err = "sp_bam_last_seq4 failed on " + path; sp_bam_free(bam); return SP_ERR_INVALID_ARG; }
+        for (uint32_t i = 0; i < n; ++i) {
+            if (!seen.insert(reads[i].qname).second) continue;
+            Read4 r; r.qname = reads[i].qname; r.len = lens[i];
+            r.seq4.assign(seq4 + boff[i], seq4 + boff[i + 1]);
+            out.push_back(std::move(r));
+        }
+        sp_bam_free(bam);
+    }
+    return SP_OK;
+}
+
+// the reads of `order` as one SP_SEQ_BAM4 set
+int32_t upload_reads(sp_ctx* ctx, const std::vector<Read4>& reads, const std::vector<uint32_t>& order, sp_seqset** out) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off{0}; std::vector<uint32_t> lens;
+    for (uint32_t i : order) { bytes.insert(bytes.end(), reads[i].seq4.begin(), reads[i].seq4.end()); off.push_back(bytes.size()); lens.push_back(reads[i].len); }
+    if (bytes.empty()) bytes.push_back(0);
+    return sp_seqset_upload_format(ctx, SP_SEQ_BAM4, bytes.data(), off.data(), lens.data(), (uint32_t)order.size(), out);
+}
+
+std::vector<uint32_t> qname_order(const std::vector<Read4>& reads) {
+    std::vector<uint32_t> o(reads.size());
+    for (uint32_t i = 0; i < o.size(); ++i) o[i] = i;
+    std::sort(o.begin(), o.end(), [&](uint32_t a, uint32_t b) { return reads[a].qname < reads[b].qname; });    // BTreeMap<String, _> order (bytes)
+    return o;
+}
+
+bool read_lines(const std::string& path, std::set<std::string>& out) {
+    std::ifstream f(path);
+    if (!f) return false;
+    std::string line;
+    while (std::getline(f, line)) { if (!line.empty() && line.back() == '\r') line.pop_back(); out.insert(line); }
+    return true;
+}
+
+struct GeneDetailsPtr {
+    sp_gene_details* d = nullptr;
+    GeneDetailsPtr() { sp_gene_details_create(&d); }
+    ~GeneDetailsPtr() { sp_gene_details_free(d); }
+};
+
+// one entry of the result, ready to be inserted: made on whichever lane computed it
+struct Entry { std::string gene; std::unique_ptr<GeneDetailsPtr> details; int32_t constructor = 0; };
+
+}  // namespace
+
+struct sp_starphase {
+    sp_ctx* ctx = nullptr; bool own_ctx = false;
+    sp_ctx* ctx2 = nullptr;                          // the CYP2D6 lane
+    sp_database* db = nullptr;
+    sp_fasta* fasta = nullptr;
+    std::string err, warnings;
+    sp_starphase_timing timing{};
+    // settings (strings copied)
+    sp_diplotype_settings s{};
+    std::string include_set, exclude_set, sample_name, sv_vcf, debug_folder;
+    std::set<std::string> include, exclude; bool has_include = false, has_exclude = false;
+    // chromosomes the variant genes were normalised against (sp_variant_gene keeps a pointer)
+    std::map<std::string, std::string> chrom_seq;
+    // variant genes, in gene_entries key order
+    struct VGene { std::string name, chrom, reference_allele, sv_chrom; bool has_sv = false; sp_variant_gene* g = nullptr; bool selected = true; };
+    std::vector<VGene> vgenes;
+    // HLA: the selected hla_config genes
+    sp_hla_db* hla = nullptr;
+    struct HGene { std::string name, chrom; uint64_t start = 0, end = 0; bool absent_capable = false; };
+    std::vector<HGene> hgenes;
+    std::vector<std::string> a_id, a_star;           // allele i: "HLA:HLA00001", "HLA-A*01:01:01:01" minus the gene ("01:01:01:01")
+    std::vector<uint32_t> a_gene;
+    // CYP2D6
+    sp_cyp_db* cyp = nullptr; bool cyp_selected = false;
+    std::string cyp_chrom; uint64_t cyp_start = 0, cyp_end = 0;     // extraction_region (src/cyp2d6/definitions.rs:72-99)
+    std::string hla_err, cyp_err;                    // why a locus could not be set up (reported by the first call that needs it)
+
+    bool selected(const std::string& gene) const {
+        if (has_include && !include.count(gene)) return false;
+        if (has_exclude && exclude.count(gene)) return false;
+        return true;
+    }
+    int32_t fail(int32_t rc, const std::string& m) { err = m; return rc; }
+};
+
+namespace {
+
+const char* chrom_bases(sp_starphase* h, const std::string& chrom, uint64_t* len) {
+    auto it = h->chrom_seq.find(chrom);
+    if (it == h->chrom_seq.end()) {
+        uint32_t n = 0; const char* const* names = nullptr; const uint64_t* lengths = nullptr;
+        if (sp_fasta_sequences(h->fasta, &n, &names, &lengths) != SP_OK) return nullptr;
+        uint64_t L = 0; bool found = false;
+        for (uint32_t i = 0; i < n; ++i) if (chrom == names[i]) { L = lengths[i]; found = true; }
+        if (!found) return nullptr;
+        const char* b = nullptr; uint64_t got = 0;
+        if (sp_fasta_fetch(h->fasta, chrom.c_str(), 0, L, &b, &got) != SP_OK) return nullptr;
+        it = h->chrom_seq.emplace(chrom, std::string(b, got)).first;
+    }
+    *len = it->second.size();
+    return it->second.c_str();
+}
+
+// ---------------------------------------------------------------- variant genes
+// het_split of solve_diplotype (src/diplotyper.rs:1263-1317): the two observed haplotypes of het assignment `comb` as problem variant ids --
+// the homozygous variants first, then the heterozygous ones in call order
+void het_split(const sp_variant_problem& p, int32_t comb, std::vector<int32_t>& h1, std::vector<int32_t>& h2) {
+    h1.clear();
+    for (int o = 0; o < p.n_obs; ++o) if (p.obs_gt[o] == SP_GT_HOM_ALT) h1.push_back(p.obs_var[o]);
+    h2 = h1;
+    int combo_index = 0;
+    std::map<int64_t, int> lookup;
+    for (int o = 0; o < p.n_obs; ++o) {
+        if (p.obs_gt[o] == SP_GT_HOM_ALT) continue;
+        int is_h1;
+        const int64_t ps = p.obs_ps[o];
+        if (ps >= 0) {
+            auto it = lookup.find(ps);
+            if (it == lookup.end()) { it = lookup.emplace(ps, (comb >> combo_index) & 1).first; ++combo_index; }
+            is_h1 = it->second;
+        } else { is_h1 = (comb >> combo_index) & 1; ++combo_index; }
+        ((is_h1 != 0) == (p.obs_gt[o] != SP_GT_HET_FLIP) ? h1 : h2).push_back(p.obs_var[o]);
+    }
+}
+
+// NormalizedPgxHaplotype::quant_match (src/data_types/normalized_variant.rs:431-479) on ids: matching / missing / extra variants
+void quant_match(const sp_variant_problem& p, int h, const std::vector<int32_t>& obs, std::vector<int32_t>& match, std::vector<int32_t>& missing,
+                 std::vector<int32_t>& extra) {
+    const int s0 = p.slot_off[h], s1 = p.slot_off[h + 1];
+    std::vector<uint8_t> matched((size_t)(s1 - s0) + 1, 0);
+    match.clear(); missing.clear(); extra.clear();
+    for (int32_t v : obs) {
+        int mi = -1;
+        for (int s = s0; s < s1 && mi < 0; ++s)
+            for (int x = p.alt_off[s]; x < p.alt_off[s + 1]; ++x) if (p.alt_var[x] == v) { mi = s - s0; break; }
+        if (mi >= 0 && !matched[mi]) { matched[mi] = 1; match.push_back(v); } else extra.push_back(v);
+    }
+    for (int s = s0; s < s1; ++s) {
+        bool has_none = false; int first_some = -1;
+        for (int x = p.alt_off[s]; x < p.alt_off[s + 1]; ++x) { if (p.alt_var[x] < 0) has_none = true; else if (first_some < 0) first_some = p.alt_var[x]; }
+        if (!(matched[s - s0] || has_none)) missing.push_back(first_some);
+    }
+}
+
+struct VarInfo { std::string name; bool is_core = true; bool is_sv = false; std::string sv_label; };
+
+// one solved gene -> its PgxGeneDetails (call_diplotypes, src/diplotyper.rs:130-204)
+int32_t package_gene(sp_starphase* h, sp_starphase::VGene& vg, const sp_variant_problem& p, const sp_variant_result& res, Entry& e) {
+    sp_variant_gene* g = vg.g;
+    if (res.overflow) return h->fail(SP_ERR_CAPACITY, vg.name + ": more than " + std::to_string(SP_VAR_MAXDIP) + " tied diplotypes");
+    // names of the problem's variants (RegionVariant labels: the database name, "structural_variant" for an SV; SVs are core variants)
+    std::vector<VarInfo> var(p.n_vars);
+    for (int v = 0; v < p.n_vars; ++v) {
+        int32_t dbv = -1; const char* label = nullptr; uint64_t s0 = 0, s1 = 0;
+        if (sp_variant_gene_problem_variant(g, v, &dbv, &label, &s0, &s1) != SP_OK) return h->fail(SP_ERR_INVALID_ARG, vg.name + ": bad problem variant");
+        if (dbv >= 0) {
+            uint64_t pos; const char *r, *a, *nm, *dbsnp; int64_t vid; int32_t core;
+            sp_variant_gene_variant(g, (uint32_t)dbv, &pos, &r, &a, &nm, &dbsnp, &vid, &core);
+            var[v] = VarInfo{opt(nm), core != 0, false, ""};
+        } else var[v] = VarInfo{"structural_variant", true, true, opt(label)};
+    }
+    auto hap_name = [&](int32_t x) -> std::string {
+        if (x < 0) { const char* l = nullptr; sp_variant_gene_problem_sv_label(g, -x - 2, &l); return opt(l); }
+        const char* n = nullptr; const char* c = nullptr; sp_variant_gene_haplotype(g, (uint32_t)x, &n, &c); return opt(n);
+    };
+    auto core_name = [&](int32_t x) -> std::string {          // build_core_allele_lookup (:378-399)
+        if (x < 0) { std::string l = hap_name(x); return l.substr(0, l.find('.')); }
+        const char* n = nullptr; const char* c = nullptr; sp_variant_gene_haplotype(g, (uint32_t)x, &n, &c); return c ? std::string(c) : opt(n);
+    };
+    const bool exact_sub = res.score[0] == 0 && res.score[1] == 0 && res.score[2] == 0 && res.score[3] == 0;
+    const bool exact_core = res.score[0] == 0 && res.score[1] == 0;
+    sp_gene_details* d = e.details->d;
+    for (int i = 0; i < res.n_dip; ++i) {
+        const int32_t a = res.dip[i][0], b = res.dip[i][1];
+        if (exact_sub) sp_gene_details_add_diplotype(d, hap_name(a).c_str(), hap_name(b).c_str());
+        else if (exact_core) sp_gene_details_add_diplotype(d, core_name(a).c_str(), core_name(b).c_str());
+        if (exact_sub || exact_core) sp_gene_details_add_simple_diplotype(d, core_name(a).c_str(), core_name(b).c_str());
+        if (exact_sub) continue;
+        // derive_inexact_haplotype (:1516-1550) of both sides
+        std::vector<int32_t> side[2];
+        het_split(p, res.dip_comb[i], side[0], side[1]);
+        std::string base[2]; std::vector<std::string> labels[2]; std::vector<uint8_t> vi[2]; std::vector<int32_t> st[2];
+        for (int k = 0; k < 2; ++k) {
+            const int32_t x = res.dip[i][k];
+            if (x >= 0) {
+                std::vector<int32_t> m, mi, ex;
+                quant_match(p, x, side[k], m, mi, ex);
+                base[k] = hap_name(x);
+                for (int32_t v : m)  { labels[k].push_back(var[v].name); vi[k].push_back(var[v].is_core); st[k].push_back(SP_REL_MATCH); }
+                for (int32_t v : mi) { labels[k].push_back(var[v].name); vi[k].push_back(var[v].is_core); st[k].push_back(SP_REL_MISSING); }
+                for (int32_t v : ex) { labels[k].push_back(var[v].name); vi[k].push_back(var[v].is_core); st[k].push_back(SP_REL_UNEXPECTED); }
+            } else {                     // the SV short-circuit (:1414-1431): the first label names the haplotype, the others are unexpected core variants
+                bool first = true;
+                for (int32_t v : side[k]) {
+                    if (!var[v].is_sv) continue;
+                    if (first) { base[k] = var[v].sv_label; first = false; continue; }
+                    labels[k].push_back(var[v].sv_label); vi[k].push_back(1); st[k].push_back(SP_REL_UNEXPECTED);
+                }
+                if (first) base[k] = hap_name(x);
+            }
+        }
+        std::vector<const char*> l0, l1;
+        for (auto& s : labels[0]) l0.push_back(s.c_str());
+        for (auto& s : labels[1]) l1.push_back(s.c_str());
+        sp_gene_details_add_inexact_diplotype(d, base[0].c_str(), (uint32_t)l0.size(), l0.data(), vi[0].data(), st[0].data(),
+                                              base[1].c_str(), (uint32_t)l1.size(), l1.data(), vi[1].data(), st[1].data());
+    }
+    // variant_details: the observed variants in NormalizedVariant order
+    for (int o = 0; o < p.n_obs; ++o) {
+        const int32_t v = p.obs_var[o];
+        int32_t dbv = -1; const char* label = nullptr; uint64_t s0 = 0, s1 = 0;
+        sp_variant_gene_problem_variant(g, v, &dbv, &label, &s0, &s1);
+        sp_variant_detail det{};
+        det.genotype = p.obs_gt[o]; det.phase_set = p.obs_ps[o];
+        if (dbv >= 0) {
+            uint64_t pos; const char *r, *a, *nm, *dbsnp; int64_t vid; int32_t core;
+            sp_variant_gene_variant(g, (uint32_t)dbv, &pos, &r, &a, &nm, &dbsnp, &vid, &core);
+            det.variant_id = (uint64_t)vid; det.variant_name = nm; det.dbsnp = dbsnp; det.chrom = vg.chrom.c_str(); det.position = pos;
+            det.reference = r; det.alternate = a; det.is_core_variant = core;
+        } else {
+            det.variant_id = UINT64_MAX; det.variant_name = "structural_variant"; det.dbsnp = nullptr; det.chrom = vg.sv_chrom.c_str(); det.position = s0;
+            det.reference = ""; det.alternate = ""; det.sv_label = label; det.sv_start = s0; det.sv_end = s1; det.is_core_variant = 1;
+        }
+        if (sp_gene_details_add_variant(d, &det) != SP_OK) return h->fail(SP_ERR_INVALID_ARG, vg.name + ": bad variant detail");
+    }
+    e.constructor = exact_sub ? SP_DETAILS_SUBALLELE_MATCH : exact_core ? SP_DETAILS_CORE_MATCH : SP_DETAILS_INEXACT_DIPLOTYPES;
+    return SP_OK;
+}
+
+int32_t variant_lane(sp_starphase* h, const std::string& vcf_path, const std::string& sv_path, const std::string& sample_in, std::vector<Entry>& out) {
+    sp_vcf* vcf = nullptr; sp_vcf* sv = nullptr;
+    char e[512] = {0};
+    if (sp_vcf_open(vcf_path.c_str(), &vcf, e, sizeof e) != SP_OK) return h->fail(SP_ERR_INVALID_ARG, "Error while opening " + vcf_path + ": " + e);
+    std::unique_ptr<sp_vcf, void (*)(sp_vcf*)> vcf_guard(vcf, sp_vcf_free);
+    std::string sample = sample_in;
+    if (sample.empty()) {
+        uint32_t n = 0; const char* const* names = nullptr;
+        if (sp_vcf_samples(vcf, &n, &names) != SP_OK || n == 0) return h->fail(SP_ERR_INVALID_ARG, "No samples found in VCF: " + vcf_path);
+        sample = names[0];
+    }
+    std::unique_ptr<sp_vcf, void (*)(sp_vcf*)> sv_guard(nullptr, sp_vcf_free);
+    if (!sv_path.empty()) {
+        if (sp_vcf_open(sv_path.c_str(), &sv, e, sizeof e) != SP_OK) return h->fail(SP_ERR_INVALID_ARG, "Error while opening " + sv_path + ": " + e);
+        sv_guard.reset(sv);
+    }
+    std::vector<size_t> solved;                         // vgenes index of every gene that goes to the solver
+    std::vector<sp_variant_problem> probs;
+    std::vector<Entry> entries;
+    for (size_t i = 0; i < h->vgenes.size(); ++i) {
+        sp_starphase::VGene& vg = h->vgenes[i];
+        if (!vg.selected) continue;
+        Entry en; en.gene = vg.name; en.details.reset(new GeneDetailsPtr());
+        sp_variant_gene_stats st{};
+        sp_variant_gene_info(vg.g, &st);
+        if (st.n_variants == 0 && !vg.has_sv) {         // "No variants found ..., returning default reference allele." (:94-105)
+            sp_gene_details_add_diplotype(en.details->d, vg.reference_allele.c_str(), vg.reference_allele.c_str());
+            sp_gene_details_add_simple_diplotype(en.details->d, vg.reference_allele.c_str(), vg.reference_allele.c_str());
+            en.constructor = SP_DETAILS_SUBALLELE_MATCH;
+            entries.push_back(std::move(en));
+            continue;
+        }
+        // the records around the gene's variants (load_vcf_variants fetches +-50 bp around each one)
+        uint64_t lo = UINT64_MAX, hi = 0;
+        for (uint32_t v = 0; v < st.n_variants; ++v) {
+            uint64_t pos; const char *r, *a, *nm, *dbsnp; int64_t vid; int32_t core;
+            sp_variant_gene_variant(vg.g, v, &pos, &r, &a, &nm, &dbsnp, &vid, &core);
+            lo = std::min(lo, pos > 50 ? pos - 50 : 0); hi = std::max(hi, pos + std::strlen(r) + 51);
+        }
+        const sp_vcf_allele* alleles = nullptr; uint32_t n_alleles = 0;
+        if (st.n_variants && sp_vcf_alleles(vcf, sample.c_str(), vg.chrom.c_str(), lo, hi, &alleles, &n_alleles) != SP_OK)
+            return h->fail(SP_ERR_INVALID_ARG, vg.name + ": " + opt(sp_vcf_last_error(vcf)));
+        std::vector<sp_vcf_allele> al(alleles, alleles + n_alleles);
+        std::vector<std::string> keep;                   // the reader's strings live until its next fetch
+        keep.reserve(2 * al.size());
+        for (auto& a : al) { keep.push_back(a.ref); a.ref = keep.back().c_str(); keep.push_back(a.alt); a.alt = keep.back().c_str(); }
+        const sp_vcf_deletion* dels = nullptr; uint32_t n_dels = 0;
+        if (sv && vg.has_sv && sp_vcf_deletions(sv, sample.c_str(), vg.sv_chrom.c_str(), 0, UINT64_MAX >> 2, &dels, &n_dels) != SP_OK)
+            return h->fail(SP_ERR_INVALID_ARG, vg.name + ": " + opt(sp_vcf_last_error(sv)));
+        sp_variant_problem p{};
+        if (sp_variant_gene_problem(vg.g, (uint32_t)al.size(), al.data(), n_dels, dels, h->s.max_sv_length, &p) != SP_OK)
+            return h->fail(SP_ERR_INVALID_ARG, vg.name + ": " + opt(sp_variant_gene_last_error(vg.g)));
+        probs.push_back(p); solved.push_back(i);
+        entries.push_back(std::move(en));
+    }
+    // every gene's problem in one launch (K6); the problems point into their sp_variant_gene, which keeps its last problem
+    std::vector<sp_variant_result> res(probs.size());
+    std::vector<int32_t> rcs(probs.size(), SP_OK);
+    if (!probs.empty()) {
+        std::vector<const sp_variant_problem*> pp;
+        for (auto& p : probs) pp.push_back(&p);
+        const int32_t rc = sp_variant_solve_batch(h->ctx, (uint32_t)probs.size(), pp.data(), res.data(), rcs.data());
+        if (rc != SP_OK) return h->fail(rc, "sp_variant_solve_batch: " + opt(sp_last_error(h->ctx)));
+    }
+    size_t k = 0;
+    for (auto& en : entries) {
+        if (k < solved.size() && h->vgenes[solved[k]].name == en.gene) {
+            const int32_t rc = package_gene(h, h->vgenes[solved[k]], probs[k], res[k], en);
+            if (rc != SP_OK) return rc;
+            ++k;
+        }
+        out.push_back(std::move(en));
+    }
+    return SP_OK;
+}
+
+// ---------------------------------------------------------------- HLA
+int32_t hla_lane(sp_starphase* h, const std::vector<std::string>& bams, std::vector<Entry>& out, double* decode_ms, uint32_t* n_reads_out) {
+    const size_t G = h->hgenes.size();
+    // the read loop (src/hla/caller.rs:540-596): genes in hla_config order, every BAM in the given order, a QNAME once
+    std::vector<Read4> reads; std::vector<uint32_t> searched;       // the gene whose region handed out read r
+    std::set<std::string> seen;
+    auto t0 = std::chrono::steady_clock::now();
+    for (size_t g = 0; g < G; ++g) {
+        const size_t before = reads.size();
+        std::string err;
+        if (collect_reads(bams, h->hgenes[g].chrom, h->hgenes[g].start, h->hgenes[g].end, seen, reads, h->warnings, err) != SP_OK)
+            return h->fail(SP_ERR_INVALID_ARG, err);
+        searched.resize(reads.size(), (uint32_t)g);
+        (void)before;
+    }
+    *decode_ms += ms_since(t0);
+    *n_reads_out = (uint32_t)reads.size();
+    // K1 on every read (each read is realigned by itself: any order gives the same records); the gene buckets are in QNAME order
+    const std::vector<uint32_t> order = qname_order(reads);
+    std::vector<sp_hla_realign> rec(reads.size());
+    std::vector<sp_hla_call> calls(G);
+    const uint32_t cap = 1 << 16;
+    std::vector<char> cons(G * 2 * (size_t)cap, 0);
+    std::vector<sp_hla_call_config> cfg(G);
+    double coverage = -1.0;
+    if (!reads.empty()) {
+        sp_seqset* set = nullptr;
+        int32_t rc = upload_reads(h->ctx, reads, order, &set);
+        if (rc != SP_OK) return h->fail(rc, "read upload: " + opt(sp_last_error(h->ctx)));
+        std::unique_ptr<sp_seqset, void (*)(sp_seqset*)> guard(set, sp_seqset_free);
+        rc = sp_hla_realign_reads(h->ctx, h->hla, set, rec.data(), nullptr);
+        if (rc != SP_OK) return h->fail(rc, "sp_hla_realign_reads: " + opt(sp_last_error(h->ctx)));
+        // NORMALIZING_HLA_GENES (src/hla/alleles.rs:49-59)
+        std::vector<uint32_t> norm;
+        for (size_t g = 0; g < G; ++g) if (h->hgenes[g].name == "HLA-DRB1") norm.push_back((uint32_t)g);
+        sp_hla_normalized_coverage(rec.data(), (uint32_t)rec.size(), norm.data(), (uint32_t)norm.size(), &coverage);
+        for (size_t g = 0; g < G; ++g) {
+            sp_hla_call_config& c = cfg[g];
+            c.min_consensus_count = (int32_t)h->s.min_consensus_count; c.dual_max_ed_delta = (int32_t)h->s.dual_max_ed_delta;
+            c.min_consensus_fraction = h->s.min_consensus_fraction; c.expected_maf = h->s.expected_maf; c.min_cdf = h->s.min_cdf_prob;
+            c.require_dna = h->s.hla_require_dna; c.disable_cdna = h->s.disable_cdna_scoring; c.absent_capable = h->hgenes[g].absent_capable;
+            c.normalized_coverage = coverage;
+        }
+        std::vector<uint32_t> genes(G);
+        for (size_t g = 0; g < G; ++g) genes[g] = (uint32_t)g;
+        rc = sp_hla_diplotype_genes(h->ctx, h->hla, (uint32_t)G, genes.data(), set, rec.data(), cfg.data(), calls.data(), cons.data(), cap, nullptr);
+        if (rc != SP_OK) return h->fail(rc, "sp_hla_diplotype_genes: " + opt(sp_last_error(h->ctx)));
+    } else {
+        for (auto& c : calls) { std::memset(&c, 0, sizeof c); c.status = 1; }
+    }
+    // a read whose accepted mapping is on the reverse strand (status 2): the reference names that mapping's allele and reports its stats
+    // (src/hla/realigner.rs:178-193).  The seeded record carries no allele for it, so those reads alone are mapped again through the audit entry,
+    // which hands out the mappings and the accepted one; the same acceptance rule (:124-146) picks it out of them.
+    struct RevHit { int32_t allele = -1; uint64_t t_len = 0, nm = 0, unmapped = 0; };
+    std::map<uint32_t, RevHit> rev;                                  // by position in QNAME order
+    {
+        std::vector<uint32_t> rev_pos, sub;
+        for (uint32_t k = 0; k < rec.size(); ++k) if (rec[k].status == 2 && rec[k].best_allele < 0) { rev_pos.push_back(k); sub.push_back(order[k]); }
+        if (!rev_pos.empty()) {
+            sp_seqset* set2 = nullptr;
+            int32_t rc = upload_reads(h->ctx, reads, sub, &set2);
+            if (rc != SP_OK) return h->fail(rc, "read upload: " + opt(sp_last_error(h->ctx)));
+            std::unique_ptr<sp_seqset, void (*)(sp_seqset*)> guard2(set2, sp_seqset_free);
+            std::vector<int32_t> chains(10 * 256);
+            for (uint32_t i = 0; i < rev_pos.size(); ++i) {
+                sp_k1_seed_hit hits[SP_K1_SEL]; uint32_t n_chains = 0, n_hits = 0; int32_t pick = -1; uint64_t counters[4];
+                rc = sp_hla_realign_seeded_audit(h->ctx, h->hla, set2, i, chains.data(), 256, &n_chains, hits, &n_hits, &pick, counters);
+                if (rc != SP_OK) return h->fail(rc, "sp_hla_realign_seeded_audit: " + opt(sp_last_error(h->ctx)));
+                double best = 1.0; int b = -1;
+                for (uint32_t x = 0; x < std::min<uint32_t>(n_hits, SP_K1_SEL); ++x) {
+                    const int tl = hits[x].t_len, um = tl - (hits[x].t_end - hits[x].t_start), nm = hits[x].nm;
+                    if (tl <= 0 || tl - um <= 0) continue;
+                    const double pen = std::max(0.1, (double)(nm + um)) / tl, ed = std::max(0.1, (double)nm) / (tl - um);
+                    if (pen <= 0.5 && ed <= 0.03 && ed < best) { best = ed; b = (int)x; }
+                }
+                if (b >= 0 && hits[b].rev && hits[b].allele >= 0) {
+                    const sp_k1_seed_hit& q = hits[b];
+                    rev[rev_pos[i]] = RevHit{q.allele, (uint64_t)q.t_len, (uint64_t)q.nm, (uint64_t)(q.t_len - (q.t_end - q.t_start))};
+                }
+            }
+        }
+    }
+    // PgxMappingDetails of every read, in the order the loop met them, in the bucket of its gene (realigned) or of the gene searched (ignored)
+    std::vector<std::unique_ptr<GeneDetailsPtr>> det(G);
+    for (auto& d : det) d.reset(new GeneDetailsPtr());
+    std::vector<uint32_t> pos_of(reads.size());
+    for (uint32_t k = 0; k < order.size(); ++k) pos_of[order[k]] = k;
+    for (uint32_t r = 0; r < reads.size(); ++r) {
+        const sp_hla_realign& q = rec[pos_of[r]];
+        sp_mapping_stats dna{}; dna.present = 1;
+        uint32_t gene = searched[r]; const char* id = "REFERENCE"; std::string star = "REFERENCE"; int32_t ignored = 1;
+        auto rv = rev.find(pos_of[r]);
+        if (rv != rev.end()) {                                       // accepted on the reverse strand: ignored, named after that mapping
+            const uint32_t a = (uint32_t)rv->second.allele;
+            id = h->a_id[a].c_str(); star = h->hgenes[h->a_gene[a]].name + "*" + h->a_star[a];
+            dna.seq_len = rv->second.t_len; dna.nm = rv->second.nm; dna.unmapped = rv->second.unmapped;
+        } else if (q.best_allele >= 0 && q.status != 1) {
+            const uint32_t a = (uint32_t)q.best_allele;
+            id = h->a_id[a].c_str(); star = h->hgenes[h->a_gene[a]].name + "*" + h->a_star[a];
+            dna.seq_len = (uint64_t)q.target_len; dna.nm = (uint64_t)q.mm2_nm;
+            dna.unmapped = (uint64_t)std::max(0, q.target_len - (q.mm2_t_end - q.mm2_t_start));
+            if (q.status == 0) { ignored = 0; gene = h->a_gene[a]; }
+        } else { dna.seq_len = reads[r].len; dna.nm = reads[r].len; dna.unmapped = 0; }      // MappingStats::new(read_len, read_len, 0) (realigner.rs:124)
+        sp_gene_details_add_mapping(det[gene]->d, reads[r].qname.c_str(), id, star.c_str(), nullptr, &dna, ignored);
+    }
+    // the diplotypes (src/hla/caller.rs:662-668,889-923,451-474)
+    auto name = [&](int32_t a) -> std::string {
+        if (a == -2) return ".";
+        if (a < 0) return "";
+        return "*" + h->a_star[(size_t)a];
+    };
+    for (size_t g = 0; g < G; ++g) {
+        const sp_hla_call& c = calls[g];
+        std::string n1, n2;
+        if (c.status == 1) n1 = n2 = h->hgenes[g].absent_capable ? "." : "NO_READS";
+        else { n1 = name(c.allele1); n2 = name(c.allele2); }
+        sp_gene_details_add_diplotype(det[g]->d, n1.c_str(), n2.c_str());
+        Entry en; en.gene = h->hgenes[g].name; en.details = std::move(det[g]); en.constructor = SP_DETAILS_FROM_MAPPINGS;
+        out.push_back(std::move(en));
+    }
+    // hla_debug.json: the DualPassingStats of every gene that had reads (src/hla/caller.rs:1042-1048)
+    if (!h->debug_folder.empty()) {
+        sp_hla_debug* dbg = nullptr;
+        sp_hla_debug_create(&dbg);
+        for (size_t g = 0; g < G; ++g) {
+            if (calls[g].status == 1) continue;
+            for (int k = 0; k < 2; ++k) {
+                const int32_t t = k ? calls[g].typed2 : calls[g].typed1;
+                if (k == 1 && !calls[g].is_dual) continue;
+                const std::string who = k ? "consensus2" : "consensus1";
+                const std::string st = t >= 0 ? h->hgenes[h->a_gene[t]].name + "*" + h->a_star[t] : "";
+                sp_hla_debug_add_read(dbg, h->hgenes[g].name.c_str(), who.c_str(), t >= 0 ? h->a_id[t].c_str() : nullptr, st.c_str());
+            }
+            sp_hla_debug_add_dual_stats(dbg, h->hgenes[g].name.c_str(), &calls[g]);
+        }
+        const std::string path = h->debug_folder + "/hla_debug.json";
+        const int32_t rc = sp_hla_debug_save(dbg, path.c_str());
+        sp_hla_debug_free(dbg);
+        if (rc != SP_OK) return h->fail(rc, "Error while writing " + path);
+    }
+    return SP_OK;
+}
+
+// ---------------------------------------------------------------- CYP2D6
+struct CypLane {
+    int32_t rc = SP_OK; std::string err, warnings;
+    Entry entry; double decode_ms = 0, ms = 0; uint32_t n_reads = 0;
+};
+
+void cyp_lane(sp_starphase* h, const std::vector<std::string>& bams, CypLane* L) {
+    auto t_lane = std::chrono::steady_clock::now();
+    L->entry.gene = "CYP2D6"; L->entry.details.reset(new GeneDetailsPtr());
+    sp_gene_details* d = L->entry.details->d;
+    std::vector<Read4> reads; std::set<std::string> seen;
+    auto t0 = std::chrono::steady_clock::now();
+    if (collect_reads(bams, h->cyp_chrom, h->cyp_start, h->cyp_end, seen, reads, L->warnings, L->err) != SP_OK) { L->rc = SP_ERR_INVALID_ARG; return; }
+    L->decode_ms = ms_since(t0);
+    L->n_reads = (uint32_t)reads.size();
+    L->entry.constructor = SP_DETAILS_FROM_MULTI_MAPPINGS;
+    if (reads.empty()) {                            // "No reads found for CYP2D6 consensus generation." (src/cyp2d6/caller.rs:254-266)
+        sp_gene_details_add_diplotype(d, "NO_READS", "NO_READS");
+        L->ms = ms_since(t_lane);
+        return;
+    }
+    sp_cyp_problem pr{};
+    sp_cyp_db_problem(h->cyp, &pr);
+    pr.min_consensus_count = (int32_t)h->s.min_consensus_count; pr.dual_max_ed_delta = (int32_t)h->s.dual_max_ed_delta;
+    pr.min_consensus_fraction = h->s.min_consensus_fraction; pr.infer_connections = h->s.infer_connections; pr.normalize_d6_only = h->s.normalize_d6_only;
+    sp_seqset* set = nullptr;
+    const std::vector<uint32_t> order = qname_order(reads);                        // read_collection is a BTreeMap: QNAME order
+    int32_t rc = upload_reads(h->ctx2, reads, order, &set);
+    if (rc != SP_OK) { L->rc = rc; L->err = "read upload: " + opt(sp_last_error(h->ctx2)); return; }
+    std::unique_ptr<sp_seqset, void (*)(sp_seqset*)> guard(set, sp_seqset_free);
+    sp_cyp_call call{};
+    std::vector<uint8_t> state((size_t)SP_CYP_MAXCONS * std::max<uint32_t>(pr.n_variants, 1));
+    sp_cyp_region_variants rv{}; rv.state = state.data();
+    std::vector<sp_cyp_read_mapping> mappings;
+    rc = spi_cyp_diplotype_mappings(h->ctx2, &pr, set, &call, nullptr, 0, &rv, &mappings);
+    if (rc != SP_OK) { L->rc = rc; L->err = "sp_cyp_diplotype: " + opt(sp_last_error(h->ctx2)); return; }
+    if (call.status == 16 || call.status == 17 || call.status == 18) {              // CallerError -> PgxGeneDetails::no_match() (src/diplotyper.rs:316-327)
+        L->entry.constructor = SP_DETAILS_NO_MATCH;
+    } else if (call.status == 1) {
+        sp_gene_details_add_diplotype(d, "NO_READS", "NO_READS");
+    } else if (call.status != 0) {
+        L->rc = SP_ERR_CHAIN_COLLAPSE; L->err = "CYP2D6: chain collapse"; return;
+    } else {
+        sp_gene_details_add_diplotype(d, call.hap1, call.hap2);
+        sp_gene_details_add_simple_diplotype(d, call.core1, call.core2);
+        sp_gene_details_add_diplotype_only(d, call.deep1, call.deep2);
+        for (const sp_cyp_read_mapping& m : mappings)                               // multi_mapping_details (src/cyp2d6/caller.rs:541-565)
+            sp_gene_details_add_multi_mapping(d, reads[order[m.read]].qname.c_str(), m.read_start, m.read_end, m.consensus, m.index_label);
+        if (!h->debug_folder.empty()) {
+            uint64_t need = 0;
+            sp_cyp_alleles_json(&pr, &call, &rv, nullptr, 0, &need);
+            std::string text(need, '\0');
+            if (sp_cyp_alleles_json(&pr, &call, &rv, &text[0], need, &need) != SP_OK) { L->rc = SP_ERR_INVALID_ARG; L->err = "cyp2d6_alleles.json"; return; }
+            text.resize(std::strlen(text.c_str()));
+            const std::string path = h->debug_folder + "/cyp2d6_alleles.json";
+            FILE* f = std::fopen(path.c_str(), "wb");
+            if (!f || std::fwrite(text.data(), 1, text.size(), f) != text.size()) { if (f) std::fclose(f); L->rc = SP_ERR_INVALID_ARG; L->err = "Error while writing " + path; return; }
+            std::fclose(f);
+        }
+    }
+    L->ms = ms_since(t_lane);
+}
+
+}  // namespace
+
+extern "C" {
+
+void sp_diplotype_settings_default(sp_diplotype_settings* s) {
+    if (!s) return;
+    std::memset(s, 0, sizeof *s);
+    s->max_sv_length = 1000000; s->max_error_rate = 0.07; s->min_cdf_prob = 0.001; s->expected_maf = 0.45;
+    s->min_consensus_fraction = 0.10; s->min_consensus_count = 3; s->dual_max_ed_delta = 100;
+}
+
+// check_diplotype_settings (src/cli/diplotype.rs:200-330), messages as the reference's
+int32_t sp_diplotype_settings_check(sp_diplotype_settings* s, const sp_sample_inputs* in, char* err, uint32_t err_cap) {
+    auto fail = [&](const char* m) { if (err && err_cap) { std::snprintf(err, err_cap, "%s", m); } return (int32_t)SP_ERR_INVALID_ARG; };
+    if (err && err_cap) err[0] = 0;
+    if (!s) return fail("no settings");
+    const bool has_vcf = in && in->vcf, has_bam = in && in->n_bams > 0;
+    if (!has_vcf && !has_bam) return fail("Must provide a VCF file and/or aligned BAM file to perform diplotyping.");
+    if (s->include_set && s->exclude_set) return fail("Only one of --exclude-set and --include-set can be specified.");
+    if (has_bam) {
+        if (s->disable_cdna_scoring) s->hla_require_dna = 1;                 // "Automatically enabling HLA DNA requirement"
+        if (!(s->max_error_rate >= 0.0 && s->max_error_rate <= 1.0)) return fail("--max-error-rate must be between 0.0 and 1.0");
+        if (!(s->min_cdf_prob >= 0.0 && s->min_cdf_prob <= 1.0)) return fail("--min-cdf-prob must be between 0.0 and 1.0");
+        if (!(s->expected_maf >= 0.01 && s->expected_maf <= 0.5)) return fail("--expected-maf must be between 0.01 and 0.5");
+        if (!(s->min_consensus_fraction >= 0.0 && s->min_consensus_fraction <= 1.0)) return fail("--min-consensus-fraction must be between 0.0 and 1.0");
+    }
+    return SP_OK;
+}
+
+void sp_starphase_free(sp_starphase* h) {
+    if (!h) return;
+    for (auto& v : h->vgenes) sp_variant_gene_free(v.g);
+    if (h->hla) sp_hla_db_free(h->hla);
+    if (h->cyp) sp_cyp_db_free(h->cyp);
+    if (h->fasta) sp_fasta_free(h->fasta);
+    if (h->db) sp_database_free(h->db);
+    if (h->ctx2) sp_ctx_destroy(h->ctx2);
+    if (h->own_ctx && h->ctx) sp_ctx_destroy(h->ctx);
+    delete h;
+}
+
+const char* sp_starphase_last_error(const sp_starphase* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+const char* sp_starphase_warnings(const sp_starphase* h) { return h ? h->warnings.c_str() : ""; }
+int32_t sp_starphase_last_timing(const sp_starphase* h, sp_starphase_timing* out) {
+    if (!h || !out) return SP_ERR_INVALID_ARG;
+    *out = h->timing;
+    return SP_OK;
+}
+
+int32_t sp_starphase_create(sp_ctx* ctx, const char* database_path, const char* reference_fasta, const sp_diplotype_settings* settings, sp_starphase** out) {
+    g_create_error.clear();
+    if (!out || !database_path || !settings) { g_create_error = "sp_starphase_create: missing argument"; return SP_ERR_INVALID_ARG; }
+    *out = nullptr;
+    std::unique_ptr<sp_starphase, void (*)(sp_starphase*)> h(new sp_starphase(), sp_starphase_free);
+    auto fail = [&](int32_t rc, const std::string& m) { g_create_error = m; return rc; };
+    // the two contexts first: no device is an error before any file is read
+    h->ctx = ctx;
+    if (!ctx) {
+        const int32_t rc = sp_ctx_create(0, nullptr, &h->ctx);
+        if (rc != SP_OK) return fail(rc, "sp_starphase_create: no usable HIP device");
+        h->own_ctx = true;
+    }
+    sp_ctx_info info{};
+    sp_ctx_get_info(h->ctx, &info);
+    if (sp_ctx_create(info.device, nullptr, &h->ctx2) != SP_OK) return fail(SP_ERR_NO_DEVICE, "sp_starphase_create: no second context on the device");
+    h->s = *settings;
+    h->include_set = opt(settings->include_set); h->exclude_set = opt(settings->exclude_set); h->sample_name = opt(settings->sample_name);
+    h->sv_vcf = opt(settings->sv_vcf); h->debug_folder = opt(settings->debug_folder);
+    h->s.include_set = h->s.exclude_set = h->s.sample_name = h->s.sv_vcf = h->s.debug_folder = nullptr;
+    if (settings->include_set && settings->exclude_set) return fail(SP_ERR_INVALID_ARG, "Only one of --exclude-set and --include-set can be specified.");
+    if (!h->include_set.empty()) { h->has_include = true; if (!read_lines(h->include_set, h->include)) return fail(SP_ERR_INVALID_ARG, "Include set does not exist: \"" + h->include_set + "\""); }
+    if (!h->exclude_set.empty()) { h->has_exclude = true; if (!read_lines(h->exclude_set, h->exclude)) return fail(SP_ERR_INVALID_ARG, "Exclude set does not exist: \"" + h->exclude_set + "\""); }
+    char e[1024] = {0};
+    if (sp_database_load(database_path, &h->db, e, sizeof e) != SP_OK) return fail(SP_ERR_INVALID_ARG, std::string("Error while loading PGx database file: ") + e);
+    if (reference_fasta && sp_fasta_open(reference_fasta, &h->fasta, e, sizeof e) != SP_OK)
+        return fail(SP_ERR_INVALID_ARG, std::string("Error while loading reference genome file: ") + e);
+    sp_database_stats st{};
+    sp_database_info(h->db, &st);
+    // variant genes: load_database_haplotypes once per gene (key order)
+    for (uint32_t i = 0; i < st.n_gene_entries; ++i) {
+        const char* name = nullptr; const char* chrom = nullptr;
+        sp_database_gene_entry(h->db, i, &name, &chrom);
+        sp_starphase::VGene vg; vg.name = name; vg.chrom = chrom; vg.selected = h->selected(vg.name);
+        const char* seq = nullptr; uint64_t len = 0;
+        if (h->fasta && !(seq = chrom_bases(h.get(), vg.chrom, &len)))
+            return fail(SP_ERR_INVALID_ARG, vg.name + ": Reference genome does not contain contig \"" + vg.chrom + "\"");
+        if (sp_variant_gene_create(h->db, name, seq, len, &vg.g) != SP_OK) return fail(SP_ERR_INVALID_ARG, vg.name + ": " + opt(sp_database_last_error(h->db)));
+        spi_gene_entry_extras(h->db, vg.g, &vg.reference_allele, &vg.has_sv, &vg.sv_chrom);
+        h->vgenes.push_back(std::move(vg));
+    }
+    if (!h->fasta) { *out = h.release(); return SP_OK; }          // no genome: the BAM loci cannot run (sp_starphase_call says so)
+    // HLA: the hla_config genes that are selected, flattened against the reference (+-100 bp, src/hla/realigner.rs:74-81).  The reference builds
+    // its realigner only when a sample has BAMs: a locus that cannot be set up here (its contig is not in the FASTA, ...) fails the first call with BAMs
+    auto setup_hla = [&]() -> int32_t {
+        std::vector<std::string> names, refs;
+        for (uint32_t g = 0; g < st.n_hla_genes; ++g) {
+            sp_gene_region r{};
+            sp_database_hla_gene(h->db, g, &r);
+            if (!h->selected(r.name)) continue;
+            const char* b = nullptr; uint64_t n = 0;
+            const uint64_t lo = r.start >= 100 ? r.start - 100 : 0;
+            if (sp_fasta_fetch(h->fasta, r.chrom, lo, r.end + 100, &b, &n) != SP_OK)
+                return fail(SP_ERR_INVALID_ARG, std::string(r.name) + ": " + opt(sp_fasta_last_error(h->fasta)));
+            names.push_back(r.name); refs.emplace_back(b, n);
+            h->hgenes.push_back(sp_starphase::HGene{r.name, r.chrom, r.start, r.end, r.is_absent_capable != 0});
+        }
+        if (!names.empty()) {
+            std::vector<const char*> pn, pr;
+            for (size_t i = 0; i < names.size(); ++i) { pn.push_back(names[i].c_str()); pr.push_back(refs[i].c_str()); }
+            sp_hla_db_desc desc{};
+            if (sp_database_hla_flatten(h->db, (uint32_t)names.size(), pn.data(), pr.data(), 100, &desc) != SP_OK)
+                return fail(SP_ERR_INVALID_ARG, "HLA: " + opt(sp_database_last_error(h->db)));
+            for (uint32_t a = 0; a < desc.n_alleles; ++a) {
+                const char *id, *gene, *star;
+                sp_database_hla_allele(h->db, a, &id, &gene, &star);
+                h->a_id.push_back(id); h->a_star.push_back(star); h->a_gene.push_back(desc.gene_of[a]);
+            }
+            const int32_t rc = sp_hla_db_create(h->ctx, &desc, &h->hla);
+            if (rc != SP_OK) return fail(rc, "sp_hla_db_create: " + opt(sp_last_error(h->ctx)));
+        }
+        return SP_OK;
+    };
+    // CYP2D6: the window of the configuration, the templates and tables on the second context
+    h->cyp_selected = h->selected("CYP2D6");
+    auto setup_cyp = [&]() -> int32_t {
+        const char* chrom = nullptr; uint64_t ws = 0, we = 0;
+        if (sp_database_cyp_window(h->db, &chrom, &ws, &we) != SP_OK) return fail(SP_ERR_INVALID_ARG, "CYP2D6: " + opt(sp_database_last_error(h->db)));
+        h->cyp_chrom = chrom;
+        // the templates reach past the configured coordinates (the *5 signature takes flanks around the deletion): the window gets 10 kb each side
+        uint32_t nseq = 0; const char* const* names = nullptr; const uint64_t* lengths = nullptr;
+        sp_fasta_sequences(h->fasta, &nseq, &names, &lengths);
+        uint64_t clen = 0;
+        for (uint32_t i = 0; i < nseq; ++i) if (h->cyp_chrom == names[i]) clen = lengths[i];
+        ws = ws > 10000 ? ws - 10000 : 0; we = std::min(we + 10000, clen);
+        const char* b = nullptr; uint64_t n = 0;
+        if (sp_fasta_fetch(h->fasta, chrom, ws, we, &b, &n) != SP_OK) return fail(SP_ERR_INVALID_ARG, "CYP2D6: " + opt(sp_fasta_last_error(h->fasta)));
+        const std::string window(b, n);
+        sp_cyp_locus locus{}; sp_cyp_gene_def gd{}; sp_cyp_config cc{};
+        if (sp_database_cyp_flatten(h->db, window.c_str(), ws, window.size(), &locus, &gd, &cc) != SP_OK)
+            return fail(SP_ERR_INVALID_ARG, "CYP2D6: " + opt(sp_database_last_error(h->db)));
+        const int32_t rc = sp_cyp_db_create(h->ctx2, &locus, &gd, &cc, &h->cyp);
+        if (rc != SP_OK) return fail(rc, "sp_cyp_db_create: " + opt(sp_last_error(h->ctx2)));
+        // extraction_region (src/cyp2d6/definitions.rs:72-99; STAR5_PRE_BUFFER 500, STAR5_POST_BUFFER 3000)
+        h->cyp_start = std::min({locus.d6_start, locus.star5_start - 500, locus.d7_start, locus.rep6_start, locus.rep7_start});
+        h->cyp_end = std::max({locus.d6_end, locus.star5_end + 3000, locus.d7_end, locus.rep6_end, locus.rep7_end});
+        return SP_OK;
+    };
+    if (!settings->debug_skip_hla && setup_hla() != SP_OK) { h->hla_err = g_create_error; h->hgenes.clear(); g_create_error.clear(); }
+    if (h->cyp_selected && setup_cyp() != SP_OK) { h->cyp_err = g_create_error; g_create_error.clear(); }
+    *out = h.release();
+    return SP_OK;
+}
+
+int32_t sp_starphase_call(sp_starphase* h, const sp_sample_inputs* in, sp_result** out) {
+    if (!h || !in || !out) return SP_ERR_INVALID_ARG;
+    *out = nullptr;
+    h->err.clear(); h->warnings.clear(); h->timing = sp_starphase_timing{};
+    const auto t_call = std::chrono::steady_clock::now();
+    std::vector<std::string> bams;
+    for (uint32_t i = 0; i < in->n_bams; ++i) bams.push_back(opt(in->bams[i]));
+    if (!bams.empty() && !h->fasta) return h->fail(SP_ERR_INVALID_ARG, "Reference genome is required for reading alignment files");
+    if (!bams.empty() && !h->s.debug_skip_hla && !h->hla_err.empty()) return h->fail(SP_ERR_INVALID_ARG, h->hla_err);
+    if (!bams.empty() && h->cyp_selected && !h->cyp_err.empty()) return h->fail(SP_ERR_INVALID_ARG, h->cyp_err);
+    const std::string sample = in->sample_name ? opt(in->sample_name) : h->sample_name;
+    const std::string sv = in->sv_vcf ? opt(in->sv_vcf) : h->sv_vcf;
+    if (!h->debug_folder.empty()) mkdir(h->debug_folder.c_str(), 0755);
+    // the CYP2D6 lane: on its own host thread and context unless sequential
+    CypLane cyp;
+    const bool run_cyp = !bams.empty() && h->cyp_selected && h->cyp;
+    std::thread worker;
+    if (run_cyp && !h->s.sequential) worker = std::thread(cyp_lane, h, std::cref(bams), &cyp);
+    std::vector<Entry> var_entries, hla_entries;
+    int32_t rc = SP_OK;
+    auto t0 = std::chrono::steady_clock::now();
+    if (in->vcf) rc = variant_lane(h, in->vcf, sv, sample, var_entries);
+    h->timing.variant_ms = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    if (rc == SP_OK && !bams.empty() && h->hla && !h->s.debug_skip_hla)
+        rc = hla_lane(h, bams, hla_entries, &h->timing.bam_decode_ms, &h->timing.n_hla_reads);
+    h->timing.hla_ms = ms_since(t0);
+    if (worker.joinable()) worker.join();
+    else if (run_cyp && rc == SP_OK) cyp_lane(h, bams, &cyp);
+    if (rc != SP_OK) return rc;
+    h->warnings += cyp.warnings;
+    if (cyp.rc != SP_OK) return h->fail(cyp.rc, cyp.err);
+    h->timing.bam_decode_ms += cyp.decode_ms; h->timing.cyp_ms = cyp.ms; h->timing.n_cyp_reads = cyp.n_reads;
+    // the entries in the reference's order: variant genes, HLA genes, CYP2D6 (StarphaseJson::insert refuses a second entry for a gene)
+    sp_result* res = nullptr;
+    sp_result_create(h->db, nullptr, &res);
+    std::unique_ptr<sp_result, void (*)(sp_result*)> guard(res, sp_result_free);
+    if (run_cyp) cyp.entry.gene = "CYP2D6";
+    std::vector<Entry*> all;
+    for (auto& e : var_entries) all.push_back(&e);
+    for (auto& e : hla_entries) all.push_back(&e);
+    if (run_cyp) all.push_back(&cyp.entry);
+    for (Entry* e : all)
+        if (sp_result_insert(res, e->gene.c_str(), e->details->d, e->constructor) != SP_OK) return h->fail(SP_ERR_INVALID_ARG, opt(sp_result_last_error(res)));
+    h->timing.call_ms = ms_since(t_call);
+    *out = guard.release();
+    return SP_OK;
+}
+
+}  // extern "C"

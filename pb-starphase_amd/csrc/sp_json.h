@@ -18,6 +18,7 @@ namespace spj {
 struct Value {
     enum Kind { Null, Bool, Int, Double, String, Array, Object } kind = Null;
     bool b = false; int64_t i = 0; double d = 0.0; std::string s;
+    bool is_u64 = false;                          // an Int written as an unsigned 64-bit number (a u64 field above i64::MAX, e.g. u64::MAX)
     std::vector<Value> arr;
     std::vector<std::pair<std::string, Value>> obj;
     std::vector<uint32_t> by_key;                 // large objects: member numbers sorted by (key, position), built when the object has been read
@@ -167,7 +168,7 @@ inline void write_pretty(std::string& out, const Value& v, int depth = 0) {
     switch (v.kind) {
         case Value::Null: out += "null"; break;
         case Value::Bool: out += v.b ? "true" : "false"; break;
-        case Value::Int: out += std::to_string(v.i); break;
+        case Value::Int: out += v.is_u64 ? std::to_string((uint64_t)v.i) : std::to_string(v.i); break;
         case Value::Double: write_double(out, v.d); break;
         case Value::String: write_string(out, v.s); break;
         case Value::Array:
@@ -186,6 +187,7 @@ inline void write_pretty(std::string& out, const Value& v, int depth = 0) {
 }
 inline Value str(const std::string& s) { Value v; v.kind = Value::String; v.s = s; return v; }
 inline Value num(int64_t i) { Value v; v.kind = Value::Int; v.i = i; return v; }
+inline Value unum(uint64_t u) { Value v; v.kind = Value::Int; v.i = (int64_t)u; v.is_u64 = true; return v; }
 inline Value real(double d) { Value v; v.kind = Value::Double; v.d = d; return v; }
 inline Value boolean(bool b) { Value v; v.kind = Value::Bool; v.b = b; return v; }
 inline Value object() { Value v; v.kind = Value::Object; return v; }

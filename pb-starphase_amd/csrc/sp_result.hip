@@ -147,7 +147,7 @@ int32_t sp_gene_details_add_variant(sp_gene_details* d, const sp_variant_detail*
     Value g = spj::object();
     g.obj.emplace_back("genotype", spj::str(gt_names[v->genotype])); g.obj.emplace_back("phase_set", option_u64(v->phase_set >= 0, (uint64_t)v->phase_set));
     Value x = spj::object();
-    x.obj.emplace_back("variant_id", spj::num((int64_t)v->variant_id)); x.obj.emplace_back("variant_name", spj::str(v->variant_name ? v->variant_name : ""));
+    x.obj.emplace_back("variant_id", spj::unum(v->variant_id)); x.obj.emplace_back("variant_name", spj::str(v->variant_name ? v->variant_name : ""));
     x.obj.emplace_back("dbsnp", v->dbsnp ? spj::str(v->dbsnp) : Value());
     x.obj.emplace_back("normalized_variant", std::move(nv)); x.obj.emplace_back("normalized_genotype", std::move(g));
     x.obj.emplace_back("is_core_variant", spj::boolean(v->is_core_variant != 0));

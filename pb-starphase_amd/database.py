@@ -50,6 +50,25 @@ class sp_detailed_mapping(C.Structure):
                 ("query_unmapped", _u64), ("target_unmapped", _u64), ("cigar", _s), ("md", _s)]
 
 
+class sp_diplotype_settings(C.Structure):
+    _fields_ = [(k, _s) for k in ("include_set", "exclude_set", "sample_name", "sv_vcf", "debug_folder")] + [("max_sv_length", _u64)] + \
+               [("disable_cdna_scoring", _i32), ("hla_require_dna", _i32)] + [(k, C.c_double) for k in ("max_error_rate", "min_cdf_prob", "expected_maf")] + \
+               [("infer_connections", _i32), ("normalize_d6_only", _i32), ("min_consensus_fraction", C.c_double),
+                ("min_consensus_count", _u64), ("dual_max_ed_delta", _u64), ("debug_skip_hla", _i32), ("sequential", _i32)]
+
+
+class sp_sample_inputs(C.Structure):
+    _fields_ = [("n_bams", _u32), ("bams", C.POINTER(_s)), ("vcf", _s), ("sv_vcf", _s), ("sample_name", _s)]
+
+
+class sp_cyp_read_mapping(C.Structure):
+    _fields_ = [("read", _u32), ("consensus", _u32), ("read_start", _u64), ("read_end", _u64), ("index_label", C.c_char * 64)]
+
+
+class sp_starphase_timing(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("call_ms", "bam_decode_ms", "variant_ms", "hla_ms", "cyp_ms")] + [("n_hla_reads", _u32), ("n_cyp_reads", _u32)]
+
+
 SUBALLELE_MATCH, CORE_MATCH, INEXACT_DIPLOTYPES, FROM_MAPPINGS, FROM_MULTI_MAPPINGS, NO_MATCH = range(6)
 _bound = False
 
@@ -111,6 +130,16 @@ def _lib():
         "sp_hla_debug_add_dual_stats": (_i32, [_vp, _s, P(ffi.sp_hla_call)]),
         "sp_hla_debug_json": (_i32, [_vp, P(_s), P(_u64)]),
         "sp_hla_debug_save": (_i32, [_vp, _s]),
+        "sp_cyp_diplotype_mappings": (_i32, [_vp, P(ffi.sp_cyp_problem), _vp, P(ffi.sp_cyp_call), _s, _u32, P(ffi.sp_cyp_region_variants), P(sp_cyp_read_mapping),
+                                             _u64, P(_u64)]),
+        "sp_diplotype_settings_default": (None, [P(sp_diplotype_settings)]),
+        "sp_diplotype_settings_check": (_i32, [P(sp_diplotype_settings), P(sp_sample_inputs), _s, _u32]),
+        "sp_starphase_create": (_i32, [_vp, _s, _s, P(sp_diplotype_settings), P(_vp)]),
+        "sp_starphase_free": (None, [_vp]),
+        "sp_starphase_last_error": (_s, [_vp]),
+        "sp_starphase_call": (_i32, [_vp, P(sp_sample_inputs), P(_vp)]),
+        "sp_starphase_warnings": (_s, [_vp]),
+        "sp_starphase_last_timing": (_i32, [_vp, P(sp_starphase_timing)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -673,3 +702,97 @@ class Fasta:
         if rc != SP_OK:
             raise StarphaseError(rc, _io().sp_fasta_last_error(self._h).decode())
         return C.string_at(b, n.value).decode()
+
+
+# ---------------------------------------------------------------- files to files (sp_starphase_*)
+SETTINGS_STRINGS = ("include_set", "exclude_set", "sample_name", "sv_vcf", "debug_folder")
+
+
+def settings_default():
+    """sp_diplotype_settings_default() as a dict"""
+    s = sp_diplotype_settings()
+    _lib().sp_diplotype_settings_default(C.byref(s))
+    return {k: (_d(getattr(s, k)) if k in SETTINGS_STRINGS else getattr(s, k)) for k, _t in sp_diplotype_settings._fields_}
+
+
+def _settings(**kw):
+    s = sp_diplotype_settings()
+    _lib().sp_diplotype_settings_default(C.byref(s))
+    for k, v in kw.items():
+        if k not in dict(sp_diplotype_settings._fields_):
+            raise KeyError(k)
+        setattr(s, k, _b(v) if k in SETTINGS_STRINGS else v)
+    return s
+
+
+def _inputs(bams=(), vcf=None, sv_vcf=None, sample_name=None):
+    arr = (_s * max(1, len(bams)))(*[_b(b) for b in bams])
+    return sp_sample_inputs(len(bams), arr, _b(vcf), _b(sv_vcf), _b(sample_name)), arr
+
+
+def settings_check(bams=(), vcf=None, **kw):
+    """sp_diplotype_settings_check: (status, message, settings dict after the check)"""
+    s = _settings(**kw)
+    inp, _keep = _inputs(bams, vcf)
+    err = C.create_string_buffer(512)
+    rc = _lib().sp_diplotype_settings_check(C.byref(s), C.byref(inp), err, 512)
+    return rc, err.value.decode(), {k: getattr(s, k) for k, _t in sp_diplotype_settings._fields_ if k not in SETTINGS_STRINGS}
+
+
+class Starphase:
+    """sp_starphase: a database + reference loaded once, sp_starphase_call per sample.  ctx: a Context or None (the handle makes its own)."""
+
+    def __init__(self, database, reference=None, ctx=None, **settings):
+        self._h = _vp()
+        self._s = _settings(**settings)
+        rc = _lib().sp_starphase_create(ctx._h if ctx is not None else None, _b(database), _b(reference), C.byref(self._s), C.byref(self._h))
+        if rc != SP_OK:
+            raise StarphaseError(rc, _d(_lib().sp_starphase_last_error(None)))
+
+    def close(self):
+        if self._h:
+            _lib().sp_starphase_free(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def call(self, bams=(), vcf=None, sv_vcf=None, sample_name=None):
+        """one sample -> Result"""
+        inp, _keep = _inputs(bams, vcf, sv_vcf, sample_name)
+        res = Result.__new__(Result)
+        res._h = _vp()
+        rc = _lib().sp_starphase_call(self._h, C.byref(inp), C.byref(res._h))
+        if rc != SP_OK:
+            raise StarphaseError(rc, _d(_lib().sp_starphase_last_error(self._h)))
+        return res
+
+    def warnings(self):
+        return _d(_lib().sp_starphase_warnings(self._h))
+
+    def timing(self):
+        t = sp_starphase_timing()
+        _lib().sp_starphase_last_timing(self._h, C.byref(t))
+        return {k: getattr(t, k) for k, _ty in sp_starphase_timing._fields_}
+
+
+def cli_path():
+    """the `starphase_hip` executable the csrc Makefile builds next to the library"""
+    import os
+    return os.path.join(os.path.dirname(ffi.lib_path()), "starphase_hip")
+
+
+def cyp_diplotype_mappings(cdb, reads, cap=None, **overrides):
+    """sp_cyp_diplotype_mappings on a CypDb: (sp_cyp_call, [(read, read_start, read_end, consensus, index_label)])"""
+    pr = cdb.problem(**overrides)
+    call = ffi.sp_cyp_call()
+    n = C.c_uint64(0)
+    cap = cap if cap is not None else 64 * reads.n + 64
+    buf = (sp_cyp_read_mapping * max(1, cap))()
+    rc = _lib().sp_cyp_diplotype_mappings(cdb.ctx._h, C.byref(pr), reads._h, C.byref(call), None, 0, None, buf, cap, C.byref(n))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_cyp_diplotype_mappings")
+    return call, [(m.read, m.read_start, m.read_end, m.consensus, m.index_label.decode()) for m in buf[:n.value]]
