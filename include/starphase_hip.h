@@ -300,6 +300,13 @@ int32_t sp_hla_realign_seeded_audit(sp_ctx* ctx, const sp_hla_db* db, const sp_s
 int32_t sp_hla_realign_reads(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads,
                              sp_hla_realign* out /* n_reads */,
                              uint32_t* cell_out /* optional n_reads*n_alleles: (nm<<16 | span) or 0xFFFFFFFF */);
+/* sp_hla_realign_reads in seeded mode (k1_best_n > 0, else SP_ERR_INVALID_ARG) that also names every read it drops on the reverse strand: out[] is what
+ * sp_hla_realign_reads writes for the same set; rev[r] is, for a record with status 2 and best_allele -1, the accepted reverse-strand mapping of
+ * realign_record's loop (src/hla/realigner.rs:124-146,178-193: penalty <= 0.5, edit fraction <= 0.03, the lowest edit fraction wins) -- the indexed
+ * allele, its length, NM and the target span (unmapped = t_len - (t_end - t_start)); allele -1 for every other read.  It comes out of the same launches
+ * as the records (the pick stage writes it), so it costs no per-read audit. */
+typedef struct { int32_t allele, t_len, nm, t_start, t_end, reserved_; } sp_hla_rev_hit;
+int32_t sp_hla_realign_reads_rev(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, sp_hla_realign* out /* n_reads */, sp_hla_rev_hit* rev /* n_reads */);
 
 /* ------------------------------------------------------------------ K2: consensus -> every allele of a gene
  * Replaces score_read's allele loop + HlaProcessedMatch (src/hla/caller.rs:1411-1510,
@@ -529,6 +536,12 @@ int32_t sp_cyp_alleles_json(const sp_cyp_problem* problem, const sp_cyp_call* ca
 typedef struct { uint32_t read, consensus; uint64_t read_start, read_end; char index_label[64]; } sp_cyp_read_mapping;
 int32_t sp_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* problem, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
                                   sp_cyp_region_variants* region_variants /* optional */, sp_cyp_read_mapping* mappings, uint64_t cap, uint64_t* n_mappings);
+/* sp_cyp_diplotype_cohort that also hands out, per sample, what sp_cyp_diplotype_mappings gives for it: region_variants[i] (optional; n_samples
+ * entries, each with its own state block) and the read mappings of sample i at mappings[mapping_off[i] .. mapping_off[i + 1]) (mapping_off: n_samples + 1
+ * entries, always filled; SP_ERR_CAPACITY when mapping_off[n_samples] > cap: the calls are complete, call again with more room for the list). */
+int32_t sp_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* problem, uint32_t n_samples, const sp_seqset* const* reads, sp_cyp_call* calls,
+                                         char* consensus, uint32_t cons_cap, sp_cyp_region_variants* region_variants /* optional */,
+                                         sp_cyp_read_mapping* mappings, uint64_t cap, uint64_t* mapping_off, int32_t* sample_rc);
 
 /* ------------------------------------------------------------------ CYP2D6 templates and typing tables
  * Replaces generate_cyp_hybrids (src/cyp2d6/definitions.rs:346-464), LoadedVariants::load_variant_database
@@ -808,6 +821,11 @@ int32_t sp_hla_diplotype_genes(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_gene
 int32_t sp_hla_diplotype_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
                                 const sp_seqset* reads, const sp_hla_realign* realign, const sp_hla_call_config* cfgs, sp_hla_call* calls,
                                 char* cons, uint32_t cap, uint8_t* is_cons1);
+/* the same with a configuration per (sample, gene): cfgs has n_samples * n_genes entries, sample-major like calls.  A cohort of files needs it:
+ * normalized_coverage (sp_hla_normalized_coverage over the sample's own HLA-DRB1 records) differs from sample to sample. */
+int32_t sp_hla_diplotype_cohort_samples(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
+                                        const sp_seqset* reads, const sp_hla_realign* realign, const sp_hla_call_config* cfgs, sp_hla_call* calls,
+                                        char* cons, uint32_t cap, uint8_t* is_cons1);
 
 /* ------------------------------------------------------------------ host-side decisions of the path (no device work)
  * Small scalar routines the reference evaluates between the kernels; kept behind the same ABI so a host can drop the whole
@@ -1158,6 +1176,34 @@ const char* sp_starphase_warnings(const sp_starphase* handle);      /* the warni
 /* where the last call spent its time (wall ms): whole call, BAM decode (host, both loci), variant genes, HLA lane, CYP2D6 lane */
 typedef struct { double call_ms, bam_decode_ms, variant_ms, hla_ms, cyp_ms; uint32_t n_hla_reads, n_cyp_reads; } sp_starphase_timing;
 int32_t sp_starphase_last_timing(const sp_starphase* handle, sp_starphase_timing* out);
+/* Many samples at once.  out[i] (sp_result_free) is what sp_starphase_call(handle, &inputs[i], ...) returns on the same handle: the same result
+ * bytes, the same PharmCAT TSV and, when debug_folders[i] names a folder, the same hla_debug.json and cyp2d6_alleles.json as a single call with that
+ * debug folder -- for every max_group and decode_threads, whichever samples share a group.  debug_folders: NULL, or n entries (NULL = none for that
+ * sample); a handle created with settings.debug_folder needs them (else SP_ERR_INVALID_ARG: every sample would write the one folder).
+ * Per group of max_group samples (default 64): the host decodes every sample's BAMs and VCFs on decode_threads workers (default min(16, hardware
+ * threads)) -- while the device works on the group before --; the variant genes of all samples go through one sp_variant_solve_batch; the HLA reads
+ * of all samples through one sp_hla_realign_reads_rev and one sp_hla_diplotype_cohort_samples; CYP2D6 through one sp_cyp_diplotype_cohort_mappings on
+ * the handle's second context and a host thread of its own (settings.sequential: after the others).  Device memory is bounded by the group, not n.
+ * A sample that fails gets out[i] = NULL, sample_rc[i] (optional) and its text in sp_starphase_sample_error(handle, i); the others are still typed
+ * (a pass the group shares that fails as a whole is run again sample by sample, so each failure and its text are those of the sample's single call).
+ * Returns the first status that is not SP_OK (sp_starphase_last_error names that sample).  Warnings are kept per sample. */
+typedef struct {
+    uint32_t max_group;                 /* samples per device pass; 0 = 64 */
+    uint32_t decode_threads;            /* host BAM / VCF decode workers; 0 = min(16, hardware threads) */
+    uint32_t reserved_[6];
+} sp_batch_options;
+int32_t sp_starphase_call_batch(sp_starphase* handle, uint32_t n, const sp_sample_inputs* inputs, const char* const* debug_folders /* optional */,
+                                const sp_batch_options* opts /* NULL = defaults */, sp_result** out /* n */, int32_t* sample_rc /* n, optional */);
+const char* sp_starphase_sample_error(const sp_starphase* handle, uint32_t i);      /* of the last batch; valid until the next call */
+const char* sp_starphase_sample_warnings(const sp_starphase* handle, uint32_t i);
+/* where the last batch spent its time (wall ms): the whole call; host decode (per group, the pool's wall time); variant genes, HLA lane, CYP2D6 lane
+ * (its own thread, beside the two) and packaging summed over the groups; the counts */
+typedef struct {
+    double wall_ms, decode_ms, variant_ms, hla_ms, cyp_ms, package_ms;
+    uint32_t n_samples, n_groups, n_failed, reserved_;
+    uint64_t n_hla_reads, n_cyp_reads;
+} sp_starphase_batch_timing;
+int32_t sp_starphase_last_batch_timing(const sp_starphase* handle, sp_starphase_batch_timing* out);
 
 #ifdef __cplusplus
 }

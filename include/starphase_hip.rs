@@ -139,6 +139,15 @@ pub struct sp_k1_seed_hit {
     pub primary: i32,
 }
 #[repr(C)]
+pub struct sp_hla_rev_hit {
+    pub allele: i32,
+    pub t_len: i32,
+    pub nm: i32,
+    pub t_start: i32,
+    pub t_end: i32,
+    pub reserved_: i32,
+}
+#[repr(C)]
 pub struct sp_hla_best {
     pub best_allele: i32,
     pub n_scored: i32,
@@ -627,6 +636,27 @@ pub struct sp_starphase_timing {
     pub n_hla_reads: u32,
     pub n_cyp_reads: u32,
 }
+#[repr(C)]
+pub struct sp_batch_options {
+    pub max_group: u32,
+    pub decode_threads: u32,
+    pub reserved_: [u32; 6],
+}
+#[repr(C)]
+pub struct sp_starphase_batch_timing {
+    pub wall_ms: f64,
+    pub decode_ms: f64,
+    pub variant_ms: f64,
+    pub hla_ms: f64,
+    pub cyp_ms: f64,
+    pub package_ms: f64,
+    pub n_samples: u32,
+    pub n_groups: u32,
+    pub n_failed: u32,
+    pub reserved_: u32,
+    pub n_hla_reads: u64,
+    pub n_cyp_reads: u64,
+}
 
 #[repr(C)] pub struct sp_bam { _private: [u8; 0] }
 #[repr(C)] pub struct sp_ctx { _private: [u8; 0] }
@@ -672,6 +702,7 @@ extern "C" {
     pub fn sp_seqset_sketch(ctx: *mut sp_ctx, set: *const sp_seqset, idx: u32, hash: *mut u64, end_pos: *mut i32, strand: *mut u8, cap: u32, n_out: *mut u32) -> i32;
     pub fn sp_hla_realign_seeded_audit(ctx: *mut sp_ctx, db: *const sp_hla_db, reads: *const sp_seqset, read: u32, chains: *mut i32, chain_cap: u32, n_chains: *mut u32, hits: *mut sp_k1_seed_hit, n_hits: *mut u32, pick: *mut i32, counters: *mut u64) -> i32;
     pub fn sp_hla_realign_reads(ctx: *mut sp_ctx, db: *const sp_hla_db, reads: *const sp_seqset, out: *mut sp_hla_realign, cell_out: *mut u32) -> i32;
+    pub fn sp_hla_realign_reads_rev(ctx: *mut sp_ctx, db: *const sp_hla_db, reads: *const sp_seqset, out: *mut sp_hla_realign, rev: *mut sp_hla_rev_hit) -> i32;
     pub fn sp_hla_score_consensus(ctx: *mut sp_ctx, db: *const sp_hla_db, gene: u32, cons_dna: *const c_char, cons_dna_len: u32, cons_cdna: *const c_char, cons_cdna_len: u32, require_dna: i32, disable_cdna: i32, best: *mut sp_hla_best, stats: *mut i32) -> i32;
     pub fn sp_hla_score_consensus_batch(ctx: *mut sp_ctx, db: *const sp_hla_db, n: u32, genes: *const u32, cons_dna: *const *const c_char, cons_dna_len: *const u32, cons_cdna: *const *const c_char, cons_cdna_len: *const u32, require_dna: i32, disable_cdna: i32, best: *mut sp_hla_best) -> i32;
     pub fn sp_hla_type_consensus(ctx: *mut sp_ctx, db: *const sp_hla_db, gene: u32, consensus_fwd: *const c_char, consensus_len: u32, require_dna: i32, disable_cdna: i32, best: *mut sp_hla_best, stats: *mut i32, cdna_out: *mut c_char, cdna_cap: u32, cdna_len: *mut u32) -> i32;
@@ -686,6 +717,7 @@ extern "C" {
     pub fn sp_cyp_diplotype_detailed(ctx: *mut sp_ctx, problem: *const sp_cyp_problem, reads: *const sp_seqset, call: *mut sp_cyp_call, consensus: *mut c_char, cons_cap: u32, region_variants: *mut sp_cyp_region_variants) -> i32;
     pub fn sp_cyp_alleles_json(problem: *const sp_cyp_problem, call: *const sp_cyp_call, region_variants: *const sp_cyp_region_variants, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
     pub fn sp_cyp_diplotype_mappings(ctx: *mut sp_ctx, problem: *const sp_cyp_problem, reads: *const sp_seqset, call: *mut sp_cyp_call, consensus: *mut c_char, cons_cap: u32, region_variants: *mut sp_cyp_region_variants, mappings: *mut sp_cyp_read_mapping, cap: u64, n_mappings: *mut u64) -> i32;
+    pub fn sp_cyp_diplotype_cohort_mappings(ctx: *mut sp_ctx, problem: *const sp_cyp_problem, n_samples: u32, reads: *const *const sp_seqset, calls: *mut sp_cyp_call, consensus: *mut c_char, cons_cap: u32, region_variants: *mut sp_cyp_region_variants, mappings: *mut sp_cyp_read_mapping, cap: u64, mapping_off: *mut u64, sample_rc: *mut i32) -> i32;
     pub fn sp_cyp_db_create(ctx: *mut sp_ctx, locus: *const sp_cyp_locus, gene_def: *const sp_cyp_gene_def, config: *const sp_cyp_config, out: *mut *mut sp_cyp_db) -> i32;
     pub fn sp_cyp_db_free(db: *mut sp_cyp_db);
     pub fn sp_cyp_db_info(db: *const sp_cyp_db, stats: *mut sp_cyp_db_stats) -> i32;
@@ -707,6 +739,7 @@ extern "C" {
     pub fn sp_hla_diplotype_gene(ctx: *mut sp_ctx, db: *const sp_hla_db, gene: u32, reads: *const sp_seqset, realign: *const sp_hla_realign, cfg: *const sp_hla_call_config, call: *mut sp_hla_call, cons1: *mut c_char, cons2: *mut c_char, cap: u32, is_cons1: *mut u8) -> i32;
     pub fn sp_hla_diplotype_genes(ctx: *mut sp_ctx, db: *const sp_hla_db, n_genes: u32, genes: *const u32, reads: *const sp_seqset, realign: *const sp_hla_realign, cfgs: *const sp_hla_call_config, calls: *mut sp_hla_call, cons: *mut c_char, cap: u32, is_cons1: *mut u8) -> i32;
     pub fn sp_hla_diplotype_cohort(ctx: *mut sp_ctx, db: *const sp_hla_db, n_samples: u32, read_sample: *const u32, n_genes: u32, genes: *const u32, reads: *const sp_seqset, realign: *const sp_hla_realign, cfgs: *const sp_hla_call_config, calls: *mut sp_hla_call, cons: *mut c_char, cap: u32, is_cons1: *mut u8) -> i32;
+    pub fn sp_hla_diplotype_cohort_samples(ctx: *mut sp_ctx, db: *const sp_hla_db, n_samples: u32, read_sample: *const u32, n_genes: u32, genes: *const u32, reads: *const sp_seqset, realign: *const sp_hla_realign, cfgs: *const sp_hla_call_config, calls: *mut sp_hla_call, cons: *mut c_char, cap: u32, is_cons1: *mut u8) -> i32;
     pub fn sp_hla_is_passing_dual(counts1: u64, counts2: u64, min_consensus_fraction: f64, expected_maf: f64, min_cdf: f64, maf_out: *mut f64, cdf_out: *mut f64) -> i32;
     pub fn sp_hla_is_hemizygous_better(scores1: *const i64, scores2: *const i64, is_consensus1: *const u8, n_reads: u32, is_dual: i32, dual_max_ed_delta: u64, normalized_coverage: f64, haploid_cost: *mut f64, diploid_cost: *mut f64) -> i32;
     pub fn sp_hla_normalized_coverage(realign: *const sp_hla_realign, n_reads: u32, normalizing_genes: *const u32, n_normalizing: u32, normalized_coverage: *mut f64) -> i32;
@@ -803,4 +836,8 @@ extern "C" {
     pub fn sp_starphase_call(handle: *mut sp_starphase, inputs: *const sp_sample_inputs, out: *mut *mut sp_result) -> i32;
     pub fn sp_starphase_warnings(handle: *const sp_starphase) -> *const c_char;
     pub fn sp_starphase_last_timing(handle: *const sp_starphase, out: *mut sp_starphase_timing) -> i32;
+    pub fn sp_starphase_call_batch(handle: *mut sp_starphase, n: u32, inputs: *const sp_sample_inputs, debug_folders: *const *const c_char, opts: *const sp_batch_options, out: *mut *mut sp_result, sample_rc: *mut i32) -> i32;
+    pub fn sp_starphase_sample_error(handle: *const sp_starphase, i: u32) -> *const c_char;
+    pub fn sp_starphase_sample_warnings(handle: *const sp_starphase, i: u32) -> *const c_char;
+    pub fn sp_starphase_last_batch_timing(handle: *const sp_starphase, out: *mut sp_starphase_batch_timing) -> i32;
 }

@@ -175,6 +175,9 @@ int32_t sp_struct_size(const char* name) {
     SP_SZ(sp_vcf_allele)
     SP_SZ(sp_vcf_deletion)
     SP_SZ(sp_mapping_stats)
+    SP_SZ(sp_hla_rev_hit)
+    SP_SZ(sp_batch_options)
+    SP_SZ(sp_starphase_batch_timing)
 #undef SP_SZ
     return -1;
 }

@@ -2150,8 +2150,10 @@ extern "C" int32_t sp_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* 
 // The CYP2D6 calls of several samples (one GPU's share of a cohort): each sample alone is a chain of small launches that wait for one another, so
 // GROUPS of samples are handed to the context and its helper streams (sp_ctx_set_option "hla_split_genes" / "cyp_cohort_streams"), one host thread
 // per stream for the length of the call, and a group goes through every stage that allows it together.  Every call is the call sp_cyp_diplotype makes.
-extern "C" int32_t sp_cyp_diplotype_cohort(sp_ctx* ctx, const sp_cyp_problem* pr, uint32_t n_samples, const sp_seqset* const* reads, sp_cyp_call* calls,
-                                           char* consensus, uint32_t cons_cap, int32_t* sample_rc) {
+// region_variants / mappings (optional, n_samples entries): what sp_cyp_diplotype_mappings hands out for the sample, filled by the same (a) / (c1) / (c2)
+int32_t spi_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, uint32_t n_samples, const sp_seqset* const* reads, sp_cyp_call* calls,
+                                          char* consensus, uint32_t cons_cap, sp_cyp_region_variants* region_variants,
+                                          std::vector<sp_cyp_read_mapping>* mappings, int32_t* sample_rc) {
     if (!ctx) return SP_ERR_INVALID_ARG;
     if (!pr || (n_samples && (!reads || !calls))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_diplotype_cohort: null argument");
     for (uint32_t i = 0; i < n_samples; ++i) if (!reads[i]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_diplotype_cohort: null read set");
@@ -2191,9 +2193,10 @@ extern "C" int32_t sp_cyp_diplotype_cohort(sp_ctx* ctx, const sp_cyp_problem* pr
                     const uint32_t i = first + k;
                     where[i] = x;
                     mids[k].reset(new CypMid());
+                    if (mappings) { mappings[i].clear(); mids[k]->mappings = &mappings[i]; }
                     const std::string prefix = "cypc" + std::to_string(k);
                     if (searched && rc_regions != SP_OK) { rcs[i] = rc_regions; continue; }
-                    rcs[i] = cyp_part_a(c, pr, reads[i], &calls[i], nullptr, prefix.c_str(), *mids[k], searched ? &group_hits[k] : nullptr);
+                    rcs[i] = cyp_part_a(c, pr, reads[i], &calls[i], region_variants ? &region_variants[i] : nullptr, prefix.c_str(), *mids[k], searched ? &group_hits[k] : nullptr);
                     if (rcs[i] != SP_OK || mids[k]->finished) continue;
                     CypMid& m = *mids[k];
                     sp_priority_job J; J.problem = &m.pp; J.max_groups = SP_CYP_MAXCONS; J.cap = m.cap; J.n_groups = &m.n_groups; J.group_of = m.group_of.data(); J.cons = m.text.data(); J.status = SP_OK; J.gave_up = 0;
@@ -2220,7 +2223,7 @@ extern "C" int32_t sp_cyp_diplotype_cohort(sp_ctx* ctx, const sp_cyp_problem* pr
                     if (rc_all != SP_OK) { rcs[i] = rc_all; continue; }
                     calls[i].searches_gave_up = jobs[q].gave_up;
                     if (jobs[q].status != SP_OK) { rcs[i] = jobs[q].status; c->err = jobs[q].status == SP_ERR_CAPACITY ? "sp_consensus_priority: more groups than max_groups" : "sp_consensus_priority: more groups than reads"; continue; }
-                    rcs[i] = cyp_part_c1(c, pr, reads[i], nullptr, *mids[k], &types, nullptr);
+                    rcs[i] = cyp_part_c1(c, pr, reads[i], region_variants ? &region_variants[i] : nullptr, *mids[k], &types, nullptr);
                     if (rcs[i] == SP_OK) in_play[k] = mids[k].get();
                 }
                 std::vector<std::vector<uint64_t>> ed; std::vector<std::vector<double>> ov; std::vector<std::vector<uint8_t>> kept;
@@ -2251,10 +2254,33 @@ extern "C" int32_t sp_cyp_diplotype_cohort(sp_ctx* ctx, const sp_cyp_problem* pr
     for (int x = 1; x < n_parts; ++x) if (started[x]) beside[x].join();
     int32_t rc = SP_OK;
     for (uint32_t i = 0; i < n_samples; ++i) {
+        if (mappings && (rcs[i] != SP_OK || calls[i].status != 0)) mappings[i].clear();
         if (sample_rc) sample_rc[i] = rcs[i];
         if (rcs[i] != SP_OK && rc == SP_OK) { rc = rcs[i]; if (where[i] > 0) ctx->err = on[where[i]]->err; }
     }
     return rc;
+}
+
+extern "C" int32_t sp_cyp_diplotype_cohort(sp_ctx* ctx, const sp_cyp_problem* pr, uint32_t n_samples, const sp_seqset* const* reads, sp_cyp_call* calls,
+                                           char* consensus, uint32_t cons_cap, int32_t* sample_rc) {
+    return spi_cyp_diplotype_cohort_mappings(ctx, pr, n_samples, reads, calls, consensus, cons_cap, nullptr, nullptr, sample_rc);
+}
+
+extern "C" int32_t sp_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, uint32_t n_samples, const sp_seqset* const* reads, sp_cyp_call* calls,
+                                                    char* consensus, uint32_t cons_cap, sp_cyp_region_variants* region_variants, sp_cyp_read_mapping* mappings,
+                                                    uint64_t cap, uint64_t* mapping_off, int32_t* sample_rc) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (!mapping_off || (cap && !mappings)) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_diplotype_cohort_mappings: null argument");
+    std::vector<std::vector<sp_cyp_read_mapping>> per(n_samples);
+    const int32_t rc = spi_cyp_diplotype_cohort_mappings(ctx, pr, n_samples, reads, calls, consensus, cons_cap, region_variants, per.data(), sample_rc);
+    mapping_off[0] = 0;
+    for (uint32_t i = 0; i < n_samples; ++i) {
+        const uint64_t at = mapping_off[i];
+        for (uint64_t x = 0; x < per[i].size() && at + x < cap; ++x) mappings[at + x] = per[i][x];
+        mapping_off[i + 1] = at + per[i].size();
+    }
+    if (rc != SP_OK) return rc;
+    return mapping_off[n_samples] > cap ? sp_fail(ctx, SP_ERR_CAPACITY, "sp_cyp_diplotype_cohort_mappings: more read mappings than cap") : SP_OK;
 }
 
 // cyp2d6_alleles.json: DeeplotypeDebug (src/cyp2d6/debug.rs:10-70) written as save_json writes it (serde_json pretty print)

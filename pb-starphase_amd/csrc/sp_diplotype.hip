@@ -7,8 +7,12 @@
 // The CYP2D6 lane (BAM decode, upload, call) runs on a host thread of its own with the second context while the calling thread does the variant genes
 // and the HLA genes; every entry is built from its own lane's inputs only, and the entries are inserted in one fixed order at the end, so the result is
 // the same whichever way the lanes ran (settings.sequential = 1 runs them one after another).
+// sp_starphase_call_batch types groups of samples with the same pieces: per group one variant solve, one K1 pass (sp_hla_realign_reads_rev), one HLA
+// cohort call and one CYP2D6 cohort call, the host decode of the next group beside the device work of this one; every sample's entries are those
+// sp_starphase_call makes for it.
 #include "sp_internal.h"
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -94,6 +98,9 @@ struct GeneDetailsPtr {
 // one entry of the result, ready to be inserted: made on whichever lane computed it
 struct Entry { std::string gene; std::unique_ptr<GeneDetailsPtr> details; int32_t constructor = 0; };
 
+// the VCF records variant_lane fetches for a gene: +-50 bp around each of its variants; fetch = selected and with variants (or an SV)
+struct GeneWindow { bool fetch = false; uint64_t lo = 0, hi = 0; uint32_t n_variants = 0; };
+
 }  // namespace
 
 struct sp_starphase {
@@ -112,6 +119,7 @@ struct sp_starphase {
     // variant genes, in gene_entries key order
     struct VGene { std::string name, chrom, reference_allele, sv_chrom; bool has_sv = false; sp_variant_gene* g = nullptr; bool selected = true; };
     std::vector<VGene> vgenes;
+    std::vector<GeneWindow> win;                     // per vgenes entry, made once by sp_starphase_create
     // HLA: the selected hla_config genes
     sp_hla_db* hla = nullptr;
     struct HGene { std::string name, chrom; uint64_t start = 0, end = 0; bool absent_capable = false; };
@@ -122,6 +130,10 @@ struct sp_starphase {
     sp_cyp_db* cyp = nullptr; bool cyp_selected = false;
     std::string cyp_chrom; uint64_t cyp_start = 0, cyp_end = 0;     // extraction_region (src/cyp2d6/definitions.rs:72-99)
     std::string hla_err, cyp_err;                    // why a locus could not be set up (reported by the first call that needs it)
+    // sp_starphase_call_batch: per-sample errors and warnings of the last batch, its timing
+    std::vector<std::string> batch_err, batch_warn;
+    sp_starphase_batch_timing batch_timing{};
+    std::vector<char> batch_cons;                    // the HLA cohort's consensus texts (not read; kept across groups)
 
     bool selected(const std::string& gene) const {
         if (has_include && !include.count(gene)) return false;
@@ -275,164 +287,192 @@ int32_t package_gene(sp_starphase* h, sp_starphase::VGene& vg, const sp_variant_
     return SP_OK;
 }
 
-int32_t variant_lane(sp_starphase* h, const std::string& vcf_path, const std::string& sv_path, const std::string& sample_in, std::vector<Entry>& out) {
+// A variant problem points into its sp_variant_gene, which keeps only its last problem: a batch holds copies of every sample's problems for the one
+// solve, and rebuilds a sample's problems from the same records before it packages them (the build is host work and gives the same problem).
+struct OwnedProblem {
+    std::vector<uint8_t> hap_is_sv, hap_is_core, var_is_core; std::vector<int32_t> slot_off, alt_off, alt_var, obs_var, obs_gt, obs_sv_label; std::vector<int64_t> obs_ps;
+    sp_variant_problem p{};
+    void take(const sp_variant_problem& q) {
+        const size_t H = (size_t)std::max(0, q.n_haps), V = (size_t)std::max(0, q.n_vars), O = (size_t)std::max(0, q.n_obs);
+        slot_off.assign(q.slot_off, q.slot_off + H + 1);
+        const size_t S = (size_t)slot_off[H];
+        alt_off.assign(q.alt_off, q.alt_off + S + 1);
+        alt_var.assign(q.alt_var, q.alt_var + alt_off[S]);
+        hap_is_sv.assign(q.hap_is_sv, q.hap_is_sv + H); hap_is_core.assign(q.hap_is_core, q.hap_is_core + H);
+        var_is_core.assign(q.var_is_core, q.var_is_core + V);
+        obs_var.assign(q.obs_var, q.obs_var + O); obs_gt.assign(q.obs_gt, q.obs_gt + O); obs_ps.assign(q.obs_ps, q.obs_ps + O);
+        obs_sv_label.assign(q.obs_sv_label, q.obs_sv_label + O);
+        p = q;
+        p.hap_is_sv = hap_is_sv.data(); p.hap_is_core = hap_is_core.data(); p.slot_off = slot_off.data(); p.alt_off = alt_off.data(); p.alt_var = alt_var.data();
+        p.var_is_core = var_is_core.data(); p.obs_var = obs_var.data(); p.obs_gt = obs_gt.data(); p.obs_ps = obs_ps.data(); p.obs_sv_label = obs_sv_label.data();
+    }
+};
+
+// the VCF (+ SV VCF) records variant_lane fetches for every selected gene with variants, read on a decode worker.  fail_at: the vgenes index of the
+// first gene whose fetch failed (0 with fail_rc set: the files themselves); the genes before it still build their problems first, as in variant_lane.
+struct VcfGene { std::vector<uint64_t> pos; std::vector<std::string> ref, alt; std::vector<int32_t> gt; std::vector<int64_t> ps; std::vector<sp_vcf_deletion> dels; };
+struct VcfFetch { std::vector<VcfGene> genes; size_t fail_at = SIZE_MAX; int32_t fail_rc = SP_OK; std::string fail_err; };
+
+void vcf_fetch(sp_starphase* h, const std::vector<GeneWindow>& win, const std::string& vcf_path, const std::string& sv_path, const std::string& sample_in, VcfFetch& F) {
+    F.genes.assign(h->vgenes.size(), VcfGene());
+    auto fail = [&](size_t at, const std::string& m) { F.fail_at = at; F.fail_rc = SP_ERR_INVALID_ARG; F.fail_err = m; };
     sp_vcf* vcf = nullptr; sp_vcf* sv = nullptr;
     char e[512] = {0};
-    if (sp_vcf_open(vcf_path.c_str(), &vcf, e, sizeof e) != SP_OK) return h->fail(SP_ERR_INVALID_ARG, "Error while opening " + vcf_path + ": " + e);
+    if (sp_vcf_open(vcf_path.c_str(), &vcf, e, sizeof e) != SP_OK) return fail(0, "Error while opening " + vcf_path + ": " + e);
     std::unique_ptr<sp_vcf, void (*)(sp_vcf*)> vcf_guard(vcf, sp_vcf_free);
     std::string sample = sample_in;
     if (sample.empty()) {
         uint32_t n = 0; const char* const* names = nullptr;
-        if (sp_vcf_samples(vcf, &n, &names) != SP_OK || n == 0) return h->fail(SP_ERR_INVALID_ARG, "No samples found in VCF: " + vcf_path);
+        if (sp_vcf_samples(vcf, &n, &names) != SP_OK || n == 0) return fail(0, "No samples found in VCF: " + vcf_path);
         sample = names[0];
     }
     std::unique_ptr<sp_vcf, void (*)(sp_vcf*)> sv_guard(nullptr, sp_vcf_free);
     if (!sv_path.empty()) {
-        if (sp_vcf_open(sv_path.c_str(), &sv, e, sizeof e) != SP_OK) return h->fail(SP_ERR_INVALID_ARG, "Error while opening " + sv_path + ": " + e);
+        if (sp_vcf_open(sv_path.c_str(), &sv, e, sizeof e) != SP_OK) return fail(0, "Error while opening " + sv_path + ": " + e);
         sv_guard.reset(sv);
     }
-    std::vector<size_t> solved;                         // vgenes index of every gene that goes to the solver
-    std::vector<sp_variant_problem> probs;
-    std::vector<Entry> entries;
     for (size_t i = 0; i < h->vgenes.size(); ++i) {
-        sp_starphase::VGene& vg = h->vgenes[i];
-        if (!vg.selected) continue;
-        Entry en; en.gene = vg.name; en.details.reset(new GeneDetailsPtr());
-        sp_variant_gene_stats st{};
-        sp_variant_gene_info(vg.g, &st);
-        if (st.n_variants == 0 && !vg.has_sv) {         // "No variants found ..., returning default reference allele." (:94-105)
-            sp_gene_details_add_diplotype(en.details->d, vg.reference_allele.c_str(), vg.reference_allele.c_str());
-            sp_gene_details_add_simple_diplotype(en.details->d, vg.reference_allele.c_str(), vg.reference_allele.c_str());
-            en.constructor = SP_DETAILS_SUBALLELE_MATCH;
-            entries.push_back(std::move(en));
-            continue;
-        }
-        // the records around the gene's variants (load_vcf_variants fetches +-50 bp around each one)
-        uint64_t lo = UINT64_MAX, hi = 0;
-        for (uint32_t v = 0; v < st.n_variants; ++v) {
-            uint64_t pos; const char *r, *a, *nm, *dbsnp; int64_t vid; int32_t core;
-            sp_variant_gene_variant(vg.g, v, &pos, &r, &a, &nm, &dbsnp, &vid, &core);
-            lo = std::min(lo, pos > 50 ? pos - 50 : 0); hi = std::max(hi, pos + std::strlen(r) + 51);
-        }
+        const sp_starphase::VGene& vg = h->vgenes[i];
+        if (!win[i].fetch) continue;
+        VcfGene& G = F.genes[i];
         const sp_vcf_allele* alleles = nullptr; uint32_t n_alleles = 0;
-        if (st.n_variants && sp_vcf_alleles(vcf, sample.c_str(), vg.chrom.c_str(), lo, hi, &alleles, &n_alleles) != SP_OK)
-            return h->fail(SP_ERR_INVALID_ARG, vg.name + ": " + opt(sp_vcf_last_error(vcf)));
-        std::vector<sp_vcf_allele> al(alleles, alleles + n_alleles);
-        std::vector<std::string> keep;                   // the reader's strings live until its next fetch
-        keep.reserve(2 * al.size());
-        for (auto& a : al) { keep.push_back(a.ref); a.ref = keep.back().c_str(); keep.push_back(a.alt); a.alt = keep.back().c_str(); }
+        if (win[i].n_variants && sp_vcf_alleles(vcf, sample.c_str(), vg.chrom.c_str(), win[i].lo, win[i].hi, &alleles, &n_alleles) != SP_OK)
+            return fail(i, vg.name + ": " + opt(sp_vcf_last_error(vcf)));
+        for (uint32_t a = 0; a < n_alleles; ++a) {
+            G.pos.push_back(alleles[a].position); G.ref.push_back(opt(alleles[a].ref)); G.alt.push_back(opt(alleles[a].alt));
+            G.gt.push_back(alleles[a].gt); G.ps.push_back(alleles[a].ps);
+        }
         const sp_vcf_deletion* dels = nullptr; uint32_t n_dels = 0;
         if (sv && vg.has_sv && sp_vcf_deletions(sv, sample.c_str(), vg.sv_chrom.c_str(), 0, UINT64_MAX >> 2, &dels, &n_dels) != SP_OK)
-            return h->fail(SP_ERR_INVALID_ARG, vg.name + ": " + opt(sp_vcf_last_error(sv)));
-        sp_variant_problem p{};
-        if (sp_variant_gene_problem(vg.g, (uint32_t)al.size(), al.data(), n_dels, dels, h->s.max_sv_length, &p) != SP_OK)
-            return h->fail(SP_ERR_INVALID_ARG, vg.name + ": " + opt(sp_variant_gene_last_error(vg.g)));
-        probs.push_back(p); solved.push_back(i);
-        entries.push_back(std::move(en));
+            return fail(i, vg.name + ": " + opt(sp_vcf_last_error(sv)));
+        G.dels.assign(dels, dels + n_dels);
     }
-    // every gene's problem in one launch (K6); the problems point into their sp_variant_gene, which keeps its last problem
-    std::vector<sp_variant_result> res(probs.size());
-    std::vector<int32_t> rcs(probs.size(), SP_OK);
-    if (!probs.empty()) {
-        std::vector<const sp_variant_problem*> pp;
-        for (auto& p : probs) pp.push_back(&p);
-        const int32_t rc = sp_variant_solve_batch(h->ctx, (uint32_t)probs.size(), pp.data(), res.data(), rcs.data());
-        if (rc != SP_OK) return h->fail(rc, "sp_variant_solve_batch: " + opt(sp_last_error(h->ctx)));
-    }
-    size_t k = 0;
-    for (auto& en : entries) {
-        if (k < solved.size() && h->vgenes[solved[k]].name == en.gene) {
-            const int32_t rc = package_gene(h, h->vgenes[solved[k]], probs[k], res[k], en);
-            if (rc != SP_OK) return rc;
-            ++k;
+}
+
+int32_t vcf_problem(sp_starphase* h, size_t i, const VcfGene& G, sp_variant_problem& p) {
+    std::vector<sp_vcf_allele> al(G.pos.size());
+    for (size_t a = 0; a < al.size(); ++a) { al[a] = sp_vcf_allele{}; al[a].position = G.pos[a]; al[a].ref = G.ref[a].c_str(); al[a].alt = G.alt[a].c_str(); al[a].gt = G.gt[a]; al[a].ps = G.ps[a]; }
+    sp_starphase::VGene& vg = h->vgenes[i];
+    p = sp_variant_problem{};
+    if (sp_variant_gene_problem(vg.g, (uint32_t)al.size(), al.data(), (uint32_t)G.dels.size(), G.dels.data(), h->s.max_sv_length, &p) != SP_OK)
+        return h->fail(SP_ERR_INVALID_ARG, vg.name + ": " + opt(sp_variant_gene_last_error(vg.g)));
+    return SP_OK;
+}
+
+// one sample's variant genes, for sp_starphase_call and for each sample of a batch group
+struct VarSample {
+    bool has_vcf = false; std::string vcf, sv, sample;
+    VcfFetch vf;                                     // read by vcf_fetch (a decode worker, in a batch)
+    int32_t rc = SP_OK; std::string err;
+    std::vector<Entry> entries; std::vector<size_t> solved; std::vector<OwnedProblem> probs; size_t res0 = 0;
+};
+
+// call_diplotypes' gene loop (src/diplotyper.rs:94-204) for every sample of `group` whose VCF was read: each sample's problems, ONE
+// sp_variant_solve_batch over all of them, then the entries sample by sample.  A sample fails with what sp_starphase_call reports for it: when the
+// shared launch fails, each sample's problems are solved once more on their own, so a failure and its text belong to the sample that has it.
+void variant_samples(sp_starphase* h, const std::vector<VarSample*>& group) {
+    std::vector<const sp_variant_problem*> pp;
+    for (VarSample* b : group) {
+        if (!b->has_vcf || b->rc != SP_OK) continue;
+        for (size_t i = 0; i < h->vgenes.size() && b->rc == SP_OK; ++i) {
+            if (i >= b->vf.fail_at) { b->rc = b->vf.fail_rc; b->err = b->vf.fail_err; break; }
+            sp_starphase::VGene& vg = h->vgenes[i];
+            if (!vg.selected) continue;
+            Entry en; en.gene = vg.name; en.details.reset(new GeneDetailsPtr());
+            if (!h->win[i].fetch) {                     // "No variants found ..., returning default reference allele." (:94-105)
+                sp_gene_details_add_diplotype(en.details->d, vg.reference_allele.c_str(), vg.reference_allele.c_str());
+                sp_gene_details_add_simple_diplotype(en.details->d, vg.reference_allele.c_str(), vg.reference_allele.c_str());
+                en.constructor = SP_DETAILS_SUBALLELE_MATCH;
+                b->entries.push_back(std::move(en));
+                continue;
+            }
+            sp_variant_problem p{};
+            const int32_t rc = vcf_problem(h, i, b->vf.genes[i], p);
+            if (rc != SP_OK) { b->rc = rc; b->err = h->err; break; }
+            b->probs.emplace_back(); b->probs.back().take(p); b->solved.push_back(i);
+            b->entries.push_back(std::move(en));
         }
-        out.push_back(std::move(en));
     }
+    std::vector<VarSample*> solving;
+    for (VarSample* b : group) if (b->has_vcf && b->rc == SP_OK) { b->res0 = pp.size(); for (auto& q : b->probs) pp.push_back(&q.p); solving.push_back(b); }
+    std::vector<sp_variant_result> res(pp.size());
+    if (!pp.empty()) {
+        std::vector<int32_t> rcs(pp.size(), SP_OK);
+        const int32_t rc = sp_variant_solve_batch(h->ctx, (uint32_t)pp.size(), pp.data(), res.data(), rcs.data());
+        if (rc != SP_OK && solving.size() == 1) { solving[0]->rc = rc; solving[0]->err = "sp_variant_solve_batch: " + opt(sp_last_error(h->ctx)); }
+        else if (rc != SP_OK) {
+            for (VarSample* b : solving) {
+                const size_t n = b->probs.size();
+                if (n == 0) continue;
+                std::vector<int32_t> own(n, SP_OK);
+                const int32_t rb = sp_variant_solve_batch(h->ctx, (uint32_t)n, pp.data() + b->res0, res.data() + b->res0, own.data());
+                if (rb != SP_OK) { b->rc = rb; b->err = "sp_variant_solve_batch: " + opt(sp_last_error(h->ctx)); }
+            }
+        }
+    }
+    // the entries; a sample's problems are built once more first (the gene keeps only its last problem, which package_gene reads back)
+    for (VarSample* b : solving) {
+        if (b->rc != SP_OK) continue;
+        size_t k = 0;
+        for (auto& en : b->entries) {
+            if (k < b->solved.size() && h->vgenes[b->solved[k]].name == en.gene) {
+                sp_variant_problem p{};
+                int32_t rc = vcf_problem(h, b->solved[k], b->vf.genes[b->solved[k]], p);
+                if (rc == SP_OK) rc = package_gene(h, h->vgenes[b->solved[k]], p, res[b->res0 + k], en);
+                if (rc != SP_OK) { b->rc = rc; b->err = h->err; break; }
+                ++k;
+            }
+        }
+        b->probs.clear();
+    }
+}
+
+int32_t variant_lane(sp_starphase* h, const std::string& vcf_path, const std::string& sv_path, const std::string& sample_in, std::vector<Entry>& out) {
+    VarSample v; v.has_vcf = true;
+    vcf_fetch(h, h->win, vcf_path, sv_path, sample_in, v.vf);
+    variant_samples(h, {&v});
+    if (v.rc != SP_OK) return h->fail(v.rc, v.err);
+    for (auto& e : v.entries) out.push_back(std::move(e));
     return SP_OK;
 }
 
 // ---------------------------------------------------------------- HLA
-int32_t hla_lane(sp_starphase* h, const std::vector<std::string>& bams, std::vector<Entry>& out, double* decode_ms, uint32_t* n_reads_out) {
-    const size_t G = h->hgenes.size();
-    // the read loop (src/hla/caller.rs:540-596): genes in hla_config order, every BAM in the given order, a QNAME once
-    std::vector<Read4> reads; std::vector<uint32_t> searched;       // the gene whose region handed out read r
+// the read loop (src/hla/caller.rs:540-596): genes in hla_config order, every BAM in the given order, a QNAME once; searched[r] = the gene whose
+// region handed out read r
+int32_t hla_collect(sp_starphase* h, const std::vector<std::string>& bams, std::vector<Read4>& reads, std::vector<uint32_t>& searched, std::string& warnings,
+                    std::string& err) {
     std::set<std::string> seen;
-    auto t0 = std::chrono::steady_clock::now();
-    for (size_t g = 0; g < G; ++g) {
-        const size_t before = reads.size();
-        std::string err;
-        if (collect_reads(bams, h->hgenes[g].chrom, h->hgenes[g].start, h->hgenes[g].end, seen, reads, h->warnings, err) != SP_OK)
-            return h->fail(SP_ERR_INVALID_ARG, err);
+    for (size_t g = 0; g < h->hgenes.size(); ++g) {
+        if (collect_reads(bams, h->hgenes[g].chrom, h->hgenes[g].start, h->hgenes[g].end, seen, reads, warnings, err) != SP_OK) return SP_ERR_INVALID_ARG;
         searched.resize(reads.size(), (uint32_t)g);
-        (void)before;
     }
-    *decode_ms += ms_since(t0);
-    *n_reads_out = (uint32_t)reads.size();
-    // K1 on every read (each read is realigned by itself: any order gives the same records); the gene buckets are in QNAME order
-    const std::vector<uint32_t> order = qname_order(reads);
-    std::vector<sp_hla_realign> rec(reads.size());
-    std::vector<sp_hla_call> calls(G);
-    const uint32_t cap = 1 << 16;
-    std::vector<char> cons(G * 2 * (size_t)cap, 0);
-    std::vector<sp_hla_call_config> cfg(G);
+    return SP_OK;
+}
+
+// the call configuration of every gene of one sample, from the sample's records (NORMALIZING_HLA_GENES, src/hla/alleles.rs:49-59)
+void hla_configs(sp_starphase* h, const sp_hla_realign* rec, uint32_t n, sp_hla_call_config* cfg) {
+    const size_t G = h->hgenes.size();
+    std::vector<uint32_t> norm;
+    for (size_t g = 0; g < G; ++g) if (h->hgenes[g].name == "HLA-DRB1") norm.push_back((uint32_t)g);
     double coverage = -1.0;
-    if (!reads.empty()) {
-        sp_seqset* set = nullptr;
-        int32_t rc = upload_reads(h->ctx, reads, order, &set);
-        if (rc != SP_OK) return h->fail(rc, "read upload: " + opt(sp_last_error(h->ctx)));
-        std::unique_ptr<sp_seqset, void (*)(sp_seqset*)> guard(set, sp_seqset_free);
-        rc = sp_hla_realign_reads(h->ctx, h->hla, set, rec.data(), nullptr);
-        if (rc != SP_OK) return h->fail(rc, "sp_hla_realign_reads: " + opt(sp_last_error(h->ctx)));
-        // NORMALIZING_HLA_GENES (src/hla/alleles.rs:49-59)
-        std::vector<uint32_t> norm;
-        for (size_t g = 0; g < G; ++g) if (h->hgenes[g].name == "HLA-DRB1") norm.push_back((uint32_t)g);
-        sp_hla_normalized_coverage(rec.data(), (uint32_t)rec.size(), norm.data(), (uint32_t)norm.size(), &coverage);
-        for (size_t g = 0; g < G; ++g) {
-            sp_hla_call_config& c = cfg[g];
-            c.min_consensus_count = (int32_t)h->s.min_consensus_count; c.dual_max_ed_delta = (int32_t)h->s.dual_max_ed_delta;
-            c.min_consensus_fraction = h->s.min_consensus_fraction; c.expected_maf = h->s.expected_maf; c.min_cdf = h->s.min_cdf_prob;
-            c.require_dna = h->s.hla_require_dna; c.disable_cdna = h->s.disable_cdna_scoring; c.absent_capable = h->hgenes[g].absent_capable;
-            c.normalized_coverage = coverage;
-        }
-        std::vector<uint32_t> genes(G);
-        for (size_t g = 0; g < G; ++g) genes[g] = (uint32_t)g;
-        rc = sp_hla_diplotype_genes(h->ctx, h->hla, (uint32_t)G, genes.data(), set, rec.data(), cfg.data(), calls.data(), cons.data(), cap, nullptr);
-        if (rc != SP_OK) return h->fail(rc, "sp_hla_diplotype_genes: " + opt(sp_last_error(h->ctx)));
-    } else {
-        for (auto& c : calls) { std::memset(&c, 0, sizeof c); c.status = 1; }
+    sp_hla_normalized_coverage(rec, n, norm.data(), (uint32_t)norm.size(), &coverage);
+    for (size_t g = 0; g < G; ++g) {
+        sp_hla_call_config& c = cfg[g];
+        c = sp_hla_call_config{};
+        c.min_consensus_count = (int32_t)h->s.min_consensus_count; c.dual_max_ed_delta = (int32_t)h->s.dual_max_ed_delta;
+        c.min_consensus_fraction = h->s.min_consensus_fraction; c.expected_maf = h->s.expected_maf; c.min_cdf = h->s.min_cdf_prob;
+        c.require_dna = h->s.hla_require_dna; c.disable_cdna = h->s.disable_cdna_scoring; c.absent_capable = h->hgenes[g].absent_capable;
+        c.normalized_coverage = coverage;
     }
-    // a read whose accepted mapping is on the reverse strand (status 2): the reference names that mapping's allele and reports its stats
-    // (src/hla/realigner.rs:178-193).  The seeded record carries no allele for it, so those reads alone are mapped again through the audit entry,
-    // which hands out the mappings and the accepted one; the same acceptance rule (:124-146) picks it out of them.
-    struct RevHit { int32_t allele = -1; uint64_t t_len = 0, nm = 0, unmapped = 0; };
-    std::map<uint32_t, RevHit> rev;                                  // by position in QNAME order
-    {
-        std::vector<uint32_t> rev_pos, sub;
-        for (uint32_t k = 0; k < rec.size(); ++k) if (rec[k].status == 2 && rec[k].best_allele < 0) { rev_pos.push_back(k); sub.push_back(order[k]); }
-        if (!rev_pos.empty()) {
-            sp_seqset* set2 = nullptr;
-            int32_t rc = upload_reads(h->ctx, reads, sub, &set2);
-            if (rc != SP_OK) return h->fail(rc, "read upload: " + opt(sp_last_error(h->ctx)));
-            std::unique_ptr<sp_seqset, void (*)(sp_seqset*)> guard2(set2, sp_seqset_free);
-            std::vector<int32_t> chains(10 * 256);
-            for (uint32_t i = 0; i < rev_pos.size(); ++i) {
-                sp_k1_seed_hit hits[SP_K1_SEL]; uint32_t n_chains = 0, n_hits = 0; int32_t pick = -1; uint64_t counters[4];
-                rc = sp_hla_realign_seeded_audit(h->ctx, h->hla, set2, i, chains.data(), 256, &n_chains, hits, &n_hits, &pick, counters);
-                if (rc != SP_OK) return h->fail(rc, "sp_hla_realign_seeded_audit: " + opt(sp_last_error(h->ctx)));
-                double best = 1.0; int b = -1;
-                for (uint32_t x = 0; x < std::min<uint32_t>(n_hits, SP_K1_SEL); ++x) {
-                    const int tl = hits[x].t_len, um = tl - (hits[x].t_end - hits[x].t_start), nm = hits[x].nm;
-                    if (tl <= 0 || tl - um <= 0) continue;
-                    const double pen = std::max(0.1, (double)(nm + um)) / tl, ed = std::max(0.1, (double)nm) / (tl - um);
-                    if (pen <= 0.5 && ed <= 0.03 && ed < best) { best = ed; b = (int)x; }
-                }
-                if (b >= 0 && hits[b].rev && hits[b].allele >= 0) {
-                    const sp_k1_seed_hit& q = hits[b];
-                    rev[rev_pos[i]] = RevHit{q.allele, (uint64_t)q.t_len, (uint64_t)q.nm, (uint64_t)(q.t_len - (q.t_end - q.t_start))};
-                }
-            }
-        }
-    }
+}
+
+struct RevHit { int32_t allele = -1; uint64_t t_len = 0, nm = 0, unmapped = 0; };
+
+// the HLA entries of one sample: PgxMappingDetails of every read, the diplotypes, hla_debug.json.  rec / rev: by position in QNAME order
+int32_t hla_package(sp_starphase* h, const std::vector<Read4>& reads, const std::vector<uint32_t>& searched, const std::vector<uint32_t>& order,
+                    const sp_hla_realign* rec, const std::map<uint32_t, RevHit>& rev, const sp_hla_call* calls, const std::string& debug_folder,
+                    std::vector<Entry>& out, std::string& err) {
+    const size_t G = h->hgenes.size();
     // PgxMappingDetails of every read, in the order the loop met them, in the bucket of its gene (realigned) or of the gene searched (ignored)
     std::vector<std::unique_ptr<GeneDetailsPtr>> det(G);
     for (auto& d : det) d.reset(new GeneDetailsPtr());
@@ -472,7 +512,7 @@ int32_t hla_lane(sp_starphase* h, const std::vector<std::string>& bams, std::vec
         out.push_back(std::move(en));
     }
     // hla_debug.json: the DualPassingStats of every gene that had reads (src/hla/caller.rs:1042-1048)
-    if (!h->debug_folder.empty()) {
+    if (!debug_folder.empty()) {
         sp_hla_debug* dbg = nullptr;
         sp_hla_debug_create(&dbg);
         for (size_t g = 0; g < G; ++g) {
@@ -486,12 +526,81 @@ int32_t hla_lane(sp_starphase* h, const std::vector<std::string>& bams, std::vec
             }
             sp_hla_debug_add_dual_stats(dbg, h->hgenes[g].name.c_str(), &calls[g]);
         }
-        const std::string path = h->debug_folder + "/hla_debug.json";
+        const std::string path = debug_folder + "/hla_debug.json";
         const int32_t rc = sp_hla_debug_save(dbg, path.c_str());
         sp_hla_debug_free(dbg);
-        if (rc != SP_OK) return h->fail(rc, "Error while writing " + path);
+        if (rc != SP_OK) { err = "Error while writing " + path; return rc; }
     }
     return SP_OK;
+}
+
+int32_t hla_lane(sp_starphase* h, const std::vector<std::string>& bams, std::vector<Entry>& out, double* decode_ms, uint32_t* n_reads_out) {
+    const size_t G = h->hgenes.size();
+    std::vector<Read4> reads; std::vector<uint32_t> searched;
+    auto t0 = std::chrono::steady_clock::now();
+    {
+        std::string err;
+        if (hla_collect(h, bams, reads, searched, h->warnings, err) != SP_OK) return h->fail(SP_ERR_INVALID_ARG, err);
+    }
+    *decode_ms += ms_since(t0);
+    *n_reads_out = (uint32_t)reads.size();
+    // K1 on every read (each read is realigned by itself: any order gives the same records); the gene buckets are in QNAME order
+    const std::vector<uint32_t> order = qname_order(reads);
+    std::vector<sp_hla_realign> rec(reads.size());
+    std::vector<sp_hla_call> calls(G);
+    const uint32_t cap = 1 << 16;
+    std::vector<char> cons(G * 2 * (size_t)cap, 0);
+    std::vector<sp_hla_call_config> cfg(G);
+    if (!reads.empty()) {
+        sp_seqset* set = nullptr;
+        int32_t rc = upload_reads(h->ctx, reads, order, &set);
+        if (rc != SP_OK) return h->fail(rc, "read upload: " + opt(sp_last_error(h->ctx)));
+        std::unique_ptr<sp_seqset, void (*)(sp_seqset*)> guard(set, sp_seqset_free);
+        rc = sp_hla_realign_reads(h->ctx, h->hla, set, rec.data(), nullptr);
+        if (rc != SP_OK) return h->fail(rc, "sp_hla_realign_reads: " + opt(sp_last_error(h->ctx)));
+        hla_configs(h, rec.data(), (uint32_t)rec.size(), cfg.data());
+        std::vector<uint32_t> genes(G);
+        for (size_t g = 0; g < G; ++g) genes[g] = (uint32_t)g;
+        rc = sp_hla_diplotype_genes(h->ctx, h->hla, (uint32_t)G, genes.data(), set, rec.data(), cfg.data(), calls.data(), cons.data(), cap, nullptr);
+        if (rc != SP_OK) return h->fail(rc, "sp_hla_diplotype_genes: " + opt(sp_last_error(h->ctx)));
+    } else {
+        for (auto& c : calls) { std::memset(&c, 0, sizeof c); c.status = 1; }
+    }
+    // a read whose accepted mapping is on the reverse strand (status 2): the reference names that mapping's allele and reports its stats
+    // (src/hla/realigner.rs:178-193).  The seeded record carries no allele for it, so those reads alone are mapped again through the audit entry,
+    // which hands out the mappings and the accepted one; the same acceptance rule (:124-146) picks it out of them.
+    // (sp_starphase_call_batch takes the same mappings from sp_hla_realign_reads_rev instead.)
+    std::map<uint32_t, RevHit> rev;                                  // by position in QNAME order
+    {
+        std::vector<uint32_t> rev_pos, sub;
+        for (uint32_t k = 0; k < rec.size(); ++k) if (rec[k].status == 2 && rec[k].best_allele < 0) { rev_pos.push_back(k); sub.push_back(order[k]); }
+        if (!rev_pos.empty()) {
+            sp_seqset* set2 = nullptr;
+            int32_t rc = upload_reads(h->ctx, reads, sub, &set2);
+            if (rc != SP_OK) return h->fail(rc, "read upload: " + opt(sp_last_error(h->ctx)));
+            std::unique_ptr<sp_seqset, void (*)(sp_seqset*)> guard2(set2, sp_seqset_free);
+            std::vector<int32_t> chains(10 * 256);
+            for (uint32_t i = 0; i < rev_pos.size(); ++i) {
+                sp_k1_seed_hit hits[SP_K1_SEL]; uint32_t n_chains = 0, n_hits = 0; int32_t pick = -1; uint64_t counters[4];
+                rc = sp_hla_realign_seeded_audit(h->ctx, h->hla, set2, i, chains.data(), 256, &n_chains, hits, &n_hits, &pick, counters);
+                if (rc != SP_OK) return h->fail(rc, "sp_hla_realign_seeded_audit: " + opt(sp_last_error(h->ctx)));
+                double best = 1.0; int b = -1;
+                for (uint32_t x = 0; x < std::min<uint32_t>(n_hits, SP_K1_SEL); ++x) {
+                    const int tl = hits[x].t_len, um = tl - (hits[x].t_end - hits[x].t_start), nm = hits[x].nm;
+                    if (tl <= 0 || tl - um <= 0) continue;
+                    const double pen = std::max(0.1, (double)(nm + um)) / tl, ed = std::max(0.1, (double)nm) / (tl - um);
+                    if (pen <= 0.5 && ed <= 0.03 && ed < best) { best = ed; b = (int)x; }
+                }
+                if (b >= 0 && hits[b].rev && hits[b].allele >= 0) {
+                    const sp_k1_seed_hit& q = hits[b];
+                    rev[rev_pos[i]] = RevHit{q.allele, (uint64_t)q.t_len, (uint64_t)q.nm, (uint64_t)(q.t_len - (q.t_end - q.t_start))};
+                }
+            }
+        }
+    }
+    std::string err;
+    const int32_t rc = hla_package(h, reads, searched, order, rec.data(), rev, calls.data(), h->debug_folder, out, err);
+    return rc != SP_OK ? h->fail(rc, err) : SP_OK;
 }
 
 // ---------------------------------------------------------------- CYP2D6
@@ -499,6 +608,42 @@ struct CypLane {
     int32_t rc = SP_OK; std::string err, warnings;
     Entry entry; double decode_ms = 0, ms = 0; uint32_t n_reads = 0;
 };
+
+void cyp_problem(sp_starphase* h, sp_cyp_problem& pr) {
+    sp_cyp_db_problem(h->cyp, &pr);
+    pr.min_consensus_count = (int32_t)h->s.min_consensus_count; pr.dual_max_ed_delta = (int32_t)h->s.dual_max_ed_delta;
+    pr.min_consensus_fraction = h->s.min_consensus_fraction; pr.infer_connections = h->s.infer_connections; pr.normalize_d6_only = h->s.normalize_d6_only;
+}
+
+// the CYP2D6 entry of a sample whose reads were typed: the call, multi_mapping_details, cyp2d6_alleles.json
+void cyp_package(sp_starphase* h, const sp_cyp_problem& pr, const sp_cyp_call& call, const sp_cyp_region_variants& rv, const std::vector<sp_cyp_read_mapping>& mappings,
+                 const std::vector<Read4>& reads, const std::vector<uint32_t>& order, const std::string& debug_folder, CypLane* L) {
+    sp_gene_details* d = L->entry.details->d;
+    if (call.status == 16 || call.status == 17 || call.status == 18) {              // CallerError -> PgxGeneDetails::no_match() (src/diplotyper.rs:316-327)
+        L->entry.constructor = SP_DETAILS_NO_MATCH;
+    } else if (call.status == 1) {
+        sp_gene_details_add_diplotype(d, "NO_READS", "NO_READS");
+    } else if (call.status != 0) {
+        L->rc = SP_ERR_CHAIN_COLLAPSE; L->err = "CYP2D6: chain collapse"; return;
+    } else {
+        sp_gene_details_add_diplotype(d, call.hap1, call.hap2);
+        sp_gene_details_add_simple_diplotype(d, call.core1, call.core2);
+        sp_gene_details_add_diplotype_only(d, call.deep1, call.deep2);
+        for (const sp_cyp_read_mapping& m : mappings)                               // multi_mapping_details (src/cyp2d6/caller.rs:541-565)
+            sp_gene_details_add_multi_mapping(d, reads[order[m.read]].qname.c_str(), m.read_start, m.read_end, m.consensus, m.index_label);
+        if (!debug_folder.empty()) {
+            uint64_t need = 0;
+            sp_cyp_alleles_json(&pr, &call, &rv, nullptr, 0, &need);
+            std::string text(need, '\0');
+            if (sp_cyp_alleles_json(&pr, &call, &rv, &text[0], need, &need) != SP_OK) { L->rc = SP_ERR_INVALID_ARG; L->err = "cyp2d6_alleles.json"; return; }
+            text.resize(std::strlen(text.c_str()));
+            const std::string path = debug_folder + "/cyp2d6_alleles.json";
+            FILE* f = std::fopen(path.c_str(), "wb");
+            if (!f || std::fwrite(text.data(), 1, text.size(), f) != text.size()) { if (f) std::fclose(f); L->rc = SP_ERR_INVALID_ARG; L->err = "Error while writing " + path; return; }
+            std::fclose(f);
+        }
+    }
+}
 
 void cyp_lane(sp_starphase* h, const std::vector<std::string>& bams, CypLane* L) {
     auto t_lane = std::chrono::steady_clock::now();
@@ -516,9 +661,7 @@ void cyp_lane(sp_starphase* h, const std::vector<std::string>& bams, CypLane* L)
         return;
     }
     sp_cyp_problem pr{};
-    sp_cyp_db_problem(h->cyp, &pr);
-    pr.min_consensus_count = (int32_t)h->s.min_consensus_count; pr.dual_max_ed_delta = (int32_t)h->s.dual_max_ed_delta;
-    pr.min_consensus_fraction = h->s.min_consensus_fraction; pr.infer_connections = h->s.infer_connections; pr.normalize_d6_only = h->s.normalize_d6_only;
+    cyp_problem(h, pr);
     sp_seqset* set = nullptr;
     const std::vector<uint32_t> order = qname_order(reads);                        // read_collection is a BTreeMap: QNAME order
     int32_t rc = upload_reads(h->ctx2, reads, order, &set);
@@ -530,31 +673,159 @@ void cyp_lane(sp_starphase* h, const std::vector<std::string>& bams, CypLane* L)
     std::vector<sp_cyp_read_mapping> mappings;
     rc = spi_cyp_diplotype_mappings(h->ctx2, &pr, set, &call, nullptr, 0, &rv, &mappings);
     if (rc != SP_OK) { L->rc = rc; L->err = "sp_cyp_diplotype: " + opt(sp_last_error(h->ctx2)); return; }
-    if (call.status == 16 || call.status == 17 || call.status == 18) {              // CallerError -> PgxGeneDetails::no_match() (src/diplotyper.rs:316-327)
-        L->entry.constructor = SP_DETAILS_NO_MATCH;
-    } else if (call.status == 1) {
-        sp_gene_details_add_diplotype(d, "NO_READS", "NO_READS");
-    } else if (call.status != 0) {
-        L->rc = SP_ERR_CHAIN_COLLAPSE; L->err = "CYP2D6: chain collapse"; return;
-    } else {
-        sp_gene_details_add_diplotype(d, call.hap1, call.hap2);
-        sp_gene_details_add_simple_diplotype(d, call.core1, call.core2);
-        sp_gene_details_add_diplotype_only(d, call.deep1, call.deep2);
-        for (const sp_cyp_read_mapping& m : mappings)                               // multi_mapping_details (src/cyp2d6/caller.rs:541-565)
-            sp_gene_details_add_multi_mapping(d, reads[order[m.read]].qname.c_str(), m.read_start, m.read_end, m.consensus, m.index_label);
-        if (!h->debug_folder.empty()) {
-            uint64_t need = 0;
-            sp_cyp_alleles_json(&pr, &call, &rv, nullptr, 0, &need);
-            std::string text(need, '\0');
-            if (sp_cyp_alleles_json(&pr, &call, &rv, &text[0], need, &need) != SP_OK) { L->rc = SP_ERR_INVALID_ARG; L->err = "cyp2d6_alleles.json"; return; }
-            text.resize(std::strlen(text.c_str()));
-            const std::string path = h->debug_folder + "/cyp2d6_alleles.json";
-            FILE* f = std::fopen(path.c_str(), "wb");
-            if (!f || std::fwrite(text.data(), 1, text.size(), f) != text.size()) { if (f) std::fclose(f); L->rc = SP_ERR_INVALID_ARG; L->err = "Error while writing " + path; return; }
-            std::fclose(f);
+    cyp_package(h, pr, call, rv, mappings, reads, order, h->debug_folder, L);
+    if (L->rc == SP_OK) L->ms = ms_since(t_lane);
+}
+
+// ---------------------------------------------------------------- sp_starphase_call_batch
+struct BSample : VarSample {
+    std::vector<std::string> bams; std::string debug; bool run_hla = false, run_cyp = false;
+    int stage = 0;                                   // where it failed: 0 the checks, 1 variant genes, 2 HLA, 3 CYP2D6 or the result
+    std::string warnings;
+    // decoded
+    std::vector<Read4> hreads; std::vector<uint32_t> hsearched; std::string hwarn, herr; int32_t hrc = SP_OK;
+    std::vector<Read4> creads; std::string cwarn, cerr; int32_t crc = SP_OK;
+    // typed
+    std::vector<Entry> hla_entries;
+    CypLane cyp;
+    void fail(int at, int32_t code, const std::string& m) { if (rc == SP_OK) { rc = code; err = m; stage = at; } }
+    void release_reads() { std::vector<Read4>().swap(hreads); std::vector<uint32_t>().swap(hsearched); std::vector<Read4>().swap(creads); vf = VcfFetch(); }
+};
+
+void decode_sample(sp_starphase* h, BSample& b) {
+    if (b.rc != SP_OK) return;
+    if (b.has_vcf) vcf_fetch(h, h->win, b.vcf, b.sv, b.sample, b.vf);
+    if (b.run_hla) b.hrc = hla_collect(h, b.bams, b.hreads, b.hsearched, b.hwarn, b.herr);
+    if (b.run_cyp) {
+        std::set<std::string> seen;
+        b.crc = collect_reads(b.bams, h->cyp_chrom, h->cyp_start, h->cyp_end, seen, b.creads, b.cwarn, b.cerr);
+    }
+}
+
+// the CYP2D6 lane of a group: one cohort call on the second context for every sample with reads.  only_ok (settings.sequential): the samples whose
+// other lanes failed are skipped, as sp_starphase_call does not run the lane after a failure
+void cyp_group(sp_starphase* h, std::vector<BSample*> group, bool only_ok, double* ms) {
+    auto t0 = std::chrono::steady_clock::now();
+    sp_cyp_problem pr{};
+    cyp_problem(h, pr);
+    std::vector<BSample*> typed; std::vector<std::vector<uint32_t>> orders; std::vector<sp_seqset*> sets;
+    for (BSample* b : group) {
+        if (!b->run_cyp || (only_ok && b->rc != SP_OK)) continue;
+        CypLane* L = &b->cyp;
+        L->entry.gene = "CYP2D6"; L->entry.details.reset(new GeneDetailsPtr());
+        L->warnings = b->cwarn; L->n_reads = (uint32_t)b->creads.size();
+        if (b->crc != SP_OK) { L->rc = b->crc; L->err = b->cerr; continue; }
+        L->entry.constructor = SP_DETAILS_FROM_MULTI_MAPPINGS;
+        if (b->creads.empty()) { sp_gene_details_add_diplotype(L->entry.details->d, "NO_READS", "NO_READS"); continue; }
+        orders.push_back(qname_order(b->creads));
+        sp_seqset* set = nullptr;
+        const int32_t rc = upload_reads(h->ctx2, b->creads, orders.back(), &set);
+        if (rc != SP_OK) { L->rc = rc; L->err = "read upload: " + opt(sp_last_error(h->ctx2)); orders.pop_back(); continue; }
+        typed.push_back(b); sets.push_back(set);
+    }
+    const uint32_t n = (uint32_t)typed.size();
+    if (n) {
+        std::vector<sp_cyp_call> calls(n);
+        const size_t per = (size_t)SP_CYP_MAXCONS * std::max<uint32_t>(pr.n_variants, 1);
+        std::vector<uint8_t> state(per * n);
+        std::vector<sp_cyp_region_variants> rv(n);
+        for (uint32_t k = 0; k < n; ++k) { rv[k] = sp_cyp_region_variants{}; rv[k].state = state.data() + per * k; }
+        std::vector<std::vector<sp_cyp_read_mapping>> mappings(n);
+        std::vector<int32_t> rcs(n, SP_OK);
+        spi_cyp_diplotype_cohort_mappings(h->ctx2, &pr, n, sets.data(), calls.data(), nullptr, 0, rv.data(), mappings.data(), rcs.data());
+        for (uint32_t k = 0; k < n; ++k) {
+            CypLane* L = &typed[k]->cyp;
+            if (rcs[k] != SP_OK) {
+                // the context's error text may be another sample's: the sample goes through the call sp_starphase_call makes, alone
+                const int32_t rc = spi_cyp_diplotype_mappings(h->ctx2, &pr, sets[k], &calls[k], nullptr, 0, &rv[k], &mappings[k]);
+                if (rc != SP_OK) { L->rc = rc; L->err = "sp_cyp_diplotype: " + opt(sp_last_error(h->ctx2)); continue; }
+            }
+            cyp_package(h, pr, calls[k], rv[k], mappings[k], typed[k]->creads, orders[k], typed[k]->debug, L);
         }
     }
-    L->ms = ms_since(t_lane);
+    for (sp_seqset* s : sets) sp_seqset_free(s);
+    *ms += ms_since(t0);
+}
+
+// the HLA lane of samples that share the device passes: their reads in one set (sample by sample, QNAME order within a sample), one K1 pass that
+// also names the reverse-strand reads, the (sample, gene) problems in one cohort call, then each sample's entries as hla_lane makes them.
+// Errors are named as sp_starphase_call names them.
+int32_t hla_pass(sp_starphase* h, const std::vector<BSample*>& with, std::string& err) {
+    const size_t G = h->hgenes.size();
+    const uint32_t cap = 1 << 16;
+    std::vector<std::vector<uint32_t>> orders; std::vector<uint32_t> first{0};
+    for (BSample* b : with) { orders.push_back(qname_order(b->hreads)); first.push_back(first.back() + (uint32_t)b->hreads.size()); }
+    const uint32_t R = first.back();
+    std::vector<sp_hla_realign> rec(R); std::vector<sp_hla_rev_hit> rev(R);
+    std::vector<sp_hla_call> calls(with.size() * G);
+    for (auto& c : calls) { std::memset(&c, 0, sizeof c); c.status = 1; }
+    if (R) {
+        std::vector<uint8_t> bytes; std::vector<uint64_t> off{0}; std::vector<uint32_t> lens;
+        for (size_t k = 0; k < with.size(); ++k)
+            for (uint32_t i : orders[k]) { const Read4& r = with[k]->hreads[i]; bytes.insert(bytes.end(), r.seq4.begin(), r.seq4.end()); off.push_back(bytes.size()); lens.push_back(r.len); }
+        if (bytes.empty()) bytes.push_back(0);
+        sp_seqset* set = nullptr;
+        int32_t rc = sp_seqset_upload_format(h->ctx, SP_SEQ_BAM4, bytes.data(), off.data(), lens.data(), R, &set);
+        if (rc != SP_OK) { err = "read upload: " + opt(sp_last_error(h->ctx)); return rc; }
+        std::unique_ptr<sp_seqset, void (*)(sp_seqset*)> guard(set, sp_seqset_free);
+        rc = sp_hla_realign_reads_rev(h->ctx, h->hla, set, rec.data(), rev.data());
+        if (rc != SP_OK) { err = "sp_hla_realign_reads: " + opt(sp_last_error(h->ctx)); return rc; }
+        // the samples with reads are the cohort; a sample without reads keeps the no-reads calls, as hla_lane does
+        std::vector<uint32_t> read_sample(R), at;
+        std::vector<sp_hla_call_config> cfg;
+        for (size_t k = 0; k < with.size(); ++k) {
+            if (first[k + 1] == first[k]) continue;
+            for (uint32_t r = first[k]; r < first[k + 1]; ++r) read_sample[r] = (uint32_t)at.size();
+            at.push_back((uint32_t)k);
+            cfg.resize(at.size() * G);
+            hla_configs(h, rec.data() + first[k], first[k + 1] - first[k], cfg.data() + (at.size() - 1) * G);
+        }
+        std::vector<uint32_t> genes(G);
+        for (size_t g = 0; g < G; ++g) genes[g] = (uint32_t)g;
+        std::vector<sp_hla_call> cc(at.size() * G);
+        const size_t need = at.size() * G * 2 * (size_t)cap;
+        if (h->batch_cons.size() < need) h->batch_cons.resize(need);
+        rc = at.size() == 1 ? sp_hla_diplotype_genes(h->ctx, h->hla, (uint32_t)G, genes.data(), set, rec.data(), cfg.data(), cc.data(), h->batch_cons.data(), cap, nullptr)
+                            : sp_hla_diplotype_cohort_samples(h->ctx, h->hla, (uint32_t)at.size(), read_sample.data(), (uint32_t)G, genes.data(), set, rec.data(),
+                                                              cfg.data(), cc.data(), h->batch_cons.data(), cap, nullptr);
+        if (rc != SP_OK) { err = "sp_hla_diplotype_genes: " + opt(sp_last_error(h->ctx)); return rc; }
+        for (size_t x = 0; x < at.size(); ++x) std::copy(cc.begin() + x * G, cc.begin() + (x + 1) * G, calls.begin() + (size_t)at[x] * G);
+    }
+    for (size_t k = 0; k < with.size(); ++k) {
+        BSample* b = with[k];
+        std::map<uint32_t, RevHit> rv;
+        for (uint32_t p = 0; p < first[k + 1] - first[k]; ++p) {
+            const sp_hla_rev_hit& q = rev[first[k] + p];
+            if (q.allele >= 0) rv[p] = RevHit{q.allele, (uint64_t)q.t_len, (uint64_t)q.nm, (uint64_t)(q.t_len - (q.t_end - q.t_start))};
+        }
+        std::string e;
+        const int32_t rc = hla_package(h, b->hreads, b->hsearched, orders[k], rec.data() + first[k], rv, calls.data() + k * G, b->debug, b->hla_entries, e);
+        if (rc != SP_OK) b->fail(2, rc, e);
+    }
+    return SP_OK;
+}
+
+// the HLA lane of a group.  The shared passes fail as a whole (a read too long for K1, a failing consensus unit of one sample, ...): the group then
+// goes through them once more sample by sample, so only the sample that has the failure fails, with its own text
+void hla_group(sp_starphase* h, const std::vector<BSample*>& group, uint64_t* n_reads) {
+    std::vector<BSample*> with;
+    for (BSample* b : group) {
+        if (!b->run_hla || b->rc != SP_OK) continue;
+        if (b->hrc != SP_OK) { b->fail(2, b->hrc, b->herr); continue; }
+        *n_reads += b->hreads.size();
+        with.push_back(b);
+    }
+    if (with.empty()) return;
+    std::string err;
+    const int32_t rc = hla_pass(h, with, err);
+    if (rc == SP_OK) return;
+    if (with.size() == 1) { with[0]->fail(2, rc, err); return; }
+    for (BSample* b : with) {
+        b->hla_entries.clear();
+        std::string e;
+        const int32_t rb = hla_pass(h, {b}, e);
+        if (rb != SP_OK) b->fail(2, rb, e);
+    }
 }
 
 }  // namespace
@@ -647,6 +918,21 @@ int32_t sp_starphase_create(sp_ctx* ctx, const char* database_path, const char* 
         spi_gene_entry_extras(h->db, vg.g, &vg.reference_allele, &vg.has_sv, &vg.sv_chrom);
         h->vgenes.push_back(std::move(vg));
     }
+    // the fetch window of every selected gene with variants (variant_lane: +-50 bp around each variant)
+    h->win.assign(h->vgenes.size(), GeneWindow());
+    for (size_t i = 0; i < h->vgenes.size(); ++i) {
+        const sp_starphase::VGene& vg = h->vgenes[i];
+        sp_variant_gene_stats st{};
+        sp_variant_gene_info(vg.g, &st);
+        h->win[i].fetch = vg.selected && !(st.n_variants == 0 && !vg.has_sv); h->win[i].n_variants = st.n_variants;
+        uint64_t lo = UINT64_MAX, hi = 0;
+        for (uint32_t v = 0; v < st.n_variants; ++v) {
+            uint64_t pos; const char *r, *a, *nm, *dbsnp; int64_t vid; int32_t core;
+            sp_variant_gene_variant(vg.g, v, &pos, &r, &a, &nm, &dbsnp, &vid, &core);
+            lo = std::min(lo, pos > 50 ? pos - 50 : 0); hi = std::max(hi, pos + std::strlen(r) + 51);
+        }
+        h->win[i].lo = lo; h->win[i].hi = hi;
+    }
     if (!h->fasta) { *out = h.release(); return SP_OK; }          // no genome: the BAM loci cannot run (sp_starphase_call says so)
     // HLA: the hla_config genes that are selected, flattened against the reference (+-100 bp, src/hla/realigner.rs:74-81).  The reference builds
     // its realigner only when a sample has BAMs: a locus that cannot be set up here (its contig is not in the FASTA, ...) fails the first call with BAMs
@@ -708,6 +994,116 @@ int32_t sp_starphase_create(sp_ctx* ctx, const char* database_path, const char* 
     if (h->cyp_selected && setup_cyp() != SP_OK) { h->cyp_err = g_create_error; g_create_error.clear(); }
     *out = h.release();
     return SP_OK;
+}
+
+const char* sp_starphase_sample_error(const sp_starphase* h, uint32_t i) { return h && i < h->batch_err.size() ? h->batch_err[i].c_str() : ""; }
+const char* sp_starphase_sample_warnings(const sp_starphase* h, uint32_t i) { return h && i < h->batch_warn.size() ? h->batch_warn[i].c_str() : ""; }
+int32_t sp_starphase_last_batch_timing(const sp_starphase* h, sp_starphase_batch_timing* out) {
+    if (!h || !out) return SP_ERR_INVALID_ARG;
+    *out = h->batch_timing;
+    return SP_OK;
+}
+
+int32_t sp_starphase_call_batch(sp_starphase* h, uint32_t n, const sp_sample_inputs* inputs, const char* const* debug_folders, const sp_batch_options* opts,
+                                sp_result** out, int32_t* sample_rc) {
+    if (!h) return SP_ERR_INVALID_ARG;
+    h->err.clear(); h->warnings.clear(); h->batch_timing = sp_starphase_batch_timing{};
+    if (n && (!inputs || !out)) return h->fail(SP_ERR_INVALID_ARG, "sp_starphase_call_batch: null argument");
+    if (!h->debug_folder.empty() && !debug_folders)
+        return h->fail(SP_ERR_INVALID_ARG, "sp_starphase_call_batch: the handle has a debug folder, which every sample would overwrite; pass debug_folders");
+    const auto t_call = std::chrono::steady_clock::now();
+    const uint32_t max_group = opts && opts->max_group ? opts->max_group : 64u;
+    const uint32_t hw = std::max(1u, std::thread::hardware_concurrency());
+    const uint32_t n_threads = opts && opts->decode_threads ? opts->decode_threads : std::min(16u, hw);
+    h->batch_err.assign(n, std::string()); h->batch_warn.assign(n, std::string());
+    for (uint32_t i = 0; i < n; ++i) { out[i] = nullptr; if (sample_rc) sample_rc[i] = SP_OK; }
+    // the samples, with the checks sp_starphase_call makes before it reads anything
+    std::vector<BSample> S(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const sp_sample_inputs& in = inputs[i]; BSample& b = S[i];
+        for (uint32_t k = 0; k < in.n_bams; ++k) b.bams.push_back(opt(in.bams[k]));
+        b.has_vcf = in.vcf != nullptr; b.vcf = opt(in.vcf);
+        b.sample = in.sample_name ? opt(in.sample_name) : h->sample_name;
+        b.sv = in.sv_vcf ? opt(in.sv_vcf) : h->sv_vcf;
+        b.debug = debug_folders && debug_folders[i] ? std::string(debug_folders[i]) : std::string();
+        b.run_hla = !b.bams.empty() && h->hla && !h->s.debug_skip_hla;
+        b.run_cyp = !b.bams.empty() && h->cyp_selected && h->cyp;
+        if (!b.bams.empty() && !h->fasta) { b.rc = SP_ERR_INVALID_ARG; b.err = "Reference genome is required for reading alignment files"; }
+        else if (!b.bams.empty() && !h->s.debug_skip_hla && !h->hla_err.empty()) { b.rc = SP_ERR_INVALID_ARG; b.err = h->hla_err; }
+        else if (!b.bams.empty() && h->cyp_selected && !h->cyp_err.empty()) { b.rc = SP_ERR_INVALID_ARG; b.err = h->cyp_err; }
+        if (b.rc != SP_OK) b.run_hla = b.run_cyp = false;
+        else if (!b.debug.empty()) mkdir(b.debug.c_str(), 0755);
+    }
+    sp_starphase_batch_timing& T = h->batch_timing;
+    T.n_samples = n;
+    // host decode of a group on the worker pool; group k + 1 is decoded while group k is on the device
+    auto decode = [&](uint32_t g0, uint32_t g1, double* ms) {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::atomic<uint32_t> next(g0);
+        auto work = [&]() { for (uint32_t i; (i = next.fetch_add(1)) < g1;) decode_sample(h, S[i]); };
+        std::vector<std::thread> pool;
+        for (uint32_t t = 1; t < std::min(n_threads, g1 - g0); ++t) {
+            try { pool.emplace_back(work); } catch (const std::system_error&) { break; }
+        }
+        work();
+        for (auto& t : pool) t.join();
+        *ms = ms_since(t0);
+    };
+    std::thread ahead; double ahead_ms = 0;
+    int32_t first_rc = SP_OK;
+    for (uint32_t g0 = 0; g0 < n; g0 += max_group) {
+        const uint32_t g1 = std::min(n, g0 + max_group);
+        if (g0 == 0) decode(g0, g1, &ahead_ms);
+        else ahead.join();
+        T.decode_ms += ahead_ms; ++T.n_groups;
+        if (g1 < n) ahead = std::thread(decode, g1, std::min(n, g1 + max_group), &ahead_ms);
+        std::vector<BSample*> group;
+        for (uint32_t i = g0; i < g1; ++i) group.push_back(&S[i]);
+        // CYP2D6 on its own thread and context, beside the variant genes and the HLA genes (settings.sequential: after them)
+        double cyp_ms = 0;
+        std::thread cyp;
+        if (!h->s.sequential) cyp = std::thread(cyp_group, h, group, false, &cyp_ms);
+        auto t0 = std::chrono::steady_clock::now();
+        std::vector<VarSample*> vs;
+        for (BSample* b : group) if (b->rc == SP_OK) vs.push_back(b);
+        variant_samples(h, vs);
+        for (VarSample* v : vs) if (v->rc != SP_OK) static_cast<BSample*>(v)->stage = 1;
+        T.variant_ms += ms_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        hla_group(h, group, &T.n_hla_reads);
+        T.hla_ms += ms_since(t0);
+        if (cyp.joinable()) cyp.join();
+        else cyp_group(h, group, true, &cyp_ms);
+        T.cyp_ms += cyp_ms;
+        // the results, in sp_starphase_call's order of errors: the checks, variant genes, HLA, CYP2D6; the warnings it keeps up to its failure
+        t0 = std::chrono::steady_clock::now();
+        for (uint32_t i = g0; i < g1; ++i) {
+            BSample& b = S[i];
+            if (b.run_cyp) T.n_cyp_reads += b.cyp.n_reads;
+            if (b.rc == SP_OK && b.run_cyp && b.cyp.rc != SP_OK) b.fail(3, b.cyp.rc, b.cyp.err);
+            const bool hla_ran = b.rc == SP_OK || b.stage >= 2, cyp_kept = b.rc == SP_OK || b.stage >= 3;
+            b.warnings = (hla_ran ? b.hwarn : std::string()) + (cyp_kept && b.run_cyp ? b.cyp.warnings : std::string());
+            if (b.rc == SP_OK) {
+                sp_result* res = nullptr;
+                sp_result_create(h->db, nullptr, &res);
+                std::unique_ptr<sp_result, void (*)(sp_result*)> guard(res, sp_result_free);
+                std::vector<Entry*> all;
+                for (auto& e : b.entries) all.push_back(&e);
+                for (auto& e : b.hla_entries) all.push_back(&e);
+                if (b.run_cyp) { b.cyp.entry.gene = "CYP2D6"; all.push_back(&b.cyp.entry); }
+                for (Entry* e : all)
+                    if (b.rc == SP_OK && sp_result_insert(res, e->gene.c_str(), e->details->d, e->constructor) != SP_OK) b.fail(3, SP_ERR_INVALID_ARG, opt(sp_result_last_error(res)));
+                if (b.rc == SP_OK) out[i] = guard.release();
+            }
+            if (b.rc != SP_OK) { ++T.n_failed; if (first_rc == SP_OK) { first_rc = b.rc; h->err = "sample " + std::to_string(i) + ": " + b.err; } }
+            if (sample_rc) sample_rc[i] = b.rc;
+            h->batch_err[i] = b.err; h->batch_warn[i] = b.warnings;
+            b.release_reads(); b.entries.clear(); b.hla_entries.clear(); b.cyp.entry.details.reset();
+        }
+        T.package_ms += ms_since(t0);
+    }
+    T.wall_ms = ms_since(t_call);
+    return first_rc;
 }
 
 int32_t sp_starphase_call(sp_starphase* h, const sp_sample_inputs* in, sp_result** out) {

@@ -1112,7 +1112,7 @@ int32_t sp_hla_db_create(sp_ctx* ctx, const sp_hla_db_desc* d, sp_hla_db** out) 
     return SP_OK;
 }
 
-static int32_t k1_realign_chunk(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, sp_hla_realign* out, uint32_t* cell_out);
+static int32_t k1_realign_chunk(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, sp_hla_realign* out, uint32_t* cell_out, sp_hla_rev_hit* rev = nullptr);
 
 static int32_t k1_seed_index(sp_ctx* ctx, const sp_hla_db* db) {
     std::lock_guard<std::mutex> guard(db->lazy);
@@ -1154,14 +1154,31 @@ int32_t sp_hla_realign_seeded_audit(sp_ctx* ctx, const sp_hla_db* db, const sp_s
     return SP_OK;
 }
 
+static int32_t k1_realign_sliced(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, sp_hla_realign* out, uint32_t* cell_out, sp_hla_rev_hit* rev);
+
 int32_t sp_hla_realign_reads(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, sp_hla_realign* out, uint32_t* cell_out) {
     if (!ctx || !db || !reads || !out) return SP_ERR_INVALID_ARG;
+    return k1_realign_sliced(ctx, db, reads, out, cell_out, nullptr);
+}
+
+int32_t sp_hla_realign_reads_rev(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, sp_hla_realign* out, sp_hla_rev_hit* rev) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (!db || !reads || !out || !rev) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_hla_realign_reads_rev: null argument");
+    if (ctx->k1_best_n <= 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_hla_realign_reads_rev: the reverse-strand mappings come from the seeded stage (k1_best_n > 0)");
+    const int32_t rc = k1_realign_sliced(ctx, db, reads, out, nullptr, rev);
+    if (rc != SP_OK) return rc;
+    // the pick stage names the accepted reverse mapping of every read; only a record that was dropped for it keeps it
+    for (uint32_t r = 0; r < reads->n; ++r) if (!(out[r].status == 2 && out[r].best_allele < 0)) rev[r] = sp_hla_rev_hit{ -1, 0, 0, 0, 0, 0 };
+    return SP_OK;
+}
+
+static int32_t k1_realign_sliced(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, sp_hla_realign* out, uint32_t* cell_out, sp_hla_rev_hit* rev) {
     HostScope host_total(ctx, "host:k1_total");
     // big batches go through in slices of 65,536 reads (a shallow view of the same packed words): the read x allele matrix of a
     // slice is what bounds the device memory of a call, however many reads the caller hands over
     const char* env = std::getenv("SP_K1_SLICE");              // (tests shrink the slice to exercise this path)
     const uint32_t slice = env && std::atoi(env) > 0 ? (uint32_t)std::atoi(env) : 65536u;
-    if (reads->n <= slice) return k1_realign_chunk(ctx, db, reads, out, cell_out);
+    if (reads->n <= slice) return k1_realign_chunk(ctx, db, reads, out, cell_out, rev);
     for (uint32_t r0 = 0; r0 < reads->n; r0 += slice) {
         const uint32_t k = std::min<uint32_t>(slice, reads->n - r0);
         sp_seqset part;
@@ -1169,19 +1186,19 @@ int32_t sp_hla_realign_reads(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* 
         part.d_words = reads->d_words; part.d_nplane = reads->d_nplane; part.d_word_off = reads->d_word_off + r0; part.d_len = reads->d_len + r0;
         part.h_len.assign(reads->h_len.begin() + r0, reads->h_len.begin() + r0 + k);
         part.h_word_off.assign(reads->h_word_off.begin() + r0, reads->h_word_off.begin() + r0 + k + 1);
-        const int32_t rc = k1_realign_chunk(ctx, db, &part, out + r0, cell_out ? cell_out + (size_t)r0 * db->n_alleles : nullptr);
+        const int32_t rc = k1_realign_chunk(ctx, db, &part, out + r0, cell_out ? cell_out + (size_t)r0 * db->n_alleles : nullptr, rev ? rev + r0 : nullptr);
         if (rc != SP_OK) return rc;
     }
     return SP_OK;
 }
 
-static int32_t k1_realign_chunk(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, sp_hla_realign* out, uint32_t* cell_out) {
+static int32_t k1_realign_chunk(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, sp_hla_realign* out, uint32_t* cell_out, sp_hla_rev_hit* rev) {
     const uint32_t R = reads->n, G = db->n_genes, NA = db->n_alleles;
     if (R == 0) return SP_OK;
     (void)hipSetDevice(ctx->device);
     // the reference's call pattern (seeds, chains, best_n: sp_hla_seed.hip) unless the caller wants every cell or has switched it off
     const bool seeded = ctx->k1_best_n > 0 && !cell_out;
-    sp_aln* d_win_aln = nullptr; sp_affine_aln* d_win_af = nullptr; sp_k1_seed_info* d_seed_info = nullptr;
+    sp_aln* d_win_aln = nullptr; sp_affine_aln* d_win_af = nullptr; sp_k1_seed_info* d_seed_info = nullptr; sp_hla_rev_hit* d_rev = nullptr;
     if (seeded) {
         std::lock_guard<std::mutex> guard(db->lazy);
         if (!db->seed) { const int brc = sp_k1_seed_build(ctx, db->dna_fwd, &db->seed); if (brc != SP_OK) return brc; }
@@ -1246,8 +1263,9 @@ static int32_t k1_realign_chunk(sp_ctx* ctx, const sp_hla_db* db, const sp_seqse
     if (rc == SP_OK && seeded) {
         d_win_aln = (sp_aln*)sp_pool(ctx, "k1s_win_aln", (size_t)R * sizeof(sp_aln)); d_win_af = (sp_affine_aln*)sp_pool(ctx, "k1s_win_af", (size_t)R * sizeof(sp_affine_aln));
         d_seed_info = (sp_k1_seed_info*)sp_pool(ctx, "k1s_info", (size_t)R * sizeof(sp_k1_seed_info));
-        if (!d_win_aln || !d_win_af || !d_seed_info) rc = sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
-        else rc = sp_k1_seed_map(ctx, db->seed, db->dna_fwd, reads, ctx->k1_best_n, d_best, d_seed_info, d_win_aln, d_win_af, nullptr);
+        if (rev) d_rev = (sp_hla_rev_hit*)sp_pool(ctx, "k1s_rev", (size_t)R * sizeof(sp_hla_rev_hit));
+        if (!d_win_aln || !d_win_af || !d_seed_info || (rev && !d_rev)) rc = sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
+        else rc = sp_k1_seed_map(ctx, db->seed, db->dna_fwd, reads, ctx->k1_best_n, d_best, d_seed_info, d_win_aln, d_win_af, nullptr, d_rev);
         if (rc == SP_OK) {
             hipLaunchKernelGGL(k1_seed_pairs_kernel, dim3((R * G + 255) / 256), dim3(256), 0, ctx->stream, d_best, db->d_gene_of, R, G, d_a, d_b);
             rc = sp_launch_anchor(ctx, db->ref_fwd, reads, d_a, d_b, (uint64_t)R * G, d_rg, d_votes, 1, "anchor_k1", G);
@@ -1393,6 +1411,7 @@ static int32_t k1_realign_chunk(sp_ctx* ctx, const sp_hla_db* db, const sp_seqse
         if (h_isrev) (void)hipMemcpyAsync(h_isrev, d_isrev, R, hipMemcpyDeviceToHost, ctx->stream);
         (void)hipMemcpyAsync(h_out ? h_out : (void*)out, d_out, (size_t)R * sizeof(sp_hla_realign), hipMemcpyDeviceToHost, ctx->stream);
         if (cell_out) (void)hipMemcpyAsync(cell_out, d_cells, (size_t)R * NA * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (d_rev) (void)hipMemcpyAsync(rev, d_rev, (size_t)R * sizeof(sp_hla_rev_hit), hipMemcpyDeviceToHost, ctx->stream);
         hipError_t e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) rc = sp_fail(ctx, SP_ERR_HIP, std::string("realign: ") + hipGetErrorString(e));
         else if (h_out) std::memcpy(out, h_out, (size_t)R * sizeof(sp_hla_realign));

@@ -397,9 +397,21 @@ int32_t sp_hla_diplotype_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_sam
     if (!db || !reads || !realign || !cfgs || !calls || !cons || !genes || !read_sample || cap == 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_hla_diplotype_cohort: null argument");
     for (uint32_t r = 0; r < reads->n; ++r) if (read_sample[r] >= n_samples) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_hla_diplotype_cohort: sample index out of range");
     const uint32_t units = n_samples * n_genes;
-    std::vector<uint32_t> ug(units), us(units); std::vector<sp_hla_call_config> uc(units);
-    for (uint32_t s = 0; s < n_samples; ++s) for (uint32_t g = 0; g < n_genes; ++g) { ug[s * n_genes + g] = genes[g]; us[s * n_genes + g] = s; uc[s * n_genes + g] = cfgs[g]; }
-    return hla_solve_side_by_side(ctx, db, units, ug.data(), us.data(), read_sample, reads, realign, uc.data(), calls, cons, cap, is_cons1_out);
+    std::vector<sp_hla_call_config> uc(units);
+    for (uint32_t s = 0; s < n_samples; ++s) for (uint32_t g = 0; g < n_genes; ++g) uc[s * n_genes + g] = cfgs[g];
+    return sp_hla_diplotype_cohort_samples(ctx, db, n_samples, read_sample, n_genes, genes, reads, realign, uc.data(), calls, cons, cap, is_cons1_out);
+}
+
+int32_t sp_hla_diplotype_cohort_samples(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
+                                        const sp_seqset* reads, const sp_hla_realign* realign, const sp_hla_call_config* cfgs, sp_hla_call* calls,
+                                        char* cons, uint32_t cap, uint8_t* is_cons1_out) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (!db || !reads || !realign || !cfgs || !calls || !cons || !genes || !read_sample || cap == 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_hla_diplotype_cohort: null argument");
+    for (uint32_t r = 0; r < reads->n; ++r) if (read_sample[r] >= n_samples) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_hla_diplotype_cohort: sample index out of range");
+    const uint32_t units = n_samples * n_genes;
+    std::vector<uint32_t> ug(units), us(units);
+    for (uint32_t s = 0; s < n_samples; ++s) for (uint32_t g = 0; g < n_genes; ++g) { ug[s * n_genes + g] = genes[g]; us[s * n_genes + g] = s; }
+    return hla_solve_side_by_side(ctx, db, units, ug.data(), us.data(), read_sample, reads, realign, cfgs, calls, cons, cap, is_cons1_out);
 }
 
 int32_t sp_hla_diplotype_gene(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const sp_seqset* reads, const sp_hla_realign* realign,

@@ -1198,7 +1198,7 @@ __device__ __forceinline__ double seed_score_value(int len, int nm, int unmapped
 __global__ void k1s_pick_kernel(SeqSetView reads, const SSel* __restrict__ sel, const uint32_t* __restrict__ sel_cnt, uint32_t n_reads, const sp_aln* __restrict__ alns,
                                 const sp_affine_aln* __restrict__ afs, const uint32_t* __restrict__ rid_allele, const int32_t* __restrict__ allele_len, int best_n,
                                 int32_t* __restrict__ best_out, sp_k1_seed_info* __restrict__ info, sp_aln* __restrict__ win_aln, sp_affine_aln* __restrict__ win_af,
-                                sp_k1_seed_hit* __restrict__ dbg_hits, uint32_t* __restrict__ dbg_n, uint32_t dbg_read) {
+                                sp_k1_seed_hit* __restrict__ dbg_hits, uint32_t* __restrict__ dbg_n, uint32_t dbg_read, sp_hla_rev_hit* __restrict__ rev_out) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_reads) return;
     const int qlen = reads.len[r];
@@ -1228,6 +1228,7 @@ __global__ void k1s_pick_kernel(SeqSetView reads, const SSel* __restrict__ sel, 
         }
     }
     int pick = -1, n_out = 0, n2 = 0; double best = 1.0;
+    int rpick = -1; double rbest = 1.0;            // rev_out: hla_lane's audit rule over the same mappings (it skips an empty aligned span instead of dividing by it)
     for (int i = 0; i < nh; ++i) {
         const int p = h[i].parent;
         bool keep = p == i;
@@ -1237,6 +1238,7 @@ __global__ void k1s_pick_kernel(SeqSetView reads, const SSel* __restrict__ sel, 
         const int tl = h[i].tl, um = tl - (h[i].re - h[i].rs), nm = h[i].nm;
         const double pen = seed_score_value(tl, nm, um), ed = seed_score_value(tl - um, nm, 0);
         if (pen <= 0.5 && ed <= 0.03 && ed < best) { best = ed; pick = i; }
+        if (rev_out && tl > 0 && tl - um > 0 && pen <= 0.5 && ed <= 0.03 && ed < rbest) { rbest = ed; rpick = i; }
         if (dbg_hits && r == dbg_read) {
             sp_k1_seed_hit d; const size_t x = (size_t)r * SEL_CAP + h[i].slot; const SSel q = sel[x]; const sp_aln a = alns[x];
             d.allele = (int32_t)rid_allele[h[i].rid]; d.rev = h[i].rev; d.chain_score = q.score; d.n_seeds = q.cnt; d.t_len = tl; d.sel_rank = h[i].slot; d.diag = q.diag;
@@ -1258,6 +1260,11 @@ __global__ void k1s_pick_kernel(SeqSetView reads, const SSel* __restrict__ sel, 
         if (!h[pick].rev) { b = (int32_t)rid_allele[h[pick].rid]; wa = alns[x]; wf = afs[x]; }
     }
     best_out[r] = b; info[r] = o; win_aln[r] = wa; win_af[r] = wf;
+    if (rev_out) {
+        sp_hla_rev_hit v; v.allele = -1; v.t_len = v.nm = v.t_start = v.t_end = v.reserved_ = 0;
+        if (rpick >= 0 && h[rpick].rev) { v.allele = (int32_t)rid_allele[h[rpick].rid]; v.t_len = h[rpick].tl; v.nm = h[rpick].nm; v.t_start = h[rpick].rs; v.t_end = h[rpick].re; }
+        rev_out[r] = v;
+    }
 }
 
 } // namespace
@@ -1389,9 +1396,10 @@ int sp_k1_seed_sketch(sp_ctx* ctx, const sp_seqset* set, uint32_t idx, uint64_t*
 }
 
 // The seeded map of a batch of reads.  On return (stream-ordered, nothing copied back): d_best[r] = accepted allele or -1, d_info[r], d_win_aln[r] / d_win_af[r] = the
-// accepted mapping's cell and its re-score.  dbg (optional): the chain list, selection and mappings of one read.
+// accepted mapping's cell and its re-score.  dbg (optional): the chain list, selection and mappings of one read.  d_rev (optional): per read, the mapping
+// sp_hla_realign_reads_rev hands out (the accepted one when it is on the reverse strand, else allele -1).
 int sp_k1_seed_map(sp_ctx* ctx, const K1Seed* idx, const sp_seqset* alleles, const sp_seqset* reads, int best_n, int32_t* d_best, sp_k1_seed_info* d_info,
-                   sp_aln* d_win_aln, sp_affine_aln* d_win_af, const K1SeedDebug* dbg) {
+                   sp_aln* d_win_aln, sp_affine_aln* d_win_af, const K1SeedDebug* dbg, sp_hla_rev_hit* d_rev) {
     const uint32_t R = reads->n;
     if (R == 0) return SP_OK;
     (void)hipSetDevice(ctx->device);
@@ -1565,7 +1573,7 @@ int sp_k1_seed_map(sp_ctx* ctx, const K1Seed* idx, const sp_seqset* alleles, con
         dbg_nh = dbg_n + 1;
     }
     hipLaunchKernelGGL(k1s_pick_kernel, dim3((R + 63) / 64), dim3(64), 0, ctx->stream, reads->view(), d_sel, d_sel_cnt, R, d_aln, d_af, idx->d_rid_allele, alleles->d_len, best_n,
-                       d_best, d_info, d_win_aln, d_win_af, dbg_hits, dbg_nh, dbg ? dbg->read : 0u);
+                       d_best, d_info, d_win_aln, d_win_af, dbg_hits, dbg_nh, dbg ? dbg->read : 0u, d_rev);
     SP_HIP_CHECK(ctx, hipGetLastError());
     if (dbg) {
         uint32_t n2[2] = { 0, 0 };

@@ -149,7 +149,7 @@ void sp_k1_seed_free(K1Seed* s);
 void sp_k1_seed_stats(const K1Seed* s, int64_t out[4]);            // minimizers, distinct minimizers, mid_occ, indexed sequences
 int  sp_k1_seed_sketch(sp_ctx* ctx, const sp_seqset* set, uint32_t idx, uint64_t* hash, int32_t* end_pos, uint8_t* strand, uint32_t cap, uint32_t* n_out);
 int  sp_k1_seed_map(sp_ctx* ctx, const K1Seed* idx, const sp_seqset* alleles, const sp_seqset* reads, int best_n, int32_t* d_best, sp_k1_seed_info* d_info,
-                    sp_aln* d_win_aln, sp_affine_aln* d_win_af, const K1SeedDebug* dbg);
+                    sp_aln* d_win_aln, sp_affine_aln* d_win_af, const K1SeedDebug* dbg, sp_hla_rev_hit* d_rev = nullptr);
 
 // ---------------------------------------------------------------- launchers (sp_device.hip)
 sp_ctx* sp_ctx_helper(sp_ctx* ctx, int i = 0);                           // helper i (0..6); nullptr when it cannot be made
@@ -223,3 +223,7 @@ int32_t spi_gene_entry_extras(const sp_database* db, const sp_variant_gene* g, s
 // sp_cyp.hip, for sp_diplotype.hip: sp_cyp_diplotype_mappings with the list in a vector the library sizes
 int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
                                    sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings);
+// sp_cyp_diplotype_cohort that also hands out each sample's region variants and multi_mapping_details (optional, n_samples entries each)
+int32_t spi_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, uint32_t n_samples, const sp_seqset* const* reads, sp_cyp_call* calls,
+                                          char* consensus, uint32_t cons_cap, sp_cyp_region_variants* region_variants,
+                                          std::vector<sp_cyp_read_mapping>* mappings, int32_t* sample_rc);

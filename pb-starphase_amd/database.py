@@ -69,6 +69,15 @@ class sp_starphase_timing(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("call_ms", "bam_decode_ms", "variant_ms", "hla_ms", "cyp_ms")] + [("n_hla_reads", _u32), ("n_cyp_reads", _u32)]
 
 
+class sp_batch_options(C.Structure):
+    _fields_ = [("max_group", _u32), ("decode_threads", _u32), ("reserved_", _u32 * 6)]
+
+
+class sp_starphase_batch_timing(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("wall_ms", "decode_ms", "variant_ms", "hla_ms", "cyp_ms", "package_ms")] + \
+               [(k, _u32) for k in ("n_samples", "n_groups", "n_failed", "reserved_")] + [("n_hla_reads", _u64), ("n_cyp_reads", _u64)]
+
+
 SUBALLELE_MATCH, CORE_MATCH, INEXACT_DIPLOTYPES, FROM_MAPPINGS, FROM_MULTI_MAPPINGS, NO_MATCH = range(6)
 _bound = False
 
@@ -140,6 +149,12 @@ def _lib():
         "sp_starphase_call": (_i32, [_vp, P(sp_sample_inputs), P(_vp)]),
         "sp_starphase_warnings": (_s, [_vp]),
         "sp_starphase_last_timing": (_i32, [_vp, P(sp_starphase_timing)]),
+        "sp_starphase_call_batch": (_i32, [_vp, _u32, P(sp_sample_inputs), P(_s), P(sp_batch_options), P(_vp), P(_i32)]),
+        "sp_starphase_sample_error": (_s, [_vp, _u32]),
+        "sp_starphase_sample_warnings": (_s, [_vp, _u32]),
+        "sp_starphase_last_batch_timing": (_i32, [_vp, P(sp_starphase_batch_timing)]),
+        "sp_cyp_diplotype_cohort_mappings": (_i32, [_vp, P(ffi.sp_cyp_problem), _u32, P(_vp), P(ffi.sp_cyp_call), _s, _u32, P(ffi.sp_cyp_region_variants),
+                                                    P(sp_cyp_read_mapping), _u64, P(_u64), P(_i32)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -770,6 +785,42 @@ class Starphase:
             raise StarphaseError(rc, _d(_lib().sp_starphase_last_error(self._h)))
         return res
 
+    def call_batch(self, samples, max_group=None, threads=None, debug_folders=None):
+        """sp_starphase_call_batch: samples = [dict(bams=..., vcf=..., sv_vcf=..., sample_name=...)] -> per sample a Result, or the StarphaseError
+        that sample failed with (the others are still typed).  debug_folders: None or one folder (or None) per sample."""
+        n = len(samples)
+        keep = [_inputs(**smp) for smp in samples]
+        inp = (sp_sample_inputs * max(1, n))(*[k[0] for k in keep])
+        dbg = None
+        if debug_folders is not None:
+            if len(debug_folders) != n:
+                raise ValueError("debug_folders: one entry per sample")
+            dbg = (_s * max(1, n))(*[_b(d) for d in debug_folders])
+        opts = sp_batch_options(max_group or 0, threads or 0)
+        out = (_vp * max(1, n))()
+        rcs = (_i32 * max(1, n))()
+        rc = _lib().sp_starphase_call_batch(self._h, n, inp, dbg, C.byref(opts), out, rcs)
+        if rc != SP_OK and not any(rcs[i] != SP_OK for i in range(n)):
+            raise StarphaseError(rc, _d(_lib().sp_starphase_last_error(self._h)))
+        res = []
+        for i in range(n):
+            if rcs[i] != SP_OK or not out[i]:
+                res.append(StarphaseError(rcs[i], _d(_lib().sp_starphase_sample_error(self._h, i))))
+                continue
+            r = Result.__new__(Result)
+            r._h = _vp(out[i])
+            res.append(r)
+        return res
+
+    def sample_warnings(self, i):
+        """the warnings of sample i of the last call_batch"""
+        return _d(_lib().sp_starphase_sample_warnings(self._h, i))
+
+    def batch_timing(self):
+        t = sp_starphase_batch_timing()
+        _lib().sp_starphase_last_batch_timing(self._h, C.byref(t))
+        return {k: getattr(t, k) for k, _ty in sp_starphase_batch_timing._fields_ if k != "reserved_"}
+
     def warnings(self):
         return _d(_lib().sp_starphase_warnings(self._h))
 
@@ -783,6 +834,22 @@ def cli_path():
     """the `starphase_hip` executable the csrc Makefile builds next to the library"""
     import os
     return os.path.join(os.path.dirname(ffi.lib_path()), "starphase_hip")
+
+
+def cyp_diplotype_cohort_mappings(cdb, read_sets, cap=None, **overrides):
+    """sp_cyp_diplotype_cohort_mappings on a CypDb: per sample (sp_cyp_call, [(read, read_start, read_end, consensus, index_label)], status)"""
+    pr = cdb.problem(**overrides)
+    n = len(read_sets)
+    calls = (ffi.sp_cyp_call * max(1, n))()
+    handles = (_vp * max(1, n))(*[r._h.value if isinstance(r._h, C.c_void_p) else r._h for r in read_sets])
+    cap = cap if cap is not None else sum(64 * r.n + 64 for r in read_sets)
+    buf = (sp_cyp_read_mapping * max(1, cap))()
+    off = (_u64 * (n + 1))()
+    rcs = (_i32 * max(1, n))()
+    rc = _lib().sp_cyp_diplotype_cohort_mappings(cdb.ctx._h, C.byref(pr), n, handles, calls, None, 0, None, buf, cap, off, rcs)
+    if rc != SP_OK and not any(rcs[i] != SP_OK for i in range(n)):
+        raise StarphaseError(rc, "sp_cyp_diplotype_cohort_mappings")
+    return [(calls[i], [(m.read, m.read_start, m.read_end, m.consensus, m.index_label.decode()) for m in buf[off[i]:off[i + 1]]], rcs[i]) for i in range(n)]
 
 
 def cyp_diplotype_mappings(cdb, reads, cap=None, **overrides):

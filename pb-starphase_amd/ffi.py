@@ -219,6 +219,7 @@ REALIGN_DTYPE = np.dtype([("status", np.int32), ("best_allele", np.int32), ("gen
                           ("mm2_score", np.int32), ("mm2_nm", np.int32), ("mm2_t_start", np.int32), ("mm2_t_end", np.int32), ("mm2_q_start", np.int32), ("mm2_q_end", np.int32),
                           ("k1_chains", np.int32), ("k1_mappings", np.int32), ("k1_chain_score", np.int32), ("reserved_", np.int32)])
 K1_HIT_DTYPE = np.dtype([(n, np.int32) for n in K1_HIT_FIELDS])
+REV_HIT_DTYPE = np.dtype([(n, np.int32) for n in ("allele", "t_len", "nm", "t_start", "t_end", "reserved_")])     # sp_hla_rev_hit
 
 _lib = None
 
@@ -261,6 +262,7 @@ def lib():
         "sp_hla_db_create": (i32, [vp, C.POINTER(sp_hla_db_desc), C.POINTER(vp)]),
         "sp_hla_db_free": (None, [vp]),
         "sp_hla_realign_reads": (i32, [vp, vp, vp, vp, vp]),
+        "sp_hla_realign_reads_rev": (i32, [vp, vp, vp, vp, vp]),
         "sp_hla_score_consensus": (i32, [vp, vp, u32, C.c_char_p, u32, C.c_char_p, u32, i32, i32, C.POINTER(sp_hla_best), vp]),
         "sp_hla_score_consensus_batch": (i32, [vp, vp, u32, vp, C.POINTER(C.c_char_p), vp, C.POINTER(C.c_char_p), vp, i32, i32, vp]),
         "sp_hla_type_consensus_batch": (i32, [vp, vp, u32, vp, C.POINTER(C.c_char_p), vp, i32, i32, vp]),
@@ -296,6 +298,7 @@ def lib():
         "sp_hla_diplotype_gene": (i32, [vp, vp, u32, vp, vp, C.POINTER(sp_hla_call_config), C.POINTER(sp_hla_call), C.c_char_p, C.c_char_p, u32, vp]),
         "sp_hla_diplotype_genes": (i32, [vp, vp, u32, vp, vp, vp, C.POINTER(sp_hla_call_config), C.POINTER(sp_hla_call), C.c_char_p, u32, vp]),
         "sp_hla_diplotype_cohort": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, C.POINTER(sp_hla_call_config), C.POINTER(sp_hla_call), C.c_char_p, u32, vp]),
+        "sp_hla_diplotype_cohort_samples": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, C.POINTER(sp_hla_call_config), C.POINTER(sp_hla_call), C.c_char_p, u32, vp]),
         "sp_diplotype_string": (u32, [C.c_char_p, C.c_char_p, i32, C.c_char_p, u32]),
         "sp_inexact_haplotype": (u32, [C.c_char_p, u32, C.POINTER(C.c_char_p), vp, vp, C.POINTER(i32), C.c_char_p, u32]),
         "sp_cyp_db_create": (i32, [vp, C.POINTER(sp_cyp_locus), C.POINTER(sp_cyp_gene_def), C.POINTER(sp_cyp_config), C.POINTER(vp)]),
@@ -324,7 +327,7 @@ def lib():
     if L.sp_abi_version() != SP_ABI_VERSION:
         raise ImportError(f"{path}: ABI version {L.sp_abi_version()}, this binding was written for {SP_ABI_VERSION} (rebuild: __graft_entry__.build())")
     for name, size in (("sp_hla_realign", REALIGN_DTYPE.itemsize), ("sp_aln", ALN_DTYPE.itemsize), ("sp_k1_seed_hit", K1_HIT_DTYPE.itemsize),
-                       ("sp_hla_best", C.sizeof(sp_hla_best)), ("sp_hla_realign", C.sizeof(sp_hla_realign))):
+                       ("sp_hla_best", C.sizeof(sp_hla_best)), ("sp_hla_realign", C.sizeof(sp_hla_realign)), ("sp_hla_rev_hit", REV_HIT_DTYPE.itemsize)):
         if L.sp_struct_size(name.encode()) != size:
             raise ImportError(f"{path}: {name} is {L.sp_struct_size(name.encode())} bytes in the library, {size} in this binding")
     _lib = L
@@ -1170,6 +1173,13 @@ class HlaDb:
         self.ctx.check(lib().sp_hla_realign_reads(self.ctx._h, self._h, reads._h, _ptr(out), _ptr(cell)))
         return (out, cell) if cells else out
 
+    def realign_reads_rev(self, reads):
+        """sp_hla_realign_reads_rev -> (records as realign_reads gives them, REV_HIT_DTYPE per read: the accepted reverse-strand mapping or allele -1)"""
+        out = np.zeros(reads.n, REALIGN_DTYPE)
+        rev = np.zeros(reads.n, REV_HIT_DTYPE)
+        self.ctx.check(lib().sp_hla_realign_reads_rev(self.ctx._h, self._h, reads._h, _ptr(out), _ptr(rev)))
+        return out, rev
+
     def seed_index_info(self):
         """sp_hla_seed_index_info -> dict(minimizers, distinct, mid_occ, sequences) of the minimizer index of the DNA alleles (built on first use)"""
         out = np.zeros(4, np.int64)
@@ -1222,6 +1232,19 @@ class HlaDb:
         self.ctx.check(lib().sp_hla_diplotype_cohort(self.ctx._h, self._h, n_samples, _ptr(rs), k, _ptr(g), reads._h, _ptr(realign), cf, calls, buf, cap, _ptr(is1)))
         text = lambda j: _cstr(buf, j * cap, cap)
         return [[(calls[s * k + i], text(2 * (s * k + i)), text(2 * (s * k + i) + 1)) for i in range(k)] for s in range(n_samples)], is1[:reads.n].astype(bool)
+
+    def diplotype_cohort_samples(self, n_samples, read_sample, genes, reads, realign, cfgs, cap=16384):
+        """sp_hla_diplotype_cohort_samples: diplotype_cohort with cfgs[sample][gene] -> calls[sample][gene] = (sp_hla_call, consensus1, consensus2)"""
+        k = len(genes)
+        g = np.ascontiguousarray(genes, np.uint32)
+        rs = np.ascontiguousarray(read_sample, np.uint32)
+        cf = (sp_hla_call_config * (k * n_samples))(*[cfgs[s][i] for s in range(n_samples) for i in range(k)])
+        calls = (sp_hla_call * (k * n_samples))()
+        buf = C.create_string_buffer(2 * k * n_samples * cap)
+        realign = np.ascontiguousarray(realign)
+        self.ctx.check(lib().sp_hla_diplotype_cohort_samples(self.ctx._h, self._h, n_samples, _ptr(rs), k, _ptr(g), reads._h, _ptr(realign), cf, calls, buf, cap, None))
+        text = lambda j: _cstr(buf, j * cap, cap)
+        return [[(calls[s * k + i], text(2 * (s * k + i)), text(2 * (s * k + i) + 1)) for i in range(k)] for s in range(n_samples)]
 
     def type_consensus(self, gene, consensus_fwd, require_dna=False, disable_cdna=False, stats=True):
         """score_consensus of the reference: hg38-forward consensus in, best allele + spliced gene-strand cDNA out"""
