@@ -206,6 +206,18 @@ typedef struct { int32_t a, b, q, e, q2, e2, sc_ambi; } sp_affine_opts;         
 typedef struct { int32_t score, nm, a_start, a_end, b_start, b_end; } sp_affine_aln;
 int32_t sp_affine_rescore_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts,
                                 int32_t band, sp_affine_aln* out);
+/* The same pairs WITH the alignment itself: out[p] is what sp_affine_rescore_batch writes for the same call, and cigar[p * cigar_stride ..] holds n_cigar[p] ops in
+ * BAM encoding (len << 4 | op; 7 '=', 8 'X' -- a column with an ambiguous base is an 'X' --, 1 'I' = bases of the query a only, 2 'D' = bases of the target b only)
+ * that cover exactly [b_start, b_end) and [a_start, a_end).  The path is the traceback of the forward pass (oracle/affine.c), not a choice of its own: from the
+ * first best cell by anti-diagonal, then row, back through the predecessor the forward pass took in every cell -- H from the diagonal, then E1, F1, E2, F2, each only
+ * when strictly greater; a gap continued only where that was strictly better than opening it; F ties to the nearest opening -- to the cell the path started in.  So the
+ * ops spell out score, nm and spans of out[p].  n_cigar[p] is the true op count even when it exceeds cigar_stride (the row then holds the first cigar_stride ops,
+ * SP_OK: the events_stride convention); score 0 (nothing aligns, or max_ed < 0 = skip) gives n_cigar 0.  The direction records (one byte per cell) live in a
+ * scratch of up to 512 MB that the call allocates and frees (a batch runs in chunks of pairs whose rows fit it); the device copies of pairs, results and
+ * CIGAR rows (n_pairs * cigar_stride words) are pooled buffers the context keeps, like those of the other batch calls.  A walk that does not arrive in the cell
+ * its path started in -- the forward pass's records do not allow it -- fails the call with SP_ERR_HIP instead of returning a path. */
+int32_t sp_affine_align_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts,
+                              int32_t band, sp_affine_aln* out, uint32_t* cigar, uint32_t cigar_stride, uint32_t* n_cigar);
 
 /* ------------------------------------------------------------------ HLA database
  * Replaces HlaRealigner::new + create_hla_fasta (src/hla/realigner.rs:42-91,497-526) and the per-call
@@ -307,6 +319,13 @@ int32_t sp_hla_realign_reads(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* 
  * as the records (the pick stage writes it), so it costs no per-read audit. */
 typedef struct { int32_t allele, t_len, nm, t_start, t_end, reserved_; } sp_hla_rev_hit;
 int32_t sp_hla_realign_reads_rev(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, sp_hla_realign* out /* n_reads */, sp_hla_rev_hit* rev /* n_reads */);
+/* HOW the accepted reads align: for every record with status 0 the CIGAR (sp_affine_align_batch's encoding and stride convention) of the read (query) against
+ * best_allele in hg38 orientation (target) at the map-hifi scores {1, 4, 6, 2, 26, 1, 1} -- the alignment whose numbers the record's mm2_* fields are: it covers
+ * mm2_t_start..mm2_t_end and mm2_q_start..mm2_q_end, and its X + I + D bases are mm2_nm.  Other records get n_cigar 0.  The band (64 diagonals, 256 for an alignment
+ * across a long gap) and the diagonal are derived from the record's own cell (aln) the way the re-score derived them; a pair whose traceback does not reproduce the
+ * record is run on the other band, and one that matches on neither is an error (SP_ERR_INVALID_ARG: the records are not this read set's). */
+int32_t sp_hla_realign_cigars(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, const sp_hla_realign* records, uint32_t n_reads,
+                              uint32_t* cigar, uint32_t cigar_stride, uint32_t* n_cigar);
 
 /* ------------------------------------------------------------------ K2: consensus -> every allele of a gene
  * Replaces score_read's allele loop + HlaProcessedMatch (src/hla/caller.rs:1411-1510,
@@ -1020,11 +1039,17 @@ int32_t sp_result_save_pharmcat_tsv(sp_result* result, const char* path);
  * sp_aln_strings turns an alignment of this library (sp_align_batch with events; A = query, B = target) into what
  * DetailedMappingStats::from_mapping copies from minimap2 (:148-172): the CIGAR string (M / I / D, no --eqx), the MD tag and
  * match_len (matching bases); query_unmapped / target_unmapped are a_len - (a_end - a_start) and b_len - (b_end - b_start).
+ * sp_affine_cigar_strings does the same for a mapping under the reference's scores (sp_affine_align_batch / sp_hla_realign_cigars): the dna_mapping of a
+ * realigned read's ReadMappingStats (src/hla/caller.rs:575-577; the per-read records a host collects into a `read_debug.json`).
  * `cyp2d6_alleles.json` is written by sp_cyp_alleles_json above. */
 typedef struct { int32_t present, reserved; uint64_t query_len, target_len, match_len, nm, query_unmapped, target_unmapped;
                  const char* cigar; const char* md; } sp_detailed_mapping;                    /* Option<DetailedMappingStats> */
 int32_t sp_aln_strings(const sp_aln* aln, const uint32_t* events, const char* target, uint64_t target_len,
                        char* cigar, uint32_t cigar_cap, char* md, uint32_t md_cap, uint64_t* match_len);
+/* the same strings for a mapping of sp_affine_align_batch / sp_hla_realign_cigars (a = query, b = target): '=' and 'X' merge into M, MD prints the target base
+ * of every 'X' column and ^bases of a deletion, match_len is the number of '=' columns.  SP_ERR_INVALID_ARG when the ops do not consume exactly the spans of aln. */
+int32_t sp_affine_cigar_strings(const sp_affine_aln* aln, const uint32_t* cigar, uint32_t n_cigar, const char* target, uint64_t target_len,
+                                char* cigar_str, uint32_t cigar_cap, char* md, uint32_t md_cap, uint64_t* match_len);
 typedef struct sp_hla_debug sp_hla_debug;
 int32_t sp_hla_debug_create(sp_hla_debug** out);
 void    sp_hla_debug_free(sp_hla_debug* debug);
@@ -1135,7 +1160,8 @@ int32_t sp_fasta_fetch(sp_fasta* fasta, const char* chrom, uint64_t start, uint6
  * reference's default_values (max_sv_length 1,000,000, max_error_rate 0.07, min_cdf_prob 0.001, expected_maf 0.45, min_consensus_fraction 0.10,
  * min_consensus_count 3, dual_max_ed_delta 100, every switch off, every path NULL).  include_set / exclude_set: files of gene names, one per line
  * (load_file_lines); sample_name NULL = the first sample of the VCF; sv_vcf: the SV VCF of every sample unless sp_sample_inputs names one.
- * debug_folder: hla_debug.json (per gene: the consensus matches and DualPassingStats) and cyp2d6_alleles.json are written there, nothing else.
+ * debug_folder: hla_debug.json (per gene: the consensus matches and DualPassingStats) and cyp2d6_alleles.json are written there, and, after
+ * sp_starphase_set_read_debug(handle, 1), read_debug.json (below); nothing else.
  * sp_diplotype_settings_check is check_diplotype_settings (:200-330) without the file-existence checks (a host does those; the command line exits
  * with NOINPUT): SP_ERR_INVALID_ARG with the reference's message in err ("Must provide a VCF file and/or aligned BAM file to perform diplotyping.",
  * "Only one of --exclude-set and --include-set can be specified.", "--max-error-rate must be between 0.0 and 1.0", ...); with BAMs and
@@ -1172,6 +1198,17 @@ const char* sp_starphase_last_error(const sp_starphase* handle);
 /* one sample: *out is a new sp_result (sp_result_free).  Errors as the reference's: a region fetch that fails counts as no reads (the warning is kept:
  * sp_starphase_warnings), an expected CYP2D6 CallerError gives the NO_MATCH entry, anything else fails the call (DATAERR on the command line). */
 int32_t sp_starphase_call(sp_starphase* handle, const sp_sample_inputs* inputs, sp_result** out);
+/* read_debug.json, off by default (enable 0): with the switch on, a call with a debug folder (settings.debug_folder; debug_folders[i] of sp_starphase_call_batch)
+ * also writes <folder>/read_debug.json -- the reference's `read_debug` (src/hla/caller.rs:536,575-577,631-635): an HlaDebug object (sp_hla_debug_*) whose
+ * read_mapping_stats hold, per gene and QNAME, best_match_id / best_match_star and mapping_stats = { <allele id>: { cdna_mapping: null, dna_mapping: { query_len,
+ * target_len, match_len, nm, query_unmapped, target_unmapped, cigar, md } } }; dual_passing_stats is null.  Included are the reads with is_realigned() (a
+ * RealignedHlaRecord exists: the records with status 0), in the bucket of the accepted allele's gene -- exactly the HLA mapping details of the result that are not
+ * ignored.  A status-3 record (the segment did not map forward to the gene reference, src/hla/realigner.rs:332-342) has realigned_record None in the reference:
+ * it keeps its PgxMappingDetails but gets no entry here, like status 1 and 2.  best_match_star is the star string of the read's mapping details ("HLA-A*01:01:01:01").
+ * The mapping is the traceback of the record's own re-score (sp_hla_realign_cigars + sp_affine_cigar_strings): one extra pass over the accepted reads, several times
+ * the cost of the K1 pass it explains.  With the switch off no kernel is launched and no memory is taken for it; every other output is the
+ * same bytes either way. */
+int32_t sp_starphase_set_read_debug(sp_starphase* handle, int32_t enable);
 const char* sp_starphase_warnings(const sp_starphase* handle);      /* the warnings of the last call, one per line */
 /* where the last call spent its time (wall ms): whole call, BAM decode (host, both loci), variant genes, HLA lane, CYP2D6 lane */
 typedef struct { double call_ms, bam_decode_ms, variant_ms, hla_ms, cyp_ms; uint32_t n_hla_reads, n_cyp_reads; } sp_starphase_timing;

@@ -696,6 +696,7 @@ extern "C" {
     pub fn sp_anchor_batch_topk(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, a_idx: *const u32, b_idx: *const u32, n_pairs: u64, topk: i32, diag_out: *mut i32, votes_out: *mut i32) -> i32;
     pub fn sp_align_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, out: *mut sp_aln, events: *mut u32, events_stride: u32) -> i32;
     pub fn sp_affine_rescore_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, band: i32, out: *mut sp_affine_aln) -> i32;
+    pub fn sp_affine_align_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, band: i32, out: *mut sp_affine_aln, cigar: *mut u32, cigar_stride: u32, n_cigar: *mut u32) -> i32;
     pub fn sp_hla_db_create(ctx: *mut sp_ctx, desc: *const sp_hla_db_desc, out: *mut *mut sp_hla_db) -> i32;
     pub fn sp_hla_db_free(db: *mut sp_hla_db);
     pub fn sp_hla_seed_index_info(ctx: *mut sp_ctx, db: *const sp_hla_db, out: *mut i64) -> i32;
@@ -703,6 +704,7 @@ extern "C" {
     pub fn sp_hla_realign_seeded_audit(ctx: *mut sp_ctx, db: *const sp_hla_db, reads: *const sp_seqset, read: u32, chains: *mut i32, chain_cap: u32, n_chains: *mut u32, hits: *mut sp_k1_seed_hit, n_hits: *mut u32, pick: *mut i32, counters: *mut u64) -> i32;
     pub fn sp_hla_realign_reads(ctx: *mut sp_ctx, db: *const sp_hla_db, reads: *const sp_seqset, out: *mut sp_hla_realign, cell_out: *mut u32) -> i32;
     pub fn sp_hla_realign_reads_rev(ctx: *mut sp_ctx, db: *const sp_hla_db, reads: *const sp_seqset, out: *mut sp_hla_realign, rev: *mut sp_hla_rev_hit) -> i32;
+    pub fn sp_hla_realign_cigars(ctx: *mut sp_ctx, db: *const sp_hla_db, reads: *const sp_seqset, records: *const sp_hla_realign, n_reads: u32, cigar: *mut u32, cigar_stride: u32, n_cigar: *mut u32) -> i32;
     pub fn sp_hla_score_consensus(ctx: *mut sp_ctx, db: *const sp_hla_db, gene: u32, cons_dna: *const c_char, cons_dna_len: u32, cons_cdna: *const c_char, cons_cdna_len: u32, require_dna: i32, disable_cdna: i32, best: *mut sp_hla_best, stats: *mut i32) -> i32;
     pub fn sp_hla_score_consensus_batch(ctx: *mut sp_ctx, db: *const sp_hla_db, n: u32, genes: *const u32, cons_dna: *const *const c_char, cons_dna_len: *const u32, cons_cdna: *const *const c_char, cons_cdna_len: *const u32, require_dna: i32, disable_cdna: i32, best: *mut sp_hla_best) -> i32;
     pub fn sp_hla_type_consensus(ctx: *mut sp_ctx, db: *const sp_hla_db, gene: u32, consensus_fwd: *const c_char, consensus_len: u32, require_dna: i32, disable_cdna: i32, best: *mut sp_hla_best, stats: *mut i32, cdna_out: *mut c_char, cdna_cap: u32, cdna_len: *mut u32) -> i32;
@@ -793,6 +795,7 @@ extern "C" {
     pub fn sp_result_pharmcat_tsv(result: *mut sp_result, text: *mut *const c_char, len: *mut u64) -> i32;
     pub fn sp_result_save_pharmcat_tsv(result: *mut sp_result, path: *const c_char) -> i32;
     pub fn sp_aln_strings(aln: *const sp_aln, events: *const u32, target: *const c_char, target_len: u64, cigar: *mut c_char, cigar_cap: u32, md: *mut c_char, md_cap: u32, match_len: *mut u64) -> i32;
+    pub fn sp_affine_cigar_strings(aln: *const sp_affine_aln, cigar: *const u32, n_cigar: u32, target: *const c_char, target_len: u64, cigar_str: *mut c_char, cigar_cap: u32, md: *mut c_char, md_cap: u32, match_len: *mut u64) -> i32;
     pub fn sp_hla_debug_create(out: *mut *mut sp_hla_debug) -> i32;
     pub fn sp_hla_debug_free(debug: *mut sp_hla_debug);
     pub fn sp_hla_debug_last_error(debug: *const sp_hla_debug) -> *const c_char;
@@ -834,6 +837,7 @@ extern "C" {
     pub fn sp_starphase_free(handle: *mut sp_starphase);
     pub fn sp_starphase_last_error(handle: *const sp_starphase) -> *const c_char;
     pub fn sp_starphase_call(handle: *mut sp_starphase, inputs: *const sp_sample_inputs, out: *mut *mut sp_result) -> i32;
+    pub fn sp_starphase_set_read_debug(handle: *mut sp_starphase, enable: i32) -> i32;
     pub fn sp_starphase_warnings(handle: *const sp_starphase) -> *const c_char;
     pub fn sp_starphase_last_timing(handle: *const sp_starphase, out: *mut sp_starphase_timing) -> i32;
     pub fn sp_starphase_call_batch(handle: *mut sp_starphase, n: u32, inputs: *const sp_sample_inputs, debug_folders: *const *const c_char, opts: *const sp_batch_options, out: *mut *mut sp_result, sample_rc: *mut i32) -> i32;

@@ -13,7 +13,7 @@
 // j' < j of H(j') - q - (j - j') e is a max-plus prefix scan over the lanes -- the gfx9 DPP scan (row_shr 1, 2, 4, 8, row_bcast 15 / 31) on a packed
 // key (score + position * e, ties to the nearest opening, as the sequential recurrence decides them) with the path's counters riding along.  Every state
 // carries the mismatch + gap + ambiguous bases of its path and the cell it began in: the result needs no traceback and no memory beyond the two packed
-// sequences in LDS.
+// sequences in LDS.  sp_affine_align_batch (affine_tb_kernel, below) is the same pass with a direction record per cell and the walk back through them: the path itself.
 #include "sp_internal.h"
 #include "sp_wfa.hip.h"
 #include <mutex>
@@ -228,6 +228,194 @@ __global__ __launch_bounds__(64) void affine_kernel(SeqSetView A, SeqSetView B, 
         if (bs > 0) { res.score = bs; res.nm = (int32_t)bm1; res.b_start = (int32_t)(bm0 >> 16); res.b_end = bi + 1; res.a_start = (int32_t)(bm0 & 0xFFFFu); res.a_end = bj + 1; }
         out[p] = res;
     }
+}
+
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// The same DP with its traceback (sp_affine_align_batch): HOW a pair aligns under the reference's scores.  The forward pass is affine_kernel's over all rows of the
+// band (no AfWin / AfMid shortcuts), cell for cell, and additionally leaves ONE byte per cell in global memory, row by row:
+//   bits 0-2  where H came from: the diagonal, E1, F1, E2, F2 (in the order of ties, each replacing only when strictly greater), the diagonal of a cell the path
+//             STARTS in (the h.s <= 0 reset), or nothing (H = 0 / outside the rectangle)
+//   bit 3 / 4 E1 / E2 of this cell continue the gap of the cell above (strictly better than opening one there)
+//   bit 5 / 6 F1 / F2 of this cell continue the gap of the cell to the left (the scan key's source is not the nearest cell)
+//   bit 7     the column of this cell is a mismatch or holds an ambiguous base
+// The path is then not chosen afresh: from the forward pass's end cell the wave walks these records back to the cell the path started in.  The wave stages
+// AF_TB_TILE bytes of direction rows into LDS at a time (over the packed sequences, which the walk does not need: bit 7) and lane 0 follows them, writing
+// run-length ops backwards into the pair's own scratch behind its direction rows (a row adds at most two ops: a run of F steps and one step upwards); at the end
+// they are copied out in forward order, the first `stride` of them.  Score, NM and spans are the forward pass's own.
+// ------------------------------------------------------------------------------------------------------------------------------
+constexpr int AF_TB_TILE = 8192;
+constexpr uint32_t AF_TB_LOST = 0xFFFFFFFFu;               // n_cigar of a pair whose walk did not arrive: the host turns it into an error
+constexpr uint32_t AF_D_DIAG = 0, AF_D_E1 = 1, AF_D_F1 = 2, AF_D_E2 = 3, AF_D_F2 = 4, AF_D_START = 5, AF_D_NONE = 6;
+constexpr uint32_t AF_D_E1C = 0x08, AF_D_E2C = 0x10, AF_D_F1C = 0x20, AF_D_F2C = 0x40, AF_D_X = 0x80;
+
+template <int DPL, bool HASN>
+__global__ __launch_bounds__(64) void affine_tb_kernel(SeqSetView A, SeqSetView B, const AfPair* __restrict__ pairs, uint32_t n_pairs, sp_affine_opts o, sp_affine_aln* __restrict__ out,
+                                                        int t_words_max, uint8_t* __restrict__ scratch, const uint64_t* __restrict__ off, uint32_t* __restrict__ cigar, uint32_t stride,
+                                                        uint32_t* __restrict__ n_cigar) {
+    extern __shared__ uint32_t lds[];
+    const uint32_t p = blockIdx.x;
+    if (p >= n_pairs) return;
+    const int lane = threadIdx.x;
+    const AfPair pr = pairs[p];
+    const int tlen = B.len[pr.b], qlen = A.len[pr.a];
+    sp_affine_aln res; res.score = 0; res.nm = 0; res.a_start = res.a_end = res.b_start = res.b_end = 0;
+    constexpr int BAND = 64 * DPL;
+    const int klo = -pr.diag - BAND / 2;
+    int i_lo = -(klo + BAND - 1); if (i_lo < 0) i_lo = 0;
+    int i_hi = qlen - 1 - klo; if (i_hi > tlen - 1) i_hi = tlen - 1;
+    if (pr.pad < 0 || tlen <= 0 || qlen <= 0 || i_lo > i_hi) { if (lane == 0) { out[p] = res; n_cigar[p] = 0; } return; }
+    constexpr bool hasn = HASN;
+    const int tw0 = i_lo >> 4, tw1 = (i_hi >> 4) + 1;
+    int q_lo = i_lo + klo; if (q_lo < 0) q_lo = 0;
+    int q_hi = i_hi + klo + BAND - 1; if (q_hi > qlen - 1) q_hi = qlen - 1;
+    const int qw0 = q_lo >> 4, qw1 = (q_hi >> 4) + 1;
+    uint32_t* LT = lds; uint32_t* LQ = LT + t_words_max; uint32_t* NT = LQ + t_words_max + 2 * BAND / 16 + 8; uint32_t* NQ = NT + t_words_max;
+    {
+        const uint32_t* tw = B.words + B.word_off[pr.b]; const uint32_t* qw = A.words + A.word_off[pr.a];
+        const uint32_t* tn = B.nplane ? B.nplane + B.word_off[pr.b] : nullptr; const uint32_t* qn = A.nplane ? A.nplane + A.word_off[pr.a] : nullptr;
+        for (int w = lane; w < tw1 - tw0; w += SP_WAVE) { LT[w] = tw[tw0 + w]; if (hasn) NT[w] = tn ? tn[tw0 + w] : 0u; }
+        for (int w = lane; w < qw1 - qw0; w += SP_WAVE) { LQ[w] = qw[qw0 + w]; if (hasn) NQ[w] = qn ? qn[qw0 + w] : 0u; }
+    }
+    spw::wave_lds_sync();
+    auto base_of = [&](const uint32_t* W, const uint32_t* N, int pos, int w0) {
+        const int w = (pos >> 4) - w0; const uint32_t sh = (uint32_t)(pos & 15) << 1;
+        if (hasn && ((N[w] >> sh) & 1u)) return 4;
+        return (int)((W[w] >> sh) & 3u);
+    };
+    const int rows = i_hi - i_lo + 1;                       // (the host sized this pair's scratch from the same numbers: af_tb_rows)
+    uint8_t* dirs = scratch + off[p];
+    AfState H[DPL], E1[DPL], E2[DPL];
+#pragma unroll
+    for (int c = 0; c < DPL; ++c) H[c] = E1[c] = E2[c] = af_none();
+    int bs = 0, bi = -1, bj = -1; uint32_t bm0 = 0, bm1 = 0;
+    const int q1 = o.q, e1 = o.e, q2 = o.q2, e2 = o.e2;
+    for (int i = i_lo; i <= i_hi; ++i) {
+        const int ct = base_of(LT, NT, i, tw0);
+        const AfState upH = af_from_upper(H[0]), upE1 = af_from_upper(E1[0]), upE2 = af_from_upper(E2[0]);
+        AfState hA[DPL], e1n[DPL], e2n[DPL]; AfKey k1[DPL], k2[DPL]; bool valid[DPL]; uint32_t dir[DPL];
+#pragma unroll
+        for (int c = 0; c < DPL; ++c) {
+            const int idx = lane * DPL + c, j = i + klo + idx;
+            valid[c] = (unsigned)j < (unsigned)qlen;
+            const AfState hu = c + 1 < DPL ? H[c + 1] : upH, eu = c + 1 < DPL ? E1[c + 1] : upE1, eu2 = c + 1 < DPL ? E2[c + 1] : upE2;
+            AfState a1, a2; uint32_t d = AF_D_DIAG;
+            { const int eo = hu.s - q1; if (eu.s > eo) { a1 = eu; a1.s = eu.s - e1; d |= AF_D_E1C; } else { a1 = hu; a1.s = eo - e1; } a1.m1 += 1; }
+            { const int eo = hu.s - q2; if (eu2.s > eo) { a2 = eu2; a2.s = eu2.s - e2; d |= AF_D_E2C; } else { a2 = hu; a2.s = eo - e2; } a2.m1 += 1; }
+            if (a1.s < AF_NEG) a1.s = AF_NEG;
+            if (a2.s < AF_NEG) a2.s = AF_NEG;
+            AfState h = H[c];
+            const int cq = valid[c] ? base_of(LQ, NQ, j, qw0) : 4;
+            const bool ambi = ct > 3 || cq > 3;
+            const int sub = ambi ? -o.sc_ambi : (ct == cq ? o.a : -o.b);
+            if (h.s <= 0) { h.s = 0; h.m1 = 0; h.m0 = ((uint32_t)i << 16) | (uint32_t)(j & 0xFFFF); d |= AF_D_START; }
+            h.s += sub; h.m1 += (ambi || ct != cq) ? 1u : 0u;
+            if (ambi || ct != cq) d |= AF_D_X;
+            if (a1.s > h.s) { h = a1; d = (d & ~7u) | AF_D_E1; }
+            if (!valid[c]) { h = af_none(); a1 = af_none(); a2 = af_none(); }
+            hA[c] = h; e1n[c] = a1; e2n[c] = a2; dir[c] = d;
+            AfState src = h; if (a2.s > src.s) src = a2;
+            if (src.s <= 0) { src.s = 0; }
+            const bool offer = valid[c] && src.s > 0;
+            k1[c].k = offer ? (((uint32_t)(src.s + idx * e1) + AF_BIAS) << 8 | (uint32_t)idx) : 0u; k1[c].m0 = src.m0; k1[c].m1 = src.m1;
+            k2[c].k = offer ? (((uint32_t)(src.s + idx * e2) + AF_BIAS) << 8 | (uint32_t)idx) : 0u; k2[c].m0 = src.m0; k2[c].m1 = src.m1;
+        }
+        AfKey in1 = k1[0], in2 = k2[0];
+#pragma unroll
+        for (int c = 1; c < DPL; ++c) { in1 = af_max(in1, k1[c]); in2 = af_max(in2, k2[c]); }
+        in1 = af_from_lower(af_scan(in1)); in2 = af_from_lower(af_scan(in2));
+        uint32_t packed = 0;
+#pragma unroll
+        for (int c = 0; c < DPL; ++c) {
+            const int idx = lane * DPL + c, j = i + klo + idx;
+            AfState f1 = af_none(), f2 = af_none(); uint32_t d = dir[c];
+            if (in1.k) { const int src_idx = (int)(in1.k & 0xFFu), v = (int)((in1.k >> 8) - AF_BIAS); f1.s = v - q1 - idx * e1; f1.m0 = in1.m0; f1.m1 = in1.m1 + (uint32_t)(idx - src_idx); if (src_idx < idx - 1) d |= AF_D_F1C; }
+            if (in2.k) { const int src_idx = (int)(in2.k & 0xFFu), v = (int)((in2.k >> 8) - AF_BIAS); f2.s = v - q2 - idx * e2; f2.m0 = in2.m0; f2.m1 = in2.m1 + (uint32_t)(idx - src_idx); if (src_idx < idx - 1) d |= AF_D_F2C; }
+            AfState h = hA[c];
+            if (valid[c]) {
+                if (f1.s > h.s) { h = f1; d = (d & ~7u) | AF_D_F1; }
+                if (e2n[c].s > h.s) { h = e2n[c]; d = (d & ~7u) | AF_D_E2; }
+                if (f2.s > h.s) { h = f2; d = (d & ~7u) | AF_D_F2; }
+                if (h.s <= 0) { h.s = 0; h.m1 = 0; h.m0 = ((uint32_t)i << 16) | (uint32_t)(j & 0xFFFF); d = (d & ~7u) | AF_D_NONE; }
+                const bool better = h.s > bs || (h.s == bs && h.s > 0 && (i + j < bi + bj || (i + j == bi + bj && i < bi)));
+                bs = better ? h.s : bs; bi = better ? i : bi; bj = better ? j : bj; bm0 = better ? h.m0 : bm0; bm1 = better ? h.m1 : bm1;
+            } else d = AF_D_NONE;
+            H[c] = h; E1[c] = e1n[c]; E2[c] = e2n[c];
+            in1 = af_max(in1, k1[c]); in2 = af_max(in2, k2[c]);
+            packed |= d << (8 * c);
+        }
+        // the row's records: lane's DPL cells are DPL consecutive bytes -- 64 (one byte a lane) or 256 (one word a lane) contiguous bytes per wave
+        if (DPL == 1) dirs[(size_t)(i - i_lo) * BAND + lane] = (uint8_t)packed;
+        else ((uint32_t*)dirs)[(size_t)(i - i_lo) * (BAND / 4) + lane] = packed;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const int os = __shfl_xor(bs, d), oi = __shfl_xor(bi, d), oj = __shfl_xor(bj, d);
+        const uint32_t om0 = (uint32_t)__shfl_xor((int)bm0, d), om1 = (uint32_t)__shfl_xor((int)bm1, d);
+        if (os > bs || (os == bs && os > 0 && (oi + oj < bi + bj || (oi + oj == bi + bj && oi < bi)))) { bs = os; bi = oi; bj = oj; bm0 = om0; bm1 = om1; }
+    }
+    if (bs <= 0) { if (lane == 0) { out[p] = res; n_cigar[p] = 0; } return; }
+    // the walk back.  The rows were written by all lanes and are read by all lanes: they are this workgroup's own, one release / acquire at its scope orders them
+    __threadfence_block();
+    uint8_t* tile = (uint8_t*)lds;
+    uint32_t* ops = (uint32_t*)(dirs + (size_t)rows * BAND);
+    const uint32_t ops_cap = 2u * (uint32_t)rows + 2u;
+    constexpr int TR = AF_TB_TILE / BAND;
+    int ci = bi, cidx = bj - bi - klo, st = 0, done = 0;       // the cell the walk is in (row, diagonal index), its state (0 = H, else AF_D_E1 .. AF_D_F2), 1 = at the start, 2 = lost
+    uint32_t n_ops = 0, run_op = 0xF, run_len = 0;
+    auto emit = [&](uint32_t op) {
+        if (op == run_op) { ++run_len; return; }
+        if (run_len) { if (n_ops < ops_cap) ops[n_ops] = run_len << 4 | run_op; ++n_ops; }
+        run_op = op; run_len = 1;
+    };
+    while (!done) {
+        const int r1 = ci - i_lo, r0 = r1 - TR + 1 > 0 ? r1 - TR + 1 : 0;
+        spw::wave_lds_sync();                               // (the sequences, or the tile before this one, have been read)
+        {
+            const uint4* src = (const uint4*)(dirs + (size_t)r0 * BAND); const int n16 = (r1 - r0 + 1) * (BAND / 16);
+            for (int w = lane; w < n16; w += SP_WAVE) ((uint4*)tile)[w] = src[w];
+        }
+        spw::wave_lds_sync();
+        if (lane == 0) {
+            while (true) {
+                const int r = ci - i_lo - r0;
+                if (r < 0) break;                           // the next tile
+                if ((unsigned)cidx >= (unsigned)BAND) { done = 2; break; }
+                const uint32_t d = tile[r * BAND + cidx];
+                if (st == 0) {
+                    const uint32_t h = d & 7u;
+                    if (h == AF_D_DIAG || h == AF_D_START) { emit((d & AF_D_X) ? 8u : 7u); --ci; if (h == AF_D_START) { done = 1; break; } continue; }
+                    if (h >= AF_D_NONE) { done = 2; break; }
+                    st = (int)h;
+                }
+                if (st == (int)AF_D_E1 || st == (int)AF_D_E2) {            // a base of the target only; the gap came from the cell above: the next diagonal of the row before
+                    emit(2u); const bool cont = d & (st == (int)AF_D_E1 ? AF_D_E1C : AF_D_E2C); --ci; ++cidx; if (!cont) st = 0;
+                } else {                                                      // a base of the query only; from the cell to the left
+                    emit(1u); const bool cont = d & (st == (int)AF_D_F1 ? AF_D_F1C : AF_D_F2C); --cidx; if (!cont) st = 0;
+                }
+            }
+        }
+        ci = __shfl(ci, 0); done = __shfl(done, 0);
+        if (ci < i_lo && !done) done = 2;
+    }
+    if (lane == 0) {
+        emit(0xE);                                          // closes the last run
+        res.score = bs; res.nm = (int32_t)bm1; res.b_start = (int32_t)(bm0 >> 16); res.b_end = bi + 1; res.a_start = (int32_t)(bm0 & 0xFFFFu); res.a_end = bj + 1;
+        // a walk that left the band, met a cell nothing ends in or ran out of ops (none of which the forward pass's records allow) is reported, not passed on as a path
+        const bool lost = done != 1 || n_ops > ops_cap;
+        out[p] = res; n_cigar[p] = lost ? AF_TB_LOST : n_ops;
+        const uint32_t n_out = lost ? 0u : (n_ops < stride ? n_ops : stride);
+        for (uint32_t k = 0; k < n_out; ++k) cigar[(size_t)p * stride + k] = ops[n_ops - 1 - k];
+    }
+}
+
+// rows of the target that hold a cell of the pair's band (what both kernels run), 0: nothing to do
+inline int64_t af_tb_rows(int tlen, int qlen, int diag, int band) {
+    const int64_t klo = -(int64_t)diag - band / 2;
+    int64_t i_lo = -(klo + band - 1); if (i_lo < 0) i_lo = 0;
+    int64_t i_hi = (int64_t)qlen - 1 - klo; if (i_hi > (int64_t)tlen - 1) i_hi = (int64_t)tlen - 1;
+    if (tlen <= 0 || qlen <= 0 || i_lo > i_hi) return 0;
+    return i_hi - i_lo + 1;
 }
 
 } // namespace
@@ -451,5 +639,70 @@ extern "C" int32_t sp_affine_rescore_batch(sp_ctx* ctx, const sp_seqset* A, cons
     if (rc != SP_OK) return rc;
     SP_HIP_CHECK(ctx, hipMemcpyAsync(out, d_out, n_pairs * sizeof(sp_affine_aln), hipMemcpyDeviceToHost, ctx->stream));
     SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return SP_OK;
+}
+
+// The direction rows of a batch would be a few GB at once (10,000 reads against 3.5 - 16 kb alleles: rows x 64 bytes each), so the batch runs in chunks of pairs
+// whose rows fit AF_TB_BUDGET bytes of one pooled scratch (a single pair is at most 65,535 rows x 256 bytes = 16 MB); the launches of a call follow one another on
+// the context's stream and reuse it.
+constexpr size_t AF_TB_BUDGET = 512ull << 20;
+
+extern "C" int32_t sp_affine_align_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts,
+                                         int32_t band, sp_affine_aln* out, uint32_t* cigar, uint32_t cigar_stride, uint32_t* n_cigar) {
+    if (!ctx || !A || !B || !opts || (n_pairs && (!pairs || !out || !n_cigar || (cigar_stride && !cigar)))) return SP_ERR_INVALID_ARG;
+    if (n_pairs == 0) return SP_OK;
+    if (n_pairs > 0xFFFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "affine: too many pairs");
+    if (band != 64 && band != 256) return sp_fail(ctx, SP_ERR_INVALID_ARG, "affine: band must be 64 or 256");
+    if (B->max_len > 65535 || A->max_len > 65535) return sp_fail(ctx, SP_ERR_TOO_LONG, "affine: sequences of up to 65,535 bases");
+    (void)hipSetDevice(ctx->device);
+    for (uint64_t i = 0; i < n_pairs; ++i) if (pairs[i].a >= A->n || pairs[i].b >= B->n) return sp_fail(ctx, SP_ERR_INVALID_ARG, "affine: index out of range");
+    // every pair's place in the scratch of its chunk: rows x band direction bytes, then 2 rows + 2 op words
+    std::vector<uint64_t> off(n_pairs); std::vector<uint64_t> chunk_end;         // chunk_end: one past the last pair of each chunk
+    size_t used = 0, largest = 0;
+    for (uint64_t i = 0; i < n_pairs; ++i) {
+        const int64_t rows = pairs[i].max_ed < 0 ? 0 : af_tb_rows(B->h_len[pairs[i].b], A->h_len[pairs[i].a], pairs[i].diag, band);
+        const size_t bytes = rows ? (((size_t)rows * band + ((size_t)2 * rows + 2) * 4 + 15) & ~(size_t)15) : 0;
+        if (used && used + bytes > AF_TB_BUDGET) { chunk_end.push_back(i); used = 0; }
+        off[i] = used; used += bytes; largest = std::max(largest, used);
+    }
+    chunk_end.push_back(n_pairs);
+    void* d_pairs = sp_pool(ctx, "affine_pairs", n_pairs * sizeof(sp_pair));
+    sp_affine_aln* d_out = (sp_affine_aln*)sp_pool(ctx, "affine_out", n_pairs * sizeof(sp_affine_aln));
+    uint64_t* d_off = (uint64_t*)sp_pool(ctx, "affine_tb_off", n_pairs * 8);
+    uint32_t* d_nc = (uint32_t*)sp_pool(ctx, "affine_tb_n", n_pairs * 4);
+    uint32_t* d_cg = (uint32_t*)sp_pool(ctx, "affine_tb_cigar", std::max<size_t>(16, n_pairs * (size_t)cigar_stride * 4));
+    if (!d_pairs || !d_out || !d_off || !d_nc || !d_cg) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "affine traceback buffers");
+    // the direction rows are the call's own, not the pool's: up to AF_TB_BUDGET bytes that a context which has written one debug file should not keep
+    struct Rows { uint8_t* p = nullptr; ~Rows() { if (p) (void)hipFree(p); } } rows_buf;
+    if (hipMalloc((void**)&rows_buf.p, std::max<size_t>(16, largest)) != hipSuccess) { rows_buf.p = nullptr; return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "affine traceback: direction rows"); }
+    uint8_t* d_scr = rows_buf.p;
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(d_pairs, pairs, n_pairs * sizeof(sp_pair), hipMemcpyHostToDevice, ctx->stream));
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(d_off, off.data(), n_pairs * 8, hipMemcpyHostToDevice, ctx->stream));
+    const int t_words_max = (B->max_len >> 4) + 4;
+    const size_t lds_bytes = std::max<size_t>(AF_TB_TILE, sizeof(uint32_t) * (size_t)(4 * t_words_max + 2 * (2 * band / 16 + 8)));
+    const bool hasn = A->has_n || B->has_n;
+#define SP_AF_TB_ATTR(D, N) (void)hipFuncSetAttribute((const void*)affine_tb_kernel<D, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)
+    if (band == 64) { if (hasn) SP_AF_TB_ATTR(1, true); else SP_AF_TB_ATTR(1, false); }
+    else { if (hasn) SP_AF_TB_ATTR(4, true); else SP_AF_TB_ATTR(4, false); }
+    uint64_t p0 = 0;
+    for (const uint64_t p1 : chunk_end) {
+        const uint32_t n = (uint32_t)(p1 - p0);
+        ProfScope ps(ctx, "affine_align", n);
+#define SP_AF_TB_LAUNCH(D, N) do { \
+        hipLaunchKernelGGL((affine_tb_kernel<D, N>), dim3(n), dim3(64), lds_bytes, ctx->stream, A->view(), B->view(), (const AfPair*)d_pairs + p0, n, *opts, d_out + p0, t_words_max, \
+                           d_scr, d_off + p0, d_cg + p0 * cigar_stride, cigar_stride, d_nc + p0); } while (0)
+        if (band == 64) { if (hasn) SP_AF_TB_LAUNCH(1, true); else SP_AF_TB_LAUNCH(1, false); }
+        else { if (hasn) SP_AF_TB_LAUNCH(4, true); else SP_AF_TB_LAUNCH(4, false); }
+#undef SP_AF_TB_LAUNCH
+#undef SP_AF_TB_ATTR
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "affine traceback launch failed");
+        p0 = p1;
+    }
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(out, d_out, n_pairs * sizeof(sp_affine_aln), hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(n_cigar, d_nc, n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (cigar_stride) SP_HIP_CHECK(ctx, hipMemcpyAsync(cigar, d_cg, n_pairs * (size_t)cigar_stride * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint64_t i = 0; i < n_pairs; ++i)
+        if (n_cigar[i] == AF_TB_LOST) { n_cigar[i] = 0; return sp_fail(ctx, SP_ERR_HIP, "affine traceback: the walk of pair " + std::to_string(i) + " did not reach the cell its path started in"); }
     return SP_OK;
 }

@@ -113,6 +113,7 @@ struct sp_starphase {
     // settings (strings copied)
     sp_diplotype_settings s{};
     std::string include_set, exclude_set, sample_name, sv_vcf, debug_folder;
+    int32_t read_debug = 0;                          // sp_starphase_set_read_debug: a debug folder also receives read_debug.json
     std::set<std::string> include, exclude; bool has_include = false, has_exclude = false;
     // chromosomes the variant genes were normalised against (sp_variant_gene keeps a pointer)
     std::map<std::string, std::string> chrom_seq;
@@ -468,10 +469,65 @@ void hla_configs(sp_starphase* h, const sp_hla_realign* rec, uint32_t n, sp_hla_
 
 struct RevHit { int32_t allele = -1; uint64_t t_len = 0, nm = 0, unmapped = 0; };
 
+// read_debug.json (sp_starphase_set_read_debug): the reference's `read_debug` (src/hla/caller.rs:536,575-577,631-635) -- an HlaDebug whose read_mapping_stats hold, per
+// gene and QNAME, the ReadMappingStats realign_record made for a read it realigned (src/hla/realigner.rs:198-201): the accepted allele as best match and the one DNA
+// mapping against it with minimap2's CIGAR and MD; no dual statistics.  Included are the reads with is_realigned() -- a RealignedHlaRecord exists --, in the bucket of
+// the accepted allele's gene: the records with status 0.  A status-3 record (the segment did not map forward to the gene reference, realigner.rs:332-342) has
+// realigned_record None in the reference: its PgxMappingDetails are kept but it gets no read_debug entry, like status 1 and 2.  best_match_star is the star string of
+// the read's PgxMappingDetails ("HLA-A*01:01:01:01"), as this library's hla_debug.json writes it for the consensuses.
+// The CIGARs come from sp_hla_realign_cigars on the set the K1 pass ran on (positions of the set; a row too short for a read's ops is run again with room).
+struct ReadCigars { std::vector<uint32_t> cigar, n; uint32_t stride = 0; };
+int32_t read_cigars(sp_starphase* h, const sp_seqset* set, const sp_hla_realign* rec, uint32_t R, ReadCigars* out, std::string& err) {
+    out->stride = 256; out->n.assign(R, 0);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        out->cigar.assign((size_t)R * out->stride, 0);
+        const int32_t rc = sp_hla_realign_cigars(h->ctx, h->hla, set, rec, R, out->cigar.data(), out->stride, out->n.data());
+        if (rc != SP_OK) { err = "sp_hla_realign_cigars: " + opt(sp_last_error(h->ctx)); return rc; }
+        uint32_t most = 0;
+        for (uint32_t x : out->n) most = std::max(most, x);
+        if (most <= out->stride) break;
+        out->stride = most;
+    }
+    return SP_OK;
+}
+int32_t read_debug_save(sp_starphase* h, const std::vector<Read4>& reads, const std::vector<uint32_t>& pos_of, const sp_hla_realign* rec, const ReadCigars& cg,
+                        uint32_t cg_first, const std::string& debug_folder, std::string& err) {
+    sp_hla_debug* dbg = nullptr;
+    sp_hla_debug_create(&dbg);
+    std::unique_ptr<sp_hla_debug, void (*)(sp_hla_debug*)> guard(dbg, sp_hla_debug_free);
+    std::map<int32_t, std::string> target;                           // the accepted alleles in hg38 orientation
+    std::vector<char> cs, md;
+    for (uint32_t r = 0; r < reads.size(); ++r) {
+        const sp_hla_realign& q = rec[pos_of[r]];
+        if (q.status != 0 || q.best_allele < 0) continue;
+        const uint32_t a = (uint32_t)q.best_allele;
+        auto t = target.find(q.best_allele);
+        if (t == target.end()) t = target.emplace(q.best_allele, spi_hla_allele_fwd(h->ctx, h->hla, a)).first;
+        const size_t at = (size_t)cg_first + pos_of[r];
+        const sp_affine_aln aln = { q.mm2_score, q.mm2_nm, q.mm2_q_start, q.mm2_q_end, q.mm2_t_start, q.mm2_t_end };
+        const size_t cap = 12 * ((size_t)cg.n[at] + 2) + (size_t)std::max(0, q.mm2_t_end - q.mm2_t_start) + 32;
+        cs.resize(cap); md.resize(cap);
+        uint64_t match_len = 0;
+        int32_t rc = sp_affine_cigar_strings(&aln, cg.cigar.data() + at * cg.stride, cg.n[at], t->second.data(), t->second.size(), cs.data(), (uint32_t)cap, md.data(), (uint32_t)cap, &match_len);
+        if (rc != SP_OK) { err = "read_debug.json: the CIGAR of " + reads[r].qname + " does not spell its mapping"; return rc; }
+        sp_detailed_mapping dm{}; dm.present = 1;
+        dm.query_len = reads[r].len; dm.target_len = t->second.size(); dm.match_len = match_len; dm.nm = (uint64_t)q.mm2_nm;
+        dm.query_unmapped = reads[r].len - (uint64_t)(q.mm2_q_end - q.mm2_q_start); dm.target_unmapped = t->second.size() - (uint64_t)(q.mm2_t_end - q.mm2_t_start);
+        dm.cigar = cs.data(); dm.md = md.data();
+        const std::string& gene = h->hgenes[h->a_gene[a]].name; const std::string star = gene + "*" + h->a_star[a];
+        rc = sp_hla_debug_add_read(dbg, gene.c_str(), reads[r].qname.c_str(), h->a_id[a].c_str(), star.c_str());
+        if (rc == SP_OK) rc = sp_hla_debug_add_mapping(dbg, gene.c_str(), reads[r].qname.c_str(), h->a_id[a].c_str(), nullptr, &dm);
+        if (rc != SP_OK) { err = std::string("read_debug.json: ") + sp_hla_debug_last_error(dbg); return rc; }
+    }
+    const std::string path = debug_folder + "/read_debug.json";
+    if (sp_hla_debug_save(dbg, path.c_str()) != SP_OK) { err = "Error while writing " + path; return SP_ERR_INVALID_ARG; }
+    return SP_OK;
+}
+
 // the HLA entries of one sample: PgxMappingDetails of every read, the diplotypes, hla_debug.json.  rec / rev: by position in QNAME order
 int32_t hla_package(sp_starphase* h, const std::vector<Read4>& reads, const std::vector<uint32_t>& searched, const std::vector<uint32_t>& order,
                     const sp_hla_realign* rec, const std::map<uint32_t, RevHit>& rev, const sp_hla_call* calls, const std::string& debug_folder,
-                    std::vector<Entry>& out, std::string& err) {
+                    std::vector<Entry>& out, std::string& err, const ReadCigars* cigars = nullptr, uint32_t cigars_first = 0) {
     const size_t G = h->hgenes.size();
     // PgxMappingDetails of every read, in the order the loop met them, in the bucket of its gene (realigned) or of the gene searched (ignored)
     std::vector<std::unique_ptr<GeneDetailsPtr>> det(G);
@@ -530,6 +586,7 @@ int32_t hla_package(sp_starphase* h, const std::vector<Read4>& reads, const std:
         const int32_t rc = sp_hla_debug_save(dbg, path.c_str());
         sp_hla_debug_free(dbg);
         if (rc != SP_OK) { err = "Error while writing " + path; return rc; }
+        if (cigars) { const int32_t rd = read_debug_save(h, reads, pos_of, rec, *cigars, cigars_first, debug_folder, err); if (rd != SP_OK) return rd; }
     }
     return SP_OK;
 }
@@ -551,6 +608,8 @@ int32_t hla_lane(sp_starphase* h, const std::vector<std::string>& bams, std::vec
     const uint32_t cap = 1 << 16;
     std::vector<char> cons(G * 2 * (size_t)cap, 0);
     std::vector<sp_hla_call_config> cfg(G);
+    const bool want_cigars = h->read_debug && !h->debug_folder.empty();
+    ReadCigars cigars;
     if (!reads.empty()) {
         sp_seqset* set = nullptr;
         int32_t rc = upload_reads(h->ctx, reads, order, &set);
@@ -563,6 +622,7 @@ int32_t hla_lane(sp_starphase* h, const std::vector<std::string>& bams, std::vec
         for (size_t g = 0; g < G; ++g) genes[g] = (uint32_t)g;
         rc = sp_hla_diplotype_genes(h->ctx, h->hla, (uint32_t)G, genes.data(), set, rec.data(), cfg.data(), calls.data(), cons.data(), cap, nullptr);
         if (rc != SP_OK) return h->fail(rc, "sp_hla_diplotype_genes: " + opt(sp_last_error(h->ctx)));
+        if (want_cigars) { std::string e; rc = read_cigars(h, set, rec.data(), (uint32_t)rec.size(), &cigars, e); if (rc != SP_OK) return h->fail(rc, e); }
     } else {
         for (auto& c : calls) { std::memset(&c, 0, sizeof c); c.status = 1; }
     }
@@ -599,7 +659,8 @@ int32_t hla_lane(sp_starphase* h, const std::vector<std::string>& bams, std::vec
         }
     }
     std::string err;
-    const int32_t rc = hla_package(h, reads, searched, order, rec.data(), rev, calls.data(), h->debug_folder, out, err);
+    if (want_cigars && reads.empty()) cigars.stride = 1;
+    const int32_t rc = hla_package(h, reads, searched, order, rec.data(), rev, calls.data(), h->debug_folder, out, err, want_cigars ? &cigars : nullptr, 0);
     return rc != SP_OK ? h->fail(rc, err) : SP_OK;
 }
 
@@ -759,6 +820,9 @@ int32_t hla_pass(sp_starphase* h, const std::vector<BSample*>& with, std::string
     std::vector<sp_hla_realign> rec(R); std::vector<sp_hla_rev_hit> rev(R);
     std::vector<sp_hla_call> calls(with.size() * G);
     for (auto& c : calls) { std::memset(&c, 0, sizeof c); c.status = 1; }
+    bool want_cigars = false;                                        // one traceback pass for the group when any of its samples has a debug folder
+    for (BSample* b : with) want_cigars |= h->read_debug && !b->debug.empty();
+    ReadCigars cigars; cigars.stride = 1;
     if (R) {
         std::vector<uint8_t> bytes; std::vector<uint64_t> off{0}; std::vector<uint32_t> lens;
         for (size_t k = 0; k < with.size(); ++k)
@@ -790,6 +854,7 @@ int32_t hla_pass(sp_starphase* h, const std::vector<BSample*>& with, std::string
                                                               cfg.data(), cc.data(), h->batch_cons.data(), cap, nullptr);
         if (rc != SP_OK) { err = "sp_hla_diplotype_genes: " + opt(sp_last_error(h->ctx)); return rc; }
         for (size_t x = 0; x < at.size(); ++x) std::copy(cc.begin() + x * G, cc.begin() + (x + 1) * G, calls.begin() + (size_t)at[x] * G);
+        if (want_cigars) { rc = read_cigars(h, set, rec.data(), R, &cigars, err); if (rc != SP_OK) return rc; }
     }
     for (size_t k = 0; k < with.size(); ++k) {
         BSample* b = with[k];
@@ -799,7 +864,7 @@ int32_t hla_pass(sp_starphase* h, const std::vector<BSample*>& with, std::string
             if (q.allele >= 0) rv[p] = RevHit{q.allele, (uint64_t)q.t_len, (uint64_t)q.nm, (uint64_t)(q.t_len - (q.t_end - q.t_start))};
         }
         std::string e;
-        const int32_t rc = hla_package(h, b->hreads, b->hsearched, orders[k], rec.data() + first[k], rv, calls.data() + k * G, b->debug, b->hla_entries, e);
+        const int32_t rc = hla_package(h, b->hreads, b->hsearched, orders[k], rec.data() + first[k], rv, calls.data() + k * G, b->debug, b->hla_entries, e, want_cigars ? &cigars : nullptr, first[k]);
         if (rc != SP_OK) b->fail(2, rc, e);
     }
     return SP_OK;
@@ -871,6 +936,11 @@ void sp_starphase_free(sp_starphase* h) {
 
 const char* sp_starphase_last_error(const sp_starphase* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 const char* sp_starphase_warnings(const sp_starphase* h) { return h ? h->warnings.c_str() : ""; }
+int32_t sp_starphase_set_read_debug(sp_starphase* h, int32_t enable) {
+    if (!h) return SP_ERR_INVALID_ARG;
+    h->read_debug = enable ? 1 : 0;
+    return SP_OK;
+}
 int32_t sp_starphase_last_timing(const sp_starphase* h, sp_starphase_timing* out) {
     if (!h || !out) return SP_ERR_INVALID_ARG;
     *out = h->timing;

@@ -1172,6 +1172,53 @@ int32_t sp_hla_realign_reads_rev(sp_ctx* ctx, const sp_hla_db* db, const sp_seqs
     return SP_OK;
 }
 
+// The CIGARs of the accepted mappings (sp_affine_align_batch: the traceback of the re-score's DP).  The pair of a record is the one its re-score ran: the read against
+// best_allele of dna_fwd on the middle diagonal of the record's own cell, on 256 diagonals when the cell's ends lie more than 32 diagonals apart (sp_hla_seed.hip,
+// k1s_rescore_cells_kernel) and on 64 otherwise; the record does not carry that choice, so a traceback whose numbers are not the record's is run on the other band.
+int32_t sp_hla_realign_cigars(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, const sp_hla_realign* records, uint32_t n_reads,
+                              uint32_t* cigar, uint32_t cigar_stride, uint32_t* n_cigar) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (!db || !reads || (n_reads && (!records || !n_cigar || (cigar_stride && !cigar)))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_hla_realign_cigars: null argument");
+    if (n_reads > reads->n) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_hla_realign_cigars: more records than reads");
+    const sp_affine_opts ao = { 1, 4, 6, 2, 26, 1, 1 };
+    std::vector<uint32_t> todo[2];                                   // reads to run on 64 / 256 diagonals
+    std::vector<sp_pair> pair_of(n_reads);
+    for (uint32_t r = 0; r < n_reads; ++r) {
+        n_cigar[r] = 0;
+        const sp_hla_realign& q = records[r];
+        if (q.status != 0 || q.mm2_score <= 0) continue;
+        if (q.best_allele < 0 || (uint32_t)q.best_allele >= db->n_alleles) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_hla_realign_cigars: allele out of range");
+        const int s0 = q.aln.b_start - q.aln.a_start, s1 = q.aln.b_end - q.aln.a_end;      // read position - allele position at the two ends of the cell
+        pair_of[r] = sp_pair{ r, (uint32_t)q.best_allele, -((s0 + s1) / 2), 0 };
+        todo[(s1 - s0 > 32 || s1 - s0 < -32) ? 1 : 0].push_back(r);
+    }
+    std::vector<sp_pair> pairs; std::vector<sp_affine_aln> got; std::vector<uint32_t> cg, nc;
+    for (int pass = 0; pass < 2; ++pass) {
+        std::vector<uint32_t> again[2];
+        for (int w = 0; w < 2; ++w) {
+            const std::vector<uint32_t>& list = todo[w];
+            if (list.empty()) continue;
+            pairs.resize(list.size()); got.resize(list.size()); nc.resize(list.size()); cg.resize(list.size() * (size_t)cigar_stride + 1);
+            for (size_t k = 0; k < list.size(); ++k) pairs[k] = pair_of[list[k]];
+            const int32_t rc = sp_affine_align_batch(ctx, reads, db->dna_fwd, pairs.data(), pairs.size(), &ao, w ? 256 : 64, got.data(), cg.data(), cigar_stride, nc.data());
+            if (rc != SP_OK) return rc;
+            for (size_t k = 0; k < list.size(); ++k) {
+                const uint32_t r = list[k]; const sp_hla_realign& q = records[r]; const sp_affine_aln& g = got[k];
+                if (g.score != q.mm2_score || g.nm != q.mm2_nm || g.b_start != q.mm2_t_start || g.b_end != q.mm2_t_end || g.a_start != q.mm2_q_start || g.a_end != q.mm2_q_end) {
+                    if (pass) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_hla_realign_cigars: record " + std::to_string(r) + " is not reproduced by its read and allele");
+                    again[1 - w].push_back(r);
+                    continue;
+                }
+                n_cigar[r] = nc[k];
+                if (cigar_stride) std::memcpy(cigar + (size_t)r * cigar_stride, cg.data() + k * (size_t)cigar_stride, (size_t)std::min(nc[k], cigar_stride) * 4);
+            }
+        }
+        todo[0].swap(again[0]); todo[1].swap(again[1]);
+        if (todo[0].empty() && todo[1].empty()) break;
+    }
+    return SP_OK;
+}
+
 static int32_t k1_realign_sliced(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, sp_hla_realign* out, uint32_t* cell_out, sp_hla_rev_hit* rev) {
     HostScope host_total(ctx, "host:k1_total");
     // big batches go through in slices of 65,536 reads (a shallow view of the same packed words): the read x allele matrix of a
@@ -1750,6 +1797,11 @@ int32_t sp_hla_type_consensus_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n
 }
 
 } // extern "C"
+
+std::string spi_hla_allele_fwd(sp_ctx* ctx, const sp_hla_db* db, uint32_t a) {
+    if (!db || a >= db->n_alleles) return std::string();
+    return sp_seqset_decode(ctx, db->dna_fwd, a);
+}
 
 #ifdef SP_K1_STATS
 extern "C" int32_t sp_debug_wfa_stats(uint64_t* out, int32_t reset) {

@@ -220,6 +220,8 @@ struct ProfScope {
 
 // sp_database.hip, for sp_diplotype.hip (not part of the C ABI)
 int32_t spi_gene_entry_extras(const sp_database* db, const sp_variant_gene* g, std::string* reference_allele, bool* has_sv, std::string* sv_chrom);
+// sp_hla.hip, for sp_diplotype.hip: allele a of the database in hg38 orientation (the target of sp_hla_realign_cigars), ASCII; empty: no DNA sequence
+std::string spi_hla_allele_fwd(sp_ctx* ctx, const sp_hla_db* db, uint32_t a);
 // sp_cyp.hip, for sp_diplotype.hip: sp_cyp_diplotype_mappings with the list in a vector the library sizes
 int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
                                    sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings);

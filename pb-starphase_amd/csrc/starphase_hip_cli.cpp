@@ -32,6 +32,7 @@ const char* HELP =
     "      --include-set <TXT>          Optional file indicating the list of genes to include in diplotyping, one per line\n"
     "      --exclude-set <TXT>          Optional file indicating the list of genes to exclude from diplotyping, one per line\n"
     "      --output-debug <DIR>         Optional output debug folder (hla_debug.json, cyp2d6_alleles.json)\n"
+    "      --debug-reads                Also write read_debug.json there: every realigned HLA read's accepted allele with CIGAR and MD (needs --output-debug)\n"
     "      --sample-name <STRING>       Sample name from the input VCFs (default: first sample)\n"
     "\n"
     "Variant parameters:\n"
@@ -112,6 +113,7 @@ const char* BATCH_HELP =
     "      --max-group <N>              Samples per device pass [default: 64]\n"
     "  -t, --threads <THREADS>          Host BAM / VCF decode workers [default: min(16, hardware threads)]\n"
     "      --sequential                 Run CYP2D6 after the variant genes and the HLA genes of a group (the calls are the same)\n"
+    "      --debug-reads                Also write read_debug.json into every sample's debug folder (needs an output_debug column that names one)\n"
     "  -v, --verbose...                 Enable verbose output (print the warnings and the timings of the batch)\n"
     "  -h, --help                       Print help\n"
     "\n"
@@ -147,7 +149,7 @@ int batch_main(int argc, char** argv) {
     sp_diplotype_settings_default(&s);
     std::string database, reference, manifest, include, exclude;
     uint64_t max_group = 0, threads = 0;
-    int verbose = 0;
+    int verbose = 0; bool debug_reads = false;
     for (int i = 2; i < argc; ++i) {
         std::string a = argv[i], val;
         bool has_inline = false;
@@ -173,6 +175,7 @@ int batch_main(int argc, char** argv) {
         else if (a == "--infer-connections") s.infer_connections = 1;
         else if (a == "--normalize-d6-only") s.normalize_d6_only = 1;
         else if (a == "--sequential") s.sequential = 1;
+        else if (a == "--debug-reads") debug_reads = true;
         else if (a == "-v" || a == "--verbose") ++verbose;
         else if (a.size() > 2 && a[0] == '-' && a[1] == 'v' && a.find_first_not_of('v', 1) == std::string::npos) verbose += (int)a.size() - 1;
         else if (a == "--max-sv-length" || a == "--min-consensus-count" || a == "--dual-max-ed-delta" || a == "-t" || a == "--threads" || a == "--max-group") {
@@ -242,6 +245,11 @@ int batch_main(int argc, char** argv) {
         }
     }
     if (rows.empty()) { std::fprintf(stderr, "error: manifest \"%s\" lists no samples\n", manifest.c_str()); return EX_USAGE_; }
+    if (debug_reads) {
+        bool any = false;
+        for (const Row& r : rows) any |= !r.debug.empty();
+        if (!any) { std::fprintf(stderr, "error: --debug-reads needs a debug folder: no manifest row names one (output_debug)\n"); return EX_USAGE_; }
+    }
     // every row through the checks of `diplotype`: the files (NOINPUT), then check_diplotype_settings (USAGE)
     std::vector<std::vector<const char*>> bam_ptrs(rows.size());
     std::vector<sp_sample_inputs> in(rows.size());
@@ -281,6 +289,7 @@ int batch_main(int argc, char** argv) {
         std::fprintf(stderr, "error: %s\n", sp_starphase_last_error(nullptr));
         return rc == SP_ERR_NO_DEVICE || rc == SP_ERR_HIP ? EX_UNAVAILABLE_ : EX_IOERR_;
     }
+    if (debug_reads) sp_starphase_set_read_debug(h, 1);
     sp_batch_options o{};
     o.max_group = (uint32_t)max_group; o.decode_threads = (uint32_t)threads;
     std::vector<sp_result*> out(rows.size(), nullptr);
@@ -329,7 +338,7 @@ int main(int argc, char** argv) {
     sp_diplotype_settings_default(&s);
     std::string database, reference, vcf, sv_vcf, output, pharmcat, include, exclude, debug, sample;
     std::vector<std::string> bams;
-    int verbose = 0;
+    int verbose = 0; bool debug_reads = false;
     for (int i = 2; i < argc; ++i) {
         std::string a = argv[i], val;
         bool has_inline = false;
@@ -364,6 +373,7 @@ int main(int argc, char** argv) {
         else if (a == "--infer-connections") s.infer_connections = 1;
         else if (a == "--normalize-d6-only") s.normalize_d6_only = 1;
         else if (a == "--sequential") s.sequential = 1;
+        else if (a == "--debug-reads") debug_reads = true;
         else if (a == "-v" || a == "--verbose") ++verbose;
         else if (a.size() > 2 && a[0] == '-' && a[1] == 'v' && a.find_first_not_of('v', 1) == std::string::npos) verbose += (int)a.size() - 1;
         else if (a == "--max-sv-length" || a == "--min-consensus-count" || a == "--dual-max-ed-delta" || a == "-t" || a == "--threads") {
@@ -406,6 +416,7 @@ int main(int argc, char** argv) {
     s.include_set = include.empty() ? nullptr : include.c_str(); s.exclude_set = exclude.empty() ? nullptr : exclude.c_str();
     s.sample_name = sample.empty() ? nullptr : sample.c_str(); s.sv_vcf = sv_vcf.empty() ? nullptr : sv_vcf.c_str();
     s.debug_folder = debug.empty() ? nullptr : debug.c_str();
+    if (debug_reads && debug.empty()) { std::fprintf(stderr, "error: --debug-reads needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
     char err[512];
     if (sp_diplotype_settings_check(&s, &in, err, sizeof err) != SP_OK) {
         std::fprintf(stderr, "error: Error while processing CLI settings: %s\n", err);
@@ -428,6 +439,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "error: %s\n", sp_starphase_last_error(nullptr));
         return rc == SP_ERR_NO_DEVICE || rc == SP_ERR_HIP ? EX_UNAVAILABLE_ : EX_IOERR_;
     }
+    if (debug_reads) sp_starphase_set_read_debug(h, 1);
     sp_result* result = nullptr;
     rc = sp_starphase_call(h, &in, &result);
     const char* warn = sp_starphase_warnings(h);

@@ -245,6 +245,8 @@ def lib():
         "sp_ctx_create": (i32, [i32, vp, C.POINTER(vp)]),
         "sp_ctx_destroy": (None, [vp]),
         "sp_affine_rescore_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, vp]),
+        "sp_affine_align_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, vp, vp, u32, vp]),
+        "sp_hla_realign_cigars": (i32, [vp, vp, vp, vp, u32, vp, u32, vp]),
         "sp_ctx_get_info": (i32, [vp, C.POINTER(sp_ctx_info)]),
         "sp_last_error": (C.c_char_p, [vp]),
         "sp_ctx_synchronize": (i32, [vp]),
@@ -383,6 +385,19 @@ class Context:
         op = sp_affine_opts(a, 4, 6, 2, 26, 1, 1)
         self.check(lib().sp_affine_rescore_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), int(band), _ptr(out)))
         return out
+
+    def affine_align(self, A, B, pairs, a=1, band=64, cigar_stride=1024):
+        """sp_affine_align_batch: pairs = [(a index, b index, diag = b_pos - a_pos[, max_ed])] -> (what affine_rescore returns, cigar uint32[n][cigar_stride] in BAM
+        encoding len << 4 | op with 7 '=', 8 'X', 1 'I', 2 'D', n_cigar uint32[n]: the true op counts, which may exceed cigar_stride)"""
+        rows = np.zeros(len(pairs), PAIR_DTYPE)
+        for i, pr in enumerate(pairs):
+            rows[i] = (pr[0], pr[1], pr[2], pr[3] if len(pr) > 3 else 0)
+        out = np.zeros(len(pairs), AFFINE_DTYPE)
+        cigar = np.zeros((len(pairs), int(cigar_stride)), np.uint32)
+        n_cigar = np.zeros(len(pairs), np.uint32)
+        op = sp_affine_opts(a, 4, 6, 2, 26, 1, 1)
+        self.check(lib().sp_affine_align_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), int(band), _ptr(out), _ptr(cigar), int(cigar_stride), _ptr(n_cigar)))
+        return out, cigar, n_cigar
 
     def info(self):
         """sp_ctx_get_info -> dict(device, num_cus, hw_queues, hw_queues_set_by_library, warning)"""
@@ -1179,6 +1194,15 @@ class HlaDb:
         rev = np.zeros(reads.n, REV_HIT_DTYPE)
         self.ctx.check(lib().sp_hla_realign_reads_rev(self.ctx._h, self._h, reads._h, _ptr(out), _ptr(rev)))
         return out, rev
+
+    def realign_cigars(self, reads, records, cigar_stride=1024):
+        """sp_hla_realign_cigars: the CIGAR of every status-0 record's accepted mapping (read = query, best_allele in hg38 orientation = target)
+        -> (cigar uint32[n][cigar_stride], n_cigar uint32[n]; encoding of affine_align)"""
+        records = np.ascontiguousarray(records, REALIGN_DTYPE)
+        cigar = np.zeros((len(records), int(cigar_stride)), np.uint32)
+        n_cigar = np.zeros(len(records), np.uint32)
+        self.ctx.check(lib().sp_hla_realign_cigars(self.ctx._h, self._h, reads._h, _ptr(records), len(records), _ptr(cigar), int(cigar_stride), _ptr(n_cigar)))
+        return cigar, n_cigar
 
     def seed_index_info(self):
         """sp_hla_seed_index_info -> dict(minimizers, distinct, mid_occ, sequences) of the minimizer index of the DNA alleles (built on first use)"""
