@@ -105,7 +105,7 @@ int32_t sp_ctx_synchronize(sp_ctx* ctx);
  * (a second row of workgroups); the children of an expansion made ahead wait unseen until the search takes their parent out at that column and are adopted without a launch --
  * and whether a window may be ordered WITH the children of the branch its lookahead votes foresee at its end (taken when the window stands and the exact votes of that column
  * name no other children).  Neither changes what the search does -- strings, read assignment, per-read scores and the number of nodes expanded are those of the one-order search,
- * bit for bit --, only how many dependent launches it takes (a 2,000-read CYP2D6 sample 423 -> 285 launches, the branching `*4+*68/*1` 2,485 -> 1,417).
+ * bit for bit --, only how many dependent launches it takes (a 2,000-read CYP2D6 sample 423 -> 285 launches, the branching sample `*4+*68` / `*1` 2,485 -> 1,417).
  * "k8_side_max_blocks" (default 4096): batches with more step workgroups than this keep to the search's own order.  Persistent batches keep to the search's own order as well.
  * "cyp_cohort_streams" (1..8, default 8): streams sp_cyp_diplotype_cohort spreads its groups of samples over (one host thread each).
  * "k5_block_pairs" (0..1048576, default 4096): sp_cyp_best_chain_pair scores up to this many chain pairs with one workgroup per pair (the few pairs
@@ -1196,7 +1196,8 @@ int32_t sp_starphase_create(sp_ctx* ctx, const char* database_path, const char* 
 void    sp_starphase_free(sp_starphase* handle);
 const char* sp_starphase_last_error(const sp_starphase* handle);
 /* one sample: *out is a new sp_result (sp_result_free).  Errors as the reference's: a region fetch that fails counts as no reads (the warning is kept:
- * sp_starphase_warnings), an expected CYP2D6 CallerError gives the NO_MATCH entry, anything else fails the call (DATAERR on the command line). */
+ * sp_starphase_warnings), an expected CYP2D6 CallerError gives the NO_MATCH entry, anything else fails the call (DATAERR on the command line).
+ * On a caller's context in exhaustive K1 mode ("k1_best_n" = 0) no HLA read is named after a reverse-strand mapping (those come from the seeded stage). */
 int32_t sp_starphase_call(sp_starphase* handle, const sp_sample_inputs* inputs, sp_result** out);
 /* read_debug.json, off by default (enable 0): with the switch on, a call with a debug folder (settings.debug_folder; debug_folders[i] of sp_starphase_call_batch)
  * also writes <folder>/read_debug.json -- the reference's `read_debug` (src/hla/caller.rs:536,575-577,631-635): an HlaDebug object (sp_hla_debug_*) whose

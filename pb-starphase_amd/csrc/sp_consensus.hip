@@ -2453,12 +2453,11 @@ static int32_t run_chunk(sp_ctx* ctx, uint32_t n_prob, const sp_cons_problem* pr
                                                                                                                //  workgroups do not: one CYP2D6 lane beside the HLA lane 183k -> 199k reads/s)
     if (ctx->k8_persist_backoff > 0) --ctx->k8_persist_backoff;
     else if (persist_wanted && n_prob > 0) {
-        uint64_t blocks1 = 0; bool small = true;
+        bool small = true;
         for (uint32_t p = 0; p < n_prob; ++p) {
             const uint32_t n = probs[p].read_idx ? probs[p].n : probs[p].reads->n;
             const uint32_t nb = (n + CWAVES - 1) / CWAVES;
             small = small && nb <= (uint32_t)PERSIST_BLOCKS;
-            blocks1 += nb;
         }
         constexpr int WG_PER_CU = SP_K8_MIN_WAVES * 4 / CWAVES;             // step workgroups a CU holds at the kernel's register budget
         int budget = WG_PER_CU * std::max(0, ctx->num_cus - 32); const int ctl = 2 * (int)n_prob;

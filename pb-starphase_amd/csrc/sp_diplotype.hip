@@ -4,12 +4,13 @@
 //   variant genes  VCF (+ SV VCF) -> sp_variant_gene_problem -> one sp_variant_solve_batch (K6) -> the packaging of call_diplotypes (:130-204)
 //   HLA            the read loop of diplotype_hla_batch (src/hla/caller.rs:540-596) -> K1 -> buckets in QNAME order -> K8 / K2 -> new_from_mappings
 //   CYP2D6         the read collection of diplotype_cyp2d6 (src/cyp2d6/caller.rs:60-139) -> K3 / K8 / K9 / K7 / K4 / K5 -> new_from_multi_mappings
-// The CYP2D6 lane (BAM decode, upload, call) runs on a host thread of its own with the second context while the calling thread does the variant genes
-// and the HLA genes; every entry is built from its own lane's inputs only, and the entries are inserted in one fixed order at the end, so the result is
-// the same whichever way the lanes ran (settings.sequential = 1 runs them one after another).
-// sp_starphase_call_batch types groups of samples with the same pieces: per group one variant solve, one K1 pass (sp_hla_realign_reads_rev), one HLA
-// cohort call and one CYP2D6 cohort call, the host decode of the next group beside the device work of this one; every sample's entries are those
-// sp_starphase_call makes for it.
+// There is one pipeline, over a group of samples: sample_setup (inputs, checks) -> variant_samples / hla_group / cyp_group (one variant solve, one K1 pass
+// that also names the reverse-strand reads, one HLA call and one CYP2D6 call per group; the single-sample entry points for a group of one) -> sample_result
+// (the entries in one fixed order, the error precedence, the warnings).  The CYP2D6 lane runs on a host thread of its own with the second context while the
+// calling thread does the variant genes and the HLA genes; every entry is built from its own lane's inputs only, so the result is the same whichever way the
+// lanes ran (settings.sequential = 1 runs them one after another).
+// sp_starphase_call is that pipeline for a group of one, decoding its files inside its lanes; sp_starphase_call_batch runs it per group of max_group
+// samples, the host decode of the next group beside the device work of this one.
 #include "sp_internal.h"
 #include <algorithm>
 #include <atomic>
@@ -66,12 +67,14 @@ int32_t collect_reads(const std::vector<std::string>& bams, const std::string& c
     return SP_OK;
 }
 
-// the reads of `order` as one SP_SEQ_BAM4 set
-int32_t upload_reads(sp_ctx* ctx, const std::vector<Read4>& reads, const std::vector<uint32_t>& order, sp_seqset** out) {
+// one SP_SEQ_BAM4 set: part after part, the reads of a part in its `order`
+struct ReadPart { const std::vector<Read4>* reads; const std::vector<uint32_t>* order; };
+int32_t upload_reads(sp_ctx* ctx, const std::vector<ReadPart>& parts, sp_seqset** out) {
     std::vector<uint8_t> bytes; std::vector<uint64_t> off{0}; std::vector<uint32_t> lens;
-    for (uint32_t i : order) { bytes.insert(bytes.end(), reads[i].seq4.begin(), reads[i].seq4.end()); off.push_back(bytes.size()); lens.push_back(reads[i].len); }
+    for (const ReadPart& p : parts)
+        for (uint32_t i : *p.order) { const Read4& r = (*p.reads)[i]; bytes.insert(bytes.end(), r.seq4.begin(), r.seq4.end()); off.push_back(bytes.size()); lens.push_back(r.len); }
     if (bytes.empty()) bytes.push_back(0);
-    return sp_seqset_upload_format(ctx, SP_SEQ_BAM4, bytes.data(), off.data(), lens.data(), (uint32_t)order.size(), out);
+    return sp_seqset_upload_format(ctx, SP_SEQ_BAM4, bytes.data(), off.data(), lens.data(), (uint32_t)lens.size(), out);
 }
 
 std::vector<uint32_t> qname_order(const std::vector<Read4>& reads) {
@@ -98,7 +101,7 @@ struct GeneDetailsPtr {
 // one entry of the result, ready to be inserted: made on whichever lane computed it
 struct Entry { std::string gene; std::unique_ptr<GeneDetailsPtr> details; int32_t constructor = 0; };
 
-// the VCF records variant_lane fetches for a gene: +-50 bp around each of its variants; fetch = selected and with variants (or an SV)
+// the VCF records vcf_fetch reads for a gene: +-50 bp around each of its variants; fetch = selected and with variants (or an SV)
 struct GeneWindow { bool fetch = false; uint64_t lo = 0, hi = 0; uint32_t n_variants = 0; };
 
 }  // namespace
@@ -134,7 +137,7 @@ struct sp_starphase {
     // sp_starphase_call_batch: per-sample errors and warnings of the last batch, its timing
     std::vector<std::string> batch_err, batch_warn;
     sp_starphase_batch_timing batch_timing{};
-    std::vector<char> batch_cons;                    // the HLA cohort's consensus texts (not read; kept across groups)
+    std::vector<char> hla_cons;                      // the HLA call's consensus texts (not read; kept across calls)
 
     bool selected(const std::string& gene) const {
         if (has_include && !include.count(gene)) return false;
@@ -203,25 +206,58 @@ void quant_match(const sp_variant_problem& p, int h, const std::vector<int32_t>&
     }
 }
 
+// A variant problem points into its sp_variant_gene, which keeps only its last problem.  This is a problem on its own: the arrays, and what the gene
+// says about this problem's ids (id -> database variant or deletion, the deletion labels), so solving and packaging need the gene's static tables only.
+struct OwnedProblem {
+    struct Var { int32_t db_variant = -1; bool has_label = false; std::string sv_label; uint64_t sv_start = 0, sv_end = 0; };
+    size_t gene = 0, entry = 0;                      // the vgenes index, the sample's entry it fills
+    std::vector<uint8_t> hap_is_sv, hap_is_core, var_is_core; std::vector<int32_t> slot_off, alt_off, alt_var, obs_var, obs_gt, obs_sv_label; std::vector<int64_t> obs_ps;
+    std::vector<Var> vars; std::vector<std::string> labels;
+    sp_variant_problem p{};
+    bool take(const sp_variant_gene* g, const sp_variant_problem& q) {
+        const size_t H = (size_t)std::max(0, q.n_haps), V = (size_t)std::max(0, q.n_vars), O = (size_t)std::max(0, q.n_obs);
+        slot_off.assign(q.slot_off, q.slot_off + H + 1);
+        const size_t S = (size_t)slot_off[H];
+        alt_off.assign(q.alt_off, q.alt_off + S + 1);
+        alt_var.assign(q.alt_var, q.alt_var + alt_off[S]);
+        hap_is_sv.assign(q.hap_is_sv, q.hap_is_sv + H); hap_is_core.assign(q.hap_is_core, q.hap_is_core + H);
+        var_is_core.assign(q.var_is_core, q.var_is_core + V);
+        obs_var.assign(q.obs_var, q.obs_var + O); obs_gt.assign(q.obs_gt, q.obs_gt + O); obs_ps.assign(q.obs_ps, q.obs_ps + O);
+        obs_sv_label.assign(q.obs_sv_label, q.obs_sv_label + O);
+        p = q;
+        p.hap_is_sv = hap_is_sv.data(); p.hap_is_core = hap_is_core.data(); p.slot_off = slot_off.data(); p.alt_off = alt_off.data(); p.alt_var = alt_var.data();
+        p.var_is_core = var_is_core.data(); p.obs_var = obs_var.data(); p.obs_gt = obs_gt.data(); p.obs_ps = obs_ps.data(); p.obs_sv_label = obs_sv_label.data();
+        vars.assign(V, Var());
+        for (size_t v = 0; v < V; ++v) {
+            const char* label = nullptr;
+            if (sp_variant_gene_problem_variant(g, (int32_t)v, &vars[v].db_variant, &label, &vars[v].sv_start, &vars[v].sv_end) != SP_OK) return false;
+            vars[v].has_label = label != nullptr; vars[v].sv_label = opt(label);
+        }
+        labels.clear();
+        for (const char* l = nullptr; sp_variant_gene_problem_sv_label(g, (int32_t)labels.size(), &l) == SP_OK;) labels.push_back(opt(l));
+        return true;
+    }
+};
+
 struct VarInfo { std::string name; bool is_core = true; bool is_sv = false; std::string sv_label; };
 
 // one solved gene -> its PgxGeneDetails (call_diplotypes, src/diplotyper.rs:130-204)
-int32_t package_gene(sp_starphase* h, sp_starphase::VGene& vg, const sp_variant_problem& p, const sp_variant_result& res, Entry& e) {
-    sp_variant_gene* g = vg.g;
+int32_t package_gene(sp_starphase* h, const sp_starphase::VGene& vg, const OwnedProblem& q, const sp_variant_result& res, Entry& e) {
+    const sp_variant_gene* g = vg.g;
+    const sp_variant_problem& p = q.p;
     if (res.overflow) return h->fail(SP_ERR_CAPACITY, vg.name + ": more than " + std::to_string(SP_VAR_MAXDIP) + " tied diplotypes");
     // names of the problem's variants (RegionVariant labels: the database name, "structural_variant" for an SV; SVs are core variants)
     std::vector<VarInfo> var(p.n_vars);
     for (int v = 0; v < p.n_vars; ++v) {
-        int32_t dbv = -1; const char* label = nullptr; uint64_t s0 = 0, s1 = 0;
-        if (sp_variant_gene_problem_variant(g, v, &dbv, &label, &s0, &s1) != SP_OK) return h->fail(SP_ERR_INVALID_ARG, vg.name + ": bad problem variant");
-        if (dbv >= 0) {
+        const OwnedProblem::Var& pv = q.vars[v];
+        if (pv.db_variant >= 0) {
             uint64_t pos; const char *r, *a, *nm, *dbsnp; int64_t vid; int32_t core;
-            sp_variant_gene_variant(g, (uint32_t)dbv, &pos, &r, &a, &nm, &dbsnp, &vid, &core);
+            sp_variant_gene_variant(g, (uint32_t)pv.db_variant, &pos, &r, &a, &nm, &dbsnp, &vid, &core);
             var[v] = VarInfo{opt(nm), core != 0, false, ""};
-        } else var[v] = VarInfo{"structural_variant", true, true, opt(label)};
+        } else var[v] = VarInfo{"structural_variant", true, true, pv.sv_label};
     }
     auto hap_name = [&](int32_t x) -> std::string {
-        if (x < 0) { const char* l = nullptr; sp_variant_gene_problem_sv_label(g, -x - 2, &l); return opt(l); }
+        if (x < 0) return (size_t)(-x - 2) < q.labels.size() ? q.labels[(size_t)(-x - 2)] : std::string();
         const char* n = nullptr; const char* c = nullptr; sp_variant_gene_haplotype(g, (uint32_t)x, &n, &c); return opt(n);
     };
     auto core_name = [&](int32_t x) -> std::string {          // build_core_allele_lookup (:378-399)
@@ -268,19 +304,18 @@ int32_t package_gene(sp_starphase* h, sp_starphase::VGene& vg, const sp_variant_
     }
     // variant_details: the observed variants in NormalizedVariant order
     for (int o = 0; o < p.n_obs; ++o) {
-        const int32_t v = p.obs_var[o];
-        int32_t dbv = -1; const char* label = nullptr; uint64_t s0 = 0, s1 = 0;
-        sp_variant_gene_problem_variant(g, v, &dbv, &label, &s0, &s1);
+        const OwnedProblem::Var& pv = q.vars[(size_t)p.obs_var[o]];
+        const uint64_t s0 = pv.sv_start, s1 = pv.sv_end;
         sp_variant_detail det{};
         det.genotype = p.obs_gt[o]; det.phase_set = p.obs_ps[o];
-        if (dbv >= 0) {
+        if (pv.db_variant >= 0) {
             uint64_t pos; const char *r, *a, *nm, *dbsnp; int64_t vid; int32_t core;
-            sp_variant_gene_variant(g, (uint32_t)dbv, &pos, &r, &a, &nm, &dbsnp, &vid, &core);
+            sp_variant_gene_variant(g, (uint32_t)pv.db_variant, &pos, &r, &a, &nm, &dbsnp, &vid, &core);
             det.variant_id = (uint64_t)vid; det.variant_name = nm; det.dbsnp = dbsnp; det.chrom = vg.chrom.c_str(); det.position = pos;
             det.reference = r; det.alternate = a; det.is_core_variant = core;
         } else {
             det.variant_id = UINT64_MAX; det.variant_name = "structural_variant"; det.dbsnp = nullptr; det.chrom = vg.sv_chrom.c_str(); det.position = s0;
-            det.reference = ""; det.alternate = ""; det.sv_label = label; det.sv_start = s0; det.sv_end = s1; det.is_core_variant = 1;
+            det.reference = ""; det.alternate = ""; det.sv_label = pv.has_label ? pv.sv_label.c_str() : nullptr; det.sv_start = s0; det.sv_end = s1; det.is_core_variant = 1;
         }
         if (sp_gene_details_add_variant(d, &det) != SP_OK) return h->fail(SP_ERR_INVALID_ARG, vg.name + ": bad variant detail");
     }
@@ -288,29 +323,8 @@ int32_t package_gene(sp_starphase* h, sp_starphase::VGene& vg, const sp_variant_
     return SP_OK;
 }
 
-// A variant problem points into its sp_variant_gene, which keeps only its last problem: a batch holds copies of every sample's problems for the one
-// solve, and rebuilds a sample's problems from the same records before it packages them (the build is host work and gives the same problem).
-struct OwnedProblem {
-    std::vector<uint8_t> hap_is_sv, hap_is_core, var_is_core; std::vector<int32_t> slot_off, alt_off, alt_var, obs_var, obs_gt, obs_sv_label; std::vector<int64_t> obs_ps;
-    sp_variant_problem p{};
-    void take(const sp_variant_problem& q) {
-        const size_t H = (size_t)std::max(0, q.n_haps), V = (size_t)std::max(0, q.n_vars), O = (size_t)std::max(0, q.n_obs);
-        slot_off.assign(q.slot_off, q.slot_off + H + 1);
-        const size_t S = (size_t)slot_off[H];
-        alt_off.assign(q.alt_off, q.alt_off + S + 1);
-        alt_var.assign(q.alt_var, q.alt_var + alt_off[S]);
-        hap_is_sv.assign(q.hap_is_sv, q.hap_is_sv + H); hap_is_core.assign(q.hap_is_core, q.hap_is_core + H);
-        var_is_core.assign(q.var_is_core, q.var_is_core + V);
-        obs_var.assign(q.obs_var, q.obs_var + O); obs_gt.assign(q.obs_gt, q.obs_gt + O); obs_ps.assign(q.obs_ps, q.obs_ps + O);
-        obs_sv_label.assign(q.obs_sv_label, q.obs_sv_label + O);
-        p = q;
-        p.hap_is_sv = hap_is_sv.data(); p.hap_is_core = hap_is_core.data(); p.slot_off = slot_off.data(); p.alt_off = alt_off.data(); p.alt_var = alt_var.data();
-        p.var_is_core = var_is_core.data(); p.obs_var = obs_var.data(); p.obs_gt = obs_gt.data(); p.obs_ps = obs_ps.data(); p.obs_sv_label = obs_sv_label.data();
-    }
-};
-
-// the VCF (+ SV VCF) records variant_lane fetches for every selected gene with variants, read on a decode worker.  fail_at: the vgenes index of the
-// first gene whose fetch failed (0 with fail_rc set: the files themselves); the genes before it still build their problems first, as in variant_lane.
+// the VCF (+ SV VCF) records of every selected gene with variants (+-50 bp around each variant), read by the decode.  fail_at: the vgenes index of the
+// first gene whose fetch failed (0 with fail_rc set: the files themselves); the genes before it still build their problems first.
 struct VcfGene { std::vector<uint64_t> pos; std::vector<std::string> ref, alt; std::vector<int32_t> gt; std::vector<int64_t> ps; std::vector<sp_vcf_deletion> dels; };
 struct VcfFetch { std::vector<VcfGene> genes; size_t fail_at = SIZE_MAX; int32_t fail_rc = SP_OK; std::string fail_err; };
 
@@ -360,17 +374,17 @@ int32_t vcf_problem(sp_starphase* h, size_t i, const VcfGene& G, sp_variant_prob
     return SP_OK;
 }
 
-// one sample's variant genes, for sp_starphase_call and for each sample of a batch group
+// one sample's variant genes
 struct VarSample {
     bool has_vcf = false; std::string vcf, sv, sample;
-    VcfFetch vf;                                     // read by vcf_fetch (a decode worker, in a batch)
+    VcfFetch vf;                                     // read by vcf_fetch
     int32_t rc = SP_OK; std::string err;
-    std::vector<Entry> entries; std::vector<size_t> solved; std::vector<OwnedProblem> probs; size_t res0 = 0;
+    std::vector<Entry> entries; std::vector<OwnedProblem> probs; size_t res0 = 0;
 };
 
 // call_diplotypes' gene loop (src/diplotyper.rs:94-204) for every sample of `group` whose VCF was read: each sample's problems, ONE
-// sp_variant_solve_batch over all of them, then the entries sample by sample.  A sample fails with what sp_starphase_call reports for it: when the
-// shared launch fails, each sample's problems are solved once more on their own, so a failure and its text belong to the sample that has it.
+// sp_variant_solve_batch over all of them, then the entries sample by sample.  A failure and its text belong to the sample that has it: when the
+// shared launch fails, each sample's problems are solved once more on their own.
 void variant_samples(sp_starphase* h, const std::vector<VarSample*>& group) {
     std::vector<const sp_variant_problem*> pp;
     for (VarSample* b : group) {
@@ -390,7 +404,9 @@ void variant_samples(sp_starphase* h, const std::vector<VarSample*>& group) {
             sp_variant_problem p{};
             const int32_t rc = vcf_problem(h, i, b->vf.genes[i], p);
             if (rc != SP_OK) { b->rc = rc; b->err = h->err; break; }
-            b->probs.emplace_back(); b->probs.back().take(p); b->solved.push_back(i);
+            b->probs.emplace_back();
+            OwnedProblem& q = b->probs.back(); q.gene = i; q.entry = b->entries.size();
+            if (!q.take(vg.g, p)) { b->rc = SP_ERR_INVALID_ARG; b->err = vg.name + ": bad problem variant"; break; }
             b->entries.push_back(std::move(en));
         }
     }
@@ -411,30 +427,14 @@ void variant_samples(sp_starphase* h, const std::vector<VarSample*>& group) {
             }
         }
     }
-    // the entries; a sample's problems are built once more first (the gene keeps only its last problem, which package_gene reads back)
     for (VarSample* b : solving) {
-        if (b->rc != SP_OK) continue;
-        size_t k = 0;
-        for (auto& en : b->entries) {
-            if (k < b->solved.size() && h->vgenes[b->solved[k]].name == en.gene) {
-                sp_variant_problem p{};
-                int32_t rc = vcf_problem(h, b->solved[k], b->vf.genes[b->solved[k]], p);
-                if (rc == SP_OK) rc = package_gene(h, h->vgenes[b->solved[k]], p, res[b->res0 + k], en);
-                if (rc != SP_OK) { b->rc = rc; b->err = h->err; break; }
-                ++k;
-            }
+        for (size_t k = 0; k < b->probs.size() && b->rc == SP_OK; ++k) {
+            const OwnedProblem& q = b->probs[k];
+            const int32_t rc = package_gene(h, h->vgenes[q.gene], q, res[b->res0 + k], b->entries[q.entry]);
+            if (rc != SP_OK) { b->rc = rc; b->err = h->err; }
         }
         b->probs.clear();
     }
-}
-
-int32_t variant_lane(sp_starphase* h, const std::string& vcf_path, const std::string& sv_path, const std::string& sample_in, std::vector<Entry>& out) {
-    VarSample v; v.has_vcf = true;
-    vcf_fetch(h, h->win, vcf_path, sv_path, sample_in, v.vf);
-    variant_samples(h, {&v});
-    if (v.rc != SP_OK) return h->fail(v.rc, v.err);
-    for (auto& e : v.entries) out.push_back(std::move(e));
-    return SP_OK;
 }
 
 // ---------------------------------------------------------------- HLA
@@ -466,8 +466,6 @@ void hla_configs(sp_starphase* h, const sp_hla_realign* rec, uint32_t n, sp_hla_
         c.normalized_coverage = coverage;
     }
 }
-
-struct RevHit { int32_t allele = -1; uint64_t t_len = 0, nm = 0, unmapped = 0; };
 
 // read_debug.json (sp_starphase_set_read_debug): the reference's `read_debug` (src/hla/caller.rs:536,575-577,631-635) -- an HlaDebug whose read_mapping_stats hold, per
 // gene and QNAME, the ReadMappingStats realign_record made for a read it realigned (src/hla/realigner.rs:198-201): the accepted allele as best match and the one DNA
@@ -524,10 +522,11 @@ int32_t read_debug_save(sp_starphase* h, const std::vector<Read4>& reads, const 
     return SP_OK;
 }
 
-// the HLA entries of one sample: PgxMappingDetails of every read, the diplotypes, hla_debug.json.  rec / rev: by position in QNAME order
+// the HLA entries of one sample: PgxMappingDetails of every read, the diplotypes, hla_debug.json.  rec / rev: by position in QNAME order; rev[k].allele
+// >= 0 names the reverse-strand mapping a read was dropped for (src/hla/realigner.rs:178-193)
 int32_t hla_package(sp_starphase* h, const std::vector<Read4>& reads, const std::vector<uint32_t>& searched, const std::vector<uint32_t>& order,
-                    const sp_hla_realign* rec, const std::map<uint32_t, RevHit>& rev, const sp_hla_call* calls, const std::string& debug_folder,
-                    std::vector<Entry>& out, std::string& err, const ReadCigars* cigars = nullptr, uint32_t cigars_first = 0) {
+                    const sp_hla_realign* rec, const sp_hla_rev_hit* rev, const sp_hla_call* calls, const std::string& debug_folder,
+                    std::vector<Entry>& out, std::string& err, const ReadCigars* cigars, uint32_t cigars_first) {
     const size_t G = h->hgenes.size();
     // PgxMappingDetails of every read, in the order the loop met them, in the bucket of its gene (realigned) or of the gene searched (ignored)
     std::vector<std::unique_ptr<GeneDetailsPtr>> det(G);
@@ -538,11 +537,11 @@ int32_t hla_package(sp_starphase* h, const std::vector<Read4>& reads, const std:
         const sp_hla_realign& q = rec[pos_of[r]];
         sp_mapping_stats dna{}; dna.present = 1;
         uint32_t gene = searched[r]; const char* id = "REFERENCE"; std::string star = "REFERENCE"; int32_t ignored = 1;
-        auto rv = rev.find(pos_of[r]);
-        if (rv != rev.end()) {                                       // accepted on the reverse strand: ignored, named after that mapping
-            const uint32_t a = (uint32_t)rv->second.allele;
+        const sp_hla_rev_hit& rv = rev[pos_of[r]];
+        if (rv.allele >= 0) {                                        // accepted on the reverse strand: ignored, named after that mapping
+            const uint32_t a = (uint32_t)rv.allele;
             id = h->a_id[a].c_str(); star = h->hgenes[h->a_gene[a]].name + "*" + h->a_star[a];
-            dna.seq_len = rv->second.t_len; dna.nm = rv->second.nm; dna.unmapped = rv->second.unmapped;
+            dna.seq_len = (uint64_t)rv.t_len; dna.nm = (uint64_t)rv.nm; dna.unmapped = (uint64_t)(rv.t_len - (rv.t_end - rv.t_start));
         } else if (q.best_allele >= 0 && q.status != 1) {
             const uint32_t a = (uint32_t)q.best_allele;
             id = h->a_id[a].c_str(); star = h->hgenes[h->a_gene[a]].name + "*" + h->a_star[a];
@@ -591,83 +590,11 @@ int32_t hla_package(sp_starphase* h, const std::vector<Read4>& reads, const std:
     return SP_OK;
 }
 
-int32_t hla_lane(sp_starphase* h, const std::vector<std::string>& bams, std::vector<Entry>& out, double* decode_ms, uint32_t* n_reads_out) {
-    const size_t G = h->hgenes.size();
-    std::vector<Read4> reads; std::vector<uint32_t> searched;
-    auto t0 = std::chrono::steady_clock::now();
-    {
-        std::string err;
-        if (hla_collect(h, bams, reads, searched, h->warnings, err) != SP_OK) return h->fail(SP_ERR_INVALID_ARG, err);
-    }
-    *decode_ms += ms_since(t0);
-    *n_reads_out = (uint32_t)reads.size();
-    // K1 on every read (each read is realigned by itself: any order gives the same records); the gene buckets are in QNAME order
-    const std::vector<uint32_t> order = qname_order(reads);
-    std::vector<sp_hla_realign> rec(reads.size());
-    std::vector<sp_hla_call> calls(G);
-    const uint32_t cap = 1 << 16;
-    std::vector<char> cons(G * 2 * (size_t)cap, 0);
-    std::vector<sp_hla_call_config> cfg(G);
-    const bool want_cigars = h->read_debug && !h->debug_folder.empty();
-    ReadCigars cigars;
-    if (!reads.empty()) {
-        sp_seqset* set = nullptr;
-        int32_t rc = upload_reads(h->ctx, reads, order, &set);
-        if (rc != SP_OK) return h->fail(rc, "read upload: " + opt(sp_last_error(h->ctx)));
-        std::unique_ptr<sp_seqset, void (*)(sp_seqset*)> guard(set, sp_seqset_free);
-        rc = sp_hla_realign_reads(h->ctx, h->hla, set, rec.data(), nullptr);
-        if (rc != SP_OK) return h->fail(rc, "sp_hla_realign_reads: " + opt(sp_last_error(h->ctx)));
-        hla_configs(h, rec.data(), (uint32_t)rec.size(), cfg.data());
-        std::vector<uint32_t> genes(G);
-        for (size_t g = 0; g < G; ++g) genes[g] = (uint32_t)g;
-        rc = sp_hla_diplotype_genes(h->ctx, h->hla, (uint32_t)G, genes.data(), set, rec.data(), cfg.data(), calls.data(), cons.data(), cap, nullptr);
-        if (rc != SP_OK) return h->fail(rc, "sp_hla_diplotype_genes: " + opt(sp_last_error(h->ctx)));
-        if (want_cigars) { std::string e; rc = read_cigars(h, set, rec.data(), (uint32_t)rec.size(), &cigars, e); if (rc != SP_OK) return h->fail(rc, e); }
-    } else {
-        for (auto& c : calls) { std::memset(&c, 0, sizeof c); c.status = 1; }
-    }
-    // a read whose accepted mapping is on the reverse strand (status 2): the reference names that mapping's allele and reports its stats
-    // (src/hla/realigner.rs:178-193).  The seeded record carries no allele for it, so those reads alone are mapped again through the audit entry,
-    // which hands out the mappings and the accepted one; the same acceptance rule (:124-146) picks it out of them.
-    // (sp_starphase_call_batch takes the same mappings from sp_hla_realign_reads_rev instead.)
-    std::map<uint32_t, RevHit> rev;                                  // by position in QNAME order
-    {
-        std::vector<uint32_t> rev_pos, sub;
-        for (uint32_t k = 0; k < rec.size(); ++k) if (rec[k].status == 2 && rec[k].best_allele < 0) { rev_pos.push_back(k); sub.push_back(order[k]); }
-        if (!rev_pos.empty()) {
-            sp_seqset* set2 = nullptr;
-            int32_t rc = upload_reads(h->ctx, reads, sub, &set2);
-            if (rc != SP_OK) return h->fail(rc, "read upload: " + opt(sp_last_error(h->ctx)));
-            std::unique_ptr<sp_seqset, void (*)(sp_seqset*)> guard2(set2, sp_seqset_free);
-            std::vector<int32_t> chains(10 * 256);
-            for (uint32_t i = 0; i < rev_pos.size(); ++i) {
-                sp_k1_seed_hit hits[SP_K1_SEL]; uint32_t n_chains = 0, n_hits = 0; int32_t pick = -1; uint64_t counters[4];
-                rc = sp_hla_realign_seeded_audit(h->ctx, h->hla, set2, i, chains.data(), 256, &n_chains, hits, &n_hits, &pick, counters);
-                if (rc != SP_OK) return h->fail(rc, "sp_hla_realign_seeded_audit: " + opt(sp_last_error(h->ctx)));
-                double best = 1.0; int b = -1;
-                for (uint32_t x = 0; x < std::min<uint32_t>(n_hits, SP_K1_SEL); ++x) {
-                    const int tl = hits[x].t_len, um = tl - (hits[x].t_end - hits[x].t_start), nm = hits[x].nm;
-                    if (tl <= 0 || tl - um <= 0) continue;
-                    const double pen = std::max(0.1, (double)(nm + um)) / tl, ed = std::max(0.1, (double)nm) / (tl - um);
-                    if (pen <= 0.5 && ed <= 0.03 && ed < best) { best = ed; b = (int)x; }
-                }
-                if (b >= 0 && hits[b].rev && hits[b].allele >= 0) {
-                    const sp_k1_seed_hit& q = hits[b];
-                    rev[rev_pos[i]] = RevHit{q.allele, (uint64_t)q.t_len, (uint64_t)q.nm, (uint64_t)(q.t_len - (q.t_end - q.t_start))};
-                }
-            }
-        }
-    }
-    std::string err;
-    if (want_cigars && reads.empty()) cigars.stride = 1;
-    const int32_t rc = hla_package(h, reads, searched, order, rec.data(), rev, calls.data(), h->debug_folder, out, err, want_cigars ? &cigars : nullptr, 0);
-    return rc != SP_OK ? h->fail(rc, err) : SP_OK;
-}
-
 // ---------------------------------------------------------------- CYP2D6
 struct CypLane {
+    bool decoded = false; std::vector<Read4> reads;  // the reads of the extraction region (cyp_decode)
     int32_t rc = SP_OK; std::string err, warnings;
-    Entry entry; double decode_ms = 0, ms = 0; uint32_t n_reads = 0;
+    Entry entry; double decode_ms = 0; uint32_t n_reads = 0;
 };
 
 void cyp_problem(sp_starphase* h, sp_cyp_problem& pr) {
@@ -678,7 +605,8 @@ void cyp_problem(sp_starphase* h, sp_cyp_problem& pr) {
 
 // the CYP2D6 entry of a sample whose reads were typed: the call, multi_mapping_details, cyp2d6_alleles.json
 void cyp_package(sp_starphase* h, const sp_cyp_problem& pr, const sp_cyp_call& call, const sp_cyp_region_variants& rv, const std::vector<sp_cyp_read_mapping>& mappings,
-                 const std::vector<Read4>& reads, const std::vector<uint32_t>& order, const std::string& debug_folder, CypLane* L) {
+                 const std::vector<uint32_t>& order, const std::string& debug_folder, CypLane* L) {
+    const std::vector<Read4>& reads = L->reads;
     sp_gene_details* d = L->entry.details->d;
     if (call.status == 16 || call.status == 17 || call.status == 18) {              // CallerError -> PgxGeneDetails::no_match() (src/diplotyper.rs:316-327)
         L->entry.constructor = SP_DETAILS_NO_MATCH;
@@ -706,81 +634,71 @@ void cyp_package(sp_starphase* h, const sp_cyp_problem& pr, const sp_cyp_call& c
     }
 }
 
-void cyp_lane(sp_starphase* h, const std::vector<std::string>& bams, CypLane* L) {
-    auto t_lane = std::chrono::steady_clock::now();
-    L->entry.gene = "CYP2D6"; L->entry.details.reset(new GeneDetailsPtr());
-    sp_gene_details* d = L->entry.details->d;
-    std::vector<Read4> reads; std::set<std::string> seen;
-    auto t0 = std::chrono::steady_clock::now();
-    if (collect_reads(bams, h->cyp_chrom, h->cyp_start, h->cyp_end, seen, reads, L->warnings, L->err) != SP_OK) { L->rc = SP_ERR_INVALID_ARG; return; }
-    L->decode_ms = ms_since(t0);
-    L->n_reads = (uint32_t)reads.size();
-    L->entry.constructor = SP_DETAILS_FROM_MULTI_MAPPINGS;
-    if (reads.empty()) {                            // "No reads found for CYP2D6 consensus generation." (src/cyp2d6/caller.rs:254-266)
-        sp_gene_details_add_diplotype(d, "NO_READS", "NO_READS");
-        L->ms = ms_since(t_lane);
-        return;
-    }
-    sp_cyp_problem pr{};
-    cyp_problem(h, pr);
-    sp_seqset* set = nullptr;
-    const std::vector<uint32_t> order = qname_order(reads);                        // read_collection is a BTreeMap: QNAME order
-    int32_t rc = upload_reads(h->ctx2, reads, order, &set);
-    if (rc != SP_OK) { L->rc = rc; L->err = "read upload: " + opt(sp_last_error(h->ctx2)); return; }
-    std::unique_ptr<sp_seqset, void (*)(sp_seqset*)> guard(set, sp_seqset_free);
-    sp_cyp_call call{};
-    std::vector<uint8_t> state((size_t)SP_CYP_MAXCONS * std::max<uint32_t>(pr.n_variants, 1));
-    sp_cyp_region_variants rv{}; rv.state = state.data();
-    std::vector<sp_cyp_read_mapping> mappings;
-    rc = spi_cyp_diplotype_mappings(h->ctx2, &pr, set, &call, nullptr, 0, &rv, &mappings);
-    if (rc != SP_OK) { L->rc = rc; L->err = "sp_cyp_diplotype: " + opt(sp_last_error(h->ctx2)); return; }
-    cyp_package(h, pr, call, rv, mappings, reads, order, h->debug_folder, L);
-    if (L->rc == SP_OK) L->ms = ms_since(t_lane);
-}
-
-// ---------------------------------------------------------------- sp_starphase_call_batch
-struct BSample : VarSample {
+// ---------------------------------------------------------------- the pipeline of a group of samples
+struct Sample : VarSample {
     std::vector<std::string> bams; std::string debug; bool run_hla = false, run_cyp = false;
     int stage = 0;                                   // where it failed: 0 the checks, 1 variant genes, 2 HLA, 3 CYP2D6 or the result
     std::string warnings;
-    // decoded
+    // HLA: decoded (hla_decode), typed
     std::vector<Read4> hreads; std::vector<uint32_t> hsearched; std::string hwarn, herr; int32_t hrc = SP_OK;
-    std::vector<Read4> creads; std::string cwarn, cerr; int32_t crc = SP_OK;
-    // typed
     std::vector<Entry> hla_entries;
     CypLane cyp;
     void fail(int at, int32_t code, const std::string& m) { if (rc == SP_OK) { rc = code; err = m; stage = at; } }
-    void release_reads() { std::vector<Read4>().swap(hreads); std::vector<uint32_t>().swap(hsearched); std::vector<Read4>().swap(creads); vf = VcfFetch(); }
 };
 
-void decode_sample(sp_starphase* h, BSample& b) {
+// the inputs of a sample, resolved against the handle's, and the checks made before anything is read
+void sample_setup(sp_starphase* h, const sp_sample_inputs& in, const std::string& debug_folder, Sample& b) {
+    for (uint32_t k = 0; k < in.n_bams; ++k) b.bams.push_back(opt(in.bams[k]));
+    b.has_vcf = in.vcf != nullptr; b.vcf = opt(in.vcf);
+    b.sample = in.sample_name ? opt(in.sample_name) : h->sample_name;
+    b.sv = in.sv_vcf ? opt(in.sv_vcf) : h->sv_vcf;
+    b.debug = debug_folder;
+    if (!b.bams.empty() && !h->fasta) b.fail(0, SP_ERR_INVALID_ARG, "Reference genome is required for reading alignment files");
+    else if (!b.bams.empty() && !h->s.debug_skip_hla && !h->hla_err.empty()) b.fail(0, SP_ERR_INVALID_ARG, h->hla_err);
+    else if (!b.bams.empty() && h->cyp_selected && !h->cyp_err.empty()) b.fail(0, SP_ERR_INVALID_ARG, h->cyp_err);
     if (b.rc != SP_OK) return;
-    if (b.has_vcf) vcf_fetch(h, h->win, b.vcf, b.sv, b.sample, b.vf);
-    if (b.run_hla) b.hrc = hla_collect(h, b.bams, b.hreads, b.hsearched, b.hwarn, b.herr);
-    if (b.run_cyp) {
-        std::set<std::string> seen;
-        b.crc = collect_reads(b.bams, h->cyp_chrom, h->cyp_start, h->cyp_end, seen, b.creads, b.cwarn, b.cerr);
-    }
+    b.run_hla = !b.bams.empty() && h->hla && !h->s.debug_skip_hla;
+    b.run_cyp = !b.bams.empty() && h->cyp_selected && h->cyp;
+    if (!b.debug.empty()) mkdir(b.debug.c_str(), 0755);
 }
 
-// the CYP2D6 lane of a group: one cohort call on the second context for every sample with reads.  only_ok (settings.sequential): the samples whose
-// other lanes failed are skipped, as sp_starphase_call does not run the lane after a failure
-void cyp_group(sp_starphase* h, std::vector<BSample*> group, bool only_ok, double* ms) {
+void hla_decode(sp_starphase* h, Sample& b) { b.hrc = hla_collect(h, b.bams, b.hreads, b.hsearched, b.hwarn, b.herr); }
+void cyp_decode(sp_starphase* h, Sample& b) {
+    const auto t0 = std::chrono::steady_clock::now();
+    CypLane& L = b.cyp;
+    std::set<std::string> seen;
+    L.rc = collect_reads(b.bams, h->cyp_chrom, h->cyp_start, h->cyp_end, seen, L.reads, L.warnings, L.err);
+    L.decoded = true; L.decode_ms = ms_since(t0);
+}
+// everything a sample reads from its files, ahead of the lanes (a decode worker of a batch)
+void decode_sample(sp_starphase* h, Sample& b) {
+    if (b.rc != SP_OK) return;
+    if (b.has_vcf) vcf_fetch(h, h->win, b.vcf, b.sv, b.sample, b.vf);
+    if (b.run_hla) hla_decode(h, b);
+    if (b.run_cyp) cyp_decode(h, b);
+}
+
+// the CYP2D6 lane of a group, on the second context: a sample not decoded ahead reads its BAMs here (so a single call's decode runs on this lane's thread),
+// then one cohort call for the samples with reads -- a lane with one such sample takes the single-sample entry point.
+// only_ok (settings.sequential): the samples whose other lanes failed are skipped
+void cyp_group(sp_starphase* h, std::vector<Sample*> group, bool only_ok, double* ms) {
     auto t0 = std::chrono::steady_clock::now();
     sp_cyp_problem pr{};
     cyp_problem(h, pr);
-    std::vector<BSample*> typed; std::vector<std::vector<uint32_t>> orders; std::vector<sp_seqset*> sets;
-    for (BSample* b : group) {
+    std::vector<Sample*> typed; std::vector<std::vector<uint32_t>> orders; std::vector<sp_seqset*> sets;
+    for (Sample* b : group) {
         if (!b->run_cyp || (only_ok && b->rc != SP_OK)) continue;
         CypLane* L = &b->cyp;
         L->entry.gene = "CYP2D6"; L->entry.details.reset(new GeneDetailsPtr());
-        L->warnings = b->cwarn; L->n_reads = (uint32_t)b->creads.size();
-        if (b->crc != SP_OK) { L->rc = b->crc; L->err = b->cerr; continue; }
+        if (!L->decoded) cyp_decode(h, *b);
+        L->n_reads = (uint32_t)L->reads.size();
+        if (L->rc != SP_OK) continue;
         L->entry.constructor = SP_DETAILS_FROM_MULTI_MAPPINGS;
-        if (b->creads.empty()) { sp_gene_details_add_diplotype(L->entry.details->d, "NO_READS", "NO_READS"); continue; }
-        orders.push_back(qname_order(b->creads));
+        // "No reads found for CYP2D6 consensus generation." (src/cyp2d6/caller.rs:254-266)
+        if (L->reads.empty()) { sp_gene_details_add_diplotype(L->entry.details->d, "NO_READS", "NO_READS"); continue; }
+        orders.push_back(qname_order(L->reads));                     // read_collection is a BTreeMap: QNAME order
         sp_seqset* set = nullptr;
-        const int32_t rc = upload_reads(h->ctx2, b->creads, orders.back(), &set);
+        const int32_t rc = upload_reads(h->ctx2, {{&L->reads, &orders.back()}}, &set);
         if (rc != SP_OK) { L->rc = rc; L->err = "read upload: " + opt(sp_last_error(h->ctx2)); orders.pop_back(); continue; }
         typed.push_back(b); sets.push_back(set);
     }
@@ -792,49 +710,47 @@ void cyp_group(sp_starphase* h, std::vector<BSample*> group, bool only_ok, doubl
         std::vector<sp_cyp_region_variants> rv(n);
         for (uint32_t k = 0; k < n; ++k) { rv[k] = sp_cyp_region_variants{}; rv[k].state = state.data() + per * k; }
         std::vector<std::vector<sp_cyp_read_mapping>> mappings(n);
-        std::vector<int32_t> rcs(n, SP_OK);
-        spi_cyp_diplotype_cohort_mappings(h->ctx2, &pr, n, sets.data(), calls.data(), nullptr, 0, rv.data(), mappings.data(), rcs.data());
+        std::vector<int32_t> rcs(n, SP_ERR_INVALID_ARG);             // until the cohort call has typed it
+        if (n > 1) spi_cyp_diplotype_cohort_mappings(h->ctx2, &pr, n, sets.data(), calls.data(), nullptr, 0, rv.data(), mappings.data(), rcs.data());
         for (uint32_t k = 0; k < n; ++k) {
             CypLane* L = &typed[k]->cyp;
             if (rcs[k] != SP_OK) {
-                // the context's error text may be another sample's: the sample goes through the call sp_starphase_call makes, alone
+                // alone: the only sample of the lane, or one the cohort call failed (the context's error text may be another sample's)
                 const int32_t rc = spi_cyp_diplotype_mappings(h->ctx2, &pr, sets[k], &calls[k], nullptr, 0, &rv[k], &mappings[k]);
                 if (rc != SP_OK) { L->rc = rc; L->err = "sp_cyp_diplotype: " + opt(sp_last_error(h->ctx2)); continue; }
             }
-            cyp_package(h, pr, calls[k], rv[k], mappings[k], typed[k]->creads, orders[k], typed[k]->debug, L);
+            cyp_package(h, pr, calls[k], rv[k], mappings[k], orders[k], typed[k]->debug, L);
         }
     }
     for (sp_seqset* s : sets) sp_seqset_free(s);
     *ms += ms_since(t0);
 }
 
-// the HLA lane of samples that share the device passes: their reads in one set (sample by sample, QNAME order within a sample), one K1 pass that
-// also names the reverse-strand reads, the (sample, gene) problems in one cohort call, then each sample's entries as hla_lane makes them.
-// Errors are named as sp_starphase_call names them.
-int32_t hla_pass(sp_starphase* h, const std::vector<BSample*>& with, std::string& err) {
+// the HLA lane of samples that share the device passes: their reads in one set (sample by sample, QNAME order within a sample; each read is realigned
+// by itself, so any order gives the same records), one K1 pass that also names the reverse-strand reads, the (sample, gene) problems in one call
+// (the single-sample entry point when one sample has reads), then each sample's entries.
+// Exhaustive K1 (a caller's context with k1_best_n = 0) has no seeded stage to take reverse-strand mappings from: no read is named after one.
+int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string& err) {
     const size_t G = h->hgenes.size();
     const uint32_t cap = 1 << 16;
-    std::vector<std::vector<uint32_t>> orders; std::vector<uint32_t> first{0};
-    for (BSample* b : with) { orders.push_back(qname_order(b->hreads)); first.push_back(first.back() + (uint32_t)b->hreads.size()); }
+    std::vector<std::vector<uint32_t>> orders; std::vector<uint32_t> first{0}; std::vector<ReadPart> parts;
+    for (Sample* b : with) { orders.push_back(qname_order(b->hreads)); first.push_back(first.back() + (uint32_t)b->hreads.size()); }
+    for (size_t k = 0; k < with.size(); ++k) parts.push_back(ReadPart{&with[k]->hreads, &orders[k]});
     const uint32_t R = first.back();
-    std::vector<sp_hla_realign> rec(R); std::vector<sp_hla_rev_hit> rev(R);
+    std::vector<sp_hla_realign> rec(R); std::vector<sp_hla_rev_hit> rev(R, sp_hla_rev_hit{-1, 0, 0, 0, 0, 0});
     std::vector<sp_hla_call> calls(with.size() * G);
     for (auto& c : calls) { std::memset(&c, 0, sizeof c); c.status = 1; }
     bool want_cigars = false;                                        // one traceback pass for the group when any of its samples has a debug folder
-    for (BSample* b : with) want_cigars |= h->read_debug && !b->debug.empty();
+    for (Sample* b : with) want_cigars |= h->read_debug && !b->debug.empty();
     ReadCigars cigars; cigars.stride = 1;
     if (R) {
-        std::vector<uint8_t> bytes; std::vector<uint64_t> off{0}; std::vector<uint32_t> lens;
-        for (size_t k = 0; k < with.size(); ++k)
-            for (uint32_t i : orders[k]) { const Read4& r = with[k]->hreads[i]; bytes.insert(bytes.end(), r.seq4.begin(), r.seq4.end()); off.push_back(bytes.size()); lens.push_back(r.len); }
-        if (bytes.empty()) bytes.push_back(0);
         sp_seqset* set = nullptr;
-        int32_t rc = sp_seqset_upload_format(h->ctx, SP_SEQ_BAM4, bytes.data(), off.data(), lens.data(), R, &set);
+        int32_t rc = upload_reads(h->ctx, parts, &set);
         if (rc != SP_OK) { err = "read upload: " + opt(sp_last_error(h->ctx)); return rc; }
         std::unique_ptr<sp_seqset, void (*)(sp_seqset*)> guard(set, sp_seqset_free);
-        rc = sp_hla_realign_reads_rev(h->ctx, h->hla, set, rec.data(), rev.data());
+        rc = h->ctx->k1_best_n > 0 ? sp_hla_realign_reads_rev(h->ctx, h->hla, set, rec.data(), rev.data()) : sp_hla_realign_reads(h->ctx, h->hla, set, rec.data(), nullptr);
         if (rc != SP_OK) { err = "sp_hla_realign_reads: " + opt(sp_last_error(h->ctx)); return rc; }
-        // the samples with reads are the cohort; a sample without reads keeps the no-reads calls, as hla_lane does
+        // the samples with reads are the cohort; a sample without reads keeps the no-reads calls
         std::vector<uint32_t> read_sample(R), at;
         std::vector<sp_hla_call_config> cfg;
         for (size_t k = 0; k < with.size(); ++k) {
@@ -848,49 +764,69 @@ int32_t hla_pass(sp_starphase* h, const std::vector<BSample*>& with, std::string
         for (size_t g = 0; g < G; ++g) genes[g] = (uint32_t)g;
         std::vector<sp_hla_call> cc(at.size() * G);
         const size_t need = at.size() * G * 2 * (size_t)cap;
-        if (h->batch_cons.size() < need) h->batch_cons.resize(need);
-        rc = at.size() == 1 ? sp_hla_diplotype_genes(h->ctx, h->hla, (uint32_t)G, genes.data(), set, rec.data(), cfg.data(), cc.data(), h->batch_cons.data(), cap, nullptr)
+        if (h->hla_cons.size() < need) h->hla_cons.resize(need);
+        rc = at.size() == 1 ? sp_hla_diplotype_genes(h->ctx, h->hla, (uint32_t)G, genes.data(), set, rec.data(), cfg.data(), cc.data(), h->hla_cons.data(), cap, nullptr)
                             : sp_hla_diplotype_cohort_samples(h->ctx, h->hla, (uint32_t)at.size(), read_sample.data(), (uint32_t)G, genes.data(), set, rec.data(),
-                                                              cfg.data(), cc.data(), h->batch_cons.data(), cap, nullptr);
+                                                              cfg.data(), cc.data(), h->hla_cons.data(), cap, nullptr);
         if (rc != SP_OK) { err = "sp_hla_diplotype_genes: " + opt(sp_last_error(h->ctx)); return rc; }
         for (size_t x = 0; x < at.size(); ++x) std::copy(cc.begin() + x * G, cc.begin() + (x + 1) * G, calls.begin() + (size_t)at[x] * G);
         if (want_cigars) { rc = read_cigars(h, set, rec.data(), R, &cigars, err); if (rc != SP_OK) return rc; }
     }
     for (size_t k = 0; k < with.size(); ++k) {
-        BSample* b = with[k];
-        std::map<uint32_t, RevHit> rv;
-        for (uint32_t p = 0; p < first[k + 1] - first[k]; ++p) {
-            const sp_hla_rev_hit& q = rev[first[k] + p];
-            if (q.allele >= 0) rv[p] = RevHit{q.allele, (uint64_t)q.t_len, (uint64_t)q.nm, (uint64_t)(q.t_len - (q.t_end - q.t_start))};
-        }
+        Sample* b = with[k];
         std::string e;
-        const int32_t rc = hla_package(h, b->hreads, b->hsearched, orders[k], rec.data() + first[k], rv, calls.data() + k * G, b->debug, b->hla_entries, e, want_cigars ? &cigars : nullptr, first[k]);
+        const int32_t rc = hla_package(h, b->hreads, b->hsearched, orders[k], rec.data() + first[k], rev.data() + first[k], calls.data() + k * G, b->debug, b->hla_entries, e,
+                                       want_cigars ? &cigars : nullptr, first[k]);
         if (rc != SP_OK) b->fail(2, rc, e);
     }
     return SP_OK;
 }
 
-// the HLA lane of a group.  The shared passes fail as a whole (a read too long for K1, a failing consensus unit of one sample, ...): the group then
-// goes through them once more sample by sample, so only the sample that has the failure fails, with its own text
-void hla_group(sp_starphase* h, const std::vector<BSample*>& group, uint64_t* n_reads) {
-    std::vector<BSample*> with;
-    for (BSample* b : group) {
+// the HLA lane of a group (decoded already); returns the reads it typed.  The shared passes fail as a whole (a read too long for K1, a failing consensus
+// unit of one sample, ...): the group then goes through them once more sample by sample, so only the sample that has the failure fails, with its own text
+uint64_t hla_group(sp_starphase* h, const std::vector<Sample*>& group) {
+    std::vector<Sample*> with; uint64_t n_reads = 0;
+    for (Sample* b : group) {
         if (!b->run_hla || b->rc != SP_OK) continue;
         if (b->hrc != SP_OK) { b->fail(2, b->hrc, b->herr); continue; }
-        *n_reads += b->hreads.size();
+        n_reads += b->hreads.size();
         with.push_back(b);
     }
-    if (with.empty()) return;
+    if (with.empty()) return n_reads;
     std::string err;
     const int32_t rc = hla_pass(h, with, err);
-    if (rc == SP_OK) return;
-    if (with.size() == 1) { with[0]->fail(2, rc, err); return; }
-    for (BSample* b : with) {
+    if (rc == SP_OK) return n_reads;
+    if (with.size() == 1) { with[0]->fail(2, rc, err); return n_reads; }
+    for (Sample* b : with) {
         b->hla_entries.clear();
         std::string e;
         const int32_t rb = hla_pass(h, {b}, e);
         if (rb != SP_OK) b->fail(2, rb, e);
     }
+    return n_reads;
+}
+
+// the result of a sample whose lanes are done.  Errors in the order the checks, variant genes, HLA, CYP2D6, the result itself; the warnings are the HLA
+// lane's if it ran and the CYP2D6 lane's only if everything before it succeeded.  The entries in the reference's order: variant genes, HLA genes, CYP2D6
+// (StarphaseJson::insert refuses a second entry for a gene).  Gives the sample's reads and entries back.
+void sample_result(sp_starphase* h, Sample& b, sp_result** out) {
+    if (b.rc == SP_OK && b.run_cyp && b.cyp.rc != SP_OK) b.fail(3, b.cyp.rc, b.cyp.err);
+    const bool hla_ran = b.rc == SP_OK || b.stage >= 2, cyp_kept = b.rc == SP_OK || b.stage >= 3;
+    b.warnings = (hla_ran ? b.hwarn : std::string()) + (cyp_kept && b.run_cyp ? b.cyp.warnings : std::string());
+    if (b.rc == SP_OK) {
+        sp_result* res = nullptr;
+        sp_result_create(h->db, nullptr, &res);
+        std::unique_ptr<sp_result, void (*)(sp_result*)> guard(res, sp_result_free);
+        std::vector<Entry*> all;
+        for (auto& e : b.entries) all.push_back(&e);
+        for (auto& e : b.hla_entries) all.push_back(&e);
+        if (b.run_cyp) all.push_back(&b.cyp.entry);
+        for (Entry* e : all)
+            if (b.rc == SP_OK && sp_result_insert(res, e->gene.c_str(), e->details->d, e->constructor) != SP_OK) b.fail(3, SP_ERR_INVALID_ARG, opt(sp_result_last_error(res)));
+        if (b.rc == SP_OK) *out = guard.release();
+    }
+    std::vector<Read4>().swap(b.hreads); std::vector<uint32_t>().swap(b.hsearched); std::vector<Read4>().swap(b.cyp.reads); b.vf = VcfFetch();
+    b.entries.clear(); b.hla_entries.clear(); b.cyp.entry.details.reset();
 }
 
 }  // namespace
@@ -988,7 +924,7 @@ int32_t sp_starphase_create(sp_ctx* ctx, const char* database_path, const char* 
         spi_gene_entry_extras(h->db, vg.g, &vg.reference_allele, &vg.has_sv, &vg.sv_chrom);
         h->vgenes.push_back(std::move(vg));
     }
-    // the fetch window of every selected gene with variants (variant_lane: +-50 bp around each variant)
+    // the fetch window of every selected gene with variants (vcf_fetch: +-50 bp around each variant)
     h->win.assign(h->vgenes.size(), GeneWindow());
     for (size_t i = 0; i < h->vgenes.size(); ++i) {
         const sp_starphase::VGene& vg = h->vgenes[i];
@@ -1087,23 +1023,8 @@ int32_t sp_starphase_call_batch(sp_starphase* h, uint32_t n, const sp_sample_inp
     const uint32_t n_threads = opts && opts->decode_threads ? opts->decode_threads : std::min(16u, hw);
     h->batch_err.assign(n, std::string()); h->batch_warn.assign(n, std::string());
     for (uint32_t i = 0; i < n; ++i) { out[i] = nullptr; if (sample_rc) sample_rc[i] = SP_OK; }
-    // the samples, with the checks sp_starphase_call makes before it reads anything
-    std::vector<BSample> S(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        const sp_sample_inputs& in = inputs[i]; BSample& b = S[i];
-        for (uint32_t k = 0; k < in.n_bams; ++k) b.bams.push_back(opt(in.bams[k]));
-        b.has_vcf = in.vcf != nullptr; b.vcf = opt(in.vcf);
-        b.sample = in.sample_name ? opt(in.sample_name) : h->sample_name;
-        b.sv = in.sv_vcf ? opt(in.sv_vcf) : h->sv_vcf;
-        b.debug = debug_folders && debug_folders[i] ? std::string(debug_folders[i]) : std::string();
-        b.run_hla = !b.bams.empty() && h->hla && !h->s.debug_skip_hla;
-        b.run_cyp = !b.bams.empty() && h->cyp_selected && h->cyp;
-        if (!b.bams.empty() && !h->fasta) { b.rc = SP_ERR_INVALID_ARG; b.err = "Reference genome is required for reading alignment files"; }
-        else if (!b.bams.empty() && !h->s.debug_skip_hla && !h->hla_err.empty()) { b.rc = SP_ERR_INVALID_ARG; b.err = h->hla_err; }
-        else if (!b.bams.empty() && h->cyp_selected && !h->cyp_err.empty()) { b.rc = SP_ERR_INVALID_ARG; b.err = h->cyp_err; }
-        if (b.rc != SP_OK) b.run_hla = b.run_cyp = false;
-        else if (!b.debug.empty()) mkdir(b.debug.c_str(), 0755);
-    }
+    std::vector<Sample> S(n);
+    for (uint32_t i = 0; i < n; ++i) sample_setup(h, inputs[i], debug_folders && debug_folders[i] ? std::string(debug_folders[i]) : std::string(), S[i]);
     sp_starphase_batch_timing& T = h->batch_timing;
     T.n_samples = n;
     // host decode of a group on the worker pool; group k + 1 is decoded while group k is on the device
@@ -1127,7 +1048,7 @@ int32_t sp_starphase_call_batch(sp_starphase* h, uint32_t n, const sp_sample_inp
         else ahead.join();
         T.decode_ms += ahead_ms; ++T.n_groups;
         if (g1 < n) ahead = std::thread(decode, g1, std::min(n, g1 + max_group), &ahead_ms);
-        std::vector<BSample*> group;
+        std::vector<Sample*> group;
         for (uint32_t i = g0; i < g1; ++i) group.push_back(&S[i]);
         // CYP2D6 on its own thread and context, beside the variant genes and the HLA genes (settings.sequential: after them)
         double cyp_ms = 0;
@@ -1135,40 +1056,24 @@ int32_t sp_starphase_call_batch(sp_starphase* h, uint32_t n, const sp_sample_inp
         if (!h->s.sequential) cyp = std::thread(cyp_group, h, group, false, &cyp_ms);
         auto t0 = std::chrono::steady_clock::now();
         std::vector<VarSample*> vs;
-        for (BSample* b : group) if (b->rc == SP_OK) vs.push_back(b);
+        for (Sample* b : group) if (b->rc == SP_OK) vs.push_back(b);
         variant_samples(h, vs);
-        for (VarSample* v : vs) if (v->rc != SP_OK) static_cast<BSample*>(v)->stage = 1;
+        for (VarSample* v : vs) if (v->rc != SP_OK) static_cast<Sample*>(v)->stage = 1;
         T.variant_ms += ms_since(t0);
         t0 = std::chrono::steady_clock::now();
-        hla_group(h, group, &T.n_hla_reads);
+        T.n_hla_reads += hla_group(h, group);
         T.hla_ms += ms_since(t0);
         if (cyp.joinable()) cyp.join();
         else cyp_group(h, group, true, &cyp_ms);
         T.cyp_ms += cyp_ms;
-        // the results, in sp_starphase_call's order of errors: the checks, variant genes, HLA, CYP2D6; the warnings it keeps up to its failure
         t0 = std::chrono::steady_clock::now();
         for (uint32_t i = g0; i < g1; ++i) {
-            BSample& b = S[i];
+            Sample& b = S[i];
             if (b.run_cyp) T.n_cyp_reads += b.cyp.n_reads;
-            if (b.rc == SP_OK && b.run_cyp && b.cyp.rc != SP_OK) b.fail(3, b.cyp.rc, b.cyp.err);
-            const bool hla_ran = b.rc == SP_OK || b.stage >= 2, cyp_kept = b.rc == SP_OK || b.stage >= 3;
-            b.warnings = (hla_ran ? b.hwarn : std::string()) + (cyp_kept && b.run_cyp ? b.cyp.warnings : std::string());
-            if (b.rc == SP_OK) {
-                sp_result* res = nullptr;
-                sp_result_create(h->db, nullptr, &res);
-                std::unique_ptr<sp_result, void (*)(sp_result*)> guard(res, sp_result_free);
-                std::vector<Entry*> all;
-                for (auto& e : b.entries) all.push_back(&e);
-                for (auto& e : b.hla_entries) all.push_back(&e);
-                if (b.run_cyp) { b.cyp.entry.gene = "CYP2D6"; all.push_back(&b.cyp.entry); }
-                for (Entry* e : all)
-                    if (b.rc == SP_OK && sp_result_insert(res, e->gene.c_str(), e->details->d, e->constructor) != SP_OK) b.fail(3, SP_ERR_INVALID_ARG, opt(sp_result_last_error(res)));
-                if (b.rc == SP_OK) out[i] = guard.release();
-            }
+            sample_result(h, b, &out[i]);
             if (b.rc != SP_OK) { ++T.n_failed; if (first_rc == SP_OK) { first_rc = b.rc; h->err = "sample " + std::to_string(i) + ": " + b.err; } }
             if (sample_rc) sample_rc[i] = b.rc;
             h->batch_err[i] = b.err; h->batch_warn[i] = b.warnings;
-            b.release_reads(); b.entries.clear(); b.hla_entries.clear(); b.cyp.entry.details.reset();
         }
         T.package_ms += ms_since(t0);
     }
@@ -1176,52 +1081,42 @@ int32_t sp_starphase_call_batch(sp_starphase* h, uint32_t n, const sp_sample_inp
     return first_rc;
 }
 
+// The pipeline for a group of one.  Nothing is decoded ahead: the CYP2D6 lane reads its BAM region on its own thread beside the variant genes and the
+// HLA decode.  On a caller's context in exhaustive K1 mode (k1_best_n = 0) no read is named after a reverse-strand mapping (hla_pass).
 int32_t sp_starphase_call(sp_starphase* h, const sp_sample_inputs* in, sp_result** out) {
     if (!h || !in || !out) return SP_ERR_INVALID_ARG;
     *out = nullptr;
     h->err.clear(); h->warnings.clear(); h->timing = sp_starphase_timing{};
     const auto t_call = std::chrono::steady_clock::now();
-    std::vector<std::string> bams;
-    for (uint32_t i = 0; i < in->n_bams; ++i) bams.push_back(opt(in->bams[i]));
-    if (!bams.empty() && !h->fasta) return h->fail(SP_ERR_INVALID_ARG, "Reference genome is required for reading alignment files");
-    if (!bams.empty() && !h->s.debug_skip_hla && !h->hla_err.empty()) return h->fail(SP_ERR_INVALID_ARG, h->hla_err);
-    if (!bams.empty() && h->cyp_selected && !h->cyp_err.empty()) return h->fail(SP_ERR_INVALID_ARG, h->cyp_err);
-    const std::string sample = in->sample_name ? opt(in->sample_name) : h->sample_name;
-    const std::string sv = in->sv_vcf ? opt(in->sv_vcf) : h->sv_vcf;
-    if (!h->debug_folder.empty()) mkdir(h->debug_folder.c_str(), 0755);
+    Sample b;
+    sample_setup(h, *in, h->debug_folder, b);
+    if (b.rc != SP_OK) return h->fail(b.rc, b.err);
+    const std::vector<Sample*> one{&b};
+    sp_starphase_timing& T = h->timing;
     // the CYP2D6 lane: on its own host thread and context unless sequential
-    CypLane cyp;
-    const bool run_cyp = !bams.empty() && h->cyp_selected && h->cyp;
     std::thread worker;
-    if (run_cyp && !h->s.sequential) worker = std::thread(cyp_lane, h, std::cref(bams), &cyp);
-    std::vector<Entry> var_entries, hla_entries;
-    int32_t rc = SP_OK;
+    if (b.run_cyp && !h->s.sequential) worker = std::thread(cyp_group, h, one, false, &T.cyp_ms);
     auto t0 = std::chrono::steady_clock::now();
-    if (in->vcf) rc = variant_lane(h, in->vcf, sv, sample, var_entries);
-    h->timing.variant_ms = ms_since(t0);
+    if (b.has_vcf) {
+        vcf_fetch(h, h->win, b.vcf, b.sv, b.sample, b.vf);
+        variant_samples(h, {&b});
+        if (b.rc != SP_OK) b.stage = 1;
+    }
+    T.variant_ms = ms_since(t0);
     t0 = std::chrono::steady_clock::now();
-    if (rc == SP_OK && !bams.empty() && h->hla && !h->s.debug_skip_hla)
-        rc = hla_lane(h, bams, hla_entries, &h->timing.bam_decode_ms, &h->timing.n_hla_reads);
-    h->timing.hla_ms = ms_since(t0);
+    if (b.run_hla && b.rc == SP_OK) {
+        hla_decode(h, b);
+        T.bam_decode_ms = ms_since(t0);
+        T.n_hla_reads = (uint32_t)hla_group(h, one);
+    }
+    T.hla_ms = ms_since(t0);
     if (worker.joinable()) worker.join();
-    else if (run_cyp && rc == SP_OK) cyp_lane(h, bams, &cyp);
-    if (rc != SP_OK) return rc;
-    h->warnings += cyp.warnings;
-    if (cyp.rc != SP_OK) return h->fail(cyp.rc, cyp.err);
-    h->timing.bam_decode_ms += cyp.decode_ms; h->timing.cyp_ms = cyp.ms; h->timing.n_cyp_reads = cyp.n_reads;
-    // the entries in the reference's order: variant genes, HLA genes, CYP2D6 (StarphaseJson::insert refuses a second entry for a gene)
-    sp_result* res = nullptr;
-    sp_result_create(h->db, nullptr, &res);
-    std::unique_ptr<sp_result, void (*)(sp_result*)> guard(res, sp_result_free);
-    if (run_cyp) cyp.entry.gene = "CYP2D6";
-    std::vector<Entry*> all;
-    for (auto& e : var_entries) all.push_back(&e);
-    for (auto& e : hla_entries) all.push_back(&e);
-    if (run_cyp) all.push_back(&cyp.entry);
-    for (Entry* e : all)
-        if (sp_result_insert(res, e->gene.c_str(), e->details->d, e->constructor) != SP_OK) return h->fail(SP_ERR_INVALID_ARG, opt(sp_result_last_error(res)));
-    h->timing.call_ms = ms_since(t_call);
-    *out = guard.release();
+    else if (b.run_cyp) cyp_group(h, one, true, &T.cyp_ms);
+    T.bam_decode_ms += b.cyp.decode_ms; T.n_cyp_reads = b.cyp.n_reads;
+    sample_result(h, b, out);
+    h->warnings = b.warnings;
+    if (b.rc != SP_OK) return h->fail(b.rc, b.err);
+    T.call_ms = ms_since(t_call);
     return SP_OK;
 }
 

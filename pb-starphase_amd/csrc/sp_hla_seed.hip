@@ -24,7 +24,7 @@ namespace {
 // ---- the reference's settings (map-hifi; oracle/mm2.c omm_default_opts)
 constexpr int MZ_K = 19, MZ_W = 19;
 constexpr uint64_t MZ_MASK = (1ull << (2 * MZ_K)) - 1;
-constexpr int MIN_MID_OCC = 50, MAX_MID_OCC = 500, MAX_MAX_OCC = 4095, OCC_DIST = 500;
+constexpr int MIN_MID_OCC = 50, MAX_MID_OCC = 500, MAX_MAX_OCC = 4095;
 constexpr float MID_OCC_FRAC = 2e-4f;
 constexpr int CH_MAX_GAP = 10000, CH_BW = 500, CH_MAX_SKIP = 25, CH_MAX_ITER = 5000, CH_MIN_CNT = 3, CH_MIN_SCORE = 40;
 constexpr float MASK_LEVEL = 0.5f, PRI_RATIO = 0.8f;
@@ -305,8 +305,6 @@ struct SSel { int32_t rid, rev, score, cnt, diag, qs, qe, rs, re, n_chains; };  
 struct SDp { uint32_t key; int32_t f; int16_t p; uint16_t t; };               // one anchor of a DP: 12 bytes of LDS
 
 constexpr int CH_THREADS = 256;
-constexpr int DP_CAP = 3584;                    // anchors a DP round of a workgroup holds in LDS
-constexpr int DP_CHUNK = 1024;                  // targets a workgroup takes from the list at a time
 constexpr int WIN_KEYS = 12288;                 // targets per window (4 bytes each in LDS)
 
 __device__ __forceinline__ int32_t chain_sc(uint32_t ai, uint32_t aj, const int32_t* __restrict__ pen) {
@@ -1228,7 +1226,7 @@ __global__ void k1s_pick_kernel(SeqSetView reads, const SSel* __restrict__ sel, 
         }
     }
     int pick = -1, n_out = 0, n2 = 0; double best = 1.0;
-    int rpick = -1; double rbest = 1.0;            // rev_out: hla_lane's audit rule over the same mappings (it skips an empty aligned span instead of dividing by it)
+    int rpick = -1; double rbest = 1.0;            // rev_out: the same acceptance rule over the same mappings, but an empty aligned span is skipped instead of divided by
     for (int i = 0; i < nh; ++i) {
         const int p = h[i].parent;
         bool keep = p == i;

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -16,7 +17,11 @@ namespace {
 
 enum { EX_OK_ = 0, EX_CLAP = 2, EX_USAGE_ = 64, EX_DATAERR_ = 65, EX_NOINPUT_ = 66, EX_UNAVAILABLE_ = 69, EX_IOERR_ = 74 };
 
-const char* HELP =
+const char* USAGE = "starphase_hip diplotype [OPTIONS] --database <JSON> --reference <FASTA> --output-calls <JSON>";
+const char* BATCH_USAGE = "starphase_hip diplotype-batch [OPTIONS] --database <JSON> --reference <FASTA> --manifest <TSV>";
+
+// the help texts: each command's own head and Execution section around the sections of the options both take
+const char* HELP_HEAD =
     "Diplotype a sample from its VCF / BAM files against a PGx database (pbstarphase diplotype)\n"
     "\n"
     "Usage: starphase_hip diplotype [OPTIONS] --database <JSON> --reference <FASTA> --output-calls <JSON>\n"
@@ -34,49 +39,8 @@ const char* HELP =
     "      --output-debug <DIR>         Optional output debug folder (hla_debug.json, cyp2d6_alleles.json)\n"
     "      --debug-reads                Also write read_debug.json there: every realigned HLA read's accepted allele with CIGAR and MD (needs --output-debug)\n"
     "      --sample-name <STRING>       Sample name from the input VCFs (default: first sample)\n"
-    "\n"
-    "Variant parameters:\n"
-    "      --max-sv-length <BASEPAIRS>  The maximum length of an SV to consider, anything longer is ignored [default: 1000000]\n"
-    "\n"
-    "HLA calling:\n"
-    "      --disable-cdna-scoring       Disables scoring by cDNA (implies --hla-require-dna)\n"
-    "      --hla-require-dna            Requires HLA alleles to have a DNA sequence definition\n"
-    "      --max-error-rate <FLOAT>     The maximum error rate for a read to the HLA reference allele [default: 0.07]\n"
-    "      --min-cdf-prob <FLOAT>       The minimum cumulative distribution function probability for a heterozygous call [default: 0.001]\n"
-    "      --expected-maf <FLOAT>       Expected minor allele frequency; reduce to account for skew from sequencing bias [default: 0.45]\n"
-    "      --debug-skip-hla             Skips HLA diplotyping\n"
-    "\n"
-    "CYP2D6 calling:\n"
-    "      --infer-connections          Enables inferrence of connected alleles based on population observations\n"
-    "      --normalize-d6-only          Disables normalizing coverage with D7 and hybrid alleles\n"
-    "\n"
-    "Consensus (HLA and CYP2D6):\n"
-    "      --min-consensus-fraction <FLOAT>  The minimum fraction of sequences required to split into multiple consensuses (e.g. MAF) [default: 0.10]\n"
-    "      --min-consensus-count <COUNT>     The minimum counts of sequences required to split into multiple consensuses [default: 3]\n"
-    "      --dual-max-ed-delta <COUNT>       The edit distance delta threshold to stop tracking divergent sequences (efficiency heuristic) [default: 100]\n"
-    "\n"
-    "Execution:\n"
-    "      --sequential                 Run the variant genes, the HLA genes and CYP2D6 one after another (the calls are the same)\n"
-    "  -t, --threads <THREADS>          Accepted for compatibility; the reference deprecates it [default: 1]\n"
-    "  -v, --verbose...                 Enable verbose output (print the warnings and timings of the call)\n"
-    "  -h, --help                       Print help\n"
-    "\n"
-    "Not supported here: --hla-revert-method, --output-cyp2d6-bam, --debug-hla-target\n";
-
-bool exists(const std::string& p) { struct stat st; return ::stat(p.c_str(), &st) == 0; }
-
-int clap_error(const std::string& m) {
-    std::fprintf(stderr, "error: %s\n\nUsage: starphase_hip diplotype [OPTIONS] --database <JSON> --reference <FASTA> --output-calls <JSON>\n\nFor more information, try '--help'.\n", m.c_str());
-    return EX_CLAP;
-}
-
-bool parse_f64(const std::string& s, double* out) { char* end = nullptr; errno = 0; *out = std::strtod(s.c_str(), &end); return !s.empty() && end && *end == 0 && errno == 0; }
-bool parse_u64(const std::string& s, uint64_t* out) {
-    if (s.empty() || s[0] == '-' || s[0] == '+') return false;
-    char* end = nullptr; errno = 0; *out = std::strtoull(s.c_str(), &end, 10); return end && *end == 0 && errno == 0;
-}
-
-const char* BATCH_HELP =
+    "\n";
+const char* BATCH_HELP_HEAD =
     "Diplotype many samples, listed in a manifest, against one PGx database (many samples per device pass)\n"
     "\n"
     "Usage: starphase_hip diplotype-batch [OPTIONS] --database <JSON> --reference <FASTA> --manifest <TSV>\n"
@@ -88,7 +52,8 @@ const char* BATCH_HELP =
     "                                   pharmcat_tsv, output_debug ('-' or empty = none); lines starting with '#' are headers\n"
     "      --include-set <TXT>          Optional file indicating the list of genes to include in diplotyping, one per line\n"
     "      --exclude-set <TXT>          Optional file indicating the list of genes to exclude from diplotyping, one per line\n"
-    "\n"
+    "\n";
+const char* HELP_SHARED =
     "Variant parameters:\n"
     "      --max-sv-length <BASEPAIRS>  The maximum length of an SV to consider, anything longer is ignored [default: 1000000]\n"
     "\n"
@@ -108,7 +73,16 @@ const char* BATCH_HELP =
     "      --min-consensus-fraction <FLOAT>  The minimum fraction of sequences required to split into multiple consensuses (e.g. MAF) [default: 0.10]\n"
     "      --min-consensus-count <COUNT>     The minimum counts of sequences required to split into multiple consensuses [default: 3]\n"
     "      --dual-max-ed-delta <COUNT>       The edit distance delta threshold to stop tracking divergent sequences (efficiency heuristic) [default: 100]\n"
+    "\n";
+const char* HELP_TAIL =
+    "Execution:\n"
+    "      --sequential                 Run the variant genes, the HLA genes and CYP2D6 one after another (the calls are the same)\n"
+    "  -t, --threads <THREADS>          Accepted for compatibility; the reference deprecates it [default: 1]\n"
+    "  -v, --verbose...                 Enable verbose output (print the warnings and timings of the call)\n"
+    "  -h, --help                       Print help\n"
     "\n"
+    "Not supported here: --hla-revert-method, --output-cyp2d6-bam, --debug-hla-target\n";
+const char* BATCH_HELP_TAIL =
     "Execution:\n"
     "      --max-group <N>              Samples per device pass [default: 64]\n"
     "  -t, --threads <THREADS>          Host BAM / VCF decode workers [default: min(16, hardware threads)]\n"
@@ -120,18 +94,95 @@ const char* BATCH_HELP =
     "Every sample's files are what `starphase_hip diplotype` takes for one sample; the debug folder is a manifest column (--output-debug is refused).\n"
     "Exit status: 0 when every sample was written, 65 when a sample failed (the others are written; each failure is printed with its row).\n";
 
-int batch_clap_error(const std::string& m) {
-    std::fprintf(stderr, "error: %s\n\nUsage: starphase_hip diplotype-batch [OPTIONS] --database <JSON> --reference <FASTA> --manifest <TSV>\n\nFor more information, try '--help'.\n", m.c_str());
+bool exists(const std::string& p) { struct stat st; return ::stat(p.c_str(), &st) == 0; }
+
+int clap_error(const char* usage, const std::string& m) {
+    std::fprintf(stderr, "error: %s\n\nUsage: %s\n\nFor more information, try '--help'.\n", m.c_str(), usage);
     return EX_CLAP;
 }
 
-// one manifest row: the files of one sample
-struct Row { int line = 0; std::string output, vcf, sample, sv_vcf, pharmcat, debug; std::vector<std::string> bams; };
+int noinput(const std::string& where, const char* label, const std::string& p) {
+    std::fprintf(stderr, "error: %s%s does not exist: \"%s\"\n", where.c_str(), label, p.c_str());
+    return EX_NOINPUT_;
+}
 
-std::vector<std::string> split(const std::string& s, char sep) {
-    std::vector<std::string> out; size_t a = 0;
-    for (;;) { const size_t b = s.find(sep, a); out.push_back(s.substr(a, b == std::string::npos ? std::string::npos : b - a)); if (b == std::string::npos) break; a = b + 1; }
-    return out;
+bool parse_f64(const std::string& s, double* out) { char* end = nullptr; errno = 0; *out = std::strtod(s.c_str(), &end); return !s.empty() && end && *end == 0 && errno == 0; }
+bool parse_u64(const std::string& s, uint64_t* out) {
+    if (s.empty() || s[0] == '-' || s[0] == '+') return false;
+    char* end = nullptr; errno = 0; *out = std::strtoull(s.c_str(), &end, 10); return end && *end == 0 && errno == 0;
+}
+
+// the options both commands take
+struct Options {
+    sp_diplotype_settings s;
+    std::string database, reference, include, exclude;
+    int verbose = 0; bool debug_reads = false;
+};
+
+// the option being parsed: its name (a `--key=value` split) and where its value comes from.  need*: 0, or the exit status of the clap error
+struct Arg {
+    int argc; char** argv; int i; const char* usage;
+    std::string a, val; bool has_inline = false;
+    int need(std::string* out) {
+        if (has_inline) { *out = val; return 0; }
+        if (i + 1 >= argc) return clap_error(usage, "a value is required for '" + a + "' but none was supplied");
+        *out = argv[++i];
+        return 0;
+    }
+    int need_u64(uint64_t* v) {
+        std::string tmp;
+        if (int rc = need(&tmp)) return rc;
+        return parse_u64(tmp, v) ? 0 : clap_error(usage, "invalid value '" + tmp + "' for '" + a + "': invalid digit found in string");
+    }
+    int need_f64(double* v) {
+        std::string tmp;
+        if (int rc = need(&tmp)) return rc;
+        return parse_f64(tmp, v) ? 0 : clap_error(usage, "invalid value '" + tmp + "' for '" + a + "': invalid float literal");
+    }
+};
+
+// argv[2..] of either command.  own(arg): the options only that command has -- NOT_MINE, 0 when it took the option, else the exit status.
+// Returns PARSED, or the exit status (0 after --help).
+enum { PARSED = -1, NOT_MINE = -2 };
+int parse_options(int argc, char** argv, const char* usage, const std::string& help, Options& o, const std::function<int(Arg&)>& own) {
+    sp_diplotype_settings& s = o.s;
+    Arg arg{argc, argv, 2, usage};
+    for (int& i = arg.i; i < argc; ++i) {
+        std::string& a = arg.a;
+        a = argv[i]; arg.has_inline = false;
+        const size_t eq = a.find('=');
+        if (a.rfind("--", 0) == 0 && eq != std::string::npos) { arg.val = a.substr(eq + 1); a = a.substr(0, eq); arg.has_inline = true; }
+        int rc = 0;
+        uint64_t u = 0; double f = 0;
+        if (a == "-h" || a == "--help") { std::fputs(help.c_str(), stdout); return EX_OK_; }
+        else if (a == "-d" || a == "--database") rc = arg.need(&o.database);
+        else if (a == "-r" || a == "--reference") rc = arg.need(&o.reference);
+        else if (a == "--include-set") rc = arg.need(&o.include);
+        else if (a == "--exclude-set") rc = arg.need(&o.exclude);
+        else if (a == "--disable-cdna-scoring") s.disable_cdna_scoring = 1;
+        else if (a == "--hla-require-dna") s.hla_require_dna = 1;
+        else if (a == "--debug-skip-hla") s.debug_skip_hla = 1;
+        else if (a == "--infer-connections") s.infer_connections = 1;
+        else if (a == "--normalize-d6-only") s.normalize_d6_only = 1;
+        else if (a == "--sequential") s.sequential = 1;
+        else if (a == "--debug-reads") o.debug_reads = true;
+        else if (a == "-v" || a == "--verbose") ++o.verbose;
+        else if (a.size() > 2 && a[0] == '-' && a[1] == 'v' && a.find_first_not_of('v', 1) == std::string::npos) o.verbose += (int)a.size() - 1;
+        else if (a == "--max-sv-length") { if (!(rc = arg.need_u64(&u))) s.max_sv_length = u; }
+        else if (a == "--min-consensus-count") { if (!(rc = arg.need_u64(&u))) s.min_consensus_count = u; }
+        else if (a == "--dual-max-ed-delta") { if (!(rc = arg.need_u64(&u))) s.dual_max_ed_delta = u; }
+        else if (a == "--max-error-rate") { if (!(rc = arg.need_f64(&f))) s.max_error_rate = f; }
+        else if (a == "--min-cdf-prob") { if (!(rc = arg.need_f64(&f))) s.min_cdf_prob = f; }
+        else if (a == "--expected-maf") { if (!(rc = arg.need_f64(&f))) s.expected_maf = f; }
+        else if (a == "--min-consensus-fraction") { if (!(rc = arg.need_f64(&f))) s.min_consensus_fraction = f; }
+        else if ((rc = own(arg)) != NOT_MINE) {}
+        else if (a == "--hla-revert-method" || a == "--output-cyp2d6-bam" || a == "--debug-hla-target") {
+            std::fprintf(stderr, "error: %s is not supported by starphase_hip (the batch HLA method and the debug folder outputs listed in --help are)\n", a.c_str());
+            return EX_USAGE_;
+        } else return clap_error(usage, "unexpected argument '" + a + "' found");
+        if (rc) return rc;
+    }
+    return PARSED;
 }
 
 // create_dir_all; false with errno set when a component cannot be made
@@ -144,75 +195,69 @@ bool make_dirs(const std::string& dir) {
     return true;
 }
 
+// the handle of the parsed options (o.s complete), or NULL and the exit status: UNAVAILABLE without a device, IOERR for what it loads
+sp_starphase* create_handle(const Options& o, int* code) {
+    sp_starphase* h = nullptr;
+    const int32_t rc = sp_starphase_create(nullptr, o.database.c_str(), o.reference.c_str(), &o.s, &h);
+    if (rc != SP_OK) {
+        std::fprintf(stderr, "error: %s\n", sp_starphase_last_error(nullptr));
+        *code = rc == SP_ERR_NO_DEVICE || rc == SP_ERR_HIP ? EX_UNAVAILABLE_ : EX_IOERR_;
+        return nullptr;
+    }
+    if (o.debug_reads) sp_starphase_set_read_debug(h, 1);
+    return h;
+}
+
+// the calls JSON and, when named, the PharmCAT TSV of one result
+int save_result(sp_result* result, const std::string& where, const std::string& output, const std::string& pharmcat) {
+    if (sp_result_save(result, output.c_str()) != SP_OK) {
+        std::fprintf(stderr, "error: %sError while writing diplotypes to file: %s\n", where.c_str(), sp_result_last_error(result));
+        return EX_IOERR_;
+    }
+    if (!pharmcat.empty() && sp_result_save_pharmcat_tsv(result, pharmcat.c_str()) != SP_OK) {
+        std::fprintf(stderr, "error: %sError while writing PharmCAT diplotypes to file: %s\n", where.c_str(), sp_result_last_error(result));
+        return EX_IOERR_;
+    }
+    return EX_OK_;
+}
+
+// one manifest row: the files of one sample
+struct Row { int line = 0; std::string output, vcf, sample, sv_vcf, pharmcat, debug; std::vector<std::string> bams; };
+
+std::vector<std::string> split(const std::string& s, char sep) {
+    std::vector<std::string> out; size_t a = 0;
+    for (;;) { const size_t b = s.find(sep, a); out.push_back(s.substr(a, b == std::string::npos ? std::string::npos : b - a)); if (b == std::string::npos) break; a = b + 1; }
+    return out;
+}
+
 int batch_main(int argc, char** argv) {
-    sp_diplotype_settings s;
+    Options o;
+    sp_diplotype_settings& s = o.s;
     sp_diplotype_settings_default(&s);
-    std::string database, reference, manifest, include, exclude;
+    const std::string &database = o.database, &reference = o.reference, &include = o.include, &exclude = o.exclude;
+    std::string manifest;
     uint64_t max_group = 0, threads = 0;
-    int verbose = 0; bool debug_reads = false;
-    for (int i = 2; i < argc; ++i) {
-        std::string a = argv[i], val;
-        bool has_inline = false;
-        const size_t eq = a.find('=');
-        if (a.rfind("--", 0) == 0 && eq != std::string::npos) { val = a.substr(eq + 1); a = a.substr(0, eq); has_inline = true; }
-        auto need = [&](std::string* out) -> int {
-            if (has_inline) { *out = val; return 0; }
-            if (i + 1 >= argc) return batch_clap_error("a value is required for '" + a + "' but none was supplied");
-            *out = argv[++i];
-            return 0;
-        };
-        int rc = 0;
-        std::string tmp;
-        if (a == "-h" || a == "--help") { std::fputs(BATCH_HELP, stdout); return EX_OK_; }
-        else if (a == "-d" || a == "--database") rc = need(&database);
-        else if (a == "-r" || a == "--reference") rc = need(&reference);
-        else if (a == "-m" || a == "--manifest") rc = need(&manifest);
-        else if (a == "--include-set") rc = need(&include);
-        else if (a == "--exclude-set") rc = need(&exclude);
-        else if (a == "--disable-cdna-scoring") s.disable_cdna_scoring = 1;
-        else if (a == "--hla-require-dna") s.hla_require_dna = 1;
-        else if (a == "--debug-skip-hla") s.debug_skip_hla = 1;
-        else if (a == "--infer-connections") s.infer_connections = 1;
-        else if (a == "--normalize-d6-only") s.normalize_d6_only = 1;
-        else if (a == "--sequential") s.sequential = 1;
-        else if (a == "--debug-reads") debug_reads = true;
-        else if (a == "-v" || a == "--verbose") ++verbose;
-        else if (a.size() > 2 && a[0] == '-' && a[1] == 'v' && a.find_first_not_of('v', 1) == std::string::npos) verbose += (int)a.size() - 1;
-        else if (a == "--max-sv-length" || a == "--min-consensus-count" || a == "--dual-max-ed-delta" || a == "-t" || a == "--threads" || a == "--max-group") {
-            uint64_t v = 0;
-            if ((rc = need(&tmp))) return rc;
-            if (!parse_u64(tmp, &v)) return batch_clap_error("invalid value '" + tmp + "' for '" + a + "': invalid digit found in string");
-            if (a == "--max-sv-length") s.max_sv_length = v;
-            else if (a == "--min-consensus-count") s.min_consensus_count = v;
-            else if (a == "--dual-max-ed-delta") s.dual_max_ed_delta = v;
-            else if (a == "--max-group") max_group = v;
-            else threads = v;
-        } else if (a == "--max-error-rate" || a == "--min-cdf-prob" || a == "--expected-maf" || a == "--min-consensus-fraction") {
-            double v = 0;
-            if ((rc = need(&tmp))) return rc;
-            if (!parse_f64(tmp, &v)) return batch_clap_error("invalid value '" + tmp + "' for '" + a + "': invalid float literal");
-            if (a == "--max-error-rate") s.max_error_rate = v;
-            else if (a == "--min-cdf-prob") s.min_cdf_prob = v;
-            else if (a == "--expected-maf") s.expected_maf = v;
-            else s.min_consensus_fraction = v;
-        } else if (a == "--output-debug" || a == "-o" || a == "--output-calls" || a == "-c" || a == "--vcf" || a == "-b" || a == "--bam" || a == "-s" ||
-                   a == "--sv-vcf" || a == "--sample-name" || a == "--pharmcat-tsv") {
+    const int parsed = parse_options(argc, argv, BATCH_USAGE, std::string(BATCH_HELP_HEAD) + HELP_SHARED + BATCH_HELP_TAIL, o, [&](Arg& arg) -> int {
+        const std::string& a = arg.a;
+        if (a == "-m" || a == "--manifest") return arg.need(&manifest);
+        if (a == "-t" || a == "--threads" || a == "--max-group") {
+            if (int rc = arg.need_u64(a == "--max-group" ? &max_group : &threads)) return rc;
+            return max_group > 0xFFFFFFFFull || threads > 0xFFFFFFFFull ? clap_error(BATCH_USAGE, "value too large for '" + a + "'") : 0;
+        }
+        if (a == "--output-debug" || a == "-o" || a == "--output-calls" || a == "-c" || a == "--vcf" || a == "-b" || a == "--bam" || a == "-s" ||
+            a == "--sv-vcf" || a == "--sample-name" || a == "--pharmcat-tsv") {
             std::fprintf(stderr, "error: %s is a column of the manifest in diplotype-batch (one value per sample)\n", a.c_str());
             return EX_USAGE_;
-        } else if (a == "--hla-revert-method" || a == "--output-cyp2d6-bam" || a == "--debug-hla-target") {
-            std::fprintf(stderr, "error: %s is not supported by starphase_hip (the batch HLA method and the debug folder outputs listed in --help are)\n", a.c_str());
-            return EX_USAGE_;
-        } else return batch_clap_error("unexpected argument '" + a + "' found");
-        if (rc) return rc;
-        if (max_group > 0xFFFFFFFFull || threads > 0xFFFFFFFFull) return batch_clap_error("value too large for '" + a + "'");
-    }
+        }
+        return NOT_MINE;
+    });
+    if (parsed != PARSED) return parsed;
+    const int verbose = o.verbose; const bool debug_reads = o.debug_reads;
     std::string missing;
     if (database.empty()) missing += "\n  --database <JSON>";
     if (reference.empty()) missing += "\n  --reference <FASTA>";
     if (manifest.empty()) missing += "\n  --manifest <TSV>";
-    if (!missing.empty()) return batch_clap_error("the following required arguments were not provided:" + missing);
-    auto noinput = [](const std::string& where, const char* label, const std::string& p) {
-        std::fprintf(stderr, "error: %s%s does not exist: \"%s\"\n", where.c_str(), label, p.c_str()); return EX_NOINPUT_; };
+    if (!missing.empty()) return clap_error(BATCH_USAGE, "the following required arguments were not provided:" + missing);
     if (!exists(database)) return noinput("", "Database JSON", database);
     if (!exists(reference)) return noinput("", "Reference FASTA", reference);
     if (!exists(manifest)) return noinput("", "Manifest", manifest);
@@ -283,19 +328,15 @@ int batch_main(int argc, char** argv) {
     }
     s.include_set = include.empty() ? nullptr : include.c_str(); s.exclude_set = exclude.empty() ? nullptr : exclude.c_str();
     // the device work
-    sp_starphase* h = nullptr;
-    int32_t rc = sp_starphase_create(nullptr, database.c_str(), reference.c_str(), &s, &h);
-    if (rc != SP_OK) {
-        std::fprintf(stderr, "error: %s\n", sp_starphase_last_error(nullptr));
-        return rc == SP_ERR_NO_DEVICE || rc == SP_ERR_HIP ? EX_UNAVAILABLE_ : EX_IOERR_;
-    }
-    if (debug_reads) sp_starphase_set_read_debug(h, 1);
-    sp_batch_options o{};
-    o.max_group = (uint32_t)max_group; o.decode_threads = (uint32_t)threads;
+    int code = EX_OK_;
+    sp_starphase* h = create_handle(o, &code);
+    if (!h) return code;
+    sp_batch_options bo{};
+    bo.max_group = (uint32_t)max_group; bo.decode_threads = (uint32_t)threads;
     std::vector<sp_result*> out(rows.size(), nullptr);
     std::vector<int32_t> rcs(rows.size(), SP_OK);
-    sp_starphase_call_batch(h, (uint32_t)rows.size(), in.data(), any_debug ? debug.data() : nullptr, &o, out.data(), rcs.data());
-    int code = EX_OK_; bool failed = false;
+    sp_starphase_call_batch(h, (uint32_t)rows.size(), in.data(), any_debug ? debug.data() : nullptr, &bo, out.data(), rcs.data());
+    bool failed = false;
     for (size_t k = 0; k < rows.size(); ++k) {
         const char* warn = sp_starphase_sample_warnings(h, (uint32_t)k);
         if (warn && *warn && (verbose || rcs[k] != SP_OK)) std::fprintf(stderr, "manifest row %zu: %s", k + 1, warn);
@@ -304,13 +345,7 @@ int batch_main(int argc, char** argv) {
             failed = true;
             continue;
         }
-        if (sp_result_save(out[k], rows[k].output.c_str()) != SP_OK) {
-            std::fprintf(stderr, "error: manifest row %zu: Error while writing diplotypes to file: %s\n", k + 1, sp_result_last_error(out[k]));
-            code = EX_IOERR_;
-        } else if (!rows[k].pharmcat.empty() && sp_result_save_pharmcat_tsv(out[k], rows[k].pharmcat.c_str()) != SP_OK) {
-            std::fprintf(stderr, "error: manifest row %zu: Error while writing PharmCAT diplotypes to file: %s\n", k + 1, sp_result_last_error(out[k]));
-            code = EX_IOERR_;
-        }
+        if (save_result(out[k], "manifest row " + std::to_string(k + 1) + ": ", rows[k].output, rows[k].pharmcat) != EX_OK_) code = EX_IOERR_;
         sp_result_free(out[k]);
     }
     if (verbose) {
@@ -333,82 +368,38 @@ int main(int argc, char** argv) {
         return argc < 2 ? EX_CLAP : EX_OK_;
     }
     if (!std::strcmp(argv[1], "diplotype-batch")) return batch_main(argc, argv);
-    if (std::strcmp(argv[1], "diplotype") != 0) return clap_error(std::string("unrecognized subcommand '") + argv[1] + "'");
-    sp_diplotype_settings s;
+    if (std::strcmp(argv[1], "diplotype") != 0) return clap_error(USAGE, std::string("unrecognized subcommand '") + argv[1] + "'");
+    Options o;
+    sp_diplotype_settings& s = o.s;
     sp_diplotype_settings_default(&s);
-    std::string database, reference, vcf, sv_vcf, output, pharmcat, include, exclude, debug, sample;
+    const std::string &database = o.database, &reference = o.reference, &include = o.include, &exclude = o.exclude;
+    std::string vcf, sv_vcf, output, pharmcat, debug, sample;
     std::vector<std::string> bams;
-    int verbose = 0; bool debug_reads = false;
-    for (int i = 2; i < argc; ++i) {
-        std::string a = argv[i], val;
-        bool has_inline = false;
-        const size_t eq = a.find('=');
-        if (a.rfind("--", 0) == 0 && eq != std::string::npos) { val = a.substr(eq + 1); a = a.substr(0, eq); has_inline = true; }
-        auto value = [&](std::string* out) -> bool {
-            if (has_inline) { *out = val; return true; }
-            if (i + 1 >= argc) return false;
-            *out = argv[++i];
-            return true;
-        };
-        auto need = [&](std::string* out) -> int {
-            return value(out) ? 0 : clap_error("a value is required for '" + a + "' but none was supplied");
-        };
-        int rc = 0;
-        std::string tmp;
-        if (a == "-h" || a == "--help") { std::fputs(HELP, stdout); return EX_OK_; }
-        else if (a == "-d" || a == "--database") rc = need(&database);
-        else if (a == "-r" || a == "--reference") rc = need(&reference);
-        else if (a == "-c" || a == "--vcf") rc = need(&vcf);
-        else if (a == "-s" || a == "--sv-vcf") rc = need(&sv_vcf);
-        else if (a == "-b" || a == "--bam") { rc = need(&tmp); if (!rc) bams.push_back(tmp); }
-        else if (a == "-o" || a == "--output-calls") rc = need(&output);
-        else if (a == "--pharmcat-tsv") rc = need(&pharmcat);
-        else if (a == "--include-set") rc = need(&include);
-        else if (a == "--exclude-set") rc = need(&exclude);
-        else if (a == "--output-debug") rc = need(&debug);
-        else if (a == "--sample-name") rc = need(&sample);
-        else if (a == "--disable-cdna-scoring") s.disable_cdna_scoring = 1;
-        else if (a == "--hla-require-dna") s.hla_require_dna = 1;
-        else if (a == "--debug-skip-hla") s.debug_skip_hla = 1;
-        else if (a == "--infer-connections") s.infer_connections = 1;
-        else if (a == "--normalize-d6-only") s.normalize_d6_only = 1;
-        else if (a == "--sequential") s.sequential = 1;
-        else if (a == "--debug-reads") debug_reads = true;
-        else if (a == "-v" || a == "--verbose") ++verbose;
-        else if (a.size() > 2 && a[0] == '-' && a[1] == 'v' && a.find_first_not_of('v', 1) == std::string::npos) verbose += (int)a.size() - 1;
-        else if (a == "--max-sv-length" || a == "--min-consensus-count" || a == "--dual-max-ed-delta" || a == "-t" || a == "--threads") {
-            uint64_t v = 0;
-            if ((rc = need(&tmp))) return rc;
-            if (!parse_u64(tmp, &v)) return clap_error("invalid value '" + tmp + "' for '" + a + "': invalid digit found in string");
-            if (a == "--max-sv-length") s.max_sv_length = v;
-            else if (a == "--min-consensus-count") s.min_consensus_count = v;
-            else if (a == "--dual-max-ed-delta") s.dual_max_ed_delta = v;
-        } else if (a == "--max-error-rate" || a == "--min-cdf-prob" || a == "--expected-maf" || a == "--min-consensus-fraction") {
-            double v = 0;
-            if ((rc = need(&tmp))) return rc;
-            if (!parse_f64(tmp, &v)) return clap_error("invalid value '" + tmp + "' for '" + a + "': invalid float literal");
-            if (a == "--max-error-rate") s.max_error_rate = v;
-            else if (a == "--min-cdf-prob") s.min_cdf_prob = v;
-            else if (a == "--expected-maf") s.expected_maf = v;
-            else s.min_consensus_fraction = v;
-        } else if (a == "--hla-revert-method" || a == "--output-cyp2d6-bam" || a == "--debug-hla-target") {
-            std::fprintf(stderr, "error: %s is not supported by starphase_hip (the batch HLA method and the debug folder outputs listed in --help are)\n", a.c_str());
-            return EX_USAGE_;
-        } else return clap_error("unexpected argument '" + a + "' found");
-        if (rc) return rc;
-    }
+    const int parsed = parse_options(argc, argv, USAGE, std::string(HELP_HEAD) + HELP_SHARED + HELP_TAIL, o, [&](Arg& arg) -> int {
+        const std::string& a = arg.a;
+        std::string tmp; uint64_t ignored = 0;
+        if (a == "-c" || a == "--vcf") return arg.need(&vcf);
+        if (a == "-s" || a == "--sv-vcf") return arg.need(&sv_vcf);
+        if (a == "-b" || a == "--bam") { const int rc = arg.need(&tmp); if (!rc) bams.push_back(tmp); return rc; }
+        if (a == "-o" || a == "--output-calls") return arg.need(&output);
+        if (a == "--pharmcat-tsv") return arg.need(&pharmcat);
+        if (a == "--output-debug") return arg.need(&debug);
+        if (a == "--sample-name") return arg.need(&sample);
+        if (a == "-t" || a == "--threads") return arg.need_u64(&ignored);
+        return NOT_MINE;
+    });
+    if (parsed != PARSED) return parsed;
     std::string missing;
     if (database.empty()) missing += "\n  --database <JSON>";
     if (reference.empty()) missing += "\n  --reference <FASTA>";
     if (output.empty()) missing += "\n  --output-calls <JSON>";
-    if (!missing.empty()) return clap_error("the following required arguments were not provided:" + missing);
+    if (!missing.empty()) return clap_error(USAGE, "the following required arguments were not provided:" + missing);
     // check_diplotype_settings (src/cli/diplotype.rs:200-330): the files first (check_required_filename exits with NOINPUT), then the rules
-    auto noinput = [](const char* label, const std::string& p) { std::fprintf(stderr, "error: %s does not exist: \"%s\"\n", label, p.c_str()); return EX_NOINPUT_; };
-    if (!exists(database)) return noinput("Database JSON", database);
-    if (!exists(reference)) return noinput("Reference FASTA", reference);
-    if (!vcf.empty() && !exists(vcf)) return noinput("VCF file", vcf);
-    if (!sv_vcf.empty() && !exists(sv_vcf)) return noinput("SV VCF file", sv_vcf);
-    for (const auto& b : bams) if (!exists(b)) return noinput("Alignment file", b);
+    if (!exists(database)) return noinput("", "Database JSON", database);
+    if (!exists(reference)) return noinput("", "Reference FASTA", reference);
+    if (!vcf.empty() && !exists(vcf)) return noinput("", "VCF file", vcf);
+    if (!sv_vcf.empty() && !exists(sv_vcf)) return noinput("", "SV VCF file", sv_vcf);
+    for (const auto& b : bams) if (!exists(b)) return noinput("", "Alignment file", b);
     std::vector<const char*> bam_ptrs;
     for (const auto& b : bams) bam_ptrs.push_back(b.c_str());
     sp_sample_inputs in{};
@@ -416,32 +407,21 @@ int main(int argc, char** argv) {
     s.include_set = include.empty() ? nullptr : include.c_str(); s.exclude_set = exclude.empty() ? nullptr : exclude.c_str();
     s.sample_name = sample.empty() ? nullptr : sample.c_str(); s.sv_vcf = sv_vcf.empty() ? nullptr : sv_vcf.c_str();
     s.debug_folder = debug.empty() ? nullptr : debug.c_str();
-    if (debug_reads && debug.empty()) { std::fprintf(stderr, "error: --debug-reads needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
+    if (o.debug_reads && debug.empty()) { std::fprintf(stderr, "error: --debug-reads needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
     char err[512];
     if (sp_diplotype_settings_check(&s, &in, err, sizeof err) != SP_OK) {
         std::fprintf(stderr, "error: Error while processing CLI settings: %s\n", err);
         return EX_USAGE_;
     }
-    if (!include.empty() && !exists(include)) return noinput("Include set", include);
-    if (!exclude.empty() && !exists(exclude)) return noinput("Exclude set", exclude);
-    if (!debug.empty()) {
-        std::string acc;                                   // create_dir_all
-        for (size_t p = 0; p <= debug.size(); ++p) {
-            if (p == debug.size() || debug[p] == '/') { if (!acc.empty() && !exists(acc) && ::mkdir(acc.c_str(), 0755) != 0) {
-                std::fprintf(stderr, "error: Error while creating debug folder: %s\n", std::strerror(errno)); return EX_IOERR_; } }
-            if (p < debug.size()) acc += debug[p];
-        }
-    }
+    if (!include.empty() && !exists(include)) return noinput("", "Include set", include);
+    if (!exclude.empty() && !exists(exclude)) return noinput("", "Exclude set", exclude);
+    if (!debug.empty() && !make_dirs(debug)) { std::fprintf(stderr, "error: Error while creating debug folder: %s\n", std::strerror(errno)); return EX_IOERR_; }
     // the device work
-    sp_starphase* h = nullptr;
-    int32_t rc = sp_starphase_create(nullptr, database.c_str(), reference.c_str(), &s, &h);
-    if (rc != SP_OK) {
-        std::fprintf(stderr, "error: %s\n", sp_starphase_last_error(nullptr));
-        return rc == SP_ERR_NO_DEVICE || rc == SP_ERR_HIP ? EX_UNAVAILABLE_ : EX_IOERR_;
-    }
-    if (debug_reads) sp_starphase_set_read_debug(h, 1);
+    int code = EX_OK_;
+    sp_starphase* h = create_handle(o, &code);
+    if (!h) return code;
     sp_result* result = nullptr;
-    rc = sp_starphase_call(h, &in, &result);
+    const int32_t rc = sp_starphase_call(h, &in, &result);
     const char* warn = sp_starphase_warnings(h);
     if (warn && *warn) std::fprintf(stderr, "%s", warn);
     if (rc != SP_OK) {
@@ -449,20 +429,13 @@ int main(int argc, char** argv) {
         sp_starphase_free(h);
         return EX_DATAERR_;
     }
-    if (verbose) {
+    if (o.verbose) {
         sp_starphase_timing t{};
         sp_starphase_last_timing(h, &t);
         std::fprintf(stderr, "call %.1f ms (BAM decode %.1f, variant genes %.1f, HLA %.1f with %u reads, CYP2D6 %.1f with %u reads)\n", t.call_ms, t.bam_decode_ms,
                      t.variant_ms, t.hla_ms, t.n_hla_reads, t.cyp_ms, t.n_cyp_reads);
     }
-    int code = EX_OK_;
-    if (sp_result_save(result, output.c_str()) != SP_OK) {
-        std::fprintf(stderr, "error: Error while writing diplotypes to file: %s\n", sp_result_last_error(result));
-        code = EX_IOERR_;
-    } else if (!pharmcat.empty() && sp_result_save_pharmcat_tsv(result, pharmcat.c_str()) != SP_OK) {
-        std::fprintf(stderr, "error: Error while writing PharmCAT diplotypes to file: %s\n", sp_result_last_error(result));
-        code = EX_IOERR_;
-    }
+    code = save_result(result, "", output, pharmcat);
     sp_result_free(result);
     sp_starphase_free(h);
     return code;

@@ -125,6 +125,49 @@ def test_hla_failure_stays_with_its_sample(pkg, cohort, handle, tmp_path):
             assert (got[i].json(), got[i].pharmcat_tsv()) == want[i], (i, max_group)
 
 
+def test_exhaustive_k1_context_single_and_batch_agree(pkg, cohort, k1_exhaustive):
+    """a handle on a caller's context in exhaustive K1 mode (k1_best_n = 0): both entry points run, give the same bytes, and the reverse-strand
+    reads are ignored (no seeded stage names a mapping for them)"""
+    import json
+    h = pkg.database.Starphase(cohort[0].db, cohort[0].fasta, ctx=k1_exhaustive)
+    try:
+        inputs = [dict(bams=c.bams, vcf=c.vcf) for c in cohort[:2]]
+        want = [h.call(**kw) for kw in inputs]
+        got = h.call_batch(inputs)
+        for i, (g, w) in enumerate(zip(got, want)):
+            assert not isinstance(g, Exception), (i, g)
+            assert (g.json(), g.pharmcat_tsv()) == (w.json(), w.pharmcat_tsv()), i
+            details = json.loads(w.json())["gene_details"]
+            by_name = {m["read_qname"]: m for n in ("HLA-A", "HLA-B") for m in details[n]["mapping_details"]}
+            assert all(by_name[f"m84/rev{k}/ccs"]["is_ignored"] for k in range(3)), i
+    finally:
+        h.close()
+
+
+def test_batch_variant_problems_stay_with_their_sample(pkg, tmp_path):
+    """samples of one group with different records for the same gene, two of them structural variants given per sample: each entry is packaged from
+    its own sample's problem (ids, deletion labels), so it equals that sample's single call, whatever the order in the group"""
+    import json
+    from test_gpu_diplotype_files import GOLDEN, VCF_DIR, genome_fasta
+    from test_oracle_variant import SV_CASES
+    small = os.path.join(VCF_DIR, "DPYD-sv-test/empty_small.vcf.gz")
+    h = pkg.database.Starphase(os.path.join(GOLDEN, "variant_dbs", "DPYD-sv-test.json"), genome_fasta(tmp_path / "ref.fa"))
+    try:
+        inputs = [dict(vcf=small, sv_vcf=os.path.join(VCF_DIR, sv)) for sv, _d, _i in SV_CASES] + [dict(vcf=small)]
+        want = [h.call(**kw) for kw in inputs]
+        dips = [[(d["hap1"], d["hap2"]) for d in json.loads(w.json())["gene_details"]["DPYD"]["diplotypes"]] for w in want]
+        assert dips[:2] == [d for _s, d, _i in SV_CASES] and dips[0] != dips[1] != dips[2]
+        n_sv = [sum(v["variant_name"] == "structural_variant" for v in json.loads(w.json())["gene_details"]["DPYD"]["variant_details"]) for w in want]
+        assert n_sv == [2, 2, 0]
+        for order in ([0, 1, 2], [2, 1, 0], [1, 0, 2, 0, 1]):
+            got = h.call_batch([inputs[k] for k in order])
+            for g, k in zip(got, order):
+                assert not isinstance(g, Exception), (order, k, g)
+                assert (g.json(), g.pharmcat_tsv()) == (want[k].json(), want[k].pharmcat_tsv()), (order, k)
+    finally:
+        h.close()
+
+
 # ------------------------------------------------------------------ the pieces
 def hla_reads(sample):
     """the fixture's HLA reads plus reverse complements of some of them (K1 drops those on the reverse strand)"""
@@ -134,7 +177,7 @@ def hla_reads(sample):
 
 
 def audit_rev(db, gpu_ctx, seqs, rec):
-    """hla_lane's loop: the status-2 reads alone, one seeded audit each, realign_record's acceptance rule over the mappings"""
+    """the per-read statement of the reverse mappings: the status-2 reads alone, one seeded audit each, realign_record's acceptance rule over the mappings"""
     want = {}
     pos = [k for k in range(len(rec)) if rec["status"][k] == 2 and rec["best_allele"][k] < 0]
     if not pos:
