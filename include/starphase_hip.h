@@ -373,6 +373,45 @@ int32_t sp_hla_type_consensus_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n
                                     const char* const* consensus_fwd, const uint32_t* consensus_len,
                                     int32_t require_dna, int32_t disable_cdna, sp_hla_best* best /* n */);
 
+/* ------------------------------------------------------------------ K2 map: score_read's per-allele mappings
+ * score_read (src/hla/caller.rs:1332-1511) also returns the cDNA and DNA mapping of the consensus against EVERY allowed allele of its gene (ReadMappingStats, written to
+ * hla_debug.json, src/hla/debug.rs:64-183).  sp_hla_map_consensus(_batch) take the arguments of sp_hla_score_consensus(_batch), run the same K2 and then, for every
+ * (consensus, level, allowed allele) whose own cell found an alignment, the two-piece affine alignment at {5, 4, 6, 2, 26, 1, 1} on the 64 diagonals around that cell's
+ * diagonal ((b_start - a_start + b_end - a_end) / 2 of the cell): the pair, diagonal and band of the winner's mm2_stats.  For the same pair, diagonal, band and scores
+ * the sp_affine_aln and the ops are bit-identical to sp_affine_align_batch's (same encoding: a = allele = minimap2's query, b = consensus = its target).  Unlike that
+ * call the map keeps no direction byte per cell: the forward pass leaves a checkpoint of the wave's state every 128 rows and the walk back re-runs one block of rows at a
+ * time into LDS, so its scratch is bounded by the grid (pooled buffers of the context, no allocation on a warm context; sp_profile_get "pool:device" counts them).
+ * A cell that found nothing (ok = 0) has no mapping (None in the reference): score 0, n_cigar 0, stats_mm2 -1.
+ *   best_allele  the winner of sp_hla_score_consensus (the scan on the library's unit-cost alignments), unchanged
+ *   best_mm2     score_read's running best (processed_match.rs:53-184) decided on the a = 5 alignments instead: the same scan run a second time on event rows and level
+ *                records made from the ops.  A mapping with more than 255 edit bases (the event-row cap of the unit-cost scan) is no mapping to this scan: its level
+ *                is absent there, as the level of an allele beyond the cap is absent in the unit-cost scan.  Its mapping is still handed out.  -1: nothing maps.
+ *   stats_mm2    n_alleles * 6 in the order of `alleles`: cDNA (len, nm, unmapped), DNA (len, nm, unmapped) with len = the allele's length and unmapped = len - (a_end -
+ *                a_start), as in sp_hla_best.mm2_stats; -1, -1, -1 = no mapping.
+ * An alignment of more than 4,096 runs fails the call with SP_ERR_CAPACITY.  The handle owns everything its accessors point to, until sp_hla_map_free.  A call that
+ * fails hands out no handle (*out = NULL): the reason is the context's sp_last_error; sp_hla_map_last_error is for the accessors (an index out of range). */
+typedef struct sp_hla_map sp_hla_map;
+int32_t sp_hla_map_consensus(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene,
+                             const char* cons_dna, uint32_t cons_dna_len, const char* cons_cdna, uint32_t cons_cdna_len,
+                             int32_t require_dna, int32_t disable_cdna, sp_hla_map** out);
+int32_t sp_hla_map_consensus_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, const uint32_t* genes,
+                                   const char* const* cons_dna, const uint32_t* cons_dna_len, const char* const* cons_cdna, const uint32_t* cons_cdna_len,
+                                   int32_t require_dna, int32_t disable_cdna, sp_hla_map** out);
+/* the same from the hg38-forward consensus, as sp_hla_type_consensus takes it (placement, splice, gene strand): one item, or none when the consensus is empty or does
+ * not align to its gene's reference */
+int32_t sp_hla_map_type_consensus(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const char* consensus_fwd, uint32_t consensus_len,
+                                  int32_t require_dna, int32_t disable_cdna, sp_hla_map** out);
+void sp_hla_map_free(sp_hla_map* map);
+const char* sp_hla_map_last_error(const sp_hla_map* map);
+uint32_t sp_hla_map_n_items(const sp_hla_map* map);
+/* item `item` of the call: its gene, its allowed alleles in database order (n_alleles database indices), the two winners and stats_mm2; every output is optional */
+int32_t sp_hla_map_item(const sp_hla_map* map, uint32_t item, uint32_t* gene, uint32_t* n_alleles, const uint32_t** alleles,
+                        int32_t* best_allele, int32_t* best_mm2, const int32_t** stats_mm2);
+/* the gene-strand consensus of a level (0 = cDNA, 1 = DNA): the target of the item's mappings at that level (not NUL-terminated; empty: cDNA scoring disabled) */
+int32_t sp_hla_map_consensus_seq(const sp_hla_map* map, uint32_t item, int32_t level, const char** seq, uint32_t* len);
+/* the mapping of allowed allele k of the item at a level: the alignment, the diagonal it was banded around (b_pos - a_pos), n_cigar ops at *cigar (NULL when 0) */
+int32_t sp_hla_map_mapping(const sp_hla_map* map, uint32_t item, uint32_t k, int32_t level, sp_affine_aln* aln, int32_t* diag, uint32_t* n_cigar, const uint32_t** cigar);
+
 /* ------------------------------------------------------------------ K5: CYP2D6 chain-pair likelihood search
  * Replaces find_best_chain_pair (src/cyp2d6/chaining.rs:223-592) with containment_score (:683-731),
  * get_multinomial_score (:854-903), count_unexpected_alleles (:794-819), unexpected_count (:739-775),
@@ -1050,6 +1089,10 @@ int32_t sp_aln_strings(const sp_aln* aln, const uint32_t* events, const char* ta
  * of every 'X' column and ^bases of a deletion, match_len is the number of '=' columns.  SP_ERR_INVALID_ARG when the ops do not consume exactly the spans of aln. */
 int32_t sp_affine_cigar_strings(const sp_affine_aln* aln, const uint32_t* cigar, uint32_t n_cigar, const char* target, uint64_t target_len,
                                 char* cigar_str, uint32_t cigar_cap, char* md, uint32_t md_cap, uint64_t* match_len);
+/* the same with '=' and 'X' runs kept apart, as minimap2 writes a CIGAR under --eqx (score_read maps with flag 0x4000000, src/hla/caller.rs:1395: the cigar of
+ * hla_debug.json's per-allele mappings); same arguments, same MD and match_len, same errors */
+int32_t sp_affine_cigar_strings_eqx(const sp_affine_aln* aln, const uint32_t* cigar, uint32_t n_cigar, const char* target, uint64_t target_len,
+                                char* cigar_str, uint32_t cigar_cap, char* md, uint32_t md_cap, uint64_t* match_len);
 typedef struct sp_hla_debug sp_hla_debug;
 int32_t sp_hla_debug_create(sp_hla_debug** out);
 void    sp_hla_debug_free(sp_hla_debug* debug);
@@ -1131,7 +1174,10 @@ int32_t sp_profile_get(sp_ctx* ctx, const char* kernel, double* total_ms, uint64
 /* device-side counters since the last sp_profile_reset come back in *cells under the names "count:k1_cells_active" (cells of the
  * first K1 pass whose gene the read anchors in), "count:k1_cells_executed" (those that ran the DP; the others were settled by prefix
  * sharing), "count:k1_cells_resumed" (executed cells that started from their predecessor's snapshot), "count:k1_cells_bytes"
- * (algorithmic bytes of the executed cells), "count:cons_launches", "count:cons_columns" (K8). */
+ * (algorithmic bytes of the executed cells), "count:cons_launches", "count:cons_columns" (K8).
+ * "pool:device": the context's pooled device buffers (its helpers' included) -- *launches = device allocations they have made since the context was created (never
+ * reset; a call on a warm context adds none), *cells = bytes they hold.  Only the pooled buffers (sp_pool, the scratch) are counted: the buffers of a sequence set a
+ * caller uploads or a database builds are that object's own and are not. */
 /* roofline peaks measured on this device in this run: what = "valu_int" (v_add_u32 wave-instructions / s), "match16" (VALU
  * wave-instructions / s of the WFA cell's 16-base compare), "hbm_copy" (bytes / s, read + written, of a 2 x 1 GiB streaming copy) */
 int32_t sp_microbench(sp_ctx* ctx, const char* what, double* rate);
@@ -1210,6 +1256,18 @@ int32_t sp_starphase_call(sp_starphase* handle, const sp_sample_inputs* inputs, 
  * the cost of the K1 pass it explains.  With the switch off no kernel is launched and no memory is taken for it; every other output is the
  * same bytes either way. */
 int32_t sp_starphase_set_read_debug(sp_starphase* handle, int32_t enable);
+/* the per-allele mappings of hla_debug.json, off by default (on 0): with the switch on, a call with a debug folder fills read_mapping_stats[gene]["consensus1" |
+ * "consensus2"].mapping_stats of <folder>/hla_debug.json with one PairedMappingStats per allowed allele of the gene (score_read maps with all_hla_targets = true,
+ * src/hla/caller.rs:1398), keyed by the star allele joined with ':' (:1473-1476): cdna_mapping / dna_mapping are DetailedMappingStats::from_mapping
+ * (src/hla/debug.rs:161-182) of the K2 map (sp_hla_map_type_consensus above) -- query_* the allele, target_* the gene-strand consensus, cigar with '=' / 'X'
+ * (sp_affine_cigar_strings_eqx), md over the consensus bases; null where the level has no mapping, and cdna_mapping null with disable_cdna_scoring.  best_match_id /
+ * best_match_star stay the call's typed allele.  A star allele that occurs twice among the allowed alleles is the reference's "Entry ... is already occupied!" error;
+ * here the first entry stays and the later one is skipped with a line in sp_starphase_warnings / sp_starphase_sample_warnings.  The map runs once per group of a
+ * batch, over every consensus of the group's samples that have a debug folder.  With the switch off nothing of this runs and every output is the same bytes; with
+ * it on, every output but hla_debug.json is.  The switch can turn a call that succeeds into one that fails: the map is part of the HLA pass, so an error of
+ * sp_hla_map_type_consensus (out of memory; an allele whose alignment has more than 4,096 runs, SP_ERR_CAPACITY) fails the pass -- in a batch the group then goes
+ * through it once more sample by sample, as for every other failure of a shared pass, and only the samples whose own map fails are failed. */
+int32_t sp_starphase_set_hla_debug_mappings(sp_starphase* handle, int32_t on);
 const char* sp_starphase_warnings(const sp_starphase* handle);      /* the warnings of the last call, one per line */
 /* where the last call spent its time (wall ms): whole call, BAM decode (host, both loci), variant genes, HLA lane, CYP2D6 lane */
 typedef struct { double call_ms, bam_decode_ms, variant_ms, hla_ms, cyp_ms; uint32_t n_hla_reads, n_cyp_reads; } sp_starphase_timing;

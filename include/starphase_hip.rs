@@ -667,6 +667,7 @@ pub struct sp_starphase_batch_timing {
 #[repr(C)] pub struct sp_group { _private: [u8; 0] }
 #[repr(C)] pub struct sp_hla_db { _private: [u8; 0] }
 #[repr(C)] pub struct sp_hla_debug { _private: [u8; 0] }
+#[repr(C)] pub struct sp_hla_map { _private: [u8; 0] }
 #[repr(C)] pub struct sp_result { _private: [u8; 0] }
 #[repr(C)] pub struct sp_seqset { _private: [u8; 0] }
 #[repr(C)] pub struct sp_starphase { _private: [u8; 0] }
@@ -709,6 +710,15 @@ extern "C" {
     pub fn sp_hla_score_consensus_batch(ctx: *mut sp_ctx, db: *const sp_hla_db, n: u32, genes: *const u32, cons_dna: *const *const c_char, cons_dna_len: *const u32, cons_cdna: *const *const c_char, cons_cdna_len: *const u32, require_dna: i32, disable_cdna: i32, best: *mut sp_hla_best) -> i32;
     pub fn sp_hla_type_consensus(ctx: *mut sp_ctx, db: *const sp_hla_db, gene: u32, consensus_fwd: *const c_char, consensus_len: u32, require_dna: i32, disable_cdna: i32, best: *mut sp_hla_best, stats: *mut i32, cdna_out: *mut c_char, cdna_cap: u32, cdna_len: *mut u32) -> i32;
     pub fn sp_hla_type_consensus_batch(ctx: *mut sp_ctx, db: *const sp_hla_db, n: u32, genes: *const u32, consensus_fwd: *const *const c_char, consensus_len: *const u32, require_dna: i32, disable_cdna: i32, best: *mut sp_hla_best) -> i32;
+    pub fn sp_hla_map_consensus(ctx: *mut sp_ctx, db: *const sp_hla_db, gene: u32, cons_dna: *const c_char, cons_dna_len: u32, cons_cdna: *const c_char, cons_cdna_len: u32, require_dna: i32, disable_cdna: i32, out: *mut *mut sp_hla_map) -> i32;
+    pub fn sp_hla_map_consensus_batch(ctx: *mut sp_ctx, db: *const sp_hla_db, n: u32, genes: *const u32, cons_dna: *const *const c_char, cons_dna_len: *const u32, cons_cdna: *const *const c_char, cons_cdna_len: *const u32, require_dna: i32, disable_cdna: i32, out: *mut *mut sp_hla_map) -> i32;
+    pub fn sp_hla_map_type_consensus(ctx: *mut sp_ctx, db: *const sp_hla_db, gene: u32, consensus_fwd: *const c_char, consensus_len: u32, require_dna: i32, disable_cdna: i32, out: *mut *mut sp_hla_map) -> i32;
+    pub fn sp_hla_map_free(map: *mut sp_hla_map);
+    pub fn sp_hla_map_last_error(map: *const sp_hla_map) -> *const c_char;
+    pub fn sp_hla_map_n_items(map: *const sp_hla_map) -> u32;
+    pub fn sp_hla_map_item(map: *const sp_hla_map, item: u32, gene: *mut u32, n_alleles: *mut u32, alleles: *mut *const u32, best_allele: *mut i32, best_mm2: *mut i32, stats_mm2: *mut *const i32) -> i32;
+    pub fn sp_hla_map_consensus_seq(map: *const sp_hla_map, item: u32, level: i32, seq: *mut *const c_char, len: *mut u32) -> i32;
+    pub fn sp_hla_map_mapping(map: *const sp_hla_map, item: u32, k: u32, level: i32, aln: *mut sp_affine_aln, diag: *mut i32, n_cigar: *mut u32, cigar: *mut *const u32) -> i32;
     pub fn sp_cyp_best_chain_pair(ctx: *mut sp_ctx, problem: *const sp_chain_problem, result: *mut sp_chain_result) -> i32;
     pub fn sp_cyp_find_regions(ctx: *mut sp_ctx, templates: *const sp_seqset, template_type: *const i32, reads: *const sp_seqset, max_missing_frac: f64, hits: *mut sp_region_hit, hits_cap: u64, n_hits: *mut u64) -> i32;
     pub fn sp_cyp_weight_segments(ctx: *mut sp_ctx, consensus: *const sp_seqset, allowed: *const u8, segments: *const sp_seqset, ed: *mut u64, ov: *mut f64, kept: *mut u8) -> i32;
@@ -796,6 +806,7 @@ extern "C" {
     pub fn sp_result_save_pharmcat_tsv(result: *mut sp_result, path: *const c_char) -> i32;
     pub fn sp_aln_strings(aln: *const sp_aln, events: *const u32, target: *const c_char, target_len: u64, cigar: *mut c_char, cigar_cap: u32, md: *mut c_char, md_cap: u32, match_len: *mut u64) -> i32;
     pub fn sp_affine_cigar_strings(aln: *const sp_affine_aln, cigar: *const u32, n_cigar: u32, target: *const c_char, target_len: u64, cigar_str: *mut c_char, cigar_cap: u32, md: *mut c_char, md_cap: u32, match_len: *mut u64) -> i32;
+    pub fn sp_affine_cigar_strings_eqx(aln: *const sp_affine_aln, cigar: *const u32, n_cigar: u32, target: *const c_char, target_len: u64, cigar_str: *mut c_char, cigar_cap: u32, md: *mut c_char, md_cap: u32, match_len: *mut u64) -> i32;
     pub fn sp_hla_debug_create(out: *mut *mut sp_hla_debug) -> i32;
     pub fn sp_hla_debug_free(debug: *mut sp_hla_debug);
     pub fn sp_hla_debug_last_error(debug: *const sp_hla_debug) -> *const c_char;
@@ -838,6 +849,7 @@ extern "C" {
     pub fn sp_starphase_last_error(handle: *const sp_starphase) -> *const c_char;
     pub fn sp_starphase_call(handle: *mut sp_starphase, inputs: *const sp_sample_inputs, out: *mut *mut sp_result) -> i32;
     pub fn sp_starphase_set_read_debug(handle: *mut sp_starphase, enable: i32) -> i32;
+    pub fn sp_starphase_set_hla_debug_mappings(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_warnings(handle: *const sp_starphase) -> *const c_char;
     pub fn sp_starphase_last_timing(handle: *const sp_starphase, out: *mut sp_starphase_timing) -> i32;
     pub fn sp_starphase_call_batch(handle: *mut sp_starphase, n: u32, inputs: *const sp_sample_inputs, debug_folders: *const *const c_char, opts: *const sp_batch_options, out: *mut *mut sp_result, sample_rc: *mut i32) -> i32;

@@ -706,3 +706,258 @@ extern "C" int32_t sp_affine_align_batch(sp_ctx* ctx, const sp_seqset* A, const 
         if (n_cigar[i] == AF_TB_LOST) { n_cigar[i] = 0; return sp_fail(ctx, SP_ERR_HIP, "affine traceback: the walk of pair " + std::to_string(i) + " did not reach the cell its path started in"); }
     return SP_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// The K2 map (sp_hla_map_consensus): the same alignment as sp_affine_align_batch on 64 diagonals, for the thousands of (allele, consensus) pairs of a K2 call, WITHOUT
+// a direction byte per cell in global memory.  A persistent grid of single-wave workgroups strides over the pair list; what a wave keeps outside its registers and
+// LDS belongs to its SLOT in the grid, not to a pair, so the scratch of a call is (slots x a bound per slot) whatever the number of pairs or cells:
+//   forward  the rows of affine_tb_kernel's forward pass (DPL = 1) on scores alone -- every decision of that pass compares scores, the counters and start cells only ride
+//            along -- for the best cell; before every AF_MAP_ROWS-th row the wave leaves its H / E1 / E2 scores in its slot's checkpoint list: 768 bytes a checkpoint
+//   walk     from the best cell block by block backwards: the wave runs the block's rows again from its checkpoint -- scores only, the same comparisons, so the same
+//            decisions -- writing the direction bytes of affine_tb_kernel's format into an LDS tile of AF_MAP_ROWS x 64 bytes (8 KB, beside the packed sequences), and
+//            lane 0 follows them as affine_tb_kernel's walk does.  Rows behind the cell the walk is in are not run again.
+//   ops      written backwards into the slot's ring of AF_MAP_RING words, then copied in forward order to a place the wave takes from a bump cursor in ONE compact op
+//            buffer for the whole launch (op_off[p]; AF_MAP_NO_OPS: the buffer or the ring was too small -- n_cigar[p] is the true count either way and the cursor the
+//            space the launch asked for in all, so the host grows the pooled buffer and launches again).
+// Why the result is affine_tb_kernel's: every decision of the DP -- which predecessor a state takes, whether a gap continues, which cell is best -- compares scores, and both
+// runs here make those comparisons on the same scores in the same order; the counters and start cells affine_tb_kernel carries along take no part in them.  So the best
+// cell, the direction bytes and hence the walk and its ops are the same; NM is the number of the path's columns that are not '=' and the start cell is the cell the walk
+// ends in, which is what the carried counters add up to along that same path.
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int AF_MAP_ROWS = 128;
+constexpr uint32_t AF_MAP_RING = 4096;
+constexpr uint64_t AF_MAP_NO_OPS = ~0ull;
+
+// af_scan on the key alone
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t af_map_dpp(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false); }
+__device__ __forceinline__ uint32_t af_map_max(uint32_t a, uint32_t b) { return b > a ? b : a; }
+__device__ __forceinline__ uint32_t af_map_scan(uint32_t v) {
+    v = af_map_max(v, af_map_dpp<0x111, 0xf>(v));
+    v = af_map_max(v, af_map_dpp<0x112, 0xf>(v));
+    v = af_map_max(v, af_map_dpp<0x114, 0xf>(v));
+    v = af_map_max(v, af_map_dpp<0x118, 0xf>(v));
+    v = af_map_max(v, af_map_dpp<0x142, 0xa>(v));
+    v = af_map_max(v, af_map_dpp<0x143, 0xc>(v));
+    return v;
+}
+
+template <bool HASN>
+__global__ __launch_bounds__(64) void affine_map_kernel(SeqSetView A, SeqSetView B, const AfPair* __restrict__ pairs, uint32_t n_pairs, sp_affine_opts o, sp_affine_aln* __restrict__ out,
+                                                         int t_words_max, int32_t* __restrict__ ckpt_all, uint32_t ckpt_per_slot, uint32_t* __restrict__ ring_all,
+                                                         uint32_t* __restrict__ ops_out, uint64_t ops_cap, unsigned long long* __restrict__ cursor, uint64_t* __restrict__ op_off,
+                                                         uint32_t* __restrict__ n_cigar) {
+    extern __shared__ uint32_t lds[];
+    constexpr int BAND = 64;
+    constexpr bool hasn = HASN;
+    const int lane = threadIdx.x;
+    int32_t* ckpt = ckpt_all + (size_t)blockIdx.x * ckpt_per_slot * (3 * BAND);
+    uint32_t* ring = ring_all + (size_t)blockIdx.x * AF_MAP_RING;
+    uint32_t* LT = lds; uint32_t* LQ = LT + t_words_max; uint32_t* NT = LQ + t_words_max + 2 * BAND / 16 + 8; uint32_t* NQ = NT + t_words_max;
+    uint8_t* tile = (uint8_t*)(NQ + t_words_max + 2 * BAND / 16 + 8);
+    const int q1 = o.q, e1 = o.e, q2 = o.q2, e2 = o.e2;
+    for (uint32_t p = blockIdx.x; p < n_pairs; p += gridDim.x) {
+        const AfPair pr = pairs[p];
+        const int tlen = pr.pad < 0 ? 0 : B.len[pr.b], qlen = pr.pad < 0 ? 0 : A.len[pr.a];
+        sp_affine_aln res; res.score = 0; res.nm = 0; res.a_start = res.a_end = res.b_start = res.b_end = 0;
+        const int klo = -pr.diag - BAND / 2;
+        int i_lo = -(klo + BAND - 1); if (i_lo < 0) i_lo = 0;
+        int i_hi = qlen - 1 - klo; if (i_hi > tlen - 1) i_hi = tlen - 1;
+        if (pr.pad < 0 || tlen <= 0 || qlen <= 0 || i_lo > i_hi) { if (lane == 0) { out[p] = res; n_cigar[p] = 0; op_off[p] = AF_MAP_NO_OPS; } continue; }
+        const int tw0 = i_lo >> 4, tw1 = (i_hi >> 4) + 1;
+        int q_lo = i_lo + klo; if (q_lo < 0) q_lo = 0;
+        int q_hi = i_hi + klo + BAND - 1; if (q_hi > qlen - 1) q_hi = qlen - 1;
+        const int qw0 = q_lo >> 4, qw1 = (q_hi >> 4) + 1;
+        spw::wave_lds_sync();                               // (the pair before this one has been read)
+        {
+            const uint32_t* tw = B.words + B.word_off[pr.b]; const uint32_t* qw = A.words + A.word_off[pr.a];
+            const uint32_t* tn = B.nplane ? B.nplane + B.word_off[pr.b] : nullptr; const uint32_t* qn = A.nplane ? A.nplane + A.word_off[pr.a] : nullptr;
+            for (int w = lane; w < tw1 - tw0; w += SP_WAVE) { LT[w] = tw[tw0 + w]; if (hasn) NT[w] = tn ? tn[tw0 + w] : 0u; }
+            for (int w = lane; w < qw1 - qw0; w += SP_WAVE) { LQ[w] = qw[qw0 + w]; if (hasn) NQ[w] = qn ? qn[qw0 + w] : 0u; }
+        }
+        spw::wave_lds_sync();
+        auto base_of = [&](const uint32_t* W, const uint32_t* N, int pos, int w0) {
+            const int w = (pos >> 4) - w0; const uint32_t sh = (uint32_t)(pos & 15) << 1;
+            if (hasn && ((N[w] >> sh) & 1u)) return 4;
+            return (int)((W[w] >> sh) & 3u);
+        };
+        const int idx = lane;
+        // ---- forward: affine_tb_kernel's rows on scores alone (its comparisons, so its decisions): the best cell and the checkpoints
+        int hs = AF_NEG, e1s = AF_NEG, e2s = AF_NEG;
+        int bs = 0, bi = -1, bj = -1;
+        for (int i = i_lo; i <= i_hi; ++i) {
+            if (((i - i_lo) & (AF_MAP_ROWS - 1)) == 0) {
+                int32_t* c = ckpt + (size_t)((i - i_lo) / AF_MAP_ROWS) * (3 * BAND);
+                c[lane] = hs; c[BAND + lane] = e1s; c[2 * BAND + lane] = e2s;
+            }
+            const int ct = base_of(LT, NT, i, tw0);
+            const int hus = spw::from_upper(hs, AF_NEG), eus = spw::from_upper(e1s, AF_NEG), eu2s = spw::from_upper(e2s, AF_NEG);
+            const int j = i + klo + idx;
+            const bool valid = (unsigned)j < (unsigned)qlen;
+            int a1s, a2s;
+            { const int eo = hus - q1; a1s = (eus > eo ? eus : eo) - e1; }
+            { const int eo = hus - q2; a2s = (eu2s > eo ? eu2s : eo) - e2; }
+            if (a1s < AF_NEG) a1s = AF_NEG;
+            if (a2s < AF_NEG) a2s = AF_NEG;
+            int h = hs;
+            const int cq = valid ? base_of(LQ, NQ, j, qw0) : 4;
+            const bool ambi = ct > 3 || cq > 3;
+            const int sub = ambi ? -o.sc_ambi : (ct == cq ? o.a : -o.b);
+            if (h <= 0) h = 0;
+            h += sub;
+            if (a1s > h) h = a1s;
+            if (!valid) { h = AF_NEG; a1s = AF_NEG; a2s = AF_NEG; }
+            int srcs = h; if (a2s > srcs) srcs = a2s;
+            const bool offer = valid && srcs > 0;
+            // the scan's keys order by (score + position * e, position): the maximum alone is needed, the counters of AfKey do not ride along
+            uint32_t k1 = offer ? (((uint32_t)(srcs + idx * e1) + AF_BIAS) << 8 | (uint32_t)idx) : 0u;
+            uint32_t k2 = offer ? (((uint32_t)(srcs + idx * e2) + AF_BIAS) << 8 | (uint32_t)idx) : 0u;
+            k1 = af_map_scan(k1); k2 = af_map_scan(k2);
+            const uint32_t in1 = (uint32_t)spw::from_lower((int)k1, 0), in2 = (uint32_t)spw::from_lower((int)k2, 0);
+            int f1s = AF_NEG, f2s = AF_NEG;
+            if (in1) f1s = (int)((in1 >> 8) - AF_BIAS) - q1 - idx * e1;
+            if (in2) f2s = (int)((in2 >> 8) - AF_BIAS) - q2 - idx * e2;
+            if (valid) {
+                if (f1s > h) h = f1s;
+                if (a2s > h) h = a2s;
+                if (f2s > h) h = f2s;
+                if (h <= 0) h = 0;
+                const bool better = h > bs || (h == bs && h > 0 && (i + j < bi + bj || (i + j == bi + bj && i < bi)));
+                bs = better ? h : bs; bi = better ? i : bi; bj = better ? j : bj;
+            }
+            hs = h; e1s = a1s; e2s = a2s;
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const int os = __shfl_xor(bs, d), oi = __shfl_xor(bi, d), oj = __shfl_xor(bj, d);
+            if (os > bs || (os == bs && os > 0 && (oi + oj < bi + bj || (oi + oj == bi + bj && oi < bi)))) { bs = os; bi = oi; bj = oj; }
+        }
+        if (bs <= 0) { if (lane == 0) { out[p] = res; n_cigar[p] = 0; op_off[p] = AF_MAP_NO_OPS; } continue; }
+        // ---- the walk back, block by block
+        int ci = bi, cidx = bj - bi - klo, st = 0, done = 0;
+        uint32_t n_ops = 0, run_op = 0xF, run_len = 0, nm = 0; int si = 0, sj = 0;      // (nm and the start cell are the path's own: the columns that are not '=', the cell the walk ends in)
+        auto emit = [&](uint32_t op) {
+            nm += (op == 8u || op == 1u || op == 2u) ? 1u : 0u;
+            if (op == run_op) { ++run_len; return; }
+            if (run_len) { ring[n_ops % AF_MAP_RING] = run_len << 4 | run_op; ++n_ops; }
+            run_op = op; run_len = 1;
+        };
+        while (!done) {
+            const int blk = (ci - i_lo) / AF_MAP_ROWS, r0 = blk * AF_MAP_ROWS, r1 = ci - i_lo;
+            spw::wave_lds_sync();                           // (the tile before this one has been read)
+            {
+                // the block's rows again from its checkpoint: scores alone, affine_tb_kernel's comparisons and records
+                const int32_t* c = ckpt + (size_t)blk * (3 * BAND);
+                int hs = c[lane], e1s = c[BAND + lane], e2s = c[2 * BAND + lane];
+                for (int r = r0; r <= r1; ++r) {
+                    const int i = i_lo + r;
+                    const int ct = base_of(LT, NT, i, tw0);
+                    const int hus = spw::from_upper(hs, AF_NEG), eus = spw::from_upper(e1s, AF_NEG), eu2s = spw::from_upper(e2s, AF_NEG);
+                    const int j = i + klo + idx;
+                    const bool valid = (unsigned)j < (unsigned)qlen;
+                    int a1s, a2s; uint32_t d = AF_D_DIAG;
+                    { const int eo = hus - q1; if (eus > eo) { a1s = eus - e1; d |= AF_D_E1C; } else a1s = eo - e1; }
+                    { const int eo = hus - q2; if (eu2s > eo) { a2s = eu2s - e2; d |= AF_D_E2C; } else a2s = eo - e2; }
+                    if (a1s < AF_NEG) a1s = AF_NEG;
+                    if (a2s < AF_NEG) a2s = AF_NEG;
+                    int h = hs;
+                    const int cq = valid ? base_of(LQ, NQ, j, qw0) : 4;
+                    const bool ambi = ct > 3 || cq > 3;
+                    const int sub = ambi ? -o.sc_ambi : (ct == cq ? o.a : -o.b);
+                    if (h <= 0) { h = 0; d |= AF_D_START; }
+                    h += sub;
+                    if (ambi || ct != cq) d |= AF_D_X;
+                    if (a1s > h) { h = a1s; d = (d & ~7u) | AF_D_E1; }
+                    if (!valid) { h = AF_NEG; a1s = AF_NEG; a2s = AF_NEG; }
+                    int srcs = h; if (a2s > srcs) srcs = a2s;
+                    const bool offer = valid && srcs > 0;
+                    uint32_t k1 = offer ? (((uint32_t)(srcs + idx * e1) + AF_BIAS) << 8 | (uint32_t)idx) : 0u;
+                    uint32_t k2 = offer ? (((uint32_t)(srcs + idx * e2) + AF_BIAS) << 8 | (uint32_t)idx) : 0u;
+                    k1 = af_map_scan(k1); k2 = af_map_scan(k2);
+                    const uint32_t in1 = (uint32_t)spw::from_lower((int)k1, 0), in2 = (uint32_t)spw::from_lower((int)k2, 0);
+                    int f1s = AF_NEG, f2s = AF_NEG;
+                    if (in1) { const int src_idx = (int)(in1 & 0xFFu), v = (int)((in1 >> 8) - AF_BIAS); f1s = v - q1 - idx * e1; if (src_idx < idx - 1) d |= AF_D_F1C; }
+                    if (in2) { const int src_idx = (int)(in2 & 0xFFu), v = (int)((in2 >> 8) - AF_BIAS); f2s = v - q2 - idx * e2; if (src_idx < idx - 1) d |= AF_D_F2C; }
+                    if (valid) {
+                        if (f1s > h) { h = f1s; d = (d & ~7u) | AF_D_F1; }
+                        if (a2s > h) { h = a2s; d = (d & ~7u) | AF_D_E2; }
+                        if (f2s > h) { h = f2s; d = (d & ~7u) | AF_D_F2; }
+                        if (h <= 0) { h = 0; d = (d & ~7u) | AF_D_NONE; }
+                    } else d = AF_D_NONE;
+                    hs = h; e1s = a1s; e2s = a2s;
+                    tile[(r - r0) * BAND + lane] = (uint8_t)d;
+                }
+            }
+            spw::wave_lds_sync();
+            if (lane == 0) {
+                while (true) {
+                    const int r = ci - i_lo - r0;
+                    if (r < 0) break;                       // the block before this one
+                    if ((unsigned)cidx >= (unsigned)BAND) { done = 2; break; }
+                    const uint32_t d = tile[r * BAND + cidx];
+                    if (st == 0) {
+                        const uint32_t h = d & 7u;
+                        if (h == AF_D_DIAG || h == AF_D_START) { emit((d & AF_D_X) ? 8u : 7u); if (h == AF_D_START) { si = ci; sj = ci + klo + cidx; } --ci; if (h == AF_D_START) { done = 1; break; } continue; }
+                        if (h >= AF_D_NONE) { done = 2; break; }
+                        st = (int)h;
+                    }
+                    if (st == (int)AF_D_E1 || st == (int)AF_D_E2) {
+                        emit(2u); const bool cont = d & (st == (int)AF_D_E1 ? AF_D_E1C : AF_D_E2C); --ci; ++cidx; if (!cont) st = 0;
+                    } else {
+                        emit(1u); const bool cont = d & (st == (int)AF_D_F1 ? AF_D_F1C : AF_D_F2C); --cidx; if (!cont) st = 0;
+                    }
+                }
+            }
+            ci = __shfl(ci, 0); done = __shfl(done, 0);
+            if (ci < i_lo && !done) done = 2;
+        }
+        if (lane == 0) {
+            emit(0xE);                                      // closes the last run
+            res.score = bs; res.nm = (int32_t)nm; res.b_start = si; res.b_end = bi + 1; res.a_start = sj; res.a_end = bj + 1;
+            out[p] = res;
+            if (done != 1) { n_cigar[p] = AF_TB_LOST; op_off[p] = AF_MAP_NO_OPS; }
+            else {
+                n_cigar[p] = n_ops;
+                uint64_t at = AF_MAP_NO_OPS;
+                if (n_ops <= AF_MAP_RING) {
+                    at = atomicAdd(cursor, (unsigned long long)n_ops);
+                    if (at + n_ops <= ops_cap) for (uint32_t k = 0; k < n_ops; ++k) ops_out[at + k] = ring[n_ops - 1 - k];
+                    else at = AF_MAP_NO_OPS;
+                }
+                op_off[p] = at;
+            }
+        }
+    }
+}
+
+} // namespace
+
+// the K2 map over a device pair list (AfPair rows; pad < 0: no mapping): results, op counts and op offsets per pair, the ops in d_ops (ops_cap words) from *d_cursor on.
+// Everything it needs beside them is pooled under `prefix` and sized by the grid, not by the pairs.
+int sp_launch_affine_map(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const void* d_pairs, uint64_t n_pairs, const sp_affine_opts& o, sp_affine_aln* d_out,
+                         uint32_t* d_n_cigar, uint64_t* d_op_off, uint32_t* d_ops, uint64_t ops_cap, unsigned long long* d_cursor, const char* prof_name) {
+    if (n_pairs == 0) return SP_OK;
+    if (n_pairs > 0xFFFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "affine map: too many pairs");
+    if (B->max_len > 65535 || A->max_len > 65535) return sp_fail(ctx, SP_ERR_TOO_LONG, "affine: sequences of up to 65,535 bases");
+    const int band = 64;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(n_pairs, (uint64_t)ctx->num_cus * 8);
+    const uint32_t ckpt_per_slot = (uint32_t)(B->max_len / AF_MAP_ROWS + 2);
+    int32_t* d_ckpt = (int32_t*)sp_pool(ctx, "af_map_ckpt", (size_t)ctx->num_cus * 8 * ckpt_per_slot * 3 * band * 4);
+    uint32_t* d_ring = (uint32_t*)sp_pool(ctx, "af_map_ring", (size_t)ctx->num_cus * 8 * AF_MAP_RING * 4);
+    if (!d_ckpt || !d_ring) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "affine map buffers");
+    const int t_words_max = (B->max_len >> 4) + 4;
+    const size_t lds_bytes = sizeof(uint32_t) * (size_t)(4 * t_words_max + 2 * (2 * band / 16 + 8)) + (size_t)AF_MAP_ROWS * band;
+    if (lds_bytes > 160 * 1024) return sp_fail(ctx, SP_ERR_TOO_LONG, "affine map: sequences do not fit the LDS");
+    const bool hasn = A->has_n || B->has_n;
+    ProfScope ps(ctx, prof_name, n_pairs);
+#define SP_AF_MAP_LAUNCH(N) do { \
+        (void)hipFuncSetAttribute((const void*)affine_map_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
+        hipLaunchKernelGGL((affine_map_kernel<N>), dim3(grid), dim3(64), lds_bytes, ctx->stream, A->view(), B->view(), (const AfPair*)d_pairs, (uint32_t)n_pairs, o, d_out, t_words_max, \
+                           d_ckpt, ckpt_per_slot, d_ring, d_ops, ops_cap, d_cursor, d_op_off, d_n_cigar); } while (0)
+    if (hasn) SP_AF_MAP_LAUNCH(true); else SP_AF_MAP_LAUNCH(false);
+#undef SP_AF_MAP_LAUNCH
+    if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "affine map launch failed");
+    return SP_OK;
+}

@@ -238,6 +238,16 @@ int32_t sp_profile_get(sp_ctx* ctx, const char* kernel, double* total_ms, uint64
         if (cells) *cells = v;
         return SP_OK;
     }
+    // "pool:device": the context's pooled device memory -- launches = device allocations made so far (a warm call adds none), cells = bytes held
+    if (std::strcmp(kernel, "pool:device") == 0) {
+        uint64_t allocs = ctx->pool_allocs, bytes = ctx->scratch_bytes;
+        for (const auto& b : ctx->pool) bytes += b.second.second;
+        for (sp_ctx* h : ctx->helper) if (h) { allocs += h->pool_allocs; bytes += h->scratch_bytes; for (const auto& b : h->pool) bytes += b.second.second; }
+        if (total_ms) *total_ms = 0.0;
+        if (launches) *launches = allocs;
+        if (cells) *cells = bytes;
+        return SP_OK;
+    }
     auto it = ctx->prof.find(kernel);
     ProfileEntry e; if (it != ctx->prof.end()) e = it->second;
     if (total_ms) *total_ms = e.ms;

@@ -31,6 +31,51 @@ Value detailed(const sp_detailed_mapping* m) {
     return v;
 }
 
+// the same three for a mapping of sp_affine_align_batch / sp_hla_realign_cigars (ops in BAM encoding, len << 4 | op: 7 '=', 8 'X', 1 'I', 2 'D'; a = query, b = target):
+// '=' and 'X' runs merge into M (eqx: they stay '=' and 'X', as minimap2 writes them under flag 0x4000000), MD prints the target base of an 'X' column and ^bases of a deletion, match_len counts the '=' columns.  The ops must consume exactly
+// the spans of aln on both sequences.
+int32_t affine_strings(const sp_affine_aln* aln, const uint32_t* cigar, uint32_t n_cigar, const char* target, uint64_t target_len,
+                       char* cigar_str, uint32_t cigar_cap, char* md, uint32_t md_cap, uint64_t* match_len, bool eqx) {
+    if (!aln || (!cigar && n_cigar) || !target) return SP_ERR_INVALID_ARG;
+    if (aln->b_start < 0 || aln->b_end < aln->b_start || (uint64_t)aln->b_end > target_len || aln->a_start < 0 || aln->a_end < aln->a_start) return SP_ERR_INVALID_ARG;
+    std::string cg, tag;
+    char last_op = 0; int64_t run = 0, same = 0, matches = 0; bool in_del = false;
+    auto push = [&](char op, int64_t n) {
+        if (op == last_op) { run += n; return; }
+        if (run > 0) { cg += std::to_string(run); cg += last_op; }
+        last_op = op; run = n;
+    };
+    int64_t j = aln->b_start, i = aln->a_start;
+    for (uint32_t k = 0; k < n_cigar; ++k) {
+        const uint32_t op = cigar[k] & 0xFu; const int64_t n = (int64_t)(cigar[k] >> 4);
+        if (n == 0) return SP_ERR_INVALID_ARG;
+        if (op == 7u) {
+            if (j + n > aln->b_end) return SP_ERR_INVALID_ARG;
+            push(eqx ? '=' : 'M', n); same += n; matches += n; in_del = false; j += n; i += n;
+        } else if (op == 8u) {
+            if (j + n > aln->b_end) return SP_ERR_INVALID_ARG;
+            push(eqx ? 'X' : 'M', n);
+            for (int64_t x = 0; x < n; ++x) { tag += std::to_string(same); tag += target[j + x]; same = 0; }
+            in_del = false; j += n; i += n;
+        } else if (op == 2u) {
+            if (j + n > aln->b_end) return SP_ERR_INVALID_ARG;
+            push('D', n);
+            if (!in_del) { tag += std::to_string(same); tag += '^'; same = 0; in_del = true; }
+            tag.append(target + j, (size_t)n); j += n;
+        } else if (op == 1u) {
+            push('I', n); i += n;                                     // (query-only bases do not appear in MD; a deletion run on either side of them stays one run)
+        } else return SP_ERR_INVALID_ARG;
+    }
+    if (j != aln->b_end || i != aln->a_end) return SP_ERR_INVALID_ARG;
+    if (run > 0) { cg += std::to_string(run); cg += last_op; }
+    tag += std::to_string(same);
+    if (match_len) *match_len = (uint64_t)matches;
+    int32_t rc = SP_OK;
+    if (cigar_str && cigar_cap) { const size_t n = std::min<size_t>(cg.size(), cigar_cap - 1); std::memcpy(cigar_str, cg.data(), n); cigar_str[n] = 0; if (n < cg.size()) rc = SP_ERR_CAPACITY; }
+    if (md && md_cap) { const size_t n = std::min<size_t>(tag.size(), md_cap - 1); std::memcpy(md, tag.data(), n); md[n] = 0; if (n < tag.size()) rc = SP_ERR_CAPACITY; }
+    return rc;
+}
+
 } // namespace
 
 extern "C" {
@@ -74,49 +119,15 @@ int32_t sp_aln_strings(const sp_aln* aln, const uint32_t* events, const char* ta
     return rc;
 }
 
-// the same three for a mapping of sp_affine_align_batch / sp_hla_realign_cigars (ops in BAM encoding, len << 4 | op: 7 '=', 8 'X', 1 'I', 2 'D'; a = query, b = target):
-// '=' and 'X' runs merge into M, MD prints the target base of an 'X' column and ^bases of a deletion, match_len counts the '=' columns.  The ops must consume exactly
-// the spans of aln on both sequences.
+// cigar_str as minimap2 builds it without --eqx: '=' and 'X' merge into M (include/starphase_hip.h)
 int32_t sp_affine_cigar_strings(const sp_affine_aln* aln, const uint32_t* cigar, uint32_t n_cigar, const char* target, uint64_t target_len,
                                 char* cigar_str, uint32_t cigar_cap, char* md, uint32_t md_cap, uint64_t* match_len) {
-    if (!aln || (!cigar && n_cigar) || !target) return SP_ERR_INVALID_ARG;
-    if (aln->b_start < 0 || aln->b_end < aln->b_start || (uint64_t)aln->b_end > target_len || aln->a_start < 0 || aln->a_end < aln->a_start) return SP_ERR_INVALID_ARG;
-    std::string cg, tag;
-    char last_op = 0; int64_t run = 0, same = 0, matches = 0; bool in_del = false;
-    auto push = [&](char op, int64_t n) {
-        if (op == last_op) { run += n; return; }
-        if (run > 0) { cg += std::to_string(run); cg += last_op; }
-        last_op = op; run = n;
-    };
-    int64_t j = aln->b_start, i = aln->a_start;
-    for (uint32_t k = 0; k < n_cigar; ++k) {
-        const uint32_t op = cigar[k] & 0xFu; const int64_t n = (int64_t)(cigar[k] >> 4);
-        if (n == 0) return SP_ERR_INVALID_ARG;
-        if (op == 7u) {
-            if (j + n > aln->b_end) return SP_ERR_INVALID_ARG;
-            push('M', n); same += n; matches += n; in_del = false; j += n; i += n;
-        } else if (op == 8u) {
-            if (j + n > aln->b_end) return SP_ERR_INVALID_ARG;
-            push('M', n);
-            for (int64_t x = 0; x < n; ++x) { tag += std::to_string(same); tag += target[j + x]; same = 0; }
-            in_del = false; j += n; i += n;
-        } else if (op == 2u) {
-            if (j + n > aln->b_end) return SP_ERR_INVALID_ARG;
-            push('D', n);
-            if (!in_del) { tag += std::to_string(same); tag += '^'; same = 0; in_del = true; }
-            tag.append(target + j, (size_t)n); j += n;
-        } else if (op == 1u) {
-            push('I', n); i += n;                                     // (query-only bases do not appear in MD; a deletion run on either side of them stays one run)
-        } else return SP_ERR_INVALID_ARG;
-    }
-    if (j != aln->b_end || i != aln->a_end) return SP_ERR_INVALID_ARG;
-    if (run > 0) { cg += std::to_string(run); cg += last_op; }
-    tag += std::to_string(same);
-    if (match_len) *match_len = (uint64_t)matches;
-    int32_t rc = SP_OK;
-    if (cigar_str && cigar_cap) { const size_t n = std::min<size_t>(cg.size(), cigar_cap - 1); std::memcpy(cigar_str, cg.data(), n); cigar_str[n] = 0; if (n < cg.size()) rc = SP_ERR_CAPACITY; }
-    if (md && md_cap) { const size_t n = std::min<size_t>(tag.size(), md_cap - 1); std::memcpy(md, tag.data(), n); md[n] = 0; if (n < tag.size()) rc = SP_ERR_CAPACITY; }
-    return rc;
+    return affine_strings(aln, cigar, n_cigar, target, target_len, cigar_str, cigar_cap, md, md_cap, match_len, false);
+}
+// the same with '=' and 'X' kept apart: score_read maps with the eqx flag (caller.rs:1395), so hla_debug.json's per-allele CIGARs carry them
+int32_t sp_affine_cigar_strings_eqx(const sp_affine_aln* aln, const uint32_t* cigar, uint32_t n_cigar, const char* target, uint64_t target_len,
+                                    char* cigar_str, uint32_t cigar_cap, char* md, uint32_t md_cap, uint64_t* match_len) {
+    return affine_strings(aln, cigar, n_cigar, target, target_len, cigar_str, cigar_cap, md, md_cap, match_len, true);
 }
 
 int32_t sp_hla_debug_create(sp_hla_debug** out) {

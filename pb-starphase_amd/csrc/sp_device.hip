@@ -426,6 +426,7 @@ void* sp_scratch(sp_ctx* ctx, size_t bytes) {
     (void)hipSetDevice(ctx->device);       // the current device is per host thread: a helper thread's first HIP call may be this allocation
     if (ctx->scratch) { hipFree(ctx->scratch); ctx->scratch = nullptr; ctx->scratch_bytes = 0; }
     size_t want = bytes + bytes / 4;
+    ++ctx->pool_allocs;
     if (hipMalloc(&ctx->scratch, want) != hipSuccess) { ctx->scratch = nullptr; return nullptr; }
     ctx->scratch_bytes = want;
     return ctx->scratch;
@@ -437,6 +438,7 @@ void* sp_pool(sp_ctx* ctx, const char* name, size_t bytes) {
     (void)hipSetDevice(ctx->device);       // (as in sp_scratch: never allocate on whatever device the calling thread happens to have current)
     if (e.first) { (void)hipFree(e.first); e.first = nullptr; e.second = 0; }
     size_t want = bytes + bytes / 8 + 256;
+    ++ctx->pool_allocs;
     if (hipMalloc(&e.first, want) != hipSuccess) { e.first = nullptr; return nullptr; }
     e.second = want;
     return e.first;

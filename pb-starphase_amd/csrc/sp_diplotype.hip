@@ -117,6 +117,7 @@ struct sp_starphase {
     sp_diplotype_settings s{};
     std::string include_set, exclude_set, sample_name, sv_vcf, debug_folder;
     int32_t read_debug = 0;                          // sp_starphase_set_read_debug: a debug folder also receives read_debug.json
+    int32_t hla_debug_mappings = 0;                  // sp_starphase_set_hla_debug_mappings: hla_debug.json carries the mapping of each consensus against every allowed allele
     std::set<std::string> include, exclude; bool has_include = false, has_exclude = false;
     // chromosomes the variant genes were normalised against (sp_variant_gene keeps a pointer)
     std::map<std::string, std::string> chrom_seq;
@@ -522,11 +523,60 @@ int32_t read_debug_save(sp_starphase* h, const std::vector<Read4>& reads, const 
     return SP_OK;
 }
 
+// the per-allele mappings of a group's consensuses (sp_starphase_set_hla_debug_mappings): ONE batched map over every consensus of the group's samples that have a debug
+// folder; item[(gene * 2 + k)] of a sample = its item in the map, -1: no consensus, or one that does not place
+struct HlaMaps { sp_hla_map* map = nullptr; ~HlaMaps() { sp_hla_map_free(map); } };
+
+// ReadMappingStats::add_mapping for every allowed allele of one consensus (score_read with all_hla_targets, src/hla/caller.rs:1398,1473-1476): keyed by the star allele,
+// cdna_mapping / dna_mapping from the map (DetailedMappingStats::from_mapping, src/hla/debug.rs:161-182: query = allele, target = consensus).  A star allele met twice is
+// the reference's "Entry ... is already occupied!" error; here the first entry stays and the later one is skipped with a warning.
+int32_t hla_debug_mappings_add(sp_starphase* h, sp_hla_debug* dbg, const std::string& gene, const std::string& who, const sp_hla_map* map, uint32_t item, std::string& warnings, std::string& err) {
+    uint32_t n = 0; const uint32_t* alleles = nullptr; const int32_t* st = nullptr;
+    int32_t rc = sp_hla_map_item(map, item, nullptr, &n, &alleles, nullptr, nullptr, &st);
+    if (rc != SP_OK) { err = "hla_debug.json: " + opt(sp_hla_map_last_error(map)); return rc; }
+    const char* seq[2] = { nullptr, nullptr }; uint32_t len[2] = { 0, 0 };
+    for (int L = 0; L < 2; ++L) sp_hla_map_consensus_seq(map, item, L, &seq[L], &len[L]);
+    const std::string target[2] = { std::string(seq[0] ? seq[0] : "", len[0]), std::string(seq[1] ? seq[1] : "", len[1]) };
+    std::set<std::string> seen;
+    std::string cs, md;
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t a = alleles[k];
+        const std::string& key = h->a_star[a];
+        if (!seen.insert(key).second) {
+            warnings += "hla_debug.json: " + gene + " " + who + ": star allele " + key + " of " + h->a_id[a] + " is already in the mapping_stats; entry skipped\n";
+            continue;
+        }
+        sp_detailed_mapping dm[2]; std::string strings[2][2]; bool have[2] = { false, false };
+        for (int L = 0; L < 2; ++L) {
+            sp_affine_aln aln; uint32_t nc = 0; const uint32_t* ops = nullptr;
+            rc = sp_hla_map_mapping(map, item, k, L, &aln, nullptr, &nc, &ops);
+            if (rc != SP_OK) { err = "hla_debug.json: " + opt(sp_hla_map_last_error(map)); return rc; }
+            if (aln.score <= 0 || (L == 0 && h->s.disable_cdna_scoring)) continue;
+            const size_t cap = 12 * ((size_t)nc + 2) + (size_t)(aln.b_end - aln.b_start) + 32;
+            cs.assign(cap, 0); md.assign(cap, 0);
+            uint64_t match_len = 0;
+            rc = sp_affine_cigar_strings_eqx(&aln, ops, nc, target[L].data(), target[L].size(), cs.data(), (uint32_t)cap, md.data(), (uint32_t)cap, &match_len);
+            if (rc != SP_OK) { err = "hla_debug.json: the CIGAR of " + h->a_id[a] + " does not spell its mapping"; return rc; }
+            strings[L][0] = cs.c_str(); strings[L][1] = md.c_str();
+            const int32_t qlen = st[(size_t)k * 6 + 3 * L];                      // the allele's length at this level (stats_mm2)
+            sp_detailed_mapping& d = dm[L]; d = sp_detailed_mapping{};
+            d.present = 1; d.query_len = (uint64_t)qlen; d.target_len = target[L].size(); d.match_len = match_len; d.nm = (uint64_t)aln.nm;
+            d.query_unmapped = (uint64_t)(qlen - (aln.a_end - aln.a_start)); d.target_unmapped = (uint64_t)(target[L].size() - (size_t)(aln.b_end - aln.b_start));
+            d.cigar = strings[L][0].c_str(); d.md = strings[L][1].c_str();
+            have[L] = true;
+        }
+        rc = sp_hla_debug_add_mapping(dbg, gene.c_str(), who.c_str(), key.c_str(), have[0] ? &dm[0] : nullptr, have[1] ? &dm[1] : nullptr);
+        if (rc != SP_OK) { err = std::string("hla_debug.json: ") + sp_hla_debug_last_error(dbg); return rc; }
+    }
+    return SP_OK;
+}
+
 // the HLA entries of one sample: PgxMappingDetails of every read, the diplotypes, hla_debug.json.  rec / rev: by position in QNAME order; rev[k].allele
 // >= 0 names the reverse-strand mapping a read was dropped for (src/hla/realigner.rs:178-193)
 int32_t hla_package(sp_starphase* h, const std::vector<Read4>& reads, const std::vector<uint32_t>& searched, const std::vector<uint32_t>& order,
                     const sp_hla_realign* rec, const sp_hla_rev_hit* rev, const sp_hla_call* calls, const std::string& debug_folder,
-                    std::vector<Entry>& out, std::string& err, const ReadCigars* cigars, uint32_t cigars_first) {
+                    std::vector<Entry>& out, std::string& err, const ReadCigars* cigars, uint32_t cigars_first,
+                    const sp_hla_map* maps = nullptr, const int32_t* map_item = nullptr, std::string* warnings = nullptr) {
     const size_t G = h->hgenes.size();
     // PgxMappingDetails of every read, in the order the loop met them, in the bucket of its gene (realigned) or of the gene searched (ignored)
     std::vector<std::unique_ptr<GeneDetailsPtr>> det(G);
@@ -578,6 +628,10 @@ int32_t hla_package(sp_starphase* h, const std::vector<Read4>& reads, const std:
                 const std::string who = k ? "consensus2" : "consensus1";
                 const std::string st = t >= 0 ? h->hgenes[h->a_gene[t]].name + "*" + h->a_star[t] : "";
                 sp_hla_debug_add_read(dbg, h->hgenes[g].name.c_str(), who.c_str(), t >= 0 ? h->a_id[t].c_str() : nullptr, st.c_str());
+                if (maps && map_item && warnings && map_item[g * 2 + k] >= 0) {
+                    const int32_t mr = hla_debug_mappings_add(h, dbg, h->hgenes[g].name, who, maps, (uint32_t)map_item[g * 2 + k], *warnings, err);
+                    if (mr != SP_OK) { sp_hla_debug_free(dbg); return mr; }
+                }
             }
             sp_hla_debug_add_dual_stats(dbg, h->hgenes[g].name.c_str(), &calls[g]);
         }
@@ -743,6 +797,9 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
     bool want_cigars = false;                                        // one traceback pass for the group when any of its samples has a debug folder
     for (Sample* b : with) want_cigars |= h->read_debug && !b->debug.empty();
     ReadCigars cigars; cigars.stride = 1;
+    bool want_maps = false;                                          // likewise one batched map of the group's consensuses
+    for (Sample* b : with) want_maps |= h->hla_debug_mappings && !b->debug.empty();
+    HlaMaps maps; std::vector<int32_t> map_item(with.size() * G * 2, -1);
     if (R) {
         sp_seqset* set = nullptr;
         int32_t rc = upload_reads(h->ctx, parts, &set);
@@ -771,12 +828,36 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
         if (rc != SP_OK) { err = "sp_hla_diplotype_genes: " + opt(sp_last_error(h->ctx)); return rc; }
         for (size_t x = 0; x < at.size(); ++x) std::copy(cc.begin() + x * G, cc.begin() + (x + 1) * G, calls.begin() + (size_t)at[x] * G);
         if (want_cigars) { rc = read_cigars(h, set, rec.data(), R, &cigars, err); if (rc != SP_OK) return rc; }
+        // the per-allele mappings of hla_debug.json: every consensus of the samples that have a debug folder, in one batched map
+        if (want_maps) {
+            std::vector<uint32_t> mg, ml, where; std::vector<const char*> mc;
+            for (size_t x = 0; x < at.size(); ++x) {
+                if (with[at[x]]->debug.empty()) continue;
+                for (size_t g = 0; g < G; ++g) {
+                    const sp_hla_call& c = cc[x * G + g];
+                    if (c.status == 1) continue;
+                    for (int k = 0; k < 2; ++k) {
+                        if (k == 1 && !c.is_dual) continue;
+                        const char* cons = h->hla_cons.data() + ((x * G + g) * 2 + k) * (size_t)cap;
+                        const size_t len = strnlen(cons, cap);
+                        if (!len) continue;
+                        mg.push_back((uint32_t)g); mc.push_back(cons); ml.push_back((uint32_t)len); where.push_back((uint32_t)(((size_t)at[x] * G + g) * 2 + k));
+                    }
+                }
+            }
+            if (!mg.empty()) {
+                std::vector<uint32_t> item_of;
+                rc = spi_hla_map_type_batch(h->ctx, h->hla, (uint32_t)mg.size(), mg.data(), mc.data(), ml.data(), h->s.hla_require_dna, h->s.disable_cdna_scoring, &maps.map, &item_of);
+                if (rc != SP_OK) { err = "sp_hla_map_type_consensus: " + opt(sp_last_error(h->ctx)); return rc; }
+                for (size_t i = 0; i < item_of.size(); ++i) map_item[where[item_of[i]]] = (int32_t)i;
+            }
+        }
     }
     for (size_t k = 0; k < with.size(); ++k) {
         Sample* b = with[k];
         std::string e;
         const int32_t rc = hla_package(h, b->hreads, b->hsearched, orders[k], rec.data() + first[k], rev.data() + first[k], calls.data() + k * G, b->debug, b->hla_entries, e,
-                                       want_cigars ? &cigars : nullptr, first[k]);
+                                       want_cigars ? &cigars : nullptr, first[k], maps.map, maps.map ? map_item.data() + k * G * 2 : nullptr, &b->hwarn);
         if (rc != SP_OK) b->fail(2, rc, e);
     }
     return SP_OK;
@@ -872,6 +953,11 @@ void sp_starphase_free(sp_starphase* h) {
 
 const char* sp_starphase_last_error(const sp_starphase* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 const char* sp_starphase_warnings(const sp_starphase* h) { return h ? h->warnings.c_str() : ""; }
+int32_t sp_starphase_set_hla_debug_mappings(sp_starphase* h, int32_t on) {
+    if (!h) return SP_ERR_INVALID_ARG;
+    h->hla_debug_mappings = on ? 1 : 0;
+    return SP_OK;
+}
 int32_t sp_starphase_set_read_debug(sp_starphase* h, int32_t enable) {
     if (!h) return SP_ERR_INVALID_ARG;
     h->read_debug = enable ? 1 : 0;

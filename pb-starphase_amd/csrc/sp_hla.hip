@@ -850,9 +850,61 @@ __global__ void k2_stats_kernel(const K2Level* __restrict__ lv, uint32_t total, 
     }
 }
 
+// ---- the K2 map (sp_hla_map_consensus): every pair of a level re-scored the reference's way WITH its alignment, and score_read's running best decided on those alignments
+// the pair list of one level for sp_launch_affine_map: pair t's allele (minimap2's query) against its consensus (its target) on the diagonal the level's own cell lies on --
+// what k2_rescore_cells_kernel does for the winner alone; a cell that found nothing (ok = 0) has no mapping (max_ed < 0: skipped)
+__global__ void k2_map_pairs_kernel(const uint32_t* __restrict__ allele_idx, const uint32_t* __restrict__ cons_idx, const sp_aln* __restrict__ alns, uint32_t n, sp_pair* __restrict__ pairs) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const sp_aln al = alns[t];
+    sp_pair p; p.a = allele_idx[t]; p.b = cons_idx[t]; p.diag = 0; p.max_ed = -1;
+    if (al.ok) { p.diag = ((al.b_start - al.a_start) + (al.b_end - al.a_end)) / 2; p.max_ed = K2_MAX_ED; }
+    pairs[t] = p;
+}
+// the ops of a mapping as the event row k2_scan_kernel reads (type << 30 | b_pos in path order) and as the sp_aln k2_levels_kernel reads (spans and NM of the affine alignment).
+// A mapping with more than `stride` edit bases does not fit a row: it is no mapping to the scan (ok = 0), as an allele beyond K2_MAX_ED edits is none to the unit-cost one.
+__global__ void k2_map_events_kernel(const sp_affine_aln* __restrict__ af, const uint32_t* __restrict__ n_cigar, const uint64_t* __restrict__ op_off, const uint32_t* __restrict__ ops,
+                                     const sp_pair* __restrict__ pairs, const int32_t* __restrict__ a_len, const int32_t* __restrict__ b_len, uint32_t n, uint32_t stride,
+                                     sp_aln* __restrict__ alns, uint32_t* __restrict__ ev) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const sp_affine_aln f = af[t];
+    sp_aln al; al.ok = 0; al.nm = 0; al.a_start = al.a_end = al.b_start = al.b_end = al.a_len = al.b_len = 0;
+    if (f.score > 0 && f.nm >= 0 && (uint32_t)f.nm <= stride && op_off[t] != ~0ull && n_cigar[t] != 0xFFFFFFFFu) {
+        const uint32_t* o = ops + op_off[t]; uint32_t* e = ev + (size_t)t * stride;
+        int j = f.b_start; uint32_t k = 0;
+        for (uint32_t x = 0; x < n_cigar[t]; ++x) {
+            const uint32_t op = o[x] & 0xFu, len = o[x] >> 4;
+            if (op == 7u) { j += (int)len; continue; }
+            for (uint32_t y = 0; y < len && k < stride; ++y) {
+                if (op == 8u) { e[k++] = (SP_EV_X << 30) | (uint32_t)j; ++j; }
+                else if (op == 2u) { e[k++] = (SP_EV_D << 30) | (uint32_t)j; ++j; }
+                else e[k++] = (SP_EV_I << 30) | (uint32_t)j;
+            }
+        }
+        al.ok = 1; al.nm = (int32_t)k; al.a_start = f.a_start; al.a_end = f.a_end; al.b_start = f.b_start; al.b_end = f.b_end;
+        al.a_len = a_len[pairs[t].a]; al.b_len = b_len[pairs[t].b];
+    }
+    alns[t] = al;
+}
+
 // =============================================================================================
 // host side
 // =============================================================================================
+// what sp_hla_map_consensus(_batch) / sp_hla_map_type_consensus hand out: per item the allowed alleles and, per (allele, level), the mapping of the K2 map
+struct sp_hla_map {
+    struct Item {
+        uint32_t gene = 0; int32_t best = -1, best_mm2 = -1;
+        std::vector<uint32_t> alleles; std::vector<int32_t> stats_mm2;          // n, n * 6
+        std::vector<sp_affine_aln> aln; std::vector<int32_t> diag; std::vector<uint32_t> n_cigar; std::vector<uint64_t> off;   // [level * n + k]
+        std::string seq[2];                                                      // the consensus of each level, gene strand (the target of the mappings)
+    };
+    std::vector<Item> items;
+    std::vector<uint32_t> src;                                                   // sp_hla_map_type_consensus and its batch form: the consensus of the call each item is (those that place)
+    std::vector<uint32_t> ops;
+    std::string err;
+};
+
 static std::string revcomp(const char* s, size_t n) {
     std::string r(n, 'N');
     for (size_t i = 0; i < n; ++i) {
@@ -1493,12 +1545,12 @@ __global__ __launch_bounds__(256) void k2_pairs_kernel(uint32_t T, uint32_t n_it
 
 struct K2Item { uint32_t gene; const char* dna; uint32_t dna_len; const char* cdna; uint32_t cdna_len; };
 static int32_t k2_score_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_items, const K2Item* items, int32_t require_dna, int32_t disable_cdna,
-                              sp_hla_best* best, int32_t* const* stats) {
+                              sp_hla_best* best, int32_t* const* stats, sp_hla_map* map = nullptr) {
     // "If cDNA scoring is disabled, require HLA DNA must be enabled" (caller.rs:517-520)
     if (disable_cdna && !require_dna) return sp_fail(ctx, SP_ERR_INVALID_ARG, "If cDNA scoring is disabled, require HLA DNA must be enabled");
     (void)hipSetDevice(ctx->device);
     // the samples of a cohort carry the same common alleles: consensuses that are the same gene and the same two strings are scored once
-    if (n_items > 1 && !stats) {
+    if (n_items > 1 && !stats && !map) {
         std::map<std::tuple<uint32_t, std::string, std::string>, uint32_t> seen;
         std::vector<K2Item> uniq; std::vector<uint32_t> as(n_items);
         for (uint32_t k = 0; k < n_items; ++k) {
@@ -1536,6 +1588,17 @@ static int32_t k2_score_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_items
         coff.push_back(blob.size());
     }
     const uint32_t T = seg_off[n_items];
+    if (map) {
+        map->items.assign(n_items, sp_hla_map::Item()); map->ops.clear();
+        for (uint32_t k = 0; k < n_items; ++k) {
+            sp_hla_map::Item& it = map->items[k];
+            it.gene = items[k].gene; it.alleles = lists[k]->idx;
+            if (!disable_cdna) it.seq[0].assign(items[k].cdna, items[k].cdna_len);
+            it.seq[1].assign(items[k].dna, items[k].dna_len);
+            const size_t n = it.alleles.size();
+            it.stats_mm2.assign(n * 6, -1); it.aln.assign(2 * n, sp_affine_aln{0, 0, 0, 0, 0, 0}); it.diag.assign(2 * n, 0); it.n_cigar.assign(2 * n, 0); it.off.assign(2 * n, 0);
+        }
+    }
     if (T == 0) return SP_OK;
     sp_seqset cons_set; sp_seqset* cons = &cons_set;       // pooled: no allocation, no free
     int rc = sp_seqset_make_small(ctx, "k2_cons", blob.data(), coff.data(), 2 * n_items, true, cons);
@@ -1624,6 +1687,83 @@ static int32_t k2_score_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_items
         }
         if (rc == SP_OK) { af.resize((size_t)2 * n_items); (void)hipMemcpyAsync(af.data(), d_af, af.size() * sizeof(sp_affine_aln), hipMemcpyDeviceToHost, ctx->stream); }
     }
+    // the map: every pair of both levels through the traceback kernel, then the scan a second time on what it found
+    // (a lambda so that its failures reach the common tail through rc, like every other stage of this function; each of them comes before the stage's copies or after a wait for them)
+    auto run_map = [&]() -> int32_t {
+        std::vector<int32_t> b_mm2;
+        const size_t T2 = (size_t)2 * T;
+        const sp_affine_opts ao = { 5, 4, 6, 2, 26, 1, 1 };
+        sp_pair* d_mp = (sp_pair*)sp_pool(ctx, "k2m_pairs", T2 * sizeof(sp_pair));
+        sp_affine_aln* d_maf = (sp_affine_aln*)sp_pool(ctx, "k2m_af", T2 * sizeof(sp_affine_aln));
+        uint32_t* d_mnc = (uint32_t*)sp_pool(ctx, "k2m_ncig", T2 * 4);
+        uint64_t* d_moff = (uint64_t*)sp_pool(ctx, "k2m_off", T2 * 8 + 8);              // (+ the cursor)
+        sp_aln* d_maln = (sp_aln*)sp_pool(ctx, "k2m_alns", T2 * sizeof(sp_aln));
+        uint32_t* d_mev = (uint32_t*)sp_pool(ctx, "k2m_ev", T2 * stride * 4);
+        K2Level* d_mlv = (K2Level*)sp_pool(ctx, "k2m_lv", T2 * sizeof(K2Level));
+        int32_t* d_mbest = (int32_t*)sp_pool(ctx, "k2m_best", (size_t)n_items * 4);
+        if (!d_mp || !d_maf || !d_mnc || !d_moff || !d_maln || !d_mev || !d_mlv || !d_mbest) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "map_consensus buffers");
+        unsigned long long* d_cur = (unsigned long long*)(d_moff + T2);
+        for (int L = 0; L < 2; ++L)
+            hipLaunchKernelGGL(k2_map_pairs_kernel, dim3(nb), dim3(tb), 0, ctx->stream, d_idx, L == 0 ? d_c0 : d_c1, d_alns + (size_t)L * T, T, d_mp + (size_t)L * T);
+        SP_HIP_CHECK(ctx, hipGetLastError());
+        // the ops of all pairs lie compact in one pooled buffer; a launch that asks for more than it holds is run again on a larger one (a warm context: once)
+        auto held = ctx->pool.find("k2m_ops");
+        uint64_t ops_cap = std::max<uint64_t>(held != ctx->pool.end() ? held->second.second / 4 : 0, T2 * 96);      // (96 words a pair and level to begin with: the alleles of HLA-A / -B against a consensus of their gene have 84 ops a mapped pair)
+        unsigned long long used = 0;
+        int32_t rc = SP_OK;
+        for (int attempt = 0; attempt < 2 && rc == SP_OK; ++attempt) {
+            uint32_t* d_ops = (uint32_t*)sp_pool(ctx, "k2m_ops", (size_t)ops_cap * 4);
+            if (!d_ops) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "map_consensus ops");
+            (void)hipMemsetAsync(d_cur, 0, 8, ctx->stream);
+            for (int L = 0; L < 2 && rc == SP_OK; ++L)
+                rc = sp_launch_affine_map(ctx, L == 0 ? db->cdna_gene : db->dna_gene, cons, d_mp + (size_t)L * T, T, ao, d_maf + (size_t)L * T, d_mnc + (size_t)L * T, d_moff + (size_t)L * T,
+                                          d_ops, ops_cap, d_cur, L == 0 ? "k2_map_cdna" : "k2_map_dna");
+            if (rc != SP_OK) break;
+            (void)hipMemcpyAsync(&used, d_cur, 8, hipMemcpyDeviceToHost, ctx->stream);
+            if (hipStreamSynchronize(ctx->stream) != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "map_consensus: the map kernel failed");
+            if (used <= ops_cap) break;
+            if (attempt == 1) return sp_fail(ctx, SP_ERR_HIP, "map_consensus: the op buffer did not hold a second run");
+            ops_cap = used;
+        }
+        if (rc == SP_OK) {
+            const uint32_t* d_ops = (const uint32_t*)ctx->pool["k2m_ops"].first;
+            for (int L = 0; L < 2; ++L) {
+                const sp_seqset* aset = L == 0 ? db->cdna_gene : db->dna_gene;
+                hipLaunchKernelGGL(k2_map_events_kernel, dim3(nb), dim3(tb), 0, ctx->stream, d_maf + (size_t)L * T, d_mnc + (size_t)L * T, d_moff + (size_t)L * T, d_ops, d_mp + (size_t)L * T,
+                                   aset->d_len, cons->d_len, T, stride, d_maln + (size_t)L * T, d_mev + (size_t)L * T * stride);
+                SP_HIP_CHECK(ctx, hipGetLastError());
+                hipLaunchKernelGGL(k2_levels_kernel, dim3(nb), dim3(tb), 0, ctx->stream, d_maln + (size_t)L * T, T, d_mlv + (size_t)L * T);
+                SP_HIP_CHECK(ctx, hipGetLastError());
+            }
+            { ProfScope ps(ctx, "k2_scan_mm2", T); hipLaunchKernelGGL(k2_scan_kernel, dim3(n_items), dim3(1024), 0, ctx->stream, d_mlv, d_maln, d_mev, stride, T, d_seg, d_mbest); }
+            SP_HIP_CHECK(ctx, hipGetLastError());
+            std::vector<sp_pair> hp(T2); std::vector<sp_affine_aln> haf(T2); std::vector<uint32_t> hnc(T2); std::vector<uint64_t> hoff(T2);
+            b_mm2.assign(n_items, -1); map->ops.resize((size_t)used);
+            (void)hipMemcpyAsync(hp.data(), d_mp, T2 * sizeof(sp_pair), hipMemcpyDeviceToHost, ctx->stream);
+            (void)hipMemcpyAsync(haf.data(), d_maf, T2 * sizeof(sp_affine_aln), hipMemcpyDeviceToHost, ctx->stream);
+            (void)hipMemcpyAsync(hnc.data(), d_mnc, T2 * 4, hipMemcpyDeviceToHost, ctx->stream);
+            (void)hipMemcpyAsync(hoff.data(), d_moff, T2 * 8, hipMemcpyDeviceToHost, ctx->stream);
+            if (used) (void)hipMemcpyAsync(map->ops.data(), d_ops, (size_t)used * 4, hipMemcpyDeviceToHost, ctx->stream);
+            (void)hipMemcpyAsync(b_mm2.data(), d_mbest, (size_t)n_items * 4, hipMemcpyDeviceToHost, ctx->stream);
+            if (hipStreamSynchronize(ctx->stream) != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "map_consensus: results");
+            for (uint32_t k = 0; k < n_items; ++k) {
+                sp_hla_map::Item& it = map->items[k];
+                const size_t n = it.alleles.size();
+                it.best_mm2 = b_mm2[k] >= 0 ? (int32_t)it.alleles[b_mm2[k]] : -1;
+                for (int L = 0; L < 2; ++L) for (size_t i = 0; i < n; ++i) {
+                    const size_t x = (size_t)L * T + seg_off[k] + i, y = (size_t)L * n + i;
+                    if (hnc[x] == 0xFFFFFFFFu) return sp_fail(ctx, SP_ERR_HIP, "map_consensus: the walk of allele " + std::to_string(it.alleles[i]) + " did not reach the cell its path started in");
+                    if (hp[x].max_ed < 0 || haf[x].score <= 0) continue;
+                    if (hoff[x] == ~0ull) return sp_fail(ctx, SP_ERR_CAPACITY, "map_consensus: the alignment of allele " + std::to_string(it.alleles[i]) + " has more runs than the map keeps");
+                    it.aln[y] = haf[x]; it.diag[y] = hp[x].diag; it.n_cigar[y] = hnc[x]; it.off[y] = hoff[x];
+                    const int len = (L == 0 ? db->cdna_gene : db->dna_gene)->h_len[it.alleles[i]];
+                    it.stats_mm2[i * 6 + 3 * L] = len; it.stats_mm2[i * 6 + 3 * L + 1] = haf[x].nm; it.stats_mm2[i * 6 + 3 * L + 2] = len - (haf[x].a_end - haf[x].a_start);
+                }
+            }
+        }
+        return rc;
+    };
+    if (rc == SP_OK && map) rc = run_map();
     if (rc == SP_OK) {
         std::vector<int32_t> b(n_items, -1);
         (void)hipMemcpyAsync(b.data(), d_best, (size_t)n_items * 4, hipMemcpyDeviceToHost, ctx->stream);
@@ -1631,6 +1771,7 @@ static int32_t k2_score_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_items
         if (e != hipSuccess) rc = sp_fail(ctx, SP_ERR_HIP, std::string("score_consensus: ") + hipGetErrorString(e));
         else for (uint32_t k = 0; k < n_items; ++k) {
             best[k].best_allele = b[k] >= 0 ? (int32_t)lists[k]->idx[b[k]] : -1;
+            if (map) map->items[k].best = best[k].best_allele;
             for (int x = 0; x < 6; ++x) best[k].mm2_stats[x] = -1;
             if (best[k].best_allele >= 0 && !af.empty()) for (int L = 0; L < 2; ++L) {
                 const sp_affine_aln& a = af[(size_t)L * n_items + k];
@@ -1667,7 +1808,7 @@ int32_t sp_hla_score_consensus_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t 
 // and one traced cell launch, the splicing is host work on the event lists, and the typing is one k2_score_batch.
 struct TypeItem { uint32_t gene; const char* cons; uint32_t len; };
 static int32_t type_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_items, const TypeItem* items, int32_t require_dna, int32_t disable_cdna,
-                          sp_hla_best* best, int32_t* const* stats, std::vector<std::string>* cdna_out) {
+                          sp_hla_best* best, int32_t* const* stats, std::vector<std::string>* cdna_out, sp_hla_map* map = nullptr) {
     (void)hipSetDevice(ctx->device);
     for (uint32_t k = 0; k < n_items; ++k) {
         if (items[k].gene >= db->n_genes || (items[k].len && !items[k].cons)) return sp_fail(ctx, SP_ERR_INVALID_ARG, "type_consensus: bad item");
@@ -1763,7 +1904,8 @@ static int32_t type_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_items, co
     if (k2.empty()) return SP_OK;
     std::vector<sp_hla_best> b2(k2.size()); std::vector<int32_t*> st2(k2.size(), nullptr);
     if (stats) for (size_t y = 0; y < k2.size(); ++y) st2[y] = stats[k2_of[y]];
-    rc = k2_score_batch(ctx, db, (uint32_t)k2.size(), k2.data(), require_dna, disable_cdna, b2.data(), stats ? st2.data() : nullptr);
+    if (map) map->src = k2_of;
+    rc = k2_score_batch(ctx, db, (uint32_t)k2.size(), k2.data(), require_dna, disable_cdna, b2.data(), stats ? st2.data() : nullptr, map);
     if (rc != SP_OK) return rc;
     for (size_t y = 0; y < k2.size(); ++y) best[k2_of[y]] = b2[y];
     return SP_OK;
@@ -1796,7 +1938,93 @@ int32_t sp_hla_type_consensus_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n
     return n ? type_batch(ctx, db, n, items.data(), require_dna, disable_cdna, best, nullptr, nullptr) : SP_OK;
 }
 
+// ---- the K2 map: score_read's per-allele mappings (include/starphase_hip.h)
+static int32_t map_new(sp_hla_map** out, sp_hla_map** m) { if (!out) return SP_ERR_INVALID_ARG; *out = nullptr; *m = new sp_hla_map(); return SP_OK; }
+static int32_t map_done(int32_t rc, sp_hla_map* m, sp_hla_map** out) {          // a call that fails hands out no handle: why is the context's last error
+    if (rc != SP_OK) { delete m; return rc; }
+    *out = m; return SP_OK;
+}
+int32_t sp_hla_map_consensus_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, const uint32_t* genes,
+                                   const char* const* cons_dna, const uint32_t* cons_dna_len, const char* const* cons_cdna, const uint32_t* cons_cdna_len,
+                                   int32_t require_dna, int32_t disable_cdna, sp_hla_map** out) {
+    if (!ctx || !db || !out || (n && (!genes || !cons_dna || !cons_dna_len || !cons_cdna || !cons_cdna_len))) return SP_ERR_INVALID_ARG;
+    std::vector<K2Item> items(n);
+    for (uint32_t k = 0; k < n; ++k) {
+        if ((cons_dna_len[k] && !cons_dna[k]) || (cons_cdna_len[k] && !cons_cdna[k])) return SP_ERR_INVALID_ARG;
+        items[k] = K2Item{ genes[k], cons_dna[k], cons_dna_len[k], cons_cdna[k], cons_cdna_len[k] };
+    }
+    sp_hla_map* m = nullptr;
+    int32_t rc = map_new(out, &m);
+    if (rc != SP_OK) return rc;
+    std::vector<sp_hla_best> best(std::max<uint32_t>(1, n));
+    if (n) rc = k2_score_batch(ctx, db, n, items.data(), require_dna, disable_cdna, best.data(), nullptr, m);
+    return map_done(rc, m, out);
+}
+int32_t sp_hla_map_consensus(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const char* cons_dna, uint32_t cons_dna_len, const char* cons_cdna, uint32_t cons_cdna_len,
+                             int32_t require_dna, int32_t disable_cdna, sp_hla_map** out) {
+    return sp_hla_map_consensus_batch(ctx, db, 1, &gene, &cons_dna, &cons_dna_len, &cons_cdna, &cons_cdna_len, require_dna, disable_cdna, out);
+}
+int32_t sp_hla_map_type_consensus(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const char* consensus_fwd, uint32_t consensus_len,
+                                  int32_t require_dna, int32_t disable_cdna, sp_hla_map** out) {
+    if (!ctx || !db || !out || gene >= db->n_genes || (consensus_len && !consensus_fwd)) return SP_ERR_INVALID_ARG;
+    sp_hla_map* m = nullptr;
+    int32_t rc = map_new(out, &m);
+    if (rc != SP_OK) return rc;
+    const TypeItem item{ gene, consensus_fwd, consensus_len };
+    sp_hla_best best;
+    rc = type_batch(ctx, db, 1, &item, require_dna, disable_cdna, &best, nullptr, nullptr, m);
+    return map_done(rc, m, out);
+}
+void sp_hla_map_free(sp_hla_map* m) { delete m; }
+const char* sp_hla_map_last_error(const sp_hla_map* m) { return m ? m->err.c_str() : ""; }
+uint32_t sp_hla_map_n_items(const sp_hla_map* m) { return m ? (uint32_t)m->items.size() : 0u; }
+int32_t sp_hla_map_item(const sp_hla_map* m, uint32_t item, uint32_t* gene, uint32_t* n_alleles, const uint32_t** alleles, int32_t* best_allele, int32_t* best_mm2, const int32_t** stats_mm2) {
+    if (!m) return SP_ERR_INVALID_ARG;
+    if (item >= m->items.size()) { const_cast<sp_hla_map*>(m)->err = "item out of range"; return SP_ERR_INVALID_ARG; }
+    const sp_hla_map::Item& it = m->items[item];
+    if (gene) *gene = it.gene;
+    if (n_alleles) *n_alleles = (uint32_t)it.alleles.size();
+    if (alleles) *alleles = it.alleles.data();
+    if (best_allele) *best_allele = it.best;
+    if (best_mm2) *best_mm2 = it.best_mm2;
+    if (stats_mm2) *stats_mm2 = it.stats_mm2.data();
+    return SP_OK;
+}
+int32_t sp_hla_map_consensus_seq(const sp_hla_map* m, uint32_t item, int32_t level, const char** seq, uint32_t* len) {
+    if (!m) return SP_ERR_INVALID_ARG;
+    if (item >= m->items.size() || (level != 0 && level != 1)) { const_cast<sp_hla_map*>(m)->err = "item or level out of range"; return SP_ERR_INVALID_ARG; }
+    if (seq) *seq = m->items[item].seq[level].data();
+    if (len) *len = (uint32_t)m->items[item].seq[level].size();
+    return SP_OK;
+}
+int32_t sp_hla_map_mapping(const sp_hla_map* m, uint32_t item, uint32_t k, int32_t level, sp_affine_aln* aln, int32_t* diag, uint32_t* n_cigar, const uint32_t** cigar) {
+    if (!m) return SP_ERR_INVALID_ARG;
+    if (item >= m->items.size() || (level != 0 && level != 1) || k >= m->items[item].alleles.size()) { const_cast<sp_hla_map*>(m)->err = "item, allele or level out of range"; return SP_ERR_INVALID_ARG; }
+    const sp_hla_map::Item& it = m->items[item];
+    const size_t y = (size_t)level * it.alleles.size() + k;
+    if (aln) *aln = it.aln[y];
+    if (diag) *diag = it.diag[y];
+    if (n_cigar) *n_cigar = it.n_cigar[y];
+    if (cigar) *cigar = it.n_cigar[y] ? m->ops.data() + it.off[y] : nullptr;
+    return SP_OK;
+}
+
 } // extern "C"
+
+// sp_hla_map_type_consensus for n hg38-forward consensuses at once (one placement launch, one batched K2, one map): item_of[x] = the consensus item x of the map is
+int32_t spi_hla_map_type_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, const uint32_t* genes, const char* const* consensus_fwd, const uint32_t* consensus_len,
+                               int32_t require_dna, int32_t disable_cdna, sp_hla_map** out, std::vector<uint32_t>* item_of) {
+    if (!ctx || !db || !out || !item_of || (n && (!genes || !consensus_fwd || !consensus_len))) return SP_ERR_INVALID_ARG;
+    sp_hla_map* m = nullptr;
+    int32_t rc = map_new(out, &m);
+    if (rc != SP_OK) return rc;
+    std::vector<TypeItem> items(n);
+    for (uint32_t k = 0; k < n; ++k) items[k] = TypeItem{ genes[k], consensus_fwd[k], consensus_len[k] };
+    std::vector<sp_hla_best> best(std::max<uint32_t>(1, n));
+    if (n) rc = type_batch(ctx, db, n, items.data(), require_dna, disable_cdna, best.data(), nullptr, nullptr, m);
+    if (rc == SP_OK) *item_of = m->src;
+    return map_done(rc, m, out);
+}
 
 std::string spi_hla_allele_fwd(sp_ctx* ctx, const sp_hla_db* db, uint32_t a) {
     if (!db || a >= db->n_alleles) return std::string();

@@ -79,6 +79,7 @@ struct sp_ctx {
     // reusable scratch
     void* scratch = nullptr; size_t scratch_bytes = 0;
     std::map<std::string, std::pair<void*, size_t>> pool;   // named grow-only device buffers (no malloc/free per call)
+    uint64_t pool_allocs = 0;                                // hipMalloc calls sp_pool / sp_scratch have made for this context (sp_profile_get "pool:device")
     std::map<std::string, std::pair<void*, size_t>> host_pool;   // named grow-only pinned host buffers (results leave the device through them)
     // device buffers of read sets that were freed, kept for the next upload (sp_dev_alloc / sp_dev_release, sp_api.hip): hipFree waits for EVERY stream of the device --
     // a lane that closed its sample's read set stood still until the other lane's kernels had ended, 1.2 ms per sample -- and an upload began with three hipMalloc
@@ -167,6 +168,8 @@ int sp_launch_affine(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const 
                      sp_affine_aln* d_out, const char* prof_name, const uint32_t* d_n_live = nullptr, const void* d_wins = nullptr, const void* d_mids = nullptr);   // sp_affine.hip: two-piece affine re-score, pairs and results in device memory
 int sp_rescore_mappings(sp_ctx* ctx, const sp_seqset* Aw, const sp_seqset* Bw, const CellDesc* d_cells, const sp_aln* d_ref, uint64_t n, bool target_is_a,
                         const sp_affine_opts& o, int band, sp_affine_aln* d_out, const char* prefix, uint32_t stride, int trace_retry_wide = 0, const sp_aln* d_tr_in = nullptr, const uint32_t* d_ev_in = nullptr, int ends_only = 0);   // sp_affine.hip: mappings the caller holds, re-scored (no DP for isolated edits); trace_retry_wide: the trace of a mapping the 64-diagonal cell loses runs on the wide band; ends_only > 0: the caller takes the EXTENT of the mapping only -- edits that far from both ends of the alignment never take the DP (af_classify_kernel)
+int sp_launch_affine_map(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const void* d_pairs /* sp_pair rows, max_ed < 0: skip */, uint64_t n_pairs, const sp_affine_opts& o, sp_affine_aln* d_out,
+                         uint32_t* d_n_cigar, uint64_t* d_op_off, uint32_t* d_ops, uint64_t ops_cap, unsigned long long* d_cursor, const char* prof_name);   // sp_affine.hip: the K2 map -- sp_affine_align_batch's alignment on 64 diagonals from checkpoints and an LDS tile, no per-cell scratch; ops compact in d_ops from *d_cursor on (op_off ~0: no room, n_cigar 0xFFFFFFFF: lost walk)
 constexpr uint32_t SP_ANCHOR_SKIP = 0xFFFFFFFFu;     // b index of a pair of a device-made pair list that sp_launch_anchor is to skip (votes 0, diagonal 0)
 int sp_launch_cells_wide(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const CellDesc* d_cells, uint64_t n_cells, sp_aln* d_out);
 int sp_launch_pack_on(hipStream_t stream, int num_cus, int format, const void* d_src, const uint64_t* d_off, const uint64_t* d_word_off, const int32_t* d_len, uint32_t n,
@@ -222,6 +225,9 @@ struct ProfScope {
 int32_t spi_gene_entry_extras(const sp_database* db, const sp_variant_gene* g, std::string* reference_allele, bool* has_sv, std::string* sv_chrom);
 // sp_hla.hip, for sp_diplotype.hip: allele a of the database in hg38 orientation (the target of sp_hla_realign_cigars), ASCII; empty: no DNA sequence
 std::string spi_hla_allele_fwd(sp_ctx* ctx, const sp_hla_db* db, uint32_t a);
+// sp_hla.hip, for sp_diplotype.hip: sp_hla_map_type_consensus for n consensuses in one batched map; item_of[x] = the consensus that item x of the map is (those that place)
+int32_t spi_hla_map_type_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, const uint32_t* genes, const char* const* consensus_fwd, const uint32_t* consensus_len,
+                               int32_t require_dna, int32_t disable_cdna, sp_hla_map** out, std::vector<uint32_t>* item_of);
 // sp_cyp.hip, for sp_diplotype.hip: sp_cyp_diplotype_mappings with the list in a vector the library sizes
 int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
                                    sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings);

@@ -38,6 +38,7 @@ const char* HELP_HEAD =
     "      --exclude-set <TXT>          Optional file indicating the list of genes to exclude from diplotyping, one per line\n"
     "      --output-debug <DIR>         Optional output debug folder (hla_debug.json, cyp2d6_alleles.json)\n"
     "      --debug-reads                Also write read_debug.json there: every realigned HLA read's accepted allele with CIGAR and MD (needs --output-debug)\n"
+    "      --debug-hla-mappings         Fill hla_debug.json's mapping_stats: each HLA consensus against every allowed allele, CIGAR and MD (needs --output-debug)\n"
     "      --sample-name <STRING>       Sample name from the input VCFs (default: first sample)\n"
     "\n";
 const char* BATCH_HELP_HEAD =
@@ -88,6 +89,7 @@ const char* BATCH_HELP_TAIL =
     "  -t, --threads <THREADS>          Host BAM / VCF decode workers [default: min(16, hardware threads)]\n"
     "      --sequential                 Run CYP2D6 after the variant genes and the HLA genes of a group (the calls are the same)\n"
     "      --debug-reads                Also write read_debug.json into every sample's debug folder (needs an output_debug column that names one)\n"
+    "      --debug-hla-mappings         Fill the mapping_stats of every sample's hla_debug.json (needs an output_debug column that names a folder)\n"
     "  -v, --verbose...                 Enable verbose output (print the warnings and the timings of the batch)\n"
     "  -h, --help                       Print help\n"
     "\n"
@@ -116,7 +118,7 @@ bool parse_u64(const std::string& s, uint64_t* out) {
 struct Options {
     sp_diplotype_settings s;
     std::string database, reference, include, exclude;
-    int verbose = 0; bool debug_reads = false;
+    int verbose = 0; bool debug_reads = false, debug_hla_mappings = false;
 };
 
 // the option being parsed: its name (a `--key=value` split) and where its value comes from.  need*: 0, or the exit status of the clap error
@@ -166,6 +168,7 @@ int parse_options(int argc, char** argv, const char* usage, const std::string& h
         else if (a == "--normalize-d6-only") s.normalize_d6_only = 1;
         else if (a == "--sequential") s.sequential = 1;
         else if (a == "--debug-reads") o.debug_reads = true;
+        else if (a == "--debug-hla-mappings") o.debug_hla_mappings = true;
         else if (a == "-v" || a == "--verbose") ++o.verbose;
         else if (a.size() > 2 && a[0] == '-' && a[1] == 'v' && a.find_first_not_of('v', 1) == std::string::npos) o.verbose += (int)a.size() - 1;
         else if (a == "--max-sv-length") { if (!(rc = arg.need_u64(&u))) s.max_sv_length = u; }
@@ -205,6 +208,7 @@ sp_starphase* create_handle(const Options& o, int* code) {
         return nullptr;
     }
     if (o.debug_reads) sp_starphase_set_read_debug(h, 1);
+    if (o.debug_hla_mappings) sp_starphase_set_hla_debug_mappings(h, 1);
     return h;
 }
 
@@ -252,7 +256,7 @@ int batch_main(int argc, char** argv) {
         return NOT_MINE;
     });
     if (parsed != PARSED) return parsed;
-    const int verbose = o.verbose; const bool debug_reads = o.debug_reads;
+    const int verbose = o.verbose; const bool debug_reads = o.debug_reads, debug_hla_mappings = o.debug_hla_mappings;
     std::string missing;
     if (database.empty()) missing += "\n  --database <JSON>";
     if (reference.empty()) missing += "\n  --reference <FASTA>";
@@ -290,10 +294,10 @@ int batch_main(int argc, char** argv) {
         }
     }
     if (rows.empty()) { std::fprintf(stderr, "error: manifest \"%s\" lists no samples\n", manifest.c_str()); return EX_USAGE_; }
-    if (debug_reads) {
+    if (debug_reads || debug_hla_mappings) {
         bool any = false;
         for (const Row& r : rows) any |= !r.debug.empty();
-        if (!any) { std::fprintf(stderr, "error: --debug-reads needs a debug folder: no manifest row names one (output_debug)\n"); return EX_USAGE_; }
+        if (!any) { std::fprintf(stderr, "error: %s needs a debug folder: no manifest row names one (output_debug)\n", debug_reads ? "--debug-reads" : "--debug-hla-mappings"); return EX_USAGE_; }
     }
     // every row through the checks of `diplotype`: the files (NOINPUT), then check_diplotype_settings (USAGE)
     std::vector<std::vector<const char*>> bam_ptrs(rows.size());
@@ -408,6 +412,7 @@ int main(int argc, char** argv) {
     s.sample_name = sample.empty() ? nullptr : sample.c_str(); s.sv_vcf = sv_vcf.empty() ? nullptr : sv_vcf.c_str();
     s.debug_folder = debug.empty() ? nullptr : debug.c_str();
     if (o.debug_reads && debug.empty()) { std::fprintf(stderr, "error: --debug-reads needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
+    if (o.debug_hla_mappings && debug.empty()) { std::fprintf(stderr, "error: --debug-hla-mappings needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
     char err[512];
     if (sp_diplotype_settings_check(&s, &in, err, sizeof err) != SP_OK) {
         std::fprintf(stderr, "error: Error while processing CLI settings: %s\n", err);

@@ -132,6 +132,7 @@ def _lib():
         "sp_result_save_pharmcat_tsv": (_i32, [_vp, _s]),
         "sp_aln_strings": (_i32, [P(ffi.sp_aln), _vp, _s, _u64, _s, _u32, _s, _u32, P(_u64)]),
         "sp_affine_cigar_strings": (_i32, [_vp, _vp, _u32, _s, _u64, _s, _u32, _s, _u32, P(_u64)]),
+        "sp_affine_cigar_strings_eqx": (_i32, [_vp, _vp, _u32, _s, _u64, _s, _u32, _s, _u32, P(_u64)]),
         "sp_hla_debug_create": (_i32, [P(_vp)]),
         "sp_hla_debug_free": (None, [_vp]),
         "sp_hla_debug_last_error": (_s, [_vp]),
@@ -151,6 +152,7 @@ def _lib():
         "sp_starphase_warnings": (_s, [_vp]),
         "sp_starphase_last_timing": (_i32, [_vp, P(sp_starphase_timing)]),
         "sp_starphase_set_read_debug": (_i32, [_vp, _i32]),
+        "sp_starphase_set_hla_debug_mappings": (_i32, [_vp, _i32]),
         "sp_starphase_call_batch": (_i32, [_vp, _u32, P(sp_sample_inputs), P(_s), P(sp_batch_options), P(_vp), P(_i32)]),
         "sp_starphase_sample_error": (_s, [_vp, _u32]),
         "sp_starphase_sample_warnings": (_s, [_vp, _u32]),
@@ -504,6 +506,19 @@ def affine_cigar_strings(aln, cigar, target, cigar_cap=None, md_cap=None):
     return cg.value.decode(), md.value.decode(), ml.value
 
 
+def affine_cigar_strings_eqx(aln, cigar, target, cigar_cap=None, md_cap=None):
+    """sp_affine_cigar_strings_eqx: affine_cigar_strings with '=' and 'X' runs kept apart (the cigar of hla_debug.json's per-allele mappings)"""
+    a = np.array([tuple(int(aln[k]) for k in ("score", "nm", "a_start", "a_end", "b_start", "b_end"))], ffi.AFFINE_DTYPE)
+    ops = np.ascontiguousarray(cigar, np.uint32)
+    cap = 12 * (len(ops) + 2) + int(aln["b_end"]) - int(aln["b_start"]) + 32
+    ccap, mcap = cigar_cap or cap, md_cap or cap
+    cg, md, ml = C.create_string_buffer(ccap), C.create_string_buffer(mcap), _u64()
+    rc = _lib().sp_affine_cigar_strings_eqx(a.ctypes.data, ops.ctypes.data, len(ops), _b(target), len(target), cg, ccap, md, mcap, C.byref(ml))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_affine_cigar_strings_eqx")
+    return cg.value.decode(), md.value.decode(), ml.value
+
+
 def affine_detailed_mapping(aln, cigar, target, query_len):
     """DetailedMappingStats::from_mapping for such a row: a dict with the fields of sp_detailed_mapping"""
     cg, md, ml = affine_cigar_strings(aln, cigar, target)
@@ -797,6 +812,13 @@ class Starphase:
             self.close()
         except Exception:
             pass
+
+    def set_hla_debug_mappings(self, on=True):
+        """sp_starphase_set_hla_debug_mappings: hla_debug.json of a debug folder carries the mapping of each consensus against every allowed allele of its gene; off by default"""
+        rc = _lib().sp_starphase_set_hla_debug_mappings(self._h, 1 if on else 0)
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_starphase_set_hla_debug_mappings")
+        return self
 
     def set_read_debug(self, enable=True):
         """sp_starphase_set_read_debug: a debug folder also receives read_debug.json (every realigned HLA read's accepted allele with CIGAR and MD); off by default"""

@@ -206,6 +206,15 @@ def hla_call_config(min_consensus_count=3, dual_max_ed_delta=100, min_consensus_
                               int(disable_cdna), int(absent_capable), normalized_coverage)
 
 
+class HlaMap:
+    """one consensus of HlaDb.map_consensus(_batch) / map_type_consensus: alleles = the allowed alleles (database indices, database order); best_allele = the K2 winner,
+    best_mm2 = score_read's running best decided on the a = 5 alignments; stats_mm2[k] = cDNA (len, nm, unmapped), DNA (len, nm, unmapped), -1 = no mapping;
+    aln[level, k] (AFFINE_DTYPE; a = allele, b = consensus), diag[level, k], cigar[level][k] (ops, len << 4 | op); cons_cdna / cons_dna = the targets"""
+    def __init__(self, gene, alleles, best_allele, best_mm2, stats_mm2, aln, diag, cigar, cons_cdna, cons_dna):
+        self.gene, self.alleles, self.best_allele, self.best_mm2, self.stats_mm2 = gene, alleles, best_allele, best_mm2, stats_mm2
+        self.aln, self.diag, self.cigar, self.cons_cdna, self.cons_dna = aln, diag, cigar, cons_cdna, cons_dna
+
+
 class sp_hla_best(C.Structure):
     _fields_ = [("best_allele", C.c_int32), ("n_scored", C.c_int32), ("mm2_stats", C.c_int32 * 6)]
 
@@ -265,6 +274,15 @@ def lib():
         "sp_hla_db_free": (None, [vp]),
         "sp_hla_realign_reads": (i32, [vp, vp, vp, vp, vp]),
         "sp_hla_realign_reads_rev": (i32, [vp, vp, vp, vp, vp]),
+        "sp_hla_map_consensus": (i32, [vp, vp, u32, C.c_char_p, u32, C.c_char_p, u32, i32, i32, C.POINTER(vp)]),
+        "sp_hla_map_consensus_batch": (i32, [vp, vp, u32, vp, C.POINTER(C.c_char_p), vp, C.POINTER(C.c_char_p), vp, i32, i32, C.POINTER(vp)]),
+        "sp_hla_map_type_consensus": (i32, [vp, vp, u32, C.c_char_p, u32, i32, i32, C.POINTER(vp)]),
+        "sp_hla_map_free": (None, [vp]),
+        "sp_hla_map_last_error": (C.c_char_p, [vp]),
+        "sp_hla_map_n_items": (u32, [vp]),
+        "sp_hla_map_item": (i32, [vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(vp)]),
+        "sp_hla_map_consensus_seq": (i32, [vp, u32, i32, C.POINTER(vp), C.POINTER(u32)]),
+        "sp_hla_map_mapping": (i32, [vp, u32, u32, i32, vp, C.POINTER(i32), C.POINTER(u32), C.POINTER(vp)]),
         "sp_hla_score_consensus": (i32, [vp, vp, u32, C.c_char_p, u32, C.c_char_p, u32, i32, i32, C.POINTER(sp_hla_best), vp]),
         "sp_hla_score_consensus_batch": (i32, [vp, vp, u32, vp, C.POINTER(C.c_char_p), vp, C.POINTER(C.c_char_p), vp, i32, i32, vp]),
         "sp_hla_type_consensus_batch": (i32, [vp, vp, u32, vp, C.POINTER(C.c_char_p), vp, i32, i32, vp]),
@@ -1299,6 +1317,59 @@ class HlaDb:
         best = (sp_hla_best * max(1, n))()
         self.ctx.check(lib().sp_hla_type_consensus_batch(self.ctx._h, self._h, n, _ptr(g), d, _ptr(dl), int(require_dna), int(disable_cdna), best))
         return [(best[i].best_allele, best[i].n_scored) for i in range(n)]
+
+    def _read_map(self, h):
+        """an sp_hla_map handle -> [HlaMap item], and frees it"""
+        L = lib()
+        vp, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+        try:
+            out = []
+            for item in range(L.sp_hla_map_n_items(h)):
+                gene, n, best, best_mm2, pa, ps = u32(), u32(), i32(), i32(), vp(), vp()
+                self.ctx.check(L.sp_hla_map_item(h, item, C.byref(gene), C.byref(n), C.byref(pa), C.byref(best), C.byref(best_mm2), C.byref(ps)))
+                n = n.value
+                alleles = np.ctypeslib.as_array(C.cast(pa, C.POINTER(u32)), (n,)).copy() if n else np.zeros(0, np.uint32)
+                stats = np.ctypeslib.as_array(C.cast(ps, C.POINTER(i32)), (n * 6,)).copy().reshape(n, 6) if n else np.zeros((0, 6), np.int32)
+                seqs = []
+                for lv in (0, 1):
+                    p, ln = vp(), u32()
+                    self.ctx.check(L.sp_hla_map_consensus_seq(h, item, lv, C.byref(p), C.byref(ln)))
+                    seqs.append(C.string_at(p, ln.value).decode() if ln.value else "")
+                aln = np.zeros((2, n), AFFINE_DTYPE); diag = np.zeros((2, n), np.int32); cigars = [[None] * n, [None] * n]
+                for lv in (0, 1):
+                    for k in range(n):
+                        d, nc, pc = i32(), u32(), vp()
+                        self.ctx.check(L.sp_hla_map_mapping(h, item, k, lv, aln[lv, k:k + 1].ctypes.data, C.byref(d), C.byref(nc), C.byref(pc)))
+                        diag[lv, k] = d.value
+                        cigars[lv][k] = np.ctypeslib.as_array(C.cast(pc, C.POINTER(u32)), (nc.value,)).copy() if nc.value else np.zeros(0, np.uint32)
+                out.append(HlaMap(gene.value, alleles, best.value, best_mm2.value, stats, aln, diag, cigars, seqs[0], seqs[1]))
+            return out
+        finally:
+            L.sp_hla_map_free(h)
+
+    def map_consensus(self, gene, cons_dna, cons_cdna, require_dna=False, disable_cdna=False):
+        """sp_hla_map_consensus: score_read's per-allele mappings of one gene-strand consensus -> HlaMap"""
+        h = C.c_void_p()
+        self.ctx.check(lib().sp_hla_map_consensus(self.ctx._h, self._h, int(gene), cons_dna.encode(), len(cons_dna), cons_cdna.encode(), len(cons_cdna),
+                                                  int(require_dna), int(disable_cdna), C.byref(h)))
+        return self._read_map(h)[0]
+
+    def map_consensus_batch(self, items, require_dna=False, disable_cdna=False):
+        """sp_hla_map_consensus_batch: items = [(gene, cons_dna, cons_cdna)] -> [HlaMap], one launch set for all of them"""
+        n = len(items)
+        g = np.array([it[0] for it in items], np.uint32)
+        d = (C.c_char_p * max(1, n))(*[it[1].encode() for it in items]); dl = np.array([len(it[1]) for it in items], np.uint32)
+        c = (C.c_char_p * max(1, n))(*[it[2].encode() for it in items]); cl = np.array([len(it[2]) for it in items], np.uint32)
+        h = C.c_void_p()
+        self.ctx.check(lib().sp_hla_map_consensus_batch(self.ctx._h, self._h, n, _ptr(g), d, _ptr(dl), c, _ptr(cl), int(require_dna), int(disable_cdna), C.byref(h)))
+        return self._read_map(h)
+
+    def map_type_consensus(self, gene, consensus_fwd, require_dna=False, disable_cdna=False):
+        """sp_hla_map_type_consensus: the same from the hg38-forward consensus (placement, splice, gene strand) -> HlaMap, or None when the consensus does not place"""
+        h = C.c_void_p()
+        self.ctx.check(lib().sp_hla_map_type_consensus(self.ctx._h, self._h, int(gene), consensus_fwd.encode(), len(consensus_fwd), int(require_dna), int(disable_cdna), C.byref(h)))
+        m = self._read_map(h)
+        return m[0] if m else None
 
     def score_consensus(self, gene, cons_dna, cons_cdna, require_dna=False, disable_cdna=False, stats=True):
         best = sp_hla_best()
