@@ -1301,6 +1301,80 @@ typedef struct {
 } sp_starphase_batch_timing;
 int32_t sp_starphase_last_batch_timing(const sp_starphase* handle, sp_starphase_batch_timing* out);
 
+/* ------------------------------------------------------------------ update-hla: a database's HLA section rebuilt from IMGT/HLA FASTA files
+ * The HLA half of `pbstarphase build` without its downloads: the two files of an IMGT/HLA release a user keeps locally (hla_gen.fasta, hla_nuc.fasta) ->
+ * the allele table (host) -> the gene coordinates stretched over every allele's best mapping (device) -> a database file `diplotype` can use (host).
+ *
+ * sp_hla_fasta_load: convert_fasta_str_to_map + collapse_hla_lookup (src/build_database.rs:233-325) + HlaAlleleDefinition::new (src/hla/alleles.rs:353-382).
+ * The id is the record id, the star allele the first word of the description; a repeated id with the same (star allele, sequence) is accepted, with another it
+ * fails with "FASTA record with multiple IDs/sequences detected: <id>"; a DNA record without a cDNA record is dropped (one warning with the count); a
+ * description that differs between the files fails with `<id> has description "<dna>" for DNA and "<cdna>" for cDNA.`; an allele of a gene outside
+ * SUPPORTED_HLA_GENES (alleles.rs:16-47) is dropped and counted; the table is in id order (the reference's BTreeMap).  Plain and gzip files are read.
+ * Errors: SP_ERR_INVALID_ARG, no handle, the text in sp_hla_fasta_last_error() (per thread). */
+typedef struct sp_hla_alleles sp_hla_alleles;
+typedef struct {
+    uint32_t n_alleles, n_dna;                        /* alleles kept; those of them with a DNA sequence */
+    uint32_t n_dropped_no_cdna, n_dropped_gene;       /* DNA records without a cDNA record; alleles of unsupported genes */
+    const char* warnings;                             /* one per line, "" when there are none */
+} sp_hla_alleles_stats;
+int32_t sp_hla_fasta_load(const char* hla_gen, const char* hla_nuc, sp_hla_alleles** out);
+const char* sp_hla_fasta_last_error(void);
+void    sp_hla_alleles_free(sp_hla_alleles* alleles);
+int32_t sp_hla_alleles_info(const sp_hla_alleles* alleles, sp_hla_alleles_stats* out);
+/* allele i in id order: "HLA:HLA00001", "HLA-A", "01:01:01:01", the DNA sequence (NULL: none) and the cDNA sequence; every output is optional */
+int32_t sp_hla_alleles_get(const sp_hla_alleles* alleles, uint32_t i, const char** hla_id, const char** gene_name, const char** star_allele,
+                           const char** dna, const char** cdna);
+
+/* sp_hla_config_extend: HlaConfig::new (src/hla/alleles.rs:109-207).  The starting gene collection is the hla_config of `db` (the two-gene default when the file
+ * has none, or db = NULL) reduced to SUPPORTED_HLA_GENES, with HLA-DRB3 / HLA-DRB4 copied from HLA-DRB1 when they are missing (HLA_COORDINATE_COPIES) and
+ * HLA-DRB3 / 4 / 5 marked absent-capable (ABSENT_HLA_GENES).  Per gene, in name order: the window is [start - 2000, end + 2000) of the gene's INITIAL
+ * coordinates on `reference`; every allele of the gene with a DNA sequence is mapped on it on both strands the library's way -- k-mer vote anchor
+ * (sp_anchor_batch's kernel), then the two-piece affine re-score at the map-hifi scores on 256 diagonals around it (sp_affine_rescore_batch's kernel), which
+ * reports minimap2's numbers; a cell whose score is below 200 is no mapping (map-hifi's min_dp_max: minimap2 drops it) -- back to back on the device, (allele, strand) cells of up to batch_alleles alleles (0 = 1,024; also bounded by bases, so memory
+ * is bounded by the batch, not by the gene) per pass.  hlacfg_pick_extend_kernel then takes, per allele, its strands in minimap2's output order (higher DP
+ * score first, forward first on a tie), keeps the one with the strictly smallest (nm + unmapped query bases) / allele length (0.1 for a zero numerator:
+ * MappingScore::score_value) when that is strictly below 1.0, and folds window_start + t_start / t_end into the gene's minimum / maximum and the worst kept
+ * score into the gene's slot (wave reduction, one partial per wave, a second small pass).  Comparisons are exact (integer cross-multiplication); ties for
+ * "worst" go to the lowest allele index (the reference visits alleles in id order and replaces on strictly greater), so neither batch size nor launch
+ * geometry changes a result.  extend_coordinates is src/database/gene_definition.rs:112-116: start = min, end = max, moved = either changed.
+ * A window that starts before the chromosome (start < 2000; the reference's u64 subtraction underflows there and panics) or ends behind it fails the call
+ * with SP_ERR_INVALID_ARG and a message.  An allele whose chosen re-score ends on the outermost diagonal of its band (the alignment may have left it) is
+ * reported as "none" (status -1) with a warning naming it, as is one longer than 65,534 bases; neither fails the call (the reference skips an allele
+ * without a mapping). */
+typedef struct {
+    int32_t status;                     /* 1 = mapping chosen; 0 = none (no DNA, no mapping, or no mapping scoring below 1.0); -1 = none: band overflow / too long */
+    int32_t rev, nm;                    /* strand of the chosen mapping (1 = reverse), minimap2's NM */
+    int32_t q_start, q_end;             /* span on the allele as given (minimap2 reports query coordinates on the query's own strand) */
+    int32_t t_start, t_end;             /* span on the window: chromosome position = gene start - 2000 + t */
+    int32_t gene;                       /* index into the result's genes, -1: the allele's gene is not in the collection */
+} sp_hla_cfg_mapping;
+typedef struct {
+    const char* name; const char* chrom;
+    uint64_t start, end;                /* the extended coordinates, 0-based half-open */
+    int32_t  moved, is_absent_capable;
+    int32_t  worst_allele;              /* index (sp_hla_alleles order) of the worst accepted mapping, -1: none beat the perfect match of the window */
+    int32_t  worst_len, worst_nm, worst_unmapped;     /* its MappingStats */
+    uint32_t n_dna_alleles, n_mapped;
+} sp_hla_cfg_gene;
+typedef struct sp_hla_config_result sp_hla_config_result;
+int32_t sp_hla_config_extend(sp_ctx* ctx, sp_fasta* reference, const sp_database* db, const sp_hla_alleles* alleles, uint32_t batch_alleles,
+                             sp_hla_config_result** out);
+/* a result made by hand (host only): genes by name with their coordinates; moved = 0, no mappings */
+int32_t sp_hla_config_result_create(uint32_t n_genes, const char* const* names, const uint64_t* start, const uint64_t* end, sp_hla_config_result** out);
+void    sp_hla_config_result_free(sp_hla_config_result* result);
+int32_t sp_hla_config_result_info(const sp_hla_config_result* result, uint32_t* n_genes, uint32_t* n_alleles, const char** warnings);
+int32_t sp_hla_config_result_gene(const sp_hla_config_result* result, uint32_t g, sp_hla_cfg_gene* out);           /* g < n_genes, name order */
+int32_t sp_hla_config_result_mapping(const sp_hla_config_result* result, uint32_t allele, sp_hla_cfg_mapping* out); /* allele < n_alleles */
+
+/* The input database written again with its HLA part replaced (host only): hla_sequences = the table (HlaAlleleDefinition's fields in its order,
+ * src/hla/alleles.rs:332-344), hla_config = { gene_collection: { version, gene_dict } } with the result's genes (GeneDefinition's fields in its order,
+ * src/database/gene_definition.rs:18-34; a gene's transcript id, strand and exons are the input's, or the default's), database_metadata.hla_version =
+ * hla_version; members in PgxDatabase's order (src/database/pgx_database.rs:23-41); every other section is carried over with unchanged content.  gzip when
+ * out_path ends in ".gz".  A result gene the input's hla_config cannot supply (neither itself nor its HLA_COORDINATE_COPIES source), or one without an exon
+ * (validate_config), fails with SP_ERR_INVALID_ARG (sp_database_last_error). */
+int32_t sp_database_save_hla(const sp_database* db, const sp_hla_alleles* alleles, const sp_hla_config_result* result, const char* hla_version,
+                             const char* out_path);
+
 #ifdef __cplusplus
 }
 #endif

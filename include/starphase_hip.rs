@@ -657,6 +657,40 @@ pub struct sp_starphase_batch_timing {
     pub n_hla_reads: u64,
     pub n_cyp_reads: u64,
 }
+#[repr(C)]
+pub struct sp_hla_alleles_stats {
+    pub n_alleles: u32,
+    pub n_dna: u32,
+    pub n_dropped_no_cdna: u32,
+    pub n_dropped_gene: u32,
+    pub warnings: *const c_char,
+}
+#[repr(C)]
+pub struct sp_hla_cfg_mapping {
+    pub status: i32,
+    pub rev: i32,
+    pub nm: i32,
+    pub q_start: i32,
+    pub q_end: i32,
+    pub t_start: i32,
+    pub t_end: i32,
+    pub gene: i32,
+}
+#[repr(C)]
+pub struct sp_hla_cfg_gene {
+    pub name: *const c_char,
+    pub chrom: *const c_char,
+    pub start: u64,
+    pub end: u64,
+    pub moved: i32,
+    pub is_absent_capable: i32,
+    pub worst_allele: i32,
+    pub worst_len: i32,
+    pub worst_nm: i32,
+    pub worst_unmapped: i32,
+    pub n_dna_alleles: u32,
+    pub n_mapped: u32,
+}
 
 #[repr(C)] pub struct sp_bam { _private: [u8; 0] }
 #[repr(C)] pub struct sp_ctx { _private: [u8; 0] }
@@ -665,6 +699,8 @@ pub struct sp_starphase_batch_timing {
 #[repr(C)] pub struct sp_fasta { _private: [u8; 0] }
 #[repr(C)] pub struct sp_gene_details { _private: [u8; 0] }
 #[repr(C)] pub struct sp_group { _private: [u8; 0] }
+#[repr(C)] pub struct sp_hla_alleles { _private: [u8; 0] }
+#[repr(C)] pub struct sp_hla_config_result { _private: [u8; 0] }
 #[repr(C)] pub struct sp_hla_db { _private: [u8; 0] }
 #[repr(C)] pub struct sp_hla_debug { _private: [u8; 0] }
 #[repr(C)] pub struct sp_hla_map { _private: [u8; 0] }
@@ -856,4 +892,16 @@ extern "C" {
     pub fn sp_starphase_sample_error(handle: *const sp_starphase, i: u32) -> *const c_char;
     pub fn sp_starphase_sample_warnings(handle: *const sp_starphase, i: u32) -> *const c_char;
     pub fn sp_starphase_last_batch_timing(handle: *const sp_starphase, out: *mut sp_starphase_batch_timing) -> i32;
+    pub fn sp_hla_fasta_load(hla_gen: *const c_char, hla_nuc: *const c_char, out: *mut *mut sp_hla_alleles) -> i32;
+    pub fn sp_hla_fasta_last_error() -> *const c_char;
+    pub fn sp_hla_alleles_free(alleles: *mut sp_hla_alleles);
+    pub fn sp_hla_alleles_info(alleles: *const sp_hla_alleles, out: *mut sp_hla_alleles_stats) -> i32;
+    pub fn sp_hla_alleles_get(alleles: *const sp_hla_alleles, i: u32, hla_id: *mut *const c_char, gene_name: *mut *const c_char, star_allele: *mut *const c_char, dna: *mut *const c_char, cdna: *mut *const c_char) -> i32;
+    pub fn sp_hla_config_extend(ctx: *mut sp_ctx, reference: *mut sp_fasta, db: *const sp_database, alleles: *const sp_hla_alleles, batch_alleles: u32, out: *mut *mut sp_hla_config_result) -> i32;
+    pub fn sp_hla_config_result_create(n_genes: u32, names: *const *const c_char, start: *const u64, end: *const u64, out: *mut *mut sp_hla_config_result) -> i32;
+    pub fn sp_hla_config_result_free(result: *mut sp_hla_config_result);
+    pub fn sp_hla_config_result_info(result: *const sp_hla_config_result, n_genes: *mut u32, n_alleles: *mut u32, warnings: *mut *const c_char) -> i32;
+    pub fn sp_hla_config_result_gene(result: *const sp_hla_config_result, g: u32, out: *mut sp_hla_cfg_gene) -> i32;
+    pub fn sp_hla_config_result_mapping(result: *const sp_hla_config_result, allele: u32, out: *mut sp_hla_cfg_mapping) -> i32;
+    pub fn sp_database_save_hla(db: *const sp_database, alleles: *const sp_hla_alleles, result: *const sp_hla_config_result, hla_version: *const c_char, out_path: *const c_char) -> i32;
 }

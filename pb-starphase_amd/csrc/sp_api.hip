@@ -178,6 +178,9 @@ int32_t sp_struct_size(const char* name) {
     SP_SZ(sp_hla_rev_hit)
     SP_SZ(sp_batch_options)
     SP_SZ(sp_starphase_batch_timing)
+    SP_SZ(sp_hla_alleles_stats)
+    SP_SZ(sp_hla_cfg_mapping)
+    SP_SZ(sp_hla_cfg_gene)
 #undef SP_SZ
     return -1;
 }

@@ -76,6 +76,9 @@ bool read_gene_dict(const Value* dict, std::vector<Region>& out, std::string& er
     return true;
 }
 
+// Region of the gene `name`, or nullptr
+const Region* find_region(const std::vector<Region>& v, const std::string& name) { for (const Region& r : v) if (r.name == name) return &r; return nullptr; }
+
 template <class T> const T* data_or_dummy(const std::vector<T>& v) { static const T dummy[1] = {}; return v.empty() ? dummy : v.data(); }
 
 struct CStrings {                       // an array of C strings that may hold NULLs
@@ -88,8 +91,17 @@ struct CStrings {                       // an array of C strings that may hold N
 
 } // namespace
 
+// a file as it is, or inflated when it starts with the gzip magic number (the FASTA intake of sp_hla_build.hip reads through it)
+bool spi_read_text_file(const char* path, std::string& out, std::string& err) {
+    std::string raw;
+    if (!read_file(path, raw, err)) return false;
+    if (raw.size() >= 2 && (unsigned char)raw[0] == 0x1f && (unsigned char)raw[1] == 0x8b) return gunzip(raw, out, err);
+    out.swap(raw);
+    return true;
+}
+
 struct sp_database {
-    Value root; std::string err;
+    Value root; mutable std::string err;
     std::string md[5];
     std::vector<Region> hla_genes, collection;
     Value cyp_cfg_default, hla_cfg_default;
@@ -360,6 +372,109 @@ int32_t sp_database_cyp_flatten(sp_database* db, const char* chrom_seq, uint64_t
     K->n_translate = (uint32_t)tr.size(); K->translate_key = f.tk.finish(); K->translate_val = f.tv.finish();
     K->n_connections = (uint32_t)con.size(); K->connection_a = f.ca.finish(); K->connection_b = f.cb.finish();
     K->n_singletons = (uint32_t)sg.size(); K->singletons = f.sg.finish();
+    return SP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ update-hla: the database written again
+// PgxDatabase's members in its order (src/database/pgx_database.rs:23-41); hla_config and hla_sequences are made here, the rest is the input's
+int32_t sp_database_save_hla(const sp_database* db, const sp_hla_alleles* alleles, const sp_hla_config_result* result, const char* hla_version, const char* out_path) {
+    if (!db) return SP_ERR_INVALID_ARG;
+    if (!alleles || !result || !hla_version || !out_path) { db->err = "save_hla: alleles, result, hla_version and out_path are required"; return SP_ERR_INVALID_ARG; }
+    auto coords = [](const std::string& chrom, uint64_t s, uint64_t e) {
+        Value c = spj::object();
+        c.obj.emplace_back("chrom", spj::str(chrom)); c.obj.emplace_back("start", spj::unum(s)); c.obj.emplace_back("end", spj::unum(e));
+        return c;
+    };
+    // hla_config: the result's genes on the input's definitions (GeneDefinition: gene_name, coordinates, is_forward_strand, transcript_id, exons, is_absent_capable)
+    const Value* hc = member(db->root, "hla_config");
+    const Value* in_gc = hc ? member(*hc, "gene_collection") : nullptr;
+    const Value* in_dict = in_gc ? in_gc->get("gene_dict") : nullptr;
+    static const char* const COPIES[][2] = { { "HLA-DRB3", "HLA-DRB1" }, { "HLA-DRB4", "HLA-DRB1" } };           // HLA_COORDINATE_COPIES (src/hla/alleles.rs:36-46)
+    static const char* const DEFAULT_TRANSCRIPT[][2] = { { "HLA-A", "NM_002116.8" }, { "HLA-B", "NM_005514.8" } }; // default_gene_collection (alleles.rs:247-249)
+    uint32_t n_genes = 0, n_maps = 0;
+    sp_hla_config_result_info(result, &n_genes, &n_maps, nullptr);
+    Value dict = spj::object();
+    for (uint32_t g = 0; g < n_genes; ++g) {
+        sp_hla_cfg_gene rg{};
+        sp_hla_config_result_gene(result, g, &rg);
+        std::string src = rg.name;
+        const Region* r = find_region(db->hla_genes, src);
+        if (!r) for (const auto& cp : COPIES) if (src == cp[0]) { src = cp[1]; r = find_region(db->hla_genes, src); break; }
+        if (!r) { db->err = std::string("save_hla: the database's hla_config has no definition for ") + rg.name; return SP_ERR_INVALID_ARG; }
+        if (r->es.empty()) { db->err = std::string("Found 0 exons for \"") + rg.name + "\", expected >0."; return SP_ERR_INVALID_ARG; }
+        Value def = spj::object();
+        const Value* in_def = in_dict ? in_dict->get(src.c_str()) : nullptr;
+        const Value* in_name = in_def ? in_def->get("gene_name") : nullptr;
+        def.obj.emplace_back("gene_name", spj::str(in_name && in_name->kind == Value::String ? in_name->s : r->name));
+        def.obj.emplace_back("coordinates", coords(r->chrom, rg.start, rg.end));
+        def.obj.emplace_back("is_forward_strand", spj::boolean(r->fwd));
+        Value tid;                                                                     // (null)
+        if (in_def) { if (const Value* t = in_def->get("transcript_id")) tid = *t; }
+        else for (const auto& dt : DEFAULT_TRANSCRIPT) if (!hc && r->name == dt[0]) tid = spj::str(dt[1]);
+        def.obj.emplace_back("transcript_id", tid);
+        Value exons = spj::array();
+        for (size_t e = 0; e < r->es.size(); ++e) exons.arr.push_back(coords(r->chrom, r->es[e], r->ee[e]));
+        def.obj.emplace_back("exons", exons);
+        def.obj.emplace_back("is_absent_capable", spj::boolean(rg.is_absent_capable != 0));
+        dict.obj.emplace_back(rg.name, std::move(def));
+    }
+    Value gc = spj::object();
+    const Value* in_version = in_gc ? in_gc->get("version") : nullptr;
+    gc.obj.emplace_back("version", spj::str(in_version && in_version->kind == Value::String ? in_version->s : std::string("starphase_hip_default")));
+    gc.obj.emplace_back("gene_dict", std::move(dict));
+    Value cfg = spj::object();
+    cfg.obj.emplace_back("gene_collection", std::move(gc));
+    // hla_sequences: HlaAlleleDefinition (hla_id, gene_name, star_allele, dna_sequence, cdna_sequence), id order
+    sp_hla_alleles_stats st{};
+    sp_hla_alleles_info(alleles, &st);
+    Value seqs = spj::object();
+    for (uint32_t i = 0; i < st.n_alleles; ++i) {
+        const char *id, *gene, *star, *dna, *cdna;
+        sp_hla_alleles_get(alleles, i, &id, &gene, &star, &dna, &cdna);
+        Value a = spj::object();
+        a.obj.emplace_back("hla_id", spj::str(id)); a.obj.emplace_back("gene_name", spj::str(gene));
+        Value fields = spj::array();
+        for (const char* p = star;;) { const char* q = std::strchr(p, ':'); fields.arr.push_back(spj::str(q ? std::string(p, q) : std::string(p))); if (!q) break; p = q + 1; }
+        a.obj.emplace_back("star_allele", std::move(fields));
+        a.obj.emplace_back("dna_sequence", dna ? spj::str(dna) : Value());
+        a.obj.emplace_back("cdna_sequence", spj::str(cdna));
+        seqs.obj.emplace_back(id, std::move(a));
+    }
+    Value md = spj::object();
+    static const char* md_keys[5] = { "pbstarphase_version", "cpic_version", "hla_version", "pharmvar_version", "build_time" };
+    for (int i = 0; i < 5; ++i) md.obj.emplace_back(md_keys[i], spj::str(i == 2 ? std::string(hla_version) : db->md[i]));
+    // the document, member by member (the carried sections are written from where they are: a database is tens of megabytes)
+    static const char* order[7] = { "database_metadata", "gene_collection", "gene_entries", "hla_config", "hla_sequences", "cyp2d6_config", "cyp2d6_gene_def" };
+    std::vector<std::pair<std::string, const Value*>> members;
+    for (const char* k : order) {
+        const std::string key(k);
+        if (key == "database_metadata") members.emplace_back(key, &md);
+        else if (key == "hla_config") members.emplace_back(key, &cfg);
+        else if (key == "hla_sequences") members.emplace_back(key, &seqs);
+        else if (const Value* v = db->root.get(k)) members.emplace_back(key, v);
+    }
+    for (const auto& kv : db->root.obj) if (std::find_if(std::begin(order), std::end(order), [&](const char* k) { return kv.first == k; }) == std::end(order)) members.emplace_back(kv.first, &kv.second);
+    std::string text = "{\n";
+    for (size_t k = 0; k < members.size(); ++k) {
+        text += "  "; spj::write_string(text, members[k].first); text += ": ";
+        spj::write_pretty(text, *members[k].second, 1);
+        text += k + 1 < members.size() ? ",\n" : "\n";
+    }
+    text += "}";
+    const std::string path(out_path);
+    if (path.size() >= 3 && path.compare(path.size() - 3, 3, ".gz") == 0) {
+        gzFile f = gzopen(out_path, "wb");
+        if (!f) { db->err = "cannot open " + path + " for writing"; return SP_ERR_INVALID_ARG; }
+        size_t at = 0; bool ok = true;
+        while (at < text.size() && ok) { const unsigned n = (unsigned)std::min<size_t>(text.size() - at, 1u << 30); ok = gzwrite(f, text.data() + at, n) == (int)n; at += n; }
+        if (gzclose(f) != Z_OK) ok = false;
+        if (!ok) { db->err = "error while writing " + path; return SP_ERR_INVALID_ARG; }
+    } else {
+        FILE* f = std::fopen(out_path, "wb");
+        if (!f) { db->err = "cannot open " + path + " for writing"; return SP_ERR_INVALID_ARG; }
+        const bool ok = std::fwrite(text.data(), 1, text.size(), f) == text.size();
+        if (std::fclose(f) != 0 || !ok) { db->err = "error while writing " + path; return SP_ERR_INVALID_ARG; }
+    }
     return SP_OK;
 }
 

@@ -3,6 +3,7 @@
 // 2 for a command line that does not parse (clap), NOINPUT (66) for an input file that does not exist, USAGE (64) when check_diplotype_settings
 // refuses the settings, IOERR (74) for the database / reference / output files, DATAERR (65) when the call fails.  Every check of the command
 // line is made before the first device call.  `starphase_hip diplotype-batch` types the samples of a manifest through sp_starphase_call_batch.
+// `starphase_hip update-hla` rebuilds a database's HLA section from the two FASTA files of an IMGT/HLA release (the HLA half of `pbstarphase build`, offline).
 #include "../../include/starphase_hip.h"
 #include <sys/stat.h>
 #include <cerrno>
@@ -95,6 +96,27 @@ const char* BATCH_HELP_TAIL =
     "\n"
     "Every sample's files are what `starphase_hip diplotype` takes for one sample; the debug folder is a manifest column (--output-debug is refused).\n"
     "Exit status: 0 when every sample was written, 65 when a sample failed (the others are written; each failure is printed with its row).\n";
+
+const char* UPDATE_USAGE = "starphase_hip update-hla [OPTIONS] --database <JSON> --reference <FASTA> --hla-gen <FASTA> --hla-nuc <FASTA> --output-db <JSON>";
+const char* UPDATE_HELP =
+    "Rebuild a database's HLA section from the FASTA files of an IMGT/HLA release (the HLA half of pbstarphase build, offline)\n"
+    "\n"
+    "Usage: starphase_hip update-hla [OPTIONS] --database <JSON> --reference <FASTA> --hla-gen <FASTA> --hla-nuc <FASTA> --output-db <JSON>\n"
+    "\n"
+    "Input/Output:\n"
+    "  -d, --database <JSON>            Input database file (JSON); its hla_config gives the starting gene coordinates (HLA-A / HLA-B defaults without one)\n"
+    "  -r, --reference <FASTA>          Reference FASTA file\n"
+    "      --hla-gen <FASTA>            Genomic allele sequences of the release (hla_gen.fasta, plain or gzip)\n"
+    "      --hla-nuc <FASTA>            cDNA allele sequences of the release (hla_nuc.fasta, plain or gzip)\n"
+    "      --hla-version <STRING>       Version string stored as database_metadata.hla_version [default: the input database's]\n"
+    "  -o, --output-db <JSON>           Output database file (JSON; gzip when the name ends in .gz)\n"
+    "\n"
+    "Execution:\n"
+    "      --batch-alleles <N>          Alleles per device pass [default: 1024]\n"
+    "  -v, --verbose...                 Enable verbose output (print the warnings, every gene's coordinates and its worst mapping)\n"
+    "  -h, --help                       Print help\n"
+    "\n"
+    "CPIC and PharmVar sections are carried over unchanged (the reference builds them from the network).\n";
 
 bool exists(const std::string& p) { struct stat st; return ::stat(p.c_str(), &st) == 0; }
 
@@ -363,15 +385,96 @@ int batch_main(int argc, char** argv) {
     return code != EX_OK_ ? code : failed ? EX_DATAERR_ : EX_OK_;
 }
 
+int update_hla_main(int argc, char** argv) {
+    std::string database, reference, gen, nuc, version, output;
+    bool has_version = false; int verbose = 0; uint64_t batch = 0;
+    Arg arg{argc, argv, 2, UPDATE_USAGE};
+    for (int& i = arg.i; i < argc; ++i) {
+        std::string& a = arg.a;
+        a = argv[i]; arg.has_inline = false;
+        const size_t eq = a.find('=');
+        if (a.rfind("--", 0) == 0 && eq != std::string::npos) { arg.val = a.substr(eq + 1); a = a.substr(0, eq); arg.has_inline = true; }
+        int rc = 0;
+        if (a == "-h" || a == "--help") { std::fputs(UPDATE_HELP, stdout); return EX_OK_; }
+        else if (a == "-d" || a == "--database") rc = arg.need(&database);
+        else if (a == "-r" || a == "--reference") rc = arg.need(&reference);
+        else if (a == "--hla-gen") rc = arg.need(&gen);
+        else if (a == "--hla-nuc") rc = arg.need(&nuc);
+        else if (a == "--hla-version") { rc = arg.need(&version); has_version = true; }
+        else if (a == "-o" || a == "--output-db") rc = arg.need(&output);
+        else if (a == "--batch-alleles") { rc = arg.need_u64(&batch); if (!rc && batch > 0xFFFFFFFFull) rc = clap_error(UPDATE_USAGE, "value too large for '--batch-alleles'"); }
+        else if (a == "-v" || a == "--verbose") ++verbose;
+        else if (a.size() > 2 && a[0] == '-' && a[1] == 'v' && a.find_first_not_of('v', 1) == std::string::npos) verbose += (int)a.size() - 1;
+        else return clap_error(UPDATE_USAGE, "unexpected argument '" + a + "' found");
+        if (rc) return rc;
+    }
+    std::string missing;
+    if (database.empty()) missing += "\n  --database <JSON>";
+    if (reference.empty()) missing += "\n  --reference <FASTA>";
+    if (gen.empty()) missing += "\n  --hla-gen <FASTA>";
+    if (nuc.empty()) missing += "\n  --hla-nuc <FASTA>";
+    if (output.empty()) missing += "\n  --output-db <JSON>";
+    if (!missing.empty()) return clap_error(UPDATE_USAGE, "the following required arguments were not provided:" + missing);
+    if (!exists(database)) return noinput("", "Database JSON", database);
+    if (!exists(reference)) return noinput("", "Reference FASTA", reference);
+    if (!exists(gen)) return noinput("", "HLA genomic FASTA", gen);
+    if (!exists(nuc)) return noinput("", "HLA cDNA FASTA", nuc);
+    // the host side first: the database, the two FASTA files (DATAERR), the reference
+    char err[512];
+    sp_database* db = nullptr; sp_hla_alleles* alleles = nullptr; sp_fasta* fasta = nullptr; sp_ctx* ctx = nullptr; sp_hla_config_result* res = nullptr;
+    int code = EX_OK_;
+    auto done = [&](int c) { sp_hla_config_result_free(res); if (ctx) sp_ctx_destroy(ctx); if (fasta) sp_fasta_free(fasta); sp_hla_alleles_free(alleles); if (db) sp_database_free(db); return c; };
+    if (sp_database_load(database.c_str(), &db, err, sizeof err) != SP_OK) { std::fprintf(stderr, "error: Error while loading database: %s\n", err); return done(EX_IOERR_); }
+    if (sp_hla_fasta_load(gen.c_str(), nuc.c_str(), &alleles) != SP_OK) { std::fprintf(stderr, "error: Error while reading HLA sequences: %s\n", sp_hla_fasta_last_error()); return done(EX_DATAERR_); }
+    sp_hla_alleles_stats st{};
+    sp_hla_alleles_info(alleles, &st);
+    if (st.warnings && *st.warnings) std::fprintf(stderr, "%s", st.warnings);
+    if (sp_fasta_open(reference.c_str(), &fasta, err, sizeof err) != SP_OK) { std::fprintf(stderr, "error: Error while loading reference: %s\n", err); return done(EX_IOERR_); }
+    // the device work
+    const int32_t crc = sp_ctx_create(0, nullptr, &ctx);
+    if (crc != SP_OK) { ctx = nullptr; std::fprintf(stderr, "error: no usable HIP device (sp_ctx_create: status %d)\n", crc); return done(EX_UNAVAILABLE_); }
+    const int32_t rc = sp_hla_config_extend(ctx, fasta, db, alleles, (uint32_t)batch, &res);
+    if (rc != SP_OK) {
+        std::fprintf(stderr, "error: Error while extending HLA coordinates: %s\n", sp_last_error(ctx));
+        return done(rc == SP_ERR_HIP || rc == SP_ERR_NO_DEVICE ? EX_UNAVAILABLE_ : EX_DATAERR_);
+    }
+    uint32_t n_genes = 0, n_alleles = 0; const char* warn = nullptr;
+    sp_hla_config_result_info(res, &n_genes, &n_alleles, &warn);
+    if (warn && *warn) std::fprintf(stderr, "%s", warn);
+    if (verbose) {
+        std::fprintf(stderr, "%u alleles (%u with DNA), %u dropped without cDNA, %u of unsupported genes\n", st.n_alleles, st.n_dna, st.n_dropped_no_cdna, st.n_dropped_gene);
+        for (uint32_t g = 0; g < n_genes; ++g) {
+            sp_hla_cfg_gene x{};
+            sp_hla_config_result_gene(res, g, &x);
+            std::fprintf(stderr, "%s %s:%llu-%llu%s, %u of %u DNA alleles mapped", x.name, x.chrom, (unsigned long long)x.start, (unsigned long long)x.end, x.moved ? " (updated)" : "", x.n_mapped, x.n_dna_alleles);
+            if (x.worst_allele >= 0) {
+                const char* id = "";
+                sp_hla_alleles_get(alleles, (uint32_t)x.worst_allele, &id, nullptr, nullptr, nullptr, nullptr);
+                std::fprintf(stderr, ", worst mapping %s (%d+%d)/%d", id, x.worst_nm, x.worst_unmapped, x.worst_len);
+            }
+            std::fprintf(stderr, "\n");
+        }
+    }
+    sp_database_metadata md{};
+    sp_database_get_metadata(db, &md);
+    if (sp_database_save_hla(db, alleles, res, has_version ? version.c_str() : md.hla_version, output.c_str()) != SP_OK) {
+        std::fprintf(stderr, "error: Error while writing database: %s\n", sp_database_last_error(db));
+        code = EX_IOERR_;
+    }
+    return done(code);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc < 2 || !std::strcmp(argv[1], "-h") || !std::strcmp(argv[1], "--help")) {
         std::printf("starphase_hip: PGx diplotyping on AMD Instinct GPUs\n\nUsage: starphase_hip <COMMAND> [OPTIONS]\n\nCommands:\n  diplotype        Diplotype a sample from its files\n"
-                    "  diplotype-batch  Diplotype the samples of a manifest, many per device pass\n");
+                    "  diplotype-batch  Diplotype the samples of a manifest, many per device pass\n"
+                    "  update-hla       Rebuild a database's HLA section from the FASTA files of an IMGT/HLA release\n");
         return argc < 2 ? EX_CLAP : EX_OK_;
     }
     if (!std::strcmp(argv[1], "diplotype-batch")) return batch_main(argc, argv);
+    if (!std::strcmp(argv[1], "update-hla")) return update_hla_main(argc, argv);
     if (std::strcmp(argv[1], "diplotype") != 0) return clap_error(USAGE, std::string("unrecognized subcommand '") + argv[1] + "'");
     Options o;
     sp_diplotype_settings& s = o.s;

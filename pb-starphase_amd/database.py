@@ -78,6 +78,19 @@ class sp_starphase_batch_timing(C.Structure):
                [(k, _u32) for k in ("n_samples", "n_groups", "n_failed", "reserved_")] + [("n_hla_reads", _u64), ("n_cyp_reads", _u64)]
 
 
+class sp_hla_alleles_stats(C.Structure):
+    _fields_ = [(k, _u32) for k in ("n_alleles", "n_dna", "n_dropped_no_cdna", "n_dropped_gene")] + [("warnings", _s)]
+
+
+class sp_hla_cfg_mapping(C.Structure):
+    _fields_ = [(k, _i32) for k in ("status", "rev", "nm", "q_start", "q_end", "t_start", "t_end", "gene")]
+
+
+class sp_hla_cfg_gene(C.Structure):
+    _fields_ = [("name", _s), ("chrom", _s), ("start", _u64), ("end", _u64), ("moved", _i32), ("is_absent_capable", _i32), ("worst_allele", _i32),
+                ("worst_len", _i32), ("worst_nm", _i32), ("worst_unmapped", _i32), ("n_dna_alleles", _u32), ("n_mapped", _u32)]
+
+
 SUBALLELE_MATCH, CORE_MATCH, INEXACT_DIPLOTYPES, FROM_MAPPINGS, FROM_MULTI_MAPPINGS, NO_MATCH = range(6)
 _bound = False
 
@@ -159,10 +172,25 @@ def _lib():
         "sp_starphase_last_batch_timing": (_i32, [_vp, P(sp_starphase_batch_timing)]),
         "sp_cyp_diplotype_cohort_mappings": (_i32, [_vp, P(ffi.sp_cyp_problem), _u32, P(_vp), P(ffi.sp_cyp_call), _s, _u32, P(ffi.sp_cyp_region_variants),
                                                     P(sp_cyp_read_mapping), _u64, P(_u64), P(_i32)]),
+        "sp_hla_fasta_load": (_i32, [_s, _s, P(_vp)]),
+        "sp_hla_fasta_last_error": (_s, []),
+        "sp_hla_alleles_free": (None, [_vp]),
+        "sp_hla_alleles_info": (_i32, [_vp, P(sp_hla_alleles_stats)]),
+        "sp_hla_alleles_get": (_i32, [_vp, _u32, P(_s), P(_s), P(_s), P(_s), P(_s)]),
+        "sp_hla_config_extend": (_i32, [_vp, _vp, _vp, _vp, _u32, P(_vp)]),
+        "sp_hla_config_result_create": (_i32, [_u32, P(_s), P(_u64), P(_u64), P(_vp)]),
+        "sp_hla_config_result_free": (None, [_vp]),
+        "sp_hla_config_result_info": (_i32, [_vp, P(_u32), P(_u32), P(_s)]),
+        "sp_hla_config_result_gene": (_i32, [_vp, _u32, P(sp_hla_cfg_gene)]),
+        "sp_hla_config_result_mapping": (_i32, [_vp, _u32, P(sp_hla_cfg_mapping)]),
+        "sp_database_save_hla": (_i32, [_vp, _vp, _vp, _s, _s]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
+    for t in (sp_hla_alleles_stats, sp_hla_cfg_mapping, sp_hla_cfg_gene):
+        if L.sp_struct_size(t.__name__.encode()) != C.sizeof(t):
+            raise ImportError(f"{t.__name__} is {L.sp_struct_size(t.__name__.encode())} bytes in the library, {C.sizeof(t)} in this binding")
     _bound = True
     return L
 
@@ -270,6 +298,129 @@ class Database:
 
     def variant_gene(self, gene_name, chrom_seq=None):
         return VariantGene(self, gene_name, chrom_seq)
+
+    def save_hla(self, alleles, result, hla_version, out_path):
+        """sp_database_save_hla: this database with hla_sequences = `alleles` (HlaAlleles), hla_config = the genes of `result` (HlaConfigResult) and
+        database_metadata.hla_version = hla_version, written to out_path (gzip when it ends in .gz)"""
+        self._check(_lib().sp_database_save_hla(self._h, alleles._h, result._h, _b(hla_version), _b(out_path)))
+
+
+class HlaAlleles:
+    """sp_hla_alleles: the allele table of an IMGT/HLA release (hla_gen.fasta + hla_nuc.fasta, plain or gzip), in id order."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def load(cls, gen, nuc):
+        h = _vp()
+        rc = _lib().sp_hla_fasta_load(_b(gen), _b(nuc), C.byref(h))
+        if rc != SP_OK:
+            raise StarphaseError(rc, _lib().sp_hla_fasta_last_error().decode())
+        return cls(h)
+
+    def close(self):
+        if self._h:
+            _lib().sp_hla_alleles_free(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def stats(self):
+        """dict(n_alleles, n_dna, n_dropped_no_cdna, n_dropped_gene, warnings)"""
+        s = sp_hla_alleles_stats()
+        rc = _lib().sp_hla_alleles_info(self._h, C.byref(s))
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_hla_alleles_info")
+        return dict(n_alleles=s.n_alleles, n_dna=s.n_dna, n_dropped_no_cdna=s.n_dropped_no_cdna, n_dropped_gene=s.n_dropped_gene, warnings=s.warnings.decode())
+
+    def __len__(self):
+        return self.stats["n_alleles"]
+
+    def allele(self, i):
+        """dict(hla_id, gene_name, star_allele = list of fields, dna_sequence = str or None, cdna_sequence): HlaAlleleDefinition"""
+        a = [_s() for _ in range(5)]
+        rc = _lib().sp_hla_alleles_get(self._h, int(i), *[C.byref(x) for x in a])
+        if rc != SP_OK:
+            raise StarphaseError(rc, f"sp_hla_alleles_get({i})")
+        return dict(hla_id=a[0].value.decode(), gene_name=a[1].value.decode(), star_allele=a[2].value.decode().split(":"),
+                    dna_sequence=_d(a[3].value), cdna_sequence=a[4].value.decode())
+
+    def table(self):
+        """{hla_id: allele}: the database's hla_sequences"""
+        return {a["hla_id"]: a for a in (self.allele(i) for i in range(len(self)))}
+
+
+class HlaConfigResult:
+    """sp_hla_config_result: what Context.hla_config_extend found (or a hand-made one: HlaConfigResult.make)."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def make(cls, genes):
+        """genes: [(name, start, end)]"""
+        n = len(genes)
+        names = ffi._strs([g[0] for g in genes])
+        start, end = (_u64 * max(1, n))(*[g[1] for g in genes]), (_u64 * max(1, n))(*[g[2] for g in genes])
+        h = _vp()
+        rc = _lib().sp_hla_config_result_create(n, names, start, end, C.byref(h))
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_hla_config_result_create")
+        return cls(h)
+
+    def close(self):
+        if self._h:
+            _lib().sp_hla_config_result_free(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _info(self):
+        n, m, w = _u32(), _u32(), _s()
+        rc = _lib().sp_hla_config_result_info(self._h, C.byref(n), C.byref(m), C.byref(w))
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_hla_config_result_info")
+        return n.value, m.value, w.value.decode()
+
+    @property
+    def warnings(self):
+        return self._info()[2]
+
+    def genes(self):
+        """per gene, name order: dict(name, chrom, start, end, moved, is_absent_capable, worst_allele (index or None), worst = (len, nm, unmapped), n_dna_alleles, n_mapped)"""
+        out = []
+        for g in range(self._info()[0]):
+            x = sp_hla_cfg_gene()
+            rc = _lib().sp_hla_config_result_gene(self._h, g, C.byref(x))
+            if rc != SP_OK:
+                raise StarphaseError(rc, "sp_hla_config_result_gene")
+            out.append(dict(name=x.name.decode(), chrom=x.chrom.decode(), start=x.start, end=x.end, moved=bool(x.moved), is_absent_capable=bool(x.is_absent_capable),
+                            worst_allele=x.worst_allele if x.worst_allele >= 0 else None,
+                            worst=(x.worst_len, x.worst_nm, x.worst_unmapped) if x.worst_allele >= 0 else None, n_dna_alleles=x.n_dna_alleles, n_mapped=x.n_mapped))
+        return out
+
+    def mappings(self):
+        """per allele of the table: None, or dict(rev, nm, q_start, q_end, t_start, t_end); `overflow` lists the alleles reported as none for the band / their length"""
+        out, self.overflow = [], []
+        for a in range(self._info()[1]):
+            m = sp_hla_cfg_mapping()
+            rc = _lib().sp_hla_config_result_mapping(self._h, a, C.byref(m))
+            if rc != SP_OK:
+                raise StarphaseError(rc, "sp_hla_config_result_mapping")
+            if m.status < 0:
+                self.overflow.append(a)
+            out.append(dict(rev=m.rev, nm=m.nm, q_start=m.q_start, q_end=m.q_end, t_start=m.t_start, t_end=m.t_end) if m.status == 1 else None)
+        return out
 
 
 class VariantGene:

@@ -417,6 +417,14 @@ class Context:
         self.check(lib().sp_affine_align_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), int(band), _ptr(out), _ptr(cigar), int(cigar_stride), _ptr(n_cigar)))
         return out, cigar, n_cigar
 
+    def hla_config_extend(self, reference, alleles, db=None, batch_alleles=0):
+        """sp_hla_config_extend: HlaConfig::new on the device -- reference = database.Fasta, alleles = database.HlaAlleles, db = database.Database whose hla_config
+        gives the starting genes (None: the HLA-A / HLA-B default) -> database.HlaConfigResult"""
+        from . import database
+        h = C.c_void_p()
+        self.check(database._lib().sp_hla_config_extend(self._h, reference._h, db._h if db is not None else None, alleles._h, int(batch_alleles), C.byref(h)))
+        return database.HlaConfigResult(h)
+
     def info(self):
         """sp_ctx_get_info -> dict(device, num_cus, hw_queues, hw_queues_set_by_library, warning)"""
         st = sp_ctx_info()
