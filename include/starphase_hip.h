@@ -219,6 +219,30 @@ int32_t sp_affine_rescore_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
 int32_t sp_affine_align_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts,
                               int32_t band, sp_affine_aln* out, uint32_t* cigar, uint32_t cigar_stride, uint32_t* n_cigar);
 
+/* ------------------------------------------------------------------ pileup: many alignments -> counts per target column
+ * The reduction a person does by eye on a pile of reads under a sequence.  pairs / aln / cigar / cigar_stride / n_cigar are what sp_affine_align_batch (or
+ * sp_hla_realign_cigars) returned for the same pairs on the same sets (a = query in A, b = target in B; same encoding, same stride convention).  For target t of B,
+ * out[col_offset[t] + j] is column j of t over all pairs that name t (col_offset: n_targets + 1 entries, col_offset[0] = 0 and col_offset[t + 1] - col_offset[t] = the
+ * length of t, so out has col_offset[n_targets] entries):
+ *   depth  pairs whose alignment has an '=', 'X' or 'D' op on column j        eq / del  the '=' / the 'D' ones of those
+ *   x[c]   the 'X' ones whose query base on that column has the 2-bit code c (A C G T = 0 1 2 3) as the packed set holds it: a base outside ACGT is stored with
+ *          code 0 (the set's N plane is not consulted), so an 'X' column facing an N of the query counts under x[0]
+ *   ins    pairs with an 'I' op between column j and j + 1: one per op, not per base
+ * so depth == eq + x[0] + x[1] + x[2] + x[3] + del on every column.  A pair with n_cigar 0 contributes nothing; a target no pair names is all zeros.
+ * Every argument is checked on the host before anything is launched or written: an index out of range, spans outside the sequences, ops that do not consume exactly the
+ * spans of aln (the rule of sp_affine_cigar_strings; a row cut off at cigar_stride is such a case), an op other than = X I D, a run of length 0, or an 'I' op before the
+ * alignment's first target column (no traceback of this library has one) return SP_ERR_INVALID_ARG.
+ * Kernel: the pairs are bucketed by target on the host; one workgroup of SP_PILEUP_WAVES waves per (target, tile of SP_PILEUP_TILE columns) keeps the tile's counters in
+ * LDS (one plane per field, so the lanes of a run land on different banks); its waves take the target's pairs in turn, 64 ops at a time: a wave-wide prefix sum gives
+ * every op its first target column and query base, ops that miss the tile are skipped, the others add to LDS (long runs with the lanes across columns); query bases are
+ * read for 'X' ops only; the tile leaves with plain coalesced stores.  No global atomics, and integer counts in any order are exact: the result does not depend on the
+ * order of the pairs or on launch geometry.  Device memory: pooled buffers of the context (no allocation on a warm context). */
+#define SP_PILEUP_TILE  2048
+#define SP_PILEUP_WAVES 4
+typedef struct { uint32_t depth, eq, x[4], del, ins; } sp_pileup_col;   /* 32 bytes */
+int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
+                        const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset, sp_pileup_col* out);
+
 /* ------------------------------------------------------------------ HLA database
  * Replaces HlaRealigner::new + create_hla_fasta (src/hla/realigner.rs:42-91,497-526) and the per-call
  * one-sequence indexes of score_read (src/hla/caller.rs:1370-1379).
@@ -885,6 +909,47 @@ int32_t sp_hla_diplotype_cohort_samples(sp_ctx* ctx, const sp_hla_db* db, uint32
                                         const sp_seqset* reads, const sp_hla_realign* realign, const sp_hla_call_config* cfgs, sp_hla_call* calls,
                                         char* cons, uint32_t cap, uint8_t* is_cons1);
 
+/* ------------------------------------------------------------------ consensus support: how well the member reads back each consensus of a gene call
+ * An output of this library's own (the reference has no such table: its users open debug_consensus.bam in IGV and look at the pile of reads under each consensus base;
+ * this hands out the integers they read off that picture, not the picture).  Arguments as sp_hla_diplotype_gene took and returned them.  Members of consensus 1 / 2 are
+ * the realigned reads of the gene (realign[r].status == 0 and .gene == gene) with is_cons1[r] != 0 / == 0.  Query: the read's DNA segment [seg_start, seg_end), the one
+ * the group consensus was built from, put on the gene strand (reverse-complemented for a reverse-strand gene).  Target: the gene-strand DNA consensus (cons as given
+ * for a forward gene, its reverse complement otherwise: sp_hla_map_consensus_seq's level 1).  Alignment: sp_affine_align_batch at the map-hifi scores {1, 4, 6, 2, 26,
+ * 1, 1} on the diagonal the anchor gives -- sp_anchor_batch(A = the consensuses, B = the segments) votes for (segment position - consensus position), the pair's diag
+ * is its negation -- on 64 diagonals, and once more on 256 when that found nothing (score 0).  A member without an anchor (0 votes) or without an alignment on either
+ * band is counted in n_unaligned and left out; it is not an error.  cols1 / cols2: strlen(cons1) / strlen(cons2) columns of sp_pileup_batch over the aligned members
+ * (gene-strand coordinates); an empty consensus gets a zeroed summary.  Either pair of outputs may be NULL.
+ * sp_support_summary: length = columns; min_depth and median_depth (the lower median: element (length - 1) / 2 of the sorted depths) over all columns; n_contested
+ * columns are contested: 2 * eq <= depth with depth > 0 (the consensus base lacks a strict majority of the spanning members) or 2 * ins > depth (an insertion
+ * behind the column has one).  The rule has no parameter.  sp_support_summarize / sp_support_contested apply it to any table (host only).
+ * sp_hla_consensus_support_cohort: every (sample, gene) unit of sp_hla_diplotype_cohort_samples in one pass -- one segment set, one anchor launch, one alignment
+ * launch per band, one pileup launch.  cons / is_cons1 as that call returned them; read_sample NULL = one sample.  unit_on (optional, n_samples * n_genes): 0 skips a
+ * unit (its consensuses get no columns and zeroed summaries).  col_offset (n_samples * n_genes * 2 + 1 entries, always filled): consensus c of unit u owns
+ * cols[col_offset[2u + c] .. col_offset[2u + c + 1]); SP_ERR_CAPACITY when col_offset[last] > cols_cap (nothing else is written: call again with more room).
+ * summaries: n_samples * n_genes * 2. */
+typedef struct { uint32_t n_members, n_aligned, n_unaligned, length, min_depth, median_depth, n_contested, reserved_; } sp_support_summary;   /* 32 bytes */
+int32_t sp_support_summarize(const sp_pileup_col* cols, uint32_t length, uint32_t n_members, uint32_t n_aligned, sp_support_summary* out);
+/* the contested columns in ascending order: pos holds cap entries, *n = how many there are (SP_ERR_CAPACITY when more than cap) */
+int32_t sp_support_contested(const sp_pileup_col* cols, uint32_t length, uint32_t* pos, uint32_t cap, uint32_t* n);
+int32_t sp_hla_consensus_support(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1,
+                                 const char* cons1, const char* cons2, sp_pileup_col* cols1, sp_pileup_col* cols2, sp_support_summary* s1, sp_support_summary* s2);
+int32_t sp_hla_consensus_support_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
+                                        const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1, const char* cons, uint32_t cap,
+                                        const uint8_t* unit_on, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries);
+/* `consensus_support.json` (host only; the layout of the other debug files: two-space indent).  One entry per gene; the file is keyed by gene in name order, then by
+ * "consensus1" / "consensus2" (a consensus whose `consensus` is NULL or empty is left out, a gene with neither is omitted).  Each holds n_members, n_aligned,
+ * n_unaligned, length, min_depth, median_depth, n_contested, typed_allele (NULL: null) and contested = [{pos, depth, eq, x: [a, c, g, t], del, ins, consensus_base}]
+ * for the contested columns of cols (pos 0-based on the gene-strand consensus, consensus_base its letter).  The full table stays behind the API.
+ * out / cap / needed as sp_cyp_alleles_json. */
+typedef struct {
+    const char* gene;
+    const char* typed_allele[2];        /* the star string of the call for each consensus */
+    const char* consensus[2];           /* gene-strand DNA consensus, NUL-terminated; its length must be summary[c]->length */
+    const sp_pileup_col* cols[2];
+    const sp_support_summary* summary[2];
+} sp_support_entry;
+int32_t sp_consensus_support_json(const sp_support_entry* entries, uint32_t n_entries, char* out, uint64_t cap, uint64_t* needed);
+
 /* ------------------------------------------------------------------ host-side decisions of the path (no device work)
  * Small scalar routines the reference evaluates between the kernels; kept behind the same ABI so a host can drop the whole
  * path in.  statrs 0.16 formulas (Binomial::cdf / ln_pmf, Normal::ln_pdf, ln_factorial). */
@@ -1268,6 +1333,16 @@ int32_t sp_starphase_set_read_debug(sp_starphase* handle, int32_t enable);
  * sp_hla_map_type_consensus (out of memory; an allele whose alignment has more than 4,096 runs, SP_ERR_CAPACITY) fails the pass -- in a batch the group then goes
  * through it once more sample by sample, as for every other failure of a shared pass, and only the samples whose own map fails are failed. */
 int32_t sp_starphase_set_hla_debug_mappings(sp_starphase* handle, int32_t on);
+/* consensus_support.json, off by default (on 0): with the switch on, a call with a debug folder also writes <folder>/consensus_support.json (sp_consensus_support_json
+ * above): keyed by gene in name order, then "consensus1" / "consensus2" (the second for a dual call only, as in hla_debug.json), each with the fields of
+ * sp_support_summary, typed_allele (the star string of the call's typed allele, "HLA-A*01:01:01:01", or null) and the contested columns; genes without a call (no
+ * realigned reads) are omitted: a sample whose BAMs hold no HLA read writes {}, a sample without BAMs has no HLA pass and gets none of its debug files.  The tables are sp_hla_consensus_support_cohort's over the reads, records, is_cons1 and
+ * consensuses of the call itself; the full per-column table stays behind the API.  The pass runs once per group of a batch, over the samples of the group that
+ * have a debug folder; each sample's file equals its single call's file.  With the switch off no kernel is launched, no pool memory is taken and every output is the
+ * same bytes; with it on, every other output is still the same bytes.  A failure of the support pass fails the HLA pass, like the K2 map above: the switch can turn a
+ * call that succeeds into one that fails (out of memory; an alignment of more than 4,096 runs, SP_ERR_CAPACITY) -- in a batch the group then goes through the pass
+ * once more sample by sample, and only the samples whose own pass fails are failed.  CYP2D6 consensuses are not covered. */
+int32_t sp_starphase_set_consensus_support(sp_starphase* handle, int32_t on);
 const char* sp_starphase_warnings(const sp_starphase* handle);      /* the warnings of the last call, one per line */
 /* where the last call spent its time (wall ms): whole call, BAM decode (host, both loci), variant genes, HLA lane, CYP2D6 lane */
 typedef struct { double call_ms, bam_decode_ms, variant_ms, hla_ms, cyp_ms; uint32_t n_hla_reads, n_cyp_reads; } sp_starphase_timing;

@@ -14,6 +14,8 @@ pub const SP_NO_DIAG: i64 = -2147483648;
 pub const SP_EV_X: i64 = 0;
 pub const SP_EV_D: i64 = 1;
 pub const SP_EV_I: i64 = 2;
+pub const SP_PILEUP_TILE: i64 = 2048;
+pub const SP_PILEUP_WAVES: i64 = 4;
 pub const SP_K1_SEL: i64 = 16;
 pub const SP_MAX_CHAIN: i64 = 64;
 pub const SP_CYP_MAXCONS: i64 = 64;
@@ -64,6 +66,14 @@ pub struct sp_affine_aln {
     pub a_end: i32,
     pub b_start: i32,
     pub b_end: i32,
+}
+#[repr(C)]
+pub struct sp_pileup_col {
+    pub depth: u32,
+    pub eq: u32,
+    pub x: [u32; 4],
+    pub del: u32,
+    pub ins: u32,
 }
 #[repr(C)]
 pub struct sp_hla_db_desc {
@@ -481,6 +491,25 @@ pub struct sp_hla_call {
     pub cdf: f64,
 }
 #[repr(C)]
+pub struct sp_support_summary {
+    pub n_members: u32,
+    pub n_aligned: u32,
+    pub n_unaligned: u32,
+    pub length: u32,
+    pub min_depth: u32,
+    pub median_depth: u32,
+    pub n_contested: u32,
+    pub reserved_: u32,
+}
+#[repr(C)]
+pub struct sp_support_entry {
+    pub gene: *const c_char,
+    pub typed_allele: [*const c_char; 2],
+    pub consensus: [*const c_char; 2],
+    pub cols: [*const sp_pileup_col; 2],
+    pub summary: [*const sp_support_summary; 2],
+}
+#[repr(C)]
 pub struct sp_chain_build_info {
     pub n_reads: u32,
     pub n_chains: u32,
@@ -734,6 +763,7 @@ extern "C" {
     pub fn sp_align_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, out: *mut sp_aln, events: *mut u32, events_stride: u32) -> i32;
     pub fn sp_affine_rescore_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, band: i32, out: *mut sp_affine_aln) -> i32;
     pub fn sp_affine_align_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, band: i32, out: *mut sp_affine_aln, cigar: *mut u32, cigar_stride: u32, n_cigar: *mut u32) -> i32;
+    pub fn sp_pileup_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, aln: *const sp_affine_aln, cigar: *const u32, cigar_stride: u32, n_cigar: *const u32, col_offset: *const u64, out: *mut sp_pileup_col) -> i32;
     pub fn sp_hla_db_create(ctx: *mut sp_ctx, desc: *const sp_hla_db_desc, out: *mut *mut sp_hla_db) -> i32;
     pub fn sp_hla_db_free(db: *mut sp_hla_db);
     pub fn sp_hla_seed_index_info(ctx: *mut sp_ctx, db: *const sp_hla_db, out: *mut i64) -> i32;
@@ -788,6 +818,11 @@ extern "C" {
     pub fn sp_hla_diplotype_genes(ctx: *mut sp_ctx, db: *const sp_hla_db, n_genes: u32, genes: *const u32, reads: *const sp_seqset, realign: *const sp_hla_realign, cfgs: *const sp_hla_call_config, calls: *mut sp_hla_call, cons: *mut c_char, cap: u32, is_cons1: *mut u8) -> i32;
     pub fn sp_hla_diplotype_cohort(ctx: *mut sp_ctx, db: *const sp_hla_db, n_samples: u32, read_sample: *const u32, n_genes: u32, genes: *const u32, reads: *const sp_seqset, realign: *const sp_hla_realign, cfgs: *const sp_hla_call_config, calls: *mut sp_hla_call, cons: *mut c_char, cap: u32, is_cons1: *mut u8) -> i32;
     pub fn sp_hla_diplotype_cohort_samples(ctx: *mut sp_ctx, db: *const sp_hla_db, n_samples: u32, read_sample: *const u32, n_genes: u32, genes: *const u32, reads: *const sp_seqset, realign: *const sp_hla_realign, cfgs: *const sp_hla_call_config, calls: *mut sp_hla_call, cons: *mut c_char, cap: u32, is_cons1: *mut u8) -> i32;
+    pub fn sp_support_summarize(cols: *const sp_pileup_col, length: u32, n_members: u32, n_aligned: u32, out: *mut sp_support_summary) -> i32;
+    pub fn sp_support_contested(cols: *const sp_pileup_col, length: u32, pos: *mut u32, cap: u32, n: *mut u32) -> i32;
+    pub fn sp_hla_consensus_support(ctx: *mut sp_ctx, db: *const sp_hla_db, gene: u32, reads: *const sp_seqset, realign: *const sp_hla_realign, is_cons1: *const u8, cons1: *const c_char, cons2: *const c_char, cols1: *mut sp_pileup_col, cols2: *mut sp_pileup_col, s1: *mut sp_support_summary, s2: *mut sp_support_summary) -> i32;
+    pub fn sp_hla_consensus_support_cohort(ctx: *mut sp_ctx, db: *const sp_hla_db, n_samples: u32, read_sample: *const u32, n_genes: u32, genes: *const u32, reads: *const sp_seqset, realign: *const sp_hla_realign, is_cons1: *const u8, cons: *const c_char, cap: u32, unit_on: *const u8, col_offset: *mut u64, cols: *mut sp_pileup_col, cols_cap: u64, summaries: *mut sp_support_summary) -> i32;
+    pub fn sp_consensus_support_json(entries: *const sp_support_entry, n_entries: u32, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
     pub fn sp_hla_is_passing_dual(counts1: u64, counts2: u64, min_consensus_fraction: f64, expected_maf: f64, min_cdf: f64, maf_out: *mut f64, cdf_out: *mut f64) -> i32;
     pub fn sp_hla_is_hemizygous_better(scores1: *const i64, scores2: *const i64, is_consensus1: *const u8, n_reads: u32, is_dual: i32, dual_max_ed_delta: u64, normalized_coverage: f64, haploid_cost: *mut f64, diploid_cost: *mut f64) -> i32;
     pub fn sp_hla_normalized_coverage(realign: *const sp_hla_realign, n_reads: u32, normalizing_genes: *const u32, n_normalizing: u32, normalized_coverage: *mut f64) -> i32;
@@ -886,6 +921,7 @@ extern "C" {
     pub fn sp_starphase_call(handle: *mut sp_starphase, inputs: *const sp_sample_inputs, out: *mut *mut sp_result) -> i32;
     pub fn sp_starphase_set_read_debug(handle: *mut sp_starphase, enable: i32) -> i32;
     pub fn sp_starphase_set_hla_debug_mappings(handle: *mut sp_starphase, on: i32) -> i32;
+    pub fn sp_starphase_set_consensus_support(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_warnings(handle: *const sp_starphase) -> *const c_char;
     pub fn sp_starphase_last_timing(handle: *const sp_starphase, out: *mut sp_starphase_timing) -> i32;
     pub fn sp_starphase_call_batch(handle: *mut sp_starphase, n: u32, inputs: *const sp_sample_inputs, debug_folders: *const *const c_char, opts: *const sp_batch_options, out: *mut *mut sp_result, sample_rc: *mut i32) -> i32;

@@ -181,6 +181,9 @@ int32_t sp_struct_size(const char* name) {
     SP_SZ(sp_hla_alleles_stats)
     SP_SZ(sp_hla_cfg_mapping)
     SP_SZ(sp_hla_cfg_gene)
+    SP_SZ(sp_pileup_col)
+    SP_SZ(sp_support_summary)
+    SP_SZ(sp_support_entry)
 #undef SP_SZ
     return -1;
 }

@@ -117,6 +117,7 @@ struct sp_starphase {
     sp_diplotype_settings s{};
     std::string include_set, exclude_set, sample_name, sv_vcf, debug_folder;
     int32_t read_debug = 0;                          // sp_starphase_set_read_debug: a debug folder also receives read_debug.json
+    int32_t consensus_support = 0;                   // sp_starphase_set_consensus_support: a debug folder also receives consensus_support.json
     int32_t hla_debug_mappings = 0;                  // sp_starphase_set_hla_debug_mappings: hla_debug.json carries the mapping of each consensus against every allowed allele
     std::set<std::string> include, exclude; bool has_include = false, has_exclude = false;
     // chromosomes the variant genes were normalised against (sp_variant_gene keeps a pointer)
@@ -571,12 +572,53 @@ int32_t hla_debug_mappings_add(sp_starphase* h, sp_hla_debug* dbg, const std::st
     return SP_OK;
 }
 
+// consensus_support.json of one sample (sp_starphase_set_consensus_support): the tables of the group's one support pass that belong to this sample.  off / sm are
+// indexed by gene * 2 + consensus; cons holds the sample's hg38-forward consensuses, cap bytes each.  A sample without reads has no view and writes an empty object.
+struct SupportView { const uint64_t* off; const sp_pileup_col* cols; const sp_support_summary* sm; const char* cons; uint32_t cap; };
+int32_t consensus_support_save(sp_starphase* h, const sp_hla_call* calls, const SupportView* view, const std::string& debug_folder, std::string& err) {
+    const size_t G = h->hgenes.size();
+    std::vector<sp_support_entry> entries; std::vector<std::string> keep; keep.reserve(G * 4);
+    for (size_t g = 0; view && g < G; ++g) {
+        if (calls[g].status == 1) continue;
+        sp_support_entry en; std::memset(&en, 0, sizeof en);
+        en.gene = h->hgenes[g].name.c_str();
+        for (int k = 0; k < 2; ++k) {
+            if (k == 1 && !calls[g].is_dual) continue;
+            const uint64_t lo = view->off[g * 2 + k], hi = view->off[g * 2 + k + 1];
+            if (hi == lo) continue;
+            const char* fwd = view->cons + (g * 2 + k) * (size_t)view->cap;
+            std::string strand(fwd, (size_t)(hi - lo));
+            if (!spi_hla_gene_fwd(h->hla, (uint32_t)g)) {
+                std::reverse(strand.begin(), strand.end());
+                for (char& c : strand) c = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 'N';
+            }
+            keep.push_back(std::move(strand)); en.consensus[k] = keep.back().c_str();
+            const int32_t t = k ? calls[g].typed2 : calls[g].typed1;
+            if (t >= 0) { keep.push_back(h->hgenes[h->a_gene[t]].name + "*" + h->a_star[t]); en.typed_allele[k] = keep.back().c_str(); }
+            en.cols[k] = view->cols + lo; en.summary[k] = view->sm + g * 2 + k;
+        }
+        entries.push_back(en);
+    }
+    uint64_t need = 0;
+    int32_t rc = sp_consensus_support_json(entries.data(), (uint32_t)entries.size(), nullptr, 0, &need);
+    if (rc != SP_OK && rc != SP_ERR_CAPACITY) { err = "consensus_support.json: the tables do not fit their consensuses"; return rc; }
+    std::string text((size_t)need, '\0');
+    rc = sp_consensus_support_json(entries.data(), (uint32_t)entries.size(), &text[0], need, &need);
+    if (rc != SP_OK) { err = "consensus_support.json: the tables do not fit their consensuses"; return rc; }
+    const std::string path = debug_folder + "/consensus_support.json";
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f || std::fwrite(text.data(), 1, (size_t)need - 1, f) != (size_t)need - 1) { if (f) std::fclose(f); err = "Error while writing " + path; return SP_ERR_INVALID_ARG; }
+    std::fclose(f);
+    return SP_OK;
+}
+
 // the HLA entries of one sample: PgxMappingDetails of every read, the diplotypes, hla_debug.json.  rec / rev: by position in QNAME order; rev[k].allele
 // >= 0 names the reverse-strand mapping a read was dropped for (src/hla/realigner.rs:178-193)
 int32_t hla_package(sp_starphase* h, const std::vector<Read4>& reads, const std::vector<uint32_t>& searched, const std::vector<uint32_t>& order,
                     const sp_hla_realign* rec, const sp_hla_rev_hit* rev, const sp_hla_call* calls, const std::string& debug_folder,
                     std::vector<Entry>& out, std::string& err, const ReadCigars* cigars, uint32_t cigars_first,
-                    const sp_hla_map* maps = nullptr, const int32_t* map_item = nullptr, std::string* warnings = nullptr) {
+                    const sp_hla_map* maps = nullptr, const int32_t* map_item = nullptr, std::string* warnings = nullptr,
+                    bool want_support = false, const SupportView* support = nullptr) {
     const size_t G = h->hgenes.size();
     // PgxMappingDetails of every read, in the order the loop met them, in the bucket of its gene (realigned) or of the gene searched (ignored)
     std::vector<std::unique_ptr<GeneDetailsPtr>> det(G);
@@ -640,6 +682,7 @@ int32_t hla_package(sp_starphase* h, const std::vector<Read4>& reads, const std:
         sp_hla_debug_free(dbg);
         if (rc != SP_OK) { err = "Error while writing " + path; return rc; }
         if (cigars) { const int32_t rd = read_debug_save(h, reads, pos_of, rec, *cigars, cigars_first, debug_folder, err); if (rd != SP_OK) return rd; }
+        if (want_support) { const int32_t rs = consensus_support_save(h, calls, support, debug_folder, err); if (rs != SP_OK) return rs; }
     }
     return SP_OK;
 }
@@ -800,6 +843,10 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
     bool want_maps = false;                                          // likewise one batched map of the group's consensuses
     for (Sample* b : with) want_maps |= h->hla_debug_mappings && !b->debug.empty();
     HlaMaps maps; std::vector<int32_t> map_item(with.size() * G * 2, -1);
+    bool want_support = false;                                       // likewise one support pass (anchor, alignment, pileup) over the group's consensuses
+    for (Sample* b : with) want_support |= h->consensus_support && !b->debug.empty();
+    std::vector<uint8_t> is1; std::vector<uint64_t> sup_off; std::vector<sp_pileup_col> sup_cols; std::vector<sp_support_summary> sup_sm;
+    std::vector<int32_t> cohort_of(with.size(), -1);                 // a sample's place among the samples with reads
     if (R) {
         sp_seqset* set = nullptr;
         int32_t rc = upload_reads(h->ctx, parts, &set);
@@ -813,6 +860,7 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
         for (size_t k = 0; k < with.size(); ++k) {
             if (first[k + 1] == first[k]) continue;
             for (uint32_t r = first[k]; r < first[k + 1]; ++r) read_sample[r] = (uint32_t)at.size();
+            cohort_of[k] = (int32_t)at.size();
             at.push_back((uint32_t)k);
             cfg.resize(at.size() * G);
             hla_configs(h, rec.data() + first[k], first[k + 1] - first[k], cfg.data() + (at.size() - 1) * G);
@@ -822,12 +870,31 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
         std::vector<sp_hla_call> cc(at.size() * G);
         const size_t need = at.size() * G * 2 * (size_t)cap;
         if (h->hla_cons.size() < need) h->hla_cons.resize(need);
-        rc = at.size() == 1 ? sp_hla_diplotype_genes(h->ctx, h->hla, (uint32_t)G, genes.data(), set, rec.data(), cfg.data(), cc.data(), h->hla_cons.data(), cap, nullptr)
+        if (want_support) is1.assign(R, 0);
+        uint8_t* is1_out = want_support ? is1.data() : nullptr;
+        rc = at.size() == 1 ? sp_hla_diplotype_genes(h->ctx, h->hla, (uint32_t)G, genes.data(), set, rec.data(), cfg.data(), cc.data(), h->hla_cons.data(), cap, is1_out)
                             : sp_hla_diplotype_cohort_samples(h->ctx, h->hla, (uint32_t)at.size(), read_sample.data(), (uint32_t)G, genes.data(), set, rec.data(),
-                                                              cfg.data(), cc.data(), h->hla_cons.data(), cap, nullptr);
+                                                              cfg.data(), cc.data(), h->hla_cons.data(), cap, is1_out);
         if (rc != SP_OK) { err = "sp_hla_diplotype_genes: " + opt(sp_last_error(h->ctx)); return rc; }
         for (size_t x = 0; x < at.size(); ++x) std::copy(cc.begin() + x * G, cc.begin() + (x + 1) * G, calls.begin() + (size_t)at[x] * G);
         if (want_cigars) { rc = read_cigars(h, set, rec.data(), R, &cigars, err); if (rc != SP_OK) return rc; }
+        // consensus_support.json: the member reads of every called gene of the samples that have a debug folder, piled under their consensuses in one pass
+        if (want_support) {
+            std::vector<uint8_t> unit_on(at.size() * G, 0);
+            uint64_t n_cols = 0;
+            for (size_t x = 0; x < at.size(); ++x) {
+                if (with[at[x]]->debug.empty()) continue;
+                for (size_t g = 0; g < G; ++g) {
+                    if (cc[x * G + g].status == 1) continue;
+                    unit_on[x * G + g] = 1;
+                    for (int k = 0; k < 2; ++k) n_cols += strnlen(h->hla_cons.data() + ((x * G + g) * 2 + k) * (size_t)cap, cap);
+                }
+            }
+            sup_off.assign(at.size() * G * 2 + 1, 0); sup_cols.resize((size_t)n_cols + 1); sup_sm.resize(at.size() * G * 2);
+            rc = sp_hla_consensus_support_cohort(h->ctx, h->hla, (uint32_t)at.size(), read_sample.data(), (uint32_t)G, genes.data(), set, rec.data(), is1.data(),
+                                                 h->hla_cons.data(), cap, unit_on.data(), sup_off.data(), sup_cols.data(), n_cols, sup_sm.data());
+            if (rc != SP_OK) { err = "sp_hla_consensus_support: " + opt(sp_last_error(h->ctx)); return rc; }
+        }
         // the per-allele mappings of hla_debug.json: every consensus of the samples that have a debug folder, in one batched map
         if (want_maps) {
             std::vector<uint32_t> mg, ml, where; std::vector<const char*> mc;
@@ -856,8 +923,12 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
     for (size_t k = 0; k < with.size(); ++k) {
         Sample* b = with[k];
         std::string e;
+        SupportView sv{};
+        const bool sup = want_support && cohort_of[k] >= 0 && !sup_off.empty();
+        if (sup) { const size_t x = (size_t)cohort_of[k]; sv = SupportView{ sup_off.data() + x * G * 2, sup_cols.data(), sup_sm.data() + x * G * 2, h->hla_cons.data() + x * G * 2 * (size_t)cap, cap }; }
         const int32_t rc = hla_package(h, b->hreads, b->hsearched, orders[k], rec.data() + first[k], rev.data() + first[k], calls.data() + k * G, b->debug, b->hla_entries, e,
-                                       want_cigars ? &cigars : nullptr, first[k], maps.map, maps.map ? map_item.data() + k * G * 2 : nullptr, &b->hwarn);
+                                       want_cigars ? &cigars : nullptr, first[k], maps.map, maps.map ? map_item.data() + k * G * 2 : nullptr, &b->hwarn,
+                                       h->consensus_support != 0, sup ? &sv : nullptr);
         if (rc != SP_OK) b->fail(2, rc, e);
     }
     return SP_OK;
@@ -956,6 +1027,11 @@ const char* sp_starphase_warnings(const sp_starphase* h) { return h ? h->warning
 int32_t sp_starphase_set_hla_debug_mappings(sp_starphase* h, int32_t on) {
     if (!h) return SP_ERR_INVALID_ARG;
     h->hla_debug_mappings = on ? 1 : 0;
+    return SP_OK;
+}
+int32_t sp_starphase_set_consensus_support(sp_starphase* h, int32_t on) {
+    if (!h) return SP_ERR_INVALID_ARG;
+    h->consensus_support = on ? 1 : 0;
     return SP_OK;
 }
 int32_t sp_starphase_set_read_debug(sp_starphase* h, int32_t enable) {

@@ -62,6 +62,8 @@ struct sp_hla_db {
     mutable std::mutex lazy;          // guards gene_lists and kdict: two contexts may type consensuses on one database at the same time
 };
 
+int spi_hla_gene_fwd(const sp_hla_db* db, uint32_t gene) { return gene < db->n_genes ? (db->gene_fwd[gene] ? 1 : 0) : -1; }
+
 // ---------------------------------------------------------------------------------------------
 // f64 score algebra (src/data_types/mapping.rs:60-84,191-195)
 __device__ __forceinline__ double score_value(int len, int nm, int unmapped) {

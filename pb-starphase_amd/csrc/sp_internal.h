@@ -225,6 +225,8 @@ struct ProfScope {
 int32_t spi_gene_entry_extras(const sp_database* db, const sp_variant_gene* g, std::string* reference_allele, bool* has_sv, std::string* sv_chrom);
 // sp_hla.hip, for sp_diplotype.hip: allele a of the database in hg38 orientation (the target of sp_hla_realign_cigars), ASCII; empty: no DNA sequence
 std::string spi_hla_allele_fwd(sp_ctx* ctx, const sp_hla_db* db, uint32_t a);
+// sp_hla.hip, for sp_pileup.hip: is_forward_strand of a gene of the database (1 / 0), -1: no such gene
+int spi_hla_gene_fwd(const sp_hla_db* db, uint32_t gene);
 // sp_hla.hip, for sp_diplotype.hip: sp_hla_map_type_consensus for n consensuses in one batched map; item_of[x] = the consensus that item x of the map is (those that place)
 int32_t spi_hla_map_type_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, const uint32_t* genes, const char* const* consensus_fwd, const uint32_t* consensus_len,
                                int32_t require_dna, int32_t disable_cdna, sp_hla_map** out, std::vector<uint32_t>* item_of);

@@ -1,0 +1,378 @@
+// sp_pileup.hip -- many alignments -> integer counts per target column (sp_pileup_batch), and what is built on it: the support of the consensuses of an HLA gene call
+// by their member reads (sp_hla_consensus_support*), its summary rule and the `consensus_support.json` debug file (host only).  Contract: include/starphase_hip.h;
+// design: DESIGN.md section 7.2.
+#include "sp_internal.h"
+#include "sp_json.h"
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <numeric>
+
+namespace {
+
+// one alignment as the kernel reads it, in bucket (target) order
+struct PuPair { uint64_t op_off; uint32_t a, n_ops; int32_t b_start, a_start; };      // 24 bytes
+struct PuTile { uint32_t target, c0; };
+
+constexpr int PU_TILE = SP_PILEUP_TILE, PU_WAVES = SP_PILEUP_WAVES;
+// The tile's counters live in LDS as one plane per field of sp_pileup_col, PU_STRIDE words apart: the lanes of a run add to consecutive words of one plane (one bank
+// each), and the 32 lanes of a half wave that writes the tile out (8 fields x 4 columns of the array-of-structs output) read bank 4 f + column: no two alike.
+// (Worked out from the bank rule -- 32 banks of 4 bytes for 4-byte LDS accesses -- not measured with the bank-conflict counter.)
+constexpr int PU_STRIDE = PU_TILE + 4;
+constexpr size_t PU_LDS_BYTES = (size_t)8 * PU_STRIDE * sizeof(uint32_t);              // 65,664 bytes: two workgroups per CU (160 KiB)
+constexpr int PU_SHORT = 8;                                                            // runs of up to this many columns are expanded by their own lane, longer ones by the wave
+enum { PU_DEPTH = 0, PU_EQ = 1, PU_X = 2, PU_DEL = 6, PU_INS = 7 };                    // plane = word of sp_pileup_col
+
+__device__ __forceinline__ uint32_t pu_query_code(const uint32_t* words, int q) { return (words[q >> 4] >> ((q & 15) << 1)) & 3u; }
+
+// one column of one run: op 7 '=', 8 'X', 2 'D'
+__device__ __forceinline__ void pu_add(uint32_t* lds, int col, uint32_t op, const uint32_t* qwords, int q) {
+    atomicAdd(&lds[PU_DEPTH * PU_STRIDE + col], 1u);
+    const int plane = op == 7u ? PU_EQ : op == 2u ? PU_DEL : PU_X + (int)pu_query_code(qwords, q);
+    atomicAdd(&lds[plane * PU_STRIDE + col], 1u);
+}
+
+__global__ __launch_bounds__(PU_WAVES * SP_WAVE) void pileup_kernel(SeqSetView A, const int32_t* __restrict__ t_len, const PuPair* __restrict__ pairs, const uint32_t* __restrict__ bucket_off,
+                                                                    const uint32_t* __restrict__ ops, const PuTile* __restrict__ tiles, const uint64_t* __restrict__ col_offset,
+                                                                    uint32_t* __restrict__ out) {
+    extern __shared__ uint32_t lds[];
+    const PuTile tile = tiles[blockIdx.x];
+    const int c0 = (int)tile.c0, c1 = min(c0 + PU_TILE, t_len[tile.target]);           // the tile's columns [c0, c1)
+    for (int i = threadIdx.x; i < 8 * PU_STRIDE; i += PU_WAVES * SP_WAVE) lds[i] = 0u;
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (uint32_t p = bucket_off[tile.target] + wave; p < bucket_off[tile.target + 1]; p += PU_WAVES) {
+        const PuPair pr = pairs[p];
+        const uint32_t* qwords = A.words + A.word_off[pr.a];
+        int tpos = pr.b_start, qpos = pr.a_start;                                      // first target column / query base of the chunk (wave-uniform)
+        for (uint32_t k0 = 0; k0 < pr.n_ops && tpos <= c1; k0 += SP_WAVE) {            // (an 'I' op at column c1 counts for column c1 - 1: <=)
+            const bool live = k0 + lane < pr.n_ops;
+            const uint32_t w = live ? ops[pr.op_off + k0 + lane] : 0u;
+            const uint32_t op = w & 15u; const int n = (int)(w >> 4);
+            const int tl = (op == 7u || op == 8u || op == 2u) ? n : 0, ql = (op == 7u || op == 8u || op == 1u) ? n : 0;
+            int ts = tl, qs = ql;                                                      // inclusive prefix sums over the chunk
+#pragma unroll
+            for (int d = 1; d < SP_WAVE; d <<= 1) {
+                const int u = __shfl_up(ts, d), v = __shfl_up(qs, d);
+                if (lane >= d) { ts += u; qs += v; }
+            }
+            const int t0 = tpos + ts - tl, q0 = qpos + qs - ql;                        // this op's first target column and query base
+            tpos += __shfl(ts, SP_WAVE - 1); qpos += __shfl(qs, SP_WAVE - 1);
+            if (live && op == 1u && t0 - 1 >= c0 && t0 - 1 < c1) atomicAdd(&lds[PU_INS * PU_STRIDE + (t0 - 1 - c0)], 1u);
+            const int lo = max(t0, c0), hi = min(t0 + tl, c1);                         // the op's columns inside the tile
+            const bool hit = live && tl > 0 && lo < hi;
+            if (hit && tl <= PU_SHORT) for (int c = lo; c < hi; ++c) pu_add(lds, c - c0, op, qwords, q0 + (c - t0));
+            unsigned long long longs = __ballot(hit && tl > PU_SHORT);
+            while (longs) {                                                            // long runs: the wave's lanes across the run's columns
+                const int src = __ffsll((long long)longs) - 1; longs &= longs - 1;
+                const int rlo = __shfl(lo, src), rhi = __shfl(hi, src), rt0 = __shfl(t0, src), rq0 = __shfl(q0, src);
+                const uint32_t rop = (uint32_t)__shfl((int)op, src);
+                for (int c = rlo + lane; c < rhi; c += SP_WAVE) pu_add(lds, c - c0, rop, qwords, rq0 + (c - rt0));
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t* dst = out + (col_offset[tile.target] + (uint64_t)c0) * 8u;                // the tile as an array of sp_pileup_col: consecutive threads, consecutive words
+    for (int i = threadIdx.x; i < (c1 - c0) * 8; i += PU_WAVES * SP_WAVE) dst[i] = lds[(i & 7) * PU_STRIDE + (i >> 3)];
+}
+
+static bool contested_col(const sp_pileup_col& c) { return (c.depth > 0 && 2ull * c.eq <= c.depth) || 2ull * c.ins > c.depth; }
+
+static std::string revcomp_str(const char* s, size_t n) {
+    std::string r(n, 'N');
+    for (size_t i = 0; i < n; ++i) {
+        char c = s[n - 1 - i];
+        switch (c) { case 'A': case 'a': c = 'T'; break; case 'C': case 'c': c = 'G'; break; case 'G': case 'g': c = 'C'; break; case 'T': case 't': c = 'A'; break; default: c = 'N'; }
+        r[i] = c;
+    }
+    return r;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
+                        const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset, sp_pileup_col* out) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (!A || !B || !col_offset || (n_pairs && (!pairs || !aln || !n_cigar))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: null argument");
+    if (n_pairs > 0xFFFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: too many pairs");
+    const uint32_t n_t = B->n;
+    if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset[0] must be 0");
+    for (uint32_t t = 0; t < n_t; ++t)
+        if (col_offset[t + 1] < col_offset[t] || col_offset[t + 1] - col_offset[t] != (uint64_t)B->h_len[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset does not follow the target lengths");
+    const uint64_t n_cols = col_offset[n_t];
+    if (n_cols && !out) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: null argument");
+    // ---- every alignment is walked here, before anything is launched or written: what the kernel indexes with is what this loop has seen
+    std::vector<uint32_t> bucket_off((size_t)n_t + 1, 0);
+    uint64_t total_ops = 0;
+    for (uint64_t i = 0; i < n_pairs; ++i) {
+        if (pairs[i].a >= A->n || pairs[i].b >= B->n) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: index out of range");
+        if (n_cigar[i] == 0) continue;
+        const std::string who = "pileup: pair " + std::to_string(i);
+        if (n_cigar[i] > cigar_stride || !cigar) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + " has more ops than its row holds");
+        const sp_affine_aln& g = aln[i];
+        if (g.b_start < 0 || g.b_end < g.b_start || g.b_end > B->h_len[pairs[i].b] || g.a_start < 0 || g.a_end < g.a_start || g.a_end > A->h_len[pairs[i].a])
+            return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": spans outside the sequences");
+        int64_t j = g.b_start, q = g.a_start;
+        const uint32_t* row = cigar + i * (size_t)cigar_stride;
+        for (uint32_t k = 0; k < n_cigar[i]; ++k) {
+            const uint32_t op = row[k] & 15u; const int64_t n = (int64_t)(row[k] >> 4);
+            if (n == 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": a run of length 0");
+            if (op == 7u || op == 8u) { j += n; q += n; }
+            else if (op == 2u) j += n;
+            else if (op == 1u) { if (j == g.b_start) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": an insertion before the first target column"); q += n; }
+            else return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": an op other than = X I D");
+            if (j > g.b_end || q > g.a_end) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": the ops do not consume the spans of its alignment");
+        }
+        if (j != g.b_end || q != g.a_end) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": the ops do not consume the spans of its alignment");
+        ++bucket_off[pairs[i].b + 1]; total_ops += n_cigar[i];
+    }
+    if (n_cols == 0) return SP_OK;
+    for (uint32_t t = 0; t < n_t; ++t) bucket_off[t + 1] += bucket_off[t];
+    const uint32_t n_live = bucket_off[n_t];
+    uint64_t n_tiles = 0;
+    for (uint32_t t = 0; t < n_t; ++t) n_tiles += ((uint64_t)B->h_len[t] + PU_TILE - 1) / PU_TILE;
+    if (n_tiles > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: too many tiles");
+    (void)hipSetDevice(ctx->device);
+    // ---- one staging block, one copy: pairs in bucket order, bucket offsets, tiles, column offsets, the ops back to back
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t at_pairs = 0, at_bucket = up16(at_pairs + sizeof(PuPair) * (size_t)n_live), at_tiles = up16(at_bucket + 4 * ((size_t)n_t + 1)),
+                 at_cols = up16(at_tiles + sizeof(PuTile) * (size_t)n_tiles), at_ops = up16(at_cols + 8 * ((size_t)n_t + 1)), in_bytes = up16(at_ops + 4 * (size_t)total_ops) + 16;
+    uint8_t* h_in = (uint8_t*)sp_host_pool(ctx, "pileup_in", in_bytes);
+    uint8_t* d_in = (uint8_t*)sp_pool(ctx, "pileup_in", in_bytes);
+    uint32_t* d_out = (uint32_t*)sp_pool(ctx, "pileup_out", n_cols * sizeof(sp_pileup_col));
+    if (!h_in || !d_in || !d_out) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "pileup buffers");
+    {
+        PuPair* hp = (PuPair*)(h_in + at_pairs); uint32_t* hops = (uint32_t*)(h_in + at_ops);
+        std::vector<uint32_t> at(bucket_off.begin(), bucket_off.end() - 1);
+        uint64_t op_at = 0;
+        for (uint64_t i = 0; i < n_pairs; ++i) {
+            if (n_cigar[i] == 0) continue;
+            hp[at[pairs[i].b]++] = PuPair{ op_at, pairs[i].a, n_cigar[i], aln[i].b_start, aln[i].a_start };
+            std::memcpy(hops + op_at, cigar + i * (size_t)cigar_stride, 4 * (size_t)n_cigar[i]);
+            op_at += n_cigar[i];
+        }
+        std::memcpy(h_in + at_bucket, bucket_off.data(), 4 * ((size_t)n_t + 1));
+        std::memcpy(h_in + at_cols, col_offset, 8 * ((size_t)n_t + 1));
+        PuTile* ht = (PuTile*)(h_in + at_tiles); uint64_t x = 0;
+        for (uint32_t t = 0; t < n_t; ++t) for (int32_t c0 = 0; c0 < B->h_len[t]; c0 += PU_TILE) ht[x++] = PuTile{ t, (uint32_t)c0 };
+    }
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    {   // more dynamic LDS than the 64 KiB a kernel gets unasked: said once per device of the process, not per call
+        static std::atomic<uint64_t> lds_set(0);
+        const uint64_t bit = 1ull << (ctx->device & 63);
+        if (!(lds_set.load() & bit)) {
+            SP_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)pileup_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PU_LDS_BYTES));
+            lds_set.fetch_or(bit);
+        }
+    }
+    {
+        ProfScope ps(ctx, "pileup", n_cols);
+        hipLaunchKernelGGL(pileup_kernel, dim3((unsigned)n_tiles), dim3(PU_WAVES * SP_WAVE), PU_LDS_BYTES, ctx->stream, A->view(), B->d_len, (const PuPair*)(d_in + at_pairs),
+                           (const uint32_t*)(d_in + at_bucket), (const uint32_t*)(d_in + at_ops), (const PuTile*)(d_in + at_tiles), (const uint64_t*)(d_in + at_cols), d_out);
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "pileup launch failed");
+    }
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(out, d_out, n_cols * sizeof(sp_pileup_col), hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return SP_OK;
+}
+
+int32_t sp_support_summarize(const sp_pileup_col* cols, uint32_t length, uint32_t n_members, uint32_t n_aligned, sp_support_summary* out) {
+    if (!out || (length && !cols) || n_aligned > n_members) return SP_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    out->n_members = n_members; out->n_aligned = n_aligned; out->n_unaligned = n_members - n_aligned; out->length = length;
+    if (length == 0) return SP_OK;
+    std::vector<uint32_t> depth(length);
+    for (uint32_t j = 0; j < length; ++j) { depth[j] = cols[j].depth; if (contested_col(cols[j])) ++out->n_contested; }
+    std::nth_element(depth.begin(), depth.begin() + (length - 1) / 2, depth.end());
+    out->median_depth = depth[(length - 1) / 2];
+    out->min_depth = *std::min_element(depth.begin(), depth.end());
+    return SP_OK;
+}
+
+int32_t sp_support_contested(const sp_pileup_col* cols, uint32_t length, uint32_t* pos, uint32_t cap, uint32_t* n) {
+    if (!n || (length && !cols) || (cap && !pos)) return SP_ERR_INVALID_ARG;
+    uint32_t k = 0;
+    for (uint32_t j = 0; j < length; ++j) if (contested_col(cols[j])) { if (k < cap) pos[k] = j; ++k; }
+    *n = k;
+    return k > cap ? SP_ERR_CAPACITY : SP_OK;
+}
+
+int32_t sp_consensus_support_json(const sp_support_entry* entries, uint32_t n_entries, char* out, uint64_t cap, uint64_t* needed) {
+    if ((n_entries && !entries) || (cap && !out)) return SP_ERR_INVALID_ARG;
+    std::vector<uint32_t> order;
+    for (uint32_t e = 0; e < n_entries; ++e) {
+        if (!entries[e].gene) return SP_ERR_INVALID_ARG;
+        for (int c = 0; c < 2; ++c) {
+            const char* s = entries[e].consensus[c];
+            if (!s || !*s) continue;
+            if (!entries[e].summary[c] || !entries[e].cols[c] || std::strlen(s) != entries[e].summary[c]->length) return SP_ERR_INVALID_ARG;
+        }
+        order.push_back(e);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return std::strcmp(entries[a].gene, entries[b].gene) < 0; });
+    spj::Value root = spj::object();
+    for (size_t o = 0; o < order.size(); ++o) {
+        const sp_support_entry& en = entries[order[o]];
+        if (o && std::strcmp(entries[order[o - 1]].gene, en.gene) == 0) return SP_ERR_INVALID_ARG;      // one entry per gene
+        spj::Value gene = spj::object();
+        for (int c = 0; c < 2; ++c) {
+            const char* s = en.consensus[c];
+            if (!s || !*s) continue;
+            const sp_support_summary& sm = *en.summary[c]; const sp_pileup_col* cols = en.cols[c];
+            spj::Value v = spj::object();
+            v.obj.emplace_back("n_members", spj::unum(sm.n_members)); v.obj.emplace_back("n_aligned", spj::unum(sm.n_aligned)); v.obj.emplace_back("n_unaligned", spj::unum(sm.n_unaligned));
+            v.obj.emplace_back("length", spj::unum(sm.length)); v.obj.emplace_back("min_depth", spj::unum(sm.min_depth)); v.obj.emplace_back("median_depth", spj::unum(sm.median_depth));
+            v.obj.emplace_back("n_contested", spj::unum(sm.n_contested));
+            v.obj.emplace_back("typed_allele", en.typed_allele[c] ? spj::str(en.typed_allele[c]) : spj::Value());
+            spj::Value list = spj::array();
+            for (uint32_t j = 0; j < sm.length; ++j) {
+                if (!contested_col(cols[j])) continue;
+                spj::Value k = spj::object();
+                k.obj.emplace_back("pos", spj::unum(j)); k.obj.emplace_back("depth", spj::unum(cols[j].depth)); k.obj.emplace_back("eq", spj::unum(cols[j].eq));
+                spj::Value x = spj::array();
+                for (int b = 0; b < 4; ++b) x.arr.push_back(spj::unum(cols[j].x[b]));
+                k.obj.emplace_back("x", std::move(x));
+                k.obj.emplace_back("del", spj::unum(cols[j].del)); k.obj.emplace_back("ins", spj::unum(cols[j].ins));
+                k.obj.emplace_back("consensus_base", spj::str(std::string(1, s[j])));
+                list.arr.push_back(std::move(k));
+            }
+            v.obj.emplace_back("contested", std::move(list));
+            gene.obj.emplace_back(c ? "consensus2" : "consensus1", std::move(v));
+        }
+        if (!gene.obj.empty()) root.obj.emplace_back(en.gene, std::move(gene));
+    }
+    std::string text;
+    spj::write_pretty(text, root);
+    if (needed) *needed = text.size() + 1;
+    if (cap < text.size() + 1) { if (cap) out[0] = '\0'; return SP_ERR_CAPACITY; }
+    std::memcpy(out, text.c_str(), text.size() + 1);
+    return SP_OK;
+}
+
+int32_t sp_hla_consensus_support_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
+                                        const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1, const char* cons, uint32_t cap,
+                                        const uint8_t* unit_on, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (!db || !reads || !col_offset || !summaries || n_samples == 0 || (n_genes && (!genes || !cons || cap == 0)) || (reads->n && (!realign || !is_cons1)) || (n_samples > 1 && !read_sample))
+        return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: null argument");
+    const uint64_t n_units = (uint64_t)n_samples * n_genes;
+    // ---- the targets: every non-empty consensus of a unit that is on, put on the gene strand
+    std::vector<int32_t> target_of(2 * n_units, -1);
+    std::string tblob; std::vector<uint64_t> toff(1, 0);
+    std::map<uint32_t, uint32_t> gene_slot;                                   // gene -> its place in `genes`
+    for (uint32_t k = 0; k < n_genes; ++k) {
+        const int fwd = spi_hla_gene_fwd(db, genes[k]);
+        if (fwd < 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: gene out of range");
+        if (!gene_slot.emplace(genes[k], k).second) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: a gene is listed twice");
+    }
+    col_offset[0] = 0;
+    for (uint64_t u = 0; u < n_units; ++u) for (int c = 0; c < 2; ++c) {
+        const char* s = cons + (2 * u + c) * (size_t)cap;
+        const size_t len = (unit_on && !unit_on[u]) ? 0 : strnlen(s, cap);
+        col_offset[2 * u + c + 1] = col_offset[2 * u + c] + len;
+        if (len == 0) continue;
+        target_of[2 * u + c] = (int32_t)(toff.size() - 1);
+        if (spi_hla_gene_fwd(db, genes[u % n_genes])) tblob.append(s, len); else tblob += revcomp_str(s, len);
+        toff.push_back(tblob.size());
+    }
+    const uint64_t n_cols = col_offset[2 * n_units];
+    if (n_cols > cols_cap || (n_cols && !cols)) return sp_fail(ctx, SP_ERR_CAPACITY, "consensus support: " + std::to_string(n_cols) + " columns, room for " + std::to_string(cols ? cols_cap : 0));
+    std::memset(summaries, 0, sizeof(sp_support_summary) * 2 * n_units);
+    const uint32_t n_t = (uint32_t)toff.size() - 1;
+    if (n_t == 0) return SP_OK;
+    // ---- the members: the realigned reads of every unit whose group has a consensus; their segments on the gene strand
+    std::vector<uint32_t> m_target; std::vector<uint32_t> members_of(n_t, 0);
+    std::string qblob; std::vector<uint64_t> qoff(1, 0);
+    for (uint32_t r = 0; r < reads->n; ++r) {
+        const sp_hla_realign& q = realign[r];
+        if (q.status != 0 || q.gene < 0) continue;
+        const auto slot = gene_slot.find((uint32_t)q.gene);
+        if (slot == gene_slot.end()) continue;
+        const uint32_t sample = read_sample ? read_sample[r] : 0;
+        if (sample >= n_samples) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: read_sample out of range");
+        const int32_t t = target_of[2 * ((uint64_t)sample * n_genes + slot->second) + (is_cons1[r] ? 0 : 1)];
+        if (t < 0) continue;
+        if (q.seg_start < 0 || q.seg_end <= q.seg_start || q.seg_end > reads->h_len[r]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: segment outside its read");
+        const std::string whole = sp_seqset_decode(ctx, reads, r);
+        if ((int32_t)whole.size() != reads->h_len[r]) return sp_fail(ctx, SP_ERR_HIP, "consensus support: fetching the reads failed");
+        if (spi_hla_gene_fwd(db, (uint32_t)q.gene)) qblob.append(whole, (size_t)q.seg_start, (size_t)(q.seg_end - q.seg_start));
+        else qblob += revcomp_str(whole.data() + q.seg_start, (size_t)(q.seg_end - q.seg_start));
+        qoff.push_back(qblob.size()); m_target.push_back((uint32_t)t); ++members_of[t];
+    }
+    const uint32_t n_m = (uint32_t)m_target.size();
+    sp_seqset T, Q;
+    int32_t rc = sp_seqset_make_small(ctx, "csup_t", tblob.data(), toff.data(), n_t, true, &T);
+    if (rc != SP_OK) return rc;
+    std::vector<uint64_t> t_cols((size_t)n_t + 1, 0);
+    for (uint32_t t = 0; t < n_t; ++t) t_cols[t + 1] = toff[t + 1];
+    std::vector<sp_pileup_col> table(n_cols);
+    std::vector<uint32_t> aligned_of(n_t, 0);
+    if (n_m) {
+        rc = sp_seqset_make_small(ctx, "csup_q", qblob.data(), qoff.data(), n_m, false, &Q);
+        if (rc != SP_OK) return rc;
+        std::vector<uint32_t> ident(n_m); std::iota(ident.begin(), ident.end(), 0u);
+        std::vector<int32_t> diag(n_m), votes(n_m);
+        rc = sp_anchor_batch(ctx, &T, &Q, m_target.data(), ident.data(), n_m, diag.data(), votes.data());
+        if (rc != SP_OK) return rc;
+        const sp_affine_opts ao = { 1, 4, 6, 2, 26, 1, 1 };
+        // the tracebacks run in slices of SLICE pairs with rows of 4,096 ops (the most a traceback of this library has); what they return is kept back to back and
+        // handed to the pileup in rows as long as the longest alignment actually seen, so the host holds SLICE x 16 KB of rows, not members x 16 KB
+        const uint32_t row_cap = 4096, SLICE = 256;
+        std::vector<sp_pair> pairs(n_m); std::vector<sp_affine_aln> aln(n_m); std::vector<uint32_t> n_cg(n_m, 0); std::vector<std::vector<uint32_t>> ops_of(n_m);
+        std::vector<uint32_t> todo;
+        for (uint32_t m = 0; m < n_m; ++m) { pairs[m] = sp_pair{ m, m_target[m], -diag[m], 0 }; aln[m] = sp_affine_aln{ 0, 0, 0, 0, 0, 0 }; if (votes[m] > 0) todo.push_back(m); }
+        std::vector<sp_pair> pp(SLICE); std::vector<sp_affine_aln> got(SLICE); std::vector<uint32_t> nc(SLICE), rows((size_t)SLICE * row_cap);
+        for (int band = 64; band <= 256 && !todo.empty(); band *= 4) {
+            std::vector<uint32_t> again;
+            for (size_t k0 = 0; k0 < todo.size(); k0 += SLICE) {
+                const size_t n = std::min<size_t>(SLICE, todo.size() - k0);
+                for (size_t k = 0; k < n; ++k) pp[k] = pairs[todo[k0 + k]];
+                rc = sp_affine_align_batch(ctx, &Q, &T, pp.data(), n, &ao, band, got.data(), rows.data(), row_cap, nc.data());
+                if (rc != SP_OK) return rc;
+                for (size_t k = 0; k < n; ++k) {
+                    const uint32_t m = todo[k0 + k];
+                    if (got[k].score <= 0 || nc[k] == 0) { again.push_back(m); continue; }
+                    if (nc[k] > row_cap) return sp_fail(ctx, SP_ERR_CAPACITY, "consensus support: an alignment of more than 4,096 runs");
+                    aln[m] = got[k]; n_cg[m] = nc[k]; ops_of[m].assign(rows.data() + k * (size_t)row_cap, rows.data() + k * (size_t)row_cap + nc[k]);
+                    ++aligned_of[m_target[m]];
+                }
+            }
+            todo.swap(again);
+        }
+        const uint32_t stride = std::max<uint32_t>(1, *std::max_element(n_cg.begin(), n_cg.end()));
+        std::vector<uint32_t> cg((size_t)n_m * stride);
+        for (uint32_t m = 0; m < n_m; ++m) { std::copy(ops_of[m].begin(), ops_of[m].end(), cg.begin() + (size_t)m * stride); std::vector<uint32_t>().swap(ops_of[m]); }
+        rc = sp_pileup_batch(ctx, &Q, &T, pairs.data(), n_m, aln.data(), cg.data(), stride, n_cg.data(), t_cols.data(), table.data());
+        if (rc != SP_OK) return rc;
+    }
+    for (uint64_t x = 0; x < 2 * n_units; ++x) {
+        const int32_t t = target_of[x];
+        if (t < 0) continue;
+        const sp_pileup_col* src = table.data() + t_cols[t];
+        const uint32_t len = (uint32_t)(t_cols[t + 1] - t_cols[t]);
+        std::memcpy(cols + col_offset[x], src, sizeof(sp_pileup_col) * (size_t)len);
+        sp_support_summarize(src, len, members_of[t], aligned_of[t], &summaries[x]);
+    }
+    return SP_OK;
+}
+
+int32_t sp_hla_consensus_support(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1,
+                                 const char* cons1, const char* cons2, sp_pileup_col* cols1, sp_pileup_col* cols2, sp_support_summary* s1, sp_support_summary* s2) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (!cons1 || !cons2) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: null argument");
+    const size_t l1 = cols1 && s1 ? std::strlen(cons1) : 0, l2 = cols2 && s2 ? std::strlen(cons2) : 0;
+    const uint32_t cap = (uint32_t)std::max(l1, l2) + 1;
+    std::vector<char> both((size_t)2 * cap, '\0');
+    std::memcpy(both.data(), cons1, l1); std::memcpy(both.data() + cap, cons2, l2);
+    uint64_t off[3]; sp_support_summary sm[2];
+    std::vector<sp_pileup_col> table(l1 + l2);
+    const int32_t rc = sp_hla_consensus_support_cohort(ctx, db, 1, nullptr, 1, &gene, reads, realign, is_cons1, both.data(), cap, nullptr, off, table.data(), table.size(), sm);
+    if (rc != SP_OK) return rc;
+    if (cols1 && s1) { std::memcpy(cols1, table.data(), sizeof(sp_pileup_col) * l1); *s1 = sm[0]; }
+    if (cols2 && s2) { std::memcpy(cols2, table.data() + off[1], sizeof(sp_pileup_col) * l2); *s2 = sm[1]; }
+    return SP_OK;
+}
+
+} // extern "C"

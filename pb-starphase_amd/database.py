@@ -166,6 +166,7 @@ def _lib():
         "sp_starphase_last_timing": (_i32, [_vp, P(sp_starphase_timing)]),
         "sp_starphase_set_read_debug": (_i32, [_vp, _i32]),
         "sp_starphase_set_hla_debug_mappings": (_i32, [_vp, _i32]),
+        "sp_starphase_set_consensus_support": (_i32, [_vp, _i32]),
         "sp_starphase_call_batch": (_i32, [_vp, _u32, P(sp_sample_inputs), P(_s), P(sp_batch_options), P(_vp), P(_i32)]),
         "sp_starphase_sample_error": (_s, [_vp, _u32]),
         "sp_starphase_sample_warnings": (_s, [_vp, _u32]),
@@ -944,14 +945,17 @@ def settings_check(bams=(), vcf=None, **kw):
 
 
 class Starphase:
-    """sp_starphase: a database + reference loaded once, sp_starphase_call per sample.  ctx: a Context or None (the handle makes its own)."""
+    """sp_starphase: a database + reference loaded once, sp_starphase_call per sample.  ctx: a Context or None (the handle makes its own).
+    consensus_support=True: set_consensus_support() at once (a call with a debug folder also writes consensus_support.json)."""
 
-    def __init__(self, database, reference=None, ctx=None, **settings):
+    def __init__(self, database, reference=None, ctx=None, consensus_support=False, **settings):
         self._h = _vp()
         self._s = _settings(**settings)
         rc = _lib().sp_starphase_create(ctx._h if ctx is not None else None, _b(database), _b(reference), C.byref(self._s), C.byref(self._h))
         if rc != SP_OK:
             raise StarphaseError(rc, _d(_lib().sp_starphase_last_error(None)))
+        if consensus_support:
+            self.set_consensus_support(True)
 
     def close(self):
         if self._h:
@@ -963,6 +967,14 @@ class Starphase:
             self.close()
         except Exception:
             pass
+
+    def set_consensus_support(self, on=True):
+        """sp_starphase_set_consensus_support: a debug folder also receives consensus_support.json (per HLA gene and consensus: how many member reads span, agree with or
+        contest each consensus column); off by default"""
+        rc = _lib().sp_starphase_set_consensus_support(self._h, 1 if on else 0)
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_starphase_set_consensus_support")
+        return self
 
     def set_hla_debug_mappings(self, on=True):
         """sp_starphase_set_hla_debug_mappings: hla_debug.json of a debug folder carries the mapping of each consensus against every allowed allele of its gene; off by default"""

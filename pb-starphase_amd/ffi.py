@@ -18,7 +18,9 @@ class StarphaseError(RuntimeError):
 
 
 SP_OK = 0
+SP_ERR_INVALID_ARG = 1
 SP_ERR_NO_DEVICE = 2
+SP_ERR_CAPACITY = 6
 SP_NO_DIAG = -(2 ** 31)
 SP_MAX_ED = 511
 
@@ -230,6 +232,72 @@ REALIGN_DTYPE = np.dtype([("status", np.int32), ("best_allele", np.int32), ("gen
 K1_HIT_DTYPE = np.dtype([(n, np.int32) for n in K1_HIT_FIELDS])
 REV_HIT_DTYPE = np.dtype([(n, np.int32) for n in ("allele", "t_len", "nm", "t_start", "t_end", "reserved_")])     # sp_hla_rev_hit
 
+# sp_pileup_batch: one record per target column; SP_PILEUP_TILE columns per workgroup, SP_PILEUP_WAVES waves per workgroup (include/starphase_hip.h)
+SP_PILEUP_TILE = 2048
+SP_PILEUP_WAVES = 4
+PILEUP_DTYPE = np.dtype([("depth", np.uint32), ("eq", np.uint32), ("x", np.uint32, (4,)), ("del", np.uint32), ("ins", np.uint32)])       # sp_pileup_col
+SUPPORT_FIELDS = ("n_members", "n_aligned", "n_unaligned", "length", "min_depth", "median_depth", "n_contested", "reserved_")
+SUPPORT_DTYPE = np.dtype([(n, np.uint32) for n in SUPPORT_FIELDS])                                                                      # sp_support_summary
+
+
+class sp_support_summary(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in SUPPORT_FIELDS]
+
+
+class sp_support_entry(C.Structure):
+    _fields_ = [("gene", C.c_char_p), ("typed_allele", C.c_char_p * 2), ("consensus", C.c_char_p * 2), ("cols", C.c_void_p * 2), ("summary", C.POINTER(sp_support_summary) * 2)]
+
+
+def support_summarize(cols, n_members=0, n_aligned=0):
+    """sp_support_summarize (host only): cols = PILEUP_DTYPE[length] -> dict of the summary fields"""
+    cols = np.ascontiguousarray(cols, PILEUP_DTYPE)
+    sm = sp_support_summary()
+    rc = lib().sp_support_summarize(_ptr(cols), len(cols), int(n_members), int(n_aligned), C.byref(sm))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_support_summarize")
+    return {n: int(getattr(sm, n)) for n in SUPPORT_FIELDS[:-1]}
+
+
+def support_contested(cols):
+    """sp_support_contested (host only): the contested columns of a table, ascending"""
+    cols = np.ascontiguousarray(cols, PILEUP_DTYPE)
+    pos = np.zeros(max(1, len(cols)), np.uint32)
+    n = C.c_uint32(0)
+    rc = lib().sp_support_contested(_ptr(cols), len(cols), _ptr(pos), len(pos), C.byref(n))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_support_contested")
+    return pos[:n.value].copy()
+
+
+def consensus_support_json(entries):
+    """sp_consensus_support_json (host only): entries = [(gene, [(typed_allele or None, gene-strand consensus, cols PILEUP_DTYPE, summary dict) or None] * 2)]
+    -> the text of consensus_support.json"""
+    arr = (sp_support_entry * max(1, len(entries)))()
+    keep = []
+    for e, (gene, sides) in zip(arr, entries):
+        e.gene = gene.encode()
+        for c, side in enumerate(sides):
+            if side is None:
+                continue
+            typed, cons, cols, summary = side
+            cols = np.ascontiguousarray(cols, PILEUP_DTYPE)
+            sm = sp_support_summary(**{n: int(summary.get(n, 0)) for n in SUPPORT_FIELDS})
+            keep.append((cols, sm))
+            e.typed_allele[c] = typed.encode() if typed is not None else None
+            e.consensus[c] = cons.encode()
+            e.cols[c] = cols.ctypes.data if len(cols) else None
+            e.summary[c] = C.pointer(sm)
+    need = C.c_uint64(0)
+    rc = lib().sp_consensus_support_json(arr, len(entries), None, 0, C.byref(need))
+    if rc not in (SP_OK, SP_ERR_CAPACITY):
+        raise StarphaseError(rc, "sp_consensus_support_json")
+    buf = C.create_string_buffer(need.value)
+    rc = lib().sp_consensus_support_json(arr, len(entries), buf, need.value, C.byref(need))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_consensus_support_json")
+    return buf.value.decode()
+
+
 _lib = None
 
 
@@ -256,6 +324,12 @@ def lib():
         "sp_affine_rescore_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, vp]),
         "sp_affine_align_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, vp, vp, u32, vp]),
         "sp_hla_realign_cigars": (i32, [vp, vp, vp, vp, u32, vp, u32, vp]),
+        "sp_pileup_batch": (i32, [vp, vp, vp, vp, u64, vp, vp, u32, vp, vp, vp]),
+        "sp_support_summarize": (i32, [vp, u32, u32, u32, C.POINTER(sp_support_summary)]),
+        "sp_support_contested": (i32, [vp, u32, vp, u32, C.POINTER(u32)]),
+        "sp_hla_consensus_support": (i32, [vp, vp, u32, vp, vp, vp, C.c_char_p, C.c_char_p, vp, vp, C.POINTER(sp_support_summary), C.POINTER(sp_support_summary)]),
+        "sp_hla_consensus_support_cohort": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp, C.c_char_p, u32, vp, vp, vp, u64, vp]),
+        "sp_consensus_support_json": (i32, [C.POINTER(sp_support_entry), u32, C.c_char_p, u64, C.POINTER(u64)]),
         "sp_ctx_get_info": (i32, [vp, C.POINTER(sp_ctx_info)]),
         "sp_last_error": (C.c_char_p, [vp]),
         "sp_ctx_synchronize": (i32, [vp]),
@@ -347,7 +421,8 @@ def lib():
     if L.sp_abi_version() != SP_ABI_VERSION:
         raise ImportError(f"{path}: ABI version {L.sp_abi_version()}, this binding was written for {SP_ABI_VERSION} (rebuild: __graft_entry__.build())")
     for name, size in (("sp_hla_realign", REALIGN_DTYPE.itemsize), ("sp_aln", ALN_DTYPE.itemsize), ("sp_k1_seed_hit", K1_HIT_DTYPE.itemsize),
-                       ("sp_hla_best", C.sizeof(sp_hla_best)), ("sp_hla_realign", C.sizeof(sp_hla_realign)), ("sp_hla_rev_hit", REV_HIT_DTYPE.itemsize)):
+                       ("sp_hla_best", C.sizeof(sp_hla_best)), ("sp_hla_realign", C.sizeof(sp_hla_realign)), ("sp_hla_rev_hit", REV_HIT_DTYPE.itemsize),
+                       ("sp_pileup_col", PILEUP_DTYPE.itemsize), ("sp_support_summary", SUPPORT_DTYPE.itemsize)):
         if L.sp_struct_size(name.encode()) != size:
             raise ImportError(f"{path}: {name} is {L.sp_struct_size(name.encode())} bytes in the library, {size} in this binding")
     _lib = L
@@ -416,6 +491,22 @@ class Context:
         op = sp_affine_opts(a, 4, 6, 2, 26, 1, 1)
         self.check(lib().sp_affine_align_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), int(band), _ptr(out), _ptr(cigar), int(cigar_stride), _ptr(n_cigar)))
         return out, cigar, n_cigar
+
+    def pileup(self, A, B, pairs, aln, cigar, n_cigar):
+        """sp_pileup_batch: pairs / aln / cigar / n_cigar as affine_align took and returned them (A = queries, B = targets) -> one PILEUP_DTYPE array per target of B,
+        one record per column"""
+        rows = np.zeros(len(pairs), PAIR_DTYPE)
+        for i, pr in enumerate(pairs):
+            rows[i] = (pr[0], pr[1], pr[2], pr[3] if len(pr) > 3 else 0)
+        aln = np.ascontiguousarray(aln, AFFINE_DTYPE)
+        cigar = np.ascontiguousarray(cigar, np.uint32).reshape(len(pairs), -1) if len(pairs) else np.zeros((0, 1), np.uint32)
+        n_cigar = np.ascontiguousarray(n_cigar, np.uint32)
+        lens = [int(x) for x in B.lengths]
+        off = np.zeros(B.n + 1, np.uint64)
+        off[1:] = np.cumsum(lens)
+        out = np.zeros(int(off[-1]), PILEUP_DTYPE)
+        self.check(lib().sp_pileup_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), _ptr(aln), _ptr(cigar), cigar.shape[1], _ptr(n_cigar), _ptr(off), _ptr(out)))
+        return [out[int(off[t]):int(off[t + 1])] for t in range(B.n)]
 
     def hla_config_extend(self, reference, alleles, db=None, batch_alleles=0):
         """sp_hla_config_extend: HlaConfig::new on the device -- reference = database.Fasta, alleles = database.HlaAlleles, db = database.Database whose hla_config
@@ -1255,6 +1346,37 @@ class HlaDb:
         realign = np.ascontiguousarray(realign)
         self.ctx.check(lib().sp_hla_diplotype_gene(self.ctx._h, self._h, int(gene), reads._h, _ptr(realign), C.byref(cfg), C.byref(call), c1, c2, cap, _ptr(is1)))
         return call, c1.value.decode(), c2.value.decode(), is1[(realign["status"] == 0) & (realign["gene"] == gene)].astype(bool)
+
+    def consensus_support(self, gene, reads, realign, is_cons1, cons1, cons2):
+        """sp_hla_consensus_support: is_cons1 per read of `reads` (as diplotype_genes returns it), cons1 / cons2 the hg38-forward consensuses of the call
+        -> ((cols1 PILEUP_DTYPE, summary1 dict), (cols2, summary2)) in gene-strand coordinates"""
+        realign = np.ascontiguousarray(realign)
+        is1 = np.ascontiguousarray(is_cons1, np.uint8)
+        cols = [np.zeros(len(cons1), PILEUP_DTYPE), np.zeros(len(cons2), PILEUP_DTYPE)]
+        sm = [sp_support_summary(), sp_support_summary()]
+        self.ctx.check(lib().sp_hla_consensus_support(self.ctx._h, self._h, int(gene), reads._h, _ptr(realign), _ptr(is1), cons1.encode(), cons2.encode(),
+                                                      cols[0].ctypes.data, cols[1].ctypes.data, C.byref(sm[0]), C.byref(sm[1])))
+        return tuple((cols[c], {n: int(getattr(sm[c], n)) for n in SUPPORT_FIELDS[:-1]}) for c in range(2))
+
+    def consensus_support_cohort(self, n_samples, read_sample, genes, reads, realign, is_cons1, cons, unit_on=None):
+        """sp_hla_consensus_support_cohort: cons[sample][gene] = (consensus1, consensus2), hg38 forward -> out[sample][gene] = ((cols1, summary1), (cols2, summary2))"""
+        k = len(genes)
+        g = np.ascontiguousarray(genes, np.uint32)
+        rs = np.ascontiguousarray(read_sample, np.uint32) if read_sample is not None else None
+        realign = np.ascontiguousarray(realign)
+        is1 = np.ascontiguousarray(is_cons1, np.uint8)
+        flat = [cons[s][i][c] for s in range(n_samples) for i in range(k) for c in range(2)]
+        cap = max([len(x) for x in flat] + [0]) + 1
+        buf = C.create_string_buffer(b"".join(x.encode().ljust(cap, b"\0") for x in flat), len(flat) * cap)
+        on = np.ascontiguousarray(unit_on, np.uint8) if unit_on is not None else None
+        off = np.zeros(len(flat) + 1, np.uint64)
+        total = sum(len(x) for x in flat)
+        cols = np.zeros(max(1, total), PILEUP_DTYPE)
+        sm = np.zeros(len(flat), SUPPORT_DTYPE)
+        self.ctx.check(lib().sp_hla_consensus_support_cohort(self.ctx._h, self._h, n_samples, _ptr(rs), k, _ptr(g), reads._h, _ptr(realign), _ptr(is1), buf, cap,
+                                                             _ptr(on), _ptr(off), _ptr(cols), total, _ptr(sm)))
+        side = lambda x: (cols[int(off[x]):int(off[x + 1])].copy(), {n: int(sm[x][n]) for n in SUPPORT_FIELDS[:-1]})
+        return [[(side(2 * (s * k + i)), side(2 * (s * k + i) + 1)) for i in range(k)] for s in range(n_samples)]
 
     def diplotype_genes(self, genes, reads, realign, cfgs=None, cap=65536):
         """sp_hla_diplotype_genes -> list of (sp_hla_call, consensus1, consensus2) per gene, and is_consensus1 per read"""
