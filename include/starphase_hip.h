@@ -243,6 +243,30 @@ typedef struct { uint32_t depth, eq, x[4], del, ins; } sp_pileup_col;   /* 32 by
 int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
                         const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset, sp_pileup_col* out);
 
+/* ------------------------------------------------------------------ align + pileup + summary in one device-resident pass
+ * sp_affine_align_batch(band = 64, cigar_stride = 4096) followed by sp_pileup_batch and, per target, sp_support_summarize -- without the op rows leaving the device.
+ * pairs / opts as sp_affine_align_batch takes them (a = query in A, b = target in B, diag, max_ed < 0: skip), col_offset as sp_pileup_batch takes it.  The band is
+ * 64 diagonals; there is no other.  Every output is optional (NULL: not computed where nothing else needs it, and never downloaded):
+ *   aln        n_pairs records, bit for bit sp_affine_align_batch's
+ *   cols       col_offset[n_targets] records, bit for bit sp_pileup_batch's over those alignments (a pair with score 0 contributes nothing)
+ *   summaries  one per target of B: what sp_support_summarize returns for the target's columns, with n_aligned = the pairs naming the target with score > 0,
+ *              n_unaligned = the other pairs naming it, n_members = n_members[t] when that list is given, n_aligned + n_unaligned otherwise.  A target no pair names
+ *              is all zeros but for length (and n_members).
+ * How: the alignment is the checkpointed traceback of sp_hla_map_consensus's map kernel (no direction byte per cell), writing compact op rows into one pooled buffer;
+ * a pileup kernel of sp_pileup_batch's tile design reads op offsets, op counts and spans from device memory (pairs bucketed by target on the host from `pairs` alone:
+ * no op row is walked on the host, the rows are the library's own); a summary kernel makes one pass over each target's columns with a depth histogram of
+ * SP_SUPPORT_HIST_BINS bins in LDS -- a target with more pairs than bins is binned coarsely and the median's bin resolved by further passes, never capped.  Integer
+ * results, exact in any order.  A batch of more than SP_ALIGN_PILEUP_SLICE pairs runs in slices of that many (in the order given) through one op buffer; a tile that
+ * an earlier slice has written is loaded, added to and stored again by its one owner per launch (plain loads and stores, no atomics on global memory).  Device memory:
+ * pooled buffers of the context only (a second identical call allocates nothing).
+ * Errors: SP_ERR_INVALID_ARG before any launch for a NULL set / col_offset, an index out of range or a col_offset that does not follow B's lengths; SP_ERR_TOO_LONG
+ * for sequences the map kernel does not take; SP_ERR_CAPACITY for an alignment of more than 4,096 runs (the row sp_affine_align_batch would have cut off). */
+#define SP_ALIGN_PILEUP_SLICE 4096
+#define SP_SUPPORT_HIST_BINS  1024
+typedef struct { uint32_t n_members, n_aligned, n_unaligned, length, min_depth, median_depth, n_contested, reserved_; } sp_support_summary;   /* 32 bytes; the rule: consensus support, below */
+int32_t sp_align_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts,
+                              const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members);
+
 /* ------------------------------------------------------------------ HLA database
  * Replaces HlaRealigner::new + create_hla_fasta (src/hla/realigner.rs:42-91,497-526) and the per-call
  * one-sequence indexes of score_read (src/hla/caller.rs:1370-1379).
@@ -625,6 +649,38 @@ int32_t sp_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* prob
                                          char* consensus, uint32_t cons_cap, sp_cyp_region_variants* region_variants /* optional */,
                                          sp_cyp_read_mapping* mappings, uint64_t cap, uint64_t* mapping_off, int32_t* sample_rc);
 
+/* ------------------------------------------------------------------ CYP2D6 consensus support: how well the member reads back each consensus region of a call
+ * The table of sp_hla_consensus_support (below) for the consensus regions of a CYP2D6 call; an output of this library's own.  call / consensus / cons_cap / mappings as
+ * sp_cyp_diplotype_mappings returned them for `reads`.
+ *   members    of consensus h: the mapping records with .consensus == h -- the reads with exactly one chain, the reference's rule for multi_mapping_details, kept as it
+ *              is: a read with several chains backs no consensus here.  A read with several regions on one consensus is several members.
+ *   pairs      query = reads[r][read_start, read_end), target = consensus h as the call returned it.  Orientation: the regions of interest are cut out of the reads as
+ *              uploaded (sp_region_hit has no strand, the segments are forward views of the reads) and every consensus is built from such segments, so reads and
+ *              consensuses share one orientation; there is no strand handling.
+ *   alignment  sp_anchor_batch(A = the consensuses, B = the segments) gives the diagonal (negated, as in the HLA pass); sp_align_pileup_batch at the map-hifi scores
+ *              {1, 4, 6, 2, 26, 1, 1} on 64 diagonals.  There is NO second try on 256 diagonals (the HLA pass has one): a member without an anchor (0 votes) or
+ *              without an alignment on 64 diagonals is counted in n_unaligned and left out; it is not an error.
+ * col_offset (n_consensus + 1 entries, always filled): consensus h owns cols[col_offset[h] .. col_offset[h + 1]); cols may be NULL (cols_cap ignored: no table is
+ * downloaded, the summaries are computed on the device all the same); SP_ERR_CAPACITY when cols is given and col_offset[n_consensus] > cols_cap (call again with more
+ * room).  summaries: n_consensus records.  call->status != 0: SP_OK, col_offset all 0, the summaries zeroed, nothing launched.
+ * sp_cyp_consensus_support_cohort: n_samples calls in one pass -- one segment set, one anchor launch, one sp_align_pileup_batch.  calls[i], the consensus block of sample i
+ * (n_samples * SP_CYP_MAXCONS * cons_cap bytes) and mappings[mapping_off[i] .. mapping_off[i + 1]) as sp_cyp_diplotype_cohort_mappings returned them; col_offset:
+ * n_samples * SP_CYP_MAXCONS + 1 entries, summaries: n_samples * SP_CYP_MAXCONS (consensus h of sample i at i * SP_CYP_MAXCONS + h; the slots behind n_consensus own no
+ * columns and are zeroed).
+ * sp_cyp_support_json: `cyp2d6_consensus_support.json` (host only; two-space indent, the layout of consensus_support.json): one entry per consensus region in consensus
+ * order, keyed by its index_label ("<index>_<full allele>", the key of cyp2d6_alleles.json), each with n_members, n_aligned, n_unaligned, length, min_depth,
+ * median_depth, n_contested, region_type (the full allele label of cons_type / cons_subtype) and contested = [{pos, depth, eq, x: [a, c, g, t], del, ins,
+ * consensus_base}].  col_offset / cols / summaries: n_consensus (+ 1) entries as sp_cyp_consensus_support filled them (cols must be given).  A call with
+ * status != 0 has no entries: the text is {} (the whole-sample call writes no file for it).  out / cap / needed as sp_cyp_alleles_json. */
+int32_t sp_cyp_consensus_support(sp_ctx* ctx, const sp_seqset* reads, const sp_cyp_call* call, const char* consensus, uint32_t cons_cap,
+                                 const sp_cyp_read_mapping* mappings, uint64_t n_mappings, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                                 sp_support_summary* summaries);
+int32_t sp_cyp_consensus_support_cohort(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
+                                        const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                                        sp_support_summary* summaries);
+int32_t sp_cyp_support_json(const sp_cyp_call* call, const char* consensus, uint32_t cons_cap, const uint64_t* col_offset, const sp_pileup_col* cols,
+                            const sp_support_summary* summaries, char* out, uint64_t cap, uint64_t* needed);
+
 /* ------------------------------------------------------------------ CYP2D6 templates and typing tables
  * Replaces generate_cyp_hybrids (src/cyp2d6/definitions.rs:346-464), LoadedVariants::load_variant_database
  * (src/cyp2d6/haplotyper.rs:650-773) and the table building of Cyp2d6Extractor::new (src/cyp2d6/haplotyper.rs:45-132).
@@ -926,8 +982,7 @@ int32_t sp_hla_diplotype_cohort_samples(sp_ctx* ctx, const sp_hla_db* db, uint32
  * launch per band, one pileup launch.  cons / is_cons1 as that call returned them; read_sample NULL = one sample.  unit_on (optional, n_samples * n_genes): 0 skips a
  * unit (its consensuses get no columns and zeroed summaries).  col_offset (n_samples * n_genes * 2 + 1 entries, always filled): consensus c of unit u owns
  * cols[col_offset[2u + c] .. col_offset[2u + c + 1]); SP_ERR_CAPACITY when col_offset[last] > cols_cap (nothing else is written: call again with more room).
- * summaries: n_samples * n_genes * 2. */
-typedef struct { uint32_t n_members, n_aligned, n_unaligned, length, min_depth, median_depth, n_contested, reserved_; } sp_support_summary;   /* 32 bytes */
+ * summaries: n_samples * n_genes * 2.  (sp_support_summary: declared with sp_align_pileup_batch above, 32 bytes.) */
 int32_t sp_support_summarize(const sp_pileup_col* cols, uint32_t length, uint32_t n_members, uint32_t n_aligned, sp_support_summary* out);
 /* the contested columns in ascending order: pos holds cap entries, *n = how many there are (SP_ERR_CAPACITY when more than cap) */
 int32_t sp_support_contested(const sp_pileup_col* cols, uint32_t length, uint32_t* pos, uint32_t cap, uint32_t* n);
@@ -1343,6 +1398,14 @@ int32_t sp_starphase_set_hla_debug_mappings(sp_starphase* handle, int32_t on);
  * call that succeeds into one that fails (out of memory; an alignment of more than 4,096 runs, SP_ERR_CAPACITY) -- in a batch the group then goes through the pass
  * once more sample by sample, and only the samples whose own pass fails are failed.  CYP2D6 consensuses are not covered. */
 int32_t sp_starphase_set_consensus_support(sp_starphase* handle, int32_t on);
+/* cyp2d6_consensus_support.json, off by default (on 0) and a switch of its own (sp_starphase_set_consensus_support writes the HLA file only): with it on, a call with
+ * a debug folder whose CYP2D6 call has status 0 also writes <folder>/cyp2d6_consensus_support.json (sp_cyp_support_json above) from sp_cyp_consensus_support_cohort over the
+ * reads, the consensuses and the multi_mapping_details records of the call itself; a sample without CYP2D6 reads or without a call writes no file.  The CYP2D6 lane then
+ * asks its calls for their consensuses (the calls are the same) and runs one support pass per group of a batch, over the samples of the group that have a debug
+ * folder; each sample's file equals its single call's file.  Off: no launch, no pool memory, every output the same bytes; on: every other output the same bytes.  A
+ * failure of the pass fails the sample's CYP2D6 entry (out of memory; an alignment of more than 4,096 runs, SP_ERR_CAPACITY); in a batch the group's samples then go
+ * through the pass one by one and only those whose own pass fails are failed. */
+int32_t sp_starphase_set_cyp_consensus_support(sp_starphase* handle, int32_t on);
 const char* sp_starphase_warnings(const sp_starphase* handle);      /* the warnings of the last call, one per line */
 /* where the last call spent its time (wall ms): whole call, BAM decode (host, both loci), variant genes, HLA lane, CYP2D6 lane */
 typedef struct { double call_ms, bam_decode_ms, variant_ms, hla_ms, cyp_ms; uint32_t n_hla_reads, n_cyp_reads; } sp_starphase_timing;

@@ -16,6 +16,8 @@ pub const SP_EV_D: i64 = 1;
 pub const SP_EV_I: i64 = 2;
 pub const SP_PILEUP_TILE: i64 = 2048;
 pub const SP_PILEUP_WAVES: i64 = 4;
+pub const SP_ALIGN_PILEUP_SLICE: i64 = 4096;
+pub const SP_SUPPORT_HIST_BINS: i64 = 1024;
 pub const SP_K1_SEL: i64 = 16;
 pub const SP_MAX_CHAIN: i64 = 64;
 pub const SP_CYP_MAXCONS: i64 = 64;
@@ -74,6 +76,17 @@ pub struct sp_pileup_col {
     pub x: [u32; 4],
     pub del: u32,
     pub ins: u32,
+}
+#[repr(C)]
+pub struct sp_support_summary {
+    pub n_members: u32,
+    pub n_aligned: u32,
+    pub n_unaligned: u32,
+    pub length: u32,
+    pub min_depth: u32,
+    pub median_depth: u32,
+    pub n_contested: u32,
+    pub reserved_: u32,
 }
 #[repr(C)]
 pub struct sp_hla_db_desc {
@@ -491,17 +504,6 @@ pub struct sp_hla_call {
     pub cdf: f64,
 }
 #[repr(C)]
-pub struct sp_support_summary {
-    pub n_members: u32,
-    pub n_aligned: u32,
-    pub n_unaligned: u32,
-    pub length: u32,
-    pub min_depth: u32,
-    pub median_depth: u32,
-    pub n_contested: u32,
-    pub reserved_: u32,
-}
-#[repr(C)]
 pub struct sp_support_entry {
     pub gene: *const c_char,
     pub typed_allele: [*const c_char; 2],
@@ -764,6 +766,7 @@ extern "C" {
     pub fn sp_affine_rescore_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, band: i32, out: *mut sp_affine_aln) -> i32;
     pub fn sp_affine_align_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, band: i32, out: *mut sp_affine_aln, cigar: *mut u32, cigar_stride: u32, n_cigar: *mut u32) -> i32;
     pub fn sp_pileup_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, aln: *const sp_affine_aln, cigar: *const u32, cigar_stride: u32, n_cigar: *const u32, col_offset: *const u64, out: *mut sp_pileup_col) -> i32;
+    pub fn sp_align_pileup_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, col_offset: *const u64, aln: *mut sp_affine_aln, cols: *mut sp_pileup_col, summaries: *mut sp_support_summary, n_members: *const u32) -> i32;
     pub fn sp_hla_db_create(ctx: *mut sp_ctx, desc: *const sp_hla_db_desc, out: *mut *mut sp_hla_db) -> i32;
     pub fn sp_hla_db_free(db: *mut sp_hla_db);
     pub fn sp_hla_seed_index_info(ctx: *mut sp_ctx, db: *const sp_hla_db, out: *mut i64) -> i32;
@@ -796,6 +799,9 @@ extern "C" {
     pub fn sp_cyp_alleles_json(problem: *const sp_cyp_problem, call: *const sp_cyp_call, region_variants: *const sp_cyp_region_variants, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
     pub fn sp_cyp_diplotype_mappings(ctx: *mut sp_ctx, problem: *const sp_cyp_problem, reads: *const sp_seqset, call: *mut sp_cyp_call, consensus: *mut c_char, cons_cap: u32, region_variants: *mut sp_cyp_region_variants, mappings: *mut sp_cyp_read_mapping, cap: u64, n_mappings: *mut u64) -> i32;
     pub fn sp_cyp_diplotype_cohort_mappings(ctx: *mut sp_ctx, problem: *const sp_cyp_problem, n_samples: u32, reads: *const *const sp_seqset, calls: *mut sp_cyp_call, consensus: *mut c_char, cons_cap: u32, region_variants: *mut sp_cyp_region_variants, mappings: *mut sp_cyp_read_mapping, cap: u64, mapping_off: *mut u64, sample_rc: *mut i32) -> i32;
+    pub fn sp_cyp_consensus_support(ctx: *mut sp_ctx, reads: *const sp_seqset, call: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, mappings: *const sp_cyp_read_mapping, n_mappings: u64, col_offset: *mut u64, cols: *mut sp_pileup_col, cols_cap: u64, summaries: *mut sp_support_summary) -> i32;
+    pub fn sp_cyp_consensus_support_cohort(ctx: *mut sp_ctx, n_samples: u32, reads: *const *const sp_seqset, calls: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, mappings: *const sp_cyp_read_mapping, mapping_off: *const u64, col_offset: *mut u64, cols: *mut sp_pileup_col, cols_cap: u64, summaries: *mut sp_support_summary) -> i32;
+    pub fn sp_cyp_support_json(call: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, col_offset: *const u64, cols: *const sp_pileup_col, summaries: *const sp_support_summary, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
     pub fn sp_cyp_db_create(ctx: *mut sp_ctx, locus: *const sp_cyp_locus, gene_def: *const sp_cyp_gene_def, config: *const sp_cyp_config, out: *mut *mut sp_cyp_db) -> i32;
     pub fn sp_cyp_db_free(db: *mut sp_cyp_db);
     pub fn sp_cyp_db_info(db: *const sp_cyp_db, stats: *mut sp_cyp_db_stats) -> i32;
@@ -922,6 +928,7 @@ extern "C" {
     pub fn sp_starphase_set_read_debug(handle: *mut sp_starphase, enable: i32) -> i32;
     pub fn sp_starphase_set_hla_debug_mappings(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_consensus_support(handle: *mut sp_starphase, on: i32) -> i32;
+    pub fn sp_starphase_set_cyp_consensus_support(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_warnings(handle: *const sp_starphase) -> *const c_char;
     pub fn sp_starphase_last_timing(handle: *const sp_starphase, out: *mut sp_starphase_timing) -> i32;
     pub fn sp_starphase_call_batch(handle: *mut sp_starphase, n: u32, inputs: *const sp_sample_inputs, debug_folders: *const *const c_char, opts: *const sp_batch_options, out: *mut *mut sp_result, sample_rc: *mut i32) -> i32;

@@ -444,6 +444,11 @@ void* sp_pool(sp_ctx* ctx, const char* name, size_t bytes) {
     return e.first;
 }
 
+size_t sp_pool_bytes(const sp_ctx* ctx, const char* name) {
+    const auto it = ctx->pool.find(name);
+    return it != ctx->pool.end() && it->second.first ? it->second.second : 0;
+}
+
 unsigned long long* sp_counters(sp_ctx* ctx) {
     auto it = ctx->pool.find("prof_counters");
     if (it != ctx->pool.end() && it->second.first) return (unsigned long long*)it->second.first;

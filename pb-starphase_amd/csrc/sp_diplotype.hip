@@ -118,6 +118,7 @@ struct sp_starphase {
     std::string include_set, exclude_set, sample_name, sv_vcf, debug_folder;
     int32_t read_debug = 0;                          // sp_starphase_set_read_debug: a debug folder also receives read_debug.json
     int32_t consensus_support = 0;                   // sp_starphase_set_consensus_support: a debug folder also receives consensus_support.json
+    int32_t cyp_consensus_support = 0;               // sp_starphase_set_cyp_consensus_support: a debug folder also receives cyp2d6_consensus_support.json
     int32_t hla_debug_mappings = 0;                  // sp_starphase_set_hla_debug_mappings: hla_debug.json carries the mapping of each consensus against every allowed allele
     std::set<std::string> include, exclude; bool has_include = false, has_exclude = false;
     // chromosomes the variant genes were normalised against (sp_variant_gene keeps a pointer)
@@ -731,6 +732,21 @@ void cyp_package(sp_starphase* h, const sp_cyp_problem& pr, const sp_cyp_call& c
     }
 }
 
+// cyp2d6_consensus_support.json of one sample (sp_starphase_set_cyp_consensus_support): the tables of the group's one support pass that belong to this sample
+// (off: MAXCONS + 1 offsets into cols, sm: MAXCONS summaries, cons: the sample's consensus block).  A failure fails the sample's CYP2D6 entry.
+void cyp_support_save(const sp_cyp_call& call, const char* cons, uint32_t cons_cap, const uint64_t* off, const sp_pileup_col* cols, const sp_support_summary* sm,
+                      const std::string& debug_folder, CypLane* L) {
+    uint64_t need = 0;
+    int32_t rc = sp_cyp_support_json(&call, cons, cons_cap, off, cols, sm, nullptr, 0, &need);
+    std::string text((size_t)need, '\0');
+    if (rc == SP_OK || rc == SP_ERR_CAPACITY) rc = sp_cyp_support_json(&call, cons, cons_cap, off, cols, sm, &text[0], need, &need);
+    if (rc != SP_OK) { L->rc = rc; L->err = "cyp2d6_consensus_support.json: the tables do not fit their consensuses"; return; }
+    const std::string path = debug_folder + "/cyp2d6_consensus_support.json";
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f || std::fwrite(text.data(), 1, (size_t)need - 1, f) != (size_t)need - 1) { if (f) std::fclose(f); L->rc = SP_ERR_INVALID_ARG; L->err = "Error while writing " + path; return; }
+    std::fclose(f);
+}
+
 // ---------------------------------------------------------------- the pipeline of a group of samples
 struct Sample : VarSample {
     std::vector<std::string> bams; std::string debug; bool run_hla = false, run_cyp = false;
@@ -808,15 +824,52 @@ void cyp_group(sp_starphase* h, std::vector<Sample*> group, bool only_ok, double
         for (uint32_t k = 0; k < n; ++k) { rv[k] = sp_cyp_region_variants{}; rv[k].state = state.data() + per * k; }
         std::vector<std::vector<sp_cyp_read_mapping>> mappings(n);
         std::vector<int32_t> rcs(n, SP_ERR_INVALID_ARG);             // until the cohort call has typed it
-        if (n > 1) spi_cyp_diplotype_cohort_mappings(h->ctx2, &pr, n, sets.data(), calls.data(), nullptr, 0, rv.data(), mappings.data(), rcs.data());
+        // cyp2d6_consensus_support.json: the calls also hand out their consensuses (the calls themselves are the same), for one support pass over the group below
+        bool want_support = false;
+        for (uint32_t k = 0; k < n; ++k) want_support |= h->cyp_consensus_support && !typed[k]->debug.empty();
+        // (a consensus has at most 65,534 bases, like a read; the block is SP_CYP_MAXCONS x that = 4 MB of host memory per sample of the group while the lane runs,
+        //  256 MB for a group of 64: sized by the limit, not by the reads, because a consensus over offset reads may be longer than any one of its segments)
+        const uint32_t cons_cap = want_support ? 65536u : 0u;
+        const size_t cons_block = (size_t)SP_CYP_MAXCONS * cons_cap;
+        std::vector<char> cons(want_support ? cons_block * n : 0, '\0');
+        char* cons_out = want_support ? cons.data() : nullptr;
+        if (n > 1) spi_cyp_diplotype_cohort_mappings(h->ctx2, &pr, n, sets.data(), calls.data(), cons_out, cons_cap, rv.data(), mappings.data(), rcs.data());
+        std::vector<uint8_t> packaged(n, 0);
         for (uint32_t k = 0; k < n; ++k) {
             CypLane* L = &typed[k]->cyp;
             if (rcs[k] != SP_OK) {
                 // alone: the only sample of the lane, or one the cohort call failed (the context's error text may be another sample's)
-                const int32_t rc = spi_cyp_diplotype_mappings(h->ctx2, &pr, sets[k], &calls[k], nullptr, 0, &rv[k], &mappings[k]);
+                const int32_t rc = spi_cyp_diplotype_mappings(h->ctx2, &pr, sets[k], &calls[k], cons_out ? cons_out + cons_block * k : nullptr, cons_cap, &rv[k], &mappings[k]);
                 if (rc != SP_OK) { L->rc = rc; L->err = "sp_cyp_diplotype: " + opt(sp_last_error(h->ctx2)); continue; }
             }
             cyp_package(h, pr, calls[k], rv[k], mappings[k], orders[k], typed[k]->debug, L);
+            packaged[k] = L->rc == SP_OK;
+        }
+        if (want_support) {
+            // one pass over the samples that have a debug folder and a call (status 0: the others write no file); the others are handed over as failed calls, which own nothing
+            std::vector<sp_cyp_call> sc(calls); std::vector<sp_cyp_read_mapping> flat; std::vector<uint64_t> moff(n + 1, 0); std::vector<uint32_t> on;
+            uint64_t n_cols = 0;
+            for (uint32_t k = 0; k < n; ++k) {
+                const bool take = packaged[k] && !typed[k]->debug.empty() && calls[k].status == 0;
+                if (take) {
+                    on.push_back(k); flat.insert(flat.end(), mappings[k].begin(), mappings[k].end());
+                    for (int32_t x = 0; x < calls[k].n_consensus && x < SP_CYP_MAXCONS; ++x) n_cols += strnlen(cons.data() + cons_block * k + (size_t)x * cons_cap, cons_cap);
+                } else sc[k].status = -1;
+                moff[k + 1] = flat.size();
+            }
+            if (!on.empty()) {
+                std::vector<uint64_t> off((size_t)n * SP_CYP_MAXCONS + 1, 0); std::vector<sp_pileup_col> cols((size_t)n_cols + 1); std::vector<sp_support_summary> sm((size_t)n * SP_CYP_MAXCONS);
+                int32_t rc = sp_cyp_consensus_support_cohort(h->ctx2, n, sets.data(), sc.data(), cons.data(), cons_cap, flat.data(), moff.data(), off.data(), cols.data(), n_cols, sm.data());
+                if (rc == SP_OK) {
+                    for (uint32_t k : on) cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data() + (size_t)k * SP_CYP_MAXCONS, cols.data(), sm.data() + (size_t)k * SP_CYP_MAXCONS, typed[k]->debug, &typed[k]->cyp);
+                } else for (uint32_t k : on) {
+                    // the shared pass failed: sample by sample, and only the samples whose own pass fails are failed (alone in the pass: that failure is its own)
+                    CypLane* L = &typed[k]->cyp;
+                    if (on.size() > 1) rc = sp_cyp_consensus_support(h->ctx2, sets[k], &calls[k], cons.data() + cons_block * k, cons_cap, mappings[k].data(), mappings[k].size(), off.data(), cols.data(), n_cols, sm.data());
+                    if (rc != SP_OK) { L->rc = rc; L->err = "sp_cyp_consensus_support: " + opt(sp_last_error(h->ctx2)); continue; }
+                    cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data(), cols.data(), sm.data(), typed[k]->debug, L);
+                }
+            }
         }
     }
     for (sp_seqset* s : sets) sp_seqset_free(s);
@@ -1032,6 +1085,11 @@ int32_t sp_starphase_set_hla_debug_mappings(sp_starphase* h, int32_t on) {
 int32_t sp_starphase_set_consensus_support(sp_starphase* h, int32_t on) {
     if (!h) return SP_ERR_INVALID_ARG;
     h->consensus_support = on ? 1 : 0;
+    return SP_OK;
+}
+int32_t sp_starphase_set_cyp_consensus_support(sp_starphase* h, int32_t on) {
+    if (!h) return SP_ERR_INVALID_ARG;
+    h->cyp_consensus_support = on ? 1 : 0;
     return SP_OK;
 }
 int32_t sp_starphase_set_read_debug(sp_starphase* h, int32_t enable) {

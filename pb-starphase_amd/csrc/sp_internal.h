@@ -186,6 +186,7 @@ enum { SPC_K1_ACTIVE = 0, SPC_K1_EXECUTED, SPC_K1_RESUMED, SPC_K1_BYTES, SPC_CON
 unsigned long long* sp_counters(sp_ctx* ctx);
 void* sp_scratch(sp_ctx* ctx, size_t bytes);
 void* sp_pool(sp_ctx* ctx, const char* name, size_t bytes);
+size_t sp_pool_bytes(const sp_ctx* ctx, const char* name);   // what the named pooled device buffer holds now (0: none yet)
 void* sp_host_pool(sp_ctx* ctx, const char* name, size_t bytes);
 int   sp_fail(sp_ctx* ctx, int code, const std::string& msg);
 #define SP_HIP_CHECK(ctx, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) \

@@ -1,6 +1,6 @@
 // sp_pileup.hip -- many alignments -> integer counts per target column (sp_pileup_batch), and what is built on it: the support of the consensuses of an HLA gene call
-// by their member reads (sp_hla_consensus_support*), its summary rule and the `consensus_support.json` debug file (host only).  Contract: include/starphase_hip.h;
-// design: DESIGN.md section 7.2.
+// by their member reads (sp_hla_consensus_support*), its summary rule and the `consensus_support.json` debug file (host only); and sp_align_pileup_batch: alignment,
+// pileup and summary in one device-resident pass (the CYP2D6 support of sp_cyp.hip runs on it).  Contract: include/starphase_hip.h; design: DESIGN.md section 7.2.
 #include "sp_internal.h"
 #include "sp_json.h"
 #include <algorithm>
@@ -32,6 +32,37 @@ __device__ __forceinline__ void pu_add(uint32_t* lds, int col, uint32_t op, cons
     atomicAdd(&lds[plane * PU_STRIDE + col], 1u);
 }
 
+// one alignment under one tile: the wave takes the row's ops 64 at a time (a wave-wide prefix sum gives every op its first target column and query base) and adds the
+// columns inside [c0, c1) to the tile's planes.  row / n_ops / b_start / a_start are wave-uniform.
+__device__ __forceinline__ void pu_pair(uint32_t* lds, int c0, int c1, const uint32_t* qwords, const uint32_t* __restrict__ row, uint32_t n_ops, int b_start, int a_start, int lane) {
+    int tpos = b_start, qpos = a_start;                                                // first target column / query base of the chunk (wave-uniform)
+    for (uint32_t k0 = 0; k0 < n_ops && tpos <= c1; k0 += SP_WAVE) {                   // (an 'I' op at column c1 counts for column c1 - 1: <=)
+        const bool live = k0 + lane < n_ops;
+        const uint32_t w = live ? row[k0 + lane] : 0u;
+        const uint32_t op = w & 15u; const int n = (int)(w >> 4);
+        const int tl = (op == 7u || op == 8u || op == 2u) ? n : 0, ql = (op == 7u || op == 8u || op == 1u) ? n : 0;
+        int ts = tl, qs = ql;                                                          // inclusive prefix sums over the chunk
+#pragma unroll
+        for (int d = 1; d < SP_WAVE; d <<= 1) {
+            const int u = __shfl_up(ts, d), v = __shfl_up(qs, d);
+            if (lane >= d) { ts += u; qs += v; }
+        }
+        const int t0 = tpos + ts - tl, q0 = qpos + qs - ql;                            // this op's first target column and query base
+        tpos += __shfl(ts, SP_WAVE - 1); qpos += __shfl(qs, SP_WAVE - 1);
+        if (live && op == 1u && t0 - 1 >= c0 && t0 - 1 < c1) atomicAdd(&lds[PU_INS * PU_STRIDE + (t0 - 1 - c0)], 1u);
+        const int lo = max(t0, c0), hi = min(t0 + tl, c1);                             // the op's columns inside the tile
+        const bool hit = live && tl > 0 && lo < hi;
+        if (hit && tl <= PU_SHORT) for (int c = lo; c < hi; ++c) pu_add(lds, c - c0, op, qwords, q0 + (c - t0));
+        unsigned long long longs = __ballot(hit && tl > PU_SHORT);
+        while (longs) {                                                                // long runs: the wave's lanes across the run's columns
+            const int src = __ffsll((long long)longs) - 1; longs &= longs - 1;
+            const int rlo = __shfl(lo, src), rhi = __shfl(hi, src), rt0 = __shfl(t0, src), rq0 = __shfl(q0, src);
+            const uint32_t rop = (uint32_t)__shfl((int)op, src);
+            for (int c = rlo + lane; c < rhi; c += SP_WAVE) pu_add(lds, c - c0, rop, qwords, rq0 + (c - rt0));
+        }
+    }
+}
+
 __global__ __launch_bounds__(PU_WAVES * SP_WAVE) void pileup_kernel(SeqSetView A, const int32_t* __restrict__ t_len, const PuPair* __restrict__ pairs, const uint32_t* __restrict__ bucket_off,
                                                                     const uint32_t* __restrict__ ops, const PuTile* __restrict__ tiles, const uint64_t* __restrict__ col_offset,
                                                                     uint32_t* __restrict__ out) {
@@ -43,37 +74,122 @@ __global__ __launch_bounds__(PU_WAVES * SP_WAVE) void pileup_kernel(SeqSetView A
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (uint32_t p = bucket_off[tile.target] + wave; p < bucket_off[tile.target + 1]; p += PU_WAVES) {
         const PuPair pr = pairs[p];
-        const uint32_t* qwords = A.words + A.word_off[pr.a];
-        int tpos = pr.b_start, qpos = pr.a_start;                                      // first target column / query base of the chunk (wave-uniform)
-        for (uint32_t k0 = 0; k0 < pr.n_ops && tpos <= c1; k0 += SP_WAVE) {            // (an 'I' op at column c1 counts for column c1 - 1: <=)
-            const bool live = k0 + lane < pr.n_ops;
-            const uint32_t w = live ? ops[pr.op_off + k0 + lane] : 0u;
-            const uint32_t op = w & 15u; const int n = (int)(w >> 4);
-            const int tl = (op == 7u || op == 8u || op == 2u) ? n : 0, ql = (op == 7u || op == 8u || op == 1u) ? n : 0;
-            int ts = tl, qs = ql;                                                      // inclusive prefix sums over the chunk
-#pragma unroll
-            for (int d = 1; d < SP_WAVE; d <<= 1) {
-                const int u = __shfl_up(ts, d), v = __shfl_up(qs, d);
-                if (lane >= d) { ts += u; qs += v; }
-            }
-            const int t0 = tpos + ts - tl, q0 = qpos + qs - ql;                        // this op's first target column and query base
-            tpos += __shfl(ts, SP_WAVE - 1); qpos += __shfl(qs, SP_WAVE - 1);
-            if (live && op == 1u && t0 - 1 >= c0 && t0 - 1 < c1) atomicAdd(&lds[PU_INS * PU_STRIDE + (t0 - 1 - c0)], 1u);
-            const int lo = max(t0, c0), hi = min(t0 + tl, c1);                         // the op's columns inside the tile
-            const bool hit = live && tl > 0 && lo < hi;
-            if (hit && tl <= PU_SHORT) for (int c = lo; c < hi; ++c) pu_add(lds, c - c0, op, qwords, q0 + (c - t0));
-            unsigned long long longs = __ballot(hit && tl > PU_SHORT);
-            while (longs) {                                                            // long runs: the wave's lanes across the run's columns
-                const int src = __ffsll((long long)longs) - 1; longs &= longs - 1;
-                const int rlo = __shfl(lo, src), rhi = __shfl(hi, src), rt0 = __shfl(t0, src), rq0 = __shfl(q0, src);
-                const uint32_t rop = (uint32_t)__shfl((int)op, src);
-                for (int c = rlo + lane; c < rhi; c += SP_WAVE) pu_add(lds, c - c0, rop, qwords, rq0 + (c - rt0));
-            }
-        }
+        pu_pair(lds, c0, c1, A.words + A.word_off[pr.a], ops + pr.op_off, pr.n_ops, pr.b_start, pr.a_start, lane);
     }
     __syncthreads();
     uint32_t* dst = out + (col_offset[tile.target] + (uint64_t)c0) * 8u;                // the tile as an array of sp_pileup_col: consecutive threads, consecutive words
     for (int i = threadIdx.x; i < (c1 - c0) * 8; i += PU_WAVES * SP_WAVE) dst[i] = lds[(i & 7) * PU_STRIDE + (i >> 3)];
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// sp_align_pileup_batch: the same tile, fed from what the map kernel (sp_launch_affine_map) left in device memory.  `order` lists the batch's pairs by target and, inside
+// a target, in the order given, so the pairs of target t that fall into slice s of the batch are order[boff[t * (n_slices + 1) + s] .. boff[t * (n_slices + 1) + s + 1]).
+// Slice 0 starts every tile from zero; a later slice loads the tile as the slices before it left it, adds its own pairs and stores it again -- the workgroup is the
+// tile's one owner in its launch, the launches follow one another on one stream: plain loads and stores.  A tile none of the slice's pairs names is left as it is.
+// The load is the store's transposition: 32 lanes write bank 4 f + column of the planes (PU_STRIDE = 4 mod 32), no two alike (derived from the bank rule, as above).
+// ------------------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t AP_LOST = 0xFFFFFFFFu;                   // n_cigar of a walk that did not arrive, op_off of a row that was not kept (sp_launch_affine_map)
+constexpr uint64_t AP_NO_OPS = ~0ull;
+
+__global__ __launch_bounds__(PU_WAVES * SP_WAVE) void pileup_rows_kernel(SeqSetView A, const int32_t* __restrict__ t_len, const sp_pair* __restrict__ pairs, const sp_affine_aln* __restrict__ aln,
+                                                                         const uint32_t* __restrict__ n_cigar, const uint64_t* __restrict__ op_off, const uint32_t* __restrict__ ops,
+                                                                         const uint32_t* __restrict__ order, const uint32_t* __restrict__ boff, uint32_t n_slices, uint32_t slice,
+                                                                         const PuTile* __restrict__ tiles, const uint64_t* __restrict__ col_offset, uint32_t* __restrict__ out) {
+    extern __shared__ uint32_t lds[];
+    const PuTile tile = tiles[blockIdx.x];
+    const uint32_t k_lo = boff[(size_t)tile.target * (n_slices + 1) + slice], k_hi = boff[(size_t)tile.target * (n_slices + 1) + slice + 1];
+    if (slice > 0 && k_lo == k_hi) return;                                              // (uniform over the workgroup)
+    const int c0 = (int)tile.c0, c1 = min(c0 + PU_TILE, t_len[tile.target]);
+    uint32_t* dst = out + (col_offset[tile.target] + (uint64_t)c0) * 8u;
+    if (slice == 0) for (int i = threadIdx.x; i < 8 * PU_STRIDE; i += PU_WAVES * SP_WAVE) lds[i] = 0u;
+    else for (int i = threadIdx.x; i < (c1 - c0) * 8; i += PU_WAVES * SP_WAVE) lds[(i & 7) * PU_STRIDE + (i >> 3)] = dst[i];
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (uint32_t k = k_lo + wave; k < k_hi; k += PU_WAVES) {
+        const uint32_t p = order[k], n_ops = n_cigar[p];
+        const uint64_t off = op_off[p];
+        if (n_ops == 0 || n_ops == AP_LOST || off == AP_NO_OPS) continue;               // (wave-uniform; the host reports the last two)
+        const sp_affine_aln g = aln[p];
+        if (g.score <= 0) continue;
+        pu_pair(lds, c0, c1, A.words + A.word_off[pairs[p].a], ops + off, n_ops, g.b_start, g.a_start, lane);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < (c1 - c0) * 8; i += PU_WAVES * SP_WAVE) dst[i] = lds[(i & 7) * PU_STRIDE + (i >> 3)];
+}
+
+// what the host has to know about a slice before it piles it up: status[0] = a walk got lost, status[1] = an alignment with more runs than a row keeps
+__global__ void ap_status_kernel(const sp_affine_aln* __restrict__ aln, const uint32_t* __restrict__ n_cigar, const uint64_t* __restrict__ op_off, uint32_t n, uint32_t* __restrict__ status) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (n_cigar[i] == AP_LOST) status[0] = 1u;
+    else if (aln[i].score > 0 && op_off[i] == AP_NO_OPS) status[1] = 1u;
+}
+
+// sp_support_summarize per target, on the device.  One workgroup per target, one pass over its columns: the minimum depth and the contested columns fall out of it, and a
+// histogram of the depths in LDS gives the lower median -- element (length - 1) / 2 of the sorted depths is the first bin at which the running count exceeds that rank.
+// A depth is at most the number of pairs that name the target.  With more possible depths than AP_BINS the bins are W = ceil(range / AP_BINS) depths wide, and the bin the
+// median falls into is resolved by another pass over the columns on that bin's W depths alone (rank reduced by the count below the bin), until W is 1.  Integers only.
+constexpr int AP_SUM_THREADS = 256, AP_BINS = SP_SUPPORT_HIST_BINS;
+static_assert(AP_BINS % AP_SUM_THREADS == 0, "bins per thread");
+
+__global__ __launch_bounds__(AP_SUM_THREADS) void support_summary_kernel(const uint32_t* __restrict__ table, const uint64_t* __restrict__ col_offset, const int32_t* __restrict__ t_len,
+                                                                          const sp_affine_aln* __restrict__ aln, const uint32_t* __restrict__ order, const uint32_t* __restrict__ boff,
+                                                                          uint32_t n_slices, const uint32_t* __restrict__ n_members, sp_support_summary* __restrict__ out) {
+    __shared__ uint32_t hist[AP_BINS], part[AP_SUM_THREADS], s_min, s_cont, s_al, s_lo, s_k;
+    const uint32_t t = blockIdx.x, tid = threadIdx.x;
+    const uint32_t len = (uint32_t)t_len[t], k_lo = boff[(size_t)t * (n_slices + 1)], k_hi = boff[(size_t)t * (n_slices + 1) + n_slices];
+    if (tid == 0) { s_min = 0xFFFFFFFFu; s_cont = 0; s_al = 0; }
+    __syncthreads();
+    {
+        uint32_t al = 0;
+        for (uint32_t k = k_lo + tid; k < k_hi; k += AP_SUM_THREADS) al += aln[order[k]].score > 0 ? 1u : 0u;
+        if (al) atomicAdd(&s_al, al);
+    }
+    const uint4* cols = (const uint4*)(table + col_offset[t] * 8u);                     // a column = two 16-byte halves: depth eq x0 x1 | x2 x3 del ins
+    uint32_t lo = 0, range = k_hi - k_lo + 1, rank = len ? (len - 1) / 2 : 0;
+    for (bool first = true; len > 0; first = false) {
+        const uint32_t W = (range + AP_BINS - 1) / AP_BINS;
+        for (int i = tid; i < AP_BINS; i += AP_SUM_THREADS) hist[i] = 0u;
+        __syncthreads();
+        uint32_t mn = 0xFFFFFFFFu, cont = 0;
+        for (uint32_t j = tid; j < len; j += AP_SUM_THREADS) {
+            const uint4 a = cols[2 * (size_t)j];
+            const uint32_t depth = a.x;
+            if (first) {
+                const uint32_t ins = cols[2 * (size_t)j + 1].w;
+                mn = min(mn, depth);
+                cont += ((depth > 0 && 2ull * a.y <= depth) || 2ull * ins > depth) ? 1u : 0u;
+            }
+            if (depth >= lo && depth - lo < range) atomicAdd(&hist[(depth - lo) / W], 1u);
+        }
+        if (first) { atomicMin(&s_min, mn); if (cont) atomicAdd(&s_cont, cont); }
+        __syncthreads();
+        {
+            uint32_t s = 0;
+            for (int i = 0; i < AP_BINS / AP_SUM_THREADS; ++i) s += hist[tid * (AP_BINS / AP_SUM_THREADS) + i];
+            part[tid] = s;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t cum = 0; int g = 0;
+            while (g < AP_SUM_THREADS - 1 && cum + part[g] <= rank) cum += part[g++];
+            int b = g * (AP_BINS / AP_SUM_THREADS);
+            while (b < AP_BINS - 1 && cum + hist[b] <= rank) cum += hist[b++];
+            s_lo = lo + (uint32_t)b * W; s_k = rank - cum;
+        }
+        __syncthreads();
+        lo = s_lo; rank = s_k;
+        if (W == 1) break;
+        range = W;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        sp_support_summary sm;
+        const uint32_t named = k_hi - k_lo;
+        sm.n_members = n_members ? n_members[t] : named; sm.n_aligned = s_al; sm.n_unaligned = named - s_al; sm.length = len;
+        sm.min_depth = len ? s_min : 0u; sm.median_depth = len ? lo : 0u; sm.n_contested = s_cont; sm.reserved_ = 0;
+        out[t] = sm;
+    }
 }
 
 static bool contested_col(const sp_pileup_col& c) { return (c.depth > 0 && 2ull * c.eq <= c.depth) || 2ull * c.ins > c.depth; }
@@ -174,6 +290,120 @@ int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, con
         if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "pileup launch failed");
     }
     SP_HIP_CHECK(ctx, hipMemcpyAsync(out, d_out, n_cols * sizeof(sp_pileup_col), hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return SP_OK;
+}
+
+int32_t sp_align_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, const uint64_t* col_offset,
+                              sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (!A || !B || !opts || !col_offset || (n_pairs && !pairs)) return sp_fail(ctx, SP_ERR_INVALID_ARG, "align_pileup: null argument");
+    if (n_pairs > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "align_pileup: too many pairs");
+    const uint32_t n_t = B->n, n = (uint32_t)n_pairs;
+    if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "align_pileup: col_offset[0] must be 0");
+    for (uint32_t t = 0; t < n_t; ++t)
+        if (col_offset[t + 1] < col_offset[t] || col_offset[t + 1] - col_offset[t] != (uint64_t)B->h_len[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "align_pileup: col_offset does not follow the target lengths");
+    const uint64_t n_cols = col_offset[n_t];
+    // ---- the pairs by target, from `pairs` alone: target t's pairs of slice s are order[boff[t * (n_slices + 1) + s] ...) (pileup_rows_kernel)
+    const uint32_t n_slices = std::max<uint32_t>(1, (n + SP_ALIGN_PILEUP_SLICE - 1) / SP_ALIGN_PILEUP_SLICE);
+    std::vector<uint32_t> boff((size_t)n_t * (n_slices + 1) + 1, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (pairs[i].a >= A->n || pairs[i].b >= B->n) return sp_fail(ctx, SP_ERR_INVALID_ARG, "align_pileup: index out of range");
+        ++boff[(size_t)pairs[i].b * (n_slices + 1) + i / SP_ALIGN_PILEUP_SLICE + 1];
+    }
+    if (n_pairs == 0 && n_t == 0) return SP_OK;
+    const bool want_table = (cols || summaries) && n_t > 0;
+    if (!aln && !want_table) return SP_OK;
+    // boff[t * (S + 1) + s + 1] holds the count of (t, s): into running offsets; entry t * (S + 1) is where target t begins = where target t - 1 ended
+    {
+        uint32_t run = 0;
+        for (uint32_t t = 0; t < n_t; ++t) {
+            uint32_t* row = boff.data() + (size_t)t * (n_slices + 1);
+            row[0] = run;
+            for (uint32_t s2 = 0; s2 < n_slices; ++s2) { run += row[s2 + 1]; row[s2 + 1] = run; }
+        }
+    }
+    uint64_t n_tiles = 0;
+    if (want_table) for (uint32_t t = 0; t < n_t; ++t) n_tiles += ((uint64_t)B->h_len[t] + PU_TILE - 1) / PU_TILE;
+    if (n_tiles > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "align_pileup: too many tiles");
+    (void)hipSetDevice(ctx->device);
+    // ---- one staging block, one copy: the pair list as given, the order, the offsets, tiles, column offsets, member counts
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t at_pairs = 0, at_order = up16(at_pairs + sizeof(sp_pair) * (size_t)n), at_boff = up16(at_order + 4 * (size_t)n), at_tiles = up16(at_boff + 4 * boff.size()),
+                 at_cols = up16(at_tiles + sizeof(PuTile) * (size_t)n_tiles), at_mem = up16(at_cols + 8 * ((size_t)n_t + 1)), in_bytes = up16(at_mem + 4 * (size_t)n_t) + 16;
+    uint8_t* h_in = (uint8_t*)sp_host_pool(ctx, "appile_in", in_bytes);
+    uint64_t* h_st = (uint64_t*)sp_host_pool(ctx, "appile_st", 16);
+    uint8_t* d_in = (uint8_t*)sp_pool(ctx, "appile_in", in_bytes);
+    sp_affine_aln* d_aln = (sp_affine_aln*)sp_pool(ctx, "appile_aln", std::max<size_t>(16, (size_t)n * sizeof(sp_affine_aln)));
+    uint32_t* d_nc = (uint32_t*)sp_pool(ctx, "appile_nc", std::max<size_t>(16, (size_t)n * 4));
+    uint64_t* d_off = (uint64_t*)sp_pool(ctx, "appile_off", (size_t)n * 8 + 16);                   // (+ the cursor and the two status words)
+    uint32_t* d_table = want_table ? (uint32_t*)sp_pool(ctx, "appile_out", std::max<size_t>(16, n_cols * sizeof(sp_pileup_col))) : nullptr;
+    sp_support_summary* d_sum = summaries && n_t ? (sp_support_summary*)sp_pool(ctx, "appile_sum", (size_t)n_t * sizeof(sp_support_summary)) : nullptr;
+    if (!h_in || !h_st || !d_in || !d_aln || !d_nc || !d_off || (want_table && !d_table) || (summaries && n_t && !d_sum)) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "align_pileup buffers");
+    unsigned long long* d_cur = (unsigned long long*)(d_off + n); uint32_t* d_status = (uint32_t*)(d_off + n + 1);
+    {
+        if (n) std::memcpy(h_in + at_pairs, pairs, sizeof(sp_pair) * (size_t)n);
+        uint32_t* ho = (uint32_t*)(h_in + at_order);
+        std::vector<uint32_t> at(n_t);
+        for (uint32_t t = 0; t < n_t; ++t) at[t] = boff[(size_t)t * (n_slices + 1)];
+        for (uint32_t i = 0; i < n; ++i) ho[at[pairs[i].b]++] = i;                                 // (by target, then in the order given: a slice's pairs of a target are consecutive)
+        std::memcpy(h_in + at_boff, boff.data(), 4 * boff.size());
+        std::memcpy(h_in + at_cols, col_offset, 8 * ((size_t)n_t + 1));
+        if (n_members && n_t) std::memcpy(h_in + at_mem, n_members, 4 * (size_t)n_t);
+        PuTile* ht = (PuTile*)(h_in + at_tiles); uint64_t x = 0;
+        if (want_table) for (uint32_t t = 0; t < n_t; ++t) for (int32_t c0 = 0; c0 < B->h_len[t]; c0 += PU_TILE) ht[x++] = PuTile{ t, (uint32_t)c0 };
+    }
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const sp_pair* d_pairs = (const sp_pair*)(d_in + at_pairs);
+    const uint32_t* d_order = (const uint32_t*)(d_in + at_order); const uint32_t* d_boff = (const uint32_t*)(d_in + at_boff);
+    if (n_tiles) {   // more dynamic LDS than the 64 KiB a kernel gets unasked: said once per device of the process
+        static std::atomic<uint64_t> lds_set(0);
+        const uint64_t bit = 1ull << (ctx->device & 63);
+        if (!(lds_set.load() & bit)) {
+            SP_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)pileup_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PU_LDS_BYTES));
+            lds_set.fetch_or(bit);
+        }
+    }
+    // ---- slice by slice: the map into the op buffer (run again on a larger one when it asked for more: a warm context does not), what the host must know, the pileup
+    uint64_t ops_cap = std::max<uint64_t>(sp_pool_bytes(ctx, "appile_ops") / 4, (uint64_t)std::min<uint32_t>(std::max<uint32_t>(n, 1), SP_ALIGN_PILEUP_SLICE) * 64);
+    for (uint32_t s2 = 0; s2 < n_slices; ++s2) {
+        const uint32_t p0 = s2 * SP_ALIGN_PILEUP_SLICE, m = std::min<uint32_t>(SP_ALIGN_PILEUP_SLICE, n - p0);
+        uint32_t* d_ops = nullptr;
+        for (int attempt = 0; m > 0; ++attempt) {
+            d_ops = (uint32_t*)sp_pool(ctx, "appile_ops", (size_t)ops_cap * 4);
+            if (!d_ops) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "align_pileup: op rows");
+            SP_HIP_CHECK(ctx, hipMemsetAsync(d_cur, 0, 16, ctx->stream));
+            const int rc = sp_launch_affine_map(ctx, A, B, d_pairs + p0, m, *opts, d_aln + p0, d_nc + p0, d_off + p0, d_ops, ops_cap, d_cur, "align_pileup_map");
+            if (rc != SP_OK) return rc;
+            hipLaunchKernelGGL(ap_status_kernel, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, d_aln + p0, d_nc + p0, d_off + p0, m, d_status);
+            SP_HIP_CHECK(ctx, hipMemcpyAsync(h_st, d_cur, 16, hipMemcpyDeviceToHost, ctx->stream));
+            if (hipStreamSynchronize(ctx->stream) != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "align_pileup: the map kernel failed");
+            if (h_st[0] <= ops_cap) break;
+            if (attempt == 1) return sp_fail(ctx, SP_ERR_HIP, "align_pileup: the op buffer did not hold a second run");
+            ops_cap = h_st[0];
+        }
+        if (m > 0) {
+            const uint32_t* st = (const uint32_t*)(h_st + 1);
+            if (st[0]) return sp_fail(ctx, SP_ERR_HIP, "align_pileup: a walk did not reach the cell its path started in");
+            if (st[1]) return sp_fail(ctx, SP_ERR_CAPACITY, "align_pileup: an alignment of more than 4,096 runs");
+        }
+        if (n_tiles) {
+            ProfScope ps(ctx, "align_pileup_pile", n_cols);
+            hipLaunchKernelGGL(pileup_rows_kernel, dim3((unsigned)n_tiles), dim3(PU_WAVES * SP_WAVE), PU_LDS_BYTES, ctx->stream, A->view(), B->d_len, d_pairs, d_aln, d_nc, d_off, d_ops,
+                               d_order, d_boff, n_slices, s2, (const PuTile*)(d_in + at_tiles), (const uint64_t*)(d_in + at_cols), d_table);
+            if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "align_pileup: pileup launch failed");
+        }
+    }
+    if (d_sum) {
+        ProfScope ps(ctx, "align_pileup_summary", n_cols);
+        hipLaunchKernelGGL(support_summary_kernel, dim3(n_t), dim3(AP_SUM_THREADS), 0, ctx->stream, d_table, (const uint64_t*)(d_in + at_cols), B->d_len, d_aln, d_order, d_boff, n_slices,
+                           n_members ? (const uint32_t*)(d_in + at_mem) : nullptr, d_sum);
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "align_pileup: summary launch failed");
+    }
+    // ---- only what was asked for comes back
+    if (aln && n) SP_HIP_CHECK(ctx, hipMemcpyAsync(aln, d_aln, (size_t)n * sizeof(sp_affine_aln), hipMemcpyDeviceToHost, ctx->stream));
+    if (cols && n_cols) SP_HIP_CHECK(ctx, hipMemcpyAsync(cols, d_table, n_cols * sizeof(sp_pileup_col), hipMemcpyDeviceToHost, ctx->stream));
+    if (d_sum) SP_HIP_CHECK(ctx, hipMemcpyAsync(summaries, d_sum, (size_t)n_t * sizeof(sp_support_summary), hipMemcpyDeviceToHost, ctx->stream));
     SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return SP_OK;
 }

@@ -156,6 +156,9 @@ def _lib():
         "sp_hla_debug_save": (_i32, [_vp, _s]),
         "sp_cyp_diplotype_mappings": (_i32, [_vp, P(ffi.sp_cyp_problem), _vp, P(ffi.sp_cyp_call), _s, _u32, P(ffi.sp_cyp_region_variants), P(sp_cyp_read_mapping),
                                              _u64, P(_u64)]),
+        "sp_cyp_consensus_support": (_i32, [_vp, _vp, P(ffi.sp_cyp_call), _vp, _u32, P(sp_cyp_read_mapping), _u64, _vp, _vp, _u64, _vp]),
+        "sp_cyp_consensus_support_cohort": (_i32, [_vp, _u32, P(_vp), P(ffi.sp_cyp_call), _vp, _u32, P(sp_cyp_read_mapping), _vp, _vp, _vp, _u64, _vp]),
+        "sp_cyp_support_json": (_i32, [P(ffi.sp_cyp_call), _vp, _u32, _vp, _vp, _vp, _s, _u64, P(_u64)]),
         "sp_diplotype_settings_default": (None, [P(sp_diplotype_settings)]),
         "sp_diplotype_settings_check": (_i32, [P(sp_diplotype_settings), P(sp_sample_inputs), _s, _u32]),
         "sp_starphase_create": (_i32, [_vp, _s, _s, P(sp_diplotype_settings), P(_vp)]),
@@ -167,6 +170,7 @@ def _lib():
         "sp_starphase_set_read_debug": (_i32, [_vp, _i32]),
         "sp_starphase_set_hla_debug_mappings": (_i32, [_vp, _i32]),
         "sp_starphase_set_consensus_support": (_i32, [_vp, _i32]),
+        "sp_starphase_set_cyp_consensus_support": (_i32, [_vp, _i32]),
         "sp_starphase_call_batch": (_i32, [_vp, _u32, P(sp_sample_inputs), P(_s), P(sp_batch_options), P(_vp), P(_i32)]),
         "sp_starphase_sample_error": (_s, [_vp, _u32]),
         "sp_starphase_sample_warnings": (_s, [_vp, _u32]),
@@ -946,9 +950,10 @@ def settings_check(bams=(), vcf=None, **kw):
 
 class Starphase:
     """sp_starphase: a database + reference loaded once, sp_starphase_call per sample.  ctx: a Context or None (the handle makes its own).
-    consensus_support=True: set_consensus_support() at once (a call with a debug folder also writes consensus_support.json)."""
+    consensus_support=True: set_consensus_support() at once (a call with a debug folder also writes consensus_support.json); cyp_consensus_support=True:
+    set_cyp_consensus_support() at once (it also writes cyp2d6_consensus_support.json)."""
 
-    def __init__(self, database, reference=None, ctx=None, consensus_support=False, **settings):
+    def __init__(self, database, reference=None, ctx=None, consensus_support=False, cyp_consensus_support=False, **settings):
         self._h = _vp()
         self._s = _settings(**settings)
         rc = _lib().sp_starphase_create(ctx._h if ctx is not None else None, _b(database), _b(reference), C.byref(self._s), C.byref(self._h))
@@ -956,6 +961,8 @@ class Starphase:
             raise StarphaseError(rc, _d(_lib().sp_starphase_last_error(None)))
         if consensus_support:
             self.set_consensus_support(True)
+        if cyp_consensus_support:
+            self.set_cyp_consensus_support(True)
 
     def close(self):
         if self._h:
@@ -974,6 +981,14 @@ class Starphase:
         rc = _lib().sp_starphase_set_consensus_support(self._h, 1 if on else 0)
         if rc != SP_OK:
             raise StarphaseError(rc, "sp_starphase_set_consensus_support")
+        return self
+
+    def set_cyp_consensus_support(self, on=True):
+        """sp_starphase_set_cyp_consensus_support: a debug folder also receives cyp2d6_consensus_support.json (per CYP2D6 consensus region: how many member reads span,
+        agree with or contest each column); off by default"""
+        rc = _lib().sp_starphase_set_cyp_consensus_support(self._h, 1 if on else 0)
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_starphase_set_cyp_consensus_support")
         return self
 
     def set_hla_debug_mappings(self, on=True):
@@ -1078,3 +1093,103 @@ def cyp_diplotype_mappings(cdb, reads, cap=None, **overrides):
     if rc != SP_OK:
         raise StarphaseError(rc, "sp_cyp_diplotype_mappings")
     return call, [(m.read, m.read_start, m.read_end, m.consensus, m.index_label.decode()) for m in buf[:n.value]]
+
+
+def cyp_call_with_consensus(cdb, reads, cons_cap=65536, **overrides):
+    """sp_cyp_diplotype_mappings on a CypDb, keeping what sp_cyp_consensus_support takes: (sp_cyp_call, the consensus block (ctypes buffer of SP_CYP_MAXCONS * cons_cap
+    bytes), [sp_cyp_read_mapping])"""
+    return cyp_problem_call_with_consensus(cdb.ctx, cdb.problem(**overrides), reads, cons_cap)
+
+
+def cyp_problem_call_with_consensus(ctx, pr, reads, cons_cap=65536):
+    """the same on an sp_cyp_problem (ffi.Context.cyp_problem)"""
+    call = ffi.sp_cyp_call()
+    n = C.c_uint64(0)
+    cap = 64 * reads.n + 64
+    buf = (sp_cyp_read_mapping * max(1, cap))()
+    cons = C.create_string_buffer(ffi.SP_CYP_MAXCONS * cons_cap)
+    ctx.check(_lib().sp_cyp_diplotype_mappings(ctx._h, C.byref(pr), reads._h, C.byref(call), cons, cons_cap, None, buf, cap, C.byref(n)))
+    return call, cons, [buf[i] for i in range(n.value)]
+
+
+def cyp_consensus_of(cons, cons_cap, h):
+    """consensus h of a consensus block, as text"""
+    return cons.raw[h * cons_cap:(h + 1) * cons_cap].split(b"\0", 1)[0].decode()
+
+
+def _mapping_array(mappings):
+    arr = (sp_cyp_read_mapping * max(1, len(mappings)))()
+    for i, m in enumerate(mappings):
+        arr[i] = m
+    return arr
+
+
+def cyp_consensus_support(ctx, reads, call, cons, cons_cap, mappings, want_cols=True):
+    """sp_cyp_consensus_support: call / cons / mappings as cyp_call_with_consensus returned them -> ([cols PILEUP_DTYPE per consensus] or None, [summary dict per consensus])"""
+    import numpy as np
+    H = max(0, min(call.n_consensus, ffi.SP_CYP_MAXCONS))
+    off = np.zeros(ffi.SP_CYP_MAXCONS + 1, np.uint64)
+    total = sum(len(cyp_consensus_of(cons, cons_cap, h)) for h in range(H)) if call.status == 0 else 0
+    cols = np.zeros(max(1, total), ffi.PILEUP_DTYPE) if want_cols else None
+    sm = np.zeros(ffi.SP_CYP_MAXCONS, ffi.SUPPORT_DTYPE)
+    arr = _mapping_array(mappings)
+    ctx.check(_lib().sp_cyp_consensus_support(ctx._h, reads._h, C.byref(call), C.cast(cons, _vp), cons_cap, arr, len(mappings), ffi._ptr(off), ffi._ptr(cols), total, ffi._ptr(sm)))
+    return ([cols[int(off[h]):int(off[h + 1])].copy() for h in range(H)] if want_cols else None,
+            [{n: int(sm[h][n]) for n in ffi.SUPPORT_FIELDS[:-1]} for h in range(H)])
+
+
+def cyp_consensus_support_cohort(ctx, read_sets, calls, cons_blocks, cons_cap, mapping_lists):
+    """sp_cyp_consensus_support_cohort: per sample what cyp_call_with_consensus returned -> per sample ([cols per consensus], [summary dict per consensus])"""
+    import numpy as np
+    n = len(read_sets)
+    M = ffi.SP_CYP_MAXCONS
+    carr = (ffi.sp_cyp_call * n)()
+    for i, c in enumerate(calls):
+        C.memmove(C.byref(carr[i]), C.byref(c), C.sizeof(ffi.sp_cyp_call))
+    block = C.create_string_buffer(b"".join(b.raw for b in cons_blocks), n * M * cons_cap)
+    flat = [m for ms in mapping_lists for m in ms]
+    moff = np.zeros(n + 1, np.uint64)
+    moff[1:] = np.cumsum([len(ms) for ms in mapping_lists])
+    handles = (_vp * n)(*[r._h.value if isinstance(r._h, C.c_void_p) else r._h for r in read_sets])
+    off = np.zeros(n * M + 1, np.uint64)
+    total = sum(len(cyp_consensus_of(cons_blocks[i], cons_cap, h)) for i in range(n) if calls[i].status == 0 for h in range(max(0, min(calls[i].n_consensus, M))))
+    cols = np.zeros(max(1, total), ffi.PILEUP_DTYPE)
+    sm = np.zeros(n * M, ffi.SUPPORT_DTYPE)
+    ctx.check(_lib().sp_cyp_consensus_support_cohort(ctx._h, n, handles, carr, C.cast(block, _vp), cons_cap, _mapping_array(flat), ffi._ptr(moff), ffi._ptr(off), ffi._ptr(cols), total, ffi._ptr(sm)))
+    out = []
+    for i in range(n):
+        H = max(0, min(calls[i].n_consensus, M)) if calls[i].status == 0 else 0
+        out.append(([cols[int(off[i * M + h]):int(off[i * M + h + 1])].copy() for h in range(H)], [{k: int(sm[i * M + h][k]) for k in ffi.SUPPORT_FIELDS[:-1]} for h in range(H)]))
+    return out
+
+
+def cyp_support_json(call, consensus, cols, summaries, cap=None):
+    """sp_cyp_support_json (host only): consensus = [text per consensus], cols = [PILEUP_DTYPE per consensus], summaries = [dict per consensus] -> the text of
+    cyp2d6_consensus_support.json.  cap: a buffer size to try -> (status, text, needed)"""
+    import numpy as np
+    H = len(consensus)
+    cons_cap = max([len(s) for s in consensus] + [0]) + 1
+    block = C.create_string_buffer(b"".join(s.encode().ljust(cons_cap, b"\0") for s in consensus), max(1, H * cons_cap))
+    off = np.zeros(H + 1, np.uint64)
+    off[1:] = np.cumsum([len(c) for c in cols]) if H else 0
+    table = np.ascontiguousarray(np.concatenate([np.ascontiguousarray(c, ffi.PILEUP_DTYPE) for c in cols]) if H else np.zeros(0, ffi.PILEUP_DTYPE), ffi.PILEUP_DTYPE)
+    if not len(table):
+        table = np.zeros(1, ffi.PILEUP_DTYPE)
+    sm = np.zeros(max(1, H), ffi.SUPPORT_DTYPE)
+    for h, d in enumerate(summaries):
+        for k in ffi.SUPPORT_FIELDS[:-1]:
+            sm[h][k] = int(d.get(k, 0))
+    need = _u64(0)
+    args = (C.byref(call), C.cast(block, _vp), cons_cap, ffi._ptr(off), ffi._ptr(table), ffi._ptr(sm))
+    if cap is not None:
+        buf = C.create_string_buffer(max(1, cap))
+        rc = _lib().sp_cyp_support_json(*args, buf if cap else None, cap, C.byref(need))
+        return rc, buf.value.decode() if cap else "", need.value
+    rc = _lib().sp_cyp_support_json(*args, None, 0, C.byref(need))
+    if rc not in (SP_OK, ffi.SP_ERR_CAPACITY):
+        raise StarphaseError(rc, "sp_cyp_support_json")
+    buf = C.create_string_buffer(need.value)
+    rc = _lib().sp_cyp_support_json(*args, buf, need.value, C.byref(need))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_cyp_support_json")
+    return buf.value.decode()

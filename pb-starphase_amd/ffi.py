@@ -235,6 +235,8 @@ REV_HIT_DTYPE = np.dtype([(n, np.int32) for n in ("allele", "t_len", "nm", "t_st
 # sp_pileup_batch: one record per target column; SP_PILEUP_TILE columns per workgroup, SP_PILEUP_WAVES waves per workgroup (include/starphase_hip.h)
 SP_PILEUP_TILE = 2048
 SP_PILEUP_WAVES = 4
+SP_ALIGN_PILEUP_SLICE = 4096      # sp_align_pileup_batch: pairs per slice of a batch
+SP_SUPPORT_HIST_BINS = 1024       # bins of the summary kernel's depth histogram
 PILEUP_DTYPE = np.dtype([("depth", np.uint32), ("eq", np.uint32), ("x", np.uint32, (4,)), ("del", np.uint32), ("ins", np.uint32)])       # sp_pileup_col
 SUPPORT_FIELDS = ("n_members", "n_aligned", "n_unaligned", "length", "min_depth", "median_depth", "n_contested", "reserved_")
 SUPPORT_DTYPE = np.dtype([(n, np.uint32) for n in SUPPORT_FIELDS])                                                                      # sp_support_summary
@@ -325,6 +327,7 @@ def lib():
         "sp_affine_align_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, vp, vp, u32, vp]),
         "sp_hla_realign_cigars": (i32, [vp, vp, vp, vp, u32, vp, u32, vp]),
         "sp_pileup_batch": (i32, [vp, vp, vp, vp, u64, vp, vp, u32, vp, vp, vp]),
+        "sp_align_pileup_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), vp, vp, vp, vp, vp]),
         "sp_support_summarize": (i32, [vp, u32, u32, u32, C.POINTER(sp_support_summary)]),
         "sp_support_contested": (i32, [vp, u32, vp, u32, C.POINTER(u32)]),
         "sp_hla_consensus_support": (i32, [vp, vp, u32, vp, vp, vp, C.c_char_p, C.c_char_p, vp, vp, C.POINTER(sp_support_summary), C.POINTER(sp_support_summary)]),
@@ -507,6 +510,26 @@ class Context:
         out = np.zeros(int(off[-1]), PILEUP_DTYPE)
         self.check(lib().sp_pileup_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), _ptr(aln), _ptr(cigar), cigar.shape[1], _ptr(n_cigar), _ptr(off), _ptr(out)))
         return [out[int(off[t]):int(off[t + 1])] for t in range(B.n)]
+
+    def align_pileup(self, A, B, pairs, a=1, aln=True, cols=True, summaries=True, n_members=None, col_offset=None):
+        """sp_align_pileup_batch: pairs as affine_align takes them -> (aln AFFINE_DTYPE[n] or None, [PILEUP_DTYPE array per target of B] or None,
+        [summary dict per target] or None); an output switched off is handed to the library as NULL.  col_offset: None = the one that follows B's lengths"""
+        rows = np.zeros(len(pairs), PAIR_DTYPE)
+        for i, pr in enumerate(pairs):
+            rows[i] = (pr[0], pr[1], pr[2], pr[3] if len(pr) > 3 else 0)
+        if col_offset is None:
+            off = np.zeros(B.n + 1, np.uint64)
+            off[1:] = np.cumsum([int(x) for x in B.lengths])
+        else:
+            off = np.ascontiguousarray(col_offset, np.uint64)
+        out = np.zeros(len(pairs), AFFINE_DTYPE) if aln else None
+        table = np.zeros(max(1, int(off[-1])), PILEUP_DTYPE) if cols else None
+        sm = np.zeros(max(1, B.n), SUPPORT_DTYPE) if summaries else None
+        mem = np.ascontiguousarray(n_members, np.uint32) if n_members is not None else None
+        op = sp_affine_opts(a, 4, 6, 2, 26, 1, 1)
+        self.check(lib().sp_align_pileup_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), _ptr(off), _ptr(out), _ptr(table), _ptr(sm), _ptr(mem)))
+        return (out, [table[int(off[t]):int(off[t + 1])] for t in range(B.n)] if cols else None,
+                [{n: int(sm[t][n]) for n in SUPPORT_FIELDS[:-1]} for t in range(B.n)] if summaries else None)
 
     def hla_config_extend(self, reference, alleles, db=None, batch_alleles=0):
         """sp_hla_config_extend: HlaConfig::new on the device -- reference = database.Fasta, alleles = database.HlaAlleles, db = database.Database whose hla_config
@@ -767,10 +790,9 @@ class Context:
         self.check(lib().sp_cyp_variant_states(self._h, seqs._h, backbone.encode(), len(backbone), nv, _ptr(pos), refs, alts, _ptr(states), _ptr(alns)))
         return states, alns[:seqs.n]
 
-    def cyp_diplotype(self, templates, template_type, template_subtype, template_deep, backbone, variants, is_vi, allele_subtype, hap_matrix,
-                      cfg, reads, min_count=3, min_af=0.10, delta=100, infer=False, normalize_d6_only=False, cons_cap=16384, var_labels=None):
-        """sp_cyp_diplotype.  templates: SeqSet; variants: [(pos, ref, alt)]; cfg: dict(translate, connections, singletons).
-        Returns (sp_cyp_call, [consensus strings], [(type, subtype|None)])"""
+    def cyp_problem(self, templates, template_type, template_subtype, template_deep, backbone, variants, is_vi, allele_subtype, hap_matrix,
+                    cfg, min_count=3, min_af=0.10, delta=100, infer=False, normalize_d6_only=False, var_labels=None):
+        """the sp_cyp_problem of cyp_diplotype's arguments (the arrays it points to live as long as the record)"""
         def strs(items):
             arr = (C.c_char_p * max(1, len(items)))()
             for i, x in enumerate(items):
@@ -788,6 +810,15 @@ class Context:
                             len(variants), pos.ctypes.data, keep[1], keep[2], vi.ctypes.data, len(allele_subtype), keep[3], hm.ctypes.data,
                             len(cfg["translate"]), keep[4], keep[5], len(cfg["connections"]), keep[6], keep[7], len(cfg["singletons"]), keep[8],
                             min_count, delta, min_af, int(infer), int(normalize_d6_only), strs(list(var_labels)) if var_labels is not None else None)
+        pr._keep = (templates, tt, deep, pos, vi, hm, keep, backbone.encode())
+        return pr
+
+    def cyp_diplotype(self, templates, template_type, template_subtype, template_deep, backbone, variants, is_vi, allele_subtype, hap_matrix,
+                      cfg, reads, min_count=3, min_af=0.10, delta=100, infer=False, normalize_d6_only=False, cons_cap=16384, var_labels=None):
+        """sp_cyp_diplotype.  templates: SeqSet; variants: [(pos, ref, alt)]; cfg: dict(translate, connections, singletons).
+        Returns (sp_cyp_call, [consensus strings], [(type, subtype|None)])"""
+        pr = self.cyp_problem(templates, template_type, template_subtype, template_deep, backbone, variants, is_vi, allele_subtype, hap_matrix, cfg,
+                              min_count, min_af, delta, infer, normalize_d6_only, var_labels)
         call = sp_cyp_call()
         buf = C.create_string_buffer(SP_CYP_MAXCONS * cons_cap)
         self.check(lib().sp_cyp_diplotype(self._h, C.byref(pr), reads._h, C.byref(call), buf, cons_cap))
