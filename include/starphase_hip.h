@@ -90,6 +90,8 @@ int32_t sp_ctx_synchronize(sp_ctx* ctx);
  * the reference's way (fields mm2_*; sp_affine_rescore_batch), and the weights of sp_cyp_weight_segments / sp_cyp_diplotype* are taken from the re-scored placement wherever it is
  * within 16 (edits + unmapped bases) of its segment's smallest; 0 leaves the fields zero, the weights on unit-cost counts, and saves the extra launches; 2 = as 1, but every mapping with edits that do not stand alone
  * takes the DP over all of its rows instead of over the rows around those edits (a check of the shortcut, an order of magnitude slower).
+ * "profile_rescore_counts" (default 0): 1 makes every such re-score fetch how many of its mappings it left to the DP (sp_profile_get "<stage>_dp_pairs", e.g. k1_segrs_dp_pairs:
+ * launches = re-scores, cells = mappings); the host waits for the device at each one -- for measuring runs.
  * "k8_persistent" (0 | 1 | 2, default 2; also the environment variable SP_K8_PERSISTENT): consensus batches whose problems have at most 1,024 reads each can run as two
  * persistent kernels (step workgroups and one control workgroup per problem on a second stream, resident for the length of the batch; the two sides hand over through one word
  * each in memory: write-through stores, `sc1` loads and memory-side atomics, no L2 fences -- gfx950 behaviour) instead of a launch pair per step -- the
@@ -356,6 +358,19 @@ int32_t sp_hla_seed_index_info(sp_ctx* ctx, const sp_hla_db* db, int64_t* out /*
 int32_t sp_seqset_sketch(sp_ctx* ctx, const sp_seqset* set, uint32_t idx, uint64_t* hash, int32_t* end_pos, uint8_t* strand, uint32_t cap, uint32_t* n_out);
 int32_t sp_hla_realign_seeded_audit(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, uint32_t read, int32_t* chains, uint32_t chain_cap, uint32_t* n_chains,
                                     sp_k1_seed_hit* hits /* SP_K1_SEL */, uint32_t* n_hits, int32_t* pick, uint64_t* counters /* 4 */);
+/* Audit of the re-score of mappings the library holds (the mm2_* numbers and K1's second-stage extents; tests hold every route of it to oracle/affine.c):
+ *   sp_affine_rescore_mappings_audit  for each pair (a in set A = the streamed side, b in set B = the window side, diag and max_ed as sp_align_batch takes them;
+ *                            max_ed < 0 = no mapping) the pair's cell is run as sp_align_batch runs it -- the alignment "the caller holds" -- and re-scored the way
+ *                            the library's own callers have it re-scored, with exactly these knobs: band (64 | 256 diagonals of the DP), target_is_a (which set is
+ *                            minimap2's target), events_stride (edit events kept per pair, 1 .. SP_MAX_ED + 1: a mapping with more takes the DP over all rows),
+ *                            windows (1: the DP runs over the rows around the clustered edits, context option "mm2_rescore" 1; 0: over all rows, option 2),
+ *                            ends_only (0: all six numbers; > 0: the caller takes the extent only, K1's second stage passes 64).  out[p] as
+ *                            sp_affine_rescore_batch reports (a_* on the query, b_* on the target); route[p] = 0 closed form (no DP), 1 DP over the rows around
+ *                            the clusters, 2 DP over all rows, 3 no mapping; diag[p] = the diagonal, target position - query position, the DP is (or would be)
+ *                            centred on: the middle diagonal of the cell's alignment, the cell's own when the cell found none */
+int32_t sp_affine_rescore_mappings_audit(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts,
+                                         int32_t band, int32_t target_is_a, uint32_t events_stride, int32_t windows, int32_t ends_only, sp_affine_aln* out,
+                                         int32_t* route, int32_t* diag);
 
 int32_t sp_hla_realign_reads(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads,
                              sp_hla_realign* out /* n_reads */,

@@ -772,6 +772,7 @@ extern "C" {
     pub fn sp_hla_seed_index_info(ctx: *mut sp_ctx, db: *const sp_hla_db, out: *mut i64) -> i32;
     pub fn sp_seqset_sketch(ctx: *mut sp_ctx, set: *const sp_seqset, idx: u32, hash: *mut u64, end_pos: *mut i32, strand: *mut u8, cap: u32, n_out: *mut u32) -> i32;
     pub fn sp_hla_realign_seeded_audit(ctx: *mut sp_ctx, db: *const sp_hla_db, reads: *const sp_seqset, read: u32, chains: *mut i32, chain_cap: u32, n_chains: *mut u32, hits: *mut sp_k1_seed_hit, n_hits: *mut u32, pick: *mut i32, counters: *mut u64) -> i32;
+    pub fn sp_affine_rescore_mappings_audit(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, band: i32, target_is_a: i32, events_stride: u32, windows: i32, ends_only: i32, out: *mut sp_affine_aln, route: *mut i32, diag: *mut i32) -> i32;
     pub fn sp_hla_realign_reads(ctx: *mut sp_ctx, db: *const sp_hla_db, reads: *const sp_seqset, out: *mut sp_hla_realign, cell_out: *mut u32) -> i32;
     pub fn sp_hla_realign_reads_rev(ctx: *mut sp_ctx, db: *const sp_hla_db, reads: *const sp_seqset, out: *mut sp_hla_realign, rev: *mut sp_hla_rev_hit) -> i32;
     pub fn sp_hla_realign_cigars(ctx: *mut sp_ctx, db: *const sp_hla_db, reads: *const sp_seqset, records: *const sp_hla_realign, n_reads: u32, cigar: *mut u32, cigar_stride: u32, n_cigar: *mut u32) -> i32;

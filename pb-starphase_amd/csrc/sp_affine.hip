@@ -451,20 +451,42 @@ int sp_launch_affine(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const 
 // ------------------------------------------------------------------------------------------------------------------------------
 constexpr int AF_ISOLATED = 16;
 constexpr int AF_MARGIN = 24;
+// what the classification decided for a pair (sp_affine_rescore_mappings_audit): route 0 closed form, 1 the DP over the rows around the clusters, 2 the DP over all rows,
+// 3 no mapping; diag = the diagonal (target position - query position) the DP is, or would be, centred on
+struct AfAudit { int32_t route, diag; };
+// what a stretch of the cell's path costs under the reference's scores: mismatches b each, every RUN of l gap bases min(q + l e, q2 + l e2) (events in path order:
+// a run of B-only bases has consecutive positions, a run of A-only bases one position)
+__device__ __forceinline__ int af_gap_cost(const sp_affine_opts& o, int l) { const int c1 = o.q + l * o.e, c2 = o.q2 + l * o.e2; return c1 < c2 ? c1 : c2; }
+struct AfPathCost {
+    int pen = 0, type = -1, pos = 0, run = 0;
+    __device__ __forceinline__ void step(const sp_affine_opts& o, int t, int p) {
+        if (t == (int)SP_EV_X) { pen += o.b; run = 0; }
+        else {
+            const bool more = run > 0 && t == type && p == (t == (int)SP_EV_D ? pos + 1 : pos);
+            run = more ? run + 1 : 1;
+            pen += af_gap_cost(o, run) - (run > 1 ? af_gap_cost(o, run - 1) : 0);
+        }
+        type = t; pos = p;
+    }
+};
 
-// d_ref: the alignment the caller holds for each pair (WFA orientation: a_* on Aw, b_* on Bw); cells[x].max_ed < 0: no mapping (score 0)
+// d_ref: the alignment the caller holds for each pair (WFA orientation: a_* on Aw, b_* on Bw); cells[x].max_ed < 0: no mapping (score 0).  ENDS: the ends_only rule is compiled in
+// (callers that take all six numbers run the kernel without it)
+template <bool ENDS>
 __global__ void af_classify_kernel(const CellDesc* __restrict__ cells, const sp_aln* __restrict__ ref, const sp_aln* __restrict__ tr, const uint32_t* __restrict__ ev,
                                    uint32_t stride, uint32_t n, int target_is_a, int has_n, sp_affine_opts o, sp_affine_aln* __restrict__ out,
-                                   AfPair* __restrict__ todo, uint32_t* __restrict__ todo_at, uint32_t* __restrict__ n_todo, AfWin* __restrict__ wins, AfMid* __restrict__ mids, int band, int windows, int ends_only) {
+                                   AfPair* __restrict__ todo, uint32_t* __restrict__ todo_at, uint32_t* __restrict__ n_todo, AfWin* __restrict__ wins, AfMid* __restrict__ mids, int band, int windows, int ends_only, AfAudit* __restrict__ audit) {
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= n) return;
     sp_affine_aln res; res.score = 0; res.nm = 0; res.a_start = res.a_end = res.b_start = res.b_end = 0;
     const CellDesc c = cells[x];
-    if (c.max_ed < 0) { out[x] = res; return; }
+    if (c.max_ed < 0) { out[x] = res; if (audit) { audit[x].route = 3; audit[x].diag = target_is_a ? -c.diag : c.diag; } return; }
     const sp_aln r = ref[x], t = tr[x];
+    const int d_mid = ((r.b_start - r.a_start) + (r.b_end - r.a_end)) / 2;         // b_pos - a_pos (WFA orientation)
+    const int d_dp = r.ok ? (target_is_a ? -d_mid : d_mid) : (target_is_a ? -c.diag : c.diag);      // in the affine kernel's order; a lost cell: the cell's own diagonal
     bool simple = !has_n && r.ok && t.ok && t.nm == r.nm && t.a_start == r.a_start && t.a_end == r.a_end && t.b_start == r.b_start && t.b_end == r.b_end && (uint32_t)r.nm <= stride;
     const bool traced = simple;
-    int nx = 0, ngap = 0;
+    int nx = 0, ngap = 0, gap_cost = -1;                                     // (gap_cost >= 0: the gap bases' cost in true runs, ends_only)
     if (simple) {
         const uint32_t* e = ev + (size_t)x * stride;
         int prev = -(1 << 29);
@@ -477,35 +499,65 @@ __global__ void af_classify_kernel(const CellDesc* __restrict__ cells, const sp_
             prev = pos;
         }
     }
-    // ends_only: the caller takes the mapping's EXTENT (where minimap2's end clipping leaves its two ends) and nothing else.  Where an alignment ends is decided by its last
-    // bases alone -- every candidate end carries the same score of what lies in front of it, and that score is far from the restart at zero --: an end without an edit
-    // within AF_ISOLATED bases is not clipped (the rule above), and an end with one takes the DP over the rows from that end to the first stretch of AF_MARGIN + AF_ISOLATED
-    // bases without an edit; what lies in between enters in the closed form of lone edits, clustered or not (its count and the score's magnitude are then the unit-cost
-    // spelling's: such a caller uses neither).  An HLA read is 40 - 100 clustered edits from the reference: the DP over all of its rows was 17.5 ms per 10,000 reads.
-    bool ends_head = false, ends_tail = false;
-    if (ends_only > 0 && traced && !simple && r.nm > 0) {
+    // ends_only: the caller takes the mapping's EXTENT (where minimap2's end clipping leaves its two ends) and nothing else.  An end is clipped where the alignment from it
+    // inwards does not pay, so that is what is tested: the cell's path is scored the reference's way (mismatches, gap RUNS at min(q + l e, q2 + l e2)) from the head to
+    // behind every edit and from the tail to in front of every edit.  That is a lower bound of what the DP finds between the same two points ON THAT PATH; where it stays at or above
+    // `clear` -- the least the lone-edit rule above lets stand, AF_ISOLATED matches less a one-base gap -- the end is taken not to be clipped.  This is a criterion held by
+    // tests (tests/test_gpu_rescore_shortcuts.py against oracle/affine.c), not a proof: it does not exclude an optimum on another path with another extent, as repeats could
+    // offer one.  A mapping with both ends so cleared keeps the cell's extent without a DP, whatever its edits in between (count and score are then the unit-cost spelling's under true gap-run costs: positive, and
+    // such a caller uses neither).  An end that is not cleared takes the DP from that end to behind the last edit that is in doubt (kh: the last one whose score from the head
+    // falls below it, kt: the first one whose score to the tail does), and so does an end with an edit that does not stand alone within ends_only bases of it; both
+    // stretches run on to the first AF_MARGIN + AF_ISOLATED bases without an edit, what lies between them enters in closed form, and two that meet are the DP over all rows --
+    // as is a path that leaves the diagonals of the DP's band, whose optimum is then another alignment.
+    // An HLA read is 40 - 100 clustered edits from the reference: the DP over all of its rows was 17.5 ms per 10,000 reads.
+    int kh = -1, kt = r.nm;
+    if (ENDS && ends_only > 0 && traced && !simple && r.nm > 0) {
         const uint32_t* e = ev + (size_t)x * stride;
-        ends_head = (int)(e[0] & 0x3FFFFFFFu) - r.b_start < AF_ISOLATED; ends_tail = r.b_end - (int)(e[r.nm - 1] & 0x3FFFFFFFu) < AF_ISOLATED;
-        if (!ends_head && !ends_tail) { simple = true; nx = 0; ngap = 0; for (int k = 0; k < r.nm; ++k) { if ((int)(e[k] >> 30) == (int)SP_EV_X) ++nx; else ++ngap; } }
+        const int clear = o.a * AF_ISOLATED - af_gap_cost(o, 1);
+        AfPathCost pc; int nxd = 0, total = 0, drift = 0;
+        bool in_band = true;                                                   // the path stays on the diagonals the DP would run: otherwise the DP's optimum is not this path's
+        nx = 0; ngap = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            // pass 0: the path's score from the head to behind edit k, and the whole path's (total); pass 1: from in front of edit k to the tail = total - (the score up to there)
+            pc = AfPathCost(); nxd = 0;
+            for (int k = 0; k < r.nm; ++k) {
+                const uint32_t w = e[k]; const int pos = (int)(w & 0x3FFFFFFFu), type = (int)(w >> 30);
+                const int before = o.a * (pos - r.b_start - nxd) - pc.pen;
+                pc.step(o, type, pos);
+                if (type != (int)SP_EV_I) ++nxd;
+                if (pass == 0) {
+                    if (type == (int)SP_EV_X) ++nx; else ++ngap;
+                    drift += type == (int)SP_EV_D ? 1 : type == (int)SP_EV_I ? -1 : 0;
+                    const int off = (r.b_start - r.a_start) + drift - d_mid;
+                    if (off <= -(band / 2 - 2) || off >= band / 2 - 2) in_band = false;
+                    const int prev = k > 0 ? (int)(e[k - 1] & 0x3FFFFFFFu) : -(1 << 29), next = k + 1 < r.nm ? (int)(e[k + 1] & 0x3FFFFFFFu) : (1 << 29);
+                    const bool lone = pos - prev >= AF_ISOLATED && next - pos >= AF_ISOLATED && pos - r.b_start >= AF_ISOLATED && r.b_end - pos >= AF_ISOLATED;
+                    if (o.a * (pos - r.b_start - (nxd - (type != (int)SP_EV_I ? 1 : 0))) - pc.pen < clear || (!lone && pos - r.b_start < ends_only)) kh = k;
+                    if (!lone && r.b_end - pos < ends_only && k < kt) kt = k;
+                } else if (total - before < clear && k < kt) kt = k;
+            }
+            if (pass == 0) total = o.a * (r.b_end - r.b_start - nxd) - pc.pen;
+        }
+        if (!in_band) { kh = r.nm - 1; kt = 0; }                              // (the two stretches meet: the DP over all rows)
+        if (kh < 0 && kt == r.nm) { simple = true; gap_cost = pc.pen - o.b * nx; }
     }
     if (simple) {
         // columns: M matches, X mismatches, gap bases on either side; a_span = M + X + (A-only bases), b_span = M + X + (B-only bases), gap bases = ngap
         const int a_span = r.a_end - r.a_start, b_span = r.b_end - r.b_start;
         const int m2 = a_span + b_span - 2 * nx - ngap;                          // = 2 M
         const int M = m2 / 2;
-        res.score = o.a * M - o.b * nx - (o.q + o.e) * ngap; res.nm = r.nm;
+        res.score = o.a * M - o.b * nx - (gap_cost >= 0 ? gap_cost : (o.q + o.e) * ngap); res.nm = r.nm;
         if (target_is_a) { res.b_start = r.a_start; res.b_end = r.a_end; res.a_start = r.b_start; res.a_end = r.b_end; }
         else { res.a_start = r.a_start; res.a_end = r.a_end; res.b_start = r.b_start; res.b_end = r.b_end; }
         out[x] = res;
+        if (audit) { audit[x].route = 0; audit[x].diag = d_dp; }
         return;
     }
     // the DP: query / target in the affine kernel's order, on the diagonal the alignment lies on
     const uint32_t at = atomicAdd(n_todo, 1u);
-    const int d_mid = ((r.b_start - r.a_start) + (r.b_end - r.a_end)) / 2;         // b_pos - a_pos (WFA orientation)
     AfPair p;
-    if (target_is_a) { p.a = c.b; p.b = c.a; p.diag = -d_mid; } else { p.a = c.a; p.b = c.b; p.diag = d_mid; }
-    p.pad = 0;
-    if (!r.ok) p.diag = target_is_a ? -c.diag : c.diag;
+    if (target_is_a) { p.a = c.b; p.b = c.a; } else { p.a = c.a; p.b = c.b; }
+    p.diag = d_dp; p.pad = 0;
     todo[at] = p; todo_at[at] = x;
     // the rows the DP has to run: for every run of edits that do not stand alone, from AF_MARGIN bases before its first edit to AF_MARGIN behind its last one, both ends
     // moved outwards until no other edit lies within AF_ISOLATED bases of them; what lies before, between and behind these stretches is spelled by both scoring schemes
@@ -516,11 +568,11 @@ __global__ void af_classify_kernel(const CellDesc* __restrict__ cells, const sp_
         const uint32_t* e = ev + (size_t)x * stride;
         auto pos_of = [&](int k) { return (int)(e[k] & 0x3FFFFFFFu); };
         int wF[AF_MAXMID + 1], wL[AF_MAXMID + 1], wIn[AF_MAXMID + 1], wOut[AF_MAXMID + 1], nw = 0;
+        const bool ends_head = ENDS && kh >= 0, ends_tail = ENDS && kt < r.nm;
         if (ends_head || ends_tail) {
-            // (ends_only: at most two stretches, one per end that has an edit close to it)
-            int kh = -1, kt = r.nm;
-            if (ends_head) { kh = 0; while (kh + 1 < r.nm && pos_of(kh + 1) - pos_of(kh) < AF_MARGIN + AF_ISOLATED) ++kh; }
-            if (ends_tail) { kt = r.nm - 1; while (kt > 0 && pos_of(kt) - pos_of(kt - 1) < AF_MARGIN + AF_ISOLATED) --kt; }
+            // (ends_only: at most two stretches, one per end that was not shown to stand)
+            if (ends_head) { while (kh + 1 < r.nm && pos_of(kh + 1) - pos_of(kh) < AF_MARGIN + AF_ISOLATED) ++kh; }
+            if (ends_tail) { while (kt > 0 && pos_of(kt) - pos_of(kt - 1) < AF_MARGIN + AF_ISOLATED) --kt; }
             if (kh < kt) {
                 if (ends_head) { wF[nw] = 0; wL[nw] = kh; wIn[nw] = pos_of(0) - AF_MARGIN; wOut[nw] = pos_of(kh) + AF_MARGIN; ++nw; }
                 if (ends_tail) { wF[nw] = kt; wL[nw] = r.nm - 1; wIn[nw] = pos_of(kt) - AF_MARGIN; wOut[nw] = pos_of(r.nm - 1) + AF_MARGIN; ++nw; }
@@ -543,8 +595,10 @@ __global__ void af_classify_kernel(const CellDesc* __restrict__ cells, const sp_
         if (nw > 0) {
             const int klo = -p.diag - band / 2;
             // the walk along the alignment: (i, j) = the next bases of the streamed and the window sequence; cx / cd / ci = the lone edits since the last stretch
-            int i = r.a_start, j = r.b_start, cx = 0, cd = 0, ci = 0, k = 0;
-            auto step_to = [&](int k2) { const int pos = pos_of(k2), type = (int)(e[k2] >> 30); i += pos - j; j = pos; if (type == (int)SP_EV_X) { ++i; ++j; ++cx; } else if (type == (int)SP_EV_D) { ++j; ++cd; } else { ++i; ++ci; } };
+            // (pc.pen: what they cost the reference's way, gap runs as runs -- between the two stretches of an ends_only pair the edits need not stand alone)
+            int i = r.a_start, j = r.b_start, cx = 0, cd = 0, ci = 0, k = 0; AfPathCost pc;
+            auto piece_cost = [&]() { return ENDS ? pc.pen : o.b * cx + (o.q + o.e) * (cd + ci); };
+            auto step_to = [&](int k2) { const int pos = pos_of(k2), type = (int)(e[k2] >> 30); if (ENDS) pc.step(o, type, pos); i += pos - j; j = pos; if (type == (int)SP_EV_X) { ++i; ++j; ++cx; } else if (type == (int)SP_EV_D) { ++j; ++cd; } else { ++i; ++ci; } };
             AfMid* mid = mids + (size_t)at * AF_MAXMID;
             int out_t = 0, out_idx = 0, out_b = 0; bool have_out = false;
             for (int v = 0; v < nw; ++v) {
@@ -557,18 +611,18 @@ __global__ void af_classify_kernel(const CellDesc* __restrict__ cells, const sp_
                     if (v == 0) {
                         if (wIn[0] - r.b_start >= AF_ISOLATED && fits) {
                             w.r0 = t_in; w.idx_in = idx;
-                            w.s_in = o.a * ((wIn[0] - r.b_start) - cx - cd) - o.b * cx - (o.q + o.e) * (cd + ci); w.nm_in = cx + cd + ci;
+                            w.s_in = o.a * ((wIn[0] - r.b_start) - cx - cd) - piece_cost(); w.nm_in = cx + cd + ci;
                             const int ts = target_is_a ? r.a_start : r.b_start, qs = target_is_a ? r.b_start : r.a_start;
                             w.start_cell = ((uint32_t)ts << 16) | (uint32_t)(qs & 0xFFFF);
                         }
                     } else if (have_out && fits && t_in > out_t + 1) {
                         AfMid m; m.r_exit = out_t; m.idx_out = out_idx; m.r_entry = t_in; m.idx_in = idx;
-                        m.d_score = o.a * ((wIn[v] - out_b - 1) - cx - cd) - o.b * cx - (o.q + o.e) * (cd + ci); m.d_nm = cx + cd + ci;
+                        m.d_score = o.a * ((wIn[v] - out_b - 1) - cx - cd) - piece_cost(); m.d_nm = cx + cd + ci;
                         mid[w.n_mid++] = m;
                     }
                 }
                 for (; k <= wL[v]; ++k) step_to(k);
-                cx = cd = ci = 0;
+                cx = cd = ci = 0; pc.pen = 0;
                 {
                     const int ia = i + (wOut[v] - j), jb = wOut[v];                                 // a matching cell AF_MARGIN behind the last edit of the stretch
                     const int t_out = target_is_a ? ia : jb, q_out = target_is_a ? jb : ia;
@@ -580,12 +634,13 @@ __global__ void af_classify_kernel(const CellDesc* __restrict__ cells, const sp_
             if (have_out && r.b_end - out_b >= AF_ISOLATED) {
                 for (; k < r.nm; ++k) step_to(k);
                 w.r1 = out_t; w.idx_out = out_idx;
-                w.d_score = o.a * ((r.b_end - out_b - 1) - cx - cd) - o.b * cx - (o.q + o.e) * (cd + ci); w.d_nm = cx + cd + ci;
+                w.d_score = o.a * ((r.b_end - out_b - 1) - cx - cd) - piece_cost(); w.d_nm = cx + cd + ci;
                 w.end_t = target_is_a ? r.a_end : r.b_end; w.end_q = target_is_a ? r.b_end : r.a_end;
             }
         }
     }
     wins[at] = w;
+    if (audit) { audit[x].route = (w.r0 >= 0 || w.r1 >= 0 || w.n_mid > 0) ? 1 : 2; audit[x].diag = d_dp; }
 }
 __global__ void af_scatter_kernel(const sp_affine_aln* __restrict__ part, const uint32_t* __restrict__ todo_at, const uint32_t* __restrict__ n_todo, sp_affine_aln* __restrict__ out) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -595,7 +650,7 @@ __global__ void af_scatter_kernel(const sp_affine_aln* __restrict__ part, const 
 // the mappings of cells (WFA orientation: Aw streamed, Bw window; d_ref = the alignments the caller holds) re-scored into d_out (a_* on minimap2's query, b_* on its target:
 // target_is_a tells which of the two sets is the target); everything stays on the device
 int sp_rescore_mappings(sp_ctx* ctx, const sp_seqset* Aw, const sp_seqset* Bw, const CellDesc* d_cells, const sp_aln* d_ref, uint64_t n, bool target_is_a,
-                        const sp_affine_opts& o, int band, sp_affine_aln* d_out, const char* prefix, uint32_t stride, int trace_retry_wide, const sp_aln* d_tr_in, const uint32_t* d_ev_in, int ends_only) {
+                        const sp_affine_opts& o, int band, sp_affine_aln* d_out, const char* prefix, uint32_t stride, int trace_retry_wide, const sp_aln* d_tr_in, const uint32_t* d_ev_in, int ends_only, int windows, void* d_audit) {
     if (n == 0) return SP_OK;
     const std::string pre(prefix);
     static std::mutex names_lock; static std::set<std::string> names;                 // (the profiler keeps the pointers it is given)
@@ -614,12 +669,20 @@ int sp_rescore_mappings(sp_ctx* ctx, const sp_seqset* Aw, const sp_seqset* Bw, c
     int rc = SP_OK;
     if (!d_tr_in) rc = sp_launch_cells(ctx, Aw, Bw, d_cells, n, const_cast<sp_aln*>(d_tr), const_cast<uint32_t*>(d_ev), stride, stable(pre + "_trace"), trace_retry_wide);
     if (rc != SP_OK) return rc;
-    hipLaunchKernelGGL(af_classify_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_cells, d_ref, d_tr, d_ev, stride, (uint32_t)n, target_is_a ? 1 : 0,
-                       (Aw->has_n || Bw->has_n) ? 1 : 0, o, d_out, d_todo, d_at, d_n, d_win, d_mid, band, ctx->mm2_rescore == 2 ? 0 : 1, ends_only);
+    auto* classify = ends_only > 0 ? af_classify_kernel<true> : af_classify_kernel<false>;
+    hipLaunchKernelGGL(classify, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_cells, d_ref, d_tr, d_ev, stride, (uint32_t)n, target_is_a ? 1 : 0,
+                       (Aw->has_n || Bw->has_n) ? 1 : 0, o, d_out, d_todo, d_at, d_n, d_win, d_mid, band, windows < 0 ? (ctx->mm2_rescore == 2 ? 0 : 1) : windows, ends_only, (AfAudit*)d_audit);
     // the DP over the list the classification left: launched for every pair, the workgroups behind the list's end return at once (no host round trip for the count)
     rc = sp_launch_affine(ctx, target_is_a ? Bw : Aw, target_is_a ? Aw : Bw, d_todo, n, o, band, d_part, stable(pre + "_dp"), d_n, d_win, d_mid);
     if (rc != SP_OK) return rc;
     hipLaunchKernelGGL(af_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_part, d_at, d_n, d_out);
+    if (ctx->profile_rescore_counts && ctx->profiling) {
+        // (a measuring run: how many pairs the classification left to the DP -- one word fetched, the host waits for the stream)
+        uint32_t n_dp = 0;
+        SP_HIP_CHECK(ctx, hipMemcpyAsync(&n_dp, d_n, 4, hipMemcpyDeviceToHost, ctx->stream));
+        SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        auto& e = ctx->prof[pre + "_dp_pairs"]; e.cells += n_dp; e.launches += 1;
+    }
     return SP_OK;
 }
 
@@ -639,6 +702,42 @@ extern "C" int32_t sp_affine_rescore_batch(sp_ctx* ctx, const sp_seqset* A, cons
     if (rc != SP_OK) return rc;
     SP_HIP_CHECK(ctx, hipMemcpyAsync(out, d_out, n_pairs * sizeof(sp_affine_aln), hipMemcpyDeviceToHost, ctx->stream));
     SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return SP_OK;
+}
+
+// sp_rescore_mappings as the library's own callers run it, for pairs a test hands in: each pair's cell (what sp_align_batch runs for it) is the alignment "the caller
+// holds", the re-score takes exactly the knobs given, and what the classification decided comes back beside the numbers
+extern "C" int32_t sp_affine_rescore_mappings_audit(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts,
+                                                    int32_t band, int32_t target_is_a, uint32_t events_stride, int32_t windows, int32_t ends_only, sp_affine_aln* out,
+                                                    int32_t* route, int32_t* diag) {
+    if (!ctx || !A || !B || !opts || (n_pairs && (!pairs || !out || !route || !diag))) return SP_ERR_INVALID_ARG;
+    if (n_pairs == 0) return SP_OK;
+    if (n_pairs > 0xFFFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "rescore audit: too many pairs");
+    if (events_stride == 0 || events_stride > SP_MAX_ED + 1) return sp_fail(ctx, SP_ERR_INVALID_ARG, "rescore audit: events_stride must be 1..SP_MAX_ED + 1");
+    if (ends_only < 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "rescore audit: ends_only must be >= 0");
+    (void)hipSetDevice(ctx->device);
+    std::vector<CellDesc> cells(n_pairs);
+    for (uint64_t i = 0; i < n_pairs; ++i) {
+        if (pairs[i].a >= A->n || pairs[i].b >= B->n) return sp_fail(ctx, SP_ERR_INVALID_ARG, "rescore audit: index out of range");
+        if (pairs[i].max_ed > SP_MAX_ED) return sp_fail(ctx, SP_ERR_INVALID_ARG, "rescore audit: max_ed must be <= SP_MAX_ED (< 0: no mapping)");
+        cells[i] = CellDesc{pairs[i].a, pairs[i].b, pairs[i].diag, pairs[i].max_ed, 0, -1};
+    }
+    CellDesc* d_cells = (CellDesc*)sp_pool(ctx, "af_audit_cells", n_pairs * sizeof(CellDesc));
+    sp_aln* d_ref = (sp_aln*)sp_pool(ctx, "af_audit_ref", n_pairs * sizeof(sp_aln));
+    sp_affine_aln* d_out = (sp_affine_aln*)sp_pool(ctx, "af_audit_out", n_pairs * sizeof(sp_affine_aln));
+    AfAudit* d_audit = (AfAudit*)sp_pool(ctx, "af_audit_route", n_pairs * sizeof(AfAudit));
+    if (!d_cells || !d_ref || !d_out || !d_audit) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "rescore audit buffers");
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(d_cells, cells.data(), n_pairs * sizeof(CellDesc), hipMemcpyHostToDevice, ctx->stream));
+    SP_HIP_CHECK(ctx, hipMemsetAsync(d_ref, 0, n_pairs * sizeof(sp_aln), ctx->stream));       // (a cell with max_ed < 0 is not run: ok = 0)
+    int rc = sp_launch_cells(ctx, A, B, d_cells, n_pairs, d_ref, nullptr, 0, "af_audit_cells", 2);
+    if (rc != SP_OK) return rc;
+    rc = sp_rescore_mappings(ctx, A, B, d_cells, d_ref, n_pairs, target_is_a != 0, *opts, band, d_out, "af_audit", events_stride, 2, nullptr, nullptr, ends_only, windows ? 1 : 0, d_audit);
+    if (rc != SP_OK) return rc;
+    std::vector<AfAudit> au(n_pairs);
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(out, d_out, n_pairs * sizeof(sp_affine_aln), hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(au.data(), d_audit, n_pairs * sizeof(AfAudit), hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint64_t i = 0; i < n_pairs; ++i) { route[i] = au[i].route; diag[i] = au[i].diag; }
     return SP_OK;
 }
 

@@ -95,6 +95,7 @@ struct sp_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int k1_best_n = 5;                   // sp_ctx_set_option "k1_best_n": K1 base-aligns the chains minimap2's seeding and chaining select (best_n secondaries per read, the reference's 5);
                                          // 0 = every allele of every anchored gene (the exhaustive argmin of rounds 1-4)
+    int profile_rescore_counts = 0;      // sp_ctx_set_option "profile_rescore_counts": sp_rescore_mappings fetches the number of pairs it left to the DP (profile entry <prefix>_dp_pairs); the host waits for it
     int mm2_rescore = 1;                 // sp_ctx_set_option "mm2_rescore": the entry points that return mappings also report them re-scored with the reference's affine scores (mm2_* fields)
     int k8_persistent = 2;               // sp_ctx_set_option "k8_persistent" (or SP_K8_PERSISTENT): small consensus batches as two persistent kernels instead of a launch pair per step.
                                          // 0 never, 1 whenever a batch fits, 2 (default) the library decides: a single sample's batches (<= 8 problems) when the process's streams
@@ -167,7 +168,11 @@ int sp_launch_cells(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B,
 int sp_launch_affine(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const void* d_pairs /* sp_pair rows */, uint64_t n_pairs, const sp_affine_opts& o, int band,
                      sp_affine_aln* d_out, const char* prof_name, const uint32_t* d_n_live = nullptr, const void* d_wins = nullptr, const void* d_mids = nullptr);   // sp_affine.hip: two-piece affine re-score, pairs and results in device memory
 int sp_rescore_mappings(sp_ctx* ctx, const sp_seqset* Aw, const sp_seqset* Bw, const CellDesc* d_cells, const sp_aln* d_ref, uint64_t n, bool target_is_a,
-                        const sp_affine_opts& o, int band, sp_affine_aln* d_out, const char* prefix, uint32_t stride, int trace_retry_wide = 0, const sp_aln* d_tr_in = nullptr, const uint32_t* d_ev_in = nullptr, int ends_only = 0);   // sp_affine.hip: mappings the caller holds, re-scored (no DP for isolated edits); trace_retry_wide: the trace of a mapping the 64-diagonal cell loses runs on the wide band; ends_only > 0: the caller takes the EXTENT of the mapping only -- edits that far from both ends of the alignment never take the DP (af_classify_kernel)
+                        const sp_affine_opts& o, int band, sp_affine_aln* d_out, const char* prefix, uint32_t stride, int trace_retry_wide = 0, const sp_aln* d_tr_in = nullptr, const uint32_t* d_ev_in = nullptr, int ends_only = 0, int windows = -1, void* d_audit = nullptr);   // sp_affine.hip: mappings the caller holds, re-scored (no DP for isolated edits)
+    // trace_retry_wide: the trace of a mapping the 64-diagonal cell loses runs on the wide band
+    // ends_only > 0: the caller takes the EXTENT of the mapping only -- an end takes the DP unless the cell's path, scored with true gap runs from that end inwards, clears it and no clustered edit lies within ends_only bases of it
+    // windows 0 | 1: the DP over all rows | the rows around the clusters (-1: as context option mm2_rescore says)
+    // d_audit: AfAudit rows (route, diagonal) per pair for sp_affine_rescore_mappings_audit (af_classify_kernel)
 int sp_launch_affine_map(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const void* d_pairs /* sp_pair rows, max_ed < 0: skip */, uint64_t n_pairs, const sp_affine_opts& o, sp_affine_aln* d_out,
                          uint32_t* d_n_cigar, uint64_t* d_op_off, uint32_t* d_ops, uint64_t ops_cap, unsigned long long* d_cursor, const char* prof_name);   // sp_affine.hip: the K2 map -- sp_affine_align_batch's alignment on 64 diagonals from checkpoints and an LDS tile, no per-cell scratch; ops compact in d_ops from *d_cursor on (op_off ~0: no room, n_cigar 0xFFFFFFFF: lost walk)
 constexpr uint32_t SP_ANCHOR_SKIP = 0xFFFFFFFFu;     // b index of a pair of a device-made pair list that sp_launch_anchor is to skip (votes 0, diagonal 0)

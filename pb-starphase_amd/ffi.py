@@ -325,6 +325,7 @@ def lib():
         "sp_ctx_destroy": (None, [vp]),
         "sp_affine_rescore_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, vp]),
         "sp_affine_align_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, vp, vp, u32, vp]),
+        "sp_affine_rescore_mappings_audit": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, i32, u32, i32, i32, vp, vp, vp]),
         "sp_hla_realign_cigars": (i32, [vp, vp, vp, vp, u32, vp, u32, vp]),
         "sp_pileup_batch": (i32, [vp, vp, vp, vp, u64, vp, vp, u32, vp, vp, vp]),
         "sp_align_pileup_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), vp, vp, vp, vp, vp]),
@@ -481,6 +482,21 @@ class Context:
         op = sp_affine_opts(a, 4, 6, 2, 26, 1, 1)
         self.check(lib().sp_affine_rescore_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), int(band), _ptr(out)))
         return out
+
+    def rescore_mappings_audit(self, A, B, pairs, a=1, band=64, target_is_a=False, events_stride=128, windows=1, ends_only=0):
+        """sp_affine_rescore_mappings_audit: pairs = [(a index, b index, diag = b_pos - a_pos, max_ed)] (A streamed, B window side) -> (what affine_rescore returns:
+        a_* on the query, b_* on the target; route int32[n]: 0 closed form, 1 DP over the rows around the clusters, 2 DP over all rows, 3 no mapping;
+        diag int32[n] = target position - query position the DP is, or would be, centred on)"""
+        rows = np.zeros(len(pairs), PAIR_DTYPE)
+        for i, pr in enumerate(pairs):
+            rows[i] = (pr[0], pr[1], pr[2], pr[3])
+        out = np.zeros(len(pairs), AFFINE_DTYPE)
+        route = np.zeros(len(pairs), np.int32)
+        diag = np.zeros(len(pairs), np.int32)
+        op = sp_affine_opts(a, 4, 6, 2, 26, 1, 1)
+        self.check(lib().sp_affine_rescore_mappings_audit(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), int(band), 1 if target_is_a else 0, int(events_stride),
+                                                          int(windows), int(ends_only), _ptr(out), _ptr(route), _ptr(diag)))
+        return out, route, diag
 
     def affine_align(self, A, B, pairs, a=1, band=64, cigar_stride=1024):
         """sp_affine_align_batch: pairs = [(a index, b index, diag = b_pos - a_pos[, max_ed])] -> (what affine_rescore returns, cigar uint32[n][cigar_stride] in BAM
