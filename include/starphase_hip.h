@@ -248,7 +248,7 @@ int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, con
 /* ------------------------------------------------------------------ align + pileup + summary in one device-resident pass
  * sp_affine_align_batch(band = 64, cigar_stride = 4096) followed by sp_pileup_batch and, per target, sp_support_summarize -- without the op rows leaving the device.
  * pairs / opts as sp_affine_align_batch takes them (a = query in A, b = target in B, diag, max_ed < 0: skip), col_offset as sp_pileup_batch takes it.  The band is
- * 64 diagonals; there is no other.  Every output is optional (NULL: not computed where nothing else needs it, and never downloaded):
+ * 64 diagonals; sp_align_pileup_band_batch (below) is the same pass on 256 diagonals, or on 64 with a second try on 256.  Every output is optional (NULL: not computed where nothing else needs it, and never downloaded):
  *   aln        n_pairs records, bit for bit sp_affine_align_batch's
  *   cols       col_offset[n_targets] records, bit for bit sp_pileup_batch's over those alignments (a pair with score 0 contributes nothing)
  *   summaries  one per target of B: what sp_support_summarize returns for the target's columns, with n_aligned = the pairs naming the target with score > 0,
@@ -268,6 +268,20 @@ int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, con
 typedef struct { uint32_t n_members, n_aligned, n_unaligned, length, min_depth, median_depth, n_contested, reserved_; } sp_support_summary;   /* 32 bytes; the rule: consensus support, below */
 int32_t sp_align_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts,
                               const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members);
+
+/* The same pass with the band chosen by the caller: sp_align_pileup_batch is this call with band = 64, retry_band = 0, band_used = NULL.
+ *   band        64 or 256 diagonals around each pair's diag: aln is bit for bit sp_affine_align_batch's at that band
+ *   retry_band  0: none.  256 (with band = 64 only): every pair that was attempted (max_ed >= 0) and came back from the 64-diagonal launch with score 0 or without ops
+ *               is aligned again on 256 diagonals, and that result stands -- the rule of sp_hla_consensus_support.  The list of those pairs is made, put in pair order and
+ *               read by the second launch on the device: there is no host round trip between the two launches of a slice.
+ *   band_used   optional, n_pairs entries: 0 when the pair did not align, otherwise the band (64 or 256) that produced its alignment
+ * Any other band / retry_band returns SP_ERR_INVALID_ARG before any launch.  Everything else -- outputs, slices, pooled memory, errors -- as sp_align_pileup_batch.
+ * The 256-diagonal launch is the map kernel with four diagonals per lane; it runs its walk's rows again in blocks of SP_ALIGN_PILEUP_WIDE_ROWS target rows (one
+ * checkpoint of 3 x 256 scores per block and grid slot). */
+#define SP_ALIGN_PILEUP_WIDE_ROWS 128
+int32_t sp_align_pileup_band_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts,
+                                   int32_t band, int32_t retry_band, const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols,
+                                   sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used);
 
 /* ------------------------------------------------------------------ HLA database
  * Replaces HlaRealigner::new + create_hla_fasta (src/hla/realigner.rs:42-91,497-526) and the per-call

@@ -18,6 +18,7 @@ pub const SP_PILEUP_TILE: i64 = 2048;
 pub const SP_PILEUP_WAVES: i64 = 4;
 pub const SP_ALIGN_PILEUP_SLICE: i64 = 4096;
 pub const SP_SUPPORT_HIST_BINS: i64 = 1024;
+pub const SP_ALIGN_PILEUP_WIDE_ROWS: i64 = 128;
 pub const SP_K1_SEL: i64 = 16;
 pub const SP_MAX_CHAIN: i64 = 64;
 pub const SP_CYP_MAXCONS: i64 = 64;
@@ -767,6 +768,7 @@ extern "C" {
     pub fn sp_affine_align_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, band: i32, out: *mut sp_affine_aln, cigar: *mut u32, cigar_stride: u32, n_cigar: *mut u32) -> i32;
     pub fn sp_pileup_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, aln: *const sp_affine_aln, cigar: *const u32, cigar_stride: u32, n_cigar: *const u32, col_offset: *const u64, out: *mut sp_pileup_col) -> i32;
     pub fn sp_align_pileup_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, col_offset: *const u64, aln: *mut sp_affine_aln, cols: *mut sp_pileup_col, summaries: *mut sp_support_summary, n_members: *const u32) -> i32;
+    pub fn sp_align_pileup_band_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, band: i32, retry_band: i32, col_offset: *const u64, aln: *mut sp_affine_aln, cols: *mut sp_pileup_col, summaries: *mut sp_support_summary, n_members: *const u32, band_used: *mut u32) -> i32;
     pub fn sp_hla_db_create(ctx: *mut sp_ctx, desc: *const sp_hla_db_desc, out: *mut *mut sp_hla_db) -> i32;
     pub fn sp_hla_db_free(db: *mut sp_hla_db);
     pub fn sp_hla_seed_index_info(ctx: *mut sp_ctx, db: *const sp_hla_db, out: *mut i64) -> i32;

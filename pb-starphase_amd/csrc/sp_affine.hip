@@ -822,12 +822,29 @@ extern "C" int32_t sp_affine_align_batch(sp_ctx* ctx, const sp_seqset* A, const 
 // runs here make those comparisons on the same scores in the same order; the counters and start cells affine_tb_kernel carries along take no part in them.  So the best
 // cell, the direction bytes and hence the walk and its ops are the same; NM is the number of the path's columns that are not '=' and the start cell is the cell the walk
 // ends in, which is what the carried counters add up to along that same path.
+//
+// The wide instance (DPL = 4: 256 diagonals, sp_align_pileup_band_batch and the second try of sp_hla_consensus_support) is the same kernel with affine_tb_kernel<4>'s
+// cell layout: lane l holds diagonals 4 l .. 4 l + 3, the upper neighbour of its last diagonal is lane l + 1's first, the F scan runs over the maximum of the lane's
+// four keys and is finished inside the lane in diagonal order (the diagonal index, 0 .. 255, still fills the key's low 8 bits).  The argument above carries over word
+// for word with affine_tb_kernel<4> in the place of affine_tb_kernel<1>: H / E1 / E2 are int[4], scores only, and every comparison is the one that kernel makes, in its
+// order.  A row of direction bytes is 256 bytes, a lane's four cells one 32-bit LDS store (as affine_tb_kernel<4> stores them to global memory), lane 0's walk is the
+// same with that row pitch, and a checkpoint is 3 x 256 words = 3 KB.
+//   rows per block   AF_MAP_ROWS_WIDE = SP_ALIGN_PILEUP_WIDE_ROWS = 128: a 32 KB tile
+//   slots per CU     AF_MAP_SLOTS_WIDE = 4 (the 64-diagonal instance: 8): one wave per SIMD
+//   LDS              32,768 + target length + 384 bytes: 36.6 KB for a 3.5 kb target (four workgroups a CU), 49.2 KB for 16 kb (three)
+//   pooled scratch   slots x ((max target / 128 + 2) checkpoints x 3 KB + 16 KB ring); 1,024 slots on 256 CUs: 107 MB for 3.5 kb targets, 416 MB for 16 kb ones,
+//                    whatever the number of pairs (the 64-diagonal instance: 2,048 slots x 768-byte checkpoints = 79 MB and 233 MB)
+// 64 rows per block halve the tile, but the checkpoints double and only buy occupancy if the slots double as well: four times the checkpoint scratch.  That
+// alternative has not been measured; the choice rests on these figures (profiles/support/wide_map.txt: 16.6 ms against affine_tb_kernel<4>'s 37.6).
 // ------------------------------------------------------------------------------------------------------------------------------
 namespace {
 
 constexpr int AF_MAP_ROWS = 128;
+constexpr int AF_MAP_ROWS_WIDE = SP_ALIGN_PILEUP_WIDE_ROWS;
+constexpr int AF_MAP_SLOTS = 8, AF_MAP_SLOTS_WIDE = 4;     // workgroups of the persistent grid per CU
 constexpr uint32_t AF_MAP_RING = 4096;
 constexpr uint64_t AF_MAP_NO_OPS = ~0ull;
+static_assert((AF_MAP_ROWS & (AF_MAP_ROWS - 1)) == 0 && (AF_MAP_ROWS_WIDE & (AF_MAP_ROWS_WIDE - 1)) == 0, "rows per block: a power of two");
 
 // af_scan on the key alone
 template <int CTRL, int ROW_MASK>
@@ -843,13 +860,16 @@ __device__ __forceinline__ uint32_t af_map_scan(uint32_t v) {
     return v;
 }
 
-template <bool HASN>
-__global__ __launch_bounds__(64) void affine_map_kernel(SeqSetView A, SeqSetView B, const AfPair* __restrict__ pairs, uint32_t n_pairs, sp_affine_opts o, sp_affine_aln* __restrict__ out,
+// n_live: the launch runs min(*n_live, n_pairs) entries (a count a kernel before it left); list: entry k is pair list[k], its results go to that pair's own index
+template <int DPL, bool HASN>
+__global__ __launch_bounds__(64) void affine_map_kernel(SeqSetView A, SeqSetView B, const AfPair* __restrict__ pairs, uint32_t n_pairs, const uint32_t* __restrict__ n_live,
+                                                         const uint32_t* __restrict__ list, sp_affine_opts o, sp_affine_aln* __restrict__ out,
                                                          int t_words_max, int32_t* __restrict__ ckpt_all, uint32_t ckpt_per_slot, uint32_t* __restrict__ ring_all,
                                                          uint32_t* __restrict__ ops_out, uint64_t ops_cap, unsigned long long* __restrict__ cursor, uint64_t* __restrict__ op_off,
                                                          uint32_t* __restrict__ n_cigar) {
     extern __shared__ uint32_t lds[];
-    constexpr int BAND = 64;
+    constexpr int BAND = 64 * DPL;
+    constexpr int ROWS = DPL == 1 ? AF_MAP_ROWS : AF_MAP_ROWS_WIDE;
     constexpr bool hasn = HASN;
     const int lane = threadIdx.x;
     int32_t* ckpt = ckpt_all + (size_t)blockIdx.x * ckpt_per_slot * (3 * BAND);
@@ -857,7 +877,10 @@ __global__ __launch_bounds__(64) void affine_map_kernel(SeqSetView A, SeqSetView
     uint32_t* LT = lds; uint32_t* LQ = LT + t_words_max; uint32_t* NT = LQ + t_words_max + 2 * BAND / 16 + 8; uint32_t* NQ = NT + t_words_max;
     uint8_t* tile = (uint8_t*)(NQ + t_words_max + 2 * BAND / 16 + 8);
     const int q1 = o.q, e1 = o.e, q2 = o.q2, e2 = o.e2;
-    for (uint32_t p = blockIdx.x; p < n_pairs; p += gridDim.x) {
+    uint32_t n_run = n_pairs;
+    if (n_live) { const uint32_t v = *n_live; n_run = v < n_pairs ? v : n_pairs; }
+    for (uint32_t k = blockIdx.x; k < n_run; k += gridDim.x) {
+        const uint32_t p = list ? list[k] : k;
         const AfPair pr = pairs[p];
         const int tlen = pr.pad < 0 ? 0 : B.len[pr.b], qlen = pr.pad < 0 ? 0 : A.len[pr.a];
         sp_affine_aln res; res.score = 0; res.nm = 0; res.a_start = res.a_end = res.b_start = res.b_end = 0;
@@ -882,51 +905,70 @@ __global__ __launch_bounds__(64) void affine_map_kernel(SeqSetView A, SeqSetView
             if (hasn && ((N[w] >> sh) & 1u)) return 4;
             return (int)((W[w] >> sh) & 3u);
         };
-        const int idx = lane;
         // ---- forward: affine_tb_kernel's rows on scores alone (its comparisons, so its decisions): the best cell and the checkpoints
-        int hs = AF_NEG, e1s = AF_NEG, e2s = AF_NEG;
+        int hs[DPL], e1s[DPL], e2s[DPL];
+#pragma unroll
+        for (int c = 0; c < DPL; ++c) hs[c] = e1s[c] = e2s[c] = AF_NEG;
         int bs = 0, bi = -1, bj = -1;
         for (int i = i_lo; i <= i_hi; ++i) {
-            if (((i - i_lo) & (AF_MAP_ROWS - 1)) == 0) {
-                int32_t* c = ckpt + (size_t)((i - i_lo) / AF_MAP_ROWS) * (3 * BAND);
-                c[lane] = hs; c[BAND + lane] = e1s; c[2 * BAND + lane] = e2s;
+            if (((i - i_lo) & (ROWS - 1)) == 0) {
+                // a lane's DPL scores are DPL consecutive words of each of the checkpoint's three planes
+                int32_t* cp = ckpt + (size_t)((i - i_lo) / ROWS) * (3 * BAND) + lane * DPL;
+#pragma unroll
+                for (int c = 0; c < DPL; ++c) { cp[c] = hs[c]; cp[BAND + c] = e1s[c]; cp[2 * BAND + c] = e2s[c]; }
             }
             const int ct = base_of(LT, NT, i, tw0);
-            const int hus = spw::from_upper(hs, AF_NEG), eus = spw::from_upper(e1s, AF_NEG), eu2s = spw::from_upper(e2s, AF_NEG);
-            const int j = i + klo + idx;
-            const bool valid = (unsigned)j < (unsigned)qlen;
-            int a1s, a2s;
-            { const int eo = hus - q1; a1s = (eus > eo ? eus : eo) - e1; }
-            { const int eo = hus - q2; a2s = (eu2s > eo ? eu2s : eo) - e2; }
-            if (a1s < AF_NEG) a1s = AF_NEG;
-            if (a2s < AF_NEG) a2s = AF_NEG;
-            int h = hs;
-            const int cq = valid ? base_of(LQ, NQ, j, qw0) : 4;
-            const bool ambi = ct > 3 || cq > 3;
-            const int sub = ambi ? -o.sc_ambi : (ct == cq ? o.a : -o.b);
-            if (h <= 0) h = 0;
-            h += sub;
-            if (a1s > h) h = a1s;
-            if (!valid) { h = AF_NEG; a1s = AF_NEG; a2s = AF_NEG; }
-            int srcs = h; if (a2s > srcs) srcs = a2s;
-            const bool offer = valid && srcs > 0;
-            // the scan's keys order by (score + position * e, position): the maximum alone is needed, the counters of AfKey do not ride along
-            uint32_t k1 = offer ? (((uint32_t)(srcs + idx * e1) + AF_BIAS) << 8 | (uint32_t)idx) : 0u;
-            uint32_t k2 = offer ? (((uint32_t)(srcs + idx * e2) + AF_BIAS) << 8 | (uint32_t)idx) : 0u;
-            k1 = af_map_scan(k1); k2 = af_map_scan(k2);
-            const uint32_t in1 = (uint32_t)spw::from_lower((int)k1, 0), in2 = (uint32_t)spw::from_lower((int)k2, 0);
-            int f1s = AF_NEG, f2s = AF_NEG;
-            if (in1) f1s = (int)((in1 >> 8) - AF_BIAS) - q1 - idx * e1;
-            if (in2) f2s = (int)((in2 >> 8) - AF_BIAS) - q2 - idx * e2;
-            if (valid) {
-                if (f1s > h) h = f1s;
-                if (a2s > h) h = a2s;
-                if (f2s > h) h = f2s;
+            // the diagonal above the lane's last cell: lane l + 1's first cell of the row before
+            const int upH = spw::from_upper(hs[0], AF_NEG), upE1 = spw::from_upper(e1s[0], AF_NEG), upE2 = spw::from_upper(e2s[0], AF_NEG);
+            int hA[DPL], a1n[DPL], a2n[DPL]; uint32_t k1[DPL], k2[DPL]; bool valid[DPL];
+#pragma unroll
+            for (int c = 0; c < DPL; ++c) {
+                const int idx = lane * DPL + c, j = i + klo + idx;
+                valid[c] = (unsigned)j < (unsigned)qlen;
+                const int hus = c + 1 < DPL ? hs[c + 1] : upH, eus = c + 1 < DPL ? e1s[c + 1] : upE1, eu2s = c + 1 < DPL ? e2s[c + 1] : upE2;
+                int a1s, a2s;
+                { const int eo = hus - q1; a1s = (eus > eo ? eus : eo) - e1; }
+                { const int eo = hus - q2; a2s = (eu2s > eo ? eu2s : eo) - e2; }
+                if (a1s < AF_NEG) a1s = AF_NEG;
+                if (a2s < AF_NEG) a2s = AF_NEG;
+                int h = hs[c];
+                const int cq = valid[c] ? base_of(LQ, NQ, j, qw0) : 4;
+                const bool ambi = ct > 3 || cq > 3;
+                const int sub = ambi ? -o.sc_ambi : (ct == cq ? o.a : -o.b);
                 if (h <= 0) h = 0;
-                const bool better = h > bs || (h == bs && h > 0 && (i + j < bi + bj || (i + j == bi + bj && i < bi)));
-                bs = better ? h : bs; bi = better ? i : bi; bj = better ? j : bj;
+                h += sub;
+                if (a1s > h) h = a1s;
+                if (!valid[c]) { h = AF_NEG; a1s = AF_NEG; a2s = AF_NEG; }
+                int srcs = h; if (a2s > srcs) srcs = a2s;
+                const bool offer = valid[c] && srcs > 0;
+                // the scan's keys order by (score + position * e, position): the maximum alone is needed, the counters of AfKey do not ride along
+                k1[c] = offer ? (((uint32_t)(srcs + idx * e1) + AF_BIAS) << 8 | (uint32_t)idx) : 0u;
+                k2[c] = offer ? (((uint32_t)(srcs + idx * e2) + AF_BIAS) << 8 | (uint32_t)idx) : 0u;
+                hA[c] = h; a1n[c] = a1s; a2n[c] = a2s;
             }
-            hs = h; e1s = a1s; e2s = a2s;
+            // exclusive prefix maxima over the diagonals to the left: across the lanes by DPP on the lane's maximum, inside a lane cell by cell
+            uint32_t in1 = k1[0], in2 = k2[0];
+#pragma unroll
+            for (int c = 1; c < DPL; ++c) { in1 = af_map_max(in1, k1[c]); in2 = af_map_max(in2, k2[c]); }
+            in1 = (uint32_t)spw::from_lower((int)af_map_scan(in1), 0); in2 = (uint32_t)spw::from_lower((int)af_map_scan(in2), 0);
+#pragma unroll
+            for (int c = 0; c < DPL; ++c) {
+                const int idx = lane * DPL + c, j = i + klo + idx;
+                int f1s = AF_NEG, f2s = AF_NEG;
+                if (in1) f1s = (int)((in1 >> 8) - AF_BIAS) - q1 - idx * e1;
+                if (in2) f2s = (int)((in2 >> 8) - AF_BIAS) - q2 - idx * e2;
+                int h = hA[c];
+                if (valid[c]) {
+                    if (f1s > h) h = f1s;
+                    if (a2n[c] > h) h = a2n[c];
+                    if (f2s > h) h = f2s;
+                    if (h <= 0) h = 0;
+                    const bool better = h > bs || (h == bs && h > 0 && (i + j < bi + bj || (i + j == bi + bj && i < bi)));
+                    bs = better ? h : bs; bi = better ? i : bi; bj = better ? j : bj;
+                }
+                hs[c] = h; e1s[c] = a1n[c]; e2s[c] = a2n[c];
+                in1 = af_map_max(in1, k1[c]); in2 = af_map_max(in2, k2[c]);
+            }
         }
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) {
@@ -944,49 +986,69 @@ __global__ __launch_bounds__(64) void affine_map_kernel(SeqSetView A, SeqSetView
             run_op = op; run_len = 1;
         };
         while (!done) {
-            const int blk = (ci - i_lo) / AF_MAP_ROWS, r0 = blk * AF_MAP_ROWS, r1 = ci - i_lo;
+            const int blk = (ci - i_lo) / ROWS, r0 = blk * ROWS, r1 = ci - i_lo;
             spw::wave_lds_sync();                           // (the tile before this one has been read)
             {
                 // the block's rows again from its checkpoint: scores alone, affine_tb_kernel's comparisons and records
-                const int32_t* c = ckpt + (size_t)blk * (3 * BAND);
-                int hs = c[lane], e1s = c[BAND + lane], e2s = c[2 * BAND + lane];
+                const int32_t* cp = ckpt + (size_t)blk * (3 * BAND) + lane * DPL;
+                int hs[DPL], e1s[DPL], e2s[DPL];
+#pragma unroll
+                for (int c = 0; c < DPL; ++c) { hs[c] = cp[c]; e1s[c] = cp[BAND + c]; e2s[c] = cp[2 * BAND + c]; }
                 for (int r = r0; r <= r1; ++r) {
                     const int i = i_lo + r;
                     const int ct = base_of(LT, NT, i, tw0);
-                    const int hus = spw::from_upper(hs, AF_NEG), eus = spw::from_upper(e1s, AF_NEG), eu2s = spw::from_upper(e2s, AF_NEG);
-                    const int j = i + klo + idx;
-                    const bool valid = (unsigned)j < (unsigned)qlen;
-                    int a1s, a2s; uint32_t d = AF_D_DIAG;
-                    { const int eo = hus - q1; if (eus > eo) { a1s = eus - e1; d |= AF_D_E1C; } else a1s = eo - e1; }
-                    { const int eo = hus - q2; if (eu2s > eo) { a2s = eu2s - e2; d |= AF_D_E2C; } else a2s = eo - e2; }
-                    if (a1s < AF_NEG) a1s = AF_NEG;
-                    if (a2s < AF_NEG) a2s = AF_NEG;
-                    int h = hs;
-                    const int cq = valid ? base_of(LQ, NQ, j, qw0) : 4;
-                    const bool ambi = ct > 3 || cq > 3;
-                    const int sub = ambi ? -o.sc_ambi : (ct == cq ? o.a : -o.b);
-                    if (h <= 0) { h = 0; d |= AF_D_START; }
-                    h += sub;
-                    if (ambi || ct != cq) d |= AF_D_X;
-                    if (a1s > h) { h = a1s; d = (d & ~7u) | AF_D_E1; }
-                    if (!valid) { h = AF_NEG; a1s = AF_NEG; a2s = AF_NEG; }
-                    int srcs = h; if (a2s > srcs) srcs = a2s;
-                    const bool offer = valid && srcs > 0;
-                    uint32_t k1 = offer ? (((uint32_t)(srcs + idx * e1) + AF_BIAS) << 8 | (uint32_t)idx) : 0u;
-                    uint32_t k2 = offer ? (((uint32_t)(srcs + idx * e2) + AF_BIAS) << 8 | (uint32_t)idx) : 0u;
-                    k1 = af_map_scan(k1); k2 = af_map_scan(k2);
-                    const uint32_t in1 = (uint32_t)spw::from_lower((int)k1, 0), in2 = (uint32_t)spw::from_lower((int)k2, 0);
-                    int f1s = AF_NEG, f2s = AF_NEG;
-                    if (in1) { const int src_idx = (int)(in1 & 0xFFu), v = (int)((in1 >> 8) - AF_BIAS); f1s = v - q1 - idx * e1; if (src_idx < idx - 1) d |= AF_D_F1C; }
-                    if (in2) { const int src_idx = (int)(in2 & 0xFFu), v = (int)((in2 >> 8) - AF_BIAS); f2s = v - q2 - idx * e2; if (src_idx < idx - 1) d |= AF_D_F2C; }
-                    if (valid) {
-                        if (f1s > h) { h = f1s; d = (d & ~7u) | AF_D_F1; }
-                        if (a2s > h) { h = a2s; d = (d & ~7u) | AF_D_E2; }
-                        if (f2s > h) { h = f2s; d = (d & ~7u) | AF_D_F2; }
-                        if (h <= 0) { h = 0; d = (d & ~7u) | AF_D_NONE; }
-                    } else d = AF_D_NONE;
-                    hs = h; e1s = a1s; e2s = a2s;
-                    tile[(r - r0) * BAND + lane] = (uint8_t)d;
+                    const int upH = spw::from_upper(hs[0], AF_NEG), upE1 = spw::from_upper(e1s[0], AF_NEG), upE2 = spw::from_upper(e2s[0], AF_NEG);
+                    int hA[DPL], a1n[DPL], a2n[DPL]; uint32_t k1[DPL], k2[DPL], dir[DPL]; bool valid[DPL];
+#pragma unroll
+                    for (int c = 0; c < DPL; ++c) {
+                        const int idx = lane * DPL + c, j = i + klo + idx;
+                        valid[c] = (unsigned)j < (unsigned)qlen;
+                        const int hus = c + 1 < DPL ? hs[c + 1] : upH, eus = c + 1 < DPL ? e1s[c + 1] : upE1, eu2s = c + 1 < DPL ? e2s[c + 1] : upE2;
+                        int a1s, a2s; uint32_t d = AF_D_DIAG;
+                        { const int eo = hus - q1; if (eus > eo) { a1s = eus - e1; d |= AF_D_E1C; } else a1s = eo - e1; }
+                        { const int eo = hus - q2; if (eu2s > eo) { a2s = eu2s - e2; d |= AF_D_E2C; } else a2s = eo - e2; }
+                        if (a1s < AF_NEG) a1s = AF_NEG;
+                        if (a2s < AF_NEG) a2s = AF_NEG;
+                        int h = hs[c];
+                        const int cq = valid[c] ? base_of(LQ, NQ, j, qw0) : 4;
+                        const bool ambi = ct > 3 || cq > 3;
+                        const int sub = ambi ? -o.sc_ambi : (ct == cq ? o.a : -o.b);
+                        if (h <= 0) { h = 0; d |= AF_D_START; }
+                        h += sub;
+                        if (ambi || ct != cq) d |= AF_D_X;
+                        if (a1s > h) { h = a1s; d = (d & ~7u) | AF_D_E1; }
+                        if (!valid[c]) { h = AF_NEG; a1s = AF_NEG; a2s = AF_NEG; }
+                        int srcs = h; if (a2s > srcs) srcs = a2s;
+                        const bool offer = valid[c] && srcs > 0;
+                        k1[c] = offer ? (((uint32_t)(srcs + idx * e1) + AF_BIAS) << 8 | (uint32_t)idx) : 0u;
+                        k2[c] = offer ? (((uint32_t)(srcs + idx * e2) + AF_BIAS) << 8 | (uint32_t)idx) : 0u;
+                        hA[c] = h; a1n[c] = a1s; a2n[c] = a2s; dir[c] = d;
+                    }
+                    uint32_t in1 = k1[0], in2 = k2[0];
+#pragma unroll
+                    for (int c = 1; c < DPL; ++c) { in1 = af_map_max(in1, k1[c]); in2 = af_map_max(in2, k2[c]); }
+                    in1 = (uint32_t)spw::from_lower((int)af_map_scan(in1), 0); in2 = (uint32_t)spw::from_lower((int)af_map_scan(in2), 0);
+                    uint32_t packed = 0;
+#pragma unroll
+                    for (int c = 0; c < DPL; ++c) {
+                        const int idx = lane * DPL + c;
+                        int f1s = AF_NEG, f2s = AF_NEG; uint32_t d = dir[c];
+                        if (in1) { const int src_idx = (int)(in1 & 0xFFu), v = (int)((in1 >> 8) - AF_BIAS); f1s = v - q1 - idx * e1; if (src_idx < idx - 1) d |= AF_D_F1C; }
+                        if (in2) { const int src_idx = (int)(in2 & 0xFFu), v = (int)((in2 >> 8) - AF_BIAS); f2s = v - q2 - idx * e2; if (src_idx < idx - 1) d |= AF_D_F2C; }
+                        int h = hA[c];
+                        if (valid[c]) {
+                            if (f1s > h) { h = f1s; d = (d & ~7u) | AF_D_F1; }
+                            if (a2n[c] > h) { h = a2n[c]; d = (d & ~7u) | AF_D_E2; }
+                            if (f2s > h) { h = f2s; d = (d & ~7u) | AF_D_F2; }
+                            if (h <= 0) { h = 0; d = (d & ~7u) | AF_D_NONE; }
+                        } else d = AF_D_NONE;
+                        hs[c] = h; e1s[c] = a1n[c]; e2s[c] = a2n[c];
+                        in1 = af_map_max(in1, k1[c]); in2 = af_map_max(in2, k2[c]);
+                        packed |= d << (8 * c);
+                    }
+                    // the row's records: the lane's DPL cells are DPL consecutive bytes of the tile's row -- one byte, or one 32-bit word, a lane
+                    if (DPL == 1) tile[(r - r0) * BAND + lane] = (uint8_t)packed;
+                    else ((uint32_t*)tile)[(r - r0) * (BAND / 4) + lane] = packed;
                 }
             }
             spw::wave_lds_sync();
@@ -1022,7 +1084,7 @@ __global__ __launch_bounds__(64) void affine_map_kernel(SeqSetView A, SeqSetView
                 uint64_t at = AF_MAP_NO_OPS;
                 if (n_ops <= AF_MAP_RING) {
                     at = atomicAdd(cursor, (unsigned long long)n_ops);
-                    if (at + n_ops <= ops_cap) for (uint32_t k = 0; k < n_ops; ++k) ops_out[at + k] = ring[n_ops - 1 - k];
+                    if (at + n_ops <= ops_cap) for (uint32_t x = 0; x < n_ops; ++x) ops_out[at + x] = ring[n_ops - 1 - x];
                     else at = AF_MAP_NO_OPS;
                 }
                 op_off[p] = at;
@@ -1034,28 +1096,33 @@ __global__ __launch_bounds__(64) void affine_map_kernel(SeqSetView A, SeqSetView
 } // namespace
 
 // the K2 map over a device pair list (AfPair rows; pad < 0: no mapping): results, op counts and op offsets per pair, the ops in d_ops (ops_cap words) from *d_cursor on.
-// Everything it needs beside them is pooled under `prefix` and sized by the grid, not by the pairs.
-int sp_launch_affine_map(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const void* d_pairs, uint64_t n_pairs, const sp_affine_opts& o, sp_affine_aln* d_out,
-                         uint32_t* d_n_cigar, uint64_t* d_op_off, uint32_t* d_ops, uint64_t ops_cap, unsigned long long* d_cursor, const char* prof_name) {
+// Everything it needs beside them is pooled and sized by the grid, not by the pairs (the two bands keep checkpoint lists of their own: their slots differ in size and number).
+int sp_launch_affine_map(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const void* d_pairs, uint64_t n_pairs, const sp_affine_opts& o, int band, sp_affine_aln* d_out,
+                         uint32_t* d_n_cigar, uint64_t* d_op_off, uint32_t* d_ops, uint64_t ops_cap, unsigned long long* d_cursor, const char* prof_name,
+                         const uint32_t* d_n_live, const uint32_t* d_list, uint64_t prof_cells) {
     if (n_pairs == 0) return SP_OK;
+    if (band != 64 && band != 256) return sp_fail(ctx, SP_ERR_INVALID_ARG, "affine map: band must be 64 or 256");
     if (n_pairs > 0xFFFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "affine map: too many pairs");
     if (B->max_len > 65535 || A->max_len > 65535) return sp_fail(ctx, SP_ERR_TOO_LONG, "affine: sequences of up to 65,535 bases");
-    const int band = 64;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(n_pairs, (uint64_t)ctx->num_cus * 8);
-    const uint32_t ckpt_per_slot = (uint32_t)(B->max_len / AF_MAP_ROWS + 2);
-    int32_t* d_ckpt = (int32_t*)sp_pool(ctx, "af_map_ckpt", (size_t)ctx->num_cus * 8 * ckpt_per_slot * 3 * band * 4);
-    uint32_t* d_ring = (uint32_t*)sp_pool(ctx, "af_map_ring", (size_t)ctx->num_cus * 8 * AF_MAP_RING * 4);
+    const bool wide = band == 256;
+    const int rows = wide ? AF_MAP_ROWS_WIDE : AF_MAP_ROWS;
+    const uint64_t slots = (uint64_t)ctx->num_cus * (wide ? AF_MAP_SLOTS_WIDE : AF_MAP_SLOTS);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(n_pairs, slots);
+    const uint32_t ckpt_per_slot = (uint32_t)(B->max_len / rows + 2);
+    int32_t* d_ckpt = (int32_t*)sp_pool(ctx, wide ? "af_map_ckpt_wide" : "af_map_ckpt", (size_t)slots * ckpt_per_slot * 3 * band * 4);
+    uint32_t* d_ring = (uint32_t*)sp_pool(ctx, "af_map_ring", (size_t)ctx->num_cus * AF_MAP_SLOTS * AF_MAP_RING * 4);
     if (!d_ckpt || !d_ring) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "affine map buffers");
     const int t_words_max = (B->max_len >> 4) + 4;
-    const size_t lds_bytes = sizeof(uint32_t) * (size_t)(4 * t_words_max + 2 * (2 * band / 16 + 8)) + (size_t)AF_MAP_ROWS * band;
+    const size_t lds_bytes = sizeof(uint32_t) * (size_t)(4 * t_words_max + 2 * (2 * band / 16 + 8)) + (size_t)rows * band;
     if (lds_bytes > 160 * 1024) return sp_fail(ctx, SP_ERR_TOO_LONG, "affine map: sequences do not fit the LDS");
     const bool hasn = A->has_n || B->has_n;
-    ProfScope ps(ctx, prof_name, n_pairs);
-#define SP_AF_MAP_LAUNCH(N) do { \
-        (void)hipFuncSetAttribute((const void*)affine_map_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-        hipLaunchKernelGGL((affine_map_kernel<N>), dim3(grid), dim3(64), lds_bytes, ctx->stream, A->view(), B->view(), (const AfPair*)d_pairs, (uint32_t)n_pairs, o, d_out, t_words_max, \
+    ProfScope ps(ctx, prof_name, prof_cells == ~0ull ? n_pairs : prof_cells);
+#define SP_AF_MAP_LAUNCH(D, N) do { \
+        (void)hipFuncSetAttribute((const void*)affine_map_kernel<D, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
+        hipLaunchKernelGGL((affine_map_kernel<D, N>), dim3(grid), dim3(64), lds_bytes, ctx->stream, A->view(), B->view(), (const AfPair*)d_pairs, (uint32_t)n_pairs, d_n_live, d_list, o, d_out, t_words_max, \
                            d_ckpt, ckpt_per_slot, d_ring, d_ops, ops_cap, d_cursor, d_op_off, d_n_cigar); } while (0)
-    if (hasn) SP_AF_MAP_LAUNCH(true); else SP_AF_MAP_LAUNCH(false);
+    if (wide) { if (hasn) SP_AF_MAP_LAUNCH(4, true); else SP_AF_MAP_LAUNCH(4, false); }
+    else { if (hasn) SP_AF_MAP_LAUNCH(1, true); else SP_AF_MAP_LAUNCH(1, false); }
 #undef SP_AF_MAP_LAUNCH
     if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "affine map launch failed");
     return SP_OK;

@@ -1719,7 +1719,7 @@ static int32_t k2_score_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_items
             if (!d_ops) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "map_consensus ops");
             (void)hipMemsetAsync(d_cur, 0, 8, ctx->stream);
             for (int L = 0; L < 2 && rc == SP_OK; ++L)
-                rc = sp_launch_affine_map(ctx, L == 0 ? db->cdna_gene : db->dna_gene, cons, d_mp + (size_t)L * T, T, ao, d_maf + (size_t)L * T, d_mnc + (size_t)L * T, d_moff + (size_t)L * T,
+                rc = sp_launch_affine_map(ctx, L == 0 ? db->cdna_gene : db->dna_gene, cons, d_mp + (size_t)L * T, T, ao, 64, d_maf + (size_t)L * T, d_mnc + (size_t)L * T, d_moff + (size_t)L * T,
                                           d_ops, ops_cap, d_cur, L == 0 ? "k2_map_cdna" : "k2_map_dna");
             if (rc != SP_OK) break;
             (void)hipMemcpyAsync(&used, d_cur, 8, hipMemcpyDeviceToHost, ctx->stream);

@@ -173,8 +173,11 @@ int sp_rescore_mappings(sp_ctx* ctx, const sp_seqset* Aw, const sp_seqset* Bw, c
     // ends_only > 0: the caller takes the EXTENT of the mapping only -- an end takes the DP unless the cell's path, scored with true gap runs from that end inwards, clears it and no clustered edit lies within ends_only bases of it
     // windows 0 | 1: the DP over all rows | the rows around the clusters (-1: as context option mm2_rescore says)
     // d_audit: AfAudit rows (route, diagonal) per pair for sp_affine_rescore_mappings_audit (af_classify_kernel)
-int sp_launch_affine_map(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const void* d_pairs /* sp_pair rows, max_ed < 0: skip */, uint64_t n_pairs, const sp_affine_opts& o, sp_affine_aln* d_out,
-                         uint32_t* d_n_cigar, uint64_t* d_op_off, uint32_t* d_ops, uint64_t ops_cap, unsigned long long* d_cursor, const char* prof_name);   // sp_affine.hip: the K2 map -- sp_affine_align_batch's alignment on 64 diagonals from checkpoints and an LDS tile, no per-cell scratch; ops compact in d_ops from *d_cursor on (op_off ~0: no room, n_cigar 0xFFFFFFFF: lost walk)
+int sp_launch_affine_map(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const void* d_pairs /* sp_pair rows, max_ed < 0: skip */, uint64_t n_pairs, const sp_affine_opts& o, int band, sp_affine_aln* d_out,
+                         uint32_t* d_n_cigar, uint64_t* d_op_off, uint32_t* d_ops, uint64_t ops_cap, unsigned long long* d_cursor, const char* prof_name,
+                         const uint32_t* d_n_live = nullptr, const uint32_t* d_list = nullptr, uint64_t prof_cells = ~0ull);   // sp_affine.hip: the K2 map -- sp_affine_align_batch's alignment on 64 or 256 diagonals from checkpoints and an LDS tile, no per-cell scratch; ops compact in d_ops from *d_cursor on (op_off ~0: no room, n_cigar 0xFFFFFFFF: lost walk)
+    // d_n_live: the launch runs min(*d_n_live, n_pairs) entries, a number a kernel before it left in device memory (sp_launch_affine's d_n_live); d_list: entry k is pair d_list[k] of
+    // d_pairs (results in place, at the pair's own index) instead of pair k; prof_cells: what the profile entry counts (default: n_pairs)
 constexpr uint32_t SP_ANCHOR_SKIP = 0xFFFFFFFFu;     // b index of a pair of a device-made pair list that sp_launch_anchor is to skip (votes 0, diagonal 0)
 int sp_launch_cells_wide(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const CellDesc* d_cells, uint64_t n_cells, sp_aln* d_out);
 int sp_launch_pack_on(hipStream_t stream, int num_cus, int format, const void* d_src, const uint64_t* d_off, const uint64_t* d_word_off, const int32_t* d_len, uint32_t n,

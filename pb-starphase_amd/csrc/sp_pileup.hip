@@ -125,6 +125,45 @@ __global__ void ap_status_kernel(const sp_affine_aln* __restrict__ aln, const ui
     else if (aln[i].score > 0 && op_off[i] == AP_NO_OPS) status[1] = 1u;
 }
 
+// The second try of a slice (retry_band of sp_align_pileup_band_batch), decided on the device.  One thread per pair of the slice: a pair that was attempted (max_ed >= 0)
+// and came back from the first map launch with score 0 or without ops goes onto the retry list.  A wave takes its places with one ballot and one atomic on the list's
+// counter; tried[i] (optional) keeps the decision for band_used.
+__global__ void ap_retry_list_kernel(const sp_pair* __restrict__ pairs, const sp_affine_aln* __restrict__ aln, const uint32_t* __restrict__ n_cigar, uint32_t n,
+                                     uint32_t* __restrict__ list, uint32_t* __restrict__ count, uint32_t* __restrict__ tried) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & (SP_WAVE - 1);
+    const bool want = i < n && pairs[i].max_ed >= 0 && (aln[i].score <= 0 || n_cigar[i] == 0);
+    const unsigned long long vote = __ballot(want);
+    if (vote) {
+        const int leader = __ffsll((long long)vote) - 1;
+        uint32_t base = 0;
+        if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(vote));
+        base = (uint32_t)__shfl((int)base, leader);
+        if (want) list[base + (uint32_t)__popcll(vote & ((1ull << lane) - 1ull))] = i;
+    }
+    if (i < n && tried) tried[i] = want ? 1u : 0u;
+}
+
+// The list in pair order (the waves took their places in the order they arrived): entry k goes to the place of its rank among the *count distinct pair numbers.  The
+// second launch then meets the pairs, and takes its op rows, in an order that depends on the results of the first alone.
+__global__ void ap_retry_sort_kernel(const uint32_t* __restrict__ list, const uint32_t* __restrict__ count, uint32_t* __restrict__ sorted) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x, n = *count;
+    if (k >= n) return;
+    const uint32_t v = list[k];
+    uint32_t rank = 0;
+    for (uint32_t x = 0; x < n; ++x) rank += list[x] < v ? 1u : 0u;
+    sorted[rank] = v;
+}
+
+// band_used: 0 for a pair without an alignment, else the band its alignment came from (in place over tried[]: the second try's when the pair was on the retry list)
+__global__ void ap_band_used_kernel(const sp_affine_aln* __restrict__ aln, const uint32_t* __restrict__ n_cigar, uint32_t n, uint32_t band, uint32_t retry_band, int has_tried,
+                                    uint32_t* __restrict__ tried_then_band) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool second = has_tried && tried_then_band[i] != 0u;
+    tried_then_band[i] = (aln[i].score > 0 && n_cigar[i] > 0) ? (second ? retry_band : band) : 0u;
+}
+
 // sp_support_summarize per target, on the device.  One workgroup per target, one pass over its columns: the minimum depth and the contested columns fall out of it, and a
 // histogram of the depths in LDS gives the lower median -- element (length - 1) / 2 of the sorted depths is the first bin at which the running count exceeds that rank.
 // A depth is at most the number of pairs that name the target.  With more possible depths than AP_BINS the bins are W = ceil(range / AP_BINS) depths wide, and the bin the
@@ -294,21 +333,25 @@ int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, con
     return SP_OK;
 }
 
-int32_t sp_align_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, const uint64_t* col_offset,
-                              sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members) {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    if (!A || !B || !opts || !col_offset || (n_pairs && !pairs)) return sp_fail(ctx, SP_ERR_INVALID_ARG, "align_pileup: null argument");
-    if (n_pairs > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "align_pileup: too many pairs");
+// sp_align_pileup_band_batch for the library's own callers as well: `who` begins its error texts, prof[] names its four launches (map, second map, pileup, summary) in the
+// context's profile, and the first map launch counts the pairs it attempts (max_ed >= 0) when count_attempted is set, every pair of the slice otherwise.
+static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
+                                const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
+                                const std::string& who, const char* const prof[4], bool count_attempted) {
+    if (!A || !B || !opts || !col_offset || (n_pairs && !pairs)) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": null argument");
+    if ((band != 64 && band != 256) || (retry_band != 0 && retry_band != 256) || (retry_band != 0 && band != 64))
+        return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": band must be 64 or 256, retry_band 0 or (with band 64) 256");
+    if (n_pairs > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": too many pairs");
     const uint32_t n_t = B->n, n = (uint32_t)n_pairs;
-    if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "align_pileup: col_offset[0] must be 0");
+    if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": col_offset[0] must be 0");
     for (uint32_t t = 0; t < n_t; ++t)
-        if (col_offset[t + 1] < col_offset[t] || col_offset[t + 1] - col_offset[t] != (uint64_t)B->h_len[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "align_pileup: col_offset does not follow the target lengths");
+        if (col_offset[t + 1] < col_offset[t] || col_offset[t + 1] - col_offset[t] != (uint64_t)B->h_len[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": col_offset does not follow the target lengths");
     const uint64_t n_cols = col_offset[n_t];
     // ---- the pairs by target, from `pairs` alone: target t's pairs of slice s are order[boff[t * (n_slices + 1) + s] ...) (pileup_rows_kernel)
     const uint32_t n_slices = std::max<uint32_t>(1, (n + SP_ALIGN_PILEUP_SLICE - 1) / SP_ALIGN_PILEUP_SLICE);
     std::vector<uint32_t> boff((size_t)n_t * (n_slices + 1) + 1, 0);
     for (uint32_t i = 0; i < n; ++i) {
-        if (pairs[i].a >= A->n || pairs[i].b >= B->n) return sp_fail(ctx, SP_ERR_INVALID_ARG, "align_pileup: index out of range");
+        if (pairs[i].a >= A->n || pairs[i].b >= B->n) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": index out of range");
         ++boff[(size_t)pairs[i].b * (n_slices + 1) + i / SP_ALIGN_PILEUP_SLICE + 1];
     }
     if (n_pairs == 0 && n_t == 0) return SP_OK;
@@ -325,7 +368,7 @@ int32_t sp_align_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* 
     }
     uint64_t n_tiles = 0;
     if (want_table) for (uint32_t t = 0; t < n_t; ++t) n_tiles += ((uint64_t)B->h_len[t] + PU_TILE - 1) / PU_TILE;
-    if (n_tiles > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "align_pileup: too many tiles");
+    if (n_tiles > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": too many tiles");
     (void)hipSetDevice(ctx->device);
     // ---- one staging block, one copy: the pair list as given, the order, the offsets, tiles, column offsets, member counts
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
@@ -336,11 +379,14 @@ int32_t sp_align_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* 
     uint8_t* d_in = (uint8_t*)sp_pool(ctx, "appile_in", in_bytes);
     sp_affine_aln* d_aln = (sp_affine_aln*)sp_pool(ctx, "appile_aln", std::max<size_t>(16, (size_t)n * sizeof(sp_affine_aln)));
     uint32_t* d_nc = (uint32_t*)sp_pool(ctx, "appile_nc", std::max<size_t>(16, (size_t)n * 4));
-    uint64_t* d_off = (uint64_t*)sp_pool(ctx, "appile_off", (size_t)n * 8 + 16);                   // (+ the cursor and the two status words)
+    uint64_t* d_off = (uint64_t*)sp_pool(ctx, "appile_off", (size_t)n * 8 + 32);                   // (+ the cursor, the two status words and the retry list's counter)
+    const uint32_t slice_max = std::min<uint32_t>(std::max<uint32_t>(n, 1), SP_ALIGN_PILEUP_SLICE);
+    uint32_t* d_retry = retry_band ? (uint32_t*)sp_pool(ctx, "appile_retry", (size_t)slice_max * 8) : nullptr;      // the list as the waves made it, and in pair order
+    uint32_t* d_band = (retry_band || band_used) ? (uint32_t*)sp_pool(ctx, "appile_band", std::max<size_t>(16, (size_t)n * 4)) : nullptr;
     uint32_t* d_table = want_table ? (uint32_t*)sp_pool(ctx, "appile_out", std::max<size_t>(16, n_cols * sizeof(sp_pileup_col))) : nullptr;
     sp_support_summary* d_sum = summaries && n_t ? (sp_support_summary*)sp_pool(ctx, "appile_sum", (size_t)n_t * sizeof(sp_support_summary)) : nullptr;
-    if (!h_in || !h_st || !d_in || !d_aln || !d_nc || !d_off || (want_table && !d_table) || (summaries && n_t && !d_sum)) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "align_pileup buffers");
-    unsigned long long* d_cur = (unsigned long long*)(d_off + n); uint32_t* d_status = (uint32_t*)(d_off + n + 1);
+    if (!h_in || !h_st || !d_in || !d_aln || !d_nc || !d_off || (retry_band && !d_retry) || ((retry_band || band_used) && !d_band) || (want_table && !d_table) || (summaries && n_t && !d_sum)) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, who + " buffers");
+    unsigned long long* d_cur = (unsigned long long*)(d_off + n); uint32_t* d_status = (uint32_t*)(d_off + n + 1); uint32_t* d_n_retry = (uint32_t*)(d_off + n + 2);
     {
         if (n) std::memcpy(h_in + at_pairs, pairs, sizeof(sp_pair) * (size_t)n);
         uint32_t* ho = (uint32_t*)(h_in + at_order);
@@ -371,41 +417,68 @@ int32_t sp_align_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* 
         uint32_t* d_ops = nullptr;
         for (int attempt = 0; m > 0; ++attempt) {
             d_ops = (uint32_t*)sp_pool(ctx, "appile_ops", (size_t)ops_cap * 4);
-            if (!d_ops) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "align_pileup: op rows");
-            SP_HIP_CHECK(ctx, hipMemsetAsync(d_cur, 0, 16, ctx->stream));
-            const int rc = sp_launch_affine_map(ctx, A, B, d_pairs + p0, m, *opts, d_aln + p0, d_nc + p0, d_off + p0, d_ops, ops_cap, d_cur, "align_pileup_map");
+            if (!d_ops) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, who + ": op rows");
+            SP_HIP_CHECK(ctx, hipMemsetAsync(d_cur, 0, 32, ctx->stream));
+            uint64_t attempted = m;
+            if (count_attempted) { attempted = 0; for (uint32_t i = 0; i < m; ++i) attempted += pairs[p0 + i].max_ed >= 0 ? 1 : 0; }
+            int rc = sp_launch_affine_map(ctx, A, B, d_pairs + p0, m, *opts, band, d_aln + p0, d_nc + p0, d_off + p0, d_ops, ops_cap, d_cur, prof[0], nullptr, nullptr, attempted);
             if (rc != SP_OK) return rc;
+            if (retry_band) {
+                // the second try: the list, in pair order, then the map on retry_band over it -- its length read from device memory, its results in place, its ops behind the first launch's
+                hipLaunchKernelGGL(ap_retry_list_kernel, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, d_pairs + p0, d_aln + p0, d_nc + p0, m, d_retry, d_n_retry, d_band + p0);
+                hipLaunchKernelGGL(ap_retry_sort_kernel, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, d_retry, d_n_retry, d_retry + slice_max);
+                if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": retry list launch failed");
+                rc = sp_launch_affine_map(ctx, A, B, d_pairs + p0, m, *opts, retry_band, d_aln + p0, d_nc + p0, d_off + p0, d_ops, ops_cap, d_cur, prof[1], d_n_retry, d_retry + slice_max, 0);
+                if (rc != SP_OK) return rc;
+            }
             hipLaunchKernelGGL(ap_status_kernel, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, d_aln + p0, d_nc + p0, d_off + p0, m, d_status);
             SP_HIP_CHECK(ctx, hipMemcpyAsync(h_st, d_cur, 16, hipMemcpyDeviceToHost, ctx->stream));
-            if (hipStreamSynchronize(ctx->stream) != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "align_pileup: the map kernel failed");
+            if (hipStreamSynchronize(ctx->stream) != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": the map kernel failed");
             if (h_st[0] <= ops_cap) break;
-            if (attempt == 1) return sp_fail(ctx, SP_ERR_HIP, "align_pileup: the op buffer did not hold a second run");
+            if (attempt == 1) return sp_fail(ctx, SP_ERR_HIP, who + ": the op buffer did not hold a second run");
             ops_cap = h_st[0];
         }
         if (m > 0) {
             const uint32_t* st = (const uint32_t*)(h_st + 1);
-            if (st[0]) return sp_fail(ctx, SP_ERR_HIP, "align_pileup: a walk did not reach the cell its path started in");
-            if (st[1]) return sp_fail(ctx, SP_ERR_CAPACITY, "align_pileup: an alignment of more than 4,096 runs");
+            if (st[0]) return sp_fail(ctx, SP_ERR_HIP, who + ": a walk did not reach the cell its path started in");
+            if (st[1]) return sp_fail(ctx, SP_ERR_CAPACITY, who + ": an alignment of more than 4,096 runs");
         }
         if (n_tiles) {
-            ProfScope ps(ctx, "align_pileup_pile", n_cols);
+            ProfScope ps(ctx, prof[2], n_cols);
             hipLaunchKernelGGL(pileup_rows_kernel, dim3((unsigned)n_tiles), dim3(PU_WAVES * SP_WAVE), PU_LDS_BYTES, ctx->stream, A->view(), B->d_len, d_pairs, d_aln, d_nc, d_off, d_ops,
                                d_order, d_boff, n_slices, s2, (const PuTile*)(d_in + at_tiles), (const uint64_t*)(d_in + at_cols), d_table);
-            if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "align_pileup: pileup launch failed");
+            if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": pileup launch failed");
         }
     }
     if (d_sum) {
-        ProfScope ps(ctx, "align_pileup_summary", n_cols);
+        ProfScope ps(ctx, prof[3], n_cols);
         hipLaunchKernelGGL(support_summary_kernel, dim3(n_t), dim3(AP_SUM_THREADS), 0, ctx->stream, d_table, (const uint64_t*)(d_in + at_cols), B->d_len, d_aln, d_order, d_boff, n_slices,
                            n_members ? (const uint32_t*)(d_in + at_mem) : nullptr, d_sum);
-        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "align_pileup: summary launch failed");
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": summary launch failed");
+    }
+    if (band_used && n) {
+        hipLaunchKernelGGL(ap_band_used_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_aln, d_nc, n, (uint32_t)band, (uint32_t)retry_band, retry_band ? 1 : 0, d_band);
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": band_used launch failed");
     }
     // ---- only what was asked for comes back
+    if (band_used && n) SP_HIP_CHECK(ctx, hipMemcpyAsync(band_used, d_band, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (aln && n) SP_HIP_CHECK(ctx, hipMemcpyAsync(aln, d_aln, (size_t)n * sizeof(sp_affine_aln), hipMemcpyDeviceToHost, ctx->stream));
     if (cols && n_cols) SP_HIP_CHECK(ctx, hipMemcpyAsync(cols, d_table, n_cols * sizeof(sp_pileup_col), hipMemcpyDeviceToHost, ctx->stream));
     if (d_sum) SP_HIP_CHECK(ctx, hipMemcpyAsync(summaries, d_sum, (size_t)n_t * sizeof(sp_support_summary), hipMemcpyDeviceToHost, ctx->stream));
     SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return SP_OK;
+}
+
+int32_t sp_align_pileup_band_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
+                                   const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    static const char* const prof[4] = { "align_pileup_map", "align_pileup_map_retry", "align_pileup_pile", "align_pileup_summary" };
+    return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, "align_pileup", prof, false);
+}
+
+int32_t sp_align_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, const uint64_t* col_offset,
+                              sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members) {
+    return sp_align_pileup_band_batch(ctx, A, B, pairs, n_pairs, opts, 64, 0, col_offset, aln, cols, summaries, n_members, nullptr);
 }
 
 int32_t sp_support_summarize(const sp_pileup_col* cols, uint32_t length, uint32_t n_members, uint32_t n_aligned, sp_support_summary* out) {
@@ -538,7 +611,7 @@ int32_t sp_hla_consensus_support_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32
     std::vector<uint64_t> t_cols((size_t)n_t + 1, 0);
     for (uint32_t t = 0; t < n_t; ++t) t_cols[t + 1] = toff[t + 1];
     std::vector<sp_pileup_col> table(n_cols);
-    std::vector<uint32_t> aligned_of(n_t, 0);
+    std::vector<sp_support_summary> sums(n_t);
     if (n_m) {
         rc = sp_seqset_make_small(ctx, "csup_q", qblob.data(), qoff.data(), n_m, false, &Q);
         if (rc != SP_OK) return rc;
@@ -547,43 +620,22 @@ int32_t sp_hla_consensus_support_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32
         rc = sp_anchor_batch(ctx, &T, &Q, m_target.data(), ident.data(), n_m, diag.data(), votes.data());
         if (rc != SP_OK) return rc;
         const sp_affine_opts ao = { 1, 4, 6, 2, 26, 1, 1 };
-        // the tracebacks run in slices of SLICE pairs with rows of 4,096 ops (the most a traceback of this library has); what they return is kept back to back and
-        // handed to the pileup in rows as long as the longest alignment actually seen, so the host holds SLICE x 16 KB of rows, not members x 16 KB
-        const uint32_t row_cap = 4096, SLICE = 256;
-        std::vector<sp_pair> pairs(n_m); std::vector<sp_affine_aln> aln(n_m); std::vector<uint32_t> n_cg(n_m, 0); std::vector<std::vector<uint32_t>> ops_of(n_m);
-        std::vector<uint32_t> todo;
-        for (uint32_t m = 0; m < n_m; ++m) { pairs[m] = sp_pair{ m, m_target[m], -diag[m], 0 }; aln[m] = sp_affine_aln{ 0, 0, 0, 0, 0, 0 }; if (votes[m] > 0) todo.push_back(m); }
-        std::vector<sp_pair> pp(SLICE); std::vector<sp_affine_aln> got(SLICE); std::vector<uint32_t> nc(SLICE), rows((size_t)SLICE * row_cap);
-        for (int band = 64; band <= 256 && !todo.empty(); band *= 4) {
-            std::vector<uint32_t> again;
-            for (size_t k0 = 0; k0 < todo.size(); k0 += SLICE) {
-                const size_t n = std::min<size_t>(SLICE, todo.size() - k0);
-                for (size_t k = 0; k < n; ++k) pp[k] = pairs[todo[k0 + k]];
-                rc = sp_affine_align_batch(ctx, &Q, &T, pp.data(), n, &ao, band, got.data(), rows.data(), row_cap, nc.data());
-                if (rc != SP_OK) return rc;
-                for (size_t k = 0; k < n; ++k) {
-                    const uint32_t m = todo[k0 + k];
-                    if (got[k].score <= 0 || nc[k] == 0) { again.push_back(m); continue; }
-                    if (nc[k] > row_cap) return sp_fail(ctx, SP_ERR_CAPACITY, "consensus support: an alignment of more than 4,096 runs");
-                    aln[m] = got[k]; n_cg[m] = nc[k]; ops_of[m].assign(rows.data() + k * (size_t)row_cap, rows.data() + k * (size_t)row_cap + nc[k]);
-                    ++aligned_of[m_target[m]];
-                }
-            }
-            todo.swap(again);
-        }
-        const uint32_t stride = std::max<uint32_t>(1, *std::max_element(n_cg.begin(), n_cg.end()));
-        std::vector<uint32_t> cg((size_t)n_m * stride);
-        for (uint32_t m = 0; m < n_m; ++m) { std::copy(ops_of[m].begin(), ops_of[m].end(), cg.begin() + (size_t)m * stride); std::vector<uint32_t>().swap(ops_of[m]); }
-        rc = sp_pileup_batch(ctx, &Q, &T, pairs.data(), n_m, aln.data(), cg.data(), stride, n_cg.data(), t_cols.data(), table.data());
+        // every member is a pair of ONE device-resident pass: 64 diagonals, then 256 for the attempted pairs that came back with score 0 or without ops -- the list of
+        // those is made and read on the device, no op row reaches the host.  A member without a vote stays in the list switched off, so it counts as unaligned.
+        std::vector<sp_pair> pairs(n_m);
+        for (uint32_t m = 0; m < n_m; ++m) pairs[m] = sp_pair{ m, m_target[m], -diag[m], votes[m] > 0 ? 0 : -1 };
+        // (the pileup launch keeps the profile name it has had in this pass: "pileup")
+        static const char* const prof[4] = { "consensus_support_map", "consensus_support_map_retry", "pileup", "consensus_support_summary" };
+        rc = align_pileup_run(ctx, &Q, &T, pairs.data(), n_m, &ao, 64, 256, t_cols.data(), nullptr, table.data(), sums.data(), members_of.data(), nullptr, "consensus support", prof, true);
         if (rc != SP_OK) return rc;
-    }
+    } else for (uint32_t t = 0; t < n_t; ++t) sp_support_summarize(table.data() + t_cols[t], (uint32_t)(t_cols[t + 1] - t_cols[t]), 0, 0, &sums[t]);
     for (uint64_t x = 0; x < 2 * n_units; ++x) {
         const int32_t t = target_of[x];
         if (t < 0) continue;
         const sp_pileup_col* src = table.data() + t_cols[t];
         const uint32_t len = (uint32_t)(t_cols[t + 1] - t_cols[t]);
         std::memcpy(cols + col_offset[x], src, sizeof(sp_pileup_col) * (size_t)len);
-        sp_support_summarize(src, len, members_of[t], aligned_of[t], &summaries[x]);
+        summaries[x] = sums[t];
     }
     return SP_OK;
 }

@@ -237,6 +237,7 @@ SP_PILEUP_TILE = 2048
 SP_PILEUP_WAVES = 4
 SP_ALIGN_PILEUP_SLICE = 4096      # sp_align_pileup_batch: pairs per slice of a batch
 SP_SUPPORT_HIST_BINS = 1024       # bins of the summary kernel's depth histogram
+SP_ALIGN_PILEUP_WIDE_ROWS = 128   # sp_align_pileup_band_batch on 256 diagonals: target rows per checkpoint block of the map kernel
 PILEUP_DTYPE = np.dtype([("depth", np.uint32), ("eq", np.uint32), ("x", np.uint32, (4,)), ("del", np.uint32), ("ins", np.uint32)])       # sp_pileup_col
 SUPPORT_FIELDS = ("n_members", "n_aligned", "n_unaligned", "length", "min_depth", "median_depth", "n_contested", "reserved_")
 SUPPORT_DTYPE = np.dtype([(n, np.uint32) for n in SUPPORT_FIELDS])                                                                      # sp_support_summary
@@ -329,6 +330,7 @@ def lib():
         "sp_hla_realign_cigars": (i32, [vp, vp, vp, vp, u32, vp, u32, vp]),
         "sp_pileup_batch": (i32, [vp, vp, vp, vp, u64, vp, vp, u32, vp, vp, vp]),
         "sp_align_pileup_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), vp, vp, vp, vp, vp]),
+        "sp_align_pileup_band_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, i32, vp, vp, vp, vp, vp, vp]),
         "sp_support_summarize": (i32, [vp, u32, u32, u32, C.POINTER(sp_support_summary)]),
         "sp_support_contested": (i32, [vp, u32, vp, u32, C.POINTER(u32)]),
         "sp_hla_consensus_support": (i32, [vp, vp, u32, vp, vp, vp, C.c_char_p, C.c_char_p, vp, vp, C.POINTER(sp_support_summary), C.POINTER(sp_support_summary)]),
@@ -527,9 +529,11 @@ class Context:
         self.check(lib().sp_pileup_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), _ptr(aln), _ptr(cigar), cigar.shape[1], _ptr(n_cigar), _ptr(off), _ptr(out)))
         return [out[int(off[t]):int(off[t + 1])] for t in range(B.n)]
 
-    def align_pileup(self, A, B, pairs, a=1, aln=True, cols=True, summaries=True, n_members=None, col_offset=None):
+    def align_pileup(self, A, B, pairs, a=1, aln=True, cols=True, summaries=True, n_members=None, col_offset=None, band=64, retry_band=0, band_used=False):
         """sp_align_pileup_batch: pairs as affine_align takes them -> (aln AFFINE_DTYPE[n] or None, [PILEUP_DTYPE array per target of B] or None,
-        [summary dict per target] or None); an output switched off is handed to the library as NULL.  col_offset: None = the one that follows B's lengths"""
+        [summary dict per target] or None); an output switched off is handed to the library as NULL.  col_offset: None = the one that follows B's lengths.
+        band (64 | 256), retry_band (0 | 256 with band 64) or band_used other than the defaults: sp_align_pileup_band_batch; band_used=True adds a fourth item,
+        uint32[n]: 0 for a pair that did not align, else the band its alignment came from"""
         rows = np.zeros(len(pairs), PAIR_DTYPE)
         for i, pr in enumerate(pairs):
             rows[i] = (pr[0], pr[1], pr[2], pr[3] if len(pr) > 3 else 0)
@@ -543,9 +547,15 @@ class Context:
         sm = np.zeros(max(1, B.n), SUPPORT_DTYPE) if summaries else None
         mem = np.ascontiguousarray(n_members, np.uint32) if n_members is not None else None
         op = sp_affine_opts(a, 4, 6, 2, 26, 1, 1)
-        self.check(lib().sp_align_pileup_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), _ptr(off), _ptr(out), _ptr(table), _ptr(sm), _ptr(mem)))
-        return (out, [table[int(off[t]):int(off[t + 1])] for t in range(B.n)] if cols else None,
-                [{n: int(sm[t][n]) for n in SUPPORT_FIELDS[:-1]} for t in range(B.n)] if summaries else None)
+        used = np.zeros(max(1, len(pairs)), np.uint32) if band_used else None
+        if int(band) == 64 and int(retry_band) == 0 and not band_used:
+            self.check(lib().sp_align_pileup_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), _ptr(off), _ptr(out), _ptr(table), _ptr(sm), _ptr(mem)))
+        else:
+            self.check(lib().sp_align_pileup_band_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), int(band), int(retry_band), _ptr(off), _ptr(out), _ptr(table),
+                                                        _ptr(sm), _ptr(mem), _ptr(used)))
+        res = (out, [table[int(off[t]):int(off[t + 1])] for t in range(B.n)] if cols else None,
+               [{n: int(sm[t][n]) for n in SUPPORT_FIELDS[:-1]} for t in range(B.n)] if summaries else None)
+        return res + (used[:len(pairs)],) if band_used else res
 
     def hla_config_extend(self, reference, alleles, db=None, batch_alleles=0):
         """sp_hla_config_extend: HlaConfig::new on the device -- reference = database.Fasta, alleles = database.HlaAlleles, db = database.Database whose hla_config
