@@ -283,6 +283,58 @@ int32_t sp_align_pileup_band_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seq
                                    int32_t band, int32_t retry_band, const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols,
                                    sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used);
 
+/* ------------------------------------------------------------------ insertion alleles: WHAT the reads insert behind a column
+ * sp_pileup_col.ins says how many alignments have an 'I' run behind a column; this list says which bases those runs hold -- what a person reads off the purple marker
+ * in IGV.  One record per distinct (target, column, inserted string).  Every 'I' run of an alignment belongs to the column in front of it, the column whose `ins` it
+ * counts in; its bases are the query's at the run's query position.
+ * Identity of an inserted string is the key (len, p0, p1, h): p0 / p1 hold its first 64 bases as 2-bit codes (A C G T = 0 1 2 3), base i in bits [2 i, 2 i + 1] of p0
+ * for i < 32 and in bits [2 (i - 32), 2 (i - 32) + 1] of p1 for 32 <= i < 64, zero padded; h is the 64-bit FNV-1a (offset basis 0xcbf29ce484222325, prime
+ * 0x100000001b3) over the 2-bit codes of all len bases, one code per step.  Up to 64 bases the key is the string; beyond, the key is the definition of "the same
+ * insertion" (two longer strings with one key are one record).  A run that holds a base outside ACGT (the query set's N plane) is not listed: it counts in n_other.
+ *   col         the column in the caller's col_offset space (col_offset[t] + j for column j of target t)
+ *   count       alignments that carry the string behind the column
+ *   first_pair  the lowest pair index among them; first_qpos the run's position in that pair's query -- where a caller fetches a string of more than 64 bases
+ *   n_other     on the first record of a column: the column's runs that are not listed (a base outside ACGT), 0 on the others.  A column whose runs are all of that
+ *               kind has one record with len = 0, count = 0 (p0 = p1 = h = first_pair = first_qpos = 0)
+ * so count + n_other summed over a column's records is the column's sp_pileup_col.ins.  Order: col ascending, then count descending, len ascending, (p0, p1, h)
+ * ascending (a record with len 0 has no neighbour in its column).  The list does not depend on the order of the pairs or on launch geometry.
+ * Kernels: one wave per alignment lists its runs (key, pair, query position) into a pooled buffer; the runs are binned by (target, tile of
+ * SP_PILEUP_TILE columns); one workgroup per tile sorts its runs on the whole key (a bitonic network in LDS; a tile with more than SP_PILEUP_INS_LDS_RUNS runs sorts in
+ * its slice of the pooled buffer instead, same code, same result), run-length compacts them, sorts the records into the order above and writes them to its slice of a
+ * pooled output; a last pass packs the slices.  Atomics: the sums (run cursor, runs per tile) do not depend on their order; the PLACES a run takes in the run buffer
+ * and in its tile's slice do -- the list does not, because the sort that follows is on a total order ((pair, qpos) is unique, and the runs with a base outside ACGT
+ * are made identical), so every arrival order sorts to the same sequence.
+ * Pooled buffers only; the run buffer is guessed at four runs per pair plus one per 64 query bases, and a batch with more makes the WHOLE pass run once more on a
+ * buffer that holds them (a warm context does not).
+ * sp_pileup_ins_batch: the list over host op rows -- arguments and checks of sp_pileup_batch.  sp_align_pileup_ins_batch: sp_align_pileup_band_batch that also lists
+ * the insertions of the alignments it piles up; ins == NULL is that call, nothing else is launched and no further pool memory is taken.
+ * ins holds ins_cap records; *n_ins = the number there are; SP_ERR_CAPACITY when n_ins > ins_cap (every other output is complete, ins is not written: call again with
+ * more room).  n_ins must be given with ins. */
+#define SP_PILEUP_INS_LDS_RUNS 1024
+typedef struct {
+    uint64_t col;
+    uint32_t len, count;
+    uint64_t p0, p1, h;
+    uint32_t first_pair, first_qpos;
+    uint32_t n_other, reserved_;
+} sp_pileup_ins;   /* 56 bytes */
+int32_t sp_pileup_ins_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
+                            const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset,
+                            sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins);
+int32_t sp_align_pileup_ins_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts,
+                                  int32_t band, int32_t retry_band, const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols,
+                                  sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
+                                  sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins);
+/* The ASCII of a record (host only).  Up to 64 bases it comes from the key; a longer string is read from sequence `query` of `queries` at rec->first_qpos -- the query
+ * of pair rec->first_pair of the call that made the record (pairs[first_pair].a); both may be NULL / 0 for a record of up to 64 bases, SP_ERR_INVALID_ARG for a longer one
+ * without them or with a position outside the sequence.  out / cap / needed as sp_cyp_alleles_json (NUL-terminated; *needed = len + 1; SP_ERR_CAPACITY).
+ * NOT directly on the records of the HLA / CYP2D6 support calls when len > 64: there first_pair names a read (or a mapping record) and first_qpos is a position in the
+ * member's SEGMENT, which the caller's read set does not hold as a sequence.  CYP2D6: the string is read r = mappings[first_pair].read at
+ * [mappings[first_pair].read_start + first_qpos, + len).  HLA, forward gene: read first_pair at [seg_start + first_qpos, + len); reverse gene: the reverse complement
+ * of read first_pair at [seg_end - first_qpos - len, seg_end - first_qpos).  (Up to 64 bases the key is the string and none of this is needed; the support calls
+ * align on 64 diagonals, where a run of more than 64 bases does not fit -- only the HLA pass's second try on 256 can list one.) */
+int32_t sp_support_ins_string(const sp_pileup_ins* rec, const sp_seqset* queries, uint32_t query, char* out, uint64_t cap, uint64_t* needed);
+
 /* ------------------------------------------------------------------ HLA database
  * Replaces HlaRealigner::new + create_hla_fasta (src/hla/realigner.rs:42-91,497-526) and the per-call
  * one-sequence indexes of score_read (src/hla/caller.rs:1370-1379).
@@ -709,6 +761,20 @@ int32_t sp_cyp_consensus_support_cohort(sp_ctx* ctx, uint32_t n_samples, const s
                                         sp_support_summary* summaries);
 int32_t sp_cyp_support_json(const sp_cyp_call* call, const char* consensus, uint32_t cons_cap, const uint64_t* col_offset, const sp_pileup_col* cols,
                             const sp_support_summary* summaries, char* out, uint64_t cap, uint64_t* needed);
+/* The same calls with the insertion list of sp_align_pileup_ins_batch (ins / ins_cap / n_ins as there; ins == NULL is the call above: nothing else is launched).  Same
+ * members, band and rule.  col is in the call's col_offset space; first_pair is the index of the member's record in `mappings`, first_qpos the run's position in the
+ * member's segment (read position - read_start).  sp_cyp_support_json_ins: every contested entry with 2 * ins > depth gains "insertions" (and "other", "more") as
+ * sp_consensus_support_json_ins writes them; read_names (optional): the QNAME of read r of the sample at read_names[r], n_read_names entries; ins == NULL or
+ * n_ins == 0: the bytes of sp_cyp_support_json. */
+int32_t sp_cyp_consensus_support_ins(sp_ctx* ctx, const sp_seqset* reads, const sp_cyp_call* call, const char* consensus, uint32_t cons_cap,
+                                     const sp_cyp_read_mapping* mappings, uint64_t n_mappings, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                                     sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins);
+int32_t sp_cyp_consensus_support_cohort_ins(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
+                                            const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                                            sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins);
+int32_t sp_cyp_support_json_ins(const sp_cyp_call* call, const char* consensus, uint32_t cons_cap, const uint64_t* col_offset, const sp_pileup_col* cols,
+                                const sp_support_summary* summaries, const sp_pileup_ins* ins, uint64_t n_ins, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
+                                const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed);
 
 /* ------------------------------------------------------------------ CYP2D6 templates and typing tables
  * Replaces generate_cyp_hybrids (src/cyp2d6/definitions.rs:346-464), LoadedVariants::load_variant_database
@@ -1033,6 +1099,26 @@ typedef struct {
     const sp_support_summary* summary[2];
 } sp_support_entry;
 int32_t sp_consensus_support_json(const sp_support_entry* entries, uint32_t n_entries, char* out, uint64_t cap, uint64_t* needed);
+/* The support calls with the insertion list of sp_align_pileup_ins_batch (ins / ins_cap / n_ins as there; ins == NULL is the call without: nothing else is launched).
+ * Same members, bands and retry rule.  col: sp_hla_consensus_support_ins numbers consensus 1's columns from 0 and consensus 2's from strlen(cons1) (only the
+ * consensuses whose outputs are given take part); the cohort form uses its col_offset.  Strings and positions are on the gene strand, as the columns are.  first_pair
+ * is the index of the member READ in `reads`, first_qpos the run's position in the member's gene-strand segment.
+ * sp_consensus_support_json_ins: sp_consensus_support_json with a list.  col_base: 2 per entry, the col of column 0 of consensus c of entry e at col_base[2 e + c]
+ * (not read, and may be NULL, when there are no entries: the text is {} whatever the list holds -- a list may be a whole batch group's).
+ * Every contested entry with 2 * ins > depth gains
+ *     "insertions": [{"seq": "...", "count": n}, ...], "other": n_other
+ * -- the column's records with len > 0 in record order, at most 8 ("more": the number left out, only when there are any); a string of more than 64 bases is written
+ * as its first 64 with "len": L behind count; "first_read": the QNAME, behind those, when read_names (n_read_names entries, indexed by first_pair) is given; "other" only
+ * when n_other > 0.  ins == NULL or n_ins == 0: the bytes of sp_consensus_support_json. */
+int32_t sp_hla_consensus_support_ins(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1,
+                                     const char* cons1, const char* cons2, sp_pileup_col* cols1, sp_pileup_col* cols2, sp_support_summary* s1, sp_support_summary* s2,
+                                     sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins);
+int32_t sp_hla_consensus_support_cohort_ins(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
+                                            const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1, const char* cons, uint32_t cap,
+                                            const uint8_t* unit_on, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries,
+                                            sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins);
+int32_t sp_consensus_support_json_ins(const sp_support_entry* entries, uint32_t n_entries, const uint64_t* col_base, const sp_pileup_ins* ins, uint64_t n_ins,
+                                      const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed);
 
 /* ------------------------------------------------------------------ host-side decisions of the path (no device work)
  * Small scalar routines the reference evaluates between the kernels; kept behind the same ABI so a host can drop the whole
@@ -1435,6 +1521,12 @@ int32_t sp_starphase_set_consensus_support(sp_starphase* handle, int32_t on);
  * failure of the pass fails the sample's CYP2D6 entry (out of memory; an alignment of more than 4,096 runs, SP_ERR_CAPACITY); in a batch the group's samples then go
  * through the pass one by one and only those whose own pass fails are failed. */
 int32_t sp_starphase_set_cyp_consensus_support(sp_starphase* handle, int32_t on);
+/* A switch of its own, off by default, with effect only where one of the two switches above writes its file: the support pass of that file also makes the insertion
+ * list (sp_hla_consensus_support_cohort_ins / sp_cyp_consensus_support_cohort_ins: the same one pass per batch group) and the file is rendered with it
+ * (sp_consensus_support_json_ins / sp_cyp_support_json_ins, without first_read): every contested column with 2 * ins > depth gains "insertions" (and "more", "other").
+ * Off: no further launch, no further pool memory, every output the same bytes as on a handle that was never told; on: every output but those two files the same bytes,
+ * and a sample's file in a batch equals its single call's file. */
+int32_t sp_starphase_set_support_insertions(sp_starphase* handle, int32_t on);
 const char* sp_starphase_warnings(const sp_starphase* handle);      /* the warnings of the last call, one per line */
 /* where the last call spent its time (wall ms): whole call, BAM decode (host, both loci), variant genes, HLA lane, CYP2D6 lane */
 typedef struct { double call_ms, bam_decode_ms, variant_ms, hla_ms, cyp_ms; uint32_t n_hla_reads, n_cyp_reads; } sp_starphase_timing;

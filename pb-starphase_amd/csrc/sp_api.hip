@@ -184,6 +184,7 @@ int32_t sp_struct_size(const char* name) {
     SP_SZ(sp_pileup_col)
     SP_SZ(sp_support_summary)
     SP_SZ(sp_support_entry)
+    SP_SZ(sp_pileup_ins)
 #undef SP_SZ
     return -1;
 }

@@ -2328,7 +2328,15 @@ extern "C" int32_t sp_cyp_alleles_json(const sp_cyp_problem* pr, const sp_cyp_ca
 extern "C" int32_t sp_cyp_consensus_support_cohort(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
                                                    const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
                                                    sp_support_summary* summaries) {
+    return sp_cyp_consensus_support_cohort_ins(ctx, n_samples, reads, calls, consensus, cons_cap, mappings, mapping_off, col_offset, cols, cols_cap, summaries, nullptr, 0, nullptr);
+}
+
+extern "C" int32_t sp_cyp_consensus_support_cohort_ins(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
+                                                       const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                                                       sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
     if (!ctx) return SP_ERR_INVALID_ARG;
+    if (ins && !n_ins) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: null argument");
+    if (ins) *n_ins = 0;
     if (!reads || !calls || !mapping_off || !col_offset || !summaries || n_samples == 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: null argument");
     const uint64_t n_slots = (uint64_t)n_samples * SP_CYP_MAXCONS;
     // ---- the targets: every non-empty consensus of a call that succeeded, as the call returned it
@@ -2355,6 +2363,7 @@ extern "C" int32_t sp_cyp_consensus_support_cohort(sp_ctx* ctx, uint32_t n_sampl
     if (n_t == 0) return SP_OK;
     // ---- the members: one per mapping record whose consensus is a target
     std::vector<uint32_t> m_target, members_of(n_t, 0);
+    std::vector<uint64_t> m_record;                                      // the member's record in `mappings`
     std::string qblob; std::vector<uint64_t> qoff(1, 0);
     for (uint32_t i = 0; i < n_samples; ++i) {
         if (calls[i].status != 0 || mapping_off[i + 1] == mapping_off[i]) continue;
@@ -2372,7 +2381,7 @@ extern "C" int32_t sp_cyp_consensus_support_cohort(sp_ctx* ctx, uint32_t n_sampl
                 if ((int32_t)it->second.size() != reads[i]->h_len[q.read]) return sp_fail(ctx, SP_ERR_HIP, "cyp consensus support: fetching the reads failed");
             }
             qblob.append(it->second, (size_t)q.read_start, (size_t)(q.read_end - q.read_start));
-            qoff.push_back(qblob.size()); m_target.push_back((uint32_t)t); ++members_of[t];
+            qoff.push_back(qblob.size()); m_target.push_back((uint32_t)t); m_record.push_back(k); ++members_of[t];
         }
     }
     const uint32_t n_m = (uint32_t)m_target.size();
@@ -2393,13 +2402,25 @@ extern "C" int32_t sp_cyp_consensus_support_cohort(sp_ctx* ctx, uint32_t n_sampl
     std::vector<uint64_t> t_cols(toff);
     std::vector<sp_pileup_col> table(cols ? n_cols : 0);
     std::vector<sp_support_summary> sm(n_t);
-    rc = sp_align_pileup_batch(ctx, &Q, &T, pairs.data(), n_m, &ao, t_cols.data(), nullptr, cols ? table.data() : nullptr, sm.data(), members_of.data());
-    if (rc != SP_OK) return rc;
+    if (ins) rc = sp_align_pileup_ins_batch(ctx, &Q, &T, pairs.data(), n_m, &ao, 64, 0, t_cols.data(), nullptr, cols ? table.data() : nullptr, sm.data(), members_of.data(), nullptr, ins, ins_cap, n_ins);
+    else rc = sp_align_pileup_batch(ctx, &Q, &T, pairs.data(), n_m, &ao, t_cols.data(), nullptr, cols ? table.data() : nullptr, sm.data(), members_of.data());
+    if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ins && *n_ins > ins_cap)) return rc;
     for (uint64_t x = 0; x < n_slots; ++x) {
         const int32_t t = target_of[x];
         if (t < 0) continue;
         summaries[x] = sm[t];
         if (cols) std::memcpy(cols + col_offset[x], table.data() + t_cols[t], sizeof(sp_pileup_col) * (size_t)(t_cols[t + 1] - t_cols[t]));
+    }
+    if (rc != SP_OK) return rc;                                          // (the list did not fit: everything else is complete)
+    if (ins && *n_ins) {
+        // the list in the caller's terms: the targets are the consensuses that have columns, in col_offset's order, so the records stay in order
+        std::vector<uint64_t> base(n_t, 0);
+        for (uint64_t x = 0; x < n_slots; ++x) if (target_of[x] >= 0) base[target_of[x]] = col_offset[x];
+        for (uint64_t k = 0; k < *n_ins; ++k) {
+            const uint32_t t = (uint32_t)(std::upper_bound(t_cols.begin(), t_cols.end(), ins[k].col) - t_cols.begin()) - 1;
+            ins[k].col = base[t] + (ins[k].col - t_cols[t]);
+            if (ins[k].len) ins[k].first_pair = (uint32_t)m_record[ins[k].first_pair];
+        }
     }
     return SP_OK;
 }
@@ -2407,21 +2428,33 @@ extern "C" int32_t sp_cyp_consensus_support_cohort(sp_ctx* ctx, uint32_t n_sampl
 extern "C" int32_t sp_cyp_consensus_support(sp_ctx* ctx, const sp_seqset* reads, const sp_cyp_call* call, const char* consensus, uint32_t cons_cap,
                                             const sp_cyp_read_mapping* mappings, uint64_t n_mappings, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
                                             sp_support_summary* summaries) {
+    return sp_cyp_consensus_support_ins(ctx, reads, call, consensus, cons_cap, mappings, n_mappings, col_offset, cols, cols_cap, summaries, nullptr, 0, nullptr);
+}
+
+extern "C" int32_t sp_cyp_consensus_support_ins(sp_ctx* ctx, const sp_seqset* reads, const sp_cyp_call* call, const char* consensus, uint32_t cons_cap,
+                                                const sp_cyp_read_mapping* mappings, uint64_t n_mappings, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                                                sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
     if (!ctx) return SP_ERR_INVALID_ARG;
     if (!call || !col_offset || !summaries) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: null argument");
     const int32_t H = std::min<int32_t>(std::max<int32_t>(call->n_consensus, 0), SP_CYP_MAXCONS);
     uint64_t off[SP_CYP_MAXCONS + 1] = { 0 }; sp_support_summary sm[SP_CYP_MAXCONS];
     const uint64_t moff[2] = { 0, n_mappings };
-    const int32_t rc = sp_cyp_consensus_support_cohort(ctx, 1, &reads, call, consensus, cons_cap, mappings, moff, off, cols, cols_cap, sm);
+    const int32_t rc = sp_cyp_consensus_support_cohort_ins(ctx, 1, &reads, call, consensus, cons_cap, mappings, moff, off, cols, cols_cap, sm, ins, ins_cap, n_ins);
     std::memcpy(col_offset, off, sizeof(uint64_t) * ((size_t)H + 1));
-    if (rc != SP_OK) return rc;
+    if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ins && n_ins && *n_ins > ins_cap)) return rc;
     std::memcpy(summaries, sm, sizeof(sp_support_summary) * (size_t)H);
-    return SP_OK;
+    return rc;
 }
 
 extern "C" int32_t sp_cyp_support_json(const sp_cyp_call* call, const char* consensus, uint32_t cons_cap, const uint64_t* col_offset, const sp_pileup_col* cols,
                                        const sp_support_summary* summaries, char* out, uint64_t cap, uint64_t* needed) {
-    if (!call || (cap && !out)) return SP_ERR_INVALID_ARG;
+    return sp_cyp_support_json_ins(call, consensus, cons_cap, col_offset, cols, summaries, nullptr, 0, nullptr, 0, nullptr, 0, out, cap, needed);
+}
+
+extern "C" int32_t sp_cyp_support_json_ins(const sp_cyp_call* call, const char* consensus, uint32_t cons_cap, const uint64_t* col_offset, const sp_pileup_col* cols,
+                                           const sp_support_summary* summaries, const sp_pileup_ins* ins, uint64_t n_ins, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
+                                           const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed) {
+    if (!call || (cap && !out) || (n_ins && !ins)) return SP_ERR_INVALID_ARG;
     const int32_t H = call->status == 0 ? std::min<int32_t>(std::max<int32_t>(call->n_consensus, 0), SP_CYP_MAXCONS) : 0;
     if (H > 0 && (!consensus || cons_cap == 0 || !col_offset || !summaries)) return SP_ERR_INVALID_ARG;
     spj::Value root = spj::object();
@@ -2446,6 +2479,7 @@ extern "C" int32_t sp_cyp_support_json(const sp_cyp_call* call, const char* cons
             k.obj.emplace_back("x", std::move(x));
             k.obj.emplace_back("del", spj::unum(c[j].del)); k.obj.emplace_back("ins", spj::unum(c[j].ins));
             k.obj.emplace_back("consensus_base", spj::str(std::string(1, s[j])));
+            if (n_ins && 2ull * c[j].ins > c[j].depth) spi_support_ins_json(&k, ins, n_ins, col_offset[h] + j, mappings, n_mappings, mappings ? read_names : nullptr, n_read_names);
             list.arr.push_back(std::move(k));
         }
         v.obj.emplace_back("contested", std::move(list));

@@ -118,6 +118,7 @@ struct sp_starphase {
     std::string include_set, exclude_set, sample_name, sv_vcf, debug_folder;
     int32_t read_debug = 0;                          // sp_starphase_set_read_debug: a debug folder also receives read_debug.json
     int32_t consensus_support = 0;                   // sp_starphase_set_consensus_support: a debug folder also receives consensus_support.json
+    int32_t support_insertions = 0;                  // sp_starphase_set_support_insertions: those two files also list the inserted strings of their contested columns
     int32_t cyp_consensus_support = 0;               // sp_starphase_set_cyp_consensus_support: a debug folder also receives cyp2d6_consensus_support.json
     int32_t hla_debug_mappings = 0;                  // sp_starphase_set_hla_debug_mappings: hla_debug.json carries the mapping of each consensus against every allowed allele
     std::set<std::string> include, exclude; bool has_include = false, has_exclude = false;
@@ -575,10 +576,20 @@ int32_t hla_debug_mappings_add(sp_starphase* h, sp_hla_debug* dbg, const std::st
 
 // consensus_support.json of one sample (sp_starphase_set_consensus_support): the tables of the group's one support pass that belong to this sample.  off / sm are
 // indexed by gene * 2 + consensus; cons holds the sample's hg38-forward consensuses, cap bytes each.  A sample without reads has no view and writes an empty object.
-struct SupportView { const uint64_t* off; const sp_pileup_col* cols; const sp_support_summary* sm; const char* cons; uint32_t cap; };
+struct SupportView { const uint64_t* off; const sp_pileup_col* cols; const sp_support_summary* sm; const char* cons; uint32_t cap; const sp_pileup_ins* ins; uint64_t n_ins; };
+// a support call that also makes its insertion list: `call(ins, cap, &n)` with room for a guess, once more with the room it asked for
+template <class F> int32_t support_with_ins(std::vector<sp_pileup_ins>& ins, F call) {
+    if (ins.size() < 16384) ins.resize(16384);                       // (0.9 MB; a list that is longer costs the pass a second run)
+    uint64_t n = 0;
+    int32_t rc = call(ins.data(), (uint64_t)ins.size(), &n);
+    if (rc == SP_ERR_CAPACITY && n > ins.size()) { ins.resize((size_t)n); rc = call(ins.data(), (uint64_t)ins.size(), &n); }
+    ins.resize(rc == SP_OK ? (size_t)n : 0);
+    return rc;
+}
 int32_t consensus_support_save(sp_starphase* h, const sp_hla_call* calls, const SupportView* view, const std::string& debug_folder, std::string& err) {
     const size_t G = h->hgenes.size();
     std::vector<sp_support_entry> entries; std::vector<std::string> keep; keep.reserve(G * 4);
+    std::vector<uint64_t> col_base;                                  // of each entry's two consensuses, in the support pass's column space (the list's)
     for (size_t g = 0; view && g < G; ++g) {
         if (calls[g].status == 1) continue;
         sp_support_entry en; std::memset(&en, 0, sizeof en);
@@ -599,12 +610,16 @@ int32_t consensus_support_save(sp_starphase* h, const sp_hla_call* calls, const 
             en.cols[k] = view->cols + lo; en.summary[k] = view->sm + g * 2 + k;
         }
         entries.push_back(en);
+        col_base.push_back(view->off[g * 2]); col_base.push_back(view->off[g * 2 + 1]);
     }
+    // (the list is the whole group's: a sample none of whose genes has a call has no entry, no column of the list is its own, and its file is the empty object)
+    const bool listed = view && view->ins && !entries.empty();
+    const sp_pileup_ins* ins = listed ? view->ins : nullptr; const uint64_t n_ins = listed ? view->n_ins : 0;
     uint64_t need = 0;
-    int32_t rc = sp_consensus_support_json(entries.data(), (uint32_t)entries.size(), nullptr, 0, &need);
+    int32_t rc = sp_consensus_support_json_ins(entries.data(), (uint32_t)entries.size(), col_base.data(), ins, n_ins, nullptr, 0, nullptr, 0, &need);
     if (rc != SP_OK && rc != SP_ERR_CAPACITY) { err = "consensus_support.json: the tables do not fit their consensuses"; return rc; }
     std::string text((size_t)need, '\0');
-    rc = sp_consensus_support_json(entries.data(), (uint32_t)entries.size(), &text[0], need, &need);
+    rc = sp_consensus_support_json_ins(entries.data(), (uint32_t)entries.size(), col_base.data(), ins, n_ins, nullptr, 0, &text[0], need, &need);
     if (rc != SP_OK) { err = "consensus_support.json: the tables do not fit their consensuses"; return rc; }
     const std::string path = debug_folder + "/consensus_support.json";
     FILE* f = std::fopen(path.c_str(), "wb");
@@ -735,11 +750,11 @@ void cyp_package(sp_starphase* h, const sp_cyp_problem& pr, const sp_cyp_call& c
 // cyp2d6_consensus_support.json of one sample (sp_starphase_set_cyp_consensus_support): the tables of the group's one support pass that belong to this sample
 // (off: MAXCONS + 1 offsets into cols, sm: MAXCONS summaries, cons: the sample's consensus block).  A failure fails the sample's CYP2D6 entry.
 void cyp_support_save(const sp_cyp_call& call, const char* cons, uint32_t cons_cap, const uint64_t* off, const sp_pileup_col* cols, const sp_support_summary* sm,
-                      const std::string& debug_folder, CypLane* L) {
+                      const std::vector<sp_pileup_ins>& ins, const std::string& debug_folder, CypLane* L) {
     uint64_t need = 0;
-    int32_t rc = sp_cyp_support_json(&call, cons, cons_cap, off, cols, sm, nullptr, 0, &need);
+    int32_t rc = sp_cyp_support_json_ins(&call, cons, cons_cap, off, cols, sm, ins.data(), ins.size(), nullptr, 0, nullptr, 0, nullptr, 0, &need);
     std::string text((size_t)need, '\0');
-    if (rc == SP_OK || rc == SP_ERR_CAPACITY) rc = sp_cyp_support_json(&call, cons, cons_cap, off, cols, sm, &text[0], need, &need);
+    if (rc == SP_OK || rc == SP_ERR_CAPACITY) rc = sp_cyp_support_json_ins(&call, cons, cons_cap, off, cols, sm, ins.data(), ins.size(), nullptr, 0, nullptr, 0, &text[0], need, &need);
     if (rc != SP_OK) { L->rc = rc; L->err = "cyp2d6_consensus_support.json: the tables do not fit their consensuses"; return; }
     const std::string path = debug_folder + "/cyp2d6_consensus_support.json";
     FILE* f = std::fopen(path.c_str(), "wb");
@@ -859,15 +874,22 @@ void cyp_group(sp_starphase* h, std::vector<Sample*> group, bool only_ok, double
             }
             if (!on.empty()) {
                 std::vector<uint64_t> off((size_t)n * SP_CYP_MAXCONS + 1, 0); std::vector<sp_pileup_col> cols((size_t)n_cols + 1); std::vector<sp_support_summary> sm((size_t)n * SP_CYP_MAXCONS);
-                int32_t rc = sp_cyp_consensus_support_cohort(h->ctx2, n, sets.data(), sc.data(), cons.data(), cons_cap, flat.data(), moff.data(), off.data(), cols.data(), n_cols, sm.data());
+                std::vector<sp_pileup_ins> ins;                      // (stays empty without sp_starphase_set_support_insertions: the renderer then writes the file as before)
+                int32_t rc = !h->support_insertions
+                    ? sp_cyp_consensus_support_cohort(h->ctx2, n, sets.data(), sc.data(), cons.data(), cons_cap, flat.data(), moff.data(), off.data(), cols.data(), n_cols, sm.data())
+                    : support_with_ins(ins, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got) {
+                          return sp_cyp_consensus_support_cohort_ins(h->ctx2, n, sets.data(), sc.data(), cons.data(), cons_cap, flat.data(), moff.data(), off.data(), cols.data(), n_cols, sm.data(), p, room, got); });
                 if (rc == SP_OK) {
-                    for (uint32_t k : on) cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data() + (size_t)k * SP_CYP_MAXCONS, cols.data(), sm.data() + (size_t)k * SP_CYP_MAXCONS, typed[k]->debug, &typed[k]->cyp);
+                    for (uint32_t k : on) cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data() + (size_t)k * SP_CYP_MAXCONS, cols.data(), sm.data() + (size_t)k * SP_CYP_MAXCONS, ins, typed[k]->debug, &typed[k]->cyp);
                 } else for (uint32_t k : on) {
                     // the shared pass failed: sample by sample, and only the samples whose own pass fails are failed (alone in the pass: that failure is its own)
                     CypLane* L = &typed[k]->cyp;
-                    if (on.size() > 1) rc = sp_cyp_consensus_support(h->ctx2, sets[k], &calls[k], cons.data() + cons_block * k, cons_cap, mappings[k].data(), mappings[k].size(), off.data(), cols.data(), n_cols, sm.data());
+                    if (on.size() > 1) rc = !h->support_insertions
+                        ? sp_cyp_consensus_support(h->ctx2, sets[k], &calls[k], cons.data() + cons_block * k, cons_cap, mappings[k].data(), mappings[k].size(), off.data(), cols.data(), n_cols, sm.data())
+                        : support_with_ins(ins, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got) {
+                              return sp_cyp_consensus_support_ins(h->ctx2, sets[k], &calls[k], cons.data() + cons_block * k, cons_cap, mappings[k].data(), mappings[k].size(), off.data(), cols.data(), n_cols, sm.data(), p, room, got); });
                     if (rc != SP_OK) { L->rc = rc; L->err = "sp_cyp_consensus_support: " + opt(sp_last_error(h->ctx2)); continue; }
-                    cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data(), cols.data(), sm.data(), typed[k]->debug, L);
+                    cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data(), cols.data(), sm.data(), ins, typed[k]->debug, L);
                 }
             }
         }
@@ -899,6 +921,7 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
     bool want_support = false;                                       // likewise one support pass (anchor, alignment, pileup) over the group's consensuses
     for (Sample* b : with) want_support |= h->consensus_support && !b->debug.empty();
     std::vector<uint8_t> is1; std::vector<uint64_t> sup_off; std::vector<sp_pileup_col> sup_cols; std::vector<sp_support_summary> sup_sm;
+    std::vector<sp_pileup_ins> sup_ins;                              // (sp_starphase_set_support_insertions; empty otherwise)
     std::vector<int32_t> cohort_of(with.size(), -1);                 // a sample's place among the samples with reads
     if (R) {
         sp_seqset* set = nullptr;
@@ -944,8 +967,13 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
                 }
             }
             sup_off.assign(at.size() * G * 2 + 1, 0); sup_cols.resize((size_t)n_cols + 1); sup_sm.resize(at.size() * G * 2);
-            rc = sp_hla_consensus_support_cohort(h->ctx, h->hla, (uint32_t)at.size(), read_sample.data(), (uint32_t)G, genes.data(), set, rec.data(), is1.data(),
-                                                 h->hla_cons.data(), cap, unit_on.data(), sup_off.data(), sup_cols.data(), n_cols, sup_sm.data());
+            if (!h->support_insertions)
+                rc = sp_hla_consensus_support_cohort(h->ctx, h->hla, (uint32_t)at.size(), read_sample.data(), (uint32_t)G, genes.data(), set, rec.data(), is1.data(),
+                                                     h->hla_cons.data(), cap, unit_on.data(), sup_off.data(), sup_cols.data(), n_cols, sup_sm.data());
+            else
+                rc = support_with_ins(sup_ins, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got) {
+                    return sp_hla_consensus_support_cohort_ins(h->ctx, h->hla, (uint32_t)at.size(), read_sample.data(), (uint32_t)G, genes.data(), set, rec.data(), is1.data(),
+                                                               h->hla_cons.data(), cap, unit_on.data(), sup_off.data(), sup_cols.data(), n_cols, sup_sm.data(), p, room, got); });
             if (rc != SP_OK) { err = "sp_hla_consensus_support: " + opt(sp_last_error(h->ctx)); return rc; }
         }
         // the per-allele mappings of hla_debug.json: every consensus of the samples that have a debug folder, in one batched map
@@ -978,7 +1006,7 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
         std::string e;
         SupportView sv{};
         const bool sup = want_support && cohort_of[k] >= 0 && !sup_off.empty();
-        if (sup) { const size_t x = (size_t)cohort_of[k]; sv = SupportView{ sup_off.data() + x * G * 2, sup_cols.data(), sup_sm.data() + x * G * 2, h->hla_cons.data() + x * G * 2 * (size_t)cap, cap }; }
+        if (sup) { const size_t x = (size_t)cohort_of[k]; sv = SupportView{ sup_off.data() + x * G * 2, sup_cols.data(), sup_sm.data() + x * G * 2, h->hla_cons.data() + x * G * 2 * (size_t)cap, cap, sup_ins.data(), sup_ins.size() }; }
         const int32_t rc = hla_package(h, b->hreads, b->hsearched, orders[k], rec.data() + first[k], rev.data() + first[k], calls.data() + k * G, b->debug, b->hla_entries, e,
                                        want_cigars ? &cigars : nullptr, first[k], maps.map, maps.map ? map_item.data() + k * G * 2 : nullptr, &b->hwarn,
                                        h->consensus_support != 0, sup ? &sv : nullptr);
@@ -1090,6 +1118,11 @@ int32_t sp_starphase_set_consensus_support(sp_starphase* h, int32_t on) {
 int32_t sp_starphase_set_cyp_consensus_support(sp_starphase* h, int32_t on) {
     if (!h) return SP_ERR_INVALID_ARG;
     h->cyp_consensus_support = on ? 1 : 0;
+    return SP_OK;
+}
+int32_t sp_starphase_set_support_insertions(sp_starphase* h, int32_t on) {
+    if (!h) return SP_ERR_INVALID_ARG;
+    h->support_insertions = on ? 1 : 0;
     return SP_OK;
 }
 int32_t sp_starphase_set_read_debug(sp_starphase* h, int32_t enable) {

@@ -239,6 +239,11 @@ int spi_hla_gene_fwd(const sp_hla_db* db, uint32_t gene);
 // sp_hla.hip, for sp_diplotype.hip: sp_hla_map_type_consensus for n consensuses in one batched map; item_of[x] = the consensus that item x of the map is (those that place)
 int32_t spi_hla_map_type_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, const uint32_t* genes, const char* const* consensus_fwd, const uint32_t* consensus_len,
                                int32_t require_dna, int32_t disable_cdna, sp_hla_map** out, std::vector<uint32_t>* item_of);
+// sp_pileup.hip, for the two support renderers: adds "insertions" (and "more", "other") to the object of a contested column from the records of column `col` of a list in
+// record order.  first_read: names[first_pair], or names[mappings[first_pair].read] when mappings is given; left out without names or for an index outside them.
+namespace spj { struct Value; }
+void spi_support_ins_json(spj::Value* column, const sp_pileup_ins* ins, uint64_t n_ins, uint64_t col, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
+                          const char* const* names, uint32_t n_names);
 // sp_cyp.hip, for sp_diplotype.hip: sp_cyp_diplotype_mappings with the list in a vector the library sizes
 int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
                                    sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings);

@@ -231,6 +231,222 @@ __global__ __launch_bounds__(AP_SUM_THREADS) void support_summary_kernel(const u
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// Insertion alleles (sp_pileup_ins; contract: include/starphase_hip.h, design: DESIGN.md section 7.2).  Five small kernels on one stream:
+//   ins_collect   one wave per alignment walks its op row 64 ops at a time (the prefix sums of pu_pair); the lane of an 'I' op makes the run's record -- column, key,
+//                 pair, query position -- and the wave appends its records to the run buffer (one ballot, one atomic on the cursor) and counts them per tile
+//   ins_scan      one workgroup: exclusive sums of the tile counts
+//   ins_scatter   every run to its tile's slice (a place from an atomic: the order inside a slice is whatever it is, the sort below makes it one order)
+//   ins_tile      one workgroup per tile: sort the slice on (col, len, p0, p1, h, pair, qpos) -- a total order, (pair, qpos) is unique --, run-length compact it into
+//                 distinct records (the first run of a record is its lowest pair), sort those into the list's order, fold the runs with a base outside ACGT (len 0)
+//                 into n_other of their column's first record, write the tile's slice of the output
+//   ins_pack      the slices back to back
+// A run is listed behind the column pileup_rows_kernel counts it in (t0 - 1, when that is a column at all); the same pairs are skipped.
+// ------------------------------------------------------------------------------------------------------------------------------
+struct InsRun { uint64_t col, p0, p1, h; uint32_t len, pair, qpos, tile; };           // 48 bytes; len 0: a run with a base outside ACGT (p0 = p1 = h = 0)
+static_assert(sizeof(InsRun) == 48 && sizeof(sp_pileup_ins) == 56, "record sizes");
+constexpr int INS_THREADS = 256, INS_LDS_RUNS = SP_PILEUP_INS_LDS_RUNS;
+constexpr uint64_t INS_FNV_BASIS = 0xcbf29ce484222325ull, INS_FNV_PRIME = 0x100000001b3ull;
+
+__device__ __forceinline__ bool ins_same(const InsRun& a, const InsRun& b) { return a.col == b.col && a.len == b.len && a.p0 == b.p0 && a.p1 == b.p1 && a.h == b.h; }
+__device__ __forceinline__ bool ins_run_less(const InsRun& a, const InsRun& b) {
+    if (a.col != b.col) return a.col < b.col;
+    if (a.len != b.len) return a.len < b.len;
+    if (a.p0 != b.p0) return a.p0 < b.p0;
+    if (a.p1 != b.p1) return a.p1 < b.p1;
+    if (a.h != b.h) return a.h < b.h;
+    if (a.pair != b.pair) return a.pair < b.pair;
+    return a.qpos < b.qpos;
+}
+
+__global__ __launch_bounds__(INS_THREADS) void ins_collect_kernel(SeqSetView A, const int32_t* __restrict__ t_len, const sp_pair* __restrict__ pairs, const sp_affine_aln* __restrict__ aln,
+                                                                  const uint32_t* __restrict__ n_cigar, const uint64_t* __restrict__ op_off, const uint32_t* __restrict__ ops, uint32_t n,
+                                                                  uint32_t pair0, int need_score, const uint64_t* __restrict__ col_offset, const uint32_t* __restrict__ tile_first,
+                                                                  InsRun* __restrict__ runs, uint64_t runs_cap, unsigned long long* __restrict__ n_runs, uint32_t* __restrict__ tile_count) {
+    const uint32_t i = blockIdx.x * (INS_THREADS / SP_WAVE) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & (SP_WAVE - 1);
+    if (i >= n) return;                                                                 // (everything up to the loop is wave-uniform)
+    const uint32_t n_ops = n_cigar[i];
+    const uint64_t off = op_off[i];
+    if (n_ops == 0 || n_ops == AP_LOST || off == AP_NO_OPS) return;
+    const sp_affine_aln g = aln[i];
+    if (need_score && g.score <= 0) return;
+    const sp_pair pr = pairs[i];
+    const uint32_t* qwords = A.words + A.word_off[pr.a];
+    const uint32_t* qn = A.nplane ? A.nplane + A.word_off[pr.a] : nullptr;
+    const uint32_t* row = ops + off;
+    const int tl_max = t_len[pr.b];
+    int tpos = g.b_start, qpos = g.a_start;
+    for (uint32_t k0 = 0; k0 < n_ops; k0 += SP_WAVE) {
+        const bool live = k0 + lane < n_ops;
+        const uint32_t w = live ? row[k0 + lane] : 0u;
+        const uint32_t op = w & 15u; const int len = (int)(w >> 4);
+        const int tl = (op == 7u || op == 8u || op == 2u) ? len : 0, ql = (op == 7u || op == 8u || op == 1u) ? len : 0;
+        int ts = tl, qs = ql;
+#pragma unroll
+        for (int d = 1; d < SP_WAVE; d <<= 1) {
+            const int u = __shfl_up(ts, d), v = __shfl_up(qs, d);
+            if (lane >= d) { ts += u; qs += v; }
+        }
+        const int t0 = tpos + ts - tl, q0 = qpos + qs - ql;
+        tpos += __shfl(ts, SP_WAVE - 1); qpos += __shfl(qs, SP_WAVE - 1);
+        const bool is_ins = live && op == 1u && len > 0 && t0 - 1 >= 0 && t0 - 1 < tl_max;
+        InsRun r;
+        if (is_ins) {
+            r.col = col_offset[pr.b] + (uint64_t)(t0 - 1); r.tile = tile_first[pr.b] + (uint32_t)(t0 - 1) / (uint32_t)PU_TILE;
+            r.pair = pair0 + i; r.qpos = (uint32_t)q0; r.len = (uint32_t)len; r.p0 = 0; r.p1 = 0; r.h = INS_FNV_BASIS;
+            bool other = false;
+            for (int b = 0; b < len; ++b) {
+                const int q = q0 + b;
+                const uint64_t code = pu_query_code(qwords, q);
+                if (qn && ((qn[q >> 4] >> ((q & 15) << 1)) & 3u)) other = true;
+                if (b < 32) r.p0 |= code << (2 * b); else if (b < 64) r.p1 |= code << (2 * (b - 32));
+                r.h = (r.h ^ code) * INS_FNV_PRIME;
+            }
+            if (other) { r.len = 0; r.p0 = 0; r.p1 = 0; r.h = 0; r.qpos = 0; r.pair = 0; }
+        }
+        const unsigned long long vote = __ballot(is_ins);
+        if (vote) {
+            const int leader = __ffsll((long long)vote) - 1;
+            unsigned long long base = 0;
+            if (lane == leader) base = atomicAdd(n_runs, (unsigned long long)__popcll(vote));
+            base = __shfl(base, leader);
+            const unsigned long long at = base + (unsigned long long)__popcll(vote & ((1ull << lane) - 1ull));
+            if (is_ins && at < runs_cap) { runs[at] = r; atomicAdd(&tile_count[r.tile], 1u); }
+        }
+    }
+}
+
+// exclusive sums of cnt[0 .. n) into off[0 .. n], the total into off[n]; zero (optional): n words cleared on the way.  One workgroup.
+__global__ __launch_bounds__(INS_THREADS) void ins_scan_kernel(const uint32_t* __restrict__ cnt, uint32_t n, uint32_t* __restrict__ off, uint32_t* __restrict__ zero) {
+    __shared__ uint32_t part[INS_THREADS];
+    const uint32_t tid = threadIdx.x, per = (n + INS_THREADS - 1) / INS_THREADS, lo = min(n, tid * per), hi = min(n, lo + per);
+    uint32_t s = 0;
+    for (uint32_t j = lo; j < hi; ++j) s += cnt[j];
+    part[tid] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < INS_THREADS; d <<= 1) {
+        const uint32_t v = tid >= d ? part[tid - d] : 0u;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[tid] - s;
+    for (uint32_t j = lo; j < hi; ++j) { off[j] = run; run += cnt[j]; if (zero) zero[j] = 0u; }
+    if (tid == INS_THREADS - 1) off[n] = part[tid];
+}
+
+__global__ void ins_scatter_kernel(const InsRun* __restrict__ runs, uint32_t n, const uint32_t* __restrict__ tile_off, uint32_t* __restrict__ tile_cur, InsRun* __restrict__ binned) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const InsRun r = runs[i];
+    binned[tile_off[r.tile] + atomicAdd(&tile_cur[r.tile], 1u)] = r;
+}
+
+// the workgroup's exclusive prefix of `mine` (part: INS_THREADS words of LDS); *total = the sum
+__device__ __forceinline__ uint32_t ins_block_scan(uint32_t mine, uint32_t* part, uint32_t* total) {
+    const uint32_t tid = threadIdx.x;
+    __syncthreads();
+    part[tid] = mine;
+    __syncthreads();
+    for (uint32_t d = 1; d < INS_THREADS; d <<= 1) {
+        const uint32_t v = tid >= d ? part[tid - d] : 0u;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    *total = part[INS_THREADS - 1];
+    return part[tid] - mine;
+}
+
+// v[0 .. n) into ascending order of `less`, by the whole workgroup.  The bitonic network whose comparators all put the smaller element at the lower index (a merge
+// begins with the mirrored step, then halves): for an n that is no power of two the places from n on stand for elements larger than all others, which such a
+// comparator never moves -- a comparator that reaches past n is left out.
+template <class Less> __device__ __forceinline__ void ins_bitonic(uint32_t* v, uint32_t n, Less less) {
+    uint32_t P = 1;
+    while (P < n) P <<= 1;
+    for (uint32_t k = 2; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t t = threadIdx.x; t < P / 2; t += INS_THREADS) {
+                const uint32_t blk = t / j, at = t % j;
+                const uint32_t lo = (j == k >> 1) ? blk * k + at : blk * 2 * j + at, hi = (j == k >> 1) ? blk * k + k - 1 - at : lo + j;
+                if (hi < n) {
+                    const uint32_t a = v[lo], b = v[hi];
+                    if (less(b, a)) { v[lo] = b; v[hi] = a; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// one tile's runs R[0 .. n) -> its records, in the list's order, to out; returns their number.  idx / didx / dcnt: n words each, where R lives (LDS or the pooled scratch).
+__device__ __forceinline__ uint32_t ins_tile_work(const InsRun* R, uint32_t* idx, uint32_t* didx, uint32_t* dcnt, uint32_t n, uint32_t* part, sp_pileup_ins* __restrict__ out) {
+    const uint32_t tid = threadIdx.x, per = (n + INS_THREADS - 1) / INS_THREADS, lo = min(n, tid * per), hi = min(n, lo + per);
+    for (uint32_t s = tid; s < n; s += INS_THREADS) idx[s] = s;
+    __syncthreads();
+    ins_bitonic(idx, n, [&](uint32_t a, uint32_t b) { return ins_run_less(R[a], R[b]); });
+    // ---- distinct records: didx[d] = the first run of record d (its lowest pair), dcnt[d] = how many runs it has
+    uint32_t heads = 0, m = 0;
+    for (uint32_t s = lo; s < hi; ++s) heads += (s == 0 || !ins_same(R[idx[s]], R[idx[s - 1]])) ? 1u : 0u;
+    uint32_t d = ins_block_scan(heads, part, &m);
+    for (uint32_t s = lo; s < hi; ++s) if (s == 0 || !ins_same(R[idx[s]], R[idx[s - 1]])) didx[d++] = s;
+    __syncthreads();
+    for (uint32_t e = tid; e < m; e += INS_THREADS) dcnt[e] = (e + 1 < m ? didx[e + 1] : n) - didx[e];
+    __syncthreads();
+    for (uint32_t e = tid; e < m; e += INS_THREADS) didx[e] = idx[didx[e]];
+    __syncthreads();
+    // ---- the list's order: col, a column's len-0 record first (it is folded away below), count descending, len, key
+    for (uint32_t e = tid; e < m; e += INS_THREADS) idx[e] = e;
+    __syncthreads();
+    ins_bitonic(idx, m, [&](uint32_t a, uint32_t b) {
+        const InsRun& x = R[didx[a]]; const InsRun& y = R[didx[b]];
+        if (x.col != y.col) return x.col < y.col;
+        if ((x.len == 0) != (y.len == 0)) return x.len == 0;
+        if (dcnt[a] != dcnt[b]) return dcnt[a] > dcnt[b];
+        if (x.len != y.len) return x.len < y.len;
+        if (x.p0 != y.p0) return x.p0 < y.p0;
+        if (x.p1 != y.p1) return x.p1 < y.p1;
+        return x.h < y.h;
+    });
+    // ---- a len-0 record with a neighbour behind it in its column leaves its count in that neighbour's n_other
+    const uint32_t mper = (m + INS_THREADS - 1) / INS_THREADS, mlo = min(m, tid * mper), mhi = min(m, mlo + mper);
+    auto dropped = [&](uint32_t e) { const InsRun& x = R[didx[idx[e]]]; return x.len == 0 && e + 1 < m && R[didx[idx[e + 1]]].col == x.col; };
+    uint32_t kept = 0, total = 0;
+    for (uint32_t e = mlo; e < mhi; ++e) kept += dropped(e) ? 0u : 1u;
+    uint32_t at = ins_block_scan(kept, part, &total);
+    for (uint32_t e = mlo; e < mhi; ++e) {
+        if (dropped(e)) continue;
+        const InsRun& x = R[didx[idx[e]]];
+        sp_pileup_ins o;
+        o.col = x.col; o.len = x.len; o.count = x.len ? dcnt[idx[e]] : 0u; o.p0 = x.p0; o.p1 = x.p1; o.h = x.h; o.first_pair = x.pair; o.first_qpos = x.qpos; o.reserved_ = 0;
+        o.n_other = x.len == 0 ? dcnt[idx[e]] : (e > 0 && R[didx[idx[e - 1]]].len == 0 && R[didx[idx[e - 1]]].col == x.col) ? dcnt[idx[e - 1]] : 0u;
+        out[at++] = o;
+    }
+    return total;
+}
+
+__global__ __launch_bounds__(INS_THREADS) void ins_tile_kernel(InsRun* __restrict__ binned, const uint32_t* __restrict__ tile_off, uint32_t* __restrict__ scratch, uint64_t scratch_stride,
+                                                               sp_pileup_ins* __restrict__ tmp, uint32_t* __restrict__ n_dist) {
+    __shared__ InsRun s_runs[INS_LDS_RUNS];
+    __shared__ uint32_t s_idx[INS_LDS_RUNS], s_didx[INS_LDS_RUNS], s_dcnt[INS_LDS_RUNS], part[INS_THREADS];
+    const uint32_t tile = blockIdx.x, b0 = tile_off[tile], n = tile_off[tile + 1] - b0;
+    uint32_t m = 0;
+    if (n == 0) { /* (uniform over the workgroup) */ }
+    else if (n <= (uint32_t)INS_LDS_RUNS) {
+        for (uint32_t s = threadIdx.x; s < n; s += INS_THREADS) s_runs[s] = binned[b0 + s];
+        __syncthreads();
+        m = ins_tile_work(s_runs, s_idx, s_didx, s_dcnt, n, part, tmp + b0);
+    } else
+        m = ins_tile_work(binned + b0, scratch + b0, scratch + scratch_stride + b0, scratch + 2 * scratch_stride + b0, n, part, tmp + b0);
+    if (threadIdx.x == 0) n_dist[tile] = m;
+}
+
+__global__ void ins_pack_kernel(const sp_pileup_ins* __restrict__ tmp, const uint32_t* __restrict__ tile_off, const uint32_t* __restrict__ n_dist, const uint32_t* __restrict__ out_off,
+                                sp_pileup_ins* __restrict__ out) {
+    const uint32_t tile = blockIdx.x, n = n_dist[tile];
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) out[out_off[tile] + i] = tmp[tile_off[tile] + i];
+}
+
 static bool contested_col(const sp_pileup_col& c) { return (c.depth > 0 && 2ull * c.eq <= c.depth) || 2ull * c.ins > c.depth; }
 
 static std::string revcomp_str(const char* s, size_t n) {
@@ -243,24 +459,89 @@ static std::string revcomp_str(const char* s, size_t n) {
     return r;
 }
 
-} // namespace
+// ---- the host side of the insertion list: pooled buffers sized by the run buffer's capacity (a warm context allocates nothing), the launches, the way out
+struct InsPass {
+    uint64_t cap = 0; uint32_t n_tiles = 0, n_t = 0;
+    InsRun* d_runs = nullptr; InsRun* d_binned = nullptr; sp_pileup_ins* d_tmp = nullptr; uint32_t* d_scratch = nullptr;
+    unsigned long long* d_n = nullptr; uint32_t *d_cnt = nullptr, *d_off = nullptr, *d_cur = nullptr, *d_ooff = nullptr, *d_tfirst = nullptr;
+    uint64_t* h_st = nullptr;
+};
 
-extern "C" {
+// min_cap: the runs the caller knows of (0: a guess from the number of pairs; the pass is run again when it was too small)
+static int32_t ins_begin(sp_ctx* ctx, const std::string& who, const sp_seqset* B, uint64_t n_pairs, uint64_t min_cap, InsPass* ip) {
+    ip->n_t = B->n;
+    uint64_t n_tiles = 0;
+    for (uint32_t t = 0; t < B->n; ++t) n_tiles += ((uint64_t)B->h_len[t] + PU_TILE - 1) / PU_TILE;
+    if (n_tiles > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": too many tiles");
+    ip->n_tiles = (uint32_t)n_tiles;
+    const uint64_t held = std::min(std::min<uint64_t>(sp_pool_bytes(ctx, "ins_runs") / sizeof(sp_pileup_ins), sp_pool_bytes(ctx, "ins_binned") / sizeof(InsRun)),
+                                   std::min<uint64_t>(sp_pool_bytes(ctx, "ins_tmp") / sizeof(sp_pileup_ins), sp_pool_bytes(ctx, "ins_scratch") / 12));
+    ip->cap = std::max<uint64_t>(held, min_cap ? min_cap : 1024 + 4 * n_pairs);
+    if (ip->cap > 0x7FFFFFFFull) /* (ins_bitonic rounds a tile's runs up to a power of two in 32 bits) */ return sp_fail(ctx, SP_ERR_CAPACITY, who + ": more insertion runs than the list counts");
+    const size_t tw = (size_t)n_tiles + 1, words = 4 + 4 * tw + (size_t)B->n + 1;
+    ip->d_runs = (InsRun*)sp_pool(ctx, "ins_runs", (size_t)ip->cap * sizeof(sp_pileup_ins));          // (the packed list takes the runs' place once they are binned)
+    ip->d_binned = (InsRun*)sp_pool(ctx, "ins_binned", (size_t)ip->cap * sizeof(InsRun));
+    ip->d_tmp = (sp_pileup_ins*)sp_pool(ctx, "ins_tmp", (size_t)ip->cap * sizeof(sp_pileup_ins));
+    ip->d_scratch = (uint32_t*)sp_pool(ctx, "ins_scratch", (size_t)ip->cap * 12);
+    uint32_t* d_w = (uint32_t*)sp_pool(ctx, "ins_tiles", words * 4);
+    uint32_t* h_tf = (uint32_t*)sp_host_pool(ctx, "ins_tiles", ((size_t)B->n + 1) * 4);
+    ip->h_st = (uint64_t*)sp_host_pool(ctx, "ins_st", 16);
+    if (!ip->d_runs || !ip->d_binned || !ip->d_tmp || !ip->d_scratch || !d_w || !h_tf || !ip->h_st) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, who + ": insertion list buffers");
+    ip->d_n = (unsigned long long*)d_w; ip->d_cnt = d_w + 4; ip->d_off = ip->d_cnt + tw; ip->d_cur = ip->d_off + tw; ip->d_ooff = ip->d_cur + tw; ip->d_tfirst = ip->d_ooff + tw;
+    uint32_t x = 0;
+    for (uint32_t t = 0; t < B->n; ++t) { h_tf[t] = x; x += (uint32_t)(((uint64_t)B->h_len[t] + PU_TILE - 1) / PU_TILE); }
+    h_tf[B->n] = x;
+    SP_HIP_CHECK(ctx, hipMemsetAsync(d_w, 0, (4 + 4 * tw) * 4, ctx->stream));
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(ip->d_tfirst, h_tf, ((size_t)B->n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    return SP_OK;
+}
 
-int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
-                        const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset, sp_pileup_col* out) {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    if (!A || !B || !col_offset || (n_pairs && (!pairs || !aln || !n_cigar))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: null argument");
-    if (n_pairs > 0xFFFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: too many pairs");
-    const uint32_t n_t = B->n;
-    if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset[0] must be 0");
-    for (uint32_t t = 0; t < n_t; ++t)
-        if (col_offset[t + 1] < col_offset[t] || col_offset[t + 1] - col_offset[t] != (uint64_t)B->h_len[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset does not follow the target lengths");
-    const uint64_t n_cols = col_offset[n_t];
-    if (n_cols && !out) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: null argument");
-    // ---- every alignment is walked here, before anything is launched or written: what the kernel indexes with is what this loop has seen
-    std::vector<uint32_t> bucket_off((size_t)n_t + 1, 0);
-    uint64_t total_ops = 0;
+// the runs of m alignments (pair numbers pair0 ...) whose rows lie in device memory
+static int32_t ins_collect(sp_ctx* ctx, const std::string& who, const InsPass& ip, const sp_seqset* A, const sp_seqset* B, const sp_pair* d_pairs, const sp_affine_aln* d_aln,
+                           const uint32_t* d_nc, const uint64_t* d_op_off, const uint32_t* d_ops, uint32_t m, uint32_t pair0, bool need_score, const uint64_t* d_col_offset) {
+    if (m == 0 || ip.n_tiles == 0) return SP_OK;
+    ProfScope ps(ctx, "pileup_ins_collect", m);
+    constexpr uint32_t per = INS_THREADS / SP_WAVE;
+    hipLaunchKernelGGL(ins_collect_kernel, dim3((m + per - 1) / per), dim3(INS_THREADS), 0, ctx->stream, A->view(), B->d_len, d_pairs, d_aln, d_nc, d_op_off, d_ops, m, pair0,
+                       need_score ? 1 : 0, d_col_offset, ip.d_tfirst, ip.d_runs, ip.cap, ip.d_n, ip.d_cnt);
+    if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": insertion collect launch failed");
+    return SP_OK;
+}
+
+// everything behind the last collect.  *grow != 0 on return: the run buffer was too small for that many runs, nothing was written -- run the pass again.
+static int32_t ins_finish(sp_ctx* ctx, const std::string& who, const InsPass& ip, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins, uint64_t* grow) {
+    *grow = 0; *n_ins = 0;
+    if (ip.n_tiles == 0) return SP_OK;
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(ip.h_st, ip.d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t n_runs = ip.h_st[0];
+    if (n_runs > ip.cap) { *grow = n_runs; return SP_OK; }
+    if (n_runs == 0) return SP_OK;
+    const uint32_t N = (uint32_t)n_runs;
+    sp_pileup_ins* d_out = (sp_pileup_ins*)ip.d_runs;
+    {
+        ProfScope ps(ctx, "pileup_ins_reduce", n_runs);
+        hipLaunchKernelGGL(ins_scan_kernel, dim3(1), dim3(INS_THREADS), 0, ctx->stream, ip.d_cnt, ip.n_tiles, ip.d_off, ip.d_cur);
+        hipLaunchKernelGGL(ins_scatter_kernel, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, ip.d_runs, N, ip.d_off, ip.d_cur, ip.d_binned);
+        hipLaunchKernelGGL(ins_tile_kernel, dim3(ip.n_tiles), dim3(INS_THREADS), 0, ctx->stream, ip.d_binned, ip.d_off, ip.d_scratch, ip.cap, ip.d_tmp, ip.d_cur);
+        hipLaunchKernelGGL(ins_scan_kernel, dim3(1), dim3(INS_THREADS), 0, ctx->stream, ip.d_cur, ip.n_tiles, ip.d_ooff, (uint32_t*)nullptr);
+        hipLaunchKernelGGL(ins_pack_kernel, dim3(ip.n_tiles), dim3(256), 0, ctx->stream, ip.d_tmp, ip.d_off, ip.d_cur, ip.d_ooff, d_out);
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": insertion list launch failed");
+    }
+    uint32_t* h_total = (uint32_t*)(ip.h_st + 1);
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(h_total, ip.d_ooff + ip.n_tiles, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    *n_ins = *h_total;
+    if (*n_ins > ins_cap) return sp_fail(ctx, SP_ERR_CAPACITY, who + ": " + std::to_string(*n_ins) + " insertion records, room for " + std::to_string(ins_cap));
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(ins, d_out, (size_t)*n_ins * sizeof(sp_pileup_ins), hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return SP_OK;
+}
+
+// Every alignment of host op rows is walked here, before anything is launched or written: what the kernels index with is what this loop has seen.  bucket_off[t + 1]
+// counts the live pairs of target t; *total_ops their ops, *n_ins_ops the 'I' ops among them.
+static int32_t pileup_check_rows(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln, const uint32_t* cigar,
+                                 uint32_t cigar_stride, const uint32_t* n_cigar, std::vector<uint32_t>& bucket_off, uint64_t* total_ops, uint64_t* n_ins_ops) {
     for (uint64_t i = 0; i < n_pairs; ++i) {
         if (pairs[i].a >= A->n || pairs[i].b >= B->n) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: index out of range");
         if (n_cigar[i] == 0) continue;
@@ -276,13 +557,82 @@ int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, con
             if (n == 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": a run of length 0");
             if (op == 7u || op == 8u) { j += n; q += n; }
             else if (op == 2u) j += n;
-            else if (op == 1u) { if (j == g.b_start) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": an insertion before the first target column"); q += n; }
+            else if (op == 1u) { if (j == g.b_start) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": an insertion before the first target column"); q += n; ++*n_ins_ops; }
             else return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": an op other than = X I D");
             if (j > g.b_end || q > g.a_end) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": the ops do not consume the spans of its alignment");
         }
         if (j != g.b_end || q != g.a_end) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": the ops do not consume the spans of its alignment");
-        ++bucket_off[pairs[i].b + 1]; total_ops += n_cigar[i];
+        ++bucket_off[pairs[i].b + 1]; *total_ops += n_cigar[i];
     }
+    return SP_OK;
+}
+
+// the first min(len, 64) bases of a record, from its key
+static std::string ins_key_string(const sp_pileup_ins& r) {
+    std::string out(std::min<uint32_t>(r.len, 64), 'A');
+    for (size_t i = 0; i < out.size(); ++i) out[i] = "ACGT"[((i < 32 ? r.p0 >> (2 * i) : r.p1 >> (2 * (i - 32)))) & 3u];
+    return out;
+}
+
+} // namespace
+
+void spi_support_ins_json(spj::Value* column, const sp_pileup_ins* ins, uint64_t n_ins, uint64_t col, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
+                          const char* const* names, uint32_t n_names) {
+    const sp_pileup_ins* end = ins + n_ins;
+    const sp_pileup_ins* r = std::lower_bound(ins, end, col, [](const sp_pileup_ins& a, uint64_t c) { return a.col < c; });
+    spj::Value list = spj::array();
+    uint64_t more = 0, other = 0;
+    for (; r != end && r->col == col; ++r) {
+        other += r->n_other;
+        if (r->len == 0) continue;
+        if (list.arr.size() >= 8) { ++more; continue; }
+        spj::Value v = spj::object();
+        v.obj.emplace_back("seq", spj::str(ins_key_string(*r))); v.obj.emplace_back("count", spj::unum(r->count));
+        if (r->len > 64) v.obj.emplace_back("len", spj::unum(r->len));
+        uint64_t who = r->first_pair;
+        bool known = names != nullptr;
+        if (known && mappings) { known = who < n_mappings; if (known) who = mappings[who].read; }
+        if (known && who < n_names && names[who]) v.obj.emplace_back("first_read", spj::str(names[who]));
+        list.arr.push_back(std::move(v));
+    }
+    column->obj.emplace_back("insertions", std::move(list));
+    if (more) column->obj.emplace_back("more", spj::unum(more));
+    if (other) column->obj.emplace_back("other", spj::unum(other));
+}
+
+extern "C" {
+
+int32_t sp_support_ins_string(const sp_pileup_ins* rec, const sp_seqset* queries, uint32_t query, char* out, uint64_t cap, uint64_t* needed) {
+    if (!rec || (cap && !out)) return SP_ERR_INVALID_ARG;
+    std::string text;
+    if (rec->len <= 64) text = ins_key_string(*rec);
+    else {
+        if (!queries || !queries->ctx || query >= queries->n || (uint64_t)rec->first_qpos + rec->len > (uint64_t)queries->h_len[query]) return SP_ERR_INVALID_ARG;
+        const std::string whole = sp_seqset_decode(queries->ctx, queries, query);
+        if ((int32_t)whole.size() != queries->h_len[query]) return SP_ERR_HIP;
+        text = whole.substr(rec->first_qpos, rec->len);
+    }
+    if (needed) *needed = text.size() + 1;
+    if (cap < text.size() + 1) { if (cap) out[0] = '\0'; return SP_ERR_CAPACITY; }
+    std::memcpy(out, text.c_str(), text.size() + 1);
+    return SP_OK;
+}
+
+int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
+                        const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset, sp_pileup_col* out) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (!A || !B || !col_offset || (n_pairs && (!pairs || !aln || !n_cigar))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: null argument");
+    if (n_pairs > 0xFFFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: too many pairs");
+    const uint32_t n_t = B->n;
+    if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset[0] must be 0");
+    for (uint32_t t = 0; t < n_t; ++t)
+        if (col_offset[t + 1] < col_offset[t] || col_offset[t + 1] - col_offset[t] != (uint64_t)B->h_len[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset does not follow the target lengths");
+    const uint64_t n_cols = col_offset[n_t];
+    if (n_cols && !out) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: null argument");
+    std::vector<uint32_t> bucket_off((size_t)n_t + 1, 0);
+    uint64_t total_ops = 0, n_ins_ops = 0;
+    const int32_t rc_rows = pileup_check_rows(ctx, A, B, pairs, n_pairs, aln, cigar, cigar_stride, n_cigar, bucket_off, &total_ops, &n_ins_ops);
+    if (rc_rows != SP_OK) return rc_rows;
     if (n_cols == 0) return SP_OK;
     for (uint32_t t = 0; t < n_t; ++t) bucket_off[t + 1] += bucket_off[t];
     const uint32_t n_live = bucket_off[n_t];
@@ -333,12 +683,64 @@ int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, con
     return SP_OK;
 }
 
+int32_t sp_pileup_ins_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
+                            const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (!A || !B || !col_offset || !n_ins || (ins_cap && !ins) || (n_pairs && (!pairs || !aln || !n_cigar))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: null argument");
+    if (n_pairs > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: too many pairs");
+    const uint32_t n_t = B->n, n = (uint32_t)n_pairs;
+    if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset[0] must be 0");
+    for (uint32_t t = 0; t < n_t; ++t)
+        if (col_offset[t + 1] < col_offset[t] || col_offset[t + 1] - col_offset[t] != (uint64_t)B->h_len[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset does not follow the target lengths");
+    std::vector<uint32_t> bucket_off((size_t)n_t + 1, 0);
+    uint64_t total_ops = 0, n_ins_ops = 0;
+    int32_t rc = pileup_check_rows(ctx, A, B, pairs, n_pairs, aln, cigar, cigar_stride, n_cigar, bucket_off, &total_ops, &n_ins_ops);
+    if (rc != SP_OK) return rc;
+    *n_ins = 0;
+    if (n_ins_ops == 0 || col_offset[n_t] == 0) return SP_OK;
+    (void)hipSetDevice(ctx->device);
+    // ---- one staging block, one copy: the pair list, the spans, op counts and op offsets per pair, the column offsets, the ops back to back
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t at_pairs = 0, at_aln = up16(at_pairs + sizeof(sp_pair) * (size_t)n), at_nc = up16(at_aln + sizeof(sp_affine_aln) * (size_t)n), at_off = up16(at_nc + 4 * (size_t)n),
+                 at_cols = up16(at_off + 8 * (size_t)n), at_ops = up16(at_cols + 8 * ((size_t)n_t + 1)), in_bytes = up16(at_ops + 4 * (size_t)total_ops) + 16;
+    uint8_t* h_in = (uint8_t*)sp_host_pool(ctx, "pileup_ins_in", in_bytes);
+    uint8_t* d_in = (uint8_t*)sp_pool(ctx, "pileup_ins_in", in_bytes);
+    if (!h_in || !d_in) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "pileup buffers");
+    {
+        std::memcpy(h_in + at_pairs, pairs, sizeof(sp_pair) * (size_t)n);
+        std::memcpy(h_in + at_aln, aln, sizeof(sp_affine_aln) * (size_t)n);
+        std::memcpy(h_in + at_nc, n_cigar, 4 * (size_t)n);
+        std::memcpy(h_in + at_cols, col_offset, 8 * ((size_t)n_t + 1));
+        uint64_t* hoff = (uint64_t*)(h_in + at_off); uint32_t* hops = (uint32_t*)(h_in + at_ops);
+        uint64_t op_at = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            hoff[i] = op_at;
+            if (n_cigar[i] == 0) continue;
+            std::memcpy(hops + op_at, cigar + i * (size_t)cigar_stride, 4 * (size_t)n_cigar[i]);
+            op_at += n_cigar[i];
+        }
+    }
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    InsPass ip;
+    rc = ins_begin(ctx, "pileup", B, n_pairs, n_ins_ops, &ip);                            // (the host has counted the runs: the buffer is never too small)
+    if (rc != SP_OK) return rc;
+    rc = ins_collect(ctx, "pileup", ip, A, B, (const sp_pair*)(d_in + at_pairs), (const sp_affine_aln*)(d_in + at_aln), (const uint32_t*)(d_in + at_nc), (const uint64_t*)(d_in + at_off),
+                     (const uint32_t*)(d_in + at_ops), n, 0, false, (const uint64_t*)(d_in + at_cols));
+    if (rc != SP_OK) return rc;
+    uint64_t grow = 0;
+    rc = ins_finish(ctx, "pileup", ip, ins, ins_cap, n_ins, &grow);
+    if (rc != SP_OK) return rc;
+    if (grow) return sp_fail(ctx, SP_ERR_HIP, "pileup: the run buffer did not hold the runs the host counted");
+    return SP_OK;
+}
+
 // sp_align_pileup_band_batch for the library's own callers as well: `who` begins its error texts, prof[] names its four launches (map, second map, pileup, summary) in the
 // context's profile, and the first map launch counts the pairs it attempts (max_ed >= 0) when count_attempted is set, every pair of the slice otherwise.
 static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
                                 const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
-                                const std::string& who, const char* const prof[4], bool count_attempted) {
-    if (!A || !B || !opts || !col_offset || (n_pairs && !pairs)) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": null argument");
+                                const std::string& who, const char* const prof[4], bool count_attempted,
+                                sp_pileup_ins* ins = nullptr, uint64_t ins_cap = 0, uint64_t* n_ins = nullptr, uint64_t ins_runs = 0) {
+    if (!A || !B || !opts || !col_offset || (n_pairs && !pairs) || (ins && !n_ins)) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": null argument");
     if ((band != 64 && band != 256) || (retry_band != 0 && retry_band != 256) || (retry_band != 0 && band != 64))
         return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": band must be 64 or 256, retry_band 0 or (with band 64) 256");
     if (n_pairs > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": too many pairs");
@@ -354,9 +756,10 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
         if (pairs[i].a >= A->n || pairs[i].b >= B->n) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": index out of range");
         ++boff[(size_t)pairs[i].b * (n_slices + 1) + i / SP_ALIGN_PILEUP_SLICE + 1];
     }
+    if (ins) *n_ins = 0;
     if (n_pairs == 0 && n_t == 0) return SP_OK;
     const bool want_table = (cols || summaries) && n_t > 0;
-    if (!aln && !want_table) return SP_OK;
+    if (!aln && !want_table && !ins) return SP_OK;
     // boff[t * (S + 1) + s + 1] holds the count of (t, s): into running offsets; entry t * (S + 1) is where target t begins = where target t - 1 ended
     {
         uint32_t run = 0;
@@ -410,6 +813,14 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
             lds_set.fetch_or(bit);
         }
     }
+    InsPass ip;                                                                                       // the insertion list, when asked for: its runs are collected slice by slice
+    if (ins) {
+        // the first guess: one run per 64 query bases (HiFi members against their own consensus carry far fewer) on top of four per pair; more than that runs the pass again
+        uint64_t q_bases = 0;
+        for (uint32_t i = 0; i < n; ++i) q_bases += (uint64_t)A->h_len[pairs[i].a];
+        const int32_t rc = ins_begin(ctx, who, B, n_pairs, ins_runs ? ins_runs : 1024 + 4 * n_pairs + q_bases / 64, &ip);
+        if (rc != SP_OK) return rc;
+    }
     // ---- slice by slice: the map into the op buffer (run again on a larger one when it asked for more: a warm context does not), what the host must know, the pileup
     uint64_t ops_cap = std::max<uint64_t>(sp_pool_bytes(ctx, "appile_ops") / 4, (uint64_t)std::min<uint32_t>(std::max<uint32_t>(n, 1), SP_ALIGN_PILEUP_SLICE) * 64);
     for (uint32_t s2 = 0; s2 < n_slices; ++s2) {
@@ -449,6 +860,10 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
                                d_order, d_boff, n_slices, s2, (const PuTile*)(d_in + at_tiles), (const uint64_t*)(d_in + at_cols), d_table);
             if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": pileup launch failed");
         }
+        if (ins && m > 0) {
+            const int32_t rc = ins_collect(ctx, who, ip, A, B, d_pairs + p0, d_aln + p0, d_nc + p0, d_off + p0, d_ops, m, p0, true, (const uint64_t*)(d_in + at_cols));
+            if (rc != SP_OK) return rc;
+        }
     }
     if (d_sum) {
         ProfScope ps(ctx, prof[3], n_cols);
@@ -466,6 +881,17 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
     if (cols && n_cols) SP_HIP_CHECK(ctx, hipMemcpyAsync(cols, d_table, n_cols * sizeof(sp_pileup_col), hipMemcpyDeviceToHost, ctx->stream));
     if (d_sum) SP_HIP_CHECK(ctx, hipMemcpyAsync(summaries, d_sum, (size_t)n_t * sizeof(sp_support_summary), hipMemcpyDeviceToHost, ctx->stream));
     SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ins) {
+        // the list last: everything else is complete when it does not fit.  A run buffer that was guessed too small: the whole pass once more on one that holds them
+        // (the op rows of the earlier slices are gone) -- a warm context's buffer is large enough
+        uint64_t grow = 0;
+        const int32_t rc = ins_finish(ctx, who, ip, ins, ins_cap, n_ins, &grow);
+        if (rc != SP_OK) return rc;
+        if (grow) {
+            if (ins_runs) return sp_fail(ctx, SP_ERR_HIP, who + ": the run buffer did not hold a second run");
+            return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, who, prof, count_attempted, ins, ins_cap, n_ins, grow);
+        }
+    }
     return SP_OK;
 }
 
@@ -474,6 +900,14 @@ int32_t sp_align_pileup_band_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seq
     if (!ctx) return SP_ERR_INVALID_ARG;
     static const char* const prof[4] = { "align_pileup_map", "align_pileup_map_retry", "align_pileup_pile", "align_pileup_summary" };
     return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, "align_pileup", prof, false);
+}
+
+int32_t sp_align_pileup_ins_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
+                                  const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
+                                  sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    static const char* const prof[4] = { "align_pileup_map", "align_pileup_map_retry", "align_pileup_pile", "align_pileup_summary" };
+    return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, "align_pileup", prof, false, ins, ins_cap, n_ins);
 }
 
 int32_t sp_align_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, const uint64_t* col_offset,
@@ -503,7 +937,12 @@ int32_t sp_support_contested(const sp_pileup_col* cols, uint32_t length, uint32_
 }
 
 int32_t sp_consensus_support_json(const sp_support_entry* entries, uint32_t n_entries, char* out, uint64_t cap, uint64_t* needed) {
-    if ((n_entries && !entries) || (cap && !out)) return SP_ERR_INVALID_ARG;
+    return sp_consensus_support_json_ins(entries, n_entries, nullptr, nullptr, 0, nullptr, 0, out, cap, needed);
+}
+
+int32_t sp_consensus_support_json_ins(const sp_support_entry* entries, uint32_t n_entries, const uint64_t* col_base, const sp_pileup_ins* ins, uint64_t n_ins,
+                                      const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed) {
+    if ((n_entries && !entries) || (cap && !out) || (n_ins && !ins) || (n_entries && n_ins && !col_base)) return SP_ERR_INVALID_ARG;     // (without entries no col_base is read)
     std::vector<uint32_t> order;
     for (uint32_t e = 0; e < n_entries; ++e) {
         if (!entries[e].gene) return SP_ERR_INVALID_ARG;
@@ -539,6 +978,7 @@ int32_t sp_consensus_support_json(const sp_support_entry* entries, uint32_t n_en
                 k.obj.emplace_back("x", std::move(x));
                 k.obj.emplace_back("del", spj::unum(cols[j].del)); k.obj.emplace_back("ins", spj::unum(cols[j].ins));
                 k.obj.emplace_back("consensus_base", spj::str(std::string(1, s[j])));
+                if (n_ins && 2ull * cols[j].ins > cols[j].depth) spi_support_ins_json(&k, ins, n_ins, col_base[2 * (size_t)order[o] + c] + j, nullptr, 0, read_names, n_read_names);
                 list.arr.push_back(std::move(k));
             }
             v.obj.emplace_back("contested", std::move(list));
@@ -554,10 +994,13 @@ int32_t sp_consensus_support_json(const sp_support_entry* entries, uint32_t n_en
     return SP_OK;
 }
 
-int32_t sp_hla_consensus_support_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
-                                        const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1, const char* cons, uint32_t cap,
-                                        const uint8_t* unit_on, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries) {
+int32_t sp_hla_consensus_support_cohort_ins(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
+                                            const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1, const char* cons, uint32_t cap,
+                                            const uint8_t* unit_on, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries,
+                                            sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
     if (!ctx) return SP_ERR_INVALID_ARG;
+    if (ins && !n_ins) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: null argument");
+    if (ins) *n_ins = 0;
     if (!db || !reads || !col_offset || !summaries || n_samples == 0 || (n_genes && (!genes || !cons || cap == 0)) || (reads->n && (!realign || !is_cons1)) || (n_samples > 1 && !read_sample))
         return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: null argument");
     const uint64_t n_units = (uint64_t)n_samples * n_genes;
@@ -586,7 +1029,7 @@ int32_t sp_hla_consensus_support_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32
     const uint32_t n_t = (uint32_t)toff.size() - 1;
     if (n_t == 0) return SP_OK;
     // ---- the members: the realigned reads of every unit whose group has a consensus; their segments on the gene strand
-    std::vector<uint32_t> m_target; std::vector<uint32_t> members_of(n_t, 0);
+    std::vector<uint32_t> m_target, m_read; std::vector<uint32_t> members_of(n_t, 0);
     std::string qblob; std::vector<uint64_t> qoff(1, 0);
     for (uint32_t r = 0; r < reads->n; ++r) {
         const sp_hla_realign& q = realign[r];
@@ -602,7 +1045,7 @@ int32_t sp_hla_consensus_support_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32
         if ((int32_t)whole.size() != reads->h_len[r]) return sp_fail(ctx, SP_ERR_HIP, "consensus support: fetching the reads failed");
         if (spi_hla_gene_fwd(db, (uint32_t)q.gene)) qblob.append(whole, (size_t)q.seg_start, (size_t)(q.seg_end - q.seg_start));
         else qblob += revcomp_str(whole.data() + q.seg_start, (size_t)(q.seg_end - q.seg_start));
-        qoff.push_back(qblob.size()); m_target.push_back((uint32_t)t); ++members_of[t];
+        qoff.push_back(qblob.size()); m_target.push_back((uint32_t)t); m_read.push_back(r); ++members_of[t];
     }
     const uint32_t n_m = (uint32_t)m_target.size();
     sp_seqset T, Q;
@@ -626,8 +1069,9 @@ int32_t sp_hla_consensus_support_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32
         for (uint32_t m = 0; m < n_m; ++m) pairs[m] = sp_pair{ m, m_target[m], -diag[m], votes[m] > 0 ? 0 : -1 };
         // (the pileup launch keeps the profile name it has had in this pass: "pileup")
         static const char* const prof[4] = { "consensus_support_map", "consensus_support_map_retry", "pileup", "consensus_support_summary" };
-        rc = align_pileup_run(ctx, &Q, &T, pairs.data(), n_m, &ao, 64, 256, t_cols.data(), nullptr, table.data(), sums.data(), members_of.data(), nullptr, "consensus support", prof, true);
-        if (rc != SP_OK) return rc;
+        rc = align_pileup_run(ctx, &Q, &T, pairs.data(), n_m, &ao, 64, 256, t_cols.data(), nullptr, table.data(), sums.data(), members_of.data(), nullptr, "consensus support", prof, true,
+                              ins, ins_cap, n_ins);
+        if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ins && *n_ins > ins_cap)) return rc;
     } else for (uint32_t t = 0; t < n_t; ++t) sp_support_summarize(table.data() + t_cols[t], (uint32_t)(t_cols[t + 1] - t_cols[t]), 0, 0, &sums[t]);
     for (uint64_t x = 0; x < 2 * n_units; ++x) {
         const int32_t t = target_of[x];
@@ -637,11 +1081,29 @@ int32_t sp_hla_consensus_support_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32
         std::memcpy(cols + col_offset[x], src, sizeof(sp_pileup_col) * (size_t)len);
         summaries[x] = sums[t];
     }
+    if (rc != SP_OK) return rc;                                                        // (the list did not fit: everything else is complete)
+    if (ins && *n_ins) {
+        // the list in the caller's terms: the targets are the consensuses that have columns, in col_offset's order, so the records stay in order
+        std::vector<uint64_t> base(n_t, 0);
+        for (uint64_t x = 0; x < 2 * n_units; ++x) if (target_of[x] >= 0) base[target_of[x]] = col_offset[x];
+        for (uint64_t k = 0; k < *n_ins; ++k) {
+            const uint32_t t = (uint32_t)(std::upper_bound(t_cols.begin(), t_cols.end(), ins[k].col) - t_cols.begin()) - 1;
+            ins[k].col = base[t] + (ins[k].col - t_cols[t]);
+            if (ins[k].len) ins[k].first_pair = m_read[ins[k].first_pair];
+        }
+    }
     return SP_OK;
 }
 
-int32_t sp_hla_consensus_support(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1,
-                                 const char* cons1, const char* cons2, sp_pileup_col* cols1, sp_pileup_col* cols2, sp_support_summary* s1, sp_support_summary* s2) {
+int32_t sp_hla_consensus_support_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
+                                        const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1, const char* cons, uint32_t cap,
+                                        const uint8_t* unit_on, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries) {
+    return sp_hla_consensus_support_cohort_ins(ctx, db, n_samples, read_sample, n_genes, genes, reads, realign, is_cons1, cons, cap, unit_on, col_offset, cols, cols_cap, summaries, nullptr, 0, nullptr);
+}
+
+int32_t sp_hla_consensus_support_ins(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1,
+                                     const char* cons1, const char* cons2, sp_pileup_col* cols1, sp_pileup_col* cols2, sp_support_summary* s1, sp_support_summary* s2,
+                                     sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
     if (!ctx) return SP_ERR_INVALID_ARG;
     if (!cons1 || !cons2) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: null argument");
     const size_t l1 = cols1 && s1 ? std::strlen(cons1) : 0, l2 = cols2 && s2 ? std::strlen(cons2) : 0;
@@ -650,11 +1112,16 @@ int32_t sp_hla_consensus_support(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene
     std::memcpy(both.data(), cons1, l1); std::memcpy(both.data() + cap, cons2, l2);
     uint64_t off[3]; sp_support_summary sm[2];
     std::vector<sp_pileup_col> table(l1 + l2);
-    const int32_t rc = sp_hla_consensus_support_cohort(ctx, db, 1, nullptr, 1, &gene, reads, realign, is_cons1, both.data(), cap, nullptr, off, table.data(), table.size(), sm);
-    if (rc != SP_OK) return rc;
+    const int32_t rc = sp_hla_consensus_support_cohort_ins(ctx, db, 1, nullptr, 1, &gene, reads, realign, is_cons1, both.data(), cap, nullptr, off, table.data(), table.size(), sm, ins, ins_cap, n_ins);
+    if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ins && n_ins && *n_ins > ins_cap)) return rc;
     if (cols1 && s1) { std::memcpy(cols1, table.data(), sizeof(sp_pileup_col) * l1); *s1 = sm[0]; }
     if (cols2 && s2) { std::memcpy(cols2, table.data() + off[1], sizeof(sp_pileup_col) * l2); *s2 = sm[1]; }
-    return SP_OK;
+    return rc;
+}
+
+int32_t sp_hla_consensus_support(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1,
+                                 const char* cons1, const char* cons2, sp_pileup_col* cols1, sp_pileup_col* cols2, sp_support_summary* s1, sp_support_summary* s2) {
+    return sp_hla_consensus_support_ins(ctx, db, gene, reads, realign, is_cons1, cons1, cons2, cols1, cols2, s1, s2, nullptr, 0, nullptr);
 }
 
 } // extern "C"

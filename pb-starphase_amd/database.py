@@ -159,6 +159,9 @@ def _lib():
         "sp_cyp_consensus_support": (_i32, [_vp, _vp, P(ffi.sp_cyp_call), _vp, _u32, P(sp_cyp_read_mapping), _u64, _vp, _vp, _u64, _vp]),
         "sp_cyp_consensus_support_cohort": (_i32, [_vp, _u32, P(_vp), P(ffi.sp_cyp_call), _vp, _u32, P(sp_cyp_read_mapping), _vp, _vp, _vp, _u64, _vp]),
         "sp_cyp_support_json": (_i32, [P(ffi.sp_cyp_call), _vp, _u32, _vp, _vp, _vp, _s, _u64, P(_u64)]),
+        "sp_cyp_consensus_support_ins": (_i32, [_vp, _vp, P(ffi.sp_cyp_call), _vp, _u32, P(sp_cyp_read_mapping), _u64, _vp, _vp, _u64, _vp, _vp, _u64, P(_u64)]),
+        "sp_cyp_consensus_support_cohort_ins": (_i32, [_vp, _u32, P(_vp), P(ffi.sp_cyp_call), _vp, _u32, P(sp_cyp_read_mapping), _vp, _vp, _vp, _u64, _vp, _vp, _u64, P(_u64)]),
+        "sp_cyp_support_json_ins": (_i32, [P(ffi.sp_cyp_call), _vp, _u32, _vp, _vp, _vp, _vp, _u64, P(sp_cyp_read_mapping), _u64, P(C.c_char_p), _u32, _s, _u64, P(_u64)]),
         "sp_diplotype_settings_default": (None, [P(sp_diplotype_settings)]),
         "sp_diplotype_settings_check": (_i32, [P(sp_diplotype_settings), P(sp_sample_inputs), _s, _u32]),
         "sp_starphase_create": (_i32, [_vp, _s, _s, P(sp_diplotype_settings), P(_vp)]),
@@ -171,6 +174,7 @@ def _lib():
         "sp_starphase_set_hla_debug_mappings": (_i32, [_vp, _i32]),
         "sp_starphase_set_consensus_support": (_i32, [_vp, _i32]),
         "sp_starphase_set_cyp_consensus_support": (_i32, [_vp, _i32]),
+        "sp_starphase_set_support_insertions": (_i32, [_vp, _i32]),
         "sp_starphase_call_batch": (_i32, [_vp, _u32, P(sp_sample_inputs), P(_s), P(sp_batch_options), P(_vp), P(_i32)]),
         "sp_starphase_sample_error": (_s, [_vp, _u32]),
         "sp_starphase_sample_warnings": (_s, [_vp, _u32]),
@@ -951,9 +955,10 @@ def settings_check(bams=(), vcf=None, **kw):
 class Starphase:
     """sp_starphase: a database + reference loaded once, sp_starphase_call per sample.  ctx: a Context or None (the handle makes its own).
     consensus_support=True: set_consensus_support() at once (a call with a debug folder also writes consensus_support.json); cyp_consensus_support=True:
-    set_cyp_consensus_support() at once (it also writes cyp2d6_consensus_support.json)."""
+    set_cyp_consensus_support() at once (it also writes cyp2d6_consensus_support.json); support_insertions=True: set_support_insertions() at once (those two files
+    also list the inserted strings of the columns their insertions contest)."""
 
-    def __init__(self, database, reference=None, ctx=None, consensus_support=False, cyp_consensus_support=False, **settings):
+    def __init__(self, database, reference=None, ctx=None, consensus_support=False, cyp_consensus_support=False, support_insertions=False, **settings):
         self._h = _vp()
         self._s = _settings(**settings)
         rc = _lib().sp_starphase_create(ctx._h if ctx is not None else None, _b(database), _b(reference), C.byref(self._s), C.byref(self._h))
@@ -963,6 +968,8 @@ class Starphase:
             self.set_consensus_support(True)
         if cyp_consensus_support:
             self.set_cyp_consensus_support(True)
+        if support_insertions:
+            self.set_support_insertions(True)
 
     def close(self):
         if self._h:
@@ -981,6 +988,14 @@ class Starphase:
         rc = _lib().sp_starphase_set_consensus_support(self._h, 1 if on else 0)
         if rc != SP_OK:
             raise StarphaseError(rc, "sp_starphase_set_consensus_support")
+        return self
+
+    def set_support_insertions(self, on=True):
+        """sp_starphase_set_support_insertions: consensus_support.json and cyp2d6_consensus_support.json, where their own switches write them, also carry "insertions":
+        the inserted strings, with counts, behind every column that is contested by its insertions.  Off by default; no effect without one of those switches."""
+        rc = _lib().sp_starphase_set_support_insertions(self._h, 1 if on else 0)
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_starphase_set_support_insertions")
         return self
 
     def set_cyp_consensus_support(self, on=True):
@@ -1124,8 +1139,9 @@ def _mapping_array(mappings):
     return arr
 
 
-def cyp_consensus_support(ctx, reads, call, cons, cons_cap, mappings, want_cols=True):
-    """sp_cyp_consensus_support: call / cons / mappings as cyp_call_with_consensus returned them -> ([cols PILEUP_DTYPE per consensus] or None, [summary dict per consensus])"""
+def cyp_consensus_support(ctx, reads, call, cons, cons_cap, mappings, want_cols=True, insertions=False):
+    """sp_cyp_consensus_support: call / cons / mappings as cyp_call_with_consensus returned them -> ([cols PILEUP_DTYPE per consensus] or None, [summary dict per consensus]).
+    insertions=True (sp_cyp_consensus_support_ins) adds the INS_DTYPE records (col: consensus h's columns from the sum of the lengths before it) as a third item"""
     import numpy as np
     H = max(0, min(call.n_consensus, ffi.SP_CYP_MAXCONS))
     off = np.zeros(ffi.SP_CYP_MAXCONS + 1, np.uint64)
@@ -1133,13 +1149,20 @@ def cyp_consensus_support(ctx, reads, call, cons, cons_cap, mappings, want_cols=
     cols = np.zeros(max(1, total), ffi.PILEUP_DTYPE) if want_cols else None
     sm = np.zeros(ffi.SP_CYP_MAXCONS, ffi.SUPPORT_DTYPE)
     arr = _mapping_array(mappings)
-    ctx.check(_lib().sp_cyp_consensus_support(ctx._h, reads._h, C.byref(call), C.cast(cons, _vp), cons_cap, arr, len(mappings), ffi._ptr(off), ffi._ptr(cols), total, ffi._ptr(sm)))
-    return ([cols[int(off[h]):int(off[h + 1])].copy() for h in range(H)] if want_cols else None,
-            [{n: int(sm[h][n]) for n in ffi.SUPPORT_FIELDS[:-1]} for h in range(H)])
+    ins = None
+    if insertions:
+        ins = ctx._with_ins(lambda ins, cap, n: _lib().sp_cyp_consensus_support_ins(ctx._h, reads._h, C.byref(call), C.cast(cons, _vp), cons_cap, arr, len(mappings), ffi._ptr(off),
+                                                                                    ffi._ptr(cols), total, ffi._ptr(sm), ins, cap, n), 16384)
+    else:
+        ctx.check(_lib().sp_cyp_consensus_support(ctx._h, reads._h, C.byref(call), C.cast(cons, _vp), cons_cap, arr, len(mappings), ffi._ptr(off), ffi._ptr(cols), total, ffi._ptr(sm)))
+    res = ([cols[int(off[h]):int(off[h + 1])].copy() for h in range(H)] if want_cols else None,
+           [{n: int(sm[h][n]) for n in ffi.SUPPORT_FIELDS[:-1]} for h in range(H)])
+    return res + (ins,) if insertions else res
 
 
-def cyp_consensus_support_cohort(ctx, read_sets, calls, cons_blocks, cons_cap, mapping_lists):
-    """sp_cyp_consensus_support_cohort: per sample what cyp_call_with_consensus returned -> per sample ([cols per consensus], [summary dict per consensus])"""
+def cyp_consensus_support_cohort(ctx, read_sets, calls, cons_blocks, cons_cap, mapping_lists, insertions=False):
+    """sp_cyp_consensus_support_cohort: per sample what cyp_call_with_consensus returned -> per sample ([cols per consensus], [summary dict per consensus]).
+    insertions=True (sp_cyp_consensus_support_cohort_ins): -> (that, INS_DTYPE records, col_offset uint64[n * SP_CYP_MAXCONS + 1])"""
     import numpy as np
     n = len(read_sets)
     M = ffi.SP_CYP_MAXCONS
@@ -1155,17 +1178,24 @@ def cyp_consensus_support_cohort(ctx, read_sets, calls, cons_blocks, cons_cap, m
     total = sum(len(cyp_consensus_of(cons_blocks[i], cons_cap, h)) for i in range(n) if calls[i].status == 0 for h in range(max(0, min(calls[i].n_consensus, M))))
     cols = np.zeros(max(1, total), ffi.PILEUP_DTYPE)
     sm = np.zeros(n * M, ffi.SUPPORT_DTYPE)
-    ctx.check(_lib().sp_cyp_consensus_support_cohort(ctx._h, n, handles, carr, C.cast(block, _vp), cons_cap, _mapping_array(flat), ffi._ptr(moff), ffi._ptr(off), ffi._ptr(cols), total, ffi._ptr(sm)))
+    marr = _mapping_array(flat)
+    ins = None
+    if insertions:
+        ins = ctx._with_ins(lambda ins, cap, k: _lib().sp_cyp_consensus_support_cohort_ins(ctx._h, n, handles, carr, C.cast(block, _vp), cons_cap, marr, ffi._ptr(moff), ffi._ptr(off),
+                                                                                           ffi._ptr(cols), total, ffi._ptr(sm), ins, cap, k), 16384)
+    else:
+        ctx.check(_lib().sp_cyp_consensus_support_cohort(ctx._h, n, handles, carr, C.cast(block, _vp), cons_cap, marr, ffi._ptr(moff), ffi._ptr(off), ffi._ptr(cols), total, ffi._ptr(sm)))
     out = []
     for i in range(n):
         H = max(0, min(calls[i].n_consensus, M)) if calls[i].status == 0 else 0
         out.append(([cols[int(off[i * M + h]):int(off[i * M + h + 1])].copy() for h in range(H)], [{k: int(sm[i * M + h][k]) for k in ffi.SUPPORT_FIELDS[:-1]} for h in range(H)]))
-    return out
+    return (out, ins, off.copy()) if insertions else out
 
 
-def cyp_support_json(call, consensus, cols, summaries, cap=None):
+def cyp_support_json(call, consensus, cols, summaries, cap=None, insertions=None, mappings=None, read_names=None):
     """sp_cyp_support_json (host only): consensus = [text per consensus], cols = [PILEUP_DTYPE per consensus], summaries = [dict per consensus] -> the text of
-    cyp2d6_consensus_support.json.  cap: a buffer size to try -> (status, text, needed)"""
+    cyp2d6_consensus_support.json.  cap: a buffer size to try -> (status, text, needed).  insertions (INS_DTYPE; mappings and read_names optional, for first_read):
+    sp_cyp_support_json_ins"""
     import numpy as np
     H = len(consensus)
     cons_cap = max([len(s) for s in consensus] + [0]) + 1
@@ -1181,6 +1211,20 @@ def cyp_support_json(call, consensus, cols, summaries, cap=None):
             sm[h][k] = int(d.get(k, 0))
     need = _u64(0)
     args = (C.byref(call), C.cast(block, _vp), cons_cap, ffi._ptr(off), ffi._ptr(table), ffi._ptr(sm))
+    if insertions is not None:
+        ins = np.ascontiguousarray(insertions, ffi.INS_DTYPE)
+        marr = _mapping_array(mappings) if mappings is not None else None
+        names, n_names = ffi._name_array(read_names)
+        need = _u64(0)
+        more = (ffi._ptr(ins) if len(ins) else None, len(ins), marr, len(mappings) if mappings is not None else 0, names, n_names)
+        rc = _lib().sp_cyp_support_json_ins(*args, *more, None, 0, C.byref(need))
+        if rc not in (SP_OK, ffi.SP_ERR_CAPACITY):
+            raise StarphaseError(rc, "sp_cyp_support_json_ins")
+        buf = C.create_string_buffer(need.value)
+        rc = _lib().sp_cyp_support_json_ins(*args, *more, buf, need.value, C.byref(need))
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_cyp_support_json_ins")
+        return buf.value.decode()
     if cap is not None:
         buf = C.create_string_buffer(max(1, cap))
         rc = _lib().sp_cyp_support_json(*args, buf if cap else None, cap, C.byref(need))

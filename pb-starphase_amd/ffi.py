@@ -243,6 +243,12 @@ SUPPORT_FIELDS = ("n_members", "n_aligned", "n_unaligned", "length", "min_depth"
 SUPPORT_DTYPE = np.dtype([(n, np.uint32) for n in SUPPORT_FIELDS])                                                                      # sp_support_summary
 
 
+# sp_pileup_ins: one record per distinct (column, inserted string); a tile with more runs than SP_PILEUP_INS_LDS_RUNS sorts in device memory instead of LDS
+SP_PILEUP_INS_LDS_RUNS = 1024
+INS_DTYPE = np.dtype([("col", np.uint64), ("len", np.uint32), ("count", np.uint32), ("p0", np.uint64), ("p1", np.uint64), ("h", np.uint64),
+                      ("first_pair", np.uint32), ("first_qpos", np.uint32), ("n_other", np.uint32), ("reserved_", np.uint32)])
+
+
 class sp_support_summary(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in SUPPORT_FIELDS]
 
@@ -272,9 +278,34 @@ def support_contested(cols):
     return pos[:n.value].copy()
 
 
-def consensus_support_json(entries):
+def support_ins_string(rec, queries=None, query=0):
+    """sp_support_ins_string (host only): the ASCII of one INS_DTYPE record; queries / query: the set and sequence a string of more than 64 bases is read from"""
+    one = np.ascontiguousarray(np.asarray(rec, INS_DTYPE).reshape(1))
+    buf = C.create_string_buffer(int(one[0]["len"]) + 1)
+    need = C.c_uint64(0)
+    rc = lib().sp_support_ins_string(_ptr(one), queries._h if queries is not None else None, int(query), buf, len(buf), C.byref(need))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_support_ins_string")
+    return buf.value.decode()
+
+
+def _name_array(names):
+    if names is None:
+        return None, 0
+    return (C.c_char_p * max(1, len(names)))(*[n.encode() if n is not None else None for n in names]), len(names)
+
+
+def consensus_support_json(entries, insertions=None, col_base=None, read_names=None):
     """sp_consensus_support_json (host only): entries = [(gene, [(typed_allele or None, gene-strand consensus, cols PILEUP_DTYPE, summary dict) or None] * 2)]
-    -> the text of consensus_support.json"""
+    -> the text of consensus_support.json.  insertions (INS_DTYPE, with col_base = [(col of column 0 of consensus1, of consensus2)] per entry and, optionally,
+    read_names indexed by first_pair): sp_consensus_support_json_ins"""
+    if insertions is not None:
+        ins = np.ascontiguousarray(insertions, INS_DTYPE)
+        base = np.ascontiguousarray(np.asarray(col_base, np.uint64).reshape(-1), np.uint64) if len(entries) else np.zeros(2, np.uint64)
+        names, n_names = _name_array(read_names)
+        render = lambda a, n, out, cap, need: lib().sp_consensus_support_json_ins(a, n, _ptr(base), _ptr(ins) if len(ins) else None, len(ins), names, n_names, out, cap, need)
+    else:
+        render = lib().sp_consensus_support_json
     arr = (sp_support_entry * max(1, len(entries)))()
     keep = []
     for e, (gene, sides) in zip(arr, entries):
@@ -291,11 +322,11 @@ def consensus_support_json(entries):
             e.cols[c] = cols.ctypes.data if len(cols) else None
             e.summary[c] = C.pointer(sm)
     need = C.c_uint64(0)
-    rc = lib().sp_consensus_support_json(arr, len(entries), None, 0, C.byref(need))
+    rc = render(arr, len(entries), None, 0, C.byref(need))
     if rc not in (SP_OK, SP_ERR_CAPACITY):
         raise StarphaseError(rc, "sp_consensus_support_json")
     buf = C.create_string_buffer(need.value)
-    rc = lib().sp_consensus_support_json(arr, len(entries), buf, need.value, C.byref(need))
+    rc = render(arr, len(entries), buf, need.value, C.byref(need))
     if rc != SP_OK:
         raise StarphaseError(rc, "sp_consensus_support_json")
     return buf.value.decode()
@@ -331,6 +362,12 @@ def lib():
         "sp_pileup_batch": (i32, [vp, vp, vp, vp, u64, vp, vp, u32, vp, vp, vp]),
         "sp_align_pileup_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), vp, vp, vp, vp, vp]),
         "sp_align_pileup_band_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, i32, vp, vp, vp, vp, vp, vp]),
+        "sp_pileup_ins_batch": (i32, [vp, vp, vp, vp, u64, vp, vp, u32, vp, vp, vp, u64, C.POINTER(u64)]),
+        "sp_align_pileup_ins_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, i32, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]),
+        "sp_support_ins_string": (i32, [vp, vp, u32, C.c_char_p, u64, C.POINTER(u64)]),
+        "sp_hla_consensus_support_ins": (i32, [vp, vp, u32, vp, vp, vp, C.c_char_p, C.c_char_p, vp, vp, C.POINTER(sp_support_summary), C.POINTER(sp_support_summary), vp, u64, C.POINTER(u64)]),
+        "sp_hla_consensus_support_cohort_ins": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp, C.c_char_p, u32, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]),
+        "sp_consensus_support_json_ins": (i32, [C.POINTER(sp_support_entry), u32, vp, vp, u64, C.POINTER(C.c_char_p), u32, C.c_char_p, u64, C.POINTER(u64)]),
         "sp_support_summarize": (i32, [vp, u32, u32, u32, C.POINTER(sp_support_summary)]),
         "sp_support_contested": (i32, [vp, u32, vp, u32, C.POINTER(u32)]),
         "sp_hla_consensus_support": (i32, [vp, vp, u32, vp, vp, vp, C.c_char_p, C.c_char_p, vp, vp, C.POINTER(sp_support_summary), C.POINTER(sp_support_summary)]),
@@ -428,7 +465,7 @@ def lib():
         raise ImportError(f"{path}: ABI version {L.sp_abi_version()}, this binding was written for {SP_ABI_VERSION} (rebuild: __graft_entry__.build())")
     for name, size in (("sp_hla_realign", REALIGN_DTYPE.itemsize), ("sp_aln", ALN_DTYPE.itemsize), ("sp_k1_seed_hit", K1_HIT_DTYPE.itemsize),
                        ("sp_hla_best", C.sizeof(sp_hla_best)), ("sp_hla_realign", C.sizeof(sp_hla_realign)), ("sp_hla_rev_hit", REV_HIT_DTYPE.itemsize),
-                       ("sp_pileup_col", PILEUP_DTYPE.itemsize), ("sp_support_summary", SUPPORT_DTYPE.itemsize)):
+                       ("sp_pileup_col", PILEUP_DTYPE.itemsize), ("sp_support_summary", SUPPORT_DTYPE.itemsize), ("sp_pileup_ins", INS_DTYPE.itemsize)):
         if L.sp_struct_size(name.encode()) != size:
             raise ImportError(f"{path}: {name} is {L.sp_struct_size(name.encode())} bytes in the library, {size} in this binding")
     _lib = L
@@ -529,11 +566,46 @@ class Context:
         self.check(lib().sp_pileup_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), _ptr(aln), _ptr(cigar), cigar.shape[1], _ptr(n_cigar), _ptr(off), _ptr(out)))
         return [out[int(off[t]):int(off[t + 1])] for t in range(B.n)]
 
-    def align_pileup(self, A, B, pairs, a=1, aln=True, cols=True, summaries=True, n_members=None, col_offset=None, band=64, retry_band=0, band_used=False):
+    def _with_ins(self, call, guess):
+        """runs call(ins, cap, byref(n)) with room for `guess` records, once more with the room it asked for -> INS_DTYPE array"""
+        n = C.c_uint64(0)
+        ins = np.zeros(max(1, int(guess)), INS_DTYPE)
+        rc = call(_ptr(ins), len(ins), C.byref(n))
+        if rc == SP_ERR_CAPACITY and n.value > len(ins):
+            ins = np.zeros(n.value, INS_DTYPE)
+            rc = call(_ptr(ins), len(ins), C.byref(n))
+        self.check(rc)
+        return ins[:n.value].copy()
+
+    def pileup_ins(self, A, B, pairs, aln, cigar, n_cigar, col_offset=None, ins_cap=None):
+        """sp_pileup_ins_batch: the arguments of pileup -> INS_DTYPE array, one record per distinct (column, inserted string).  ins_cap: a capacity to try, once
+        -> (status, records or None, n_ins)"""
+        rows = np.zeros(len(pairs), PAIR_DTYPE)
+        for i, pr in enumerate(pairs):
+            rows[i] = (pr[0], pr[1], pr[2], pr[3] if len(pr) > 3 else 0)
+        aln = np.ascontiguousarray(aln, AFFINE_DTYPE)
+        cigar = np.ascontiguousarray(cigar, np.uint32).reshape(len(pairs), -1) if len(pairs) else np.zeros((0, 1), np.uint32)
+        n_cigar = np.ascontiguousarray(n_cigar, np.uint32)
+        if col_offset is None:
+            off = np.zeros(B.n + 1, np.uint64)
+            off[1:] = np.cumsum([int(x) for x in B.lengths])
+        else:
+            off = np.ascontiguousarray(col_offset, np.uint64)
+        call = lambda ins, cap, n: lib().sp_pileup_ins_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), _ptr(aln), _ptr(cigar), cigar.shape[1], _ptr(n_cigar), _ptr(off), ins, cap, n)
+        if ins_cap is not None:
+            n = C.c_uint64(0)
+            ins = np.zeros(max(1, int(ins_cap)), INS_DTYPE)
+            rc = call(_ptr(ins), int(ins_cap), C.byref(n))
+            return rc, (ins[:n.value].copy() if rc == SP_OK else None), n.value
+        return self._with_ins(call, 4096 + 4 * len(pairs))
+
+    def align_pileup(self, A, B, pairs, a=1, aln=True, cols=True, summaries=True, n_members=None, col_offset=None, band=64, retry_band=0, band_used=False, insertions=False,
+                     ins_cap=None):
         """sp_align_pileup_batch: pairs as affine_align takes them -> (aln AFFINE_DTYPE[n] or None, [PILEUP_DTYPE array per target of B] or None,
         [summary dict per target] or None); an output switched off is handed to the library as NULL.  col_offset: None = the one that follows B's lengths.
         band (64 | 256), retry_band (0 | 256 with band 64) or band_used other than the defaults: sp_align_pileup_band_batch; band_used=True adds a fourth item,
-        uint32[n]: 0 for a pair that did not align, else the band its alignment came from"""
+        uint32[n]: 0 for a pair that did not align, else the band its alignment came from.  insertions=True (sp_align_pileup_ins_batch) adds the INS_DTYPE records
+        as the last item; with ins_cap, a capacity to try once, the last item is (status, records or None, n_ins) instead"""
         rows = np.zeros(len(pairs), PAIR_DTYPE)
         for i, pr in enumerate(pairs):
             rows[i] = (pr[0], pr[1], pr[2], pr[3] if len(pr) > 3 else 0)
@@ -548,14 +620,28 @@ class Context:
         mem = np.ascontiguousarray(n_members, np.uint32) if n_members is not None else None
         op = sp_affine_opts(a, 4, 6, 2, 26, 1, 1)
         used = np.zeros(max(1, len(pairs)), np.uint32) if band_used else None
-        if int(band) == 64 and int(retry_band) == 0 and not band_used:
+        ins_out = None
+        if insertions:
+            call = lambda ins, cap, n: lib().sp_align_pileup_ins_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), int(band), int(retry_band), _ptr(off), _ptr(out),
+                                                                       _ptr(table), _ptr(sm), _ptr(mem), _ptr(used), ins, cap, n)
+            if ins_cap is not None:
+                n = C.c_uint64(0)
+                ins = np.zeros(max(1, int(ins_cap)), INS_DTYPE)
+                rc = call(_ptr(ins), int(ins_cap), C.byref(n))
+                if rc not in (SP_OK, SP_ERR_CAPACITY):
+                    self.check(rc)
+                ins_out = (rc, (ins[:n.value].copy() if rc == SP_OK else None), n.value)
+            else:
+                ins_out = self._with_ins(call, 4096 + 4 * len(pairs))
+        elif int(band) == 64 and int(retry_band) == 0 and not band_used:
             self.check(lib().sp_align_pileup_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), _ptr(off), _ptr(out), _ptr(table), _ptr(sm), _ptr(mem)))
         else:
             self.check(lib().sp_align_pileup_band_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), int(band), int(retry_band), _ptr(off), _ptr(out), _ptr(table),
                                                         _ptr(sm), _ptr(mem), _ptr(used)))
         res = (out, [table[int(off[t]):int(off[t + 1])] for t in range(B.n)] if cols else None,
                [{n: int(sm[t][n]) for n in SUPPORT_FIELDS[:-1]} for t in range(B.n)] if summaries else None)
-        return res + (used[:len(pairs)],) if band_used else res
+        res = res + (used[:len(pairs)],) if band_used else res
+        return res + (ins_out,) if insertions else res
 
     def hla_config_extend(self, reference, alleles, db=None, batch_alleles=0):
         """sp_hla_config_extend: HlaConfig::new on the device -- reference = database.Fasta, alleles = database.HlaAlleles, db = database.Database whose hla_config
@@ -1404,19 +1490,26 @@ class HlaDb:
         self.ctx.check(lib().sp_hla_diplotype_gene(self.ctx._h, self._h, int(gene), reads._h, _ptr(realign), C.byref(cfg), C.byref(call), c1, c2, cap, _ptr(is1)))
         return call, c1.value.decode(), c2.value.decode(), is1[(realign["status"] == 0) & (realign["gene"] == gene)].astype(bool)
 
-    def consensus_support(self, gene, reads, realign, is_cons1, cons1, cons2):
+    def consensus_support(self, gene, reads, realign, is_cons1, cons1, cons2, insertions=False):
         """sp_hla_consensus_support: is_cons1 per read of `reads` (as diplotype_genes returns it), cons1 / cons2 the hg38-forward consensuses of the call
-        -> ((cols1 PILEUP_DTYPE, summary1 dict), (cols2, summary2)) in gene-strand coordinates"""
+        -> ((cols1 PILEUP_DTYPE, summary1 dict), (cols2, summary2)) in gene-strand coordinates.  insertions=True (sp_hla_consensus_support_ins) adds a third item: the
+        INS_DTYPE records, consensus 1's columns from 0, consensus 2's from len(cons1)"""
         realign = np.ascontiguousarray(realign)
         is1 = np.ascontiguousarray(is_cons1, np.uint8)
         cols = [np.zeros(len(cons1), PILEUP_DTYPE), np.zeros(len(cons2), PILEUP_DTYPE)]
         sm = [sp_support_summary(), sp_support_summary()]
+        if insertions:
+            ins = self.ctx._with_ins(lambda ins, cap, n: lib().sp_hla_consensus_support_ins(
+                self.ctx._h, self._h, int(gene), reads._h, _ptr(realign), _ptr(is1), cons1.encode(), cons2.encode(), cols[0].ctypes.data, cols[1].ctypes.data,
+                C.byref(sm[0]), C.byref(sm[1]), ins, cap, n), 16384)
+            return tuple((cols[c], {n: int(getattr(sm[c], n)) for n in SUPPORT_FIELDS[:-1]}) for c in range(2)) + (ins,)
         self.ctx.check(lib().sp_hla_consensus_support(self.ctx._h, self._h, int(gene), reads._h, _ptr(realign), _ptr(is1), cons1.encode(), cons2.encode(),
                                                       cols[0].ctypes.data, cols[1].ctypes.data, C.byref(sm[0]), C.byref(sm[1])))
         return tuple((cols[c], {n: int(getattr(sm[c], n)) for n in SUPPORT_FIELDS[:-1]}) for c in range(2))
 
-    def consensus_support_cohort(self, n_samples, read_sample, genes, reads, realign, is_cons1, cons, unit_on=None):
-        """sp_hla_consensus_support_cohort: cons[sample][gene] = (consensus1, consensus2), hg38 forward -> out[sample][gene] = ((cols1, summary1), (cols2, summary2))"""
+    def consensus_support_cohort(self, n_samples, read_sample, genes, reads, realign, is_cons1, cons, unit_on=None, insertions=False):
+        """sp_hla_consensus_support_cohort: cons[sample][gene] = (consensus1, consensus2), hg38 forward -> out[sample][gene] = ((cols1, summary1), (cols2, summary2)).
+        insertions=True (sp_hla_consensus_support_cohort_ins): -> (that, INS_DTYPE records, col_offset uint64[2 * n_samples * n_genes + 1])"""
         k = len(genes)
         g = np.ascontiguousarray(genes, np.uint32)
         rs = np.ascontiguousarray(read_sample, np.uint32) if read_sample is not None else None
@@ -1430,10 +1523,16 @@ class HlaDb:
         total = sum(len(x) for x in flat)
         cols = np.zeros(max(1, total), PILEUP_DTYPE)
         sm = np.zeros(len(flat), SUPPORT_DTYPE)
-        self.ctx.check(lib().sp_hla_consensus_support_cohort(self.ctx._h, self._h, n_samples, _ptr(rs), k, _ptr(g), reads._h, _ptr(realign), _ptr(is1), buf, cap,
-                                                             _ptr(on), _ptr(off), _ptr(cols), total, _ptr(sm)))
+        ins = None
+        if insertions:
+            ins = self.ctx._with_ins(lambda ins, icap, n: lib().sp_hla_consensus_support_cohort_ins(
+                self.ctx._h, self._h, n_samples, _ptr(rs), k, _ptr(g), reads._h, _ptr(realign), _ptr(is1), buf, cap, _ptr(on), _ptr(off), _ptr(cols), total, _ptr(sm), ins, icap, n), 16384)
+        else:
+            self.ctx.check(lib().sp_hla_consensus_support_cohort(self.ctx._h, self._h, n_samples, _ptr(rs), k, _ptr(g), reads._h, _ptr(realign), _ptr(is1), buf, cap,
+                                                                 _ptr(on), _ptr(off), _ptr(cols), total, _ptr(sm)))
         side = lambda x: (cols[int(off[x]):int(off[x + 1])].copy(), {n: int(sm[x][n]) for n in SUPPORT_FIELDS[:-1]})
-        return [[(side(2 * (s * k + i)), side(2 * (s * k + i) + 1)) for i in range(k)] for s in range(n_samples)]
+        res = [[(side(2 * (s * k + i)), side(2 * (s * k + i) + 1)) for i in range(k)] for s in range(n_samples)]
+        return (res, ins, off.copy()) if insertions else res
 
     def diplotype_genes(self, genes, reads, realign, cfgs=None, cap=65536):
         """sp_hla_diplotype_genes -> list of (sp_hla_call, consensus1, consensus2) per gene, and is_consensus1 per read"""
