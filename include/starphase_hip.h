@@ -335,6 +335,62 @@ int32_t sp_align_pileup_ins_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqs
  * align on 64 diagonals, where a run of more than 64 bases does not fit -- only the HLA pass's second try on 256 can list one.) */
 int32_t sp_support_ins_string(const sp_pileup_ins* rec, const sp_seqset* queries, uint32_t query, char* out, uint64_t cap, uint64_t* needed);
 
+/* ------------------------------------------------------------------ read haplotypes: WHICH reads disagree together at the contested columns
+ * The counts of two contested columns cannot say whether their mismatches sit in the same reads (two haplotypes collapsed into one consensus) or are scattered over
+ * the reads (noise).  This list can: it is the pile sorted by the reads' calls at the contested columns, what a person does in IGV with "sort by base".
+ * Columns used: for target t, c_0 < c_1 < ... < c_{K'-1} are its contested columns by the rule of sp_support_contested over the FINISHED table (all pairs of the batch,
+ * all slices); the first K = min(K', SP_SUPPORT_HAP_COLS) of them are used.  K' is reported (n_cols_total), so a cut is visible.
+ * The call of an aligned pair (n_cigar > 0; in sp_align_pileup_hap_batch also score > 0 -- the pairs the table counts) at column j of its target is a 4-bit code:
+ *   low 3 bits  0 the alignment does not cover j (j outside [b_start, b_end));  1 an '=' op;  2 + c an 'X' op whose query base has the 2-bit code c, exactly as
+ *               sp_pileup_col.x[c] counts it (a base outside ACGT is code 0: call 2);  6 a 'D' op
+ *   bit 3       set when an 'I' run of that alignment sits directly behind column j -- the run that sp_pileup_col.ins of j counts
+ * The pattern of a pair is its K calls packed into w[4]: call k in bits [4 (k mod 16), 4 (k mod 16) + 4) of w[k / 16]; unused bits are zero.
+ * One sp_support_hap record per distinct (target, pattern) over the aligned pairs that name the target:
+ *   target      the target (in the support calls: the slot of the caller's col_offset)      n_cols   K
+ *   count       aligned pairs with this pattern                                              first_pair  the lowest pair index among them
+ * Order: target ascending, then count descending, then the 256-bit pattern ascending with w[3] most significant.  A target with K' = 0, or with no aligned pair, has
+ * no records.  One sp_support_hap_head per target: its records are haps[first_record .. first_record + n_records), n_cols = K, n_cols_total = K'.
+ * Invariants: for a target with K > 0 the counts of its records sum to the aligned pairs naming it (n_aligned of its summary) -- the all-zero pattern of the pairs that
+ * span none of the columns is a record like any other; for every used column c_k the counts summed over the records whose call k has low bits 1 / 2 + c / 6 equal that
+ * column's eq / x[c] / del, and over the records with bit 3 set its ins.  The list does not depend on the order of the pairs or on launch geometry, except that
+ * first_pair follows the caller's indices.
+ * Kernels: one workgroup per target lists the first SP_SUPPORT_HAP_COLS contested columns of the finished table (on the device: no host round
+ * trip between pileup, list and patterns); one wave per aligned pair stages its target's list in LDS, walks its op row 64 ops at a time (the prefix sums of the pileup
+ * kernel), finds the listed columns inside each op's run by binary search and ORs the calls into the pair's pattern in LDS (a column is covered by at most one non-'I'
+ * op of an alignment, so the order of the ORs cannot matter); query bases are read for 'X' ops only; the pattern leaves with a plain store.  One workgroup per target
+ * then sorts its (pattern, pair) keys on that total order -- a bitonic network in LDS; a target with more than SP_SUPPORT_HAP_LDS_KEYS pairs sorts in its slice of a
+ * pooled buffer, same code, same result --, run-length compacts them, sorts the records into the order above; a pack pass writes the list and the heads.  No global
+ * atomics.  Pooled buffers only.
+ * sp_pileup_hap_batch: the list over host op rows -- arguments and checks of sp_pileup_batch.  sp_align_pileup_hap_batch: sp_align_pileup_ins_batch that also makes this
+ * list; haps == NULL is that call, nothing else is launched and no further pool memory is taken.  With haps, a batch of more than SP_ALIGN_PILEUP_SLICE pairs keeps
+ * the op rows of every slice (the contested set is known only after the last one): the op buffer then holds the batch's rows, nothing is aligned twice.
+ * haps holds hap_cap records; *n_haps = the number there are; heads: one per target of B.  SP_ERR_CAPACITY when n_haps > hap_cap: every other output is complete, haps
+ * and heads are not written.  n_haps and heads must be given with haps. */
+#define SP_SUPPORT_HAP_COLS     64
+#define SP_SUPPORT_HAP_LDS_KEYS 1024
+typedef struct {
+    uint64_t target;
+    uint32_t n_cols, count;
+    uint32_t first_pair, reserved_;
+    uint64_t w[4];
+} sp_support_hap;        /* 56 bytes */
+typedef struct {
+    uint64_t first_record;
+    uint32_t n_records, n_cols;
+    uint32_t n_cols_total, reserved_;
+} sp_support_hap_head;   /* 24 bytes */
+int32_t sp_pileup_hap_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
+                            const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset,
+                            sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads);
+int32_t sp_align_pileup_hap_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts,
+                                  int32_t band, int32_t retry_band, const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols,
+                                  sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
+                                  sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
+                                  sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads);
+/* A pattern as text (host only): one token per used column -- '=' a match, 'A' 'C' 'G' 'T' a mismatch with that base, '-' a deletion, '?' not covered -- each followed
+ * by '+' when bit 3 is set (a low code of 7 is written '?').  out / cap / needed as sp_support_ins_string; SP_ERR_INVALID_ARG for n_cols > SP_SUPPORT_HAP_COLS. */
+int32_t sp_support_hap_string(const sp_support_hap* rec, char* out, uint64_t cap, uint64_t* needed);
+
 /* ------------------------------------------------------------------ HLA database
  * Replaces HlaRealigner::new + create_hla_fasta (src/hla/realigner.rs:42-91,497-526) and the per-call
  * one-sequence indexes of score_read (src/hla/caller.rs:1370-1379).
@@ -775,6 +831,25 @@ int32_t sp_cyp_consensus_support_cohort_ins(sp_ctx* ctx, uint32_t n_samples, con
 int32_t sp_cyp_support_json_ins(const sp_cyp_call* call, const char* consensus, uint32_t cons_cap, const uint64_t* col_offset, const sp_pileup_col* cols,
                                 const sp_support_summary* summaries, const sp_pileup_ins* ins, uint64_t n_ins, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
                                 const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed);
+/* The _ins forms with the haplotype list of sp_align_pileup_hap_batch as well (haps / hap_cap / n_haps / heads as there; haps == NULL is the _ins form: nothing else is
+ * launched).  target is the consensus' slot of col_offset (h for the single call, sample * SP_CYP_MAXCONS + h for the cohort); heads: one per slot (n_consensus for the
+ * single call, n_samples * SP_CYP_MAXCONS for the cohort), an unused slot's is empty; first_pair is the index of the member's record in `mappings`.  Either list may be
+ * asked for without the other; SP_ERR_CAPACITY names the list that did not fit by its count (n_ins > ins_cap, n_haps > hap_cap), the other one is complete.
+ * sp_cyp_support_json_hap: sp_cyp_support_json_ins with a list: consensus h is target target0 + h of it, its head heads[target0 + h] (target0 = 0 for the list of the
+ * single call, sample * SP_CYP_MAXCONS for a sample of the cohort call): a region whose head has n_cols > 0 and records gains
+ * "haplotypes" as sp_consensus_support_json_hap writes it, behind "contested"; haps == NULL or n_haps == 0: the bytes of sp_cyp_support_json_ins. */
+int32_t sp_cyp_consensus_support_hap(sp_ctx* ctx, const sp_seqset* reads, const sp_cyp_call* call, const char* consensus, uint32_t cons_cap,
+                                     const sp_cyp_read_mapping* mappings, uint64_t n_mappings, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                                     sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
+                                     sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads);
+int32_t sp_cyp_consensus_support_cohort_hap(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
+                                            const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                                            sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
+                                            sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads);
+int32_t sp_cyp_support_json_hap(const sp_cyp_call* call, const char* consensus, uint32_t cons_cap, const uint64_t* col_offset, const sp_pileup_col* cols,
+                                const sp_support_summary* summaries, const sp_pileup_ins* ins, uint64_t n_ins, const sp_support_hap* haps, uint64_t n_haps,
+                                const sp_support_hap_head* heads, uint64_t target0, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
+                                const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed);
 
 /* ------------------------------------------------------------------ CYP2D6 templates and typing tables
  * Replaces generate_cyp_hybrids (src/cyp2d6/definitions.rs:346-464), LoadedVariants::load_variant_database
@@ -1118,6 +1193,26 @@ int32_t sp_hla_consensus_support_cohort_ins(sp_ctx* ctx, const sp_hla_db* db, ui
                                             const uint8_t* unit_on, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries,
                                             sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins);
 int32_t sp_consensus_support_json_ins(const sp_support_entry* entries, uint32_t n_entries, const uint64_t* col_base, const sp_pileup_ins* ins, uint64_t n_ins,
+                                      const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed);
+/* The _ins forms with the haplotype list of sp_align_pileup_hap_batch as well (haps / hap_cap / n_haps / heads as there; haps == NULL is the _ins form: nothing else is
+ * launched).  target is numbered as the columns are: sp_hla_consensus_support_hap gives consensus 1 target 0 and consensus 2 target 1 (heads: 2); the cohort form uses the
+ * slot of its col_offset, 2 * unit + consensus (heads: one per slot, an unused slot's is empty).  first_pair is the index of the member READ in `reads`.  Calls are on the
+ * gene strand, as the columns are.  Either list may be asked for without the other; SP_ERR_CAPACITY names the list that did not fit by its count, the other is complete.
+ * sp_consensus_support_json_hap: sp_consensus_support_json_ins with a list.  hap_target: 2 per entry, the target of consensus c of entry e at hap_target[2 e + c];
+ * heads: n_heads records indexed by target.  A consensus whose head has n_cols > 0 and records gains, behind "contested",
+ *     "haplotypes": {"columns": [pos, ...], "columns_total": K', "patterns": [{"count": n, "calls": "...", "first_read": "QNAME"}, ...], "more": n}
+ * -- columns: the n_cols used positions; patterns: the records in record order, at most 16, calls as sp_support_hap_string writes them; "more": the number of reads in
+ * the patterns left out, only when there are any; "first_read" only when read_names (indexed by first_pair) is given.  haps == NULL or n_haps == 0: the bytes of
+ * sp_consensus_support_json_ins. */
+int32_t sp_hla_consensus_support_hap(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1,
+                                     const char* cons1, const char* cons2, sp_pileup_col* cols1, sp_pileup_col* cols2, sp_support_summary* s1, sp_support_summary* s2,
+                                     sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins, sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads);
+int32_t sp_hla_consensus_support_cohort_hap(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
+                                            const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1, const char* cons, uint32_t cap,
+                                            const uint8_t* unit_on, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries,
+                                            sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins, sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads);
+int32_t sp_consensus_support_json_hap(const sp_support_entry* entries, uint32_t n_entries, const uint64_t* col_base, const sp_pileup_ins* ins, uint64_t n_ins,
+                                      const sp_support_hap* haps, uint64_t n_haps, const sp_support_hap_head* heads, uint64_t n_heads, const uint64_t* hap_target,
                                       const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed);
 
 /* ------------------------------------------------------------------ host-side decisions of the path (no device work)
@@ -1527,6 +1622,12 @@ int32_t sp_starphase_set_cyp_consensus_support(sp_starphase* handle, int32_t on)
  * Off: no further launch, no further pool memory, every output the same bytes as on a handle that was never told; on: every output but those two files the same bytes,
  * and a sample's file in a batch equals its single call's file. */
 int32_t sp_starphase_set_support_insertions(sp_starphase* handle, int32_t on);
+/* The same rule for the haplotype list: a switch of its own, off by default, with effect only where one of the two support switches writes its file.  The support pass
+ * of that file also makes the list (sp_hla_consensus_support_cohort_hap / sp_cyp_consensus_support_cohort_hap: the same one pass per batch group, with the insertion
+ * list only when that switch is on as well) and the file is rendered with it (sp_consensus_support_json_hap / sp_cyp_support_json_hap, without first_read): every
+ * consensus or region whose list has columns and records gains "haplotypes".  Off: no further launch, no further pool memory, every output the same bytes as on a
+ * handle that was never told; on: every output but those two files the same bytes, and a sample's file in a batch equals its single call's file. */
+int32_t sp_starphase_set_support_haplotypes(sp_starphase* handle, int32_t on);
 const char* sp_starphase_warnings(const sp_starphase* handle);      /* the warnings of the last call, one per line */
 /* where the last call spent its time (wall ms): whole call, BAM decode (host, both loci), variant genes, HLA lane, CYP2D6 lane */
 typedef struct { double call_ms, bam_decode_ms, variant_ms, hla_ms, cyp_ms; uint32_t n_hla_reads, n_cyp_reads; } sp_starphase_timing;

@@ -20,6 +20,8 @@ pub const SP_ALIGN_PILEUP_SLICE: i64 = 4096;
 pub const SP_SUPPORT_HIST_BINS: i64 = 1024;
 pub const SP_ALIGN_PILEUP_WIDE_ROWS: i64 = 128;
 pub const SP_PILEUP_INS_LDS_RUNS: i64 = 1024;
+pub const SP_SUPPORT_HAP_COLS: i64 = 64;
+pub const SP_SUPPORT_HAP_LDS_KEYS: i64 = 1024;
 pub const SP_K1_SEL: i64 = 16;
 pub const SP_MAX_CHAIN: i64 = 64;
 pub const SP_CYP_MAXCONS: i64 = 64;
@@ -101,6 +103,23 @@ pub struct sp_pileup_ins {
     pub first_pair: u32,
     pub first_qpos: u32,
     pub n_other: u32,
+    pub reserved_: u32,
+}
+#[repr(C)]
+pub struct sp_support_hap {
+    pub target: u64,
+    pub n_cols: u32,
+    pub count: u32,
+    pub first_pair: u32,
+    pub reserved_: u32,
+    pub w: [u64; 4],
+}
+#[repr(C)]
+pub struct sp_support_hap_head {
+    pub first_record: u64,
+    pub n_records: u32,
+    pub n_cols: u32,
+    pub n_cols_total: u32,
     pub reserved_: u32,
 }
 #[repr(C)]
@@ -786,6 +805,9 @@ extern "C" {
     pub fn sp_pileup_ins_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, aln: *const sp_affine_aln, cigar: *const u32, cigar_stride: u32, n_cigar: *const u32, col_offset: *const u64, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64) -> i32;
     pub fn sp_align_pileup_ins_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, band: i32, retry_band: i32, col_offset: *const u64, aln: *mut sp_affine_aln, cols: *mut sp_pileup_col, summaries: *mut sp_support_summary, n_members: *const u32, band_used: *mut u32, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64) -> i32;
     pub fn sp_support_ins_string(rec: *const sp_pileup_ins, queries: *const sp_seqset, query: u32, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
+    pub fn sp_pileup_hap_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, aln: *const sp_affine_aln, cigar: *const u32, cigar_stride: u32, n_cigar: *const u32, col_offset: *const u64, haps: *mut sp_support_hap, hap_cap: u64, n_haps: *mut u64, heads: *mut sp_support_hap_head) -> i32;
+    pub fn sp_align_pileup_hap_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, band: i32, retry_band: i32, col_offset: *const u64, aln: *mut sp_affine_aln, cols: *mut sp_pileup_col, summaries: *mut sp_support_summary, n_members: *const u32, band_used: *mut u32, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64, haps: *mut sp_support_hap, hap_cap: u64, n_haps: *mut u64, heads: *mut sp_support_hap_head) -> i32;
+    pub fn sp_support_hap_string(rec: *const sp_support_hap, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
     pub fn sp_hla_db_create(ctx: *mut sp_ctx, desc: *const sp_hla_db_desc, out: *mut *mut sp_hla_db) -> i32;
     pub fn sp_hla_db_free(db: *mut sp_hla_db);
     pub fn sp_hla_seed_index_info(ctx: *mut sp_ctx, db: *const sp_hla_db, out: *mut i64) -> i32;
@@ -825,6 +847,9 @@ extern "C" {
     pub fn sp_cyp_consensus_support_ins(ctx: *mut sp_ctx, reads: *const sp_seqset, call: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, mappings: *const sp_cyp_read_mapping, n_mappings: u64, col_offset: *mut u64, cols: *mut sp_pileup_col, cols_cap: u64, summaries: *mut sp_support_summary, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64) -> i32;
     pub fn sp_cyp_consensus_support_cohort_ins(ctx: *mut sp_ctx, n_samples: u32, reads: *const *const sp_seqset, calls: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, mappings: *const sp_cyp_read_mapping, mapping_off: *const u64, col_offset: *mut u64, cols: *mut sp_pileup_col, cols_cap: u64, summaries: *mut sp_support_summary, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64) -> i32;
     pub fn sp_cyp_support_json_ins(call: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, col_offset: *const u64, cols: *const sp_pileup_col, summaries: *const sp_support_summary, ins: *const sp_pileup_ins, n_ins: u64, mappings: *const sp_cyp_read_mapping, n_mappings: u64, read_names: *const *const c_char, n_read_names: u32, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
+    pub fn sp_cyp_consensus_support_hap(ctx: *mut sp_ctx, reads: *const sp_seqset, call: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, mappings: *const sp_cyp_read_mapping, n_mappings: u64, col_offset: *mut u64, cols: *mut sp_pileup_col, cols_cap: u64, summaries: *mut sp_support_summary, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64, haps: *mut sp_support_hap, hap_cap: u64, n_haps: *mut u64, heads: *mut sp_support_hap_head) -> i32;
+    pub fn sp_cyp_consensus_support_cohort_hap(ctx: *mut sp_ctx, n_samples: u32, reads: *const *const sp_seqset, calls: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, mappings: *const sp_cyp_read_mapping, mapping_off: *const u64, col_offset: *mut u64, cols: *mut sp_pileup_col, cols_cap: u64, summaries: *mut sp_support_summary, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64, haps: *mut sp_support_hap, hap_cap: u64, n_haps: *mut u64, heads: *mut sp_support_hap_head) -> i32;
+    pub fn sp_cyp_support_json_hap(call: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, col_offset: *const u64, cols: *const sp_pileup_col, summaries: *const sp_support_summary, ins: *const sp_pileup_ins, n_ins: u64, haps: *const sp_support_hap, n_haps: u64, heads: *const sp_support_hap_head, target0: u64, mappings: *const sp_cyp_read_mapping, n_mappings: u64, read_names: *const *const c_char, n_read_names: u32, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
     pub fn sp_cyp_db_create(ctx: *mut sp_ctx, locus: *const sp_cyp_locus, gene_def: *const sp_cyp_gene_def, config: *const sp_cyp_config, out: *mut *mut sp_cyp_db) -> i32;
     pub fn sp_cyp_db_free(db: *mut sp_cyp_db);
     pub fn sp_cyp_db_info(db: *const sp_cyp_db, stats: *mut sp_cyp_db_stats) -> i32;
@@ -855,6 +880,9 @@ extern "C" {
     pub fn sp_hla_consensus_support_ins(ctx: *mut sp_ctx, db: *const sp_hla_db, gene: u32, reads: *const sp_seqset, realign: *const sp_hla_realign, is_cons1: *const u8, cons1: *const c_char, cons2: *const c_char, cols1: *mut sp_pileup_col, cols2: *mut sp_pileup_col, s1: *mut sp_support_summary, s2: *mut sp_support_summary, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64) -> i32;
     pub fn sp_hla_consensus_support_cohort_ins(ctx: *mut sp_ctx, db: *const sp_hla_db, n_samples: u32, read_sample: *const u32, n_genes: u32, genes: *const u32, reads: *const sp_seqset, realign: *const sp_hla_realign, is_cons1: *const u8, cons: *const c_char, cap: u32, unit_on: *const u8, col_offset: *mut u64, cols: *mut sp_pileup_col, cols_cap: u64, summaries: *mut sp_support_summary, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64) -> i32;
     pub fn sp_consensus_support_json_ins(entries: *const sp_support_entry, n_entries: u32, col_base: *const u64, ins: *const sp_pileup_ins, n_ins: u64, read_names: *const *const c_char, n_read_names: u32, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
+    pub fn sp_hla_consensus_support_hap(ctx: *mut sp_ctx, db: *const sp_hla_db, gene: u32, reads: *const sp_seqset, realign: *const sp_hla_realign, is_cons1: *const u8, cons1: *const c_char, cons2: *const c_char, cols1: *mut sp_pileup_col, cols2: *mut sp_pileup_col, s1: *mut sp_support_summary, s2: *mut sp_support_summary, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64, haps: *mut sp_support_hap, hap_cap: u64, n_haps: *mut u64, heads: *mut sp_support_hap_head) -> i32;
+    pub fn sp_hla_consensus_support_cohort_hap(ctx: *mut sp_ctx, db: *const sp_hla_db, n_samples: u32, read_sample: *const u32, n_genes: u32, genes: *const u32, reads: *const sp_seqset, realign: *const sp_hla_realign, is_cons1: *const u8, cons: *const c_char, cap: u32, unit_on: *const u8, col_offset: *mut u64, cols: *mut sp_pileup_col, cols_cap: u64, summaries: *mut sp_support_summary, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64, haps: *mut sp_support_hap, hap_cap: u64, n_haps: *mut u64, heads: *mut sp_support_hap_head) -> i32;
+    pub fn sp_consensus_support_json_hap(entries: *const sp_support_entry, n_entries: u32, col_base: *const u64, ins: *const sp_pileup_ins, n_ins: u64, haps: *const sp_support_hap, n_haps: u64, heads: *const sp_support_hap_head, n_heads: u64, hap_target: *const u64, read_names: *const *const c_char, n_read_names: u32, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
     pub fn sp_hla_is_passing_dual(counts1: u64, counts2: u64, min_consensus_fraction: f64, expected_maf: f64, min_cdf: f64, maf_out: *mut f64, cdf_out: *mut f64) -> i32;
     pub fn sp_hla_is_hemizygous_better(scores1: *const i64, scores2: *const i64, is_consensus1: *const u8, n_reads: u32, is_dual: i32, dual_max_ed_delta: u64, normalized_coverage: f64, haploid_cost: *mut f64, diploid_cost: *mut f64) -> i32;
     pub fn sp_hla_normalized_coverage(realign: *const sp_hla_realign, n_reads: u32, normalizing_genes: *const u32, n_normalizing: u32, normalized_coverage: *mut f64) -> i32;
@@ -956,6 +984,7 @@ extern "C" {
     pub fn sp_starphase_set_consensus_support(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_cyp_consensus_support(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_support_insertions(handle: *mut sp_starphase, on: i32) -> i32;
+    pub fn sp_starphase_set_support_haplotypes(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_warnings(handle: *const sp_starphase) -> *const c_char;
     pub fn sp_starphase_last_timing(handle: *const sp_starphase, out: *mut sp_starphase_timing) -> i32;
     pub fn sp_starphase_call_batch(handle: *mut sp_starphase, n: u32, inputs: *const sp_sample_inputs, debug_folders: *const *const c_char, opts: *const sp_batch_options, out: *mut *mut sp_result, sample_rc: *mut i32) -> i32;

@@ -185,6 +185,8 @@ int32_t sp_struct_size(const char* name) {
     SP_SZ(sp_support_summary)
     SP_SZ(sp_support_entry)
     SP_SZ(sp_pileup_ins)
+    SP_SZ(sp_support_hap)
+    SP_SZ(sp_support_hap_head)
 #undef SP_SZ
     return -1;
 }

@@ -2334,9 +2334,18 @@ extern "C" int32_t sp_cyp_consensus_support_cohort(sp_ctx* ctx, uint32_t n_sampl
 extern "C" int32_t sp_cyp_consensus_support_cohort_ins(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
                                                        const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
                                                        sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
+    return sp_cyp_consensus_support_cohort_hap(ctx, n_samples, reads, calls, consensus, cons_cap, mappings, mapping_off, col_offset, cols, cols_cap, summaries, ins, ins_cap, n_ins,
+                                               nullptr, 0, nullptr, nullptr);
+}
+
+extern "C" int32_t sp_cyp_consensus_support_cohort_hap(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
+                                                       const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                                                       sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
+                                                       sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
     if (!ctx) return SP_ERR_INVALID_ARG;
-    if (ins && !n_ins) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: null argument");
+    if ((ins && !n_ins) || (haps && (!n_haps || !heads))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: null argument");
     if (ins) *n_ins = 0;
+    if (haps) *n_haps = 0;
     if (!reads || !calls || !mapping_off || !col_offset || !summaries || n_samples == 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: null argument");
     const uint64_t n_slots = (uint64_t)n_samples * SP_CYP_MAXCONS;
     // ---- the targets: every non-empty consensus of a call that succeeded, as the call returned it
@@ -2360,7 +2369,7 @@ extern "C" int32_t sp_cyp_consensus_support_cohort_ins(sp_ctx* ctx, uint32_t n_s
     std::memset(summaries, 0, sizeof(sp_support_summary) * n_slots);
     if (cols && n_cols > cols_cap) return sp_fail(ctx, SP_ERR_CAPACITY, "cyp consensus support: " + std::to_string(n_cols) + " columns, room for " + std::to_string(cols_cap));
     const uint32_t n_t = (uint32_t)toff.size() - 1;
-    if (n_t == 0) return SP_OK;
+    if (n_t == 0) { if (haps) std::memset(heads, 0, sizeof(sp_support_hap_head) * n_slots); return SP_OK; }
     // ---- the members: one per mapping record whose consensus is a target
     std::vector<uint32_t> m_target, members_of(n_t, 0);
     std::vector<uint64_t> m_record;                                      // the member's record in `mappings`
@@ -2402,17 +2411,20 @@ extern "C" int32_t sp_cyp_consensus_support_cohort_ins(sp_ctx* ctx, uint32_t n_s
     std::vector<uint64_t> t_cols(toff);
     std::vector<sp_pileup_col> table(cols ? n_cols : 0);
     std::vector<sp_support_summary> sm(n_t);
-    if (ins) rc = sp_align_pileup_ins_batch(ctx, &Q, &T, pairs.data(), n_m, &ao, 64, 0, t_cols.data(), nullptr, cols ? table.data() : nullptr, sm.data(), members_of.data(), nullptr, ins, ins_cap, n_ins);
+    std::vector<sp_support_hap_head> t_heads(haps ? n_t : 0);
+    if (haps) rc = sp_align_pileup_hap_batch(ctx, &Q, &T, pairs.data(), n_m, &ao, 64, 0, t_cols.data(), nullptr, cols ? table.data() : nullptr, sm.data(), members_of.data(), nullptr, ins, ins_cap, n_ins,
+                                             haps, hap_cap, n_haps, t_heads.data());
+    else if (ins) rc = sp_align_pileup_ins_batch(ctx, &Q, &T, pairs.data(), n_m, &ao, 64, 0, t_cols.data(), nullptr, cols ? table.data() : nullptr, sm.data(), members_of.data(), nullptr, ins, ins_cap, n_ins);
     else rc = sp_align_pileup_batch(ctx, &Q, &T, pairs.data(), n_m, &ao, t_cols.data(), nullptr, cols ? table.data() : nullptr, sm.data(), members_of.data());
-    if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ins && *n_ins > ins_cap)) return rc;
+    if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ((ins && *n_ins > ins_cap) || (haps && *n_haps > hap_cap)))) return rc;
     for (uint64_t x = 0; x < n_slots; ++x) {
         const int32_t t = target_of[x];
         if (t < 0) continue;
         summaries[x] = sm[t];
         if (cols) std::memcpy(cols + col_offset[x], table.data() + t_cols[t], sizeof(sp_pileup_col) * (size_t)(t_cols[t + 1] - t_cols[t]));
     }
-    if (rc != SP_OK) return rc;                                          // (the list did not fit: everything else is complete)
-    if (ins && *n_ins) {
+    // (a list that did not fit: everything else is complete, the other list included)
+    if (ins && *n_ins && *n_ins <= ins_cap) {
         // the list in the caller's terms: the targets are the consensuses that have columns, in col_offset's order, so the records stay in order
         std::vector<uint64_t> base(n_t, 0);
         for (uint64_t x = 0; x < n_slots; ++x) if (target_of[x] >= 0) base[target_of[x]] = col_offset[x];
@@ -2422,7 +2434,18 @@ extern "C" int32_t sp_cyp_consensus_support_cohort_ins(sp_ctx* ctx, uint32_t n_s
             if (ins[k].len) ins[k].first_pair = (uint32_t)m_record[ins[k].first_pair];
         }
     }
-    return SP_OK;
+    if (haps && *n_haps <= hap_cap) {
+        // the haplotype list in the caller's terms: target = the slot of col_offset, first_pair = the member's record in `mappings`
+        std::vector<uint64_t> slot_of(n_t, 0);
+        uint64_t at = 0;
+        for (uint64_t x = 0; x < n_slots; ++x) {
+            const int32_t t = target_of[x];
+            if (t >= 0) { slot_of[t] = x; heads[x] = t_heads[t]; at = t_heads[t].first_record + t_heads[t].n_records; }
+            else { heads[x] = sp_support_hap_head{}; heads[x].first_record = at; }
+        }
+        for (uint64_t k = 0; k < *n_haps; ++k) { haps[k].target = slot_of[haps[k].target]; haps[k].first_pair = (uint32_t)m_record[haps[k].first_pair]; }
+    }
+    return rc;
 }
 
 extern "C" int32_t sp_cyp_consensus_support(sp_ctx* ctx, const sp_seqset* reads, const sp_cyp_call* call, const char* consensus, uint32_t cons_cap,
@@ -2434,15 +2457,25 @@ extern "C" int32_t sp_cyp_consensus_support(sp_ctx* ctx, const sp_seqset* reads,
 extern "C" int32_t sp_cyp_consensus_support_ins(sp_ctx* ctx, const sp_seqset* reads, const sp_cyp_call* call, const char* consensus, uint32_t cons_cap,
                                                 const sp_cyp_read_mapping* mappings, uint64_t n_mappings, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
                                                 sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
+    return sp_cyp_consensus_support_hap(ctx, reads, call, consensus, cons_cap, mappings, n_mappings, col_offset, cols, cols_cap, summaries, ins, ins_cap, n_ins, nullptr, 0, nullptr, nullptr);
+}
+
+extern "C" int32_t sp_cyp_consensus_support_hap(sp_ctx* ctx, const sp_seqset* reads, const sp_cyp_call* call, const char* consensus, uint32_t cons_cap,
+                                                const sp_cyp_read_mapping* mappings, uint64_t n_mappings, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                                                sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
+                                                sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
     if (!ctx) return SP_ERR_INVALID_ARG;
     if (!call || !col_offset || !summaries) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: null argument");
     const int32_t H = std::min<int32_t>(std::max<int32_t>(call->n_consensus, 0), SP_CYP_MAXCONS);
     uint64_t off[SP_CYP_MAXCONS + 1] = { 0 }; sp_support_summary sm[SP_CYP_MAXCONS];
     const uint64_t moff[2] = { 0, n_mappings };
-    const int32_t rc = sp_cyp_consensus_support_cohort_ins(ctx, 1, &reads, call, consensus, cons_cap, mappings, moff, off, cols, cols_cap, sm, ins, ins_cap, n_ins);
+    if (haps && !heads) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: null argument");
+    sp_support_hap_head hd[SP_CYP_MAXCONS];
+    const int32_t rc = sp_cyp_consensus_support_cohort_hap(ctx, 1, &reads, call, consensus, cons_cap, mappings, moff, off, cols, cols_cap, sm, ins, ins_cap, n_ins, haps, hap_cap, n_haps, haps ? hd : nullptr);
     std::memcpy(col_offset, off, sizeof(uint64_t) * ((size_t)H + 1));
-    if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ins && n_ins && *n_ins > ins_cap)) return rc;
+    if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ((ins && n_ins && *n_ins > ins_cap) || (haps && n_haps && *n_haps > hap_cap)))) return rc;
     std::memcpy(summaries, sm, sizeof(sp_support_summary) * (size_t)H);
+    if (haps && n_haps && *n_haps <= hap_cap) std::memcpy(heads, hd, sizeof(sp_support_hap_head) * (size_t)H);
     return rc;
 }
 
@@ -2454,7 +2487,14 @@ extern "C" int32_t sp_cyp_support_json(const sp_cyp_call* call, const char* cons
 extern "C" int32_t sp_cyp_support_json_ins(const sp_cyp_call* call, const char* consensus, uint32_t cons_cap, const uint64_t* col_offset, const sp_pileup_col* cols,
                                            const sp_support_summary* summaries, const sp_pileup_ins* ins, uint64_t n_ins, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
                                            const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed) {
-    if (!call || (cap && !out) || (n_ins && !ins)) return SP_ERR_INVALID_ARG;
+    return sp_cyp_support_json_hap(call, consensus, cons_cap, col_offset, cols, summaries, ins, n_ins, nullptr, 0, nullptr, 0, mappings, n_mappings, read_names, n_read_names, out, cap, needed);
+}
+
+extern "C" int32_t sp_cyp_support_json_hap(const sp_cyp_call* call, const char* consensus, uint32_t cons_cap, const uint64_t* col_offset, const sp_pileup_col* cols,
+                                           const sp_support_summary* summaries, const sp_pileup_ins* ins, uint64_t n_ins, const sp_support_hap* haps, uint64_t n_haps,
+                                           const sp_support_hap_head* heads, uint64_t target0, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
+                                           const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed) {
+    if (!call || (cap && !out) || (n_ins && !ins) || (n_haps && (!haps || !heads))) return SP_ERR_INVALID_ARG;
     const int32_t H = call->status == 0 ? std::min<int32_t>(std::max<int32_t>(call->n_consensus, 0), SP_CYP_MAXCONS) : 0;
     if (H > 0 && (!consensus || cons_cap == 0 || !col_offset || !summaries)) return SP_ERR_INVALID_ARG;
     spj::Value root = spj::object();
@@ -2483,6 +2523,7 @@ extern "C" int32_t sp_cyp_support_json_ins(const sp_cyp_call* call, const char* 
             list.arr.push_back(std::move(k));
         }
         v.obj.emplace_back("contested", std::move(list));
+        if (n_haps) spi_support_hap_json(&v, c, sm.length, haps, n_haps, heads + target0 + h, target0 + (uint64_t)h, mappings, n_mappings, mappings ? read_names : nullptr, n_read_names);
         root.obj.emplace_back(std::to_string(h) + "_" + type, std::move(v));
     }
     std::string text;

@@ -119,6 +119,7 @@ struct sp_starphase {
     int32_t read_debug = 0;                          // sp_starphase_set_read_debug: a debug folder also receives read_debug.json
     int32_t consensus_support = 0;                   // sp_starphase_set_consensus_support: a debug folder also receives consensus_support.json
     int32_t support_insertions = 0;                  // sp_starphase_set_support_insertions: those two files also list the inserted strings of their contested columns
+    int32_t support_haplotypes = 0;                  // sp_starphase_set_support_haplotypes: those two files also list the read haplotypes at their contested columns
     int32_t cyp_consensus_support = 0;               // sp_starphase_set_cyp_consensus_support: a debug folder also receives cyp2d6_consensus_support.json
     int32_t hla_debug_mappings = 0;                  // sp_starphase_set_hla_debug_mappings: hla_debug.json carries the mapping of each consensus against every allowed allele
     std::set<std::string> include, exclude; bool has_include = false, has_exclude = false;
@@ -576,7 +577,29 @@ int32_t hla_debug_mappings_add(sp_starphase* h, sp_hla_debug* dbg, const std::st
 
 // consensus_support.json of one sample (sp_starphase_set_consensus_support): the tables of the group's one support pass that belong to this sample.  off / sm are
 // indexed by gene * 2 + consensus; cons holds the sample's hg38-forward consensuses, cap bytes each.  A sample without reads has no view and writes an empty object.
-struct SupportView { const uint64_t* off; const sp_pileup_col* cols; const sp_support_summary* sm; const char* cons; uint32_t cap; const sp_pileup_ins* ins; uint64_t n_ins; };
+struct SupportView { const uint64_t* off; const sp_pileup_col* cols; const sp_support_summary* sm; const char* cons; uint32_t cap; const sp_pileup_ins* ins; uint64_t n_ins;
+                     const sp_support_hap* haps = nullptr; uint64_t n_haps = 0; const sp_support_hap_head* heads = nullptr; uint64_t n_heads = 0, slot0 = 0; };   // slot0: the sample's first slot in the group's pass
+// the lists of a support pass (sp_starphase_set_support_insertions / _haplotypes): each stays empty when it is not asked for
+struct SupportLists { std::vector<sp_pileup_ins> ins; std::vector<sp_support_hap> haps; std::vector<sp_support_hap_head> heads; };
+// a support call that makes the haplotype list, and the insertion list when that is asked for as well: `call(ins, ins_cap, &n_ins, haps, hap_cap, &n_haps, heads)` with
+// room for a guess, again with the room it asked for (each list can ask once)
+template <class F> int32_t support_with_lists(SupportLists& L, bool want_ins, size_t n_heads, F call) {
+    if (want_ins && L.ins.size() < 16384) L.ins.resize(16384);
+    if (L.haps.size() < 16384) L.haps.resize(16384);
+    L.heads.assign(std::max<size_t>(n_heads, 1), sp_support_hap_head{});
+    uint64_t n_i = 0, n_h = 0;
+    int32_t rc = SP_OK;
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        rc = call(want_ins ? L.ins.data() : nullptr, (uint64_t)(want_ins ? L.ins.size() : 0), want_ins ? &n_i : nullptr, L.haps.data(), (uint64_t)L.haps.size(), &n_h, L.heads.data());
+        if (rc != SP_ERR_CAPACITY) break;
+        bool grew = false;
+        if (want_ins && n_i > L.ins.size()) { L.ins.resize((size_t)n_i); grew = true; }
+        if (n_h > L.haps.size()) { L.haps.resize((size_t)n_h); grew = true; }
+        if (!grew) break;
+    }
+    L.ins.resize(rc == SP_OK && want_ins ? (size_t)n_i : 0); L.haps.resize(rc == SP_OK ? (size_t)n_h : 0);
+    return rc;
+}
 // a support call that also makes its insertion list: `call(ins, cap, &n)` with room for a guess, once more with the room it asked for
 template <class F> int32_t support_with_ins(std::vector<sp_pileup_ins>& ins, F call) {
     if (ins.size() < 16384) ins.resize(16384);                       // (0.9 MB; a list that is longer costs the pass a second run)
@@ -590,6 +613,7 @@ int32_t consensus_support_save(sp_starphase* h, const sp_hla_call* calls, const 
     const size_t G = h->hgenes.size();
     std::vector<sp_support_entry> entries; std::vector<std::string> keep; keep.reserve(G * 4);
     std::vector<uint64_t> col_base;                                  // of each entry's two consensuses, in the support pass's column space (the list's)
+    std::vector<uint64_t> hap_target;                                // ... and their slots in the pass (the haplotype list's targets)
     for (size_t g = 0; view && g < G; ++g) {
         if (calls[g].status == 1) continue;
         sp_support_entry en; std::memset(&en, 0, sizeof en);
@@ -611,15 +635,19 @@ int32_t consensus_support_save(sp_starphase* h, const sp_hla_call* calls, const 
         }
         entries.push_back(en);
         col_base.push_back(view->off[g * 2]); col_base.push_back(view->off[g * 2 + 1]);
+        hap_target.push_back(view->slot0 + g * 2); hap_target.push_back(view->slot0 + g * 2 + 1);
     }
     // (the list is the whole group's: a sample none of whose genes has a call has no entry, no column of the list is its own, and its file is the empty object)
     const bool listed = view && view->ins && !entries.empty();
     const sp_pileup_ins* ins = listed ? view->ins : nullptr; const uint64_t n_ins = listed ? view->n_ins : 0;
+    const bool hap_listed = view && view->haps && view->n_haps && !entries.empty();
+    const sp_support_hap* haps = hap_listed ? view->haps : nullptr; const uint64_t n_haps = hap_listed ? view->n_haps : 0;
+    const sp_support_hap_head* heads = hap_listed ? view->heads : nullptr; const uint64_t n_heads = hap_listed ? view->n_heads : 0;
     uint64_t need = 0;
-    int32_t rc = sp_consensus_support_json_ins(entries.data(), (uint32_t)entries.size(), col_base.data(), ins, n_ins, nullptr, 0, nullptr, 0, &need);
+    int32_t rc = sp_consensus_support_json_hap(entries.data(), (uint32_t)entries.size(), col_base.data(), ins, n_ins, haps, n_haps, heads, n_heads, hap_target.data(), nullptr, 0, nullptr, 0, &need);
     if (rc != SP_OK && rc != SP_ERR_CAPACITY) { err = "consensus_support.json: the tables do not fit their consensuses"; return rc; }
     std::string text((size_t)need, '\0');
-    rc = sp_consensus_support_json_ins(entries.data(), (uint32_t)entries.size(), col_base.data(), ins, n_ins, nullptr, 0, &text[0], need, &need);
+    rc = sp_consensus_support_json_hap(entries.data(), (uint32_t)entries.size(), col_base.data(), ins, n_ins, haps, n_haps, heads, n_heads, hap_target.data(), nullptr, 0, &text[0], need, &need);
     if (rc != SP_OK) { err = "consensus_support.json: the tables do not fit their consensuses"; return rc; }
     const std::string path = debug_folder + "/consensus_support.json";
     FILE* f = std::fopen(path.c_str(), "wb");
@@ -750,11 +778,15 @@ void cyp_package(sp_starphase* h, const sp_cyp_problem& pr, const sp_cyp_call& c
 // cyp2d6_consensus_support.json of one sample (sp_starphase_set_cyp_consensus_support): the tables of the group's one support pass that belong to this sample
 // (off: MAXCONS + 1 offsets into cols, sm: MAXCONS summaries, cons: the sample's consensus block).  A failure fails the sample's CYP2D6 entry.
 void cyp_support_save(const sp_cyp_call& call, const char* cons, uint32_t cons_cap, const uint64_t* off, const sp_pileup_col* cols, const sp_support_summary* sm,
-                      const std::vector<sp_pileup_ins>& ins, const std::string& debug_folder, CypLane* L) {
+                      const SupportLists& lists, uint64_t slot0, const std::string& debug_folder, CypLane* L) {
+    const std::vector<sp_pileup_ins>& ins = lists.ins;
+    const uint64_t n_haps = lists.haps.size();                       // (heads: the pass's, the sample's first at slot0)
     uint64_t need = 0;
-    int32_t rc = sp_cyp_support_json_ins(&call, cons, cons_cap, off, cols, sm, ins.data(), ins.size(), nullptr, 0, nullptr, 0, nullptr, 0, &need);
+    int32_t rc = sp_cyp_support_json_hap(&call, cons, cons_cap, off, cols, sm, ins.data(), ins.size(), n_haps ? lists.haps.data() : nullptr, n_haps, n_haps ? lists.heads.data() : nullptr, slot0,
+                                         nullptr, 0, nullptr, 0, nullptr, 0, &need);
     std::string text((size_t)need, '\0');
-    if (rc == SP_OK || rc == SP_ERR_CAPACITY) rc = sp_cyp_support_json_ins(&call, cons, cons_cap, off, cols, sm, ins.data(), ins.size(), nullptr, 0, nullptr, 0, &text[0], need, &need);
+    if (rc == SP_OK || rc == SP_ERR_CAPACITY) rc = sp_cyp_support_json_hap(&call, cons, cons_cap, off, cols, sm, ins.data(), ins.size(), n_haps ? lists.haps.data() : nullptr, n_haps,
+                                                                           n_haps ? lists.heads.data() : nullptr, slot0, nullptr, 0, nullptr, 0, &text[0], need, &need);
     if (rc != SP_OK) { L->rc = rc; L->err = "cyp2d6_consensus_support.json: the tables do not fit their consensuses"; return; }
     const std::string path = debug_folder + "/cyp2d6_consensus_support.json";
     FILE* f = std::fopen(path.c_str(), "wb");
@@ -874,22 +906,29 @@ void cyp_group(sp_starphase* h, std::vector<Sample*> group, bool only_ok, double
             }
             if (!on.empty()) {
                 std::vector<uint64_t> off((size_t)n * SP_CYP_MAXCONS + 1, 0); std::vector<sp_pileup_col> cols((size_t)n_cols + 1); std::vector<sp_support_summary> sm((size_t)n * SP_CYP_MAXCONS);
-                std::vector<sp_pileup_ins> ins;                      // (stays empty without sp_starphase_set_support_insertions: the renderer then writes the file as before)
-                int32_t rc = !h->support_insertions
+                SupportLists lists;                                  // (stay empty without sp_starphase_set_support_insertions / _haplotypes: the renderer then writes the file as before)
+                std::vector<sp_pileup_ins>& ins = lists.ins;
+                int32_t rc = h->support_haplotypes
+                    ? support_with_lists(lists, h->support_insertions != 0, (size_t)n * SP_CYP_MAXCONS, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got, sp_support_hap* hp, uint64_t hroom, uint64_t* hgot, sp_support_hap_head* hd) {
+                          return sp_cyp_consensus_support_cohort_hap(h->ctx2, n, sets.data(), sc.data(), cons.data(), cons_cap, flat.data(), moff.data(), off.data(), cols.data(), n_cols, sm.data(), p, room, got, hp, hroom, hgot, hd); })
+                    : !h->support_insertions
                     ? sp_cyp_consensus_support_cohort(h->ctx2, n, sets.data(), sc.data(), cons.data(), cons_cap, flat.data(), moff.data(), off.data(), cols.data(), n_cols, sm.data())
                     : support_with_ins(ins, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got) {
                           return sp_cyp_consensus_support_cohort_ins(h->ctx2, n, sets.data(), sc.data(), cons.data(), cons_cap, flat.data(), moff.data(), off.data(), cols.data(), n_cols, sm.data(), p, room, got); });
                 if (rc == SP_OK) {
-                    for (uint32_t k : on) cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data() + (size_t)k * SP_CYP_MAXCONS, cols.data(), sm.data() + (size_t)k * SP_CYP_MAXCONS, ins, typed[k]->debug, &typed[k]->cyp);
+                    for (uint32_t k : on) cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data() + (size_t)k * SP_CYP_MAXCONS, cols.data(), sm.data() + (size_t)k * SP_CYP_MAXCONS, lists, (uint64_t)k * SP_CYP_MAXCONS, typed[k]->debug, &typed[k]->cyp);
                 } else for (uint32_t k : on) {
                     // the shared pass failed: sample by sample, and only the samples whose own pass fails are failed (alone in the pass: that failure is its own)
                     CypLane* L = &typed[k]->cyp;
-                    if (on.size() > 1) rc = !h->support_insertions
+                    if (on.size() > 1) rc = h->support_haplotypes
+                        ? support_with_lists(lists, h->support_insertions != 0, SP_CYP_MAXCONS, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got, sp_support_hap* hp, uint64_t hroom, uint64_t* hgot, sp_support_hap_head* hd) {
+                              return sp_cyp_consensus_support_hap(h->ctx2, sets[k], &calls[k], cons.data() + cons_block * k, cons_cap, mappings[k].data(), mappings[k].size(), off.data(), cols.data(), n_cols, sm.data(), p, room, got, hp, hroom, hgot, hd); })
+                        : !h->support_insertions
                         ? sp_cyp_consensus_support(h->ctx2, sets[k], &calls[k], cons.data() + cons_block * k, cons_cap, mappings[k].data(), mappings[k].size(), off.data(), cols.data(), n_cols, sm.data())
                         : support_with_ins(ins, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got) {
                               return sp_cyp_consensus_support_ins(h->ctx2, sets[k], &calls[k], cons.data() + cons_block * k, cons_cap, mappings[k].data(), mappings[k].size(), off.data(), cols.data(), n_cols, sm.data(), p, room, got); });
                     if (rc != SP_OK) { L->rc = rc; L->err = "sp_cyp_consensus_support: " + opt(sp_last_error(h->ctx2)); continue; }
-                    cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data(), cols.data(), sm.data(), ins, typed[k]->debug, L);
+                    cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data(), cols.data(), sm.data(), lists, 0, typed[k]->debug, L);
                 }
             }
         }
@@ -921,7 +960,8 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
     bool want_support = false;                                       // likewise one support pass (anchor, alignment, pileup) over the group's consensuses
     for (Sample* b : with) want_support |= h->consensus_support && !b->debug.empty();
     std::vector<uint8_t> is1; std::vector<uint64_t> sup_off; std::vector<sp_pileup_col> sup_cols; std::vector<sp_support_summary> sup_sm;
-    std::vector<sp_pileup_ins> sup_ins;                              // (sp_starphase_set_support_insertions; empty otherwise)
+    SupportLists sup_lists;                                          // (sp_starphase_set_support_insertions / _haplotypes; empty otherwise)
+    std::vector<sp_pileup_ins>& sup_ins = sup_lists.ins;
     std::vector<int32_t> cohort_of(with.size(), -1);                 // a sample's place among the samples with reads
     if (R) {
         sp_seqset* set = nullptr;
@@ -967,7 +1007,11 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
                 }
             }
             sup_off.assign(at.size() * G * 2 + 1, 0); sup_cols.resize((size_t)n_cols + 1); sup_sm.resize(at.size() * G * 2);
-            if (!h->support_insertions)
+            if (h->support_haplotypes)
+                rc = support_with_lists(sup_lists, h->support_insertions != 0, at.size() * G * 2, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got, sp_support_hap* hp, uint64_t hroom, uint64_t* hgot, sp_support_hap_head* hd) {
+                    return sp_hla_consensus_support_cohort_hap(h->ctx, h->hla, (uint32_t)at.size(), read_sample.data(), (uint32_t)G, genes.data(), set, rec.data(), is1.data(),
+                                                               h->hla_cons.data(), cap, unit_on.data(), sup_off.data(), sup_cols.data(), n_cols, sup_sm.data(), p, room, got, hp, hroom, hgot, hd); });
+            else if (!h->support_insertions)
                 rc = sp_hla_consensus_support_cohort(h->ctx, h->hla, (uint32_t)at.size(), read_sample.data(), (uint32_t)G, genes.data(), set, rec.data(), is1.data(),
                                                      h->hla_cons.data(), cap, unit_on.data(), sup_off.data(), sup_cols.data(), n_cols, sup_sm.data());
             else
@@ -1006,7 +1050,8 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
         std::string e;
         SupportView sv{};
         const bool sup = want_support && cohort_of[k] >= 0 && !sup_off.empty();
-        if (sup) { const size_t x = (size_t)cohort_of[k]; sv = SupportView{ sup_off.data() + x * G * 2, sup_cols.data(), sup_sm.data() + x * G * 2, h->hla_cons.data() + x * G * 2 * (size_t)cap, cap, sup_ins.data(), sup_ins.size() }; }
+        if (sup) { const size_t x = (size_t)cohort_of[k]; sv = SupportView{ sup_off.data() + x * G * 2, sup_cols.data(), sup_sm.data() + x * G * 2, h->hla_cons.data() + x * G * 2 * (size_t)cap, cap, sup_ins.data(), sup_ins.size(),
+                                                                            sup_lists.haps.data(), sup_lists.haps.size(), sup_lists.heads.data(), sup_lists.heads.size(), x * G * 2 }; }
         const int32_t rc = hla_package(h, b->hreads, b->hsearched, orders[k], rec.data() + first[k], rev.data() + first[k], calls.data() + k * G, b->debug, b->hla_entries, e,
                                        want_cigars ? &cigars : nullptr, first[k], maps.map, maps.map ? map_item.data() + k * G * 2 : nullptr, &b->hwarn,
                                        h->consensus_support != 0, sup ? &sv : nullptr);
@@ -1118,6 +1163,11 @@ int32_t sp_starphase_set_consensus_support(sp_starphase* h, int32_t on) {
 int32_t sp_starphase_set_cyp_consensus_support(sp_starphase* h, int32_t on) {
     if (!h) return SP_ERR_INVALID_ARG;
     h->cyp_consensus_support = on ? 1 : 0;
+    return SP_OK;
+}
+int32_t sp_starphase_set_support_haplotypes(sp_starphase* h, int32_t on) {
+    if (!h) return SP_ERR_INVALID_ARG;
+    h->support_haplotypes = on ? 1 : 0;
     return SP_OK;
 }
 int32_t sp_starphase_set_support_insertions(sp_starphase* h, int32_t on) {

@@ -244,6 +244,10 @@ int32_t spi_hla_map_type_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, con
 namespace spj { struct Value; }
 void spi_support_ins_json(spj::Value* column, const sp_pileup_ins* ins, uint64_t n_ins, uint64_t col, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
                           const char* const* names, uint32_t n_names);
+// the same for the haplotype list: adds "haplotypes" to the object of a consensus (cols: its `length` columns) from the records of target `target` of a list; nothing
+// when the target's head has n_cols == 0 or no records.  first_read as above.
+void spi_support_hap_json(spj::Value* consensus, const sp_pileup_col* cols, uint32_t length, const sp_support_hap* haps, uint64_t n_haps, const sp_support_hap_head* head,
+                          uint64_t target, const sp_cyp_read_mapping* mappings, uint64_t n_mappings, const char* const* names, uint32_t n_names);
 // sp_cyp.hip, for sp_diplotype.hip: sp_cyp_diplotype_mappings with the list in a vector the library sizes
 int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
                                    sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings);

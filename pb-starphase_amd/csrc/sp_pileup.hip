@@ -447,6 +447,210 @@ __global__ void ins_pack_kernel(const sp_pileup_ins* __restrict__ tmp, const uin
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) out[out_off[tile] + i] = tmp[tile_off[tile] + i];
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// Read haplotypes (sp_support_hap; contract: include/starphase_hip.h, design: DESIGN.md section 7.2).  Behind the finished table, on one stream:
+//   hap_cols      one workgroup per target: the first HAP_COLS contested columns (the rule of support_summary_kernel), ascending, and how many there are
+//   hap_pattern   one wave per pair: the pair's calls at its target's listed columns, ORed into a 256-bit pattern in LDS, stored to pat[pair][4]; valid[pair] says
+//                 whether the pair is one the table counts (the pairs pileup_rows_kernel skips are skipped)
+//   hap_reduce    one workgroup per target: sort its (pattern, pair) keys -- a total order --, run-length compact them (the first key of a run is its lowest pair),
+//                 sort the records by (count descending, pattern ascending), write them to the target's slice of a pooled output
+//   hap_pack      the slices back to back, and the heads
+// No global atomics: every word has one writer.
+// ------------------------------------------------------------------------------------------------------------------------------
+struct HapKey { uint64_t w[4]; uint32_t pair, valid; };                                // 40 bytes
+static_assert(sizeof(HapKey) == 40 && sizeof(sp_support_hap) == 56 && sizeof(sp_support_hap_head) == 24, "record sizes");
+constexpr int HAP_COLS = SP_SUPPORT_HAP_COLS, HAP_LDS_KEYS = SP_SUPPORT_HAP_LDS_KEYS, HAP_WAVES = INS_THREADS / SP_WAVE;
+static_assert(HAP_COLS == 64 && HAP_WAVES == 4, "a pattern is 64 calls of 4 bits; hap_cols sums four waves");
+
+__global__ __launch_bounds__(INS_THREADS) void hap_cols_kernel(const uint32_t* __restrict__ table, const uint64_t* __restrict__ col_offset, const int32_t* __restrict__ t_len,
+                                                               uint32_t* __restrict__ list, uint32_t* __restrict__ ktot) {
+    __shared__ uint32_t s_w[HAP_WAVES];
+    const uint32_t t = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const uint32_t len = (uint32_t)t_len[t];
+    const uint4* cols = (const uint4*)(table + col_offset[t] * 8u);                     // a column = two 16-byte halves: depth eq x0 x1 | x2 x3 del ins
+    uint32_t base = 0;                                                                  // contested columns in front of this chunk (uniform)
+    for (uint32_t j0 = 0; j0 < len; j0 += INS_THREADS) {
+        const uint32_t j = j0 + tid;
+        bool c = false;
+        if (j < len) {
+            const uint4 a = cols[2 * (size_t)j];
+            const uint32_t ins = cols[2 * (size_t)j + 1].w;
+            c = (a.x > 0 && 2ull * a.y <= a.x) || 2ull * ins > a.x;
+        }
+        const unsigned long long vote = __ballot(c);
+        if (lane == 0) s_w[wave] = (uint32_t)__popcll(vote);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t w = 0; w < (uint32_t)HAP_WAVES; ++w) { before += w < wave ? s_w[w] : 0u; total += s_w[w]; }
+        if (c) {
+            const uint32_t at = base + before + (uint32_t)__popcll(vote & ((1ull << lane) - 1ull));
+            if (at < (uint32_t)HAP_COLS) list[(size_t)t * HAP_COLS + at] = j;
+        }
+        base += total;
+        __syncthreads();
+    }
+    if (tid == 0) ktot[t] = base;
+}
+
+// first k in [0, K) with cols[k] >= c (K when there is none)
+__device__ __forceinline__ int hap_lower(const uint32_t* cols, int K, uint32_t c) {
+    int lo = 0, hi = K;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (cols[mid] < c) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
+__global__ __launch_bounds__(INS_THREADS) void hap_pattern_kernel(SeqSetView A, const int32_t* __restrict__ t_len, const sp_pair* __restrict__ pairs, const sp_affine_aln* __restrict__ aln,
+                                                                  const uint32_t* __restrict__ n_cigar, const uint64_t* __restrict__ op_off, const uint32_t* __restrict__ ops, uint32_t n,
+                                                                  int need_score, const uint32_t* __restrict__ list, const uint32_t* __restrict__ ktot,
+                                                                  uint64_t* __restrict__ pat, uint32_t* __restrict__ valid) {
+    __shared__ uint32_t s_cols[HAP_WAVES][HAP_COLS], s_pat[HAP_WAVES][8];
+    const uint32_t wave = threadIdx.x >> 6, i = blockIdx.x * HAP_WAVES + wave;
+    const int lane = threadIdx.x & (SP_WAVE - 1);
+    // ---- everything the wave decides on is wave-uniform; the barriers are met by every wave of the workgroup
+    bool act = i < n;
+    uint32_t n_ops = 0; uint64_t off = 0; sp_affine_aln g = {}; sp_pair pr = {}; int K = 0;
+    if (act) {
+        n_ops = n_cigar[i]; off = op_off[i];
+        act = !(n_ops == 0 || n_ops == AP_LOST || off == AP_NO_OPS);
+    }
+    if (act) { g = aln[i]; act = !(need_score && g.score <= 0); }
+    if (act) {
+        pr = pairs[i];
+        K = (int)min(ktot[pr.b], (uint32_t)HAP_COLS);
+        if (lane < K) s_cols[wave][lane] = list[(size_t)pr.b * HAP_COLS + lane];
+    }
+    if (lane < 8) s_pat[wave][lane] = 0u;
+    __syncthreads();
+    if (act && K > 0) {
+        const uint32_t* cols = s_cols[wave];
+        uint32_t* mine = s_pat[wave];
+        const uint32_t* qwords = A.words + A.word_off[pr.a];
+        const uint32_t* row = ops + off;
+        const int tl_max = t_len[pr.b], last = (int)cols[K - 1];
+        int tpos = g.b_start, qpos = g.a_start;
+        for (uint32_t k0 = 0; k0 < n_ops && tpos <= last + 1; k0 += SP_WAVE) {         // (an 'I' op at column last + 1 sits behind column last: <=)
+            const bool live = k0 + lane < n_ops;
+            const uint32_t w = live ? row[k0 + lane] : 0u;
+            const uint32_t op = w & 15u; const int len = (int)(w >> 4);
+            const int tl = (op == 7u || op == 8u || op == 2u) ? len : 0, ql = (op == 7u || op == 8u || op == 1u) ? len : 0;
+            int ts = tl, qs = ql;
+#pragma unroll
+            for (int d = 1; d < SP_WAVE; d <<= 1) {
+                const int u = __shfl_up(ts, d), v = __shfl_up(qs, d);
+                if (lane >= d) { ts += u; qs += v; }
+            }
+            const int t0 = tpos + ts - tl, q0 = qpos + qs - ql;
+            tpos += __shfl(ts, SP_WAVE - 1); qpos += __shfl(qs, SP_WAVE - 1);
+            if (live && tl > 0) {
+                for (int k = hap_lower(cols, K, (uint32_t)t0); k < K && (int)cols[k] < t0 + tl; ++k) {
+                    const uint32_t call = op == 7u ? 1u : op == 2u ? 6u : 2u + pu_query_code(qwords, q0 + ((int)cols[k] - t0));
+                    atomicOr(&mine[k >> 3], call << ((k & 7) << 2));
+                }
+            }
+            if (live && op == 1u && t0 - 1 >= 0 && t0 - 1 < tl_max) {
+                const int k = hap_lower(cols, K, (uint32_t)(t0 - 1));
+                if (k < K && (int)cols[k] == t0 - 1) atomicOr(&mine[k >> 3], 8u << ((k & 7) << 2));
+            }
+        }
+    }
+    __syncthreads();
+    if (i < n) {
+        if (lane < 4) pat[(size_t)i * 4 + lane] = (uint64_t)s_pat[wave][2 * lane] | (uint64_t)s_pat[wave][2 * lane + 1] << 32;
+        if (lane == 0) valid[i] = act ? 1u : 0u;
+    }
+}
+
+__device__ __forceinline__ bool hap_same(const HapKey& a, const HapKey& b) { return a.w[0] == b.w[0] && a.w[1] == b.w[1] && a.w[2] == b.w[2] && a.w[3] == b.w[3]; }
+__device__ __forceinline__ bool hap_pat_less(const HapKey& a, const HapKey& b, bool* equal) {
+    *equal = false;
+    if (a.w[3] != b.w[3]) return a.w[3] < b.w[3];
+    if (a.w[2] != b.w[2]) return a.w[2] < b.w[2];
+    if (a.w[1] != b.w[1]) return a.w[1] < b.w[1];
+    if (a.w[0] != b.w[0]) return a.w[0] < b.w[0];
+    *equal = true;
+    return false;
+}
+
+// one target's keys R[0 .. n) -> its records, in the list's order, to out; returns their number.  idx / didx / dcnt: n words each, where R lives (LDS or the pooled scratch).
+__device__ __forceinline__ uint32_t hap_target_work(const HapKey* R, uint32_t* idx, uint32_t* didx, uint32_t* dcnt, uint32_t n, uint32_t* part, uint32_t target, uint32_t K,
+                                                    sp_support_hap* __restrict__ out) {
+    const uint32_t tid = threadIdx.x, per = (n + INS_THREADS - 1) / INS_THREADS, lo = min(n, tid * per), hi = min(n, lo + per);
+    for (uint32_t s = tid; s < n; s += INS_THREADS) idx[s] = s;
+    __syncthreads();
+    // the pairs the table does not count go behind all others; then the pattern, then the pair: a total order
+    ins_bitonic(idx, n, [&](uint32_t a, uint32_t b) {
+        const HapKey& x = R[a]; const HapKey& y = R[b];
+        if (x.valid != y.valid) return x.valid > y.valid;
+        bool eq;
+        const bool less = hap_pat_less(x, y, &eq);
+        return eq ? x.pair < y.pair : less;
+    });
+    uint32_t mine = 0, nv = 0;
+    for (uint32_t s = lo; s < hi; ++s) mine += R[idx[s]].valid ? 1u : 0u;
+    (void)ins_block_scan(mine, part, &nv);
+    // ---- distinct records over the nv keys in front: didx[d] = the first key of record d (its lowest pair), dcnt[d] = how many keys it has
+    uint32_t heads = 0, m = 0;
+    for (uint32_t s = lo; s < hi; ++s) heads += (s < nv && (s == 0 || !hap_same(R[idx[s]], R[idx[s - 1]]))) ? 1u : 0u;
+    uint32_t d = ins_block_scan(heads, part, &m);
+    for (uint32_t s = lo; s < hi; ++s) if (s < nv && (s == 0 || !hap_same(R[idx[s]], R[idx[s - 1]]))) didx[d++] = s;
+    __syncthreads();
+    for (uint32_t e = tid; e < m; e += INS_THREADS) dcnt[e] = (e + 1 < m ? didx[e + 1] : nv) - didx[e];
+    __syncthreads();
+    for (uint32_t e = tid; e < m; e += INS_THREADS) didx[e] = idx[didx[e]];
+    __syncthreads();
+    // ---- the list's order: count descending, then the pattern ascending (distinct records have distinct patterns)
+    for (uint32_t e = tid; e < m; e += INS_THREADS) idx[e] = e;
+    __syncthreads();
+    ins_bitonic(idx, m, [&](uint32_t a, uint32_t b) {
+        if (dcnt[a] != dcnt[b]) return dcnt[a] > dcnt[b];
+        bool eq;
+        return hap_pat_less(R[didx[a]], R[didx[b]], &eq);
+    });
+    for (uint32_t e = tid; e < m; e += INS_THREADS) {
+        const HapKey& x = R[didx[idx[e]]];
+        sp_support_hap o;
+        o.target = target; o.n_cols = K; o.count = dcnt[idx[e]]; o.first_pair = x.pair; o.reserved_ = 0;
+        o.w[0] = x.w[0]; o.w[1] = x.w[1]; o.w[2] = x.w[2]; o.w[3] = x.w[3];
+        out[e] = o;
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(INS_THREADS) void hap_reduce_kernel(const uint64_t* __restrict__ pat, const uint32_t* __restrict__ valid, const uint32_t* __restrict__ order,
+                                                                 const uint32_t* __restrict__ boff, uint32_t n_slices, const uint32_t* __restrict__ ktot, HapKey* __restrict__ keys,
+                                                                 uint32_t* __restrict__ scratch, uint64_t scratch_stride, sp_support_hap* __restrict__ tmp, uint32_t* __restrict__ n_dist) {
+    __shared__ HapKey s_keys[HAP_LDS_KEYS];
+    __shared__ uint32_t s_idx[HAP_LDS_KEYS], s_didx[HAP_LDS_KEYS], s_dcnt[HAP_LDS_KEYS], part[INS_THREADS];
+    const uint32_t t = blockIdx.x, k_lo = boff[(size_t)t * (n_slices + 1)], n = boff[(size_t)t * (n_slices + 1) + n_slices] - k_lo;
+    const uint32_t K = min(ktot[t], (uint32_t)HAP_COLS);
+    uint32_t m = 0;
+    if (n > 0 && K > 0) {                                                              // (uniform over the workgroup)
+        const bool in_lds = n <= (uint32_t)HAP_LDS_KEYS;
+        HapKey* R = in_lds ? s_keys : keys + k_lo;
+        for (uint32_t s = threadIdx.x; s < n; s += INS_THREADS) {
+            const uint32_t p = order[k_lo + s];
+            HapKey k;
+            k.w[0] = pat[(size_t)p * 4]; k.w[1] = pat[(size_t)p * 4 + 1]; k.w[2] = pat[(size_t)p * 4 + 2]; k.w[3] = pat[(size_t)p * 4 + 3]; k.pair = p; k.valid = valid[p];
+            R[s] = k;
+        }
+        __syncthreads();
+        if (in_lds) m = hap_target_work(R, s_idx, s_didx, s_dcnt, n, part, t, K, tmp + k_lo);
+        else m = hap_target_work(R, scratch + k_lo, scratch + scratch_stride + k_lo, scratch + 2 * scratch_stride + k_lo, n, part, t, K, tmp + k_lo);
+    }
+    if (threadIdx.x == 0) n_dist[t] = m;
+}
+
+__global__ void hap_pack_kernel(const sp_support_hap* __restrict__ tmp, const uint32_t* __restrict__ boff, uint32_t n_slices, const uint32_t* __restrict__ n_dist,
+                                const uint32_t* __restrict__ out_off, const uint32_t* __restrict__ ktot, sp_support_hap* __restrict__ out, sp_support_hap_head* __restrict__ heads) {
+    const uint32_t t = blockIdx.x, n = n_dist[t], k_lo = boff[(size_t)t * (n_slices + 1)];
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) out[out_off[t] + i] = tmp[k_lo + i];
+    if (threadIdx.x == 0) {
+        sp_support_hap_head h;
+        h.first_record = out_off[t]; h.n_records = n; h.n_cols = min(ktot[t], (uint32_t)HAP_COLS); h.n_cols_total = ktot[t]; h.reserved_ = 0;
+        heads[t] = h;
+    }
+}
+
 static bool contested_col(const sp_pileup_col& c) { return (c.depth > 0 && 2ull * c.eq <= c.depth) || 2ull * c.ins > c.depth; }
 
 static std::string revcomp_str(const char* s, size_t n) {
@@ -567,6 +771,62 @@ static int32_t pileup_check_rows(sp_ctx* ctx, const sp_seqset* A, const sp_seqse
     return SP_OK;
 }
 
+// pileup_rows_kernel takes more dynamic LDS than the 64 KiB a kernel gets unasked: said once per device of the process
+static int32_t pileup_rows_lds(sp_ctx* ctx) {
+    static std::atomic<uint64_t> lds_set(0);
+    const uint64_t bit = 1ull << (ctx->device & 63);
+    if (!(lds_set.load() & bit)) {
+        SP_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)pileup_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PU_LDS_BYTES));
+        lds_set.fetch_or(bit);
+    }
+    return SP_OK;
+}
+
+// ---- the host side of the haplotype list: one pooled buffer carved by the numbers of pairs and targets (a warm context allocates nothing), the launches, the way out
+struct HapOut { sp_support_hap* haps; uint64_t cap; uint64_t* n_haps; sp_support_hap_head* heads; };
+
+// the list over n pairs whose rows lie in device memory (d_ops: the rows of ALL of them), behind the finished table d_table.  A list that does not fit: SP_ERR_CAPACITY,
+// *n_haps set, nothing written.
+static int32_t hap_run(sp_ctx* ctx, const std::string& who, const sp_seqset* A, const sp_seqset* B, uint32_t n, const uint32_t* d_table, const uint64_t* d_col_offset,
+                       const sp_pair* d_pairs, const sp_affine_aln* d_aln, const uint32_t* d_nc, const uint64_t* d_op_off, const uint32_t* d_ops, bool need_score,
+                       const uint32_t* d_order, const uint32_t* d_boff, uint32_t n_slices, const HapOut& ho) {
+    const uint32_t n_t = B->n;
+    *ho.n_haps = 0;
+    if (n_t == 0) return SP_OK;
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t np = std::max<size_t>(n, 1);
+    const size_t at_list = 0, at_ktot = up16(at_list + 4 * (size_t)n_t * HAP_COLS), at_ndist = up16(at_ktot + 4 * (size_t)n_t), at_ooff = up16(at_ndist + 4 * (size_t)n_t),
+                 at_valid = up16(at_ooff + 4 * ((size_t)n_t + 1)), at_scratch = up16(at_valid + 4 * np), at_pat = up16(at_scratch + 12 * np), at_keys = up16(at_pat + 32 * np),
+                 at_tmp = up16(at_keys + sizeof(HapKey) * np), at_out = up16(at_tmp + sizeof(sp_support_hap) * np), at_heads = up16(at_out + sizeof(sp_support_hap) * np),
+                 bytes = up16(at_heads + sizeof(sp_support_hap_head) * (size_t)n_t);
+    uint8_t* d = (uint8_t*)sp_pool(ctx, "hap", bytes);
+    uint32_t* h_total = (uint32_t*)sp_host_pool(ctx, "hap_st", 16);
+    if (!d || !h_total) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, who + ": haplotype list buffers");
+    uint32_t *d_list = (uint32_t*)(d + at_list), *d_ktot = (uint32_t*)(d + at_ktot), *d_ndist = (uint32_t*)(d + at_ndist), *d_ooff = (uint32_t*)(d + at_ooff);
+    uint32_t *d_valid = (uint32_t*)(d + at_valid), *d_scratch = (uint32_t*)(d + at_scratch);
+    uint64_t* d_pat = (uint64_t*)(d + at_pat); HapKey* d_keys = (HapKey*)(d + at_keys);
+    sp_support_hap *d_tmp = (sp_support_hap*)(d + at_tmp), *d_out = (sp_support_hap*)(d + at_out);
+    sp_support_hap_head* d_heads = (sp_support_hap_head*)(d + at_heads);
+    {
+        ProfScope ps(ctx, "support_hap", n);
+        hipLaunchKernelGGL(hap_cols_kernel, dim3(n_t), dim3(INS_THREADS), 0, ctx->stream, d_table, d_col_offset, B->d_len, d_list, d_ktot);
+        if (n) hipLaunchKernelGGL(hap_pattern_kernel, dim3((n + HAP_WAVES - 1) / HAP_WAVES), dim3(INS_THREADS), 0, ctx->stream, A->view(), B->d_len, d_pairs, d_aln, d_nc, d_op_off, d_ops, n,
+                                  need_score ? 1 : 0, d_list, d_ktot, d_pat, d_valid);
+        hipLaunchKernelGGL(hap_reduce_kernel, dim3(n_t), dim3(INS_THREADS), 0, ctx->stream, d_pat, d_valid, d_order, d_boff, n_slices, d_ktot, d_keys, d_scratch, (uint64_t)np, d_tmp, d_ndist);
+        hipLaunchKernelGGL(ins_scan_kernel, dim3(1), dim3(INS_THREADS), 0, ctx->stream, d_ndist, n_t, d_ooff, (uint32_t*)nullptr);
+        hipLaunchKernelGGL(hap_pack_kernel, dim3(n_t), dim3(256), 0, ctx->stream, d_tmp, d_boff, n_slices, d_ndist, d_ooff, d_ktot, d_out, d_heads);
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": haplotype list launch failed");
+    }
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(h_total, d_ooff + n_t, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    *ho.n_haps = *h_total;
+    if (*ho.n_haps > ho.cap) return sp_fail(ctx, SP_ERR_CAPACITY, who + ": " + std::to_string(*ho.n_haps) + " haplotype records, room for " + std::to_string(ho.cap));
+    if (*ho.n_haps) SP_HIP_CHECK(ctx, hipMemcpyAsync(ho.haps, d_out, (size_t)*ho.n_haps * sizeof(sp_support_hap), hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(ho.heads, d_heads, (size_t)n_t * sizeof(sp_support_hap_head), hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return SP_OK;
+}
+
 // the first min(len, 64) bases of a record, from its key
 static std::string ins_key_string(const sp_pileup_ins& r) {
     std::string out(std::min<uint32_t>(r.len, 64), 'A');
@@ -598,6 +858,32 @@ void spi_support_ins_json(spj::Value* column, const sp_pileup_ins* ins, uint64_t
     column->obj.emplace_back("insertions", std::move(list));
     if (more) column->obj.emplace_back("more", spj::unum(more));
     if (other) column->obj.emplace_back("other", spj::unum(other));
+}
+
+void spi_support_hap_json(spj::Value* consensus, const sp_pileup_col* cols, uint32_t length, const sp_support_hap* haps, uint64_t n_haps, const sp_support_hap_head* head,
+                          uint64_t target, const sp_cyp_read_mapping* mappings, uint64_t n_mappings, const char* const* names, uint32_t n_names) {
+    if (!head || head->n_cols == 0 || head->n_records == 0) return;
+    const sp_support_hap* end = haps + n_haps;
+    const sp_support_hap* r = std::lower_bound(haps, end, target, [](const sp_support_hap& a, uint64_t t) { return a.target < t; });
+    if (r == end || r->target != target) return;
+    spj::Value v = spj::object(), columns = spj::array(), patterns = spj::array();
+    for (uint32_t j = 0; j < length && columns.arr.size() < head->n_cols; ++j) if (contested_col(cols[j])) columns.arr.push_back(spj::unum(j));
+    uint64_t more = 0;
+    for (; r != end && r->target == target; ++r) {
+        if (patterns.arr.size() >= 16) { more += r->count; continue; }
+        char text[2 * SP_SUPPORT_HAP_COLS + 1];
+        if (sp_support_hap_string(r, text, sizeof text, nullptr) != SP_OK) text[0] = '\0';
+        spj::Value p = spj::object();
+        p.obj.emplace_back("count", spj::unum(r->count)); p.obj.emplace_back("calls", spj::str(text));
+        uint64_t who = r->first_pair;
+        bool known = names != nullptr;
+        if (known && mappings) { known = who < n_mappings; if (known) who = mappings[who].read; }
+        if (known && who < n_names && names[who]) p.obj.emplace_back("first_read", spj::str(names[who]));
+        patterns.arr.push_back(std::move(p));
+    }
+    v.obj.emplace_back("columns", std::move(columns)); v.obj.emplace_back("columns_total", spj::unum(head->n_cols_total)); v.obj.emplace_back("patterns", std::move(patterns));
+    if (more) v.obj.emplace_back("more", spj::unum(more));
+    consensus->obj.emplace_back("haplotypes", std::move(v));
 }
 
 extern "C" {
@@ -734,13 +1020,99 @@ int32_t sp_pileup_ins_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B,
     return SP_OK;
 }
 
+int32_t sp_support_hap_string(const sp_support_hap* rec, char* out, uint64_t cap, uint64_t* needed) {
+    if (!rec || (cap && !out) || rec->n_cols > SP_SUPPORT_HAP_COLS) return SP_ERR_INVALID_ARG;
+    std::string text;
+    for (uint32_t k = 0; k < rec->n_cols; ++k) {
+        const uint32_t call = (uint32_t)(rec->w[k >> 4] >> ((k & 15) << 2)) & 15u;
+        text += "?=ACGT-?"[call & 7u];
+        if (call & 8u) text += '+';
+    }
+    if (needed) *needed = text.size() + 1;
+    if (cap < text.size() + 1) { if (cap) out[0] = '\0'; return SP_ERR_CAPACITY; }
+    std::memcpy(out, text.c_str(), text.size() + 1);
+    return SP_OK;
+}
+
+int32_t sp_pileup_hap_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
+                            const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset,
+                            sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (!A || !B || !col_offset || !n_haps || !heads || (hap_cap && !haps) || (n_pairs && (!pairs || !aln || !n_cigar))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: null argument");
+    if (n_pairs > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: too many pairs");
+    const uint32_t n_t = B->n, n = (uint32_t)n_pairs;
+    if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset[0] must be 0");
+    for (uint32_t t = 0; t < n_t; ++t)
+        if (col_offset[t + 1] < col_offset[t] || col_offset[t + 1] - col_offset[t] != (uint64_t)B->h_len[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset does not follow the target lengths");
+    const uint64_t n_cols = col_offset[n_t];
+    std::vector<uint32_t> live_of((size_t)n_t + 1, 0);
+    uint64_t total_ops = 0, n_ins_ops = 0;
+    int32_t rc = pileup_check_rows(ctx, A, B, pairs, n_pairs, aln, cigar, cigar_stride, n_cigar, live_of, &total_ops, &n_ins_ops);
+    if (rc != SP_OK) return rc;
+    *n_haps = 0;
+    if (n_t == 0) return SP_OK;
+    uint64_t n_tiles = 0;
+    for (uint32_t t = 0; t < n_t; ++t) n_tiles += ((uint64_t)B->h_len[t] + PU_TILE - 1) / PU_TILE;
+    if (n_tiles > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: too many tiles");
+    (void)hipSetDevice(ctx->device);
+    // ---- one staging block, one copy: what the device-resident pass keeps per pair (pairs, spans, op counts, op offsets), its order and offsets for ONE slice, the tiles,
+    //      the column offsets, the ops back to back.  The table is pileup_rows_kernel's, which skips score <= 0: sp_pileup_batch counts every pair with ops, so the
+    //      staged spans of those carry score 1.
+    std::vector<uint32_t> boff((size_t)n_t * 2 + 1, 0);
+    for (uint32_t i = 0; i < n; ++i) ++boff[(size_t)pairs[i].b * 2 + 1];
+    { uint32_t run = 0; for (uint32_t t = 0; t < n_t; ++t) { boff[(size_t)t * 2] = run; run += boff[(size_t)t * 2 + 1]; boff[(size_t)t * 2 + 1] = run; } }
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t at_pairs = 0, at_aln = up16(at_pairs + sizeof(sp_pair) * (size_t)n), at_nc = up16(at_aln + sizeof(sp_affine_aln) * (size_t)n), at_off = up16(at_nc + 4 * (size_t)n),
+                 at_order = up16(at_off + 8 * (size_t)n), at_boff = up16(at_order + 4 * (size_t)n), at_tiles = up16(at_boff + 4 * boff.size()),
+                 at_cols = up16(at_tiles + sizeof(PuTile) * (size_t)n_tiles), at_ops = up16(at_cols + 8 * ((size_t)n_t + 1)), in_bytes = up16(at_ops + 4 * (size_t)total_ops) + 16;
+    uint8_t* h_in = (uint8_t*)sp_host_pool(ctx, "pileup_hap_in", in_bytes);
+    uint8_t* d_in = (uint8_t*)sp_pool(ctx, "pileup_hap_in", in_bytes);
+    uint32_t* d_table = (uint32_t*)sp_pool(ctx, "pileup_out", std::max<size_t>(16, n_cols * sizeof(sp_pileup_col)));
+    if (!h_in || !d_in || !d_table) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "pileup buffers");
+    {
+        if (n) std::memcpy(h_in + at_pairs, pairs, sizeof(sp_pair) * (size_t)n);
+        if (n) std::memcpy(h_in + at_nc, n_cigar, 4 * (size_t)n);
+        std::memcpy(h_in + at_boff, boff.data(), 4 * boff.size());
+        std::memcpy(h_in + at_cols, col_offset, 8 * ((size_t)n_t + 1));
+        sp_affine_aln* ha = (sp_affine_aln*)(h_in + at_aln);
+        uint64_t* hoff = (uint64_t*)(h_in + at_off); uint32_t* hops = (uint32_t*)(h_in + at_ops); uint32_t* hord = (uint32_t*)(h_in + at_order);
+        std::vector<uint32_t> at(n_t);
+        for (uint32_t t = 0; t < n_t; ++t) at[t] = boff[(size_t)t * 2];
+        uint64_t op_at = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            hord[at[pairs[i].b]++] = i;
+            ha[i] = aln[i]; hoff[i] = op_at;
+            if (n_cigar[i] == 0) continue;
+            ha[i].score = 1;
+            std::memcpy(hops + op_at, cigar + i * (size_t)cigar_stride, 4 * (size_t)n_cigar[i]);
+            op_at += n_cigar[i];
+        }
+        PuTile* ht = (PuTile*)(h_in + at_tiles); uint64_t x = 0;
+        for (uint32_t t = 0; t < n_t; ++t) for (int32_t c0 = 0; c0 < B->h_len[t]; c0 += PU_TILE) ht[x++] = PuTile{ t, (uint32_t)c0 };
+    }
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const sp_pair* d_pairs = (const sp_pair*)(d_in + at_pairs); const sp_affine_aln* d_aln = (const sp_affine_aln*)(d_in + at_aln);
+    const uint32_t* d_nc = (const uint32_t*)(d_in + at_nc); const uint64_t* d_off = (const uint64_t*)(d_in + at_off); const uint32_t* d_ops = (const uint32_t*)(d_in + at_ops);
+    const uint32_t* d_order = (const uint32_t*)(d_in + at_order); const uint32_t* d_boff = (const uint32_t*)(d_in + at_boff);
+    if (n_tiles) {
+        rc = pileup_rows_lds(ctx);
+        if (rc != SP_OK) return rc;
+        ProfScope ps(ctx, "pileup", n_cols);
+        hipLaunchKernelGGL(pileup_rows_kernel, dim3((unsigned)n_tiles), dim3(PU_WAVES * SP_WAVE), PU_LDS_BYTES, ctx->stream, A->view(), B->d_len, d_pairs, d_aln, d_nc, d_off, d_ops,
+                           d_order, d_boff, 1u, 0u, (const PuTile*)(d_in + at_tiles), (const uint64_t*)(d_in + at_cols), d_table);
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "pileup launch failed");
+    }
+    HapOut ho; ho.haps = haps; ho.cap = hap_cap; ho.n_haps = n_haps; ho.heads = heads;
+    return hap_run(ctx, "pileup", A, B, n, d_table, (const uint64_t*)(d_in + at_cols), d_pairs, d_aln, d_nc, d_off, d_ops, false, d_order, d_boff, 1, ho);
+}
+
 // sp_align_pileup_band_batch for the library's own callers as well: `who` begins its error texts, prof[] names its four launches (map, second map, pileup, summary) in the
 // context's profile, and the first map launch counts the pairs it attempts (max_ed >= 0) when count_attempted is set, every pair of the slice otherwise.
 static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
                                 const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
                                 const std::string& who, const char* const prof[4], bool count_attempted,
-                                sp_pileup_ins* ins = nullptr, uint64_t ins_cap = 0, uint64_t* n_ins = nullptr, uint64_t ins_runs = 0) {
-    if (!A || !B || !opts || !col_offset || (n_pairs && !pairs) || (ins && !n_ins)) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": null argument");
+                                sp_pileup_ins* ins = nullptr, uint64_t ins_cap = 0, uint64_t* n_ins = nullptr, uint64_t ins_runs = 0, const HapOut* hap = nullptr) {
+    if (!A || !B || !opts || !col_offset || (n_pairs && !pairs) || (ins && !n_ins) || (hap && (!hap->n_haps || !hap->heads))) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": null argument");
     if ((band != 64 && band != 256) || (retry_band != 0 && retry_band != 256) || (retry_band != 0 && band != 64))
         return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": band must be 64 or 256, retry_band 0 or (with band 64) 256");
     if (n_pairs > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": too many pairs");
@@ -757,8 +1129,9 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
         ++boff[(size_t)pairs[i].b * (n_slices + 1) + i / SP_ALIGN_PILEUP_SLICE + 1];
     }
     if (ins) *n_ins = 0;
+    if (hap) *hap->n_haps = 0;
     if (n_pairs == 0 && n_t == 0) return SP_OK;
-    const bool want_table = (cols || summaries) && n_t > 0;
+    const bool want_table = (cols || summaries || hap) && n_t > 0;                                    // (the haplotype list reads the finished table)
     if (!aln && !want_table && !ins) return SP_OK;
     // boff[t * (S + 1) + s + 1] holds the count of (t, s): into running offsets; entry t * (S + 1) is where target t begins = where target t - 1 ended
     {
@@ -805,13 +1178,9 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
     SP_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     const sp_pair* d_pairs = (const sp_pair*)(d_in + at_pairs);
     const uint32_t* d_order = (const uint32_t*)(d_in + at_order); const uint32_t* d_boff = (const uint32_t*)(d_in + at_boff);
-    if (n_tiles) {   // more dynamic LDS than the 64 KiB a kernel gets unasked: said once per device of the process
-        static std::atomic<uint64_t> lds_set(0);
-        const uint64_t bit = 1ull << (ctx->device & 63);
-        if (!(lds_set.load() & bit)) {
-            SP_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)pileup_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PU_LDS_BYTES));
-            lds_set.fetch_or(bit);
-        }
+    if (n_tiles) {
+        const int32_t rc = pileup_rows_lds(ctx);
+        if (rc != SP_OK) return rc;
     }
     InsPass ip;                                                                                       // the insertion list, when asked for: its runs are collected slice by slice
     if (ins) {
@@ -822,14 +1191,26 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
         if (rc != SP_OK) return rc;
     }
     // ---- slice by slice: the map into the op buffer (run again on a larger one when it asked for more: a warm context does not), what the host must know, the pileup
-    uint64_t ops_cap = std::max<uint64_t>(sp_pool_bytes(ctx, "appile_ops") / 4, (uint64_t)std::min<uint32_t>(std::max<uint32_t>(n, 1), SP_ALIGN_PILEUP_SLICE) * 64);
+    // With the haplotype list the buffer holds the rows of the WHOLE batch (the contested columns are known only behind the last slice): the cursor is not rewound
+    // between slices.  A buffer that turns out too small behind the first slice must not lose the rows it holds: the batch moves into the context's second op buffer
+    // ("appile_ops_b": the rows so far are copied, the slice runs again), sized from what the slices so far took per pair; nothing else is run again.  A warm context
+    // begins on the larger of the two.  Without the list only "appile_ops" is used, as before.
+    const bool keep_rows = hap && n_slices > 1;
+    const char* ops_name = (keep_rows && sp_pool_bytes(ctx, "appile_ops_b") > sp_pool_bytes(ctx, "appile_ops")) ? "appile_ops_b" : "appile_ops";
+    uint64_t ops_cap = std::max<uint64_t>(sp_pool_bytes(ctx, ops_name) / 4, (uint64_t)std::min<uint32_t>(std::max<uint32_t>(n, 1), keep_rows ? n : SP_ALIGN_PILEUP_SLICE) * 64);
+    uint64_t kept = 0;                                                                                // (keep_rows) the cursor behind the last finished slice
+    uint64_t* h_keep = keep_rows ? (uint64_t*)sp_host_pool(ctx, "appile_keep", 16) : nullptr;
+    if (keep_rows && !h_keep) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, who + " buffers");
+    uint32_t* d_ops = nullptr;
     for (uint32_t s2 = 0; s2 < n_slices; ++s2) {
         const uint32_t p0 = s2 * SP_ALIGN_PILEUP_SLICE, m = std::min<uint32_t>(SP_ALIGN_PILEUP_SLICE, n - p0);
-        uint32_t* d_ops = nullptr;
         for (int attempt = 0; m > 0; ++attempt) {
-            d_ops = (uint32_t*)sp_pool(ctx, "appile_ops", (size_t)ops_cap * 4);
+            d_ops = (uint32_t*)sp_pool(ctx, ops_name, (size_t)ops_cap * 4);
             if (!d_ops) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, who + ": op rows");
-            SP_HIP_CHECK(ctx, hipMemsetAsync(d_cur, 0, 32, ctx->stream));
+            if (keep_rows && s2 > 0) {
+                SP_HIP_CHECK(ctx, hipMemsetAsync(d_cur + 1, 0, 24, ctx->stream));                        // (the status words and the retry counter; the cursor stands ...
+                if (attempt > 0) { *h_keep = kept; SP_HIP_CHECK(ctx, hipMemcpyAsync(d_cur, h_keep, 8, hipMemcpyHostToDevice, ctx->stream)); }      // ... or goes back behind the last finished slice)
+            } else SP_HIP_CHECK(ctx, hipMemsetAsync(d_cur, 0, 32, ctx->stream));
             uint64_t attempted = m;
             if (count_attempted) { attempted = 0; for (uint32_t i = 0; i < m; ++i) attempted += pairs[p0 + i].max_ed >= 0 ? 1 : 0; }
             int rc = sp_launch_affine_map(ctx, A, B, d_pairs + p0, m, *opts, band, d_aln + p0, d_nc + p0, d_off + p0, d_ops, ops_cap, d_cur, prof[0], nullptr, nullptr, attempted);
@@ -847,8 +1228,20 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
             if (hipStreamSynchronize(ctx->stream) != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": the map kernel failed");
             if (h_st[0] <= ops_cap) break;
             if (attempt == 1) return sp_fail(ctx, SP_ERR_HIP, who + ": the op buffer did not hold a second run");
+            if (keep_rows && s2 > 0) {
+                // what this slice needs on top of the rows kept, and for the pairs still to come what the pairs so far took each, and a quarter
+                const uint64_t done = (uint64_t)p0 + m, per_pair = (h_st[0] + done - 1) / done;
+                const uint64_t new_cap = std::max<uint64_t>(2 * ops_cap, h_st[0] + per_pair * (n - done) * 5 / 4 + 64);
+                const char* other = std::strcmp(ops_name, "appile_ops") == 0 ? "appile_ops_b" : "appile_ops";
+                uint32_t* d_new = (uint32_t*)sp_pool(ctx, other, (size_t)new_cap * 4);
+                if (!d_new) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, who + ": op rows");
+                if (kept) SP_HIP_CHECK(ctx, hipMemcpyAsync(d_new, d_ops, (size_t)kept * 4, hipMemcpyDeviceToDevice, ctx->stream));
+                ops_name = other; ops_cap = new_cap;
+                continue;
+            }
             ops_cap = h_st[0];
         }
+        if (keep_rows && m > 0) kept = h_st[0];
         if (m > 0) {
             const uint32_t* st = (const uint32_t*)(h_st + 1);
             if (st[0]) return sp_fail(ctx, SP_ERR_HIP, who + ": a walk did not reach the cell its path started in");
@@ -881,17 +1274,23 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
     if (cols && n_cols) SP_HIP_CHECK(ctx, hipMemcpyAsync(cols, d_table, n_cols * sizeof(sp_pileup_col), hipMemcpyDeviceToHost, ctx->stream));
     if (d_sum) SP_HIP_CHECK(ctx, hipMemcpyAsync(summaries, d_sum, (size_t)n_t * sizeof(sp_support_summary), hipMemcpyDeviceToHost, ctx->stream));
     SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    int32_t rc_ins = SP_OK;
     if (ins) {
-        // the list last: everything else is complete when it does not fit.  A run buffer that was guessed too small: the whole pass once more on one that holds them
-        // (the op rows of the earlier slices are gone) -- a warm context's buffer is large enough
+        // the lists last: everything else is complete when one does not fit.  A run buffer that was guessed too small: the whole pass once more on one that holds them
+        // (the op rows of the earlier slices are gone) -- a warm context's buffer is large enough.  That is decided before the haplotype list is made.
         uint64_t grow = 0;
-        const int32_t rc = ins_finish(ctx, who, ip, ins, ins_cap, n_ins, &grow);
-        if (rc != SP_OK) return rc;
+        rc_ins = ins_finish(ctx, who, ip, ins, ins_cap, n_ins, &grow);
+        if (rc_ins != SP_OK && !(hap && rc_ins == SP_ERR_CAPACITY && *n_ins > ins_cap)) return rc_ins;      // (with the other list asked for, that one is still made)
         if (grow) {
             if (ins_runs) return sp_fail(ctx, SP_ERR_HIP, who + ": the run buffer did not hold a second run");
-            return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, who, prof, count_attempted, ins, ins_cap, n_ins, grow);
+            return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, who, prof, count_attempted, ins, ins_cap, n_ins, grow, hap);
         }
     }
+    if (hap) {
+        const int32_t rc = hap_run(ctx, who, A, B, n, d_table, (const uint64_t*)(d_in + at_cols), d_pairs, d_aln, d_nc, d_off, d_ops, true, d_order, d_boff, n_slices, *hap);
+        if (rc != SP_OK) return rc;
+    }
+    if (rc_ins != SP_OK) return sp_fail(ctx, rc_ins, who + ": " + std::to_string(*n_ins) + " insertion records, room for " + std::to_string(ins_cap));
     return SP_OK;
 }
 
@@ -908,6 +1307,16 @@ int32_t sp_align_pileup_ins_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqs
     if (!ctx) return SP_ERR_INVALID_ARG;
     static const char* const prof[4] = { "align_pileup_map", "align_pileup_map_retry", "align_pileup_pile", "align_pileup_summary" };
     return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, "align_pileup", prof, false, ins, ins_cap, n_ins);
+}
+
+int32_t sp_align_pileup_hap_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
+                                  const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
+                                  sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins, sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    static const char* const prof[4] = { "align_pileup_map", "align_pileup_map_retry", "align_pileup_pile", "align_pileup_summary" };
+    HapOut ho; ho.haps = haps; ho.cap = hap_cap; ho.n_haps = n_haps; ho.heads = heads;
+    return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, "align_pileup", prof, false, ins, ins_cap, n_ins, 0,
+                            haps ? &ho : nullptr);
 }
 
 int32_t sp_align_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, const uint64_t* col_offset,
@@ -942,6 +1351,13 @@ int32_t sp_consensus_support_json(const sp_support_entry* entries, uint32_t n_en
 
 int32_t sp_consensus_support_json_ins(const sp_support_entry* entries, uint32_t n_entries, const uint64_t* col_base, const sp_pileup_ins* ins, uint64_t n_ins,
                                       const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed) {
+    return sp_consensus_support_json_hap(entries, n_entries, col_base, ins, n_ins, nullptr, 0, nullptr, 0, nullptr, read_names, n_read_names, out, cap, needed);
+}
+
+int32_t sp_consensus_support_json_hap(const sp_support_entry* entries, uint32_t n_entries, const uint64_t* col_base, const sp_pileup_ins* ins, uint64_t n_ins,
+                                      const sp_support_hap* haps, uint64_t n_haps, const sp_support_hap_head* heads, uint64_t n_heads, const uint64_t* hap_target,
+                                      const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed) {
+    if (n_haps && (!haps || !heads || (n_entries && !hap_target))) return SP_ERR_INVALID_ARG;
     if ((n_entries && !entries) || (cap && !out) || (n_ins && !ins) || (n_entries && n_ins && !col_base)) return SP_ERR_INVALID_ARG;     // (without entries no col_base is read)
     std::vector<uint32_t> order;
     for (uint32_t e = 0; e < n_entries; ++e) {
@@ -982,6 +1398,10 @@ int32_t sp_consensus_support_json_ins(const sp_support_entry* entries, uint32_t 
                 list.arr.push_back(std::move(k));
             }
             v.obj.emplace_back("contested", std::move(list));
+            if (n_haps) {
+                const uint64_t target = hap_target[2 * (size_t)order[o] + c];
+                if (target < n_heads) spi_support_hap_json(&v, cols, sm.length, haps, n_haps, heads + target, target, nullptr, 0, read_names, n_read_names);
+            }
             gene.obj.emplace_back(c ? "consensus2" : "consensus1", std::move(v));
         }
         if (!gene.obj.empty()) root.obj.emplace_back(en.gene, std::move(gene));
@@ -998,9 +1418,19 @@ int32_t sp_hla_consensus_support_cohort_ins(sp_ctx* ctx, const sp_hla_db* db, ui
                                             const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1, const char* cons, uint32_t cap,
                                             const uint8_t* unit_on, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries,
                                             sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
+    return sp_hla_consensus_support_cohort_hap(ctx, db, n_samples, read_sample, n_genes, genes, reads, realign, is_cons1, cons, cap, unit_on, col_offset, cols, cols_cap, summaries,
+                                               ins, ins_cap, n_ins, nullptr, 0, nullptr, nullptr);
+}
+
+int32_t sp_hla_consensus_support_cohort_hap(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
+                                            const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1, const char* cons, uint32_t cap,
+                                            const uint8_t* unit_on, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries,
+                                            sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
+                                            sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
     if (!ctx) return SP_ERR_INVALID_ARG;
-    if (ins && !n_ins) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: null argument");
+    if ((ins && !n_ins) || (haps && (!n_haps || !heads))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: null argument");
     if (ins) *n_ins = 0;
+    if (haps) *n_haps = 0;
     if (!db || !reads || !col_offset || !summaries || n_samples == 0 || (n_genes && (!genes || !cons || cap == 0)) || (reads->n && (!realign || !is_cons1)) || (n_samples > 1 && !read_sample))
         return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: null argument");
     const uint64_t n_units = (uint64_t)n_samples * n_genes;
@@ -1027,7 +1457,9 @@ int32_t sp_hla_consensus_support_cohort_ins(sp_ctx* ctx, const sp_hla_db* db, ui
     if (n_cols > cols_cap || (n_cols && !cols)) return sp_fail(ctx, SP_ERR_CAPACITY, "consensus support: " + std::to_string(n_cols) + " columns, room for " + std::to_string(cols ? cols_cap : 0));
     std::memset(summaries, 0, sizeof(sp_support_summary) * 2 * n_units);
     const uint32_t n_t = (uint32_t)toff.size() - 1;
-    if (n_t == 0) return SP_OK;
+    if (n_t == 0) { if (haps) std::memset(heads, 0, sizeof(sp_support_hap_head) * 2 * n_units); return SP_OK; }
+    std::vector<sp_support_hap_head> t_heads(haps ? n_t : 0);
+    HapOut ho; ho.haps = haps; ho.cap = hap_cap; ho.n_haps = n_haps; ho.heads = t_heads.data();
     // ---- the members: the realigned reads of every unit whose group has a consensus; their segments on the gene strand
     std::vector<uint32_t> m_target, m_read; std::vector<uint32_t> members_of(n_t, 0);
     std::string qblob; std::vector<uint64_t> qoff(1, 0);
@@ -1070,8 +1502,8 @@ int32_t sp_hla_consensus_support_cohort_ins(sp_ctx* ctx, const sp_hla_db* db, ui
         // (the pileup launch keeps the profile name it has had in this pass: "pileup")
         static const char* const prof[4] = { "consensus_support_map", "consensus_support_map_retry", "pileup", "consensus_support_summary" };
         rc = align_pileup_run(ctx, &Q, &T, pairs.data(), n_m, &ao, 64, 256, t_cols.data(), nullptr, table.data(), sums.data(), members_of.data(), nullptr, "consensus support", prof, true,
-                              ins, ins_cap, n_ins);
-        if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ins && *n_ins > ins_cap)) return rc;
+                              ins, ins_cap, n_ins, 0, haps ? &ho : nullptr);
+        if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ((ins && *n_ins > ins_cap) || (haps && *n_haps > hap_cap)))) return rc;
     } else for (uint32_t t = 0; t < n_t; ++t) sp_support_summarize(table.data() + t_cols[t], (uint32_t)(t_cols[t + 1] - t_cols[t]), 0, 0, &sums[t]);
     for (uint64_t x = 0; x < 2 * n_units; ++x) {
         const int32_t t = target_of[x];
@@ -1081,8 +1513,8 @@ int32_t sp_hla_consensus_support_cohort_ins(sp_ctx* ctx, const sp_hla_db* db, ui
         std::memcpy(cols + col_offset[x], src, sizeof(sp_pileup_col) * (size_t)len);
         summaries[x] = sums[t];
     }
-    if (rc != SP_OK) return rc;                                                        // (the list did not fit: everything else is complete)
-    if (ins && *n_ins) {
+    // (a list that did not fit: everything else is complete, the other list included)
+    if (ins && *n_ins && *n_ins <= ins_cap) {
         // the list in the caller's terms: the targets are the consensuses that have columns, in col_offset's order, so the records stay in order
         std::vector<uint64_t> base(n_t, 0);
         for (uint64_t x = 0; x < 2 * n_units; ++x) if (target_of[x] >= 0) base[target_of[x]] = col_offset[x];
@@ -1092,7 +1524,18 @@ int32_t sp_hla_consensus_support_cohort_ins(sp_ctx* ctx, const sp_hla_db* db, ui
             if (ins[k].len) ins[k].first_pair = m_read[ins[k].first_pair];
         }
     }
-    return SP_OK;
+    if (haps && *n_haps <= hap_cap) {
+        // the haplotype list in the caller's terms: target = the slot of col_offset, first_pair = the member read; a slot without a target has an empty head
+        std::vector<uint64_t> slot_of(n_t, 0);
+        uint64_t at = 0;
+        for (uint64_t x = 0; x < 2 * n_units; ++x) {
+            const int32_t t = target_of[x];
+            if (t >= 0) { slot_of[t] = x; heads[x] = t_heads[t]; at = t_heads[t].first_record + t_heads[t].n_records; }
+            else { heads[x] = sp_support_hap_head{}; heads[x].first_record = at; }
+        }
+        for (uint64_t k = 0; k < *n_haps; ++k) { haps[k].target = slot_of[haps[k].target]; haps[k].first_pair = m_read[haps[k].first_pair]; }
+    }
+    return rc;
 }
 
 int32_t sp_hla_consensus_support_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
@@ -1104,6 +1547,12 @@ int32_t sp_hla_consensus_support_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32
 int32_t sp_hla_consensus_support_ins(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1,
                                      const char* cons1, const char* cons2, sp_pileup_col* cols1, sp_pileup_col* cols2, sp_support_summary* s1, sp_support_summary* s2,
                                      sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
+    return sp_hla_consensus_support_hap(ctx, db, gene, reads, realign, is_cons1, cons1, cons2, cols1, cols2, s1, s2, ins, ins_cap, n_ins, nullptr, 0, nullptr, nullptr);
+}
+
+int32_t sp_hla_consensus_support_hap(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1,
+                                     const char* cons1, const char* cons2, sp_pileup_col* cols1, sp_pileup_col* cols2, sp_support_summary* s1, sp_support_summary* s2,
+                                     sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins, sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
     if (!ctx) return SP_ERR_INVALID_ARG;
     if (!cons1 || !cons2) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: null argument");
     const size_t l1 = cols1 && s1 ? std::strlen(cons1) : 0, l2 = cols2 && s2 ? std::strlen(cons2) : 0;
@@ -1112,8 +1561,9 @@ int32_t sp_hla_consensus_support_ins(sp_ctx* ctx, const sp_hla_db* db, uint32_t 
     std::memcpy(both.data(), cons1, l1); std::memcpy(both.data() + cap, cons2, l2);
     uint64_t off[3]; sp_support_summary sm[2];
     std::vector<sp_pileup_col> table(l1 + l2);
-    const int32_t rc = sp_hla_consensus_support_cohort_ins(ctx, db, 1, nullptr, 1, &gene, reads, realign, is_cons1, both.data(), cap, nullptr, off, table.data(), table.size(), sm, ins, ins_cap, n_ins);
-    if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ins && n_ins && *n_ins > ins_cap)) return rc;
+    const int32_t rc = sp_hla_consensus_support_cohort_hap(ctx, db, 1, nullptr, 1, &gene, reads, realign, is_cons1, both.data(), cap, nullptr, off, table.data(), table.size(), sm, ins, ins_cap, n_ins,
+                                                           haps, hap_cap, n_haps, heads);
+    if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ((ins && n_ins && *n_ins > ins_cap) || (haps && n_haps && *n_haps > hap_cap)))) return rc;
     if (cols1 && s1) { std::memcpy(cols1, table.data(), sizeof(sp_pileup_col) * l1); *s1 = sm[0]; }
     if (cols2 && s2) { std::memcpy(cols2, table.data() + off[1], sizeof(sp_pileup_col) * l2); *s2 = sm[1]; }
     return rc;

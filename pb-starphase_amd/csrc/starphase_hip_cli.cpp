@@ -43,6 +43,7 @@ const char* HELP_HEAD =
     "      --debug-consensus-support    Also write consensus_support.json: how the member reads back each HLA consensus, column by column (needs --output-debug)\n"
     "      --debug-cyp2d6-support       Also write cyp2d6_consensus_support.json: the same for each CYP2D6 consensus region (needs --output-debug)\n"
     "      --debug-support-insertions   Those two files also list the inserted strings behind the columns their insertions contest (with one of the two switches above)\n"
+    "      --debug-support-haplotypes   Those two files also list the read haplotypes: the patterns of calls the reads make at the contested columns (with one of the two switches above)\n"
     "      --sample-name <STRING>       Sample name from the input VCFs (default: first sample)\n"
     "\n";
 const char* BATCH_HELP_HEAD =
@@ -97,6 +98,7 @@ const char* BATCH_HELP_TAIL =
     "      --debug-consensus-support    Also write every sample's consensus_support.json (needs an output_debug column that names a folder)\n"
     "      --debug-cyp2d6-support       Also write every sample's cyp2d6_consensus_support.json (needs an output_debug column that names a folder)\n"
     "      --debug-support-insertions   Those two files also list the inserted strings behind the columns their insertions contest (with one of the two switches above)\n"
+    "      --debug-support-haplotypes   Those two files also list the read haplotypes: the patterns of calls the reads make at the contested columns (with one of the two switches above)\n"
     "  -v, --verbose...                 Enable verbose output (print the warnings and the timings of the batch)\n"
     "  -h, --help                       Print help\n"
     "\n"
@@ -146,7 +148,7 @@ bool parse_u64(const std::string& s, uint64_t* out) {
 struct Options {
     sp_diplotype_settings s;
     std::string database, reference, include, exclude;
-    int verbose = 0; bool debug_reads = false, debug_hla_mappings = false, debug_consensus_support = false, debug_cyp2d6_support = false, debug_support_insertions = false;
+    int verbose = 0; bool debug_reads = false, debug_hla_mappings = false, debug_consensus_support = false, debug_cyp2d6_support = false, debug_support_insertions = false, debug_support_haplotypes = false;
 };
 
 // the option being parsed: its name (a `--key=value` split) and where its value comes from.  need*: 0, or the exit status of the clap error
@@ -200,6 +202,7 @@ int parse_options(int argc, char** argv, const char* usage, const std::string& h
         else if (a == "--debug-consensus-support") o.debug_consensus_support = true;
         else if (a == "--debug-cyp2d6-support") o.debug_cyp2d6_support = true;
         else if (a == "--debug-support-insertions") o.debug_support_insertions = true;
+        else if (a == "--debug-support-haplotypes") o.debug_support_haplotypes = true;
         else if (a == "-v" || a == "--verbose") ++o.verbose;
         else if (a.size() > 2 && a[0] == '-' && a[1] == 'v' && a.find_first_not_of('v', 1) == std::string::npos) o.verbose += (int)a.size() - 1;
         else if (a == "--max-sv-length") { if (!(rc = arg.need_u64(&u))) s.max_sv_length = u; }
@@ -243,6 +246,7 @@ sp_starphase* create_handle(const Options& o, int* code) {
     if (o.debug_consensus_support) sp_starphase_set_consensus_support(h, 1);
     if (o.debug_cyp2d6_support) sp_starphase_set_cyp_consensus_support(h, 1);
     if (o.debug_support_insertions) sp_starphase_set_support_insertions(h, 1);
+    if (o.debug_support_haplotypes) sp_starphase_set_support_haplotypes(h, 1);
     return h;
 }
 

@@ -162,6 +162,9 @@ def _lib():
         "sp_cyp_consensus_support_ins": (_i32, [_vp, _vp, P(ffi.sp_cyp_call), _vp, _u32, P(sp_cyp_read_mapping), _u64, _vp, _vp, _u64, _vp, _vp, _u64, P(_u64)]),
         "sp_cyp_consensus_support_cohort_ins": (_i32, [_vp, _u32, P(_vp), P(ffi.sp_cyp_call), _vp, _u32, P(sp_cyp_read_mapping), _vp, _vp, _vp, _u64, _vp, _vp, _u64, P(_u64)]),
         "sp_cyp_support_json_ins": (_i32, [P(ffi.sp_cyp_call), _vp, _u32, _vp, _vp, _vp, _vp, _u64, P(sp_cyp_read_mapping), _u64, P(C.c_char_p), _u32, _s, _u64, P(_u64)]),
+        "sp_cyp_consensus_support_hap": (_i32, [_vp, _vp, P(ffi.sp_cyp_call), _vp, _u32, P(sp_cyp_read_mapping), _u64, _vp, _vp, _u64, _vp, _vp, _u64, P(_u64), _vp, _u64, P(_u64), _vp]),
+        "sp_cyp_consensus_support_cohort_hap": (_i32, [_vp, _u32, _vp, _vp, _vp, _u32, P(sp_cyp_read_mapping), _vp, _vp, _vp, _u64, _vp, _vp, _u64, P(_u64), _vp, _u64, P(_u64), _vp]),
+        "sp_cyp_support_json_hap": (_i32, [P(ffi.sp_cyp_call), _vp, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, P(sp_cyp_read_mapping), _u64, P(C.c_char_p), _u32, _s, _u64, P(_u64)]),
         "sp_diplotype_settings_default": (None, [P(sp_diplotype_settings)]),
         "sp_diplotype_settings_check": (_i32, [P(sp_diplotype_settings), P(sp_sample_inputs), _s, _u32]),
         "sp_starphase_create": (_i32, [_vp, _s, _s, P(sp_diplotype_settings), P(_vp)]),
@@ -175,6 +178,7 @@ def _lib():
         "sp_starphase_set_consensus_support": (_i32, [_vp, _i32]),
         "sp_starphase_set_cyp_consensus_support": (_i32, [_vp, _i32]),
         "sp_starphase_set_support_insertions": (_i32, [_vp, _i32]),
+        "sp_starphase_set_support_haplotypes": (_i32, [_vp, _i32]),
         "sp_starphase_call_batch": (_i32, [_vp, _u32, P(sp_sample_inputs), P(_s), P(sp_batch_options), P(_vp), P(_i32)]),
         "sp_starphase_sample_error": (_s, [_vp, _u32]),
         "sp_starphase_sample_warnings": (_s, [_vp, _u32]),
@@ -958,7 +962,7 @@ class Starphase:
     set_cyp_consensus_support() at once (it also writes cyp2d6_consensus_support.json); support_insertions=True: set_support_insertions() at once (those two files
     also list the inserted strings of the columns their insertions contest)."""
 
-    def __init__(self, database, reference=None, ctx=None, consensus_support=False, cyp_consensus_support=False, support_insertions=False, **settings):
+    def __init__(self, database, reference=None, ctx=None, consensus_support=False, cyp_consensus_support=False, support_insertions=False, support_haplotypes=False, **settings):
         self._h = _vp()
         self._s = _settings(**settings)
         rc = _lib().sp_starphase_create(ctx._h if ctx is not None else None, _b(database), _b(reference), C.byref(self._s), C.byref(self._h))
@@ -970,6 +974,8 @@ class Starphase:
             self.set_cyp_consensus_support(True)
         if support_insertions:
             self.set_support_insertions(True)
+        if support_haplotypes:
+            self.set_support_haplotypes(True)
 
     def close(self):
         if self._h:
@@ -988,6 +994,14 @@ class Starphase:
         rc = _lib().sp_starphase_set_consensus_support(self._h, 1 if on else 0)
         if rc != SP_OK:
             raise StarphaseError(rc, "sp_starphase_set_consensus_support")
+        return self
+
+    def set_support_haplotypes(self, on=True):
+        """sp_starphase_set_support_haplotypes: consensus_support.json and cyp2d6_consensus_support.json, where their own switches write them, also carry "haplotypes":
+        the distinct patterns of calls the member reads make at the contested columns, with counts.  Off by default; no effect without one of those switches."""
+        rc = _lib().sp_starphase_set_support_haplotypes(self._h, 1 if on else 0)
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_starphase_set_support_haplotypes")
         return self
 
     def set_support_insertions(self, on=True):
@@ -1139,9 +1153,10 @@ def _mapping_array(mappings):
     return arr
 
 
-def cyp_consensus_support(ctx, reads, call, cons, cons_cap, mappings, want_cols=True, insertions=False):
+def cyp_consensus_support(ctx, reads, call, cons, cons_cap, mappings, want_cols=True, insertions=False, haplotypes=False):
     """sp_cyp_consensus_support: call / cons / mappings as cyp_call_with_consensus returned them -> ([cols PILEUP_DTYPE per consensus] or None, [summary dict per consensus]).
-    insertions=True (sp_cyp_consensus_support_ins) adds the INS_DTYPE records (col: consensus h's columns from the sum of the lengths before it) as a third item"""
+    insertions=True (sp_cyp_consensus_support_ins) adds the INS_DTYPE records (col: consensus h's columns from the sum of the lengths before it) as a third item;
+    haplotypes=True (sp_cyp_consensus_support_hap) adds, last, (HAP_DTYPE records, HAP_HEAD_DTYPE per consensus): target h, first_pair the member's mapping record"""
     import numpy as np
     H = max(0, min(call.n_consensus, ffi.SP_CYP_MAXCONS))
     off = np.zeros(ffi.SP_CYP_MAXCONS + 1, np.uint64)
@@ -1150,17 +1165,32 @@ def cyp_consensus_support(ctx, reads, call, cons, cons_cap, mappings, want_cols=
     sm = np.zeros(ffi.SP_CYP_MAXCONS, ffi.SUPPORT_DTYPE)
     arr = _mapping_array(mappings)
     ins = None
-    if insertions:
+    if haplotypes:
+        n_i = _u64(0)
+        ibuf = [np.zeros(16384, ffi.INS_DTYPE) if insertions else None]
+
+        def run(haps, cap, n, heads):
+            rc = _lib().sp_cyp_consensus_support_hap(ctx._h, reads._h, C.byref(call), C.cast(cons, _vp), cons_cap, arr, len(mappings), ffi._ptr(off), ffi._ptr(cols), total, ffi._ptr(sm),
+                                                     ffi._ptr(ibuf[0]), len(ibuf[0]) if insertions else 0, C.byref(n_i) if insertions else None, haps, cap, n, heads)
+            if insertions and rc == ffi.SP_ERR_CAPACITY and n_i.value > len(ibuf[0]):
+                ibuf[0] = np.zeros(n_i.value, ffi.INS_DTYPE)
+                return run(haps, cap, n, heads)
+            return rc
+        hap = ctx._with_haps(run, 4096, ffi.SP_CYP_MAXCONS)
+        hap = (hap[0], hap[1][:H].copy())
+        ins = ibuf[0][:n_i.value].copy() if insertions else None
+    elif insertions:
         ins = ctx._with_ins(lambda ins, cap, n: _lib().sp_cyp_consensus_support_ins(ctx._h, reads._h, C.byref(call), C.cast(cons, _vp), cons_cap, arr, len(mappings), ffi._ptr(off),
                                                                                     ffi._ptr(cols), total, ffi._ptr(sm), ins, cap, n), 16384)
     else:
         ctx.check(_lib().sp_cyp_consensus_support(ctx._h, reads._h, C.byref(call), C.cast(cons, _vp), cons_cap, arr, len(mappings), ffi._ptr(off), ffi._ptr(cols), total, ffi._ptr(sm)))
     res = ([cols[int(off[h]):int(off[h + 1])].copy() for h in range(H)] if want_cols else None,
            [{n: int(sm[h][n]) for n in ffi.SUPPORT_FIELDS[:-1]} for h in range(H)])
-    return res + (ins,) if insertions else res
+    res = res + (ins,) if insertions else res
+    return res + (hap,) if haplotypes else res
 
 
-def cyp_consensus_support_cohort(ctx, read_sets, calls, cons_blocks, cons_cap, mapping_lists, insertions=False):
+def cyp_consensus_support_cohort(ctx, read_sets, calls, cons_blocks, cons_cap, mapping_lists, insertions=False, haplotypes=False):
     """sp_cyp_consensus_support_cohort: per sample what cyp_call_with_consensus returned -> per sample ([cols per consensus], [summary dict per consensus]).
     insertions=True (sp_cyp_consensus_support_cohort_ins): -> (that, INS_DTYPE records, col_offset uint64[n * SP_CYP_MAXCONS + 1])"""
     import numpy as np
@@ -1180,7 +1210,21 @@ def cyp_consensus_support_cohort(ctx, read_sets, calls, cons_blocks, cons_cap, m
     sm = np.zeros(n * M, ffi.SUPPORT_DTYPE)
     marr = _mapping_array(flat)
     ins = None
-    if insertions:
+    if haplotypes:
+        # sp_cyp_consensus_support_cohort_hap: -> (that, INS_DTYPE records or None, col_offset, (HAP_DTYPE records, HAP_HEAD_DTYPE per slot sample * SP_CYP_MAXCONS + h))
+        n_i = _u64(0)
+        ibuf = [np.zeros(16384, ffi.INS_DTYPE) if insertions else None]
+
+        def run(haps, hcap, k, heads):
+            rc = _lib().sp_cyp_consensus_support_cohort_hap(ctx._h, n, handles, carr, C.cast(block, _vp), cons_cap, marr, ffi._ptr(moff), ffi._ptr(off), ffi._ptr(cols), total, ffi._ptr(sm),
+                                                            ffi._ptr(ibuf[0]), len(ibuf[0]) if insertions else 0, C.byref(n_i) if insertions else None, haps, hcap, k, heads)
+            if insertions and rc == ffi.SP_ERR_CAPACITY and n_i.value > len(ibuf[0]):
+                ibuf[0] = np.zeros(n_i.value, ffi.INS_DTYPE)
+                return run(haps, hcap, k, heads)
+            return rc
+        hap = ctx._with_haps(run, 16384, n * M)
+        ins = ibuf[0][:n_i.value].copy() if insertions else None
+    elif insertions:
         ins = ctx._with_ins(lambda ins, cap, k: _lib().sp_cyp_consensus_support_cohort_ins(ctx._h, n, handles, carr, C.cast(block, _vp), cons_cap, marr, ffi._ptr(moff), ffi._ptr(off),
                                                                                            ffi._ptr(cols), total, ffi._ptr(sm), ins, cap, k), 16384)
     else:
@@ -1189,13 +1233,15 @@ def cyp_consensus_support_cohort(ctx, read_sets, calls, cons_blocks, cons_cap, m
     for i in range(n):
         H = max(0, min(calls[i].n_consensus, M)) if calls[i].status == 0 else 0
         out.append(([cols[int(off[i * M + h]):int(off[i * M + h + 1])].copy() for h in range(H)], [{k: int(sm[i * M + h][k]) for k in ffi.SUPPORT_FIELDS[:-1]} for h in range(H)]))
+    if haplotypes:
+        return out, ins, off.copy(), hap
     return (out, ins, off.copy()) if insertions else out
 
 
-def cyp_support_json(call, consensus, cols, summaries, cap=None, insertions=None, mappings=None, read_names=None):
+def cyp_support_json(call, consensus, cols, summaries, cap=None, insertions=None, mappings=None, read_names=None, haplotypes=None):
     """sp_cyp_support_json (host only): consensus = [text per consensus], cols = [PILEUP_DTYPE per consensus], summaries = [dict per consensus] -> the text of
     cyp2d6_consensus_support.json.  cap: a buffer size to try -> (status, text, needed).  insertions (INS_DTYPE; mappings and read_names optional, for first_read):
-    sp_cyp_support_json_ins"""
+    sp_cyp_support_json_ins; haplotypes = (HAP_DTYPE records, HAP_HEAD_DTYPE per consensus): sp_cyp_support_json_hap"""
     import numpy as np
     H = len(consensus)
     cons_cap = max([len(s) for s in consensus] + [0]) + 1
@@ -1211,6 +1257,21 @@ def cyp_support_json(call, consensus, cols, summaries, cap=None, insertions=None
             sm[h][k] = int(d.get(k, 0))
     need = _u64(0)
     args = (C.byref(call), C.cast(block, _vp), cons_cap, ffi._ptr(off), ffi._ptr(table), ffi._ptr(sm))
+    if haplotypes is not None:
+        ins = np.ascontiguousarray(insertions if insertions is not None else np.zeros(0, ffi.INS_DTYPE), ffi.INS_DTYPE)
+        haps, heads = np.ascontiguousarray(haplotypes[0], ffi.HAP_DTYPE), np.ascontiguousarray(haplotypes[1], ffi.HAP_HEAD_DTYPE)
+        marr = _mapping_array(mappings) if mappings is not None else None
+        names, n_names = ffi._name_array(read_names)
+        more = (ffi._ptr(ins) if len(ins) else None, len(ins), ffi._ptr(haps) if len(haps) else None, len(haps), ffi._ptr(heads) if len(heads) else None, 0,
+                marr, len(mappings) if mappings is not None else 0, names, n_names)
+        rc = _lib().sp_cyp_support_json_hap(*args, *more, None, 0, C.byref(need))
+        if rc not in (SP_OK, ffi.SP_ERR_CAPACITY):
+            raise StarphaseError(rc, "sp_cyp_support_json_hap")
+        buf = C.create_string_buffer(need.value)
+        rc = _lib().sp_cyp_support_json_hap(*args, *more, buf, need.value, C.byref(need))
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_cyp_support_json_hap")
+        return buf.value.decode()
     if insertions is not None:
         ins = np.ascontiguousarray(insertions, ffi.INS_DTYPE)
         marr = _mapping_array(mappings) if mappings is not None else None

@@ -249,6 +249,13 @@ INS_DTYPE = np.dtype([("col", np.uint64), ("len", np.uint32), ("count", np.uint3
                       ("first_pair", np.uint32), ("first_qpos", np.uint32), ("n_other", np.uint32), ("reserved_", np.uint32)])
 
 
+# sp_support_hap: one record per distinct (target, pattern of calls at the target's first SP_SUPPORT_HAP_COLS contested columns); sp_support_hap_head: one per target
+SP_SUPPORT_HAP_COLS = 64
+SP_SUPPORT_HAP_LDS_KEYS = 1024
+HAP_DTYPE = np.dtype([("target", np.uint64), ("n_cols", np.uint32), ("count", np.uint32), ("first_pair", np.uint32), ("reserved_", np.uint32), ("w", np.uint64, (4,))])
+HAP_HEAD_DTYPE = np.dtype([("first_record", np.uint64), ("n_records", np.uint32), ("n_cols", np.uint32), ("n_cols_total", np.uint32), ("reserved_", np.uint32)])
+
+
 class sp_support_summary(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in SUPPORT_FIELDS]
 
@@ -289,17 +296,37 @@ def support_ins_string(rec, queries=None, query=0):
     return buf.value.decode()
 
 
+def support_hap_string(rec):
+    """sp_support_hap_string (host only): one HAP_DTYPE record -> its calls as text, one token per used column (= ACGT - ?, each with + for an insertion behind it)"""
+    one = np.ascontiguousarray(np.asarray(rec, HAP_DTYPE).reshape(1))
+    buf = C.create_string_buffer(2 * SP_SUPPORT_HAP_COLS + 1)
+    need = C.c_uint64(0)
+    rc = lib().sp_support_hap_string(_ptr(one), buf, len(buf), C.byref(need))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_support_hap_string")
+    return buf.value.decode()
+
+
 def _name_array(names):
     if names is None:
         return None, 0
     return (C.c_char_p * max(1, len(names)))(*[n.encode() if n is not None else None for n in names]), len(names)
 
 
-def consensus_support_json(entries, insertions=None, col_base=None, read_names=None):
+def consensus_support_json(entries, insertions=None, col_base=None, read_names=None, haplotypes=None, hap_target=None):
     """sp_consensus_support_json (host only): entries = [(gene, [(typed_allele or None, gene-strand consensus, cols PILEUP_DTYPE, summary dict) or None] * 2)]
     -> the text of consensus_support.json.  insertions (INS_DTYPE, with col_base = [(col of column 0 of consensus1, of consensus2)] per entry and, optionally,
-    read_names indexed by first_pair): sp_consensus_support_json_ins"""
-    if insertions is not None:
+    read_names indexed by first_pair): sp_consensus_support_json_ins.  haplotypes = (HAP_DTYPE records, HAP_HEAD_DTYPE heads indexed by target) with hap_target =
+    [(target of consensus1, of consensus2)] per entry: sp_consensus_support_json_hap"""
+    if haplotypes is not None:
+        ins = np.ascontiguousarray(insertions if insertions is not None else np.zeros(0, INS_DTYPE), INS_DTYPE)
+        base = np.ascontiguousarray(np.asarray(col_base, np.uint64).reshape(-1), np.uint64) if (len(entries) and col_base is not None) else np.zeros(max(2, 2 * len(entries)), np.uint64)
+        haps, heads = np.ascontiguousarray(haplotypes[0], HAP_DTYPE), np.ascontiguousarray(haplotypes[1], HAP_HEAD_DTYPE)
+        tgt = np.ascontiguousarray(np.asarray(hap_target, np.uint64).reshape(-1), np.uint64) if len(entries) else np.zeros(2, np.uint64)
+        names, n_names = _name_array(read_names)
+        render = lambda a, n, out, cap, need: lib().sp_consensus_support_json_hap(a, n, _ptr(base), _ptr(ins) if len(ins) else None, len(ins), _ptr(haps) if len(haps) else None, len(haps),
+                                                                                  _ptr(heads) if len(heads) else None, len(heads), _ptr(tgt), names, n_names, out, cap, need)
+    elif insertions is not None:
         ins = np.ascontiguousarray(insertions, INS_DTYPE)
         base = np.ascontiguousarray(np.asarray(col_base, np.uint64).reshape(-1), np.uint64) if len(entries) else np.zeros(2, np.uint64)
         names, n_names = _name_array(read_names)
@@ -365,9 +392,16 @@ def lib():
         "sp_pileup_ins_batch": (i32, [vp, vp, vp, vp, u64, vp, vp, u32, vp, vp, vp, u64, C.POINTER(u64)]),
         "sp_align_pileup_ins_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, i32, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]),
         "sp_support_ins_string": (i32, [vp, vp, u32, C.c_char_p, u64, C.POINTER(u64)]),
+        "sp_pileup_hap_batch": (i32, [vp, vp, vp, vp, u64, vp, vp, u32, vp, vp, vp, u64, C.POINTER(u64), vp]),
+        "sp_align_pileup_hap_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, i32, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), vp]),
+        "sp_support_hap_string": (i32, [vp, C.c_char_p, u64, C.POINTER(u64)]),
         "sp_hla_consensus_support_ins": (i32, [vp, vp, u32, vp, vp, vp, C.c_char_p, C.c_char_p, vp, vp, C.POINTER(sp_support_summary), C.POINTER(sp_support_summary), vp, u64, C.POINTER(u64)]),
         "sp_hla_consensus_support_cohort_ins": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp, C.c_char_p, u32, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]),
         "sp_consensus_support_json_ins": (i32, [C.POINTER(sp_support_entry), u32, vp, vp, u64, C.POINTER(C.c_char_p), u32, C.c_char_p, u64, C.POINTER(u64)]),
+        "sp_hla_consensus_support_hap": (i32, [vp, vp, u32, vp, vp, vp, C.c_char_p, C.c_char_p, vp, vp, C.POINTER(sp_support_summary), C.POINTER(sp_support_summary), vp, u64, C.POINTER(u64),
+                                               vp, u64, C.POINTER(u64), vp]),
+        "sp_hla_consensus_support_cohort_hap": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp, C.c_char_p, u32, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), vp]),
+        "sp_consensus_support_json_hap": (i32, [C.POINTER(sp_support_entry), u32, vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(C.c_char_p), u32, C.c_char_p, u64, C.POINTER(u64)]),
         "sp_support_summarize": (i32, [vp, u32, u32, u32, C.POINTER(sp_support_summary)]),
         "sp_support_contested": (i32, [vp, u32, vp, u32, C.POINTER(u32)]),
         "sp_hla_consensus_support": (i32, [vp, vp, u32, vp, vp, vp, C.c_char_p, C.c_char_p, vp, vp, C.POINTER(sp_support_summary), C.POINTER(sp_support_summary)]),
@@ -465,7 +499,8 @@ def lib():
         raise ImportError(f"{path}: ABI version {L.sp_abi_version()}, this binding was written for {SP_ABI_VERSION} (rebuild: __graft_entry__.build())")
     for name, size in (("sp_hla_realign", REALIGN_DTYPE.itemsize), ("sp_aln", ALN_DTYPE.itemsize), ("sp_k1_seed_hit", K1_HIT_DTYPE.itemsize),
                        ("sp_hla_best", C.sizeof(sp_hla_best)), ("sp_hla_realign", C.sizeof(sp_hla_realign)), ("sp_hla_rev_hit", REV_HIT_DTYPE.itemsize),
-                       ("sp_pileup_col", PILEUP_DTYPE.itemsize), ("sp_support_summary", SUPPORT_DTYPE.itemsize), ("sp_pileup_ins", INS_DTYPE.itemsize)):
+                       ("sp_pileup_col", PILEUP_DTYPE.itemsize), ("sp_support_summary", SUPPORT_DTYPE.itemsize), ("sp_pileup_ins", INS_DTYPE.itemsize),
+                       ("sp_support_hap", HAP_DTYPE.itemsize), ("sp_support_hap_head", HAP_HEAD_DTYPE.itemsize)):
         if L.sp_struct_size(name.encode()) != size:
             raise ImportError(f"{path}: {name} is {L.sp_struct_size(name.encode())} bytes in the library, {size} in this binding")
     _lib = L
@@ -577,6 +612,42 @@ class Context:
         self.check(rc)
         return ins[:n.value].copy()
 
+    def _with_haps(self, call, guess, n_heads, hap_cap=None):
+        """runs call(haps, cap, byref(n), heads) with room for `guess` records, once more with the room it asked for -> (HAP_DTYPE records, HAP_HEAD_DTYPE[n_heads]);
+        hap_cap: a capacity to try, once -> (status, records or None, n_haps, heads or None)"""
+        n = C.c_uint64(0)
+        heads = np.zeros(max(1, int(n_heads)), HAP_HEAD_DTYPE)
+        haps = np.zeros(max(1, int(guess if hap_cap is None else hap_cap)), HAP_DTYPE)
+        if hap_cap is not None:
+            rc = call(_ptr(haps), int(hap_cap), C.byref(n), _ptr(heads))
+            if rc not in (SP_OK, SP_ERR_CAPACITY):
+                self.check(rc)
+            return rc, (haps[:n.value].copy() if rc == SP_OK else None), n.value, (heads[:n_heads].copy() if rc == SP_OK else None)
+        rc = call(_ptr(haps), len(haps), C.byref(n), _ptr(heads))
+        if rc == SP_ERR_CAPACITY and n.value > len(haps):
+            haps = np.zeros(n.value, HAP_DTYPE)
+            rc = call(_ptr(haps), len(haps), C.byref(n), _ptr(heads))
+        self.check(rc)
+        return haps[:n.value].copy(), heads[:n_heads].copy()
+
+    def pileup_hap(self, A, B, pairs, aln, cigar, n_cigar, col_offset=None, hap_cap=None):
+        """sp_pileup_hap_batch: the arguments of pileup -> (HAP_DTYPE records, HAP_HEAD_DTYPE[B.n]): the distinct patterns of calls the alignments make at the contested
+        columns of their targets.  hap_cap: a capacity to try, once -> (status, records or None, n_haps, heads or None)"""
+        rows = np.zeros(len(pairs), PAIR_DTYPE)
+        for i, pr in enumerate(pairs):
+            rows[i] = (pr[0], pr[1], pr[2], pr[3] if len(pr) > 3 else 0)
+        aln = np.ascontiguousarray(aln, AFFINE_DTYPE)
+        cigar = np.ascontiguousarray(cigar, np.uint32).reshape(len(pairs), -1) if len(pairs) else np.zeros((0, 1), np.uint32)
+        n_cigar = np.ascontiguousarray(n_cigar, np.uint32)
+        if col_offset is None:
+            off = np.zeros(B.n + 1, np.uint64)
+            off[1:] = np.cumsum([int(x) for x in B.lengths])
+        else:
+            off = np.ascontiguousarray(col_offset, np.uint64)
+        call = lambda haps, cap, n, heads: lib().sp_pileup_hap_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), _ptr(aln), _ptr(cigar), cigar.shape[1], _ptr(n_cigar), _ptr(off),
+                                                                     haps, cap, n, heads)
+        return self._with_haps(call, 1024 + len(pairs), B.n, hap_cap)
+
     def pileup_ins(self, A, B, pairs, aln, cigar, n_cigar, col_offset=None, ins_cap=None):
         """sp_pileup_ins_batch: the arguments of pileup -> INS_DTYPE array, one record per distinct (column, inserted string).  ins_cap: a capacity to try, once
         -> (status, records or None, n_ins)"""
@@ -600,12 +671,14 @@ class Context:
         return self._with_ins(call, 4096 + 4 * len(pairs))
 
     def align_pileup(self, A, B, pairs, a=1, aln=True, cols=True, summaries=True, n_members=None, col_offset=None, band=64, retry_band=0, band_used=False, insertions=False,
-                     ins_cap=None):
+                     ins_cap=None, haplotypes=False, hap_cap=None):
         """sp_align_pileup_batch: pairs as affine_align takes them -> (aln AFFINE_DTYPE[n] or None, [PILEUP_DTYPE array per target of B] or None,
         [summary dict per target] or None); an output switched off is handed to the library as NULL.  col_offset: None = the one that follows B's lengths.
         band (64 | 256), retry_band (0 | 256 with band 64) or band_used other than the defaults: sp_align_pileup_band_batch; band_used=True adds a fourth item,
         uint32[n]: 0 for a pair that did not align, else the band its alignment came from.  insertions=True (sp_align_pileup_ins_batch) adds the INS_DTYPE records
-        as the last item; with ins_cap, a capacity to try once, the last item is (status, records or None, n_ins) instead"""
+        as the last item; with ins_cap, a capacity to try once, the last item is (status, records or None, n_ins) instead.  haplotypes=True
+        (sp_align_pileup_hap_batch; insertions are then made only when asked for as well) adds (HAP_DTYPE records, HAP_HEAD_DTYPE[B.n]) behind everything else; with
+        hap_cap, a capacity to try once, (status, records or None, n_haps, heads or None)"""
         rows = np.zeros(len(pairs), PAIR_DTYPE)
         for i, pr in enumerate(pairs):
             rows[i] = (pr[0], pr[1], pr[2], pr[3] if len(pr) > 3 else 0)
@@ -620,8 +693,23 @@ class Context:
         mem = np.ascontiguousarray(n_members, np.uint32) if n_members is not None else None
         op = sp_affine_opts(a, 4, 6, 2, 26, 1, 1)
         used = np.zeros(max(1, len(pairs)), np.uint32) if band_used else None
-        ins_out = None
-        if insertions:
+        ins_out = hap_out = None
+        if haplotypes:
+            n_i = C.c_uint64(0)
+            ibuf = [np.zeros(4096 + 4 * len(pairs), INS_DTYPE) if insertions else None]
+
+            def call(haps, cap, n, heads):
+                rc = lib().sp_align_pileup_hap_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), int(band), int(retry_band), _ptr(off), _ptr(out), _ptr(table),
+                                                     _ptr(sm), _ptr(mem), _ptr(used), _ptr(ibuf[0]), len(ibuf[0]) if insertions else 0, C.byref(n_i) if insertions else None,
+                                                     haps, cap, n, heads)
+                if insertions and rc == SP_ERR_CAPACITY and n_i.value > len(ibuf[0]):
+                    ibuf[0] = np.zeros(n_i.value, INS_DTYPE)
+                    return call(haps, cap, n, heads)
+                return rc
+            hap_out = self._with_haps(call, 1024 + len(pairs), B.n, hap_cap)
+            if insertions:
+                ins_out = ibuf[0][:n_i.value].copy()
+        elif insertions:
             call = lambda ins, cap, n: lib().sp_align_pileup_ins_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), int(band), int(retry_band), _ptr(off), _ptr(out),
                                                                        _ptr(table), _ptr(sm), _ptr(mem), _ptr(used), ins, cap, n)
             if ins_cap is not None:
@@ -641,7 +729,8 @@ class Context:
         res = (out, [table[int(off[t]):int(off[t + 1])] for t in range(B.n)] if cols else None,
                [{n: int(sm[t][n]) for n in SUPPORT_FIELDS[:-1]} for t in range(B.n)] if summaries else None)
         res = res + (used[:len(pairs)],) if band_used else res
-        return res + (ins_out,) if insertions else res
+        res = res + (ins_out,) if insertions else res
+        return res + (hap_out,) if haplotypes else res
 
     def hla_config_extend(self, reference, alleles, db=None, batch_alleles=0):
         """sp_hla_config_extend: HlaConfig::new on the device -- reference = database.Fasta, alleles = database.HlaAlleles, db = database.Database whose hla_config
@@ -1490,14 +1579,30 @@ class HlaDb:
         self.ctx.check(lib().sp_hla_diplotype_gene(self.ctx._h, self._h, int(gene), reads._h, _ptr(realign), C.byref(cfg), C.byref(call), c1, c2, cap, _ptr(is1)))
         return call, c1.value.decode(), c2.value.decode(), is1[(realign["status"] == 0) & (realign["gene"] == gene)].astype(bool)
 
-    def consensus_support(self, gene, reads, realign, is_cons1, cons1, cons2, insertions=False):
+    def consensus_support(self, gene, reads, realign, is_cons1, cons1, cons2, insertions=False, haplotypes=False):
         """sp_hla_consensus_support: is_cons1 per read of `reads` (as diplotype_genes returns it), cons1 / cons2 the hg38-forward consensuses of the call
         -> ((cols1 PILEUP_DTYPE, summary1 dict), (cols2, summary2)) in gene-strand coordinates.  insertions=True (sp_hla_consensus_support_ins) adds a third item: the
-        INS_DTYPE records, consensus 1's columns from 0, consensus 2's from len(cons1)"""
+        INS_DTYPE records, consensus 1's columns from 0, consensus 2's from len(cons1).  haplotypes=True (sp_hla_consensus_support_hap) adds, last, (HAP_DTYPE records,
+        HAP_HEAD_DTYPE[2]): target 0 is consensus 1, target 1 consensus 2, first_pair the member read"""
         realign = np.ascontiguousarray(realign)
         is1 = np.ascontiguousarray(is_cons1, np.uint8)
         cols = [np.zeros(len(cons1), PILEUP_DTYPE), np.zeros(len(cons2), PILEUP_DTYPE)]
         sm = [sp_support_summary(), sp_support_summary()]
+        if haplotypes:
+            n_i = C.c_uint64(0)
+            ibuf = [np.zeros(16384, INS_DTYPE) if insertions else None]
+
+            def call(haps, cap, n, heads):
+                rc = lib().sp_hla_consensus_support_hap(self.ctx._h, self._h, int(gene), reads._h, _ptr(realign), _ptr(is1), cons1.encode(), cons2.encode(), cols[0].ctypes.data,
+                                                        cols[1].ctypes.data, C.byref(sm[0]), C.byref(sm[1]), _ptr(ibuf[0]), len(ibuf[0]) if insertions else 0,
+                                                        C.byref(n_i) if insertions else None, haps, cap, n, heads)
+                if insertions and rc == SP_ERR_CAPACITY and n_i.value > len(ibuf[0]):
+                    ibuf[0] = np.zeros(n_i.value, INS_DTYPE)
+                    return call(haps, cap, n, heads)
+                return rc
+            hap = self.ctx._with_haps(call, 4096, 2)
+            res = tuple((cols[c], {n: int(getattr(sm[c], n)) for n in SUPPORT_FIELDS[:-1]}) for c in range(2))
+            return res + ((ibuf[0][:n_i.value].copy(),) if insertions else ()) + (hap,)
         if insertions:
             ins = self.ctx._with_ins(lambda ins, cap, n: lib().sp_hla_consensus_support_ins(
                 self.ctx._h, self._h, int(gene), reads._h, _ptr(realign), _ptr(is1), cons1.encode(), cons2.encode(), cols[0].ctypes.data, cols[1].ctypes.data,
@@ -1507,7 +1612,7 @@ class HlaDb:
                                                       cols[0].ctypes.data, cols[1].ctypes.data, C.byref(sm[0]), C.byref(sm[1])))
         return tuple((cols[c], {n: int(getattr(sm[c], n)) for n in SUPPORT_FIELDS[:-1]}) for c in range(2))
 
-    def consensus_support_cohort(self, n_samples, read_sample, genes, reads, realign, is_cons1, cons, unit_on=None, insertions=False):
+    def consensus_support_cohort(self, n_samples, read_sample, genes, reads, realign, is_cons1, cons, unit_on=None, insertions=False, haplotypes=False):
         """sp_hla_consensus_support_cohort: cons[sample][gene] = (consensus1, consensus2), hg38 forward -> out[sample][gene] = ((cols1, summary1), (cols2, summary2)).
         insertions=True (sp_hla_consensus_support_cohort_ins): -> (that, INS_DTYPE records, col_offset uint64[2 * n_samples * n_genes + 1])"""
         k = len(genes)
@@ -1524,7 +1629,22 @@ class HlaDb:
         cols = np.zeros(max(1, total), PILEUP_DTYPE)
         sm = np.zeros(len(flat), SUPPORT_DTYPE)
         ins = None
-        if insertions:
+        if haplotypes:
+            # sp_hla_consensus_support_cohort_hap: -> (that, INS_DTYPE records or None, col_offset, (HAP_DTYPE records, HAP_HEAD_DTYPE per slot 2 * unit + consensus))
+            n_i = C.c_uint64(0)
+            ibuf = [np.zeros(16384, INS_DTYPE) if insertions else None]
+
+            def call(haps, hcap, n, heads):
+                rc = lib().sp_hla_consensus_support_cohort_hap(self.ctx._h, self._h, n_samples, _ptr(rs), k, _ptr(g), reads._h, _ptr(realign), _ptr(is1), buf, cap, _ptr(on), _ptr(off),
+                                                               _ptr(cols), total, _ptr(sm), _ptr(ibuf[0]), len(ibuf[0]) if insertions else 0, C.byref(n_i) if insertions else None,
+                                                               haps, hcap, n, heads)
+                if insertions and rc == SP_ERR_CAPACITY and n_i.value > len(ibuf[0]):
+                    ibuf[0] = np.zeros(n_i.value, INS_DTYPE)
+                    return call(haps, hcap, n, heads)
+                return rc
+            hap = self.ctx._with_haps(call, 16384, len(flat))
+            ins = ibuf[0][:n_i.value].copy() if insertions else None
+        elif insertions:
             ins = self.ctx._with_ins(lambda ins, icap, n: lib().sp_hla_consensus_support_cohort_ins(
                 self.ctx._h, self._h, n_samples, _ptr(rs), k, _ptr(g), reads._h, _ptr(realign), _ptr(is1), buf, cap, _ptr(on), _ptr(off), _ptr(cols), total, _ptr(sm), ins, icap, n), 16384)
         else:
@@ -1532,6 +1652,8 @@ class HlaDb:
                                                                  _ptr(on), _ptr(off), _ptr(cols), total, _ptr(sm)))
         side = lambda x: (cols[int(off[x]):int(off[x + 1])].copy(), {n: int(sm[x][n]) for n in SUPPORT_FIELDS[:-1]})
         res = [[(side(2 * (s * k + i)), side(2 * (s * k + i) + 1)) for i in range(k)] for s in range(n_samples)]
+        if haplotypes:
+            return res, ins, off.copy(), hap
         return (res, ins, off.copy()) if insertions else res
 
     def diplotype_genes(self, genes, reads, realign, cfgs=None, cap=65536):
