@@ -10,7 +10,7 @@
 
 namespace {
 
-// one alignment as the kernel reads it, in bucket (target) order
+// one alignment as pileup_kernel reads it, in bucket (target) order
 struct PuPair { uint64_t op_off; uint32_t a, n_ops; int32_t b_start, a_start; };      // 24 bytes
 struct PuTile { uint32_t target, c0; };
 
@@ -32,8 +32,30 @@ __device__ __forceinline__ void pu_add(uint32_t* lds, int col, uint32_t op, cons
     atomicAdd(&lds[plane * PU_STRIDE + col], 1u);
 }
 
-// one alignment under one tile: the wave takes the row's ops 64 at a time (a wave-wide prefix sum gives every op its first target column and query base) and adds the
-// columns inside [c0, c1) to the tile's planes.  row / n_ops / b_start / a_start are wave-uniform.
+// The walk over an op row (row / n_ops / b_start / a_start wave-uniform): the wave takes the ops 64 at a time, two wave-wide inclusive prefix sums give every op its first
+// target column t0 and query base q0, and f(live, op, len, t0, q0) is called once per chunk on ALL 64 lanes (the callers ballot and shuffle inside).  A chunk that
+// begins behind column `stop` (wave-uniform) ends the walk.
+template <class F> __device__ __forceinline__ void pu_walk(const uint32_t* __restrict__ row, uint32_t n_ops, int b_start, int a_start, int lane, int stop, F f) {
+    int tpos = b_start, qpos = a_start;                                                // first target column / query base of the chunk (wave-uniform)
+    for (uint32_t k0 = 0; k0 < n_ops && tpos <= stop; k0 += SP_WAVE) {
+        const bool live = k0 + lane < n_ops;
+        const uint32_t w = live ? row[k0 + lane] : 0u;
+        const uint32_t op = w & 15u; const int n = (int)(w >> 4);
+        const int tl = (op == 7u || op == 8u || op == 2u) ? n : 0, ql = (op == 7u || op == 8u || op == 1u) ? n : 0;
+        int ts = tl, qs = ql;                                                          // inclusive prefix sums over the chunk
+#pragma unroll
+        for (int d = 1; d < SP_WAVE; d <<= 1) {
+            const int u = __shfl_up(ts, d), v = __shfl_up(qs, d);
+            if (lane >= d) { ts += u; qs += v; }
+        }
+        const int t0 = tpos + ts - tl, q0 = qpos + qs - ql;                            // this op's first target column and query base
+        tpos += __shfl(ts, SP_WAVE - 1); qpos += __shfl(qs, SP_WAVE - 1);
+        f(live, op, n, t0, q0);
+    }
+}
+
+// One alignment under one tile: the columns of its ops inside [c0, c1) are added to the tile's planes.  The walk is pu_walk's, written out: through pu_walk
+// pileup_kernel kept its registers, yet ran 0.622-0.626 ms where the parent's spread was 0.593-0.598 ms (2,108 pairs; profiles/support/refactor.txt, section 1, state B).
 __device__ __forceinline__ void pu_pair(uint32_t* lds, int c0, int c1, const uint32_t* qwords, const uint32_t* __restrict__ row, uint32_t n_ops, int b_start, int a_start, int lane) {
     int tpos = b_start, qpos = a_start;                                                // first target column / query base of the chunk (wave-uniform)
     for (uint32_t k0 = 0; k0 < n_ops && tpos <= c1; k0 += SP_WAVE) {                   // (an 'I' op at column c1 counts for column c1 - 1: <=)
@@ -91,6 +113,22 @@ __global__ __launch_bounds__(PU_WAVES * SP_WAVE) void pileup_kernel(SeqSetView A
 constexpr uint32_t AP_LOST = 0xFFFFFFFFu;                   // n_cigar of a walk that did not arrive, op_off of a row that was not kept (sp_launch_affine_map)
 constexpr uint64_t AP_NO_OPS = ~0ull;
 
+// the pairs the table counts (wave-uniform): a row of ops that was kept (the host reports the other two) and an alignment.  Host op rows are staged with score 1.
+__device__ __forceinline__ bool ap_counted(uint32_t n_ops, uint64_t off, const sp_affine_aln* g) { return n_ops != 0 && n_ops != AP_LOST && off != AP_NO_OPS && g->score > 0; }
+
+// a column whose consensus base, or the absence of an insertion behind it, lacks a strict majority of the members that span it
+__host__ __device__ inline bool pu_contested(uint32_t depth, uint32_t eq, uint32_t ins) { return (depth > 0 && 2ull * eq <= depth) || 2ull * ins > depth; }
+
+// A wave takes its places in a list with one ballot and one atomic on the list's counter: the place of a lane that wants one (all 64 lanes call).
+template <class T> __device__ __forceinline__ T wave_append(bool want, T* count, int lane) {
+    const unsigned long long vote = __ballot(want);
+    if (!vote) return 0;
+    const int leader = __ffsll((long long)vote) - 1;
+    T base = 0;
+    if (lane == leader) base = atomicAdd(count, (T)__popcll(vote));
+    return __shfl(base, leader) + (T)__popcll(vote & ((1ull << lane) - 1ull));
+}
+
 __global__ __launch_bounds__(PU_WAVES * SP_WAVE) void pileup_rows_kernel(SeqSetView A, const int32_t* __restrict__ t_len, const sp_pair* __restrict__ pairs, const sp_affine_aln* __restrict__ aln,
                                                                          const uint32_t* __restrict__ n_cigar, const uint64_t* __restrict__ op_off, const uint32_t* __restrict__ ops,
                                                                          const uint32_t* __restrict__ order, const uint32_t* __restrict__ boff, uint32_t n_slices, uint32_t slice,
@@ -108,9 +146,8 @@ __global__ __launch_bounds__(PU_WAVES * SP_WAVE) void pileup_rows_kernel(SeqSetV
     for (uint32_t k = k_lo + wave; k < k_hi; k += PU_WAVES) {
         const uint32_t p = order[k], n_ops = n_cigar[p];
         const uint64_t off = op_off[p];
-        if (n_ops == 0 || n_ops == AP_LOST || off == AP_NO_OPS) continue;               // (wave-uniform; the host reports the last two)
+        if (!ap_counted(n_ops, off, aln + p)) continue;
         const sp_affine_aln g = aln[p];
-        if (g.score <= 0) continue;
         pu_pair(lds, c0, c1, A.words + A.word_off[pairs[p].a], ops + off, n_ops, g.b_start, g.a_start, lane);
     }
     __syncthreads();
@@ -133,14 +170,8 @@ __global__ void ap_retry_list_kernel(const sp_pair* __restrict__ pairs, const sp
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & (SP_WAVE - 1);
     const bool want = i < n && pairs[i].max_ed >= 0 && (aln[i].score <= 0 || n_cigar[i] == 0);
-    const unsigned long long vote = __ballot(want);
-    if (vote) {
-        const int leader = __ffsll((long long)vote) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(vote));
-        base = (uint32_t)__shfl((int)base, leader);
-        if (want) list[base + (uint32_t)__popcll(vote & ((1ull << lane) - 1ull))] = i;
-    }
+    const uint32_t at = wave_append(want, count, lane);
+    if (want) list[at] = i;
     if (i < n && tried) tried[i] = want ? 1u : 0u;
 }
 
@@ -197,7 +228,7 @@ __global__ __launch_bounds__(AP_SUM_THREADS) void support_summary_kernel(const u
             if (first) {
                 const uint32_t ins = cols[2 * (size_t)j + 1].w;
                 mn = min(mn, depth);
-                cont += ((depth > 0 && 2ull * a.y <= depth) || 2ull * ins > depth) ? 1u : 0u;
+                cont += pu_contested(depth, a.y, ins) ? 1u : 0u;
             }
             if (depth >= lo && depth - lo < range) atomicAdd(&hist[(depth - lo) / W], 1u);
         }
@@ -261,35 +292,20 @@ __device__ __forceinline__ bool ins_run_less(const InsRun& a, const InsRun& b) {
 
 __global__ __launch_bounds__(INS_THREADS) void ins_collect_kernel(SeqSetView A, const int32_t* __restrict__ t_len, const sp_pair* __restrict__ pairs, const sp_affine_aln* __restrict__ aln,
                                                                   const uint32_t* __restrict__ n_cigar, const uint64_t* __restrict__ op_off, const uint32_t* __restrict__ ops, uint32_t n,
-                                                                  uint32_t pair0, int need_score, const uint64_t* __restrict__ col_offset, const uint32_t* __restrict__ tile_first,
+                                                                  uint32_t pair0, const uint64_t* __restrict__ col_offset, const uint32_t* __restrict__ tile_first,
                                                                   InsRun* __restrict__ runs, uint64_t runs_cap, unsigned long long* __restrict__ n_runs, uint32_t* __restrict__ tile_count) {
     const uint32_t i = blockIdx.x * (INS_THREADS / SP_WAVE) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & (SP_WAVE - 1);
     if (i >= n) return;                                                                 // (everything up to the loop is wave-uniform)
     const uint32_t n_ops = n_cigar[i];
     const uint64_t off = op_off[i];
-    if (n_ops == 0 || n_ops == AP_LOST || off == AP_NO_OPS) return;
+    if (!ap_counted(n_ops, off, aln + i)) return;
     const sp_affine_aln g = aln[i];
-    if (need_score && g.score <= 0) return;
     const sp_pair pr = pairs[i];
     const uint32_t* qwords = A.words + A.word_off[pr.a];
     const uint32_t* qn = A.nplane ? A.nplane + A.word_off[pr.a] : nullptr;
-    const uint32_t* row = ops + off;
     const int tl_max = t_len[pr.b];
-    int tpos = g.b_start, qpos = g.a_start;
-    for (uint32_t k0 = 0; k0 < n_ops; k0 += SP_WAVE) {
-        const bool live = k0 + lane < n_ops;
-        const uint32_t w = live ? row[k0 + lane] : 0u;
-        const uint32_t op = w & 15u; const int len = (int)(w >> 4);
-        const int tl = (op == 7u || op == 8u || op == 2u) ? len : 0, ql = (op == 7u || op == 8u || op == 1u) ? len : 0;
-        int ts = tl, qs = ql;
-#pragma unroll
-        for (int d = 1; d < SP_WAVE; d <<= 1) {
-            const int u = __shfl_up(ts, d), v = __shfl_up(qs, d);
-            if (lane >= d) { ts += u; qs += v; }
-        }
-        const int t0 = tpos + ts - tl, q0 = qpos + qs - ql;
-        tpos += __shfl(ts, SP_WAVE - 1); qpos += __shfl(qs, SP_WAVE - 1);
+    pu_walk(ops + off, n_ops, g.b_start, g.a_start, lane, 0x7FFFFFFF, [&](bool live, uint32_t op, int len, int t0, int q0) {
         const bool is_ins = live && op == 1u && len > 0 && t0 - 1 >= 0 && t0 - 1 < tl_max;
         InsRun r;
         if (is_ins) {
@@ -305,42 +321,9 @@ __global__ __launch_bounds__(INS_THREADS) void ins_collect_kernel(SeqSetView A, 
             }
             if (other) { r.len = 0; r.p0 = 0; r.p1 = 0; r.h = 0; r.qpos = 0; r.pair = 0; }
         }
-        const unsigned long long vote = __ballot(is_ins);
-        if (vote) {
-            const int leader = __ffsll((long long)vote) - 1;
-            unsigned long long base = 0;
-            if (lane == leader) base = atomicAdd(n_runs, (unsigned long long)__popcll(vote));
-            base = __shfl(base, leader);
-            const unsigned long long at = base + (unsigned long long)__popcll(vote & ((1ull << lane) - 1ull));
-            if (is_ins && at < runs_cap) { runs[at] = r; atomicAdd(&tile_count[r.tile], 1u); }
-        }
-    }
-}
-
-// exclusive sums of cnt[0 .. n) into off[0 .. n], the total into off[n]; zero (optional): n words cleared on the way.  One workgroup.
-__global__ __launch_bounds__(INS_THREADS) void ins_scan_kernel(const uint32_t* __restrict__ cnt, uint32_t n, uint32_t* __restrict__ off, uint32_t* __restrict__ zero) {
-    __shared__ uint32_t part[INS_THREADS];
-    const uint32_t tid = threadIdx.x, per = (n + INS_THREADS - 1) / INS_THREADS, lo = min(n, tid * per), hi = min(n, lo + per);
-    uint32_t s = 0;
-    for (uint32_t j = lo; j < hi; ++j) s += cnt[j];
-    part[tid] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < INS_THREADS; d <<= 1) {
-        const uint32_t v = tid >= d ? part[tid - d] : 0u;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[tid] - s;
-    for (uint32_t j = lo; j < hi; ++j) { off[j] = run; run += cnt[j]; if (zero) zero[j] = 0u; }
-    if (tid == INS_THREADS - 1) off[n] = part[tid];
-}
-
-__global__ void ins_scatter_kernel(const InsRun* __restrict__ runs, uint32_t n, const uint32_t* __restrict__ tile_off, uint32_t* __restrict__ tile_cur, InsRun* __restrict__ binned) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const InsRun r = runs[i];
-    binned[tile_off[r.tile] + atomicAdd(&tile_cur[r.tile], 1u)] = r;
+        const unsigned long long at = wave_append(is_ins, n_runs, lane);
+        if (is_ins && at < runs_cap) { runs[at] = r; atomicAdd(&tile_count[r.tile], 1u); }
+    });
 }
 
 // the workgroup's exclusive prefix of `mine` (part: INS_THREADS words of LDS); *total = the sum
@@ -359,10 +342,30 @@ __device__ __forceinline__ uint32_t ins_block_scan(uint32_t mine, uint32_t* part
     return part[tid] - mine;
 }
 
-// v[0 .. n) into ascending order of `less`, by the whole workgroup.  The bitonic network whose comparators all put the smaller element at the lower index (a merge
+// exclusive sums of cnt[0 .. n) into off[0 .. n], the total into off[n]; zero (optional): n words cleared on the way.  One workgroup.
+__global__ __launch_bounds__(INS_THREADS) void ins_scan_kernel(const uint32_t* __restrict__ cnt, uint32_t n, uint32_t* __restrict__ off, uint32_t* __restrict__ zero) {
+    __shared__ uint32_t part[INS_THREADS];
+    const uint32_t tid = threadIdx.x, per = (n + INS_THREADS - 1) / INS_THREADS, lo = min(n, tid * per), hi = min(n, lo + per);
+    uint32_t s = 0, total = 0;
+    for (uint32_t j = lo; j < hi; ++j) s += cnt[j];
+    uint32_t run = ins_block_scan(s, part, &total);
+    for (uint32_t j = lo; j < hi; ++j) { off[j] = run; run += cnt[j]; if (zero) zero[j] = 0u; }
+    if (tid == INS_THREADS - 1) off[n] = total;
+}
+
+__global__ void ins_scatter_kernel(const InsRun* __restrict__ runs, uint32_t n, const uint32_t* __restrict__ tile_off, uint32_t* __restrict__ tile_cur, InsRun* __restrict__ binned) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const InsRun r = runs[i];
+    binned[tile_off[r.tile] + atomicAdd(&tile_cur[r.tile], 1u)] = r;
+}
+
+// v[0 .. n) = the numbers 0 .. n - 1 in ascending order of `less` (a total order on them), by the whole workgroup.  The bitonic network whose comparators all put the smaller element at the lower index (a merge
 // begins with the mirrored step, then halves): for an n that is no power of two the places from n on stand for elements larger than all others, which such a
 // comparator never moves -- a comparator that reaches past n is left out.
 template <class Less> __device__ __forceinline__ void ins_bitonic(uint32_t* v, uint32_t n, Less less) {
+    for (uint32_t s = threadIdx.x; s < n; s += INS_THREADS) v[s] = s;
+    __syncthreads();
     uint32_t P = 1;
     while (P < n) P <<= 1;
     for (uint32_t k = 2; k <= P; k <<= 1)
@@ -379,25 +382,29 @@ template <class Less> __device__ __forceinline__ void ins_bitonic(uint32_t* v, u
         }
 }
 
-// one tile's runs R[0 .. n) -> its records, in the list's order, to out; returns their number.  idx / didx / dcnt: n words each, where R lives (LDS or the pooled scratch).
-__device__ __forceinline__ uint32_t ins_tile_work(const InsRun* R, uint32_t* idx, uint32_t* didx, uint32_t* dcnt, uint32_t n, uint32_t* part, sp_pileup_ins* __restrict__ out) {
+// The distinct records of the sorted idx[0 .. n), `same` telling whether two numbers belong to one record: didx[d] = the first number of record d in the order (the
+// lowest of the record where the order ends on that), dcnt[d] = how many numbers the record has.  Returns the number of records.
+template <class Same> __device__ __forceinline__ uint32_t ins_distinct(const uint32_t* idx, uint32_t* didx, uint32_t* dcnt, uint32_t n, uint32_t* part, Same same) {
     const uint32_t tid = threadIdx.x, per = (n + INS_THREADS - 1) / INS_THREADS, lo = min(n, tid * per), hi = min(n, lo + per);
-    for (uint32_t s = tid; s < n; s += INS_THREADS) idx[s] = s;
-    __syncthreads();
-    ins_bitonic(idx, n, [&](uint32_t a, uint32_t b) { return ins_run_less(R[a], R[b]); });
-    // ---- distinct records: didx[d] = the first run of record d (its lowest pair), dcnt[d] = how many runs it has
+    auto head = [&](uint32_t s) { return s == 0 || !same(idx[s], idx[s - 1]); };
     uint32_t heads = 0, m = 0;
-    for (uint32_t s = lo; s < hi; ++s) heads += (s == 0 || !ins_same(R[idx[s]], R[idx[s - 1]])) ? 1u : 0u;
+    for (uint32_t s = lo; s < hi; ++s) heads += head(s) ? 1u : 0u;
     uint32_t d = ins_block_scan(heads, part, &m);
-    for (uint32_t s = lo; s < hi; ++s) if (s == 0 || !ins_same(R[idx[s]], R[idx[s - 1]])) didx[d++] = s;
+    for (uint32_t s = lo; s < hi; ++s) if (head(s)) didx[d++] = s;
     __syncthreads();
     for (uint32_t e = tid; e < m; e += INS_THREADS) dcnt[e] = (e + 1 < m ? didx[e + 1] : n) - didx[e];
     __syncthreads();
     for (uint32_t e = tid; e < m; e += INS_THREADS) didx[e] = idx[didx[e]];
     __syncthreads();
+    return m;
+}
+
+// one tile's runs R[0 .. n) -> its records, in the list's order, to out; returns their number.  idx / didx / dcnt: n words each, where R lives (LDS or the pooled scratch).
+__device__ __forceinline__ uint32_t ins_tile_work(const InsRun* R, uint32_t* idx, uint32_t* didx, uint32_t* dcnt, uint32_t n, uint32_t* part, sp_pileup_ins* __restrict__ out) {
+    const uint32_t tid = threadIdx.x;
+    ins_bitonic(idx, n, [&](uint32_t a, uint32_t b) { return ins_run_less(R[a], R[b]); });
+    const uint32_t m = ins_distinct(idx, didx, dcnt, n, part, [&](uint32_t a, uint32_t b) { return ins_same(R[a], R[b]); });      // (a record's first run is its lowest pair)
     // ---- the list's order: col, a column's len-0 record first (it is folded away below), count descending, len, key
-    for (uint32_t e = tid; e < m; e += INS_THREADS) idx[e] = e;
-    __syncthreads();
     ins_bitonic(idx, m, [&](uint32_t a, uint32_t b) {
         const InsRun& x = R[didx[a]]; const InsRun& y = R[didx[b]];
         if (x.col != y.col) return x.col < y.col;
@@ -475,7 +482,7 @@ __global__ __launch_bounds__(INS_THREADS) void hap_cols_kernel(const uint32_t* _
         if (j < len) {
             const uint4 a = cols[2 * (size_t)j];
             const uint32_t ins = cols[2 * (size_t)j + 1].w;
-            c = (a.x > 0 && 2ull * a.y <= a.x) || 2ull * ins > a.x;
+            c = pu_contested(a.x, a.y, ins);
         }
         const unsigned long long vote = __ballot(c);
         if (lane == 0) s_w[wave] = (uint32_t)__popcll(vote);
@@ -501,7 +508,7 @@ __device__ __forceinline__ int hap_lower(const uint32_t* cols, int K, uint32_t c
 
 __global__ __launch_bounds__(INS_THREADS) void hap_pattern_kernel(SeqSetView A, const int32_t* __restrict__ t_len, const sp_pair* __restrict__ pairs, const sp_affine_aln* __restrict__ aln,
                                                                   const uint32_t* __restrict__ n_cigar, const uint64_t* __restrict__ op_off, const uint32_t* __restrict__ ops, uint32_t n,
-                                                                  int need_score, const uint32_t* __restrict__ list, const uint32_t* __restrict__ ktot,
+                                                                  const uint32_t* __restrict__ list, const uint32_t* __restrict__ ktot,
                                                                   uint64_t* __restrict__ pat, uint32_t* __restrict__ valid) {
     __shared__ uint32_t s_cols[HAP_WAVES][HAP_COLS], s_pat[HAP_WAVES][8];
     const uint32_t wave = threadIdx.x >> 6, i = blockIdx.x * HAP_WAVES + wave;
@@ -511,11 +518,10 @@ __global__ __launch_bounds__(INS_THREADS) void hap_pattern_kernel(SeqSetView A, 
     uint32_t n_ops = 0; uint64_t off = 0; sp_affine_aln g = {}; sp_pair pr = {}; int K = 0;
     if (act) {
         n_ops = n_cigar[i]; off = op_off[i];
-        act = !(n_ops == 0 || n_ops == AP_LOST || off == AP_NO_OPS);
+        act = ap_counted(n_ops, off, aln + i);
     }
-    if (act) { g = aln[i]; act = !(need_score && g.score <= 0); }
     if (act) {
-        pr = pairs[i];
+        g = aln[i]; pr = pairs[i];
         K = (int)min(ktot[pr.b], (uint32_t)HAP_COLS);
         if (lane < K) s_cols[wave][lane] = list[(size_t)pr.b * HAP_COLS + lane];
     }
@@ -525,22 +531,10 @@ __global__ __launch_bounds__(INS_THREADS) void hap_pattern_kernel(SeqSetView A, 
         const uint32_t* cols = s_cols[wave];
         uint32_t* mine = s_pat[wave];
         const uint32_t* qwords = A.words + A.word_off[pr.a];
-        const uint32_t* row = ops + off;
         const int tl_max = t_len[pr.b], last = (int)cols[K - 1];
-        int tpos = g.b_start, qpos = g.a_start;
-        for (uint32_t k0 = 0; k0 < n_ops && tpos <= last + 1; k0 += SP_WAVE) {         // (an 'I' op at column last + 1 sits behind column last: <=)
-            const bool live = k0 + lane < n_ops;
-            const uint32_t w = live ? row[k0 + lane] : 0u;
-            const uint32_t op = w & 15u; const int len = (int)(w >> 4);
-            const int tl = (op == 7u || op == 8u || op == 2u) ? len : 0, ql = (op == 7u || op == 8u || op == 1u) ? len : 0;
-            int ts = tl, qs = ql;
-#pragma unroll
-            for (int d = 1; d < SP_WAVE; d <<= 1) {
-                const int u = __shfl_up(ts, d), v = __shfl_up(qs, d);
-                if (lane >= d) { ts += u; qs += v; }
-            }
-            const int t0 = tpos + ts - tl, q0 = qpos + qs - ql;
-            tpos += __shfl(ts, SP_WAVE - 1); qpos += __shfl(qs, SP_WAVE - 1);
+        // (an 'I' op at column last + 1 sits behind column last: the walk stops behind last + 1)
+        pu_walk(ops + off, n_ops, g.b_start, g.a_start, lane, last + 1, [&](bool live, uint32_t op, int len, int t0, int q0) {
+            const int tl = (op == 7u || op == 8u || op == 2u) ? len : 0;
             if (live && tl > 0) {
                 for (int k = hap_lower(cols, K, (uint32_t)t0); k < K && (int)cols[k] < t0 + tl; ++k) {
                     const uint32_t call = op == 7u ? 1u : op == 2u ? 6u : 2u + pu_query_code(qwords, q0 + ((int)cols[k] - t0));
@@ -551,7 +545,7 @@ __global__ __launch_bounds__(INS_THREADS) void hap_pattern_kernel(SeqSetView A, 
                 const int k = hap_lower(cols, K, (uint32_t)(t0 - 1));
                 if (k < K && (int)cols[k] == t0 - 1) atomicOr(&mine[k >> 3], 8u << ((k & 7) << 2));
             }
-        }
+        });
     }
     __syncthreads();
     if (i < n) {
@@ -575,8 +569,6 @@ __device__ __forceinline__ bool hap_pat_less(const HapKey& a, const HapKey& b, b
 __device__ __forceinline__ uint32_t hap_target_work(const HapKey* R, uint32_t* idx, uint32_t* didx, uint32_t* dcnt, uint32_t n, uint32_t* part, uint32_t target, uint32_t K,
                                                     sp_support_hap* __restrict__ out) {
     const uint32_t tid = threadIdx.x, per = (n + INS_THREADS - 1) / INS_THREADS, lo = min(n, tid * per), hi = min(n, lo + per);
-    for (uint32_t s = tid; s < n; s += INS_THREADS) idx[s] = s;
-    __syncthreads();
     // the pairs the table does not count go behind all others; then the pattern, then the pair: a total order
     ins_bitonic(idx, n, [&](uint32_t a, uint32_t b) {
         const HapKey& x = R[a]; const HapKey& y = R[b];
@@ -588,19 +580,9 @@ __device__ __forceinline__ uint32_t hap_target_work(const HapKey* R, uint32_t* i
     uint32_t mine = 0, nv = 0;
     for (uint32_t s = lo; s < hi; ++s) mine += R[idx[s]].valid ? 1u : 0u;
     (void)ins_block_scan(mine, part, &nv);
-    // ---- distinct records over the nv keys in front: didx[d] = the first key of record d (its lowest pair), dcnt[d] = how many keys it has
-    uint32_t heads = 0, m = 0;
-    for (uint32_t s = lo; s < hi; ++s) heads += (s < nv && (s == 0 || !hap_same(R[idx[s]], R[idx[s - 1]]))) ? 1u : 0u;
-    uint32_t d = ins_block_scan(heads, part, &m);
-    for (uint32_t s = lo; s < hi; ++s) if (s < nv && (s == 0 || !hap_same(R[idx[s]], R[idx[s - 1]]))) didx[d++] = s;
-    __syncthreads();
-    for (uint32_t e = tid; e < m; e += INS_THREADS) dcnt[e] = (e + 1 < m ? didx[e + 1] : nv) - didx[e];
-    __syncthreads();
-    for (uint32_t e = tid; e < m; e += INS_THREADS) didx[e] = idx[didx[e]];
-    __syncthreads();
+    // ---- distinct records over the nv keys in front (a record's first key is its lowest pair)
+    const uint32_t m = ins_distinct(idx, didx, dcnt, nv, part, [&](uint32_t a, uint32_t b) { return hap_same(R[a], R[b]); });
     // ---- the list's order: count descending, then the pattern ascending (distinct records have distinct patterns)
-    for (uint32_t e = tid; e < m; e += INS_THREADS) idx[e] = e;
-    __syncthreads();
     ins_bitonic(idx, m, [&](uint32_t a, uint32_t b) {
         if (dcnt[a] != dcnt[b]) return dcnt[a] > dcnt[b];
         bool eq;
@@ -651,7 +633,7 @@ __global__ void hap_pack_kernel(const sp_support_hap* __restrict__ tmp, const ui
     }
 }
 
-static bool contested_col(const sp_pileup_col& c) { return (c.depth > 0 && 2ull * c.eq <= c.depth) || 2ull * c.ins > c.depth; }
+static bool contested_col(const sp_pileup_col& c) { return pu_contested(c.depth, c.eq, c.ins); }
 
 static std::string revcomp_str(const char* s, size_t n) {
     std::string r(n, 'N');
@@ -661,6 +643,24 @@ static std::string revcomp_str(const char* s, size_t n) {
         r[i] = c;
     }
     return r;
+}
+
+static int32_t check_col_offset(sp_ctx* ctx, const std::string& who, const sp_seqset* B, const uint64_t* col_offset) {
+    if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": col_offset[0] must be 0");
+    for (uint32_t t = 0; t < B->n; ++t)
+        if (col_offset[t + 1] < col_offset[t] || col_offset[t + 1] - col_offset[t] != (uint64_t)B->h_len[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": col_offset does not follow the target lengths");
+    return SP_OK;
+}
+
+// the tiles of B's targets: how many a target of `len` columns has, how many there are in all (more than 2^31 - 1: an error), and the list in target order
+static uint64_t pu_tiles_of(int32_t len) { return ((uint64_t)len + PU_TILE - 1) / PU_TILE; }
+static int32_t pu_count_tiles(sp_ctx* ctx, const std::string& who, const sp_seqset* B, uint64_t* n_tiles) {
+    *n_tiles = 0;
+    for (uint32_t t = 0; t < B->n; ++t) *n_tiles += pu_tiles_of(B->h_len[t]);
+    return *n_tiles > 0x7FFFFFFFull ? sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": too many tiles") : SP_OK;
+}
+static void pu_fill_tiles(const sp_seqset* B, PuTile* list) {
+    for (uint32_t t = 0; t < B->n; ++t) for (int32_t c0 = 0; c0 < B->h_len[t]; c0 += PU_TILE) *list++ = PuTile{ t, (uint32_t)c0 };
 }
 
 // ---- the host side of the insertion list: pooled buffers sized by the run buffer's capacity (a warm context allocates nothing), the launches, the way out
@@ -675,8 +675,8 @@ struct InsPass {
 static int32_t ins_begin(sp_ctx* ctx, const std::string& who, const sp_seqset* B, uint64_t n_pairs, uint64_t min_cap, InsPass* ip) {
     ip->n_t = B->n;
     uint64_t n_tiles = 0;
-    for (uint32_t t = 0; t < B->n; ++t) n_tiles += ((uint64_t)B->h_len[t] + PU_TILE - 1) / PU_TILE;
-    if (n_tiles > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": too many tiles");
+    const int32_t rc = pu_count_tiles(ctx, who, B, &n_tiles);
+    if (rc != SP_OK) return rc;
     ip->n_tiles = (uint32_t)n_tiles;
     const uint64_t held = std::min(std::min<uint64_t>(sp_pool_bytes(ctx, "ins_runs") / sizeof(sp_pileup_ins), sp_pool_bytes(ctx, "ins_binned") / sizeof(InsRun)),
                                    std::min<uint64_t>(sp_pool_bytes(ctx, "ins_tmp") / sizeof(sp_pileup_ins), sp_pool_bytes(ctx, "ins_scratch") / 12));
@@ -693,7 +693,7 @@ static int32_t ins_begin(sp_ctx* ctx, const std::string& who, const sp_seqset* B
     if (!ip->d_runs || !ip->d_binned || !ip->d_tmp || !ip->d_scratch || !d_w || !h_tf || !ip->h_st) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, who + ": insertion list buffers");
     ip->d_n = (unsigned long long*)d_w; ip->d_cnt = d_w + 4; ip->d_off = ip->d_cnt + tw; ip->d_cur = ip->d_off + tw; ip->d_ooff = ip->d_cur + tw; ip->d_tfirst = ip->d_ooff + tw;
     uint32_t x = 0;
-    for (uint32_t t = 0; t < B->n; ++t) { h_tf[t] = x; x += (uint32_t)(((uint64_t)B->h_len[t] + PU_TILE - 1) / PU_TILE); }
+    for (uint32_t t = 0; t < B->n; ++t) { h_tf[t] = x; x += (uint32_t)pu_tiles_of(B->h_len[t]); }
     h_tf[B->n] = x;
     SP_HIP_CHECK(ctx, hipMemsetAsync(d_w, 0, (4 + 4 * tw) * 4, ctx->stream));
     SP_HIP_CHECK(ctx, hipMemcpyAsync(ip->d_tfirst, h_tf, ((size_t)B->n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -702,12 +702,12 @@ static int32_t ins_begin(sp_ctx* ctx, const std::string& who, const sp_seqset* B
 
 // the runs of m alignments (pair numbers pair0 ...) whose rows lie in device memory
 static int32_t ins_collect(sp_ctx* ctx, const std::string& who, const InsPass& ip, const sp_seqset* A, const sp_seqset* B, const sp_pair* d_pairs, const sp_affine_aln* d_aln,
-                           const uint32_t* d_nc, const uint64_t* d_op_off, const uint32_t* d_ops, uint32_t m, uint32_t pair0, bool need_score, const uint64_t* d_col_offset) {
+                           const uint32_t* d_nc, const uint64_t* d_op_off, const uint32_t* d_ops, uint32_t m, uint32_t pair0, const uint64_t* d_col_offset) {
     if (m == 0 || ip.n_tiles == 0) return SP_OK;
     ProfScope ps(ctx, "pileup_ins_collect", m);
     constexpr uint32_t per = INS_THREADS / SP_WAVE;
     hipLaunchKernelGGL(ins_collect_kernel, dim3((m + per - 1) / per), dim3(INS_THREADS), 0, ctx->stream, A->view(), B->d_len, d_pairs, d_aln, d_nc, d_op_off, d_ops, m, pair0,
-                       need_score ? 1 : 0, d_col_offset, ip.d_tfirst, ip.d_runs, ip.cap, ip.d_n, ip.d_cnt);
+                       d_col_offset, ip.d_tfirst, ip.d_runs, ip.cap, ip.d_n, ip.d_cnt);
     if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": insertion collect launch failed");
     return SP_OK;
 }
@@ -742,10 +742,10 @@ static int32_t ins_finish(sp_ctx* ctx, const std::string& who, const InsPass& ip
     return SP_OK;
 }
 
-// Every alignment of host op rows is walked here, before anything is launched or written: what the kernels index with is what this loop has seen.  bucket_off[t + 1]
-// counts the live pairs of target t; *total_ops their ops, *n_ins_ops the 'I' ops among them.
+// Every alignment of host op rows is walked here, before anything is launched or written: what the kernels index with is what this loop has seen.  *total_ops
+// counts the ops of the pairs that have any, *n_ins_ops the 'I' ops among them.
 static int32_t pileup_check_rows(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln, const uint32_t* cigar,
-                                 uint32_t cigar_stride, const uint32_t* n_cigar, std::vector<uint32_t>& bucket_off, uint64_t* total_ops, uint64_t* n_ins_ops) {
+                                 uint32_t cigar_stride, const uint32_t* n_cigar, uint64_t* total_ops, uint64_t* n_ins_ops) {
     for (uint64_t i = 0; i < n_pairs; ++i) {
         if (pairs[i].a >= A->n || pairs[i].b >= B->n) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: index out of range");
         if (n_cigar[i] == 0) continue;
@@ -766,19 +766,78 @@ static int32_t pileup_check_rows(sp_ctx* ctx, const sp_seqset* A, const sp_seqse
             if (j > g.b_end || q > g.a_end) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": the ops do not consume the spans of its alignment");
         }
         if (j != g.b_end || q != g.a_end) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": the ops do not consume the spans of its alignment");
-        ++bucket_off[pairs[i].b + 1]; *total_ops += n_cigar[i];
+        *total_ops += n_cigar[i];
     }
     return SP_OK;
 }
 
-// pileup_rows_kernel takes more dynamic LDS than the 64 KiB a kernel gets unasked: said once per device of the process
-static int32_t pileup_rows_lds(sp_ctx* ctx) {
+// the two tile kernels take more dynamic LDS than the 64 KiB a kernel gets unasked: said once per device of the process
+static int32_t pileup_lds(sp_ctx* ctx) {
     static std::atomic<uint64_t> lds_set(0);
     const uint64_t bit = 1ull << (ctx->device & 63);
     if (!(lds_set.load() & bit)) {
+        SP_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)pileup_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PU_LDS_BYTES));
         SP_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)pileup_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PU_LDS_BYTES));
         lds_set.fetch_or(bit);
     }
+    return SP_OK;
+}
+
+// Host op rows (checked by pileup_check_rows) as the device-resident pass keeps them, in one staging block and one copy: the pair list, spans, op counts and op offsets
+// per pair, the column offsets, the ops back to back; with_table also the order and the offsets of ONE slice, the tiles, and the table's buffer.  The kernels skip
+// score <= 0 (ap_counted) where the host-row entry points count every pair with ops: the staged spans of those carry score 1.
+struct HostRows {
+    const sp_pair* pairs; const sp_affine_aln* aln; const uint32_t *nc, *ops, *order, *boff; const uint64_t *off, *cols; const PuTile* tiles;
+    uint64_t n_tiles; uint32_t* table;
+};
+
+static int32_t stage_rows(sp_ctx* ctx, const sp_seqset* B, const sp_pair* pairs, uint32_t n, const sp_affine_aln* aln, const uint32_t* cigar, uint32_t cigar_stride,
+                          const uint32_t* n_cigar, const uint64_t* col_offset, uint64_t total_ops, bool with_table, HostRows* hr) {
+    const uint32_t n_t = B->n;
+    hr->n_tiles = 0; hr->table = nullptr;
+    if (with_table) {
+        const int32_t rc = pu_count_tiles(ctx, "pileup", B, &hr->n_tiles);
+        if (rc != SP_OK) return rc;
+    }
+    (void)hipSetDevice(ctx->device);
+    const size_t n_ord = with_table ? n : 0, n_boff = with_table ? (size_t)n_t * 2 + 1 : 0;
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t at_pairs = 0, at_aln = up16(at_pairs + sizeof(sp_pair) * (size_t)n), at_nc = up16(at_aln + sizeof(sp_affine_aln) * (size_t)n), at_off = up16(at_nc + 4 * (size_t)n),
+                 at_order = up16(at_off + 8 * (size_t)n), at_boff = up16(at_order + 4 * n_ord), at_tiles = up16(at_boff + 4 * n_boff),
+                 at_cols = up16(at_tiles + sizeof(PuTile) * (size_t)hr->n_tiles), at_ops = up16(at_cols + 8 * ((size_t)n_t + 1)), in_bytes = up16(at_ops + 4 * (size_t)total_ops) + 16;
+    uint8_t* h_in = (uint8_t*)sp_host_pool(ctx, "pileup_in", in_bytes);
+    uint8_t* d_in = (uint8_t*)sp_pool(ctx, "pileup_in", in_bytes);
+    if (with_table) hr->table = (uint32_t*)sp_pool(ctx, "pileup_out", std::max<size_t>(16, col_offset[n_t] * sizeof(sp_pileup_col)));
+    if (!h_in || !d_in || (with_table && !hr->table)) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "pileup buffers");
+    if (n) std::memcpy(h_in + at_pairs, pairs, sizeof(sp_pair) * (size_t)n);
+    if (n) std::memcpy(h_in + at_nc, n_cigar, 4 * (size_t)n);
+    std::memcpy(h_in + at_cols, col_offset, 8 * ((size_t)n_t + 1));
+    sp_affine_aln* ha = (sp_affine_aln*)(h_in + at_aln);
+    uint64_t* hoff = (uint64_t*)(h_in + at_off); uint32_t* hops = (uint32_t*)(h_in + at_ops);
+    uint64_t op_at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        ha[i] = aln[i]; hoff[i] = op_at;
+        if (n_cigar[i] == 0) continue;
+        ha[i].score = 1;
+        std::memcpy(hops + op_at, cigar + i * (size_t)cigar_stride, 4 * (size_t)n_cigar[i]);
+        op_at += n_cigar[i];
+    }
+    if (with_table) {
+        // target t's pairs are order[boff[2 t] .. boff[2 t + 1]), in the order given (pileup_rows_kernel with n_slices = 1)
+        uint32_t* boff = (uint32_t*)(h_in + at_boff); uint32_t* hord = (uint32_t*)(h_in + at_order);
+        std::memset(boff, 0, 4 * n_boff);
+        for (uint32_t i = 0; i < n; ++i) ++boff[(size_t)pairs[i].b * 2 + 1];
+        uint32_t run = 0;
+        for (uint32_t t = 0; t < n_t; ++t) { boff[(size_t)t * 2] = run; run += boff[(size_t)t * 2 + 1]; boff[(size_t)t * 2 + 1] = run; }
+        std::vector<uint32_t> at(n_t);
+        for (uint32_t t = 0; t < n_t; ++t) at[t] = boff[(size_t)t * 2];
+        for (uint32_t i = 0; i < n; ++i) hord[at[pairs[i].b]++] = i;
+        pu_fill_tiles(B, (PuTile*)(h_in + at_tiles));
+    }
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    hr->pairs = (const sp_pair*)(d_in + at_pairs); hr->aln = (const sp_affine_aln*)(d_in + at_aln); hr->nc = (const uint32_t*)(d_in + at_nc); hr->off = (const uint64_t*)(d_in + at_off);
+    hr->ops = (const uint32_t*)(d_in + at_ops); hr->order = (const uint32_t*)(d_in + at_order); hr->boff = (const uint32_t*)(d_in + at_boff);
+    hr->tiles = (const PuTile*)(d_in + at_tiles); hr->cols = (const uint64_t*)(d_in + at_cols);
     return SP_OK;
 }
 
@@ -788,7 +847,7 @@ struct HapOut { sp_support_hap* haps; uint64_t cap; uint64_t* n_haps; sp_support
 // the list over n pairs whose rows lie in device memory (d_ops: the rows of ALL of them), behind the finished table d_table.  A list that does not fit: SP_ERR_CAPACITY,
 // *n_haps set, nothing written.
 static int32_t hap_run(sp_ctx* ctx, const std::string& who, const sp_seqset* A, const sp_seqset* B, uint32_t n, const uint32_t* d_table, const uint64_t* d_col_offset,
-                       const sp_pair* d_pairs, const sp_affine_aln* d_aln, const uint32_t* d_nc, const uint64_t* d_op_off, const uint32_t* d_ops, bool need_score,
+                       const sp_pair* d_pairs, const sp_affine_aln* d_aln, const uint32_t* d_nc, const uint64_t* d_op_off, const uint32_t* d_ops,
                        const uint32_t* d_order, const uint32_t* d_boff, uint32_t n_slices, const HapOut& ho) {
     const uint32_t n_t = B->n;
     *ho.n_haps = 0;
@@ -811,7 +870,7 @@ static int32_t hap_run(sp_ctx* ctx, const std::string& who, const sp_seqset* A, 
         ProfScope ps(ctx, "support_hap", n);
         hipLaunchKernelGGL(hap_cols_kernel, dim3(n_t), dim3(INS_THREADS), 0, ctx->stream, d_table, d_col_offset, B->d_len, d_list, d_ktot);
         if (n) hipLaunchKernelGGL(hap_pattern_kernel, dim3((n + HAP_WAVES - 1) / HAP_WAVES), dim3(INS_THREADS), 0, ctx->stream, A->view(), B->d_len, d_pairs, d_aln, d_nc, d_op_off, d_ops, n,
-                                  need_score ? 1 : 0, d_list, d_ktot, d_pat, d_valid);
+                                  d_list, d_ktot, d_pat, d_valid);
         hipLaunchKernelGGL(hap_reduce_kernel, dim3(n_t), dim3(INS_THREADS), 0, ctx->stream, d_pat, d_valid, d_order, d_boff, n_slices, d_ktot, d_keys, d_scratch, (uint64_t)np, d_tmp, d_ndist);
         hipLaunchKernelGGL(ins_scan_kernel, dim3(1), dim3(INS_THREADS), 0, ctx->stream, d_ndist, n_t, d_ooff, (uint32_t*)nullptr);
         hipLaunchKernelGGL(hap_pack_kernel, dim3(n_t), dim3(256), 0, ctx->stream, d_tmp, d_boff, n_slices, d_ndist, d_ooff, d_ktot, d_out, d_heads);
@@ -909,29 +968,29 @@ int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, con
     if (!ctx) return SP_ERR_INVALID_ARG;
     if (!A || !B || !col_offset || (n_pairs && (!pairs || !aln || !n_cigar))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: null argument");
     if (n_pairs > 0xFFFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: too many pairs");
-    const uint32_t n_t = B->n;
-    if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset[0] must be 0");
-    for (uint32_t t = 0; t < n_t; ++t)
-        if (col_offset[t + 1] < col_offset[t] || col_offset[t + 1] - col_offset[t] != (uint64_t)B->h_len[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset does not follow the target lengths");
-    const uint64_t n_cols = col_offset[n_t];
+    int32_t rc = check_col_offset(ctx, "pileup", B, col_offset);
+    if (rc != SP_OK) return rc;
+    const uint64_t n_cols = col_offset[B->n];
     if (n_cols && !out) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: null argument");
-    std::vector<uint32_t> bucket_off((size_t)n_t + 1, 0);
     uint64_t total_ops = 0, n_ins_ops = 0;
-    const int32_t rc_rows = pileup_check_rows(ctx, A, B, pairs, n_pairs, aln, cigar, cigar_stride, n_cigar, bucket_off, &total_ops, &n_ins_ops);
-    if (rc_rows != SP_OK) return rc_rows;
+    rc = pileup_check_rows(ctx, A, B, pairs, n_pairs, aln, cigar, cigar_stride, n_cigar, &total_ops, &n_ins_ops);
+    if (rc != SP_OK) return rc;
     if (n_cols == 0) return SP_OK;
+    const uint32_t n_t = B->n;
+    uint64_t n_tiles = 0;
+    rc = pu_count_tiles(ctx, "pileup", B, &n_tiles);
+    if (rc != SP_OK) return rc;
+    std::vector<uint32_t> bucket_off((size_t)n_t + 1, 0);                                 // the live pairs (those with ops) by target
+    for (uint64_t i = 0; i < n_pairs; ++i) if (n_cigar[i]) ++bucket_off[pairs[i].b + 1];
     for (uint32_t t = 0; t < n_t; ++t) bucket_off[t + 1] += bucket_off[t];
     const uint32_t n_live = bucket_off[n_t];
-    uint64_t n_tiles = 0;
-    for (uint32_t t = 0; t < n_t; ++t) n_tiles += ((uint64_t)B->h_len[t] + PU_TILE - 1) / PU_TILE;
-    if (n_tiles > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: too many tiles");
     (void)hipSetDevice(ctx->device);
     // ---- one staging block, one copy: pairs in bucket order, bucket offsets, tiles, column offsets, the ops back to back
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t at_pairs = 0, at_bucket = up16(at_pairs + sizeof(PuPair) * (size_t)n_live), at_tiles = up16(at_bucket + 4 * ((size_t)n_t + 1)),
                  at_cols = up16(at_tiles + sizeof(PuTile) * (size_t)n_tiles), at_ops = up16(at_cols + 8 * ((size_t)n_t + 1)), in_bytes = up16(at_ops + 4 * (size_t)total_ops) + 16;
-    uint8_t* h_in = (uint8_t*)sp_host_pool(ctx, "pileup_in", in_bytes);
-    uint8_t* d_in = (uint8_t*)sp_pool(ctx, "pileup_in", in_bytes);
+    uint8_t* h_in = (uint8_t*)sp_host_pool(ctx, "pileup_buckets", in_bytes);
+    uint8_t* d_in = (uint8_t*)sp_pool(ctx, "pileup_buckets", in_bytes);
     uint32_t* d_out = (uint32_t*)sp_pool(ctx, "pileup_out", n_cols * sizeof(sp_pileup_col));
     if (!h_in || !d_in || !d_out) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "pileup buffers");
     {
@@ -946,18 +1005,11 @@ int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, con
         }
         std::memcpy(h_in + at_bucket, bucket_off.data(), 4 * ((size_t)n_t + 1));
         std::memcpy(h_in + at_cols, col_offset, 8 * ((size_t)n_t + 1));
-        PuTile* ht = (PuTile*)(h_in + at_tiles); uint64_t x = 0;
-        for (uint32_t t = 0; t < n_t; ++t) for (int32_t c0 = 0; c0 < B->h_len[t]; c0 += PU_TILE) ht[x++] = PuTile{ t, (uint32_t)c0 };
+        pu_fill_tiles(B, (PuTile*)(h_in + at_tiles));
     }
     SP_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    {   // more dynamic LDS than the 64 KiB a kernel gets unasked: said once per device of the process, not per call
-        static std::atomic<uint64_t> lds_set(0);
-        const uint64_t bit = 1ull << (ctx->device & 63);
-        if (!(lds_set.load() & bit)) {
-            SP_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)pileup_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PU_LDS_BYTES));
-            lds_set.fetch_or(bit);
-        }
-    }
+    rc = pileup_lds(ctx);
+    if (rc != SP_OK) return rc;
     {
         ProfScope ps(ctx, "pileup", n_cols);
         hipLaunchKernelGGL(pileup_kernel, dim3((unsigned)n_tiles), dim3(PU_WAVES * SP_WAVE), PU_LDS_BYTES, ctx->stream, A->view(), B->d_len, (const PuPair*)(d_in + at_pairs),
@@ -974,44 +1026,20 @@ int32_t sp_pileup_ins_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B,
     if (!ctx) return SP_ERR_INVALID_ARG;
     if (!A || !B || !col_offset || !n_ins || (ins_cap && !ins) || (n_pairs && (!pairs || !aln || !n_cigar))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: null argument");
     if (n_pairs > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: too many pairs");
-    const uint32_t n_t = B->n, n = (uint32_t)n_pairs;
-    if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset[0] must be 0");
-    for (uint32_t t = 0; t < n_t; ++t)
-        if (col_offset[t + 1] < col_offset[t] || col_offset[t + 1] - col_offset[t] != (uint64_t)B->h_len[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset does not follow the target lengths");
-    std::vector<uint32_t> bucket_off((size_t)n_t + 1, 0);
+    int32_t rc = check_col_offset(ctx, "pileup", B, col_offset);
+    if (rc != SP_OK) return rc;
     uint64_t total_ops = 0, n_ins_ops = 0;
-    int32_t rc = pileup_check_rows(ctx, A, B, pairs, n_pairs, aln, cigar, cigar_stride, n_cigar, bucket_off, &total_ops, &n_ins_ops);
+    rc = pileup_check_rows(ctx, A, B, pairs, n_pairs, aln, cigar, cigar_stride, n_cigar, &total_ops, &n_ins_ops);
     if (rc != SP_OK) return rc;
     *n_ins = 0;
-    if (n_ins_ops == 0 || col_offset[n_t] == 0) return SP_OK;
-    (void)hipSetDevice(ctx->device);
-    // ---- one staging block, one copy: the pair list, the spans, op counts and op offsets per pair, the column offsets, the ops back to back
-    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t at_pairs = 0, at_aln = up16(at_pairs + sizeof(sp_pair) * (size_t)n), at_nc = up16(at_aln + sizeof(sp_affine_aln) * (size_t)n), at_off = up16(at_nc + 4 * (size_t)n),
-                 at_cols = up16(at_off + 8 * (size_t)n), at_ops = up16(at_cols + 8 * ((size_t)n_t + 1)), in_bytes = up16(at_ops + 4 * (size_t)total_ops) + 16;
-    uint8_t* h_in = (uint8_t*)sp_host_pool(ctx, "pileup_ins_in", in_bytes);
-    uint8_t* d_in = (uint8_t*)sp_pool(ctx, "pileup_ins_in", in_bytes);
-    if (!h_in || !d_in) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "pileup buffers");
-    {
-        std::memcpy(h_in + at_pairs, pairs, sizeof(sp_pair) * (size_t)n);
-        std::memcpy(h_in + at_aln, aln, sizeof(sp_affine_aln) * (size_t)n);
-        std::memcpy(h_in + at_nc, n_cigar, 4 * (size_t)n);
-        std::memcpy(h_in + at_cols, col_offset, 8 * ((size_t)n_t + 1));
-        uint64_t* hoff = (uint64_t*)(h_in + at_off); uint32_t* hops = (uint32_t*)(h_in + at_ops);
-        uint64_t op_at = 0;
-        for (uint32_t i = 0; i < n; ++i) {
-            hoff[i] = op_at;
-            if (n_cigar[i] == 0) continue;
-            std::memcpy(hops + op_at, cigar + i * (size_t)cigar_stride, 4 * (size_t)n_cigar[i]);
-            op_at += n_cigar[i];
-        }
-    }
-    SP_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (n_ins_ops == 0 || col_offset[B->n] == 0) return SP_OK;
+    HostRows hr;
+    rc = stage_rows(ctx, B, pairs, (uint32_t)n_pairs, aln, cigar, cigar_stride, n_cigar, col_offset, total_ops, false, &hr);
+    if (rc != SP_OK) return rc;
     InsPass ip;
     rc = ins_begin(ctx, "pileup", B, n_pairs, n_ins_ops, &ip);                            // (the host has counted the runs: the buffer is never too small)
     if (rc != SP_OK) return rc;
-    rc = ins_collect(ctx, "pileup", ip, A, B, (const sp_pair*)(d_in + at_pairs), (const sp_affine_aln*)(d_in + at_aln), (const uint32_t*)(d_in + at_nc), (const uint64_t*)(d_in + at_off),
-                     (const uint32_t*)(d_in + at_ops), n, 0, false, (const uint64_t*)(d_in + at_cols));
+    rc = ins_collect(ctx, "pileup", ip, A, B, hr.pairs, hr.aln, hr.nc, hr.off, hr.ops, (uint32_t)n_pairs, 0, hr.cols);
     if (rc != SP_OK) return rc;
     uint64_t grow = 0;
     rc = ins_finish(ctx, "pileup", ip, ins, ins_cap, n_ins, &grow);
@@ -1040,70 +1068,25 @@ int32_t sp_pileup_hap_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B,
     if (!ctx) return SP_ERR_INVALID_ARG;
     if (!A || !B || !col_offset || !n_haps || !heads || (hap_cap && !haps) || (n_pairs && (!pairs || !aln || !n_cigar))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: null argument");
     if (n_pairs > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: too many pairs");
-    const uint32_t n_t = B->n, n = (uint32_t)n_pairs;
-    if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset[0] must be 0");
-    for (uint32_t t = 0; t < n_t; ++t)
-        if (col_offset[t + 1] < col_offset[t] || col_offset[t + 1] - col_offset[t] != (uint64_t)B->h_len[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: col_offset does not follow the target lengths");
-    const uint64_t n_cols = col_offset[n_t];
-    std::vector<uint32_t> live_of((size_t)n_t + 1, 0);
+    int32_t rc = check_col_offset(ctx, "pileup", B, col_offset);
+    if (rc != SP_OK) return rc;
     uint64_t total_ops = 0, n_ins_ops = 0;
-    int32_t rc = pileup_check_rows(ctx, A, B, pairs, n_pairs, aln, cigar, cigar_stride, n_cigar, live_of, &total_ops, &n_ins_ops);
+    rc = pileup_check_rows(ctx, A, B, pairs, n_pairs, aln, cigar, cigar_stride, n_cigar, &total_ops, &n_ins_ops);
     if (rc != SP_OK) return rc;
     *n_haps = 0;
-    if (n_t == 0) return SP_OK;
-    uint64_t n_tiles = 0;
-    for (uint32_t t = 0; t < n_t; ++t) n_tiles += ((uint64_t)B->h_len[t] + PU_TILE - 1) / PU_TILE;
-    if (n_tiles > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: too many tiles");
-    (void)hipSetDevice(ctx->device);
-    // ---- one staging block, one copy: what the device-resident pass keeps per pair (pairs, spans, op counts, op offsets), its order and offsets for ONE slice, the tiles,
-    //      the column offsets, the ops back to back.  The table is pileup_rows_kernel's, which skips score <= 0: sp_pileup_batch counts every pair with ops, so the
-    //      staged spans of those carry score 1.
-    std::vector<uint32_t> boff((size_t)n_t * 2 + 1, 0);
-    for (uint32_t i = 0; i < n; ++i) ++boff[(size_t)pairs[i].b * 2 + 1];
-    { uint32_t run = 0; for (uint32_t t = 0; t < n_t; ++t) { boff[(size_t)t * 2] = run; run += boff[(size_t)t * 2 + 1]; boff[(size_t)t * 2 + 1] = run; } }
-    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t at_pairs = 0, at_aln = up16(at_pairs + sizeof(sp_pair) * (size_t)n), at_nc = up16(at_aln + sizeof(sp_affine_aln) * (size_t)n), at_off = up16(at_nc + 4 * (size_t)n),
-                 at_order = up16(at_off + 8 * (size_t)n), at_boff = up16(at_order + 4 * (size_t)n), at_tiles = up16(at_boff + 4 * boff.size()),
-                 at_cols = up16(at_tiles + sizeof(PuTile) * (size_t)n_tiles), at_ops = up16(at_cols + 8 * ((size_t)n_t + 1)), in_bytes = up16(at_ops + 4 * (size_t)total_ops) + 16;
-    uint8_t* h_in = (uint8_t*)sp_host_pool(ctx, "pileup_hap_in", in_bytes);
-    uint8_t* d_in = (uint8_t*)sp_pool(ctx, "pileup_hap_in", in_bytes);
-    uint32_t* d_table = (uint32_t*)sp_pool(ctx, "pileup_out", std::max<size_t>(16, n_cols * sizeof(sp_pileup_col)));
-    if (!h_in || !d_in || !d_table) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "pileup buffers");
-    {
-        if (n) std::memcpy(h_in + at_pairs, pairs, sizeof(sp_pair) * (size_t)n);
-        if (n) std::memcpy(h_in + at_nc, n_cigar, 4 * (size_t)n);
-        std::memcpy(h_in + at_boff, boff.data(), 4 * boff.size());
-        std::memcpy(h_in + at_cols, col_offset, 8 * ((size_t)n_t + 1));
-        sp_affine_aln* ha = (sp_affine_aln*)(h_in + at_aln);
-        uint64_t* hoff = (uint64_t*)(h_in + at_off); uint32_t* hops = (uint32_t*)(h_in + at_ops); uint32_t* hord = (uint32_t*)(h_in + at_order);
-        std::vector<uint32_t> at(n_t);
-        for (uint32_t t = 0; t < n_t; ++t) at[t] = boff[(size_t)t * 2];
-        uint64_t op_at = 0;
-        for (uint32_t i = 0; i < n; ++i) {
-            hord[at[pairs[i].b]++] = i;
-            ha[i] = aln[i]; hoff[i] = op_at;
-            if (n_cigar[i] == 0) continue;
-            ha[i].score = 1;
-            std::memcpy(hops + op_at, cigar + i * (size_t)cigar_stride, 4 * (size_t)n_cigar[i]);
-            op_at += n_cigar[i];
-        }
-        PuTile* ht = (PuTile*)(h_in + at_tiles); uint64_t x = 0;
-        for (uint32_t t = 0; t < n_t; ++t) for (int32_t c0 = 0; c0 < B->h_len[t]; c0 += PU_TILE) ht[x++] = PuTile{ t, (uint32_t)c0 };
-    }
-    SP_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    const sp_pair* d_pairs = (const sp_pair*)(d_in + at_pairs); const sp_affine_aln* d_aln = (const sp_affine_aln*)(d_in + at_aln);
-    const uint32_t* d_nc = (const uint32_t*)(d_in + at_nc); const uint64_t* d_off = (const uint64_t*)(d_in + at_off); const uint32_t* d_ops = (const uint32_t*)(d_in + at_ops);
-    const uint32_t* d_order = (const uint32_t*)(d_in + at_order); const uint32_t* d_boff = (const uint32_t*)(d_in + at_boff);
-    if (n_tiles) {
-        rc = pileup_rows_lds(ctx);
-        if (rc != SP_OK) return rc;
-        ProfScope ps(ctx, "pileup", n_cols);
-        hipLaunchKernelGGL(pileup_rows_kernel, dim3((unsigned)n_tiles), dim3(PU_WAVES * SP_WAVE), PU_LDS_BYTES, ctx->stream, A->view(), B->d_len, d_pairs, d_aln, d_nc, d_off, d_ops,
-                           d_order, d_boff, 1u, 0u, (const PuTile*)(d_in + at_tiles), (const uint64_t*)(d_in + at_cols), d_table);
+    if (B->n == 0) return SP_OK;
+    HostRows hr;
+    rc = stage_rows(ctx, B, pairs, (uint32_t)n_pairs, aln, cigar, cigar_stride, n_cigar, col_offset, total_ops, true, &hr);
+    if (rc == SP_OK && hr.n_tiles) rc = pileup_lds(ctx);
+    if (rc != SP_OK) return rc;
+    if (hr.n_tiles) {
+        ProfScope ps(ctx, "pileup", col_offset[B->n]);
+        hipLaunchKernelGGL(pileup_rows_kernel, dim3((unsigned)hr.n_tiles), dim3(PU_WAVES * SP_WAVE), PU_LDS_BYTES, ctx->stream, A->view(), B->d_len, hr.pairs, hr.aln, hr.nc, hr.off, hr.ops,
+                           hr.order, hr.boff, 1u, 0u, hr.tiles, hr.cols, hr.table);
         if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "pileup launch failed");
     }
     HapOut ho; ho.haps = haps; ho.cap = hap_cap; ho.n_haps = n_haps; ho.heads = heads;
-    return hap_run(ctx, "pileup", A, B, n, d_table, (const uint64_t*)(d_in + at_cols), d_pairs, d_aln, d_nc, d_off, d_ops, false, d_order, d_boff, 1, ho);
+    return hap_run(ctx, "pileup", A, B, (uint32_t)n_pairs, hr.table, hr.cols, hr.pairs, hr.aln, hr.nc, hr.off, hr.ops, hr.order, hr.boff, 1, ho);
 }
 
 // sp_align_pileup_band_batch for the library's own callers as well: `who` begins its error texts, prof[] names its four launches (map, second map, pileup, summary) in the
@@ -1117,9 +1100,8 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
         return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": band must be 64 or 256, retry_band 0 or (with band 64) 256");
     if (n_pairs > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": too many pairs");
     const uint32_t n_t = B->n, n = (uint32_t)n_pairs;
-    if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": col_offset[0] must be 0");
-    for (uint32_t t = 0; t < n_t; ++t)
-        if (col_offset[t + 1] < col_offset[t] || col_offset[t + 1] - col_offset[t] != (uint64_t)B->h_len[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": col_offset does not follow the target lengths");
+    const int32_t rc_cols = check_col_offset(ctx, who, B, col_offset);
+    if (rc_cols != SP_OK) return rc_cols;
     const uint64_t n_cols = col_offset[n_t];
     // ---- the pairs by target, from `pairs` alone: target t's pairs of slice s are order[boff[t * (n_slices + 1) + s] ...) (pileup_rows_kernel)
     const uint32_t n_slices = std::max<uint32_t>(1, (n + SP_ALIGN_PILEUP_SLICE - 1) / SP_ALIGN_PILEUP_SLICE);
@@ -1143,8 +1125,8 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
         }
     }
     uint64_t n_tiles = 0;
-    if (want_table) for (uint32_t t = 0; t < n_t; ++t) n_tiles += ((uint64_t)B->h_len[t] + PU_TILE - 1) / PU_TILE;
-    if (n_tiles > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": too many tiles");
+    const int32_t rc_tiles = want_table ? pu_count_tiles(ctx, who, B, &n_tiles) : SP_OK;
+    if (rc_tiles != SP_OK) return rc_tiles;
     (void)hipSetDevice(ctx->device);
     // ---- one staging block, one copy: the pair list as given, the order, the offsets, tiles, column offsets, member counts
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
@@ -1172,14 +1154,13 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
         std::memcpy(h_in + at_boff, boff.data(), 4 * boff.size());
         std::memcpy(h_in + at_cols, col_offset, 8 * ((size_t)n_t + 1));
         if (n_members && n_t) std::memcpy(h_in + at_mem, n_members, 4 * (size_t)n_t);
-        PuTile* ht = (PuTile*)(h_in + at_tiles); uint64_t x = 0;
-        if (want_table) for (uint32_t t = 0; t < n_t; ++t) for (int32_t c0 = 0; c0 < B->h_len[t]; c0 += PU_TILE) ht[x++] = PuTile{ t, (uint32_t)c0 };
+        if (want_table) pu_fill_tiles(B, (PuTile*)(h_in + at_tiles));
     }
     SP_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     const sp_pair* d_pairs = (const sp_pair*)(d_in + at_pairs);
     const uint32_t* d_order = (const uint32_t*)(d_in + at_order); const uint32_t* d_boff = (const uint32_t*)(d_in + at_boff);
     if (n_tiles) {
-        const int32_t rc = pileup_rows_lds(ctx);
+        const int32_t rc = pileup_lds(ctx);
         if (rc != SP_OK) return rc;
     }
     InsPass ip;                                                                                       // the insertion list, when asked for: its runs are collected slice by slice
@@ -1254,7 +1235,7 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
             if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": pileup launch failed");
         }
         if (ins && m > 0) {
-            const int32_t rc = ins_collect(ctx, who, ip, A, B, d_pairs + p0, d_aln + p0, d_nc + p0, d_off + p0, d_ops, m, p0, true, (const uint64_t*)(d_in + at_cols));
+            const int32_t rc = ins_collect(ctx, who, ip, A, B, d_pairs + p0, d_aln + p0, d_nc + p0, d_off + p0, d_ops, m, p0, (const uint64_t*)(d_in + at_cols));
             if (rc != SP_OK) return rc;
         }
     }
@@ -1287,26 +1268,11 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
         }
     }
     if (hap) {
-        const int32_t rc = hap_run(ctx, who, A, B, n, d_table, (const uint64_t*)(d_in + at_cols), d_pairs, d_aln, d_nc, d_off, d_ops, true, d_order, d_boff, n_slices, *hap);
+        const int32_t rc = hap_run(ctx, who, A, B, n, d_table, (const uint64_t*)(d_in + at_cols), d_pairs, d_aln, d_nc, d_off, d_ops, d_order, d_boff, n_slices, *hap);
         if (rc != SP_OK) return rc;
     }
     if (rc_ins != SP_OK) return sp_fail(ctx, rc_ins, who + ": " + std::to_string(*n_ins) + " insertion records, room for " + std::to_string(ins_cap));
     return SP_OK;
-}
-
-int32_t sp_align_pileup_band_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
-                                   const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used) {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    static const char* const prof[4] = { "align_pileup_map", "align_pileup_map_retry", "align_pileup_pile", "align_pileup_summary" };
-    return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, "align_pileup", prof, false);
-}
-
-int32_t sp_align_pileup_ins_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
-                                  const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
-                                  sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    static const char* const prof[4] = { "align_pileup_map", "align_pileup_map_retry", "align_pileup_pile", "align_pileup_summary" };
-    return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, "align_pileup", prof, false, ins, ins_cap, n_ins);
 }
 
 int32_t sp_align_pileup_hap_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
@@ -1317,6 +1283,18 @@ int32_t sp_align_pileup_hap_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqs
     HapOut ho; ho.haps = haps; ho.cap = hap_cap; ho.n_haps = n_haps; ho.heads = heads;
     return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, "align_pileup", prof, false, ins, ins_cap, n_ins, 0,
                             haps ? &ho : nullptr);
+}
+
+// the entries without one list or both: the same path, the list's arguments NULL
+int32_t sp_align_pileup_ins_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
+                                  const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
+                                  sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
+    return sp_align_pileup_hap_batch(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, ins, ins_cap, n_ins, nullptr, 0, nullptr, nullptr);
+}
+
+int32_t sp_align_pileup_band_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
+                                   const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used) {
+    return sp_align_pileup_ins_batch(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, nullptr, 0, nullptr);
 }
 
 int32_t sp_align_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, const uint64_t* col_offset,

@@ -14,6 +14,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import pileup_hap_ref as hap_ref
+import pileup_ins_ref as ins_ref
 import pileup_ref as pr
 
 pytestmark = pytest.mark.gpu
@@ -151,6 +153,58 @@ def test_determinism_and_pair_order(batch, gpu_ctx):
         o = np.array(order)
         again = gpu_ctx.pileup(b["A"], b["B"], [b["pairs"][i] for i in order], b["aln"][o], b["cigar"][o], b["n_cigar"][o])
         assert flat(again) == first
+
+
+def test_host_rows_count_every_pair_with_ops_whatever_its_score(pkg, gpu_ctx):
+    """The host-row entry points (pileup, pileup_ins, pileup_hap) count a pair when it has ops; its score is not looked at.  Hand-made rows, no aligner: targets of
+    1, 65 and T + 1 columns, '=' 'X' 'I' 'D' rows (one crosses the tile edge, one has its 'I' behind the tile's last column), one pair without ops."""
+    T = pkg.ffi.SP_PILEUP_TILE
+    rng = np.random.default_rng(99)
+    lens = [1, 65, T + 1]
+    targets = [rand_seq(rng, n) for n in lens]
+    plan = [(0, 0, [(8, 1)]),
+            (0, 0, [(7, 1)]),
+            (1, 0, [(7, 20), (8, 1), (7, 10), (1, 3), (7, 33), (8, 1)]),                                # all 65 columns, an X on the last
+            (1, 0, [(7, 20), (8, 1), (7, 10), (1, 3), (7, 34)]),                                        # the same insertion once more
+            (1, 5, [(7, 10), (2, 4), (7, 6), (8, 1), (7, 20)]),
+            (2, T - 30, [(7, 20), (2, 10), (8, 1)]),                                                    # a deletion up to the tile edge, an X in the one-column tile
+            (2, T - 5, [(7, 3), (8, 1), (7, 1), (1, 2), (8, 1)]),                                       # an insertion behind the last column of tile 0
+            (2, 0, [(8, 1), (7, 99), (1, 1), (7, 50), (2, 2), (8, 2), (7, 10)]),
+            (2, T - 30, [(7, 20), (8, 1), (7, 9), (8, 1)]),                                             # = and X across the tile edge
+            (1, 0, [])]                                                                                 # no ops: never counted
+    queries, pairs, spans, stride = [], [], [], 8
+    cigar, n_cigar = np.zeros((len(plan), stride), np.uint32), np.zeros(len(plan), np.uint32)
+    for p, (t, b0, ops) in enumerate(plan):
+        q, j = "", b0
+        for k, (op, n) in enumerate(ops):
+            cigar[p, k] = (n << 4) | op
+            if op == 7:
+                q += targets[t][j:j + n]
+            elif op == 8:
+                q += "".join(BASES[(BASES.index(c) + 1 + p % 3) % 4] for c in targets[t][j:j + n])
+            elif op == 1:
+                q += "GAT"[:n]
+            j += 0 if op == 1 else n
+        n_cigar[p] = len(ops)
+        queries.append(q or "A")
+        pairs.append((p, t, 0))
+        spans.append((0, len(q), b0, j) if ops else (0, 0, 0, 0))
+    assert any(b0 < T < b0 + sum(n for op, n in ops if op != 1) for t, b0, ops in plan if t == 2)        # a row across the tile edge
+    A, B = gpu_ctx.upload(queries), gpu_ctx.upload(targets)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    got = []
+    for scores in ([1] * len(plan), [(0, -5, 7)[p % 3] for p in range(len(plan))]):
+        aln = np.array([(s, 0) + span for s, span in zip(scores, spans)], pkg.ffi.AFFINE_DTYPE)
+        haps, heads = gpu_ctx.pileup_hap(A, B, pairs, aln, cigar, n_cigar)
+        got.append((gpu_ctx.pileup(A, B, pairs, aln, cigar, n_cigar), gpu_ctx.pileup_ins(A, B, pairs, aln, cigar, n_cigar), haps, heads))
+        want_hap = hap_ref.records(pairs, aln, cigar, n_cigar, queries, lens, need_score=False)
+        for have, ref in zip(got[-1][0], pr.pileup(queries, lens, pairs, aln, cigar, n_cigar)):
+            assert (pr.as_table(have) == ref).all()
+        assert ins_ref.as_rows(got[-1][1]) == ins_ref.records(pairs, aln, cigar, n_cigar, queries, off, need_score=False)
+        assert hap_ref.as_rows(haps) == want_hap[0] and hap_ref.as_heads(heads) == want_hap[1]
+    assert len(got[0][1]) >= 3 and len(got[0][2]) >= 3 and all(h["n_cols"] > 0 for h in got[0][3])      # the lists are not empty
+    flat = lambda g: (b"".join(t.tobytes() for t in g[0]), g[1].tobytes(), g[2].tobytes(), g[3].tobytes())
+    assert flat(got[0]) == flat(got[1])
 
 
 def raw_call(b, gpu_ctx, cigar, n_cigar=None):
