@@ -2284,6 +2284,8 @@ extern "C" int32_t sp_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_pr
     return mapping_off[n_samples] > cap ? sp_fail(ctx, SP_ERR_CAPACITY, "sp_cyp_diplotype_cohort_mappings: more read mappings than cap") : SP_OK;
 }
 
+std::string spi_cyp_region_label(const sp_cyp_call* call, int32_t h) { return full_allele(call->cons_type[h], call->cons_subtype[h][0] ? call->cons_subtype[h] : nullptr); }
+
 // cyp2d6_alleles.json: DeeplotypeDebug (src/cyp2d6/debug.rs:10-70) written as save_json writes it (serde_json pretty print)
 extern "C" int32_t sp_cyp_alleles_json(const sp_cyp_problem* pr, const sp_cyp_call* call, const sp_cyp_region_variants* rv, char* out, uint64_t cap, uint64_t* needed) {
     if (!pr || !call || !rv) return SP_ERR_INVALID_ARG;
@@ -2307,7 +2309,7 @@ extern "C" int32_t sp_cyp_alleles_json(const sp_cyp_problem* pr, const sp_cyp_ca
             e.obj.emplace_back("label", spj::str(pr->var_label[v])); e.obj.emplace_back("is_vi", spj::boolean(pr->var_is_vi[v] != 0)); e.obj.emplace_back("variant_state", spj::str(names[st]));
             list.arr.push_back(std::move(e));
         }
-        alleles.emplace(std::to_string(h) + "_" + full_allele(call->cons_type[h], call->cons_subtype[h][0] ? call->cons_subtype[h] : nullptr), std::move(list));
+        alleles.emplace(std::to_string(h) + "_" + spi_cyp_region_label(call, h), std::move(list));
     }
     spj::Value amap = spj::object();
     for (auto& kv : alleles) amap.obj.emplace_back(kv.first, std::move(kv.second));
@@ -2316,220 +2318,5 @@ extern "C" int32_t sp_cyp_alleles_json(const sp_cyp_problem* pr, const sp_cyp_ca
     spj::write_pretty(text, root);
     if (needed) *needed = text.size() + 1;
     if (out && cap) { const size_t n = std::min<size_t>(text.size(), (size_t)cap - 1); std::memcpy(out, text.data(), n); out[n] = 0; if (n < text.size()) return SP_ERR_CAPACITY; }
-    return SP_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// CYP2D6 consensus support (contract: include/starphase_hip.h; design: DESIGN.md section 7.2).  Members are the multi_mapping_details records; their segments are forward
-// views of the reads as uploaded and the consensuses were built from such segments (cyp_part_a .. cyp_part_c2 above cut every region with sp_make_segments, which has
-// no strand; sp_region_hit carries none): one orientation, no strand handling.  The segments of all samples go into one small set, one anchor launch gives the
-// diagonals, one sp_align_pileup_batch the tables and summaries; a member without an anchor stays in the pair list with max_ed < 0, so it counts as unaligned.
-// ------------------------------------------------------------------------------------------------------------------------------
-extern "C" int32_t sp_cyp_consensus_support_cohort(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
-                                                   const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
-                                                   sp_support_summary* summaries) {
-    return sp_cyp_consensus_support_cohort_ins(ctx, n_samples, reads, calls, consensus, cons_cap, mappings, mapping_off, col_offset, cols, cols_cap, summaries, nullptr, 0, nullptr);
-}
-
-extern "C" int32_t sp_cyp_consensus_support_cohort_ins(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
-                                                       const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
-                                                       sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
-    return sp_cyp_consensus_support_cohort_hap(ctx, n_samples, reads, calls, consensus, cons_cap, mappings, mapping_off, col_offset, cols, cols_cap, summaries, ins, ins_cap, n_ins,
-                                               nullptr, 0, nullptr, nullptr);
-}
-
-extern "C" int32_t sp_cyp_consensus_support_cohort_hap(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
-                                                       const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
-                                                       sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
-                                                       sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    if ((ins && !n_ins) || (haps && (!n_haps || !heads))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: null argument");
-    if (ins) *n_ins = 0;
-    if (haps) *n_haps = 0;
-    if (!reads || !calls || !mapping_off || !col_offset || !summaries || n_samples == 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: null argument");
-    const uint64_t n_slots = (uint64_t)n_samples * SP_CYP_MAXCONS;
-    // ---- the targets: every non-empty consensus of a call that succeeded, as the call returned it
-    std::vector<int32_t> target_of(n_slots, -1);
-    std::string tblob; std::vector<uint64_t> toff(1, 0);
-    col_offset[0] = 0;
-    for (uint32_t i = 0; i < n_samples; ++i) {
-        const int32_t H = calls[i].status == 0 ? std::min<int32_t>(std::max<int32_t>(calls[i].n_consensus, 0), SP_CYP_MAXCONS) : 0;
-        if (H > 0 && (!consensus || cons_cap == 0 || !reads[i])) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: null argument");
-        for (int32_t h = 0; h < SP_CYP_MAXCONS; ++h) {
-            const uint64_t x = (uint64_t)i * SP_CYP_MAXCONS + h;
-            const char* s = h < H ? consensus + x * (size_t)cons_cap : nullptr;
-            const size_t len = s ? strnlen(s, cons_cap) : 0;
-            col_offset[x + 1] = col_offset[x] + len;
-            if (len == 0) continue;
-            target_of[x] = (int32_t)(toff.size() - 1);
-            tblob.append(s, len); toff.push_back(tblob.size());
-        }
-    }
-    const uint64_t n_cols = col_offset[n_slots];
-    std::memset(summaries, 0, sizeof(sp_support_summary) * n_slots);
-    if (cols && n_cols > cols_cap) return sp_fail(ctx, SP_ERR_CAPACITY, "cyp consensus support: " + std::to_string(n_cols) + " columns, room for " + std::to_string(cols_cap));
-    const uint32_t n_t = (uint32_t)toff.size() - 1;
-    if (n_t == 0) { if (haps) std::memset(heads, 0, sizeof(sp_support_hap_head) * n_slots); return SP_OK; }
-    // ---- the members: one per mapping record whose consensus is a target
-    std::vector<uint32_t> m_target, members_of(n_t, 0);
-    std::vector<uint64_t> m_record;                                      // the member's record in `mappings`
-    std::string qblob; std::vector<uint64_t> qoff(1, 0);
-    for (uint32_t i = 0; i < n_samples; ++i) {
-        if (calls[i].status != 0 || mapping_off[i + 1] == mapping_off[i]) continue;
-        if (mapping_off[i + 1] < mapping_off[i] || !mappings || !reads[i]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: mapping_off");
-        std::map<uint32_t, std::string> decoded;                         // (a read with several regions is fetched once)
-        for (uint64_t k = mapping_off[i]; k < mapping_off[i + 1]; ++k) {
-            const sp_cyp_read_mapping& q = mappings[k];
-            if (q.consensus >= (uint32_t)SP_CYP_MAXCONS || q.read >= reads[i]->n) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: mapping out of range");
-            const int32_t t = target_of[(uint64_t)i * SP_CYP_MAXCONS + q.consensus];
-            if (t < 0) continue;
-            if (q.read_end <= q.read_start || q.read_end > (uint64_t)reads[i]->h_len[q.read]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: segment outside its read");
-            auto it = decoded.find(q.read);
-            if (it == decoded.end()) {
-                it = decoded.emplace(q.read, sp_seqset_decode(ctx, reads[i], q.read)).first;
-                if ((int32_t)it->second.size() != reads[i]->h_len[q.read]) return sp_fail(ctx, SP_ERR_HIP, "cyp consensus support: fetching the reads failed");
-            }
-            qblob.append(it->second, (size_t)q.read_start, (size_t)(q.read_end - q.read_start));
-            qoff.push_back(qblob.size()); m_target.push_back((uint32_t)t); m_record.push_back(k); ++members_of[t];
-        }
-    }
-    const uint32_t n_m = (uint32_t)m_target.size();
-    sp_seqset T, Q;
-    int32_t rc = sp_seqset_make_small(ctx, "cypsup_t", tblob.data(), toff.data(), n_t, true, &T);
-    if (rc != SP_OK) return rc;
-    if (n_m) { rc = sp_seqset_make_small(ctx, "cypsup_q", qblob.data(), qoff.data(), n_m, false, &Q); if (rc != SP_OK) return rc; }
-    else { Q = sp_seqset(); Q.ctx = ctx; }
-    std::vector<sp_pair> pairs(n_m);
-    if (n_m) {
-        std::vector<uint32_t> ident(n_m); std::iota(ident.begin(), ident.end(), 0u);
-        std::vector<int32_t> diag(n_m), votes(n_m);
-        rc = sp_anchor_batch(ctx, &T, &Q, m_target.data(), ident.data(), n_m, diag.data(), votes.data());
-        if (rc != SP_OK) return rc;
-        for (uint32_t m = 0; m < n_m; ++m) pairs[m] = sp_pair{ m, m_target[m], votes[m] > 0 ? -diag[m] : 0, votes[m] > 0 ? 0 : -1 };
-    }
-    const sp_affine_opts ao = { 1, 4, 6, 2, 26, 1, 1 };
-    std::vector<uint64_t> t_cols(toff);
-    std::vector<sp_pileup_col> table(cols ? n_cols : 0);
-    std::vector<sp_support_summary> sm(n_t);
-    std::vector<sp_support_hap_head> t_heads(haps ? n_t : 0);
-    if (haps) rc = sp_align_pileup_hap_batch(ctx, &Q, &T, pairs.data(), n_m, &ao, 64, 0, t_cols.data(), nullptr, cols ? table.data() : nullptr, sm.data(), members_of.data(), nullptr, ins, ins_cap, n_ins,
-                                             haps, hap_cap, n_haps, t_heads.data());
-    else if (ins) rc = sp_align_pileup_ins_batch(ctx, &Q, &T, pairs.data(), n_m, &ao, 64, 0, t_cols.data(), nullptr, cols ? table.data() : nullptr, sm.data(), members_of.data(), nullptr, ins, ins_cap, n_ins);
-    else rc = sp_align_pileup_batch(ctx, &Q, &T, pairs.data(), n_m, &ao, t_cols.data(), nullptr, cols ? table.data() : nullptr, sm.data(), members_of.data());
-    if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ((ins && *n_ins > ins_cap) || (haps && *n_haps > hap_cap)))) return rc;
-    for (uint64_t x = 0; x < n_slots; ++x) {
-        const int32_t t = target_of[x];
-        if (t < 0) continue;
-        summaries[x] = sm[t];
-        if (cols) std::memcpy(cols + col_offset[x], table.data() + t_cols[t], sizeof(sp_pileup_col) * (size_t)(t_cols[t + 1] - t_cols[t]));
-    }
-    // (a list that did not fit: everything else is complete, the other list included)
-    if (ins && *n_ins && *n_ins <= ins_cap) {
-        // the list in the caller's terms: the targets are the consensuses that have columns, in col_offset's order, so the records stay in order
-        std::vector<uint64_t> base(n_t, 0);
-        for (uint64_t x = 0; x < n_slots; ++x) if (target_of[x] >= 0) base[target_of[x]] = col_offset[x];
-        for (uint64_t k = 0; k < *n_ins; ++k) {
-            const uint32_t t = (uint32_t)(std::upper_bound(t_cols.begin(), t_cols.end(), ins[k].col) - t_cols.begin()) - 1;
-            ins[k].col = base[t] + (ins[k].col - t_cols[t]);
-            if (ins[k].len) ins[k].first_pair = (uint32_t)m_record[ins[k].first_pair];
-        }
-    }
-    if (haps && *n_haps <= hap_cap) {
-        // the haplotype list in the caller's terms: target = the slot of col_offset, first_pair = the member's record in `mappings`
-        std::vector<uint64_t> slot_of(n_t, 0);
-        uint64_t at = 0;
-        for (uint64_t x = 0; x < n_slots; ++x) {
-            const int32_t t = target_of[x];
-            if (t >= 0) { slot_of[t] = x; heads[x] = t_heads[t]; at = t_heads[t].first_record + t_heads[t].n_records; }
-            else { heads[x] = sp_support_hap_head{}; heads[x].first_record = at; }
-        }
-        for (uint64_t k = 0; k < *n_haps; ++k) { haps[k].target = slot_of[haps[k].target]; haps[k].first_pair = (uint32_t)m_record[haps[k].first_pair]; }
-    }
-    return rc;
-}
-
-extern "C" int32_t sp_cyp_consensus_support(sp_ctx* ctx, const sp_seqset* reads, const sp_cyp_call* call, const char* consensus, uint32_t cons_cap,
-                                            const sp_cyp_read_mapping* mappings, uint64_t n_mappings, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
-                                            sp_support_summary* summaries) {
-    return sp_cyp_consensus_support_ins(ctx, reads, call, consensus, cons_cap, mappings, n_mappings, col_offset, cols, cols_cap, summaries, nullptr, 0, nullptr);
-}
-
-extern "C" int32_t sp_cyp_consensus_support_ins(sp_ctx* ctx, const sp_seqset* reads, const sp_cyp_call* call, const char* consensus, uint32_t cons_cap,
-                                                const sp_cyp_read_mapping* mappings, uint64_t n_mappings, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
-                                                sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
-    return sp_cyp_consensus_support_hap(ctx, reads, call, consensus, cons_cap, mappings, n_mappings, col_offset, cols, cols_cap, summaries, ins, ins_cap, n_ins, nullptr, 0, nullptr, nullptr);
-}
-
-extern "C" int32_t sp_cyp_consensus_support_hap(sp_ctx* ctx, const sp_seqset* reads, const sp_cyp_call* call, const char* consensus, uint32_t cons_cap,
-                                                const sp_cyp_read_mapping* mappings, uint64_t n_mappings, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
-                                                sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
-                                                sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    if (!call || !col_offset || !summaries) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: null argument");
-    const int32_t H = std::min<int32_t>(std::max<int32_t>(call->n_consensus, 0), SP_CYP_MAXCONS);
-    uint64_t off[SP_CYP_MAXCONS + 1] = { 0 }; sp_support_summary sm[SP_CYP_MAXCONS];
-    const uint64_t moff[2] = { 0, n_mappings };
-    if (haps && !heads) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp consensus support: null argument");
-    sp_support_hap_head hd[SP_CYP_MAXCONS];
-    const int32_t rc = sp_cyp_consensus_support_cohort_hap(ctx, 1, &reads, call, consensus, cons_cap, mappings, moff, off, cols, cols_cap, sm, ins, ins_cap, n_ins, haps, hap_cap, n_haps, haps ? hd : nullptr);
-    std::memcpy(col_offset, off, sizeof(uint64_t) * ((size_t)H + 1));
-    if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ((ins && n_ins && *n_ins > ins_cap) || (haps && n_haps && *n_haps > hap_cap)))) return rc;
-    std::memcpy(summaries, sm, sizeof(sp_support_summary) * (size_t)H);
-    if (haps && n_haps && *n_haps <= hap_cap) std::memcpy(heads, hd, sizeof(sp_support_hap_head) * (size_t)H);
-    return rc;
-}
-
-extern "C" int32_t sp_cyp_support_json(const sp_cyp_call* call, const char* consensus, uint32_t cons_cap, const uint64_t* col_offset, const sp_pileup_col* cols,
-                                       const sp_support_summary* summaries, char* out, uint64_t cap, uint64_t* needed) {
-    return sp_cyp_support_json_ins(call, consensus, cons_cap, col_offset, cols, summaries, nullptr, 0, nullptr, 0, nullptr, 0, out, cap, needed);
-}
-
-extern "C" int32_t sp_cyp_support_json_ins(const sp_cyp_call* call, const char* consensus, uint32_t cons_cap, const uint64_t* col_offset, const sp_pileup_col* cols,
-                                           const sp_support_summary* summaries, const sp_pileup_ins* ins, uint64_t n_ins, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
-                                           const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed) {
-    return sp_cyp_support_json_hap(call, consensus, cons_cap, col_offset, cols, summaries, ins, n_ins, nullptr, 0, nullptr, 0, mappings, n_mappings, read_names, n_read_names, out, cap, needed);
-}
-
-extern "C" int32_t sp_cyp_support_json_hap(const sp_cyp_call* call, const char* consensus, uint32_t cons_cap, const uint64_t* col_offset, const sp_pileup_col* cols,
-                                           const sp_support_summary* summaries, const sp_pileup_ins* ins, uint64_t n_ins, const sp_support_hap* haps, uint64_t n_haps,
-                                           const sp_support_hap_head* heads, uint64_t target0, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
-                                           const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed) {
-    if (!call || (cap && !out) || (n_ins && !ins) || (n_haps && (!haps || !heads))) return SP_ERR_INVALID_ARG;
-    const int32_t H = call->status == 0 ? std::min<int32_t>(std::max<int32_t>(call->n_consensus, 0), SP_CYP_MAXCONS) : 0;
-    if (H > 0 && (!consensus || cons_cap == 0 || !col_offset || !summaries)) return SP_ERR_INVALID_ARG;
-    spj::Value root = spj::object();
-    for (int32_t h = 0; h < H; ++h) {
-        const sp_support_summary& sm = summaries[h];
-        const char* s = consensus + (size_t)h * cons_cap;
-        if (col_offset[h + 1] < col_offset[h] || col_offset[h + 1] - col_offset[h] != sm.length || strnlen(s, cons_cap) < sm.length || (sm.length && !cols)) return SP_ERR_INVALID_ARG;
-        const sp_pileup_col* c = cols ? cols + col_offset[h] : nullptr;
-        const std::string type = full_allele(call->cons_type[h], call->cons_subtype[h][0] ? call->cons_subtype[h] : nullptr);
-        spj::Value v = spj::object();
-        v.obj.emplace_back("n_members", spj::unum(sm.n_members)); v.obj.emplace_back("n_aligned", spj::unum(sm.n_aligned)); v.obj.emplace_back("n_unaligned", spj::unum(sm.n_unaligned));
-        v.obj.emplace_back("length", spj::unum(sm.length)); v.obj.emplace_back("min_depth", spj::unum(sm.min_depth)); v.obj.emplace_back("median_depth", spj::unum(sm.median_depth));
-        v.obj.emplace_back("n_contested", spj::unum(sm.n_contested));
-        v.obj.emplace_back("region_type", spj::str(type));
-        spj::Value list = spj::array();
-        for (uint32_t j = 0; j < sm.length; ++j) {
-            if (!((c[j].depth > 0 && 2ull * c[j].eq <= c[j].depth) || 2ull * c[j].ins > c[j].depth)) continue;      // the rule of sp_support_summary
-            spj::Value k = spj::object();
-            k.obj.emplace_back("pos", spj::unum(j)); k.obj.emplace_back("depth", spj::unum(c[j].depth)); k.obj.emplace_back("eq", spj::unum(c[j].eq));
-            spj::Value x = spj::array();
-            for (int b = 0; b < 4; ++b) x.arr.push_back(spj::unum(c[j].x[b]));
-            k.obj.emplace_back("x", std::move(x));
-            k.obj.emplace_back("del", spj::unum(c[j].del)); k.obj.emplace_back("ins", spj::unum(c[j].ins));
-            k.obj.emplace_back("consensus_base", spj::str(std::string(1, s[j])));
-            if (n_ins && 2ull * c[j].ins > c[j].depth) spi_support_ins_json(&k, ins, n_ins, col_offset[h] + j, mappings, n_mappings, mappings ? read_names : nullptr, n_read_names);
-            list.arr.push_back(std::move(k));
-        }
-        v.obj.emplace_back("contested", std::move(list));
-        if (n_haps) spi_support_hap_json(&v, c, sm.length, haps, n_haps, heads + target0 + h, target0 + (uint64_t)h, mappings, n_mappings, mappings ? read_names : nullptr, n_read_names);
-        root.obj.emplace_back(std::to_string(h) + "_" + type, std::move(v));
-    }
-    std::string text;
-    spj::write_pretty(text, root);
-    if (needed) *needed = text.size() + 1;
-    if (cap < text.size() + 1) { if (cap) out[0] = '\0'; return SP_ERR_CAPACITY; }
-    std::memcpy(out, text.c_str(), text.size() + 1);
     return SP_OK;
 }

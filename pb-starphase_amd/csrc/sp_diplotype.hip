@@ -581,32 +581,25 @@ struct SupportView { const uint64_t* off; const sp_pileup_col* cols; const sp_su
                      const sp_support_hap* haps = nullptr; uint64_t n_haps = 0; const sp_support_hap_head* heads = nullptr; uint64_t n_heads = 0, slot0 = 0; };   // slot0: the sample's first slot in the group's pass
 // the lists of a support pass (sp_starphase_set_support_insertions / _haplotypes): each stays empty when it is not asked for
 struct SupportLists { std::vector<sp_pileup_ins> ins; std::vector<sp_support_hap> haps; std::vector<sp_support_hap_head> heads; };
-// a support call that makes the haplotype list, and the insertion list when that is asked for as well: `call(ins, ins_cap, &n_ins, haps, hap_cap, &n_haps, heads)` with
-// room for a guess, again with the room it asked for (each list can ask once)
-template <class F> int32_t support_with_lists(SupportLists& L, bool want_ins, size_t n_heads, F call) {
+// a support call with the lists that are asked for: `call(ins, ins_cap, &n_ins, haps, hap_cap, &n_haps, heads)`, the arguments of a list that is not asked for NULL.
+// Without a list it is called once; with one, with room for a guess (16,384 records: 0.9 MB of insertions; a list that is longer costs the pass another run) and
+// again with the room it asked for -- each list can ask once, the insertion list alone is asked once
+template <class F> int32_t support_with_lists(SupportLists& L, bool want_ins, bool want_haps, size_t n_heads, F call) {
     if (want_ins && L.ins.size() < 16384) L.ins.resize(16384);
-    if (L.haps.size() < 16384) L.haps.resize(16384);
-    L.heads.assign(std::max<size_t>(n_heads, 1), sp_support_hap_head{});
+    if (want_haps && L.haps.size() < 16384) L.haps.resize(16384);
+    if (want_haps) L.heads.assign(std::max<size_t>(n_heads, 1), sp_support_hap_head{});
     uint64_t n_i = 0, n_h = 0;
     int32_t rc = SP_OK;
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        rc = call(want_ins ? L.ins.data() : nullptr, (uint64_t)(want_ins ? L.ins.size() : 0), want_ins ? &n_i : nullptr, L.haps.data(), (uint64_t)L.haps.size(), &n_h, L.heads.data());
+    for (int attempt = 0, calls = want_haps ? 3 : want_ins ? 2 : 1; attempt < calls; ++attempt) {
+        rc = call(want_ins ? L.ins.data() : nullptr, (uint64_t)(want_ins ? L.ins.size() : 0), want_ins ? &n_i : nullptr,
+                  want_haps ? L.haps.data() : nullptr, (uint64_t)(want_haps ? L.haps.size() : 0), want_haps ? &n_h : nullptr, want_haps ? L.heads.data() : nullptr);
         if (rc != SP_ERR_CAPACITY) break;
         bool grew = false;
         if (want_ins && n_i > L.ins.size()) { L.ins.resize((size_t)n_i); grew = true; }
-        if (n_h > L.haps.size()) { L.haps.resize((size_t)n_h); grew = true; }
+        if (want_haps && n_h > L.haps.size()) { L.haps.resize((size_t)n_h); grew = true; }
         if (!grew) break;
     }
-    L.ins.resize(rc == SP_OK && want_ins ? (size_t)n_i : 0); L.haps.resize(rc == SP_OK ? (size_t)n_h : 0);
-    return rc;
-}
-// a support call that also makes its insertion list: `call(ins, cap, &n)` with room for a guess, once more with the room it asked for
-template <class F> int32_t support_with_ins(std::vector<sp_pileup_ins>& ins, F call) {
-    if (ins.size() < 16384) ins.resize(16384);                       // (0.9 MB; a list that is longer costs the pass a second run)
-    uint64_t n = 0;
-    int32_t rc = call(ins.data(), (uint64_t)ins.size(), &n);
-    if (rc == SP_ERR_CAPACITY && n > ins.size()) { ins.resize((size_t)n); rc = call(ins.data(), (uint64_t)ins.size(), &n); }
-    ins.resize(rc == SP_OK ? (size_t)n : 0);
+    L.ins.resize(rc == SP_OK && want_ins ? (size_t)n_i : 0); L.haps.resize(rc == SP_OK && want_haps ? (size_t)n_h : 0);
     return rc;
 }
 int32_t consensus_support_save(sp_starphase* h, const sp_hla_call* calls, const SupportView* view, const std::string& debug_folder, std::string& err) {
@@ -779,13 +772,12 @@ void cyp_package(sp_starphase* h, const sp_cyp_problem& pr, const sp_cyp_call& c
 // (off: MAXCONS + 1 offsets into cols, sm: MAXCONS summaries, cons: the sample's consensus block).  A failure fails the sample's CYP2D6 entry.
 void cyp_support_save(const sp_cyp_call& call, const char* cons, uint32_t cons_cap, const uint64_t* off, const sp_pileup_col* cols, const sp_support_summary* sm,
                       const SupportLists& lists, uint64_t slot0, const std::string& debug_folder, CypLane* L) {
-    const std::vector<sp_pileup_ins>& ins = lists.ins;
     const uint64_t n_haps = lists.haps.size();                       // (heads: the pass's, the sample's first at slot0)
     uint64_t need = 0;
-    int32_t rc = sp_cyp_support_json_hap(&call, cons, cons_cap, off, cols, sm, ins.data(), ins.size(), n_haps ? lists.haps.data() : nullptr, n_haps, n_haps ? lists.heads.data() : nullptr, slot0,
+    int32_t rc = sp_cyp_support_json_hap(&call, cons, cons_cap, off, cols, sm, lists.ins.data(), lists.ins.size(), n_haps ? lists.haps.data() : nullptr, n_haps, n_haps ? lists.heads.data() : nullptr, slot0,
                                          nullptr, 0, nullptr, 0, nullptr, 0, &need);
     std::string text((size_t)need, '\0');
-    if (rc == SP_OK || rc == SP_ERR_CAPACITY) rc = sp_cyp_support_json_hap(&call, cons, cons_cap, off, cols, sm, ins.data(), ins.size(), n_haps ? lists.haps.data() : nullptr, n_haps,
+    if (rc == SP_OK || rc == SP_ERR_CAPACITY) rc = sp_cyp_support_json_hap(&call, cons, cons_cap, off, cols, sm, lists.ins.data(), lists.ins.size(), n_haps ? lists.haps.data() : nullptr, n_haps,
                                                                            n_haps ? lists.heads.data() : nullptr, slot0, nullptr, 0, nullptr, 0, &text[0], need, &need);
     if (rc != SP_OK) { L->rc = rc; L->err = "cyp2d6_consensus_support.json: the tables do not fit their consensuses"; return; }
     const std::string path = debug_folder + "/cyp2d6_consensus_support.json";
@@ -907,26 +899,16 @@ void cyp_group(sp_starphase* h, std::vector<Sample*> group, bool only_ok, double
             if (!on.empty()) {
                 std::vector<uint64_t> off((size_t)n * SP_CYP_MAXCONS + 1, 0); std::vector<sp_pileup_col> cols((size_t)n_cols + 1); std::vector<sp_support_summary> sm((size_t)n * SP_CYP_MAXCONS);
                 SupportLists lists;                                  // (stay empty without sp_starphase_set_support_insertions / _haplotypes: the renderer then writes the file as before)
-                std::vector<sp_pileup_ins>& ins = lists.ins;
-                int32_t rc = h->support_haplotypes
-                    ? support_with_lists(lists, h->support_insertions != 0, (size_t)n * SP_CYP_MAXCONS, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got, sp_support_hap* hp, uint64_t hroom, uint64_t* hgot, sp_support_hap_head* hd) {
-                          return sp_cyp_consensus_support_cohort_hap(h->ctx2, n, sets.data(), sc.data(), cons.data(), cons_cap, flat.data(), moff.data(), off.data(), cols.data(), n_cols, sm.data(), p, room, got, hp, hroom, hgot, hd); })
-                    : !h->support_insertions
-                    ? sp_cyp_consensus_support_cohort(h->ctx2, n, sets.data(), sc.data(), cons.data(), cons_cap, flat.data(), moff.data(), off.data(), cols.data(), n_cols, sm.data())
-                    : support_with_ins(ins, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got) {
-                          return sp_cyp_consensus_support_cohort_ins(h->ctx2, n, sets.data(), sc.data(), cons.data(), cons_cap, flat.data(), moff.data(), off.data(), cols.data(), n_cols, sm.data(), p, room, got); });
+                const bool want_ins = h->support_insertions != 0, want_haps = h->support_haplotypes != 0;
+                int32_t rc = support_with_lists(lists, want_ins, want_haps, (size_t)n * SP_CYP_MAXCONS, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got, sp_support_hap* hp, uint64_t hroom, uint64_t* hgot, sp_support_hap_head* hd) {
+                    return sp_cyp_consensus_support_cohort_hap(h->ctx2, n, sets.data(), sc.data(), cons.data(), cons_cap, flat.data(), moff.data(), off.data(), cols.data(), n_cols, sm.data(), p, room, got, hp, hroom, hgot, hd); });
                 if (rc == SP_OK) {
                     for (uint32_t k : on) cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data() + (size_t)k * SP_CYP_MAXCONS, cols.data(), sm.data() + (size_t)k * SP_CYP_MAXCONS, lists, (uint64_t)k * SP_CYP_MAXCONS, typed[k]->debug, &typed[k]->cyp);
                 } else for (uint32_t k : on) {
                     // the shared pass failed: sample by sample, and only the samples whose own pass fails are failed (alone in the pass: that failure is its own)
                     CypLane* L = &typed[k]->cyp;
-                    if (on.size() > 1) rc = h->support_haplotypes
-                        ? support_with_lists(lists, h->support_insertions != 0, SP_CYP_MAXCONS, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got, sp_support_hap* hp, uint64_t hroom, uint64_t* hgot, sp_support_hap_head* hd) {
-                              return sp_cyp_consensus_support_hap(h->ctx2, sets[k], &calls[k], cons.data() + cons_block * k, cons_cap, mappings[k].data(), mappings[k].size(), off.data(), cols.data(), n_cols, sm.data(), p, room, got, hp, hroom, hgot, hd); })
-                        : !h->support_insertions
-                        ? sp_cyp_consensus_support(h->ctx2, sets[k], &calls[k], cons.data() + cons_block * k, cons_cap, mappings[k].data(), mappings[k].size(), off.data(), cols.data(), n_cols, sm.data())
-                        : support_with_ins(ins, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got) {
-                              return sp_cyp_consensus_support_ins(h->ctx2, sets[k], &calls[k], cons.data() + cons_block * k, cons_cap, mappings[k].data(), mappings[k].size(), off.data(), cols.data(), n_cols, sm.data(), p, room, got); });
+                    if (on.size() > 1) rc = support_with_lists(lists, want_ins, want_haps, SP_CYP_MAXCONS, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got, sp_support_hap* hp, uint64_t hroom, uint64_t* hgot, sp_support_hap_head* hd) {
+                        return sp_cyp_consensus_support_hap(h->ctx2, sets[k], &calls[k], cons.data() + cons_block * k, cons_cap, mappings[k].data(), mappings[k].size(), off.data(), cols.data(), n_cols, sm.data(), p, room, got, hp, hroom, hgot, hd); });
                     if (rc != SP_OK) { L->rc = rc; L->err = "sp_cyp_consensus_support: " + opt(sp_last_error(h->ctx2)); continue; }
                     cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data(), cols.data(), sm.data(), lists, 0, typed[k]->debug, L);
                 }
@@ -961,7 +943,6 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
     for (Sample* b : with) want_support |= h->consensus_support && !b->debug.empty();
     std::vector<uint8_t> is1; std::vector<uint64_t> sup_off; std::vector<sp_pileup_col> sup_cols; std::vector<sp_support_summary> sup_sm;
     SupportLists sup_lists;                                          // (sp_starphase_set_support_insertions / _haplotypes; empty otherwise)
-    std::vector<sp_pileup_ins>& sup_ins = sup_lists.ins;
     std::vector<int32_t> cohort_of(with.size(), -1);                 // a sample's place among the samples with reads
     if (R) {
         sp_seqset* set = nullptr;
@@ -1007,17 +988,9 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
                 }
             }
             sup_off.assign(at.size() * G * 2 + 1, 0); sup_cols.resize((size_t)n_cols + 1); sup_sm.resize(at.size() * G * 2);
-            if (h->support_haplotypes)
-                rc = support_with_lists(sup_lists, h->support_insertions != 0, at.size() * G * 2, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got, sp_support_hap* hp, uint64_t hroom, uint64_t* hgot, sp_support_hap_head* hd) {
-                    return sp_hla_consensus_support_cohort_hap(h->ctx, h->hla, (uint32_t)at.size(), read_sample.data(), (uint32_t)G, genes.data(), set, rec.data(), is1.data(),
-                                                               h->hla_cons.data(), cap, unit_on.data(), sup_off.data(), sup_cols.data(), n_cols, sup_sm.data(), p, room, got, hp, hroom, hgot, hd); });
-            else if (!h->support_insertions)
-                rc = sp_hla_consensus_support_cohort(h->ctx, h->hla, (uint32_t)at.size(), read_sample.data(), (uint32_t)G, genes.data(), set, rec.data(), is1.data(),
-                                                     h->hla_cons.data(), cap, unit_on.data(), sup_off.data(), sup_cols.data(), n_cols, sup_sm.data());
-            else
-                rc = support_with_ins(sup_ins, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got) {
-                    return sp_hla_consensus_support_cohort_ins(h->ctx, h->hla, (uint32_t)at.size(), read_sample.data(), (uint32_t)G, genes.data(), set, rec.data(), is1.data(),
-                                                               h->hla_cons.data(), cap, unit_on.data(), sup_off.data(), sup_cols.data(), n_cols, sup_sm.data(), p, room, got); });
+            rc = support_with_lists(sup_lists, h->support_insertions != 0, h->support_haplotypes != 0, at.size() * G * 2, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got, sp_support_hap* hp, uint64_t hroom, uint64_t* hgot, sp_support_hap_head* hd) {
+                return sp_hla_consensus_support_cohort_hap(h->ctx, h->hla, (uint32_t)at.size(), read_sample.data(), (uint32_t)G, genes.data(), set, rec.data(), is1.data(),
+                                                           h->hla_cons.data(), cap, unit_on.data(), sup_off.data(), sup_cols.data(), n_cols, sup_sm.data(), p, room, got, hp, hroom, hgot, hd); });
             if (rc != SP_OK) { err = "sp_hla_consensus_support: " + opt(sp_last_error(h->ctx)); return rc; }
         }
         // the per-allele mappings of hla_debug.json: every consensus of the samples that have a debug folder, in one batched map
@@ -1050,7 +1023,7 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
         std::string e;
         SupportView sv{};
         const bool sup = want_support && cohort_of[k] >= 0 && !sup_off.empty();
-        if (sup) { const size_t x = (size_t)cohort_of[k]; sv = SupportView{ sup_off.data() + x * G * 2, sup_cols.data(), sup_sm.data() + x * G * 2, h->hla_cons.data() + x * G * 2 * (size_t)cap, cap, sup_ins.data(), sup_ins.size(),
+        if (sup) { const size_t x = (size_t)cohort_of[k]; sv = SupportView{ sup_off.data() + x * G * 2, sup_cols.data(), sup_sm.data() + x * G * 2, h->hla_cons.data() + x * G * 2 * (size_t)cap, cap, sup_lists.ins.data(), sup_lists.ins.size(),
                                                                             sup_lists.haps.data(), sup_lists.haps.size(), sup_lists.heads.data(), sup_lists.heads.size(), x * G * 2 }; }
         const int32_t rc = hla_package(h, b->hreads, b->hsearched, orders[k], rec.data() + first[k], rev.data() + first[k], calls.data() + k * G, b->debug, b->hla_entries, e,
                                        want_cigars ? &cigars : nullptr, first[k], maps.map, maps.map ? map_item.data() + k * G * 2 : nullptr, &b->hwarn,

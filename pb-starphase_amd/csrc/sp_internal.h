@@ -234,20 +234,23 @@ struct ProfScope {
 int32_t spi_gene_entry_extras(const sp_database* db, const sp_variant_gene* g, std::string* reference_allele, bool* has_sv, std::string* sv_chrom);
 // sp_hla.hip, for sp_diplotype.hip: allele a of the database in hg38 orientation (the target of sp_hla_realign_cigars), ASCII; empty: no DNA sequence
 std::string spi_hla_allele_fwd(sp_ctx* ctx, const sp_hla_db* db, uint32_t a);
-// sp_hla.hip, for sp_pileup.hip: is_forward_strand of a gene of the database (1 / 0), -1: no such gene
+// sp_hla.hip, for sp_support.hip: is_forward_strand of a gene of the database (1 / 0), -1: no such gene
 int spi_hla_gene_fwd(const sp_hla_db* db, uint32_t gene);
 // sp_hla.hip, for sp_diplotype.hip: sp_hla_map_type_consensus for n consensuses in one batched map; item_of[x] = the consensus that item x of the map is (those that place)
 int32_t spi_hla_map_type_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, const uint32_t* genes, const char* const* consensus_fwd, const uint32_t* consensus_len,
                                int32_t require_dna, int32_t disable_cdna, sp_hla_map** out, std::vector<uint32_t>* item_of);
-// sp_pileup.hip, for the two support renderers: adds "insertions" (and "more", "other") to the object of a contested column from the records of column `col` of a list in
-// record order.  first_read: names[first_pair], or names[mappings[first_pair].read] when mappings is given; left out without names or for an index outside them.
-namespace spj { struct Value; }
-void spi_support_ins_json(spj::Value* column, const sp_pileup_ins* ins, uint64_t n_ins, uint64_t col, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
-                          const char* const* names, uint32_t n_names);
-// the same for the haplotype list: adds "haplotypes" to the object of a consensus (cols: its `length` columns) from the records of target `target` of a list; nothing
-// when the target's head has n_cols == 0 or no records.  first_read as above.
-void spi_support_hap_json(spj::Value* consensus, const sp_pileup_col* cols, uint32_t length, const sp_support_hap* haps, uint64_t n_haps, const sp_support_hap_head* head,
-                          uint64_t target, const sp_cyp_read_mapping* mappings, uint64_t n_mappings, const char* const* names, uint32_t n_names);
+// sp_pileup.hip, for its kernels and for sp_support.hip: a column whose consensus base, or the absence of an insertion behind it, lacks a strict majority of the members that span it
+__host__ __device__ inline bool pu_contested(uint32_t depth, uint32_t eq, uint32_t ins) { return (depth > 0 && 2ull * eq <= depth) || 2ull * ins > depth; }
+// sp_pileup.hip, for sp_support.hip: sp_align_pileup_hap_batch with what no public entry carries -- `who` begins its error texts, prof[] names its four launches (map, second
+// map, pileup, summary) in the context's profile, and the first map launch counts the pairs it attempts (max_ed >= 0) when count_attempted is set, every pair of the
+// slice otherwise.  HapOut: where the haplotype list goes (heads: one per target of B).  ins_runs: 0 (the pass sizes its run buffer itself).
+struct HapOut { sp_support_hap* haps; uint64_t cap; uint64_t* n_haps; sp_support_hap_head* heads; };
+int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
+                         const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
+                         const std::string& who, const char* const prof[4], bool count_attempted,
+                         sp_pileup_ins* ins = nullptr, uint64_t ins_cap = 0, uint64_t* n_ins = nullptr, uint64_t ins_runs = 0, const HapOut* hap = nullptr);
+// sp_cyp.hip, for sp_support.hip: the label of consensus h of a call, as the debug files name a region (RegionLabel::full_allele)
+std::string spi_cyp_region_label(const sp_cyp_call* call, int32_t h);
 // sp_cyp.hip, for sp_diplotype.hip: sp_cyp_diplotype_mappings with the list in a vector the library sizes
 int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
                                    sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings);

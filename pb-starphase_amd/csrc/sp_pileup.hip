@@ -1,6 +1,6 @@
-// sp_pileup.hip -- many alignments -> integer counts per target column (sp_pileup_batch), and what is built on it: the support of the consensuses of an HLA gene call
-// by their member reads (sp_hla_consensus_support*), its summary rule and the `consensus_support.json` debug file (host only); and sp_align_pileup_batch: alignment,
-// pileup and summary in one device-resident pass (the CYP2D6 support of sp_cyp.hip runs on it).  Contract: include/starphase_hip.h; design: DESIGN.md section 7.2.
+// sp_pileup.hip -- many alignments -> integer counts per target column (sp_pileup_batch), the insertion and haplotype lists behind the table, and sp_align_pileup_batch:
+// alignment, pileup, summary and lists in one device-resident pass.  The consensus support of HLA and CYP2D6 calls (sp_support.hip) runs on that pass.  Contract:
+// include/starphase_hip.h; design: DESIGN.md section 7.2.
 #include "sp_internal.h"
 #include "sp_json.h"
 #include <algorithm>
@@ -115,9 +115,6 @@ constexpr uint64_t AP_NO_OPS = ~0ull;
 
 // the pairs the table counts (wave-uniform): a row of ops that was kept (the host reports the other two) and an alignment.  Host op rows are staged with score 1.
 __device__ __forceinline__ bool ap_counted(uint32_t n_ops, uint64_t off, const sp_affine_aln* g) { return n_ops != 0 && n_ops != AP_LOST && off != AP_NO_OPS && g->score > 0; }
-
-// a column whose consensus base, or the absence of an insertion behind it, lacks a strict majority of the members that span it
-__host__ __device__ inline bool pu_contested(uint32_t depth, uint32_t eq, uint32_t ins) { return (depth > 0 && 2ull * eq <= depth) || 2ull * ins > depth; }
 
 // A wave takes its places in a list with one ballot and one atomic on the list's counter: the place of a lane that wants one (all 64 lanes call).
 template <class T> __device__ __forceinline__ T wave_append(bool want, T* count, int lane) {
@@ -633,18 +630,6 @@ __global__ void hap_pack_kernel(const sp_support_hap* __restrict__ tmp, const ui
     }
 }
 
-static bool contested_col(const sp_pileup_col& c) { return pu_contested(c.depth, c.eq, c.ins); }
-
-static std::string revcomp_str(const char* s, size_t n) {
-    std::string r(n, 'N');
-    for (size_t i = 0; i < n; ++i) {
-        char c = s[n - 1 - i];
-        switch (c) { case 'A': case 'a': c = 'T'; break; case 'C': case 'c': c = 'G'; break; case 'G': case 'g': c = 'C'; break; case 'T': case 't': c = 'A'; break; default: c = 'N'; }
-        r[i] = c;
-    }
-    return r;
-}
-
 static int32_t check_col_offset(sp_ctx* ctx, const std::string& who, const sp_seqset* B, const uint64_t* col_offset) {
     if (col_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": col_offset[0] must be 0");
     for (uint32_t t = 0; t < B->n; ++t)
@@ -841,10 +826,8 @@ static int32_t stage_rows(sp_ctx* ctx, const sp_seqset* B, const sp_pair* pairs,
     return SP_OK;
 }
 
-// ---- the host side of the haplotype list: one pooled buffer carved by the numbers of pairs and targets (a warm context allocates nothing), the launches, the way out
-struct HapOut { sp_support_hap* haps; uint64_t cap; uint64_t* n_haps; sp_support_hap_head* heads; };
-
-// the list over n pairs whose rows lie in device memory (d_ops: the rows of ALL of them), behind the finished table d_table.  A list that does not fit: SP_ERR_CAPACITY,
+// ---- the host side of the haplotype list (HapOut: sp_internal.h): one pooled buffer carved by the numbers of pairs and targets (a warm context allocates nothing), the
+// launches, the way out.  The list over n pairs whose rows lie in device memory (d_ops: the rows of ALL of them), behind the finished table d_table.  A list that does not fit: SP_ERR_CAPACITY,
 // *n_haps set, nothing written.
 static int32_t hap_run(sp_ctx* ctx, const std::string& who, const sp_seqset* A, const sp_seqset* B, uint32_t n, const uint32_t* d_table, const uint64_t* d_col_offset,
                        const sp_pair* d_pairs, const sp_affine_aln* d_aln, const uint32_t* d_nc, const uint64_t* d_op_off, const uint32_t* d_ops,
@@ -886,82 +869,9 @@ static int32_t hap_run(sp_ctx* ctx, const std::string& who, const sp_seqset* A, 
     return SP_OK;
 }
 
-// the first min(len, 64) bases of a record, from its key
-static std::string ins_key_string(const sp_pileup_ins& r) {
-    std::string out(std::min<uint32_t>(r.len, 64), 'A');
-    for (size_t i = 0; i < out.size(); ++i) out[i] = "ACGT"[((i < 32 ? r.p0 >> (2 * i) : r.p1 >> (2 * (i - 32)))) & 3u];
-    return out;
-}
-
 } // namespace
 
-void spi_support_ins_json(spj::Value* column, const sp_pileup_ins* ins, uint64_t n_ins, uint64_t col, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
-                          const char* const* names, uint32_t n_names) {
-    const sp_pileup_ins* end = ins + n_ins;
-    const sp_pileup_ins* r = std::lower_bound(ins, end, col, [](const sp_pileup_ins& a, uint64_t c) { return a.col < c; });
-    spj::Value list = spj::array();
-    uint64_t more = 0, other = 0;
-    for (; r != end && r->col == col; ++r) {
-        other += r->n_other;
-        if (r->len == 0) continue;
-        if (list.arr.size() >= 8) { ++more; continue; }
-        spj::Value v = spj::object();
-        v.obj.emplace_back("seq", spj::str(ins_key_string(*r))); v.obj.emplace_back("count", spj::unum(r->count));
-        if (r->len > 64) v.obj.emplace_back("len", spj::unum(r->len));
-        uint64_t who = r->first_pair;
-        bool known = names != nullptr;
-        if (known && mappings) { known = who < n_mappings; if (known) who = mappings[who].read; }
-        if (known && who < n_names && names[who]) v.obj.emplace_back("first_read", spj::str(names[who]));
-        list.arr.push_back(std::move(v));
-    }
-    column->obj.emplace_back("insertions", std::move(list));
-    if (more) column->obj.emplace_back("more", spj::unum(more));
-    if (other) column->obj.emplace_back("other", spj::unum(other));
-}
-
-void spi_support_hap_json(spj::Value* consensus, const sp_pileup_col* cols, uint32_t length, const sp_support_hap* haps, uint64_t n_haps, const sp_support_hap_head* head,
-                          uint64_t target, const sp_cyp_read_mapping* mappings, uint64_t n_mappings, const char* const* names, uint32_t n_names) {
-    if (!head || head->n_cols == 0 || head->n_records == 0) return;
-    const sp_support_hap* end = haps + n_haps;
-    const sp_support_hap* r = std::lower_bound(haps, end, target, [](const sp_support_hap& a, uint64_t t) { return a.target < t; });
-    if (r == end || r->target != target) return;
-    spj::Value v = spj::object(), columns = spj::array(), patterns = spj::array();
-    for (uint32_t j = 0; j < length && columns.arr.size() < head->n_cols; ++j) if (contested_col(cols[j])) columns.arr.push_back(spj::unum(j));
-    uint64_t more = 0;
-    for (; r != end && r->target == target; ++r) {
-        if (patterns.arr.size() >= 16) { more += r->count; continue; }
-        char text[2 * SP_SUPPORT_HAP_COLS + 1];
-        if (sp_support_hap_string(r, text, sizeof text, nullptr) != SP_OK) text[0] = '\0';
-        spj::Value p = spj::object();
-        p.obj.emplace_back("count", spj::unum(r->count)); p.obj.emplace_back("calls", spj::str(text));
-        uint64_t who = r->first_pair;
-        bool known = names != nullptr;
-        if (known && mappings) { known = who < n_mappings; if (known) who = mappings[who].read; }
-        if (known && who < n_names && names[who]) p.obj.emplace_back("first_read", spj::str(names[who]));
-        patterns.arr.push_back(std::move(p));
-    }
-    v.obj.emplace_back("columns", std::move(columns)); v.obj.emplace_back("columns_total", spj::unum(head->n_cols_total)); v.obj.emplace_back("patterns", std::move(patterns));
-    if (more) v.obj.emplace_back("more", spj::unum(more));
-    consensus->obj.emplace_back("haplotypes", std::move(v));
-}
-
 extern "C" {
-
-int32_t sp_support_ins_string(const sp_pileup_ins* rec, const sp_seqset* queries, uint32_t query, char* out, uint64_t cap, uint64_t* needed) {
-    if (!rec || (cap && !out)) return SP_ERR_INVALID_ARG;
-    std::string text;
-    if (rec->len <= 64) text = ins_key_string(*rec);
-    else {
-        if (!queries || !queries->ctx || query >= queries->n || (uint64_t)rec->first_qpos + rec->len > (uint64_t)queries->h_len[query]) return SP_ERR_INVALID_ARG;
-        const std::string whole = sp_seqset_decode(queries->ctx, queries, query);
-        if ((int32_t)whole.size() != queries->h_len[query]) return SP_ERR_HIP;
-        text = whole.substr(rec->first_qpos, rec->len);
-    }
-    if (needed) *needed = text.size() + 1;
-    if (cap < text.size() + 1) { if (cap) out[0] = '\0'; return SP_ERR_CAPACITY; }
-    std::memcpy(out, text.c_str(), text.size() + 1);
-    return SP_OK;
-}
 
 int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
                         const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset, sp_pileup_col* out) {
@@ -1048,20 +958,6 @@ int32_t sp_pileup_ins_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B,
     return SP_OK;
 }
 
-int32_t sp_support_hap_string(const sp_support_hap* rec, char* out, uint64_t cap, uint64_t* needed) {
-    if (!rec || (cap && !out) || rec->n_cols > SP_SUPPORT_HAP_COLS) return SP_ERR_INVALID_ARG;
-    std::string text;
-    for (uint32_t k = 0; k < rec->n_cols; ++k) {
-        const uint32_t call = (uint32_t)(rec->w[k >> 4] >> ((k & 15) << 2)) & 15u;
-        text += "?=ACGT-?"[call & 7u];
-        if (call & 8u) text += '+';
-    }
-    if (needed) *needed = text.size() + 1;
-    if (cap < text.size() + 1) { if (cap) out[0] = '\0'; return SP_ERR_CAPACITY; }
-    std::memcpy(out, text.c_str(), text.size() + 1);
-    return SP_OK;
-}
-
 int32_t sp_pileup_hap_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
                             const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset,
                             sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
@@ -1089,12 +985,13 @@ int32_t sp_pileup_hap_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B,
     return hap_run(ctx, "pileup", A, B, (uint32_t)n_pairs, hr.table, hr.cols, hr.pairs, hr.aln, hr.nc, hr.off, hr.ops, hr.order, hr.boff, 1, ho);
 }
 
-// sp_align_pileup_band_batch for the library's own callers as well: `who` begins its error texts, prof[] names its four launches (map, second map, pileup, summary) in the
+} // extern "C"
+
+// sp_align_pileup_hap_batch for the library's own callers as well (sp_support.hip; declared in sp_internal.h): `who` begins its error texts, prof[] names its four launches (map, second map, pileup, summary) in the
 // context's profile, and the first map launch counts the pairs it attempts (max_ed >= 0) when count_attempted is set, every pair of the slice otherwise.
-static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
-                                const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
-                                const std::string& who, const char* const prof[4], bool count_attempted,
-                                sp_pileup_ins* ins = nullptr, uint64_t ins_cap = 0, uint64_t* n_ins = nullptr, uint64_t ins_runs = 0, const HapOut* hap = nullptr) {
+int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
+                         const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
+                         const std::string& who, const char* const prof[4], bool count_attempted, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins, uint64_t ins_runs, const HapOut* hap) {
     if (!A || !B || !opts || !col_offset || (n_pairs && !pairs) || (ins && !n_ins) || (hap && (!hap->n_haps || !hap->heads))) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": null argument");
     if ((band != 64 && band != 256) || (retry_band != 0 && retry_band != 256) || (retry_band != 0 && band != 64))
         return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": band must be 64 or 256, retry_band 0 or (with band 64) 256");
@@ -1275,6 +1172,8 @@ static int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset
     return SP_OK;
 }
 
+extern "C" {
+
 int32_t sp_align_pileup_hap_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
                                   const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
                                   sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins, sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
@@ -1300,256 +1199,6 @@ int32_t sp_align_pileup_band_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seq
 int32_t sp_align_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, const uint64_t* col_offset,
                               sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members) {
     return sp_align_pileup_band_batch(ctx, A, B, pairs, n_pairs, opts, 64, 0, col_offset, aln, cols, summaries, n_members, nullptr);
-}
-
-int32_t sp_support_summarize(const sp_pileup_col* cols, uint32_t length, uint32_t n_members, uint32_t n_aligned, sp_support_summary* out) {
-    if (!out || (length && !cols) || n_aligned > n_members) return SP_ERR_INVALID_ARG;
-    std::memset(out, 0, sizeof *out);
-    out->n_members = n_members; out->n_aligned = n_aligned; out->n_unaligned = n_members - n_aligned; out->length = length;
-    if (length == 0) return SP_OK;
-    std::vector<uint32_t> depth(length);
-    for (uint32_t j = 0; j < length; ++j) { depth[j] = cols[j].depth; if (contested_col(cols[j])) ++out->n_contested; }
-    std::nth_element(depth.begin(), depth.begin() + (length - 1) / 2, depth.end());
-    out->median_depth = depth[(length - 1) / 2];
-    out->min_depth = *std::min_element(depth.begin(), depth.end());
-    return SP_OK;
-}
-
-int32_t sp_support_contested(const sp_pileup_col* cols, uint32_t length, uint32_t* pos, uint32_t cap, uint32_t* n) {
-    if (!n || (length && !cols) || (cap && !pos)) return SP_ERR_INVALID_ARG;
-    uint32_t k = 0;
-    for (uint32_t j = 0; j < length; ++j) if (contested_col(cols[j])) { if (k < cap) pos[k] = j; ++k; }
-    *n = k;
-    return k > cap ? SP_ERR_CAPACITY : SP_OK;
-}
-
-int32_t sp_consensus_support_json(const sp_support_entry* entries, uint32_t n_entries, char* out, uint64_t cap, uint64_t* needed) {
-    return sp_consensus_support_json_ins(entries, n_entries, nullptr, nullptr, 0, nullptr, 0, out, cap, needed);
-}
-
-int32_t sp_consensus_support_json_ins(const sp_support_entry* entries, uint32_t n_entries, const uint64_t* col_base, const sp_pileup_ins* ins, uint64_t n_ins,
-                                      const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed) {
-    return sp_consensus_support_json_hap(entries, n_entries, col_base, ins, n_ins, nullptr, 0, nullptr, 0, nullptr, read_names, n_read_names, out, cap, needed);
-}
-
-int32_t sp_consensus_support_json_hap(const sp_support_entry* entries, uint32_t n_entries, const uint64_t* col_base, const sp_pileup_ins* ins, uint64_t n_ins,
-                                      const sp_support_hap* haps, uint64_t n_haps, const sp_support_hap_head* heads, uint64_t n_heads, const uint64_t* hap_target,
-                                      const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed) {
-    if (n_haps && (!haps || !heads || (n_entries && !hap_target))) return SP_ERR_INVALID_ARG;
-    if ((n_entries && !entries) || (cap && !out) || (n_ins && !ins) || (n_entries && n_ins && !col_base)) return SP_ERR_INVALID_ARG;     // (without entries no col_base is read)
-    std::vector<uint32_t> order;
-    for (uint32_t e = 0; e < n_entries; ++e) {
-        if (!entries[e].gene) return SP_ERR_INVALID_ARG;
-        for (int c = 0; c < 2; ++c) {
-            const char* s = entries[e].consensus[c];
-            if (!s || !*s) continue;
-            if (!entries[e].summary[c] || !entries[e].cols[c] || std::strlen(s) != entries[e].summary[c]->length) return SP_ERR_INVALID_ARG;
-        }
-        order.push_back(e);
-    }
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return std::strcmp(entries[a].gene, entries[b].gene) < 0; });
-    spj::Value root = spj::object();
-    for (size_t o = 0; o < order.size(); ++o) {
-        const sp_support_entry& en = entries[order[o]];
-        if (o && std::strcmp(entries[order[o - 1]].gene, en.gene) == 0) return SP_ERR_INVALID_ARG;      // one entry per gene
-        spj::Value gene = spj::object();
-        for (int c = 0; c < 2; ++c) {
-            const char* s = en.consensus[c];
-            if (!s || !*s) continue;
-            const sp_support_summary& sm = *en.summary[c]; const sp_pileup_col* cols = en.cols[c];
-            spj::Value v = spj::object();
-            v.obj.emplace_back("n_members", spj::unum(sm.n_members)); v.obj.emplace_back("n_aligned", spj::unum(sm.n_aligned)); v.obj.emplace_back("n_unaligned", spj::unum(sm.n_unaligned));
-            v.obj.emplace_back("length", spj::unum(sm.length)); v.obj.emplace_back("min_depth", spj::unum(sm.min_depth)); v.obj.emplace_back("median_depth", spj::unum(sm.median_depth));
-            v.obj.emplace_back("n_contested", spj::unum(sm.n_contested));
-            v.obj.emplace_back("typed_allele", en.typed_allele[c] ? spj::str(en.typed_allele[c]) : spj::Value());
-            spj::Value list = spj::array();
-            for (uint32_t j = 0; j < sm.length; ++j) {
-                if (!contested_col(cols[j])) continue;
-                spj::Value k = spj::object();
-                k.obj.emplace_back("pos", spj::unum(j)); k.obj.emplace_back("depth", spj::unum(cols[j].depth)); k.obj.emplace_back("eq", spj::unum(cols[j].eq));
-                spj::Value x = spj::array();
-                for (int b = 0; b < 4; ++b) x.arr.push_back(spj::unum(cols[j].x[b]));
-                k.obj.emplace_back("x", std::move(x));
-                k.obj.emplace_back("del", spj::unum(cols[j].del)); k.obj.emplace_back("ins", spj::unum(cols[j].ins));
-                k.obj.emplace_back("consensus_base", spj::str(std::string(1, s[j])));
-                if (n_ins && 2ull * cols[j].ins > cols[j].depth) spi_support_ins_json(&k, ins, n_ins, col_base[2 * (size_t)order[o] + c] + j, nullptr, 0, read_names, n_read_names);
-                list.arr.push_back(std::move(k));
-            }
-            v.obj.emplace_back("contested", std::move(list));
-            if (n_haps) {
-                const uint64_t target = hap_target[2 * (size_t)order[o] + c];
-                if (target < n_heads) spi_support_hap_json(&v, cols, sm.length, haps, n_haps, heads + target, target, nullptr, 0, read_names, n_read_names);
-            }
-            gene.obj.emplace_back(c ? "consensus2" : "consensus1", std::move(v));
-        }
-        if (!gene.obj.empty()) root.obj.emplace_back(en.gene, std::move(gene));
-    }
-    std::string text;
-    spj::write_pretty(text, root);
-    if (needed) *needed = text.size() + 1;
-    if (cap < text.size() + 1) { if (cap) out[0] = '\0'; return SP_ERR_CAPACITY; }
-    std::memcpy(out, text.c_str(), text.size() + 1);
-    return SP_OK;
-}
-
-int32_t sp_hla_consensus_support_cohort_ins(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
-                                            const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1, const char* cons, uint32_t cap,
-                                            const uint8_t* unit_on, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries,
-                                            sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
-    return sp_hla_consensus_support_cohort_hap(ctx, db, n_samples, read_sample, n_genes, genes, reads, realign, is_cons1, cons, cap, unit_on, col_offset, cols, cols_cap, summaries,
-                                               ins, ins_cap, n_ins, nullptr, 0, nullptr, nullptr);
-}
-
-int32_t sp_hla_consensus_support_cohort_hap(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
-                                            const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1, const char* cons, uint32_t cap,
-                                            const uint8_t* unit_on, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries,
-                                            sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
-                                            sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    if ((ins && !n_ins) || (haps && (!n_haps || !heads))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: null argument");
-    if (ins) *n_ins = 0;
-    if (haps) *n_haps = 0;
-    if (!db || !reads || !col_offset || !summaries || n_samples == 0 || (n_genes && (!genes || !cons || cap == 0)) || (reads->n && (!realign || !is_cons1)) || (n_samples > 1 && !read_sample))
-        return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: null argument");
-    const uint64_t n_units = (uint64_t)n_samples * n_genes;
-    // ---- the targets: every non-empty consensus of a unit that is on, put on the gene strand
-    std::vector<int32_t> target_of(2 * n_units, -1);
-    std::string tblob; std::vector<uint64_t> toff(1, 0);
-    std::map<uint32_t, uint32_t> gene_slot;                                   // gene -> its place in `genes`
-    for (uint32_t k = 0; k < n_genes; ++k) {
-        const int fwd = spi_hla_gene_fwd(db, genes[k]);
-        if (fwd < 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: gene out of range");
-        if (!gene_slot.emplace(genes[k], k).second) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: a gene is listed twice");
-    }
-    col_offset[0] = 0;
-    for (uint64_t u = 0; u < n_units; ++u) for (int c = 0; c < 2; ++c) {
-        const char* s = cons + (2 * u + c) * (size_t)cap;
-        const size_t len = (unit_on && !unit_on[u]) ? 0 : strnlen(s, cap);
-        col_offset[2 * u + c + 1] = col_offset[2 * u + c] + len;
-        if (len == 0) continue;
-        target_of[2 * u + c] = (int32_t)(toff.size() - 1);
-        if (spi_hla_gene_fwd(db, genes[u % n_genes])) tblob.append(s, len); else tblob += revcomp_str(s, len);
-        toff.push_back(tblob.size());
-    }
-    const uint64_t n_cols = col_offset[2 * n_units];
-    if (n_cols > cols_cap || (n_cols && !cols)) return sp_fail(ctx, SP_ERR_CAPACITY, "consensus support: " + std::to_string(n_cols) + " columns, room for " + std::to_string(cols ? cols_cap : 0));
-    std::memset(summaries, 0, sizeof(sp_support_summary) * 2 * n_units);
-    const uint32_t n_t = (uint32_t)toff.size() - 1;
-    if (n_t == 0) { if (haps) std::memset(heads, 0, sizeof(sp_support_hap_head) * 2 * n_units); return SP_OK; }
-    std::vector<sp_support_hap_head> t_heads(haps ? n_t : 0);
-    HapOut ho; ho.haps = haps; ho.cap = hap_cap; ho.n_haps = n_haps; ho.heads = t_heads.data();
-    // ---- the members: the realigned reads of every unit whose group has a consensus; their segments on the gene strand
-    std::vector<uint32_t> m_target, m_read; std::vector<uint32_t> members_of(n_t, 0);
-    std::string qblob; std::vector<uint64_t> qoff(1, 0);
-    for (uint32_t r = 0; r < reads->n; ++r) {
-        const sp_hla_realign& q = realign[r];
-        if (q.status != 0 || q.gene < 0) continue;
-        const auto slot = gene_slot.find((uint32_t)q.gene);
-        if (slot == gene_slot.end()) continue;
-        const uint32_t sample = read_sample ? read_sample[r] : 0;
-        if (sample >= n_samples) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: read_sample out of range");
-        const int32_t t = target_of[2 * ((uint64_t)sample * n_genes + slot->second) + (is_cons1[r] ? 0 : 1)];
-        if (t < 0) continue;
-        if (q.seg_start < 0 || q.seg_end <= q.seg_start || q.seg_end > reads->h_len[r]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: segment outside its read");
-        const std::string whole = sp_seqset_decode(ctx, reads, r);
-        if ((int32_t)whole.size() != reads->h_len[r]) return sp_fail(ctx, SP_ERR_HIP, "consensus support: fetching the reads failed");
-        if (spi_hla_gene_fwd(db, (uint32_t)q.gene)) qblob.append(whole, (size_t)q.seg_start, (size_t)(q.seg_end - q.seg_start));
-        else qblob += revcomp_str(whole.data() + q.seg_start, (size_t)(q.seg_end - q.seg_start));
-        qoff.push_back(qblob.size()); m_target.push_back((uint32_t)t); m_read.push_back(r); ++members_of[t];
-    }
-    const uint32_t n_m = (uint32_t)m_target.size();
-    sp_seqset T, Q;
-    int32_t rc = sp_seqset_make_small(ctx, "csup_t", tblob.data(), toff.data(), n_t, true, &T);
-    if (rc != SP_OK) return rc;
-    std::vector<uint64_t> t_cols((size_t)n_t + 1, 0);
-    for (uint32_t t = 0; t < n_t; ++t) t_cols[t + 1] = toff[t + 1];
-    std::vector<sp_pileup_col> table(n_cols);
-    std::vector<sp_support_summary> sums(n_t);
-    if (n_m) {
-        rc = sp_seqset_make_small(ctx, "csup_q", qblob.data(), qoff.data(), n_m, false, &Q);
-        if (rc != SP_OK) return rc;
-        std::vector<uint32_t> ident(n_m); std::iota(ident.begin(), ident.end(), 0u);
-        std::vector<int32_t> diag(n_m), votes(n_m);
-        rc = sp_anchor_batch(ctx, &T, &Q, m_target.data(), ident.data(), n_m, diag.data(), votes.data());
-        if (rc != SP_OK) return rc;
-        const sp_affine_opts ao = { 1, 4, 6, 2, 26, 1, 1 };
-        // every member is a pair of ONE device-resident pass: 64 diagonals, then 256 for the attempted pairs that came back with score 0 or without ops -- the list of
-        // those is made and read on the device, no op row reaches the host.  A member without a vote stays in the list switched off, so it counts as unaligned.
-        std::vector<sp_pair> pairs(n_m);
-        for (uint32_t m = 0; m < n_m; ++m) pairs[m] = sp_pair{ m, m_target[m], -diag[m], votes[m] > 0 ? 0 : -1 };
-        // (the pileup launch keeps the profile name it has had in this pass: "pileup")
-        static const char* const prof[4] = { "consensus_support_map", "consensus_support_map_retry", "pileup", "consensus_support_summary" };
-        rc = align_pileup_run(ctx, &Q, &T, pairs.data(), n_m, &ao, 64, 256, t_cols.data(), nullptr, table.data(), sums.data(), members_of.data(), nullptr, "consensus support", prof, true,
-                              ins, ins_cap, n_ins, 0, haps ? &ho : nullptr);
-        if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ((ins && *n_ins > ins_cap) || (haps && *n_haps > hap_cap)))) return rc;
-    } else for (uint32_t t = 0; t < n_t; ++t) sp_support_summarize(table.data() + t_cols[t], (uint32_t)(t_cols[t + 1] - t_cols[t]), 0, 0, &sums[t]);
-    for (uint64_t x = 0; x < 2 * n_units; ++x) {
-        const int32_t t = target_of[x];
-        if (t < 0) continue;
-        const sp_pileup_col* src = table.data() + t_cols[t];
-        const uint32_t len = (uint32_t)(t_cols[t + 1] - t_cols[t]);
-        std::memcpy(cols + col_offset[x], src, sizeof(sp_pileup_col) * (size_t)len);
-        summaries[x] = sums[t];
-    }
-    // (a list that did not fit: everything else is complete, the other list included)
-    if (ins && *n_ins && *n_ins <= ins_cap) {
-        // the list in the caller's terms: the targets are the consensuses that have columns, in col_offset's order, so the records stay in order
-        std::vector<uint64_t> base(n_t, 0);
-        for (uint64_t x = 0; x < 2 * n_units; ++x) if (target_of[x] >= 0) base[target_of[x]] = col_offset[x];
-        for (uint64_t k = 0; k < *n_ins; ++k) {
-            const uint32_t t = (uint32_t)(std::upper_bound(t_cols.begin(), t_cols.end(), ins[k].col) - t_cols.begin()) - 1;
-            ins[k].col = base[t] + (ins[k].col - t_cols[t]);
-            if (ins[k].len) ins[k].first_pair = m_read[ins[k].first_pair];
-        }
-    }
-    if (haps && *n_haps <= hap_cap) {
-        // the haplotype list in the caller's terms: target = the slot of col_offset, first_pair = the member read; a slot without a target has an empty head
-        std::vector<uint64_t> slot_of(n_t, 0);
-        uint64_t at = 0;
-        for (uint64_t x = 0; x < 2 * n_units; ++x) {
-            const int32_t t = target_of[x];
-            if (t >= 0) { slot_of[t] = x; heads[x] = t_heads[t]; at = t_heads[t].first_record + t_heads[t].n_records; }
-            else { heads[x] = sp_support_hap_head{}; heads[x].first_record = at; }
-        }
-        for (uint64_t k = 0; k < *n_haps; ++k) { haps[k].target = slot_of[haps[k].target]; haps[k].first_pair = m_read[haps[k].first_pair]; }
-    }
-    return rc;
-}
-
-int32_t sp_hla_consensus_support_cohort(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_samples, const uint32_t* read_sample, uint32_t n_genes, const uint32_t* genes,
-                                        const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1, const char* cons, uint32_t cap,
-                                        const uint8_t* unit_on, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries) {
-    return sp_hla_consensus_support_cohort_ins(ctx, db, n_samples, read_sample, n_genes, genes, reads, realign, is_cons1, cons, cap, unit_on, col_offset, cols, cols_cap, summaries, nullptr, 0, nullptr);
-}
-
-int32_t sp_hla_consensus_support_ins(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1,
-                                     const char* cons1, const char* cons2, sp_pileup_col* cols1, sp_pileup_col* cols2, sp_support_summary* s1, sp_support_summary* s2,
-                                     sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins) {
-    return sp_hla_consensus_support_hap(ctx, db, gene, reads, realign, is_cons1, cons1, cons2, cols1, cols2, s1, s2, ins, ins_cap, n_ins, nullptr, 0, nullptr, nullptr);
-}
-
-int32_t sp_hla_consensus_support_hap(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1,
-                                     const char* cons1, const char* cons2, sp_pileup_col* cols1, sp_pileup_col* cols2, sp_support_summary* s1, sp_support_summary* s2,
-                                     sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins, sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    if (!cons1 || !cons2) return sp_fail(ctx, SP_ERR_INVALID_ARG, "consensus support: null argument");
-    const size_t l1 = cols1 && s1 ? std::strlen(cons1) : 0, l2 = cols2 && s2 ? std::strlen(cons2) : 0;
-    const uint32_t cap = (uint32_t)std::max(l1, l2) + 1;
-    std::vector<char> both((size_t)2 * cap, '\0');
-    std::memcpy(both.data(), cons1, l1); std::memcpy(both.data() + cap, cons2, l2);
-    uint64_t off[3]; sp_support_summary sm[2];
-    std::vector<sp_pileup_col> table(l1 + l2);
-    const int32_t rc = sp_hla_consensus_support_cohort_hap(ctx, db, 1, nullptr, 1, &gene, reads, realign, is_cons1, both.data(), cap, nullptr, off, table.data(), table.size(), sm, ins, ins_cap, n_ins,
-                                                           haps, hap_cap, n_haps, heads);
-    if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ((ins && n_ins && *n_ins > ins_cap) || (haps && n_haps && *n_haps > hap_cap)))) return rc;
-    if (cols1 && s1) { std::memcpy(cols1, table.data(), sizeof(sp_pileup_col) * l1); *s1 = sm[0]; }
-    if (cols2 && s2) { std::memcpy(cols2, table.data() + off[1], sizeof(sp_pileup_col) * l2); *s2 = sm[1]; }
-    return rc;
-}
-
-int32_t sp_hla_consensus_support(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const sp_seqset* reads, const sp_hla_realign* realign, const uint8_t* is_cons1,
-                                 const char* cons1, const char* cons2, sp_pileup_col* cols1, sp_pileup_col* cols2, sp_support_summary* s1, sp_support_summary* s2) {
-    return sp_hla_consensus_support_ins(ctx, db, gene, reads, realign, is_cons1, cons1, cons2, cols1, cols2, s1, s2, nullptr, 0, nullptr);
 }
 
 } // extern "C"
