@@ -597,6 +597,50 @@ int32_t sp_hla_map_consensus_seq(const sp_hla_map* map, uint32_t item, int32_t l
 /* the mapping of allowed allele k of the item at a level: the alignment, the diagonal it was banded around (b_pos - a_pos), n_cigar ops at *cigar (NULL when 0) */
 int32_t sp_hla_map_mapping(const sp_hla_map* map, uint32_t item, uint32_t k, int32_t level, sp_affine_aln* aln, int32_t* diag, uint32_t* n_cigar, const uint32_t** cigar);
 
+/* ------------------------------------------------------------------ K2 ties: the alleles a call cannot tell from its winner
+ * score_read keeps a strict running best (is_better_match, src/hla/processed_match.rs:103-184): the first allele in database order that nothing later beats is the
+ * call, and every allele that ties with it is dropped without a word.  The _ex forms are the three map calls above plus `flags`; flags = 0 IS the call above (no
+ * further launch, no further pooled memory, every output the same bytes).  SP_HLA_MAP_TIES adds one pass per scan (k2_ties_kernel: one workgroup per consensus, the
+ * winner's records staged in LDS, no global atomic; pooled buffers, nothing allocated on a warm context): for the scan's winner W and every allowed allele X != W,
+ * b_wx = better(W, X) and b_xw = better(X, W) on the level records, alignments and event rows the scan itself read, and whether the level loop of the rule (the overlap
+ * edit counts, the presence rule; :113-168) or only the final mapping_score comparison (:174-183) decided.  The class of X is one byte:
+ *   0 distinct       !b_xw, b_wx, decided in the level loop
+ *   1 score_only     !b_xw, b_wx, decided by the mapping score alone: equal edits on every overlap, W wins the tie-break
+ *   2 equal          !b_xw, !b_wx: indistinguishable; W is the call only because it comes first in database order
+ *   3 beats_winner   b_xw: the relation is not transitive across different overlaps, so an allele beaten early in the scan can beat its final winner
+ *   4 winner         X = W
+ * A scan without a winner (-1) has class 0 for every allele and counts 0.
+ * sp_hla_map_ties: scan 0 = the unit-cost scan (winner best_allele), 1 = the a = 5 scan (winner best_mm2); *cls = n_alleles class bytes in the order of `alleles`
+ * (owned by the handle), counts[c] = the number of alleles of class c.  On a map made without SP_HLA_MAP_TIES: SP_ERR_INVALID_ARG, text in sp_hla_map_last_error. */
+#define SP_HLA_MAP_TIES 1u
+int32_t sp_hla_map_consensus_ex(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene,
+                                const char* cons_dna, uint32_t cons_dna_len, const char* cons_cdna, uint32_t cons_cdna_len,
+                                int32_t require_dna, int32_t disable_cdna, uint32_t flags, sp_hla_map** out);
+int32_t sp_hla_map_consensus_batch_ex(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, const uint32_t* genes,
+                                      const char* const* cons_dna, const uint32_t* cons_dna_len, const char* const* cons_cdna, const uint32_t* cons_cdna_len,
+                                      int32_t require_dna, int32_t disable_cdna, uint32_t flags, sp_hla_map** out);
+int32_t sp_hla_map_type_consensus_ex(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const char* consensus_fwd, uint32_t consensus_len,
+                                     int32_t require_dna, int32_t disable_cdna, uint32_t flags, sp_hla_map** out);
+int32_t sp_hla_map_ties(const sp_hla_map* map, uint32_t item, int32_t scan /* 0 unit-cost, 1 mm2 */, const uint8_t** cls /* n_alleles, order of `alleles` */, uint32_t* counts /* 5 */);
+/* `hla_ties.json` (host only; the layout of the other debug files: two-space indent).  One entry per gene; the file is keyed by gene in name order, then by
+ * "consensus1" / "consensus2" (a consensus with present = 0 is left out, a gene with neither is omitted).  Each holds typed_allele (the call's; NULL: null), winner
+ * (the scan's winner the classes are relative to; NULL: null -- the scan has none), scan ("unit_cost" | "mm2"), n_alleles, counts {distinct, score_only, equal,
+ * beats_winner, winner} and three lists, "equal", "score_only" and "beats_winner", each {"names": [...], "more": n}: the names[k] of the alleles of that class in the
+ * order given (database order), SP_HLA_TIES_MAX_NAMES at the most; "more": the number left out, only when there are any.  out / cap / needed as sp_cyp_alleles_json. */
+#define SP_HLA_TIES_MAX_NAMES 256u
+typedef struct {
+    const char* gene;
+    int32_t present[2];                 /* the consensus has a row */
+    int32_t scan[2];                    /* 0 unit-cost, 1 mm2 */
+    const char* typed_allele[2];        /* the star string of the call for each consensus */
+    const char* winner[2];              /* the star string of the scan's winner */
+    uint32_t n_alleles[2];
+    const uint8_t* cls[2];              /* n_alleles class bytes (sp_hla_map_ties) */
+    const uint32_t* counts[2];          /* 5 (sp_hla_map_ties) */
+    const char* const* names[2];        /* n_alleles full star names ("HLA-A*01:01:01:01") in the order of cls */
+} sp_hla_ties_entry;
+int32_t sp_hla_ties_json(const sp_hla_ties_entry* entries, uint32_t n_entries, char* out, uint64_t cap, uint64_t* needed);
+
 /* ------------------------------------------------------------------ K5: CYP2D6 chain-pair likelihood search
  * Replaces find_best_chain_pair (src/cyp2d6/chaining.rs:223-592) with containment_score (:683-731),
  * get_multinomial_score (:854-903), count_unexpected_alleles (:794-819), unexpected_count (:739-775),
@@ -1598,6 +1642,14 @@ int32_t sp_starphase_set_read_debug(sp_starphase* handle, int32_t enable);
  * sp_hla_map_type_consensus (out of memory; an allele whose alignment has more than 4,096 runs, SP_ERR_CAPACITY) fails the pass -- in a batch the group then goes
  * through it once more sample by sample, as for every other failure of a shared pass, and only the samples whose own map fails are failed. */
 int32_t sp_starphase_set_hla_debug_mappings(sp_starphase* handle, int32_t on);
+/* hla_ties.json, off by default (on 0): with the switch on, a call with a debug folder also writes <folder>/hla_ties.json (sp_hla_ties_json above): keyed by gene in
+ * name order, then "consensus1" / "consensus2" (the second for a dual call only, as in hla_debug.json), each the a = 5 scan's classes (sp_hla_map_ties, scan 1) of
+ * sp_hla_map_type_consensus_ex on that consensus: typed_allele the call's, winner = best_mm2, names the full star names of the gene's allowed alleles.  Genes without a
+ * call are omitted, as is a consensus that does not place; a sample whose BAMs hold no HLA read writes {}.  The map runs once per group of a batch, over every
+ * consensus of the group's samples that have a debug folder -- the same ONE map call that serves sp_starphase_set_hla_debug_mappings when both are on.  Off: no launch,
+ * no pooled memory, every output the same bytes.  On: every other output the same bytes; a sample's file in a batch is the file of its single call.  A failing map
+ * fails the pass as described above. */
+int32_t sp_starphase_set_hla_ties(sp_starphase* handle, int32_t on);
 /* consensus_support.json, off by default (on 0): with the switch on, a call with a debug folder also writes <folder>/consensus_support.json (sp_consensus_support_json
  * above): keyed by gene in name order, then "consensus1" / "consensus2" (the second for a dual call only, as in hla_debug.json), each with the fields of
  * sp_support_summary, typed_allele (the star string of the call's typed allele, "HLA-A*01:01:01:01", or null) and the contested columns; genes without a call (no

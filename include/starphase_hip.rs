@@ -23,6 +23,8 @@ pub const SP_PILEUP_INS_LDS_RUNS: i64 = 1024;
 pub const SP_SUPPORT_HAP_COLS: i64 = 64;
 pub const SP_SUPPORT_HAP_LDS_KEYS: i64 = 1024;
 pub const SP_K1_SEL: i64 = 16;
+pub const SP_HLA_MAP_TIES: i64 = 1;
+pub const SP_HLA_TIES_MAX_NAMES: i64 = 256;
 pub const SP_MAX_CHAIN: i64 = 64;
 pub const SP_CYP_MAXCONS: i64 = 64;
 pub const SP_VAR_MAXDIP: i64 = 4096;
@@ -209,6 +211,18 @@ pub struct sp_hla_best {
     pub best_allele: i32,
     pub n_scored: i32,
     pub mm2_stats: [i32; 6],
+}
+#[repr(C)]
+pub struct sp_hla_ties_entry {
+    pub gene: *const c_char,
+    pub present: [i32; 2],
+    pub scan: [i32; 2],
+    pub typed_allele: [*const c_char; 2],
+    pub winner: [*const c_char; 2],
+    pub n_alleles: [u32; 2],
+    pub cls: [*const u8; 2],
+    pub counts: [*const u32; 2],
+    pub names: [*const *const c_char; 2],
 }
 #[repr(C)]
 pub struct sp_chain_problem {
@@ -830,6 +844,11 @@ extern "C" {
     pub fn sp_hla_map_item(map: *const sp_hla_map, item: u32, gene: *mut u32, n_alleles: *mut u32, alleles: *mut *const u32, best_allele: *mut i32, best_mm2: *mut i32, stats_mm2: *mut *const i32) -> i32;
     pub fn sp_hla_map_consensus_seq(map: *const sp_hla_map, item: u32, level: i32, seq: *mut *const c_char, len: *mut u32) -> i32;
     pub fn sp_hla_map_mapping(map: *const sp_hla_map, item: u32, k: u32, level: i32, aln: *mut sp_affine_aln, diag: *mut i32, n_cigar: *mut u32, cigar: *mut *const u32) -> i32;
+    pub fn sp_hla_map_consensus_ex(ctx: *mut sp_ctx, db: *const sp_hla_db, gene: u32, cons_dna: *const c_char, cons_dna_len: u32, cons_cdna: *const c_char, cons_cdna_len: u32, require_dna: i32, disable_cdna: i32, flags: u32, out: *mut *mut sp_hla_map) -> i32;
+    pub fn sp_hla_map_consensus_batch_ex(ctx: *mut sp_ctx, db: *const sp_hla_db, n: u32, genes: *const u32, cons_dna: *const *const c_char, cons_dna_len: *const u32, cons_cdna: *const *const c_char, cons_cdna_len: *const u32, require_dna: i32, disable_cdna: i32, flags: u32, out: *mut *mut sp_hla_map) -> i32;
+    pub fn sp_hla_map_type_consensus_ex(ctx: *mut sp_ctx, db: *const sp_hla_db, gene: u32, consensus_fwd: *const c_char, consensus_len: u32, require_dna: i32, disable_cdna: i32, flags: u32, out: *mut *mut sp_hla_map) -> i32;
+    pub fn sp_hla_map_ties(map: *const sp_hla_map, item: u32, scan: i32, cls: *mut *const u8, counts: *mut u32) -> i32;
+    pub fn sp_hla_ties_json(entries: *const sp_hla_ties_entry, n_entries: u32, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
     pub fn sp_cyp_best_chain_pair(ctx: *mut sp_ctx, problem: *const sp_chain_problem, result: *mut sp_chain_result) -> i32;
     pub fn sp_cyp_find_regions(ctx: *mut sp_ctx, templates: *const sp_seqset, template_type: *const i32, reads: *const sp_seqset, max_missing_frac: f64, hits: *mut sp_region_hit, hits_cap: u64, n_hits: *mut u64) -> i32;
     pub fn sp_cyp_weight_segments(ctx: *mut sp_ctx, consensus: *const sp_seqset, allowed: *const u8, segments: *const sp_seqset, ed: *mut u64, ov: *mut f64, kept: *mut u8) -> i32;
@@ -981,6 +1000,7 @@ extern "C" {
     pub fn sp_starphase_call(handle: *mut sp_starphase, inputs: *const sp_sample_inputs, out: *mut *mut sp_result) -> i32;
     pub fn sp_starphase_set_read_debug(handle: *mut sp_starphase, enable: i32) -> i32;
     pub fn sp_starphase_set_hla_debug_mappings(handle: *mut sp_starphase, on: i32) -> i32;
+    pub fn sp_starphase_set_hla_ties(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_consensus_support(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_cyp_consensus_support(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_support_insertions(handle: *mut sp_starphase, on: i32) -> i32;

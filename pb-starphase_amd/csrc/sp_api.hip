@@ -94,6 +94,8 @@ void sp_ctx_destroy(sp_ctx* ctx) {
     if (ctx->uploading) (void)upload_finish(ctx->uploading);
     if (ctx->copy_stream) { hipStreamSynchronize(ctx->copy_stream); hipStreamDestroy(ctx->copy_stream); ctx->copy_stream = nullptr; }
     if (ctx->ctl_stream) { hipStreamSynchronize(ctx->ctl_stream); hipStreamDestroy(ctx->ctl_stream); ctx->ctl_stream = nullptr; }
+    if (ctx->pst_stream) { hipStreamSynchronize(ctx->pst_stream); hipStreamDestroy(ctx->pst_stream); ctx->pst_stream = nullptr; }
+    if (ctx->ev_join2) hipEventDestroy(ctx->ev_join2);
     if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
     hipStreamSynchronize(ctx->stream);
@@ -137,6 +139,7 @@ int32_t sp_struct_size(const char* name) {
     SP_SZ(sp_hla_realign)
     SP_SZ(sp_k1_seed_hit)
     SP_SZ(sp_hla_best)
+    SP_SZ(sp_hla_ties_entry)
     SP_SZ(sp_chain_problem)
     SP_SZ(sp_chain_result)
     SP_SZ(sp_region_hit)

@@ -2648,11 +2648,19 @@ static int32_t run_chunk(sp_ctx* ctx, uint32_t n_prob, const sp_cons_problem* pr
             // two kernels for the whole batch: the control workgroups on the context's control stream, the step workgroups on its own stream; the control stream
             // joins in behind the set-up work and hands back when its kernel has ended
             if (!ctx->ctl_stream && hipStreamCreateWithFlags(&ctx->ctl_stream, hipStreamNonBlocking) != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "sp_consensus: control stream");
+            // a process whose streams share hardware queues (fewer than the 16 the library asks for: there the mode is never the library's own choice, only a caller's) cannot
+            // count on `st`, made long before, lying on another queue than ctl_stream: the step kernel would wait behind the resident control kernel until both time out.  There
+            // the step workgroups get a stream that is made and first used right behind ctl_stream.  With 16 queues or more nothing changes: step_st is st
+            const bool own_step_stream = ctx->hw_queues_effective < 16;
+            if (own_step_stream && !ctx->pst_stream && hipStreamCreateWithFlags(&ctx->pst_stream, hipStreamNonBlocking) != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "sp_consensus: step stream");
+            if (own_step_stream && !ctx->ev_join2 && hipEventCreateWithFlags(&ctx->ev_join2, hipEventDisableTiming) != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "sp_consensus: events");
+            const hipStream_t step_st = own_step_stream ? ctx->pst_stream : st;
             if (!ctx->ev_fork && (hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess))
                 return sp_fail(ctx, SP_ERR_HIP, "sp_consensus: events");
             SP_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)cons_control_persist_kernel<MAXP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)proc_lds));
             SP_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, st));
             SP_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->ctl_stream, ctx->ev_fork, 0));
+            if (own_step_stream) SP_HIP_CHECK(ctx, hipStreamWaitEvent(step_st, ctx->ev_fork, 0));          // (the two streams' first uses, one behind the other)
             uint32_t* h_ready = (uint32_t*)sp_host_pool(ctx, "cons_ready", 64);
             if (!h_ready) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "sp_consensus ready word");
             *(volatile uint32_t*)h_ready = 0;
@@ -2660,7 +2668,7 @@ static int32_t run_chunk(sp_ctx* ctx, uint32_t n_prob, const sp_cons_problem* pr
             B.step_cap = (uint32_t)std::min<uint64_t>(limit, 0xFFFFFFFFull);
             // from here on two kernels may be running: whatever goes wrong, both streams are waited for before this function returns (the lease and the pooled buffers
             // go back to other batches when it does)
-            auto drain = [&]() { (void)hipStreamSynchronize(ctx->ctl_stream); (void)hipStreamSynchronize(st); };
+            auto drain = [&]() { (void)hipStreamSynchronize(ctx->ctl_stream); if (own_step_stream) (void)hipStreamSynchronize(step_st); (void)hipStreamSynchronize(st); };
             hipLaunchKernelGGL(cons_control_persist_kernel<MAXP>, dim3(n_prob), dim3(1024), proc_lds, ctx->ctl_stream, B);
             bool all_ready = true;
             {   // a control workgroup takes a whole CU: on a device whose CUs are held by others (another process's batches, which this process's lease cannot see) some
@@ -2674,10 +2682,12 @@ static int32_t run_chunk(sp_ctx* ctx, uint32_t n_prob, const sp_cons_problem* pr
                 }
             }
             if (all_ready) {
-                hipLaunchKernelGGL(cons_step_persist_kernel<MAXP>, dim3((uint32_t)n_blocks), block, 0, st, B);
-                const hipError_t e1 = hipGetLastError();
-                const hipError_t e2 = e1 == hipSuccess ? hipEventRecord(ctx->ev_join, ctx->ctl_stream) : e1;
-                const hipError_t e3 = e2 == hipSuccess ? hipStreamWaitEvent(st, ctx->ev_join, 0) : e2;
+                hipLaunchKernelGGL(cons_step_persist_kernel<MAXP>, dim3((uint32_t)n_blocks), block, 0, step_st, B);
+                hipError_t e3 = hipGetLastError();
+                if (e3 == hipSuccess) e3 = hipEventRecord(ctx->ev_join, ctx->ctl_stream);
+                if (e3 == hipSuccess && own_step_stream) e3 = hipEventRecord(ctx->ev_join2, step_st);
+                if (e3 == hipSuccess) e3 = hipStreamWaitEvent(st, ctx->ev_join, 0);
+                if (e3 == hipSuccess && own_step_stream) e3 = hipStreamWaitEvent(st, ctx->ev_join2, 0);
                 if (e3 != hipSuccess) {
                     const uint32_t one = 1;                    // end the control workgroups (and any step workgroup that started), then wait for both streams
                     if (!ctx->copy_stream) (void)hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking);
@@ -2734,7 +2744,7 @@ static int32_t run_chunk(sp_ctx* ctx, uint32_t n_prob, const sp_cons_problem* pr
         }
     }
     // (with persistent kernels under way an error below still waits for both streams before it returns: the lease and the pooled buffers are other batches' the moment it does)
-#define SP_K8_CHECK(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { if (persist_ran) { (void)hipStreamSynchronize(ctx->ctl_stream); (void)hipStreamSynchronize(st); } \
+#define SP_K8_CHECK(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { if (persist_ran) { (void)hipStreamSynchronize(ctx->ctl_stream); if (ctx->pst_stream) (void)hipStreamSynchronize(ctx->pst_stream); (void)hipStreamSynchronize(st); } \
         return sp_fail(ctx, SP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
     SP_K8_CHECK(hipGetLastError());
     hm.mark("host:k8_loop");

@@ -224,4 +224,55 @@ int32_t sp_hla_debug_save(sp_hla_debug* d, const char* path) {
     return SP_OK;
 }
 
+// `hla_ties.json`: per gene in name order, per consensus, the class counts of sp_hla_map_ties and the names of the alleles the call cannot tell from its winner
+int32_t sp_hla_ties_json(const sp_hla_ties_entry* entries, uint32_t n_entries, char* out, uint64_t cap, uint64_t* needed) {
+    if ((n_entries && !entries) || (cap && !out)) return SP_ERR_INVALID_ARG;
+    std::vector<uint32_t> order;
+    for (uint32_t e = 0; e < n_entries; ++e) {
+        if (!entries[e].gene) return SP_ERR_INVALID_ARG;
+        for (int c = 0; c < 2; ++c) {
+            const sp_hla_ties_entry& en = entries[e];
+            if (!en.present[c]) continue;
+            if ((en.scan[c] != 0 && en.scan[c] != 1) || !en.counts[c] || (en.n_alleles[c] && (!en.cls[c] || !en.names[c]))) return SP_ERR_INVALID_ARG;
+            for (uint32_t k = 0; k < en.n_alleles[c]; ++k) if (en.cls[c][k] > 4 || !en.names[c][k]) return SP_ERR_INVALID_ARG;
+        }
+        order.push_back(e);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return std::strcmp(entries[a].gene, entries[b].gene) < 0; });
+    static const char* const class_name[5] = { "distinct", "score_only", "equal", "beats_winner", "winner" };
+    Value root = spj::object();
+    for (size_t o = 0; o < order.size(); ++o) {
+        const sp_hla_ties_entry& en = entries[order[o]];
+        if (o && std::strcmp(entries[order[o - 1]].gene, en.gene) == 0) return SP_ERR_INVALID_ARG;      // one entry per gene
+        Value gene = spj::object();
+        for (int c = 0; c < 2; ++c) {
+            if (!en.present[c]) continue;
+            Value v = spj::object();
+            v.obj.emplace_back("typed_allele", en.typed_allele[c] ? spj::str(en.typed_allele[c]) : Value());
+            v.obj.emplace_back("winner", en.winner[c] ? spj::str(en.winner[c]) : Value());
+            v.obj.emplace_back("scan", spj::str(en.scan[c] ? "mm2" : "unit_cost"));
+            v.obj.emplace_back("n_alleles", spj::num((int64_t)en.n_alleles[c]));
+            Value counts = spj::object();
+            for (int x = 0; x < 5; ++x) counts.obj.emplace_back(class_name[x], spj::num((int64_t)en.counts[c][x]));
+            v.obj.emplace_back("counts", std::move(counts));
+            for (const uint8_t cl : { (uint8_t)2, (uint8_t)1, (uint8_t)3 }) {                          // equal, score_only, beats_winner: names in database order, 256 at the most
+                Value list = spj::object(), names = spj::array();
+                uint64_t n = 0;
+                for (uint32_t k = 0; k < en.n_alleles[c]; ++k) if (en.cls[c][k] == cl) { if (n < SP_HLA_TIES_MAX_NAMES) names.arr.push_back(spj::str(en.names[c][k])); ++n; }
+                list.obj.emplace_back("names", std::move(names));
+                if (n > SP_HLA_TIES_MAX_NAMES) list.obj.emplace_back("more", spj::num((int64_t)(n - SP_HLA_TIES_MAX_NAMES)));
+                v.obj.emplace_back(class_name[cl], std::move(list));
+            }
+            gene.obj.emplace_back(c ? "consensus2" : "consensus1", std::move(v));
+        }
+        if (!gene.obj.empty()) root.obj.emplace_back(en.gene, std::move(gene));
+    }
+    std::string text;
+    spj::write_pretty(text, root);
+    if (needed) *needed = text.size() + 1;
+    if (cap < text.size() + 1) { if (cap) out[0] = '\0'; return SP_ERR_CAPACITY; }
+    std::memcpy(out, text.c_str(), text.size() + 1);
+    return SP_OK;
+}
+
 } // extern "C"

@@ -13,10 +13,12 @@
 // samples, the host decode of the next group beside the device work of this one.
 #include "sp_internal.h"
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <fstream>
 #include <map>
 #include <memory>
@@ -121,6 +123,7 @@ struct sp_starphase {
     int32_t support_insertions = 0;                  // sp_starphase_set_support_insertions: those two files also list the inserted strings of their contested columns
     int32_t support_haplotypes = 0;                  // sp_starphase_set_support_haplotypes: those two files also list the read haplotypes at their contested columns
     int32_t cyp_consensus_support = 0;               // sp_starphase_set_cyp_consensus_support: a debug folder also receives cyp2d6_consensus_support.json
+    int32_t hla_ties = 0;                            // sp_starphase_set_hla_ties: a debug folder gets hla_ties.json, the alleles each consensus's a = 5 scan cannot tell from its winner
     int32_t hla_debug_mappings = 0;                  // sp_starphase_set_hla_debug_mappings: hla_debug.json carries the mapping of each consensus against every allowed allele
     std::set<std::string> include, exclude; bool has_include = false, has_exclude = false;
     // chromosomes the variant genes were normalised against (sp_variant_gene keeps a pointer)
@@ -649,6 +652,47 @@ int32_t consensus_support_save(sp_starphase* h, const sp_hla_call* calls, const 
     return SP_OK;
 }
 
+// hla_ties.json of one sample (sp_starphase_set_hla_ties): the a = 5 scan's classes of the group's one map that belong to this sample's consensuses.  map_item is
+// indexed by gene * 2 + consensus (-1: the consensus has no item).  A sample without reads has no map and writes an empty object.
+int32_t hla_ties_save(sp_starphase* h, const sp_hla_call* calls, const sp_hla_map* maps, const int32_t* map_item, const std::string& debug_folder, std::string& err) {
+    const size_t G = h->hgenes.size();
+    auto star = [&](uint32_t a) { return h->hgenes[h->a_gene[a]].name + "*" + h->a_star[a]; };
+    std::vector<sp_hla_ties_entry> entries;
+    std::deque<std::string> keep; std::deque<std::vector<const char*>> names; std::deque<std::array<uint32_t, 5>> counts;     // (deques: what the entries point to stays where it is)
+    for (size_t g = 0; maps && map_item && g < G; ++g) {
+        if (calls[g].status == 1) continue;
+        sp_hla_ties_entry en; std::memset(&en, 0, sizeof en);
+        en.gene = h->hgenes[g].name.c_str();
+        for (int k = 0; k < 2; ++k) {
+            if ((k == 1 && !calls[g].is_dual) || map_item[g * 2 + k] < 0) continue;
+            const uint32_t item = (uint32_t)map_item[g * 2 + k];
+            uint32_t n = 0; const uint32_t* alleles = nullptr; int32_t best_mm2 = -1; const uint8_t* cls = nullptr;
+            counts.emplace_back();
+            int32_t rc = sp_hla_map_item(maps, item, nullptr, &n, &alleles, nullptr, &best_mm2, nullptr);
+            if (rc == SP_OK) rc = sp_hla_map_ties(maps, item, 1, &cls, counts.back().data());
+            if (rc != SP_OK) { err = "hla_ties.json: " + opt(sp_hla_map_last_error(maps)); return rc; }
+            names.emplace_back();
+            for (uint32_t x = 0; x < n; ++x) { keep.push_back(star(alleles[x])); names.back().push_back(keep.back().c_str()); }
+            en.present[k] = 1; en.scan[k] = 1; en.n_alleles[k] = n; en.cls[k] = cls; en.counts[k] = counts.back().data(); en.names[k] = names.back().data();
+            const int32_t t = k ? calls[g].typed2 : calls[g].typed1;
+            if (t >= 0) { keep.push_back(star((uint32_t)t)); en.typed_allele[k] = keep.back().c_str(); }
+            if (best_mm2 >= 0) { keep.push_back(star((uint32_t)best_mm2)); en.winner[k] = keep.back().c_str(); }
+        }
+        entries.push_back(en);
+    }
+    uint64_t need = 0;
+    int32_t rc = sp_hla_ties_json(entries.data(), (uint32_t)entries.size(), nullptr, 0, &need);
+    if (rc != SP_OK && rc != SP_ERR_CAPACITY) { err = "hla_ties.json: the classes do not fit their alleles"; return rc; }
+    std::string text((size_t)need, '\0');
+    rc = sp_hla_ties_json(entries.data(), (uint32_t)entries.size(), &text[0], need, &need);
+    if (rc != SP_OK) { err = "hla_ties.json: the classes do not fit their alleles"; return rc; }
+    const std::string path = debug_folder + "/hla_ties.json";
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f || std::fwrite(text.data(), 1, (size_t)need - 1, f) != (size_t)need - 1) { if (f) std::fclose(f); err = "Error while writing " + path; return SP_ERR_INVALID_ARG; }
+    std::fclose(f);
+    return SP_OK;
+}
+
 // the HLA entries of one sample: PgxMappingDetails of every read, the diplotypes, hla_debug.json.  rec / rev: by position in QNAME order; rev[k].allele
 // >= 0 names the reverse-strand mapping a read was dropped for (src/hla/realigner.rs:178-193)
 int32_t hla_package(sp_starphase* h, const std::vector<Read4>& reads, const std::vector<uint32_t>& searched, const std::vector<uint32_t>& order,
@@ -707,7 +751,7 @@ int32_t hla_package(sp_starphase* h, const std::vector<Read4>& reads, const std:
                 const std::string who = k ? "consensus2" : "consensus1";
                 const std::string st = t >= 0 ? h->hgenes[h->a_gene[t]].name + "*" + h->a_star[t] : "";
                 sp_hla_debug_add_read(dbg, h->hgenes[g].name.c_str(), who.c_str(), t >= 0 ? h->a_id[t].c_str() : nullptr, st.c_str());
-                if (maps && map_item && warnings && map_item[g * 2 + k] >= 0) {
+                if (h->hla_debug_mappings && maps && map_item && warnings && map_item[g * 2 + k] >= 0) {
                     const int32_t mr = hla_debug_mappings_add(h, dbg, h->hgenes[g].name, who, maps, (uint32_t)map_item[g * 2 + k], *warnings, err);
                     if (mr != SP_OK) { sp_hla_debug_free(dbg); return mr; }
                 }
@@ -720,6 +764,7 @@ int32_t hla_package(sp_starphase* h, const std::vector<Read4>& reads, const std:
         if (rc != SP_OK) { err = "Error while writing " + path; return rc; }
         if (cigars) { const int32_t rd = read_debug_save(h, reads, pos_of, rec, *cigars, cigars_first, debug_folder, err); if (rd != SP_OK) return rd; }
         if (want_support) { const int32_t rs = consensus_support_save(h, calls, support, debug_folder, err); if (rs != SP_OK) return rs; }
+        if (h->hla_ties) { const int32_t rt = hla_ties_save(h, calls, maps, map_item, debug_folder, err); if (rt != SP_OK) return rt; }
     }
     return SP_OK;
 }
@@ -937,7 +982,7 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
     for (Sample* b : with) want_cigars |= h->read_debug && !b->debug.empty();
     ReadCigars cigars; cigars.stride = 1;
     bool want_maps = false;                                          // likewise one batched map of the group's consensuses
-    for (Sample* b : with) want_maps |= h->hla_debug_mappings && !b->debug.empty();
+    for (Sample* b : with) want_maps |= (h->hla_debug_mappings || h->hla_ties) && !b->debug.empty();
     HlaMaps maps; std::vector<int32_t> map_item(with.size() * G * 2, -1);
     bool want_support = false;                                       // likewise one support pass (anchor, alignment, pileup) over the group's consensuses
     for (Sample* b : with) want_support |= h->consensus_support && !b->debug.empty();
@@ -1012,7 +1057,8 @@ int32_t hla_pass(sp_starphase* h, const std::vector<Sample*>& with, std::string&
             }
             if (!mg.empty()) {
                 std::vector<uint32_t> item_of;
-                rc = spi_hla_map_type_batch(h->ctx, h->hla, (uint32_t)mg.size(), mg.data(), mc.data(), ml.data(), h->s.hla_require_dna, h->s.disable_cdna_scoring, &maps.map, &item_of);
+                rc = spi_hla_map_type_batch(h->ctx, h->hla, (uint32_t)mg.size(), mg.data(), mc.data(), ml.data(), h->s.hla_require_dna, h->s.disable_cdna_scoring, &maps.map, &item_of,
+                                            h->hla_ties ? SP_HLA_MAP_TIES : 0u);
                 if (rc != SP_OK) { err = "sp_hla_map_type_consensus: " + opt(sp_last_error(h->ctx)); return rc; }
                 for (size_t i = 0; i < item_of.size(); ++i) map_item[where[item_of[i]]] = (int32_t)i;
             }
@@ -1126,6 +1172,11 @@ const char* sp_starphase_warnings(const sp_starphase* h) { return h ? h->warning
 int32_t sp_starphase_set_hla_debug_mappings(sp_starphase* h, int32_t on) {
     if (!h) return SP_ERR_INVALID_ARG;
     h->hla_debug_mappings = on ? 1 : 0;
+    return SP_OK;
+}
+int32_t sp_starphase_set_hla_ties(sp_starphase* h, int32_t on) {
+    if (!h) return SP_ERR_INVALID_ARG;
+    h->hla_ties = on ? 1 : 0;
     return SP_OK;
 }
 int32_t sp_starphase_set_consensus_support(sp_starphase* h, int32_t on) {

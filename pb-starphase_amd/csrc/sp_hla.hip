@@ -842,6 +842,73 @@ __global__ __launch_bounds__(1024) void k2_scan_kernel(const K2Level* __restrict
     if (tid == 0) best_out[blockIdx.x] = s_best;
 }
 
+// The ties of a scan (sp_hla_map_ties): every candidate X of a consensus against the scan's winner W with is_better_match (processed_match.rs:103-184) in BOTH directions,
+// on the level records, alignments and event rows the scan itself read.  The level loop of the rule is antisymmetric -- the first level that decides, decides for one
+// side -- so the two edit counts of a level are taken once and serve better(X, W) and better(W, X); only when no level decides are the two mapping_score comparisons made.
+//   0 distinct      W beats X in the level loop            3 beats_winner   X beats W (the relation is not transitive across different overlaps)
+//   1 score_only    W beats X by the mapping score alone    4 winner         X is W
+//   2 equal         neither beats the other
+// One workgroup per consensus, W staged in LDS as the scan stages its running best, the threads stride over the candidates; counts[5] per consensus through the LDS words
+// the event rows occupied (dead once every candidate has its class): no global atomic, LDS no more than the scan's.  No winner (best < 0): classes and counts all 0.
+__global__ __launch_bounds__(1024) void k2_ties_kernel(const K2Level* __restrict__ lv_all, const sp_aln* __restrict__ alns_all,
+                                                       const uint32_t* __restrict__ ev_all, uint32_t ev_stride, uint32_t total,
+                                                       const uint32_t* __restrict__ seg_off, const int32_t* __restrict__ best,
+                                                       uint8_t* __restrict__ cls_out, uint32_t* __restrict__ counts_out) {
+    const uint32_t seg = seg_off[blockIdx.x], n = seg_off[blockIdx.x + 1] - seg;
+    __shared__ K2Level bl[2];
+    __shared__ sp_aln ba[2];
+    __shared__ uint32_t bev[2][K2_MAX_ED + 1];
+    const int tid = threadIdx.x;
+    const int32_t w = best[blockIdx.x];                    // (the same in every thread: the branches on it are uniform across the workgroup)
+    if (w < 0 || (uint32_t)w >= n) {
+        for (uint32_t i = tid; i < n; i += 1024) cls_out[seg + i] = 0;
+        if (tid < 5) counts_out[(uint64_t)blockIdx.x * 5 + tid] = 0;
+        return;
+    }
+    if (tid < 2) { bl[tid] = lv_all[(uint64_t)tid * total + seg + w]; ba[tid] = alns_all[(uint64_t)tid * total + seg + w]; }
+    for (int x = tid; x < 2 * (K2_MAX_ED + 1); x += 1024) {
+        int L = x / (K2_MAX_ED + 1), y = x % (K2_MAX_ED + 1);
+        bev[L][y] = (uint32_t)y < ev_stride ? ev_all[((uint64_t)L * total + seg + w) * ev_stride + y] : 0;
+    }
+    __syncthreads();
+    uint32_t mine[4] = { 0, 0, 0, 0 };                     // this thread's candidates of classes 0 .. 3
+    for (uint32_t i = tid; i < n; i += 1024) {
+        if (i == (uint32_t)w) { cls_out[seg + i] = 4; continue; }
+        K2Level cl[2] = { lv_all[seg + i], lv_all[(uint64_t)total + seg + i] };
+        bool b_xw = false, b_wx = false, decided = false;
+        for (int L = 0; L < 2 && !decided; ++L) {
+            if (cl[L].present && bl[L].present) {
+                int os = cl[L].range_start > bl[L].range_start ? cl[L].range_start : bl[L].range_start;
+                int oe = cl[L].range_end < bl[L].range_end ? cl[L].range_end : bl[L].range_end;
+                int cn = 0, bn = 0;
+                if (os < oe) {
+                    const sp_aln ca = alns_all[(uint64_t)L * total + seg + i];
+                    cn = k2_range_edits(cl[L], ca, ev_all + ((uint64_t)L * total + seg + i) * ev_stride, os, oe);
+                    bn = k2_range_edits(bl[L], ba[L], bev[L], os, oe);
+                }
+                if (cn < bn) { b_xw = true; decided = true; }
+                else if (cn > bn) { b_wx = true; decided = true; }
+            } else if (!cl[L].present && !bl[L].present) {
+            } else { b_xw = cl[L].present != 0; b_wx = !b_xw; decided = true; }
+        }
+        if (!decided) { b_xw = k2_score_less(cl, bl); b_wx = k2_score_less(bl, cl); }
+        const uint32_t c = b_xw ? 3u : !b_wx ? 2u : decided ? 0u : 1u;
+        cls_out[seg + i] = (uint8_t)c;
+        mine[0] += c == 0u; mine[1] += c == 1u; mine[2] += c == 2u; mine[3] += c == 3u;
+    }
+    __syncthreads();                                       // nobody reads the winner's event rows any more: their first words hold the counts
+    uint32_t* cnt = &bev[0][0];
+    if (tid < 4) cnt[tid] = 0;
+    __syncthreads();
+    for (int c = 0; c < 4; ++c) {                          // summed within the wave first: one LDS add per wave and class
+        uint32_t v = mine[c];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+        if ((tid & 63) == 0 && v) atomicAdd(&cnt[c], v);
+    }
+    __syncthreads();
+    if (tid < 5) counts_out[(uint64_t)blockIdx.x * 5 + tid] = tid < 4 ? cnt[tid] : 1u;
+}
+
 __global__ void k2_stats_kernel(const K2Level* __restrict__ lv, uint32_t total, uint32_t seg, uint32_t n, const uint32_t* __restrict__ allele_idx, int32_t* __restrict__ stats) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -900,7 +967,9 @@ struct sp_hla_map {
         std::vector<uint32_t> alleles; std::vector<int32_t> stats_mm2;          // n, n * 6
         std::vector<sp_affine_aln> aln; std::vector<int32_t> diag; std::vector<uint32_t> n_cigar; std::vector<uint64_t> off;   // [level * n + k]
         std::string seq[2];                                                      // the consensus of each level, gene strand (the target of the mappings)
+        std::vector<uint8_t> ties[2]; uint32_t tie_counts[2][5] = {};            // SP_HLA_MAP_TIES: the class of every allowed allele against the winner of the unit-cost scan [0] and of the a = 5 scan [1]
     };
+    uint32_t flags = 0;                                                          // of the call that made the map (SP_HLA_MAP_TIES)
     std::vector<Item> items;
     std::vector<uint32_t> src;                                                   // sp_hla_map_type_consensus and its batch form: the consensus of the call each item is (those that place)
     std::vector<uint32_t> ops;
@@ -1705,6 +1774,11 @@ static int32_t k2_score_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_items
         K2Level* d_mlv = (K2Level*)sp_pool(ctx, "k2m_lv", T2 * sizeof(K2Level));
         int32_t* d_mbest = (int32_t*)sp_pool(ctx, "k2m_best", (size_t)n_items * 4);
         if (!d_mp || !d_maf || !d_mnc || !d_moff || !d_maln || !d_mev || !d_mlv || !d_mbest) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "map_consensus buffers");
+        // SP_HLA_MAP_TIES: one class byte per pair and scan, five counts per item and scan (pooled; a map without the flag asks for neither)
+        const bool ties = (map->flags & SP_HLA_MAP_TIES) != 0;
+        uint8_t* d_tcls = ties ? (uint8_t*)sp_pool(ctx, "k2t_cls", T2) : nullptr;
+        uint32_t* d_tcnt = ties ? (uint32_t*)sp_pool(ctx, "k2t_counts", (size_t)2 * n_items * 5 * 4) : nullptr;
+        if (ties && (!d_tcls || !d_tcnt)) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "map_consensus ties buffers");
         unsigned long long* d_cur = (unsigned long long*)(d_moff + T2);
         for (int L = 0; L < 2; ++L)
             hipLaunchKernelGGL(k2_map_pairs_kernel, dim3(nb), dim3(tb), 0, ctx->stream, d_idx, L == 0 ? d_c0 : d_c1, d_alns + (size_t)L * T, T, d_mp + (size_t)L * T);
@@ -1740,6 +1814,15 @@ static int32_t k2_score_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_items
             }
             { ProfScope ps(ctx, "k2_scan_mm2", T); hipLaunchKernelGGL(k2_scan_kernel, dim3(n_items), dim3(1024), 0, ctx->stream, d_mlv, d_maln, d_mev, stride, T, d_seg, d_mbest); }
             SP_HIP_CHECK(ctx, hipGetLastError());
+            std::vector<uint8_t> htc; std::vector<uint32_t> htn;
+            if (ties) {                                   // both scans have their winners: the unit-cost arrays with best_allele, the a = 5 arrays with best_mm2
+                { ProfScope ps(ctx, "k2_ties", T); hipLaunchKernelGGL(k2_ties_kernel, dim3(n_items), dim3(1024), 0, ctx->stream, d_lv, d_alns, d_ev, stride, T, d_seg, d_best, d_tcls, d_tcnt); }
+                { ProfScope ps(ctx, "k2_ties_mm2", T); hipLaunchKernelGGL(k2_ties_kernel, dim3(n_items), dim3(1024), 0, ctx->stream, d_mlv, d_maln, d_mev, stride, T, d_seg, d_mbest, d_tcls + T, d_tcnt + (size_t)n_items * 5); }
+                SP_HIP_CHECK(ctx, hipGetLastError());
+                htc.resize(T2); htn.resize((size_t)2 * n_items * 5);
+                (void)hipMemcpyAsync(htc.data(), d_tcls, T2, hipMemcpyDeviceToHost, ctx->stream);
+                (void)hipMemcpyAsync(htn.data(), d_tcnt, htn.size() * 4, hipMemcpyDeviceToHost, ctx->stream);
+            }
             std::vector<sp_pair> hp(T2); std::vector<sp_affine_aln> haf(T2); std::vector<uint32_t> hnc(T2); std::vector<uint64_t> hoff(T2);
             b_mm2.assign(n_items, -1); map->ops.resize((size_t)used);
             (void)hipMemcpyAsync(hp.data(), d_mp, T2 * sizeof(sp_pair), hipMemcpyDeviceToHost, ctx->stream);
@@ -1753,6 +1836,10 @@ static int32_t k2_score_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n_items
                 sp_hla_map::Item& it = map->items[k];
                 const size_t n = it.alleles.size();
                 it.best_mm2 = b_mm2[k] >= 0 ? (int32_t)it.alleles[b_mm2[k]] : -1;
+                if (ties) for (int sc = 0; sc < 2; ++sc) {
+                    it.ties[sc].assign(htc.begin() + (size_t)sc * T + seg_off[k], htc.begin() + (size_t)sc * T + seg_off[k] + n);
+                    std::copy(htn.begin() + ((size_t)sc * n_items + k) * 5, htn.begin() + ((size_t)sc * n_items + k) * 5 + 5, it.tie_counts[sc]);
+                }
                 for (int L = 0; L < 2; ++L) for (size_t i = 0; i < n; ++i) {
                     const size_t x = (size_t)L * T + seg_off[k] + i, y = (size_t)L * n + i;
                     if (hnc[x] == 0xFFFFFFFFu) return sp_fail(ctx, SP_ERR_HIP, "map_consensus: the walk of allele " + std::to_string(it.alleles[i]) + " did not reach the cell its path started in");
@@ -1947,10 +2034,14 @@ static int32_t map_done(int32_t rc, sp_hla_map* m, sp_hla_map** out) {          
     if (rc != SP_OK) { delete m; return rc; }
     *out = m; return SP_OK;
 }
-int32_t sp_hla_map_consensus_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, const uint32_t* genes,
-                                   const char* const* cons_dna, const uint32_t* cons_dna_len, const char* const* cons_cdna, const uint32_t* cons_cdna_len,
-                                   int32_t require_dna, int32_t disable_cdna, sp_hla_map** out) {
+static int32_t map_flags_ok(sp_ctx* ctx, uint32_t flags) {
+    return (flags & ~(uint32_t)SP_HLA_MAP_TIES) ? sp_fail(ctx, SP_ERR_INVALID_ARG, "map_consensus: unknown flag") : (int32_t)SP_OK;
+}
+int32_t sp_hla_map_consensus_batch_ex(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, const uint32_t* genes,
+                                      const char* const* cons_dna, const uint32_t* cons_dna_len, const char* const* cons_cdna, const uint32_t* cons_cdna_len,
+                                      int32_t require_dna, int32_t disable_cdna, uint32_t flags, sp_hla_map** out) {
     if (!ctx || !db || !out || (n && (!genes || !cons_dna || !cons_dna_len || !cons_cdna || !cons_cdna_len))) return SP_ERR_INVALID_ARG;
+    if (map_flags_ok(ctx, flags) != SP_OK) return SP_ERR_INVALID_ARG;
     std::vector<K2Item> items(n);
     for (uint32_t k = 0; k < n; ++k) {
         if ((cons_dna_len[k] && !cons_dna[k]) || (cons_cdna_len[k] && !cons_cdna[k])) return SP_ERR_INVALID_ARG;
@@ -1959,24 +2050,40 @@ int32_t sp_hla_map_consensus_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n,
     sp_hla_map* m = nullptr;
     int32_t rc = map_new(out, &m);
     if (rc != SP_OK) return rc;
+    m->flags = flags;
     std::vector<sp_hla_best> best(std::max<uint32_t>(1, n));
     if (n) rc = k2_score_batch(ctx, db, n, items.data(), require_dna, disable_cdna, best.data(), nullptr, m);
     return map_done(rc, m, out);
 }
+int32_t sp_hla_map_consensus_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, const uint32_t* genes,
+                                   const char* const* cons_dna, const uint32_t* cons_dna_len, const char* const* cons_cdna, const uint32_t* cons_cdna_len,
+                                   int32_t require_dna, int32_t disable_cdna, sp_hla_map** out) {
+    return sp_hla_map_consensus_batch_ex(ctx, db, n, genes, cons_dna, cons_dna_len, cons_cdna, cons_cdna_len, require_dna, disable_cdna, 0, out);
+}
+int32_t sp_hla_map_consensus_ex(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const char* cons_dna, uint32_t cons_dna_len, const char* cons_cdna, uint32_t cons_cdna_len,
+                                int32_t require_dna, int32_t disable_cdna, uint32_t flags, sp_hla_map** out) {
+    return sp_hla_map_consensus_batch_ex(ctx, db, 1, &gene, &cons_dna, &cons_dna_len, &cons_cdna, &cons_cdna_len, require_dna, disable_cdna, flags, out);
+}
 int32_t sp_hla_map_consensus(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const char* cons_dna, uint32_t cons_dna_len, const char* cons_cdna, uint32_t cons_cdna_len,
                              int32_t require_dna, int32_t disable_cdna, sp_hla_map** out) {
-    return sp_hla_map_consensus_batch(ctx, db, 1, &gene, &cons_dna, &cons_dna_len, &cons_cdna, &cons_cdna_len, require_dna, disable_cdna, out);
+    return sp_hla_map_consensus_batch_ex(ctx, db, 1, &gene, &cons_dna, &cons_dna_len, &cons_cdna, &cons_cdna_len, require_dna, disable_cdna, 0, out);
 }
-int32_t sp_hla_map_type_consensus(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const char* consensus_fwd, uint32_t consensus_len,
-                                  int32_t require_dna, int32_t disable_cdna, sp_hla_map** out) {
+int32_t sp_hla_map_type_consensus_ex(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const char* consensus_fwd, uint32_t consensus_len,
+                                     int32_t require_dna, int32_t disable_cdna, uint32_t flags, sp_hla_map** out) {
     if (!ctx || !db || !out || gene >= db->n_genes || (consensus_len && !consensus_fwd)) return SP_ERR_INVALID_ARG;
+    if (map_flags_ok(ctx, flags) != SP_OK) return SP_ERR_INVALID_ARG;
     sp_hla_map* m = nullptr;
     int32_t rc = map_new(out, &m);
     if (rc != SP_OK) return rc;
+    m->flags = flags;
     const TypeItem item{ gene, consensus_fwd, consensus_len };
     sp_hla_best best;
     rc = type_batch(ctx, db, 1, &item, require_dna, disable_cdna, &best, nullptr, nullptr, m);
     return map_done(rc, m, out);
+}
+int32_t sp_hla_map_type_consensus(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene, const char* consensus_fwd, uint32_t consensus_len,
+                                  int32_t require_dna, int32_t disable_cdna, sp_hla_map** out) {
+    return sp_hla_map_type_consensus_ex(ctx, db, gene, consensus_fwd, consensus_len, require_dna, disable_cdna, 0, out);
 }
 void sp_hla_map_free(sp_hla_map* m) { delete m; }
 const char* sp_hla_map_last_error(const sp_hla_map* m) { return m ? m->err.c_str() : ""; }
@@ -1991,6 +2098,15 @@ int32_t sp_hla_map_item(const sp_hla_map* m, uint32_t item, uint32_t* gene, uint
     if (best_allele) *best_allele = it.best;
     if (best_mm2) *best_mm2 = it.best_mm2;
     if (stats_mm2) *stats_mm2 = it.stats_mm2.data();
+    return SP_OK;
+}
+int32_t sp_hla_map_ties(const sp_hla_map* m, uint32_t item, int32_t scan, const uint8_t** cls, uint32_t* counts) {
+    if (!m) return SP_ERR_INVALID_ARG;
+    if (!(m->flags & SP_HLA_MAP_TIES)) { const_cast<sp_hla_map*>(m)->err = "the map was made without SP_HLA_MAP_TIES"; return SP_ERR_INVALID_ARG; }
+    if (item >= m->items.size() || (scan != 0 && scan != 1)) { const_cast<sp_hla_map*>(m)->err = "item or scan out of range"; return SP_ERR_INVALID_ARG; }
+    const sp_hla_map::Item& it = m->items[item];
+    if (cls) *cls = it.ties[scan].data();
+    if (counts) for (int c = 0; c < 5; ++c) counts[c] = it.tie_counts[scan][c];
     return SP_OK;
 }
 int32_t sp_hla_map_consensus_seq(const sp_hla_map* m, uint32_t item, int32_t level, const char** seq, uint32_t* len) {
@@ -2016,11 +2132,12 @@ int32_t sp_hla_map_mapping(const sp_hla_map* m, uint32_t item, uint32_t k, int32
 
 // sp_hla_map_type_consensus for n hg38-forward consensuses at once (one placement launch, one batched K2, one map): item_of[x] = the consensus item x of the map is
 int32_t spi_hla_map_type_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, const uint32_t* genes, const char* const* consensus_fwd, const uint32_t* consensus_len,
-                               int32_t require_dna, int32_t disable_cdna, sp_hla_map** out, std::vector<uint32_t>* item_of) {
+                               int32_t require_dna, int32_t disable_cdna, sp_hla_map** out, std::vector<uint32_t>* item_of, uint32_t flags) {
     if (!ctx || !db || !out || !item_of || (n && (!genes || !consensus_fwd || !consensus_len))) return SP_ERR_INVALID_ARG;
     sp_hla_map* m = nullptr;
     int32_t rc = map_new(out, &m);
     if (rc != SP_OK) return rc;
+    m->flags = flags;
     std::vector<TypeItem> items(n);
     for (uint32_t k = 0; k < n; ++k) items[k] = TypeItem{ genes[k], consensus_fwd[k], consensus_len[k] };
     std::vector<sp_hla_best> best(std::max<uint32_t>(1, n));

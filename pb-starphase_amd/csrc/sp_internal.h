@@ -92,7 +92,8 @@ struct sp_ctx {
     bool cons_retry_ladder = false;  // sp_ctx_set_option "cons_retry_ladder": sp_consensus_priority's retry of searches that give up (the drivers pass it on)
     hipStream_t copy_stream = nullptr;   // uploads travel on a stream of their own, beside the kernels of ctx->stream
     hipStream_t ctl_stream = nullptr;    // the control workgroups of a persistent consensus batch run here, beside the step workgroups on ctx->stream (made on first use)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipStream_t pst_stream = nullptr;    // ... and, only in a process with fewer than 16 hardware queues, the step workgroups of such a batch here instead of on ctx->stream (sp_consensus.hip, run_chunk)
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr;
     int k1_best_n = 5;                   // sp_ctx_set_option "k1_best_n": K1 base-aligns the chains minimap2's seeding and chaining select (best_n secondaries per read, the reference's 5);
                                          // 0 = every allele of every anchored gene (the exhaustive argmin of rounds 1-4)
     int profile_rescore_counts = 0;      // sp_ctx_set_option "profile_rescore_counts": sp_rescore_mappings fetches the number of pairs it left to the DP (profile entry <prefix>_dp_pairs); the host waits for it
@@ -238,7 +239,7 @@ std::string spi_hla_allele_fwd(sp_ctx* ctx, const sp_hla_db* db, uint32_t a);
 int spi_hla_gene_fwd(const sp_hla_db* db, uint32_t gene);
 // sp_hla.hip, for sp_diplotype.hip: sp_hla_map_type_consensus for n consensuses in one batched map; item_of[x] = the consensus that item x of the map is (those that place)
 int32_t spi_hla_map_type_batch(sp_ctx* ctx, const sp_hla_db* db, uint32_t n, const uint32_t* genes, const char* const* consensus_fwd, const uint32_t* consensus_len,
-                               int32_t require_dna, int32_t disable_cdna, sp_hla_map** out, std::vector<uint32_t>* item_of);
+                               int32_t require_dna, int32_t disable_cdna, sp_hla_map** out, std::vector<uint32_t>* item_of, uint32_t flags = 0);   // flags: SP_HLA_MAP_TIES
 // sp_pileup.hip, for its kernels and for sp_support.hip: a column whose consensus base, or the absence of an insertion behind it, lacks a strict majority of the members that span it
 __host__ __device__ inline bool pu_contested(uint32_t depth, uint32_t eq, uint32_t ins) { return (depth > 0 && 2ull * eq <= depth) || 2ull * ins > depth; }
 // sp_pileup.hip, for sp_support.hip: sp_align_pileup_hap_batch with what no public entry carries -- `who` begins its error texts, prof[] names its four launches (map, second

@@ -40,6 +40,7 @@ const char* HELP_HEAD =
     "      --output-debug <DIR>         Optional output debug folder (hla_debug.json, cyp2d6_alleles.json)\n"
     "      --debug-reads                Also write read_debug.json there: every realigned HLA read's accepted allele with CIGAR and MD (needs --output-debug)\n"
     "      --debug-hla-mappings         Fill hla_debug.json's mapping_stats: each HLA consensus against every allowed allele, CIGAR and MD (needs --output-debug)\n"
+    "      --debug-hla-ties             Also write hla_ties.json: for each HLA consensus the alleles its call cannot tell from the winner -- equal, score_only, beats_winner (needs --output-debug)\n"
     "      --debug-consensus-support    Also write consensus_support.json: how the member reads back each HLA consensus, column by column (needs --output-debug)\n"
     "      --debug-cyp2d6-support       Also write cyp2d6_consensus_support.json: the same for each CYP2D6 consensus region (needs --output-debug)\n"
     "      --debug-support-insertions   Those two files also list the inserted strings behind the columns their insertions contest (with one of the two switches above)\n"
@@ -95,6 +96,7 @@ const char* BATCH_HELP_TAIL =
     "      --sequential                 Run CYP2D6 after the variant genes and the HLA genes of a group (the calls are the same)\n"
     "      --debug-reads                Also write read_debug.json into every sample's debug folder (needs an output_debug column that names one)\n"
     "      --debug-hla-mappings         Fill the mapping_stats of every sample's hla_debug.json (needs an output_debug column that names a folder)\n"
+    "      --debug-hla-ties             Also write every sample's hla_ties.json: the alleles each HLA call cannot tell from its winner (needs an output_debug column that names a folder)\n"
     "      --debug-consensus-support    Also write every sample's consensus_support.json (needs an output_debug column that names a folder)\n"
     "      --debug-cyp2d6-support       Also write every sample's cyp2d6_consensus_support.json (needs an output_debug column that names a folder)\n"
     "      --debug-support-insertions   Those two files also list the inserted strings behind the columns their insertions contest (with one of the two switches above)\n"
@@ -148,7 +150,7 @@ bool parse_u64(const std::string& s, uint64_t* out) {
 struct Options {
     sp_diplotype_settings s;
     std::string database, reference, include, exclude;
-    int verbose = 0; bool debug_reads = false, debug_hla_mappings = false, debug_consensus_support = false, debug_cyp2d6_support = false, debug_support_insertions = false, debug_support_haplotypes = false;
+    int verbose = 0; bool debug_reads = false, debug_hla_mappings = false, debug_hla_ties = false, debug_consensus_support = false, debug_cyp2d6_support = false, debug_support_insertions = false, debug_support_haplotypes = false;
 };
 
 // the option being parsed: its name (a `--key=value` split) and where its value comes from.  need*: 0, or the exit status of the clap error
@@ -199,6 +201,7 @@ int parse_options(int argc, char** argv, const char* usage, const std::string& h
         else if (a == "--sequential") s.sequential = 1;
         else if (a == "--debug-reads") o.debug_reads = true;
         else if (a == "--debug-hla-mappings") o.debug_hla_mappings = true;
+        else if (a == "--debug-hla-ties") o.debug_hla_ties = true;
         else if (a == "--debug-consensus-support") o.debug_consensus_support = true;
         else if (a == "--debug-cyp2d6-support") o.debug_cyp2d6_support = true;
         else if (a == "--debug-support-insertions") o.debug_support_insertions = true;
@@ -243,6 +246,7 @@ sp_starphase* create_handle(const Options& o, int* code) {
     }
     if (o.debug_reads) sp_starphase_set_read_debug(h, 1);
     if (o.debug_hla_mappings) sp_starphase_set_hla_debug_mappings(h, 1);
+    if (o.debug_hla_ties) sp_starphase_set_hla_ties(h, 1);
     if (o.debug_consensus_support) sp_starphase_set_consensus_support(h, 1);
     if (o.debug_cyp2d6_support) sp_starphase_set_cyp_consensus_support(h, 1);
     if (o.debug_support_insertions) sp_starphase_set_support_insertions(h, 1);
@@ -294,7 +298,7 @@ int batch_main(int argc, char** argv) {
         return NOT_MINE;
     });
     if (parsed != PARSED) return parsed;
-    const int verbose = o.verbose; const bool debug_reads = o.debug_reads, debug_hla_mappings = o.debug_hla_mappings, debug_consensus_support = o.debug_consensus_support, debug_cyp2d6_support = o.debug_cyp2d6_support;
+    const int verbose = o.verbose; const bool debug_reads = o.debug_reads, debug_hla_mappings = o.debug_hla_mappings, debug_hla_ties = o.debug_hla_ties, debug_consensus_support = o.debug_consensus_support, debug_cyp2d6_support = o.debug_cyp2d6_support;
     std::string missing;
     if (database.empty()) missing += "\n  --database <JSON>";
     if (reference.empty()) missing += "\n  --reference <FASTA>";
@@ -332,10 +336,10 @@ int batch_main(int argc, char** argv) {
         }
     }
     if (rows.empty()) { std::fprintf(stderr, "error: manifest \"%s\" lists no samples\n", manifest.c_str()); return EX_USAGE_; }
-    if (debug_reads || debug_hla_mappings || debug_consensus_support || debug_cyp2d6_support) {
+    if (debug_reads || debug_hla_mappings || debug_hla_ties || debug_consensus_support || debug_cyp2d6_support) {
         bool any = false;
         for (const Row& r : rows) any |= !r.debug.empty();
-        if (!any) { std::fprintf(stderr, "error: %s needs a debug folder: no manifest row names one (output_debug)\n", debug_reads ? "--debug-reads" : debug_hla_mappings ? "--debug-hla-mappings" : debug_consensus_support ? "--debug-consensus-support" : "--debug-cyp2d6-support"); return EX_USAGE_; }
+        if (!any) { std::fprintf(stderr, "error: %s needs a debug folder: no manifest row names one (output_debug)\n", debug_reads ? "--debug-reads" : debug_hla_mappings ? "--debug-hla-mappings" : debug_hla_ties ? "--debug-hla-ties" : debug_consensus_support ? "--debug-consensus-support" : "--debug-cyp2d6-support"); return EX_USAGE_; }
     }
     // every row through the checks of `diplotype`: the files (NOINPUT), then check_diplotype_settings (USAGE)
     std::vector<std::vector<const char*>> bam_ptrs(rows.size());
@@ -532,6 +536,7 @@ int main(int argc, char** argv) {
     s.debug_folder = debug.empty() ? nullptr : debug.c_str();
     if (o.debug_reads && debug.empty()) { std::fprintf(stderr, "error: --debug-reads needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
     if (o.debug_hla_mappings && debug.empty()) { std::fprintf(stderr, "error: --debug-hla-mappings needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
+    if (o.debug_hla_ties && debug.empty()) { std::fprintf(stderr, "error: --debug-hla-ties needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
     if (o.debug_consensus_support && debug.empty()) { std::fprintf(stderr, "error: --debug-consensus-support needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
     if (o.debug_cyp2d6_support && debug.empty()) { std::fprintf(stderr, "error: --debug-cyp2d6-support needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
     char err[512];

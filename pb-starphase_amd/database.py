@@ -175,6 +175,7 @@ def _lib():
         "sp_starphase_last_timing": (_i32, [_vp, P(sp_starphase_timing)]),
         "sp_starphase_set_read_debug": (_i32, [_vp, _i32]),
         "sp_starphase_set_hla_debug_mappings": (_i32, [_vp, _i32]),
+        "sp_starphase_set_hla_ties": (_i32, [_vp, _i32]),
         "sp_starphase_set_consensus_support": (_i32, [_vp, _i32]),
         "sp_starphase_set_cyp_consensus_support": (_i32, [_vp, _i32]),
         "sp_starphase_set_support_insertions": (_i32, [_vp, _i32]),
@@ -962,7 +963,7 @@ class Starphase:
     set_cyp_consensus_support() at once (it also writes cyp2d6_consensus_support.json); support_insertions=True: set_support_insertions() at once (those two files
     also list the inserted strings of the columns their insertions contest)."""
 
-    def __init__(self, database, reference=None, ctx=None, consensus_support=False, cyp_consensus_support=False, support_insertions=False, support_haplotypes=False, **settings):
+    def __init__(self, database, reference=None, ctx=None, consensus_support=False, cyp_consensus_support=False, support_insertions=False, support_haplotypes=False, hla_ties=False, **settings):
         self._h = _vp()
         self._s = _settings(**settings)
         rc = _lib().sp_starphase_create(ctx._h if ctx is not None else None, _b(database), _b(reference), C.byref(self._s), C.byref(self._h))
@@ -976,6 +977,8 @@ class Starphase:
             self.set_support_insertions(True)
         if support_haplotypes:
             self.set_support_haplotypes(True)
+        if hla_ties:
+            self.set_hla_ties(True)
 
     def close(self):
         if self._h:
@@ -1025,6 +1028,14 @@ class Starphase:
         rc = _lib().sp_starphase_set_hla_debug_mappings(self._h, 1 if on else 0)
         if rc != SP_OK:
             raise StarphaseError(rc, "sp_starphase_set_hla_debug_mappings")
+        return self
+
+    def set_hla_ties(self, on=True):
+        """sp_starphase_set_hla_ties: a debug folder also receives hla_ties.json (per HLA gene and consensus: the alleles the call cannot tell from the winner of its
+        a = 5 scan -- equal, score_only, beats_winner); off by default"""
+        rc = _lib().sp_starphase_set_hla_ties(self._h, 1 if on else 0)
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_starphase_set_hla_ties")
         return self
 
     def set_read_debug(self, enable=True):

@@ -215,6 +215,46 @@ class HlaMap:
     def __init__(self, gene, alleles, best_allele, best_mm2, stats_mm2, aln, diag, cigar, cons_cdna, cons_dna):
         self.gene, self.alleles, self.best_allele, self.best_mm2, self.stats_mm2 = gene, alleles, best_allele, best_mm2, stats_mm2
         self.aln, self.diag, self.cigar, self.cons_cdna, self.cons_dna = aln, diag, cigar, cons_cdna, cons_dna
+        self.ties = self.tie_counts = None          # ties=True: [scan] -> uint8[n_alleles] classes (TIE_CLASSES) / uint32[5] counts; scan 0 unit-cost, 1 mm2
+
+
+SP_HLA_MAP_TIES = 1
+SP_HLA_TIES_MAX_NAMES = 256
+TIE_CLASSES = ("distinct", "score_only", "equal", "beats_winner", "winner")
+
+
+class sp_hla_ties_entry(C.Structure):
+    _fields_ = [("gene", C.c_char_p), ("present", C.c_int32 * 2), ("scan", C.c_int32 * 2), ("typed_allele", C.c_char_p * 2), ("winner", C.c_char_p * 2),
+                ("n_alleles", C.c_uint32 * 2), ("cls", C.c_void_p * 2), ("counts", C.c_void_p * 2), ("names", C.POINTER(C.c_char_p) * 2)]
+
+
+def hla_ties_json(entries):
+    """sp_hla_ties_json (host only): entries = [(gene, [(typed_allele or None, winner or None, scan, classes uint8[n], counts[5], names[n]) or None] * 2)] -> the text
+    of hla_ties.json"""
+    arr = (sp_hla_ties_entry * max(1, len(entries)))()
+    keep = []
+    for e, (gene, sides) in zip(arr, entries):
+        e.gene = gene.encode()
+        for c, side in enumerate(sides):
+            if side is None:
+                continue
+            typed, winner, scan, cls, counts, names = side
+            cls = np.ascontiguousarray(cls, np.uint8); counts = np.ascontiguousarray(counts, np.uint32)
+            nm = (C.c_char_p * max(1, len(names)))(*[x.encode() for x in names])
+            keep += [cls, counts, nm]
+            e.present[c] = 1; e.scan[c] = int(scan); e.n_alleles[c] = len(cls)
+            e.typed_allele[c] = typed.encode() if typed is not None else None
+            e.winner[c] = winner.encode() if winner is not None else None
+            e.cls[c] = cls.ctypes.data; e.counts[c] = counts.ctypes.data; e.names[c] = nm
+    need = C.c_uint64(0)
+    rc = lib().sp_hla_ties_json(arr, len(entries), None, 0, C.byref(need))
+    if rc not in (SP_OK, SP_ERR_CAPACITY):
+        raise StarphaseError(rc, "sp_hla_ties_json")
+    buf = C.create_string_buffer(need.value)
+    rc = lib().sp_hla_ties_json(arr, len(entries), buf, need.value, C.byref(need))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_hla_ties_json")
+    return buf.value.decode()
 
 
 class sp_hla_best(C.Structure):
@@ -428,6 +468,11 @@ def lib():
         "sp_hla_map_consensus": (i32, [vp, vp, u32, C.c_char_p, u32, C.c_char_p, u32, i32, i32, C.POINTER(vp)]),
         "sp_hla_map_consensus_batch": (i32, [vp, vp, u32, vp, C.POINTER(C.c_char_p), vp, C.POINTER(C.c_char_p), vp, i32, i32, C.POINTER(vp)]),
         "sp_hla_map_type_consensus": (i32, [vp, vp, u32, C.c_char_p, u32, i32, i32, C.POINTER(vp)]),
+        "sp_hla_map_consensus_ex": (i32, [vp, vp, u32, C.c_char_p, u32, C.c_char_p, u32, i32, i32, u32, C.POINTER(vp)]),
+        "sp_hla_map_consensus_batch_ex": (i32, [vp, vp, u32, vp, C.POINTER(C.c_char_p), vp, C.POINTER(C.c_char_p), vp, i32, i32, u32, C.POINTER(vp)]),
+        "sp_hla_map_type_consensus_ex": (i32, [vp, vp, u32, C.c_char_p, u32, i32, i32, u32, C.POINTER(vp)]),
+        "sp_hla_map_ties": (i32, [vp, u32, i32, C.POINTER(vp), C.POINTER(u32 * 5)]),
+        "sp_hla_ties_json": (i32, [C.POINTER(sp_hla_ties_entry), u32, C.c_char_p, u64, C.POINTER(u64)]),
         "sp_hla_map_free": (None, [vp]),
         "sp_hla_map_last_error": (C.c_char_p, [vp]),
         "sp_hla_map_n_items": (u32, [vp]),
@@ -1726,7 +1771,7 @@ class HlaDb:
         self.ctx.check(lib().sp_hla_type_consensus_batch(self.ctx._h, self._h, n, _ptr(g), d, _ptr(dl), int(require_dna), int(disable_cdna), best))
         return [(best[i].best_allele, best[i].n_scored) for i in range(n)]
 
-    def _read_map(self, h):
+    def _read_map(self, h, ties=False):
         """an sp_hla_map handle -> [HlaMap item], and frees it"""
         L = lib()
         vp, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
@@ -1751,32 +1796,53 @@ class HlaDb:
                         diag[lv, k] = d.value
                         cigars[lv][k] = np.ctypeslib.as_array(C.cast(pc, C.POINTER(u32)), (nc.value,)).copy() if nc.value else np.zeros(0, np.uint32)
                 out.append(HlaMap(gene.value, alleles, best.value, best_mm2.value, stats, aln, diag, cigars, seqs[0], seqs[1]))
+                if ties:
+                    out[-1].ties, out[-1].tie_counts = [], []
+                    for scan in (0, 1):
+                        pt, cnt = vp(), (u32 * 5)()
+                        rc = L.sp_hla_map_ties(h, item, scan, C.byref(pt), C.byref(cnt))
+                        if rc != SP_OK:
+                            raise StarphaseError(rc, L.sp_hla_map_last_error(h).decode())
+                        out[-1].ties.append(np.ctypeslib.as_array(C.cast(pt, C.POINTER(C.c_uint8)), (n,)).copy() if n else np.zeros(0, np.uint8))
+                        out[-1].tie_counts.append(np.array(list(cnt), np.uint32))
             return out
         finally:
             L.sp_hla_map_free(h)
 
-    def map_consensus(self, gene, cons_dna, cons_cdna, require_dna=False, disable_cdna=False):
-        """sp_hla_map_consensus: score_read's per-allele mappings of one gene-strand consensus -> HlaMap"""
+    def map_consensus(self, gene, cons_dna, cons_cdna, require_dna=False, disable_cdna=False, ties=False):
+        """sp_hla_map_consensus: score_read's per-allele mappings of one gene-strand consensus -> HlaMap.  ties=True (sp_hla_map_consensus_ex, SP_HLA_MAP_TIES; the same
+        on the two calls below): the map also carries m.ties[scan] / m.tie_counts[scan], the class of every allowed allele against the scan's winner"""
         h = C.c_void_p()
-        self.ctx.check(lib().sp_hla_map_consensus(self.ctx._h, self._h, int(gene), cons_dna.encode(), len(cons_dna), cons_cdna.encode(), len(cons_cdna),
-                                                  int(require_dna), int(disable_cdna), C.byref(h)))
-        return self._read_map(h)[0]
+        if ties:
+            self.ctx.check(lib().sp_hla_map_consensus_ex(self.ctx._h, self._h, int(gene), cons_dna.encode(), len(cons_dna), cons_cdna.encode(), len(cons_cdna),
+                                                         int(require_dna), int(disable_cdna), SP_HLA_MAP_TIES, C.byref(h)))
+        else:
+            self.ctx.check(lib().sp_hla_map_consensus(self.ctx._h, self._h, int(gene), cons_dna.encode(), len(cons_dna), cons_cdna.encode(), len(cons_cdna),
+                                                      int(require_dna), int(disable_cdna), C.byref(h)))
+        return self._read_map(h, ties)[0]
 
-    def map_consensus_batch(self, items, require_dna=False, disable_cdna=False):
+    def map_consensus_batch(self, items, require_dna=False, disable_cdna=False, ties=False):
         """sp_hla_map_consensus_batch: items = [(gene, cons_dna, cons_cdna)] -> [HlaMap], one launch set for all of them"""
         n = len(items)
         g = np.array([it[0] for it in items], np.uint32)
         d = (C.c_char_p * max(1, n))(*[it[1].encode() for it in items]); dl = np.array([len(it[1]) for it in items], np.uint32)
         c = (C.c_char_p * max(1, n))(*[it[2].encode() for it in items]); cl = np.array([len(it[2]) for it in items], np.uint32)
         h = C.c_void_p()
-        self.ctx.check(lib().sp_hla_map_consensus_batch(self.ctx._h, self._h, n, _ptr(g), d, _ptr(dl), c, _ptr(cl), int(require_dna), int(disable_cdna), C.byref(h)))
-        return self._read_map(h)
+        if ties:
+            self.ctx.check(lib().sp_hla_map_consensus_batch_ex(self.ctx._h, self._h, n, _ptr(g), d, _ptr(dl), c, _ptr(cl), int(require_dna), int(disable_cdna), SP_HLA_MAP_TIES, C.byref(h)))
+        else:
+            self.ctx.check(lib().sp_hla_map_consensus_batch(self.ctx._h, self._h, n, _ptr(g), d, _ptr(dl), c, _ptr(cl), int(require_dna), int(disable_cdna), C.byref(h)))
+        return self._read_map(h, ties)
 
-    def map_type_consensus(self, gene, consensus_fwd, require_dna=False, disable_cdna=False):
+    def map_type_consensus(self, gene, consensus_fwd, require_dna=False, disable_cdna=False, ties=False):
         """sp_hla_map_type_consensus: the same from the hg38-forward consensus (placement, splice, gene strand) -> HlaMap, or None when the consensus does not place"""
         h = C.c_void_p()
-        self.ctx.check(lib().sp_hla_map_type_consensus(self.ctx._h, self._h, int(gene), consensus_fwd.encode(), len(consensus_fwd), int(require_dna), int(disable_cdna), C.byref(h)))
-        m = self._read_map(h)
+        if ties:
+            self.ctx.check(lib().sp_hla_map_type_consensus_ex(self.ctx._h, self._h, int(gene), consensus_fwd.encode(), len(consensus_fwd), int(require_dna), int(disable_cdna),
+                                                              SP_HLA_MAP_TIES, C.byref(h)))
+        else:
+            self.ctx.check(lib().sp_hla_map_type_consensus(self.ctx._h, self._h, int(gene), consensus_fwd.encode(), len(consensus_fwd), int(require_dna), int(disable_cdna), C.byref(h)))
+        m = self._read_map(h, ties)
         return m[0] if m else None
 
     def score_consensus(self, gene, cons_dna, cons_cdna, require_dna=False, disable_cdna=False, stats=True):
