@@ -80,8 +80,10 @@ struct PairConsts {
 // device
 // =============================================================================================
 #define K5_MAXH 64
+constexpr unsigned long long K5_NO_PAIR = ~0ull;                              // a block record's pair id when the block has no valid pair
 
-__device__ __forceinline__ void k5_pair_from_id(uint64_t pid, int P, int& i, int& j) {
+// pair id -> (i, j); the sqrt is only a first guess, the two loops make it exact for every pid < P(P+1)/2
+__host__ __device__ __forceinline__ void k5_pair_from_id(uint64_t pid, int P, int& i, int& j) {
     // rows i = 0..P-1 hold P - i pairs (j = i..P-1); offset(i) = i*P - i*(i-1)/2
     double Pd = (double)P;
     double disc = (2.0 * Pd + 1.0) * (2.0 * Pd + 1.0) - 8.0 * (double)pid;
@@ -133,13 +135,88 @@ __device__ __forceinline__ double k5_multinomial(const PairConsts& c, Cnt cnt, H
     return fabs(coeff + acc);
 }
 
+// ---- the scoring rule of a pair, stated once for both pair kernels below ----
+
+// The head of a pair: cnt[h] = copies of region h in chains i and j, the three penalties that need no read -- cost[0] lasso (count_unexpected_alleles,
+// chaining.rs:794-819), cost[1] unexpected chain, cost[2] inferred edge -- and the exact pruning: a pair whose cheap partial cost already exceeds the best
+// complete score cannot win (chaining.rs:457-464).
+struct K5Head { double cost[3]; bool go; };
+__device__ __forceinline__ K5Head k5_pair_head(const PairConsts& c, int i, int j, const uint8_t* __restrict__ chains, const int32_t* __restrict__ chain_len,
+                                               const uint32_t* __restrict__ chain_unexp, const uint32_t* __restrict__ chain_inf,
+                                               const uint8_t* __restrict__ hap_lasso, unsigned char* cnt, const unsigned long long* global_best) {
+    const uint8_t* ci = chains + (size_t)i * c.maxlen; const uint8_t* cj = chains + (size_t)j * c.maxlen;
+    const int ni = chain_len[i], nj = chain_len[j];
+    for (int h = 0; h < c.H; ++h) cnt[h] = 0;
+    for (int x = 0; x < ni; ++x) cnt[ci[x]]++;
+    for (int x = 0; x < nj; ++x) cnt[cj[x]]++;
+    int unexpected_alleles = 0;
+    for (int h = 0; h < c.H; ++h) if (hap_lasso[h] && cnt[h] > 0) unexpected_alleles += cnt[h] - 1;
+    K5Head hd;
+    hd.cost[0] = c.lasso * (double)unexpected_alleles;
+    hd.cost[1] = (double)(c.ignore_limits ? 0u : chain_unexp[i] + chain_unexp[j]) * c.unexpected;
+    hd.cost[2] = (double)(c.infer ? chain_inf[i] + chain_inf[j] : 0u) * c.inferred;
+    const double partial_cost = hd.cost[0] + hd.cost[1] + hd.cost[2];
+    const double gb = __longlong_as_double((long long)__hip_atomic_load(global_best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    hd.go = !(partial_cost > gb);
+    return hd;
+}
+
+// containment_score (chaining.rs:683-731) of one read from the per-chain tables: the best window total over both chains, ties kept in visiting order (chain i's
+// windows, then chain j's).  sc = the read's edit distance above its optimum, split_frac = the share of each best window; mi / mj keep only the starts that reach it.
+struct K5ReadTerms { int row0, wl; unsigned long long mi, mj, sc; double split_frac; };
+__device__ __forceinline__ K5ReadTerms k5_read_terms(int row0, int row1, unsigned long long bi, unsigned long long bj, unsigned long long mi, unsigned long long mj,
+                                                     unsigned long long worst, unsigned long long opt) {
+    unsigned long long best_score = 2ull * worst;
+    int n_best = 0;
+    if (bi < best_score) { best_score = bi; n_best = __popcll(mi); } else if (bi == best_score) n_best += __popcll(mi);
+    if (bj < best_score) { best_score = bj; n_best = __popcll(mj); } else if (bj == best_score) n_best += __popcll(mj);
+    K5ReadTerms t;
+    t.row0 = row0; t.wl = row1 - row0;
+    t.sc = best_score - opt;
+    t.split_frac = 1.0 / (double)n_best;
+    t.mi = bi == best_score ? mi : 0ull; t.mj = bj == best_score ? mj : 0ull;
+    return t;
+}
+
+// the addends of a read in the order the f64 sums need them: f(region, x) for chain i's best starts in ascending order, then chain j's; x ascends within a start
+template <typename F>
+__device__ __forceinline__ void k5_for_each_addend(const uint8_t* __restrict__ ci, const uint8_t* __restrict__ cj, unsigned long long mi, unsigned long long mj, int wl, F f) {
+    for (int which = 0; which < 2; ++which) {
+        const uint8_t* o = which ? cj : ci;
+        unsigned long long m = which ? mj : mi;
+        while (m) {
+            const int s = __builtin_ctzll(m); m &= m - 1;
+            for (int x = 0; x < wl; ++x) f((int)o[s + x], x);
+        }
+    }
+}
+
+__device__ __forceinline__ unsigned long long k5_saturating_add(unsigned long long a, unsigned long long b) {
+    const unsigned long long sum = a + b;
+    return sum < a ? ~0ull : sum;
+}
+
+// primary score in the reference's operand order (chaining.rs:172-174)
+__device__ __forceinline__ double k5_primary(double ln_ed_penalty, double mn, const double* cost) { return ln_ed_penalty + mn + cost[0] + cost[1] + cost[2]; }
+
+// the new bound for the pruning (scores are >= 0: bit order = numeric order) and the record of a block's best pair.  The atomic comes first: placed after the
+// stores it cost k5_pair_kernel a stack slot that nothing uses (profiles/k5/refactor_resources.txt)
+__device__ __forceinline__ void k5_store_result(size_t slot, unsigned long long pid, double ln_ed_penalty, double mn, const double* cost, unsigned long long ed,
+                                                double* __restrict__ blk_score, unsigned long long* __restrict__ blk_pid, double* __restrict__ blk_comp,
+                                                unsigned long long* __restrict__ blk_ed, unsigned long long* __restrict__ global_best) {
+    const double primary = k5_primary(ln_ed_penalty, mn, cost);
+    atomicMin(global_best, (unsigned long long)__double_as_longlong(primary));
+    blk_score[slot] = primary; blk_pid[slot] = pid; blk_ed[slot] = ed;
+    double* cp = blk_comp + slot * 5; cp[0] = ln_ed_penalty; cp[1] = mn; cp[2] = cost[0]; cp[3] = cost[1]; cp[4] = cost[2];
+}
+
 // one thread = one unordered pair (i <= j)
 __global__ __launch_bounds__(256) void k5_pair_kernel(PairConsts c,
                                                       const uint8_t* __restrict__ chains, const int32_t* __restrict__ chain_len,   // [P][maxlen]
                                                       const uint32_t* __restrict__ chain_unexp, const uint32_t* __restrict__ chain_inf,
                                                       const uint8_t* __restrict__ chain_has_del,
                                                       const uint8_t* __restrict__ hap_lasso, const uint8_t* __restrict__ hap_norm,
-                                                      const int32_t* __restrict__ read_w_off, const uint32_t* __restrict__ w_ed, const double* __restrict__ w_ov,
+                                                      const int32_t* __restrict__ read_w_off, const double* __restrict__ w_ov,
                                                       const unsigned long long* __restrict__ tab_best, const unsigned long long* __restrict__ tab_mask,
                                                       const uint64_t* __restrict__ read_optimum, const uint64_t* __restrict__ read_worst,
                                                       const double* __restrict__ ln_fact, int ln_fact_n,
@@ -152,27 +229,15 @@ __global__ __launch_bounds__(256) void k5_pair_kernel(PairConsts c,
     const int H = c.H;
     bool have = false;
     int scored = 0;
-    double primary = 0.0, comp_lned = 0.0, comp_mn = 0.0, comp_exp = 0.0, comp_unexp = 0.0, comp_inf = 0.0;
-    unsigned long long ed_out = 0;
+    K5Head head = {};
+    double primary = 0.0, ln_ed_penalty = 0.0, mn = 0.0;
+    unsigned long long read_combined_ed = 0;
     if (pid < c.n_pairs) {
         int i, j; k5_pair_from_id(pid, c.P, i, j);
         const uint8_t* ci = chains + (size_t)i * c.maxlen; const uint8_t* cj = chains + (size_t)j * c.maxlen;
-        const int ni = chain_len[i], nj = chain_len[j];
         unsigned char cnt[K5_MAXH];
-        for (int h = 0; h < H; ++h) cnt[h] = 0;
-        for (int x = 0; x < ni; ++x) cnt[ci[x]]++;
-        for (int x = 0; x < nj; ++x) cnt[cj[x]]++;
-        int unexpected_alleles = 0;                                           // count_unexpected_alleles (chaining.rs:794-819)
-        for (int h = 0; h < H; ++h) if (hap_lasso[h] && cnt[h] > 0) unexpected_alleles += cnt[h] - 1;
-        const double allele_expected_penalty = c.lasso * (double)unexpected_alleles;
-        const unsigned mismatch = c.ignore_limits ? 0u : chain_unexp[i] + chain_unexp[j];
-        const double unexpected_chain_penalty = (double)mismatch * c.unexpected;
-        const unsigned n_inf = c.infer ? chain_inf[i] + chain_inf[j] : 0u;
-        const double inferred_chain_penalty = (double)n_inf * c.inferred;
-        const double partial_cost = allele_expected_penalty + unexpected_chain_penalty + inferred_chain_penalty;
-        // exact pruning: a pair whose cheap partial cost already exceeds the best complete score cannot win (chaining.rs:457-464)
-        const double gb = __longlong_as_double((long long)__hip_atomic_load(global_best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        if (!(partial_cost > gb)) {
+        head = k5_pair_head(c, i, j, chains, chain_len, chain_unexp, chain_inf, hap_lasso, cnt, global_best);
+        if (head.go) {
             scored = 1;
             // per-haplotype coverage of this thread's pair, in LDS ([h][thread]: conflict-free): indexed by data, the array lived in scratch memory and
             // every add was a dependent round trip there -- 1.6 us per read for the 210 pairs of a sample
@@ -180,7 +245,6 @@ __global__ __launch_bounds__(256) void k5_pair_kernel(PairConsts c,
             double* const hw = k5_hw + threadIdx.x;
 #define HW(h) hw[(size_t)(h) * 256]
             for (int h = 0; h < H; ++h) HW(h) = 0.0;
-            unsigned long long read_combined_ed = 0;
             // (the reads are taken in order -- the f64 sums below depend on it --, but what a read needs from memory does not depend on the sums: the
             //  next read's seven words are on their way while this one is added up; a read used to cost four dependent round trips, 1.7 us)
             struct ReadWords { int row0, row1; unsigned long long bi, bj, mi, mj, worst, opt; };
@@ -196,39 +260,15 @@ __global__ __launch_bounds__(256) void k5_pair_kernel(PairConsts c,
             for (int r = 0; r < c.R; ++r) {
                 const ReadWords cur = nxt;
                 if (r + 1 < c.R) nxt = fetch(r + 1);
-                const int row0 = cur.row0, wl = cur.row1 - row0;
-                const double* ov = w_ov + (size_t)row0 * H;
-                // containment_score (chaining.rs:683-731): best window total over both chains, ties kept in visiting order (chain i's windows,
-                // then chain j's) -- from the per-chain tables
-                unsigned long long best_score = 2ull * cur.worst;
-                int n_best = 0;
-                const unsigned long long bi = cur.bi, bj = cur.bj;
-                const unsigned long long mi = cur.mi, mj = cur.mj;
-                if (bi < best_score) { best_score = bi; n_best = __popcll(mi); } else if (bi == best_score) n_best += __popcll(mi);
-                if (bj < best_score) { best_score = bj; n_best = __popcll(mj); } else if (bj == best_score) n_best += __popcll(mj);
-                const unsigned long long sc = best_score - cur.opt;
-                const unsigned long long sum = read_combined_ed + sc;
-                read_combined_ed = sum < read_combined_ed ? 0xFFFFFFFFFFFFFFFFull : sum;        // saturating_add
-                const double split_frac = 1.0 / (double)n_best;
-                for (int which = 0; which < 2; ++which) {
-                    const uint8_t* o = which ? cj : ci;
-                    unsigned long long m = (which ? bj : bi) == best_score ? (which ? mj : mi) : 0ull;
-                    while (m) {
-                        const int s = __builtin_ctzll(m); m &= m - 1;
-                        for (int x = 0; x < wl; ++x) { const int con = o[s + x]; HW(con) += split_frac * ov[(size_t)x * H + con]; }
-                    }
-                }
+                const K5ReadTerms t = k5_read_terms(cur.row0, cur.row1, cur.bi, cur.bj, cur.mi, cur.mj, cur.worst, cur.opt);
+                read_combined_ed = k5_saturating_add(read_combined_ed, t.sc);
+                const double* ov = w_ov + (size_t)t.row0 * H;
+                k5_for_each_addend(ci, cj, t.mi, t.mj, t.wl, [&](int con, int x) { HW(con) += t.split_frac * ov[(size_t)x * H + con]; });
             }
-            const double ln_ed_penalty = (double)read_combined_ed * c.ln_ed;
-            bool valid = true;
-            const double mn = k5_multinomial(c, [&](int h) { return (int)cnt[h]; }, [&](int h) { return HW(h); }, hap_norm, ln_fact, ln_fact_n, ln_p, ln_p_stride,
-                                             chain_has_del[i] && chain_has_del[j], valid);
-            if (valid) {
-                primary = ln_ed_penalty + mn + allele_expected_penalty + unexpected_chain_penalty + inferred_chain_penalty;    // chaining.rs:172-174
-                have = true; comp_lned = ln_ed_penalty; comp_mn = mn; comp_exp = allele_expected_penalty; comp_unexp = unexpected_chain_penalty;
-                comp_inf = inferred_chain_penalty; ed_out = read_combined_ed;
-                atomicMin(global_best, (unsigned long long)__double_as_longlong(primary));   // scores are >= 0: bit order = numeric order
-            }
+            ln_ed_penalty = (double)read_combined_ed * c.ln_ed;
+            mn = k5_multinomial(c, [&](int h) { return (int)cnt[h]; }, [&](int h) { return HW(h); }, hap_norm, ln_fact, ln_fact_n, ln_p, ln_p_stride,
+                                chain_has_del[i] && chain_has_del[j], have);
+            if (have) primary = k5_primary(ln_ed_penalty, mn, head.cost);
         }
     }
     {   // pairs whose read-level terms were evaluated: one atomic per wavefront, not per pair
@@ -237,22 +277,18 @@ __global__ __launch_bounds__(256) void k5_pair_kernel(PairConsts c,
     }
     // block-level lexicographic min (score, pid)
     __shared__ double s_score[256]; __shared__ unsigned long long s_pid[256];
-    s_score[threadIdx.x] = have ? primary : 1.0e308 * 10.0; s_pid[threadIdx.x] = have ? pid : 0xFFFFFFFFFFFFFFFFull;
+    s_score[threadIdx.x] = have ? primary : 1.0e308 * 10.0; s_pid[threadIdx.x] = have ? pid : K5_NO_PAIR;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if ((int)threadIdx.x < o) {
             const double so = s_score[threadIdx.x + o]; const unsigned long long po = s_pid[threadIdx.x + o];
-            if (po != 0xFFFFFFFFFFFFFFFFull && (s_pid[threadIdx.x] == 0xFFFFFFFFFFFFFFFFull || so < s_score[threadIdx.x] ||
-                                                (so == s_score[threadIdx.x] && po < s_pid[threadIdx.x]))) { s_score[threadIdx.x] = so; s_pid[threadIdx.x] = po; }
+            if (po != K5_NO_PAIR && (s_pid[threadIdx.x] == K5_NO_PAIR || so < s_score[threadIdx.x] ||
+                                     (so == s_score[threadIdx.x] && po < s_pid[threadIdx.x]))) { s_score[threadIdx.x] = so; s_pid[threadIdx.x] = po; }
         }
         __syncthreads();
     }
-    if (have && s_pid[0] == pid) {
-        blk_score[blockIdx.x] = primary; blk_pid[blockIdx.x] = pid; blk_ed[blockIdx.x] = ed_out;
-        double* cp = blk_comp + (size_t)blockIdx.x * 5; cp[0] = comp_lned; cp[1] = comp_mn; cp[2] = comp_exp; cp[3] = comp_unexp; cp[4] = comp_inf;
-    } else if (threadIdx.x == 0 && s_pid[0] == 0xFFFFFFFFFFFFFFFFull) {
-        blk_pid[blockIdx.x] = 0xFFFFFFFFFFFFFFFFull;
-    }
+    if (have && s_pid[0] == pid) k5_store_result(blockIdx.x, pid, ln_ed_penalty, mn, head.cost, read_combined_ed, blk_score, blk_pid, blk_comp, blk_ed, global_best);
+    else if (threadIdx.x == 0 && s_pid[0] == K5_NO_PAIR) blk_pid[blockIdx.x] = K5_NO_PAIR;
 }
 
 // The same score with one WORKGROUP per pair, for the few pairs of an ordinary sample (tens to hundreds: a thread per pair walks the reads one after another, 1.1 us
@@ -281,43 +317,20 @@ __global__ __launch_bounds__(K5_TILE) void k5_pair_block_kernel(PairConsts c,
     __shared__ unsigned long long s_ed[K5_TILE];
     __shared__ double s_hw[K5_MAXH];
     __shared__ unsigned char s_cnt[K5_MAXH];
-    __shared__ double s_cost[3];
-    __shared__ int s_go;
+    __shared__ K5Head s_head;
     const uint64_t pid = blockIdx.x;
     const int H = c.H, tid = (int)threadIdx.x;
     int i, j; k5_pair_from_id(pid, c.P, i, j);
     const uint8_t* ci = chains + (size_t)i * c.maxlen; const uint8_t* cj = chains + (size_t)j * c.maxlen;
     if (tid == 0) {
-        const int ni = chain_len[i], nj = chain_len[j];
-        for (int h = 0; h < H; ++h) s_cnt[h] = 0;
-        for (int x = 0; x < ni; ++x) s_cnt[ci[x]]++;
-        for (int x = 0; x < nj; ++x) s_cnt[cj[x]]++;
-        int unexpected_alleles = 0;                                           // count_unexpected_alleles (chaining.rs:794-819)
-        for (int h = 0; h < H; ++h) if (hap_lasso[h] && s_cnt[h] > 0) unexpected_alleles += s_cnt[h] - 1;
-        s_cost[0] = c.lasso * (double)unexpected_alleles;
-        s_cost[1] = (double)(c.ignore_limits ? 0u : chain_unexp[i] + chain_unexp[j]) * c.unexpected;
-        s_cost[2] = (double)(c.infer ? chain_inf[i] + chain_inf[j] : 0u) * c.inferred;
-        const double partial_cost = s_cost[0] + s_cost[1] + s_cost[2];
-        const double gb = __longlong_as_double((long long)__hip_atomic_load(global_best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        s_go = !(partial_cost > gb);                                          // exact pruning (chaining.rs:457-464)
-        if (!s_go) blk_pid[pid] = 0xFFFFFFFFFFFFFFFFull;
+        s_head = k5_pair_head(c, i, j, chains, chain_len, chain_unexp, chain_inf, hap_lasso, s_cnt, global_best);
+        if (!s_head.go) blk_pid[pid] = K5_NO_PAIR;
     }
     __syncthreads();
-    if (!s_go) return;
-    struct ReadTerms { int row0, wl; unsigned long long mi, mj, sc; double split_frac; };
+    if (!s_head.go) return;
     auto terms = [&](int r) {
-        ReadTerms t;
-        t.row0 = read_w_off[r]; t.wl = read_w_off[r + 1] - t.row0;
-        const unsigned long long bi = tab_best[(size_t)r * c.P + i], bj = tab_best[(size_t)r * c.P + j];
-        const unsigned long long mi = tab_mask[(size_t)r * c.P + i], mj = tab_mask[(size_t)r * c.P + j];
-        unsigned long long best_score = 2ull * read_worst[r];                 // containment_score (chaining.rs:683-731), as in k5_pair_kernel
-        int n_best = 0;
-        if (bi < best_score) { best_score = bi; n_best = __popcll(mi); } else if (bi == best_score) n_best += __popcll(mi);
-        if (bj < best_score) { best_score = bj; n_best = __popcll(mj); } else if (bj == best_score) n_best += __popcll(mj);
-        t.sc = best_score - read_optimum[r];
-        t.split_frac = 1.0 / (double)n_best;
-        t.mi = bi == best_score ? mi : 0ull; t.mj = bj == best_score ? mj : 0ull;
-        return t;
+        return k5_read_terms(read_w_off[r], read_w_off[r + 1], tab_best[(size_t)r * c.P + i], tab_best[(size_t)r * c.P + j],
+                             tab_mask[(size_t)r * c.P + i], tab_mask[(size_t)r * c.P + j], read_worst[r], read_optimum[r]);
     };
     double acc = 0.0;                                                         // thread h: the coverage of region h
     unsigned long long ed_part = 0;
@@ -325,26 +338,17 @@ __global__ __launch_bounds__(K5_TILE) void k5_pair_block_kernel(PairConsts c,
         const int r = base + tid;
         int nadd = 0;
         if (r < c.R) {
-            const ReadTerms t = terms(r);
-            const unsigned long long sum = ed_part + t.sc;
-            ed_part = sum < ed_part ? 0xFFFFFFFFFFFFFFFFull : sum;            // saturating_add (the order does not matter: every term is >= 0)
+            const K5ReadTerms t = terms(r);
+            ed_part = k5_saturating_add(ed_part, t.sc);                       // (the order does not matter: every term is >= 0)
             const int total = (__popcll(t.mi) + __popcll(t.mj)) * t.wl;
             unsigned long long cons = ~0ull;
             if (total > K5_ADDS) nadd = -1;
             else {
                 const double* ov = w_ov + (size_t)t.row0 * H;
-                for (int which = 0; which < 2; ++which) {
-                    const uint8_t* o = which ? cj : ci;
-                    unsigned long long m = which ? t.mj : t.mi;
-                    while (m) {
-                        const int s = __builtin_ctzll(m); m &= m - 1;
-                        for (int x = 0; x < t.wl; ++x) {
-                            const int con = o[s + x];
-                            cons = (cons & ~(0xFFull << (8 * nadd))) | ((unsigned long long)con << (8 * nadd));
-                            s_val[tid * K5_ADDS + nadd] = t.split_frac * ov[(size_t)x * H + con]; ++nadd;
-                        }
-                    }
-                }
+                k5_for_each_addend(ci, cj, t.mi, t.mj, t.wl, [&](int con, int x) {
+                    cons = (cons & ~(0xFFull << (8 * nadd))) | ((unsigned long long)con << (8 * nadd));
+                    s_val[tid * K5_ADDS + nadd] = t.split_frac * ov[(size_t)x * H + con]; ++nadd;
+                });
             }
             s_con[tid] = cons;
         }
@@ -362,16 +366,9 @@ __global__ __launch_bounds__(K5_TILE) void k5_pair_block_kernel(PairConsts c,
 #pragma unroll
                     for (int a = 0; a < K5_ADDS; ++a) if ((int)((cons >> (8 * a)) & 0xFF) == tid) acc += v[a];
                 } else {
-                    const ReadTerms t = terms(base + q);
+                    const K5ReadTerms t = terms(base + q);
                     const double* ov = w_ov + (size_t)t.row0 * H;
-                    for (int which = 0; which < 2; ++which) {
-                        const uint8_t* o = which ? cj : ci;
-                        unsigned long long m = which ? t.mj : t.mi;
-                        while (m) {
-                            const int s = __builtin_ctzll(m); m &= m - 1;
-                            for (int x = 0; x < t.wl; ++x) { const int con = o[s + x]; if (con == tid) acc += t.split_frac * ov[(size_t)x * H + con]; }
-                        }
-                    }
+                    k5_for_each_addend(ci, cj, t.mi, t.mj, t.wl, [&](int con, int x) { if (con == tid) acc += t.split_frac * ov[(size_t)x * H + con]; });
                 }
             }
         }
@@ -382,28 +379,19 @@ __global__ __launch_bounds__(K5_TILE) void k5_pair_block_kernel(PairConsts c,
     __syncthreads();
     if (tid != 0) return;
     unsigned long long read_combined_ed = 0;
-    for (int q = 0; q < K5_TILE; ++q) { const unsigned long long sum = read_combined_ed + s_ed[q]; read_combined_ed = sum < read_combined_ed ? 0xFFFFFFFFFFFFFFFFull : sum; }
+    for (int q = 0; q < K5_TILE; ++q) read_combined_ed = k5_saturating_add(read_combined_ed, s_ed[q]);
     const double ln_ed_penalty = (double)read_combined_ed * c.ln_ed;
     bool valid = true;
     const double mn = k5_multinomial(c, [&](int h) { return (int)s_cnt[h]; }, [&](int h) { return s_hw[h]; }, hap_norm, ln_fact, ln_fact_n, ln_p, ln_p_stride,
                                      chain_has_del[i] && chain_has_del[j], valid);
     atomicAdd(n_scored, 1ull);
-    if (!valid) { blk_pid[pid] = 0xFFFFFFFFFFFFFFFFull; return; }
-    const double primary = ln_ed_penalty + mn + s_cost[0] + s_cost[1] + s_cost[2];                                        // chaining.rs:172-174
-    blk_score[pid] = primary; blk_pid[pid] = pid; blk_ed[pid] = read_combined_ed;
-    double* cp = blk_comp + (size_t)pid * 5; cp[0] = ln_ed_penalty; cp[1] = mn; cp[2] = s_cost[0]; cp[3] = s_cost[1]; cp[4] = s_cost[2];
-    atomicMin(global_best, (unsigned long long)__double_as_longlong(primary));
+    if (!valid) { blk_pid[pid] = K5_NO_PAIR; return; }
+    k5_store_result(pid, pid, ln_ed_penalty, mn, s_head.cost, read_combined_ed, blk_score, blk_pid, blk_comp, blk_ed, global_best);
 }
 
 // =============================================================================================
 // host
 // =============================================================================================
-template <typename T> static T* k5_upload(sp_ctx* ctx, const char* name, const std::vector<T>& v) {
-    T* d = (T*)sp_pool(ctx, name, std::max<size_t>(1, v.size()) * sizeof(T));
-    if (d && !v.empty()) (void)hipMemcpyAsync(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-    return d;
-}
-
 extern "C" int32_t sp_cyp_best_chain_pair(sp_ctx* ctx, const sp_chain_problem* p, sp_chain_result* res) {
     if (!ctx || !p || !res || (p->n_haps && !p->hap_type)) return SP_ERR_INVALID_ARG;
     std::memset(res, 0, sizeof(*res));
@@ -582,9 +570,9 @@ extern "C" int32_t sp_cyp_best_chain_pair(sp_ctx* ctx, const sp_chain_problem* p
             hipLaunchKernelGGL(k5_pair_block_kernel, dim3((unsigned)blocks), dim3(K5_TILE), 0, ctx->stream, pc, d_chains, d_clen, d_unexp, d_ninf, d_del, d_lasso, d_norm,
                                d_rwo, d_ov, d_tb, d_tm, d_opt, d_worst, d_lf, lf_n, d_lp, max_total + 1, d_gb, d_bs, d_bp, d_bc, d_be, d_gb + 1);
         else {
-        (void)hipFuncSetAttribute((const void*)k5_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)256 * H * sizeof(double)));
-        hipLaunchKernelGGL(k5_pair_kernel, dim3((unsigned)blocks), dim3(256), (size_t)256 * H * sizeof(double), ctx->stream, pc, d_chains, d_clen, d_unexp, d_ninf, d_del, d_lasso, d_norm,
-                           d_rwo, d_ed, d_ov, d_tb, d_tm, d_opt, d_worst, d_lf, lf_n, d_lp, max_total + 1, d_gb, d_bs, d_bp, d_bc, d_be, d_gb + 1);
+            (void)hipFuncSetAttribute((const void*)k5_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)256 * H * sizeof(double)));
+            hipLaunchKernelGGL(k5_pair_kernel, dim3((unsigned)blocks), dim3(256), (size_t)256 * H * sizeof(double), ctx->stream, pc, d_chains, d_clen, d_unexp, d_ninf, d_del, d_lasso, d_norm,
+                               d_rwo, d_ov, d_tb, d_tm, d_opt, d_worst, d_lf, lf_n, d_lp, max_total + 1, d_gb, d_bs, d_bp, d_bc, d_be, d_gb + 1);
         }
         if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "k5 launch failed");
     }
@@ -597,14 +585,11 @@ extern "C" int32_t sp_cyp_best_chain_pair(sp_ctx* ctx, const sp_chain_problem* p
     res->n_pairs_scored = gb[1];
     int64_t wb = -1;
     for (uint64_t b = 0; b < blocks; ++b) {
-        if (bp[b] == 0xFFFFFFFFFFFFFFFFull) continue;
+        if (bp[b] == K5_NO_PAIR) continue;
         if (wb < 0 || bs[b] < bs[wb] || (bs[b] == bs[wb] && bp[b] < bp[wb])) wb = (int64_t)b;
     }
     if (wb < 0) return SP_ERR_NO_SCORE_PAIRS;
-    // pair id -> (i, j)
-    uint64_t pid = bp[wb]; int wi = 0;
-    while (wi + 1 < P && (uint64_t)(wi + 1) * P - (uint64_t)(wi + 1) * wi / 2 <= pid) ++wi;
-    const int wj = (int)(pid - ((uint64_t)wi * P - (uint64_t)wi * (wi - 1) / 2)) + wi;
+    int wi, wj; k5_pair_from_id(bp[wb], P, wi, wj);
     res->index1 = wi; res->index2 = wj;
     res->score = bs[wb]; res->ln_ed_penalty = bc[wb * 5]; res->mn_llh_penalty = bc[wb * 5 + 1]; res->allele_expected_penalty = bc[wb * 5 + 2];
     res->unexpected_chain_penalty = bc[wb * 5 + 3]; res->inferred_chain_penalty = bc[wb * 5 + 4]; res->edit_distance = be[wb];

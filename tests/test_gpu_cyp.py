@@ -17,8 +17,8 @@ def gpu_chain_pair(ctx, inp):
                                    inp.infer, inp.normalize_all, inp.ignore, inp.penalties)
 
 
-def same(oracle, gpu_ctx, inp):
-    exp = of.oracle_chain_pair(oracle, inp)
+def same(oracle, gpu_ctx, inp, exp=None):
+    exp = of.oracle_chain_pair(oracle, inp) if exp is None else exp
     rc, got = gpu_chain_pair(gpu_ctx, inp)
     assert rc == exp.status, (rc, exp.status)
     if rc == 0:
@@ -71,6 +71,35 @@ def test_chain_pairs_by_workgroup_and_by_thread(oracle, gpu_ctx):
     assert min(seen.values()) >= 4
     with pytest.raises(Exception):
         gpu_ctx.set_option("k5_block_pairs", -1)
+
+
+def test_chain_pair_kernels_at_tile_edges(oracle, gpu_ctx):
+    """both K5 kernels against the oracle, bit for bit, where the scoring rule they share can go wrong: one read, an even and an odd read count for the
+    thread kernel's read-ahead, the workgroup kernel's 256-read tile at its boundary and one past it; noise 0.0 gives many equally good windows (more
+    than eight addends: added up from memory), noise 0.15 mostly staged addends; 9 to 42 chains, so the thread kernel's last block is mostly past
+    n_pairs.  Seed 5: the oracle returns status 0 for every problem listed."""
+    limits = (0, 1 << 20)
+    sizes = (1, 2, 255, 256, 257, 513)
+    ok = {(limit, n): 0 for limit in limits for n in sizes}
+    problems = []
+    for n_reads in sizes:
+        for noise in (0.0, 0.15):
+            for infer in (False, True):
+                labels, obs, sc, inf = cyp_cases.synthetic_problem(np.random.default_rng(5), n_d6=3, n_reads=n_reads, noise=noise, infer=infer)
+                inp = of.ChainInputs(labels, obs, sc, inf, True, of.DEFAULT_PENALTIES, False)
+                problems.append((n_reads, inp, of.oracle_chain_pair(oracle, inp)))              # the oracle runs once per problem
+    small = next(c for c in cyp_cases.reference_cases() if c[2] == 0)           # a handful of pairs
+    try:
+        for limit in limits:
+            gpu_ctx.set_option("k5_block_pairs", limit)
+            for n_reads, inp, exp in problems:
+                rc, exp = same(oracle, gpu_ctx, inp, exp)
+                ok[limit, n_reads] += rc == 0
+            rc, exp = same(oracle, gpu_ctx, small[1])
+            assert rc == 0 and [list(exp.chain1[:exp.n1]), list(exp.chain2[:exp.n2])] == small[3]
+    finally:
+        gpu_ctx.set_option("k5_block_pairs", 4096)
+    assert min(ok.values()) >= 1, ok
 
 
 def test_topk_anchors(oracle, pkg, gpu_ctx):
