@@ -86,14 +86,22 @@ class Oracle:
         self.L.osp_encode(s, len(s), a.ctypes.data_as(C.c_void_p))
         return a[:len(s)] if len(s) else a[:0]
 
-    def wfa(self, a, b, diag, max_ed=255, events=True, retry=False):
+    def wfa(self, a, b, diag, max_ed=255, events=True, retry=False, band=None):
         """retry: the rules of the library's generic cell launcher -- True / 1: a cell that finds nothing on 64 diagonals runs again on
-        256; 2: also when it needed more than 32 edits, the wide result is kept when it has fewer (sp_align_batch, placements)"""
+        256; 2: also when it needed more than 32 edits, the wide result is kept when it has fewer (sp_align_batch, placements).
+        band (64 | 256, without retry): one run of osp_wfa_band on that many diagonals"""
         A = a if isinstance(a, np.ndarray) else self.encode(a)
         B = b if isinstance(b, np.ndarray) else self.encode(b)
         al = Aln()
         ev = np.zeros(max_ed + 1, np.uint32)
         ne = C.c_int32(0)
+        if band is not None:
+            assert not retry
+            self.L.osp_wfa_band.restype = C.c_int32
+            self.L.osp_wfa_band.argtypes = self.L.osp_wfa.argtypes[:6] + [C.c_int32] + self.L.osp_wfa.argtypes[6:]
+            self.L.osp_wfa_band(A.ctypes.data_as(C.c_void_p), len(A), B.ctypes.data_as(C.c_void_p), len(B), int(diag), int(max_ed), int(band),
+                                C.byref(al), ev.ctypes.data_as(C.c_void_p) if events else None, C.byref(ne))
+            return al, ev[:ne.value].copy()
         fn = self.L.osp_wfa_retry2 if retry == 2 else self.L.osp_wfa_retry if retry else self.L.osp_wfa
         fn.restype = C.c_int32
         fn.argtypes = self.L.osp_wfa.argtypes
@@ -107,6 +115,17 @@ class Oracle:
         d = C.c_int32(0)
         v = self.L.osp_anchor(A.ctypes.data_as(C.c_void_p), len(A), B.ctypes.data_as(C.c_void_p), len(B), C.byref(d))
         return d.value, v
+
+    def anchor_topk(self, a, b, k):
+        """osp_anchor_topk -> k pairs (diagonal, votes), (0, 0) in the unused slots"""
+        A = a if isinstance(a, np.ndarray) else self.encode(a)
+        B = b if isinstance(b, np.ndarray) else self.encode(b)
+        d, v = np.zeros(k, np.int32), np.zeros(k, np.int32)
+        self.L.osp_anchor_topk.restype = C.c_int32
+        self.L.osp_anchor_topk.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        self.L.osp_anchor_topk(A.ctypes.data_as(C.c_void_p), len(A), B.ctypes.data_as(C.c_void_p), len(B), int(k),
+                               d.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p))
+        return [(int(x), int(y)) for x, y in zip(d, v)]
 
     def cigar(self, al, ev):
         cg = np.zeros(2 * len(ev) + 4, np.uint32)
