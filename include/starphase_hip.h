@@ -391,6 +391,41 @@ int32_t sp_align_pileup_hap_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqs
  * by '+' when bit 3 is set (a low code of 7 is written '?').  out / cap / needed as sp_support_ins_string; SP_ERR_INVALID_ARG for n_cols > SP_SUPPORT_HAP_COLS. */
 int32_t sp_support_hap_string(const sp_support_hap* rec, char* out, uint64_t cap, uint64_t* needed);
 
+/* ------------------------------------------------------------------ window support: HOW MANY reads agree with the target over a whole interval
+ * The column table cannot say whether the reads that disagree at column j and at column j + 3 are the same reads; a count per INTERVAL can.  A window is a half-open
+ * interval [start, end) of target columns, start < end <= the target's length.  Target t owns windows[win_offset[t] .. win_offset[t + 1]) (win_offset: n_targets + 1
+ * entries, win_offset[0] = 0, ascending); inside a target they come in any order and may overlap, nest or repeat.  out[win_offset[t] + i] counts, over the aligned pairs
+ * that name t (n_cigar > 0; in sp_align_pileup_windows_batch also score > 0 -- the pairs the table counts), with [b_start, b_end) the pair's target span:
+ *   span     b_start <= start && end <= b_end
+ *   partial  the two intervals intersect, but the pair does not span the window
+ *   exact    the pair spans the window, every column of it lies under an '=' op, and no 'I' op sits at an INTERIOR junction of it: an 'I' between columns j and j + 1
+ *            counts when start <= j && j + 1 < end.  Insertions at the two outer junctions do not count, on either side (the rule is symmetric on purpose)
+ * reserved_ is 0.  A target without pairs, or a pair that did not align, contributes zeros.  exact <= span, and span + partial <= the pairs naming the target.
+ * Kernel: one workgroup of SP_WINDOW_WAVES waves per (target, chunk of SP_WINDOW_CHUNK windows); every lane keeps SP_WINDOW_CHUNK / 64 windows
+ * and their three counters in registers.  The waves take the target's pairs in turn; a pair that spans none of the wave's windows is not walked; otherwise the wave
+ * walks the op row ONCE, 64 ops at a time (the prefix sums of the pileup kernel), and compacts the pair's defects -- runs of columns under 'X' or 'D', junctions with an
+ * 'I' -- into LDS, in doubled coordinates (column c = [2 c, 2 c + 1), junction behind column j = [2 j + 1, 2 j + 2)), where they are sorted and disjoint by construction;
+ * each lane then decides its windows by a binary search.  A pair with more than SP_WINDOW_DEFECTS - 64 defects is decided in several such rounds (a window is inexact
+ * when any round finds a defect in it).  The waves' counters meet in LDS at the end; one thread per window stores its record.  No atomics at all; integer counts, exact
+ * in any order of the pairs and for any launch geometry.  Pooled buffers only.
+ * sp_pileup_windows_batch: over host op rows -- arguments and checks of sp_pileup_batch, and SP_ERR_INVALID_ARG before any launch for a window with start >= end or end
+ * beyond its target, or a win_offset that does not start at 0 and ascend.
+ * sp_align_pileup_windows_batch: sp_align_pileup_band_batch that also counts the windows from the op rows in the pooled op buffer (same checks of the windows);
+ * windows == NULL is exactly that call: nothing more is launched or pooled.  A batch of more than SP_ALIGN_PILEUP_SLICE pairs accumulates across slices as the column
+ * tiles do: a chunk's workgroup is the one owner of its records in its launch and loads, adds to and stores them (plain loads and stores). */
+#define SP_WINDOW_CHUNK   256
+#define SP_WINDOW_WAVES   4
+#define SP_WINDOW_DEFECTS 256
+typedef struct { uint32_t start, end; } sp_window;
+typedef struct { uint32_t span, exact, partial, reserved_; } sp_window_support;   /* 16 bytes */
+int32_t sp_pileup_windows_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
+                                const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset,
+                                const uint64_t* win_offset, const sp_window* windows, sp_window_support* out);
+int32_t sp_align_pileup_windows_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts,
+                                      int32_t band, int32_t retry_band, const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols,
+                                      sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
+                                      const uint64_t* win_offset, const sp_window* windows, sp_window_support* win_out);
+
 /* ------------------------------------------------------------------ HLA database
  * Replaces HlaRealigner::new + create_hla_fasta (src/hla/realigner.rs:42-91,497-526) and the per-call
  * one-sequence indexes of score_read (src/hla/caller.rs:1370-1379).
@@ -895,6 +930,50 @@ int32_t sp_cyp_support_json_hap(const sp_cyp_call* call, const char* consensus, 
                                 const sp_support_hap_head* heads, uint64_t target0, const sp_cyp_read_mapping* mappings, uint64_t n_mappings,
                                 const char* const* read_names, uint32_t n_read_names, char* out, uint64_t cap, uint64_t* needed);
 
+/* ------------------------------------------------------------------ cyp2d6_alleles.vcf.gz: the variants of the typed regions as a VCF, with read support
+ * write_cyp2d6_vcf (src/cyp2d6/vcf_writer.rs; caller.rs:410-413): one haploid sample column per region typed as a CYP2D6 star allele (has_variants[h] == 1), in
+ * region order, named by its index label "<index>_<full allele>" (the key of cyp2d6_alleles.json), and one record per database variant that at least one such region
+ * lists (state != 255), in variant-table order.  GT: AmbiguousUnexpected, AmbiguousMissing -> '.'; Match, Unexpected -> 1; everything else, and a region that does not
+ * list the variant -> 0.  The reference leaves QUAL and depth open; this library fills in two FORMAT fields of its own from window support (above):
+ *   SR  member reads of the region's consensus whose alignment spans the variant's window on that consensus      CR  those of them that match the consensus at every base of it
+ * They say how well the reads agree with the CONSENSUS around the variant -- not REF / ALT read counts: a region whose consensus carries ALT has CR reads carrying ALT,
+ * one whose consensus carries REF has CR reads carrying REF.
+ * sp_cyp_variant_windows (host only): the window of every variant on ONE consensus.  aln / cigar / n_cigar: the alignment of that consensus (query a) onto the backbone
+ * (target b) from sp_affine_align_batch; var_pos: positions on the backbone (sp_cyp_problem.var_pos), var_ref_len: the lengths of REF.  Variant v with the backbone
+ * interval [p - flank, p + |ref| + flank) is covered iff b_start <= p - flank and p + |ref| + flank <= b_end; a covered variant's window is [q_lo, q_hi): q_lo = the
+ * query offset when the path has consumed the backbone up to p - flank, BEFORE any 'I' at that junction, q_hi = the query offset when it has consumed it up to
+ * p + |ref| + flank, AFTER any 'I' at that junction -- inserted bases at the edges fall inside.  valid[v] = 1 and windows[v] set; 0 for a variant that is not covered or
+ * whose window is empty (the whole interval under one 'D').  SP_ERR_INVALID_ARG for ops that do not consume the spans of aln.
+ * SP_CYP_VCF_FLANK: the default flank, a design choice and not a measurement -- the smallest that puts the junction of a pure insertion (|ref| 0, or 1 after
+ * normalisation) strictly inside its window and keeps one neighbouring base on each side beyond that.
+ * sp_cyp_variant_support(_cohort): the driver -- call / consensus / cons_cap / mappings as sp_cyp_consensus_support takes them, problem and region_variants as
+ * sp_cyp_diplotype_mappings took and returned them (_cohort: one sp_cyp_region_variants per sample).  Every has_variants consensus is aligned onto problem->backbone (one
+ * sp_anchor_batch for the diagonals, one sp_affine_align_batch at the map-hifi scores on 256 diagonals), the windows are made by the rule above, and the member pass
+ * of sp_cyp_consensus_support runs with them attached (sp_align_pileup_windows_batch).  support / support_valid: SP_CYP_MAXCONS * n_variants entries (per sample),
+ * region h's at h * n_variants + v; support_valid 0 (and zero counts) where region h has no window for v.  col_offset / cols / cols_cap / summaries (optional, all or
+ * none but cols): the table of sp_cyp_consensus_support from the SAME member pass.
+ * sp_cyp_alleles_vcf (host only): the text.  support / support_valid (optional) as above: FORMAT becomes GT:SR:CR, with '.' for both where support_valid is 0; without
+ * support FORMAT is GT alone and the records are the reference's, field for field.  file_date NULL: today (UTC, %Y%m%d); command NULL: "".  call->status != 0 or no typed
+ * region: the header and the #CHROM line without samples, no records.  out / cap / needed as sp_cyp_alleles_json.
+ * sp_bgzf_save: data as a BGZF file (gzip members with the 'BC' subfield of at most 64 KiB of input and 64 KiB as a block, raw deflate, the 28-byte EOF marker last).
+ * sp_cyp_alleles_vcf_save: the text saved that way. */
+#define SP_CYP_VCF_FLANK 2
+int32_t sp_cyp_variant_windows(const sp_affine_aln* aln, const uint32_t* cigar, uint32_t n_cigar, uint32_t n_variants, const int32_t* var_pos, const uint32_t* var_ref_len,
+                               uint32_t flank, sp_window* windows, int32_t* valid);
+int32_t sp_cyp_variant_support(sp_ctx* ctx, const sp_cyp_problem* problem, const sp_seqset* reads, const sp_cyp_call* call, const char* consensus, uint32_t cons_cap,
+                               const sp_cyp_region_variants* region_variants, const sp_cyp_read_mapping* mappings, uint64_t n_mappings, uint32_t flank,
+                               sp_window_support* support, int32_t* support_valid, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries);
+int32_t sp_cyp_variant_support_cohort(sp_ctx* ctx, const sp_cyp_problem* problem, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus,
+                                      uint32_t cons_cap, const sp_cyp_region_variants* region_variants, const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint32_t flank,
+                                      sp_window_support* support, int32_t* support_valid, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries);
+typedef struct sp_cyp_db sp_cyp_db;            /* the CYP2D6 database, below */
+int32_t sp_cyp_alleles_vcf(const sp_cyp_db* db, const sp_cyp_call* call, const sp_cyp_region_variants* region_variants, const sp_window_support* support /* optional */,
+                           const int32_t* support_valid /* optional */, const char* file_date /* NULL: today, UTC, %Y%m%d */, const char* command /* NULL: "" */,
+                           char* out, uint64_t cap, uint64_t* needed);
+int32_t sp_cyp_alleles_vcf_save(const sp_cyp_db* db, const sp_cyp_call* call, const sp_cyp_region_variants* region_variants, const sp_window_support* support,
+                                const int32_t* support_valid, const char* file_date, const char* command, const char* path);
+int32_t sp_bgzf_save(const char* path, const void* data, uint64_t len);
+
 /* ------------------------------------------------------------------ CYP2D6 templates and typing tables
  * Replaces generate_cyp_hybrids (src/cyp2d6/definitions.rs:346-464), LoadedVariants::load_variant_database
  * (src/cyp2d6/haplotyper.rs:650-773) and the table building of Cyp2d6Extractor::new (src/cyp2d6/haplotyper.rs:45-132).
@@ -937,7 +1016,6 @@ typedef struct {
     uint32_t n_templates, n_variants, n_vi, n_alleles, backbone_len;
     int64_t first_variant_pos, last_variant_pos;  /* LoadedVariants::{first,last}_variant_pos, -1 when there is none */
 } sp_cyp_db_stats;
-typedef struct sp_cyp_db sp_cyp_db;
 int32_t sp_cyp_db_create(sp_ctx* ctx /* may be NULL */, const sp_cyp_locus* locus, const sp_cyp_gene_def* gene_def, const sp_cyp_config* config /* may be NULL */,
                          sp_cyp_db** out);
 void    sp_cyp_db_free(sp_cyp_db* db);
@@ -945,6 +1023,9 @@ int32_t sp_cyp_db_info(const sp_cyp_db* db, sp_cyp_db_stats* stats);
 /* the pointers stay valid for the life of the database; subtype is NULL for a label without one */
 int32_t sp_cyp_db_template(const sp_cyp_db* db, uint32_t i, int32_t* type, const char** subtype, const char** full_allele, const char** seq, uint32_t* len, int32_t* deep);
 int32_t sp_cyp_db_variant(const sp_cyp_db* db, uint32_t i, int64_t* chrom_pos, const char** ref, const char** alt, const char** label, int32_t* is_vi);
+/* the "VI" entry of variant i as the database file has it (the last definition's, as LoadedVariants keeps it); *vi = NULL when the variant is not flagged.  Valid for
+ * the life of the database. */
+int32_t sp_cyp_db_variant_vi(const sp_cyp_db* db, uint32_t i, const char** vi);
 int32_t sp_cyp_db_index_label(const sp_cyp_db* db, const char* label, uint32_t* idx);                                  /* LoadedVariants::index_label */
 int32_t sp_cyp_db_index_variant(const sp_cyp_db* db, uint64_t position, const char* ref, const char* alt, uint32_t* idx);   /* LoadedVariants::index_variant */
 int32_t sp_cyp_db_allele(const sp_cyp_db* db, uint32_t a, const char** subtype, const uint8_t** row /* n_variants 0/1 */);
@@ -1668,6 +1749,11 @@ int32_t sp_starphase_set_consensus_support(sp_starphase* handle, int32_t on);
  * failure of the pass fails the sample's CYP2D6 entry (out of memory; an alignment of more than 4,096 runs, SP_ERR_CAPACITY); in a batch the group's samples then go
  * through the pass one by one and only those whose own pass fails are failed. */
 int32_t sp_starphase_set_cyp_consensus_support(sp_starphase* handle, int32_t on);
+/* cyp2d6_alleles.vcf.gz, off by default (on 0): with it on, a call with a debug folder whose CYP2D6 call has status 0 also writes <folder>/cyp2d6_alleles.vcf.gz
+ * (sp_cyp_alleles_vcf_save above, FORMAT GT:SR:CR, flank SP_CYP_VCF_FLANK) from sp_cyp_variant_support_cohort over the samples of the batch group that have a debug
+ * folder -- the SAME member pass that serves sp_starphase_set_cyp_consensus_support when both are on.  Off, or no debug folder: no launch, no file, and every output is
+ * the same bytes; on: every other output is.  A failure of the pass or of the file fails the sample's CYP2D6 entry. */
+int32_t sp_starphase_set_cyp_vcf(sp_starphase* handle, int32_t on);
 /* A switch of its own, off by default, with effect only where one of the two switches above writes its file: the support pass of that file also makes the insertion
  * list (sp_hla_consensus_support_cohort_ins / sp_cyp_consensus_support_cohort_ins: the same one pass per batch group) and the file is rendered with it
  * (sp_consensus_support_json_ins / sp_cyp_support_json_ins, without first_read): every contested column with 2 * ins > depth gains "insertions" (and "more", "other").

@@ -22,11 +22,15 @@ pub const SP_ALIGN_PILEUP_WIDE_ROWS: i64 = 128;
 pub const SP_PILEUP_INS_LDS_RUNS: i64 = 1024;
 pub const SP_SUPPORT_HAP_COLS: i64 = 64;
 pub const SP_SUPPORT_HAP_LDS_KEYS: i64 = 1024;
+pub const SP_WINDOW_CHUNK: i64 = 256;
+pub const SP_WINDOW_WAVES: i64 = 4;
+pub const SP_WINDOW_DEFECTS: i64 = 256;
 pub const SP_K1_SEL: i64 = 16;
 pub const SP_HLA_MAP_TIES: i64 = 1;
 pub const SP_HLA_TIES_MAX_NAMES: i64 = 256;
 pub const SP_MAX_CHAIN: i64 = 64;
 pub const SP_CYP_MAXCONS: i64 = 64;
+pub const SP_CYP_VCF_FLANK: i64 = 2;
 pub const SP_VAR_MAXDIP: i64 = 4096;
 pub const SP_GROUP_ID_BYTES: i64 = 128;
 
@@ -122,6 +126,18 @@ pub struct sp_support_hap_head {
     pub n_records: u32,
     pub n_cols: u32,
     pub n_cols_total: u32,
+    pub reserved_: u32,
+}
+#[repr(C)]
+pub struct sp_window {
+    pub start: u32,
+    pub end: u32,
+}
+#[repr(C)]
+pub struct sp_window_support {
+    pub span: u32,
+    pub exact: u32,
+    pub partial: u32,
     pub reserved_: u32,
 }
 #[repr(C)]
@@ -822,6 +838,8 @@ extern "C" {
     pub fn sp_pileup_hap_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, aln: *const sp_affine_aln, cigar: *const u32, cigar_stride: u32, n_cigar: *const u32, col_offset: *const u64, haps: *mut sp_support_hap, hap_cap: u64, n_haps: *mut u64, heads: *mut sp_support_hap_head) -> i32;
     pub fn sp_align_pileup_hap_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, band: i32, retry_band: i32, col_offset: *const u64, aln: *mut sp_affine_aln, cols: *mut sp_pileup_col, summaries: *mut sp_support_summary, n_members: *const u32, band_used: *mut u32, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64, haps: *mut sp_support_hap, hap_cap: u64, n_haps: *mut u64, heads: *mut sp_support_hap_head) -> i32;
     pub fn sp_support_hap_string(rec: *const sp_support_hap, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
+    pub fn sp_pileup_windows_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, aln: *const sp_affine_aln, cigar: *const u32, cigar_stride: u32, n_cigar: *const u32, col_offset: *const u64, win_offset: *const u64, windows: *const sp_window, out: *mut sp_window_support) -> i32;
+    pub fn sp_align_pileup_windows_batch(ctx: *mut sp_ctx, A: *const sp_seqset, B: *const sp_seqset, pairs: *const sp_pair, n_pairs: u64, opts: *const sp_affine_opts, band: i32, retry_band: i32, col_offset: *const u64, aln: *mut sp_affine_aln, cols: *mut sp_pileup_col, summaries: *mut sp_support_summary, n_members: *const u32, band_used: *mut u32, win_offset: *const u64, windows: *const sp_window, win_out: *mut sp_window_support) -> i32;
     pub fn sp_hla_db_create(ctx: *mut sp_ctx, desc: *const sp_hla_db_desc, out: *mut *mut sp_hla_db) -> i32;
     pub fn sp_hla_db_free(db: *mut sp_hla_db);
     pub fn sp_hla_seed_index_info(ctx: *mut sp_ctx, db: *const sp_hla_db, out: *mut i64) -> i32;
@@ -869,11 +887,18 @@ extern "C" {
     pub fn sp_cyp_consensus_support_hap(ctx: *mut sp_ctx, reads: *const sp_seqset, call: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, mappings: *const sp_cyp_read_mapping, n_mappings: u64, col_offset: *mut u64, cols: *mut sp_pileup_col, cols_cap: u64, summaries: *mut sp_support_summary, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64, haps: *mut sp_support_hap, hap_cap: u64, n_haps: *mut u64, heads: *mut sp_support_hap_head) -> i32;
     pub fn sp_cyp_consensus_support_cohort_hap(ctx: *mut sp_ctx, n_samples: u32, reads: *const *const sp_seqset, calls: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, mappings: *const sp_cyp_read_mapping, mapping_off: *const u64, col_offset: *mut u64, cols: *mut sp_pileup_col, cols_cap: u64, summaries: *mut sp_support_summary, ins: *mut sp_pileup_ins, ins_cap: u64, n_ins: *mut u64, haps: *mut sp_support_hap, hap_cap: u64, n_haps: *mut u64, heads: *mut sp_support_hap_head) -> i32;
     pub fn sp_cyp_support_json_hap(call: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, col_offset: *const u64, cols: *const sp_pileup_col, summaries: *const sp_support_summary, ins: *const sp_pileup_ins, n_ins: u64, haps: *const sp_support_hap, n_haps: u64, heads: *const sp_support_hap_head, target0: u64, mappings: *const sp_cyp_read_mapping, n_mappings: u64, read_names: *const *const c_char, n_read_names: u32, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
+    pub fn sp_cyp_variant_windows(aln: *const sp_affine_aln, cigar: *const u32, n_cigar: u32, n_variants: u32, var_pos: *const i32, var_ref_len: *const u32, flank: u32, windows: *mut sp_window, valid: *mut i32) -> i32;
+    pub fn sp_cyp_variant_support(ctx: *mut sp_ctx, problem: *const sp_cyp_problem, reads: *const sp_seqset, call: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, region_variants: *const sp_cyp_region_variants, mappings: *const sp_cyp_read_mapping, n_mappings: u64, flank: u32, support: *mut sp_window_support, support_valid: *mut i32, col_offset: *mut u64, cols: *mut sp_pileup_col, cols_cap: u64, summaries: *mut sp_support_summary) -> i32;
+    pub fn sp_cyp_variant_support_cohort(ctx: *mut sp_ctx, problem: *const sp_cyp_problem, n_samples: u32, reads: *const *const sp_seqset, calls: *const sp_cyp_call, consensus: *const c_char, cons_cap: u32, region_variants: *const sp_cyp_region_variants, mappings: *const sp_cyp_read_mapping, mapping_off: *const u64, flank: u32, support: *mut sp_window_support, support_valid: *mut i32, col_offset: *mut u64, cols: *mut sp_pileup_col, cols_cap: u64, summaries: *mut sp_support_summary) -> i32;
+    pub fn sp_cyp_alleles_vcf(db: *const sp_cyp_db, call: *const sp_cyp_call, region_variants: *const sp_cyp_region_variants, support: *const sp_window_support, support_valid: *const i32, file_date: *const c_char, command: *const c_char, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
+    pub fn sp_cyp_alleles_vcf_save(db: *const sp_cyp_db, call: *const sp_cyp_call, region_variants: *const sp_cyp_region_variants, support: *const sp_window_support, support_valid: *const i32, file_date: *const c_char, command: *const c_char, path: *const c_char) -> i32;
+    pub fn sp_bgzf_save(path: *const c_char, data: *const c_void, len: u64) -> i32;
     pub fn sp_cyp_db_create(ctx: *mut sp_ctx, locus: *const sp_cyp_locus, gene_def: *const sp_cyp_gene_def, config: *const sp_cyp_config, out: *mut *mut sp_cyp_db) -> i32;
     pub fn sp_cyp_db_free(db: *mut sp_cyp_db);
     pub fn sp_cyp_db_info(db: *const sp_cyp_db, stats: *mut sp_cyp_db_stats) -> i32;
     pub fn sp_cyp_db_template(db: *const sp_cyp_db, i: u32, type_: *mut i32, subtype: *mut *const c_char, full_allele: *mut *const c_char, seq: *mut *const c_char, len: *mut u32, deep: *mut i32) -> i32;
     pub fn sp_cyp_db_variant(db: *const sp_cyp_db, i: u32, chrom_pos: *mut i64, ref_: *mut *const c_char, alt: *mut *const c_char, label: *mut *const c_char, is_vi: *mut i32) -> i32;
+    pub fn sp_cyp_db_variant_vi(db: *const sp_cyp_db, i: u32, vi: *mut *const c_char) -> i32;
     pub fn sp_cyp_db_index_label(db: *const sp_cyp_db, label: *const c_char, idx: *mut u32) -> i32;
     pub fn sp_cyp_db_index_variant(db: *const sp_cyp_db, position: u64, ref_: *const c_char, alt: *const c_char, idx: *mut u32) -> i32;
     pub fn sp_cyp_db_allele(db: *const sp_cyp_db, a: u32, subtype: *mut *const c_char, row: *mut *const u8) -> i32;
@@ -1003,6 +1028,7 @@ extern "C" {
     pub fn sp_starphase_set_hla_ties(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_consensus_support(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_cyp_consensus_support(handle: *mut sp_starphase, on: i32) -> i32;
+    pub fn sp_starphase_set_cyp_vcf(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_support_insertions(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_support_haplotypes(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_warnings(handle: *const sp_starphase) -> *const c_char;

@@ -186,6 +186,8 @@ int32_t sp_struct_size(const char* name) {
     SP_SZ(sp_hla_cfg_gene)
     SP_SZ(sp_pileup_col)
     SP_SZ(sp_support_summary)
+    SP_SZ(sp_window)
+    SP_SZ(sp_window_support)
     SP_SZ(sp_support_entry)
     SP_SZ(sp_pileup_ins)
     SP_SZ(sp_support_hap)

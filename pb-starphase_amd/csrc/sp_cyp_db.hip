@@ -21,7 +21,8 @@ struct sp_cyp_db {
     sp_seqset* templates = nullptr;
     // backbone + ordered variants (positions: chromosome and backbone-relative)
     std::string backbone; uint64_t backbone_start = 0;
-    std::vector<int64_t> v_pos; std::vector<int32_t> v_rel; std::vector<std::string> v_ref, v_alt, v_label; std::vector<uint8_t> v_vi;
+    std::vector<int64_t> v_pos; std::vector<int32_t> v_rel; std::vector<std::string> v_ref, v_alt, v_label, v_vi_str; std::vector<uint8_t> v_vi;
+    std::string chrom;                                                        // sp_cyp_locus::chrom_name (the contig of cyp2d6_alleles.vcf.gz)
     std::map<std::tuple<uint64_t, std::string, std::string>, uint32_t> v_lookup;
     std::map<std::string, uint32_t> label_lookup;
     // haplotype_lookup in BTreeMap<Cyp2d6RegionLabel, _> order: (Cyp2d6, Some(star_allele)) sorts by the star-allele string
@@ -110,11 +111,14 @@ int32_t sp_cyp_db_create(sp_ctx* ctx, const sp_cyp_locus* L, const sp_cyp_gene_d
     struct Raw { uint64_t pos; std::string ref, alt, label; };
     std::vector<Raw> raw;
     std::map<std::tuple<uint64_t, std::string, std::string>, bool> vi_of;      // key -> flagged VI by some definition (also the inserted set)
+    std::map<std::tuple<uint64_t, std::string, std::string>, std::string> vi_text;      // key -> the "VI" entry itself (vi_set.insert, haplotyper.rs:663-665: the last definition's stands)
     const char* chrom = L->chrom_name ? L->chrom_name : "chr22";
+    db->chrom = chrom;
     for (uint32_t a = 0; a < G->n_alleles; ++a) for (uint32_t x = G->var_off[a]; x < G->var_off[a + 1]; ++x) {
         if (!G->var_ref[x] || !G->var_alt[x]) { delete db; return fail(SP_ERR_INVALID_ARG, "sp_cyp_db_create: null allele string"); }
         const auto key = std::make_tuple(G->var_pos[x], std::string(G->var_ref[x]), std::string(G->var_alt[x]));
         const bool vi = G->var_vi && G->var_vi[x];
+        if (vi) vi_text[key] = G->var_vi[x];
         auto it = vi_of.find(key);
         if (it == vi_of.end()) {
             vi_of.emplace(key, vi);
@@ -128,7 +132,7 @@ int32_t sp_cyp_db_create(sp_ctx* ctx, const sp_cyp_locus* L, const sp_cyp_gene_d
     for (uint32_t i = 0; i < raw.size(); ++i) {
         const auto key = std::make_tuple(raw[i].pos, raw[i].ref, raw[i].alt);
         db->v_pos.push_back((int64_t)raw[i].pos); db->v_ref.push_back(raw[i].ref); db->v_alt.push_back(raw[i].alt); db->v_label.push_back(raw[i].label);
-        db->v_vi.push_back(vi_of[key] ? 1 : 0);
+        db->v_vi.push_back(vi_of[key] ? 1 : 0); db->v_vi_str.push_back(vi_of[key] ? vi_text[key] : std::string());
         db->v_lookup[key] = i;
         db->label_lookup[raw[i].label] = i;                                   // collect() into a map: the last index of a repeated label wins
     }
@@ -208,6 +212,12 @@ int32_t sp_cyp_db_variant(const sp_cyp_db* db, uint32_t i, int64_t* chrom_pos, c
     return SP_OK;
 }
 
+int32_t sp_cyp_db_variant_vi(const sp_cyp_db* db, uint32_t i, const char** vi) {
+    if (!db || i >= db->v_pos.size() || !vi) return SP_ERR_INVALID_ARG;
+    *vi = db->v_vi[i] ? db->v_vi_str[i].c_str() : nullptr;
+    return SP_OK;
+}
+
 int32_t sp_cyp_db_index_label(const sp_cyp_db* db, const char* label, uint32_t* idx) {            // LoadedVariants::index_label (haplotyper.rs:793-798)
     if (!db || !label || !idx) return SP_ERR_INVALID_ARG;
     auto it = db->label_lookup.find(label);
@@ -249,3 +259,5 @@ int32_t sp_cyp_db_problem(const sp_cyp_db* db, sp_cyp_problem* pr) {
 }
 
 } // extern "C"
+
+const char* spi_cyp_db_chrom(const sp_cyp_db* db) { return db->chrom.c_str(); }

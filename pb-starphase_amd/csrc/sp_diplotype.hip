@@ -122,6 +122,7 @@ struct sp_starphase {
     int32_t consensus_support = 0;                   // sp_starphase_set_consensus_support: a debug folder also receives consensus_support.json
     int32_t support_insertions = 0;                  // sp_starphase_set_support_insertions: those two files also list the inserted strings of their contested columns
     int32_t support_haplotypes = 0;                  // sp_starphase_set_support_haplotypes: those two files also list the read haplotypes at their contested columns
+    int32_t cyp_vcf = 0;                             // sp_starphase_set_cyp_vcf: a debug folder also receives cyp2d6_alleles.vcf.gz, with SR / CR from the support pass
     int32_t cyp_consensus_support = 0;               // sp_starphase_set_cyp_consensus_support: a debug folder also receives cyp2d6_consensus_support.json
     int32_t hla_ties = 0;                            // sp_starphase_set_hla_ties: a debug folder gets hla_ties.json, the alleles each consensus's a = 5 scan cannot tell from its winner
     int32_t hla_debug_mappings = 0;                  // sp_starphase_set_hla_debug_mappings: hla_debug.json carries the mapping of each consensus against every allowed allele
@@ -909,8 +910,10 @@ void cyp_group(sp_starphase* h, std::vector<Sample*> group, bool only_ok, double
         std::vector<std::vector<sp_cyp_read_mapping>> mappings(n);
         std::vector<int32_t> rcs(n, SP_ERR_INVALID_ARG);             // until the cohort call has typed it
         // cyp2d6_consensus_support.json: the calls also hand out their consensuses (the calls themselves are the same), for one support pass over the group below
-        bool want_support = false;
-        for (uint32_t k = 0; k < n; ++k) want_support |= h->cyp_consensus_support && !typed[k]->debug.empty();
+        // cyp2d6_alleles.vcf.gz (sp_starphase_set_cyp_vcf) takes its SR / CR from the same pass: want_support is "the pass runs", want_json / want_vcf say what is written
+        bool want_json = false, want_vcf = false;
+        for (uint32_t k = 0; k < n; ++k) { want_json |= h->cyp_consensus_support && !typed[k]->debug.empty(); want_vcf |= h->cyp_vcf && !typed[k]->debug.empty(); }
+        const bool want_support = want_json || want_vcf;
         // (a consensus has at most 65,534 bases, like a read; the block is SP_CYP_MAXCONS x that = 4 MB of host memory per sample of the group while the lane runs,
         //  256 MB for a group of 64: sized by the limit, not by the reads, because a consensus over offset reads may be longer than any one of its segments)
         const uint32_t cons_cap = want_support ? 65536u : 0u;
@@ -942,20 +945,40 @@ void cyp_group(sp_starphase* h, std::vector<Sample*> group, bool only_ok, double
                 moff[k + 1] = flat.size();
             }
             if (!on.empty()) {
+                if (!want_json) n_cols = 0;                          // (the table is not downloaded for the VCF alone)
                 std::vector<uint64_t> off((size_t)n * SP_CYP_MAXCONS + 1, 0); std::vector<sp_pileup_col> cols((size_t)n_cols + 1); std::vector<sp_support_summary> sm((size_t)n * SP_CYP_MAXCONS);
+                sp_pileup_col* cols_out = want_json ? cols.data() : nullptr;
+                // the variant support of the group (want_vcf): SP_CYP_MAXCONS * n_variants records per sample, from the windows the pass counts
+                const size_t vper = (size_t)SP_CYP_MAXCONS * pr.n_variants;
+                std::vector<sp_window_support> vsup(want_vcf ? std::max<size_t>(vper * n, 1) : 0); std::vector<int32_t> vok(want_vcf ? std::max<size_t>(vper * n, 1) : 0);
+                const CypVariantIn vin = { &pr, rv.data(), SP_CYP_VCF_FLANK, vsup.data(), vok.data() };
+                auto vcf_save = [&](uint32_t k, const sp_window_support* sup, const int32_t* ok, CypLane* L) {
+                    if (!want_vcf || L->rc != SP_OK) return;
+                    const std::string path = typed[k]->debug + "/cyp2d6_alleles.vcf.gz";
+                    const int32_t rc_v = sp_cyp_alleles_vcf_save(h->cyp, &calls[k], &rv[k], sup, ok, nullptr, nullptr, path.c_str());
+                    if (rc_v != SP_OK) { L->rc = rc_v; L->err = "Error while writing " + path; }
+                };
                 SupportLists lists;                                  // (stay empty without sp_starphase_set_support_insertions / _haplotypes: the renderer then writes the file as before)
                 const bool want_ins = h->support_insertions != 0, want_haps = h->support_haplotypes != 0;
                 int32_t rc = support_with_lists(lists, want_ins, want_haps, (size_t)n * SP_CYP_MAXCONS, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got, sp_support_hap* hp, uint64_t hroom, uint64_t* hgot, sp_support_hap_head* hd) {
-                    return sp_cyp_consensus_support_cohort_hap(h->ctx2, n, sets.data(), sc.data(), cons.data(), cons_cap, flat.data(), moff.data(), off.data(), cols.data(), n_cols, sm.data(), p, room, got, hp, hroom, hgot, hd); });
+                    return spi_cyp_support_cohort(h->ctx2, n, sets.data(), sc.data(), cons.data(), cons_cap, flat.data(), moff.data(), off.data(), cols_out, n_cols, sm.data(), p, room, got, hp, hroom, hgot, hd,
+                                                  want_vcf ? &vin : nullptr); });
                 if (rc == SP_OK) {
-                    for (uint32_t k : on) cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data() + (size_t)k * SP_CYP_MAXCONS, cols.data(), sm.data() + (size_t)k * SP_CYP_MAXCONS, lists, (uint64_t)k * SP_CYP_MAXCONS, typed[k]->debug, &typed[k]->cyp);
+                    for (uint32_t k : on) {
+                        if (want_json) cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data() + (size_t)k * SP_CYP_MAXCONS, cols.data(), sm.data() + (size_t)k * SP_CYP_MAXCONS, lists, (uint64_t)k * SP_CYP_MAXCONS, typed[k]->debug, &typed[k]->cyp);
+                        vcf_save(k, vsup.data() + vper * k, vok.data() + vper * k, &typed[k]->cyp);
+                    }
                 } else for (uint32_t k : on) {
                     // the shared pass failed: sample by sample, and only the samples whose own pass fails are failed (alone in the pass: that failure is its own)
                     CypLane* L = &typed[k]->cyp;
                     if (on.size() > 1) rc = support_with_lists(lists, want_ins, want_haps, SP_CYP_MAXCONS, [&](sp_pileup_ins* p, uint64_t room, uint64_t* got, sp_support_hap* hp, uint64_t hroom, uint64_t* hgot, sp_support_hap_head* hd) {
-                        return sp_cyp_consensus_support_hap(h->ctx2, sets[k], &calls[k], cons.data() + cons_block * k, cons_cap, mappings[k].data(), mappings[k].size(), off.data(), cols.data(), n_cols, sm.data(), p, room, got, hp, hroom, hgot, hd); });
+                        const uint64_t moff1[2] = { 0, mappings[k].size() };
+                        const CypVariantIn vin1 = { &pr, &rv[k], SP_CYP_VCF_FLANK, vsup.data(), vok.data() };
+                        return spi_cyp_support_cohort(h->ctx2, 1, &sets[k], &calls[k], cons.data() + cons_block * k, cons_cap, mappings[k].data(), moff1, off.data(), cols_out, n_cols, sm.data(), p, room, got, hp, hroom, hgot, hd,
+                                                      want_vcf ? &vin1 : nullptr); });
                     if (rc != SP_OK) { L->rc = rc; L->err = "sp_cyp_consensus_support: " + opt(sp_last_error(h->ctx2)); continue; }
-                    cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data(), cols.data(), sm.data(), lists, 0, typed[k]->debug, L);
+                    if (want_json) cyp_support_save(calls[k], cons.data() + cons_block * k, cons_cap, off.data(), cols.data(), sm.data(), lists, 0, typed[k]->debug, L);
+                    vcf_save(k, on.size() > 1 ? vsup.data() : vsup.data() + vper * k, on.size() > 1 ? vok.data() : vok.data() + vper * k, L);
                 }
             }
         }
@@ -1184,6 +1207,12 @@ int32_t sp_starphase_set_consensus_support(sp_starphase* h, int32_t on) {
     h->consensus_support = on ? 1 : 0;
     return SP_OK;
 }
+int32_t sp_starphase_set_cyp_vcf(sp_starphase* h, int32_t on) {
+    if (!h) return SP_ERR_INVALID_ARG;
+    h->cyp_vcf = on ? 1 : 0;
+    return SP_OK;
+}
+
 int32_t sp_starphase_set_cyp_consensus_support(sp_starphase* h, int32_t on) {
     if (!h) return SP_ERR_INVALID_ARG;
     h->cyp_consensus_support = on ? 1 : 0;

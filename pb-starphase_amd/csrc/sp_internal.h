@@ -246,12 +246,23 @@ __host__ __device__ inline bool pu_contested(uint32_t depth, uint32_t eq, uint32
 // map, pileup, summary) in the context's profile, and the first map launch counts the pairs it attempts (max_ed >= 0) when count_attempted is set, every pair of the
 // slice otherwise.  HapOut: where the haplotype list goes (heads: one per target of B).  ins_runs: 0 (the pass sizes its run buffer itself).
 struct HapOut { sp_support_hap* haps; uint64_t cap; uint64_t* n_haps; sp_support_hap_head* heads; };
+// WinIn: the windows of sp_align_pileup_windows_batch (win_offset: one entry per target of B and one more) and where their counts go
+struct WinIn { const uint64_t* win_offset; const sp_window* windows; sp_window_support* out; };
 int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
                          const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
                          const std::string& who, const char* const prof[4], bool count_attempted,
-                         sp_pileup_ins* ins = nullptr, uint64_t ins_cap = 0, uint64_t* n_ins = nullptr, uint64_t ins_runs = 0, const HapOut* hap = nullptr);
+                         sp_pileup_ins* ins = nullptr, uint64_t ins_cap = 0, uint64_t* n_ins = nullptr, uint64_t ins_runs = 0, const HapOut* hap = nullptr, const WinIn* win = nullptr);
+// sp_cyp_db.hip, for sp_cyp_vcf.hip: the chromosome name the database was made with
+const char* spi_cyp_db_chrom(const sp_cyp_db* db);
 // sp_cyp.hip, for sp_support.hip: the label of consensus h of a call, as the debug files name a region (RegionLabel::full_allele)
 std::string spi_cyp_region_label(const sp_cyp_call* call, int32_t h);
+// sp_support.hip, for sp_diplotype.hip: sp_cyp_consensus_support_cohort_hap that also makes the variant support of sp_cyp_variant_support_cohort (vin; NULL: without) in
+// the same member pass.  support / valid: n_samples * SP_CYP_MAXCONS * n_variants entries.
+struct CypVariantIn { const sp_cyp_problem* problem; const sp_cyp_region_variants* rv; uint32_t flank; sp_window_support* support; int32_t* valid; };
+int32_t spi_cyp_support_cohort(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
+                               const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                               sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
+                               sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads, const CypVariantIn* vin);
 // sp_cyp.hip, for sp_diplotype.hip: sp_cyp_diplotype_mappings with the list in a vector the library sizes
 int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
                                    sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings);

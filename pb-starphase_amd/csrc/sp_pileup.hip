@@ -151,6 +151,95 @@ __global__ __launch_bounds__(PU_WAVES * SP_WAVE) void pileup_rows_kernel(SeqSetV
     for (int i = threadIdx.x; i < (c1 - c0) * 8; i += PU_WAVES * SP_WAVE) dst[i] = lds[(i & 7) * PU_STRIDE + (i >> 3)];
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// Window support (sp_window_support; contract: include/starphase_hip.h, design: DESIGN.md section 7.2).  One workgroup per (target, chunk of WIN_CHUNK windows); lane l of
+// every wave keeps windows l, l + 64, ... of the chunk and their counters in registers, the waves take the target's pairs of the slice in turn (order / boff as
+// pileup_rows_kernel reads them).  A pair is walked once, and only when it spans one of the wave's windows: the defects of its op row go into the wave's part of LDS in
+// doubled coordinates -- column c is [2 c, 2 c + 1), the junction behind column j is [2 j + 1, 2 j + 2), so window [s, e) is [2 s, 2 e - 1): its columns and its INTERIOR
+// junctions --, sorted and disjoint by construction (ops follow one another on the target, an 'I' lies between two of them).  A window is inexact when the first defect
+// that ends behind its start begins in front of its end.  A row with more defects than the wave's part holds is decided in rounds.  The waves' counters meet in LDS,
+// thread i stores window i (slice > 0: on top of what the slices before it left).  No atomics.
+// ------------------------------------------------------------------------------------------------------------------------------
+struct WinChunk { uint32_t target, w0; };
+constexpr int WIN_CHUNK = SP_WINDOW_CHUNK, WIN_WAVES = SP_WINDOW_WAVES, WIN_DEFECTS = SP_WINDOW_DEFECTS, WIN_PER_LANE = WIN_CHUNK / SP_WAVE;
+static_assert(WIN_CHUNK % SP_WAVE == 0 && WIN_PER_LANE <= 32 && WIN_DEFECTS >= 2 * SP_WAVE && WIN_CHUNK <= WIN_WAVES * SP_WAVE, "a lane's windows are bits of one word; a round takes 64 ops; one thread stores one window");
+
+// what one wave wrote to LDS is read by its other lanes: the compiler must not move the accesses across, the hardware keeps a wave's LDS accesses in order
+__device__ __forceinline__ void win_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+
+__global__ __launch_bounds__(WIN_WAVES * SP_WAVE) void window_kernel(const sp_affine_aln* __restrict__ aln, const uint32_t* __restrict__ n_cigar, const uint64_t* __restrict__ op_off,
+                                                                     const uint32_t* __restrict__ ops, const uint32_t* __restrict__ order, const uint32_t* __restrict__ boff,
+                                                                     uint32_t n_slices, uint32_t slice, const WinChunk* __restrict__ chunks, const uint32_t* __restrict__ win_off,
+                                                                     const sp_window* __restrict__ windows, sp_window_support* __restrict__ out) {
+    __shared__ int2 s_def[WIN_WAVES][WIN_DEFECTS];
+    __shared__ uint32_t s_cnt[WIN_WAVES][3][WIN_CHUNK];
+    const WinChunk ch = chunks[blockIdx.x];
+    const uint32_t k_lo = boff[(size_t)ch.target * (n_slices + 1) + slice], k_hi = boff[(size_t)ch.target * (n_slices + 1) + slice + 1];
+    if (slice > 0 && k_lo == k_hi) return;                                              // (uniform over the workgroup)
+    const uint32_t w_base = win_off[ch.target] + ch.w0, n_w = min((uint32_t)WIN_CHUNK, win_off[ch.target + 1] - w_base);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int w_lo[WIN_PER_LANE], w_hi[WIN_PER_LANE];                                         // a lane's windows (a place behind n_w: the empty window, which nothing counts)
+    uint32_t c_span[WIN_PER_LANE], c_exact[WIN_PER_LANE], c_part[WIN_PER_LANE];
+    int cmin = 0x7FFFFFFF, cmax = 0;                                                    // the columns the chunk's windows lie in: [cmin, cmax)
+#pragma unroll
+    for (int j = 0; j < WIN_PER_LANE; ++j) {
+        const uint32_t i = (uint32_t)(lane + j * SP_WAVE);
+        w_lo[j] = 0; w_hi[j] = 0; c_span[j] = 0; c_exact[j] = 0; c_part[j] = 0;
+        if (i < n_w) { const sp_window w = windows[w_base + i]; w_lo[j] = (int)w.start; w_hi[j] = (int)w.end; cmin = min(cmin, w_lo[j]); cmax = max(cmax, w_hi[j]); }
+    }
+#pragma unroll
+    for (int d = 1; d < SP_WAVE; d <<= 1) { cmin = min(cmin, __shfl_xor(cmin, d)); cmax = max(cmax, __shfl_xor(cmax, d)); }
+    int2* def = s_def[wave];
+    for (uint32_t k = k_lo + wave; k < k_hi; k += WIN_WAVES) {
+        const uint32_t p = order[k], n_ops = n_cigar[p];
+        const uint64_t off = op_off[p];
+        if (!ap_counted(n_ops, off, aln + p)) continue;                                 // (everything up to the walk is wave-uniform)
+        const sp_affine_aln g = aln[p];
+        if (g.b_end <= cmin || g.b_start >= cmax) continue;                             // the pair meets none of the chunk's windows
+        uint32_t spans = 0, bad = 0;                                                    // bit j: the pair spans the lane's window j / a defect lies in it
+#pragma unroll
+        for (int j = 0; j < WIN_PER_LANE; ++j) if (w_lo[j] < w_hi[j] && g.b_start <= w_lo[j] && w_hi[j] <= g.b_end) spans |= 1u << j;
+        if (__ballot(spans != 0u)) {
+            int n_def = 0;                                                              // defects in the wave's part (wave-uniform)
+            auto decide = [&]() {                                                       // the lane's spanned windows against the defects held
+                win_wave_sync();
+#pragma unroll
+                for (int j = 0; j < WIN_PER_LANE; ++j) {
+                    if (!((spans & ~bad) >> j & 1u)) continue;
+                    const int L = 2 * w_lo[j], H = 2 * w_hi[j] - 1;
+                    int lo = 0, hi = n_def;
+                    while (lo < hi) { const int mid = (lo + hi) >> 1; if (def[mid].y <= L) lo = mid + 1; else hi = mid; }
+                    if (lo < n_def && def[lo].x < H) bad |= 1u << j;
+                }
+                win_wave_sync();
+            };
+            pu_walk(ops + off, n_ops, g.b_start, g.a_start, lane, cmax, [&](bool live, uint32_t op, int len, int t0, int) {
+                if (n_def + SP_WAVE > WIN_DEFECTS) { decide(); n_def = 0; }
+                const bool is_def = live && (op == 8u || op == 2u || op == 1u);
+                const unsigned long long vote = __ballot(is_def);
+                if (is_def) def[n_def + __popcll(vote & ((1ull << lane) - 1ull))] = op == 1u ? make_int2(2 * t0 - 1, 2 * t0) : make_int2(2 * t0, 2 * (t0 + len) - 1);
+                n_def += __popcll(vote);
+            });
+            decide();
+        }
+#pragma unroll
+        for (int j = 0; j < WIN_PER_LANE; ++j) {
+            const bool sp = (spans >> j & 1u) != 0u, meets = w_lo[j] < w_hi[j] && g.b_start < w_hi[j] && w_lo[j] < g.b_end;
+            c_span[j] += sp ? 1u : 0u; c_exact[j] += (sp && !(bad >> j & 1u)) ? 1u : 0u; c_part[j] += (meets && !sp) ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < WIN_PER_LANE; ++j) { s_cnt[wave][0][lane + j * SP_WAVE] = c_span[j]; s_cnt[wave][1][lane + j * SP_WAVE] = c_exact[j]; s_cnt[wave][2][lane + j * SP_WAVE] = c_part[j]; }
+    __syncthreads();
+    if (threadIdx.x < n_w) {
+        sp_window_support r = { 0, 0, 0, 0 };
+        if (slice > 0) r = out[w_base + threadIdx.x];
+        for (int w = 0; w < WIN_WAVES; ++w) { r.span += s_cnt[w][0][threadIdx.x]; r.exact += s_cnt[w][1][threadIdx.x]; r.partial += s_cnt[w][2][threadIdx.x]; }
+        r.reserved_ = 0;
+        out[w_base + threadIdx.x] = r;
+    }
+}
+
 // what the host has to know about a slice before it piles it up: status[0] = a walk got lost, status[1] = an alignment with more runs than a row keeps
 __global__ void ap_status_kernel(const sp_affine_aln* __restrict__ aln, const uint32_t* __restrict__ n_cigar, const uint64_t* __restrict__ op_off, uint32_t n, uint32_t* __restrict__ status) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -777,15 +866,16 @@ struct HostRows {
 };
 
 static int32_t stage_rows(sp_ctx* ctx, const sp_seqset* B, const sp_pair* pairs, uint32_t n, const sp_affine_aln* aln, const uint32_t* cigar, uint32_t cigar_stride,
-                          const uint32_t* n_cigar, const uint64_t* col_offset, uint64_t total_ops, bool with_table, HostRows* hr) {
+                          const uint32_t* n_cigar, const uint64_t* col_offset, uint64_t total_ops, bool with_table, HostRows* hr, bool order_only = false) {
     const uint32_t n_t = B->n;
+    const bool with_order = with_table || order_only;                                     // (order_only: the order and the offsets without tiles and table -- the window kernel)
     hr->n_tiles = 0; hr->table = nullptr;
     if (with_table) {
         const int32_t rc = pu_count_tiles(ctx, "pileup", B, &hr->n_tiles);
         if (rc != SP_OK) return rc;
     }
     (void)hipSetDevice(ctx->device);
-    const size_t n_ord = with_table ? n : 0, n_boff = with_table ? (size_t)n_t * 2 + 1 : 0;
+    const size_t n_ord = with_order ? n : 0, n_boff = with_order ? (size_t)n_t * 2 + 1 : 0;
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t at_pairs = 0, at_aln = up16(at_pairs + sizeof(sp_pair) * (size_t)n), at_nc = up16(at_aln + sizeof(sp_affine_aln) * (size_t)n), at_off = up16(at_nc + 4 * (size_t)n),
                  at_order = up16(at_off + 8 * (size_t)n), at_boff = up16(at_order + 4 * n_ord), at_tiles = up16(at_boff + 4 * n_boff),
@@ -807,7 +897,7 @@ static int32_t stage_rows(sp_ctx* ctx, const sp_seqset* B, const sp_pair* pairs,
         std::memcpy(hops + op_at, cigar + i * (size_t)cigar_stride, 4 * (size_t)n_cigar[i]);
         op_at += n_cigar[i];
     }
-    if (with_table) {
+    if (with_order) {
         // target t's pairs are order[boff[2 t] .. boff[2 t + 1]), in the order given (pileup_rows_kernel with n_slices = 1)
         uint32_t* boff = (uint32_t*)(h_in + at_boff); uint32_t* hord = (uint32_t*)(h_in + at_order);
         std::memset(boff, 0, 4 * n_boff);
@@ -817,7 +907,7 @@ static int32_t stage_rows(sp_ctx* ctx, const sp_seqset* B, const sp_pair* pairs,
         std::vector<uint32_t> at(n_t);
         for (uint32_t t = 0; t < n_t; ++t) at[t] = boff[(size_t)t * 2];
         for (uint32_t i = 0; i < n; ++i) hord[at[pairs[i].b]++] = i;
-        pu_fill_tiles(B, (PuTile*)(h_in + at_tiles));
+        if (with_table) pu_fill_tiles(B, (PuTile*)(h_in + at_tiles));
     }
     SP_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     hr->pairs = (const sp_pair*)(d_in + at_pairs); hr->aln = (const sp_affine_aln*)(d_in + at_aln); hr->nc = (const uint32_t*)(d_in + at_nc); hr->off = (const uint64_t*)(d_in + at_off);
@@ -869,9 +959,85 @@ static int32_t hap_run(sp_ctx* ctx, const std::string& who, const sp_seqset* A, 
     return SP_OK;
 }
 
+// ---- the host side of window support: the windows checked (before anything is launched), the chunk list, their part of a staging block, the launch of one slice
+struct WinStage { uint64_t n_w = 0, n_chunks = 0; size_t at_off = 0, at_chunks = 0, at_wins = 0, end = 0; };
+
+// from: where the part begins in the staging block (16-byte aligned); without windows the part is empty and ws->end == from
+static int32_t win_plan(sp_ctx* ctx, const std::string& who, const sp_seqset* B, const WinIn* win, size_t from, WinStage* ws) {
+    *ws = WinStage(); ws->at_off = ws->at_chunks = ws->at_wins = ws->end = from;
+    if (!win) return SP_OK;
+    const uint32_t n_t = B->n;
+    if (!win->win_offset || win->win_offset[0] != 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": win_offset must begin at 0");
+    for (uint32_t t = 0; t < n_t; ++t) if (win->win_offset[t + 1] < win->win_offset[t]) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": win_offset does not ascend");
+    ws->n_w = win->win_offset[n_t];
+    if (ws->n_w > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": too many windows");
+    if (ws->n_w && (!win->windows || !win->out)) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": null argument");
+    for (uint32_t t = 0; t < n_t; ++t) {
+        for (uint64_t i = win->win_offset[t]; i < win->win_offset[t + 1]; ++i)
+            if (win->windows[i].start >= win->windows[i].end || win->windows[i].end > (uint32_t)B->h_len[t])
+                return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": window " + std::to_string(i) + " is empty or leaves its target");
+        ws->n_chunks += (win->win_offset[t + 1] - win->win_offset[t] + WIN_CHUNK - 1) / WIN_CHUNK;
+    }
+    if (ws->n_w == 0) return SP_OK;
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    ws->at_off = from; ws->at_chunks = up16(ws->at_off + 4 * ((size_t)n_t + 1)); ws->at_wins = up16(ws->at_chunks + sizeof(WinChunk) * (size_t)ws->n_chunks);
+    ws->end = up16(ws->at_wins + sizeof(sp_window) * (size_t)ws->n_w);
+    return SP_OK;
+}
+
+static void win_fill(const WinStage& ws, uint8_t* h_in, const sp_seqset* B, const WinIn* win) {
+    if (ws.n_w == 0) return;
+    uint32_t* off = (uint32_t*)(h_in + ws.at_off); WinChunk* ch = (WinChunk*)(h_in + ws.at_chunks);
+    for (uint32_t t = 0; t <= B->n; ++t) off[t] = (uint32_t)win->win_offset[t];
+    for (uint32_t t = 0; t < B->n; ++t) for (uint32_t w0 = 0; w0 < off[t + 1] - off[t]; w0 += WIN_CHUNK) *ch++ = WinChunk{ t, w0 };
+    std::memcpy(h_in + ws.at_wins, win->windows, sizeof(sp_window) * (size_t)ws.n_w);
+}
+
+// one slice's pairs under every chunk; d_in: the staging block on the device
+static int32_t win_launch(sp_ctx* ctx, const std::string& who, const WinStage& ws, const uint8_t* d_in, const sp_affine_aln* d_aln, const uint32_t* d_nc, const uint64_t* d_op_off,
+                          const uint32_t* d_ops, const uint32_t* d_order, const uint32_t* d_boff, uint32_t n_slices, uint32_t slice, sp_window_support* d_out) {
+    if (ws.n_chunks == 0) return SP_OK;
+    ProfScope ps(ctx, "pileup_windows", ws.n_w);
+    hipLaunchKernelGGL(window_kernel, dim3((unsigned)ws.n_chunks), dim3(WIN_WAVES * SP_WAVE), 0, ctx->stream, d_aln, d_nc, d_op_off, d_ops, d_order, d_boff, n_slices, slice,
+                       (const WinChunk*)(d_in + ws.at_chunks), (const uint32_t*)(d_in + ws.at_off), (const sp_window*)(d_in + ws.at_wins), d_out);
+    if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": window launch failed");
+    return SP_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int32_t sp_pileup_windows_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
+                                const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset,
+                                const uint64_t* win_offset, const sp_window* windows, sp_window_support* out) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (!A || !B || !col_offset || !win_offset || (n_pairs && (!pairs || !aln || !n_cigar))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: null argument");
+    if (n_pairs > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_INVALID_ARG, "pileup: too many pairs");
+    int32_t rc = check_col_offset(ctx, "pileup", B, col_offset);
+    if (rc != SP_OK) return rc;
+    uint64_t total_ops = 0, n_ins_ops = 0;
+    rc = pileup_check_rows(ctx, A, B, pairs, n_pairs, aln, cigar, cigar_stride, n_cigar, &total_ops, &n_ins_ops);
+    if (rc != SP_OK) return rc;
+    const WinIn win = { win_offset, windows, out };
+    WinStage ws;
+    rc = win_plan(ctx, "pileup", B, &win, 0, &ws);
+    if (rc != SP_OK || ws.n_w == 0) return rc;
+    HostRows hr;
+    rc = stage_rows(ctx, B, pairs, (uint32_t)n_pairs, aln, cigar, cigar_stride, n_cigar, col_offset, total_ops, false, &hr, true);
+    if (rc != SP_OK) return rc;
+    uint8_t* h_w = (uint8_t*)sp_host_pool(ctx, "pileup_win_in", ws.end);
+    uint8_t* d_w = (uint8_t*)sp_pool(ctx, "pileup_win_in", ws.end);
+    sp_window_support* d_out = (sp_window_support*)sp_pool(ctx, "pileup_win_out", (size_t)ws.n_w * sizeof(sp_window_support));
+    if (!h_w || !d_w || !d_out) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "pileup buffers");
+    win_fill(ws, h_w, B, &win);
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(d_w, h_w, ws.end, hipMemcpyHostToDevice, ctx->stream));
+    rc = win_launch(ctx, "pileup", ws, d_w, hr.aln, hr.nc, hr.off, hr.ops, hr.order, hr.boff, 1, 0, d_out);
+    if (rc != SP_OK) return rc;
+    SP_HIP_CHECK(ctx, hipMemcpyAsync(out, d_out, (size_t)ws.n_w * sizeof(sp_window_support), hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return SP_OK;
+}
 
 int32_t sp_pileup_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_aln* aln,
                         const uint32_t* cigar, uint32_t cigar_stride, const uint32_t* n_cigar, const uint64_t* col_offset, sp_pileup_col* out) {
@@ -991,7 +1157,8 @@ int32_t sp_pileup_hap_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B,
 // context's profile, and the first map launch counts the pairs it attempts (max_ed >= 0) when count_attempted is set, every pair of the slice otherwise.
 int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
                          const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
-                         const std::string& who, const char* const prof[4], bool count_attempted, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins, uint64_t ins_runs, const HapOut* hap) {
+                         const std::string& who, const char* const prof[4], bool count_attempted, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins, uint64_t ins_runs, const HapOut* hap,
+                         const WinIn* win) {
     if (!A || !B || !opts || !col_offset || (n_pairs && !pairs) || (ins && !n_ins) || (hap && (!hap->n_haps || !hap->heads))) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": null argument");
     if ((band != 64 && band != 256) || (retry_band != 0 && retry_band != 256) || (retry_band != 0 && band != 64))
         return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": band must be 64 or 256, retry_band 0 or (with band 64) 256");
@@ -1007,11 +1174,14 @@ int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, co
         if (pairs[i].a >= A->n || pairs[i].b >= B->n) return sp_fail(ctx, SP_ERR_INVALID_ARG, who + ": index out of range");
         ++boff[(size_t)pairs[i].b * (n_slices + 1) + i / SP_ALIGN_PILEUP_SLICE + 1];
     }
+    if (win && !win->windows) win = nullptr;                                                          // (no windows: the call without them)
+    WinStage ws;                                                                                      // the windows are checked before anything is launched or written
+    if (win) { const int32_t rc = win_plan(ctx, who, B, win, 0, &ws); if (rc != SP_OK) return rc; if (ws.n_w == 0) win = nullptr; }
     if (ins) *n_ins = 0;
     if (hap) *hap->n_haps = 0;
     if (n_pairs == 0 && n_t == 0) return SP_OK;
     const bool want_table = (cols || summaries || hap) && n_t > 0;                                    // (the haplotype list reads the finished table)
-    if (!aln && !want_table && !ins) return SP_OK;
+    if (!aln && !want_table && !ins && !win) return SP_OK;
     // boff[t * (S + 1) + s + 1] holds the count of (t, s): into running offsets; entry t * (S + 1) is where target t begins = where target t - 1 ended
     {
         uint32_t run = 0;
@@ -1028,7 +1198,9 @@ int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, co
     // ---- one staging block, one copy: the pair list as given, the order, the offsets, tiles, column offsets, member counts
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t at_pairs = 0, at_order = up16(at_pairs + sizeof(sp_pair) * (size_t)n), at_boff = up16(at_order + 4 * (size_t)n), at_tiles = up16(at_boff + 4 * boff.size()),
-                 at_cols = up16(at_tiles + sizeof(PuTile) * (size_t)n_tiles), at_mem = up16(at_cols + 8 * ((size_t)n_t + 1)), in_bytes = up16(at_mem + 4 * (size_t)n_t) + 16;
+                 at_cols = up16(at_tiles + sizeof(PuTile) * (size_t)n_tiles), at_mem = up16(at_cols + 8 * ((size_t)n_t + 1));
+    if (win) { const int32_t rc = win_plan(ctx, who, B, win, up16(at_mem + 4 * (size_t)n_t), &ws); if (rc != SP_OK) return rc; }      // (the windows' part behind the member counts)
+    const size_t in_bytes = (win ? ws.end : up16(at_mem + 4 * (size_t)n_t)) + 16;
     uint8_t* h_in = (uint8_t*)sp_host_pool(ctx, "appile_in", in_bytes);
     uint64_t* h_st = (uint64_t*)sp_host_pool(ctx, "appile_st", 16);
     uint8_t* d_in = (uint8_t*)sp_pool(ctx, "appile_in", in_bytes);
@@ -1040,6 +1212,8 @@ int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, co
     uint32_t* d_band = (retry_band || band_used) ? (uint32_t*)sp_pool(ctx, "appile_band", std::max<size_t>(16, (size_t)n * 4)) : nullptr;
     uint32_t* d_table = want_table ? (uint32_t*)sp_pool(ctx, "appile_out", std::max<size_t>(16, n_cols * sizeof(sp_pileup_col))) : nullptr;
     sp_support_summary* d_sum = summaries && n_t ? (sp_support_summary*)sp_pool(ctx, "appile_sum", (size_t)n_t * sizeof(sp_support_summary)) : nullptr;
+    sp_window_support* d_win = win ? (sp_window_support*)sp_pool(ctx, "appile_win", (size_t)ws.n_w * sizeof(sp_window_support)) : nullptr;
+    if (win && !d_win) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, who + " buffers");
     if (!h_in || !h_st || !d_in || !d_aln || !d_nc || !d_off || (retry_band && !d_retry) || ((retry_band || band_used) && !d_band) || (want_table && !d_table) || (summaries && n_t && !d_sum)) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, who + " buffers");
     unsigned long long* d_cur = (unsigned long long*)(d_off + n); uint32_t* d_status = (uint32_t*)(d_off + n + 1); uint32_t* d_n_retry = (uint32_t*)(d_off + n + 2);
     {
@@ -1052,6 +1226,7 @@ int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, co
         std::memcpy(h_in + at_cols, col_offset, 8 * ((size_t)n_t + 1));
         if (n_members && n_t) std::memcpy(h_in + at_mem, n_members, 4 * (size_t)n_t);
         if (want_table) pu_fill_tiles(B, (PuTile*)(h_in + at_tiles));
+        if (win) win_fill(ws, h_in, B, win);
     }
     SP_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     const sp_pair* d_pairs = (const sp_pair*)(d_in + at_pairs);
@@ -1131,6 +1306,10 @@ int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, co
                                d_order, d_boff, n_slices, s2, (const PuTile*)(d_in + at_tiles), (const uint64_t*)(d_in + at_cols), d_table);
             if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, who + ": pileup launch failed");
         }
+        if (win) {
+            const int32_t rc = win_launch(ctx, who, ws, d_in, d_aln, d_nc, d_off, d_ops, d_order, d_boff, n_slices, s2, d_win);
+            if (rc != SP_OK) return rc;
+        }
         if (ins && m > 0) {
             const int32_t rc = ins_collect(ctx, who, ip, A, B, d_pairs + p0, d_aln + p0, d_nc + p0, d_off + p0, d_ops, m, p0, (const uint64_t*)(d_in + at_cols));
             if (rc != SP_OK) return rc;
@@ -1151,6 +1330,7 @@ int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, co
     if (aln && n) SP_HIP_CHECK(ctx, hipMemcpyAsync(aln, d_aln, (size_t)n * sizeof(sp_affine_aln), hipMemcpyDeviceToHost, ctx->stream));
     if (cols && n_cols) SP_HIP_CHECK(ctx, hipMemcpyAsync(cols, d_table, n_cols * sizeof(sp_pileup_col), hipMemcpyDeviceToHost, ctx->stream));
     if (d_sum) SP_HIP_CHECK(ctx, hipMemcpyAsync(summaries, d_sum, (size_t)n_t * sizeof(sp_support_summary), hipMemcpyDeviceToHost, ctx->stream));
+    if (win) SP_HIP_CHECK(ctx, hipMemcpyAsync(win->out, d_win, (size_t)ws.n_w * sizeof(sp_window_support), hipMemcpyDeviceToHost, ctx->stream));
     SP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     int32_t rc_ins = SP_OK;
     if (ins) {
@@ -1161,7 +1341,7 @@ int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, co
         if (rc_ins != SP_OK && !(hap && rc_ins == SP_ERR_CAPACITY && *n_ins > ins_cap)) return rc_ins;      // (with the other list asked for, that one is still made)
         if (grow) {
             if (ins_runs) return sp_fail(ctx, SP_ERR_HIP, who + ": the run buffer did not hold a second run");
-            return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, who, prof, count_attempted, ins, ins_cap, n_ins, grow, hap);
+            return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, who, prof, count_attempted, ins, ins_cap, n_ins, grow, hap, win);
         }
     }
     if (hap) {
@@ -1174,14 +1354,27 @@ int32_t align_pileup_run(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, co
 
 extern "C" {
 
+static const char* const AP_PROF[4] = { "align_pileup_map", "align_pileup_map_retry", "align_pileup_pile", "align_pileup_summary" };
+
+// sp_align_pileup_band_batch with windows: the same path, no list
+int32_t sp_align_pileup_windows_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
+                                      const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
+                                      const uint64_t* win_offset, const sp_window* windows, sp_window_support* win_out) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (windows && !win_offset) return sp_fail(ctx, SP_ERR_INVALID_ARG, "align_pileup: null argument");
+    const WinIn win = { win_offset, windows, win_out };
+    return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, "align_pileup", AP_PROF, false, nullptr, 0, nullptr, 0,
+                            nullptr, windows ? &win : nullptr);
+}
+
 int32_t sp_align_pileup_hap_batch(sp_ctx* ctx, const sp_seqset* A, const sp_seqset* B, const sp_pair* pairs, uint64_t n_pairs, const sp_affine_opts* opts, int32_t band, int32_t retry_band,
                                   const uint64_t* col_offset, sp_affine_aln* aln, sp_pileup_col* cols, sp_support_summary* summaries, const uint32_t* n_members, uint32_t* band_used,
                                   sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins, sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
     if (!ctx) return SP_ERR_INVALID_ARG;
-    static const char* const prof[4] = { "align_pileup_map", "align_pileup_map_retry", "align_pileup_pile", "align_pileup_summary" };
+    const char* const* prof = AP_PROF;
     HapOut ho; ho.haps = haps; ho.cap = hap_cap; ho.n_haps = n_haps; ho.heads = heads;
     return align_pileup_run(ctx, A, B, pairs, n_pairs, opts, band, retry_band, col_offset, aln, cols, summaries, n_members, band_used, "align_pileup", prof, false, ins, ins_cap, n_ins, 0,
-                            haps ? &ho : nullptr);
+                            haps ? &ho : nullptr, nullptr);
 }
 
 // the entries without one list or both: the same path, the list's arguments NULL

@@ -6,6 +6,7 @@
 #include "sp_json.h"
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <numeric>
 
@@ -147,6 +148,9 @@ struct SupportPass {
     std::vector<int32_t> target_of;                                           // slot -> target, -1: none
     std::string tblob, qblob; std::vector<uint64_t> toff{0}, qoff{0};         // the targets' and the members' bases; toff is the table's col_offset as well
     std::vector<uint32_t> m_target, members_of; std::vector<uint64_t> m_id;
+    // window support (optional): before_pass is called with the target set once it is on the device and fills woff (one entry per target and one more) and wins; the
+    // member pass then counts them into wout -- the same pass that makes the table
+    std::function<int32_t(const sp_seqset*)> before_pass; std::vector<uint64_t> woff; std::vector<sp_window> wins; std::vector<sp_window_support> wout;
 
     SupportPass(sp_ctx* c, const SupportRules& r) : ctx(c), R(r) {}
     int32_t fail(int32_t code, const std::string& what) const { return sp_fail(ctx, code, std::string(R.who) + ": " + what); }
@@ -194,6 +198,9 @@ struct SupportPass {
         sp_seqset T, Q;
         int32_t rc = sp_seqset_make_small(ctx, R.set_t, tblob.data(), toff.data(), n_t, true, &T);
         if (rc != SP_OK) return rc;
+        if (before_pass) { rc = before_pass(&T); if (rc != SP_OK) return rc; }
+        wout.assign(wins.size(), sp_window_support{});
+        const WinIn wi = { woff.data(), wins.data(), wout.data() };
         std::vector<sp_pair> pairs(n_m);
         if (n_m) {
             rc = sp_seqset_make_small(ctx, R.set_q, qblob.data(), qoff.data(), n_m, false, &Q);
@@ -211,7 +218,7 @@ struct SupportPass {
             const sp_affine_opts ao = { 1, 4, 6, 2, 26, 1, 1 };
             const HapOut ho = { haps, hap_cap, n_haps, t_heads.data() };
             rc = align_pileup_run(ctx, &Q, &T, pairs.data(), n_m, &ao, 64, R.retry_band, toff.data(), nullptr, cols ? table.data() : nullptr, sums.data(), members_of.data(), nullptr,
-                                  R.pass_who, R.prof, R.count_attempted, ins, ins_cap, n_ins, 0, haps ? &ho : nullptr);
+                                  R.pass_who, R.prof, R.count_attempted, ins, ins_cap, n_ins, 0, haps ? &ho : nullptr, wins.empty() ? nullptr : &wi);
             if (rc != SP_OK && !(rc == SP_ERR_CAPACITY && ((ins && *n_ins > ins_cap) || (haps && *n_haps > hap_cap)))) return rc;
         } else for (uint32_t t = 0; t < n_t; ++t) sp_support_summarize(table.data() + toff[t], (uint32_t)(toff[t + 1] - toff[t]), 0, 0, &sums[t]);
         for (uint64_t x = 0; x < n_slots; ++x) {
@@ -244,6 +251,11 @@ struct SupportPass {
         return rc;
     }
 };
+
+int32_t cyp_support_cohort_fill(SupportPass& P, sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
+                                const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                                sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
+                                sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads);      // (the CYP2D6 drivers' slots and members; below)
 
 // a single call's status behind its cohort form: a list that did not fit still leaves everything else to hand on
 bool only_a_list_short(int32_t rc, const sp_pileup_ins* ins, const uint64_t* n_ins, uint64_t ins_cap, const sp_support_hap* haps, const uint64_t* n_haps, uint64_t hap_cap) {
@@ -445,12 +457,111 @@ int32_t sp_hla_consensus_support(sp_ctx* ctx, const sp_hla_db* db, uint32_t gene
 // The driver's own: slots from calls[i].status / n_consensus (a call that failed owns none), members read from sp_cyp_read_mapping, a read with several regions fetched
 // once per sample.  The members' segments are forward views of the reads as uploaded and the consensuses were built from such segments (the parts of sp_cyp.hip cut
 // every region with sp_make_segments, which has no strand; sp_region_hit carries none): one orientation, no strand handling.
+} // extern "C"
+
+// The cohort pass with everything it can make (declared in sp_internal.h for the whole-sample call).  vin (optional): the variant support of sp_cyp_variant_support_cohort --
+// the windows of the database variants on every typed region, counted by the SAME member pass that makes the table.
+int32_t spi_cyp_support_cohort(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
+                               const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                               sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
+                               sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads, const CypVariantIn* vin) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    SupportPass P(ctx, CYP_RULES);
+    std::vector<uint64_t> win_at;                                        // window -> its place in vin->support
+    if (vin) {
+        if (!vin->problem || !vin->rv || !vin->support || !vin->valid || n_samples == 0) return P.fail(SP_ERR_INVALID_ARG, "null argument");
+        const size_t total = (size_t)n_samples * SP_CYP_MAXCONS * vin->problem->n_variants;
+        std::memset(vin->support, 0, sizeof(sp_window_support) * total);
+        std::memset(vin->valid, 0, sizeof(int32_t) * total);
+        // every typed consensus onto the backbone: one anchor launch for the diagonals, one affine alignment at the map-hifi scores on 256 diagonals; then the rule
+        // of sp_cyp_variant_windows
+        P.before_pass = [&P, &win_at, vin, ctx](const sp_seqset* T) -> int32_t {
+            const sp_cyp_problem* pr = vin->problem;
+            const uint32_t NV = pr->n_variants;
+            P.woff.assign((size_t)T->n + 1, 0);
+            std::vector<uint32_t> tt; std::vector<uint64_t> slot;
+            for (uint64_t x = 0; x < P.n_slots; ++x) if (P.target_of[x] >= 0 && vin->rv[x / SP_CYP_MAXCONS].has_variants[x % SP_CYP_MAXCONS] == 1) { tt.push_back((uint32_t)P.target_of[x]); slot.push_back(x); }
+            if (tt.empty() || NV == 0) return SP_OK;
+            if (!pr->backbone || !pr->var_pos || !pr->var_ref) return P.fail(SP_ERR_INVALID_ARG, "null argument");
+            const uint32_t n = (uint32_t)tt.size(), stride = 4096;
+            const uint64_t boff[2] = { 0, pr->backbone_len };
+            sp_seqset BB;
+            int32_t rc = sp_seqset_make_small(ctx, "cypvar_bb", pr->backbone, boff, 1, false, &BB);
+            if (rc != SP_OK) return rc;
+            std::vector<uint32_t> zero(n, 0), n_cigar(n), cigar((size_t)n * stride), ref_len(NV);
+            std::vector<int32_t> diag(n), votes(n), ok(NV);
+            rc = sp_anchor_batch(ctx, T, &BB, tt.data(), zero.data(), n, diag.data(), votes.data());
+            if (rc != SP_OK) return rc;
+            std::vector<sp_pair> bp(n);
+            for (uint32_t k = 0; k < n; ++k) bp[k] = sp_pair{ tt[k], 0, votes[k] > 0 ? diag[k] : 0, votes[k] > 0 ? 0 : -1 };
+            std::vector<sp_affine_aln> aln(n);
+            const sp_affine_opts ao = { 1, 4, 6, 2, 26, 1, 1 };
+            rc = sp_affine_align_batch(ctx, T, &BB, bp.data(), n, &ao, 256, aln.data(), cigar.data(), stride, n_cigar.data());
+            if (rc != SP_OK) return rc;
+            for (uint32_t v = 0; v < NV; ++v) ref_len[v] = (uint32_t)std::strlen(pr->var_ref[v]);
+            std::vector<sp_window> w(NV);
+            for (uint32_t k = 0; k < n; ++k) {                             // (tt ascends with the slots: the windows come out in target order)
+                if (n_cigar[k] == 0 || n_cigar[k] > stride) continue;        // no alignment onto the backbone (or one of more runs than a row keeps): no windows, SR and CR stay '.'
+                rc = sp_cyp_variant_windows(&aln[k], cigar.data() + (size_t)k * stride, n_cigar[k], NV, pr->var_pos, ref_len.data(), vin->flank, w.data(), ok.data());
+                if (rc != SP_OK) return P.fail(rc, "the alignment onto the backbone does not consume its spans");
+                for (uint32_t v = 0; v < NV; ++v) if (ok[v]) { P.wins.push_back(w[v]); win_at.push_back(slot[k] * NV + v); ++P.woff[(size_t)tt[k] + 1]; }
+            }
+            for (uint32_t t = 0; t < T->n; ++t) P.woff[t + 1] += P.woff[t];
+            return SP_OK;
+        };
+    }
+    const int32_t rc_pass = cyp_support_cohort_fill(P, ctx, n_samples, reads, calls, consensus, cons_cap, mappings, mapping_off, col_offset, cols, cols_cap, summaries, ins, ins_cap, n_ins,
+                                                    haps, hap_cap, n_haps, heads);
+    if (vin && (rc_pass == SP_OK || rc_pass == SP_ERR_CAPACITY) && P.wout.size() == win_at.size())
+        for (size_t j = 0; j < win_at.size(); ++j) { vin->support[win_at[j]] = P.wout[j]; vin->valid[win_at[j]] = 1; }
+    return rc_pass;
+}
+
+extern "C" {
+
 int32_t sp_cyp_consensus_support_cohort_hap(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
                                             const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
                                             sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
                                             sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
+    return spi_cyp_support_cohort(ctx, n_samples, reads, calls, consensus, cons_cap, mappings, mapping_off, col_offset, cols, cols_cap, summaries, ins, ins_cap, n_ins, haps, hap_cap, n_haps, heads, nullptr);
+}
+
+// the variant support of a cohort: the pass above with the windows attached; the table's outputs are optional (col_offset == NULL: only support / support_valid are made)
+int32_t sp_cyp_variant_support_cohort(sp_ctx* ctx, const sp_cyp_problem* problem, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus,
+                                      uint32_t cons_cap, const sp_cyp_region_variants* region_variants, const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint32_t flank,
+                                      sp_window_support* support, int32_t* support_valid, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries) {
     if (!ctx) return SP_ERR_INVALID_ARG;
-    SupportPass P(ctx, CYP_RULES);
+    if (!problem || !region_variants || !support || !support_valid || n_samples == 0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp variant support: null argument");
+    std::vector<uint64_t> off(col_offset ? 0 : (size_t)n_samples * SP_CYP_MAXCONS + 1);
+    std::vector<sp_support_summary> sm(summaries ? 0 : (size_t)n_samples * SP_CYP_MAXCONS);
+    const CypVariantIn vin = { problem, region_variants, flank, support, support_valid };
+    return spi_cyp_support_cohort(ctx, n_samples, reads, calls, consensus, cons_cap, mappings, mapping_off, col_offset ? col_offset : off.data(), col_offset ? cols : nullptr, col_offset ? cols_cap : 0,
+                                  summaries ? summaries : sm.data(), nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, &vin);
+}
+
+int32_t sp_cyp_variant_support(sp_ctx* ctx, const sp_cyp_problem* problem, const sp_seqset* reads, const sp_cyp_call* call, const char* consensus, uint32_t cons_cap,
+                               const sp_cyp_region_variants* region_variants, const sp_cyp_read_mapping* mappings, uint64_t n_mappings, uint32_t flank,
+                               sp_window_support* support, int32_t* support_valid, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap, sp_support_summary* summaries) {
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (!call) return sp_fail(ctx, SP_ERR_INVALID_ARG, "cyp variant support: null argument");
+    const int32_t H = std::min<int32_t>(std::max<int32_t>(call->n_consensus, 0), SP_CYP_MAXCONS);
+    uint64_t off[SP_CYP_MAXCONS + 1] = { 0 }; sp_support_summary sm[SP_CYP_MAXCONS];
+    const uint64_t moff[2] = { 0, n_mappings };
+    const int32_t rc = sp_cyp_variant_support_cohort(ctx, problem, 1, &reads, call, consensus, cons_cap, region_variants, mappings, moff, flank, support, support_valid,
+                                                     col_offset ? off : nullptr, cols, cols_cap, col_offset ? sm : nullptr);
+    if (col_offset) std::memcpy(col_offset, off, sizeof(uint64_t) * ((size_t)H + 1));
+    if (rc == SP_OK && col_offset && summaries) std::memcpy(summaries, sm, sizeof(sp_support_summary) * (size_t)H);
+    return rc;
+}
+
+} // extern "C"
+
+namespace {
+// the member pass of the CYP2D6 drivers: lists, slots, members, run
+int32_t cyp_support_cohort_fill(SupportPass& P, sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
+                                const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
+                                sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
+                                sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads) {
     int32_t rc = P.lists(ins, ins_cap, n_ins, haps, hap_cap, n_haps, heads);
     if (rc != SP_OK) return rc;
     if (!reads || !calls || !mapping_off || !col_offset || !summaries || n_samples == 0) return P.fail(SP_ERR_INVALID_ARG, "null argument");
@@ -488,6 +599,8 @@ int32_t sp_cyp_consensus_support_cohort_hap(sp_ctx* ctx, uint32_t n_samples, con
     }
     return P.run();
 }
+} // namespace
+extern "C" {
 
 int32_t sp_cyp_consensus_support_cohort_ins(sp_ctx* ctx, uint32_t n_samples, const sp_seqset* const* reads, const sp_cyp_call* calls, const char* consensus, uint32_t cons_cap,
                                             const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,

@@ -165,6 +165,14 @@ def _lib():
         "sp_cyp_consensus_support_hap": (_i32, [_vp, _vp, P(ffi.sp_cyp_call), _vp, _u32, P(sp_cyp_read_mapping), _u64, _vp, _vp, _u64, _vp, _vp, _u64, P(_u64), _vp, _u64, P(_u64), _vp]),
         "sp_cyp_consensus_support_cohort_hap": (_i32, [_vp, _u32, _vp, _vp, _vp, _u32, P(sp_cyp_read_mapping), _vp, _vp, _vp, _u64, _vp, _vp, _u64, P(_u64), _vp, _u64, P(_u64), _vp]),
         "sp_cyp_support_json_hap": (_i32, [P(ffi.sp_cyp_call), _vp, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, P(sp_cyp_read_mapping), _u64, P(C.c_char_p), _u32, _s, _u64, P(_u64)]),
+        "sp_cyp_variant_windows": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
+        "sp_cyp_variant_support": (_i32, [_vp, P(ffi.sp_cyp_problem), _vp, P(ffi.sp_cyp_call), _vp, _u32, P(ffi.sp_cyp_region_variants), P(sp_cyp_read_mapping), _u64, _u32,
+                                          _vp, _vp, _vp, _vp, _u64, _vp]),
+        "sp_cyp_variant_support_cohort": (_i32, [_vp, P(ffi.sp_cyp_problem), _u32, _vp, _vp, _vp, _u32, _vp, P(sp_cyp_read_mapping), _vp, _u32, _vp, _vp, _vp, _vp, _u64, _vp]),
+        "sp_cyp_alleles_vcf": (_i32, [_vp, P(ffi.sp_cyp_call), P(ffi.sp_cyp_region_variants), _vp, _vp, _s, _s, _vp, _u64, P(_u64)]),
+        "sp_cyp_alleles_vcf_save": (_i32, [_vp, P(ffi.sp_cyp_call), P(ffi.sp_cyp_region_variants), _vp, _vp, _s, _s, _s]),
+        "sp_bgzf_save": (_i32, [_s, _vp, _u64]),
+        "sp_starphase_set_cyp_vcf": (_i32, [_vp, _i32]),
         "sp_diplotype_settings_default": (None, [P(sp_diplotype_settings)]),
         "sp_diplotype_settings_check": (_i32, [P(sp_diplotype_settings), P(sp_sample_inputs), _s, _u32]),
         "sp_starphase_create": (_i32, [_vp, _s, _s, P(sp_diplotype_settings), P(_vp)]),
@@ -963,7 +971,7 @@ class Starphase:
     set_cyp_consensus_support() at once (it also writes cyp2d6_consensus_support.json); support_insertions=True: set_support_insertions() at once (those two files
     also list the inserted strings of the columns their insertions contest)."""
 
-    def __init__(self, database, reference=None, ctx=None, consensus_support=False, cyp_consensus_support=False, support_insertions=False, support_haplotypes=False, hla_ties=False, **settings):
+    def __init__(self, database, reference=None, ctx=None, consensus_support=False, cyp_consensus_support=False, support_insertions=False, support_haplotypes=False, hla_ties=False, cyp_vcf=False, **settings):
         self._h = _vp()
         self._s = _settings(**settings)
         rc = _lib().sp_starphase_create(ctx._h if ctx is not None else None, _b(database), _b(reference), C.byref(self._s), C.byref(self._h))
@@ -979,6 +987,8 @@ class Starphase:
             self.set_support_haplotypes(True)
         if hla_ties:
             self.set_hla_ties(True)
+        if cyp_vcf:
+            self.set_cyp_vcf(True)
 
     def close(self):
         if self._h:
@@ -1013,6 +1023,14 @@ class Starphase:
         rc = _lib().sp_starphase_set_support_insertions(self._h, 1 if on else 0)
         if rc != SP_OK:
             raise StarphaseError(rc, "sp_starphase_set_support_insertions")
+        return self
+
+    def set_cyp_vcf(self, on=True):
+        """sp_starphase_set_cyp_vcf: a debug folder also receives cyp2d6_alleles.vcf.gz (one haploid sample per typed CYP2D6 region, one record per listed database variant,
+        GT:SR:CR -- SR / CR: the member reads that span / agree with the consensus over the variant's window); off by default"""
+        rc = _lib().sp_starphase_set_cyp_vcf(self._h, 1 if on else 0)
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_starphase_set_cyp_vcf")
         return self
 
     def set_cyp_consensus_support(self, on=True):
@@ -1150,6 +1168,117 @@ def cyp_problem_call_with_consensus(ctx, pr, reads, cons_cap=65536):
     cons = C.create_string_buffer(ffi.SP_CYP_MAXCONS * cons_cap)
     ctx.check(_lib().sp_cyp_diplotype_mappings(ctx._h, C.byref(pr), reads._h, C.byref(call), cons, cons_cap, None, buf, cap, C.byref(n)))
     return call, cons, [buf[i] for i in range(n.value)]
+
+
+SP_CYP_VCF_FLANK = 2       # the default flank of a variant's window (include/starphase_hip.h)
+
+
+def cyp_region_variants(has_variants, state):
+    """an sp_cyp_region_variants from has_variants (up to SP_CYP_MAXCONS 0/1 entries) and state (uint8 [SP_CYP_MAXCONS, n_variants] or flat; kept alive by the record's
+    `_state` attribute)"""
+    import numpy as np
+    rv = ffi.sp_cyp_region_variants()
+    for h, x in enumerate(has_variants):
+        rv.has_variants[h] = int(x)
+    rv._state = np.ascontiguousarray(state, np.uint8)
+    rv.state = rv._state.ctypes.data_as(_vp).value if rv._state.size else None
+    return rv
+
+
+def cyp_call_with_variants(cdb, reads, cons_cap=65536, **overrides):
+    """sp_cyp_diplotype_mappings on a CypDb, keeping what sp_cyp_variant_support takes: (sp_cyp_problem, sp_cyp_call, consensus block, sp_cyp_region_variants,
+    [sp_cyp_read_mapping])"""
+    import numpy as np
+    pr = cdb.problem(**overrides)
+    call = ffi.sp_cyp_call()
+    n = C.c_uint64(0)
+    cap = 64 * reads.n + 64
+    buf = (sp_cyp_read_mapping * max(1, cap))()
+    cons = C.create_string_buffer(ffi.SP_CYP_MAXCONS * cons_cap)
+    rv = cyp_region_variants([], np.full(ffi.SP_CYP_MAXCONS * max(1, pr.n_variants), 255, np.uint8))
+    cdb.ctx.check(_lib().sp_cyp_diplotype_mappings(cdb.ctx._h, C.byref(pr), reads._h, C.byref(call), cons, cons_cap, C.byref(rv), buf, cap, C.byref(n)))
+    return pr, call, cons, rv, [buf[i] for i in range(n.value)]
+
+
+def cyp_variant_windows(aln, cigar, var_pos, var_ref_len, flank=SP_CYP_VCF_FLANK):
+    """sp_cyp_variant_windows (host only): aln = one AFFINE_DTYPE record (consensus = query a, backbone = target b), cigar = its ops -> [(start, end) or None per variant]"""
+    import numpy as np
+    a = np.ascontiguousarray(aln, ffi.AFFINE_DTYPE).reshape(1)
+    ops = np.ascontiguousarray(cigar, np.uint32)
+    pos = np.ascontiguousarray(var_pos, np.int32)
+    rl = np.ascontiguousarray(var_ref_len, np.uint32)
+    win = np.zeros(max(1, len(pos)), ffi.WINDOW_DTYPE)
+    ok = np.zeros(max(1, len(pos)), np.int32)
+    rc = _lib().sp_cyp_variant_windows(ffi._ptr(a), ffi._ptr(ops), len(ops), len(pos), ffi._ptr(pos), ffi._ptr(rl), int(flank), ffi._ptr(win), ffi._ptr(ok))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_cyp_variant_windows")
+    return [(int(win[v]["start"]), int(win[v]["end"])) if ok[v] else None for v in range(len(pos))]
+
+
+def cyp_variant_support(ctx, pr, reads, call, cons, cons_cap, rv, mappings, flank=SP_CYP_VCF_FLANK, table=False):
+    """sp_cyp_variant_support: what cyp_call_with_variants returned -> (support WINDOW_SUPPORT_DTYPE [SP_CYP_MAXCONS, n_variants], valid int32 of that shape); table=True
+    adds what cyp_consensus_support returns ([cols per consensus], [summary dict per consensus]) from the same member pass"""
+    import numpy as np
+    NV = int(pr.n_variants)
+    sup = np.zeros((ffi.SP_CYP_MAXCONS, max(1, NV)), ffi.WINDOW_SUPPORT_DTYPE)
+    ok = np.zeros((ffi.SP_CYP_MAXCONS, max(1, NV)), np.int32)
+    arr = _mapping_array(mappings)
+    H = max(0, min(call.n_consensus, ffi.SP_CYP_MAXCONS))
+    off = cols = sm = None
+    total = 0
+    if table:
+        off = np.zeros(ffi.SP_CYP_MAXCONS + 1, np.uint64)
+        total = sum(len(cyp_consensus_of(cons, cons_cap, h)) for h in range(H)) if call.status == 0 else 0
+        cols = np.zeros(max(1, total), ffi.PILEUP_DTYPE)
+        sm = np.zeros(ffi.SP_CYP_MAXCONS, ffi.SUPPORT_DTYPE)
+    ctx.check(_lib().sp_cyp_variant_support(ctx._h, C.byref(pr), reads._h, C.byref(call), C.cast(cons, _vp), cons_cap, C.byref(rv), arr, len(mappings), int(flank),
+                                            ffi._ptr(sup), ffi._ptr(ok), ffi._ptr(off), ffi._ptr(cols), total, ffi._ptr(sm)))
+    sup, ok = sup[:, :NV], ok[:, :NV]
+    if not table:
+        return sup, ok
+    return sup, ok, ([cols[int(off[h]):int(off[h + 1])].copy() for h in range(H)], [{n: int(sm[h][n]) for n in ffi.SUPPORT_FIELDS[:-1]} for h in range(H)])
+
+
+def cyp_alleles_vcf(cdb, call, rv, support=None, support_valid=None, file_date=None, command=None, cap=None):
+    """sp_cyp_alleles_vcf (host only): the text of cyp2d6_alleles.vcf.gz.  support / support_valid: [SP_CYP_MAXCONS, n_variants] as cyp_variant_support returned them.
+    cap: a capacity to try, once -> (status, text, needed)"""
+    import numpy as np
+    sup = np.ascontiguousarray(support, ffi.WINDOW_SUPPORT_DTYPE) if support is not None else None
+    ok = np.ascontiguousarray(support_valid, np.int32) if support_valid is not None else None
+    need = _u64(0)
+    args = (cdb._h, C.byref(call), C.byref(rv) if rv is not None else None, ffi._ptr(sup), ffi._ptr(ok), _b(file_date) if file_date is not None else None,
+            _b(command) if command is not None else None)
+    if cap is not None:
+        buf = C.create_string_buffer(max(1, int(cap)))
+        rc = _lib().sp_cyp_alleles_vcf(*args, buf, int(cap), C.byref(need))
+        return rc, buf.value.decode(), need.value
+    rc = _lib().sp_cyp_alleles_vcf(*args, None, 0, C.byref(need))
+    if rc not in (SP_OK, ffi.SP_ERR_CAPACITY):
+        raise StarphaseError(rc, "sp_cyp_alleles_vcf")
+    buf = C.create_string_buffer(need.value)
+    rc = _lib().sp_cyp_alleles_vcf(*args, buf, need.value, C.byref(need))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_cyp_alleles_vcf")
+    return buf.value.decode()
+
+
+def cyp_alleles_vcf_save(cdb, call, rv, path, support=None, support_valid=None, file_date=None, command=None):
+    """sp_cyp_alleles_vcf_save: the text of cyp_alleles_vcf as a BGZF file"""
+    import numpy as np
+    sup = np.ascontiguousarray(support, ffi.WINDOW_SUPPORT_DTYPE) if support is not None else None
+    ok = np.ascontiguousarray(support_valid, np.int32) if support_valid is not None else None
+    rc = _lib().sp_cyp_alleles_vcf_save(cdb._h, C.byref(call), C.byref(rv) if rv is not None else None, ffi._ptr(sup), ffi._ptr(ok),
+                                        _b(file_date) if file_date is not None else None, _b(command) if command is not None else None, _b(path))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_cyp_alleles_vcf_save")
+
+
+def bgzf_save(path, data):
+    """sp_bgzf_save: bytes -> a BGZF file"""
+    data = bytes(data)
+    rc = _lib().sp_bgzf_save(_b(path), C.cast(C.c_char_p(data), _vp), len(data))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_bgzf_save")
 
 
 def cyp_consensus_of(cons, cons_cap, h):

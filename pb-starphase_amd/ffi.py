@@ -296,6 +296,38 @@ HAP_DTYPE = np.dtype([("target", np.uint64), ("n_cols", np.uint32), ("count", np
 HAP_HEAD_DTYPE = np.dtype([("first_record", np.uint64), ("n_records", np.uint32), ("n_cols", np.uint32), ("n_cols_total", np.uint32), ("reserved_", np.uint32)])
 
 
+# window support (sp_pileup_windows_batch): one workgroup of SP_WINDOW_WAVES waves per (target, chunk of SP_WINDOW_CHUNK windows); SP_WINDOW_DEFECTS defects of a pair per
+# wave and round in LDS
+SP_WINDOW_CHUNK = 256
+SP_WINDOW_WAVES = 4
+SP_WINDOW_DEFECTS = 256
+WINDOW_DTYPE = np.dtype([("start", np.uint32), ("end", np.uint32)])                                                                      # sp_window
+WINDOW_SUPPORT_DTYPE = np.dtype([("span", np.uint32), ("exact", np.uint32), ("partial", np.uint32), ("reserved_", np.uint32)])           # sp_window_support
+
+
+class sp_window(C.Structure):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32)]
+
+
+class sp_window_support(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("span", "exact", "partial", "reserved_")]
+
+
+def _windows_arrays(windows, n_targets):
+    """windows = one list of (start, end) per target -> (win_offset uint64[n_targets + 1], WINDOW_DTYPE array)"""
+    if len(windows) != n_targets:
+        raise ValueError("one window list per target")
+    woff = np.zeros(n_targets + 1, np.uint64)
+    woff[1:] = np.cumsum([len(w) for w in windows])
+    flat = np.zeros(max(1, int(woff[-1])), WINDOW_DTYPE)
+    k = 0
+    for w in windows:
+        for s_, e_ in w:
+            flat[k] = (s_, e_)
+            k += 1
+    return woff, flat
+
+
 class sp_support_summary(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in SUPPORT_FIELDS]
 
@@ -429,6 +461,8 @@ def lib():
         "sp_pileup_batch": (i32, [vp, vp, vp, vp, u64, vp, vp, u32, vp, vp, vp]),
         "sp_align_pileup_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), vp, vp, vp, vp, vp]),
         "sp_align_pileup_band_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, i32, vp, vp, vp, vp, vp, vp]),
+        "sp_pileup_windows_batch": (i32, [vp, vp, vp, vp, u64, vp, vp, u32, vp, vp, vp, vp, vp]),
+        "sp_align_pileup_windows_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "sp_pileup_ins_batch": (i32, [vp, vp, vp, vp, u64, vp, vp, u32, vp, vp, vp, u64, C.POINTER(u64)]),
         "sp_align_pileup_ins_batch": (i32, [vp, vp, vp, vp, u64, C.POINTER(sp_affine_opts), i32, i32, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]),
         "sp_support_ins_string": (i32, [vp, vp, u32, C.c_char_p, u64, C.POINTER(u64)]),
@@ -522,6 +556,7 @@ def lib():
         "sp_cyp_db_info": (i32, [vp, C.POINTER(sp_cyp_db_stats)]),
         "sp_cyp_db_template": (i32, [vp, u32, C.POINTER(i32), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(u32), C.POINTER(i32)]),
         "sp_cyp_db_variant": (i32, [vp, u32, C.POINTER(C.c_int64), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(i32)]),
+        "sp_cyp_db_variant_vi": (i32, [vp, u32, C.POINTER(C.c_char_p)]),
         "sp_cyp_db_index_label": (i32, [vp, C.c_char_p, C.POINTER(u32)]),
         "sp_cyp_db_index_variant": (i32, [vp, u64, C.c_char_p, C.c_char_p, C.POINTER(u32)]),
         "sp_cyp_db_allele": (i32, [vp, u32, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(C.c_uint8))]),
@@ -544,7 +579,7 @@ def lib():
         raise ImportError(f"{path}: ABI version {L.sp_abi_version()}, this binding was written for {SP_ABI_VERSION} (rebuild: __graft_entry__.build())")
     for name, size in (("sp_hla_realign", REALIGN_DTYPE.itemsize), ("sp_aln", ALN_DTYPE.itemsize), ("sp_k1_seed_hit", K1_HIT_DTYPE.itemsize),
                        ("sp_hla_best", C.sizeof(sp_hla_best)), ("sp_hla_realign", C.sizeof(sp_hla_realign)), ("sp_hla_rev_hit", REV_HIT_DTYPE.itemsize),
-                       ("sp_pileup_col", PILEUP_DTYPE.itemsize), ("sp_support_summary", SUPPORT_DTYPE.itemsize), ("sp_pileup_ins", INS_DTYPE.itemsize),
+                       ("sp_pileup_col", PILEUP_DTYPE.itemsize), ("sp_support_summary", SUPPORT_DTYPE.itemsize), ("sp_pileup_ins", INS_DTYPE.itemsize), ("sp_window", WINDOW_DTYPE.itemsize), ("sp_window_support", WINDOW_SUPPORT_DTYPE.itemsize),
                        ("sp_support_hap", HAP_DTYPE.itemsize), ("sp_support_hap_head", HAP_HEAD_DTYPE.itemsize)):
         if L.sp_struct_size(name.encode()) != size:
             raise ImportError(f"{path}: {name} is {L.sp_struct_size(name.encode())} bytes in the library, {size} in this binding")
@@ -646,6 +681,29 @@ class Context:
         self.check(lib().sp_pileup_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), _ptr(aln), _ptr(cigar), cigar.shape[1], _ptr(n_cigar), _ptr(off), _ptr(out)))
         return [out[int(off[t]):int(off[t + 1])] for t in range(B.n)]
 
+    def pileup_windows(self, A, B, pairs, aln, cigar, n_cigar, windows, win_offset=None):
+        """sp_pileup_windows_batch: the arguments of pileup and one list of (start, end) windows per target of B -> one WINDOW_SUPPORT_DTYPE array per target, a record
+        per window in the order given.  win_offset: the offsets to hand over instead of the ones that follow the lists (`windows` is then the flat list)"""
+        rows = np.zeros(len(pairs), PAIR_DTYPE)
+        for i, pr in enumerate(pairs):
+            rows[i] = (pr[0], pr[1], pr[2], pr[3] if len(pr) > 3 else 0)
+        aln = np.ascontiguousarray(aln, AFFINE_DTYPE)
+        cigar = np.ascontiguousarray(cigar, np.uint32).reshape(len(pairs), -1) if len(pairs) else np.zeros((0, 1), np.uint32)
+        n_cigar = np.ascontiguousarray(n_cigar, np.uint32)
+        off = np.zeros(B.n + 1, np.uint64)
+        off[1:] = np.cumsum([int(x) for x in B.lengths])
+        if win_offset is None:
+            woff, flat = _windows_arrays(windows, B.n)
+        else:
+            woff = np.ascontiguousarray(win_offset, np.uint64)
+            flat = np.zeros(max(1, len(windows)), WINDOW_DTYPE)
+            for k, w in enumerate(windows):
+                flat[k] = (w[0], w[1])
+        out = np.zeros(max(1, len(flat)), WINDOW_SUPPORT_DTYPE)
+        self.check(lib().sp_pileup_windows_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), _ptr(aln), _ptr(cigar), cigar.shape[1], _ptr(n_cigar), _ptr(off),
+                                                 _ptr(woff), _ptr(flat), _ptr(out)))
+        return [out[int(woff[t]):int(woff[t + 1])] for t in range(B.n)]
+
     def _with_ins(self, call, guess):
         """runs call(ins, cap, byref(n)) with room for `guess` records, once more with the room it asked for -> INS_DTYPE array"""
         n = C.c_uint64(0)
@@ -716,8 +774,10 @@ class Context:
         return self._with_ins(call, 4096 + 4 * len(pairs))
 
     def align_pileup(self, A, B, pairs, a=1, aln=True, cols=True, summaries=True, n_members=None, col_offset=None, band=64, retry_band=0, band_used=False, insertions=False,
-                     ins_cap=None, haplotypes=False, hap_cap=None):
-        """sp_align_pileup_batch: pairs as affine_align takes them -> (aln AFFINE_DTYPE[n] or None, [PILEUP_DTYPE array per target of B] or None,
+                     ins_cap=None, haplotypes=False, hap_cap=None, windows=None):
+        """windows (one list of (start, end) per target of B; not with insertions / haplotypes): sp_align_pileup_windows_batch -- one WINDOW_SUPPORT_DTYPE array per
+        target is added as the last item.
+        sp_align_pileup_batch: pairs as affine_align takes them -> (aln AFFINE_DTYPE[n] or None, [PILEUP_DTYPE array per target of B] or None,
         [summary dict per target] or None); an output switched off is handed to the library as NULL.  col_offset: None = the one that follows B's lengths.
         band (64 | 256), retry_band (0 | 256 with band 64) or band_used other than the defaults: sp_align_pileup_band_batch; band_used=True adds a fourth item,
         uint32[n]: 0 for a pair that did not align, else the band its alignment came from.  insertions=True (sp_align_pileup_ins_batch) adds the INS_DTYPE records
@@ -739,7 +799,16 @@ class Context:
         op = sp_affine_opts(a, 4, 6, 2, 26, 1, 1)
         used = np.zeros(max(1, len(pairs)), np.uint32) if band_used else None
         ins_out = hap_out = None
-        if haplotypes:
+        win_out = None
+        if windows is not None:
+            if haplotypes or insertions:
+                raise ValueError("windows come without the lists")
+            woff, flat = _windows_arrays(windows, B.n)
+            wbuf = np.zeros(max(1, len(flat)), WINDOW_SUPPORT_DTYPE)
+            self.check(lib().sp_align_pileup_windows_batch(self._h, A._h, B._h, _ptr(rows), len(pairs), C.byref(op), int(band), int(retry_band), _ptr(off), _ptr(out), _ptr(table),
+                                                           _ptr(sm), _ptr(mem), _ptr(used), _ptr(woff), _ptr(flat) if int(woff[-1]) else None, _ptr(wbuf)))
+            win_out = [wbuf[int(woff[t]):int(woff[t + 1])] for t in range(B.n)]
+        elif haplotypes:
             n_i = C.c_uint64(0)
             ibuf = [np.zeros(4096 + 4 * len(pairs), INS_DTYPE) if insertions else None]
 
@@ -775,6 +844,7 @@ class Context:
                [{n: int(sm[t][n]) for n in SUPPORT_FIELDS[:-1]} for t in range(B.n)] if summaries else None)
         res = res + (used[:len(pairs)],) if band_used else res
         res = res + (ins_out,) if insertions else res
+        res = res + (win_out,) if windows is not None else res
         return res + (hap_out,) if haplotypes else res
 
     def hla_config_extend(self, reference, alleles, db=None, batch_alleles=0):
@@ -1314,6 +1384,13 @@ class CypDb:
             lib().sp_cyp_db_variant(self._h, i, C.byref(p), C.byref(r), C.byref(a), C.byref(lab), C.byref(vi))
             out.append((p.value, r.value.decode(), a.value.decode(), lab.value.decode(), bool(vi.value)))
         return out
+
+    def variant_vi(self, i):
+        """sp_cyp_db_variant_vi: the "VI" entry of variant i, None when it is not flagged"""
+        vi = C.c_char_p()
+        if lib().sp_cyp_db_variant_vi(self._h, int(i), C.byref(vi)) != SP_OK:
+            raise IndexError(i)
+        return vi.value.decode() if vi.value is not None else None
 
     def index_label(self, label):
         idx = C.c_uint32(0)
