@@ -1351,98 +1351,83 @@ static int32_t k1_realign_sliced(sp_ctx* ctx, const sp_hla_db* db, const sp_seqs
     if (reads->n <= slice) return k1_realign_chunk(ctx, db, reads, out, cell_out, rev);
     for (uint32_t r0 = 0; r0 < reads->n; r0 += slice) {
         const uint32_t k = std::min<uint32_t>(slice, reads->n - r0);
-        sp_seqset part;
-        part.ctx = reads->ctx; part.n = k; part.has_n = reads->has_n; part.max_len = reads->max_len;
-        part.d_words = reads->d_words; part.d_nplane = reads->d_nplane; part.d_word_off = reads->d_word_off + r0; part.d_len = reads->d_len + r0;
-        part.h_len.assign(reads->h_len.begin() + r0, reads->h_len.begin() + r0 + k);
-        part.h_word_off.assign(reads->h_word_off.begin() + r0, reads->h_word_off.begin() + r0 + k + 1);
+        const sp_seqset part = sp_seqset_shallow(reads, r0, k, reads->d_words, reads->d_nplane, reads->d_len + r0);
         const int32_t rc = k1_realign_chunk(ctx, db, &part, out + r0, cell_out ? cell_out + (size_t)r0 * db->n_alleles : nullptr, rev ? rev + r0 : nullptr);
         if (rc != SP_OK) return rc;
     }
     return SP_OK;
 }
 
-static int32_t k1_realign_chunk(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, sp_hla_realign* out, uint32_t* cell_out, sp_hla_rev_hit* rev) {
-    const uint32_t R = reads->n, G = db->n_genes, NA = db->n_alleles;
-    if (R == 0) return SP_OK;
-    (void)hipSetDevice(ctx->device);
-    // the reference's call pattern (seeds, chains, best_n: sp_hla_seed.hip) unless the caller wants every cell or has switched it off
-    const bool seeded = ctx->k1_best_n > 0 && !cell_out;
-    sp_aln* d_win_aln = nullptr; sp_affine_aln* d_win_af = nullptr; sp_k1_seed_info* d_seed_info = nullptr; sp_hla_rev_hit* d_rev = nullptr;
-    if (seeded) {
-        std::lock_guard<std::mutex> guard(db->lazy);
-        if (!db->seed) { const int brc = sp_k1_seed_build(ctx, db->dna_fwd, &db->seed); if (brc != SP_OK) return brc; }
-    }
-    // 1. anchors read x gene
-    uint32_t* d_a = (uint32_t*)sp_pool(ctx, "k1_a_idx", (size_t)R * G * 4);
-    uint32_t* d_b = (uint32_t*)sp_pool(ctx, "k1_b_idx", (size_t)R * G * 4);
-    int32_t* d_rg = (int32_t*)sp_pool(ctx, "k1_rg", (size_t)R * G * 4);
-    int32_t* d_votes = (int32_t*)sp_pool(ctx, "k1_votes", (size_t)R * G * 4);
-    int32_t* d_best = (int32_t*)sp_pool(ctx, "k1_best", (size_t)R * 4);
-    // the read x allele matrix only exists when the caller asked for it (738 MB per 10,000 reads with the bundled database)
-    uint32_t* d_cells = cell_out ? (uint32_t*)sp_pool(ctx, "k1_cells", (size_t)R * NA * 4) : nullptr;
-    unsigned long long* d_win = cell_out ? nullptr : (unsigned long long*)sp_pool(ctx, "k1_winner", (size_t)R * 8);
-    sp_hla_realign* d_out = (sp_hla_realign*)sp_pool(ctx, "k1_out", (size_t)R * sizeof(sp_hla_realign));
-    int rc = SP_OK;
-    if (!d_a || !d_b || !d_rg || !d_votes || !d_best || (cell_out ? !d_cells : !d_win) || !d_out || NA >= (1u << 24)) rc = sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
-    if (rc == SP_OK && d_win) (void)hipMemsetAsync(d_win, 0xFF, (size_t)R * 8, ctx->stream);
-    // the (gene, read) pair list of the anchor and the empty bounds are written on the device: no host vectors, no waiting for copies
-    unsigned long long* d_bound = nullptr;
-    if (rc == SP_OK && !cell_out && !seeded) {
-        d_bound = (unsigned long long*)sp_pool(ctx, "k1_bound", (size_t)R * 8);
-        if (!d_bound) rc = sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign bound");
-    }
-    // (seeded mode: the anchors against the genes' references only serve the finalize stage -- the diagonal of the read's segment on the reference of the ACCEPTED allele's gene --
-    //  and are made behind the seeded map, for that gene alone)
-    if (rc == SP_OK && !seeded) hipLaunchKernelGGL(k1_init_kernel, dim3((R * G + 255) / 256), dim3(256), 0, ctx->stream, d_a, d_b, R, G, d_bound);
-    if (rc == SP_OK && !seeded) rc = sp_launch_anchor(ctx, db->ref_fwd, reads, d_a, d_b, (uint64_t)R * G, d_rg, d_votes, 1, "anchor_k1", G);
-    // reads with a weak forward anchor are listed now; their count comes back with the first pass's own host synchronisation
-    uint32_t* d_weak_n = (uint32_t*)sp_pool(ctx, "k1_weak_n", 4);
-    uint32_t* d_weak = (uint32_t*)sp_pool(ctx, "k1_weak", (size_t)R * 4);
-    uint8_t* d_isrev = (uint8_t*)sp_pool(ctx, "k1_isrev", R);
-    uint32_t n_weak = 0; bool weak_known = false;
-    if (rc == SP_OK && (!d_weak_n || !d_weak || !d_isrev)) rc = sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign strand buffers");
-    if (rc == SP_OK && !seeded) {
-        (void)hipMemsetAsync(d_weak_n, 0, 4, ctx->stream); (void)hipMemsetAsync(d_isrev, 0, R, ctx->stream);
-        hipLaunchKernelGGL(k1_weak_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, d_votes, R, G, d_weak_n, d_weak);
-    }
-    const bool hasn = db->dna_fwd->has_n || reads->has_n || db->ref_fwd->has_n;
-    // finalize: private per-wave windows of (allele, read) and (reference, read segment)
-    int slot_words = std::max(sp_slot_words(db->dna_fwd, reads, hasn), sp_slot_words(db->ref_fwd, reads, hasn));
-    const size_t lds_bytes = (size_t)slot_words * 16 + SP_LDS_TAIL;
-    // cells: the read window and one allele slot of the single wavefront of a workgroup
-    // (both multiples of 4 words: the allele slots take 16-byte LDS stores; a slot always holds a whole register prefetch)
-    const int b_words = (((reads->max_len + 15) / 16 + 4) + 3) & ~3;
-    const int a_words = std::max(K1_PRE_WORDS, (((db->dna_fwd->max_len + 15) / 16 + 4) + 3) & ~3);
-    const size_t cells_lds = (size_t)((hasn ? 2 : 1) * (b_words + a_words)) * 4 + SP_LDS_TAIL;
-    if (rc == SP_OK && (lds_bytes > 160 * 1024 - 64 || cells_lds > 160 * 1024 - 64)) rc = sp_fail(ctx, SP_ERR_TOO_LONG, "realign: window too long");
+// What the stages of one K1 call share.  k1_realign_chunk fills in the sizes and the buffers of every mode; a search stage leaves its own behind for the stages after it.
+struct K1Run {
+    sp_ctx* ctx; const sp_hla_db* db; const sp_seqset* reads;
+    uint32_t R, G, NA; bool hasn;
+    int slot_words; size_t lds_bytes;                          // finalize: private per-wave windows of (allele, read) and (reference, read segment)
+    int b_words, a_words; size_t cells_lds;                    // cells: the read window and one allele slot of the single wavefront of a workgroup
+    uint32_t *d_a, *d_b; int32_t *d_rg, *d_votes, *d_best; sp_hla_realign* d_out;
+    // exhaustive search: the read x allele matrix (only when the caller asked for it), the reads with a weak forward anchor and what the strand check made of them
+    uint32_t* d_cells = nullptr; uint32_t *d_weak = nullptr, *d_weak_n = nullptr; uint32_t n_weak = 0; uint8_t* d_isrev = nullptr;
+    // seeded search: the accepted mapping of every read; d_rm: the placement of every read's segment on its gene's reference (for the second stage's re-score)
+    sp_aln* d_win_aln = nullptr; sp_affine_aln* d_win_af = nullptr; sp_k1_seed_info* d_seed_info = nullptr; sp_hla_rev_hit* d_rev = nullptr; sp_aln* d_rm = nullptr;
+};
+
+// the reads with a weak forward anchor once more, against the reverse-complemented gene references: d_isrev says which of them anchor better there
+static int32_t k1_strand_check(const K1Run& run) {
+    sp_ctx* ctx = run.ctx; const uint32_t G = run.G, n_weak = run.n_weak;
+    const uint64_t np = (uint64_t)n_weak * G;
+    uint32_t* d_a2 = (uint32_t*)sp_pool(ctx, "k1_rev_a", np * 4); uint32_t* d_b2 = (uint32_t*)sp_pool(ctx, "k1_rev_b", np * 4);
+    int32_t* d_rg2 = (int32_t*)sp_pool(ctx, "k1_rev_rg", np * 4); int32_t* d_votes2 = (int32_t*)sp_pool(ctx, "k1_rev_votes", np * 4);
+    if (!d_a2 || !d_b2 || !d_rg2 || !d_votes2) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign strand anchors");
+    hipLaunchKernelGGL(k1_weak_pairs_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, run.d_weak, n_weak, G, d_a2, d_b2);
+    const int32_t rc = sp_launch_anchor(ctx, run.db->ref_rev, run.reads, d_a2, d_b2, np, d_rg2, d_votes2, 1, "anchor_k1_rev", G);
+    if (rc != SP_OK) return rc;
+    hipLaunchKernelGGL(k1_reverse_kernel, dim3((n_weak + 255) / 256), dim3(256), 0, ctx->stream, run.d_weak, n_weak, G, run.d_votes, d_votes2, run.d_isrev);
+    return SP_OK;
+}
+
+// The exhaustive search: every allele of every anchored gene, pruned (exact) unless the caller wants the cell matrix.  Leaves d_best, n_weak with d_isrev, and d_cells in cell-matrix mode.
+static int32_t k1_search_exhaustive(K1Run& run, const uint32_t* cell_out) {
+    sp_ctx* ctx = run.ctx; const sp_hla_db* db = run.db; const sp_seqset* reads = run.reads;
+    const uint32_t R = run.R, G = run.G, NA = run.NA;
     // (exact branch-and-bound is switched off when the caller wants the full cell matrix: d_bound stays null)
     // Pruned mode runs the cells as exact iterative deepening: pass 1 caps every cell at 12 edits (plus the running
     // bound); reads whose best acceptable cell cannot be beaten by any unfinished cell are settled; the few others
     // are redone at 40 and then at the full 3 % cap.  The full-matrix mode is one un-pruned pass.
+    unsigned long long *d_win = nullptr, *d_bound = nullptr;
+    if (cell_out) {
+        // the read x allele matrix only exists when the caller asked for it (738 MB per 10,000 reads with the bundled database)
+        run.d_cells = (uint32_t*)sp_pool(ctx, "k1_cells", (size_t)R * NA * 4);
+        if (!run.d_cells) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
+    } else {
+        d_win = (unsigned long long*)sp_pool(ctx, "k1_winner", (size_t)R * 8);
+        if (!d_win) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
+        (void)hipMemsetAsync(d_win, 0xFF, (size_t)R * 8, ctx->stream);
+        d_bound = (unsigned long long*)sp_pool(ctx, "k1_bound", (size_t)R * 8);
+        if (!d_bound) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign bound");
+    }
+    // 1. anchors read x gene
+    // the (gene, read) pair list of the anchor and the empty bounds are written on the device: no host vectors, no waiting for copies
+    hipLaunchKernelGGL(k1_init_kernel, dim3((R * G + 255) / 256), dim3(256), 0, ctx->stream, run.d_a, run.d_b, R, G, d_bound);
+    int32_t rc = sp_launch_anchor(ctx, db->ref_fwd, reads, run.d_a, run.d_b, (uint64_t)R * G, run.d_rg, run.d_votes, 1, "anchor_k1", G);
+    if (rc != SP_OK) return rc;
+    // reads with a weak forward anchor are listed now; their count comes back with the first pass's own host synchronisation
+    run.d_weak_n = (uint32_t*)sp_pool(ctx, "k1_weak_n", 4);
+    run.d_weak = (uint32_t*)sp_pool(ctx, "k1_weak", (size_t)R * 4);
+    run.d_isrev = (uint8_t*)sp_pool(ctx, "k1_isrev", R);
+    if (!run.d_weak_n || !run.d_weak || !run.d_isrev) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign strand buffers");
+    (void)hipMemsetAsync(run.d_weak_n, 0, 4, ctx->stream); (void)hipMemsetAsync(run.d_isrev, 0, R, ctx->stream);
+    hipLaunchKernelGGL(k1_weak_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, run.d_votes, R, G, run.d_weak_n, run.d_weak);
     uint8_t* d_done = nullptr; uint32_t* d_open = nullptr; uint32_t* d_open_list = nullptr; uint32_t* d_maxlen = nullptr;
-    if (rc == SP_OK && d_bound) {
+    if (d_bound) {
         d_done = (uint8_t*)sp_pool(ctx, "k1_done", R); d_open = (uint32_t*)sp_pool(ctx, "k1_open", 4);
         d_open_list = (uint32_t*)sp_pool(ctx, "k1_open_list", (size_t)R * 4); d_maxlen = (uint32_t*)sp_pool(ctx, "k1_maxlen", (size_t)R * 4);
-        if (!d_done || !d_open || !d_open_list || !d_maxlen) rc = sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign done flags");
-        else { (void)hipMemsetAsync(d_done, 0, R, ctx->stream); (void)hipMemsetAsync(d_maxlen, 0, (size_t)R * 4, ctx->stream); }
+        if (!d_done || !d_open || !d_open_list || !d_maxlen) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign done flags");
+        (void)hipMemsetAsync(d_done, 0, R, ctx->stream); (void)hipMemsetAsync(d_maxlen, 0, (size_t)R * 4, ctx->stream);
     }
     const int pass_caps[3] = {K1_CAP1, 40, SP_MAX_ED};
-    const int n_pass = seeded ? 0 : d_bound ? 3 : 1;
-    uint32_t n_open = R;
-    if (rc == SP_OK && seeded) {
-        d_win_aln = (sp_aln*)sp_pool(ctx, "k1s_win_aln", (size_t)R * sizeof(sp_aln)); d_win_af = (sp_affine_aln*)sp_pool(ctx, "k1s_win_af", (size_t)R * sizeof(sp_affine_aln));
-        d_seed_info = (sp_k1_seed_info*)sp_pool(ctx, "k1s_info", (size_t)R * sizeof(sp_k1_seed_info));
-        if (rev) d_rev = (sp_hla_rev_hit*)sp_pool(ctx, "k1s_rev", (size_t)R * sizeof(sp_hla_rev_hit));
-        if (!d_win_aln || !d_win_af || !d_seed_info || (rev && !d_rev)) rc = sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
-        else rc = sp_k1_seed_map(ctx, db->seed, db->dna_fwd, reads, ctx->k1_best_n, d_best, d_seed_info, d_win_aln, d_win_af, nullptr, d_rev);
-        if (rc == SP_OK) {
-            hipLaunchKernelGGL(k1_seed_pairs_kernel, dim3((R * G + 255) / 256), dim3(256), 0, ctx->stream, d_best, db->d_gene_of, R, G, d_a, d_b);
-            rc = sp_launch_anchor(ctx, db->ref_fwd, reads, d_a, d_b, (uint64_t)R * G, d_rg, d_votes, 1, "anchor_k1", G);
-        }
-        weak_known = true;
-    }
-    for (int pass = 0; pass < n_pass && rc == SP_OK; ++pass) {
+    const int n_pass = d_bound ? 3 : 1;
+    uint32_t n_open = R; bool synced = false;
+    for (int pass = 0; pass < n_pass; ++pass) {
         const int pass_cap = d_bound ? pass_caps[pass] : SP_MAX_ED;
         const uint32_t n_chunks = (((NA + K1_CHUNK - 1) / K1_CHUNK) + 7) & ~7u;       // padded to the 8 XCDs (k1_cells_kernel)
         const uint32_t* d_list = pass == 0 ? nullptr : d_open_list;
@@ -1455,85 +1440,95 @@ static int32_t k1_realign_chunk(sp_ctx* ctx, const sp_hla_db* db, const sp_seqse
         {
             ProfScope ps(ctx, pass == 0 ? "k1_cells" : "k1_cells_deep", (uint64_t)n_open * NA);
             auto go = [&](auto kernel) {
-                (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cells_lds);
+                (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)run.cells_lds);
                 K1Positions pos;
                 pos.alen = db->d_pos; pos.off = db->d_pos + NA; pos.gene = reinterpret_cast<const uint32_t*>(db->d_pos + (size_t)2 * NA);
                 pos.woff = reinterpret_cast<const uint32_t*>(db->d_pos + (size_t)3 * NA); pos.lcp = db->d_pos + (size_t)4 * NA;
-                hipLaunchKernelGGL(kernel, dim3(n_open * n_chunks), dim3(64), cells_lds, ctx->stream, db->dna_fwd->view(), reads->view(), pos,
-                                   d_rg, d_votes, (int)G, NA, n_chunks, d_cells, d_bound, d_list, d_maxlen, d_win, db->d_order, pass_cap, b_words, a_words, d_wgs);
+                hipLaunchKernelGGL(kernel, dim3(n_open * n_chunks), dim3(64), run.cells_lds, ctx->stream, db->dna_fwd->view(), reads->view(), pos, run.d_rg, run.d_votes,
+                                   (int)G, NA, n_chunks, run.d_cells, d_bound, d_list, d_maxlen, d_win, db->d_order, pass_cap, run.b_words, run.a_words, d_wgs);
             };
-            if (hasn) { if (pass == 0) go(k1_cells_kernel<true, false>); else go(k1_cells_kernel<true, true>); }
+            if (run.hasn) { if (pass == 0) go(k1_cells_kernel<true, false>); else go(k1_cells_kernel<true, true>); }
             else { if (pass == 0) go(k1_cells_kernel<false, false>); else go(k1_cells_kernel<false, true>); }
-            if (hipGetLastError() != hipSuccess) rc = sp_fail(ctx, SP_ERR_HIP, "k1_cells launch failed");
+            if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "k1_cells launch failed");
         }
         if (d_wgs) hipLaunchKernelGGL(k1_stats_kernel, dim3(256), dim3(256), 0, ctx->stream, d_wgs, n_open * n_chunks, d_cnt);
-        if (rc == SP_OK && d_bound && pass + 1 < n_pass) {
+        if (pass + 1 < n_pass) {
             (void)hipMemsetAsync(d_open, 0, 4, ctx->stream);
             hipLaunchKernelGGL(k1_done_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, d_bound, d_done, R, pass_cap, d_maxlen, d_open, d_open_list);
             (void)hipMemcpyAsync(&n_open, d_open, 4, hipMemcpyDeviceToHost, ctx->stream);
-            if (!weak_known) (void)hipMemcpyAsync(&n_weak, d_weak_n, 4, hipMemcpyDeviceToHost, ctx->stream);
-            if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = sp_fail(ctx, SP_ERR_HIP, "k1 done sync");
-            weak_known = true;
+            if (!synced) (void)hipMemcpyAsync(&run.n_weak, run.d_weak_n, 4, hipMemcpyDeviceToHost, ctx->stream);
+            if (hipStreamSynchronize(ctx->stream) != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "k1 done sync");
+            synced = true;
             if (n_open == 0) break;
         }
     }
-    if (rc == SP_OK && !weak_known) {                          // (the cell-matrix mode has no synchronisation of its own before this point)
-        (void)hipMemcpyAsync(&n_weak, d_weak_n, 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = sp_fail(ctx, SP_ERR_HIP, "k1 strand sync");
-        weak_known = true;
+    if (!synced) {                                             // (the cell-matrix mode has no synchronisation of its own before this point)
+        (void)hipMemcpyAsync(&run.n_weak, run.d_weak_n, 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "k1 strand sync");
     }
-    if (rc == SP_OK && n_weak > 0) {
-        const uint64_t np = (uint64_t)n_weak * G;
-        uint32_t* d_a2 = (uint32_t*)sp_pool(ctx, "k1_rev_a", np * 4); uint32_t* d_b2 = (uint32_t*)sp_pool(ctx, "k1_rev_b", np * 4);
-        int32_t* d_rg2 = (int32_t*)sp_pool(ctx, "k1_rev_rg", np * 4); int32_t* d_votes2 = (int32_t*)sp_pool(ctx, "k1_rev_votes", np * 4);
-        if (!d_a2 || !d_b2 || !d_rg2 || !d_votes2) rc = sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign strand anchors");
-        if (rc == SP_OK) {
-            hipLaunchKernelGGL(k1_weak_pairs_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, d_weak, n_weak, G, d_a2, d_b2);
-            rc = sp_launch_anchor(ctx, db->ref_rev, reads, d_a2, d_b2, np, d_rg2, d_votes2, 1, "anchor_k1_rev", G);
-        }
-        if (rc == SP_OK) hipLaunchKernelGGL(k1_reverse_kernel, dim3((n_weak + 255) / 256), dim3(256), 0, ctx->stream, d_weak, n_weak, G, d_votes, d_votes2, d_isrev);
-    }
-    if (rc == SP_OK && !seeded) {
-        ProfScope ps(ctx, "k1_reduce", R);
-        if (d_win) hipLaunchKernelGGL(k1_winner_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, d_win, R, d_best);
-        else hipLaunchKernelGGL(k1_reduce_kernel, dim3((R + 3) / 4), dim3(256), 0, ctx->stream, d_cells, db->dna_fwd->d_len, db->d_order, NA, R, d_best);
-    }
-    sp_aln* d_rm = nullptr;                                    // seeded mode: the placement of every read's segment on its gene's reference (for the second stage's re-score)
-    if (rc == SP_OK && seeded) {
-        d_rm = (sp_aln*)sp_pool(ctx, "k1_seg_rm", (size_t)R * sizeof(sp_aln));
-        if (!d_rm) rc = sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
-        else (void)hipMemsetAsync(d_rm, 0, (size_t)R * sizeof(sp_aln), ctx->stream);
-    }
-    if (rc == SP_OK) {
-        ProfScope ps(ctx, "k1_finalize", R);
-        if (hasn) {
-            (void)hipFuncSetAttribute((const void*)k1_finalize_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            hipLaunchKernelGGL(k1_finalize_kernel<true>, dim3((R + 3) / 4), dim3(256), lds_bytes, ctx->stream, db->dna_fwd->view(), db->dna_gene->view(),
-                               db->ref_fwd->view(), reads->view(), db->d_gene_of, db->d_off_fwd, d_rg, (int)G, db->d_am, db->d_hpc_ref, db->d_hpc_ref_off,
-                               d_best, R, d_out, slot_words, d_win_aln, seeded ? d_win_af : nullptr, d_rm);
-        } else {
-            (void)hipFuncSetAttribute((const void*)k1_finalize_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            hipLaunchKernelGGL(k1_finalize_kernel<false>, dim3((R + 3) / 4), dim3(256), lds_bytes, ctx->stream, db->dna_fwd->view(), db->dna_gene->view(),
-                               db->ref_fwd->view(), reads->view(), db->d_gene_of, db->d_off_fwd, d_rg, (int)G, db->d_am, db->d_hpc_ref, db->d_hpc_ref_off,
-                               d_best, R, d_out, slot_words, d_win_aln, seeded ? d_win_af : nullptr, d_rm);
-        }
-        if (hipGetLastError() != hipSuccess) rc = sp_fail(ctx, SP_ERR_HIP, "k1_finalize launch failed");
-    }
-    if (rc == SP_OK && seeded) {
+    if (run.n_weak > 0) { rc = k1_strand_check(run); if (rc != SP_OK) return rc; }
+    ProfScope ps(ctx, "k1_reduce", R);
+    if (d_win) hipLaunchKernelGGL(k1_winner_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, d_win, R, run.d_best);
+    else hipLaunchKernelGGL(k1_reduce_kernel, dim3((R + 3) / 4), dim3(256), 0, ctx->stream, run.d_cells, db->dna_fwd->d_len, db->d_order, NA, R, run.d_best);
+    return SP_OK;
+}
+
+// The seeded search, the reference's call pattern (seeds, chains, best_n: sp_hla_seed.hip).  Leaves d_best, the accepted mappings, the anchor of every read on its accepted gene and a cleared d_rm.
+static int32_t k1_search_seeded(K1Run& run, const sp_hla_rev_hit* rev) {
+    sp_ctx* ctx = run.ctx; const sp_hla_db* db = run.db; const uint32_t R = run.R, G = run.G;
+    int32_t rc = k1_seed_index(ctx, db);
+    if (rc != SP_OK) return rc;
+    // (the exhaustive search's winner words are cleared in this mode as well; no seeded stage reads them)
+    unsigned long long* d_win = (unsigned long long*)sp_pool(ctx, "k1_winner", (size_t)R * 8);
+    run.d_win_aln = (sp_aln*)sp_pool(ctx, "k1s_win_aln", (size_t)R * sizeof(sp_aln)); run.d_win_af = (sp_affine_aln*)sp_pool(ctx, "k1s_win_af", (size_t)R * sizeof(sp_affine_aln));
+    run.d_seed_info = (sp_k1_seed_info*)sp_pool(ctx, "k1s_info", (size_t)R * sizeof(sp_k1_seed_info));
+    if (rev) run.d_rev = (sp_hla_rev_hit*)sp_pool(ctx, "k1s_rev", (size_t)R * sizeof(sp_hla_rev_hit));
+    if (!d_win || !run.d_win_aln || !run.d_win_af || !run.d_seed_info || (rev && !run.d_rev)) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
+    (void)hipMemsetAsync(d_win, 0xFF, (size_t)R * 8, ctx->stream);
+    rc = sp_k1_seed_map(ctx, db->seed, db->dna_fwd, run.reads, ctx->k1_best_n, run.d_best, run.d_seed_info, run.d_win_aln, run.d_win_af, nullptr, run.d_rev);
+    if (rc != SP_OK) return rc;
+    // (the anchors against the genes' references only serve the finalize stage -- the diagonal of the read's segment on the reference of the ACCEPTED allele's gene --
+    //  and are made behind the seeded map, for that gene alone)
+    hipLaunchKernelGGL(k1_seed_pairs_kernel, dim3((R * G + 255) / 256), dim3(256), 0, ctx->stream, run.d_best, db->d_gene_of, R, G, run.d_a, run.d_b);
+    rc = sp_launch_anchor(ctx, db->ref_fwd, run.reads, run.d_a, run.d_b, (uint64_t)R * G, run.d_rg, run.d_votes, 1, "anchor_k1", G);
+    if (rc != SP_OK) return rc;
+    run.d_rm = (sp_aln*)sp_pool(ctx, "k1_seg_rm", (size_t)R * sizeof(sp_aln));
+    if (!run.d_rm) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
+    (void)hipMemsetAsync(run.d_rm, 0, (size_t)R * sizeof(sp_aln), ctx->stream);
+    return SP_OK;
+}
+
+// the record of every read from d_best: the segment against the gene's reference, the offsets (exhaustive modes: d_win_aln, d_win_af and d_rm are null)
+static int32_t k1_finalize(const K1Run& run) {
+    sp_ctx* ctx = run.ctx; const sp_hla_db* db = run.db; const uint32_t R = run.R;
+    ProfScope ps(ctx, "k1_finalize", R);
+    auto go = [&](auto kernel) {
+        (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)run.lds_bytes);
+        hipLaunchKernelGGL(kernel, dim3((R + 3) / 4), dim3(256), run.lds_bytes, ctx->stream, db->dna_fwd->view(), db->dna_gene->view(),
+                           db->ref_fwd->view(), run.reads->view(), db->d_gene_of, db->d_off_fwd, run.d_rg, (int)run.G, db->d_am, db->d_hpc_ref, db->d_hpc_ref_off,
+                           run.d_best, R, run.d_out, run.slot_words, run.d_win_aln, run.d_win_af, run.d_rm);
+    };
+    if (run.hasn) go(k1_finalize_kernel<true>); else go(k1_finalize_kernel<false>);
+    if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "k1_finalize launch failed");
+    return SP_OK;
+}
+
+static int32_t k1_seeded_second_stage(const K1Run& run) {
+    sp_ctx* ctx = run.ctx; const sp_hla_db* db = run.db; const sp_seqset* reads = run.reads; const uint32_t R = run.R;
+    {
         // segments whose cell against the gene's reference left the 64-diagonal band: once more on the wide band
         ProfScope ps(ctx, "k1_seg_retry", R);
         CellDesc* d_sc = (CellDesc*)sp_pool(ctx, "k1_seg_cells", (size_t)R * sizeof(CellDesc));
         sp_aln* d_sa = (sp_aln*)sp_pool(ctx, "k1_seg_alns", (size_t)R * sizeof(sp_aln));
-        if (!d_sc || !d_sa) rc = sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
-        else {
-            hipLaunchKernelGGL(k1_seg_retry_cells_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, d_out, R, reads->d_len, d_rg, (int)G, d_win_af, d_sc, d_sa);
-            rc = sp_launch_cells_wide(ctx, db->ref_fwd, reads, d_sc, R, d_sa);
-            if (rc == SP_OK) hipLaunchKernelGGL(k1_seg_retry_finish_kernel, dim3((R + 3) / 4), dim3(256), 0, ctx->stream, db->dna_gene->view(), db->ref_fwd->view(), db->d_am, db->d_hpc_ref,
-                                                db->d_hpc_ref_off, d_sc, d_sa, d_win_af, R, d_out, d_rm);
-            if (rc == SP_OK && hipGetLastError() != hipSuccess) rc = sp_fail(ctx, SP_ERR_HIP, "k1 segment retry launch failed");
-        }
+        if (!d_sc || !d_sa) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
+        hipLaunchKernelGGL(k1_seg_retry_cells_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, run.d_out, R, reads->d_len, run.d_rg, (int)run.G, run.d_win_af, d_sc, d_sa);
+        const int32_t rc = sp_launch_cells_wide(ctx, db->ref_fwd, reads, d_sc, R, d_sa);
+        if (rc != SP_OK) return rc;
+        hipLaunchKernelGGL(k1_seg_retry_finish_kernel, dim3((R + 3) / 4), dim3(256), 0, ctx->stream, db->dna_gene->view(), db->ref_fwd->view(), db->d_am, db->d_hpc_ref,
+                           db->d_hpc_ref_off, d_sc, d_sa, run.d_win_af, R, run.d_out, run.d_rm);
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "k1 segment retry launch failed");
     }
-    if (rc == SP_OK && seeded) {
+    {
         // the second stage in the reference's numbers: the segments' placements re-scored (segment = query, reference = target), the records completed from those extents
         ProfScope ps(ctx, "k1_seg_rescore", R);
         const size_t words = (size_t)reads->h_word_off[R] + SP_SEQ_PAD_WORDS;
@@ -1543,63 +1538,100 @@ static int32_t k1_realign_chunk(sp_ctx* ctx, const sp_hla_db* db, const sp_seqse
         uint32_t* d_sw = (uint32_t*)sp_pool(ctx, "k1_segrs_words", words * 4);
         uint32_t* d_sn = reads->d_nplane ? (uint32_t*)sp_pool(ctx, "k1_segrs_nplane", words * 4) : nullptr;
         sp_affine_aln* d_saf = (sp_affine_aln*)sp_pool(ctx, "k1_segrs_af", (size_t)R * sizeof(sp_affine_aln));
-        if (!d_c2 || !d_r2 || !d_s0 || !d_sl || !d_sw || (reads->d_nplane && !d_sn) || !d_saf) rc = sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
-        else {
-            hipLaunchKernelGGL(k1_seg_rs_prep_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, d_out, R, reads->d_len, d_win_af, d_rm, d_c2, d_r2, d_s0, d_sl);
-            hipLaunchKernelGGL(k1_seg_slice_kernel, dim3((R + 3) / 4), dim3(256), 0, ctx->stream, reads->view(), d_s0, d_sl, R, d_sw, d_sn);
-            sp_seqset segs;                                    // the segments as a set of their own: the reads' slots in a second buffer, their own lengths
-            segs.ctx = ctx; segs.n = R; segs.has_n = reads->has_n; segs.d_words = d_sw; segs.d_nplane = d_sn; segs.d_word_off = reads->d_word_off; segs.d_len = d_sl; segs.max_len = reads->max_len;
-            segs.h_len = reads->h_len; segs.h_word_off = reads->h_word_off;
-            const sp_affine_opts ao = { 1, 4, 6, 2, 26, 1, 1 };
-            // (ends only: the record takes the mapping's query span and target start; an HLA read is 40 - 100 clustered edits from the reference, and the DP over all of its
-            //  rows cost 17.5 ms per 10,000 reads.  An end keeps the cell's extent only where the cell's path, scored the reference's way from that end inwards, never
-            //  falls to where clipping could pay, and no clustered edit lies within ends_knob bases of it: af_classify_kernel)
-            constexpr int ends_knob = 64, band_knob = 256;      // bases from either end inside which an edit that does not stand alone sends that end to the DP; diagonals of that DP
-            rc = sp_rescore_mappings(ctx, db->ref_fwd, &segs, d_c2, d_r2, R, true, ao, band_knob, d_saf, "k1_segrs", SP_MAX_ED + 1, 1, nullptr, nullptr, ends_knob);
-            segs.d_words = nullptr; segs.d_nplane = nullptr; segs.d_word_off = nullptr; segs.d_len = nullptr;       // (pooled buffers: the set owns nothing)
-            if (rc == SP_OK) hipLaunchKernelGGL(k1_seg_rs_finish_kernel, dim3((R + 3) / 4), dim3(256), 0, ctx->stream, db->dna_gene->view(), db->ref_fwd->view(), db->d_am, db->d_hpc_ref,
-                                                db->d_hpc_ref_off, d_c2, d_s0, d_saf, d_win_af, R, d_out);
-            if (rc == SP_OK && hipGetLastError() != hipSuccess) rc = sp_fail(ctx, SP_ERR_HIP, "k1 segment re-score launch failed");
+        if (!d_c2 || !d_r2 || !d_s0 || !d_sl || !d_sw || (reads->d_nplane && !d_sn) || !d_saf) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
+        hipLaunchKernelGGL(k1_seg_rs_prep_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, run.d_out, R, reads->d_len, run.d_win_af, run.d_rm, d_c2, d_r2, d_s0, d_sl);
+        hipLaunchKernelGGL(k1_seg_slice_kernel, dim3((R + 3) / 4), dim3(256), 0, ctx->stream, reads->view(), d_s0, d_sl, R, d_sw, d_sn);
+        // the segments as a set of their own: the reads' slots in a second buffer, their own lengths
+        const sp_seqset segs = sp_seqset_shallow(reads, 0, R, d_sw, d_sn, d_sl);
+        const sp_affine_opts ao = { 1, 4, 6, 2, 26, 1, 1 };
+        // (ends only: the record takes the mapping's query span and target start; an HLA read is 40 - 100 clustered edits from the reference, and the DP over all of its
+        //  rows cost 17.5 ms per 10,000 reads.  An end keeps the cell's extent only where the cell's path, scored the reference's way from that end inwards, never
+        //  falls to where clipping could pay, and no clustered edit lies within ends_knob bases of it: af_classify_kernel)
+        constexpr int ends_knob = 64, band_knob = 256;      // bases from either end inside which an edit that does not stand alone sends that end to the DP; diagonals of that DP
+        const int32_t rc = sp_rescore_mappings(ctx, db->ref_fwd, &segs, d_c2, d_r2, R, true, ao, band_knob, d_saf, "k1_segrs", SP_MAX_ED + 1, 1, nullptr, nullptr, ends_knob);
+        if (rc != SP_OK) return rc;
+        hipLaunchKernelGGL(k1_seg_rs_finish_kernel, dim3((R + 3) / 4), dim3(256), 0, ctx->stream, db->dna_gene->view(), db->ref_fwd->view(), db->d_am, db->d_hpc_ref,
+                           db->d_hpc_ref_off, d_c2, d_s0, d_saf, run.d_win_af, R, run.d_out);
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "k1 segment re-score launch failed");
+    }
+    hipLaunchKernelGGL(k1_seed_store_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, run.d_out, R, run.d_seed_info, run.d_win_af);
+    return SP_OK;
+}
+
+// 3b. the winners re-scored the reference's way (two-piece affine gaps, end clipping): the numbers minimap2 reports for the read and its allele
+static int32_t k1_rescore_winners(const K1Run& run) {
+    sp_ctx* ctx = run.ctx; const uint32_t R = run.R;
+    CellDesc* d_rc = (CellDesc*)sp_pool(ctx, "k1_af_cells", (size_t)R * sizeof(CellDesc));
+    sp_aln* d_ref = (sp_aln*)sp_pool(ctx, "k1_af_ref", (size_t)R * sizeof(sp_aln));
+    sp_affine_aln* d_af = (sp_affine_aln*)sp_pool(ctx, "k1_af_out", (size_t)R * sizeof(sp_affine_aln));
+    if (!d_rc || !d_ref || !d_af) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
+    hipLaunchKernelGGL(k1_rescore_cells_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, run.d_out, R, d_rc, d_ref);
+    const sp_affine_opts ao = { 1, 4, 6, 2, 26, 1, 1 };
+    const int32_t rc = sp_rescore_mappings(ctx, run.db->dna_fwd, run.reads, d_rc, d_ref, R, true, ao, 64, d_af, "k1_af", 128);
+    if (rc != SP_OK) return rc;
+    hipLaunchKernelGGL(k1_affine_store_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, run.d_out, R, d_af);
+    return SP_OK;
+}
+
+static int32_t k1_download(const K1Run& run, sp_hla_realign* out, uint32_t* cell_out, sp_hla_rev_hit* rev) {
+    sp_ctx* ctx = run.ctx; const uint32_t R = run.R, NA = run.NA;
+    void* h_out = sp_host_pool(ctx, "k1_out", (size_t)R * sizeof(sp_hla_realign));
+    uint8_t* h_isrev = run.n_weak ? (uint8_t*)sp_host_pool(ctx, "k1_isrev", R) : nullptr;
+    if (h_isrev) (void)hipMemcpyAsync(h_isrev, run.d_isrev, R, hipMemcpyDeviceToHost, ctx->stream);
+    (void)hipMemcpyAsync(h_out ? h_out : (void*)out, run.d_out, (size_t)R * sizeof(sp_hla_realign), hipMemcpyDeviceToHost, ctx->stream);
+    if (cell_out) (void)hipMemcpyAsync(cell_out, run.d_cells, (size_t)R * NA * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (run.d_rev) (void)hipMemcpyAsync(rev, run.d_rev, (size_t)R * sizeof(sp_hla_rev_hit), hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, std::string("realign: ") + hipGetErrorString(e));
+    if (h_out) std::memcpy(out, h_out, (size_t)R * sizeof(sp_hla_realign));
+    // a read that anchors better on the reverse strand is dropped (the record keeps what the forward search found) -- unless it realigned acceptably forwards and the
+    // reverse anchor leads by less than a factor of two: the reference drops a read only when minimap2's best SCORING mapping is reverse (realigner.rs:178-193), and a
+    // read that passes the forward filters with a weak, repeat-ridden anchor is not one of those
+    if (h_isrev) for (uint32_t r = 0; r < R; ++r) if (h_isrev[r] == 2 || (h_isrev[r] == 1 && out[r].status != 0)) out[r].status = 2;
+    if (cell_out) {                                            // the device rows are in visiting order: hand them out by allele index
+        std::vector<uint32_t> row(NA);
+        for (uint32_t r = 0; r < R; ++r) {
+            uint32_t* c = cell_out + (size_t)r * NA;
+            for (uint32_t p2 = 0; p2 < NA; ++p2) row[run.db->h_order[p2]] = c[p2];
+            std::memcpy(c, row.data(), (size_t)NA * 4);
         }
     }
-    // 3b. the winners re-scored the reference's way (two-piece affine gaps, end clipping): the numbers minimap2 reports for the read and its allele
-    if (rc == SP_OK && seeded) hipLaunchKernelGGL(k1_seed_store_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, d_out, R, d_seed_info, d_win_af);
-    if (rc == SP_OK && ctx->mm2_rescore && !seeded) {
-        CellDesc* d_rc = (CellDesc*)sp_pool(ctx, "k1_af_cells", (size_t)R * sizeof(CellDesc));
-        sp_aln* d_ref = (sp_aln*)sp_pool(ctx, "k1_af_ref", (size_t)R * sizeof(sp_aln));
-        sp_affine_aln* d_af = (sp_affine_aln*)sp_pool(ctx, "k1_af_out", (size_t)R * sizeof(sp_affine_aln));
-        if (!d_rc || !d_ref || !d_af) rc = sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
-        else {
-            hipLaunchKernelGGL(k1_rescore_cells_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, d_out, R, d_rc, d_ref);
-            const sp_affine_opts ao = { 1, 4, 6, 2, 26, 1, 1 };
-            rc = sp_rescore_mappings(ctx, db->dna_fwd, reads, d_rc, d_ref, R, true, ao, 64, d_af, "k1_af", 128);
-            if (rc == SP_OK) hipLaunchKernelGGL(k1_affine_store_kernel, dim3((R + 255) / 256), dim3(256), 0, ctx->stream, d_out, R, d_af);
-        }
+    return SP_OK;
+}
+
+static int32_t k1_realign_chunk(sp_ctx* ctx, const sp_hla_db* db, const sp_seqset* reads, sp_hla_realign* out, uint32_t* cell_out, sp_hla_rev_hit* rev) {
+    K1Run run;
+    run.ctx = ctx; run.db = db; run.reads = reads;
+    const uint32_t R = run.R = reads->n, G = run.G = db->n_genes, NA = run.NA = db->n_alleles;
+    if (R == 0) return SP_OK;
+    (void)hipSetDevice(ctx->device);
+    run.d_a = (uint32_t*)sp_pool(ctx, "k1_a_idx", (size_t)R * G * 4);
+    run.d_b = (uint32_t*)sp_pool(ctx, "k1_b_idx", (size_t)R * G * 4);
+    run.d_rg = (int32_t*)sp_pool(ctx, "k1_rg", (size_t)R * G * 4);
+    run.d_votes = (int32_t*)sp_pool(ctx, "k1_votes", (size_t)R * G * 4);
+    run.d_best = (int32_t*)sp_pool(ctx, "k1_best", (size_t)R * 4);
+    run.d_out = (sp_hla_realign*)sp_pool(ctx, "k1_out", (size_t)R * sizeof(sp_hla_realign));
+    if (!run.d_a || !run.d_b || !run.d_rg || !run.d_votes || !run.d_best || !run.d_out || NA >= (1u << 24)) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "realign buffers");
+    run.hasn = db->dna_fwd->has_n || reads->has_n || db->ref_fwd->has_n;
+    run.slot_words = std::max(sp_slot_words(db->dna_fwd, reads, run.hasn), sp_slot_words(db->ref_fwd, reads, run.hasn));
+    run.lds_bytes = (size_t)run.slot_words * 16 + SP_LDS_TAIL;
+    // (both multiples of 4 words: the allele slots take 16-byte LDS stores; a slot always holds a whole register prefetch)
+    run.b_words = (((reads->max_len + 15) / 16 + 4) + 3) & ~3;
+    run.a_words = std::max(K1_PRE_WORDS, (((db->dna_fwd->max_len + 15) / 16 + 4) + 3) & ~3);
+    run.cells_lds = (size_t)((run.hasn ? 2 : 1) * (run.b_words + run.a_words)) * 4 + SP_LDS_TAIL;
+    if (run.lds_bytes > 160 * 1024 - 64 || run.cells_lds > 160 * 1024 - 64) return sp_fail(ctx, SP_ERR_TOO_LONG, "realign: window too long");
+    // the reference's call pattern (seeds, chains, best_n: sp_hla_seed.hip) unless the caller wants every cell or has switched it off
+    int32_t rc;
+    if (ctx->k1_best_n > 0 && !cell_out) {
+        rc = k1_search_seeded(run, rev);
+        if (rc == SP_OK) rc = k1_finalize(run);
+        if (rc == SP_OK) rc = k1_seeded_second_stage(run);
+    } else {
+        rc = k1_search_exhaustive(run, cell_out);
+        if (rc == SP_OK) rc = k1_finalize(run);
+        if (ctx->mm2_rescore && rc == SP_OK) rc = k1_rescore_winners(run);
     }
-    if (rc == SP_OK) {
-        void* h_out = sp_host_pool(ctx, "k1_out", (size_t)R * sizeof(sp_hla_realign));
-        uint8_t* h_isrev = n_weak ? (uint8_t*)sp_host_pool(ctx, "k1_isrev", R) : nullptr;
-        if (h_isrev) (void)hipMemcpyAsync(h_isrev, d_isrev, R, hipMemcpyDeviceToHost, ctx->stream);
-        (void)hipMemcpyAsync(h_out ? h_out : (void*)out, d_out, (size_t)R * sizeof(sp_hla_realign), hipMemcpyDeviceToHost, ctx->stream);
-        if (cell_out) (void)hipMemcpyAsync(cell_out, d_cells, (size_t)R * NA * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (d_rev) (void)hipMemcpyAsync(rev, d_rev, (size_t)R * sizeof(sp_hla_rev_hit), hipMemcpyDeviceToHost, ctx->stream);
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = sp_fail(ctx, SP_ERR_HIP, std::string("realign: ") + hipGetErrorString(e));
-        else if (h_out) std::memcpy(out, h_out, (size_t)R * sizeof(sp_hla_realign));
-        // a read that anchors better on the reverse strand is dropped (the record keeps what the forward search found) -- unless it realigned acceptably forwards and the
-        // reverse anchor leads by less than a factor of two: the reference drops a read only when minimap2's best SCORING mapping is reverse (realigner.rs:178-193), and a
-        // read that passes the forward filters with a weak, repeat-ridden anchor is not one of those
-        if (rc == SP_OK && h_isrev) for (uint32_t r = 0; r < R; ++r) if (h_isrev[r] == 2 || (h_isrev[r] == 1 && out[r].status != 0)) out[r].status = 2;
-        if (rc == SP_OK && cell_out) {                        // the device rows are in visiting order: hand them out by allele index
-            std::vector<uint32_t> row(NA);
-            for (uint32_t r = 0; r < R; ++r) {
-                uint32_t* c = cell_out + (size_t)r * NA;
-                for (uint32_t p2 = 0; p2 < NA; ++p2) row[db->h_order[p2]] = c[p2];
-                std::memcpy(c, row.data(), (size_t)NA * 4);
-            }
-        }
-    }
-    return rc;
+    return rc == SP_OK ? k1_download(run, out, cell_out, rev) : rc;
 }
 
 // K2 for a batch of consensuses: every (consensus, allowed allele) pair of a level is one cell of one launch, one scan workgroup

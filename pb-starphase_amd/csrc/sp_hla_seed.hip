@@ -1543,9 +1543,7 @@ int sp_k1_seed_map(sp_ctx* ctx, const K1Seed* idx, const sp_seqset* alleles, con
         SP_HIP_CHECK(ctx, hipMemsetAsync(d_rw, 0, words * 4, ctx->stream));
         if (d_rn) SP_HIP_CHECK(ctx, hipMemsetAsync(d_rn, 0, words * 4, ctx->stream));
         hipLaunchKernelGGL(k1s_revcomp_kernel, dim3(R), dim3(256), 0, ctx->stream, reads->view(), d_sel, d_sel_cnt, d_rw, d_rn);
-        sp_seqset rset;
-        rset.ctx = reads->ctx; rset.n = R; rset.has_n = reads->has_n; rset.max_len = reads->max_len; rset.d_words = d_rw; rset.d_nplane = d_rn; rset.d_word_off = reads->d_word_off; rset.d_len = reads->d_len;
-        rset.h_len = reads->h_len; rset.h_word_off = reads->h_word_off;
+        const sp_seqset rset = sp_seqset_shallow(reads, 0, R, d_rw, d_rn, reads->d_len);
         hipLaunchKernelGGL(k1s_cells_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_sel, d_sel_cnt, R, idx->d_rid_allele, alleles->d_len, 1, d_cells2);
         rc = sp_launch_cells(ctx, alleles, &rset, d_cells2, NC, d_aln2, nullptr, 0, "k1s_cells_rev", 1);
         if (rc != SP_OK) return rc;

@@ -60,6 +60,16 @@ struct sp_seqset {
     SeqSetView view() const { return SeqSetView{d_words, d_nplane, d_word_off, d_len, n}; }
     KmerIndexView kview() const { return KmerIndexView{d_kcode, d_kpos, d_koff}; }
 };
+// Entries [first, first + n) of s as a set that owns nothing (only sp_seqset_free frees device memory: a shallow set just goes out of scope).  The word offsets are
+// s's own; the caller names the packed words and N plane they index -- s's, or pooled buffers laid out like them -- and the lengths of the n entries on the device.
+inline sp_seqset sp_seqset_shallow(const sp_seqset* s, uint32_t first, uint32_t n, uint32_t* d_words, uint32_t* d_nplane, int32_t* d_len) {
+    sp_seqset v;
+    v.ctx = s->ctx; v.n = n; v.has_n = s->has_n; v.max_len = s->max_len;
+    v.d_words = d_words; v.d_nplane = d_nplane; v.d_word_off = s->d_word_off + first; v.d_len = d_len;
+    v.h_len.assign(s->h_len.begin() + first, s->h_len.begin() + first + n);
+    v.h_word_off.assign(s->h_word_off.begin() + first, s->h_word_off.begin() + first + n + 1);
+    return v;
+}
 
 struct ProfileEntry { double ms = 0; uint64_t launches = 0; uint64_t cells = 0; };
 

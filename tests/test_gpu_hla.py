@@ -376,6 +376,65 @@ def test_k1_gene_vote_filter(oracle, pkg, gpu_ctx, small, k1_exhaustive):
     assert (cells[2][in_a & has_dna] != none).any() and (cells[2][in_b & has_dna] != none).any()
 
 
+K1_STAGE_NAMES = ("anchor_k1", "anchor_k1_rev", "k1_cells", "k1_cells_deep", "k1_reduce", "k1_finalize", "k1_seg_retry", "k1_seg_rescore")
+# launches per profile name of ONE realign_reads call on the reads of the test below, mode by mode: what this same test body recorded with the library of the
+# commit before K1's host driver was cut into stages (SP_LIB_PATH named that build)
+K1_STAGE_LAUNCHES = {
+    "seeded": dict(zip(K1_STAGE_NAMES, (1, 0, 0, 0, 0, 1, 1, 1))),
+    "pruned": dict(zip(K1_STAGE_NAMES, (1, 1, 1, 2, 1, 1, 0, 0))),
+    "cells": dict(zip(K1_STAGE_NAMES, (1, 1, 1, 0, 1, 1, 0, 0))),
+}
+
+
+def test_k1_modes_run_their_own_stages(pkg, gpu_ctx, small):
+    """the three pipelines of sp_hla_realign_reads (seeded, pruned exhaustive, cell matrix) each record their own stages in the profile and no other mode's; and
+    the exhaustive search without the affine re-score (mm2_rescore 0) gives the same records with the mm2_* fields left zero"""
+    from pb_starphase_amd import synth
+    fx, db = small
+    rng = np.random.default_rng(17)
+    reads = []
+    for g in range(len(fx.genes)):
+        for a in rng.choice(fx.full_length_alleles(g), 2, replace=False).tolist():
+            hap, gs = fx.haplotype(g, a)
+            reads += synth.simulate_reads(rng, hap, gs, len(fx.dna[a]), 6, mean_len=6500, sd_len=1200)
+    reads = reads[:22]
+    reads.append(synth.mutate(rng, reads[1], 20, 10, 10))           # more edits than the first pass allows
+    reads.append("".join(rng.choice(list("ACGT"), 5000)))           # junk read: no allele
+    s = list(reads[3])
+    for p in rng.choice(len(s), 6, replace=False):
+        s[int(p)] = "N"
+    reads[3] = "".join(s)
+    reads[5] = synth.revcomp(reads[5])
+    rs = gpu_ctx.upload(reads)
+    got = {}
+    try:
+        gpu_ctx.set_option("k1_best_n", 0)
+        rescored = db.realign_reads(rs)
+        gpu_ctx.set_option("mm2_rescore", 0)
+        plain = db.realign_reads(rs)
+        gpu_ctx.set_option("mm2_rescore", 1)
+        for mode, best_n, cells in (("seeded", 5, False), ("pruned", 0, False), ("cells", 0, True)):
+            gpu_ctx.set_option("k1_best_n", best_n)
+            gpu_ctx.profile_reset()
+            db.realign_reads(rs, cells=cells)
+            got[mode] = {n: gpu_ctx.profile_get(n)[1] for n in K1_STAGE_NAMES}
+    finally:
+        gpu_ctx.set_option("mm2_rescore", 1)
+        gpu_ctx.set_option("k1_best_n", 5)
+    print("K1 stage launches:", got)
+    assert (rescored["status"] == 0).sum() >= len(reads) - 4 and (rescored["mm2_score"] > 0).sum() >= len(reads) - 4
+    for name in plain.dtype.names:
+        if name.startswith("mm2_"):
+            assert not plain[name].any(), name
+        else:
+            assert (plain[name] == rescored[name]).all(), name
+    assert got == K1_STAGE_LAUNCHES
+    for mode, mine, others in (("seeded", ("anchor_k1", "k1_finalize", "k1_seg_retry", "k1_seg_rescore"), ("k1_cells", "k1_cells_deep", "k1_reduce", "anchor_k1_rev")),
+                               ("pruned", ("anchor_k1", "k1_cells", "k1_reduce", "k1_finalize"), ("k1_seg_retry", "k1_seg_rescore")),
+                               ("cells", ("anchor_k1", "k1_cells", "k1_reduce", "k1_finalize"), ("k1_seg_retry", "k1_seg_rescore"))):
+        assert all(got[mode][n] > 0 for n in mine) and not any(got[mode][n] for n in others), (mode, got[mode])
+
+
 def test_k1_reverse_strand_reads_are_dropped(oracle, pkg, gpu_ctx, small, k1_exhaustive):
     """src/hla/realigner.rs:178-193: a read whose best mapping is on the reverse strand is dropped.  The library decides the strand at the seeds
     (status 2: the best anchor on the reverse-complemented gene references out-votes the best forward anchor); == the oracle's statement.  The
