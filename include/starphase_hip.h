@@ -724,6 +724,39 @@ typedef struct {
 
 int32_t sp_cyp_best_chain_pair(sp_ctx* ctx, const sp_chain_problem* problem, sp_chain_result* result);
 
+/* The runner-up pairs: the content of the reference's 10-entry heap (chaining.rs:404-405,515-526), which it prints at debug level (:540-557).
+ * Among the pairs i <= j whose get_multinomial_score is valid, the max_alts (1..64) smallest under (primary_score, i, j), ascending -- ChainScore's Ord
+ * (:188-196) with i, j in enumeration order; entry 0 is sp_cyp_best_chain_pair's winner, field for field.  The list does not depend on the launch order or on
+ * the kernel that ran: a pair is skipped only when its partial cost is strictly above a proven upper bound of the max_alts-th best complete score.
+ *   alts          max_alts records; *n_alts = min(max_alts, valid pairs) are written
+ *   hap_counts    optional [max_alts][n_haps]: copies of each region in the pair
+ *   hap_weights   optional [max_alts][n_haps]: the coverage the reads gave each region (the f64 sums the score was made from)
+ *   best          optional: entry 0 in the old record, with n_possible and n_pairs_scored
+ * Statuses as sp_cyp_best_chain_pair.  sp_cyp_possible_chains (host only; ctx may be NULL: it only receives the error text) lists the chains index1 / index2 refer to, in enumeration order:
+ * chain c is items[chain_off[c] .. chain_off[c+1]); *n_chains / *n_items are always set, SP_ERR_CAPACITY when off_cap < n_chains + 1 or items_cap < n_items. */
+#define SP_CYP_ALTERNATIVES 10         /* the reference's heap size: what the whole-sample switch asks for */
+typedef struct {
+    int32_t index1, index2;             /* i <= j, enumeration order */
+    int32_t n1, n2;
+    int32_t chain1[SP_MAX_CHAIN], chain2[SP_MAX_CHAIN];    /* sorted as in sp_chain_result */
+    double score, ln_ed_penalty, mn_llh_penalty, allele_expected_penalty, unexpected_chain_penalty, inferred_chain_penalty;
+    uint64_t edit_distance;
+    uint32_t unmet_observations;        /* reads none of whose putative chains is a sub-chain of either chain (chaining.rs:427-440) */
+    uint32_t reserved_;
+} sp_chain_alt;
+
+int32_t sp_cyp_best_chain_pairs(sp_ctx* ctx, const sp_chain_problem* problem, uint32_t max_alts, sp_chain_alt* alts, uint32_t* n_alts,
+                                int32_t* hap_counts, double* hap_weights, sp_chain_result* best);
+int32_t sp_cyp_possible_chains(sp_ctx* ctx, const sp_chain_problem* problem, uint32_t* chain_off, uint32_t off_cap, uint32_t* items, uint32_t items_cap,
+                               uint32_t* n_chains, uint32_t* n_items);
+/* `cyp2d6_alternatives.json` (sp_starphase_set_cyp_alternatives), host only: {"n_possible_chains", "n_pairs_scored"?, "alternatives": [...]}, best first; an
+ * alternative has rank (1: the call), diplotype (convert_chain_to_hap of the two chains, sub-allele detail, "hap1/hap2"), chains (two lists of "<index>_<label>" region names, the
+ * naming of DanglingAllele, chaining.rs:587), score, delta_to_best, the five components, edit_distance, unmet_observations and coverage
+ * ([{"region", "copies", "observed"}] for the regions with copies > 0; [] without hap_counts).  n_pairs_scored is written only when the pointer is given (the
+ * whole-sample call leaves it out: it differs from run to run).  problem: the labels and the translation table.  out / cap / needed as sp_cyp_alleles_json. */
+int32_t sp_cyp_alternatives_json(const sp_chain_problem* problem, uint32_t n_possible_chains, const uint64_t* n_pairs_scored, const sp_chain_alt* alts, uint32_t n_alts,
+                                 const int32_t* hap_counts, const double* hap_weights, char* out, uint64_t cap, uint64_t* needed);
+
 /* ------------------------------------------------------------------ K3: CYP2D6 template search in reads
  * Replaces Cyp2d6Extractor::find_base_type_in_sequence (src/cyp2d6/haplotyper.rs:142-315) for a batch of reads:
  * every template (D6, D7, *5 signature, hybrids, REP6/REP7, spacer, link_region -- given in the reference's key order,
@@ -1754,6 +1787,12 @@ int32_t sp_starphase_set_cyp_consensus_support(sp_starphase* handle, int32_t on)
  * folder -- the SAME member pass that serves sp_starphase_set_cyp_consensus_support when both are on.  Off, or no debug folder: no launch, no file, and every output is
  * the same bytes; on: every other output is.  A failure of the pass or of the file fails the sample's CYP2D6 entry. */
 int32_t sp_starphase_set_cyp_vcf(sp_starphase* handle, int32_t on);
+/* cyp2d6_alternatives.json, off by default (on 0): with it on, the CYP2D6 lane's chain-pair search of a sample that has a debug folder is
+ * sp_cyp_best_chain_pairs with max_alts 10 (the reference's heap size), whose entry 0 is the call, and a call of status 0 also writes
+ * <folder>/cyp2d6_alternatives.json (sp_cyp_alternatives_json, without n_pairs_scored); a call that ends in an expected CallerError writes no file.  The single call,
+ * a batch and the cohort call write the same bytes for a sample.  Off, or no debug folder: nothing more is launched or pooled and every output is the same bytes;
+ * on: every other output is. */
+int32_t sp_starphase_set_cyp_alternatives(sp_starphase* handle, int32_t on);
 /* A switch of its own, off by default, with effect only where one of the two switches above writes its file: the support pass of that file also makes the insertion
  * list (sp_hla_consensus_support_cohort_ins / sp_cyp_consensus_support_cohort_ins: the same one pass per batch group) and the file is rendered with it
  * (sp_consensus_support_json_ins / sp_cyp_support_json_ins, without first_read): every contested column with 2 * ins > depth gains "insertions" (and "more", "other").

@@ -29,6 +29,7 @@ pub const SP_K1_SEL: i64 = 16;
 pub const SP_HLA_MAP_TIES: i64 = 1;
 pub const SP_HLA_TIES_MAX_NAMES: i64 = 256;
 pub const SP_MAX_CHAIN: i64 = 64;
+pub const SP_CYP_ALTERNATIVES: i64 = 10;
 pub const SP_CYP_MAXCONS: i64 = 64;
 pub const SP_CYP_VCF_FLANK: i64 = 2;
 pub const SP_VAR_MAXDIP: i64 = 4096;
@@ -285,6 +286,24 @@ pub struct sp_chain_result {
     pub inferred_chain_penalty: f64,
     pub edit_distance: u64,
     pub n_pairs_scored: u64,
+}
+#[repr(C)]
+pub struct sp_chain_alt {
+    pub index1: i32,
+    pub index2: i32,
+    pub n1: i32,
+    pub n2: i32,
+    pub chain1: [i32; SP_MAX_CHAIN as usize],
+    pub chain2: [i32; SP_MAX_CHAIN as usize],
+    pub score: f64,
+    pub ln_ed_penalty: f64,
+    pub mn_llh_penalty: f64,
+    pub allele_expected_penalty: f64,
+    pub unexpected_chain_penalty: f64,
+    pub inferred_chain_penalty: f64,
+    pub edit_distance: u64,
+    pub unmet_observations: u32,
+    pub reserved_: u32,
 }
 #[repr(C)]
 pub struct sp_region_hit {
@@ -868,6 +887,9 @@ extern "C" {
     pub fn sp_hla_map_ties(map: *const sp_hla_map, item: u32, scan: i32, cls: *mut *const u8, counts: *mut u32) -> i32;
     pub fn sp_hla_ties_json(entries: *const sp_hla_ties_entry, n_entries: u32, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
     pub fn sp_cyp_best_chain_pair(ctx: *mut sp_ctx, problem: *const sp_chain_problem, result: *mut sp_chain_result) -> i32;
+    pub fn sp_cyp_best_chain_pairs(ctx: *mut sp_ctx, problem: *const sp_chain_problem, max_alts: u32, alts: *mut sp_chain_alt, n_alts: *mut u32, hap_counts: *mut i32, hap_weights: *mut f64, best: *mut sp_chain_result) -> i32;
+    pub fn sp_cyp_possible_chains(ctx: *mut sp_ctx, problem: *const sp_chain_problem, chain_off: *mut u32, off_cap: u32, items: *mut u32, items_cap: u32, n_chains: *mut u32, n_items: *mut u32) -> i32;
+    pub fn sp_cyp_alternatives_json(problem: *const sp_chain_problem, n_possible_chains: u32, n_pairs_scored: *const u64, alts: *const sp_chain_alt, n_alts: u32, hap_counts: *const i32, hap_weights: *const f64, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
     pub fn sp_cyp_find_regions(ctx: *mut sp_ctx, templates: *const sp_seqset, template_type: *const i32, reads: *const sp_seqset, max_missing_frac: f64, hits: *mut sp_region_hit, hits_cap: u64, n_hits: *mut u64) -> i32;
     pub fn sp_cyp_weight_segments(ctx: *mut sp_ctx, consensus: *const sp_seqset, allowed: *const u8, segments: *const sp_seqset, ed: *mut u64, ov: *mut f64, kept: *mut u8) -> i32;
     pub fn sp_cyp_score_alleles(ctx: *mut sp_ctx, n_variants: u32, n_alleles: u32, hap_matrix: *const u8, is_vi: *const u8, n_seqs: u32, states: *const u8, best_vi: *mut u32, best_all: *mut u32, tie_mask: *mut u8) -> i32;
@@ -1029,6 +1051,7 @@ extern "C" {
     pub fn sp_starphase_set_consensus_support(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_cyp_consensus_support(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_cyp_vcf(handle: *mut sp_starphase, on: i32) -> i32;
+    pub fn sp_starphase_set_cyp_alternatives(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_support_insertions(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_support_haplotypes(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_warnings(handle: *const sp_starphase) -> *const c_char;

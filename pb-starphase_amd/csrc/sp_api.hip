@@ -142,6 +142,7 @@ int32_t sp_struct_size(const char* name) {
     SP_SZ(sp_hla_ties_entry)
     SP_SZ(sp_chain_problem)
     SP_SZ(sp_chain_result)
+    SP_SZ(sp_chain_alt)
     SP_SZ(sp_region_hit)
     SP_SZ(sp_cyp_problem)
     SP_SZ(sp_cyp_call)

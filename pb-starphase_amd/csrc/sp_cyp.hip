@@ -70,6 +70,7 @@ std::string simple_allele(const sp_chain_problem* p, uint32_t h) {
 struct PairConsts {
     int H, P, maxlen, R;
     int ignore_limits, normalize_all, infer;
+    int nbest;                                                                // N of the N-best mode (sp_cyp_best_chain_pairs); 0 on the rank-1 path.  Sits in what was padding
     double lasso, ln_ed, unexpected, inferred;
     uint64_t n_pairs;
 };
@@ -141,14 +142,30 @@ __device__ __forceinline__ double k5_multinomial(const PairConsts& c, Cnt cnt, H
 // chaining.rs:794-819), cost[1] unexpected chain, cost[2] inferred edge -- and the exact pruning: a pair whose cheap partial cost already exceeds the best
 // complete score cannot win (chaining.rs:457-464).
 struct K5Head { double cost[3]; bool go; };
-__device__ __forceinline__ K5Head k5_pair_head(const PairConsts& c, int i, int j, const uint8_t* __restrict__ chains, const int32_t* __restrict__ chain_len,
-                                               const uint32_t* __restrict__ chain_unexp, const uint32_t* __restrict__ chain_inf,
-                                               const uint8_t* __restrict__ hap_lasso, unsigned char* cnt, const unsigned long long* global_best) {
+__device__ __forceinline__ void k5_pair_counts(const PairConsts& c, int i, int j, const uint8_t* __restrict__ chains, const int32_t* __restrict__ chain_len, unsigned char* cnt) {
     const uint8_t* ci = chains + (size_t)i * c.maxlen; const uint8_t* cj = chains + (size_t)j * c.maxlen;
     const int ni = chain_len[i], nj = chain_len[j];
     for (int h = 0; h < c.H; ++h) cnt[h] = 0;
     for (int x = 0; x < ni; ++x) cnt[ci[x]]++;
     for (int x = 0; x < nj; ++x) cnt[cj[x]]++;
+}
+// The bound a partial cost is held against.  Rank 1 (NB = false): the best complete score so far.  N best (NB = true): `bound` is N slots, slot s the smallest score of
+// the pairs with pid % N == s (+inf until one is scored); their maximum is at or above N distinct pairs' scores, so a pair strictly above it is none of the N best.
+// Until every slot is filled the maximum is +inf: nothing is pruned.  (scores are >= 0: bit order = numeric order)
+template <bool NB>
+__device__ __forceinline__ double k5_bound(const PairConsts& c, const unsigned long long* bound) {
+    unsigned long long b = __hip_atomic_load(bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (NB) for (int s = 1; s < c.nbest; ++s) {
+        const unsigned long long v = __hip_atomic_load(bound + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        b = v > b ? v : b;
+    }
+    return __longlong_as_double((long long)b);
+}
+template <bool NB = false>
+__device__ __forceinline__ K5Head k5_pair_head(const PairConsts& c, int i, int j, const uint8_t* __restrict__ chains, const int32_t* __restrict__ chain_len,
+                                               const uint32_t* __restrict__ chain_unexp, const uint32_t* __restrict__ chain_inf,
+                                               const uint8_t* __restrict__ hap_lasso, unsigned char* cnt, const unsigned long long* global_best) {
+    k5_pair_counts(c, i, j, chains, chain_len, cnt);
     int unexpected_alleles = 0;
     for (int h = 0; h < c.H; ++h) if (hap_lasso[h] && cnt[h] > 0) unexpected_alleles += cnt[h] - 1;
     K5Head hd;
@@ -156,7 +173,7 @@ __device__ __forceinline__ K5Head k5_pair_head(const PairConsts& c, int i, int j
     hd.cost[1] = (double)(c.ignore_limits ? 0u : chain_unexp[i] + chain_unexp[j]) * c.unexpected;
     hd.cost[2] = (double)(c.infer ? chain_inf[i] + chain_inf[j] : 0u) * c.inferred;
     const double partial_cost = hd.cost[0] + hd.cost[1] + hd.cost[2];
-    const double gb = __longlong_as_double((long long)__hip_atomic_load(global_best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const double gb = k5_bound<NB>(c, global_best);
     hd.go = !(partial_cost > gb);
     return hd;
 }
@@ -200,7 +217,7 @@ __device__ __forceinline__ unsigned long long k5_saturating_add(unsigned long lo
 __device__ __forceinline__ double k5_primary(double ln_ed_penalty, double mn, const double* cost) { return ln_ed_penalty + mn + cost[0] + cost[1] + cost[2]; }
 
 // the new bound for the pruning (scores are >= 0: bit order = numeric order) and the record of a block's best pair.  The atomic comes first: placed after the
-// stores it cost k5_pair_kernel a stack slot that nothing uses (profiles/k5/refactor_resources.txt)
+// stores it cost k5_pair_kernel a stack slot that nothing uses (profiles/k5/refactor_resources.txt).  In the N-best mode global_best is the pair's slot of k5_bound.
 __device__ __forceinline__ void k5_store_result(size_t slot, unsigned long long pid, double ln_ed_penalty, double mn, const double* cost, unsigned long long ed,
                                                 double* __restrict__ blk_score, unsigned long long* __restrict__ blk_pid, double* __restrict__ blk_comp,
                                                 unsigned long long* __restrict__ blk_ed, unsigned long long* __restrict__ global_best) {
@@ -210,7 +227,22 @@ __device__ __forceinline__ void k5_store_result(size_t slot, unsigned long long 
     double* cp = blk_comp + slot * 5; cp[0] = ln_ed_penalty; cp[1] = mn; cp[2] = cost[0]; cp[3] = cost[1]; cp[4] = cost[2];
 }
 
-// one thread = one unordered pair (i <= j)
+// block-level lexicographic min (score, pid) over the 256 entries; the winner ends in entry 0 (pid K5_NO_PAIR: the block has no entry)
+__device__ __forceinline__ void k5_block_argmin(double* s_score, unsigned long long* s_pid) {
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            const double so = s_score[threadIdx.x + o]; const unsigned long long po = s_pid[threadIdx.x + o];
+            if (po != K5_NO_PAIR && (s_pid[threadIdx.x] == K5_NO_PAIR || so < s_score[threadIdx.x] ||
+                                     (so == s_score[threadIdx.x] && po < s_pid[threadIdx.x]))) { s_score[threadIdx.x] = so; s_pid[threadIdx.x] = po; }
+        }
+        __syncthreads();
+    }
+}
+
+// one thread = one unordered pair (i <= j).  NB (the N-best mode, sp_cyp_best_chain_pairs): the pruning is against k5_bound<true>, every valid pair lowers its slot
+// there, and the block writes its c.nbest best pairs (records blockIdx.x * c.nbest + rank), not its best one
+template <bool NB>
 __global__ __launch_bounds__(256) void k5_pair_kernel(PairConsts c,
                                                       const uint8_t* __restrict__ chains, const int32_t* __restrict__ chain_len,   // [P][maxlen]
                                                       const uint32_t* __restrict__ chain_unexp, const uint32_t* __restrict__ chain_inf,
@@ -236,7 +268,7 @@ __global__ __launch_bounds__(256) void k5_pair_kernel(PairConsts c,
         int i, j; k5_pair_from_id(pid, c.P, i, j);
         const uint8_t* ci = chains + (size_t)i * c.maxlen; const uint8_t* cj = chains + (size_t)j * c.maxlen;
         unsigned char cnt[K5_MAXH];
-        head = k5_pair_head(c, i, j, chains, chain_len, chain_unexp, chain_inf, hap_lasso, cnt, global_best);
+        head = k5_pair_head<NB>(c, i, j, chains, chain_len, chain_unexp, chain_inf, hap_lasso, cnt, global_best);
         if (head.go) {
             scored = 1;
             // per-haplotype coverage of this thread's pair, in LDS ([h][thread]: conflict-free): indexed by data, the array lived in scratch memory and
@@ -277,18 +309,27 @@ __global__ __launch_bounds__(256) void k5_pair_kernel(PairConsts c,
     }
     // block-level lexicographic min (score, pid)
     __shared__ double s_score[256]; __shared__ unsigned long long s_pid[256];
-    s_score[threadIdx.x] = have ? primary : 1.0e308 * 10.0; s_pid[threadIdx.x] = have ? pid : K5_NO_PAIR;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const double so = s_score[threadIdx.x + o]; const unsigned long long po = s_pid[threadIdx.x + o];
-            if (po != K5_NO_PAIR && (s_pid[threadIdx.x] == K5_NO_PAIR || so < s_score[threadIdx.x] ||
-                                     (so == s_score[threadIdx.x] && po < s_pid[threadIdx.x]))) { s_score[threadIdx.x] = so; s_pid[threadIdx.x] = po; }
+    if constexpr (!NB) {
+        s_score[threadIdx.x] = have ? primary : 1.0e308 * 10.0; s_pid[threadIdx.x] = have ? pid : K5_NO_PAIR;
+        k5_block_argmin(s_score, s_pid);
+        if (have && s_pid[0] == pid) k5_store_result(blockIdx.x, pid, ln_ed_penalty, mn, head.cost, read_combined_ed, blk_score, blk_pid, blk_comp, blk_ed, global_best);
+        else if (threadIdx.x == 0 && s_pid[0] == K5_NO_PAIR) blk_pid[blockIdx.x] = K5_NO_PAIR;
+    } else {
+        // c.nbest rounds of the same min, each retiring its winner; a block with fewer valid pairs stops early (its other records keep the K5_NO_PAIR they were cleared to)
+        unsigned long long* const slot = global_best + pid % (unsigned long long)c.nbest;
+        if (have) atomicMin(slot, (unsigned long long)__double_as_longlong(primary));
+        for (int k = 0; k < c.nbest; ++k) {
+            s_score[threadIdx.x] = have ? primary : 1.0e308 * 10.0; s_pid[threadIdx.x] = have ? pid : K5_NO_PAIR;
+            k5_block_argmin(s_score, s_pid);
+            const unsigned long long w = s_pid[0];
+            __syncthreads();                                                  // (everyone has read the winner before the next round overwrites it)
+            if (w == K5_NO_PAIR) break;
+            if (have && w == pid) {
+                k5_store_result((size_t)blockIdx.x * c.nbest + k, pid, ln_ed_penalty, mn, head.cost, read_combined_ed, blk_score, blk_pid, blk_comp, blk_ed, slot);
+                have = false;
+            }
         }
-        __syncthreads();
     }
-    if (have && s_pid[0] == pid) k5_store_result(blockIdx.x, pid, ln_ed_penalty, mn, head.cost, read_combined_ed, blk_score, blk_pid, blk_comp, blk_ed, global_best);
-    else if (threadIdx.x == 0 && s_pid[0] == K5_NO_PAIR) blk_pid[blockIdx.x] = K5_NO_PAIR;
 }
 
 // The same score with one WORKGROUP per pair, for the few pairs of an ordinary sample (tens to hundreds: a thread per pair walks the reads one after another, 1.1 us
@@ -297,43 +338,18 @@ __global__ __launch_bounds__(256) void k5_pair_kernel(PairConsts c,
 // operands in the same order.  A read with more than K5_ADDS addends is added up from memory at its turn.
 #define K5_TILE 256
 #define K5_ADDS 8
-__global__ __launch_bounds__(K5_TILE) void k5_pair_block_kernel(PairConsts c,
-                                                      const uint8_t* __restrict__ chains, const int32_t* __restrict__ chain_len,
-                                                      const uint32_t* __restrict__ chain_unexp, const uint32_t* __restrict__ chain_inf,
-                                                      const uint8_t* __restrict__ chain_has_del,
-                                                      const uint8_t* __restrict__ hap_lasso, const uint8_t* __restrict__ hap_norm,
-                                                      const int32_t* __restrict__ read_w_off, const double* __restrict__ w_ov,
-                                                      const unsigned long long* __restrict__ tab_best, const unsigned long long* __restrict__ tab_mask,
-                                                      const uint64_t* __restrict__ read_optimum, const uint64_t* __restrict__ read_worst,
-                                                      const double* __restrict__ ln_fact, int ln_fact_n,
-                                                      const double* __restrict__ ln_p, int ln_p_stride,
-                                                      unsigned long long* __restrict__ global_best,
-                                                      double* __restrict__ blk_score, unsigned long long* __restrict__ blk_pid,
-                                                      double* __restrict__ blk_comp, unsigned long long* __restrict__ blk_ed,
-                                                      unsigned long long* __restrict__ n_scored) {
-    __shared__ double s_val[K5_TILE * K5_ADDS];
-    __shared__ unsigned long long s_con[K5_TILE];                             // the regions of a read's addends, a byte each (255: none)
-    __shared__ int s_nadd[K5_TILE];
-    __shared__ unsigned long long s_ed[K5_TILE];
-    __shared__ double s_hw[K5_MAXH];
-    __shared__ unsigned char s_cnt[K5_MAXH];
-    __shared__ K5Head s_head;
-    const uint64_t pid = blockIdx.x;
+// the read walk of a workgroup for pair (i, j): on return thread h < H holds region h's coverage in acc, and every thread its share of the reads' edit distance above
+// their optimum in ed_part.  s_val / s_con / s_nadd: K5_TILE * K5_ADDS doubles, K5_TILE words (the regions of a read's addends, a byte each; 255: none), K5_TILE ints
+__device__ __forceinline__ void k5_block_coverage(const PairConsts& c, int i, int j, const uint8_t* __restrict__ ci, const uint8_t* __restrict__ cj,
+                                                  const int32_t* __restrict__ read_w_off, const double* __restrict__ w_ov,
+                                                  const unsigned long long* __restrict__ tab_best, const unsigned long long* __restrict__ tab_mask,
+                                                  const uint64_t* __restrict__ read_optimum, const uint64_t* __restrict__ read_worst,
+                                                  double* s_val, unsigned long long* s_con, int* s_nadd, double& acc, unsigned long long& ed_part) {
     const int H = c.H, tid = (int)threadIdx.x;
-    int i, j; k5_pair_from_id(pid, c.P, i, j);
-    const uint8_t* ci = chains + (size_t)i * c.maxlen; const uint8_t* cj = chains + (size_t)j * c.maxlen;
-    if (tid == 0) {
-        s_head = k5_pair_head(c, i, j, chains, chain_len, chain_unexp, chain_inf, hap_lasso, s_cnt, global_best);
-        if (!s_head.go) blk_pid[pid] = K5_NO_PAIR;
-    }
-    __syncthreads();
-    if (!s_head.go) return;
     auto terms = [&](int r) {
         return k5_read_terms(read_w_off[r], read_w_off[r + 1], tab_best[(size_t)r * c.P + i], tab_best[(size_t)r * c.P + j],
                              tab_mask[(size_t)r * c.P + i], tab_mask[(size_t)r * c.P + j], read_worst[r], read_optimum[r]);
     };
-    double acc = 0.0;                                                         // thread h: the coverage of region h
-    unsigned long long ed_part = 0;
     for (int base = 0; base < c.R; base += K5_TILE) {
         const int r = base + tid;
         int nadd = 0;
@@ -374,6 +390,44 @@ __global__ __launch_bounds__(K5_TILE) void k5_pair_block_kernel(PairConsts c,
         }
         __syncthreads();
     }
+}
+
+// NB (the N-best mode): the pruning is against k5_bound<true> and the pair lowers its slot there; the records are a slot per pair as on the rank-1 path
+template <bool NB>
+__global__ __launch_bounds__(K5_TILE) void k5_pair_block_kernel(PairConsts c,
+                                                      const uint8_t* __restrict__ chains, const int32_t* __restrict__ chain_len,
+                                                      const uint32_t* __restrict__ chain_unexp, const uint32_t* __restrict__ chain_inf,
+                                                      const uint8_t* __restrict__ chain_has_del,
+                                                      const uint8_t* __restrict__ hap_lasso, const uint8_t* __restrict__ hap_norm,
+                                                      const int32_t* __restrict__ read_w_off, const double* __restrict__ w_ov,
+                                                      const unsigned long long* __restrict__ tab_best, const unsigned long long* __restrict__ tab_mask,
+                                                      const uint64_t* __restrict__ read_optimum, const uint64_t* __restrict__ read_worst,
+                                                      const double* __restrict__ ln_fact, int ln_fact_n,
+                                                      const double* __restrict__ ln_p, int ln_p_stride,
+                                                      unsigned long long* __restrict__ global_best,
+                                                      double* __restrict__ blk_score, unsigned long long* __restrict__ blk_pid,
+                                                      double* __restrict__ blk_comp, unsigned long long* __restrict__ blk_ed,
+                                                      unsigned long long* __restrict__ n_scored) {
+    __shared__ double s_val[K5_TILE * K5_ADDS];
+    __shared__ unsigned long long s_con[K5_TILE];                             // the regions of a read's addends, a byte each (255: none)
+    __shared__ int s_nadd[K5_TILE];
+    __shared__ unsigned long long s_ed[K5_TILE];
+    __shared__ double s_hw[K5_MAXH];
+    __shared__ unsigned char s_cnt[K5_MAXH];
+    __shared__ K5Head s_head;
+    const uint64_t pid = blockIdx.x;
+    const int H = c.H, tid = (int)threadIdx.x;
+    int i, j; k5_pair_from_id(pid, c.P, i, j);
+    const uint8_t* ci = chains + (size_t)i * c.maxlen; const uint8_t* cj = chains + (size_t)j * c.maxlen;
+    if (tid == 0) {
+        s_head = k5_pair_head<NB>(c, i, j, chains, chain_len, chain_unexp, chain_inf, hap_lasso, s_cnt, global_best);
+        if (!s_head.go) blk_pid[pid] = K5_NO_PAIR;
+    }
+    __syncthreads();
+    if (!s_head.go) return;
+    double acc = 0.0;                                                         // thread h: the coverage of region h
+    unsigned long long ed_part = 0;
+    k5_block_coverage(c, i, j, ci, cj, read_w_off, w_ov, tab_best, tab_mask, read_optimum, read_worst, s_val, s_con, s_nadd, acc, ed_part);
     if (tid < H) s_hw[tid] = acc;
     s_ed[tid] = ed_part;
     __syncthreads();
@@ -386,29 +440,104 @@ __global__ __launch_bounds__(K5_TILE) void k5_pair_block_kernel(PairConsts c,
                                      chain_has_del[i] && chain_has_del[j], valid);
     atomicAdd(n_scored, 1ull);
     if (!valid) { blk_pid[pid] = K5_NO_PAIR; return; }
-    k5_store_result(pid, pid, ln_ed_penalty, mn, s_head.cost, read_combined_ed, blk_score, blk_pid, blk_comp, blk_ed, global_best);
+    unsigned long long* slot = global_best;
+    if constexpr (NB) slot += pid % (unsigned long long)c.nbest;
+    k5_store_result(pid, pid, ln_ed_penalty, mn, s_head.cost, read_combined_ed, blk_score, blk_pid, blk_comp, blk_ed, slot);
+}
+
+// ---- the N-best mode's two small kernels (sp_cyp_best_chain_pairs) ----
+
+// One workgroup reduces the M candidate records of the pair kernel (a slot per pair, or c.nbest per block of the thread kernel; pid K5_NO_PAIR: empty) to the N smallest
+// under (score, pid) -- pid order is (i, j) order --, ascending, and writes them compactly: round k takes the smallest candidate above round k-1's (pids are distinct,
+// so nothing is marked), a strided scan per thread and the lexicographic min over LDS.  fin_pid[k] = K5_NO_PAIR from the first round that finds none.
+// head[0] = pairs scored (copied from the pair kernel's counter), head[1] = records written.
+__global__ __launch_bounds__(256) void k5_alt_select_kernel(unsigned long long M, int N, const double* __restrict__ blk_score, const unsigned long long* __restrict__ blk_pid,
+                                                            const double* __restrict__ blk_comp, const unsigned long long* __restrict__ blk_ed,
+                                                            const unsigned long long* __restrict__ n_scored, unsigned long long* __restrict__ head,
+                                                            double* __restrict__ fin_score, unsigned long long* __restrict__ fin_pid,
+                                                            double* __restrict__ fin_comp, unsigned long long* __restrict__ fin_ed) {
+    __shared__ double s_score[256]; __shared__ unsigned long long s_pid[256];
+    __shared__ unsigned long long s_at[256];                                  // where each thread's candidate lies; looked up by the winner's thread
+    const int tid = (int)threadIdx.x;
+    double last_s = 0.0; unsigned long long last_p = 0;
+    int found = 0;
+    for (int k = 0; k < N; ++k) {
+        double bs = 1.0e308 * 10.0; unsigned long long bp = K5_NO_PAIR, bat = 0;
+        for (unsigned long long q = (unsigned long long)tid; q < M; q += 256) {
+            const unsigned long long p = blk_pid[q];
+            if (p == K5_NO_PAIR) continue;
+            const double s = blk_score[q];
+            if (k > 0 && !(s > last_s || (s == last_s && p > last_p))) continue;
+            if (bp == K5_NO_PAIR || s < bs || (s == bs && p < bp)) { bs = s; bp = p; bat = q; }
+        }
+        s_score[tid] = bs; s_pid[tid] = bp; s_at[tid] = bat;
+        k5_block_argmin(s_score, s_pid);
+        const unsigned long long w = s_pid[0]; const double ws = s_score[0];
+        __syncthreads();
+        if (w == K5_NO_PAIR) break;
+        if (bp == w) {                                                        // (pids are distinct: one thread)
+            fin_score[k] = ws; fin_pid[k] = w; fin_ed[k] = blk_ed[bat];
+            for (int x = 0; x < 5; ++x) fin_comp[(size_t)k * 5 + x] = blk_comp[(size_t)bat * 5 + x];
+        }
+        last_s = ws; last_p = w; ++found;
+    }
+    if (tid == 0) { for (int k = found; k < N; ++k) fin_pid[k] = K5_NO_PAIR; head[0] = *n_scored; head[1] = (unsigned long long)found; }
+}
+
+// What the score of a winner was made from, for the N winners only, one workgroup each: hap_counts[k][h] = copies of region h in the pair, hap_weights[k][h] = the
+// coverage the reads gave it -- k5_block_coverage's sums, the operands and the order the score saw.
+__global__ __launch_bounds__(K5_TILE) void k5_alt_coverage_kernel(PairConsts c, const uint8_t* __restrict__ chains, const int32_t* __restrict__ chain_len,
+                                                                  const int32_t* __restrict__ read_w_off, const double* __restrict__ w_ov,
+                                                                  const unsigned long long* __restrict__ tab_best, const unsigned long long* __restrict__ tab_mask,
+                                                                  const uint64_t* __restrict__ read_optimum, const uint64_t* __restrict__ read_worst,
+                                                                  const unsigned long long* __restrict__ fin_pid, int32_t* __restrict__ hap_counts, double* __restrict__ hap_weights) {
+    __shared__ double s_val[K5_TILE * K5_ADDS];
+    __shared__ unsigned long long s_con[K5_TILE];
+    __shared__ int s_nadd[K5_TILE];
+    __shared__ unsigned char s_cnt[K5_MAXH];
+    const unsigned long long pid = fin_pid[blockIdx.x];
+    if (pid == K5_NO_PAIR || pid >= c.n_pairs) return;
+    const int H = c.H, tid = (int)threadIdx.x;
+    int i, j; k5_pair_from_id(pid, c.P, i, j);
+    const uint8_t* ci = chains + (size_t)i * c.maxlen; const uint8_t* cj = chains + (size_t)j * c.maxlen;
+    if (tid == 0) k5_pair_counts(c, i, j, chains, chain_len, s_cnt);
+    double acc = 0.0;
+    unsigned long long ed_part = 0;
+    k5_block_coverage(c, i, j, ci, cj, read_w_off, w_ov, tab_best, tab_mask, read_optimum, read_worst, s_val, s_con, s_nadd, acc, ed_part);
+    __syncthreads();
+    if (tid < H) { hap_counts[(size_t)blockIdx.x * H + tid] = (int32_t)s_cnt[tid]; hap_weights[(size_t)blockIdx.x * H + tid] = acc; }
 }
 
 // =============================================================================================
 // host
 // =============================================================================================
-extern "C" int32_t sp_cyp_best_chain_pair(sp_ctx* ctx, const sp_chain_problem* p, sp_chain_result* res) {
-    if (!ctx || !p || !res || (p->n_haps && !p->hap_type)) return SP_ERR_INVALID_ARG;
-    std::memset(res, 0, sizeof(*res));
-    (void)hipSetDevice(ctx->device);
-    const int H = (int)p->n_haps;
+namespace {
+
+// the host part of find_best_chain_pair up to the scoring loop: the label grammar, the edge tables and the chains, in enumeration order
+struct K5Chains {
+    int H = 0; bool ignore = false, norm_all = false, infer = false;
+    std::vector<int> type; std::vector<std::string> simple;
+    std::vector<uint8_t> inferred;                                           // [H][H] inferred edges
+    std::vector<std::vector<int>> possible;
+};
+bool k5_connected(const sp_chain_problem* p, const std::string& a, const std::string& b) {
+    for (uint32_t i = 0; i < p->n_connections; ++i) if (a == p->connection_a[i] && b == p->connection_b[i]) return true;
+    return false;
+}
+int32_t k5_enumerate(sp_ctx* ctx, const sp_chain_problem* p, K5Chains& e) {              // ctx: for the error text only; NULL is allowed (sp_cyp_possible_chains)
+    auto sp_fail = [](sp_ctx* c, int code, const char* msg) { return c ? ::sp_fail(c, code, msg) : code; };
+    const int H = e.H = (int)p->n_haps;
     if (H > K5_MAXH) return sp_fail(ctx, SP_ERR_INVALID_ARG, "chain pair: more than 64 consensus regions");
     if (p->lasso_penalty < 0.0) return sp_fail(ctx, SP_ERR_INVALID_ARG, "Lasso penalty must be >= 0.0");      // chaining.rs:233-235
-    const bool ignore = p->ignore_chain_label_limits != 0, norm_all = p->normalize_all_alleles != 0, infer = p->infer_connections != 0;
-    std::vector<int> type(p->hap_type, p->hap_type + H);
-    std::vector<std::string> simple(H);
+    const bool ignore = e.ignore = p->ignore_chain_label_limits != 0, norm_all = e.norm_all = p->normalize_all_alleles != 0, infer = e.infer = p->infer_connections != 0;
+    e.type.assign(p->hap_type, p->hap_type + H);
+    e.simple.resize(H);
+    const std::vector<int>& type = e.type; std::vector<std::string>& simple = e.simple;
     for (int h = 0; h < H; ++h) simple[h] = simple_allele(p, (uint32_t)h);
-    auto connected = [&](const std::string& a, const std::string& b) {
-        for (uint32_t i = 0; i < p->n_connections; ++i) if (a == p->connection_a[i] && b == p->connection_b[i]) return true;
-        return false;
-    };
+    auto connected = [&](const std::string& a, const std::string& b) { return k5_connected(p, a, b); };
     // observed edges (chaining.rs:245-264)
-    std::vector<uint8_t> down((size_t)H * H, 0), inferred((size_t)H * H, 0);
+    std::vector<uint8_t> down((size_t)H * H, 0); e.inferred.assign((size_t)H * H, 0);
+    std::vector<uint8_t>& inferred = e.inferred;
     for (uint32_t r = 0; r < p->n_reads; ++r)
         for (uint32_t c = p->read_chain_off[r]; c < p->read_chain_off[r + 1]; ++c)
             for (uint32_t x = p->chain_off[c] + 1; x < p->chain_off[c + 1]; ++x) {
@@ -429,7 +558,8 @@ extern "C" int32_t sp_cyp_best_chain_pair(sp_ctx* ctx, const sp_chain_problem* p
     for (int i = 0; i < H; ++i) if (ignore || t_head(type[i], norm_all)) stack.push_back({i});
     if (stack.empty()) return SP_ERR_NO_CHAINING_HEAD;
     // LIFO enumeration, copy number <= 3 (chaining.rs:326-391)
-    std::vector<std::vector<int>> possible;
+    std::vector<std::vector<int>>& possible = e.possible;
+    possible.clear();
     while (!stack.empty()) {
         std::vector<int> cur = std::move(stack.back()); stack.pop_back();
         // check_chain_inferrences (chaining.rs:603-674)
@@ -467,9 +597,22 @@ extern "C" int32_t sp_cyp_best_chain_pair(sp_ctx* ctx, const sp_chain_problem* p
         }
     }
     if (possible.empty()) return SP_ERR_NO_CHAINS_FOUND;
-    const int P = (int)possible.size();
-    res->n_possible = P;
+    return SP_OK;
+}
 
+// the problem on the device: the fourteen input arrays, the per-(chain, read) tables (k5_chain_read_kernel is launched here) and what the pair kernels are launched with
+struct K5Device {
+    PairConsts pc; int lf_n = 0, lp_stride = 0;
+    uint64_t n_pairs = 0, blocks = 0; bool block_per_pair = false;
+    uint8_t* chains; int32_t* clen; uint32_t* unexp; uint32_t* ninf; uint8_t* del; uint8_t* lasso; uint8_t* norm; int32_t* rwo; double* ov;
+    uint64_t* opt; uint64_t* worst; double* lf; double* lp; unsigned long long* tb; unsigned long long* tm;
+};
+int32_t k5_upload(sp_ctx* ctx, const sp_chain_problem* p, const K5Chains& e, int nbest, K5Device& d) {
+    const int H = e.H; const bool ignore = e.ignore, norm_all = e.norm_all, infer = e.infer;
+    const std::vector<int>& type = e.type; const std::vector<std::string>& simple = e.simple; const std::vector<uint8_t>& inferred = e.inferred;
+    const std::vector<std::vector<int>>& possible = e.possible;
+    auto connected = [&](const std::string& a, const std::string& b) { return k5_connected(p, a, b); };
+    const int P = (int)possible.size();
     // flatten for the device
     int maxlen = 1; for (auto& c : possible) maxlen = std::max(maxlen, (int)c.size());
     std::vector<uint8_t> chains((size_t)P * maxlen, 0), has_del(P, 0);
@@ -519,12 +662,13 @@ extern "C" int32_t sp_cyp_best_chain_pair(sp_ctx* ctx, const sp_chain_problem* p
     std::vector<double> ln_p((size_t)(max_cnt + 1) * (max_total + 1), 0.0);
     for (int cc = 1; cc <= max_cnt; ++cc) for (int t = cc; t <= max_total; ++t) ln_p[(size_t)cc * (max_total + 1) + t] = std::log((double)cc / (double)t);
 
-    const uint64_t n_pairs = (uint64_t)P * ((uint64_t)P + 1) / 2;
-    const bool block_per_pair = n_pairs <= (uint64_t)ctx->k5_block_pairs;   // (k5_pair_block_kernel)
-    const uint64_t blocks = block_per_pair ? n_pairs : (n_pairs + 255) / 256;
-    if (blocks > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_TOO_LONG, "chain pair: too many chain pairs for one launch");
-    PairConsts pc{H, P, maxlen, R, ignore ? 1 : 0, norm_all ? 1 : 0, infer ? 1 : 0, p->lasso_penalty, p->ln_ed_penalty, p->unexpected_chain_penalty,
-                  p->inferred_edge_penalty, n_pairs};
+    const uint64_t n_pairs = d.n_pairs = (uint64_t)P * ((uint64_t)P + 1) / 2;
+    d.block_per_pair = n_pairs <= (uint64_t)ctx->k5_block_pairs;             // (k5_pair_block_kernel)
+    d.blocks = d.block_per_pair ? n_pairs : (n_pairs + 255) / 256;
+    if (d.blocks > 0x7FFFFFFFull) return sp_fail(ctx, SP_ERR_TOO_LONG, "chain pair: too many chain pairs for one launch");
+    d.pc = PairConsts{H, P, maxlen, R, ignore ? 1 : 0, norm_all ? 1 : 0, infer ? 1 : 0, nbest, p->lasso_penalty, p->ln_ed_penalty, p->unexpected_chain_penalty,
+                      p->inferred_edge_penalty, n_pairs};
+    d.lf_n = lf_n; d.lp_stride = max_total + 1;
     std::vector<double> ovv(p->w_ov, p->w_ov + (size_t)n_rows * H);
     // the fourteen input arrays go up in ONE copy out of a pinned staging buffer (a copy each was fourteen links in the stream's chain: 0.2 ms of a small sample)
     size_t in_bytes = 0;
@@ -539,41 +683,71 @@ extern "C" int32_t sp_cyp_best_chain_pair(sp_ctx* ctx, const sp_chain_problem* p
     put(at_chains, chains); put(at_clen, clen); put(at_unexp, unexp); put(at_ninf, ninf); put(at_del, has_del); put(at_lasso, hap_lasso); put(at_norm, hap_norm); put(at_rwo, rwo);
     put(at_ed, ed32); put(at_ov, ovv); put(at_opt, optimum); put(at_worst, worst); put(at_lf, ln_fact); put(at_lp, ln_p);
     (void)hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-    uint8_t* d_chains = d_in + at_chains; int32_t* d_clen = (int32_t*)(d_in + at_clen);
-    uint32_t* d_unexp = (uint32_t*)(d_in + at_unexp); uint32_t* d_ninf = (uint32_t*)(d_in + at_ninf);
-    uint8_t* d_del = d_in + at_del; uint8_t* d_lasso = d_in + at_lasso; uint8_t* d_norm = d_in + at_norm;
-    int32_t* d_rwo = (int32_t*)(d_in + at_rwo); uint32_t* d_ed = (uint32_t*)(d_in + at_ed); double* d_ov = (double*)(d_in + at_ov);
-    uint64_t* d_opt = (uint64_t*)(d_in + at_opt); uint64_t* d_worst = (uint64_t*)(d_in + at_worst);
-    double* d_lf = (double*)(d_in + at_lf); double* d_lp = (double*)(d_in + at_lp);
-    // the results likewise come down in one copy: [global best, pairs scored | block scores | block pair ids | block edit distances | block components]
+    d.chains = d_in + at_chains; d.clen = (int32_t*)(d_in + at_clen);
+    d.unexp = (uint32_t*)(d_in + at_unexp); d.ninf = (uint32_t*)(d_in + at_ninf);
+    d.del = d_in + at_del; d.lasso = d_in + at_lasso; d.norm = d_in + at_norm;
+    d.rwo = (int32_t*)(d_in + at_rwo); uint32_t* d_ed = (uint32_t*)(d_in + at_ed); d.ov = (double*)(d_in + at_ov);
+    d.opt = (uint64_t*)(d_in + at_opt); d.worst = (uint64_t*)(d_in + at_worst);
+    d.lf = (double*)(d_in + at_lf); d.lp = (double*)(d_in + at_lp);
+    d.tb = (unsigned long long*)sp_pool(ctx, "k5_tab_best", std::max<size_t>(1, (size_t)P * R) * 8);
+    d.tm = (unsigned long long*)sp_pool(ctx, "k5_tab_mask", std::max<size_t>(1, (size_t)P * R) * 8);
+    if (!d.tb || !d.tm) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "chain pair tables");
+    if ((size_t)P * R) {
+        ProfScope ps(ctx, "k5_chain_reads", (uint64_t)P * R);
+        hipLaunchKernelGGL(k5_chain_read_kernel, dim3((unsigned)(((size_t)P * R + 255) / 256)), dim3(256), 0, ctx->stream, P, R, H, maxlen, d.chains, d.clen, d.rwo, d_ed, d.tb, d.tm);
+    }
+    return SP_OK;
+}
+
+// the pair kernel of the route the problem takes; gb: the bound (rank 1: one word; N best: N slots), the four record arrays, the counter of scored pairs
+template <bool NB>
+void k5_launch_pairs(sp_ctx* ctx, const K5Device& d, unsigned long long* gb, double* bs, unsigned long long* bp, double* bc, unsigned long long* be, unsigned long long* n_scored) {
+    if (d.block_per_pair)
+        hipLaunchKernelGGL(k5_pair_block_kernel<NB>, dim3((unsigned)d.blocks), dim3(K5_TILE), 0, ctx->stream, d.pc, d.chains, d.clen, d.unexp, d.ninf, d.del, d.lasso, d.norm,
+                           d.rwo, d.ov, d.tb, d.tm, d.opt, d.worst, d.lf, d.lf_n, d.lp, d.lp_stride, gb, bs, bp, bc, be, n_scored);
+    else {
+        (void)hipFuncSetAttribute((const void*)k5_pair_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)256 * d.pc.H * sizeof(double)));
+        hipLaunchKernelGGL(k5_pair_kernel<NB>, dim3((unsigned)d.blocks), dim3(256), (size_t)256 * d.pc.H * sizeof(double), ctx->stream, d.pc, d.chains, d.clen, d.unexp, d.ninf, d.del, d.lasso, d.norm,
+                           d.rwo, d.ov, d.tb, d.tm, d.opt, d.worst, d.lf, d.lf_n, d.lp, d.lp_stride, gb, bs, bp, bc, be, n_scored);
+    }
+}
+
+// a pair as the results name it: the two chains sorted (best_chain_pair.sort(), chaining.rs:568-573)
+void k5_sorted_pair(const K5Chains& e, int wi, int wj, int32_t* n1, int32_t* n2, int32_t* chain1, int32_t* chain2) {
+    const std::vector<int>* a = &e.possible[wi]; const std::vector<int>* b = &e.possible[wj];
+    if (*b < *a) std::swap(a, b);
+    *n1 = (int32_t)a->size(); *n2 = (int32_t)b->size();
+    for (size_t x = 0; x < a->size(); ++x) chain1[x] = (*a)[x];
+    for (size_t x = 0; x < b->size(); ++x) chain2[x] = (*b)[x];
+}
+
+} // namespace
+
+extern "C" int32_t sp_cyp_best_chain_pair(sp_ctx* ctx, const sp_chain_problem* p, sp_chain_result* res) {
+    if (!ctx || !p || !res || (p->n_haps && !p->hap_type)) return SP_ERR_INVALID_ARG;
+    std::memset(res, 0, sizeof(*res));
+    (void)hipSetDevice(ctx->device);
+    K5Chains en; K5Device d;
+    int32_t rc = k5_enumerate(ctx, p, en);
+    if (rc != SP_OK) return rc;
+    const int P = (int)en.possible.size();
+    res->n_possible = P;
+    rc = k5_upload(ctx, p, en, 0, d);
+    if (rc != SP_OK) return rc;
+    const uint64_t blocks = d.blocks;
+    // the results come down in one copy: [global best, pairs scored | block scores | block pair ids | block edit distances | block components]
     const size_t out_bytes = 16 + (size_t)blocks * (8 + 8 + 8 + 40);
     uint8_t* d_out = (uint8_t*)sp_pool(ctx, "k5_out", out_bytes); uint8_t* h_out = (uint8_t*)sp_host_pool(ctx, "k5_out", out_bytes);
+    if (!d_out || !h_out) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "chain pair buffers");
     unsigned long long* d_gb = (unsigned long long*)d_out;
     double* d_bs = (double*)(d_out + 16); unsigned long long* d_bp = (unsigned long long*)(d_out + 16 + (size_t)blocks * 8);
     unsigned long long* d_be = (unsigned long long*)(d_out + 16 + (size_t)blocks * 16); double* d_bc = (double*)(d_out + 16 + (size_t)blocks * 24);
-    if (!d_out || !h_out) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "chain pair buffers");
-    if (!d_chains || !d_clen || !d_unexp || !d_ninf || !d_del || !d_lasso || !d_norm || !d_rwo || !d_ed || !d_ov || !d_opt || !d_worst || !d_lf || !d_lp ||
-        !d_gb || !d_bs || !d_bp || !d_bc || !d_be) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "chain pair buffers");
-    unsigned long long* d_tb = (unsigned long long*)sp_pool(ctx, "k5_tab_best", std::max<size_t>(1, (size_t)P * R) * 8);
-    unsigned long long* d_tm = (unsigned long long*)sp_pool(ctx, "k5_tab_mask", std::max<size_t>(1, (size_t)P * R) * 8);
-    if (!d_tb || !d_tm) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "chain pair tables");
-    if ((size_t)P * R) {
-        ProfScope ps(ctx, "k5_chain_reads", (uint64_t)P * R);
-        hipLaunchKernelGGL(k5_chain_read_kernel, dim3((unsigned)(((size_t)P * R + 255) / 256)), dim3(256), 0, ctx->stream, P, R, H, maxlen, d_chains, d_clen, d_rwo, d_ed, d_tb, d_tm);
-    }
     const unsigned long long init[2] = {0x7FF0000000000000ull /* +inf */, 0ull};
     (void)hipMemcpyAsync(d_gb, init, 16, hipMemcpyHostToDevice, ctx->stream);
     (void)hipMemsetAsync(d_bp, 0xFF, blocks * 8, ctx->stream);
     {
-        ProfScope ps(ctx, "k5_pairs", n_pairs);
-        if (block_per_pair)
-            hipLaunchKernelGGL(k5_pair_block_kernel, dim3((unsigned)blocks), dim3(K5_TILE), 0, ctx->stream, pc, d_chains, d_clen, d_unexp, d_ninf, d_del, d_lasso, d_norm,
-                               d_rwo, d_ov, d_tb, d_tm, d_opt, d_worst, d_lf, lf_n, d_lp, max_total + 1, d_gb, d_bs, d_bp, d_bc, d_be, d_gb + 1);
-        else {
-            (void)hipFuncSetAttribute((const void*)k5_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)256 * H * sizeof(double)));
-            hipLaunchKernelGGL(k5_pair_kernel, dim3((unsigned)blocks), dim3(256), (size_t)256 * H * sizeof(double), ctx->stream, pc, d_chains, d_clen, d_unexp, d_ninf, d_del, d_lasso, d_norm,
-                               d_rwo, d_ov, d_tb, d_tm, d_opt, d_worst, d_lf, lf_n, d_lp, max_total + 1, d_gb, d_bs, d_bp, d_bc, d_be, d_gb + 1);
-        }
+        ProfScope ps(ctx, "k5_pairs", d.n_pairs);
+        k5_launch_pairs<false>(ctx, d, d_gb, d_bs, d_bp, d_bc, d_be, d_gb + 1);
         if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "k5 launch failed");
     }
     (void)hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
@@ -593,11 +767,121 @@ extern "C" int32_t sp_cyp_best_chain_pair(sp_ctx* ctx, const sp_chain_problem* p
     res->index1 = wi; res->index2 = wj;
     res->score = bs[wb]; res->ln_ed_penalty = bc[wb * 5]; res->mn_llh_penalty = bc[wb * 5 + 1]; res->allele_expected_penalty = bc[wb * 5 + 2];
     res->unexpected_chain_penalty = bc[wb * 5 + 3]; res->inferred_chain_penalty = bc[wb * 5 + 4]; res->edit_distance = be[wb];
-    const std::vector<int>* a = &possible[wi]; const std::vector<int>* b = &possible[wj];
-    if (*b < *a) std::swap(a, b);                              // best_chain_pair.sort() (chaining.rs:568-573)
-    res->n1 = (int32_t)a->size(); res->n2 = (int32_t)b->size();
-    for (size_t x = 0; x < a->size(); ++x) res->chain1[x] = (*a)[x];
-    for (size_t x = 0; x < b->size(); ++x) res->chain2[x] = (*b)[x];
+    k5_sorted_pair(en, wi, wj, &res->n1, &res->n2, res->chain1, res->chain2);
+    return SP_OK;
+}
+
+// The N best pairs (the content of the reference's 10-entry heap, chaining.rs:404-405,515-526): the N smallest under (primary_score, i, j) among the valid pairs.
+// Launches: the pair kernel of the problem's route in its N-best mode, k5_alt_select_kernel, k5_alt_coverage_kernel; one copy down of N records.
+extern "C" int32_t sp_cyp_best_chain_pairs(sp_ctx* ctx, const sp_chain_problem* p, uint32_t max_alts, sp_chain_alt* alts, uint32_t* n_alts, int32_t* hap_counts, double* hap_weights,
+                                           sp_chain_result* best) {
+    if (!ctx || !p || !alts || !n_alts || (p->n_haps && !p->hap_type)) return SP_ERR_INVALID_ARG;
+    *n_alts = 0;
+    if (best) std::memset(best, 0, sizeof(*best));
+    if (max_alts < 1 || max_alts > 64) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_best_chain_pairs: max_alts is 1..64");
+    (void)hipSetDevice(ctx->device);
+    K5Chains en; K5Device d;
+    int32_t rc = k5_enumerate(ctx, p, en);
+    if (rc != SP_OK) return rc;
+    const int P = (int)en.possible.size(), H = en.H, N = (int)max_alts;
+    if (best) best->n_possible = P;
+    rc = k5_upload(ctx, p, en, N, d);
+    if (rc != SP_OK) return rc;
+    // candidates (device only): [N bound slots, pairs scored | scores | pair ids | edit distances | components], a record per pair or N per block of the thread kernel
+    const uint64_t M = d.block_per_pair ? d.n_pairs : d.blocks * (uint64_t)N;
+    const size_t head = (((size_t)N + 1) * 8 + 15) & ~(size_t)15;
+    uint8_t* d_cand = (uint8_t*)sp_pool(ctx, "k5_alt_cand", head + (size_t)M * (8 + 8 + 8 + 40));
+    // the N winners (one copy down): [pairs scored, records | scores | pair ids | edit distances | components | hap_counts [N][H] | hap_weights [N][H]]
+    const size_t at_fs = 16, at_fp = at_fs + (size_t)N * 8, at_fe = at_fp + (size_t)N * 8, at_fc = at_fe + (size_t)N * 8, at_cnt = at_fc + (size_t)N * 40,
+                 at_hw = (at_cnt + (size_t)N * std::max(1, H) * 4 + 7) & ~(size_t)7, out_bytes = at_hw + (size_t)N * std::max(1, H) * 8;
+    uint8_t* d_out = (uint8_t*)sp_pool(ctx, "k5_alt_out", out_bytes); uint8_t* h_out = (uint8_t*)sp_host_pool(ctx, "k5_alt_out", out_bytes);
+    if (!d_cand || !d_out || !h_out) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "chain pairs buffers");
+    unsigned long long* d_slots = (unsigned long long*)d_cand;
+    double* d_bs = (double*)(d_cand + head); unsigned long long* d_bp = (unsigned long long*)(d_cand + head + (size_t)M * 8);
+    unsigned long long* d_be = (unsigned long long*)(d_cand + head + (size_t)M * 16); double* d_bc = (double*)(d_cand + head + (size_t)M * 24);
+    unsigned long long init[65];
+    for (int s = 0; s < N; ++s) init[s] = 0x7FF0000000000000ull /* +inf */;
+    init[N] = 0ull;
+    (void)hipMemcpyAsync(d_slots, init, ((size_t)N + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    (void)hipMemsetAsync(d_bp, 0xFF, (size_t)M * 8, ctx->stream);
+    {
+        ProfScope ps(ctx, "k5_alt_pairs", d.n_pairs);
+        k5_launch_pairs<true>(ctx, d, d_slots, d_bs, d_bp, d_bc, d_be, d_slots + N);
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "k5 launch failed");
+    }
+    unsigned long long* d_fp = (unsigned long long*)(d_out + at_fp);
+    {
+        ProfScope ps(ctx, "k5_alt_select", M);
+        hipLaunchKernelGGL(k5_alt_select_kernel, dim3(1), dim3(256), 0, ctx->stream, (unsigned long long)M, N, d_bs, d_bp, d_bc, d_be, d_slots + N, (unsigned long long*)d_out,
+                           (double*)(d_out + at_fs), d_fp, (double*)(d_out + at_fc), (unsigned long long*)(d_out + at_fe));
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "k5 launch failed");
+    }
+    if (hap_counts || hap_weights) {
+        ProfScope ps(ctx, "k5_alt_coverage", (uint64_t)N);
+        hipLaunchKernelGGL(k5_alt_coverage_kernel, dim3((unsigned)N), dim3(K5_TILE), 0, ctx->stream, d.pc, d.chains, d.clen, d.rwo, d.ov, d.tb, d.tm, d.opt, d.worst, d_fp,
+                           (int32_t*)(d_out + at_cnt), (double*)(d_out + at_hw));
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "k5 launch failed");
+    }
+    (void)hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, std::string("chain pairs: ") + hipGetErrorString(e));
+    const unsigned long long* hd = (const unsigned long long*)h_out;
+    const double* fs = (const double*)(h_out + at_fs); const unsigned long long* fp = (const unsigned long long*)(h_out + at_fp);
+    const unsigned long long* fe = (const unsigned long long*)(h_out + at_fe); const double* fc = (const double*)(h_out + at_fc);
+    const uint32_t found = (uint32_t)std::min<unsigned long long>(hd[1], (unsigned long long)N);
+    if (best) best->n_pairs_scored = hd[0];
+    if (found == 0) return SP_ERR_NO_SCORE_PAIRS;
+    for (uint32_t k = 0; k < found; ++k) {
+        sp_chain_alt& a = alts[k];
+        std::memset(&a, 0, sizeof a);
+        if (fp[k] >= d.n_pairs) return sp_fail(ctx, SP_ERR_HIP, "chain pairs: a record names no pair");
+        int wi, wj; k5_pair_from_id(fp[k], P, wi, wj);
+        a.index1 = wi; a.index2 = wj;
+        k5_sorted_pair(en, wi, wj, &a.n1, &a.n2, a.chain1, a.chain2);
+        a.score = fs[k]; a.ln_ed_penalty = fc[k * 5]; a.mn_llh_penalty = fc[k * 5 + 1]; a.allele_expected_penalty = fc[k * 5 + 2];
+        a.unexpected_chain_penalty = fc[k * 5 + 3]; a.inferred_chain_penalty = fc[k * 5 + 4]; a.edit_distance = fe[k];
+        // unmet observations (chaining.rs:427-440): the reads none of whose putative chains is a run of consecutive regions of either chain
+        auto is_sub = [&](const std::vector<int>& hay, const uint32_t* needle, uint32_t n) {
+            for (size_t s = 0; s + n <= hay.size(); ++s) { bool eq = true; for (uint32_t x = 0; x < n && eq; ++x) eq = (uint32_t)hay[s + x] == needle[x]; if (eq) return true; }
+            return false;
+        };
+        for (uint32_t r = 0; r < p->n_reads; ++r) {
+            bool supported = false;
+            for (uint32_t c = p->read_chain_off[r]; c < p->read_chain_off[r + 1] && !supported; ++c) {
+                const uint32_t* needle = p->chain_items + p->chain_off[c]; const uint32_t n = p->chain_off[c + 1] - p->chain_off[c];
+                supported = is_sub(en.possible[wi], needle, n) || is_sub(en.possible[wj], needle, n);
+            }
+            if (!supported) ++a.unmet_observations;
+        }
+        if (hap_counts) std::memcpy(hap_counts + (size_t)k * H, h_out + at_cnt + (size_t)k * H * 4, (size_t)H * 4);
+        if (hap_weights) std::memcpy(hap_weights + (size_t)k * H, h_out + at_hw + (size_t)k * H * 8, (size_t)H * 8);
+    }
+    *n_alts = found;
+    if (best) {
+        const sp_chain_alt& a = alts[0];
+        best->index1 = a.index1; best->index2 = a.index2; best->n1 = a.n1; best->n2 = a.n2;
+        std::memcpy(best->chain1, a.chain1, sizeof a.chain1); std::memcpy(best->chain2, a.chain2, sizeof a.chain2);
+        best->score = a.score; best->ln_ed_penalty = a.ln_ed_penalty; best->mn_llh_penalty = a.mn_llh_penalty; best->allele_expected_penalty = a.allele_expected_penalty;
+        best->unexpected_chain_penalty = a.unexpected_chain_penalty; best->inferred_chain_penalty = a.inferred_chain_penalty; best->edit_distance = a.edit_distance;
+    }
+    return SP_OK;
+}
+
+// the chains find_best_chain_pair enumerates, in enumeration order (host only); *n_chains / *n_items are what the problem has, SP_ERR_CAPACITY when a cap is smaller
+extern "C" int32_t sp_cyp_possible_chains(sp_ctx* ctx, const sp_chain_problem* p, uint32_t* chain_off, uint32_t off_cap, uint32_t* items, uint32_t items_cap,
+                                          uint32_t* n_chains, uint32_t* n_items) {
+    if (!p || !n_chains || !n_items || (p->n_haps && !p->hap_type) || (off_cap && !chain_off) || (items_cap && !items)) return SP_ERR_INVALID_ARG;
+    *n_chains = 0; *n_items = 0;
+    K5Chains en;
+    const int32_t rc = k5_enumerate(ctx, p, en);
+    if (rc != SP_OK) return rc;
+    uint64_t total = 0; for (const auto& c : en.possible) total += c.size();
+    if (total > 0xFFFFFFFFull) return ctx ? sp_fail(ctx, SP_ERR_TOO_LONG, "sp_cyp_possible_chains: more than 2^32 chain items") : SP_ERR_TOO_LONG;
+    *n_chains = (uint32_t)en.possible.size(); *n_items = (uint32_t)total;
+    if ((uint64_t)off_cap < (uint64_t)en.possible.size() + 1 || items_cap < total) return ctx ? sp_fail(ctx, SP_ERR_CAPACITY, "sp_cyp_possible_chains: more chains or items than the caps") : SP_ERR_CAPACITY;
+    uint32_t at = 0;
+    for (size_t c = 0; c < en.possible.size(); ++c) { chain_off[c] = at; for (int h : en.possible[c]) items[at++] = (uint32_t)h; }
+    chain_off[en.possible.size()] = at;
     return SP_OK;
 }
 
@@ -1674,6 +1958,7 @@ struct CypMid {
     std::vector<int32_t> group_of; std::vector<char> text;
     bool finished = false;                                // the call is complete after part (a) already (no reads)
     std::vector<sp_cyp_read_mapping>* mappings = nullptr; // sp_cyp_diplotype_mappings: the reads with one chain (multi_mapping_details)
+    std::string* alternatives = nullptr;                  // sp_starphase_set_cyp_alternatives: the text of cyp2d6_alternatives.json (empty: no call)
     // between (c1), the weights and (c2)
     std::vector<std::string> full_cons, final_cons; std::vector<int32_t> final_group; std::vector<Label> labels; DeepInfo deep; std::vector<uint8_t> allowed;
     std::vector<uint32_t> a_idx, seg_off; std::vector<int32_t> a_start, a_len; uint32_t H = 0;
@@ -2050,8 +2335,23 @@ int32_t cyp_part_c2(sp_ctx* ctx, const sp_cyp_problem* pr, sp_cyp_call* call, ch
     cp.lasso_penalty = 4.0; cp.ln_ed_penalty = 2.0; cp.unexpected_chain_penalty = 10.0; cp.inferred_edge_penalty = 2.0;      // ChainPenalties::default (chaining.rs:107-139)
     sp_chain_result cr;
     hm.mark("host:cyp_chains");
-    rc = sp_cyp_best_chain_pair(ctx, &cp, &cr);
+    sp_chain_alt alts[SP_CYP_ALTERNATIVES]; uint32_t n_alts = 0;
+    std::vector<int32_t> alt_counts; std::vector<double> alt_weights;
+    if (m.alternatives) {                // sp_starphase_set_cyp_alternatives: the N = 10 form of the same search; entry 0 is the call
+        m.alternatives->clear();
+        alt_counts.assign((size_t)SP_CYP_ALTERNATIVES * std::max<uint32_t>(H, 1), 0); alt_weights.assign((size_t)SP_CYP_ALTERNATIVES * std::max<uint32_t>(H, 1), 0.0);
+        rc = sp_cyp_best_chain_pairs(ctx, &cp, SP_CYP_ALTERNATIVES, alts, &n_alts, alt_counts.data(), alt_weights.data(), &cr);
+    } else rc = sp_cyp_best_chain_pair(ctx, &cp, &cr);
     hm.mark("host:cyp_chain_pair");
+    if (rc == SP_OK && m.alternatives) {
+        uint64_t need = 0;
+        sp_cyp_alternatives_json(&cp, (uint32_t)cr.n_possible, nullptr, alts, n_alts, alt_counts.data(), alt_weights.data(), nullptr, 0, &need);
+        std::string text((size_t)need, '\0');
+        if (sp_cyp_alternatives_json(&cp, (uint32_t)cr.n_possible, nullptr, alts, n_alts, alt_counts.data(), alt_weights.data(), &text[0], need, &need) != SP_OK)
+            return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_diplotype: cyp2d6_alternatives.json");
+        text.resize((size_t)need - 1);
+        *m.alternatives = std::move(text);
+    }
     if (rc == SP_ERR_NO_CHAINING_HEAD || rc == SP_ERR_NO_CHAINS_FOUND || rc == SP_ERR_NO_SCORE_PAIRS) { call->status = rc; return SP_OK; }
     if (rc != SP_OK) return rc;
     call->n1 = cr.n1; call->n2 = cr.n2; call->score = cr.score;
@@ -2097,10 +2397,11 @@ int32_t cyp_part_c(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads
 } // namespace
 
 int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
-                                   sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings) {
+                                   sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings, std::string* alternatives) {
     if (!ctx) return SP_ERR_INVALID_ARG;
     CypMid m;
     if (mappings) { mappings->clear(); m.mappings = mappings; }
+    if (alternatives) { alternatives->clear(); m.alternatives = alternatives; }
     int32_t rc = cyp_part_a(ctx, pr, reads, call, region_variants, "cypc", m);
     if (rc != SP_OK || m.finished) return rc;
     {
@@ -2114,6 +2415,7 @@ int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const 
     if (rc != SP_OK) return rc;
     rc = cyp_part_c(ctx, pr, reads, call, consensus, cons_cap, region_variants, m);
     if (mappings && (rc != SP_OK || call->status != 0)) mappings->clear();
+    if (alternatives && (rc != SP_OK || call->status != 0)) alternatives->clear();
     return rc;
 }
 
@@ -2139,7 +2441,7 @@ extern "C" int32_t sp_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* 
 // region_variants / mappings (optional, n_samples entries): what sp_cyp_diplotype_mappings hands out for the sample, filled by the same (a) / (c1) / (c2)
 int32_t spi_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, uint32_t n_samples, const sp_seqset* const* reads, sp_cyp_call* calls,
                                           char* consensus, uint32_t cons_cap, sp_cyp_region_variants* region_variants,
-                                          std::vector<sp_cyp_read_mapping>* mappings, int32_t* sample_rc) {
+                                          std::vector<sp_cyp_read_mapping>* mappings, int32_t* sample_rc, std::string* const* alternatives) {
     if (!ctx) return SP_ERR_INVALID_ARG;
     if (!pr || (n_samples && (!reads || !calls))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_diplotype_cohort: null argument");
     for (uint32_t i = 0; i < n_samples; ++i) if (!reads[i]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_diplotype_cohort: null read set");
@@ -2180,6 +2482,7 @@ int32_t spi_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* pr,
                     where[i] = x;
                     mids[k].reset(new CypMid());
                     if (mappings) { mappings[i].clear(); mids[k]->mappings = &mappings[i]; }
+                    if (alternatives && alternatives[i]) { alternatives[i]->clear(); mids[k]->alternatives = alternatives[i]; }
                     const std::string prefix = "cypc" + std::to_string(k);
                     if (searched && rc_regions != SP_OK) { rcs[i] = rc_regions; continue; }
                     rcs[i] = cyp_part_a(c, pr, reads[i], &calls[i], region_variants ? &region_variants[i] : nullptr, prefix.c_str(), *mids[k], searched ? &group_hits[k] : nullptr);
@@ -2241,6 +2544,7 @@ int32_t spi_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* pr,
     int32_t rc = SP_OK;
     for (uint32_t i = 0; i < n_samples; ++i) {
         if (mappings && (rcs[i] != SP_OK || calls[i].status != 0)) mappings[i].clear();
+        if (alternatives && alternatives[i] && (rcs[i] != SP_OK || calls[i].status != 0)) alternatives[i]->clear();
         if (sample_rc) sample_rc[i] = rcs[i];
         if (rcs[i] != SP_OK && rc == SP_OK) { rc = rcs[i]; if (where[i] > 0) ctx->err = on[where[i]]->err; }
     }
@@ -2249,7 +2553,7 @@ int32_t spi_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* pr,
 
 extern "C" int32_t sp_cyp_diplotype_cohort(sp_ctx* ctx, const sp_cyp_problem* pr, uint32_t n_samples, const sp_seqset* const* reads, sp_cyp_call* calls,
                                            char* consensus, uint32_t cons_cap, int32_t* sample_rc) {
-    return spi_cyp_diplotype_cohort_mappings(ctx, pr, n_samples, reads, calls, consensus, cons_cap, nullptr, nullptr, sample_rc);
+    return spi_cyp_diplotype_cohort_mappings(ctx, pr, n_samples, reads, calls, consensus, cons_cap, nullptr, nullptr, sample_rc, nullptr);
 }
 
 extern "C" int32_t sp_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, uint32_t n_samples, const sp_seqset* const* reads, sp_cyp_call* calls,
@@ -2299,6 +2603,61 @@ extern "C" int32_t sp_cyp_alleles_json(const sp_cyp_problem* pr, const sp_cyp_ca
     spj::Value amap = spj::object();
     for (auto& kv : alleles) amap.obj.emplace_back(kv.first, std::move(kv.second));
     root.obj.emplace_back("alleles", std::move(amap));
+    std::string text;
+    spj::write_pretty(text, root);
+    if (needed) *needed = text.size() + 1;
+    if (out && cap) { const size_t n = std::min<size_t>(text.size(), (size_t)cap - 1); std::memcpy(out, text.data(), n); out[n] = 0; if (n < text.size()) return SP_ERR_CAPACITY; }
+    return SP_OK;
+}
+
+// cyp2d6_alternatives.json: what find_best_chain_pair prints of its heap at debug level (chaining.rs:540-557), best first, in the layout of the other debug files
+extern "C" int32_t sp_cyp_alternatives_json(const sp_chain_problem* p, uint32_t n_possible_chains, const uint64_t* n_pairs_scored, const sp_chain_alt* alts, uint32_t n_alts,
+                                            const int32_t* hap_counts, const double* hap_weights, char* out, uint64_t cap, uint64_t* needed) {
+    if (!p || (n_alts && !alts) || (p->n_haps && !p->hap_type) || (hap_counts && !hap_weights)) return SP_ERR_INVALID_ARG;
+    const uint32_t H = p->n_haps;
+    auto region = [&](int32_t h) { return std::to_string(h) + "_" + full_allele(p->hap_type[h], p->hap_subtype ? p->hap_subtype[h] : nullptr); };
+    spj::Value root = spj::object();
+    root.obj.emplace_back("n_possible_chains", spj::unum(n_possible_chains));
+    if (n_pairs_scored) root.obj.emplace_back("n_pairs_scored", spj::unum(*n_pairs_scored));
+    spj::Value list = spj::array();
+    for (uint32_t k = 0; k < n_alts; ++k) {
+        const sp_chain_alt& a = alts[k];
+        if (a.n1 < 0 || a.n2 < 0 || a.n1 > SP_MAX_CHAIN || a.n2 > SP_MAX_CHAIN) return SP_ERR_INVALID_ARG;
+        for (int32_t x = 0; x < a.n1; ++x) if (a.chain1[x] < 0 || (uint32_t)a.chain1[x] >= H) return SP_ERR_INVALID_ARG;
+        for (int32_t x = 0; x < a.n2; ++x) if (a.chain2[x] < 0 || (uint32_t)a.chain2[x] >= H) return SP_ERR_INVALID_ARG;
+        spj::Value e = spj::object();
+        e.obj.emplace_back("rank", spj::unum((uint64_t)k + 1));               // 1: the call
+        char h1[1024], h2[1024];
+        sp_cyp_chain_to_hap(a.chain1, (uint32_t)a.n1, p->hap_type, p->hap_subtype, p->n_translate, p->translate_key, p->translate_val, 1, h1, sizeof h1);
+        sp_cyp_chain_to_hap(a.chain2, (uint32_t)a.n2, p->hap_type, p->hap_subtype, p->n_translate, p->translate_key, p->translate_val, 1, h2, sizeof h2);
+        e.obj.emplace_back("diplotype", spj::str(std::string(h1) + "/" + h2));
+        spj::Value chains = spj::array();
+        for (int which = 0; which < 2; ++which) {
+            spj::Value names = spj::array();
+            const int32_t* ch = which ? a.chain2 : a.chain1;
+            for (int32_t x = 0; x < (which ? a.n2 : a.n1); ++x) names.arr.push_back(spj::str(region(ch[x])));
+            chains.arr.push_back(std::move(names));
+        }
+        e.obj.emplace_back("chains", std::move(chains));
+        e.obj.emplace_back("score", spj::real(a.score));
+        e.obj.emplace_back("delta_to_best", spj::real(a.score - alts[0].score));
+        e.obj.emplace_back("ln_ed_penalty", spj::real(a.ln_ed_penalty)); e.obj.emplace_back("mn_llh_penalty", spj::real(a.mn_llh_penalty));
+        e.obj.emplace_back("allele_expected_penalty", spj::real(a.allele_expected_penalty)); e.obj.emplace_back("unexpected_chain_penalty", spj::real(a.unexpected_chain_penalty));
+        e.obj.emplace_back("inferred_chain_penalty", spj::real(a.inferred_chain_penalty));
+        e.obj.emplace_back("edit_distance", spj::unum(a.edit_distance));
+        e.obj.emplace_back("unmet_observations", spj::unum(a.unmet_observations));
+        spj::Value cov = spj::array();
+        if (hap_counts) for (uint32_t h = 0; h < H; ++h) {
+            if (hap_counts[(size_t)k * H + h] <= 0) continue;
+            spj::Value c = spj::object();
+            c.obj.emplace_back("region", spj::str(region((int32_t)h))); c.obj.emplace_back("copies", spj::num(hap_counts[(size_t)k * H + h]));
+            c.obj.emplace_back("observed", spj::real(hap_weights[(size_t)k * H + h]));
+            cov.arr.push_back(std::move(c));
+        }
+        e.obj.emplace_back("coverage", std::move(cov));
+        list.arr.push_back(std::move(e));
+    }
+    root.obj.emplace_back("alternatives", std::move(list));
     std::string text;
     spj::write_pretty(text, root);
     if (needed) *needed = text.size() + 1;

@@ -275,8 +275,10 @@ int32_t spi_cyp_support_cohort(sp_ctx* ctx, uint32_t n_samples, const sp_seqset*
                                sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads, const CypVariantIn* vin);
 // sp_cyp.hip, for sp_diplotype.hip: sp_cyp_diplotype_mappings with the list in a vector the library sizes
 int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
-                                   sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings);
+                                   sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings, std::string* alternatives = nullptr);
 // sp_cyp_diplotype_cohort that also hands out each sample's region variants and multi_mapping_details (optional, n_samples entries each)
+// alternatives (both; optional; the cohort call: n_samples pointers, NULL for a sample that does not want it): the chain-pair search is sp_cyp_best_chain_pairs with SP_CYP_ALTERNATIVES entries and the string receives the
+// text of cyp2d6_alternatives.json (empty: the sample has no call)
 int32_t spi_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, uint32_t n_samples, const sp_seqset* const* reads, sp_cyp_call* calls,
                                           char* consensus, uint32_t cons_cap, sp_cyp_region_variants* region_variants,
-                                          std::vector<sp_cyp_read_mapping>* mappings, int32_t* sample_rc);
+                                          std::vector<sp_cyp_read_mapping>* mappings, int32_t* sample_rc, std::string* const* alternatives = nullptr);

@@ -173,6 +173,7 @@ def _lib():
         "sp_cyp_alleles_vcf_save": (_i32, [_vp, P(ffi.sp_cyp_call), P(ffi.sp_cyp_region_variants), _vp, _vp, _s, _s, _s]),
         "sp_bgzf_save": (_i32, [_s, _vp, _u64]),
         "sp_starphase_set_cyp_vcf": (_i32, [_vp, _i32]),
+        "sp_starphase_set_cyp_alternatives": (_i32, [_vp, _i32]),
         "sp_diplotype_settings_default": (None, [P(sp_diplotype_settings)]),
         "sp_diplotype_settings_check": (_i32, [P(sp_diplotype_settings), P(sp_sample_inputs), _s, _u32]),
         "sp_starphase_create": (_i32, [_vp, _s, _s, P(sp_diplotype_settings), P(_vp)]),
@@ -971,7 +972,7 @@ class Starphase:
     set_cyp_consensus_support() at once (it also writes cyp2d6_consensus_support.json); support_insertions=True: set_support_insertions() at once (those two files
     also list the inserted strings of the columns their insertions contest)."""
 
-    def __init__(self, database, reference=None, ctx=None, consensus_support=False, cyp_consensus_support=False, support_insertions=False, support_haplotypes=False, hla_ties=False, cyp_vcf=False, **settings):
+    def __init__(self, database, reference=None, ctx=None, consensus_support=False, cyp_consensus_support=False, support_insertions=False, support_haplotypes=False, hla_ties=False, cyp_vcf=False, cyp_alternatives=False, **settings):
         self._h = _vp()
         self._s = _settings(**settings)
         rc = _lib().sp_starphase_create(ctx._h if ctx is not None else None, _b(database), _b(reference), C.byref(self._s), C.byref(self._h))
@@ -989,6 +990,8 @@ class Starphase:
             self.set_hla_ties(True)
         if cyp_vcf:
             self.set_cyp_vcf(True)
+        if cyp_alternatives:
+            self.set_cyp_alternatives(True)
 
     def close(self):
         if self._h:
@@ -1031,6 +1034,14 @@ class Starphase:
         rc = _lib().sp_starphase_set_cyp_vcf(self._h, 1 if on else 0)
         if rc != SP_OK:
             raise StarphaseError(rc, "sp_starphase_set_cyp_vcf")
+        return self
+
+    def set_cyp_alternatives(self, on=True):
+        """sp_starphase_set_cyp_alternatives: a debug folder also receives cyp2d6_alternatives.json (the ten best CYP2D6 chain pairs, best first: diplotype, chains, score,
+        its five components, edit distance, unmet observations and the coverage of each region); off by default"""
+        rc = _lib().sp_starphase_set_cyp_alternatives(self._h, 1 if on else 0)
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_starphase_set_cyp_alternatives")
         return self
 
     def set_cyp_consensus_support(self, on=True):

@@ -83,6 +83,34 @@ class sp_chain_result(C.Structure):
                 ("edit_distance", C.c_uint64), ("n_pairs_scored", C.c_uint64)]
 
 
+def possible_chains(p, ctx=None, check=None):
+    """sp_cyp_possible_chains over a filled sp_chain_problem: (status, [[region, ...], ...]); host only, so ctx may be None"""
+    def fail(rc):
+        if check:
+            check(rc)
+        raise StarphaseError(rc, "sp_cyp_possible_chains")
+    n_chains, n_items = C.c_uint32(0), C.c_uint32(0)
+    rc = lib().sp_cyp_possible_chains(ctx, C.byref(p), None, 0, None, 0, C.byref(n_chains), C.byref(n_items))
+    if rc in (16, 17, 18):
+        return rc, []
+    if rc != SP_ERR_CAPACITY:
+        fail(rc)
+    off = np.zeros(n_chains.value + 1, np.uint32)
+    items = np.zeros(max(1, n_items.value), np.uint32)
+    rc = lib().sp_cyp_possible_chains(ctx, C.byref(p), off.ctypes.data, len(off), items.ctypes.data, len(items), C.byref(n_chains), C.byref(n_items))
+    if rc != SP_OK:
+        fail(rc)
+    return 0, [[int(v) for v in items[off[c]:off[c + 1]]] for c in range(n_chains.value)]
+
+
+class sp_chain_alt(C.Structure):
+    _fields_ = [("index1", C.c_int32), ("index2", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32),
+                ("chain1", C.c_int32 * SP_MAX_CHAIN), ("chain2", C.c_int32 * SP_MAX_CHAIN),
+                ("score", C.c_double), ("ln_ed_penalty", C.c_double), ("mn_llh_penalty", C.c_double),
+                ("allele_expected_penalty", C.c_double), ("unexpected_chain_penalty", C.c_double), ("inferred_chain_penalty", C.c_double),
+                ("edit_distance", C.c_uint64), ("unmet_observations", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 REGION_HIT_DTYPE = np.dtype([(n, np.int32) for n in ("read", "template_idx", "start", "end", "seq_len", "nm", "unmapped", "clip_start", "clip_end",
                                                      "mm2_score", "mm2_nm", "mm2_start", "mm2_end", "mm2_q_start", "mm2_q_end")])
 
@@ -518,6 +546,9 @@ def lib():
         "sp_hla_type_consensus_batch": (i32, [vp, vp, u32, vp, C.POINTER(C.c_char_p), vp, i32, i32, vp]),
         "sp_hla_type_consensus": (i32, [vp, vp, u32, C.c_char_p, u32, i32, i32, C.POINTER(sp_hla_best), vp, C.c_char_p, u32, C.POINTER(u32)]),
         "sp_cyp_best_chain_pair": (i32, [vp, C.POINTER(sp_chain_problem), C.POINTER(sp_chain_result)]),
+        "sp_cyp_best_chain_pairs": (i32, [vp, C.POINTER(sp_chain_problem), C.c_uint32, C.POINTER(sp_chain_alt), C.POINTER(C.c_uint32), vp, vp, C.POINTER(sp_chain_result)]),
+        "sp_cyp_possible_chains": (i32, [vp, C.POINTER(sp_chain_problem), vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "sp_cyp_alternatives_json": (i32, [C.POINTER(sp_chain_problem), C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(sp_chain_alt), C.c_uint32, vp, vp, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "sp_anchor_batch_topk": (i32, [vp, vp, vp, vp, vp, u64, i32, vp, vp]),
         "sp_cyp_find_regions": (i32, [vp, vp, vp, vp, C.c_double, vp, u64, C.POINTER(u64)]),
         "sp_cyp_weight_segments": (i32, [vp, vp, vp, vp, vp, vp, vp]),
@@ -911,9 +942,10 @@ class Context:
         self.check(lib().sp_align_batch(self._h, A._h, B._h, _ptr(pairs), n, _ptr(out), _ptr(ev), stride))
         return (out, ev) if events else out
 
-    def cyp_best_chain_pair(self, hap_type, hap_subtype, translate, connections, singletons, read_chain_off, chain_off, chain_items,
-                            read_w_off, w_ed, w_ov, infer, normalize_all, ignore_limits, penalties):
-        """sp_cyp_best_chain_pair; returns (status, sp_chain_result).  Expected failures (16/17/18) are returned, not raised."""
+    @staticmethod
+    def _chain_problem(hap_type, hap_subtype, translate, connections, singletons, read_chain_off, chain_off, chain_items,
+                       read_w_off, w_ed, w_ov, infer, normalize_all, ignore_limits, penalties):
+        """sp_chain_problem over the arguments, and the objects its pointers refer to (keep them while the problem is in use)"""
         def strs(items):
             arr = (C.c_char_p * max(1, len(items)))()
             for i, s in enumerate(items):
@@ -940,11 +972,45 @@ class Context:
         p.read_w_off, p.w_ed, p.w_ov = rwo.ctypes.data, ed.ctypes.data, ov.ctypes.data
         p.infer_connections, p.normalize_all_alleles, p.ignore_chain_label_limits = int(infer), int(normalize_all), int(ignore_limits)
         p.lasso_penalty, p.ln_ed_penalty, p.unexpected_chain_penalty, p.inferred_edge_penalty = penalties
+        return p, (ht, st, tk, tv, ca, cb, sg, rco, co, ci, rwo, ed, ov)
+
+    def cyp_best_chain_pair(self, hap_type, hap_subtype, translate, connections, singletons, read_chain_off, chain_off, chain_items,
+                            read_w_off, w_ed, w_ov, infer, normalize_all, ignore_limits, penalties):
+        """sp_cyp_best_chain_pair; returns (status, sp_chain_result).  Expected failures (16/17/18) are returned, not raised."""
+        p, keep = self._chain_problem(hap_type, hap_subtype, translate, connections, singletons, read_chain_off, chain_off, chain_items,
+                                      read_w_off, w_ed, w_ov, infer, normalize_all, ignore_limits, penalties)
         res = sp_chain_result()
         rc = lib().sp_cyp_best_chain_pair(self._h, C.byref(p), C.byref(res))
         if rc not in (0, 16, 17, 18):
             self.check(rc)
         return rc, res
+
+    def cyp_best_chain_pairs(self, hap_type, hap_subtype, translate, connections, singletons, read_chain_off, chain_off, chain_items,
+                             read_w_off, w_ed, w_ov, infer, normalize_all, ignore_limits, penalties, n=10):
+        """sp_cyp_best_chain_pairs: the n (1..64) best chain pairs under (score, index1, index2), best first.  Returns (status, [sp_chain_alt], hap_counts [k][n_haps],
+        hap_weights [k][n_haps], sp_chain_result of entry 0).  Expected failures (16/17/18) are returned, not raised."""
+        p, keep = self._chain_problem(hap_type, hap_subtype, translate, connections, singletons, read_chain_off, chain_off, chain_items,
+                                      read_w_off, w_ed, w_ov, infer, normalize_all, ignore_limits, penalties)
+        n = int(n)
+        alts = (sp_chain_alt * max(1, n))()
+        got = C.c_uint32(0)
+        H = int(p.n_haps)
+        counts = np.zeros((max(1, n), H), np.int32)
+        weights = np.zeros((max(1, n), H), np.float64)
+        best = sp_chain_result()
+        rc = lib().sp_cyp_best_chain_pairs(self._h, C.byref(p), n, alts, C.byref(got), counts.ctypes.data, weights.ctypes.data, C.byref(best))
+        if rc not in (0, 16, 17, 18):
+            self.check(rc)
+        k = got.value
+        return rc, [alts[x] for x in range(k)], counts[:k], weights[:k], best
+
+    def cyp_possible_chains(self, hap_type, hap_subtype, translate, connections, singletons, read_chain_off, chain_off, chain_items,
+                            read_w_off, w_ed, w_ov, infer, normalize_all, ignore_limits, penalties):
+        """sp_cyp_possible_chains: the chains the search enumerates, in enumeration order (what index1 / index2 refer to).  Returns (status, [[region, ...], ...])."""
+        p, keep = self._chain_problem(hap_type, hap_subtype, translate, connections, singletons, read_chain_off, chain_off, chain_items,
+                                      read_w_off, w_ed, w_ov, infer, normalize_all, ignore_limits, penalties)
+        n_chains, n_items = C.c_uint32(0), C.c_uint32(0)
+        return possible_chains(p, self._h, self.check)
 
     def anchor_batch_topk(self, A, B, a_idx, b_idx, topk):
         a_idx = np.ascontiguousarray(a_idx, np.uint32)
