@@ -757,6 +757,56 @@ int32_t sp_cyp_possible_chains(sp_ctx* ctx, const sp_chain_problem* problem, uin
 int32_t sp_cyp_alternatives_json(const sp_chain_problem* problem, uint32_t n_possible_chains, const uint64_t* n_pairs_scored, const sp_chain_alt* alts, uint32_t n_alts,
                                  const int32_t* hap_counts, const double* hap_weights, char* out, uint64_t cap, uint64_t* needed);
 
+/* A pair read by read: the per-read quantities every read-dependent term of a pair's score is made from -- containment_score (chaining.rs:683-731) and the is_sub
+ * loop (:427-440) -- which the search reduces away and the reference never hands out.  For any n_pairs (1..64) pairs (index1[k] <= index2[k], enumeration order:
+ * sp_cyp_possible_chains), whether or not get_multinomial_score finds them valid and whatever the search ranks.  reads[k * n_reads + r], for pair (i, j) = (index1[k],
+ * index2[k]) and read r with wl weight rows:
+ *   optimum = the sum over the rows of the smallest edit distance of the row, worst = the sum of the largest
+ *   the chains are taken in the order i, then j (i == j: the same chain twice, as the reference does: mask2 == mask1); a chain shorter than wl has no start; the
+ *   starts s = 0 .. len - wl ascend; best begins at 2 * worst, a strictly smaller window total clears the placements, an equal one adds to them
+ *   mask1 / mask2  bit s: start s of chain i / chain j reaches best (SP_MAX_CHAIN is 64: a word holds every start)
+ *   n_best         popcount(mask1) + popcount(mask2): the divisor of split_frac; 0 when the read is longer than both chains
+ *   excess_ed      best - optimum (no placement: 2 * worst - optimum): what the reference adds to read_combined_ed
+ *   supported      1 when an observed chain of the read is a run of consecutive regions of chain i or of chain j; a read without observed chains is not
+ * A read with observed chains but no weight rows (wl = 0) is treated as the search treats it: every start 0 .. len of both chains is a best placement of total 0
+ * (the masks hold the starts below 64), excess_ed 0; it adds nothing to any coverage sum.
+ * edit_distance[k] (the saturating sum of excess_ed) and unmet_observations[k] (the reads with supported == 0) are the column sums, made on the device; both optional,
+ * only what is asked for is downloaded (each total by itself).  They equal sp_chain_alt's fields for a pair sp_cyp_best_chain_pairs lists, and hap_weights[k] is the sum over the reads in
+ * order, chain i's starts ascending, then chain j's, rows ascending, of (1 / n_best) * w_ov[row][region].
+ * Statuses as sp_cyp_best_chain_pair for the enumeration (SP_ERR_NO_SCORE_PAIRS does not occur: nothing is ranked); SP_ERR_INVALID_ARG for n_pairs outside 1..64, an
+ * index outside [0, n_possible) or index1 > index2.  Pooled memory only. */
+typedef struct {
+    uint64_t mask1, mask2;
+    uint64_t excess_ed;
+    uint32_t n_best;
+    uint8_t supported;
+    uint8_t reserved_[3];
+} sp_chain_pair_read;
+int32_t sp_cyp_chain_pair_reads(sp_ctx* ctx, const sp_chain_problem* problem, uint32_t n_pairs, const int32_t* index1, const int32_t* index2,
+                                sp_chain_pair_read* reads, uint64_t* edit_distance, uint32_t* unmet_observations);
+/* The observed-chain table (host only; ctx may be NULL): chain_frequency (caller.rs:544-550) -- the distinct observed chains in lexicographic order
+ * (BTreeMap<Vec<usize>>), chain c = items[chain_off[c] .. chain_off[c+1]) with frequency[c] = the sum over the reads in problem order of 1 / (chains of the read) per
+ * occurrence -- and what generate_debug_graph derives from it (visualization.rs:32-45): single_counts[n_haps] (optional) and the edges (edge_from, edge_to) in
+ * lexicographic order with edge_weight, both summed over the chains in table order.  The numbers of the reference's cyp2d6_link_graph.svg.  frequency has room for
+ * off_cap entries.  *n_chains / *n_items / *n_edges and single_counts are always set; SP_ERR_CAPACITY when off_cap < n_chains + 1, items_cap < n_items or
+ * edge_cap < n_edges. */
+int32_t sp_cyp_observed_chains(sp_ctx* ctx, const sp_chain_problem* problem, uint32_t* chain_off, uint32_t off_cap, uint32_t* items, uint32_t items_cap, double* frequency,
+                               double* single_counts, uint32_t* edge_from, uint32_t* edge_to, double* edge_weight, uint32_t edge_cap,
+                               uint32_t* n_chains, uint32_t* n_items, uint32_t* n_edges);
+/* `cyp2d6_alternative_reads.json` (sp_starphase_set_cyp_alternative_reads), host only: {"observed": {...}, "alternatives": [...]}.
+ * observed: chains [{"chain": ["<index>_<label>", ...], "reads"}], regions [{"region", "reads"}] (the regions with a non-zero total; [] without single_counts) and
+ * links [{"from", "to", "reads"}] -- the table of sp_cyp_observed_chains, region names as in cyp2d6_alternatives.json.
+ * alternatives: one object per alts[k], in the order given, with reads[k * n_reads + r] its records: rank, diplotype and chains (as sp_cyp_alternatives_json spells
+ * them: the pair sorted), hap1_chain (1 or 2: which entry of chains is the chain index1 names -- hap1 of the placements; hap2 is the other, or the same chain when
+ * index1 == index2), edit_distance, unmet_observations (the record's), for rank > 1 reads_decided_for / reads_decided_against (the reads whose excess_ed is larger /
+ * smaller than under rank 1) and reads: the reads that are not neutral -- neutral: excess_ed == 0, supported, and the same excess_ed as under rank 1 -- as {"read",
+ * "excess_ed", "delta_to_best" (signed: against rank 1), "supported", "placements": ["hap1@<start>", ..., "hap2@<start>", ...]}.  read_names: n_reads names, or NULL
+ * (or a NULL entry) for "read <r>".  index1 / index2 must name chains of the problem.  out / cap / needed as sp_cyp_alleles_json. */
+int32_t sp_cyp_alternative_reads_json(const sp_chain_problem* problem, const sp_chain_alt* alts, uint32_t n_alts, const sp_chain_pair_read* reads, const char* const* read_names,
+                                      const uint32_t* obs_chain_off, const uint32_t* obs_items, const double* obs_frequency, uint32_t n_obs_chains,
+                                      const double* single_counts, const uint32_t* edge_from, const uint32_t* edge_to, const double* edge_weight, uint32_t n_edges,
+                                      char* out, uint64_t cap, uint64_t* needed);
+
 /* ------------------------------------------------------------------ K3: CYP2D6 template search in reads
  * Replaces Cyp2d6Extractor::find_base_type_in_sequence (src/cyp2d6/haplotyper.rs:142-315) for a batch of reads:
  * every template (D6, D7, *5 signature, hybrids, REP6/REP7, spacer, link_region -- given in the reference's key order,
@@ -1793,6 +1843,12 @@ int32_t sp_starphase_set_cyp_vcf(sp_starphase* handle, int32_t on);
  * a batch and the cohort call write the same bytes for a sample.  Off, or no debug folder: nothing more is launched or pooled and every output is the same bytes;
  * on: every other output is. */
 int32_t sp_starphase_set_cyp_alternatives(sp_starphase* handle, int32_t on);
+/* cyp2d6_alternative_reads.json, off by default (on 0): with it on, a sample that has a debug folder and a CYP2D6 call of status 0 also receives
+ * <folder>/cyp2d6_alternative_reads.json (sp_cyp_alternative_reads_json): the observed-chain table and the SP_CYP_ALTERNATIVES best pairs read by read
+ * (sp_cyp_chain_pair_reads on the pairs of the N-best search -- the ONE search that also serves cyp2d6_alternatives.json when both switches are on; either works
+ * without the other), the reads named by their QNAMEs.  The single call, a batch and the cohort call write the same bytes for a sample.  Off, or no debug folder:
+ * nothing more is launched or pooled and every output is the same bytes; on: every other output is. */
+int32_t sp_starphase_set_cyp_alternative_reads(sp_starphase* handle, int32_t on);
 /* A switch of its own, off by default, with effect only where one of the two switches above writes its file: the support pass of that file also makes the insertion
  * list (sp_hla_consensus_support_cohort_ins / sp_cyp_consensus_support_cohort_ins: the same one pass per batch group) and the file is rendered with it
  * (sp_consensus_support_json_ins / sp_cyp_support_json_ins, without first_read): every contested column with 2 * ins > depth gains "insertions" (and "more", "other").

@@ -306,6 +306,15 @@ pub struct sp_chain_alt {
     pub reserved_: u32,
 }
 #[repr(C)]
+pub struct sp_chain_pair_read {
+    pub mask1: u64,
+    pub mask2: u64,
+    pub excess_ed: u64,
+    pub n_best: u32,
+    pub supported: u8,
+    pub reserved_: [u8; 3],
+}
+#[repr(C)]
 pub struct sp_region_hit {
     pub read: i32,
     pub template_idx: i32,
@@ -890,6 +899,9 @@ extern "C" {
     pub fn sp_cyp_best_chain_pairs(ctx: *mut sp_ctx, problem: *const sp_chain_problem, max_alts: u32, alts: *mut sp_chain_alt, n_alts: *mut u32, hap_counts: *mut i32, hap_weights: *mut f64, best: *mut sp_chain_result) -> i32;
     pub fn sp_cyp_possible_chains(ctx: *mut sp_ctx, problem: *const sp_chain_problem, chain_off: *mut u32, off_cap: u32, items: *mut u32, items_cap: u32, n_chains: *mut u32, n_items: *mut u32) -> i32;
     pub fn sp_cyp_alternatives_json(problem: *const sp_chain_problem, n_possible_chains: u32, n_pairs_scored: *const u64, alts: *const sp_chain_alt, n_alts: u32, hap_counts: *const i32, hap_weights: *const f64, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
+    pub fn sp_cyp_chain_pair_reads(ctx: *mut sp_ctx, problem: *const sp_chain_problem, n_pairs: u32, index1: *const i32, index2: *const i32, reads: *mut sp_chain_pair_read, edit_distance: *mut u64, unmet_observations: *mut u32) -> i32;
+    pub fn sp_cyp_observed_chains(ctx: *mut sp_ctx, problem: *const sp_chain_problem, chain_off: *mut u32, off_cap: u32, items: *mut u32, items_cap: u32, frequency: *mut f64, single_counts: *mut f64, edge_from: *mut u32, edge_to: *mut u32, edge_weight: *mut f64, edge_cap: u32, n_chains: *mut u32, n_items: *mut u32, n_edges: *mut u32) -> i32;
+    pub fn sp_cyp_alternative_reads_json(problem: *const sp_chain_problem, alts: *const sp_chain_alt, n_alts: u32, reads: *const sp_chain_pair_read, read_names: *const *const c_char, obs_chain_off: *const u32, obs_items: *const u32, obs_frequency: *const f64, n_obs_chains: u32, single_counts: *const f64, edge_from: *const u32, edge_to: *const u32, edge_weight: *const f64, n_edges: u32, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
     pub fn sp_cyp_find_regions(ctx: *mut sp_ctx, templates: *const sp_seqset, template_type: *const i32, reads: *const sp_seqset, max_missing_frac: f64, hits: *mut sp_region_hit, hits_cap: u64, n_hits: *mut u64) -> i32;
     pub fn sp_cyp_weight_segments(ctx: *mut sp_ctx, consensus: *const sp_seqset, allowed: *const u8, segments: *const sp_seqset, ed: *mut u64, ov: *mut f64, kept: *mut u8) -> i32;
     pub fn sp_cyp_score_alleles(ctx: *mut sp_ctx, n_variants: u32, n_alleles: u32, hap_matrix: *const u8, is_vi: *const u8, n_seqs: u32, states: *const u8, best_vi: *mut u32, best_all: *mut u32, tie_mask: *mut u8) -> i32;
@@ -1052,6 +1064,7 @@ extern "C" {
     pub fn sp_starphase_set_cyp_consensus_support(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_cyp_vcf(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_cyp_alternatives(handle: *mut sp_starphase, on: i32) -> i32;
+    pub fn sp_starphase_set_cyp_alternative_reads(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_support_insertions(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_support_haplotypes(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_warnings(handle: *const sp_starphase) -> *const c_char;

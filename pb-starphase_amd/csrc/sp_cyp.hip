@@ -508,6 +508,78 @@ __global__ __launch_bounds__(K5_TILE) void k5_alt_coverage_kernel(PairConsts c, 
     if (tid < H) { hap_counts[(size_t)blockIdx.x * H + tid] = (int32_t)s_cnt[tid]; hap_weights[(size_t)blockIdx.x * H + tid] = acc; }
 }
 
+// ---- a pair read by read (sp_cyp_chain_pair_reads) ----
+// One thread = one (pair blockIdx.y, read r): containment_score (chaining.rs:683-731) and the is_sub test (:427-440) of read r against the pair's two chains, stated
+// from the reads' weight rows themselves -- not from tab_best / tab_mask, so that the records also judge those tables.  The two chains are staged in LDS (every read
+// of the block has the same pair); no atomics; one 32-byte record per thread.  A read without weight rows (wl = 0) fits every start 0..len of both chains at no cost,
+// as k5_chain_read_kernel has it; bit 64 does not exist, so a mask holds the starts below 64.
+__global__ __launch_bounds__(256) void k5_pair_reads_kernel(int P, int R, int H, int maxlen, const uint8_t* __restrict__ chains, const int32_t* __restrict__ chain_len,
+                                                            const int32_t* __restrict__ read_w_off, const uint32_t* __restrict__ w_ed,
+                                                            const uint32_t* __restrict__ read_chain_off, const uint32_t* __restrict__ chain_off, const uint32_t* __restrict__ chain_items,
+                                                            const int32_t* __restrict__ index1, const int32_t* __restrict__ index2, sp_chain_pair_read* __restrict__ out) {
+    __shared__ uint8_t s_chain[2][SP_MAX_CHAIN];
+    const int k = (int)blockIdx.y, tid = (int)threadIdx.x;
+    const int i = index1[k], j = index2[k];
+    if (i < 0 || j < 0 || i >= P || j >= P) return;                            // (the host has checked them)
+    const int len[2] = { min(chain_len[i], SP_MAX_CHAIN), min(chain_len[j], SP_MAX_CHAIN) };
+    if (tid < len[0]) s_chain[0][tid] = chains[(size_t)i * maxlen + tid];
+    if (tid >= 64 && tid - 64 < len[1]) s_chain[1][tid - 64] = chains[(size_t)j * maxlen + tid - 64];
+    __syncthreads();
+    const int r = (int)blockIdx.x * 256 + tid;
+    if (r >= R) return;
+    const int row0 = read_w_off[r], wl = read_w_off[r + 1] - row0;
+    const uint32_t* ed = w_ed + (size_t)row0 * H;
+    unsigned long long optimum = 0, worst = 0;
+    for (int x = 0; x < wl; ++x) {
+        uint32_t mn = 0xFFFFFFFFu, mx = 0;
+        for (int h = 0; h < H; ++h) { const uint32_t v = ed[(size_t)x * H + h]; mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
+        optimum += mn; worst += mx;
+    }
+    unsigned long long best = 2ull * worst, mask[2] = { 0ull, 0ull };
+    for (int which = 0; which < 2; ++which) {
+        const uint8_t* o = s_chain[which];
+        for (int s = 0; s + wl <= len[which]; ++s) {                           // (a chain shorter than the read has no start)
+            unsigned long long tot = 0;
+            for (int x = 0; x < wl; ++x) tot += ed[(size_t)x * H + o[s + x]];
+            if (tot < best) { best = tot; mask[0] = 0ull; mask[1] = 0ull; }
+            if (tot == best && s < 64) mask[which] |= 1ull << s;
+        }
+    }
+    bool supported = false;
+    for (uint32_t c = read_chain_off[r]; c < read_chain_off[r + 1] && !supported; ++c) {
+        const uint32_t* needle = chain_items + chain_off[c]; const int n = (int)(chain_off[c + 1] - chain_off[c]);
+        for (int which = 0; which < 2 && !supported; ++which)
+            for (int s = 0; s + n <= len[which] && !supported; ++s) {
+                bool eq = true;
+                for (int x = 0; x < n && eq; ++x) eq = (uint32_t)s_chain[which][s + x] == needle[x];
+                supported = eq;
+            }
+    }
+    sp_chain_pair_read rec;
+    rec.mask1 = mask[0]; rec.mask2 = mask[1]; rec.excess_ed = best - optimum;
+    rec.n_best = (uint32_t)(__popcll(mask[0]) + __popcll(mask[1])); rec.supported = supported ? 1 : 0;
+    rec.reserved_[0] = rec.reserved_[1] = rec.reserved_[2] = 0;
+    out[(size_t)k * R + r] = rec;
+}
+
+// the column sums of the records, one workgroup per pair: edit_distance[k] = the saturating sum of excess_ed (every term is >= 0: any order gives the same),
+// unmet[k] = the reads that are not supported
+__global__ __launch_bounds__(256) void k5_pair_reads_totals_kernel(int R, const sp_chain_pair_read* __restrict__ recs, unsigned long long* __restrict__ edit_distance,
+                                                                   uint32_t* __restrict__ unmet) {
+    __shared__ unsigned long long s_ed[256];
+    __shared__ uint32_t s_un[256];
+    const int k = (int)blockIdx.x, tid = (int)threadIdx.x;
+    unsigned long long e = 0; uint32_t u = 0;
+    for (int r = tid; r < R; r += 256) { const sp_chain_pair_read& q = recs[(size_t)k * R + r]; e = k5_saturating_add(e, q.excess_ed); u += q.supported ? 0u : 1u; }
+    s_ed[tid] = e; s_un[tid] = u;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) { s_ed[tid] = k5_saturating_add(s_ed[tid], s_ed[tid + o]); s_un[tid] += s_un[tid + o]; }
+        __syncthreads();
+    }
+    if (tid == 0) { edit_distance[k] = s_ed[0]; unmet[k] = s_un[0]; }
+}
+
 // =============================================================================================
 // host
 // =============================================================================================
@@ -604,10 +676,11 @@ int32_t k5_enumerate(sp_ctx* ctx, const sp_chain_problem* p, K5Chains& e) {     
 struct K5Device {
     PairConsts pc; int lf_n = 0, lp_stride = 0;
     uint64_t n_pairs = 0, blocks = 0; bool block_per_pair = false;
-    uint8_t* chains; int32_t* clen; uint32_t* unexp; uint32_t* ninf; uint8_t* del; uint8_t* lasso; uint8_t* norm; int32_t* rwo; double* ov;
+    uint8_t* chains; int32_t* clen; uint32_t* unexp; uint32_t* ninf; uint8_t* del; uint8_t* lasso; uint8_t* norm; int32_t* rwo; uint32_t* ed; double* ov;
     uint64_t* opt; uint64_t* worst; double* lf; double* lp; unsigned long long* tb; unsigned long long* tm;
 };
-int32_t k5_upload(sp_ctx* ctx, const sp_chain_problem* p, const K5Chains& e, int nbest, K5Device& d) {
+// tables = false (sp_cyp_chain_pair_reads): the inputs alone -- no k5_tab_best / k5_tab_mask, no k5_chain_read_kernel launch; d.tb / d.tm are NULL
+int32_t k5_upload(sp_ctx* ctx, const sp_chain_problem* p, const K5Chains& e, int nbest, K5Device& d, bool tables = true) {
     const int H = e.H; const bool ignore = e.ignore, norm_all = e.norm_all, infer = e.infer;
     const std::vector<int>& type = e.type; const std::vector<std::string>& simple = e.simple; const std::vector<uint8_t>& inferred = e.inferred;
     const std::vector<std::vector<int>>& possible = e.possible;
@@ -686,9 +759,11 @@ int32_t k5_upload(sp_ctx* ctx, const sp_chain_problem* p, const K5Chains& e, int
     d.chains = d_in + at_chains; d.clen = (int32_t*)(d_in + at_clen);
     d.unexp = (uint32_t*)(d_in + at_unexp); d.ninf = (uint32_t*)(d_in + at_ninf);
     d.del = d_in + at_del; d.lasso = d_in + at_lasso; d.norm = d_in + at_norm;
-    d.rwo = (int32_t*)(d_in + at_rwo); uint32_t* d_ed = (uint32_t*)(d_in + at_ed); d.ov = (double*)(d_in + at_ov);
+    d.rwo = (int32_t*)(d_in + at_rwo); uint32_t* d_ed = d.ed = (uint32_t*)(d_in + at_ed); d.ov = (double*)(d_in + at_ov);
     d.opt = (uint64_t*)(d_in + at_opt); d.worst = (uint64_t*)(d_in + at_worst);
     d.lf = (double*)(d_in + at_lf); d.lp = (double*)(d_in + at_lp);
+    d.tb = d.tm = nullptr;
+    if (!tables) return SP_OK;
     d.tb = (unsigned long long*)sp_pool(ctx, "k5_tab_best", std::max<size_t>(1, (size_t)P * R) * 8);
     d.tm = (unsigned long long*)sp_pool(ctx, "k5_tab_mask", std::max<size_t>(1, (size_t)P * R) * 8);
     if (!d.tb || !d.tm) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "chain pair tables");
@@ -882,6 +957,108 @@ extern "C" int32_t sp_cyp_possible_chains(sp_ctx* ctx, const sp_chain_problem* p
     uint32_t at = 0;
     for (size_t c = 0; c < en.possible.size(); ++c) { chain_off[c] = at; for (int h : en.possible[c]) items[at++] = (uint32_t)h; }
     chain_off[en.possible.size()] = at;
+    return SP_OK;
+}
+
+// Any list of pairs read by read: the per-read quantities every read-dependent term of a pair's score is made from (k5_pair_reads_kernel), for the pairs the caller
+// names by enumeration index -- whether or not get_multinomial_score finds them valid.  Launches: k5_pair_reads_kernel (k5_upload without its tables),
+// k5_pair_reads_totals_kernel when a total is asked for; the observed chains go up in a second pooled block.
+extern "C" int32_t sp_cyp_chain_pair_reads(sp_ctx* ctx, const sp_chain_problem* p, uint32_t n_pairs, const int32_t* index1, const int32_t* index2, sp_chain_pair_read* reads,
+                                           uint64_t* edit_distance, uint32_t* unmet_observations) {
+    if (!ctx || !p || (p->n_haps && !p->hap_type)) return SP_ERR_INVALID_ARG;
+    if (n_pairs < 1 || n_pairs > 64) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_chain_pair_reads: n_pairs is 1..64");
+    if (!index1 || !index2 || (p->n_reads && (!reads || !p->read_chain_off || !p->chain_off || !p->chain_items))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_chain_pair_reads: null argument");
+    (void)hipSetDevice(ctx->device);
+    K5Chains en; K5Device d;
+    int32_t rc = k5_enumerate(ctx, p, en);
+    if (rc != SP_OK) return rc;
+    const int P = (int)en.possible.size(), H = en.H, R = (int)p->n_reads, N = (int)n_pairs;
+    for (int k = 0; k < N; ++k)
+        if (index1[k] < 0 || index2[k] >= P || index1[k] > index2[k]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_chain_pair_reads: a pair is not 0 <= index1 <= index2 < n_possible");
+    rc = k5_upload(ctx, p, en, 0, d, false);
+    if (rc != SP_OK) return rc;
+    // the observed chains and the pairs: one more copy up
+    const uint32_t n_chains = R ? p->read_chain_off[R] : 0, n_items = n_chains ? p->chain_off[n_chains] : 0;
+    const size_t at_rco = 0, at_co = at_rco + ((size_t)R + 1) * 4, at_items = at_co + ((size_t)n_chains + 1) * 4, at_i1 = at_items + (size_t)std::max<uint32_t>(1, n_items) * 4,
+                 at_i2 = at_i1 + (size_t)N * 4, in_bytes = at_i2 + (size_t)N * 4;
+    // down: [edit distances [N] | unmet [N] | records [N][R]]
+    const size_t at_un = (size_t)N * 8, at_rec = (at_un + (size_t)N * 4 + 31) & ~(size_t)31, out_bytes = at_rec + (size_t)N * std::max(1, R) * sizeof(sp_chain_pair_read);
+    uint8_t* d_in = (uint8_t*)sp_pool(ctx, "k5_reads_in", in_bytes); uint8_t* h_in = (uint8_t*)sp_host_pool(ctx, "k5_reads_in", in_bytes);
+    uint8_t* d_out = (uint8_t*)sp_pool(ctx, "k5_reads_out", out_bytes); uint8_t* h_out = (uint8_t*)sp_host_pool(ctx, "k5_reads_out", out_bytes);
+    if (!d_in || !h_in || !d_out || !h_out) return sp_fail(ctx, SP_ERR_OUT_OF_MEMORY, "chain pair reads buffers");
+    uint32_t* h_rco = (uint32_t*)(h_in + at_rco);
+    h_rco[0] = 0;
+    for (int r = 0; r <= R && R; ++r) h_rco[r] = p->read_chain_off[r];
+    uint32_t* h_co = (uint32_t*)(h_in + at_co);
+    h_co[0] = 0;
+    if (n_chains) std::memcpy(h_co, p->chain_off, ((size_t)n_chains + 1) * 4);
+    if (n_items) std::memcpy(h_in + at_items, p->chain_items, (size_t)n_items * 4);
+    std::memcpy(h_in + at_i1, index1, (size_t)N * 4); std::memcpy(h_in + at_i2, index2, (size_t)N * 4);
+    (void)hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+    sp_chain_pair_read* d_rec = (sp_chain_pair_read*)(d_out + at_rec);
+    if (R) {
+        ProfScope ps(ctx, "k5_pair_reads", (uint64_t)N * R);
+        hipLaunchKernelGGL(k5_pair_reads_kernel, dim3((unsigned)((R + 255) / 256), (unsigned)N), dim3(256), 0, ctx->stream, P, R, H, d.pc.maxlen, d.chains, d.clen, d.rwo, d.ed,
+                           (const uint32_t*)(d_in + at_rco), (const uint32_t*)(d_in + at_co), (const uint32_t*)(d_in + at_items), (const int32_t*)(d_in + at_i1),
+                           (const int32_t*)(d_in + at_i2), d_rec);
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "k5 launch failed");
+    }
+    const bool totals = edit_distance || unmet_observations;
+    if (totals) {
+        ProfScope ps(ctx, "k5_pair_reads_totals", (uint64_t)N);
+        hipLaunchKernelGGL(k5_pair_reads_totals_kernel, dim3((unsigned)N), dim3(256), 0, ctx->stream, R, d_rec, (unsigned long long*)d_out, (uint32_t*)(d_out + at_un));
+        if (hipGetLastError() != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, "k5 launch failed");
+        if (edit_distance) (void)hipMemcpyAsync(h_out, d_out, (size_t)N * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (unmet_observations) (void)hipMemcpyAsync(h_out + at_un, d_out + at_un, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    if (R) (void)hipMemcpyAsync(h_out + at_rec, d_rec, (size_t)N * R * sizeof(sp_chain_pair_read), hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return sp_fail(ctx, SP_ERR_HIP, std::string("chain pair reads: ") + hipGetErrorString(e));
+    if (R) std::memcpy(reads, h_out + at_rec, (size_t)N * R * sizeof(sp_chain_pair_read));
+    if (edit_distance) std::memcpy(edit_distance, h_out, (size_t)N * 8);
+    if (unmet_observations) std::memcpy(unmet_observations, h_out + at_un, (size_t)N * 4);
+    return SP_OK;
+}
+
+// chain_frequency (caller.rs:544-550) of the problem's observed chains and the node / edge totals generate_debug_graph derives from it (visualization.rs:32-45): the
+// numbers of cyp2d6_link_graph.svg.  Host only; every f64 is summed in the reference's order (reads in problem order; the chains in BTreeMap order).
+extern "C" int32_t sp_cyp_observed_chains(sp_ctx* ctx, const sp_chain_problem* p, uint32_t* chain_off, uint32_t off_cap, uint32_t* items, uint32_t items_cap, double* frequency,
+                                          double* single_counts, uint32_t* edge_from, uint32_t* edge_to, double* edge_weight, uint32_t edge_cap,
+                                          uint32_t* n_chains, uint32_t* n_items, uint32_t* n_edges) {
+    auto fail = [&](int code, const char* msg) { return ctx ? sp_fail(ctx, code, msg) : code; };
+    if (!p || !n_chains || !n_items || !n_edges || (off_cap && (!chain_off || !frequency)) || (items_cap && !items) || (edge_cap && (!edge_from || !edge_to || !edge_weight)))
+        return SP_ERR_INVALID_ARG;
+    *n_chains = 0; *n_items = 0; *n_edges = 0;
+    if (p->n_reads && (!p->read_chain_off || !p->chain_off || !p->chain_items)) return fail(SP_ERR_INVALID_ARG, "sp_cyp_observed_chains: null chain arrays");
+    const uint32_t H = p->n_haps;
+    std::map<std::vector<uint32_t>, double> freq;                             // BTreeMap<Vec<usize>, f64>
+    for (uint32_t r = 0; r < p->n_reads; ++r) {
+        const uint32_t c0 = p->read_chain_off[r], c1 = p->read_chain_off[r + 1];
+        if (c1 <= c0) continue;
+        const double weight = 1.0 / (double)(c1 - c0);
+        for (uint32_t c = c0; c < c1; ++c) {
+            std::vector<uint32_t> key(p->chain_items + p->chain_off[c], p->chain_items + p->chain_off[c + 1]);
+            for (uint32_t h : key) if (h >= H) return fail(SP_ERR_INVALID_ARG, "sp_cyp_observed_chains: consensus index out of range");
+            freq[std::move(key)] += weight;
+        }
+    }
+    std::vector<double> single(H, 0.0);
+    std::map<std::pair<uint32_t, uint32_t>, double> edges;                    // BTreeMap<(usize, usize), f64>
+    uint64_t total = 0;
+    for (const auto& kv : freq) {
+        total += kv.first.size();
+        for (uint32_t h : kv.first) single[h] += kv.second;
+        for (size_t x = 0; x + 1 < kv.first.size(); ++x) edges[{kv.first[x], kv.first[x + 1]}] += kv.second;
+    }
+    if (total > 0xFFFFFFFFull) return fail(SP_ERR_TOO_LONG, "sp_cyp_observed_chains: more than 2^32 chain items");
+    *n_chains = (uint32_t)freq.size(); *n_items = (uint32_t)total; *n_edges = (uint32_t)edges.size();
+    if (single_counts) std::copy(single.begin(), single.end(), single_counts);
+    if ((uint64_t)off_cap < (uint64_t)freq.size() + 1 || items_cap < total || edge_cap < edges.size()) return fail(SP_ERR_CAPACITY, "sp_cyp_observed_chains: more chains, items or edges than the caps");
+    uint32_t at = 0, c = 0;
+    for (const auto& kv : freq) { chain_off[c] = at; frequency[c] = kv.second; ++c; for (uint32_t h : kv.first) items[at++] = h; }
+    chain_off[c] = at;
+    uint32_t x = 0;
+    for (const auto& kv : edges) { edge_from[x] = kv.first.first; edge_to[x] = kv.first.second; edge_weight[x] = kv.second; ++x; }
     return SP_OK;
 }
 
@@ -1959,6 +2136,7 @@ struct CypMid {
     bool finished = false;                                // the call is complete after part (a) already (no reads)
     std::vector<sp_cyp_read_mapping>* mappings = nullptr; // sp_cyp_diplotype_mappings: the reads with one chain (multi_mapping_details)
     std::string* alternatives = nullptr;                  // sp_starphase_set_cyp_alternatives: the text of cyp2d6_alternatives.json (empty: no call)
+    SpiCypAltReads* alternative_reads = nullptr;          // sp_starphase_set_cyp_alternative_reads: the read names in, the text of cyp2d6_alternative_reads.json out
     // between (c1), the weights and (c2)
     std::vector<std::string> full_cons, final_cons; std::vector<int32_t> final_group; std::vector<Label> labels; DeepInfo deep; std::vector<uint8_t> allowed;
     std::vector<uint32_t> a_idx, seg_off; std::vector<int32_t> a_start, a_len; uint32_t H = 0;
@@ -2337,10 +2515,11 @@ int32_t cyp_part_c2(sp_ctx* ctx, const sp_cyp_problem* pr, sp_cyp_call* call, ch
     hm.mark("host:cyp_chains");
     sp_chain_alt alts[SP_CYP_ALTERNATIVES]; uint32_t n_alts = 0;
     std::vector<int32_t> alt_counts; std::vector<double> alt_weights;
-    if (m.alternatives) {                // sp_starphase_set_cyp_alternatives: the N = 10 form of the same search; entry 0 is the call
-        m.alternatives->clear();
+    if (m.alternative_reads) m.alternative_reads->text.clear();
+    if (m.alternatives || m.alternative_reads) {                // sp_starphase_set_cyp_alternatives / _alternative_reads: the N = 10 form of the same search; entry 0 is the call
+        if (m.alternatives) m.alternatives->clear();
         alt_counts.assign((size_t)SP_CYP_ALTERNATIVES * std::max<uint32_t>(H, 1), 0); alt_weights.assign((size_t)SP_CYP_ALTERNATIVES * std::max<uint32_t>(H, 1), 0.0);
-        rc = sp_cyp_best_chain_pairs(ctx, &cp, SP_CYP_ALTERNATIVES, alts, &n_alts, alt_counts.data(), alt_weights.data(), &cr);
+        rc = sp_cyp_best_chain_pairs(ctx, &cp, SP_CYP_ALTERNATIVES, alts, &n_alts, m.alternatives ? alt_counts.data() : nullptr, m.alternatives ? alt_weights.data() : nullptr, &cr);      // (the coverage: for the first file only)
     } else rc = sp_cyp_best_chain_pair(ctx, &cp, &cr);
     hm.mark("host:cyp_chain_pair");
     if (rc == SP_OK && m.alternatives) {
@@ -2351,6 +2530,34 @@ int32_t cyp_part_c2(sp_ctx* ctx, const sp_cyp_problem* pr, sp_cyp_call* call, ch
             return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_diplotype: cyp2d6_alternatives.json");
         text.resize((size_t)need - 1);
         *m.alternatives = std::move(text);
+    }
+    if (rc == SP_OK && m.alternative_reads) {         // the pairs of that search read by read, and the observed-chain table
+        const uint32_t NR = cp.n_reads;
+        int32_t i1[SP_CYP_ALTERNATIVES], i2[SP_CYP_ALTERNATIVES];
+        for (uint32_t k = 0; k < n_alts; ++k) { i1[k] = alts[k].index1; i2[k] = alts[k].index2; }
+        std::vector<sp_chain_pair_read> recs((size_t)n_alts * std::max<uint32_t>(NR, 1));
+        const int32_t rc2 = sp_cyp_chain_pair_reads(ctx, &cp, n_alts, i1, i2, recs.data(), nullptr, nullptr);
+        if (rc2 != SP_OK) return rc2;
+        uint32_t oc = 0, oi = 0, oe = 0;
+        std::vector<double> single(std::max<uint32_t>(H, 1), 0.0);
+        int32_t rc3 = sp_cyp_observed_chains(nullptr, &cp, nullptr, 0, nullptr, 0, nullptr, single.data(), nullptr, nullptr, nullptr, 0, &oc, &oi, &oe);
+        if (rc3 != SP_OK && rc3 != SP_ERR_CAPACITY) return sp_fail(ctx, rc3, "sp_cyp_diplotype: observed chains");
+        std::vector<uint32_t> o_off(oc + 1, 0), o_items(std::max<uint32_t>(oi, 1)), e_from(std::max<uint32_t>(oe, 1)), e_to(std::max<uint32_t>(oe, 1));
+        std::vector<double> o_freq(oc + 1, 0.0), e_w(std::max<uint32_t>(oe, 1), 0.0);
+        rc3 = sp_cyp_observed_chains(nullptr, &cp, o_off.data(), oc + 1, o_items.data(), (uint32_t)o_items.size(), o_freq.data(), single.data(), e_from.data(), e_to.data(), e_w.data(),
+                                     (uint32_t)e_w.size(), &oc, &oi, &oe);
+        if (rc3 != SP_OK) return sp_fail(ctx, rc3, "sp_cyp_diplotype: observed chains");
+        std::vector<const char*> names;
+        if (m.alternative_reads->read_names) for (uint32_t k = 0; k < NR; ++k) names.push_back(m.alternative_reads->read_names[read_index[k]]);
+        const char* const* np = names.empty() ? nullptr : names.data();
+        uint64_t need = 0;
+        sp_cyp_alternative_reads_json(&cp, alts, n_alts, recs.data(), np, o_off.data(), o_items.data(), o_freq.data(), oc, single.data(), e_from.data(), e_to.data(), e_w.data(), oe, nullptr, 0, &need);
+        std::string text((size_t)need, '\0');
+        if (need == 0 || sp_cyp_alternative_reads_json(&cp, alts, n_alts, recs.data(), np, o_off.data(), o_items.data(), o_freq.data(), oc, single.data(), e_from.data(), e_to.data(), e_w.data(), oe,
+                                                       &text[0], need, &need) != SP_OK)
+            return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_diplotype: cyp2d6_alternative_reads.json");
+        text.resize((size_t)need - 1);
+        m.alternative_reads->text = std::move(text);
     }
     if (rc == SP_ERR_NO_CHAINING_HEAD || rc == SP_ERR_NO_CHAINS_FOUND || rc == SP_ERR_NO_SCORE_PAIRS) { call->status = rc; return SP_OK; }
     if (rc != SP_OK) return rc;
@@ -2397,11 +2604,12 @@ int32_t cyp_part_c(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads
 } // namespace
 
 int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
-                                   sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings, std::string* alternatives) {
+                                   sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings, std::string* alternatives, SpiCypAltReads* alternative_reads) {
     if (!ctx) return SP_ERR_INVALID_ARG;
     CypMid m;
     if (mappings) { mappings->clear(); m.mappings = mappings; }
     if (alternatives) { alternatives->clear(); m.alternatives = alternatives; }
+    if (alternative_reads) { alternative_reads->text.clear(); m.alternative_reads = alternative_reads; }
     int32_t rc = cyp_part_a(ctx, pr, reads, call, region_variants, "cypc", m);
     if (rc != SP_OK || m.finished) return rc;
     {
@@ -2416,6 +2624,7 @@ int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const 
     rc = cyp_part_c(ctx, pr, reads, call, consensus, cons_cap, region_variants, m);
     if (mappings && (rc != SP_OK || call->status != 0)) mappings->clear();
     if (alternatives && (rc != SP_OK || call->status != 0)) alternatives->clear();
+    if (alternative_reads && (rc != SP_OK || call->status != 0)) alternative_reads->text.clear();
     return rc;
 }
 
@@ -2441,7 +2650,8 @@ extern "C" int32_t sp_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* 
 // region_variants / mappings (optional, n_samples entries): what sp_cyp_diplotype_mappings hands out for the sample, filled by the same (a) / (c1) / (c2)
 int32_t spi_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, uint32_t n_samples, const sp_seqset* const* reads, sp_cyp_call* calls,
                                           char* consensus, uint32_t cons_cap, sp_cyp_region_variants* region_variants,
-                                          std::vector<sp_cyp_read_mapping>* mappings, int32_t* sample_rc, std::string* const* alternatives) {
+                                          std::vector<sp_cyp_read_mapping>* mappings, int32_t* sample_rc, std::string* const* alternatives,
+                                          SpiCypAltReads* const* alternative_reads) {
     if (!ctx) return SP_ERR_INVALID_ARG;
     if (!pr || (n_samples && (!reads || !calls))) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_diplotype_cohort: null argument");
     for (uint32_t i = 0; i < n_samples; ++i) if (!reads[i]) return sp_fail(ctx, SP_ERR_INVALID_ARG, "sp_cyp_diplotype_cohort: null read set");
@@ -2483,6 +2693,7 @@ int32_t spi_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* pr,
                     mids[k].reset(new CypMid());
                     if (mappings) { mappings[i].clear(); mids[k]->mappings = &mappings[i]; }
                     if (alternatives && alternatives[i]) { alternatives[i]->clear(); mids[k]->alternatives = alternatives[i]; }
+                    if (alternative_reads && alternative_reads[i]) { alternative_reads[i]->text.clear(); mids[k]->alternative_reads = alternative_reads[i]; }
                     const std::string prefix = "cypc" + std::to_string(k);
                     if (searched && rc_regions != SP_OK) { rcs[i] = rc_regions; continue; }
                     rcs[i] = cyp_part_a(c, pr, reads[i], &calls[i], region_variants ? &region_variants[i] : nullptr, prefix.c_str(), *mids[k], searched ? &group_hits[k] : nullptr);
@@ -2545,6 +2756,7 @@ int32_t spi_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* pr,
     for (uint32_t i = 0; i < n_samples; ++i) {
         if (mappings && (rcs[i] != SP_OK || calls[i].status != 0)) mappings[i].clear();
         if (alternatives && alternatives[i] && (rcs[i] != SP_OK || calls[i].status != 0)) alternatives[i]->clear();
+        if (alternative_reads && alternative_reads[i] && (rcs[i] != SP_OK || calls[i].status != 0)) alternative_reads[i]->text.clear();
         if (sample_rc) sample_rc[i] = rcs[i];
         if (rcs[i] != SP_OK && rc == SP_OK) { rc = rcs[i]; if (where[i] > 0) ctx->err = on[where[i]]->err; }
     }
@@ -2655,6 +2867,109 @@ extern "C" int32_t sp_cyp_alternatives_json(const sp_chain_problem* p, uint32_t 
             cov.arr.push_back(std::move(c));
         }
         e.obj.emplace_back("coverage", std::move(cov));
+        list.arr.push_back(std::move(e));
+    }
+    root.obj.emplace_back("alternatives", std::move(list));
+    std::string text;
+    spj::write_pretty(text, root);
+    if (needed) *needed = text.size() + 1;
+    if (out && cap) { const size_t n = std::min<size_t>(text.size(), (size_t)cap - 1); std::memcpy(out, text.data(), n); out[n] = 0; if (n < text.size()) return SP_ERR_CAPACITY; }
+    return SP_OK;
+}
+
+// cyp2d6_alternative_reads.json: the observed-chain table (the numbers of the reference's cyp2d6_link_graph.svg) and each pair read by read -- the reads that are
+// not neutral for it
+extern "C" int32_t sp_cyp_alternative_reads_json(const sp_chain_problem* p, const sp_chain_alt* alts, uint32_t n_alts, const sp_chain_pair_read* reads, const char* const* read_names,
+                                                 const uint32_t* obs_chain_off, const uint32_t* obs_items, const double* obs_frequency, uint32_t n_obs_chains,
+                                                 const double* single_counts, const uint32_t* edge_from, const uint32_t* edge_to, const double* edge_weight, uint32_t n_edges,
+                                                 char* out, uint64_t cap, uint64_t* needed) {
+    if (!p || (n_alts && !alts) || (n_alts && p->n_reads && !reads) || (p->n_haps && !p->hap_type) || (n_obs_chains && (!obs_chain_off || !obs_items || !obs_frequency)) ||
+        (n_edges && (!edge_from || !edge_to || !edge_weight)))
+        return SP_ERR_INVALID_ARG;
+    const uint32_t H = p->n_haps, R = p->n_reads;
+    auto region = [&](int32_t h) { return std::to_string(h) + "_" + full_allele(p->hap_type[h], p->hap_subtype ? p->hap_subtype[h] : nullptr); };
+    spj::Value root = spj::object();
+    spj::Value observed = spj::object();
+    {
+        spj::Value chains = spj::array();
+        for (uint32_t c = 0; c < n_obs_chains; ++c) {
+            spj::Value names = spj::array();
+            for (uint32_t x = obs_chain_off[c]; x < obs_chain_off[c + 1]; ++x) { if (obs_items[x] >= H) return SP_ERR_INVALID_ARG; names.arr.push_back(spj::str(region((int32_t)obs_items[x]))); }
+            spj::Value e = spj::object();
+            e.obj.emplace_back("chain", std::move(names)); e.obj.emplace_back("reads", spj::real(obs_frequency[c]));
+            chains.arr.push_back(std::move(e));
+        }
+        observed.obj.emplace_back("chains", std::move(chains));
+        spj::Value regions = spj::array();
+        if (single_counts) for (uint32_t h = 0; h < H; ++h) {
+            if (single_counts[h] == 0.0) continue;
+            spj::Value e = spj::object();
+            e.obj.emplace_back("region", spj::str(region((int32_t)h))); e.obj.emplace_back("reads", spj::real(single_counts[h]));
+            regions.arr.push_back(std::move(e));
+        }
+        observed.obj.emplace_back("regions", std::move(regions));
+        spj::Value links = spj::array();
+        for (uint32_t x = 0; x < n_edges; ++x) {
+            if (edge_from[x] >= H || edge_to[x] >= H) return SP_ERR_INVALID_ARG;
+            spj::Value e = spj::object();
+            e.obj.emplace_back("from", spj::str(region((int32_t)edge_from[x]))); e.obj.emplace_back("to", spj::str(region((int32_t)edge_to[x])));
+            e.obj.emplace_back("reads", spj::real(edge_weight[x]));
+            links.arr.push_back(std::move(e));
+        }
+        observed.obj.emplace_back("links", std::move(links));
+    }
+    root.obj.emplace_back("observed", std::move(observed));
+    // hap1 / hap2 of the placements are the chains index1 / index2 name; `chains` lists the pair sorted, as cyp2d6_alternatives.json does: hap1_chain says which is hap1
+    K5Chains en;
+    if (n_alts && k5_enumerate(nullptr, p, en) != SP_OK) return SP_ERR_INVALID_ARG;
+    spj::Value list = spj::array();
+    for (uint32_t k = 0; k < n_alts; ++k) {
+        const sp_chain_alt& a = alts[k];
+        if (a.n1 < 0 || a.n2 < 0 || a.n1 > SP_MAX_CHAIN || a.n2 > SP_MAX_CHAIN) return SP_ERR_INVALID_ARG;
+        for (int32_t x = 0; x < a.n1; ++x) if (a.chain1[x] < 0 || (uint32_t)a.chain1[x] >= H) return SP_ERR_INVALID_ARG;
+        for (int32_t x = 0; x < a.n2; ++x) if (a.chain2[x] < 0 || (uint32_t)a.chain2[x] >= H) return SP_ERR_INVALID_ARG;
+        if (a.index1 < 0 || a.index1 > a.index2 || (size_t)a.index2 >= en.possible.size()) return SP_ERR_INVALID_ARG;
+        spj::Value e = spj::object();
+        e.obj.emplace_back("rank", spj::unum((uint64_t)k + 1));
+        char h1[1024], h2[1024];
+        sp_cyp_chain_to_hap(a.chain1, (uint32_t)a.n1, p->hap_type, p->hap_subtype, p->n_translate, p->translate_key, p->translate_val, 1, h1, sizeof h1);
+        sp_cyp_chain_to_hap(a.chain2, (uint32_t)a.n2, p->hap_type, p->hap_subtype, p->n_translate, p->translate_key, p->translate_val, 1, h2, sizeof h2);
+        e.obj.emplace_back("diplotype", spj::str(std::string(h1) + "/" + h2));
+        spj::Value chains = spj::array();
+        for (int which = 0; which < 2; ++which) {
+            spj::Value names = spj::array();
+            const int32_t* ch = which ? a.chain2 : a.chain1;
+            for (int32_t x = 0; x < (which ? a.n2 : a.n1); ++x) names.arr.push_back(spj::str(region(ch[x])));
+            chains.arr.push_back(std::move(names));
+        }
+        e.obj.emplace_back("chains", std::move(chains));
+        e.obj.emplace_back("hap1_chain", spj::unum(en.possible[a.index2] < en.possible[a.index1] ? 2 : 1));      // (k5_sorted_pair's swap)
+        e.obj.emplace_back("edit_distance", spj::unum(a.edit_distance));
+        e.obj.emplace_back("unmet_observations", spj::unum(a.unmet_observations));
+        const sp_chain_pair_read* mine = reads + (size_t)k * R;
+        if (k > 0) {
+            uint64_t decided_for = 0, against = 0;
+            for (uint32_t r = 0; r < R; ++r) { decided_for += mine[r].excess_ed > reads[r].excess_ed; against += mine[r].excess_ed < reads[r].excess_ed; }
+            e.obj.emplace_back("reads_decided_for", spj::unum(decided_for)); e.obj.emplace_back("reads_decided_against", spj::unum(against));
+        }
+        spj::Value rl = spj::array();
+        for (uint32_t r = 0; r < R; ++r) {
+            const sp_chain_pair_read& q = mine[r];
+            if (q.excess_ed == 0 && q.supported && q.excess_ed == reads[r].excess_ed) continue;                // neutral
+            spj::Value o = spj::object();
+            o.obj.emplace_back("read", spj::str(read_names && read_names[r] ? std::string(read_names[r]) : "read " + std::to_string(r)));
+            o.obj.emplace_back("excess_ed", spj::unum(q.excess_ed));
+            o.obj.emplace_back("delta_to_best", spj::num((int64_t)(q.excess_ed - reads[r].excess_ed)));
+            o.obj.emplace_back("supported", spj::boolean(q.supported != 0));
+            spj::Value pl = spj::array();
+            for (int which = 0; which < 2; ++which) {
+                uint64_t m = which ? q.mask2 : q.mask1;
+                while (m) { const int s = __builtin_ctzll(m); m &= m - 1; pl.arr.push_back(spj::str(std::string(which ? "hap2@" : "hap1@") + std::to_string(s))); }
+            }
+            o.obj.emplace_back("placements", std::move(pl));
+            rl.arr.push_back(std::move(o));
+        }
+        e.obj.emplace_back("reads", std::move(rl));
         list.arr.push_back(std::move(e));
     }
     root.obj.emplace_back("alternatives", std::move(list));

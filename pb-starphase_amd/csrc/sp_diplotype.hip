@@ -123,6 +123,7 @@ struct sp_starphase {
     int32_t support_insertions = 0;                  // sp_starphase_set_support_insertions: those two files also list the inserted strings of their contested columns
     int32_t support_haplotypes = 0;                  // sp_starphase_set_support_haplotypes: those two files also list the read haplotypes at their contested columns
     int32_t cyp_vcf = 0;                             // sp_starphase_set_cyp_vcf: a debug folder also receives cyp2d6_alleles.vcf.gz, with SR / CR from the support pass
+    int32_t cyp_alternative_reads = 0;               // sp_starphase_set_cyp_alternative_reads: a debug folder also receives cyp2d6_alternative_reads.json (those pairs read by read)
     int32_t cyp_alternatives = 0;                    // sp_starphase_set_cyp_alternatives: a debug folder also receives cyp2d6_alternatives.json (the ten best chain pairs)
     int32_t cyp_consensus_support = 0;               // sp_starphase_set_cyp_consensus_support: a debug folder also receives cyp2d6_consensus_support.json
     int32_t hla_ties = 0;                            // sp_starphase_set_hla_ties: a debug folder gets hla_ties.json, the alleles each consensus's a = 5 scan cannot tell from its winner
@@ -786,7 +787,7 @@ void cyp_problem(sp_starphase* h, sp_cyp_problem& pr) {
 
 // the CYP2D6 entry of a sample whose reads were typed: the call, multi_mapping_details, cyp2d6_alleles.json
 void cyp_package(sp_starphase* h, const sp_cyp_problem& pr, const sp_cyp_call& call, const sp_cyp_region_variants& rv, const std::vector<sp_cyp_read_mapping>& mappings,
-                 const std::vector<uint32_t>& order, const std::string& debug_folder, const std::string& alternatives, CypLane* L) {
+                 const std::vector<uint32_t>& order, const std::string& debug_folder, const std::string& alternatives, const std::string& alternative_reads, CypLane* L) {
     const std::vector<Read4>& reads = L->reads;
     sp_gene_details* d = L->entry.details->d;
     if (call.status == 16 || call.status == 17 || call.status == 18) {              // CallerError -> PgxGeneDetails::no_match() (src/diplotyper.rs:316-327)
@@ -816,6 +817,12 @@ void cyp_package(sp_starphase* h, const sp_cyp_problem& pr, const sp_cyp_call& c
             const std::string path = debug_folder + "/cyp2d6_alternatives.json";
             FILE* f = std::fopen(path.c_str(), "wb");
             if (!f || std::fwrite(alternatives.data(), 1, alternatives.size(), f) != alternatives.size()) { if (f) std::fclose(f); L->rc = SP_ERR_INVALID_ARG; L->err = "Error while writing " + path; return; }
+            std::fclose(f);
+        }
+        if (!debug_folder.empty() && !alternative_reads.empty()) {                 // sp_starphase_set_cyp_alternative_reads: the same search's pairs read by read
+            const std::string path = debug_folder + "/cyp2d6_alternative_reads.json";
+            FILE* f = std::fopen(path.c_str(), "wb");
+            if (!f || std::fwrite(alternative_reads.data(), 1, alternative_reads.size(), f) != alternative_reads.size()) { if (f) std::fclose(f); L->rc = SP_ERR_INVALID_ARG; L->err = "Error while writing " + path; return; }
             std::fclose(f);
         }
     }
@@ -919,6 +926,12 @@ void cyp_group(sp_starphase* h, std::vector<Sample*> group, bool only_ok, double
         // cyp2d6_alternatives.json (sp_starphase_set_cyp_alternatives): the samples with a debug folder run the N-best form of the chain-pair search, which leaves the text
         std::vector<std::string> alts(n); std::vector<std::string*> alt_of(n, nullptr); bool want_alts = false;
         for (uint32_t k = 0; k < n; ++k) if (h->cyp_alternatives && !typed[k]->debug.empty()) { alt_of[k] = &alts[k]; want_alts = true; }
+        // cyp2d6_alternative_reads.json (sp_starphase_set_cyp_alternative_reads): the same search, then its pairs read by read; the QNAMEs in the order of the sample's set
+        std::vector<SpiCypAltReads> areads(n); std::vector<SpiCypAltReads*> aread_of(n, nullptr); std::vector<std::vector<const char*>> qnames(n); bool want_areads = false;
+        for (uint32_t k = 0; k < n; ++k) if (h->cyp_alternative_reads && !typed[k]->debug.empty()) {
+            for (uint32_t i : orders[k]) qnames[k].push_back(typed[k]->cyp.reads[i].qname.c_str());
+            areads[k].read_names = qnames[k].data(); aread_of[k] = &areads[k]; want_areads = true;
+        }
         // cyp2d6_consensus_support.json: the calls also hand out their consensuses (the calls themselves are the same), for one support pass over the group below
         // cyp2d6_alleles.vcf.gz (sp_starphase_set_cyp_vcf) takes its SR / CR from the same pass: want_support is "the pass runs", want_json / want_vcf say what is written
         bool want_json = false, want_vcf = false;
@@ -930,16 +943,17 @@ void cyp_group(sp_starphase* h, std::vector<Sample*> group, bool only_ok, double
         const size_t cons_block = (size_t)SP_CYP_MAXCONS * cons_cap;
         std::vector<char> cons(want_support ? cons_block * n : 0, '\0');
         char* cons_out = want_support ? cons.data() : nullptr;
-        if (n > 1) spi_cyp_diplotype_cohort_mappings(h->ctx2, &pr, n, sets.data(), calls.data(), cons_out, cons_cap, rv.data(), mappings.data(), rcs.data(), want_alts ? alt_of.data() : nullptr);
+        if (n > 1) spi_cyp_diplotype_cohort_mappings(h->ctx2, &pr, n, sets.data(), calls.data(), cons_out, cons_cap, rv.data(), mappings.data(), rcs.data(), want_alts ? alt_of.data() : nullptr,
+                                                     want_areads ? aread_of.data() : nullptr);
         std::vector<uint8_t> packaged(n, 0);
         for (uint32_t k = 0; k < n; ++k) {
             CypLane* L = &typed[k]->cyp;
             if (rcs[k] != SP_OK) {
                 // alone: the only sample of the lane, or one the cohort call failed (the context's error text may be another sample's)
-                const int32_t rc = spi_cyp_diplotype_mappings(h->ctx2, &pr, sets[k], &calls[k], cons_out ? cons_out + cons_block * k : nullptr, cons_cap, &rv[k], &mappings[k], alt_of[k]);
+                const int32_t rc = spi_cyp_diplotype_mappings(h->ctx2, &pr, sets[k], &calls[k], cons_out ? cons_out + cons_block * k : nullptr, cons_cap, &rv[k], &mappings[k], alt_of[k], aread_of[k]);
                 if (rc != SP_OK) { L->rc = rc; L->err = "sp_cyp_diplotype: " + opt(sp_last_error(h->ctx2)); continue; }
             }
-            cyp_package(h, pr, calls[k], rv[k], mappings[k], orders[k], typed[k]->debug, alts[k], L);
+            cyp_package(h, pr, calls[k], rv[k], mappings[k], orders[k], typed[k]->debug, alts[k], areads[k].text, L);
             packaged[k] = L->rc == SP_OK;
         }
         if (want_support) {
@@ -1220,6 +1234,11 @@ int32_t sp_starphase_set_consensus_support(sp_starphase* h, int32_t on) {
 int32_t sp_starphase_set_cyp_alternatives(sp_starphase* h, int32_t on) {
     if (!h) return SP_ERR_INVALID_ARG;
     h->cyp_alternatives = on ? 1 : 0;
+    return SP_OK;
+}
+int32_t sp_starphase_set_cyp_alternative_reads(sp_starphase* h, int32_t on) {
+    if (!h) return SP_ERR_INVALID_ARG;
+    h->cyp_alternative_reads = on ? 1 : 0;
     return SP_OK;
 }
 int32_t sp_starphase_set_cyp_vcf(sp_starphase* h, int32_t on) {

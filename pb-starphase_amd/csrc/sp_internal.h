@@ -273,12 +273,19 @@ int32_t spi_cyp_support_cohort(sp_ctx* ctx, uint32_t n_samples, const sp_seqset*
                                const sp_cyp_read_mapping* mappings, const uint64_t* mapping_off, uint64_t* col_offset, sp_pileup_col* cols, uint64_t cols_cap,
                                sp_support_summary* summaries, sp_pileup_ins* ins, uint64_t ins_cap, uint64_t* n_ins,
                                sp_support_hap* haps, uint64_t hap_cap, uint64_t* n_haps, sp_support_hap_head* heads, const CypVariantIn* vin);
+// cyp2d6_alternative_reads.json of a sample (sp_starphase_set_cyp_alternative_reads).  read_names (in): the QNAMEs by read index of the sample's set -- the index
+// sp_cyp_read_mapping.read holds -- or NULL for "read <r>"; text (out): the file's text (empty: the sample has no call)
+struct SpiCypAltReads { const char* const* read_names = nullptr; std::string text; };
 // sp_cyp.hip, for sp_diplotype.hip: sp_cyp_diplotype_mappings with the list in a vector the library sizes
 int32_t spi_cyp_diplotype_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, const sp_seqset* reads, sp_cyp_call* call, char* consensus, uint32_t cons_cap,
-                                   sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings, std::string* alternatives = nullptr);
+                                   sp_cyp_region_variants* region_variants, std::vector<sp_cyp_read_mapping>* mappings, std::string* alternatives = nullptr,
+                                   SpiCypAltReads* alternative_reads = nullptr);
 // sp_cyp_diplotype_cohort that also hands out each sample's region variants and multi_mapping_details (optional, n_samples entries each)
 // alternatives (both; optional; the cohort call: n_samples pointers, NULL for a sample that does not want it): the chain-pair search is sp_cyp_best_chain_pairs with SP_CYP_ALTERNATIVES entries and the string receives the
 // text of cyp2d6_alternatives.json (empty: the sample has no call)
+// alternative_reads (both; optional; the cohort call as alternatives): the same N-best search -- one search when both are asked for --, then sp_cyp_chain_pair_reads on
+// its pairs and sp_cyp_observed_chains; the problem's read r is the sample's read the chain building names (the map multi_mapping_details uses)
 int32_t spi_cyp_diplotype_cohort_mappings(sp_ctx* ctx, const sp_cyp_problem* pr, uint32_t n_samples, const sp_seqset* const* reads, sp_cyp_call* calls,
                                           char* consensus, uint32_t cons_cap, sp_cyp_region_variants* region_variants,
-                                          std::vector<sp_cyp_read_mapping>* mappings, int32_t* sample_rc, std::string* const* alternatives = nullptr);
+                                          std::vector<sp_cyp_read_mapping>* mappings, int32_t* sample_rc, std::string* const* alternatives = nullptr,
+                                          SpiCypAltReads* const* alternative_reads = nullptr);

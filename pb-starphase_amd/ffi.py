@@ -111,6 +111,40 @@ class sp_chain_alt(C.Structure):
                 ("edit_distance", C.c_uint64), ("unmet_observations", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class sp_chain_pair_read(C.Structure):
+    _fields_ = [("mask1", C.c_uint64), ("mask2", C.c_uint64), ("excess_ed", C.c_uint64), ("n_best", C.c_uint32), ("supported", C.c_uint8), ("reserved_", C.c_uint8 * 3)]
+
+
+CHAIN_PAIR_READ_DTYPE = np.dtype([("mask1", np.uint64), ("mask2", np.uint64), ("excess_ed", np.uint64), ("n_best", np.uint32), ("supported", np.uint8),
+                                  ("reserved_", np.uint8, (3,))])
+
+
+def observed_chains(p, ctx=None, check=None):
+    """sp_cyp_observed_chains over a filled sp_chain_problem: (chains [[region, ...], ...] in lexicographic order, frequency f64 [n_chains], single_counts f64
+    [n_haps], edges [(from, to)], edge_weight f64 [n_edges]); host only, so ctx may be None"""
+    def fail(rc):
+        if check:
+            check(rc)
+        raise StarphaseError(rc, "sp_cyp_observed_chains")
+    n_chains, n_items, n_edges = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    single = np.zeros(max(1, int(p.n_haps)), np.float64)
+    rc = lib().sp_cyp_observed_chains(ctx, C.byref(p), None, 0, None, 0, None, single.ctypes.data, None, None, None, 0, C.byref(n_chains), C.byref(n_items), C.byref(n_edges))
+    if rc != SP_ERR_CAPACITY:
+        fail(rc)
+    off = np.zeros(n_chains.value + 1, np.uint32)
+    items = np.zeros(max(1, n_items.value), np.uint32)
+    freq = np.zeros(n_chains.value + 1, np.float64)
+    e_from, e_to = np.zeros(max(1, n_edges.value), np.uint32), np.zeros(max(1, n_edges.value), np.uint32)
+    e_w = np.zeros(max(1, n_edges.value), np.float64)
+    rc = lib().sp_cyp_observed_chains(ctx, C.byref(p), off.ctypes.data, len(off), items.ctypes.data, len(items), freq.ctypes.data, single.ctypes.data, e_from.ctypes.data,
+                                      e_to.ctypes.data, e_w.ctypes.data, len(e_w), C.byref(n_chains), C.byref(n_items), C.byref(n_edges))
+    if rc != SP_OK:
+        fail(rc)
+    ne = n_edges.value
+    return ([[int(v) for v in items[off[c]:off[c + 1]]] for c in range(n_chains.value)], freq[:n_chains.value], single[:int(p.n_haps)],
+            [(int(a), int(b)) for a, b in zip(e_from[:ne], e_to[:ne])], e_w[:ne])
+
+
 REGION_HIT_DTYPE = np.dtype([(n, np.int32) for n in ("read", "template_idx", "start", "end", "seq_len", "nm", "unmapped", "clip_start", "clip_end",
                                                      "mm2_score", "mm2_nm", "mm2_start", "mm2_end", "mm2_q_start", "mm2_q_end")])
 
@@ -549,6 +583,11 @@ def lib():
         "sp_cyp_best_chain_pairs": (i32, [vp, C.POINTER(sp_chain_problem), C.c_uint32, C.POINTER(sp_chain_alt), C.POINTER(C.c_uint32), vp, vp, C.POINTER(sp_chain_result)]),
         "sp_cyp_possible_chains": (i32, [vp, C.POINTER(sp_chain_problem), vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "sp_cyp_alternatives_json": (i32, [C.POINTER(sp_chain_problem), C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(sp_chain_alt), C.c_uint32, vp, vp, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "sp_cyp_chain_pair_reads": (i32, [vp, C.POINTER(sp_chain_problem), C.c_uint32, vp, vp, vp, vp, vp]),
+        "sp_cyp_observed_chains": (i32, [vp, C.POINTER(sp_chain_problem), vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint32)]),
+        "sp_cyp_alternative_reads_json": (i32, [C.POINTER(sp_chain_problem), C.POINTER(sp_chain_alt), C.c_uint32, vp, C.POINTER(C.c_char_p), vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32,
+                                                C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "sp_anchor_batch_topk": (i32, [vp, vp, vp, vp, vp, u64, i32, vp, vp]),
         "sp_cyp_find_regions": (i32, [vp, vp, vp, vp, C.c_double, vp, u64, C.POINTER(u64)]),
         "sp_cyp_weight_segments": (i32, [vp, vp, vp, vp, vp, vp, vp]),
@@ -1011,6 +1050,38 @@ class Context:
                                       read_w_off, w_ed, w_ov, infer, normalize_all, ignore_limits, penalties)
         n_chains, n_items = C.c_uint32(0), C.c_uint32(0)
         return possible_chains(p, self._h, self.check)
+
+    def cyp_chain_pair_reads(self, hap_type, hap_subtype, translate, connections, singletons, read_chain_off, chain_off, chain_items,
+                             read_w_off, w_ed, w_ov, infer, normalize_all, ignore_limits, penalties, pairs=(), totals=True):
+        """sp_cyp_chain_pair_reads: the pairs [(index1, index2), ...] (enumeration order, index1 <= index2; 1..64 of them) read by read.  Returns (status, records
+        [n_pairs, n_reads] of CHAIN_PAIR_READ_DTYPE, edit_distance u64 [n_pairs], unmet_observations u32 [n_pairs]) -- the totals None with totals=False.  Expected
+        failures (16/17) are returned, not raised."""
+        p, keep = self._chain_problem(hap_type, hap_subtype, translate, connections, singletons, read_chain_off, chain_off, chain_items,
+                                      read_w_off, w_ed, w_ov, infer, normalize_all, ignore_limits, penalties)
+        pairs = list(pairs)
+        n = len(pairs)
+        i1 = np.array([a for a, _ in pairs] or [0], np.int32)
+        i2 = np.array([b for _, b in pairs] or [0], np.int32)
+        R = int(p.n_reads)
+        recs = np.zeros((max(1, n), max(1, R)), CHAIN_PAIR_READ_DTYPE)
+        ed = np.zeros(max(1, n), np.uint64) if totals else None
+        un = np.zeros(max(1, n), np.uint32) if totals else None
+        rc = lib().sp_cyp_chain_pair_reads(self._h, C.byref(p), n, i1.ctypes.data, i2.ctypes.data, recs.ctypes.data,
+                                           ed.ctypes.data if totals else None, un.ctypes.data if totals else None)
+        if rc not in (0, 16, 17, 18):
+            self.check(rc)
+        if rc != 0:
+            return rc, recs[:0, :0], None, None
+        # the library writes [n][R] densely: the array above has that shape unless R == 0
+        return rc, recs[:n, :R], (ed[:n] if totals else None), (un[:n] if totals else None)
+
+    def cyp_observed_chains(self, hap_type, hap_subtype, translate, connections, singletons, read_chain_off, chain_off, chain_items,
+                            read_w_off, w_ed, w_ov, infer, normalize_all, ignore_limits, penalties):
+        """sp_cyp_observed_chains: the observed-chain table (chain_frequency) and the node / edge totals of the reference's link graph.  Returns (chains, frequency,
+        single_counts, edges, edge_weight) as ffi.observed_chains."""
+        p, keep = self._chain_problem(hap_type, hap_subtype, translate, connections, singletons, read_chain_off, chain_off, chain_items,
+                                      read_w_off, w_ed, w_ov, infer, normalize_all, ignore_limits, penalties)
+        return observed_chains(p, self._h, self.check)
 
     def anchor_batch_topk(self, A, B, a_idx, b_idx, topk):
         a_idx = np.ascontiguousarray(a_idx, np.uint32)
