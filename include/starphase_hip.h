@@ -1158,6 +1158,57 @@ int32_t sp_variant_solve(sp_ctx* ctx, const sp_variant_problem* problem, sp_vari
  * results[i] and problem_rc[i] (optional) are what sp_variant_solve gives for problems[i]; returns the first status that is not SP_OK */
 int32_t sp_variant_solve_batch(sp_ctx* ctx, uint32_t n, const sp_variant_problem* const* problems, sp_variant_result* results, int32_t* problem_rc);
 
+/* The runner-up diplotypes: what solve_diplotype prints of every combination at debug level and throws away (src/diplotyper.rs:1263-1357).
+ * For a problem as sp_variant_solve takes it a CANDIDATE is (comb, dip0, dip1): comb a het assignment, 0 <= comb < n_comb (2^(groups - 1); 1 without
+ * het calls), dip0 an explanation of side 0 and dip1 one of side 1.
+ *   - A side that carries an SV label (obs_sv_label >= 0 on one of its members -- the homozygous calls first, then the side's het calls, each in call
+ *     order) has exactly one explanation, -(first label + 2), with the side score (0, number of distinct labels among the remaining labelled
+ *     members, 0, 0): the short-circuit of find_best_inexact_matches (:1414-1431).
+ *   - Any other side is explained by every haplotype h that is not an SV haplotype and has core missing <= 1 (the reference's (1, MAX, MAX, MAX)
+ *     bound); the side score is the cell's (core missing, core extra, sub missing, sub extra), the number the solve computes.  A side with no
+ *     such haplotype makes its assignment contribute no candidate.
+ *   - A problem without het calls has one side: its candidates are (0, h, h) and the total is that one side score, not doubled (:1239-1250);
+ *     side_score[1] repeats side_score[0].  Otherwise the total is the component-wise sum of the two side scores.
+ *   - There is no sub-allele shadowing: a core allele tied with a sub-allele on its side is a candidate like any other; SP_VAR_ALT_SHADOWED says
+ *     that the reference's call drops it.
+ *   - The list is ordered by (total score lexicographically, comb, dip0, dip1) ascending, dip compared as the signed value: a strict total order,
+ *     so the n_best (1..64) first candidates are unique; they do not depend on the launch shape, the stream count or the position in a batch.
+ * alts: n_best records; info->n_alts = min(n_best, candidates) are filled, the others are zero.  info->n_candidates: the sum over the assignments of
+ * eligible explanations of side 0 x side 1.  info->best_score: the score sp_variant_solve reports -- entry 0's total whenever the solve lists a
+ * diplotype, (core missing, MAX, MAX, MAX) when the smallest total belongs to an assignment with a side nothing explains (the solve then lists no
+ * diplotype and n_called is 0, though candidates may exist: solve_diplotype compares such a total like any other, :1319-1357).  info->n_called: the
+ * candidates at best_score that the reference's call keeps, i.e. sp_variant_solve's n_dip without its SP_VAR_MAXDIP bound.  Limits and statuses are
+ * those of the solve (64 observations, 64 slots per haplotype, 24 groups); the batch form reports a failing problem in problem_rc (optional),
+ * leaves its records zero, runs the others and returns the first status that is not SP_OK.  All problems of a batch run in one launch pair; device
+ * memory is the tables plus workgroups x n_best records, pooled, whatever n_comb is.  The grid: with P problems in the launch, a problem runs on
+ * min(n_comb, max(1, 8 * CUs / P)) one-wave workgroups (CUs: sp_ctx_get_info), each taking every wg_count-th assignment; the profile entry "k6_alt" counts
+ * them as its cells. */
+typedef struct { int64_t score[4]; int32_t side_score[2][4]; int32_t dip[2]; int32_t comb; uint32_t flags; } sp_variant_alt;
+typedef struct { uint64_t n_comb, n_candidates; int64_t best_score[4]; uint32_t n_alts, n_called; } sp_variant_alt_info;
+#define SP_VAR_ALT_CALLED   1u   /* (dip, comb) is one of sp_variant_solve's diplotypes */
+#define SP_VAR_ALT_SHADOWED 2u   /* at the best total, but dropped from the call: a core allele tied with a sub-allele on its side */
+#define SP_VAR_ALTERNATIVES 10   /* what the whole-sample switch asks for */
+int32_t sp_variant_alternatives(sp_ctx* ctx, const sp_variant_problem* problem, uint32_t n_best, sp_variant_alt* alts, sp_variant_alt_info* info);
+int32_t sp_variant_alternatives_batch(sp_ctx* ctx, uint32_t n, const sp_variant_problem* const* problems, uint32_t n_best, sp_variant_alt* alts /* n * n_best */,
+                                      sp_variant_alt_info* infos, int32_t* problem_rc);
+/* host only: the variants of side `side` (0 / 1) of het assignment comb under explanation dip, as the inexact haplotypes of the call name them
+ * (het_split + quant_match, :1516-1550): the matching ids (SP_REL_MATCH), then the haplotype's unmatched variants (SP_REL_MISSING), then the side's
+ * unexplained ones (SP_REL_UNEXPECTED).  Their MISSING / UNEXPECTED counts, split by var_is_core, are the record's side_score.  dip < 0 (an SV label):
+ * the member that carries the label (MATCH) and the first member of every distinct label behind it (UNEXPECTED).  *n is always set (0 on
+ * SP_ERR_INVALID_ARG); SP_ERR_CAPACITY when cap < *n; SP_ERR_INVALID_ARG for a side other than 0 / 1, a comb outside 0 .. n_comb - 1, a dip >= n_haps and an SV
+ * label that is not the first one the side carries.  Any haplotype 0 .. n_haps - 1 is answered, also one the search does not list (an SV haplotype, core
+ * missing > 1). */
+int32_t sp_variant_alt_relations(const sp_variant_problem* problem, int32_t comb, int32_t side, int32_t dip, int32_t* ids, int32_t* rel, uint32_t cap, uint32_t* n);
+/* host only: the text of one gene's entry of variant_alternatives.json: {"n_combinations", "n_candidates", "best_score", "alternatives": [...]}, best
+ * first; an alternative has rank (1: the best), diplotype ("a/b" as the main call would spell this candidate: haplotype names for a score of
+ * (0, 0, 0, 0), core allele names for (0, 0, ., .), NO_MATCH/NO_MATCH otherwise), called, shadowed, score {core_missing, core_unexpected,
+ * sub_missing, sub_unexpected} (null: unset), combination, hap1 / hap2 {haplotype, score, missing, unexpected} with the variant names of
+ * sp_variant_alt_relations.  Names come from the caller: hap_names / hap_core_names [n_haps] (the core allele of a sub-allele, its own name for a
+ * core allele), sv_labels [n_sv_labels] (obs_sv_label ids), var_names [n_vars].  out / cap / needed as sp_cyp_alleles_json. */
+int32_t sp_variant_alternatives_json(const sp_variant_problem* problem, const sp_variant_alt_info* info, const sp_variant_alt* alts, const char* const* hap_names,
+                                     const char* const* hap_core_names, const char* const* sv_labels, uint32_t n_sv_labels, const char* const* var_names,
+                                     char* out, uint64_t cap, uint64_t* needed);
+
 /* is_deletion (src/diplotyper.rs:1020-1174): which defined deletion haplotype, if any, a deleted region [start, end) (0-based,
  * end exclusive) is; its label is what load_sv_vcf_variants (:739-857) attaches to the observed SV (obs_sv_label above).
  * Full-gene deletions are tried first (is_full_deletion, :1034-1089: a gene counts when its coordinates lie inside the region),
@@ -1849,6 +1900,12 @@ int32_t sp_starphase_set_cyp_alternatives(sp_starphase* handle, int32_t on);
  * without the other), the reads named by their QNAMEs.  The single call, a batch and the cohort call write the same bytes for a sample.  Off, or no debug folder:
  * nothing more is launched or pooled and every output is the same bytes; on: every other output is. */
 int32_t sp_starphase_set_cyp_alternative_reads(sp_starphase* handle, int32_t on);
+/* variant_alternatives.json, off by default (on 0): with it on, the samples of a group that have a debug folder run one sp_variant_alternatives_batch
+ * (n_best SP_VAR_ALTERNATIVES) beside the group's one sp_variant_solve_batch, and each receives <folder>/variant_alternatives.json: one object keyed by
+ * gene name, in name order, with sp_variant_alternatives_json's entry for every variant gene solved for the sample (a gene answered without a solve --
+ * no variants in the database -- has no entry).  The single call and a batch write the same bytes for a sample.  Off, or no debug folder: nothing more
+ * is launched or pooled and every output is the same bytes; on: every other output is. */
+int32_t sp_starphase_set_variant_alternatives(sp_starphase* handle, int32_t on);
 /* A switch of its own, off by default, with effect only where one of the two switches above writes its file: the support pass of that file also makes the insertion
  * list (sp_hla_consensus_support_cohort_ins / sp_cyp_consensus_support_cohort_ins: the same one pass per batch group) and the file is rendered with it
  * (sp_consensus_support_json_ins / sp_cyp_support_json_ins, without first_read): every contested column with 2 * ins > depth gains "insertions" (and "more", "other").

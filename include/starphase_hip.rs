@@ -33,6 +33,9 @@ pub const SP_CYP_ALTERNATIVES: i64 = 10;
 pub const SP_CYP_MAXCONS: i64 = 64;
 pub const SP_CYP_VCF_FLANK: i64 = 2;
 pub const SP_VAR_MAXDIP: i64 = 4096;
+pub const SP_VAR_ALT_CALLED: i64 = 1;
+pub const SP_VAR_ALT_SHADOWED: i64 = 2;
+pub const SP_VAR_ALTERNATIVES: i64 = 10;
 pub const SP_GROUP_ID_BYTES: i64 = 128;
 
 #[repr(C)]
@@ -478,6 +481,22 @@ pub struct sp_variant_result {
     pub overflow: i32,
     pub dip: [[i32; 2]; SP_VAR_MAXDIP as usize],
     pub dip_comb: [i32; SP_VAR_MAXDIP as usize],
+}
+#[repr(C)]
+pub struct sp_variant_alt {
+    pub score: [i64; 4],
+    pub side_score: [[i32; 4]; 2],
+    pub dip: [i32; 2],
+    pub comb: i32,
+    pub flags: u32,
+}
+#[repr(C)]
+pub struct sp_variant_alt_info {
+    pub n_comb: u64,
+    pub n_candidates: u64,
+    pub best_score: [i64; 4],
+    pub n_alts: u32,
+    pub n_called: u32,
 }
 #[repr(C)]
 pub struct sp_sv_definitions {
@@ -939,6 +958,10 @@ extern "C" {
     pub fn sp_cyp_db_problem(db: *const sp_cyp_db, problem: *mut sp_cyp_problem) -> i32;
     pub fn sp_variant_solve(ctx: *mut sp_ctx, problem: *const sp_variant_problem, result: *mut sp_variant_result) -> i32;
     pub fn sp_variant_solve_batch(ctx: *mut sp_ctx, n: u32, problems: *const *const sp_variant_problem, results: *mut sp_variant_result, problem_rc: *mut i32) -> i32;
+    pub fn sp_variant_alternatives(ctx: *mut sp_ctx, problem: *const sp_variant_problem, n_best: u32, alts: *mut sp_variant_alt, info: *mut sp_variant_alt_info) -> i32;
+    pub fn sp_variant_alternatives_batch(ctx: *mut sp_ctx, n: u32, problems: *const *const sp_variant_problem, n_best: u32, alts: *mut sp_variant_alt, infos: *mut sp_variant_alt_info, problem_rc: *mut i32) -> i32;
+    pub fn sp_variant_alt_relations(problem: *const sp_variant_problem, comb: i32, side: i32, dip: i32, ids: *mut i32, rel: *mut i32, cap: u32, n: *mut u32) -> i32;
+    pub fn sp_variant_alternatives_json(problem: *const sp_variant_problem, info: *const sp_variant_alt_info, alts: *const sp_variant_alt, hap_names: *const *const c_char, hap_core_names: *const *const c_char, sv_labels: *const *const c_char, n_sv_labels: u32, var_names: *const *const c_char, out: *mut c_char, cap: u64, needed: *mut u64) -> i32;
     pub fn sp_variant_is_deletion(defs: *const sp_sv_definitions, start: u64, end: u64, kind: *mut i32, index: *mut i32) -> i32;
     pub fn sp_consensus_batch(ctx: *mut sp_ctx, n_problems: u32, problems: *const sp_cons_problem, outputs: *mut sp_cons_output) -> i32;
     pub fn sp_consensus_dual_batch(ctx: *mut sp_ctx, n_problems: u32, problems: *const sp_cons_problem, outputs: *mut sp_cons_output) -> i32;
@@ -1065,6 +1088,7 @@ extern "C" {
     pub fn sp_starphase_set_cyp_vcf(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_cyp_alternatives(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_cyp_alternative_reads(handle: *mut sp_starphase, on: i32) -> i32;
+    pub fn sp_starphase_set_variant_alternatives(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_support_insertions(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_set_support_haplotypes(handle: *mut sp_starphase, on: i32) -> i32;
     pub fn sp_starphase_warnings(handle: *const sp_starphase) -> *const c_char;

@@ -143,6 +143,8 @@ int32_t sp_struct_size(const char* name) {
     SP_SZ(sp_chain_problem)
     SP_SZ(sp_chain_result)
     SP_SZ(sp_chain_alt)
+    SP_SZ(sp_variant_alt)
+    SP_SZ(sp_variant_alt_info)
     SP_SZ(sp_chain_pair_read)
     SP_SZ(sp_region_hit)
     SP_SZ(sp_cyp_problem)

@@ -12,6 +12,7 @@
 // sp_starphase_call is that pipeline for a group of one, decoding its files inside its lanes; sp_starphase_call_batch runs it per group of max_group
 // samples, the host decode of the next group beside the device work of this one.
 #include "sp_internal.h"
+#include "sp_json.h"
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -123,6 +124,7 @@ struct sp_starphase {
     int32_t support_insertions = 0;                  // sp_starphase_set_support_insertions: those two files also list the inserted strings of their contested columns
     int32_t support_haplotypes = 0;                  // sp_starphase_set_support_haplotypes: those two files also list the read haplotypes at their contested columns
     int32_t cyp_vcf = 0;                             // sp_starphase_set_cyp_vcf: a debug folder also receives cyp2d6_alleles.vcf.gz, with SR / CR from the support pass
+    int32_t variant_alternatives = 0;                // sp_starphase_set_variant_alternatives: a debug folder also receives variant_alternatives.json (the ten best candidates of every solved variant gene)
     int32_t cyp_alternative_reads = 0;               // sp_starphase_set_cyp_alternative_reads: a debug folder also receives cyp2d6_alternative_reads.json (those pairs read by read)
     int32_t cyp_alternatives = 0;                    // sp_starphase_set_cyp_alternatives: a debug folder also receives cyp2d6_alternatives.json (the ten best chain pairs)
     int32_t cyp_consensus_support = 0;               // sp_starphase_set_cyp_consensus_support: a debug folder also receives cyp2d6_consensus_support.json
@@ -177,46 +179,6 @@ const char* chrom_bases(sp_starphase* h, const std::string& chrom, uint64_t* len
 }
 
 // ---------------------------------------------------------------- variant genes
-// het_split of solve_diplotype (src/diplotyper.rs:1263-1317): the two observed haplotypes of het assignment `comb` as problem variant ids --
-// the homozygous variants first, then the heterozygous ones in call order
-void het_split(const sp_variant_problem& p, int32_t comb, std::vector<int32_t>& h1, std::vector<int32_t>& h2) {
-    h1.clear();
-    for (int o = 0; o < p.n_obs; ++o) if (p.obs_gt[o] == SP_GT_HOM_ALT) h1.push_back(p.obs_var[o]);
-    h2 = h1;
-    int combo_index = 0;
-    std::map<int64_t, int> lookup;
-    for (int o = 0; o < p.n_obs; ++o) {
-        if (p.obs_gt[o] == SP_GT_HOM_ALT) continue;
-        int is_h1;
-        const int64_t ps = p.obs_ps[o];
-        if (ps >= 0) {
-            auto it = lookup.find(ps);
-            if (it == lookup.end()) { it = lookup.emplace(ps, (comb >> combo_index) & 1).first; ++combo_index; }
-            is_h1 = it->second;
-        } else { is_h1 = (comb >> combo_index) & 1; ++combo_index; }
-        ((is_h1 != 0) == (p.obs_gt[o] != SP_GT_HET_FLIP) ? h1 : h2).push_back(p.obs_var[o]);
-    }
-}
-
-// NormalizedPgxHaplotype::quant_match (src/data_types/normalized_variant.rs:431-479) on ids: matching / missing / extra variants
-void quant_match(const sp_variant_problem& p, int h, const std::vector<int32_t>& obs, std::vector<int32_t>& match, std::vector<int32_t>& missing,
-                 std::vector<int32_t>& extra) {
-    const int s0 = p.slot_off[h], s1 = p.slot_off[h + 1];
-    std::vector<uint8_t> matched((size_t)(s1 - s0) + 1, 0);
-    match.clear(); missing.clear(); extra.clear();
-    for (int32_t v : obs) {
-        int mi = -1;
-        for (int s = s0; s < s1 && mi < 0; ++s)
-            for (int x = p.alt_off[s]; x < p.alt_off[s + 1]; ++x) if (p.alt_var[x] == v) { mi = s - s0; break; }
-        if (mi >= 0 && !matched[mi]) { matched[mi] = 1; match.push_back(v); } else extra.push_back(v);
-    }
-    for (int s = s0; s < s1; ++s) {
-        bool has_none = false; int first_some = -1;
-        for (int x = p.alt_off[s]; x < p.alt_off[s + 1]; ++x) { if (p.alt_var[x] < 0) has_none = true; else if (first_some < 0) first_some = p.alt_var[x]; }
-        if (!(matched[s - s0] || has_none)) missing.push_back(first_some);
-    }
-}
-
 // A variant problem points into its sp_variant_gene, which keeps only its last problem.  This is a problem on its own: the arrays, and what the gene
 // says about this problem's ids (id -> database variant or deletion, the deletion labels), so solving and packaging need the gene's static tables only.
 struct OwnedProblem {
@@ -286,13 +248,13 @@ int32_t package_gene(sp_starphase* h, const sp_starphase::VGene& vg, const Owned
         if (exact_sub) continue;
         // derive_inexact_haplotype (:1516-1550) of both sides
         std::vector<int32_t> side[2];
-        het_split(p, res.dip_comb[i], side[0], side[1]);
+        spi_het_split(p, res.dip_comb[i], side[0], side[1]);
         std::string base[2]; std::vector<std::string> labels[2]; std::vector<uint8_t> vi[2]; std::vector<int32_t> st[2];
         for (int k = 0; k < 2; ++k) {
             const int32_t x = res.dip[i][k];
             if (x >= 0) {
                 std::vector<int32_t> m, mi, ex;
-                quant_match(p, x, side[k], m, mi, ex);
+                spi_quant_match(p, x, side[k], m, mi, ex);
                 base[k] = hap_name(x);
                 for (int32_t v : m)  { labels[k].push_back(var[v].name); vi[k].push_back(var[v].is_core); st[k].push_back(SP_REL_MATCH); }
                 for (int32_t v : mi) { labels[k].push_back(var[v].name); vi[k].push_back(var[v].is_core); st[k].push_back(SP_REL_MISSING); }
@@ -391,7 +353,68 @@ struct VarSample {
     VcfFetch vf;                                     // read by vcf_fetch
     int32_t rc = SP_OK; std::string err;
     std::vector<Entry> entries; std::vector<OwnedProblem> probs; size_t res0 = 0;
+    std::string alt_folder;                          // sp_starphase_set_variant_alternatives: where variant_alternatives.json goes (empty: not asked for)
 };
+
+// variant_alternatives.json of the samples that ask for it: ONE sp_variant_alternatives_batch over their problems, then one object per sample, keyed by gene name
+// in name order (the order of vgenes), each value sp_variant_alternatives_json's text with the names package_gene uses
+void variant_alternatives_save(sp_starphase* h, const std::vector<VarSample*>& solving) {
+    std::vector<const sp_variant_problem*> pp; std::vector<VarSample*> want;
+    for (VarSample* b : solving) if (b->rc == SP_OK && !b->alt_folder.empty()) { want.push_back(b); for (auto& q : b->probs) pp.push_back(&q.p); }
+    if (want.empty()) return;
+    const uint32_t N = SP_VAR_ALTERNATIVES;
+    std::vector<sp_variant_alt> alts(std::max<size_t>(1, pp.size() * N)); std::vector<sp_variant_alt_info> infos(std::max<size_t>(1, pp.size()));
+    if (!pp.empty()) {
+        const int32_t rc = sp_variant_alternatives_batch(h->ctx, (uint32_t)pp.size(), pp.data(), N, alts.data(), infos.data(), nullptr);
+        if (rc != SP_OK) { for (VarSample* b : want) { b->rc = rc; b->err = "sp_variant_alternatives_batch: " + opt(sp_last_error(h->ctx)); } return; }
+    }
+    size_t first = 0;
+    for (VarSample* b : want) {
+        std::string text = "{";
+        const size_t base = first; first += b->probs.size();
+        for (size_t k = 0; k < b->probs.size(); ++k) {
+            const size_t at = base + k;
+            const OwnedProblem& q = b->probs[k];
+            const sp_starphase::VGene& vg = h->vgenes[q.gene];
+            std::vector<std::string> hap((size_t)std::max(0, q.p.n_haps)), hap_core(hap.size()), var((size_t)std::max(0, q.p.n_vars));
+            for (size_t x = 0; x < hap.size(); ++x) {
+                const char* n = nullptr; const char* c = nullptr; sp_variant_gene_haplotype(vg.g, (uint32_t)x, &n, &c);
+                hap[x] = opt(n); hap_core[x] = c ? std::string(c) : opt(n);
+            }
+            for (size_t v = 0; v < var.size(); ++v) {
+                var[v] = "structural_variant";
+                if (q.vars[v].db_variant >= 0) {
+                    uint64_t pos; const char *r, *a, *nm, *dbsnp; int64_t vid; int32_t core;
+                    sp_variant_gene_variant(vg.g, (uint32_t)q.vars[v].db_variant, &pos, &r, &a, &nm, &dbsnp, &vid, &core);
+                    var[v] = opt(nm);
+                }
+            }
+            std::vector<const char*> hp, hcp, vp, lp;
+            for (auto& x : hap) hp.push_back(x.c_str());
+            for (auto& x : hap_core) hcp.push_back(x.c_str());
+            for (auto& x : var) vp.push_back(x.c_str());
+            for (auto& x : q.labels) lp.push_back(x.c_str());
+            uint64_t need = 0;
+            int32_t rc = sp_variant_alternatives_json(&q.p, &infos[at], alts.data() + at * N, hp.data(), hcp.data(), lp.data(), (uint32_t)lp.size(), vp.data(), nullptr, 0, &need);
+            std::string entry((size_t)need, '\0');
+            if (rc == SP_OK) rc = sp_variant_alternatives_json(&q.p, &infos[at], alts.data() + at * N, hp.data(), hcp.data(), lp.data(), (uint32_t)lp.size(), vp.data(), &entry[0], need, &need);
+            if (rc != SP_OK) { b->rc = rc; b->err = vg.name + ": bad variant alternatives"; break; }
+            entry.resize(std::strlen(entry.c_str()));
+            std::string nested;
+            for (char ch : entry) { nested += ch; if (ch == '\n') nested += "  "; }
+            std::string key;
+            spj::write_string(key, vg.name);
+            text += std::string(k ? ",\n  " : "\n  ") + key + ": " + nested;
+        }
+        text += b->probs.empty() ? "}" : "\n}";
+        if (b->rc == SP_OK) {
+            const std::string path = b->alt_folder + "/variant_alternatives.json";
+            FILE* f = std::fopen(path.c_str(), "wb");
+            if (!f || std::fwrite(text.data(), 1, text.size(), f) != text.size()) { if (f) std::fclose(f); b->rc = SP_ERR_INVALID_ARG; b->err = "Error while writing " + path; continue; }
+            std::fclose(f);
+        }
+    }
+}
 
 // call_diplotypes' gene loop (src/diplotyper.rs:94-204) for every sample of `group` whose VCF was read: each sample's problems, ONE
 // sp_variant_solve_batch over all of them, then the entries sample by sample.  A failure and its text belong to the sample that has it: when the
@@ -438,6 +461,7 @@ void variant_samples(sp_starphase* h, const std::vector<VarSample*>& group) {
             }
         }
     }
+    variant_alternatives_save(h, solving);
     for (VarSample* b : solving) {
         for (size_t k = 0; k < b->probs.size() && b->rc == SP_OK; ++k) {
             const OwnedProblem& q = b->probs[k];
@@ -1236,6 +1260,11 @@ int32_t sp_starphase_set_cyp_alternatives(sp_starphase* h, int32_t on) {
     h->cyp_alternatives = on ? 1 : 0;
     return SP_OK;
 }
+int32_t sp_starphase_set_variant_alternatives(sp_starphase* h, int32_t on) {
+    if (!h) return SP_ERR_INVALID_ARG;
+    h->variant_alternatives = on ? 1 : 0;
+    return SP_OK;
+}
 int32_t sp_starphase_set_cyp_alternative_reads(sp_starphase* h, int32_t on) {
     if (!h) return SP_ERR_INVALID_ARG;
     h->cyp_alternative_reads = on ? 1 : 0;
@@ -1446,7 +1475,7 @@ int32_t sp_starphase_call_batch(sp_starphase* h, uint32_t n, const sp_sample_inp
         if (!h->s.sequential) cyp = std::thread(cyp_group, h, group, false, &cyp_ms);
         auto t0 = std::chrono::steady_clock::now();
         std::vector<VarSample*> vs;
-        for (Sample* b : group) if (b->rc == SP_OK) vs.push_back(b);
+        for (Sample* b : group) if (b->rc == SP_OK) { if (h->variant_alternatives) b->alt_folder = b->debug; vs.push_back(b); }
         variant_samples(h, vs);
         for (VarSample* v : vs) if (v->rc != SP_OK) static_cast<Sample*>(v)->stage = 1;
         T.variant_ms += ms_since(t0);
@@ -1489,6 +1518,7 @@ int32_t sp_starphase_call(sp_starphase* h, const sp_sample_inputs* in, sp_result
     auto t0 = std::chrono::steady_clock::now();
     if (b.has_vcf) {
         vcf_fetch(h, h->win, b.vcf, b.sv, b.sample, b.vf);
+        if (h->variant_alternatives) b.alt_folder = b.debug;
         variant_samples(h, {&b});
         if (b.rc != SP_OK) b.stage = 1;
     }

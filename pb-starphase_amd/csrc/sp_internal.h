@@ -241,6 +241,11 @@ struct ProfScope {
 };
 
 
+// sp_variant.hip, for sp_diplotype.hip and sp_variant_alt_relations: het_split of solve_diplotype (src/diplotyper.rs:1263-1317) -- the two observed haplotypes of het
+// assignment `comb` as problem variant ids, the homozygous variants first, then the heterozygous ones in call order -- and NormalizedPgxHaplotype::quant_match
+// (src/data_types/normalized_variant.rs:431-479) on ids: the matching, missing and extra variants of haplotype h against one of those lists
+void spi_het_split(const sp_variant_problem& p, int32_t comb, std::vector<int32_t>& h1, std::vector<int32_t>& h2);
+void spi_quant_match(const sp_variant_problem& p, int h, const std::vector<int32_t>& obs, std::vector<int32_t>& match, std::vector<int32_t>& missing, std::vector<int32_t>& extra);
 // sp_database.hip, for sp_diplotype.hip (not part of the C ABI)
 int32_t spi_gene_entry_extras(const sp_database* db, const sp_variant_gene* g, std::string* reference_allele, bool* has_sv, std::string* sv_chrom);
 // sp_hla.hip, for sp_diplotype.hip: allele a of the database in hg38 orientation (the target of sp_hla_realign_cigars), ASCII; empty: no DNA sequence

@@ -46,6 +46,7 @@ const char* HELP_HEAD =
     "      --debug-cyp2d6-vcf           Also write cyp2d6_alleles.vcf.gz: the variants of the CYP2D6 regions, with the member reads that span (SR) and agree with (CR) each (needs --output-debug)\n"
     "      --debug-cyp2d6-alternatives  Also write cyp2d6_alternatives.json: the ten best CYP2D6 chain pairs with their scores, score components and coverage (needs --output-debug)\n"
     "      --debug-cyp2d6-alternative-reads  Also write cyp2d6_alternative_reads.json: those pairs read by read (which reads decide between them, which are unmet) and the observed-chain table (needs --output-debug)\n"
+    "      --debug-variant-alternatives Also write variant_alternatives.json: the ten best diplotypes of every variant gene with their scores and their missing and unexpected variants (needs --output-debug)\n"
     "      --debug-support-insertions   Those two files also list the inserted strings behind the columns their insertions contest (with one of the two switches above)\n"
     "      --debug-support-haplotypes   Those two files also list the read haplotypes: the patterns of calls the reads make at the contested columns (with one of the two switches above)\n"
     "      --sample-name <STRING>       Sample name from the input VCFs (default: first sample)\n"
@@ -105,6 +106,7 @@ const char* BATCH_HELP_TAIL =
     "      --debug-cyp2d6-vcf           Also write every sample's cyp2d6_alleles.vcf.gz (needs an output_debug column that names a folder)\n"
     "      --debug-cyp2d6-alternatives  Also write every sample's cyp2d6_alternatives.json (needs an output_debug column that names a folder)\n"
     "      --debug-cyp2d6-alternative-reads  Also write every sample's cyp2d6_alternative_reads.json (needs an output_debug column that names a folder)\n"
+    "      --debug-variant-alternatives Also write every sample's variant_alternatives.json (needs an output_debug column that names a folder)\n"
     "      --debug-support-insertions   Those two files also list the inserted strings behind the columns their insertions contest (with one of the two switches above)\n"
     "      --debug-support-haplotypes   Those two files also list the read haplotypes: the patterns of calls the reads make at the contested columns (with one of the two switches above)\n"
     "  -v, --verbose...                 Enable verbose output (print the warnings and the timings of the batch)\n"
@@ -156,7 +158,7 @@ bool parse_u64(const std::string& s, uint64_t* out) {
 struct Options {
     sp_diplotype_settings s;
     std::string database, reference, include, exclude;
-    int verbose = 0; bool debug_reads = false, debug_hla_mappings = false, debug_hla_ties = false, debug_consensus_support = false, debug_cyp2d6_support = false, debug_cyp2d6_vcf = false, debug_cyp2d6_alternatives = false, debug_cyp2d6_alternative_reads = false, debug_support_insertions = false, debug_support_haplotypes = false;
+    int verbose = 0; bool debug_reads = false, debug_hla_mappings = false, debug_hla_ties = false, debug_consensus_support = false, debug_cyp2d6_support = false, debug_cyp2d6_vcf = false, debug_cyp2d6_alternatives = false, debug_cyp2d6_alternative_reads = false, debug_variant_alternatives = false, debug_support_insertions = false, debug_support_haplotypes = false;
 };
 
 // the option being parsed: its name (a `--key=value` split) and where its value comes from.  need*: 0, or the exit status of the clap error
@@ -213,6 +215,7 @@ int parse_options(int argc, char** argv, const char* usage, const std::string& h
         else if (a == "--debug-cyp2d6-vcf") o.debug_cyp2d6_vcf = true;
         else if (a == "--debug-cyp2d6-alternatives") o.debug_cyp2d6_alternatives = true;
         else if (a == "--debug-cyp2d6-alternative-reads") o.debug_cyp2d6_alternative_reads = true;
+        else if (a == "--debug-variant-alternatives") o.debug_variant_alternatives = true;
         else if (a == "--debug-support-insertions") o.debug_support_insertions = true;
         else if (a == "--debug-support-haplotypes") o.debug_support_haplotypes = true;
         else if (a == "-v" || a == "--verbose") ++o.verbose;
@@ -261,6 +264,7 @@ sp_starphase* create_handle(const Options& o, int* code) {
     if (o.debug_cyp2d6_vcf) sp_starphase_set_cyp_vcf(h, 1);
     if (o.debug_cyp2d6_alternatives) sp_starphase_set_cyp_alternatives(h, 1);
     if (o.debug_cyp2d6_alternative_reads) sp_starphase_set_cyp_alternative_reads(h, 1);
+    if (o.debug_variant_alternatives) sp_starphase_set_variant_alternatives(h, 1);
     if (o.debug_support_insertions) sp_starphase_set_support_insertions(h, 1);
     if (o.debug_support_haplotypes) sp_starphase_set_support_haplotypes(h, 1);
     return h;
@@ -310,7 +314,7 @@ int batch_main(int argc, char** argv) {
         return NOT_MINE;
     });
     if (parsed != PARSED) return parsed;
-    const int verbose = o.verbose; const bool debug_reads = o.debug_reads, debug_hla_mappings = o.debug_hla_mappings, debug_hla_ties = o.debug_hla_ties, debug_consensus_support = o.debug_consensus_support, debug_cyp2d6_support = o.debug_cyp2d6_support, debug_cyp2d6_vcf = o.debug_cyp2d6_vcf, debug_cyp2d6_alternatives = o.debug_cyp2d6_alternatives, debug_cyp2d6_alternative_reads = o.debug_cyp2d6_alternative_reads;
+    const int verbose = o.verbose; const bool debug_reads = o.debug_reads, debug_hla_mappings = o.debug_hla_mappings, debug_hla_ties = o.debug_hla_ties, debug_consensus_support = o.debug_consensus_support, debug_cyp2d6_support = o.debug_cyp2d6_support, debug_cyp2d6_vcf = o.debug_cyp2d6_vcf, debug_cyp2d6_alternatives = o.debug_cyp2d6_alternatives, debug_cyp2d6_alternative_reads = o.debug_cyp2d6_alternative_reads, debug_variant_alternatives = o.debug_variant_alternatives;
     std::string missing;
     if (database.empty()) missing += "\n  --database <JSON>";
     if (reference.empty()) missing += "\n  --reference <FASTA>";
@@ -348,10 +352,10 @@ int batch_main(int argc, char** argv) {
         }
     }
     if (rows.empty()) { std::fprintf(stderr, "error: manifest \"%s\" lists no samples\n", manifest.c_str()); return EX_USAGE_; }
-    if (debug_reads || debug_hla_mappings || debug_hla_ties || debug_consensus_support || debug_cyp2d6_support || debug_cyp2d6_vcf || debug_cyp2d6_alternatives || debug_cyp2d6_alternative_reads) {
+    if (debug_reads || debug_hla_mappings || debug_hla_ties || debug_consensus_support || debug_cyp2d6_support || debug_cyp2d6_vcf || debug_cyp2d6_alternatives || debug_cyp2d6_alternative_reads || debug_variant_alternatives) {
         bool any = false;
         for (const Row& r : rows) any |= !r.debug.empty();
-        if (!any) { std::fprintf(stderr, "error: %s needs a debug folder: no manifest row names one (output_debug)\n", debug_reads ? "--debug-reads" : debug_hla_mappings ? "--debug-hla-mappings" : debug_hla_ties ? "--debug-hla-ties" : debug_consensus_support ? "--debug-consensus-support" : debug_cyp2d6_support ? "--debug-cyp2d6-support" : debug_cyp2d6_vcf ? "--debug-cyp2d6-vcf" : debug_cyp2d6_alternatives ? "--debug-cyp2d6-alternatives" : "--debug-cyp2d6-alternative-reads"); return EX_USAGE_; }
+        if (!any) { std::fprintf(stderr, "error: %s needs a debug folder: no manifest row names one (output_debug)\n", debug_reads ? "--debug-reads" : debug_hla_mappings ? "--debug-hla-mappings" : debug_hla_ties ? "--debug-hla-ties" : debug_consensus_support ? "--debug-consensus-support" : debug_cyp2d6_support ? "--debug-cyp2d6-support" : debug_cyp2d6_vcf ? "--debug-cyp2d6-vcf" : debug_cyp2d6_alternatives ? "--debug-cyp2d6-alternatives" : debug_cyp2d6_alternative_reads ? "--debug-cyp2d6-alternative-reads" : "--debug-variant-alternatives"); return EX_USAGE_; }
     }
     // every row through the checks of `diplotype`: the files (NOINPUT), then check_diplotype_settings (USAGE)
     std::vector<std::vector<const char*>> bam_ptrs(rows.size());
@@ -554,6 +558,7 @@ int main(int argc, char** argv) {
     if (o.debug_cyp2d6_vcf && debug.empty()) { std::fprintf(stderr, "error: --debug-cyp2d6-vcf needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
     if (o.debug_cyp2d6_alternatives && debug.empty()) { std::fprintf(stderr, "error: --debug-cyp2d6-alternatives needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
     if (o.debug_cyp2d6_alternative_reads && debug.empty()) { std::fprintf(stderr, "error: --debug-cyp2d6-alternative-reads needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
+    if (o.debug_variant_alternatives && debug.empty()) { std::fprintf(stderr, "error: --debug-variant-alternatives needs a debug folder (--output-debug <DIR>)\n"); return EX_USAGE_; }
     char err[512];
     if (sp_diplotype_settings_check(&s, &in, err, sizeof err) != SP_OK) {
         std::fprintf(stderr, "error: Error while processing CLI settings: %s\n", err);

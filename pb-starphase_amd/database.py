@@ -175,6 +175,7 @@ def _lib():
         "sp_starphase_set_cyp_vcf": (_i32, [_vp, _i32]),
         "sp_starphase_set_cyp_alternatives": (_i32, [_vp, _i32]),
         "sp_starphase_set_cyp_alternative_reads": (_i32, [_vp, _i32]),
+        "sp_starphase_set_variant_alternatives": (_i32, [_vp, _i32]),
         "sp_diplotype_settings_default": (None, [P(sp_diplotype_settings)]),
         "sp_diplotype_settings_check": (_i32, [P(sp_diplotype_settings), P(sp_sample_inputs), _s, _u32]),
         "sp_starphase_create": (_i32, [_vp, _s, _s, P(sp_diplotype_settings), P(_vp)]),
@@ -973,7 +974,7 @@ class Starphase:
     set_cyp_consensus_support() at once (it also writes cyp2d6_consensus_support.json); support_insertions=True: set_support_insertions() at once (those two files
     also list the inserted strings of the columns their insertions contest)."""
 
-    def __init__(self, database, reference=None, ctx=None, consensus_support=False, cyp_consensus_support=False, support_insertions=False, support_haplotypes=False, hla_ties=False, cyp_vcf=False, cyp_alternatives=False, cyp_alternative_reads=False, **settings):
+    def __init__(self, database, reference=None, ctx=None, consensus_support=False, cyp_consensus_support=False, support_insertions=False, support_haplotypes=False, hla_ties=False, cyp_vcf=False, cyp_alternatives=False, cyp_alternative_reads=False, variant_alternatives=False, **settings):
         self._h = _vp()
         self._s = _settings(**settings)
         rc = _lib().sp_starphase_create(ctx._h if ctx is not None else None, _b(database), _b(reference), C.byref(self._s), C.byref(self._h))
@@ -995,6 +996,8 @@ class Starphase:
             self.set_cyp_alternatives(True)
         if cyp_alternative_reads:
             self.set_cyp_alternative_reads(True)
+        if variant_alternatives:
+            self.set_variant_alternatives(True)
 
     def close(self):
         if self._h:
@@ -1045,6 +1048,14 @@ class Starphase:
         rc = _lib().sp_starphase_set_cyp_alternatives(self._h, 1 if on else 0)
         if rc != SP_OK:
             raise StarphaseError(rc, "sp_starphase_set_cyp_alternatives")
+        return self
+
+    def set_variant_alternatives(self, on=True):
+        """sp_starphase_set_variant_alternatives: a debug folder also receives variant_alternatives.json (per solved variant gene the ten best diplotypes, best first:
+        score, het combination, whether the call keeps it, and each haplotype's missing and unexpected variants); off by default"""
+        rc = _lib().sp_starphase_set_variant_alternatives(self._h, 1 if on else 0)
+        if rc != SP_OK:
+            raise StarphaseError(rc, "sp_starphase_set_variant_alternatives")
         return self
 
     def set_cyp_alternative_reads(self, on=True):

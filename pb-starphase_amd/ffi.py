@@ -163,6 +163,49 @@ class sp_variant_result(C.Structure):
                 ("dip_comb", C.c_int32 * SP_VAR_MAXDIP)]
 
 
+SP_VAR_ALT_CALLED, SP_VAR_ALT_SHADOWED, SP_VAR_ALTERNATIVES = 1, 2, 10
+
+
+class sp_variant_alt(C.Structure):
+    """one candidate (comb, dip0, dip1) of sp_variant_alternatives: total and per-side (core missing, core extra, sub missing, sub extra)"""
+    _fields_ = [("score", C.c_int64 * 4), ("side_score", (C.c_int32 * 4) * 2), ("dip", C.c_int32 * 2), ("comb", C.c_int32), ("flags", C.c_uint32)]
+
+
+class sp_variant_alt_info(C.Structure):
+    _fields_ = [("n_comb", C.c_uint64), ("n_candidates", C.c_uint64), ("best_score", C.c_int64 * 4), ("n_alts", C.c_uint32), ("n_called", C.c_uint32)]
+
+
+def variant_alt_relations(problem, comb, side, dip):
+    """sp_variant_alt_relations (host only): [(variant id, SP_REL_*)] of side `side` of het assignment comb under explanation dip -- the matching, then the
+    missing, then the unexpected variants"""
+    ids, rel, n = np.zeros(192, np.int32), np.zeros(192, np.int32), C.c_uint32(0)
+    rc = lib().sp_variant_alt_relations(C.byref(problem), int(comb), int(side), int(dip), ids.ctypes.data, rel.ctypes.data, len(ids), C.byref(n))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_variant_alt_relations")
+    return [(int(ids[k]), int(rel[k])) for k in range(n.value)]
+
+
+def variant_alternatives_json(problem, info, alts, hap_names, hap_core_names, sv_labels, var_names):
+    """sp_variant_alternatives_json (host only): the text of one gene's entry of variant_alternatives.json.  alts: the records of sp_variant_alternatives (a list or
+    a ctypes array, info.n_alts of them are read); the names as the header says"""
+    def strs(items):
+        arr = (C.c_char_p * max(1, len(items)))()
+        for i, x in enumerate(items):
+            arr[i] = x.encode() if isinstance(x, str) else x
+        return arr
+    recs = (sp_variant_alt * max(1, len(alts)))(*alts) if not isinstance(alts, C.Array) else alts
+    hn, hc, sl, vn = strs(hap_names), strs(hap_core_names), strs(sv_labels), strs(var_names)
+    need = C.c_uint64(0)
+    rc = lib().sp_variant_alternatives_json(C.byref(problem), C.byref(info), recs, hn, hc, sl, len(sv_labels), vn, None, 0, C.byref(need))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_variant_alternatives_json")
+    out = C.create_string_buffer(need.value)
+    rc = lib().sp_variant_alternatives_json(C.byref(problem), C.byref(info), recs, hn, hc, sl, len(sv_labels), vn, out, need.value, C.byref(need))
+    if rc != SP_OK:
+        raise StarphaseError(rc, "sp_variant_alternatives_json")
+    return out.value.decode()
+
+
 class sp_sv_definitions(C.Structure):
     _fields_ = [("n_genes", C.c_int32), ("gene_start", C.c_void_p), ("gene_end", C.c_void_p), ("gene_forward", C.c_void_p),
                 ("exon_off", C.c_void_p), ("exon_start", C.c_void_p), ("exon_end", C.c_void_p),
@@ -594,6 +637,11 @@ def lib():
         "sp_cyp_score_alleles": (i32, [vp, u32, u32, vp, vp, u32, vp, vp, vp, vp]),
         "sp_variant_solve": (i32, [vp, C.POINTER(sp_variant_problem), C.POINTER(sp_variant_result)]),
         "sp_variant_solve_batch": (i32, [vp, u32, C.POINTER(C.POINTER(sp_variant_problem)), C.POINTER(sp_variant_result), C.POINTER(i32)]),
+        "sp_variant_alternatives": (i32, [vp, C.POINTER(sp_variant_problem), u32, C.POINTER(sp_variant_alt), C.POINTER(sp_variant_alt_info)]),
+        "sp_variant_alternatives_batch": (i32, [vp, u32, C.POINTER(C.POINTER(sp_variant_problem)), u32, C.POINTER(sp_variant_alt), C.POINTER(sp_variant_alt_info), C.POINTER(i32)]),
+        "sp_variant_alt_relations": (i32, [C.POINTER(sp_variant_problem), i32, i32, i32, vp, vp, u32, C.POINTER(u32)]),
+        "sp_variant_alternatives_json": (i32, [C.POINTER(sp_variant_problem), C.POINTER(sp_variant_alt_info), C.POINTER(sp_variant_alt), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
+                                               C.POINTER(C.c_char_p), u32, C.POINTER(C.c_char_p), C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "sp_variant_is_deletion": (i32, [C.POINTER(sp_sv_definitions), u64, u64, C.POINTER(i32), C.POINTER(i32)]),
         "sp_hla_is_passing_dual": (i32, [u64, u64, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "sp_hla_is_hemizygous_better": (i32, [vp, vp, vp, u32, i32, u64, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -1138,6 +1186,29 @@ class Context:
         rcs = (C.c_int32 * max(1, n))()
         self.check(lib().sp_variant_solve_batch(self._h, n, ptrs, res, rcs))
         return [(tuple(res[i].score), [(res[i].dip[k][0], res[i].dip[k][1], res[i].dip_comb[k]) for k in range(res[i].n_dip)]) for i in range(n)]
+
+    def variant_alternatives(self, problem, n=10):
+        """sp_variant_alternatives: the n (1..64) best candidates (het assignment, explanation of side 0, of side 1) of an sp_variant_problem under
+        (total score, comb, dip0, dip1).  Returns (sp_variant_alt_info, [sp_variant_alt] of info.n_alts entries)"""
+        n = int(n)
+        alts = (sp_variant_alt * max(1, n))()
+        info = sp_variant_alt_info()
+        self.check(lib().sp_variant_alternatives(self._h, C.byref(problem), n, alts, C.byref(info)))
+        return info, [alts[k] for k in range(info.n_alts)]
+
+    def variant_alternatives_batch(self, problems, n=10, problem_rc=False):
+        """sp_variant_alternatives_batch: [(sp_variant_alt_info, [sp_variant_alt])] per problem, all in one launch pair.  problem_rc=True: a problem that fails its
+        checks does not raise; the call returns (list, [status per problem]) and the failing problem's entry has no records"""
+        n, k = int(n), len(problems)
+        ptrs = (C.POINTER(sp_variant_problem) * max(1, k))(*[C.pointer(p) for p in problems])
+        alts = (sp_variant_alt * max(1, k * n))()
+        infos = (sp_variant_alt_info * max(1, k))()
+        rcs = (C.c_int32 * max(1, k))()
+        rc = lib().sp_variant_alternatives_batch(self._h, k, ptrs, n, alts, infos, rcs)
+        if not problem_rc or (rc != SP_OK and all(rcs[i] == SP_OK for i in range(k))):
+            self.check(rc)
+        out = [(infos[i], [alts[i * n + r] for r in range(infos[i].n_alts)]) for i in range(k)]
+        return (out, [int(rcs[i]) for i in range(k)]) if problem_rc else out
 
     def consensus(self, reads, cfg, offsets=None, read_idx=None, cap=None, two_pass=False):
         """sp_consensus / sp_consensus_dual (two_pass) on a SeqSet -> dict like the oracle harness returns"""
